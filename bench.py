@@ -9,8 +9,15 @@ one process per GPU, no data-path collective (blocks/surfaces are independent:
 weak scaling); torch.distributed (RCCL) is used only for the barriers and the
 max-over-ranks of the elapsed time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the
+roofline of the kernel times taken in the timed loop.  Every other leg described below (cpu_baseline,
+valu_issue, vs_previous_round, tolerance, second_tile, end_to_end, the strong-scaling leg, C3's PMC
+replay, C5's re-encode check) runs only with `--full`.  `--dump-outputs DIR` writes what the timed
+path produced in its last step (rank 0's payload: one float32 row per block, one value per byte) to
+DIR/<name>.npy, with a seeded sample of blocks when the payload is larger than DUMP_BLOCKS blocks.
 
 Launched plainly with --gpus N > 1 (no WORLD_SIZE in the environment) the script starts its N
 ranks itself (re-exec under torch.distributed.run on 127.0.0.1); under a launcher it is one rank.
@@ -61,6 +68,7 @@ ROUND = 6                     # this build's round: vs_previous_round reads the 
                               # the round, once BENCH_r06.json exists, must not compare the build with itself)
 MIN_VS_PREVIOUS = 0.90        # regression gate: a headline below this share of the previous round's is flagged in the
                               # line (`regression_gate.ok`), fails tests/test_gpu_bench.py and, with BENCH_STRICT=1, the run
+DUMP_BLOCKS = 1 << 19         # --dump-outputs: at most this many 16-byte blocks, 32 MB as float32 (+ 4 MB of indices)
 
 
 def usable_cpus() -> int:
@@ -104,6 +112,24 @@ def _previous_round(metric, n_gpus, value):
         except (OSError, ValueError):
             pass
     return best
+
+
+def dump_payload(dirname, name, payload, block_bytes=16):
+    """--dump-outputs: a payload (uint8 device tensor) as DIR/<name>.npy, float32 of shape (blocks, block_bytes),
+    and the index of each row's block as DIR/<name>_block_index.npy (float64).  A payload of more than DUMP_BLOCKS
+    blocks is sampled: the same seeded choice of blocks, in payload order, for the same payload size."""
+    import numpy as np
+    import torch
+    blocks = payload.reshape(-1, block_bytes)
+    n = blocks.shape[0]
+    if n > DUMP_BLOCKS:
+        idx = np.sort(np.random.default_rng(0).choice(n, DUMP_BLOCKS, replace=False))
+        blocks = blocks[torch.from_numpy(idx).to(blocks.device)]
+    else:
+        idx = np.arange(n)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), blocks.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(dirname, name + "_block_index.npy"), idx.astype(np.float64))
 
 
 def _oracle_flags():
@@ -535,12 +561,16 @@ def run_c5(args, rank, local_rank, world, backend):
     torch.cuda.synchronize(); barrier(); torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kernel_ms, launches = ctx.profile_end()
+    if args.dump_outputs and rank == 0:
+        dump_payload(args.dump_outputs, "bc7_chains_payload", out)
     # encode-only time of this rank's share (no gather), for the per-rank load table
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    step(gather=False)
-    torch.cuda.synchronize()
-    local_ms = (time.perf_counter() - t1) * 1e3
+    local_ms = float("nan")
+    if args.full:
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        step(gather=False)
+        torch.cuda.synchronize()
+        local_ms = (time.perf_counter() - t1) * 1e3
     stats = torch.tensor([elapsed, local_ms, float(len(mine))], dtype=torch.float64,
                          device=dev if backend == "nccl" else "cpu")
     allstats = [stats.clone() for _ in range(world)]
@@ -549,32 +579,34 @@ def run_c5(args, rank, local_rank, world, backend):
     elapsed = max(float(s[0]) for s in allstats)
 
     if rank == 0:
-        # byte-equality of the batched / sharded result against a per-texture re-encode on rank 0
-        # (texture regenerated from its seed, mips regenerated, ONE texture per encode call): the
-        # first and last texture of rank 0's own share -- so the check is not vacuous at N = 1 --
-        # and, for N > 1, of rank 1's and the last rank's share as they arrived through the gather
-        check = {"textures_checked": [], "equal": True}
-        local_view = out if parts is None else parts[0]
-        todo = [(0, pos, local_view) for pos in sorted({0, len(plan[0]) - 1}) if plan[0]]
-        if world > 1 and parts is not None:
-            for r in sorted({1, world - 1}):
-                todo += [(r, pos, parts[r]) for pos in sorted({0, len(plan[r]) - 1}) if plan[r]]
-        for r, pos, buf in todo:
-            t = plan[r][pos]
-            b = [gpu_texture(torch, n, t, dev)]
-            c = [[torch.empty((d, d, 4), dtype=torch.float32, device=dev) for d in dims[1:]]]
-            o = torch.empty(chain_bytes, dtype=torch.uint8, device=dev)
-            # torch produced the texture on ITS stream; the library reads it on the stream it is given
-            # (torch's legacy default stream has handle 0 = "the context's own stream"): finish first
-            torch.cuda.synchronize()
-            ctx.generate_mips_device(b[0].data_ptr(), PixelType.RGBA8, n, n, n * 4,
-                                     [x.data_ptr() for x in c[0]], color_space=ColorSpace.Linear,
-                                     filter=0, stream=stream)
-            ctx.encode_device(surfaces(b, c, o), params, stream)
-            torch.cuda.synchronize()
-            same = bool(torch.equal(o, buf[pos * chain_bytes:(pos + 1) * chain_bytes]))
-            check["textures_checked"].append({"texture": t, "owner_rank": r, "equal": same})
-            check["equal"] = check["equal"] and same
+        check = None
+        if args.full:
+            # byte-equality of the batched / sharded result against a per-texture re-encode on rank 0
+            # (texture regenerated from its seed, mips regenerated, ONE texture per encode call): the
+            # first and last texture of rank 0's own share -- so the check is not vacuous at N = 1 --
+            # and, for N > 1, of rank 1's and the last rank's share as they arrived through the gather
+            check = {"textures_checked": [], "equal": True}
+            local_view = out if parts is None else parts[0]
+            todo = [(0, pos, local_view) for pos in sorted({0, len(plan[0]) - 1}) if plan[0]]
+            if world > 1 and parts is not None:
+                for r in sorted({1, world - 1}):
+                    todo += [(r, pos, parts[r]) for pos in sorted({0, len(plan[r]) - 1}) if plan[r]]
+            for r, pos, buf in todo:
+                t = plan[r][pos]
+                b = [gpu_texture(torch, n, t, dev)]
+                c = [[torch.empty((d, d, 4), dtype=torch.float32, device=dev) for d in dims[1:]]]
+                o = torch.empty(chain_bytes, dtype=torch.uint8, device=dev)
+                # torch produced the texture on ITS stream; the library reads it on the stream it is given
+                # (torch's legacy default stream has handle 0 = "the context's own stream"): finish first
+                torch.cuda.synchronize()
+                ctx.generate_mips_device(b[0].data_ptr(), PixelType.RGBA8, n, n, n * 4,
+                                         [x.data_ptr() for x in c[0]], color_space=ColorSpace.Linear,
+                                         filter=0, stream=stream)
+                ctx.encode_device(surfaces(b, c, o), params, stream)
+                torch.cuda.synchronize()
+                same = bool(torch.equal(o, buf[pos * chain_bytes:(pos + 1) * chain_bytes]))
+                check["textures_checked"].append({"texture": t, "owner_rank": r, "equal": same})
+                check["equal"] = check["equal"] and same
         pixels = float(T) * px_chain
         line = {
             "metric": "Mpixels/s encode, BC7 texture-array batch (256 x 2048x2048 RGBA8 mip chains)",
@@ -589,7 +621,8 @@ def run_c5(args, rank, local_rank, world, backend):
                        "format": FORMAT_NAME, "quality": args.quality, "textures": T,
                        "surfaces": T * levels, "blocks": T * blocks_chain,
                        "parallelism": "texture-sharded x%d" % world},
-            "per_rank": [{"rank": r, "textures": int(allstats[r][2]), "encode_ms": round(float(allstats[r][1]), 3),
+            "per_rank": [{"rank": r, "textures": int(allstats[r][2]),
+                          "encode_ms": round(float(allstats[r][1]), 3) if args.full else None,
                           "gather_bytes": sizes[r]} for r in range(world)],
             "kernel_ms_rank0": round(kernel_ms / max(args.steps, 1), 3),
             "sharded_equals_local": check,
@@ -609,7 +642,7 @@ def run_c5(args, rank, local_rank, world, backend):
                     "level (SURVEY 8d); the mip levels really travel as RGBA32F (16 B/px, the reference's RGBAF), "
                     "so the bytes the launches move are higher; VALU-issue-bound search (DESIGN.md section 4.1)"}
         line["cpu_baseline"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = c5_cpu_baseline(torch, bases, mine, out, geo, args.quality)
         print(json.dumps(line), flush=True)
     ctx.close()
@@ -741,6 +774,8 @@ def run_c3(args, rank, local_rank, world, backend):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kernel_ms, launches = ctx.profile_end()
+    if args.dump_outputs and rank == 0:
+        dump_payload(args.dump_outputs, "astc_6x6_payload", out)
     per_rank = [{"rank": 0, "kernel_ms": round(kernel_ms / max(launches, 1), 4)}]
     if world > 1:
         t = torch.tensor([elapsed, kernel_ms / max(launches, 1)], dtype=torch.float64,
@@ -769,28 +804,30 @@ def run_c3(args, rank, local_rank, world, backend):
                              "launches": launches, "algorithmic_bytes_per_launch": int(algo_bytes),
                              "note": "a VALU-issue-bound search: the HBM fraction is tiny by construction; what bounds the kernel "
                                      "is valu_busy (DESIGN.md 4.5)"}}
-        try:
-            pj = json.load(open(os.path.join(ROOT, "profiles", "astc_c3_pmc.json")))
-            line["roofline"]["traffic"] = pj.get("traffic_bytes_per_launch")
-            line["roofline"]["valu_busy"] = pj.get("valu_busy")
-            line["roofline"]["lds_bank_conflict_share"] = pj.get("lds_bank_conflict_share")
-            line["roofline"]["pmc_source"] = pj.get("source")
-            line["roofline"]["traffic_measured_in_this_run"] = False
-        except (OSError, ValueError):
-            pass
-        # north_star's 0.1 dB at C3's level: the same view as the headline's `tolerance` key, read from the same table
-        try:
-            js = json.load(open(os.path.join(ROOT, "profiles", "quality_real.json")))
-            gaps = {g: js["ASTC 6x6/%s" % g]["pooled_gap_nhh"] for g in ("a", "b")}
-            inside = [QNAMES[lv] for k, lv in enumerate((2, 3, 4)) if all(gaps[g][k] <= 0.1 for g in gaps)]
-            line["tolerance"] = {"target_db": 0.1, "bound": "cfo_astc_wide_search on blocks of real photographs "
-                                                             "(tests/golden/real_blocks.npz, groups a / b)",
-                                 "gap_db_normal_high_highest": gaps, "this_level_within_target": bool(QNAMES[q] in inside),
-                                 "lowest_level_within_target": inside[0] if inside else None,
-                                 "source": "profiles/quality_real.json (tools/quality_real.py)"}
-        except (OSError, KeyError, ValueError):
-            line["tolerance"] = None
-        if world == 1 and not args.no_cpu_baseline and size == SIZE:
+        line["tolerance"] = None
+        if args.full:
+            try:
+                pj = json.load(open(os.path.join(ROOT, "profiles", "astc_c3_pmc.json")))
+                line["roofline"]["traffic"] = pj.get("traffic_bytes_per_launch")
+                line["roofline"]["valu_busy"] = pj.get("valu_busy")
+                line["roofline"]["lds_bank_conflict_share"] = pj.get("lds_bank_conflict_share")
+                line["roofline"]["pmc_source"] = pj.get("source")
+                line["roofline"]["traffic_measured_in_this_run"] = False
+            except (OSError, ValueError):
+                pass
+            # north_star's 0.1 dB at C3's level: the same view as the headline's `tolerance` key, read from the same table
+            try:
+                js = json.load(open(os.path.join(ROOT, "profiles", "quality_real.json")))
+                gaps = {g: js["ASTC 6x6/%s" % g]["pooled_gap_nhh"] for g in ("a", "b")}
+                inside = [QNAMES[lv] for k, lv in enumerate((2, 3, 4)) if all(gaps[g][k] <= 0.1 for g in gaps)]
+                line["tolerance"] = {"target_db": 0.1, "bound": "cfo_astc_wide_search on blocks of real photographs "
+                                                                 "(tests/golden/real_blocks.npz, groups a / b)",
+                                     "gap_db_normal_high_highest": gaps, "this_level_within_target": bool(QNAMES[q] in inside),
+                                     "lowest_level_within_target": inside[0] if inside else None,
+                                     "source": "profiles/quality_real.json (tools/quality_real.py)"}
+            except (OSError, KeyError, ValueError):
+                line["tolerance"] = None
+        if args.full and world == 1 and not args.no_cpu_baseline and size == SIZE:
             sys.path.insert(0, os.path.join(ROOT, "tests"))
             import oracle_lib as O
             cores = usable_cpus()
@@ -850,6 +887,8 @@ def run_c2(args, rank, local_rank, world, backend):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kernel_ms, launches = ctx.profile_end()
+    if args.dump_outputs and rank == 0:
+        dump_payload(args.dump_outputs, "bc7_payload", out)
 
     per_rank = [{"rank": 0, "kernel_ms": round(kernel_ms / max(launches, 1), 4)}]
     strong = None
@@ -896,7 +935,8 @@ def run_c2(args, rank, local_rank, world, backend):
             os._exit(3 if os.environ.get("BENCH_STRONG_STRICT", "0") == "1" else 0)   # the watchdog printed while the leg was finishing
         return res
 
-    if rank != 0 and world > 1 and not args.no_strong:
+    run_strong = args.full and world > 1 and not args.no_strong
+    if rank != 0 and run_strong:
         guarded_strong(None)
     if rank == 0:
         pixels_per_step = float(size * size) * world
@@ -925,7 +965,7 @@ def run_c2(args, rank, local_rank, world, backend):
                          "note": "VALU-issue-bound search (see valu_issue); the HBM fraction is "
                                  "tiny by construction (DESIGN.md roofline section)"},
         }
-        if size == SIZE:
+        if args.full and size == SIZE:
             ksub = "cfhip_bc7_encode_kernelILi0ELb1ELb%dE" % (1 if args.quality >= 3 else 0)
             view, traffic, source = valu_issue_view(ksub, avg_kernel_s, args.quality)
             line["roofline"]["valu_issue"] = view
@@ -935,26 +975,27 @@ def run_c2(args, rank, local_rank, world, backend):
             # PMC passes cannot run inside the timed region: traffic and the dynamic instruction
             # counts are REPLAYED from the committed profile of the same code hash, never measured here
             line["roofline"]["traffic_measured_in_this_run"] = False
-        if world == 1 and not args.no_cpu_baseline and size == SIZE:
+        if args.full and world == 1 and not args.no_cpu_baseline and size == SIZE:
             payload = out.cpu().numpy()
             line["cpu_baseline"] = cpu_baseline(img, payload, size, args.quality)
         else:
             line["cpu_baseline"] = None
-        if size == SIZE:
+        if args.full and size == SIZE:
             line["vs_previous_round"] = _previous_round(line["metric"], world, value)
             if line["vs_previous_round"] and args.quality == 2:
                 line["regression_gate"] = {"min_ratio": MIN_VS_PREVIOUS, "ok": line["vs_previous_round"]["ratio"] >= MIN_VS_PREVIOUS}
         # (the headline level's payload, taken before the tolerance leg encodes another level into the same buffer)
-        device_payload = out.cpu().numpy() if (world == 1 and not args.no_end_to_end) else None
-        if world == 1 and size == SIZE and args.quality == 2 and not args.no_tolerance:
+        run_end_to_end = args.full and world == 1 and not args.no_end_to_end
+        device_payload = out.cpu().numpy() if run_end_to_end else None
+        if args.full and world == 1 and size == SIZE and args.quality == 2 and not args.no_tolerance:
             line["tolerance"] = tolerance_view(ctx, torch, surf, size, stream, value)
-        if world == 1 and size == SIZE and not args.no_second_tile:
+        if args.full and world == 1 and size == SIZE and not args.no_second_tile:
             line["second_tile"] = second_tile(ctx, torch, size, params, max(3, args.steps // 2), stream, not args.no_cpu_baseline)
             line["second_tile"]["vs_headline_tile"] = round(line["second_tile"]["kernel_ms"] / (avg_kernel_s * 1e3), 3)
-        if world == 1 and not args.no_end_to_end:
+        if run_end_to_end:
             torch.cuda.synchronize()
             line["end_to_end"] = end_to_end(ctx, img, params, device_payload, avg_kernel_s * 1e3)
-        if world > 1 and not args.no_strong:
+        if run_strong:
             strong = guarded_strong(line)
         if strong is not None:
             line["strong_scaling"] = strong
@@ -986,6 +1027,13 @@ def main():
     ap.add_argument("--no-second-tile", action="store_true",
                     help="c2, N = 1: skip the camera-like second tile (profile passes: the kernel statistics and PMC "
                          "averages of the run must be the headline tile's alone)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline (cpu_baseline, valu_issue, vs_previous_round, "
+                         "tolerance, second_tile, end_to_end, strong_scaling; c3: PMC replay and tolerance; c5: the "
+                         "re-encode check and per-rank encode times); the --no-* options skip legs of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's payload of the last step to DIR/<name>.npy (float32, "
+                         "a seeded sample of %d blocks when larger)" % DUMP_BLOCKS)
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 20 if args.config == "c2" else (8 if args.config == "c3" else 3)
