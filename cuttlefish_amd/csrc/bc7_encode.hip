@@ -342,12 +342,28 @@ __device__ __forceinline__ uint32_t ycc_pp_sum(const Tex& tx, uint32_t mask, con
 #define CF_BC7_ABLATE 0
 #endif
 
+// Diagnostic counters (never set in the product build): per wave pass, how often the starts trip reads the
+// fit-geometry cache and how often the starts trip / the perturbation pass have only fits of <= 4 palette entries.
+// Read by cfhip_bc7_diag() below.
+#ifndef CF_BC7_DIAG
+#define CF_BC7_DIAG 0
+#endif
+#if CF_BC7_DIAG
+enum { CF_DIAG_STARTS, CF_DIAG_STARTS_CACHED, CF_DIAG_STARTS_NARROW, CF_DIAG_PERTURB, CF_DIAG_PERTURB_NARROW, CF_DIAG_N };
+__device__ unsigned long long cf_bc7_diag[CF_DIAG_N];
+#define CF_DIAG_COUNT(i, cond) do { uint32_t l_; CF_FRESH_LANE(l_); if (l_ == 0u && (cond)) atomicAdd(&cf_bc7_diag[i], 1ull); } while (0)
+#else
+#define CF_DIAG_COUNT(i, cond) do { } while (0)
+#endif
+
 struct LaneFit {
 	uint32_t q0, q1, pb, err;   // (the dequantised endpoints are an input of the assignment, not part of a result)
 	uint32_t w[4];          // weights per texel (bytes), 0 outside the subset
 };
 
-template <bool UNITW>
+// NK: palette entries walked per lane -- 8, or 4 when no lane of the wave has more than 4 (index width 2, not mode 6):
+// entries 4..7 then carry the never-winning key and dropping them changes no maximum.
+template <bool UNITW, int NK = 8>
 __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bool m6,
 	uint32_t khalf, uint32_t ib, const uint32_t (&yw)[2], uint32_t pp_sum, bool want_lsq, uint32_t fe0, uint32_t fe1,
 	LaneFit& f, float (&nx0)[4], float (&nx1)[4], float (&hq)[3], bool& ok)
@@ -363,7 +379,7 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 	uint32_t pal[8], palh[8];
 	int base[8];
 #pragma unroll
-	for (int k = 0; k < 8; ++k) {
+	for (int k = 0; k < NK; ++k) {
 		const bool valid = (uint32_t)k < nk;
 		// an entry past 2^ib interpolates with weight 0: its colour stays a byte vector, so the
 		// dot products below stay in range and its constant keeps it from ever winning
@@ -421,7 +437,7 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 				int bestk = -0x7FFFFFFF;
 				const uint32_t prg = rawj, pba = rawh[j];
 #pragma unroll
-				for (int k = 0; k < 8; ++k) {
+				for (int k = 0; k < NK; ++k) {
 					int dt;
 					if (UNITW)
 						dt = (int)__builtin_amdgcn_udot4(p, pal[k], 0u, false);
@@ -548,104 +564,163 @@ __device__ __forceinline__ void refit_window(const float (&xu0)[4], const float 
 	f.q0 = nq0; f.q1 = nq1; f.e0 = ne0; f.e1 = ne1;
 }
 
+// Fit-geometry cache (field-major like the candidate words, one column per thread): what parts A and B of
+// fit_lane derive from the texels alone -- axis, mean, the raw projection extremes (before `frac`), the
+// extremes of the rotated alpha and the constant pp_sum.  A stream-trip lane writes its fit's words; the
+// starts trip, whose four starts of a fit differ only in `frac`, reads them from the lane that fitted the
+// same (candidate, fit) in the stream trip.  Word 12 tags the column with that fit (id * 4 + fit index;
+// mode 6: fit 0) -- the tag is what says the column still holds it.
+#define CF_BC7_GEO_WORDS 13
+#define CF_BC7_GEO_NONE 0xFFFFFFFFu
+__device__ __forceinline__ uint32_t geo_tag(uint32_t id, uint32_t fi) { return id*4u + (id == 0u ? 0u : fi); }
+
+// Lane that ran fit fi of the candidate whose leader (first-fit lane) is wl, in the stream trips' layouts
+// (a guess checked by the tag: a wrong one only costs the fall-back to the full fit).
+__device__ __forceinline__ uint32_t geo_src(uint32_t id, uint32_t fi, uint32_t wl, bool lay32)
+{
+	uint32_t s = wl + fi;                                          // partitions: the subsets in consecutive lanes
+	if (id == 0u) s = wl;                                          // mode 6: both palette halves fit the same geometry
+	else if (id < 13u) s = fi ? wl + (lay32 ? (id < 5u ? 4u : 1u) : 12u) : wl;   // modes 5 / 4: scalar plane s2off lanes up
+	else if (lay32 && id >= 192u && id < 320u && fi == 2u)        // 32-lane second pass: subset 2 of slot s in lane s
+		s = (wl & 32u) + (((wl & 31u) - 11u) >> 1);
+	return s & 63u;
+}
+
 // scalar: the fit codes only the rotated alpha channel (modes 4/5 second plane); its start
 // endpoints are the exact extremes of that channel (oracle: fit_scalar).
 // frac: where the fit starts -- the extremes along the axis pulled in (positive) or pushed out by this
 // fraction of their distance (oracle: fitopt.start, cfo_start_frac; 0 = the extremes themselves).
-template <bool UNITW>
+// gmode (wave-uniform): 0 computes parts A and B, 1 computes them and writes them to the lane's own column of
+// the geometry cache gbase, 2 reads them from column gsrc instead.  NK: palette entries of the selector search
+// (assign_lsq_lane).
+template <bool UNITW, int NK = 8>
 __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, uint32_t khalf,
 	uint32_t cb, uint32_t ab, uint32_t pbk, uint32_t ib, uint32_t iters, const uint32_t (&wt)[4],
-	const uint32_t (&yw)[2], bool scalar, float frac, LaneFit& best)
+	const uint32_t (&yw)[2], bool scalar, float frac, uint32_t* gbase, uint32_t gmode, uint32_t gsrc, LaneFit& best)
 {
-	// A: statistics of the subset + extremes of the (rotated) alpha channel
-	const uint32_t n = (uint32_t)__builtin_popcount(mask);
-	uint32_t s[4] = {0, 0, 0, 0};
-	uint32_t q00 = 0, q01 = 0, q02 = 0, q03 = 0, q11 = 0, q12 = 0, q13 = 0, q22 = 0, q23 = 0,
-		q33 = 0;
-	uint32_t lo = 255u, hi = 0u;
-#pragma unroll 1
-	for (uint32_t r = 0; r < 4u; ++r) {
-		uint32_t P[4];
-		const uint4 pr = *reinterpret_cast<const uint4*>(tx.pl() + 4u*r);
-		planes<true>(tx, pr, P);
-		const uint32_t a4 = tx.rot == 0u ? pr.w : (tx.rot == 1u ? pr.x : (tx.rot == 2u ? pr.y : pr.z));
+	float axis[4], mean[4];
+	float tmin, tmax;
+	uint32_t lo, hi, pp_sum;
+	if (gmode == 2u) {
+		const uint32_t* gc = gbase + gsrc;
 #pragma unroll
-		for (int j = 0; j < 4; ++j) {
-			const uint32_t a = (a4 >> (8*j)) & 255u;
-			lo = a < lo ? a : lo;
-			hi = a > hi ? a : hi;
+		for (int c = 0; c < 4; ++c) {
+			axis[c] = __uint_as_float(gc[c*CF_WG_THREADS]);
+			mean[c] = __uint_as_float(gc[(4 + c)*CF_WG_THREADS]);
 		}
-		const uint32_t m4 = bytemask4((mask >> (4u*r)) & 15u);
-		const uint32_t M0 = P[0] & m4, M1 = P[1] & m4, M2 = P[2] & m4, M3 = P[3] & m4;
-		s[0] = __builtin_amdgcn_udot4(M0, 0x01010101u, s[0], false);
-		s[1] = __builtin_amdgcn_udot4(M1, 0x01010101u, s[1], false);
-		s[2] = __builtin_amdgcn_udot4(M2, 0x01010101u, s[2], false);
-		s[3] = __builtin_amdgcn_udot4(M3, 0x01010101u, s[3], false);
-		q00 = __builtin_amdgcn_udot4(M0, P[0], q00, false);
-		q01 = __builtin_amdgcn_udot4(M0, P[1], q01, false);
-		q02 = __builtin_amdgcn_udot4(M0, P[2], q02, false);
-		q03 = __builtin_amdgcn_udot4(M0, P[3], q03, false);
-		q11 = __builtin_amdgcn_udot4(M1, P[1], q11, false);
-		q12 = __builtin_amdgcn_udot4(M1, P[2], q12, false);
-		q13 = __builtin_amdgcn_udot4(M1, P[3], q13, false);
-		q22 = __builtin_amdgcn_udot4(M2, P[2], q22, false);
-		q23 = __builtin_amdgcn_udot4(M2, P[3], q23, false);
-		q33 = __builtin_amdgcn_udot4(M3, P[3], q33, false);
-	}
-	const float C00 = (float)(int)(__umul24(n, q00) - __umul24(s[0], s[0])), C01 = (float)(int)(__umul24(n, q01) - __umul24(s[0], s[1]));
-	const float C02 = (float)(int)(__umul24(n, q02) - __umul24(s[0], s[2])), C03 = (float)(int)(__umul24(n, q03) - __umul24(s[0], s[3]));
-	const float C11 = (float)(int)(__umul24(n, q11) - __umul24(s[1], s[1])), C12 = (float)(int)(__umul24(n, q12) - __umul24(s[1], s[2]));
-	const float C13 = (float)(int)(__umul24(n, q13) - __umul24(s[1], s[3])), C22 = (float)(int)(__umul24(n, q22) - __umul24(s[2], s[2]));
-	const float C23 = (float)(int)(__umul24(n, q23) - __umul24(s[2], s[3])), C33 = (float)(int)(__umul24(n, q33) - __umul24(s[3], s[3]));
-
-	float bestd = C00;
-	float v0 = C00, v1 = C01, v2 = C02, v3 = C03;
-	if (C11 > bestd) { bestd = C11; v0 = C01; v1 = C11; v2 = C12; v3 = C13; }
-	if (C22 > bestd) { bestd = C22; v0 = C02; v1 = C12; v2 = C22; v3 = C23; }
-	if (C33 > bestd) { bestd = C33; v0 = C03; v1 = C13; v2 = C23; v3 = C33; }
-#pragma unroll
-	for (int it = 0; it < 3; ++it) {
-		float r0 = C00*v0; r0 = fmaf(C01, v1, r0); r0 = fmaf(C02, v2, r0); r0 = fmaf(C03, v3, r0);
-		float r1 = C01*v0; r1 = fmaf(C11, v1, r1); r1 = fmaf(C12, v2, r1); r1 = fmaf(C13, v3, r1);
-		float r2 = C02*v0; r2 = fmaf(C12, v1, r2); r2 = fmaf(C22, v2, r2); r2 = fmaf(C23, v3, r2);
-		float r3 = C03*v0; r3 = fmaf(C13, v1, r3); r3 = fmaf(C23, v2, r3); r3 = fmaf(C33, v3, r3);
-		v0 = r0; v1 = r1; v2 = r2; v3 = r3;
-	}
-	const float mx = fmaxf(fmaxf(fabsf(v0), fabsf(v1)), fmaxf(fabsf(v2), fabsf(v3)));
-	float axis[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-	if (mx > 0.0f) {
-		const float im = 1.0f/mx;
-		v0 = v0*im; v1 = v1*im; v2 = v2*im; v3 = v3*im;
-		float l2 = v0*v0;
-		l2 = fmaf(v1, v1, l2);
-		l2 = fmaf(v2, v2, l2);
-		l2 = fmaf(v3, v3, l2);
-		const float is = 1.0f/sqrtf(l2);
-		axis[0] = v0*is; axis[1] = v1*is; axis[2] = v2*is; axis[3] = v3*is;
-	}
-
-	// B: extremes of the projection on the axis
-	const float in = 1.0f/(float)n;
-	float mean[4];
-#pragma unroll
-	for (int c = 0; c < 4; ++c)
-		mean[c] = (float)s[c]*in;
-	float tmin = 3.0e38f, tmax = -3.0e38f;
+		tmin = __uint_as_float(gc[8*CF_WG_THREADS]);
+		tmax = __uint_as_float(gc[9*CF_WG_THREADS]);
+		const uint32_t lh = gc[10*CF_WG_THREADS];
+		lo = lh & 255u; hi = lh >> 8;
+		pp_sum = gc[11*CF_WG_THREADS];
+	} else {
+		// A: statistics of the subset + extremes of the (rotated) alpha channel
+		const uint32_t n = (uint32_t)__builtin_popcount(mask);
+		uint32_t s[4] = {0, 0, 0, 0};
+		uint32_t q00 = 0, q01 = 0, q02 = 0, q03 = 0, q11 = 0, q12 = 0, q13 = 0, q22 = 0, q23 = 0,
+			q33 = 0;
+		lo = 255u; hi = 0u;
 #pragma unroll 1
-	for (uint32_t r = 0; r < 4u; ++r) {
-		const uint4 rw = *reinterpret_cast<const uint4*>(tx.tp() + 4u*r);
-		const uint32_t raw[4] = {rw.x, rw.y, rw.z, rw.w};
-		const uint32_t mrow = (mask >> (4u*r)) & 15u;
+		for (uint32_t r = 0; r < 4u; ++r) {
+			uint32_t P[4];
+			const uint4 pr = *reinterpret_cast<const uint4*>(tx.pl() + 4u*r);
+			planes<true>(tx, pr, P);
+			const uint32_t a4 = tx.rot == 0u ? pr.w : (tx.rot == 1u ? pr.x : (tx.rot == 2u ? pr.y : pr.z));
 #pragma unroll
-		for (int j = 0; j < 4; ++j) {
-			const uint32_t p = texel<true>(tx, raw[j]);
-			const bool m = (mrow >> j) & 1u;
-			float t = axis[0]*(fb(p, 0) - mean[0]);
-			t = fmaf(axis[1], fb(p, 1) - mean[1], t);
-			t = fmaf(axis[2], fb(p, 2) - mean[2], t);
-			t = fmaf(axis[3], fb(p, 3) - mean[3], t);
-			tmin = m ? fminf(tmin, t) : tmin;
-			tmax = m ? fmaxf(tmax, t) : tmax;
+			for (int j = 0; j < 4; ++j) {
+				const uint32_t a = (a4 >> (8*j)) & 255u;
+				lo = a < lo ? a : lo;
+				hi = a > hi ? a : hi;
+			}
+			const uint32_t m4 = bytemask4((mask >> (4u*r)) & 15u);
+			const uint32_t M0 = P[0] & m4, M1 = P[1] & m4, M2 = P[2] & m4, M3 = P[3] & m4;
+			s[0] = __builtin_amdgcn_udot4(M0, 0x01010101u, s[0], false);
+			s[1] = __builtin_amdgcn_udot4(M1, 0x01010101u, s[1], false);
+			s[2] = __builtin_amdgcn_udot4(M2, 0x01010101u, s[2], false);
+			s[3] = __builtin_amdgcn_udot4(M3, 0x01010101u, s[3], false);
+			q00 = __builtin_amdgcn_udot4(M0, P[0], q00, false);
+			q01 = __builtin_amdgcn_udot4(M0, P[1], q01, false);
+			q02 = __builtin_amdgcn_udot4(M0, P[2], q02, false);
+			q03 = __builtin_amdgcn_udot4(M0, P[3], q03, false);
+			q11 = __builtin_amdgcn_udot4(M1, P[1], q11, false);
+			q12 = __builtin_amdgcn_udot4(M1, P[2], q12, false);
+			q13 = __builtin_amdgcn_udot4(M1, P[3], q13, false);
+			q22 = __builtin_amdgcn_udot4(M2, P[2], q22, false);
+			q23 = __builtin_amdgcn_udot4(M2, P[3], q23, false);
+			q33 = __builtin_amdgcn_udot4(M3, P[3], q33, false);
+		}
+		const float C00 = (float)(int)(__umul24(n, q00) - __umul24(s[0], s[0])), C01 = (float)(int)(__umul24(n, q01) - __umul24(s[0], s[1]));
+		const float C02 = (float)(int)(__umul24(n, q02) - __umul24(s[0], s[2])), C03 = (float)(int)(__umul24(n, q03) - __umul24(s[0], s[3]));
+		const float C11 = (float)(int)(__umul24(n, q11) - __umul24(s[1], s[1])), C12 = (float)(int)(__umul24(n, q12) - __umul24(s[1], s[2]));
+		const float C13 = (float)(int)(__umul24(n, q13) - __umul24(s[1], s[3])), C22 = (float)(int)(__umul24(n, q22) - __umul24(s[2], s[2]));
+		const float C23 = (float)(int)(__umul24(n, q23) - __umul24(s[2], s[3])), C33 = (float)(int)(__umul24(n, q33) - __umul24(s[3], s[3]));
+
+		float bestd = C00;
+		float v0 = C00, v1 = C01, v2 = C02, v3 = C03;
+		if (C11 > bestd) { bestd = C11; v0 = C01; v1 = C11; v2 = C12; v3 = C13; }
+		if (C22 > bestd) { bestd = C22; v0 = C02; v1 = C12; v2 = C22; v3 = C23; }
+		if (C33 > bestd) { bestd = C33; v0 = C03; v1 = C13; v2 = C23; v3 = C33; }
+#pragma unroll
+		for (int it = 0; it < 3; ++it) {
+			float r0 = C00*v0; r0 = fmaf(C01, v1, r0); r0 = fmaf(C02, v2, r0); r0 = fmaf(C03, v3, r0);
+			float r1 = C01*v0; r1 = fmaf(C11, v1, r1); r1 = fmaf(C12, v2, r1); r1 = fmaf(C13, v3, r1);
+			float r2 = C02*v0; r2 = fmaf(C12, v1, r2); r2 = fmaf(C22, v2, r2); r2 = fmaf(C23, v3, r2);
+			float r3 = C03*v0; r3 = fmaf(C13, v1, r3); r3 = fmaf(C23, v2, r3); r3 = fmaf(C33, v3, r3);
+			v0 = r0; v1 = r1; v2 = r2; v3 = r3;
+		}
+		const float mx = fmaxf(fmaxf(fabsf(v0), fabsf(v1)), fmaxf(fabsf(v2), fabsf(v3)));
+#pragma unroll
+		for (int c = 0; c < 4; ++c) axis[c] = 0.0f;
+		if (mx > 0.0f) {
+			const float im = 1.0f/mx;
+			v0 = v0*im; v1 = v1*im; v2 = v2*im; v3 = v3*im;
+			float l2 = v0*v0;
+			l2 = fmaf(v1, v1, l2);
+			l2 = fmaf(v2, v2, l2);
+			l2 = fmaf(v3, v3, l2);
+			const float is = 1.0f/sqrtf(l2);
+			axis[0] = v0*is; axis[1] = v1*is; axis[2] = v2*is; axis[3] = v3*is;
+		}
+
+		// B: extremes of the projection on the axis
+		const float in = 1.0f/(float)n;
+#pragma unroll
+		for (int c = 0; c < 4; ++c)
+			mean[c] = (float)s[c]*in;
+		tmin = 3.0e38f; tmax = -3.0e38f;
+#pragma unroll 1
+		for (uint32_t r = 0; r < 4u; ++r) {
+			const uint4 rw = *reinterpret_cast<const uint4*>(tx.tp() + 4u*r);
+			const uint32_t raw[4] = {rw.x, rw.y, rw.z, rw.w};
+			const uint32_t mrow = (mask >> (4u*r)) & 15u;
+#pragma unroll
+			for (int j = 0; j < 4; ++j) {
+				const uint32_t p = texel<true>(tx, raw[j]);
+				const bool m = (mrow >> j) & 1u;
+				float t = axis[0]*(fb(p, 0) - mean[0]);
+				t = fmaf(axis[1], fb(p, 1) - mean[1], t);
+				t = fmaf(axis[2], fb(p, 2) - mean[2], t);
+				t = fmaf(axis[3], fb(p, 3) - mean[3], t);
+				tmin = m ? fminf(tmin, t) : tmin;
+				tmax = m ? fmaxf(tmax, t) : tmax;
+			}
+		}
+		// sum over the subset of sum_c p_c^2 (channels that are not coded have p = 0), or of the
+		// weighted squares on the perceptual axes
+		pp_sum = UNITW ? q00 + q11 + q22 + q33 : ycc_pp_sum(tx, mask, yw);
+		if (gmode == 1u) {
+			uint32_t lane;
+			CF_FRESH_LANE(lane);
+			uint32_t* gc = gbase + lane;
+#pragma unroll
+			for (int c = 0; c < 4; ++c) {
+				gc[c*CF_WG_THREADS] = __float_as_uint(axis[c]);
+				gc[(4 + c)*CF_WG_THREADS] = __float_as_uint(mean[c]);
+			}
+			gc[8*CF_WG_THREADS] = __float_as_uint(tmin);
+			gc[9*CF_WG_THREADS] = __float_as_uint(tmax);
+			gc[10*CF_WG_THREADS] = lo | (hi << 8);
+			gc[11*CF_WG_THREADS] = pp_sum;
 		}
 	}
 	{
@@ -681,11 +756,8 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 	quantize<UNITW>(x0, x1, G_CB, G_AB, G_PBK, wt, q);
 	best.q0 = q.q0; best.q1 = q.q1; best.pb = q.pb;
 	bool live;
-	// sum over the subset of sum_c p_c^2 (channels that are not coded have p = 0), or of the
-	// weighted squares on the perceptual axes
-	const uint32_t pp_sum = UNITW ? q00 + q11 + q22 + q33 : ycc_pp_sum(tx, mask, yw);
 	float hq[3];
-	assign_lsq_lane<UNITW>(tx, mask, m6, khalf, G_IB, yw, pp_sum, iters > 0u, q.e0, q.e1, best, x0, x1, hq, live);
+	assign_lsq_lane<UNITW, NK>(tx, mask, m6, khalf, G_IB, yw, pp_sum, iters > 0u, q.e0, q.e1, best, x0, x1, hq, live);
 	for (uint32_t r = 0; r < iters; ++r) {
 		LaneFit cur;
 		bool ok;
@@ -702,7 +774,7 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 		}
 		if (!(CF_BC7_ABLATE & 8)) refit_window(x0, x1, hq, G_CB, G_AB, G_PBK, q);
 		cur.q0 = q.q0; cur.q1 = q.q1; cur.pb = q.pb;
-		assign_lsq_lane<UNITW>(tx, mask, m6, khalf, G_IB, yw, pp_sum, r + 1u < iters, q.e0, q.e1, cur, x0, x1, hq, ok);
+		assign_lsq_lane<UNITW, NK>(tx, mask, m6, khalf, G_IB, yw, pp_sum, r + 1u < iters, q.e0, q.e1, cur, x0, x1, hq, ok);
 		const bool better = live && cur.err < best.err;
 		if (better)
 			best = cur;
@@ -1017,7 +1089,7 @@ __device__ __forceinline__ void column_put_fit(uint32_t* wc, const FitGeo& g, ui
 // (colour mask already applied), identical for every lane.
 template <bool UNITW, bool WIDE>
 __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint32_t* plan, const uint32_t* yccp, uint32_t b,
-	bool pair, uint32_t* cbase, const cf_kparams& kp)
+	bool pair, uint32_t* cbase, uint32_t* gbase, const cf_kparams& kp)
 {
 	uint32_t lane;
 	CF_FRESH_LANE(lane);
@@ -1216,6 +1288,8 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			bool active = m6;
 			float frac = frac_main;
 			uint32_t chm_s = 0;
+			uint32_t gmode = 1u, gsrc = 0u;   // stream trips write the fit-geometry cache, the starts trip reads it
+			bool narrow = false;              // starts trip: no active lane's fit has more than 4 palette entries
 			if (sst) {
 				// lane = (top candidate k, start variant v, fit): 8 lanes per candidate in the 32-lane layouts
 				// (k = hl >> 3, v = (hl >> 1) & 3, fit = hl & 1 -- mode 6: its two palette halves), 16 in the wide
@@ -1237,6 +1311,15 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				active = L_SLOT_OK && k < ntop && cerr != 0xFFFFFFFFu && err0 != 0u && (g.m6 ? fi < 2u : fi < g.nfits);
 				// starts 0, 2, 3, 4 of the oracle: the extremes, pushed out by 1/16, pulled in by 1/8, by 3/16
 				frac = v == 0u ? 0.0f : (v == 1u ? -1.0f/16.0f : (v == 2u ? 1.0f/8.0f : 3.0f/16.0f));
+				// parts A and B of the fit come from the cache when every active lane of the wave finds its fit there
+				// (in its own block's half); otherwise the whole wave computes them
+				gsrc = geo_src(id, fi, wl, lay32);
+				const bool ghit = gbase[gsrc + 12*CF_WG_THREADS] == geo_tag(id, fi) && (!lay32 || ((gsrc ^ wl) & 32u) == 0u);
+				gmode = __ballot(active && !ghit) == 0ull ? 2u : 0u;
+				narrow = __ballot(active && (g.m6 || g.ib > 2u)) == 0ull;
+				CF_DIAG_COUNT(CF_DIAG_STARTS, true);
+				CF_DIAG_COUNT(CF_DIAG_STARTS_CACHED, gmode == 2u);
+				CF_DIAG_COUNT(CF_DIAG_STARTS_NARROW, narrow);
 			} else if (vecp || sca) {
 				if (cid <= 4u) {
 					rot = cid - 1u; pbk = 0; ib = 2;
@@ -1294,9 +1377,14 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			// perceptual weight pairs of this fit: zero on the axes it does not code
 			const uint32_t yw[2] = {(chm & 7u) ? ywrg : 0u,
 				((chm & 7u) ? (ywba & 0xFFFFu) : 0u) | ((chm & 8u) ? (ywba & 0xFFFF0000u) : 0u)};
-			if (active)
-				fit_lane<UNITW>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib, iters,
-					wv, yw, sca, frac, lf);
+			if (active) {
+				if (narrow)
+					fit_lane<UNITW, 4>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib, iters,
+						wv, yw, sca, frac, gbase, gmode, gsrc, lf);
+				else
+					fit_lane<UNITW>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib, iters,
+						wv, yw, sca, frac, gbase, gmode, gsrc, lf);
+			}
 			CF_FRESH_LANE(lane);         // the roles below are computed again from here
 			if (sst) {
 				// (every role again from the fresh lane id: nothing but the fit's result lived across fit_lane)
@@ -1332,6 +1420,11 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				}
 				continue;
 			}
+			// the fit this lane's geometry-cache column now holds: written by every lane of the first stream trip (a
+			// column of the previous block must not pass for this one's), by the lanes that ran a fit in a later one
+			if (active || st == 0u)
+				gbase[lane + 12*CF_WG_THREADS] = active ? geo_tag(R_M6 ? 0u : ((R_VECP || R_SCA) ? R_CID : R_IDBASE + mypart),
+					R_SCA ? 1u : (R_PLANE ? R_SUB : 0u)) : CF_BC7_GEO_NONE;
 			// ---- assemble candidates in their leader lanes ----
 			//   mode 6: its first lane;  mode 4/5: vector lane (scalar plane s2off lanes up);
 			//   partitions: subset-0 lane (the other subsets in the next lanes)
@@ -1481,6 +1574,10 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				}
 			} else
 				pp_sum = ycc_pp_sum(tx, g.mask, yw);
+			// the 4-entry selector search when no active lane's fit has more than 4 palette entries (wave-uniform)
+			const bool narrow = __ballot(act && (g.m6 || g.ib > 2u)) == 0ull;
+			CF_DIAG_COUNT(CF_DIAG_PERTURB, !(CF_BC7_ABLATE & 32) && (kk == ntop ? uber2 : uber) != 0u);
+			CF_DIAG_COUNT(CF_DIAG_PERTURB_NARROW, !(CF_BC7_ABLATE & 32) && (kk == ntop ? uber2 : uber) != 0u && narrow);
 			const uint32_t S = g.pbk ? 1u : 0u;
 			const uint32_t fq0 = g.planes45 ? (g.sca ? 4u : 0u) : 2u*kf, fq1 = fq0 + 1u;   // column words of the fit's fields
 #pragma unroll 1
@@ -1536,7 +1633,10 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 					for (int j = 0; j < 4; ++j) f.w[j] = 0;
 					float x0[4], x1[4], hq[3];
 					bool okk;
-					assign_lsq_lane<UNITW>(tx, g.mask, g.m6, L_HL & 1u, g.ib, yw, pp_sum, false, fe0, fe1, f, x0, x1, hq, okk);
+					if (narrow)
+						assign_lsq_lane<UNITW, 4>(tx, g.mask, g.m6, L_HL & 1u, g.ib, yw, pp_sum, false, fe0, fe1, f, x0, x1, hq, okk);
+					else
+						assign_lsq_lane<UNITW>(tx, g.mask, g.m6, L_HL & 1u, g.ib, yw, pp_sum, false, fe0, fe1, f, x0, x1, hq, okk);
 					const uint32_t key = valid ? ((f.err << 4) | mv) : 0xFFFFFFFFu;
 					uint32_t fitmin = cf_row_min_u32(key);
 					if (g.m6) {
@@ -1602,6 +1702,7 @@ __attribute__((amdgpu_waves_per_eu(CF_BC7_WAVES(UNITW, WIDE), CF_BC7_WAVES(UNITW
 cfhip_bc7_encode_kernel(cf_kparams kp)
 {
 	__shared__ uint32_t cands[CF_BC7_CAND_WORDS*CF_WG_THREADS];
+	__shared__ uint32_t geoc[CF_BC7_GEO_WORDS*CF_WG_THREADS];
 	__shared__ __attribute__((aligned(16))) uint32_t tile[CF_BLOCKS_PER_WG*16];
 	__shared__ __attribute__((aligned(16))) uint32_t plan[CF_BLOCKS_PER_WG*16];
 	__shared__ uint4 outb[CF_BLOCKS_PER_WG];
@@ -1641,7 +1742,7 @@ cfhip_bc7_encode_kernel(cf_kparams kp)
 			!(CF_BC7_ABLATE & 4);
 		// opaque copy: keeps the (many) lane-role values of encode_blocks from being hoisted
 		// out of this loop and held in registers across all phases
-		const uint4 blk = encode_blocks<UNITW, WIDE>(tile, plan, yccp, b, pair, cands + wave*64u, kp);
+		const uint4 blk = encode_blocks<UNITW, WIDE>(tile, plan, yccp, b, pair, cands + wave*64u, geoc + wave*64u, kp);
 		uint32_t lo;
 		asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lo));
 		if (pair) {
@@ -1686,3 +1787,15 @@ extern "C" hipError_t cfhip_launch_bc7(const cf_kparams* kp, int pixel_type, int
 #undef CF_BC7_LAUNCH
 	return hipGetLastError();
 }
+
+#if CF_BC7_DIAG
+// copy the diagnostic counters to out[0 .. 4] and zero them
+extern "C" hipError_t cfhip_bc7_diag(unsigned long long* out)
+{
+	hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(cf_bc7_diag), sizeof(cf_bc7_diag));
+	const unsigned long long z[CF_DIAG_N] = {};
+	if (e == hipSuccess)
+		e = hipMemcpyToSymbol(HIP_SYMBOL(cf_bc7_diag), z, sizeof(z));
+	return e;
+}
+#endif
