@@ -151,9 +151,9 @@ struct cfhip_ctx {
 	size_t h_out_cap = 0;
 	static constexpr int kOutSlots = 4;
 	cf_host_pool* pool = nullptr;
-	// d_src / d_out / d_batch are shared by every entry point, and calls on a caller's stream
+	// d_src / d_out / d_batch / d_mip3d are shared by every entry point, and calls on a caller's stream
 	// return without synchronising: the last asynchronous user records this event and a call on
-	// ANOTHER stream waits for it before touching the buffers (same-stream reuse is ordered anyway)
+	// ANOTHER stream waits for it before touching the buffers.  Written by StagingLease alone.
 	hipEvent_t staging_done = nullptr;
 	hipEvent_t group_up = nullptr;    // grouped host path: the group's uploads have left the caller's buffers (release hook)
 	hipStream_t staging_stream = nullptr;
@@ -605,44 +605,74 @@ int reserve(cfhip_ctx* ctx, void** buf, size_t* cap, size_t need)
 	return CFHIP_OK;
 }
 
-int staging_acquire(cfhip_ctx* ctx, hipStream_t stream)
-{
-	if (ctx->staging_busy && ctx->staging_stream != stream)
-		HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->staging_done, 0));
-	return CFHIP_OK;
-}
+// The one owner of the staging buffers (d_src, d_out, d_batch, d_mip3d) for one call on one stream; the only code
+// that writes staging_busy / staging_stream / staging_done.  Declared after the context's lock guard, so that it
+// ends before the lock is released.
+//  * acquire(): before the first touch of a buffer; the first call makes the stream wait for the last asynchronous
+//    user when that was another stream (same-stream reuse is ordered anyway).
+//  * done(synchronous): the only success exit.  An asynchronous call that acquired records staging_done and becomes
+//    the last user; a synchronous one drains its stream, after which the buffers are idle if it acquired (its stream
+//    waited for the previous user) or was the last user itself.
+//  * any other exit (an error return, an exception unwinding to encode_impl): a call that acquired drains its stream
+//    and the host pipeline's copy streams, and the buffers are idle once that succeeded; a call that never acquired
+//    leaves their state as it found it -- another stream's work may still be in flight on them.
+struct StagingLease {
+	cfhip_ctx* const ctx;
+	const hipStream_t stream;
+	bool acquired = false, finished = false;
 
-int staging_release(cfhip_ctx* ctx, hipStream_t stream)
-{
-	if (!ctx->staging_done)
-		HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->staging_done, hipEventDisableTiming));
-	HIP_TRY(ctx, hipEventRecord(ctx->staging_done, stream));
-	ctx->staging_stream = stream;
-	ctx->staging_busy = true;
-	return CFHIP_OK;
-}
+	StagingLease(cfhip_ctx* c, hipStream_t s) : ctx(c), stream(s) {}
+	StagingLease(const StagingLease&) = delete;
+	StagingLease& operator=(const StagingLease&) = delete;
 
-// Error exit of a call that may already have enqueued work on the staging buffers: drain the
-// stream (errors are rare) and record the release, so a later call on another stream neither
-// skips its wait nor overwrites buffers this call's kernels still read.  Returns `rc`.
-int staging_abort(cfhip_ctx* ctx, hipStream_t stream, bool used_staging, int rc)
-{
-	if (used_staging) {
-		const std::string keep = ctx->error;
-		// the acquire made `stream` wait for the buffers' previous user, so once `stream` has
-		// drained nothing is in flight on them
-		if (hipStreamSynchronize(stream) == hipSuccess)
-			ctx->staging_busy = false;
-		ctx->error = keep;
+	int acquire()
+	{
+		if (!acquired && ctx->staging_busy && ctx->staging_stream != stream)
+			HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->staging_done, 0));
+		acquired = true;
+		return CFHIP_OK;
 	}
-	return rc;
-}
+
+	int done(bool synchronous)
+	{
+		if (synchronous) {
+			HIP_TRY(ctx, hipStreamSynchronize(stream));
+			if (acquired || ctx->staging_stream == stream)
+				ctx->staging_busy = false;
+		} else if (acquired) {
+			if (!ctx->staging_done)
+				HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->staging_done, hipEventDisableTiming));
+			HIP_TRY(ctx, hipEventRecord(ctx->staging_done, stream));
+			ctx->staging_stream = stream;
+			ctx->staging_busy = true;
+		}
+		finished = true;
+		return CFHIP_OK;
+	}
+
+	~StagingLease()
+	{
+		if (finished)
+			return;
+		if (acquired) {
+			// (the copy streams are idle unless the host pipeline ran: draining them is free otherwise)
+			bool drained = hipStreamSynchronize(stream) == hipSuccess;
+			if (ctx->up_stream) drained = hipStreamSynchronize(ctx->up_stream) == hipSuccess && drained;
+			if (ctx->down_stream) drained = hipStreamSynchronize(ctx->down_stream) == hipSuccess && drained;
+			if (drained)
+				ctx->staging_busy = false;
+		}
+		// the error's text is in ctx->error; a runtime error left behind would fail the next launch's check
+		(void)hipGetLastError();
+	}
+};
 
 // One launch for many surfaces (same format / pixel type): workgroups are numbered across
 // the surfaces, the kernel resolves its surface with a uniform binary search (cf_resolve).
-int batched_launch(cfhip_ctx* ctx, const std::vector<cf_kparams>& kps, const cfhip_params& p,
-	int pixel_type, hipStream_t stream)
+int batched_launch(cfhip_ctx* ctx, StagingLease& lease, const std::vector<cf_kparams>& kps, const cfhip_params& p,
+	int pixel_type)
 {
+	const hipStream_t stream = lease.stream;
 	if (kps.size() == 1)
 		return timed_launch(ctx, kps[0], p, pixel_type, stream);
 	if (is_std_format(p.format)) {
@@ -669,7 +699,7 @@ int batched_launch(cfhip_ctx* ctx, const std::vector<cf_kparams>& kps, const cfh
 		wg += e.wgx*kps[i].by;
 	}
 	const size_t bytes = entries.size()*sizeof(cf_batch_entry);
-	rc = staging_acquire(ctx, stream);
+	rc = lease.acquire();
 	if (rc != CFHIP_OK)
 		return rc;
 	rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, bytes);
@@ -681,10 +711,7 @@ int batched_launch(cfhip_ctx* ctx, const std::vector<cf_kparams>& kps, const cfh
 	kp.batch = static_cast<const cf_batch_entry*>(ctx->d_batch);
 	kp.nbatch = (uint32_t)entries.size();
 	kp.total_wg = wg;
-	rc = timed_launch(ctx, kp, p, pixel_type, stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	return staging_release(ctx, stream);
+	return timed_launch(ctx, kp, p, pixel_type, stream);
 }
 
 // ---- pipelined host path ----------------------------------------
@@ -795,39 +822,12 @@ unsigned usable_cpus()
 // Strips of whole block rows flow through four overlapped stages: host threads gather (and quantise) strip
 // k+2 into a pinned slot | the upload stream copies strip k+1 | the launch stream encodes strip k | the
 // download stream returns the payload of strip k-1 into a pinned landing buffer.  Three pinned slots; events
-// order slot reuse (pin_free), upload -> kernel (up_done) and kernel -> download (one pair per strip).
-int encode_host_pipelined_impl(cfhip_ctx* ctx, const cfhip_surface& s, const cfhip_params& p,
-	hipStream_t stream);
-
-// The pipeline proper is encode_host_pipelined_impl; this wrapper owns its failure modes (round-4 ADVICE):
-//  * an error return from the middle of the pipeline leaves copies queued on the upload / download streams that still
-//    read and write the pinned slots, and staging_busy set: all three streams are drained and the staging marked free
-//    before the error goes to the caller, so the next call can never stage into a slot an old upload is reading;
-//  * std::bad_alloc / std::system_error (vector growth, thread creation under a pids limit) must not cross the
-//    extern "C" boundary: they become CFHIP_E_DEVICE with the text in cfhip_last_error.
-int encode_host_pipelined(cfhip_ctx* ctx, const cfhip_surface& s, const cfhip_params& p,
-	hipStream_t stream)
+// order slot reuse (pin_free), upload -> kernel (up_done) and kernel -> download (one pair per strip).  An error return
+// from the middle leaves copies queued on the copy streams that still read and write the pinned slots: the lease drains
+// them before the error goes to the caller, so the next call can never stage into a slot an old upload is reading.
+int encode_strip_pipeline(cfhip_ctx* ctx, StagingLease& lease, const cfhip_surface& s, const cfhip_params& p)
 {
-	int rc;
-	try {
-		rc = encode_host_pipelined_impl(ctx, s, p, stream);
-	} catch (const std::exception& e) {
-		rc = fail(ctx, CFHIP_E_DEVICE, "host pipeline: %s", e.what());
-	} catch (...) {
-		rc = fail(ctx, CFHIP_E_DEVICE, "host pipeline: unknown exception");
-	}
-	if (rc != CFHIP_OK) {
-		(void)hipStreamSynchronize(stream);
-		if (ctx->up_stream) (void)hipStreamSynchronize(ctx->up_stream);
-		if (ctx->down_stream) (void)hipStreamSynchronize(ctx->down_stream);
-		ctx->staging_busy = false;
-	}
-	return rc;
-}
-
-int encode_host_pipelined_impl(cfhip_ctx* ctx, const cfhip_surface& s, const cfhip_params& p,
-	hipStream_t stream)
-{
+	const hipStream_t stream = lease.stream;
 	int fbw, fbh;
 	block_dims(p.format, &fbw, &fbh);
 	const int bs = unit_bytes(p.format, p.type);
@@ -845,7 +845,7 @@ int encode_host_pipelined_impl(cfhip_ctx* ctx, const cfhip_surface& s, const cfh
 	if (is_std_format(p.format))
 		strip_brows = (strip_brows + 3u) & ~3u;   // every strip's output stays 4-byte aligned
 	const size_t strip_bytes = (size_t)strip_brows*(size_t)fbh*dev_row;
-	int rc = staging_acquire(ctx, stream);
+	int rc = lease.acquire();
 	if (rc != CFHIP_OK) return rc;
 	rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, dev_row*(size_t)s.height);
 	if (rc != CFHIP_OK) return rc;
@@ -910,7 +910,7 @@ int encode_host_pipelined_impl(cfhip_ctx* ctx, const cfhip_surface& s, const cfh
 		return CFHIP_OK;
 	};
 	{
-		// the copy streams start after whatever the launch stream was asked to wait for (staging_acquire)
+		// the copy streams start after whatever the launch stream was asked to wait for (the lease's acquire)
 		hipEvent_t order;
 		rc = next_event(&order);
 		if (rc != CFHIP_OK) return rc;
@@ -985,10 +985,7 @@ int encode_host_pipelined_impl(cfhip_ctx* ctx, const cfhip_surface& s, const cfh
 	}
 	rc = drain(true);
 	HIP_TRY(ctx, hipStreamSynchronize(stream));
-	if (rc != CFHIP_OK)
-		return rc;
-	ctx->staging_busy = false;
-	return CFHIP_OK;
+	return rc;
 }
 
 } // namespace
@@ -1149,15 +1146,13 @@ static int validate_surfaces(cfhip_ctx* ctx, const cfhip_surface* surfaces, size
 // `consumed(user, i)`: called once the library has finished READING surfaces[i].pixels (host path only): the
 // caller may release that source then, as Converter::convert frees every source image as soon as its surface
 // is converted (Converter.cpp:586) instead of holding the whole texture until the call returns.
-static int encode_body(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n,
-	const cfhip_params* params, bool device_mem, hipStream_t user_stream,
-	cfhip_consumed_fn consumed, void* user);
+static int encode_body(cfhip_ctx* ctx, StagingLease& lease, const cfhip_surface* surfaces, size_t n,
+	const cfhip_params* params, bool device_mem, bool user_stream, cfhip_consumed_fn consumed, void* user);
 
 // Every encode entry point of the C ABI comes through here (round-5 ADVICE: the guard used to cover the strip pipeline
 // only).  No exception crosses the extern "C" boundary -- std::bad_alloc / std::system_error from the vectors and
-// threads of the body become CFHIP_E_DEVICE with the text in cfhip_last_error -- and an error return from the host
-// path never leaves uploads or downloads queued on the staging buffers with staging_busy set: the context's streams are
-// drained and the staging marked free before the error goes to the caller.
+// threads of the body become CFHIP_E_DEVICE with the text in cfhip_last_error -- and the lease, which outlives the
+// catch, drains whatever an error return or an exception left queued on the staging buffers.
 static int encode_impl(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n,
 	const cfhip_params* params, bool device_mem, hipStream_t user_stream,
 	cfhip_consumed_fn consumed = nullptr, void* user = nullptr)
@@ -1165,27 +1160,18 @@ static int encode_impl(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n,
 	if (!ctx)
 		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 	std::lock_guard<std::mutex> guard(ctx->lock);
-	int rc;
+	StagingLease lease(ctx, user_stream ? user_stream : ctx->stream);
 	try {
-		rc = encode_body(ctx, surfaces, n, params, device_mem, user_stream, consumed, user);
+		return encode_body(ctx, lease, surfaces, n, params, device_mem, user_stream != nullptr, consumed, user);
 	} catch (const std::exception& e) {
-		rc = fail(ctx, CFHIP_E_DEVICE, "encode: %s", e.what());
+		return fail(ctx, CFHIP_E_DEVICE, "encode: %s", e.what());
 	} catch (...) {
-		rc = fail(ctx, CFHIP_E_DEVICE, "encode: unknown exception");
+		return fail(ctx, CFHIP_E_DEVICE, "encode: unknown exception");
 	}
-	if (rc != CFHIP_OK && !device_mem) {
-		(void)hipStreamSynchronize(ctx->stream);
-		if (ctx->up_stream) (void)hipStreamSynchronize(ctx->up_stream);
-		if (ctx->down_stream) (void)hipStreamSynchronize(ctx->down_stream);
-		(void)hipGetLastError();
-		ctx->staging_busy = false;
-	}
-	return rc;
 }
 
-static int encode_body(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n,
-	const cfhip_params* params, bool device_mem, hipStream_t user_stream,
-	cfhip_consumed_fn consumed, void* user)
+static int encode_body(cfhip_ctx* ctx, StagingLease& lease, const cfhip_surface* surfaces, size_t n,
+	const cfhip_params* params, bool device_mem, bool user_stream, cfhip_consumed_fn consumed, void* user)
 {
 	ctx->error.clear();
 	int rc = check_params(ctx, params);
@@ -1194,7 +1180,7 @@ static int encode_body(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n,
 	if (!surfaces && n)
 		return fail(ctx, CFHIP_E_INVALID, "surfaces is NULL");
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	hipStream_t stream = user_stream ? user_stream : ctx->stream;
+	const hipStream_t stream = lease.stream;
 	if (!ctx->profiling)
 		ctx->events_used = 0;
 	ctx->events_stream = stream;
@@ -1221,7 +1207,7 @@ static int encode_body(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n,
 				kps.push_back(kp);
 				++i1;
 			}
-			rc = batched_launch(ctx, kps, *params, surfaces[i0].pixel_type, stream);
+			rc = batched_launch(ctx, lease, kps, *params, surfaces[i0].pixel_type);
 			if (rc != CFHIP_OK)
 				return rc;
 			i0 = i1;
@@ -1245,7 +1231,7 @@ static int encode_body(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n,
 		size_t g0 = 0;
 		while (g0 < n) {
 			if (pipelined(g0)) {
-				rc = encode_host_pipelined(ctx, surfaces[g0], *params, stream);
+				rc = encode_strip_pipeline(ctx, lease, surfaces[g0], *params);
 				if (rc != CFHIP_OK)
 					return rc;
 				if (consumed)
@@ -1260,7 +1246,7 @@ static int encode_body(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n,
 				out_total += (items[g1].out_bytes + 255) & ~(size_t)255;
 				++g1;
 			}
-			rc = staging_acquire(ctx, stream);
+			rc = lease.acquire();
 			if (rc != CFHIP_OK) return rc;
 			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, src_total);
 			if (rc != CFHIP_OK) return rc;
@@ -1282,7 +1268,7 @@ static int encode_body(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n,
 						(size_t)s.row_pitch_bytes, items[i].row_bytes, s.height, hipMemcpyHostToDevice,
 						stream));
 				if (s.pixel_type != run_type && !kps.empty()) {
-					rc = batched_launch(ctx, kps, *params, run_type, stream);
+					rc = batched_launch(ctx, lease, kps, *params, run_type);
 					if (rc != CFHIP_OK)
 						return rc;
 					kps.clear();
@@ -1302,7 +1288,7 @@ static int encode_body(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n,
 					HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->group_up, hipEventDisableTiming));
 				HIP_TRY(ctx, hipEventRecord(ctx->group_up, stream));
 			}
-			rc = batched_launch(ctx, kps, *params, run_type, stream);
+			rc = batched_launch(ctx, lease, kps, *params, run_type);
 			if (rc != CFHIP_OK)
 				return rc;
 			for (size_t i = g0; i < g1; ++i)
@@ -1315,13 +1301,10 @@ static int encode_body(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n,
 					consumed(user, i);             // the group's uploads have left the host buffers
 			}
 			HIP_TRY(ctx, hipStreamSynchronize(stream));   // staging buffers are reused
-			ctx->staging_busy = false;
 			g0 = g1;
 		}
 	}
-	if (!device_mem || !user_stream)
-		HIP_TRY(ctx, hipStreamSynchronize(stream));
-	return CFHIP_OK;
+	return lease.done(!device_mem || !user_stream);
 }
 
 int cfhip_encode(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n_surfaces,
@@ -1515,51 +1498,73 @@ static bool filter_valid(int filter)
 	return !(filter & CFHIP_FILTER_FALLBACK) || base <= CFHIP_FILTER_LINEAR;
 }
 
+// The argument checks every mip / resize entry point shares, in this order; `what` names the entry point in the
+// messages.  depth 0: a 2-D texture.
+static int check_mip_args(cfhip_ctx* ctx, const char* what, int pixel_type, int color_space, int filter,
+	uint32_t width, uint32_t height, uint32_t depth, uint32_t levels, size_t pitch)
+{
+	if (pixel_type < CFHIP_PIXEL_RGBA8 || pixel_type > CFHIP_PIXEL_RGBA16F)
+		return fail(ctx, CFHIP_E_INVALID, "%s: pixel type %d", what, pixel_type);
+	if (color_space != CFHIP_COLOR_LINEAR && color_space != CFHIP_COLOR_SRGB)
+		return fail(ctx, CFHIP_E_INVALID, "%s: colour space %d", what, color_space);
+	if (!filter_valid(filter))
+		return fail(ctx, CFHIP_E_INVALID, "%s: resize filter %d", what, filter);
+	// maxMipmapLevels: floor(log2(max(w, h, d))) + 1 (Texture.cpp)
+	uint32_t max_levels = 1;
+	for (uint32_t d = std::max({width, height, depth}); d > 1; d >>= 1)
+		++max_levels;
+	if (levels > max_levels && depth)
+		return fail(ctx, CFHIP_E_INVALID, "%u mip levels requested, a %ux%ux%u texture has %u", levels,
+			width, height, depth, max_levels);
+	if (levels > max_levels)
+		return fail(ctx, CFHIP_E_INVALID, "%u mip levels requested, a %ux%u texture has %u", levels,
+			width, height, max_levels);
+	if (pitch < (size_t)width*pixel_bytes(pixel_type))
+		return fail(ctx, CFHIP_E_INVALID, "%s: row pitch smaller than a row", what);
+	return CFHIP_OK;
+}
+
 // One 2-D resize of Image::resize (Image.cpp:1324-1511): prev (any pixel type) -> dst (RGBA32F,
 // tightly packed w x h): FreeImage_Rescale's two passes for all five filters; one kernel for the
 // in-tree fallback of Box / Linear (CFHIP_FILTER_FALLBACK).
-static int mip_level_2d(cfhip_ctx* ctx, const void* prev, int prev_type, size_t prev_pitch, uint32_t pw,
-	uint32_t ph, void* dst, uint32_t w, uint32_t h, int filter, int srgb, hipStream_t stream, bool* used_staging_)
+static int mip_level_2d(cfhip_ctx* ctx, StagingLease& lease, const void* prev, int prev_type, size_t prev_pitch,
+	uint32_t pw, uint32_t ph, void* dst, uint32_t w, uint32_t h, int filter, int srgb)
 {
-	bool& used_staging = *used_staging_;
-	void* const dst_levels[1] = {dst};
-	const uint32_t k = 1;
-	{
-		if (filter & CFHIP_FILTER_FALLBACK) {
-			// the loops Image::resize runs itself when FreeImage_Rescale fails (Image.cpp:1393-1505)
-			HIP_TRY(ctx, cfhip_launch_mip_resize(prev, prev_type, prev_pitch, pw, ph, dst_levels[k - 1], w, h,
-				filter & 0xFF, srgb, stream));
-		} else {
-			// FreeImage_Rescale's two passes, horizontal first when dst_w*src_h <= dst_h*src_w, with a
-			// float intermediate image in the context's staging buffer; a pass whose size does
-			// not change is skipped (the other one then does both colour conversions)
-			const bool x_first = (unsigned long long)w*ph <= (unsigned long long)h*pw;
-			const bool need_x = w != pw, need_y = h != ph;
-			// the fused kernel does taps_x * taps_y work per output texel: it beats the two passes (24 -> 8 bytes per
-			// texel) only while the footprint is small -- a mip step (2:1, at most 3 x 3 taps with an odd size).  A
-			// resize of a custom mip image can have any ratio (1024 x 1024 -> 1 x 1: a million taps in one thread
-			// against 2 x 1024 for the separable passes): those take the two-pass route
-			const bool small_taps = (unsigned long long)pw <= 2ull*w + 1ull && (unsigned long long)ph <= 2ull*h + 1ull;
-			if (need_x && need_y && filter == CFHIP_FILTER_BOX && small_taps) {
-				// the box filter: both passes in one launch, no float image in between (bit-identical)
-				HIP_TRY(ctx, cfhip_launch_mip_fused_layers(prev, prev_type, prev_pitch, pw, ph, dst_levels[k - 1], w, h,
-					x_first ? 1 : 0, filter, srgb, 1u, nullptr, nullptr, 0, 0, stream));
-			} else if (need_x && need_y) {
-				const uint32_t tw = x_first ? w : pw, th = x_first ? ph : h;
-				int rc = staging_acquire(ctx, stream);
-				if (rc != CFHIP_OK) return rc;
-				rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, (size_t)tw*th*16u);
-				if (rc != CFHIP_OK) return rc;
-				used_staging = true;
-				HIP_TRY(ctx, cfhip_launch_mip_pass(prev, prev_type, prev_pitch, x_first ? pw : ph, ctx->d_src, tw, th,
-					x_first ? 1 : 0, filter, srgb, 0, stream));
-				HIP_TRY(ctx, cfhip_launch_mip_pass(ctx->d_src, CFHIP_PIXEL_RGBA32F, (size_t)tw*16u, x_first ? ph : pw,
-					dst_levels[k - 1], w, h, x_first ? 0 : 1, filter, 0, srgb, stream));
-			} else {
-				HIP_TRY(ctx, cfhip_launch_mip_pass(prev, prev_type, prev_pitch, need_x ? pw : ph, dst_levels[k - 1], w, h,
-					need_x ? 1 : 0, filter, srgb, srgb, stream));
-			}
-		}
+	const hipStream_t stream = lease.stream;
+	if (filter & CFHIP_FILTER_FALLBACK) {
+		// the loops Image::resize runs itself when FreeImage_Rescale fails (Image.cpp:1393-1505)
+		HIP_TRY(ctx, cfhip_launch_mip_resize(prev, prev_type, prev_pitch, pw, ph, dst, w, h, filter & 0xFF, srgb,
+			stream));
+		return CFHIP_OK;
+	}
+	// FreeImage_Rescale's two passes, horizontal first when dst_w*src_h <= dst_h*src_w, with a
+	// float intermediate image in the context's staging buffer; a pass whose size does
+	// not change is skipped (the other one then does both colour conversions)
+	const bool x_first = (unsigned long long)w*ph <= (unsigned long long)h*pw;
+	const bool need_x = w != pw, need_y = h != ph;
+	// the fused kernel does taps_x * taps_y work per output texel: it beats the two passes (24 -> 8 bytes per
+	// texel) only while the footprint is small -- a mip step (2:1, at most 3 x 3 taps with an odd size).  A
+	// resize of a custom mip image can have any ratio (1024 x 1024 -> 1 x 1: a million taps in one thread
+	// against 2 x 1024 for the separable passes): those take the two-pass route
+	const bool small_taps = (unsigned long long)pw <= 2ull*w + 1ull && (unsigned long long)ph <= 2ull*h + 1ull;
+	if (need_x && need_y && filter == CFHIP_FILTER_BOX && small_taps) {
+		// the box filter: both passes in one launch, no float image in between (bit-identical)
+		HIP_TRY(ctx, cfhip_launch_mip_fused_layers(prev, prev_type, prev_pitch, pw, ph, dst, w, h,
+			x_first ? 1 : 0, filter, srgb, 1u, nullptr, nullptr, 0, 0, stream));
+	} else if (need_x && need_y) {
+		const uint32_t tw = x_first ? w : pw, th = x_first ? ph : h;
+		int rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, (size_t)tw*th*16u);
+		if (rc != CFHIP_OK)
+			return rc;
+		HIP_TRY(ctx, cfhip_launch_mip_pass(prev, prev_type, prev_pitch, x_first ? pw : ph, ctx->d_src, tw, th,
+			x_first ? 1 : 0, filter, srgb, 0, stream));
+		HIP_TRY(ctx, cfhip_launch_mip_pass(ctx->d_src, CFHIP_PIXEL_RGBA32F, (size_t)tw*16u, x_first ? ph : pw,
+			dst, w, h, x_first ? 0 : 1, filter, 0, srgb, stream));
+	} else {
+		HIP_TRY(ctx, cfhip_launch_mip_pass(prev, prev_type, prev_pitch, need_x ? pw : ph, dst, w, h,
+			need_x ? 1 : 0, filter, srgb, srgb, stream));
 	}
 	return CFHIP_OK;
 }
@@ -1573,56 +1578,32 @@ int cfhip_generate_mips_device(cfhip_ctx* ctx, const void* src, int src_pixel_ty
 	std::lock_guard<std::mutex> guard(ctx->lock);
 	if (!src || !width || !height || !levels || (levels > 1 && !dst_levels))
 		return fail(ctx, CFHIP_E_INVALID, "mip generation: NULL or empty argument");
-	if (src_pixel_type < CFHIP_PIXEL_RGBA8 || src_pixel_type > CFHIP_PIXEL_RGBA16F)
-		return fail(ctx, CFHIP_E_INVALID, "mip generation: pixel type %d", src_pixel_type);
-	if (color_space != CFHIP_COLOR_LINEAR && color_space != CFHIP_COLOR_SRGB)
-		return fail(ctx, CFHIP_E_INVALID, "mip generation: colour space %d", color_space);
-	if (!filter_valid(filter))
-		return fail(ctx, CFHIP_E_INVALID, "resize filter %d", filter);
-	// maxMipmapLevels for a 2-D texture: floor(log2(max(w, h))) + 1 (Texture.cpp)
-	uint32_t max_levels = 1;
-	for (uint32_t d = width > height ? width : height; d > 1; d >>= 1)
-		++max_levels;
-	if (levels > max_levels)
-		return fail(ctx, CFHIP_E_INVALID, "%u mip levels requested, a %ux%u texture has %u", levels,
-			width, height, max_levels);
-	const size_t texel = src_pixel_type == CFHIP_PIXEL_RGBA8 ? 4 : (src_pixel_type == CFHIP_PIXEL_RGBA32F ? 16 : 8);
-	if (src_pitch_bytes < (size_t)width*texel)
-		return fail(ctx, CFHIP_E_INVALID, "mip generation: row pitch smaller than a row");
+	int rc = check_mip_args(ctx, "mip generation", src_pixel_type, color_space, filter, width, height, 0, levels,
+		src_pitch_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
+	for (uint32_t k = 1; k < levels; ++k)
+		if (!dst_levels[k - 1])
+			return fail(ctx, CFHIP_E_INVALID, "mip generation: dst_levels[%u] is NULL", k - 1);
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream;
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
 	// level k from level k-1, as Texture::generateMipmaps does (Texture.cpp:1480-1487)
 	const void* prev = src;
 	int prev_type = src_pixel_type;
 	size_t prev_pitch = src_pitch_bytes;
-	bool used_staging = false;
 	uint32_t pw = width, ph = height;
 	for (uint32_t k = 1; k < levels; ++k) {
-		if (!dst_levels[k - 1])
-			return staging_abort(ctx, stream, used_staging,
-				fail(ctx, CFHIP_E_INVALID, "mip generation: dst_levels[%u] is NULL", k - 1));
 		const uint32_t w = (width >> k) ? (width >> k) : 1u, h = (height >> k) ? (height >> k) : 1u;
-		const int rc2 = mip_level_2d(ctx, prev, prev_type, prev_pitch, pw, ph, dst_levels[k - 1], w, h, filter,
-			color_space == CFHIP_COLOR_SRGB ? 1 : 0, stream, &used_staging);
-		if (rc2 != CFHIP_OK)
-			return staging_abort(ctx, stream, used_staging, rc2);
+		rc = mip_level_2d(ctx, lease, prev, prev_type, prev_pitch, pw, ph, dst_levels[k - 1], w, h, filter,
+			color_space == CFHIP_COLOR_SRGB ? 1 : 0);
+		if (rc != CFHIP_OK)
+			return rc;
 		prev = dst_levels[k - 1];
 		prev_type = CFHIP_PIXEL_RGBA32F;
 		prev_pitch = (size_t)w*16u;
 		pw = w; ph = h;
 	}
-	if (used_staging) {
-		const int rc = staging_release(ctx, stream);
-		if (rc != CFHIP_OK) return rc;
-	}
-	if (!stream_) {
-		HIP_TRY(ctx, hipStreamSynchronize(stream));
-		// the staging buffers are idle only if THIS stream was their last user (an earlier
-		// asynchronous call on another stream may still have d_src / d_batch / d_mip3d in flight)
-		if (used_staging || ctx->staging_stream == stream)
-			ctx->staging_busy = false;
-	}
-	return CFHIP_OK;
+	return lease.done(!stream_);
 }
 
 // Array / cube textures: Texture::generateMipmaps resizes every [depth][face] image of a level on its own
@@ -1642,21 +1623,10 @@ int cfhip_generate_mips_array_device(cfhip_ctx* ctx, const void* const* srcs, ui
 		return fail(ctx, CFHIP_E_INVALID, "mip generation: NULL or empty argument");
 	if (layers > 65535u)
 		return fail(ctx, CFHIP_E_INVALID, "mip generation: %u layers (at most 65535 per call)", layers);
-	if (src_pixel_type < CFHIP_PIXEL_RGBA8 || src_pixel_type > CFHIP_PIXEL_RGBA16F)
-		return fail(ctx, CFHIP_E_INVALID, "mip generation: pixel type %d", src_pixel_type);
-	if (color_space != CFHIP_COLOR_LINEAR && color_space != CFHIP_COLOR_SRGB)
-		return fail(ctx, CFHIP_E_INVALID, "mip generation: colour space %d", color_space);
-	if (!filter_valid(filter))
-		return fail(ctx, CFHIP_E_INVALID, "resize filter %d", filter);
-	uint32_t max_levels = 1;
-	for (uint32_t d = width > height ? width : height; d > 1; d >>= 1)
-		++max_levels;
-	if (levels > max_levels)
-		return fail(ctx, CFHIP_E_INVALID, "%u mip levels requested, a %ux%u texture has %u", levels,
-			width, height, max_levels);
-	const size_t texel = src_pixel_type == CFHIP_PIXEL_RGBA8 ? 4 : (src_pixel_type == CFHIP_PIXEL_RGBA32F ? 16 : 8);
-	if (src_pitch_bytes < (size_t)width*texel)
-		return fail(ctx, CFHIP_E_INVALID, "mip generation: row pitch smaller than a row");
+	int rc = check_mip_args(ctx, "mip generation", src_pixel_type, color_space, filter, width, height, 0, levels,
+		src_pitch_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
 	for (uint32_t l = 0; l < layers; ++l) {
 		if (!srcs[l])
 			return fail(ctx, CFHIP_E_INVALID, "mip generation: srcs[%u] is NULL", l);
@@ -1665,9 +1635,9 @@ int cfhip_generate_mips_array_device(cfhip_ctx* ctx, const void* const* srcs, ui
 				return fail(ctx, CFHIP_E_INVALID, "mip generation: dst_levels[%u][%u] is NULL", l, k - 1u);
 	}
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream;
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	const hipStream_t stream = lease.stream;
 	const int srgb = color_space == CFHIP_COLOR_SRGB ? 1 : 0;
-	bool used_staging = false;
 	if (levels > 1) {
 		// device pointer tables, level-major: row 0 = the sources, row k = level k of every layer
 		std::vector<const void*> tab((size_t)levels*layers);
@@ -1676,14 +1646,14 @@ int cfhip_generate_mips_array_device(cfhip_ctx* ctx, const void* const* srcs, ui
 			for (uint32_t k = 1; k < levels; ++k)
 				tab[(size_t)k*layers + l] = dst_levels[(size_t)l*(levels - 1u) + (k - 1u)];
 		}
-		int rc = staging_acquire(ctx, stream);
-		if (rc != CFHIP_OK) return rc;
-		used_staging = true;
-		rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab.size()*sizeof(void*));
-		if (rc != CFHIP_OK) return staging_abort(ctx, stream, used_staging, rc);
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab.size()*sizeof(void*));
+		if (rc != CFHIP_OK)
+			return rc;
 		// pageable source: the runtime stages the copy before returning, so `tab` may die
 		if (hipMemcpyAsync(ctx->d_batch, tab.data(), tab.size()*sizeof(void*), hipMemcpyHostToDevice, stream) != hipSuccess)
-			return staging_abort(ctx, stream, used_staging, fail(ctx, CFHIP_E_DEVICE, "mip generation: table upload failed"));
+			return fail(ctx, CFHIP_E_DEVICE, "mip generation: table upload failed");
 		const void* const* d_tab = static_cast<const void* const*>(ctx->d_batch);
 		const size_t kStagingBudget = (size_t)1 << 30;           // the float image between the two passes, all layers
 		uint32_t pw = width, ph = height;
@@ -1699,49 +1669,38 @@ int cfhip_generate_mips_array_device(cfhip_ctx* ctx, const void* const* srcs, ui
 			const size_t timg = (size_t)tw*th*16u;
 			const bool fused = filter == CFHIP_FILTER_BOX && need_x && need_y;
 			const bool batched = !(filter & CFHIP_FILTER_FALLBACK) && (fused || !(need_x && need_y) || timg*layers <= kStagingBudget);
+			hipError_t e = hipSuccess;
 			if (fused) {
-				const hipError_t e = cfhip_launch_mip_fused_layers(nullptr, prev_type, prev_pitch, pw, ph, nullptr, w, h,
+				e = cfhip_launch_mip_fused_layers(nullptr, prev_type, prev_pitch, pw, ph, nullptr, w, h,
 					x_first ? 1 : 0, filter, srgb, layers, s_tab, o_tab, 0, 0, stream);
-				if (e != hipSuccess)
-					return staging_abort(ctx, stream, used_staging, fail(ctx, CFHIP_E_DEVICE, "mip pass: %s", hipGetErrorString(e)));
 			} else if (!batched) {
 				for (uint32_t l = 0; l < layers; ++l) {
-					const int rc2 = mip_level_2d(ctx, tab[(size_t)(k - 1u)*layers + l], prev_type, prev_pitch, pw, ph,
-						const_cast<void*>(tab[(size_t)k*layers + l]), w, h, filter, srgb, stream, &used_staging);
-					if (rc2 != CFHIP_OK)
-						return staging_abort(ctx, stream, used_staging, rc2);
+					rc = mip_level_2d(ctx, lease, tab[(size_t)(k - 1u)*layers + l], prev_type, prev_pitch, pw, ph,
+						const_cast<void*>(tab[(size_t)k*layers + l]), w, h, filter, srgb);
+					if (rc != CFHIP_OK)
+						return rc;
 				}
 			} else if (need_x && need_y) {
 				rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, timg*layers);
-				if (rc != CFHIP_OK) return staging_abort(ctx, stream, used_staging, rc);
-				hipError_t e = cfhip_launch_mip_pass_layers(nullptr, prev_type, prev_pitch, x_first ? pw : ph, ctx->d_src, tw, th,
+				if (rc != CFHIP_OK)
+					return rc;
+				e = cfhip_launch_mip_pass_layers(nullptr, prev_type, prev_pitch, x_first ? pw : ph, ctx->d_src, tw, th,
 					x_first ? 1 : 0, filter, srgb, 0, layers, s_tab, nullptr, 0, timg, stream);
 				if (e == hipSuccess)
 					e = cfhip_launch_mip_pass_layers(ctx->d_src, CFHIP_PIXEL_RGBA32F, (size_t)tw*16u, x_first ? ph : pw, nullptr, w, h,
 						x_first ? 0 : 1, filter, 0, srgb, layers, nullptr, o_tab, timg, 0, stream);
-				if (e != hipSuccess)
-					return staging_abort(ctx, stream, used_staging, fail(ctx, CFHIP_E_DEVICE, "mip pass: %s", hipGetErrorString(e)));
 			} else {
-				const hipError_t e = cfhip_launch_mip_pass_layers(nullptr, prev_type, prev_pitch, need_x ? pw : ph, nullptr, w, h,
+				e = cfhip_launch_mip_pass_layers(nullptr, prev_type, prev_pitch, need_x ? pw : ph, nullptr, w, h,
 					need_x ? 1 : 0, filter, srgb, srgb, layers, s_tab, o_tab, 0, 0, stream);
-				if (e != hipSuccess)
-					return staging_abort(ctx, stream, used_staging, fail(ctx, CFHIP_E_DEVICE, "mip pass: %s", hipGetErrorString(e)));
 			}
+			if (e != hipSuccess)
+				return fail(ctx, CFHIP_E_DEVICE, "mip pass: %s", hipGetErrorString(e));
 			prev_type = CFHIP_PIXEL_RGBA32F;
 			prev_pitch = (size_t)w*16u;
 			pw = w; ph = h;
 		}
 	}
-	if (used_staging) {
-		const int rc = staging_release(ctx, stream);
-		if (rc != CFHIP_OK) return rc;
-	}
-	if (!stream_) {
-		HIP_TRY(ctx, hipStreamSynchronize(stream));
-		if (used_staging || ctx->staging_stream == stream)
-			ctx->staging_busy = false;
-	}
-	return CFHIP_OK;
+	return lease.done(!stream_);
 }
 
 int cfhip_resize_device(cfhip_ctx* ctx, const void* src, int src_pixel_type, uint32_t src_width,
@@ -1753,41 +1712,24 @@ int cfhip_resize_device(cfhip_ctx* ctx, const void* src, int src_pixel_type, uin
 	std::lock_guard<std::mutex> guard(ctx->lock);
 	if (!src || !dst || !src_width || !src_height || !dst_width || !dst_height)
 		return fail(ctx, CFHIP_E_INVALID, "resize: NULL or empty argument");
-	if (src_pixel_type < CFHIP_PIXEL_RGBA8 || src_pixel_type > CFHIP_PIXEL_RGBA16F)
-		return fail(ctx, CFHIP_E_INVALID, "resize: pixel type %d", src_pixel_type);
-	if (color_space != CFHIP_COLOR_LINEAR && color_space != CFHIP_COLOR_SRGB)
-		return fail(ctx, CFHIP_E_INVALID, "resize: colour space %d", color_space);
-	if (!filter_valid(filter))
-		return fail(ctx, CFHIP_E_INVALID, "resize filter %d", filter);
-	const size_t texel = src_pixel_type == CFHIP_PIXEL_RGBA8 ? 4 : (src_pixel_type == CFHIP_PIXEL_RGBA32F ? 16 : 8);
-	if (src_pitch_bytes < (size_t)src_width*texel)
-		return fail(ctx, CFHIP_E_INVALID, "resize: row pitch smaller than a row");
+	int rc = check_mip_args(ctx, "resize", src_pixel_type, color_space, filter, src_width, src_height, 0, 1,
+		src_pitch_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream;
-	bool used_staging = false;
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
 	if (src_width == dst_width && src_height == dst_height) {
 		// Image::resize returns the image itself (Image.cpp:1330-1334): the texels as RGBAF, no
 		// colour-space round trip (a 1:1 box footprint is the texel)
 		HIP_TRY(ctx, cfhip_launch_mip_resize(src, src_pixel_type, src_pitch_bytes, src_width, src_height, dst,
-			dst_width, dst_height, CFHIP_FILTER_BOX, 0, stream));
+			dst_width, dst_height, CFHIP_FILTER_BOX, 0, lease.stream));
 	} else {
-		const int rc = mip_level_2d(ctx, src, src_pixel_type, src_pitch_bytes, src_width, src_height, dst,
-			dst_width, dst_height, filter, color_space == CFHIP_COLOR_SRGB ? 1 : 0, stream, &used_staging);
+		rc = mip_level_2d(ctx, lease, src, src_pixel_type, src_pitch_bytes, src_width, src_height, dst,
+			dst_width, dst_height, filter, color_space == CFHIP_COLOR_SRGB ? 1 : 0);
 		if (rc != CFHIP_OK)
-			return staging_abort(ctx, stream, used_staging, rc);
+			return rc;
 	}
-	if (used_staging) {
-		const int rc = staging_release(ctx, stream);
-		if (rc != CFHIP_OK) return rc;
-	}
-	if (!stream_) {
-		HIP_TRY(ctx, hipStreamSynchronize(stream));
-		// the staging buffers are idle only if THIS stream was their last user (an earlier
-		// asynchronous call on another stream may still have d_src / d_batch / d_mip3d in flight)
-		if (used_staging || ctx->staging_stream == stream)
-			ctx->staging_busy = false;
-	}
-	return CFHIP_OK;
+	return lease.done(!stream_);
 }
 
 int cfhip_generate_mips3d_device(cfhip_ctx* ctx, const void* src, int src_pixel_type,
@@ -1799,25 +1741,18 @@ int cfhip_generate_mips3d_device(cfhip_ctx* ctx, const void* src, int src_pixel_
 	std::lock_guard<std::mutex> guard(ctx->lock);
 	if (!src || !width || !height || !depth || !levels || (levels > 1 && !dst_levels))
 		return fail(ctx, CFHIP_E_INVALID, "3-D mip generation: NULL or empty argument");
-	if (src_pixel_type < CFHIP_PIXEL_RGBA8 || src_pixel_type > CFHIP_PIXEL_RGBA16F)
-		return fail(ctx, CFHIP_E_INVALID, "3-D mip generation: pixel type %d", src_pixel_type);
-	if (color_space != CFHIP_COLOR_LINEAR && color_space != CFHIP_COLOR_SRGB)
-		return fail(ctx, CFHIP_E_INVALID, "3-D mip generation: colour space %d", color_space);
-	if (!filter_valid(filter))
-		return fail(ctx, CFHIP_E_INVALID, "resize filter %d", filter);
-	// maxMipmapLevels for a 3-D texture: floor(log2(max(w, h, d))) + 1
-	uint32_t max_levels = 1, big = width > height ? width : height;
-	big = big > depth ? big : depth;
-	for (uint32_t d = big; d > 1; d >>= 1)
-		++max_levels;
-	if (levels > max_levels)
-		return fail(ctx, CFHIP_E_INVALID, "%u mip levels requested, a %ux%ux%u texture has %u", levels,
-			width, height, depth, max_levels);
-	const size_t texel = src_pixel_type == CFHIP_PIXEL_RGBA8 ? 4 : (src_pixel_type == CFHIP_PIXEL_RGBA32F ? 16 : 8);
-	if (src_pitch_bytes < (size_t)width*texel || src_slice_pitch_bytes < src_pitch_bytes*height)
-		return fail(ctx, CFHIP_E_INVALID, "3-D mip generation: pitch smaller than a row / slice");
+	int rc = check_mip_args(ctx, "3-D mip generation", src_pixel_type, color_space, filter, width, height, depth,
+		levels, src_pitch_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (src_slice_pitch_bytes < src_pitch_bytes*height)
+		return fail(ctx, CFHIP_E_INVALID, "3-D mip generation: slice pitch smaller than a slice");
+	for (uint32_t k = 1; k < levels; ++k)
+		if (!dst_levels[k - 1])
+			return fail(ctx, CFHIP_E_INVALID, "3-D mip generation: dst_levels[%u] is NULL", k - 1);
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream;
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	const hipStream_t stream = lease.stream;
 	const int srgb = color_space == CFHIP_COLOR_SRGB ? 1 : 0;
 	// level k (Texture.cpp:1345-1402): every slice of level k-1 is resized to the level's width and
 	// height with Image::resize, then generateMips3d interpolates the slices along the depth
@@ -1825,32 +1760,25 @@ int cfhip_generate_mips3d_device(cfhip_ctx* ctx, const void* src, int src_pixel_
 	int prev_type = src_pixel_type;
 	size_t prev_pitch = src_pitch_bytes, prev_slice = src_slice_pitch_bytes;
 	uint32_t pw = width, ph = height, pd = depth;
-	// the slice buffer is a context buffer like the staging buffers: ordered by the same event
-	bool used_staging = levels > 1;
-	if (used_staging) {
-		const int rc = staging_acquire(ctx, stream);
-		if (rc != CFHIP_OK) return rc;
-	}
 	for (uint32_t k = 1; k < levels; ++k) {
-		if (!dst_levels[k - 1])
-			return staging_abort(ctx, stream, used_staging,
-				fail(ctx, CFHIP_E_INVALID, "3-D mip generation: dst_levels[%u] is NULL", k - 1));
 		const uint32_t w = (width >> k) ? (width >> k) : 1u, h = (height >> k) ? (height >> k) : 1u,
 			d = (depth >> k) ? (depth >> k) : 1u;
 		const size_t slice_bytes = (size_t)w*h*16u;
-		int rc = reserve(ctx, &ctx->d_mip3d, &ctx->mip3d_cap, slice_bytes*pd);
+		// the slice buffer is a context buffer like the staging buffers: owned through the same lease
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_mip3d, &ctx->mip3d_cap, slice_bytes*pd);
 		if (rc != CFHIP_OK)
-			return staging_abort(ctx, stream, used_staging, rc);
+			return rc;
 		for (uint32_t i = 0; i < pd; ++i) {
 			uint8_t* dst = static_cast<uint8_t*>(ctx->d_mip3d) + slice_bytes*i;
 			if (w == pw && h == ph)    // Image::resize returns a copy (Image.cpp:1330-1334): an exact Box identity
 				HIP_TRY(ctx, cfhip_launch_mip_resize(prev + prev_slice*i, prev_type, prev_pitch, pw, ph, dst, w, h,
 					CFHIP_FILTER_BOX, 0, stream));
 			else {
-				rc = mip_level_2d(ctx, prev + prev_slice*i, prev_type, prev_pitch, pw, ph, dst, w, h, filter, srgb,
-					stream, &used_staging);
+				rc = mip_level_2d(ctx, lease, prev + prev_slice*i, prev_type, prev_pitch, pw, ph, dst, w, h, filter, srgb);
 				if (rc != CFHIP_OK)
-					return staging_abort(ctx, stream, used_staging, rc);
+					return rc;
 			}
 		}
 		HIP_TRY(ctx, cfhip_launch_mip_depth(ctx->d_mip3d, pd, w*h, dst_levels[k - 1], d,
@@ -1861,18 +1789,7 @@ int cfhip_generate_mips3d_device(cfhip_ctx* ctx, const void* src, int src_pixel_
 		prev_slice = slice_bytes;
 		pw = w; ph = h; pd = d;
 	}
-	if (used_staging) {
-		const int rc = staging_release(ctx, stream);
-		if (rc != CFHIP_OK) return rc;
-	}
-	if (!stream_) {
-		HIP_TRY(ctx, hipStreamSynchronize(stream));
-		// the staging buffers are idle only if THIS stream was their last user (an earlier
-		// asynchronous call on another stream may still have d_src / d_batch / d_mip3d in flight)
-		if (used_staging || ctx->staging_stream == stream)
-			ctx->staging_busy = false;
-	}
-	return CFHIP_OK;
+	return lease.done(!stream_);
 }
 
 float cfhip_last_kernel_ms(cfhip_ctx* ctx)

@@ -265,3 +265,32 @@ def test_array_call_rejects_bad_arguments():
             ctx.generate_mips_array_device([a.data_ptr()], PixelType.RGBA8, 8, 8, 32, [[0]])          # NULL level
         with pytest.raises(CfhipError):
             ctx.generate_mips_array_device([a.data_ptr()], PixelType.RGBA8, 8, 8, 16, [[d.data_ptr()]])   # pitch < row
+
+
+@pytest.mark.parametrize("repeat", range(5))
+def test_failed_call_keeps_another_streams_claim_on_the_staging_buffers(repeat):
+    """A resize on a caller's stream A leaves its two passes through the context's staging image in flight; an
+    encode that fails its argument check in between never touched the staging buffers and must not hand them back,
+    so the next resize, on stream B, still waits for A before it writes that image.  Same sizes throughout: the
+    staging image is never reallocated while work is in flight."""
+    from cuttlefish_amd import ResizeFilter
+    rng = np.random.default_rng(1000 + repeat)
+    n, w, h = 4096, 3000, 2000                       # Catmull-Rom, both sizes change: two passes via the staging image
+    srcs = [torch.from_numpy(rng.integers(0, 256, (n, n, 4), dtype=np.uint8)).cuda() for _ in range(2)]
+    refs = [torch.empty((h, w, 4), dtype=torch.float32, device="cuda") for _ in range(2)]
+    outs = [torch.empty_like(r) for r in refs]
+    torch.cuda.synchronize()
+    with Context(0) as ctx:
+        def resize(i, dst, stream):
+            ctx.resize_device(srcs[i].data_ptr(), PixelType.RGBA8, n, n, n*4, dst.data_ptr(), w, h,
+                              filter=ResizeFilter.CatmullRom, stream=stream)
+        for i in range(2):
+            resize(i, refs[i], 0)                    # synchronous: the references
+        a, b = torch.cuda.Stream(), torch.cuda.Stream()
+        resize(0, outs[0], a.cuda_stream)            # not synchronised
+        with pytest.raises(CfhipError):
+            ctx.encode([synth.photo(16, 16, seed=1)], make_params(Format.BC7, Type.UNorm, 9))   # quality 9
+        resize(1, outs[1], b.cuda_stream)
+        torch.cuda.synchronize()
+    for o, r in zip(outs, refs):
+        assert torch.equal(o.view(torch.int32), r.view(torch.int32))
