@@ -134,7 +134,30 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_shard_rows",
            "cfhip_last_kernel_ms", "cfhip_last_kernel_name", "cfhip_last_error", "cfhip_pinned_bytes",
            "cfhip_profile_begin", "cfhip_profile_end", "cfhip_generate_mips_device",
-           "cfhip_generate_mips3d_device", "cfhip_resize_device", "cfhip_generate_mips_array_device"]
+           "cfhip_generate_mips3d_device", "cfhip_resize_device", "cfhip_generate_mips_array_device",
+           "cfhip_decoded_layout", "cfhip_decode", "cfhip_decode_device", "cfhip_decode_sse",
+           "cfhip_decode_sse_device"]
+
+
+class Layout(enum.IntEnum):
+    """Decoded texel layouts (enum cfhip_layout)."""
+    RGBA8 = 0
+    R8 = 1
+    R8_SNorm = 2
+    RG8 = 3
+    RG8_SNorm = 4
+    R16 = 5
+    R16_SNorm = 6
+    RG16 = 7
+    RG16_SNorm = 8
+    RGBA16F = 9
+
+
+# layout -> (channels, numpy dtype) of the decoded array
+LAYOUT_ARRAY = {Layout.RGBA8: (4, np.uint8), Layout.R8: (1, np.uint8), Layout.R8_SNorm: (1, np.int8),
+                Layout.RG8: (2, np.uint8), Layout.RG8_SNorm: (2, np.int8), Layout.R16: (1, np.uint16),
+                Layout.R16_SNorm: (1, np.int16), Layout.RG16: (2, np.uint16), Layout.RG16_SNorm: (2, np.int16),
+                Layout.RGBA16F: (4, np.float16)}
 
 
 class Params(ctypes.Structure):
@@ -231,6 +254,24 @@ def load_library(path: Optional[str] = None):
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t,
         ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
     L.cfhip_resize_device.restype = ctypes.c_int
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    L.cfhip_decoded_layout.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int),
+                                       ctypes.POINTER(ctypes.c_int)]
+    L.cfhip_decoded_layout.restype = ctypes.c_int
+    L.cfhip_decode.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                               ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, u64p]
+    L.cfhip_decode.restype = ctypes.c_int
+    L.cfhip_decode_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32,
+                                      ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                      ctypes.c_void_p]
+    L.cfhip_decode_device.restype = ctypes.c_int
+    L.cfhip_decode_sse.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                   ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, u64p]
+    L.cfhip_decode_sse.restype = ctypes.c_int
+    L.cfhip_decode_sse_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t,
+                                          ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_decode_sse_device.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -259,6 +300,24 @@ def query(fmt, typ=Type.UNorm):
 def payload_size(fmt, typ, width: int, height: int) -> int:
     bw, bh, bs = query(fmt, typ)
     return ((width + bw - 1) // bw) * ((height + bh - 1) // bh) * bs
+
+
+def decoded_layout(fmt, typ=Type.UNorm):
+    """(Layout, bytes per texel) of what decoding a (format, type) payload returns; raises for the standard
+    formats and the pairs query() rejects."""
+    lay, tb = ctypes.c_int(), ctypes.c_int()
+    rc = load_library().cfhip_decoded_layout(int(fmt), int(typ), lay, tb)
+    if rc != 0:
+        raise CfhipError(rc, "no decoded layout for (format, type) = (%r, %r)" % (fmt, typ))
+    return Layout(lay.value), tb.value
+
+
+def psnr_from_sse(sse, n_texels: int, channels: int = 3) -> float:
+    """PSNR (dB, peak 255) of the first `channels` sums of a decode_sse result over n_texels texels."""
+    total = sum(int(v) for v in list(sse)[:channels])
+    if total == 0:
+        return float("inf")
+    return 10.0 * float(np.log10(255.0 * 255.0 * n_texels * channels / total))
 
 
 def shard_rows(block_rows: int, rank: int, world: int):
@@ -423,6 +482,49 @@ class Context:
             self._h, ctypes.c_void_p(int(src)), int(pixel_type), width, height, row_pitch_bytes,
             int(color_space), int(filter), ctypes.c_void_p(int(dst)), dst_width, dst_height,
             ctypes.c_void_p(stream) if stream else None))
+
+    def decode(self, payload: np.ndarray, fmt, typ, width: int, height: int):
+        """Decode a payload on the GPU -> ((height, width, C) array in the layout's dtype, error blocks).
+        RGBA16F layouts come back as float16 (the bit patterns the decoder produced)."""
+        layout, tb = decoded_layout(fmt, typ)
+        ch, dt = LAYOUT_ARRAY[layout]
+        blocks = np.ascontiguousarray(payload, dtype=np.uint8)
+        out = np.empty((height, width, ch), dt)
+        bad = ctypes.c_uint64(0)
+        self._check(self._lib.cfhip_decode(self._h, int(fmt), int(typ), blocks.ctypes.data, blocks.nbytes, width,
+                                           height, out.ctypes.data, out.nbytes, ctypes.byref(bad)))
+        return out, int(bad.value)
+
+    def decode_device(self, blocks: int, fmt, typ, width: int, height: int, out: int, out_pitch_bytes: int,
+                      error_blocks: int = 0, stream: int = 0):
+        """Device path: blocks / out / error_blocks (one uint64, zeroed by the call; 0 = not counted) are device
+        pointers as ints.  stream 0 = the context's stream (the call then synchronises)."""
+        self._check(self._lib.cfhip_decode_device(
+            self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(out)),
+            out_pitch_bytes, ctypes.c_void_p(int(error_blocks)) if error_blocks else None,
+            ctypes.c_void_p(stream) if stream else None))
+
+    def decode_sse(self, payload: np.ndarray, ref: np.ndarray, fmt, typ=Type.UNorm):
+        """Per-channel sums of squared differences between the decoded payload and an (h, w, 4) uint8
+        reference (its size is the surface's); 4 ints, 0 for channels the layout lacks."""
+        ref = np.asarray(ref)
+        if ref.ndim != 3 or ref.shape[2] != 4 or ref.dtype != np.uint8:
+            raise ValueError("reference must be (h, w, 4) uint8")
+        if ref.strides[2] != 1 or ref.strides[1] != 4:
+            ref = np.ascontiguousarray(ref)
+        h, w = ref.shape[:2]
+        blocks = np.ascontiguousarray(payload, dtype=np.uint8)
+        sse = (ctypes.c_uint64 * 4)()
+        self._check(self._lib.cfhip_decode_sse(self._h, int(fmt), int(typ), blocks.ctypes.data, blocks.nbytes, w, h,
+                                               ref.ctypes.data, ref.strides[0], sse))
+        return [int(v) for v in sse]
+
+    def decode_sse_device(self, blocks: int, fmt, typ, width: int, height: int, ref: int, ref_pitch_bytes: int,
+                          sse: int, stream: int = 0):
+        """Device path of decode_sse: sse = device pointer to four uint64 (zeroed by the call)."""
+        self._check(self._lib.cfhip_decode_sse_device(
+            self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(ref)),
+            ref_pitch_bytes, ctypes.c_void_p(int(sse)), ctypes.c_void_p(stream) if stream else None))
 
     def last_kernel_ms(self) -> float:
         return float(self._lib.cfhip_last_kernel_ms(self._h))

@@ -114,7 +114,10 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 LLVM_BIN = "/opt/rocm/lib/llvm/bin"
 BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_bc6h_encode_kernel",
-                 "cfhip_etc_encode_kernel", "cfhip_astc_encode_kernel")
+                 "cfhip_etc_encode_kernel", "cfhip_astc_encode_kernel",
+                 # the decoders (csrc/decode.hip): every cfhip_decode_*_kernel, the fused SSE ones included
+                 "cfhip_decode_block_kernel", "cfhip_decode_astc_kernel", "cfhip_decode_sse_block_kernel",
+                 "cfhip_decode_sse_astc_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

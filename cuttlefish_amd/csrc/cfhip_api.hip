@@ -52,6 +52,9 @@ extern "C" hipError_t cfhip_launch_mip_depth(const void* prev, uint32_t n_prev, 
 	uint32_t depth, int box, int srgb, hipStream_t stream);
 extern "C" hipError_t cfhip_launch_std_pack(const cf_kparams* kp, int pixel_type, int bytes_per_pixel,
 	hipStream_t stream);
+extern "C" hipError_t cfhip_launch_decode(int format, int type, const void* blocks, int blk_vec, void* out,
+	size_t out_pitch, const void* ref, size_t ref_pitch, int out_vec, uint32_t width, uint32_t height,
+	uint32_t bx, uint32_t by, int bw, int bh, unsigned long long* acc, int sse, hipStream_t stream);
 extern "C" hipError_t cfhip_launch_bc15(const cf_kparams* kp, int format, int pixel_type,
 	int snorm, hipStream_t stream);
 
@@ -988,6 +991,94 @@ int encode_strip_pipeline(cfhip_ctx* ctx, StagingLease& lease, const cfhip_surfa
 	return rc;
 }
 
+
+// ---- decoding (csrc/decode.hip) ------------------------------------------------------------------
+// decoded texel layout of a block (format, type) pair: false for the standard formats and the illegal pairs
+bool decoded_layout(int format, int type, int* layout, int* texel_bytes)
+{
+	if (is_std_format(format) || !block_bytes(format) || !type_valid(format, type))
+		return false;
+	const bool sn = type == CFHIP_TYPE_SNORM;
+	int l = CFHIP_LAYOUT_RGBA8, tb = 4;
+	switch (format) {
+		case CFHIP_FORMAT_BC4: l = sn ? CFHIP_LAYOUT_R8_SNORM : CFHIP_LAYOUT_R8; tb = 1; break;
+		case CFHIP_FORMAT_BC5: l = sn ? CFHIP_LAYOUT_RG8_SNORM : CFHIP_LAYOUT_RG8; tb = 2; break;
+		case CFHIP_FORMAT_EAC_R11: l = sn ? CFHIP_LAYOUT_R16_SNORM : CFHIP_LAYOUT_R16; tb = 2; break;
+		case CFHIP_FORMAT_EAC_R11G11: l = sn ? CFHIP_LAYOUT_RG16_SNORM : CFHIP_LAYOUT_RG16; tb = 4; break;
+		case CFHIP_FORMAT_BC6H: l = CFHIP_LAYOUT_RGBA16F; tb = 8; break;
+		default:
+			if (format >= CFHIP_FORMAT_ASTC_4x4 && type == CFHIP_TYPE_UFLOAT) {
+				l = CFHIP_LAYOUT_RGBA16F;
+				tb = 8;
+			}
+			break;
+	}
+	*layout = l;
+	*texel_bytes = tb;
+	return true;
+}
+
+struct DecodeGeom {
+	int layout, texel_bytes, bw, bh, bb;
+	uint32_t bx, by;
+	size_t payload_bytes;
+};
+
+// the checks every decode entry point makes before anything is enqueued
+int decode_check(cfhip_ctx* ctx, const char* what, int format, int type, const void* blocks, uint32_t width,
+	uint32_t height, bool sse, DecodeGeom* g)
+{
+	if (!decoded_layout(format, type, &g->layout, &g->texel_bytes))
+		return fail(ctx, CFHIP_E_UNSUPPORTED, "%s: (format %d, type %d) has no decoded layout", what, format, type);
+	if (sse && g->layout != CFHIP_LAYOUT_RGBA8 && g->layout != CFHIP_LAYOUT_R8 && g->layout != CFHIP_LAYOUT_RG8)
+		return fail(ctx, CFHIP_E_UNSUPPORTED, "%s: SSE covers the RGBA8, R8 and RG8 layouts only (format %d, type %d)",
+			what, format, type);
+	if (!blocks)
+		return fail(ctx, CFHIP_E_INVALID, "%s: blocks is NULL", what);
+	if (!width || !height)
+		return fail(ctx, CFHIP_E_INVALID, "%s: empty surface %ux%u", what, width, height);
+	block_dims(format, &g->bw, &g->bh);
+	g->bb = block_bytes(format);
+	g->bx = (width + (uint32_t)g->bw - 1)/(uint32_t)g->bw;
+	g->by = (height + (uint32_t)g->bh - 1)/(uint32_t)g->bh;
+	g->payload_bytes = (size_t)g->bx*g->by*(size_t)g->bb;
+	// launch geometry: ASTC runs one workgroup row per block row (grid y), the 4x4 kernels one lane per block
+	if ((format >= CFHIP_FORMAT_ASTC_4x4 && g->by > 65535u) || (uint64_t)g->bx*g->by > (1ull << 38))
+		return fail(ctx, CFHIP_E_INVALID, "%s: surface %ux%u too large for one launch", what, width, height);
+	return CFHIP_OK;
+}
+
+// one decode (or decode + SSE) launch, timed like every encode launch (cfhip_last_kernel_ms / profiling)
+int decode_launch(cfhip_ctx* ctx, int format, int type, const DecodeGeom& g, const void* blocks, void* out,
+	size_t out_pitch, const void* ref, size_t ref_pitch, uint32_t width, uint32_t height, unsigned long long* acc,
+	bool sse, hipStream_t stream)
+{
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	const bool astc = format >= CFHIP_FORMAT_ASTC_4x4;
+	ctx->last_kernel = sse ? (astc ? "cfhip_decode_sse_astc_kernel" : "cfhip_decode_sse_block_kernel")
+		: (astc ? "cfhip_decode_astc_kernel" : "cfhip_decode_block_kernel");
+	const uintptr_t op = sse ? (uintptr_t)ref : (uintptr_t)out;
+	const size_t pitch = sse ? ref_pitch : out_pitch;
+	// decode: 16-byte row stores need a 16-byte aligned output; SSE: word loads of the reference need 4 bytes
+	const int align = sse ? 4 : 16;
+	const int out_vec = (op % align == 0 && pitch % align == 0) ? 1 : 0;
+	const int blk_vec = ((uintptr_t)blocks % (uintptr_t)g.bb == 0) ? 1 : 0;
+	hipEvent_t a, b;
+	int rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, stream));
+	const hipError_t e = cfhip_launch_decode(format, type, blocks, blk_vec, out, out_pitch, ref, ref_pitch, out_vec,
+		width, height, g.bx, g.by, g.bw, g.bh, acc, sse ? 1 : 0, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "decode launch: %s", hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, stream));
+	return CFHIP_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1789,6 +1880,171 @@ int cfhip_generate_mips3d_device(cfhip_ctx* ctx, const void* src, int src_pixel_
 		prev_slice = slice_bytes;
 		pw = w; ph = h; pd = d;
 	}
+	return lease.done(!stream_);
+}
+
+int cfhip_decoded_layout(int format, int type, int* layout, int* texel_bytes)
+{
+	int l, tb;
+	if (!decoded_layout(format, type, &l, &tb))
+		return CFHIP_E_UNSUPPORTED;
+	if (layout) *layout = l;
+	if (texel_bytes) *texel_bytes = tb;
+	return CFHIP_OK;
+}
+
+int cfhip_decode(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes, uint32_t width,
+	uint32_t height, void* out, size_t out_capacity, uint64_t* error_blocks)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	DecodeGeom g;
+	int rc = decode_check(ctx, "decode", format, type, blocks, width, height, false, &g);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!out)
+		return fail(ctx, CFHIP_E_INVALID, "decode: out is NULL");
+	if (blocks_bytes < g.payload_bytes)
+		return fail(ctx, CFHIP_E_INVALID, "decode: blocks_bytes %zu < %zu for %ux%u", blocks_bytes, g.payload_bytes,
+			width, height);
+	const size_t out_bytes = (size_t)width*height*(size_t)g.texel_bytes;
+	if (out_capacity < out_bytes)
+		return fail(ctx, CFHIP_E_CAPACITY, "decode: out_capacity %zu < %zu", out_capacity, out_bytes);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, ctx->stream);
+	const hipStream_t stream = lease.stream;
+	// d_src: the payload; d_out: the texels, then the error-block counter
+	const size_t cnt_off = (out_bytes + 15u) & ~(size_t)15u;
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, g.payload_bytes);
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, cnt_off + 8u);
+	if (rc != CFHIP_OK)
+		return rc;
+	unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(ctx->d_out) + cnt_off);
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, g.payload_bytes, hipMemcpyHostToDevice, stream));
+	HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 8, stream));
+	rc = decode_launch(ctx, format, type, g, ctx->d_src, ctx->d_out, (size_t)width*(size_t)g.texel_bytes, nullptr, 0,
+		width, height, d_cnt, false, stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	unsigned long long count = 0;
+	HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+	HIP_TRY(ctx, hipMemcpyAsync(&count, d_cnt, 8, hipMemcpyDeviceToHost, stream));
+	rc = lease.done(true);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (error_blocks)
+		*error_blocks = (uint64_t)count;
+	return CFHIP_OK;
+}
+
+int cfhip_decode_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width, uint32_t height,
+	void* out, size_t out_pitch_bytes, uint64_t* error_blocks_device, void* stream_)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	DecodeGeom g;
+	int rc = decode_check(ctx, "decode_device", format, type, blocks, width, height, false, &g);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!out)
+		return fail(ctx, CFHIP_E_INVALID, "decode_device: out is NULL");
+	if (out_pitch_bytes < (size_t)width*(size_t)g.texel_bytes)
+		return fail(ctx, CFHIP_E_INVALID, "decode_device: out pitch %zu < %zu", out_pitch_bytes,
+			(size_t)width*(size_t)g.texel_bytes);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	// no staging buffer is touched: the lease only carries the synchronisation rule of the stream
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	unsigned long long* cnt = reinterpret_cast<unsigned long long*>(error_blocks_device);
+	if (cnt)
+		HIP_TRY(ctx, hipMemsetAsync(cnt, 0, 8, lease.stream));
+	rc = decode_launch(ctx, format, type, g, blocks, out, out_pitch_bytes, nullptr, 0, width, height, cnt, false,
+		lease.stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	return lease.done(!stream_);
+}
+
+int cfhip_decode_sse(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes, uint32_t width,
+	uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t sse[4])
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	DecodeGeom g;
+	int rc = decode_check(ctx, "decode_sse", format, type, blocks, width, height, true, &g);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!ref_rgba8 || !sse)
+		return fail(ctx, CFHIP_E_INVALID, "decode_sse: NULL reference or result");
+	if (blocks_bytes < g.payload_bytes)
+		return fail(ctx, CFHIP_E_INVALID, "decode_sse: blocks_bytes %zu < %zu for %ux%u", blocks_bytes,
+			g.payload_bytes, width, height);
+	const size_t row = (size_t)width*4u;
+	if (ref_pitch_bytes < row)
+		return fail(ctx, CFHIP_E_INVALID, "decode_sse: reference pitch %zu < %zu", ref_pitch_bytes, row);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, ctx->stream);
+	const hipStream_t stream = lease.stream;
+	// d_src: the payload; d_out: the reference, tightly packed, then the four sums
+	const size_t sum_off = (row*height + 15u) & ~(size_t)15u;
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, g.payload_bytes);
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, sum_off + 32u);
+	if (rc != CFHIP_OK)
+		return rc;
+	unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(ctx->d_out) + sum_off);
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, g.payload_bytes, hipMemcpyHostToDevice, stream));
+	HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_out, row, ref_rgba8, ref_pitch_bytes, row, height, hipMemcpyHostToDevice,
+		stream));
+	HIP_TRY(ctx, hipMemsetAsync(d_sum, 0, 32, stream));
+	rc = decode_launch(ctx, format, type, g, ctx->d_src, nullptr, 0, ctx->d_out, row, width, height, d_sum, true,
+		stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	unsigned long long sums[4] = {0, 0, 0, 0};
+	HIP_TRY(ctx, hipMemcpyAsync(sums, d_sum, 32, hipMemcpyDeviceToHost, stream));
+	rc = lease.done(true);
+	if (rc != CFHIP_OK)
+		return rc;
+	for (int c = 0; c < 4; ++c)
+		sse[c] = (uint64_t)sums[c];
+	return CFHIP_OK;
+}
+
+int cfhip_decode_sse_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width,
+	uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t* sse_device, void* stream_)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	DecodeGeom g;
+	int rc = decode_check(ctx, "decode_sse_device", format, type, blocks, width, height, true, &g);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!ref_rgba8 || !sse_device)
+		return fail(ctx, CFHIP_E_INVALID, "decode_sse_device: NULL reference or result");
+	if (ref_pitch_bytes < (size_t)width*4u)
+		return fail(ctx, CFHIP_E_INVALID, "decode_sse_device: reference pitch %zu < %zu", ref_pitch_bytes,
+			(size_t)width*4u);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	unsigned long long* sum = reinterpret_cast<unsigned long long*>(sse_device);
+	HIP_TRY(ctx, hipMemsetAsync(sum, 0, 32, lease.stream));
+	rc = decode_launch(ctx, format, type, g, blocks, nullptr, 0, ref_rgba8, ref_pitch_bytes, width, height, sum, true,
+		lease.stream);
+	if (rc != CFHIP_OK)
+		return rc;
 	return lease.done(!stream_);
 }
 

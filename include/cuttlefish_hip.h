@@ -304,7 +304,74 @@ int cfhip_generate_mips3d_device(cfhip_ctx* ctx, const void* src, int src_pixel_
 int cfhip_shard_rows(uint32_t block_rows, int rank, int world, uint32_t* row_begin,
 	uint32_t* row_end);
 
-/* Kernel-only time of the most recent cfhip_encode or cfhip_encode_device call on
+/* ---- Decoding: the payload of every block format back to texels, on the GPU ----
+ *
+ * Output is bit-identical to the project's CPU reference decoders, which are pinned to Pillow (BC1-5, BC7)
+ * and Mesa 23.2.1 (ETC2, EAC, BC7, BC6H, ASTC) through committed fixtures.  Every legal block decodes, also
+ * encodings this library never emits (all ASTC block modes, grids and partition seeds).
+ * Texels are row-major, top-down; partial edge blocks write only the texels inside width x height.
+ * Colour space: the stored values are returned.  No sRGB transfer is applied and ASTC's sRGB decode mode is
+ * not modelled (an sRGB payload decodes to its sRGB-encoded values).
+ *
+ * Decoded layouts (cfhip_decoded_layout):
+ *   BC1, BC1A, BC2, BC3, BC7, ETC1, ETC2 x3, ASTC UNorm   RGBA8              4 bytes per texel
+ *   BC4 UNorm / SNorm                                      R8 / R8 signed     1
+ *   BC5 UNorm / SNorm                                      RG8 / RG8 signed   2
+ *   EAC R11 / RG11 UNorm / SNorm                           R16 / RG16 holding the 11-bit value,
+ *                                                          0..2047 or -1023..1023          2 / 4
+ *   BC6H UFloat / Float, ASTC UFloat                       RGBA16F bit patterns (BC6H alpha 1.0)   8
+ * BC1 three-colour blocks decode index 3 to transparent black.  ASTC: an illegal block decodes to magenta
+ * (LDR) or to 0xFFFF halves (HDR); under the LDR profile a partition with HDR endpoints decodes to magenta.
+ *
+ * Error blocks: the blocks whose reference decoder reports an error -- BC6H reserved modes, ASTC illegal
+ * blocks and (LDR profile) ASTC blocks with a texel in a partition with HDR endpoints.  0 for the other
+ * formats.
+ *
+ * Stream and error rules are those of the encode entry points: stream == NULL means the context's stream and
+ * the call synchronises; every argument is checked before anything is enqueued. */
+enum cfhip_layout {
+	CFHIP_LAYOUT_RGBA8 = 0,
+	CFHIP_LAYOUT_R8 = 1,
+	CFHIP_LAYOUT_R8_SNORM = 2,
+	CFHIP_LAYOUT_RG8 = 3,
+	CFHIP_LAYOUT_RG8_SNORM = 4,
+	CFHIP_LAYOUT_R16 = 5,           /* EAC R11 unsigned, 0..2047 */
+	CFHIP_LAYOUT_R16_SNORM = 6,     /* EAC R11 signed, -1023..1023 */
+	CFHIP_LAYOUT_RG16 = 7,
+	CFHIP_LAYOUT_RG16_SNORM = 8,
+	CFHIP_LAYOUT_RGBA16F = 9
+};
+
+/* Decoded texel layout of a block (format, type) pair; CFHIP_E_UNSUPPORTED for the standard formats and for
+ * the pairs cfhip_query rejects.  Pure, needs no device. */
+int cfhip_decoded_layout(int format, int type, int* layout, int* texel_bytes);
+
+/* Host buffers: blocks (blocks_bytes >= the payload size of width x height) -> out, width * height texels
+ * tightly packed (out_capacity >= width * height * texel_bytes, else CFHIP_E_CAPACITY).  error_blocks
+ * (optional) receives the number of error blocks.  Blocking. */
+int cfhip_decode(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes,
+	uint32_t width, uint32_t height, void* out, size_t out_capacity, uint64_t* error_blocks);
+
+/* Device buffers: blocks and out are device pointers on ctx's GPU, out rows out_pitch_bytes apart
+ * (>= width * texel_bytes).  error_blocks_device: one uint64 on the device, zeroed by the call on the stream
+ * and then receiving the count; NULL: not counted. */
+int cfhip_decode_device(cfhip_ctx* ctx, int format, int type, const void* blocks,
+	uint32_t width, uint32_t height, void* out, size_t out_pitch_bytes,
+	uint64_t* error_blocks_device, void* stream);
+
+/* Decode and compare in one pass, without writing texels: sse[c] = the exact sum over the width x height
+ * texels of (decoded - reference)^2 of channel c.  ref_rgba8: RGBA8 rows ref_pitch_bytes apart
+ * (>= width * 4).  Layouts RGBA8, and R8 / RG8 (BC4 / BC5 UNorm), which compare R (and G) and report 0 for
+ * the absent channels; every other pair is CFHIP_E_UNSUPPORTED. */
+int cfhip_decode_sse(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes,
+	uint32_t width, uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t sse[4]);
+
+/* The same on device buffers: sse_device = four uint64 on the device, zeroed by the call on the stream. */
+int cfhip_decode_sse_device(cfhip_ctx* ctx, int format, int type, const void* blocks,
+	uint32_t width, uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes,
+	uint64_t* sse_device, void* stream);
+
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device or cfhip_decode* call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
