@@ -118,6 +118,45 @@ class ResizeFilter(enum.IntEnum):
     BSpline = 4
 
 
+class Channel(enum.IntEnum):
+    """cuttlefish::Image::Channel (Image.h:104-111)."""
+    Red = 0
+    Green = 1
+    Blue = 2
+    Alpha = 3
+    None_ = 4
+
+
+class RotateAngle(enum.IntEnum):
+    """cuttlefish::Image::RotateAngle (Image.h:91-99)."""
+    CW90 = 0
+    CW180 = 1
+    CW270 = 2
+    CCW90 = 3
+    CCW180 = 4
+    CCW270 = 5
+
+
+class NormalOptions(enum.IntFlag):
+    """cuttlefish::Image::NormalOptions (Image.h:116-122), a bit mask."""
+    Default = 0
+    KeepSign = 1
+    WrapX = 2
+    WrapY = 4
+
+
+class ImageOp(enum.IntFlag):
+    """The op bits of ImageOps.ops (enum cfhip_image_op); a call runs them in this order."""
+    ColorSpace = 1 << 0
+    Rotate = 1 << 1
+    Grayscale = 1 << 2
+    NormalMap = 1 << 3
+    FlipX = 1 << 4
+    FlipY = 1 << 5
+    Swizzle = 1 << 6
+    PreMultiply = 1 << 7
+
+
 class PixelType(enum.IntEnum):
     RGBA8 = 0
     RGBA32F = 1
@@ -136,7 +175,7 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_profile_begin", "cfhip_profile_end", "cfhip_generate_mips_device",
            "cfhip_generate_mips3d_device", "cfhip_resize_device", "cfhip_generate_mips_array_device",
            "cfhip_decoded_layout", "cfhip_decode", "cfhip_decode_device", "cfhip_decode_sse",
-           "cfhip_decode_sse_device"]
+           "cfhip_decode_sse_device", "cfhip_image_ops_device"]
 
 
 class Layout(enum.IntEnum):
@@ -171,6 +210,30 @@ class Surface(ctypes.Structure):
                 ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
                 ("row_pitch_bytes", ctypes.c_ssize_t), ("out", ctypes.c_void_p),
                 ("out_capacity", ctypes.c_size_t)]
+
+
+class ImageOps(ctypes.Structure):
+    """struct cfhip_image_ops"""
+    _fields_ = [("ops", ctypes.c_uint32), ("src_color_space", ctypes.c_int32), ("dst_color_space", ctypes.c_int32),
+                ("rotate", ctypes.c_int32), ("normal_options", ctypes.c_uint32), ("rgbf", ctypes.c_uint32),
+                ("normal_height", ctypes.c_double), ("swizzle", ctypes.c_int32 * 4)]
+
+
+def make_image_ops(ops=0, src_color_space=ColorSpace.Linear, dst_color_space=None, rotate=RotateAngle.CW90,
+                   normal_options=NormalOptions.Default, normal_height=1.0,
+                   swizzle=(Channel.Red, Channel.Green, Channel.Blue, Channel.Alpha), rgbf=False) -> ImageOps:
+    """An ImageOps descriptor; dst_color_space None = the image's own."""
+    o = ImageOps()
+    o.ops = int(ops)
+    o.src_color_space = int(src_color_space)
+    o.dst_color_space = int(src_color_space if dst_color_space is None else dst_color_space)
+    o.rotate = int(rotate)
+    o.normal_options = int(normal_options)
+    o.rgbf = 1 if rgbf else 0
+    o.normal_height = float(normal_height)
+    for i in range(4):
+        o.swizzle[i] = int(swizzle[i])
+    return o
 
 
 class CfhipError(RuntimeError):
@@ -272,6 +335,10 @@ def load_library(path: Optional[str] = None):
                                           ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t,
                                           ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_decode_sse_device.restype = ctypes.c_int
+    L.cfhip_image_ops_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32,
+                                         ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(ImageOps), ctypes.c_void_p,
+                                         ctypes.c_size_t, ctypes.c_void_p]
+    L.cfhip_image_ops_device.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -482,6 +549,16 @@ class Context:
             self._h, ctypes.c_void_p(int(src)), int(pixel_type), width, height, row_pitch_bytes,
             int(color_space), int(filter), ctypes.c_void_p(int(dst)), dst_width, dst_height,
             ctypes.c_void_p(stream) if stream else None))
+
+    def image_ops_device(self, src: int, pixel_type, width: int, height: int, row_pitch_bytes: int, ops: ImageOps,
+                         dst: int, dst_pitch_bytes: int, stream: int = 0):
+        """Image's pixel ops in one pass on device buffers (cfhip_image_ops_device): src (width x height texels of
+        pixel_type) -> dst (RGBA32F, height x width under a 90 / 270 degree rotation).  stream 0 = the context's
+        stream (the call then synchronises)."""
+        self._check(self._lib.cfhip_image_ops_device(
+            self._h, ctypes.c_void_p(int(src)) if src else None, int(pixel_type), width, height, row_pitch_bytes,
+            ctypes.byref(ops) if ops is not None else None, ctypes.c_void_p(int(dst)) if dst else None,
+            dst_pitch_bytes, ctypes.c_void_p(stream) if stream else None))
 
     def decode(self, payload: np.ndarray, fmt, typ, width: int, height: int):
         """Decode a payload on the GPU -> ((height, width, C) array in the layout's dtype, error blocks).

@@ -117,7 +117,9 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  "cfhip_etc_encode_kernel", "cfhip_astc_encode_kernel",
                  # the decoders (csrc/decode.hip): every cfhip_decode_*_kernel, the fused SSE ones included
                  "cfhip_decode_block_kernel", "cfhip_decode_astc_kernel", "cfhip_decode_sse_block_kernel",
-                 "cfhip_decode_sse_astc_kernel")
+                 "cfhip_decode_sse_astc_kernel",
+                 # the per-image pixel ops (csrc/image_ops.hip)
+                 "cfhip_image_ops_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

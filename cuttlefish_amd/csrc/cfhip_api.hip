@@ -48,6 +48,8 @@ extern "C" hipError_t cfhip_launch_mip_fused_layers(const void* src, int src_pix
 extern "C" hipError_t cfhip_launch_mip_pass(const void* src, int src_pixel_type, size_t pitch,
 	uint32_t src_n, void* dst, uint32_t dst_w, uint32_t dst_h, int along_x, int filter, int to_linear,
 	int to_srgb, hipStream_t stream);
+extern "C" hipError_t cfhip_launch_image_ops(const void* src, int src_pixel_type, size_t pitch, uint32_t w,
+	uint32_t h, const cfhip_image_ops* ops, void* dst, size_t dst_pitch, hipStream_t stream);
 extern "C" hipError_t cfhip_launch_mip_depth(const void* prev, uint32_t n_prev, uint32_t texels, void* dst,
 	uint32_t depth, int box, int srgb, hipStream_t stream);
 extern "C" hipError_t cfhip_launch_std_pack(const cf_kparams* kp, int pixel_type, int bytes_per_pixel,
@@ -1821,6 +1823,77 @@ int cfhip_resize_device(cfhip_ctx* ctx, const void* src, int src_pixel_type, uin
 			return rc;
 	}
 	return lease.done(!stream_);
+}
+
+// Image's pixel operations (csrc/image_ops.hip).  No staging buffer is touched, so no StagingLease: the call
+// only follows the stream rule itself.
+int cfhip_image_ops_device(cfhip_ctx* ctx, const void* src, int src_pixel_type, uint32_t w, uint32_t h,
+	size_t src_pitch_bytes, const cfhip_image_ops* ops, void* dst, size_t dst_pitch_bytes, void* stream_)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	if (!src || !dst || !ops)
+		return fail(ctx, CFHIP_E_INVALID, "image ops: src, dst or ops is NULL");
+	if (!w || !h)
+		return fail(ctx, CFHIP_E_INVALID, "image ops: empty image %ux%u", w, h);
+	if (w > (1u << 20) || h > (1u << 20))
+		return fail(ctx, CFHIP_E_INVALID, "image ops: image %ux%u too large for one launch", w, h);
+	if (src_pixel_type < CFHIP_PIXEL_RGBA8 || src_pixel_type > CFHIP_PIXEL_RGBA16F)
+		return fail(ctx, CFHIP_E_INVALID, "image ops: pixel type %d", src_pixel_type);
+	const uint32_t all_ops = CFHIP_IMAGE_OP_COLOR_SPACE | CFHIP_IMAGE_OP_ROTATE | CFHIP_IMAGE_OP_GRAYSCALE |
+		CFHIP_IMAGE_OP_NORMAL_MAP | CFHIP_IMAGE_OP_FLIP_X | CFHIP_IMAGE_OP_FLIP_Y | CFHIP_IMAGE_OP_SWIZZLE |
+		CFHIP_IMAGE_OP_PREMULTIPLY;
+	if (ops->ops & ~all_ops)
+		return fail(ctx, CFHIP_E_INVALID, "image ops: unknown op bits 0x%x", ops->ops & ~all_ops);
+	for (int cs : {ops->src_color_space, ops->dst_color_space})
+		if (cs != CFHIP_COLOR_LINEAR && cs != CFHIP_COLOR_SRGB)
+			return fail(ctx, CFHIP_E_INVALID, "image ops: colour space %d", cs);
+	if (ops->rotate < CFHIP_ROTATE_CW90 || ops->rotate > CFHIP_ROTATE_CCW270)
+		return fail(ctx, CFHIP_E_INVALID, "image ops: rotate angle %d", ops->rotate);
+	if (ops->normal_options & ~(uint32_t)(CFHIP_NORMAL_KEEP_SIGN | CFHIP_NORMAL_WRAP_X | CFHIP_NORMAL_WRAP_Y))
+		return fail(ctx, CFHIP_E_INVALID, "image ops: normal options 0x%x", ops->normal_options);
+	for (int c = 0; c < 4; ++c)
+		if (ops->swizzle[c] < CFHIP_CHANNEL_RED || ops->swizzle[c] > CFHIP_CHANNEL_NONE)
+			return fail(ctx, CFHIP_E_INVALID, "image ops: swizzle[%d] channel %d", c, ops->swizzle[c]);
+	if (ops->rgbf > 1u)
+		return fail(ctx, CFHIP_E_INVALID, "image ops: rgbf flag %u", ops->rgbf);
+	const size_t pb = pixel_bytes(src_pixel_type);
+	const bool quarter = (ops->ops & CFHIP_IMAGE_OP_ROTATE) && ops->rotate != CFHIP_ROTATE_CW180 &&
+		ops->rotate != CFHIP_ROTATE_CCW180;
+	const uint32_t rw = quarter ? h : w, rh = quarter ? w : h;
+	if (src_pitch_bytes < (size_t)w*pb)
+		return fail(ctx, CFHIP_E_INVALID, "image ops: source pitch %zu < %zu", src_pitch_bytes, (size_t)w*pb);
+	if (dst_pitch_bytes < (size_t)rw*16u)
+		return fail(ctx, CFHIP_E_INVALID, "image ops: destination pitch %zu < %zu", dst_pitch_bytes, (size_t)rw*16u);
+	// the kernel loads whole texels and stores float4
+	if ((uintptr_t)src % pb || src_pitch_bytes % pb || (uintptr_t)dst % 16u || dst_pitch_bytes % 16u)
+		return fail(ctx, CFHIP_E_INVALID, "image ops: src / dst or a pitch not aligned to its texel size");
+	const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)(h - 1u)*src_pitch_bytes + (size_t)w*pb;
+	const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)(rh - 1u)*dst_pitch_bytes + (size_t)rw*16u;
+	if (s0 < d1 && d0 < s1)
+		return fail(ctx, CFHIP_E_INVALID, "image ops: src and dst overlap");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	const hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream;
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = "cfhip_image_ops_kernel";
+	hipEvent_t a, b;
+	int rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, stream));
+	const hipError_t e = cfhip_launch_image_ops(src, src_pixel_type, src_pitch_bytes, w, h, ops, dst,
+		dst_pitch_bytes, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "image ops launch: %s", hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, stream));
+	if (!stream_)
+		HIP_TRY(ctx, hipStreamSynchronize(stream));
+	return CFHIP_OK;
 }
 
 int cfhip_generate_mips3d_device(cfhip_ctx* ctx, const void* src, int src_pixel_type,

@@ -15,40 +15,6 @@
 
 namespace {
 
-__device__ __forceinline__ double srgb_to_linear(double c)
-{
-	if (c <= 0.04045)
-		return c/12.92;
-	return pow((c + 0.055)/1.055, 2.4);
-}
-
-__device__ __forceinline__ double linear_to_srgb(double c)
-{
-	if (c <= 0.0031308)
-		return c*12.92;
-	return 1.055*pow(c, 1.0/2.4) - 0.055;
-}
-
-// source texel as the reference's RGBAF storage holds it
-template <int SRC_PIX>
-__device__ __forceinline__ float4 load_rgbaf(const uint8_t* row, uint32_t x)
-{
-	if (SRC_PIX == 0) {
-		const uint32_t p = *reinterpret_cast<const uint32_t*>(row + (size_t)x*4u);
-		// Image::convert RGBA8 -> RGBAF: toDoubleNorm (v/255.0, Image.cpp:293-296), float store
-		return make_float4((float)((double)(p & 255u)/255.0), (float)((double)((p >> 8) & 255u)/255.0),
-			(float)((double)((p >> 16) & 255u)/255.0), (float)((double)(p >> 24)/255.0));
-	} else if (SRC_PIX == 1) {
-		return *reinterpret_cast<const float4*>(row + (size_t)x*16u);
-	} else {
-		const uint2 h = *reinterpret_cast<const uint2*>(row + (size_t)x*8u);
-		union { unsigned short u; _Float16 f; } c0, c1, c2, c3;
-		c0.u = (unsigned short)(h.x & 0xFFFFu); c1.u = (unsigned short)(h.x >> 16);
-		c2.u = (unsigned short)(h.y & 0xFFFFu); c3.u = (unsigned short)(h.y >> 16);
-		return make_float4((float)c0.f, (float)c1.f, (float)c2.f, (float)c3.f);
-	}
-}
-
 template <int SRC_PIX>
 __global__ void __launch_bounds__(256)
 cfhip_mip_resize_kernel(const uint8_t* __restrict__ src, size_t pitch, uint32_t sw, uint32_t sh,

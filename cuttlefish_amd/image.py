@@ -1,0 +1,236 @@
+"""cuttlefish::Image's pixel operations (lib/src/Image.cpp:1513-1882) on the GPU, and the cuttlefish tool's per-image
+pipeline (tool/main.cpp:147-277, loadAndProcessImage) from a loaded image to the array Texture.set_image takes.
+
+Pixels are (h, w, 4) numpy arrays, row 0 at the top (Image::getPixel(x, 0)), uint8 / float16 / float32 read as the
+reference's RGBAF image (uint8 as v/255).  Every op runs in csrc/image_ops.hip (cfhip_image_ops_device) and
+returns RGBA32F; there is no CPU path.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import api
+from .api import Channel, ColorSpace, ImageOp, NormalOptions, ResizeFilter, RotateAngle, Type
+from .texture import ImageFormat, Texture
+
+_contexts: Dict[int, api.Context] = {}
+
+
+def _context(device_id: int) -> api.Context:
+    if device_id not in _contexts:
+        _contexts[device_id] = api.Context(device_id)
+    return _contexts[device_id]
+
+
+def _pixels(image) -> np.ndarray:
+    a = np.asarray(image)
+    if a.ndim != 3 or a.shape[2] != 4 or a.shape[0] == 0 or a.shape[1] == 0:
+        raise ValueError("expected an (h, w, 4) image, got shape %r" % (a.shape,))
+    if a.dtype not in (np.uint8, np.float16, np.float32):
+        a = a.astype(np.float32)
+    return a
+
+
+def _quarter(angle) -> bool:
+    return RotateAngle(angle) not in (RotateAngle.CW180, RotateAngle.CCW180)
+
+
+class _Device:
+    """The device calls of process_image and Image: upload, one fused ops pass, one resize, download.  Buffers
+    are torch tensors (plumbing only); a buffer is (tensor, pixel type, width, height, row pitch in bytes)."""
+
+    def __init__(self, device_id: int = 0):
+        self.ctx = _context(device_id)
+        self.device = "cuda:%d" % device_id
+
+    def upload(self, pixels: np.ndarray):
+        import torch
+        host = np.ascontiguousarray(pixels)
+        t = torch.from_numpy(host).to(self.device)
+        return (t, api.pixel_type_of(host), host.shape[1], host.shape[0], host.strides[0])
+
+    def ops(self, buf, ops: api.ImageOps):
+        import torch
+        t, pt, w, h, pitch = buf
+        rw, rh = (h, w) if (ops.ops & ImageOp.Rotate) and _quarter(ops.rotate) else (w, h)
+        dst = torch.empty((rh, rw, 4), dtype=torch.float32, device=t.device)
+        self.ctx.image_ops_device(t.data_ptr(), pt, w, h, pitch, ops, dst.data_ptr(), rw * 16)
+        return (dst, api.PixelType.RGBA32F, rw, rh, rw * 16)
+
+    def resize(self, buf, width: int, height: int, color_space, filter):
+        import torch
+        t, pt, w, h, pitch = buf
+        dst = torch.empty((height, width, 4), dtype=torch.float32, device=t.device)
+        self.ctx.resize_device(t.data_ptr(), pt, w, h, pitch, dst.data_ptr(), width, height,
+                               color_space=color_space, filter=int(filter))
+        return (dst, api.PixelType.RGBA32F, width, height, width * 16)
+
+    def download(self, buf) -> np.ndarray:
+        return buf[0].cpu().numpy()
+
+
+class Image:
+    """A numpy-backed mirror of cuttlefish::Image's pixel methods, under the reference's names.  Each op runs on
+    the GPU and leaves the pixels as an RGBA32F host array.  An RGBF image (what create_normal_map returns) keeps
+    alpha at 1: swizzle drops the alpha it would write and pre_multiply_alpha does nothing."""
+
+    def __init__(self, pixels, color_space: ColorSpace = ColorSpace.Linear, rgbf: bool = False, device_id: int = 0):
+        self.pixels = _pixels(pixels)
+        self.color_space = ColorSpace(color_space)
+        self.rgbf = bool(rgbf)
+        self.device_id = device_id
+
+    @property
+    def width(self) -> int:
+        return self.pixels.shape[1]
+
+    @property
+    def height(self) -> int:
+        return self.pixels.shape[0]
+
+    def _run(self, ops: int, **fields) -> np.ndarray:
+        d = _Device(self.device_id)
+        desc = api.make_image_ops(ops, self.color_space, rgbf=self.rgbf, **fields)
+        return d.download(d.ops(d.upload(self.pixels), desc))
+
+    def _derived(self, pixels, color_space=None, rgbf=None) -> "Image":
+        return Image(pixels, self.color_space if color_space is None else color_space,
+                     self.rgbf if rgbf is None else rgbf, self.device_id)
+
+    def flip_horizontal(self) -> bool:
+        self.pixels = self._run(ImageOp.FlipX)
+        return True
+
+    def flip_vertical(self) -> bool:
+        self.pixels = self._run(ImageOp.FlipY)
+        return True
+
+    def rotate(self, angle: RotateAngle) -> "Image":
+        """A new image; width and height swap for 90 and 270 degrees."""
+        return self._derived(self._run(ImageOp.Rotate, rotate=RotateAngle(angle)))
+
+    def pre_multiply_alpha(self) -> bool:
+        self.pixels = self._run(ImageOp.PreMultiply)
+        return True
+
+    def change_color_space(self, color_space: ColorSpace) -> bool:
+        self.pixels = self._run(ImageOp.ColorSpace, dst_color_space=ColorSpace(color_space))
+        self.color_space = ColorSpace(color_space)
+        return True
+
+    def grayscale(self) -> bool:
+        self.pixels = self._run(ImageOp.Grayscale)
+        return True
+
+    def swizzle(self, red: Channel, green: Channel, blue: Channel, alpha: Channel) -> bool:
+        self.pixels = self._run(ImageOp.Swizzle, swizzle=(Channel(red), Channel(green), Channel(blue),
+                                                          Channel(alpha)))
+        return True
+
+    def create_normal_map(self, options: NormalOptions = NormalOptions.Default, height: float = 1.0) -> "Image":
+        """A new RGBF image of the same size, from the red channel."""
+        return self._derived(self._run(ImageOp.NormalMap, normal_options=NormalOptions(options),
+                                       normal_height=height), rgbf=True)
+
+    def resize(self, width: int, height: int, filter: ResizeFilter = ResizeFilter.CatmullRom) -> "Image":
+        """Image::resize through cfhip_resize_device, in linear space for an sRGB image; equal sizes copy."""
+        d = _Device(self.device_id)
+        out = d.download(d.resize(d.upload(self.pixels), width, height, self.color_space, filter))
+        return self._derived(out)
+
+
+_SIGNED = (Type.SNorm, Type.Int, Type.Float)      # isSigned (tool/main.cpp:63-75)
+
+
+def plan_process_image(width: int, height: int, src_width: int, src_height: int, image_color_space,
+                       texture_color_space, mip_level: int = 0, type=Type.UNorm, rotate=None,
+                       grayscale: bool = False, normal_map=None, flip_x: bool = False, flip_y: bool = False,
+                       swizzle=None, premultiply: bool = False):
+    """The device steps of process_image, in order: ("ops", ImageOps) and ("resize", width, height, colour space).
+    At most three ops steps: before the first resize, between the resizes, after the last."""
+    steps = []
+    cs = ColorSpace(image_color_space)
+    tcs = ColorSpace(texture_color_space)
+    this_w, this_h = max(width >> mip_level, 1), max(height >> mip_level, 1)
+    normal = normal_map is not None
+    # with a normal map at a mip level the map is made at the full target size, then resized (main.cpp:181-190)
+    normal_w, normal_h = (width, height) if normal else (this_w, this_h)
+    group = {"ops": 0, "src": cs}
+    fields = {}
+
+    def close(final=False):
+        # a group before a resize runs only when it has ops (the resize reads any pixel type); the last one also
+        # when nothing else ran (the result is RGBA32F), and after a normal map always: a resize can leave alpha
+        # a rounding step away from 1, the reference's RGBF image has none
+        nonlocal group, fields
+        if group["ops"] or (final and (normal or not steps)):
+            steps.append(("ops", api.make_image_ops(group["ops"], group["src"], dst_color_space=tcs,
+                                                    rgbf=final and normal, **fields)))
+        group, fields = {"ops": 0, "src": cs}, {}
+
+    if tcs != cs:
+        group["ops"] |= ImageOp.ColorSpace
+        cs = tcs
+    if (normal_w, normal_h) != (src_width, src_height):
+        close()
+        steps.append(("resize", normal_w, normal_h, cs))
+    if rotate is not None:
+        group["ops"] |= ImageOp.Rotate
+        fields["rotate"] = RotateAngle(rotate)
+    if grayscale:
+        group["ops"] |= ImageOp.Grayscale
+    if normal:
+        options, nheight = normal_map
+        options = NormalOptions(options)
+        if Type(type) in _SIGNED:
+            options |= NormalOptions.KeepSign
+        group["ops"] |= ImageOp.NormalMap
+        fields["normal_options"] = options
+        fields["normal_height"] = float(nheight)
+        if (normal_w, normal_h) != (this_w, this_h):
+            close()
+            steps.append(("resize", this_w, this_h, cs))
+    if flip_x:
+        group["ops"] |= ImageOp.FlipX
+    if flip_y:
+        group["ops"] |= ImageOp.FlipY
+    if swizzle is not None:
+        group["ops"] |= ImageOp.Swizzle
+        fields["swizzle"] = tuple(Channel(c) for c in swizzle)
+    if premultiply:
+        group["ops"] |= ImageOp.PreMultiply
+    close(final=True)
+    return steps
+
+
+def process_image(image, image_color_space, texture_color_space, width: int, height: int, mip_level: int = 0,
+                  type=Type.UNorm, filter=ResizeFilter.CatmullRom, rotate: Optional[RotateAngle] = None,
+                  grayscale: bool = False, normal_map: Optional[Tuple[NormalOptions, float]] = None,
+                  flip_x: bool = False, flip_y: bool = False, swizzle: Optional[Sequence[Channel]] = None,
+                  premultiply: bool = False, orig_image_format=ImageFormat.Invalid, device_id: int = 0) -> np.ndarray:
+    """loadAndProcessImage (tool/main.cpp:147-277) after the load: colour-space change, resize to the target size
+    (max(1, size >> mip_level); the full size first when a normal map is made), rotation, grayscale, normal map
+    (normal_map = (NormalOptions, height); KeepSign added for signed types; resized to the mip size afterwards),
+    X then Y flip, swizzle, premultiplication and Texture.adjust_image_value_range.  The intermediates stay on the
+    device.  Returns the RGBA32F array for Texture.set_image.  image: an (h, w, 4) array or an Image (its pixels)."""
+    if isinstance(image, Image):
+        image = image.pixels
+    pixels = _pixels(image)
+    if ImageFormat(orig_image_format) == ImageFormat.Invalid:
+        orig_image_format = ImageFormat.RGBA8 if pixels.dtype == np.uint8 else ImageFormat.RGBAF
+    steps = plan_process_image(width, height, pixels.shape[1], pixels.shape[0], image_color_space,
+                               texture_color_space, mip_level, type, rotate, grayscale, normal_map, flip_x, flip_y,
+                               swizzle, premultiply)
+    d = _Device(device_id)
+    buf = d.upload(pixels)
+    for s in steps:
+        if s[0] == "ops":
+            buf = d.ops(buf, s[1])
+        else:
+            buf = d.resize(buf, s[1], s[2], s[3], filter)
+    out = d.download(buf)
+    if normal_map is not None:
+        orig_image_format = ImageFormat.RGBF          # the image no longer matches the original input
+    return Texture.adjust_image_value_range(out, type, orig_image_format)

@@ -371,7 +371,70 @@ int cfhip_decode_sse_device(cfhip_ctx* ctx, int format, int type, const void* bl
 	uint32_t width, uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes,
 	uint64_t* sse_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device or cfhip_decode* call on
+/* ---- per-image pixel operations (Image.cpp:1513-1882): the steps the cuttlefish tool runs between loading an
+ * image and Texture::setImage (tool/main.cpp:147-277), except the resizes ---- */
+
+/* cuttlefish::Image::Channel (Image.h:104-111) */
+enum cfhip_channel {
+	CFHIP_CHANNEL_RED = 0,
+	CFHIP_CHANNEL_GREEN = 1,
+	CFHIP_CHANNEL_BLUE = 2,
+	CFHIP_CHANNEL_ALPHA = 3,
+	CFHIP_CHANNEL_NONE = 4     /* 0 for red, green and blue, 1 for alpha */
+};
+
+/* cuttlefish::Image::RotateAngle (Image.h:91-99) */
+enum cfhip_rotate {
+	CFHIP_ROTATE_CW90 = 0,
+	CFHIP_ROTATE_CW180 = 1,
+	CFHIP_ROTATE_CW270 = 2,
+	CFHIP_ROTATE_CCW90 = 3,
+	CFHIP_ROTATE_CCW180 = 4,
+	CFHIP_ROTATE_CCW270 = 5
+};
+
+/* cuttlefish::Image::NormalOptions (Image.h:116-122), a bit mask */
+enum cfhip_normal_options {
+	CFHIP_NORMAL_DEFAULT = 0,
+	CFHIP_NORMAL_KEEP_SIGN = 1,
+	CFHIP_NORMAL_WRAP_X = 2,
+	CFHIP_NORMAL_WRAP_Y = 4
+};
+
+/* The ops of one cfhip_image_ops_device call; they run in this order (the tool's), whatever the order of the bits */
+enum cfhip_image_op {
+	CFHIP_IMAGE_OP_COLOR_SPACE = 1 << 0,   /* Image::changeColorSpace(dst_color_space) */
+	CFHIP_IMAGE_OP_ROTATE = 1 << 1,        /* Image::rotate(rotate) */
+	CFHIP_IMAGE_OP_GRAYSCALE = 1 << 2,     /* Image::grayscale() */
+	CFHIP_IMAGE_OP_NORMAL_MAP = 1 << 3,    /* Image::createNormalMap(normal_options, normal_height): RGBF from here */
+	CFHIP_IMAGE_OP_FLIP_X = 1 << 4,        /* Image::flipHorizontal() */
+	CFHIP_IMAGE_OP_FLIP_Y = 1 << 5,        /* Image::flipVertical() */
+	CFHIP_IMAGE_OP_SWIZZLE = 1 << 6,       /* Image::swizzle(swizzle[0..3]) */
+	CFHIP_IMAGE_OP_PREMULTIPLY = 1 << 7    /* Image::preMultiplyAlpha() */
+};
+
+typedef struct cfhip_image_ops {
+	uint32_t ops;              /* cfhip_image_op bits */
+	int32_t src_color_space;   /* the image's colour space (cfhip_color_space) */
+	int32_t dst_color_space;   /* CFHIP_IMAGE_OP_COLOR_SPACE: the space it changes to; later ops use it */
+	int32_t rotate;            /* cfhip_rotate, read under CFHIP_IMAGE_OP_ROTATE */
+	uint32_t normal_options;   /* cfhip_normal_options bits */
+	uint32_t rgbf;             /* 1: the image is RGBF (a normal map): alpha reads 1, a swizzled alpha is dropped,
+	                            * premultiplication does nothing */
+	double normal_height;
+	int32_t swizzle[4];        /* cfhip_channel of the red, green, blue and alpha outputs */
+} cfhip_image_ops;
+
+/* One fused pass of the ops above on device buffers.  src: w x h texels of src_pixel_type, rows
+ * src_pitch_bytes apart, read as the reference's RGBAF image (RGBA8 as v/255).  dst: the result as RGBA32F,
+ * rows dst_pitch_bytes apart, h x w texels under a 90 or 270 degree rotation and w x h otherwise.  Every op
+ * rounds to float where the reference stores, so one call equals the same ops one call each, bit for bit.
+ * src and dst must not overlap.  stream NULL = the context's stream, and the call then synchronises; on a
+ * caller's stream it returns once the launch is queued. */
+int cfhip_image_ops_device(cfhip_ctx* ctx, const void* src, int src_pixel_type, uint32_t w, uint32_t h,
+	size_t src_pitch_bytes, const cfhip_image_ops* ops, void* dst, size_t dst_pitch_bytes, void* stream);
+
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_decode* or cfhip_image_ops_device call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
