@@ -6,7 +6,7 @@ reference interface for that one path (Texture.convert / Converter) used by the
 parity tests and bench.py; it never falls back to a CPU encoder.
 """
 from .api import (Alpha, CfhipError, ColorSpace, Context, Format, PixelType, Quality,  # noqa: F401
-                  Channel, ImageOp, ImageOps, Layout, NormalOptions, ResizeFilter, RotateAngle, Type, make_image_ops,
+                  Channel, CompareResult, Comparison, ImageOp, ImageOps, Layout, NormalOptions, ResizeFilter, RotateAngle, Type, make_image_ops,
                   decoded_layout, device_count, load_library, make_params, payload_size, psnr_from_sse, query,
                   shard_rows)
 from . import shard  # noqa: F401
@@ -18,4 +18,4 @@ __all__ = ["Alpha", "CfhipError", "ColorSpace", "Context", "Format", "PixelType"
            "ResizeFilter", "Type", "Texture", "Dimension", "CubeFace", "FileType", "SaveResult",
            "MipReplacement", "CustomMipImage", "ImageFormat", "image_index", "Layout", "decoded_layout", "psnr_from_sse", "device_count", "load_library", "make_params", "payload_size",
            "query", "shard", "shard_rows", "Channel", "ImageOp", "ImageOps", "NormalOptions", "RotateAngle",
-           "make_image_ops", "Image", "plan_process_image", "process_image"]
+           "make_image_ops", "Image", "plan_process_image", "process_image", "CompareResult", "Comparison"]

@@ -175,7 +175,7 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_profile_begin", "cfhip_profile_end", "cfhip_generate_mips_device",
            "cfhip_generate_mips3d_device", "cfhip_resize_device", "cfhip_generate_mips_array_device",
            "cfhip_decoded_layout", "cfhip_decode", "cfhip_decode_device", "cfhip_decode_sse",
-           "cfhip_decode_sse_device", "cfhip_image_ops_device"]
+           "cfhip_decode_sse_device", "cfhip_image_ops_device", "cfhip_compare", "cfhip_compare_device"]
 
 
 class Layout(enum.IntEnum):
@@ -197,6 +197,54 @@ LAYOUT_ARRAY = {Layout.RGBA8: (4, np.uint8), Layout.R8: (1, np.uint8), Layout.R8
                 Layout.RG8: (2, np.uint8), Layout.RG8_SNorm: (2, np.int8), Layout.R16: (1, np.uint16),
                 Layout.R16_SNorm: (1, np.int16), Layout.RG16: (2, np.uint16), Layout.RG16_SNorm: (2, np.int16),
                 Layout.RGBA16F: (4, np.float16)}
+
+COMPARE_SSIM = 1                # CFHIP_COMPARE_SSIM
+
+
+class CompareResult(ctypes.Structure):
+    """struct cfhip_compare_result."""
+    _fields_ = [("texels", ctypes.c_uint64), ("error_blocks", ctypes.c_uint64), ("channels", ctypes.c_uint32),
+                ("ssim_windows", ctypes.c_uint32), ("sse", ctypes.c_double * 4), ("log_sse", ctypes.c_double * 4),
+                ("ssim", ctypes.c_double * 4), ("ref_max", ctypes.c_double * 4)]
+
+
+class Comparison:
+    """What Context.compare returns: the metrics of one surface (cfhip_compare_result) and, when asked, the
+    (blocks_y, blocks_x) float32 map of per-block SSE."""
+
+    def __init__(self, res: CompareResult, layout: Layout, block_errors: Optional[np.ndarray] = None):
+        self.layout = Layout(layout)
+        self.texels = int(res.texels)
+        self.error_blocks = int(res.error_blocks)
+        self.channels = int(res.channels)
+        self.ssim_windows = int(res.ssim_windows)
+        self.sse = [float(v) for v in res.sse]
+        self.log_sse = [float(v) for v in res.log_sse]
+        self.ssim = [float(v) for v in res.ssim]
+        self.ref_max = [float(v) for v in res.ref_max]
+        self.block_errors = block_errors
+
+    def compared(self):
+        """Indices of the compared channels."""
+        return [c for c in range(4) if (self.channels >> c) & 1]
+
+    def peak(self, channels=None) -> float:
+        """The data range: 1 for UNorm layouts, 2 for SNorm layouts, the largest reference value for HDR."""
+        if self.layout == Layout.RGBA16F:
+            chans = self.compared() if channels is None else list(channels)
+            return max(self.ref_max[c] for c in chans)
+        return 2.0 if self.layout.name.endswith("SNorm") else 1.0
+
+    def psnr(self, channels=None, peak=None) -> float:
+        """PSNR (dB) over `channels` (default: the compared ones); peak defaults to the data range."""
+        chans = self.compared() if channels is None else list(channels)
+        if not chans:
+            raise ValueError("no channel to measure")
+        total = sum(self.sse[c] for c in chans)
+        if total == 0.0:
+            return float("inf")
+        p = self.peak(chans) if peak is None else float(peak)
+        return 10.0 * float(np.log10(p * p * self.texels * len(chans) / total))
 
 
 class Params(ctypes.Structure):
@@ -339,6 +387,16 @@ def load_library(path: Optional[str] = None):
                                          ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(ImageOps), ctypes.c_void_p,
                                          ctypes.c_size_t, ctypes.c_void_p]
     L.cfhip_image_ops_device.restype = ctypes.c_int
+    u8p, fp = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_float)
+    L.cfhip_compare.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, u8p,
+                                ctypes.c_uint, ctypes.POINTER(CompareResult), fp, ctypes.c_size_t]
+    L.cfhip_compare.restype = ctypes.c_int
+    L.cfhip_compare_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32,
+                                       ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, u8p,
+                                       ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                       ctypes.c_void_p]
+    L.cfhip_compare_device.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -602,6 +660,52 @@ class Context:
         self._check(self._lib.cfhip_decode_sse_device(
             self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(ref)),
             ref_pitch_bytes, ctypes.c_void_p(int(sse)), ctypes.c_void_p(stream) if stream else None))
+
+    @staticmethod
+    def _mask(mask):
+        if mask is None:
+            return None
+        m = list(mask)
+        if len(m) != 4:
+            raise ValueError("mask must have 4 entries (r, g, b, a)")
+        return (ctypes.c_uint8 * 4)(*[1 if v else 0 for v in m])
+
+    def compare(self, payload: np.ndarray, ref: np.ndarray, fmt, typ=Type.UNorm, mask=None, ssim: bool = False,
+                block_map: bool = False) -> Comparison:
+        """Decode a payload on the GPU and measure it against an (h, w, 4) uint8, float16 or float32 reference
+        (its size is the surface's): SSE, log SSE (HDR layouts), reference maxima, SSIM (ssim=True, LDR layouts)
+        and the per-block error map (block_map=True).  mask: 4 booleans (r, g, b, a), None = all."""
+        ref = np.asarray(ref)
+        pix = {np.dtype(np.uint8): PixelType.RGBA8, np.dtype(np.float32): PixelType.RGBA32F,
+               np.dtype(np.float16): PixelType.RGBA16F}.get(ref.dtype)
+        if ref.ndim != 3 or ref.shape[2] != 4 or pix is None:
+            raise ValueError("reference must be (h, w, 4) uint8, float16 or float32")
+        ref = np.ascontiguousarray(ref)
+        h, w = ref.shape[:2]
+        layout, _ = decoded_layout(fmt, typ)
+        blocks = np.ascontiguousarray(payload, dtype=np.uint8)
+        res = CompareResult()
+        emap = None
+        if block_map:
+            bw, bh, _ = query(fmt, typ)
+            emap = np.zeros(((h + bh - 1) // bh, (w + bw - 1) // bw), np.float32)
+        self._check(self._lib.cfhip_compare(
+            self._h, int(fmt), int(typ), blocks.ctypes.data, blocks.nbytes, w, h, ref.ctypes.data, int(pix),
+            ref.strides[0], self._mask(mask), COMPARE_SSIM if ssim else 0, ctypes.byref(res),
+            emap.ctypes.data_as(ctypes.POINTER(ctypes.c_float)) if emap is not None else None,
+            emap.size if emap is not None else 0))
+        return Comparison(res, layout, emap)
+
+    def compare_device(self, blocks: int, fmt, typ, width: int, height: int, ref: int, ref_pixel_type,
+                       ref_pitch_bytes: int, result: int, mask=None, ssim: bool = False, block_errors: int = 0,
+                       block_errors_capacity: int = 0, stream: int = 0):
+        """Device path of compare: blocks / ref / result (one cfhip_compare_result) / block_errors (floats, 0 =
+        none) are device pointers as ints.  stream 0 = the context's stream (the call then synchronises)."""
+        self._check(self._lib.cfhip_compare_device(
+            self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(ref)),
+            int(ref_pixel_type), ref_pitch_bytes, self._mask(mask), COMPARE_SSIM if ssim else 0,
+            ctypes.c_void_p(int(result)), ctypes.c_void_p(int(block_errors)) if block_errors else None,
+            block_errors_capacity, ctypes.c_void_p(stream) if stream else None))
 
     def last_kernel_ms(self) -> float:
         return float(self._lib.cfhip_last_kernel_ms(self._h))

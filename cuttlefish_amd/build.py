@@ -119,7 +119,10 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  "cfhip_decode_block_kernel", "cfhip_decode_astc_kernel", "cfhip_decode_sse_block_kernel",
                  "cfhip_decode_sse_astc_kernel",
                  # the per-image pixel ops (csrc/image_ops.hip)
-                 "cfhip_image_ops_kernel")
+                 "cfhip_image_ops_kernel",
+                 # the quality metrics (csrc/compare.hip)
+                 "cfhip_compare_block_kernel", "cfhip_compare_astc_kernel", "cfhip_compare_ssim_kernel",
+                 "cfhip_compare_final_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

@@ -9,6 +9,7 @@
 #include "astc_tables.h"
 #include "../../include/cuttlefish_hip.h"
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -57,6 +58,16 @@ extern "C" hipError_t cfhip_launch_std_pack(const cf_kparams* kp, int pixel_type
 extern "C" hipError_t cfhip_launch_decode(int format, int type, const void* blocks, int blk_vec, void* out,
 	size_t out_pitch, const void* ref, size_t ref_pitch, int out_vec, uint32_t width, uint32_t height,
 	uint32_t bx, uint32_t by, int bw, int bh, unsigned long long* acc, int sse, hipStream_t stream);
+extern "C" uint64_t cfhip_compare_partials(int format, uint32_t width, uint32_t height, uint32_t bx, uint32_t by,
+	uint64_t* ssim_partials);
+extern "C" hipError_t cfhip_launch_compare(int format, int type, const void* blocks, int blk_vec, const void* ref,
+	int ref_pix, size_t ref_pitch, uint32_t width, uint32_t height, uint32_t bx, uint32_t by, int bw, int bh,
+	unsigned cmask, float* block_errors, double* partials, hipStream_t stream);
+extern "C" hipError_t cfhip_launch_ssim(const void* dec, size_t dec_pitch, int layout, const void* ref, int ref_pix,
+	size_t ref_pitch, uint32_t width, uint32_t height, unsigned cmask, const float* taps, double range,
+	double* partials, hipStream_t stream);
+extern "C" hipError_t cfhip_launch_compare_final(const double* pa, uint64_t na, const double* pb, uint64_t nb,
+	unsigned cmask, int hdr, uint32_t windows, uint64_t texels, cfhip_compare_result* result, hipStream_t stream);
 extern "C" hipError_t cfhip_launch_bc15(const cf_kparams* kp, int format, int pixel_type,
 	int snorm, hipStream_t stream);
 
@@ -1077,6 +1088,129 @@ int decode_launch(cfhip_ctx* ctx, int format, int type, const DecodeGeom& g, con
 		width, height, g.bx, g.by, g.bw, g.bh, acc, sse ? 1 : 0, stream);
 	if (e != hipSuccess)
 		return fail(ctx, CFHIP_E_DEVICE, "decode launch: %s", hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, stream));
+	return CFHIP_OK;
+}
+
+// ---- quality metrics (csrc/compare.hip) -----------------------------------------------------------
+// What one compare call runs and where its device scratch lies: the decoded surface of the SSIM pass, then the
+// Pass A partials (16 doubles per workgroup), then the SSIM partials (4 doubles per workgroup).
+struct CompareGeom {
+	DecodeGeom g;
+	int ref_bytes;
+	unsigned cmask;
+	bool hdr, ssim;
+	uint64_t na, nb;
+	uint32_t windows;
+	size_t pa_off, pb_off, scratch_bytes;
+};
+
+size_t align16(size_t v) { return (v + 15u) & ~(size_t)15u; }
+
+// the checks every compare entry point makes before anything is enqueued
+int compare_check(cfhip_ctx* ctx, const char* what, int format, int type, const void* blocks, uint32_t width,
+	uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch, const uint8_t* mask, unsigned flags,
+	const void* result, const void* block_errors, size_t block_errors_capacity, CompareGeom* c)
+{
+	int rc = decode_check(ctx, what, format, type, blocks, width, height, false, &c->g);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!ref || !result)
+		return fail(ctx, CFHIP_E_INVALID, "%s: NULL reference or result", what);
+	switch (ref_pixel_type) {
+		case CFHIP_PIXEL_RGBA8: c->ref_bytes = 4; break;
+		case CFHIP_PIXEL_RGBA32F: c->ref_bytes = 16; break;
+		case CFHIP_PIXEL_RGBA16F: c->ref_bytes = 8; break;
+		default: return fail(ctx, CFHIP_E_INVALID, "%s: reference pixel type %d", what, ref_pixel_type);
+	}
+	if (ref_pitch < (size_t)width*(size_t)c->ref_bytes)
+		return fail(ctx, CFHIP_E_INVALID, "%s: reference pitch %zu < %zu", what, ref_pitch,
+			(size_t)width*(size_t)c->ref_bytes);
+	if (flags & ~CFHIP_COMPARE_SSIM)
+		return fail(ctx, CFHIP_E_INVALID, "%s: unknown flags 0x%x", what, flags);
+	const int l = c->g.layout;
+	const unsigned lay = (l == CFHIP_LAYOUT_RGBA8 || l == CFHIP_LAYOUT_RGBA16F) ? 15u :
+		((l == CFHIP_LAYOUT_R8 || l == CFHIP_LAYOUT_R8_SNORM || l == CFHIP_LAYOUT_R16 || l == CFHIP_LAYOUT_R16_SNORM)
+			? 1u : 3u);
+	unsigned m = 15u;
+	if (mask)
+		m = (mask[0] ? 1u : 0u) | (mask[1] ? 2u : 0u) | (mask[2] ? 4u : 0u) | (mask[3] ? 8u : 0u);
+	c->cmask = lay & m;
+	c->hdr = l == CFHIP_LAYOUT_RGBA16F;
+	const uint64_t nblk = (uint64_t)c->g.bx*c->g.by;
+	if (block_errors && block_errors_capacity < nblk)
+		return fail(ctx, CFHIP_E_CAPACITY, "%s: block_errors_capacity %zu < %llu blocks", what,
+			block_errors_capacity, (unsigned long long)nblk);
+	c->na = cfhip_compare_partials(format, width, height, c->g.bx, c->g.by, &c->nb);
+	c->ssim = (flags & CFHIP_COMPARE_SSIM) && !c->hdr && c->nb > 0 && c->cmask;
+	if (!c->ssim)
+		c->nb = 0;
+	c->windows = 0;
+	if (c->ssim) {
+		const uint64_t win = (uint64_t)(width - 10u)*(height - 10u);
+		if (win > 0xFFFFFFFFull || (height - 10u + 15u)/16u > 65535u)
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %ux%u too large for SSIM", what, width, height);
+		c->windows = (uint32_t)win;
+	}
+	const size_t dec = c->ssim ? (size_t)width*height*(size_t)c->g.texel_bytes : 0;
+	c->pa_off = align16(dec);
+	c->pb_off = c->pa_off + (size_t)c->na*16u*sizeof(double);
+	c->scratch_bytes = c->pb_off + (size_t)c->nb*4u*sizeof(double);
+	return CFHIP_OK;
+}
+
+// the normalised 11-tap Gaussian of the SSIM window (sigma 1.5), in double, rounded to float
+const float* ssim_taps()
+{
+	static float taps[11];
+	static std::once_flag once;
+	std::call_once(once, [] {
+		double w[11], s = 0.0;
+		for (int k = -5; k <= 5; ++k)
+			s += w[k + 5] = std::exp(-(double)(k*k)/4.5);
+		for (int k = 0; k < 11; ++k)
+			taps[k] = (float)(w[k]/s);
+	});
+	return taps;
+}
+
+// Pass A, the SSIM pass (decode into scratch + window statistics) and the final reduction, timed as one span
+int compare_enqueue(cfhip_ctx* ctx, int format, int type, const CompareGeom& c, const void* blocks, const void* ref,
+	int ref_pixel_type, size_t ref_pitch, uint32_t width, uint32_t height, uint8_t* scratch,
+	cfhip_compare_result* result, float* block_errors, hipStream_t stream)
+{
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = format >= CFHIP_FORMAT_ASTC_4x4 ? "cfhip_compare_astc_kernel" : "cfhip_compare_block_kernel";
+	const DecodeGeom& g = c.g;
+	const int blk_vec = ((uintptr_t)blocks % (uintptr_t)g.bb == 0) ? 1 : 0;
+	double* pa = reinterpret_cast<double*>(scratch + c.pa_off);
+	double* pb = c.ssim ? reinterpret_cast<double*>(scratch + c.pb_off) : nullptr;
+	hipEvent_t a, b;
+	int rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, stream));
+	hipError_t e = cfhip_launch_compare(format, type, blocks, blk_vec, ref, ref_pixel_type, ref_pitch, width, height,
+		g.bx, g.by, g.bw, g.bh, c.cmask, block_errors, pa, stream);
+	if (e == hipSuccess && c.ssim) {
+		const size_t dec_pitch = (size_t)width*(size_t)g.texel_bytes;
+		e = cfhip_launch_decode(format, type, blocks, blk_vec, scratch, dec_pitch, nullptr, 0,
+			dec_pitch % 16u == 0 ? 1 : 0, width, height, g.bx, g.by, g.bw, g.bh, nullptr, 0, stream);
+		if (e == hipSuccess) {
+			const double range = (g.layout == CFHIP_LAYOUT_R8_SNORM || g.layout == CFHIP_LAYOUT_RG8_SNORM ||
+				g.layout == CFHIP_LAYOUT_R16_SNORM || g.layout == CFHIP_LAYOUT_RG16_SNORM) ? 2.0 : 1.0;
+			e = cfhip_launch_ssim(scratch, dec_pitch, g.layout, ref, ref_pixel_type, ref_pitch, width, height, c.cmask,
+				ssim_taps(), range, pb, stream);
+		}
+	}
+	if (e == hipSuccess)
+		e = cfhip_launch_compare_final(pa, c.na, pb, c.nb, c.cmask, c.hdr ? 1 : 0, c.windows,
+			(uint64_t)width*height, result, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "compare launch: %s", hipGetErrorString(e));
 	HIP_TRY(ctx, hipEventRecord(b, stream));
 	return CFHIP_OK;
 }
@@ -2116,6 +2250,91 @@ int cfhip_decode_sse_device(cfhip_ctx* ctx, int format, int type, const void* bl
 	HIP_TRY(ctx, hipMemsetAsync(sum, 0, 32, lease.stream));
 	rc = decode_launch(ctx, format, type, g, blocks, nullptr, 0, ref_rgba8, ref_pitch_bytes, width, height, sum, true,
 		lease.stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	return lease.done(!stream_);
+}
+
+int cfhip_compare(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes, uint32_t width,
+	uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes, const uint8_t mask_rgba[4],
+	unsigned flags, cfhip_compare_result* result, float* block_errors, size_t block_errors_capacity)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	CompareGeom c;
+	int rc = compare_check(ctx, "compare", format, type, blocks, width, height, ref, ref_pixel_type, ref_pitch_bytes,
+		mask_rgba, flags, result, block_errors, block_errors_capacity, &c);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (blocks_bytes < c.g.payload_bytes)
+		return fail(ctx, CFHIP_E_INVALID, "compare: blocks_bytes %zu < %zu for %ux%u", blocks_bytes,
+			c.g.payload_bytes, width, height);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, ctx->stream);
+	const hipStream_t stream = lease.stream;
+	// d_src: the payload; d_out: the reference, tightly packed, the scratch, the result, the block map
+	const size_t row = (size_t)width*(size_t)c.ref_bytes;
+	const size_t scr_off = align16(row*height), res_off = align16(scr_off + c.scratch_bytes);
+	const size_t map_off = align16(res_off + sizeof(cfhip_compare_result));
+	const size_t map_bytes = block_errors ? (size_t)c.g.bx*c.g.by*sizeof(float) : 0;
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, c.g.payload_bytes);
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, map_off + map_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
+	cfhip_compare_result* d_res = reinterpret_cast<cfhip_compare_result*>(d + res_off);
+	float* d_map = block_errors ? reinterpret_cast<float*>(d + map_off) : nullptr;
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, c.g.payload_bytes, hipMemcpyHostToDevice, stream));
+	HIP_TRY(ctx, hipMemcpy2DAsync(d, row, ref, ref_pitch_bytes, row, height, hipMemcpyHostToDevice, stream));
+	rc = compare_enqueue(ctx, format, type, c, ctx->d_src, d, ref_pixel_type, row, width, height, d + scr_off, d_res,
+		d_map, stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	cfhip_compare_result res;
+	HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, stream));
+	if (d_map)
+		HIP_TRY(ctx, hipMemcpyAsync(block_errors, d_map, map_bytes, hipMemcpyDeviceToHost, stream));
+	rc = lease.done(true);
+	if (rc != CFHIP_OK)
+		return rc;
+	*result = res;
+	return CFHIP_OK;
+}
+
+int cfhip_compare_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width, uint32_t height,
+	const void* ref, int ref_pixel_type, size_t ref_pitch_bytes, const uint8_t mask_rgba[4], unsigned flags,
+	cfhip_compare_result* result_device, float* block_errors_device, size_t block_errors_capacity, void* stream_)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	CompareGeom c;
+	int rc = compare_check(ctx, "compare_device", format, type, blocks, width, height, ref, ref_pixel_type,
+		ref_pitch_bytes, mask_rgba, flags, result_device, block_errors_device, block_errors_capacity, &c);
+	if (rc != CFHIP_OK)
+		return rc;
+	// the kernels read reference texels with one aligned load each and store doubles / floats to the outputs
+	const size_t rb = (size_t)c.ref_bytes;
+	if ((uintptr_t)ref % rb != 0 || ref_pitch_bytes % rb != 0)
+		return fail(ctx, CFHIP_E_INVALID, "compare_device: reference and its pitch must be %zu-byte aligned", rb);
+	if ((uintptr_t)result_device % 8u != 0 || (uintptr_t)block_errors_device % 4u != 0)
+		return fail(ctx, CFHIP_E_INVALID, "compare_device: misaligned result or block_errors");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	// the partials (and the SSIM pass's decoded surface) live in d_out: the lease orders them across streams
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, c.scratch_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
+	rc = compare_enqueue(ctx, format, type, c, blocks, ref, ref_pixel_type, ref_pitch_bytes, width, height,
+		static_cast<uint8_t*>(ctx->d_out), result_device, block_errors_device, lease.stream);
 	if (rc != CFHIP_OK)
 		return rc;
 	return lease.done(!stream_);

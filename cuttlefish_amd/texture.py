@@ -622,6 +622,37 @@ class Texture:
         d = self.data(*args)
         return 0 if d is None else int(d.nbytes)
 
+    def compare(self, source: "Texture", ssim: bool = True):
+        """Quality of this converted texture against `source`, an unconverted texture of the same dimension, size,
+        mip levels, depth and faces (convert() frees a texture's own images).  Returns (one api.Comparison per
+        surface in (mip, depth, face) order, the pooled PSNR over every surface).  The channels compared are the
+        colour mask's, without alpha when the alpha type is None or the format has none."""
+        if not self._textures:
+            raise ValueError("compare: this texture is not converted")
+        if source is self or not source.images_complete():
+            raise ValueError("compare: source must be a separate texture holding every image")
+        if (source.dimension(), source.width(), source.height(), source.depth(), source.mip_level_count(),
+                source.face_count()) != (self._dim, self.width(), self.height(), self.depth(), self.mip_level_count(),
+                                         self.face_count()):
+            raise ValueError("compare: source differs in dimension, size, depth, mip levels or faces")
+        mask = list(self._mask)
+        if self._alpha == Alpha.None_ or not self.has_alpha(self._format):
+            mask[3] = False
+        ctx = self._context()
+        results = []
+        for m, level in enumerate(self._textures):
+            for d, dep in enumerate(level):
+                for f, payload in enumerate(dep):
+                    results.append(ctx.compare(payload, source._images[m][d][f], self._format, self._type,
+                                               mask=mask, ssim=ssim))
+        sse = sum(sum(r.sse[c] for c in r.compared()) for r in results)
+        n = sum(r.texels * len(r.compared()) for r in results)
+        if n == 0:
+            raise ValueError("compare: no channel compared")
+        peak = max(r.peak() for r in results)
+        pooled = float("inf") if sse == 0.0 else 10.0 * float(np.log10(peak * peak * n / sse))
+        return results, pooled
+
     # ---- saving (Texture.cpp:1636-1685) --------------------------------------------------------
     def _layout(self) -> containers.TextureLayout:
         dim = {Dimension.Dim1D: "1d", Dimension.Dim2D: "2d", Dimension.Dim3D: "3d", Dimension.Cube: "cube"}[self._dim]

@@ -434,7 +434,49 @@ typedef struct cfhip_image_ops {
 int cfhip_image_ops_device(cfhip_ctx* ctx, const void* src, int src_pixel_type, uint32_t w, uint32_t h,
 	size_t src_pitch_bytes, const cfhip_image_ops* ops, void* dst, size_t dst_pitch_bytes, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_decode* or cfhip_image_ops_device call on
+/* ---- Quality metrics: an encoded payload against its reference, on the GPU ----
+ *
+ * The payload is decoded as cfhip_decode decodes it and every texel normalised to double:
+ *   RGBA8 / R8 / RG8 v/255; R8 / RG8 signed max(v/127, -1); EAC R16 / RG16 v/2047, signed max(v/1023, -1);
+ *   RGBA16F half -> float (BC6H alpha 1.0).
+ * The reference is read as stored, without clamp or sRGB transfer: RGBA8 v/255, RGBA16F, RGBA32F.
+ * Channels compared: those of the decoded layout (R, RG or RGBA) AND the caller's mask.  For each:
+ *   sse[c]      = sum of (dec - ref)^2 over the width x height texels, in FP64
+ *   log_sse[c]  = sum of (log2(max(dec, 2^-24)) - log2(max(ref, 2^-24)))^2, RGBA16F layouts only (NaN otherwise)
+ *   ref_max[c]  = the maximum of the reference
+ *   ssim[c]     = with CFHIP_COMPARE_SSIM, LDR layouts: mean SSIM over the window centres whose 11 x 11 window
+ *                 lies inside the surface (Gaussian, sigma 1.5; C1 = (0.01 L)^2, C2 = (0.03 L)^2, L = 1 for UNorm
+ *                 and 2 for SNorm layouts).  NaN when not computed, for HDR layouts and when a side is below 11.
+ * Channels not compared report 0 (ssim NaN).  error_blocks counts as cfhip_decode counts.  block_errors
+ * (optional): one float per block of the payload's block grid, row-major, the block's SSE summed over the
+ * compared channels and its texels inside the surface; block_errors_capacity counts floats (>= blocks, else
+ * CFHIP_E_CAPACITY).  Partial sums are reduced in a fixed order: identical calls return identical bits. */
+typedef struct cfhip_compare_result {
+	uint64_t texels, error_blocks;
+	uint32_t channels;        /* bit c: channel c compared */
+	uint32_t ssim_windows;    /* valid window centres; 0 when SSIM was not computed */
+	double sse[4], log_sse[4], ssim[4], ref_max[4];
+} cfhip_compare_result;
+
+#define CFHIP_COMPARE_SSIM 1u
+
+/* Host buffers: blocks (blocks_bytes >= the payload size), ref: width x height texels of ref_pixel_type
+ * (cfhip_pixel_type), rows ref_pitch_bytes apart.  mask_rgba NULL = every channel.  Blocking.  Standard formats
+ * and the pairs cfhip_query rejects are CFHIP_E_UNSUPPORTED. */
+int cfhip_compare(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes,
+	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
+	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result,
+	float* block_errors, size_t block_errors_capacity);
+
+/* Device buffers on ctx's GPU: blocks, ref (pointer and pitch aligned to the texel size), result_device and
+ * block_errors_device (optional).  mask_rgba is host memory.  stream NULL = the context's stream, and the call
+ * then synchronises; on a caller's stream it returns once the work is queued. */
+int cfhip_compare_device(cfhip_ctx* ctx, int format, int type, const void* blocks,
+	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
+	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device,
+	float* block_errors_device, size_t block_errors_capacity, void* stream);
+
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_decode*, cfhip_compare* or cfhip_image_ops_device call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
