@@ -74,6 +74,17 @@ class Format(enum.IntEnum):
     ASTC_10x10 = 54
     ASTC_12x10 = 55
     ASTC_12x12 = 56
+    # PVRTC (Texture.h:124-129): query() still raises for all six; PVRTC1 4 bpp goes through pvrtc_payload_size and
+    # the Context.*_pvrtc calls, the 2 bpp and PVRTC2 formats are not built
+    PVRTC1_RGB_2BPP = 57
+    PVRTC1_RGBA_2BPP = 58
+    PVRTC1_RGB_4BPP = 59
+    PVRTC1_RGBA_4BPP = 60
+    PVRTC2_RGBA_2BPP = 61
+    PVRTC2_RGBA_4BPP = 62
+
+
+PVRTC_FORMATS = (Format.PVRTC1_RGB_4BPP, Format.PVRTC1_RGBA_4BPP)
 
 
 class Type(enum.IntEnum):
@@ -175,7 +186,9 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_profile_begin", "cfhip_profile_end", "cfhip_generate_mips_device",
            "cfhip_generate_mips3d_device", "cfhip_resize_device", "cfhip_generate_mips_array_device",
            "cfhip_decoded_layout", "cfhip_decode", "cfhip_decode_device", "cfhip_decode_sse",
-           "cfhip_decode_sse_device", "cfhip_image_ops_device", "cfhip_compare", "cfhip_compare_device"]
+           "cfhip_decode_sse_device", "cfhip_image_ops_device", "cfhip_compare", "cfhip_compare_device",
+           "cfhip_pvrtc_query", "cfhip_pvrtc_encode", "cfhip_pvrtc_encode_device", "cfhip_pvrtc_decode",
+           "cfhip_pvrtc_decode_device", "cfhip_pvrtc_decode_sse", "cfhip_pvrtc_decode_sse_device"]
 
 
 class Layout(enum.IntEnum):
@@ -397,6 +410,29 @@ def load_library(path: Optional[str] = None):
                                        ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                        ctypes.c_void_p]
     L.cfhip_compare_device.restype = ctypes.c_int
+    L.cfhip_pvrtc_query.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32,
+                                    ctypes.POINTER(ctypes.c_size_t)]
+    L.cfhip_pvrtc_query.restype = ctypes.c_int
+    for name in ("cfhip_pvrtc_encode", "cfhip_pvrtc_encode_device"):
+        fn = getattr(L, name)
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(Surface), ctypes.c_size_t, ctypes.POINTER(Params)] + \
+            ([ctypes.c_void_p] if name.endswith("device") else [])
+        fn.restype = ctypes.c_int
+    L.cfhip_pvrtc_decode.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                     ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]
+    L.cfhip_pvrtc_decode.restype = ctypes.c_int
+    L.cfhip_pvrtc_decode_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                            ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t,
+                                            ctypes.c_void_p]
+    L.cfhip_pvrtc_decode_device.restype = ctypes.c_int
+    L.cfhip_pvrtc_decode_sse.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                         ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                         ctypes.c_size_t, ctypes.POINTER(ctypes.c_uint64)]
+    L.cfhip_pvrtc_decode_sse.restype = ctypes.c_int
+    L.cfhip_pvrtc_decode_sse_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t,
+                                                ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_pvrtc_decode_sse_device.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -425,6 +461,16 @@ def query(fmt, typ=Type.UNorm):
 def payload_size(fmt, typ, width: int, height: int) -> int:
     bw, bh, bs = query(fmt, typ)
     return ((width + bw - 1) // bw) * ((height + bh - 1) // bh) * bs
+
+
+def pvrtc_payload_size(fmt, typ, width: int, height: int) -> int:
+    """Payload bytes of a PVRTC1 4 bpp level: max(w/4, 2) * max(h/4, 2) * 8.  Raises for other formats and types
+    (CFHIP_E_UNSUPPORTED) and for sizes that are not powers of two (CFHIP_E_INVALID)."""
+    n = ctypes.c_size_t()
+    rc = load_library().cfhip_pvrtc_query(int(fmt), int(typ), width, height, ctypes.byref(n))
+    if rc != 0:
+        raise CfhipError(rc, "no PVRTC1 payload for (format, type) = (%r, %r) at %dx%d" % (fmt, typ, width, height))
+    return n.value
 
 
 def decoded_layout(fmt, typ=Type.UNorm):
@@ -556,6 +602,81 @@ class Context:
         self._check(self._lib.cfhip_encode_device(self._h, surf, len(surfaces),
                                                    ctypes.byref(params),
                                                    ctypes.c_void_p(stream) if stream else None))
+
+    def encode_pvrtc(self, images: Iterable[np.ndarray], params: Params):
+        """PVRTC1 4 bpp (params.format 59 / 60): list of (h, w, 4) arrays, both sides powers of two (rows may run
+        bottom-up: a negative row stride is passed on as a negative pitch) -> list of payload byte arrays.  All
+        surfaces of the call share every launch."""
+        images = [np.asarray(im) for im in images]
+        surf = (Surface * len(images))()
+        outs, keep = [], []
+        for i, im in enumerate(images):
+            if im.ndim != 3 or im.shape[2] != 4:
+                raise ValueError("surface %d: expected (h, w, 4)" % i)
+            if im.strides[2] != im.itemsize or im.strides[1] != 4 * im.itemsize:
+                im = np.ascontiguousarray(im)
+            keep.append(im)
+            h, w = im.shape[:2]
+            out = np.zeros(pvrtc_payload_size(params.format, params.type, w, h), np.uint8)
+            outs.append(out)
+            surf[i].pixels = im.ctypes.data
+            surf[i].pixel_type = int(pixel_type_of(im))
+            surf[i].width, surf[i].height = w, h
+            surf[i].row_pitch_bytes = im.strides[0]
+            surf[i].out = out.ctypes.data
+            surf[i].out_capacity = out.nbytes
+        self._check(self._lib.cfhip_pvrtc_encode(self._h, surf, len(outs), ctypes.byref(params)))
+        return outs
+
+    def encode_pvrtc_device(self, surfaces: Sequence[dict], params: Params, stream: int = 0):
+        """Device path of encode_pvrtc; surfaces: dicts as for encode_device."""
+        surf = (Surface * len(surfaces))()
+        for i, s in enumerate(surfaces):
+            surf[i].pixels = s["pixels"]
+            surf[i].pixel_type = int(s["pixel_type"])
+            surf[i].width, surf[i].height = s["width"], s["height"]
+            surf[i].row_pitch_bytes = s["row_pitch_bytes"]
+            surf[i].out = s["out"]
+            surf[i].out_capacity = s["out_capacity"]
+        self._check(self._lib.cfhip_pvrtc_encode_device(self._h, surf, len(surfaces), ctypes.byref(params),
+                                                         ctypes.c_void_p(stream) if stream else None))
+
+    def decode_pvrtc(self, payload: np.ndarray, fmt, width: int, height: int, typ=Type.UNorm):
+        """PVRTC1 4 bpp payload -> (height, width, 4) uint8 (alpha 255 for the RGB format)"""
+        blocks = np.ascontiguousarray(payload, dtype=np.uint8)
+        out = np.empty((height, width, 4), np.uint8)
+        self._check(self._lib.cfhip_pvrtc_decode(self._h, int(fmt), int(typ), blocks.ctypes.data, blocks.nbytes,
+                                                 width, height, out.ctypes.data, out.nbytes))
+        return out
+
+    def decode_pvrtc_device(self, blocks: int, fmt, width: int, height: int, out: int, out_pitch_bytes: int,
+                            typ=Type.UNorm, stream: int = 0):
+        """Device path of decode_pvrtc: blocks / out are device pointers as ints (4-byte aligned)."""
+        self._check(self._lib.cfhip_pvrtc_decode_device(
+            self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(out)),
+            out_pitch_bytes, ctypes.c_void_p(stream) if stream else None))
+
+    def decode_pvrtc_sse(self, payload: np.ndarray, ref: np.ndarray, fmt, typ=Type.UNorm):
+        """Per-channel sums of squared differences between the decoded PVRTC1 payload and an (h, w, 4) uint8
+        reference (its size is the surface's)."""
+        ref = np.asarray(ref)
+        if ref.ndim != 3 or ref.shape[2] != 4 or ref.dtype != np.uint8:
+            raise ValueError("reference must be (h, w, 4) uint8")
+        if ref.strides[2] != 1 or ref.strides[1] != 4 or ref.strides[0] < 0:
+            ref = np.ascontiguousarray(ref)
+        h, w = ref.shape[:2]
+        blocks = np.ascontiguousarray(payload, dtype=np.uint8)
+        sse = (ctypes.c_uint64 * 4)()
+        self._check(self._lib.cfhip_pvrtc_decode_sse(self._h, int(fmt), int(typ), blocks.ctypes.data, blocks.nbytes,
+                                                     w, h, ref.ctypes.data, ref.strides[0], sse))
+        return [int(v) for v in sse]
+
+    def decode_pvrtc_sse_device(self, blocks: int, fmt, width: int, height: int, ref: int, ref_pitch_bytes: int,
+                                sse: int, typ=Type.UNorm, stream: int = 0):
+        """Device path of decode_pvrtc_sse: sse = device pointer to four uint64 (zeroed by the call)."""
+        self._check(self._lib.cfhip_pvrtc_decode_sse_device(
+            self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(ref)),
+            ref_pitch_bytes, ctypes.c_void_p(int(sse)), ctypes.c_void_p(stream) if stream else None))
 
     def generate_mips_device(self, src: int, pixel_type, width: int, height: int,
                              row_pitch_bytes: int, dst_levels: Sequence[int],

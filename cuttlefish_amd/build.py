@@ -122,7 +122,11 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  "cfhip_image_ops_kernel",
                  # the quality metrics (csrc/compare.hip)
                  "cfhip_compare_block_kernel", "cfhip_compare_astc_kernel", "cfhip_compare_ssim_kernel",
-                 "cfhip_compare_final_kernel")
+                 "cfhip_compare_final_kernel",
+                 # PVRTC1 4 bpp (csrc/pvrtc.hip): the encoder's passes and the decoder
+                 "cfhip_pvrtc_load_kernel", "cfhip_pvrtc_init_kernel", "cfhip_pvrtc_mod_kernel",
+                 "cfhip_pvrtc_refine_kernel", "cfhip_pvrtc_pack_kernel", "cfhip_pvrtc_decode_kernel",
+                 "cfhip_pvrtc_decode_sse_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

@@ -22,7 +22,23 @@ from __future__ import annotations
 import struct
 from typing import Sequence
 
-from .api import Alpha, ColorSpace, Format, Type, payload_size, query
+from .api import PVRTC_FORMATS, Alpha, ColorSpace, Format, Type, pvrtc_payload_size
+from .api import payload_size as _block_payload_size
+from .api import query as _block_query
+
+
+def payload_size(fmt, typ, width: int, height: int) -> int:
+    """payload bytes of one level; PVRTC1 4 bpp has its own size rule (never under 2 x 2 blocks)"""
+    if Format(fmt) in PVRTC_FORMATS:
+        return pvrtc_payload_size(fmt, typ, width, height)
+    return _block_payload_size(fmt, typ, width, height)
+
+
+def query(fmt, typ):
+    """(block width, height, bytes); PVRTC1 4 bpp: 4 x 4 texels in 8 bytes (Texture.cpp:596-773)"""
+    if Format(fmt) in PVRTC_FORMATS and Type(typ) == Type.UNorm:
+        return 4, 4, 8
+    return _block_query(fmt, typ)
 
 DDS_MAGIC = 0x20534444          # "DDS "  (SaveDds.cpp:26)
 _DDSD_CAPS, _DDSD_HEIGHT, _DDSD_WIDTH, _DDSD_PITCH = 0x1, 0x2, 0x4, 0x8
@@ -88,12 +104,16 @@ _ASTC = [Format.ASTC_4x4, Format.ASTC_5x4, Format.ASTC_5x5, Format.ASTC_6x5, For
          Format.ASTC_10x8, Format.ASTC_10x10, Format.ASTC_12x10, Format.ASTC_12x12]
 for _i, _f in enumerate(_ASTC):
     _GL[(_f, Type.UNorm)] = (0x93B0 + _i, 0x93D0 + _i, _GL_RGBA)
+# PVRTC1 4 bpp (SaveKtx.cpp:1116-1143); DDS has no form of it (SaveDds.cpp:541-547)
+_GL[(Format.PVRTC1_RGB_4BPP, Type.UNorm)] = (0x8C00, 0x8A55, _GL_RGB)
+_GL[(Format.PVRTC1_RGBA_4BPP, Type.UNorm)] = (0x8C02, 0x8A57, _GL_RGBA)
 
 # Texture::hasAlpha (Texture.cpp:467-512)
 _HAS_ALPHA = {Format.R4G4B4A4, Format.B4G4R4A4, Format.R5G5B5A1, Format.B5G5R5A1, Format.A1R5G5B5,
               Format.R8G8B8A8, Format.B8G8R8A8, Format.A8B8G8R8, Format.A2R10G10B10, Format.A2B10G10R10,
               Format.R16G16B16A16, Format.R32G32B32A32, Format.BC1_RGBA, Format.BC2, Format.BC3,
-              Format.BC7, Format.ETC2_R8G8B8A1, Format.ETC2_R8G8B8A8} | set(_ASTC)
+              Format.BC7, Format.ETC2_R8G8B8A1, Format.ETC2_R8G8B8A8, Format.PVRTC1_RGBA_2BPP,
+              Format.PVRTC1_RGBA_4BPP, Format.PVRTC2_RGBA_2BPP, Format.PVRTC2_RGBA_4BPP} | set(_ASTC)
 
 
 def has_alpha(fmt) -> bool:
@@ -296,6 +316,7 @@ _PVR_SPECIAL = {
     Format.BC5: 13, Format.BC6H: 14, Format.BC7: 15, Format.E5B9G9R9_UFloat: 19,
     Format.ETC2_R8G8B8: 22, Format.ETC2_R8G8B8A8: 23, Format.ETC2_R8G8B8A1: 24, Format.EAC_R11: 25,
     Format.EAC_R11G11: 26,
+    Format.PVRTC1_RGB_4BPP: 2, Format.PVRTC1_RGBA_4BPP: 3,     # SavePvr.cpp:54-57, 455-460
 }
 for _i, _f in enumerate(_ASTC):
     _PVR_SPECIAL[_f] = 27 + _i

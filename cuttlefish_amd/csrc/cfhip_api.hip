@@ -7,6 +7,7 @@
 // cfhip_create() fails and the caller (HipConverter) keeps the reference path.
 #include "cf_device.h"
 #include "astc_tables.h"
+#include "pvrtc_surf.h"
 #include "../../include/cuttlefish_hip.h"
 
 #include <cmath>
@@ -68,6 +69,11 @@ extern "C" hipError_t cfhip_launch_ssim(const void* dec, size_t dec_pitch, int l
 	double* partials, hipStream_t stream);
 extern "C" hipError_t cfhip_launch_compare_final(const double* pa, uint64_t na, const double* pb, uint64_t nb,
 	unsigned cmask, int hdr, uint32_t windows, uint64_t texels, cfhip_compare_result* result, hipStream_t stream);
+extern "C" hipError_t cfhip_pvrtc_launch(int pass, const cf_pvrtc_surf* tab, uint32_t n, uint32_t items,
+	uint32_t* tex, uint32_t* words, uint8_t* mods, uint32_t wmask, int rgb, uint32_t ox, uint32_t oy, uint32_t flags,
+	hipStream_t stream);
+extern "C" hipError_t cfhip_pvrtc_launch_decode(const void* blocks, uint32_t w, uint32_t h, int rgb, void* out,
+	size_t out_pitch, const void* ref, size_t ref_pitch, unsigned long long* sums, int sse, hipStream_t stream);
 extern "C" hipError_t cfhip_launch_bc15(const cf_kparams* kp, int format, int pixel_type,
 	int snorm, hipStream_t stream);
 
@@ -176,6 +182,8 @@ struct cfhip_ctx {
 	bool staging_busy = false;
 	void* d_mip3d = nullptr;          // 3-D mip generation: the previous level's slices resized in x, y
 	size_t mip3d_cap = 0;
+	void* d_pvrtc = nullptr;          // PVRTC1 encoder state: surface table, texels, colour words, modulation bytes
+	size_t pvrtc_cap = 0;
 	std::map<int, void*> astc_tables; // per-format device tables (built on first use)
 	std::map<int, cfastc::AstcBlobHeader> astc_hdr;   // their headers (sizes the launch's dynamic LDS)
 	std::vector<hipEvent_t> events;   // start/stop pairs of the last call
@@ -1289,6 +1297,7 @@ void cfhip_destroy(cfhip_ctx* ctx)
 	if (ctx->group_up) (void)hipEventDestroy(ctx->group_up);
 	if (ctx->d_batch) (void)hipFree(ctx->d_batch);
 	if (ctx->d_mip3d) (void)hipFree(ctx->d_mip3d);
+	if (ctx->d_pvrtc) (void)hipFree(ctx->d_pvrtc);
 	if (ctx->d_src) (void)hipFree(ctx->d_src);
 	if (ctx->d_out) (void)hipFree(ctx->d_out);
 	delete ctx;
@@ -2339,6 +2348,377 @@ int cfhip_compare_device(cfhip_ctx* ctx, int format, int type, const void* block
 		return rc;
 	return lease.done(!stream_);
 }
+
+} // extern "C"
+
+// ---- PVRTC1 4 bpp (csrc/pvrtc.hip): an entry family of its own, outside the cfhip_surface block contract ----
+static bool pow2(uint32_t v) { return v && !(v & (v - 1u)); }
+
+static int pvrtc_check(int format, int type, uint32_t width, uint32_t height, size_t* bytes)
+{
+	if ((format != CFHIP_FORMAT_PVRTC1_RGB_4BPP && format != CFHIP_FORMAT_PVRTC1_RGBA_4BPP) || type != CFHIP_TYPE_UNORM)
+		return CFHIP_E_UNSUPPORTED;
+	if (!pow2(width) || !pow2(height) || width > 32768u || height > 32768u)
+		return CFHIP_E_INVALID;
+	const size_t bx = width/4u > 2u ? width/4u : 2u, by = height/4u > 2u ? height/4u : 2u;
+	if (bytes) *bytes = bx*by*8u;
+	return CFHIP_OK;
+}
+
+// one pass of the encoder or one decode, timed like every other launch (cfhip_last_kernel_ms / profiling)
+static int pvrtc_timed(cfhip_ctx* ctx, hipStream_t stream, const std::function<hipError_t()>& launch)
+{
+	hipEvent_t a, b;
+	int rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, stream));
+	const hipError_t e = launch();
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "pvrtc launch: %s", hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, stream));
+	return CFHIP_OK;
+}
+
+// refine sweeps per quality level: each level runs the sweeps of the level below first (tests/pvrtc_ref.py
+// LEVEL_SWEEPS; flag 1 = mode trial, 2 = +-1 candidates, 4 = opacity trials)
+static const uint32_t kPvrtcSweeps[5][8] = {{0}, {0}, {0, 1}, {0, 1, 3, 3}, {0, 1, 3, 3, 7, 7, 7, 7}};
+static const uint32_t kPvrtcNumSweeps[5] = {0, 1, 2, 4, 8};
+
+static int pvrtc_encode_body(cfhip_ctx* ctx, StagingLease& lease, const cfhip_surface* surfaces, size_t n,
+	const cfhip_params* p, bool device_mem)
+{
+	const char* what = device_mem ? "pvrtc_encode_device" : "pvrtc_encode";
+	if (!surfaces || !n || !p)
+		return fail(ctx, CFHIP_E_INVALID, "%s: no surfaces or params", what);
+	int rc = pvrtc_check(p->format, p->type, 4, 4, nullptr);
+	if (rc != CFHIP_OK)
+		return fail(ctx, rc, "%s: (format %d, type %d) is not PVRTC1 4 bpp UNorm", what, p->format, p->type);
+	if (p->quality < CFHIP_QUALITY_LOWEST || p->quality > CFHIP_QUALITY_HIGHEST)
+		return fail(ctx, CFHIP_E_INVALID, "%s: bad quality %d", what, p->quality);
+	if (n > (1u << 20))
+		return fail(ctx, CFHIP_E_INVALID, "%s: too many surfaces", what);
+	const bool rgb = p->format == CFHIP_FORMAT_PVRTC1_RGB_4BPP;
+	uint32_t wmask = 0;
+	for (int c = 0; c < 4; ++c)
+		wmask |= p->mask_rgba[c] ? 1u << c : 0u;
+	if (rgb)
+		wmask &= 7u;
+	std::vector<cf_pvrtc_surf> tab(n);
+	std::vector<size_t> src_off(n), span(n), out_off(n), out_bytes(n);
+	uint64_t blocks = 0, phase = 0;
+	size_t src_total = 0, out_total = 0;
+	for (size_t i = 0; i < n; ++i) {
+		const cfhip_surface& s = surfaces[i];
+		const size_t pb = pixel_bytes(s.pixel_type);
+		size_t bytes = 0;
+		if (!s.pixels || !s.out || !pb)
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: bad pixels/out/pixel_type", what, i);
+		if (pvrtc_check(p->format, p->type, s.width, s.height, &bytes) != CFHIP_OK)
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: %ux%u is not a power-of-two size", what, i, s.width,
+				s.height);
+		const size_t row = (size_t)s.width*pb;
+		const size_t apitch = (size_t)(s.row_pitch_bytes < 0 ? -s.row_pitch_bytes : s.row_pitch_bytes);
+		if (apitch < row || apitch % pb)
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: |row pitch| %zu must be >= %zu and a multiple of %zu",
+				what, i, apitch, row, pb);
+		if (device_mem && ((uintptr_t)s.pixels % pb))
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: pixels not aligned to the pixel size", what, i);
+		if (s.out_capacity < bytes)
+			return fail(ctx, CFHIP_E_CAPACITY, "%s: surface %zu: out_capacity %zu < %zu", what, i, s.out_capacity,
+				bytes);
+		cf_pvrtc_surf& t = tab[i];
+		t.pitch = (long long)s.row_pitch_bytes;
+		t.pix = (uint32_t)s.pixel_type;
+		t.w = s.width; t.h = s.height;
+		t.bx = s.width/4u > 2u ? s.width/4u : 2u;
+		t.by = s.height/4u > 2u ? s.height/4u : 2u;
+		t.blk_off = (uint32_t)blocks;
+		t.ph_off = (uint32_t)phase;
+		t.pad = 0;
+		blocks += (uint64_t)t.bx*t.by;
+		phase += (uint64_t)(t.bx/2u)*(t.by/2u);
+		if (blocks*16u >= (1ull << 31))
+			return fail(ctx, CFHIP_E_INVALID, "%s: more than 2^31 texels in one call", what);
+		span[i] = (size_t)(s.height - 1u)*apitch + row;
+		src_off[i] = src_total;
+		src_total += (span[i] + 255u) & ~(size_t)255u;
+		out_bytes[i] = bytes;
+		out_off[i] = out_total;
+		out_total += (bytes + 255u) & ~(size_t)255u;
+	}
+	// scratch: the table, then the texels, the colour words and the modulation bytes
+	const size_t tab_bytes = (n*sizeof(cf_pvrtc_surf) + 255u) & ~(size_t)255u;
+	const size_t tex_off = tab_bytes, word_off = tex_off + (size_t)blocks*64u, mod_off = word_off + (size_t)blocks*4u;
+	const size_t scratch = mod_off + (size_t)blocks*16u;
+	const hipStream_t stream = lease.stream;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_pvrtc, &ctx->pvrtc_cap, scratch);
+	if (rc == CFHIP_OK && !device_mem)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, src_total);
+	if (rc == CFHIP_OK && !device_mem)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, out_total);
+	if (rc != CFHIP_OK)
+		return rc;
+	for (size_t i = 0; i < n; ++i) {
+		const cfhip_surface& s = surfaces[i];
+		const size_t lead = s.row_pitch_bytes < 0 ? (size_t)(s.height - 1u)*(size_t)(-s.row_pitch_bytes) : 0u;
+		if (device_mem) {
+			tab[i].src = static_cast<const uint8_t*>(s.pixels);
+			tab[i].out = static_cast<uint8_t*>(s.out);
+		} else {
+			// the whole span of rows as it lies in memory (bottom-up sources included), one copy
+			uint8_t* d = static_cast<uint8_t*>(ctx->d_src) + src_off[i];
+			HIP_TRY(ctx, hipMemcpyAsync(d, static_cast<const uint8_t*>(s.pixels) - lead, span[i], hipMemcpyHostToDevice,
+				stream));
+			tab[i].src = d + lead;
+			tab[i].out = static_cast<uint8_t*>(ctx->d_out) + out_off[i];
+		}
+	}
+	uint8_t* base = static_cast<uint8_t*>(ctx->d_pvrtc);
+	const cf_pvrtc_surf* d_tab = reinterpret_cast<const cf_pvrtc_surf*>(base);
+	uint32_t* tex = reinterpret_cast<uint32_t*>(base + tex_off);
+	uint32_t* words = reinterpret_cast<uint32_t*>(base + word_off);
+	uint8_t* mods = base + mod_off;
+	// pageable source: the runtime stages the copy before returning, so `tab` may die
+	HIP_TRY(ctx, hipMemcpyAsync(base, tab.data(), n*sizeof(cf_pvrtc_surf), hipMemcpyHostToDevice, stream));
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = "cfhip_pvrtc_refine_kernel";
+	const uint32_t nb = (uint32_t)blocks, np = (uint32_t)phase, ns = (uint32_t)n;
+	auto pass = [&](int k, uint32_t items, uint32_t ox, uint32_t oy, uint32_t flags) {
+		return pvrtc_timed(ctx, stream, [&]() {
+			return cfhip_pvrtc_launch(k, d_tab, ns, items, tex, words, mods, wmask, rgb ? 1 : 0, ox, oy, flags, stream);
+		});
+	};
+	rc = pass(0, nb, 0, 0, 0);
+	if (rc == CFHIP_OK) rc = pass(1, nb, 0, 0, 0);
+	if (rc == CFHIP_OK) rc = pass(2, nb, 0, 0, 0);
+	for (uint32_t sw = 0; rc == CFHIP_OK && sw < kPvrtcNumSweeps[p->quality]; ++sw)
+		for (uint32_t ph = 0; rc == CFHIP_OK && ph < 4; ++ph)
+			rc = pass(3, np, ph & 1u, ph >> 1, kPvrtcSweeps[p->quality][sw]);
+	if (rc == CFHIP_OK) rc = pass(4, nb, 0, 0, 0);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (device_mem)
+		return CFHIP_OK;
+	for (size_t i = 0; i < n; ++i)
+		HIP_TRY(ctx, hipMemcpyAsync(surfaces[i].out, static_cast<uint8_t*>(ctx->d_out) + out_off[i], out_bytes[i],
+			hipMemcpyDeviceToHost, stream));
+	return CFHIP_OK;
+}
+
+static int pvrtc_encode_impl(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n, const cfhip_params* p,
+	bool device_mem, hipStream_t user_stream)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	StagingLease lease(ctx, user_stream ? user_stream : ctx->stream);
+	try {
+		const int rc = pvrtc_encode_body(ctx, lease, surfaces, n, p, device_mem);
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!user_stream);
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "pvrtc_encode: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "pvrtc_encode: unknown exception");
+	}
+}
+
+// the checks every PVRTC decode entry point makes before anything is enqueued
+static int pvrtc_decode_check(cfhip_ctx* ctx, const char* what, int format, int type, const void* blocks,
+	uint32_t width, uint32_t height, size_t* payload)
+{
+	const int rc = pvrtc_check(format, type, width, height, payload);
+	if (rc == CFHIP_E_UNSUPPORTED)
+		return fail(ctx, rc, "%s: (format %d, type %d) is not PVRTC1 4 bpp UNorm", what, format, type);
+	if (rc != CFHIP_OK)
+		return fail(ctx, rc, "%s: %ux%u is not a power-of-two size", what, width, height);
+	if ((uint64_t)width*height > (1ull << 30))
+		return fail(ctx, CFHIP_E_INVALID, "%s: surface %ux%u too large for one launch", what, width, height);
+	if (!blocks)
+		return fail(ctx, CFHIP_E_INVALID, "%s: blocks is NULL", what);
+	return CFHIP_OK;
+}
+
+static int pvrtc_decode_launch(cfhip_ctx* ctx, int format, const void* blocks, uint32_t width, uint32_t height,
+	void* out, size_t out_pitch, const void* ref, size_t ref_pitch, unsigned long long* sums, bool sse,
+	hipStream_t stream)
+{
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = sse ? "cfhip_pvrtc_decode_sse_kernel" : "cfhip_pvrtc_decode_kernel";
+	const int rgb = format == CFHIP_FORMAT_PVRTC1_RGB_4BPP ? 1 : 0;
+	return pvrtc_timed(ctx, stream, [&]() {
+		return cfhip_pvrtc_launch_decode(blocks, width, height, rgb, out, out_pitch, ref, ref_pitch, sums, sse ? 1 : 0,
+			stream);
+	});
+}
+
+extern "C" {
+
+int cfhip_pvrtc_query(int format, int type, uint32_t width, uint32_t height, size_t* bytes)
+{
+	return pvrtc_check(format, type, width, height, bytes);
+}
+
+int cfhip_pvrtc_encode(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n_surfaces, const cfhip_params* params)
+{
+	return pvrtc_encode_impl(ctx, surfaces, n_surfaces, params, false, nullptr);
+}
+
+int cfhip_pvrtc_encode_device(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n_surfaces,
+	const cfhip_params* params, void* stream)
+{
+	return pvrtc_encode_impl(ctx, surfaces, n_surfaces, params, true, static_cast<hipStream_t>(stream));
+}
+
+int cfhip_pvrtc_decode(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes, uint32_t width,
+	uint32_t height, void* out, size_t out_capacity)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	size_t payload = 0;
+	int rc = pvrtc_decode_check(ctx, "pvrtc_decode", format, type, blocks, width, height, &payload);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!out)
+		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode: out is NULL");
+	if (blocks_bytes < payload)
+		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode: blocks_bytes %zu < %zu", blocks_bytes, payload);
+	const size_t out_bytes = (size_t)width*height*4u;
+	if (out_capacity < out_bytes)
+		return fail(ctx, CFHIP_E_CAPACITY, "pvrtc_decode: out_capacity %zu < %zu", out_capacity, out_bytes);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, ctx->stream);
+	const hipStream_t stream = lease.stream;
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, payload);
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, out_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, payload, hipMemcpyHostToDevice, stream));
+	rc = pvrtc_decode_launch(ctx, format, ctx->d_src, width, height, ctx->d_out, (size_t)width*4u, nullptr, 0, nullptr,
+		false, stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+	return lease.done(true);
+}
+
+int cfhip_pvrtc_decode_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width,
+	uint32_t height, void* out, size_t out_pitch_bytes, void* stream_)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	int rc = pvrtc_decode_check(ctx, "pvrtc_decode_device", format, type, blocks, width, height, nullptr);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!out || out_pitch_bytes < (size_t)width*4u || ((uintptr_t)out & 3u) || (out_pitch_bytes & 3u) ||
+		((uintptr_t)blocks & 3u))
+		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_device: out, pitch and blocks must be 4-byte aligned, "
+			"pitch >= %zu", (size_t)width*4u);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	// no staging buffer is touched: the lease only carries the synchronisation rule of the stream
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	rc = pvrtc_decode_launch(ctx, format, blocks, width, height, out, out_pitch_bytes, nullptr, 0, nullptr, false,
+		lease.stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	return lease.done(!stream_);
+}
+
+int cfhip_pvrtc_decode_sse(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes,
+	uint32_t width, uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t sse[4])
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	size_t payload = 0;
+	int rc = pvrtc_decode_check(ctx, "pvrtc_decode_sse", format, type, blocks, width, height, &payload);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!ref_rgba8 || !sse)
+		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse: NULL reference or result");
+	if (blocks_bytes < payload)
+		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse: blocks_bytes %zu < %zu", blocks_bytes, payload);
+	const size_t row = (size_t)width*4u;
+	if (ref_pitch_bytes < row)
+		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse: reference pitch %zu < %zu", ref_pitch_bytes, row);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, ctx->stream);
+	const hipStream_t stream = lease.stream;
+	// d_src: the payload; d_out: the reference, tightly packed, then the four sums
+	const size_t sum_off = (row*height + 15u) & ~(size_t)15u;
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, payload);
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, sum_off + 32u);
+	if (rc != CFHIP_OK)
+		return rc;
+	unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(ctx->d_out) + sum_off);
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, payload, hipMemcpyHostToDevice, stream));
+	HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_out, row, ref_rgba8, ref_pitch_bytes, row, height, hipMemcpyHostToDevice,
+		stream));
+	HIP_TRY(ctx, hipMemsetAsync(d_sum, 0, 32, stream));
+	rc = pvrtc_decode_launch(ctx, format, ctx->d_src, width, height, nullptr, 0, ctx->d_out, row, d_sum, true, stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	unsigned long long sums[4] = {0, 0, 0, 0};
+	HIP_TRY(ctx, hipMemcpyAsync(sums, d_sum, 32, hipMemcpyDeviceToHost, stream));
+	rc = lease.done(true);
+	if (rc != CFHIP_OK)
+		return rc;
+	for (int c = 0; c < 4; ++c)
+		sse[c] = (uint64_t)sums[c];
+	return CFHIP_OK;
+}
+
+int cfhip_pvrtc_decode_sse_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width,
+	uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t* sse_device, void* stream_)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	int rc = pvrtc_decode_check(ctx, "pvrtc_decode_sse_device", format, type, blocks, width, height, nullptr);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!ref_rgba8 || !sse_device || ref_pitch_bytes < (size_t)width*4u || ((uintptr_t)ref_rgba8 & 3u) ||
+		(ref_pitch_bytes & 3u) || ((uintptr_t)blocks & 3u))
+		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse_device: reference, pitch and blocks must be non-NULL and "
+			"4-byte aligned, pitch >= %zu", (size_t)width*4u);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	unsigned long long* sum = reinterpret_cast<unsigned long long*>(sse_device);
+	HIP_TRY(ctx, hipMemsetAsync(sum, 0, 32, lease.stream));
+	rc = pvrtc_decode_launch(ctx, format, blocks, width, height, nullptr, 0, ref_rgba8, ref_pitch_bytes, sum, true,
+		lease.stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	return lease.done(!stream_);
+}
+
+} // extern "C"
+
+extern "C" {
 
 float cfhip_last_kernel_ms(cfhip_ctx* ctx)
 {

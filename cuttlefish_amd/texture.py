@@ -43,7 +43,7 @@ from .api import Alpha, ColorSpace, Format, Quality, Type
 _NATIVE_SRGB = {Format.R8G8B8, Format.B8G8R8, Format.R8G8B8A8, Format.B8G8R8A8, Format.A8B8G8R8,
                 Format.BC1_RGB, Format.BC1_RGBA, Format.BC2, Format.BC3, Format.BC7,
                 Format.ETC2_R8G8B8, Format.ETC2_R8G8B8A1, Format.ETC2_R8G8B8A8} | \
-    {Format(v) for v in range(43, 57)}
+    {Format(v) for v in range(43, 57)} | {Format(v) for v in range(57, 63)}     # ASTC, PVRTC (Texture.cpp:438-443)
 
 
 class Dimension(enum.IntEnum):      # Texture::Dimension (Texture.h:48-54)
@@ -123,6 +123,18 @@ def image_index(*args) -> Tuple[int, int, int]:
     return (face, mip, depth)
 
 
+def _rgba8_of(image: np.ndarray) -> np.ndarray:
+    """an image as RGBA8, quantised as the PVRTC encoder quantises float sources: round(clamp(f, 0, 1) * 255),
+    NaN -> 0, in float32"""
+    if image.dtype == np.uint8:
+        return image
+    f = image.astype(np.float32)
+    f = np.minimum(np.where(f > 0, f, np.float32(0)), np.float32(1)).astype(np.float32)
+    v = (f * np.float32(255)).astype(np.float32)
+    r = np.floor(v)
+    return (r + ((v - r) >= np.float32(0.5))).astype(np.uint8)
+
+
 def _as_image(image) -> Optional[np.ndarray]:
     """What Image::convert(RGBAF) keeps of an image on this path: an (h, w, 4) array.  uint8 / float16
     arrays stay as they are (the kernels read them as the reference's RGBAF values, toColorBlock
@@ -147,7 +159,11 @@ class Texture:
         """Texture::isFormatValid(format, type[, fileType]) (Texture.cpp:318-419)."""
         try:
             format, type = Format(format), Type(type)
-            api.query(format, type)
+            if format in api.PVRTC_FORMATS:
+                if type != Type.UNorm:
+                    return False
+            else:
+                api.query(format, type)
         except (ValueError, api.CfhipError):
             return False
         if file_type is None:
@@ -187,6 +203,8 @@ class Texture:
             format = Format(format)
         except ValueError:
             return 0
+        if format in api.PVRTC_FORMATS:
+            return (4, 4, 8)[i]                     # Texture.cpp:596-773
         for t in Type:
             try:
                 return api.query(format, t)[i]
@@ -208,12 +226,13 @@ class Texture:
 
     @staticmethod
     def min_width(format) -> int:
-        """Texture::minWidth (Texture.cpp:775-855): the block width of the formats of this backend."""
-        return Texture._block(format, 0)
+        """Texture::minWidth (Texture.cpp:775-855): the block width of the formats of this backend; 8 for PVRTC1
+        4 bpp, whose levels are never smaller than 2 x 2 blocks."""
+        return 8 if Format(format) in api.PVRTC_FORMATS else Texture._block(format, 0)
 
     @staticmethod
     def min_height(format) -> int:
-        return Texture._block(format, 1)
+        return 8 if Format(format) in api.PVRTC_FORMATS else Texture._block(format, 1)
 
     @staticmethod
     def file_type(file_name: str) -> FileType:
@@ -579,7 +598,14 @@ class Texture:
         if not (format == Format.BC6H or int(format) < int(Format.BC1_RGB)):
             flat = [im.astype(np.float32) if im.dtype == np.float16 else im for im in flat]
         try:
-            outs = self._context().encode(flat, params)
+            if format in api.PVRTC_FORMATS:
+                # PVRTC1 block order is defined for power-of-two grids only: other sizes are refused
+                if any(im.shape[0] & (im.shape[0] - 1) or im.shape[1] & (im.shape[1] - 1) for im in flat):
+                    return False
+                flat = [im.astype(np.float32) if im.dtype == np.float16 else im for im in flat]
+                outs = self._context().encode_pvrtc(flat, params)
+            else:
+                outs = self._context().encode(flat, params)
         except api.CfhipError as e:
             if e.code == api.E_UNSUPPORTED:
                 return False  # createConverter -> nullptr -> convert() returns false
@@ -639,6 +665,8 @@ class Texture:
         if self._alpha == Alpha.None_ or not self.has_alpha(self._format):
             mask[3] = False
         ctx = self._context()
+        if self._format in api.PVRTC_FORMATS:
+            return self._compare_pvrtc(ctx, source, mask, ssim)
         results = []
         for m, level in enumerate(self._textures):
             for d, dep in enumerate(level):
@@ -651,6 +679,27 @@ class Texture:
             raise ValueError("compare: no channel compared")
         peak = max(r.peak() for r in results)
         pooled = float("inf") if sse == 0.0 else 10.0 * float(np.log10(peak * peak * n / sse))
+        return results, pooled
+
+    def _compare_pvrtc(self, ctx, source, mask, ssim):
+        """compare() for PVRTC1 4 bpp: PSNR from the fused decode + SSE (cfhip_pvrtc_decode_sse) against the
+        source quantised to RGBA8 as the encoder quantises it.  No SSIM and no error map for PVRTC.  Returns
+        (per surface: [sse r, g, b, a], the pooled PSNR over the compared channels)."""
+        if ssim:
+            raise ValueError("compare: PVRTC has no SSIM (pass ssim=False)")
+        chans = [c for c in range(4) if mask[c]]
+        if not chans:
+            raise ValueError("compare: no channel compared")
+        results = []
+        for m, level in enumerate(self._textures):
+            for d, dep in enumerate(level):
+                for f, payload in enumerate(dep):
+                    ref = _rgba8_of(source._images[m][d][f])
+                    results.append(ctx.decode_pvrtc_sse(payload, ref, self._format, self._type))
+        sse = sum(r[c] for r in results for c in chans)
+        n = sum(int(np.prod(source._images[m][d][f].shape[:2]))
+                for m, level in enumerate(self._textures) for d, dep in enumerate(level) for f in range(len(dep)))
+        pooled = float("inf") if sse == 0 else 10.0 * float(np.log10(255.0 * 255.0 * n * len(chans) / sse))
         return results, pooled
 
     # ---- saving (Texture.cpp:1636-1685) --------------------------------------------------------

@@ -96,7 +96,16 @@ enum cfhip_format {
 	CFHIP_FORMAT_ASTC_10x8 = 53,
 	CFHIP_FORMAT_ASTC_10x10 = 54,
 	CFHIP_FORMAT_ASTC_12x10 = 55,
-	CFHIP_FORMAT_ASTC_12x12 = 56
+	CFHIP_FORMAT_ASTC_12x12 = 56,
+	/* PVRTC (Texture.h:124-129).  cfhip_query, cfhip_encode*, cfhip_decode*, cfhip_decoded_layout and
+	 * cfhip_compare* answer CFHIP_E_UNSUPPORTED for all six: PVRTC1 4 bpp has the cfhip_pvrtc_* entries below;
+	 * the 2 bpp and PVRTC2 formats are not built. */
+	CFHIP_FORMAT_PVRTC1_RGB_2BPP = 57,
+	CFHIP_FORMAT_PVRTC1_RGBA_2BPP = 58,
+	CFHIP_FORMAT_PVRTC1_RGB_4BPP = 59,
+	CFHIP_FORMAT_PVRTC1_RGBA_4BPP = 60,
+	CFHIP_FORMAT_PVRTC2_RGBA_2BPP = 61,
+	CFHIP_FORMAT_PVRTC2_RGBA_4BPP = 62
 };
 
 /* cuttlefish::Texture::Type (Texture.h:135-143) */
@@ -476,7 +485,41 @@ int cfhip_compare_device(cfhip_ctx* ctx, int format, int type, const void* block
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device,
 	float* block_errors_device, size_t block_errors_capacity, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_decode*, cfhip_compare* or cfhip_image_ops_device call on
+/* ---- PVRTC1 4 bpp (formats 59 RGB, 60 RGBA; type UNorm) ----
+ *
+ * PVRTC1 is outside the cfhip_surface block contract: blocks are stored in twiddled (Morton) order, a level is never
+ * smaller than 2 x 2 blocks, sizes must be powers of two, and every texel blends the colours of four blocks with
+ * wrap-around.  So it has its own entries.  Payload of a w x h level: max(w/4, 2) * max(h/4, 2) * 8 bytes; a surface
+ * under 8 texels repeats itself (texel (x mod w, y mod h)) in the encoder.  The decoded layout is RGBA8 (alpha 255 for
+ * the RGB format). */
+
+/* Payload bytes of a w x h level.  CFHIP_E_UNSUPPORTED for every format but 59 / 60 and for types other than UNorm;
+ * CFHIP_E_INVALID for sizes that are not powers of two (or above 32768).  Pure, needs no device. */
+int cfhip_pvrtc_query(int format, int type, uint32_t width, uint32_t height, size_t* bytes);
+
+/* Encode with the cfhip_surface / cfhip_params of cfhip_encode: same pixel types and pitch rules, negative pitch
+ * included (|pitch| a multiple of the pixel size); out_capacity >= the cfhip_pvrtc_query size.  RGBA32F / RGBA16F
+ * are quantised as the host pipeline quantises them (toColorBlock).  mask_rgba weights the channels of the error.
+ * One launch per pass for all surfaces of the call.  Blocking.  The device form takes device pointers and the
+ * stream rules of cfhip_encode_device; both produce identical payloads. */
+int cfhip_pvrtc_encode(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n_surfaces,
+	const cfhip_params* params);
+int cfhip_pvrtc_encode_device(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n_surfaces,
+	const cfhip_params* params, void* stream);
+
+/* Decode to RGBA8 rows (the cfhip_decode rules; device buffers 4-byte aligned). */
+int cfhip_pvrtc_decode(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes,
+	uint32_t width, uint32_t height, void* out, size_t out_capacity);
+int cfhip_pvrtc_decode_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width,
+	uint32_t height, void* out, size_t out_pitch_bytes, void* stream);
+/* Decode and compare against an RGBA8 reference in one pass: exact per-channel sums of squared differences (the
+ * cfhip_decode_sse rules). */
+int cfhip_pvrtc_decode_sse(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes,
+	uint32_t width, uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t sse[4]);
+int cfhip_pvrtc_decode_sse_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width,
+	uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t* sse_device, void* stream);
+
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare* or cfhip_image_ops_device call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
