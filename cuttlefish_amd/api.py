@@ -673,7 +673,7 @@ class Context:
 
     def decode_pvrtc_sse_device(self, blocks: int, fmt, width: int, height: int, ref: int, ref_pitch_bytes: int,
                                 sse: int, typ=Type.UNorm, stream: int = 0):
-        """Device path of decode_pvrtc_sse: sse = device pointer to four uint64 (zeroed by the call)."""
+        """Device path of decode_pvrtc_sse: sse = device pointer to four uint64 (8-byte aligned, zeroed by the call)."""
         self._check(self._lib.cfhip_pvrtc_decode_sse_device(
             self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(ref)),
             ref_pitch_bytes, ctypes.c_void_p(int(sse)), ctypes.c_void_p(stream) if stream else None))
@@ -777,7 +777,7 @@ class Context:
 
     def decode_sse_device(self, blocks: int, fmt, typ, width: int, height: int, ref: int, ref_pitch_bytes: int,
                           sse: int, stream: int = 0):
-        """Device path of decode_sse: sse = device pointer to four uint64 (zeroed by the call)."""
+        """Device path of decode_sse: sse = device pointer to four uint64 (8-byte aligned, zeroed by the call)."""
         self._check(self._lib.cfhip_decode_sse_device(
             self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(ref)),
             ref_pitch_bytes, ctypes.c_void_p(int(sse)), ctypes.c_void_p(stream) if stream else None))

@@ -2253,6 +2253,9 @@ int cfhip_decode_sse_device(cfhip_ctx* ctx, int format, int type, const void* bl
 	if (ref_pitch_bytes < (size_t)width*4u)
 		return fail(ctx, CFHIP_E_INVALID, "decode_sse_device: reference pitch %zu < %zu", ref_pitch_bytes,
 			(size_t)width*4u);
+	// the kernels add to the four sums with 64-bit atomics
+	if ((uintptr_t)sse_device % 8u != 0)
+		return fail(ctx, CFHIP_E_INVALID, "decode_sse_device: sse_device must be 8-byte aligned");
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
 	unsigned long long* sum = reinterpret_cast<unsigned long long*>(sse_device);
@@ -2705,6 +2708,9 @@ int cfhip_pvrtc_decode_sse_device(cfhip_ctx* ctx, int format, int type, const vo
 		(ref_pitch_bytes & 3u) || ((uintptr_t)blocks & 3u))
 		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse_device: reference, pitch and blocks must be non-NULL and "
 			"4-byte aligned, pitch >= %zu", (size_t)width*4u);
+	// the kernel adds to the four sums with 64-bit atomics
+	if ((uintptr_t)sse_device % 8u != 0)
+		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse_device: sse_device must be 8-byte aligned");
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
 	unsigned long long* sum = reinterpret_cast<unsigned long long*>(sse_device);

@@ -375,7 +375,8 @@ int cfhip_decode_device(cfhip_ctx* ctx, int format, int type, const void* blocks
 int cfhip_decode_sse(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes,
 	uint32_t width, uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t sse[4]);
 
-/* The same on device buffers: sse_device = four uint64 on the device, zeroed by the call on the stream. */
+/* The same on device buffers: sse_device = four uint64 on the device, zeroed by the call on the stream.  It must
+ * be 8-byte aligned (the kernels add to it with 64-bit atomics); otherwise CFHIP_E_INVALID, nothing enqueued. */
 int cfhip_decode_sse_device(cfhip_ctx* ctx, int format, int type, const void* blocks,
 	uint32_t width, uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes,
 	uint64_t* sse_device, void* stream);
@@ -513,7 +514,8 @@ int cfhip_pvrtc_decode(cfhip_ctx* ctx, int format, int type, const void* blocks,
 int cfhip_pvrtc_decode_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width,
 	uint32_t height, void* out, size_t out_pitch_bytes, void* stream);
 /* Decode and compare against an RGBA8 reference in one pass: exact per-channel sums of squared differences (the
- * cfhip_decode_sse rules). */
+ * cfhip_decode_sse rules).  The device form's sse_device (four uint64, zeroed by the call on the stream) must be
+ * 8-byte aligned; otherwise CFHIP_E_INVALID, nothing enqueued. */
 int cfhip_pvrtc_decode_sse(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes,
 	uint32_t width, uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t sse[4]);
 int cfhip_pvrtc_decode_sse_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width,
