@@ -188,7 +188,8 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_decoded_layout", "cfhip_decode", "cfhip_decode_device", "cfhip_decode_sse",
            "cfhip_decode_sse_device", "cfhip_image_ops_device", "cfhip_compare", "cfhip_compare_device",
            "cfhip_pvrtc_query", "cfhip_pvrtc_encode", "cfhip_pvrtc_encode_device", "cfhip_pvrtc_decode",
-           "cfhip_pvrtc_decode_device", "cfhip_pvrtc_decode_sse", "cfhip_pvrtc_decode_sse_device"]
+           "cfhip_pvrtc_decode_device", "cfhip_pvrtc_decode_sse", "cfhip_pvrtc_decode_sse_device",
+           "cfhip_std_unpack", "cfhip_std_unpack_device", "cfhip_std_compare", "cfhip_std_compare_device"]
 
 
 class Layout(enum.IntEnum):
@@ -203,13 +204,14 @@ class Layout(enum.IntEnum):
     RG16 = 7
     RG16_SNorm = 8
     RGBA16F = 9
+    RGBA32F = 10                # what Context.unpack returns for the standard formats
 
 
 # layout -> (channels, numpy dtype) of the decoded array
 LAYOUT_ARRAY = {Layout.RGBA8: (4, np.uint8), Layout.R8: (1, np.uint8), Layout.R8_SNorm: (1, np.int8),
                 Layout.RG8: (2, np.uint8), Layout.RG8_SNorm: (2, np.int8), Layout.R16: (1, np.uint16),
                 Layout.R16_SNorm: (1, np.int16), Layout.RG16: (2, np.uint16), Layout.RG16_SNorm: (2, np.int16),
-                Layout.RGBA16F: (4, np.float16)}
+                Layout.RGBA16F: (4, np.float16), Layout.RGBA32F: (4, np.float32)}
 
 COMPARE_SSIM = 1                # CFHIP_COMPARE_SSIM
 
@@ -225,8 +227,9 @@ class Comparison:
     """What Context.compare returns: the metrics of one surface (cfhip_compare_result) and, when asked, the
     (blocks_y, blocks_x) float32 map of per-block SSE."""
 
-    def __init__(self, res: CompareResult, layout: Layout, block_errors: Optional[np.ndarray] = None):
+    def __init__(self, res: CompareResult, layout: Layout, block_errors: Optional[np.ndarray] = None, typ=None):
         self.layout = Layout(layout)
+        self.type = None if typ is None else Type(typ)      # set for the standard formats (layout RGBA32F)
         self.texels = int(res.texels)
         self.error_blocks = int(res.error_blocks)
         self.channels = int(res.channels)
@@ -242,8 +245,12 @@ class Comparison:
         return [c for c in range(4) if (self.channels >> c) & 1]
 
     def peak(self, channels=None) -> float:
-        """The data range: 1 for UNorm layouts, 2 for SNorm layouts, the largest reference value for HDR."""
-        if self.layout == Layout.RGBA16F:
+        """The data range: 1 for UNorm layouts, 2 for SNorm layouts, the largest reference value for HDR.  Standard
+        formats: 1 for UNorm, 2 for SNorm, the largest reference value of the compared channels for the other
+        types."""
+        if self.layout == Layout.RGBA32F and self.type in (Type.UNorm, Type.SNorm):
+            return 2.0 if self.type == Type.SNorm else 1.0
+        if self.layout in (Layout.RGBA16F, Layout.RGBA32F):
             chans = self.compared() if channels is None else list(channels)
             return max(self.ref_max[c] for c in chans)
         return 2.0 if self.layout.name.endswith("SNorm") else 1.0
@@ -433,6 +440,21 @@ def load_library(path: Optional[str] = None):
                                                 ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t,
                                                 ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_pvrtc_decode_sse_device.restype = ctypes.c_int
+    L.cfhip_std_unpack.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                   ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]
+    L.cfhip_std_unpack.restype = ctypes.c_int
+    L.cfhip_std_unpack_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t,
+                                          ctypes.c_void_p]
+    L.cfhip_std_unpack_device.restype = ctypes.c_int
+    L.cfhip_std_compare.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t,
+                                    ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t,
+                                    u8p, ctypes.c_uint, ctypes.POINTER(CompareResult)]
+    L.cfhip_std_compare.restype = ctypes.c_int
+    L.cfhip_std_compare_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                           ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int,
+                                           ctypes.c_size_t, u8p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_std_compare_device.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -827,6 +849,53 @@ class Context:
             int(ref_pixel_type), ref_pitch_bytes, self._mask(mask), COMPARE_SSIM if ssim else 0,
             ctypes.c_void_p(int(result)), ctypes.c_void_p(int(block_errors)) if block_errors else None,
             block_errors_capacity, ctypes.c_void_p(stream) if stream else None))
+
+    def unpack(self, payload: np.ndarray, fmt, typ, width: int, height: int) -> np.ndarray:
+        """The payload of a standard (uncompressed) format, formats 1..28, back to texels on the GPU ->
+        (height, width, 4) float32; channels the format does not store read 0, 0, 0, 1.  Raises (E_UNSUPPORTED) for
+        block formats, PVRTC and illegal (format, type) pairs."""
+        pixels = np.ascontiguousarray(payload, dtype=np.uint8)
+        out = np.empty((height, width, 4), np.float32)
+        self._check(self._lib.cfhip_std_unpack(self._h, int(fmt), int(typ), pixels.ctypes.data, pixels.nbytes, width,
+                                               height, out.ctypes.data, out.nbytes))
+        return out
+
+    def unpack_device(self, pixels: int, fmt, typ, width: int, height: int, out: int, out_pitch_bytes: int,
+                      stream: int = 0):
+        """Device path of unpack: pixels (any alignment) / out (RGBA32F rows out_pitch_bytes apart, 4-byte aligned)
+        are device pointers as ints.  stream 0 = the context's stream (the call then synchronises)."""
+        self._check(self._lib.cfhip_std_unpack_device(
+            self._h, int(fmt), int(typ), ctypes.c_void_p(int(pixels)) if pixels else None, width, height,
+            ctypes.c_void_p(int(out)) if out else None, out_pitch_bytes, ctypes.c_void_p(stream) if stream else None))
+
+    def compare_std(self, payload: np.ndarray, ref: np.ndarray, fmt, typ=Type.UNorm, mask=None,
+                    ssim: bool = False) -> Comparison:
+        """compare() for the standard formats: the payload's pixels, converted as unpack() converts them, against an
+        (h, w, 4) uint8, float16 or float32 reference.  SSE and reference maxima for every type, log SSE for Float
+        and UFloat, SSIM (ssim=True) for UNorm and SNorm (NaN otherwise).  No block error map."""
+        ref = np.asarray(ref)
+        pix = {np.dtype(np.uint8): PixelType.RGBA8, np.dtype(np.float32): PixelType.RGBA32F,
+               np.dtype(np.float16): PixelType.RGBA16F}.get(ref.dtype)
+        if ref.ndim != 3 or ref.shape[2] != 4 or pix is None:
+            raise ValueError("reference must be (h, w, 4) uint8, float16 or float32")
+        ref = np.ascontiguousarray(ref)
+        h, w = ref.shape[:2]
+        pixels = np.ascontiguousarray(payload, dtype=np.uint8)
+        res = CompareResult()
+        self._check(self._lib.cfhip_std_compare(
+            self._h, int(fmt), int(typ), pixels.ctypes.data, pixels.nbytes, w, h, ref.ctypes.data, int(pix),
+            ref.strides[0], self._mask(mask), COMPARE_SSIM if ssim else 0, ctypes.byref(res)))
+        return Comparison(res, Layout.RGBA32F, None, typ=typ)
+
+    def compare_std_device(self, pixels: int, fmt, typ, width: int, height: int, ref: int, ref_pixel_type,
+                           ref_pitch_bytes: int, result: int, mask=None, ssim: bool = False, stream: int = 0):
+        """Device path of compare_std: pixels / ref / result (one cfhip_compare_result) are device pointers as
+        ints.  stream 0 = the context's stream (the call then synchronises)."""
+        self._check(self._lib.cfhip_std_compare_device(
+            self._h, int(fmt), int(typ), ctypes.c_void_p(int(pixels)) if pixels else None, width, height,
+            ctypes.c_void_p(int(ref)) if ref else None, int(ref_pixel_type), ref_pitch_bytes, self._mask(mask),
+            COMPARE_SSIM if ssim else 0, ctypes.c_void_p(int(result)) if result else None,
+            ctypes.c_void_p(stream) if stream else None))
 
     def last_kernel_ms(self) -> float:
         return float(self._lib.cfhip_last_kernel_ms(self._h))

@@ -126,7 +126,9 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  # PVRTC1 4 bpp (csrc/pvrtc.hip): the encoder's passes and the decoder
                  "cfhip_pvrtc_load_kernel", "cfhip_pvrtc_init_kernel", "cfhip_pvrtc_mod_kernel",
                  "cfhip_pvrtc_refine_kernel", "cfhip_pvrtc_pack_kernel", "cfhip_pvrtc_decode_kernel",
-                 "cfhip_pvrtc_decode_sse_kernel")
+                 "cfhip_pvrtc_decode_sse_kernel",
+                 # the standard formats back to texels (csrc/std_unpack.hip) and their Pass A (csrc/compare.hip)
+                 "cfhip_std_unpack_kernel", "cfhip_std_compare_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

@@ -56,6 +56,12 @@ extern "C" hipError_t cfhip_launch_mip_depth(const void* prev, uint32_t n_prev, 
 	uint32_t depth, int box, int srgb, hipStream_t stream);
 extern "C" hipError_t cfhip_launch_std_pack(const cf_kparams* kp, int pixel_type, int bytes_per_pixel,
 	hipStream_t stream);
+extern "C" hipError_t cfhip_launch_std_unpack(int format, int type, int bytes_per_pixel, const void* pixels,
+	uint32_t width, uint32_t height, void* out, size_t out_pitch, hipStream_t stream);
+extern "C" uint64_t cfhip_std_compare_partials(uint32_t width, uint32_t height, uint64_t* ssim_partials);
+extern "C" hipError_t cfhip_launch_std_compare(int format, int type, int bytes_per_pixel, const void* pixels,
+	const void* ref, int ref_pix, size_t ref_pitch, uint32_t width, uint32_t height, unsigned cmask, int hdr,
+	double* partials, hipStream_t stream);
 extern "C" hipError_t cfhip_launch_decode(int format, int type, const void* blocks, int blk_vec, void* out,
 	size_t out_pitch, const void* ref, size_t ref_pitch, int out_vec, uint32_t width, uint32_t height,
 	uint32_t bx, uint32_t by, int bw, int bh, unsigned long long* acc, int sse, hipStream_t stream);
@@ -2717,6 +2723,310 @@ int cfhip_pvrtc_decode_sse_device(cfhip_ctx* ctx, int format, int type, const vo
 	HIP_TRY(ctx, hipMemsetAsync(sum, 0, 32, lease.stream));
 	rc = pvrtc_decode_launch(ctx, format, blocks, width, height, nullptr, 0, ref_rgba8, ref_pitch_bytes, sum, true,
 		lease.stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	return lease.done(!stream_);
+}
+
+} // extern "C"
+
+// ---- standard formats 1..28 back to texels (csrc/std_unpack.hip) and their metrics (csrc/compare.hip) ----
+struct StdGeom {
+	int bpp;
+	size_t payload_bytes;
+};
+
+// the checks every cfhip_std_* entry point makes before anything is enqueued
+static int std_check(cfhip_ctx* ctx, const char* what, int format, int type, const void* pixels, uint32_t width,
+	uint32_t height, StdGeom* g)
+{
+	g->bpp = is_std_format(format) ? std_pixel_bytes(format, type) : 0;
+	if (!g->bpp)
+		return fail(ctx, CFHIP_E_UNSUPPORTED, "%s: (format %d, type %d) is not a legal standard pair", what, format,
+			type);
+	if (!pixels)
+		return fail(ctx, CFHIP_E_INVALID, "%s: pixels is NULL", what);
+	if (!width || !height)
+		return fail(ctx, CFHIP_E_INVALID, "%s: empty surface %ux%u", what, width, height);
+	// one workgroup per 512 pixels in grid x
+	if ((uint64_t)width*height > (1ull << 38))
+		return fail(ctx, CFHIP_E_INVALID, "%s: surface %ux%u too large for one launch", what, width, height);
+	g->payload_bytes = (size_t)width*height*(size_t)g->bpp;
+	return CFHIP_OK;
+}
+
+// one unpack launch, timed like every encode launch (cfhip_last_kernel_ms / profiling)
+static int std_unpack_launch(cfhip_ctx* ctx, int format, int type, const StdGeom& g, const void* pixels, void* out,
+	size_t out_pitch, uint32_t width, uint32_t height, hipStream_t stream)
+{
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = "cfhip_std_unpack_kernel";
+	hipEvent_t a, b;
+	int rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, stream));
+	const hipError_t e = cfhip_launch_std_unpack(format, type, g.bpp, pixels, width, height, out, out_pitch, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "std_unpack launch: %s", hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, stream));
+	return CFHIP_OK;
+}
+
+// What one cfhip_std_compare call runs and where its device scratch lies: the unpacked surface of the SSIM pass
+// (RGBA32F, tight), then the Pass A partials, then the SSIM partials.
+struct StdCompareGeom {
+	StdGeom g;
+	int ref_bytes;
+	unsigned cmask;
+	bool hdr, ssim;
+	uint64_t na, nb;
+	uint32_t windows;
+	size_t pa_off, pb_off, scratch_bytes;
+};
+
+// the channels a standard format stores, bit c = channel c
+static unsigned std_channels(int format)
+{
+	switch (format) {
+		case CFHIP_FORMAT_R8: case CFHIP_FORMAT_R16: case CFHIP_FORMAT_R32:
+			return 1u;
+		case CFHIP_FORMAT_R4G4: case CFHIP_FORMAT_R8G8: case CFHIP_FORMAT_R16G16: case CFHIP_FORMAT_R32G32:
+			return 3u;
+		case CFHIP_FORMAT_R5G6B5: case CFHIP_FORMAT_B5G6R5: case CFHIP_FORMAT_R8G8B8: case CFHIP_FORMAT_B8G8R8:
+		case CFHIP_FORMAT_R16G16B16: case CFHIP_FORMAT_R32G32B32: case CFHIP_FORMAT_B10G11R11_UFLOAT:
+		case CFHIP_FORMAT_E5B9G9R9_UFLOAT:
+			return 7u;
+		default:
+			return 15u;
+	}
+}
+
+static int std_compare_check(cfhip_ctx* ctx, const char* what, int format, int type, const void* pixels,
+	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch, const uint8_t* mask,
+	unsigned flags, const void* result, StdCompareGeom* c)
+{
+	int rc = std_check(ctx, what, format, type, pixels, width, height, &c->g);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!ref || !result)
+		return fail(ctx, CFHIP_E_INVALID, "%s: NULL reference or result", what);
+	switch (ref_pixel_type) {
+		case CFHIP_PIXEL_RGBA8: c->ref_bytes = 4; break;
+		case CFHIP_PIXEL_RGBA32F: c->ref_bytes = 16; break;
+		case CFHIP_PIXEL_RGBA16F: c->ref_bytes = 8; break;
+		default: return fail(ctx, CFHIP_E_INVALID, "%s: reference pixel type %d", what, ref_pixel_type);
+	}
+	if (ref_pitch < (size_t)width*(size_t)c->ref_bytes)
+		return fail(ctx, CFHIP_E_INVALID, "%s: reference pitch %zu < %zu", what, ref_pitch,
+			(size_t)width*(size_t)c->ref_bytes);
+	if (flags & ~CFHIP_COMPARE_SSIM)
+		return fail(ctx, CFHIP_E_INVALID, "%s: unknown flags 0x%x", what, flags);
+	unsigned m = 15u;
+	if (mask)
+		m = (mask[0] ? 1u : 0u) | (mask[1] ? 2u : 0u) | (mask[2] ? 4u : 0u) | (mask[3] ? 8u : 0u);
+	c->cmask = std_channels(format) & m;
+	c->hdr = type == CFHIP_TYPE_FLOAT || type == CFHIP_TYPE_UFLOAT;
+	c->na = cfhip_std_compare_partials(width, height, &c->nb);
+	const bool norm = type == CFHIP_TYPE_UNORM || type == CFHIP_TYPE_SNORM;
+	c->ssim = (flags & CFHIP_COMPARE_SSIM) && norm && c->nb > 0 && c->cmask;
+	if (!c->ssim)
+		c->nb = 0;
+	c->windows = 0;
+	if (c->ssim) {
+		const uint64_t win = (uint64_t)(width - 10u)*(height - 10u);
+		if (win > 0xFFFFFFFFull || (height - 10u + 15u)/16u > 65535u)
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %ux%u too large for SSIM", what, width, height);
+		c->windows = (uint32_t)win;
+	}
+	const size_t dec = c->ssim ? (size_t)width*height*16u : 0;
+	c->pa_off = align16(dec);
+	c->pb_off = c->pa_off + (size_t)c->na*16u*sizeof(double);
+	c->scratch_bytes = c->pb_off + (size_t)c->nb*4u*sizeof(double);
+	return CFHIP_OK;
+}
+
+// Pass A, the SSIM pass (unpack into scratch + window statistics) and the final reduction, timed as one span
+static int std_compare_enqueue(cfhip_ctx* ctx, int format, int type, const StdCompareGeom& c, const void* pixels,
+	const void* ref, int ref_pixel_type, size_t ref_pitch, uint32_t width, uint32_t height, uint8_t* scratch,
+	cfhip_compare_result* result, hipStream_t stream)
+{
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = "cfhip_std_compare_kernel";
+	double* pa = reinterpret_cast<double*>(scratch + c.pa_off);
+	double* pb = c.ssim ? reinterpret_cast<double*>(scratch + c.pb_off) : nullptr;
+	hipEvent_t a, b;
+	int rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, stream));
+	hipError_t e = cfhip_launch_std_compare(format, type, c.g.bpp, pixels, ref, ref_pixel_type, ref_pitch, width,
+		height, c.cmask, c.hdr ? 1 : 0, pa, stream);
+	if (e == hipSuccess && c.ssim) {
+		const size_t dec_pitch = (size_t)width*16u;
+		e = cfhip_launch_std_unpack(format, type, c.g.bpp, pixels, width, height, scratch, dec_pitch, stream);
+		if (e == hipSuccess)
+			e = cfhip_launch_ssim(scratch, dec_pitch, CFHIP_LAYOUT_RGBA32F, ref, ref_pixel_type, ref_pitch, width,
+				height, c.cmask, ssim_taps(), type == CFHIP_TYPE_SNORM ? 2.0 : 1.0, pb, stream);
+	}
+	if (e == hipSuccess)
+		e = cfhip_launch_compare_final(pa, c.na, pb, c.nb, c.cmask, c.hdr ? 1 : 0, c.windows,
+			(uint64_t)width*height, result, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "std_compare launch: %s", hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, stream));
+	return CFHIP_OK;
+}
+
+extern "C" {
+
+int cfhip_std_unpack(cfhip_ctx* ctx, int format, int type, const void* pixels, size_t pixels_bytes, uint32_t width,
+	uint32_t height, void* out_rgba32f, size_t out_capacity)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	StdGeom g;
+	int rc = std_check(ctx, "std_unpack", format, type, pixels, width, height, &g);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!out_rgba32f)
+		return fail(ctx, CFHIP_E_INVALID, "std_unpack: out is NULL");
+	if (pixels_bytes < g.payload_bytes)
+		return fail(ctx, CFHIP_E_INVALID, "std_unpack: pixels_bytes %zu < %zu for %ux%u", pixels_bytes,
+			g.payload_bytes, width, height);
+	const size_t out_bytes = (size_t)width*height*16u;
+	if (out_capacity < out_bytes)
+		return fail(ctx, CFHIP_E_CAPACITY, "std_unpack: out_capacity %zu < %zu", out_capacity, out_bytes);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, ctx->stream);
+	const hipStream_t stream = lease.stream;
+	// d_src: the payload; d_out: the texels
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, g.payload_bytes);
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, out_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, pixels, g.payload_bytes, hipMemcpyHostToDevice, stream));
+	rc = std_unpack_launch(ctx, format, type, g, ctx->d_src, ctx->d_out, (size_t)width*16u, width, height, stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipMemcpyAsync(out_rgba32f, ctx->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+	return lease.done(true);
+}
+
+int cfhip_std_unpack_device(cfhip_ctx* ctx, int format, int type, const void* pixels, uint32_t width,
+	uint32_t height, void* out_rgba32f, size_t out_pitch_bytes, void* stream_)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	StdGeom g;
+	int rc = std_check(ctx, "std_unpack_device", format, type, pixels, width, height, &g);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!out_rgba32f)
+		return fail(ctx, CFHIP_E_INVALID, "std_unpack_device: out is NULL");
+	if (out_pitch_bytes < (size_t)width*16u)
+		return fail(ctx, CFHIP_E_INVALID, "std_unpack_device: out pitch %zu < %zu", out_pitch_bytes,
+			(size_t)width*16u);
+	// the kernel stores floats (whole float4 texels when pointer and pitch allow)
+	if ((uintptr_t)out_rgba32f % 4u != 0 || out_pitch_bytes % 4u != 0)
+		return fail(ctx, CFHIP_E_INVALID, "std_unpack_device: out and its pitch must be 4-byte aligned");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	// no staging buffer is touched: the lease only carries the synchronisation rule of the stream
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	rc = std_unpack_launch(ctx, format, type, g, pixels, out_rgba32f, out_pitch_bytes, width, height, lease.stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	return lease.done(!stream_);
+}
+
+int cfhip_std_compare(cfhip_ctx* ctx, int format, int type, const void* pixels, size_t pixels_bytes, uint32_t width,
+	uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes, const uint8_t mask_rgba[4],
+	unsigned flags, cfhip_compare_result* result)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	StdCompareGeom c;
+	int rc = std_compare_check(ctx, "std_compare", format, type, pixels, width, height, ref, ref_pixel_type,
+		ref_pitch_bytes, mask_rgba, flags, result, &c);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (pixels_bytes < c.g.payload_bytes)
+		return fail(ctx, CFHIP_E_INVALID, "std_compare: pixels_bytes %zu < %zu for %ux%u", pixels_bytes,
+			c.g.payload_bytes, width, height);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, ctx->stream);
+	const hipStream_t stream = lease.stream;
+	// d_src: the payload; d_out: the reference, tightly packed, the scratch, the result
+	const size_t row = (size_t)width*(size_t)c.ref_bytes;
+	const size_t scr_off = align16(row*height), res_off = align16(scr_off + c.scratch_bytes);
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, c.g.payload_bytes);
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, res_off + sizeof(cfhip_compare_result));
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
+	cfhip_compare_result* d_res = reinterpret_cast<cfhip_compare_result*>(d + res_off);
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, pixels, c.g.payload_bytes, hipMemcpyHostToDevice, stream));
+	HIP_TRY(ctx, hipMemcpy2DAsync(d, row, ref, ref_pitch_bytes, row, height, hipMemcpyHostToDevice, stream));
+	rc = std_compare_enqueue(ctx, format, type, c, ctx->d_src, d, ref_pixel_type, row, width, height, d + scr_off,
+		d_res, stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	cfhip_compare_result res;
+	HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, stream));
+	rc = lease.done(true);
+	if (rc != CFHIP_OK)
+		return rc;
+	*result = res;
+	return CFHIP_OK;
+}
+
+int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* pixels, uint32_t width,
+	uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes, const uint8_t mask_rgba[4],
+	unsigned flags, cfhip_compare_result* result_device, void* stream_)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	StdCompareGeom c;
+	int rc = std_compare_check(ctx, "std_compare_device", format, type, pixels, width, height, ref, ref_pixel_type,
+		ref_pitch_bytes, mask_rgba, flags, result_device, &c);
+	if (rc != CFHIP_OK)
+		return rc;
+	// the kernels read reference texels with one aligned load each and store doubles to the result
+	const size_t rb = (size_t)c.ref_bytes;
+	if ((uintptr_t)ref % rb != 0 || ref_pitch_bytes % rb != 0)
+		return fail(ctx, CFHIP_E_INVALID, "std_compare_device: reference and its pitch must be %zu-byte aligned", rb);
+	if ((uintptr_t)result_device % 8u != 0)
+		return fail(ctx, CFHIP_E_INVALID, "std_compare_device: misaligned result");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	// the partials (and the SSIM pass's unpacked surface) live in d_out: the lease orders them across streams
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, c.scratch_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
+	rc = std_compare_enqueue(ctx, format, type, c, pixels, ref, ref_pixel_type, ref_pitch_bytes, width, height,
+		static_cast<uint8_t*>(ctx->d_out), result_device, lease.stream);
 	if (rc != CFHIP_OK)
 		return rc;
 	return lease.done(!stream_);

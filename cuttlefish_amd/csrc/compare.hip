@@ -7,6 +7,9 @@
 //     the lane's own sum, so the error map needs no atomics.
 //   * Pass A, ASTC: one wave per run of 64 blocks of a block row; phase 1 parses each block into an LDS record
 //     (decode_blocks.h), phase 2 has lane b evaluate block b's texels.
+//   * Pass A, standard formats: the unpack kernel's shape (std_unpack.hip): a workgroup owns 512 consecutive pixels
+//     of the tight payload, a lane two of them; the pixel becomes the float the unpack kernel would store, then a
+//     double.  No block grid, so no error map.
 //   * Pass B (SSIM, LDR layouts): the payload is decoded into a scratch surface by the decode kernels, then one
 //     256-thread workgroup per 16x16 tile of window centres stages the tile and its 5-texel halo of one channel in
 //     LDS and runs the separable 11-tap Gaussian in FP64.
@@ -17,6 +20,7 @@
 #include <stdint.h>
 
 #include "decode_blocks.h"
+#include "std_unpack.h"
 #include "../../include/cuttlefish_hip.h"
 
 namespace {
@@ -210,6 +214,48 @@ __global__ __launch_bounds__(kCmpWg) void cfhip_compare_block_kernel(cmp_args a)
 	write_partial<kCmpWg>(s, err, a.partials);
 }
 
+struct std_cmp_args {
+	const uint8_t* pixels;        // the tight payload, any alignment
+	const uint8_t* ref;
+	unsigned long long ref_pitch;
+	uint32_t width, height;
+	uint32_t format, type;
+	uint32_t in_vec;              // pixels is aligned for the vector load of its pixel size
+	uint32_t ref_pix, cmask;
+	uint32_t hdr;                 // Float / UFloat types: log_sse is accumulated
+	double* partials;             // kPartA doubles per workgroup
+};
+
+// Pass A for the standard formats: BPP bytes per pixel, one workgroup per cfstd::kPixPerWg pixels
+template <int BPP>
+__global__ __launch_bounds__(kCmpWg) void cfhip_std_compare_kernel(std_cmp_args a)
+{
+	static_assert(cfstd::kThreads == kCmpWg, "write_partial reduces kCmpWg threads");
+	__shared__ uint32_t stage[cfstd::stage_dwords<BPP>()];
+	const unsigned long long npix = (unsigned long long)a.width*a.height;
+	const unsigned long long p0 = (unsigned long long)blockIdx.x*cfstd::kPixPerWg;
+	uint4 o[cfstd::kPerThread];
+	cfstd::load_pixels<BPP>(a.pixels, a.in_vec, p0, npix, threadIdx.x, stage, o);
+	Acc s;
+	acc_init(s);
+#pragma unroll
+	for (uint32_t j = 0; j < cfstd::kPerThread; ++j) {
+		const unsigned long long p = p0 + j*cfstd::kThreads + threadIdx.x;
+		if (p >= npix)
+			continue;
+		const uint32_t y = (uint32_t)(p/a.width), x = (uint32_t)(p - (unsigned long long)y*a.width);
+		const float4 f = cfstd::unpack_pixel<BPP>(a.format, a.type, o[j]);
+		const double d[4] = {(double)f.x, (double)f.y, (double)f.z, (double)f.w};
+		double r[4];
+		ref_load(a.ref, a.ref_pitch, a.ref_pix, x, y, r);
+		if (a.hdr)
+			acc_texel<true>(s, d, r, a.cmask);
+		else
+			acc_texel<false>(s, d, r, a.cmask);
+	}
+	write_partial<kCmpWg>(s, 0.0, a.partials);
+}
+
 // one wave = a run of kCmpRun blocks of one block row; grid (ceil(bx / kCmpRun), by)
 template <bool HDR>
 __global__ __launch_bounds__(kCmpRun) void cfhip_compare_astc_kernel(cmp_args a, int bw, int bh)
@@ -289,7 +335,7 @@ struct ssim_args {
 	double* partials;             // 4 doubles per workgroup
 };
 
-// channel c of decoded texel (x, y), normalised; LDR layouts only
+// channel c of decoded texel (x, y), normalised; LDR layouts, and the unpacked texels of a UNorm / SNorm standard format
 __device__ __forceinline__ double dec_channel(const ssim_args& a, uint32_t x, uint32_t y, int c)
 {
 	const uint8_t* row = a.dec + (uint64_t)y*a.dec_pitch;
@@ -299,6 +345,7 @@ __device__ __forceinline__ double dec_channel(const ssim_args& a, uint32_t x, ui
 		case CFHIP_LAYOUT_R8_SNORM: return snorm_div((int)(int8_t)row[x], 127.0);
 		case CFHIP_LAYOUT_RG8: return (double)row[(uint64_t)x*2u + c]/255.0;
 		case CFHIP_LAYOUT_RG8_SNORM: return snorm_div((int)(int8_t)row[(uint64_t)x*2u + c], 127.0);
+		case CFHIP_LAYOUT_RGBA32F: return (double)reinterpret_cast<const float*>(row)[(uint64_t)x*4u + c];
 		default: break;
 	}
 	const uint64_t o = (uint64_t)x*(a.layout >= CFHIP_LAYOUT_RG16 ? 4u : 2u) + 2u*c;
@@ -511,6 +558,47 @@ extern "C" hipError_t cfhip_launch_compare(int format, int type, const void* blo
 		case 42: return sn ? launch_a<42, 1>(a, stream) : launch_a<42, 0>(a, stream);
 		default: return hipErrorInvalidValue;
 	}
+}
+
+// Workgroups (partials) of the standard formats' Pass A; the SSIM pass's as above.
+extern "C" uint64_t cfhip_std_compare_partials(uint32_t width, uint32_t height, uint64_t* ssim_partials)
+{
+	if (ssim_partials)
+		cfhip_compare_partials(0, width, height, 0, 0, ssim_partials);
+	return ((uint64_t)width*height + cfstd::kPixPerWg - 1)/cfstd::kPixPerWg;
+}
+
+// Pass A for a legal standard (format, type) pair of bytes_per_pixel bytes; partials receives
+// cfhip_std_compare_partials() x 16 doubles.
+extern "C" hipError_t cfhip_launch_std_compare(int format, int type, int bytes_per_pixel, const void* pixels,
+	const void* ref, int ref_pix, size_t ref_pitch, uint32_t width, uint32_t height, unsigned cmask, int hdr,
+	double* partials, hipStream_t stream)
+{
+	std_cmp_args a;
+	a.pixels = static_cast<const uint8_t*>(pixels);
+	a.ref = static_cast<const uint8_t*>(ref);
+	a.ref_pitch = ref_pitch;
+	a.width = width; a.height = height;
+	a.format = (uint32_t)format; a.type = (uint32_t)type;
+	const uintptr_t al = bytes_per_pixel == 16 ? 16u : (bytes_per_pixel == 8 ? 8u : 4u);
+	a.in_vec = (uintptr_t)pixels % al == 0 ? 1u : 0u;
+	a.ref_pix = (uint32_t)ref_pix;
+	a.cmask = cmask;
+	a.hdr = (uint32_t)hdr;
+	a.partials = partials;
+	const dim3 grid((unsigned)cfhip_std_compare_partials(width, height, nullptr)), block(kCmpWg);
+	switch (bytes_per_pixel) {
+		case 1: hipLaunchKernelGGL(cfhip_std_compare_kernel<1>, grid, block, 0, stream, a); break;
+		case 2: hipLaunchKernelGGL(cfhip_std_compare_kernel<2>, grid, block, 0, stream, a); break;
+		case 3: hipLaunchKernelGGL(cfhip_std_compare_kernel<3>, grid, block, 0, stream, a); break;
+		case 4: hipLaunchKernelGGL(cfhip_std_compare_kernel<4>, grid, block, 0, stream, a); break;
+		case 6: hipLaunchKernelGGL(cfhip_std_compare_kernel<6>, grid, block, 0, stream, a); break;
+		case 8: hipLaunchKernelGGL(cfhip_std_compare_kernel<8>, grid, block, 0, stream, a); break;
+		case 12: hipLaunchKernelGGL(cfhip_std_compare_kernel<12>, grid, block, 0, stream, a); break;
+		case 16: hipLaunchKernelGGL(cfhip_std_compare_kernel<16>, grid, block, 0, stream, a); break;
+		default: return hipErrorInvalidValue;
+	}
+	return hipGetLastError();
 }
 
 // Pass B over a decoded surface (LDR layouts); taps: the 11 normalised Gaussian weights; range: L of C1, C2.

@@ -652,7 +652,8 @@ class Texture:
         """Quality of this converted texture against `source`, an unconverted texture of the same dimension, size,
         mip levels, depth and faces (convert() frees a texture's own images).  Returns (one api.Comparison per
         surface in (mip, depth, face) order, the pooled PSNR over every surface).  The channels compared are the
-        colour mask's, without alpha when the alpha type is None or the format has none."""
+        colour mask's, without alpha when the alpha type is None or the format has none.  Standard formats go through
+        Context.compare_std: the same return shape, SSIM NaN for the types that are not normalised."""
         if not self._textures:
             raise ValueError("compare: this texture is not converted")
         if source is self or not source.images_complete():
@@ -667,12 +668,19 @@ class Texture:
         ctx = self._context()
         if self._format in api.PVRTC_FORMATS:
             return self._compare_pvrtc(ctx, source, mask, ssim)
+        # the standard formats have their own entry (cfhip_std_compare): SSIM is NaN for the non-normalised types.
+        # Their texels are floats, so an 8-bit source is measured as the RGBAF image the converter read
+        # (float(v/255), Image.cpp:293-296): a lossless conversion then compares equal, PSNR inf.
+        std = int(self._format) < int(Format.BC1_RGB)
+        measure = ctx.compare_std if std else ctx.compare
         results = []
         for m, level in enumerate(self._textures):
             for d, dep in enumerate(level):
                 for f, payload in enumerate(dep):
-                    results.append(ctx.compare(payload, source._images[m][d][f], self._format, self._type,
-                                               mask=mask, ssim=ssim))
+                    ref = source._images[m][d][f]
+                    if std and ref.dtype == np.uint8:
+                        ref = (ref.astype(np.float64)/255.0).astype(np.float32)
+                    results.append(measure(payload, ref, self._format, self._type, mask=mask, ssim=ssim))
         sse = sum(sum(r.sse[c] for c in r.compared()) for r in results)
         n = sum(r.texels * len(r.compared()) for r in results)
         if n == 0:
@@ -680,6 +688,39 @@ class Texture:
         peak = max(r.peak() for r in results)
         pooled = float("inf") if sse == 0.0 else 10.0 * float(np.log10(peak * peak * n / sse))
         return results, pooled
+
+    def decode_image(self, *args) -> Optional[np.ndarray]:
+        """decode_image([face,] mip=0, depth=0): the surface of this converted texture as the RGBAF image a
+        cuttlefish::Image would hold, (h, w, 4) float32, for every format convert() accepts; None where data()
+        returns None.  Standard formats through Context.unpack; block formats through Context.decode, normalised as
+        cfhip_compare documents (RGBA8 v/255, SNorm max(v/127, -1), EAC v/2047 and max(v/1023, -1), halves ->
+        float); PVRTC through Context.decode_pvrtc.  Channels the format does not store read 0, 0, 1.  The stored
+        values are returned: no sRGB transfer."""
+        payload = self.data(*args)
+        if payload is None:
+            return None
+        _, mip, _ = self._face_args(args)
+        w, h = self.width(mip), self.height(mip)
+        ctx = self._context()
+        if int(self._format) < int(Format.BC1_RGB):
+            return ctx.unpack(payload, self._format, self._type, w, h)
+        if self._format in api.PVRTC_FORMATS:
+            raw, layout = ctx.decode_pvrtc(payload, self._format, w, h, self._type), api.Layout.RGBA8
+        else:
+            raw, _ = ctx.decode(payload, self._format, self._type, w, h)
+            layout, _ = api.decoded_layout(self._format, self._type)
+        out = np.zeros((h, w, 4), np.float32)
+        out[..., 3] = 1.0
+        n = raw.shape[2]
+        if layout == api.Layout.RGBA16F:
+            val = raw.astype(np.float32)
+        else:
+            div = {api.Layout.RGBA8: 255.0, api.Layout.R8: 255.0, api.Layout.RG8: 255.0, api.Layout.R8_SNorm: 127.0,
+                   api.Layout.RG8_SNorm: 127.0, api.Layout.R16: 2047.0, api.Layout.RG16: 2047.0,
+                   api.Layout.R16_SNorm: 1023.0, api.Layout.RG16_SNorm: 1023.0}[layout]
+            val = np.maximum(raw.astype(np.float64)/div, -1.0).astype(np.float32)
+        out[..., :n] = val
+        return out
 
     def _compare_pvrtc(self, ctx, source, mask, ssim):
         """compare() for PVRTC1 4 bpp: PSNR from the fused decode + SSE (cfhip_pvrtc_decode_sse) against the

@@ -348,7 +348,8 @@ enum cfhip_layout {
 	CFHIP_LAYOUT_R16_SNORM = 6,     /* EAC R11 signed, -1023..1023 */
 	CFHIP_LAYOUT_RG16 = 7,
 	CFHIP_LAYOUT_RG16_SNORM = 8,
-	CFHIP_LAYOUT_RGBA16F = 9
+	CFHIP_LAYOUT_RGBA16F = 9,
+	CFHIP_LAYOUT_RGBA32F = 10       /* what cfhip_std_unpack writes; no block (format, type) pair decodes to it */
 };
 
 /* Decoded texel layout of a block (format, type) pair; CFHIP_E_UNSUPPORTED for the standard formats and for
@@ -521,7 +522,58 @@ int cfhip_pvrtc_decode_sse(cfhip_ctx* ctx, int format, int type, const void* blo
 int cfhip_pvrtc_decode_sse_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width,
 	uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t* sse_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare* or cfhip_image_ops_device call on
+/* ---- Standard (uncompressed) formats 1..28: the payload back to texels, and its quality metrics ----
+ *
+ * The inverse of what cfhip_encode writes for these formats: width * height pixels, row-major, top-down, tightly
+ * packed -> RGBA32F texels.  Legality is cfhip_query's for formats 1..28 (66 pairs); every other (format, type) --
+ * block formats, PVRTC, illegal pairs such as (R5G6B5, Float) -- is CFHIP_E_UNSUPPORTED.  The generic
+ * cfhip_decode* / cfhip_compare* entries keep answering CFHIP_E_UNSUPPORTED for these formats.
+ *
+ * Value of a stored field v of n bits (the fixed-function conversions of Vulkan / OpenGL):
+ *   UNorm               (float)v / (float)(2^n - 1), the correctly rounded IEEE single division
+ *   SNorm               max((float)v / (float)(2^(n-1) - 1), -1.0f), v sign-extended
+ *   UInt / Int          (float)v, round to nearest even (exact up to 2^24)
+ *   Float, 16-bit       half -> float, exact
+ *   Float, 32-bit       the stored bits, copied
+ *   UFloat B10G11R11    unsigned small floats, exponent bias 15, 6 / 6 / 5 mantissa bits; exponent 0 is a denormal
+ *                       m * 2^(-14 - mbits); exponent 31 is +Inf (m == 0) or NaN
+ *   UFloat E5B9G9R9     m_c * 2^(e - 24) per channel, exact in float
+ * Channels the format does not store: green and blue 0, alpha 1.  A stored NaN stays a NaN; its bits are not
+ * specified, except for 32-bit Float, whose bits are copied.  Colour space: the stored values are returned, no
+ * sRGB transfer is applied.
+ *
+ * Stream and error rules are those of cfhip_decode*: every argument is checked before anything is enqueued,
+ * stream == NULL means the context's stream and the call synchronises. */
+
+/* Host buffers: pixels (pixels_bytes >= width * height * pixel size) -> out_rgba32f, width * height texels tightly
+ * packed (out_capacity >= width * height * 16 bytes, else CFHIP_E_CAPACITY).  Blocking. */
+int cfhip_std_unpack(cfhip_ctx* ctx, int format, int type, const void* pixels, size_t pixels_bytes,
+	uint32_t width, uint32_t height, void* out_rgba32f, size_t out_capacity);
+
+/* Device buffers on ctx's GPU.  pixels may have any alignment (a mip level inside a larger payload).  out_rgba32f:
+ * rows out_pitch_bytes apart (>= width * 16); pointer and pitch 4-byte aligned (16 for the fastest stores). */
+int cfhip_std_unpack_device(cfhip_ctx* ctx, int format, int type, const void* pixels,
+	uint32_t width, uint32_t height, void* out_rgba32f, size_t out_pitch_bytes, void* stream);
+
+/* cfhip_compare for the standard formats: every pixel is converted as above (to the float cfhip_std_unpack writes,
+ * then to double) and measured against the reference exactly as cfhip_compare measures a decoded block texel.
+ * Channels compared: those the format stores AND the caller's mask; the others report 0 (ssim NaN).
+ *   sse, ref_max   every type
+ *   log_sse        Float and UFloat types (NaN otherwise)
+ *   ssim           with CFHIP_COMPARE_SSIM, UNorm (L = 1) and SNorm (L = 2) types; NaN for the other types, when
+ *                  not asked for and when a side is below 11
+ * error_blocks is 0 and there is no per-block error map.  Identical calls return identical bits. */
+int cfhip_std_compare(cfhip_ctx* ctx, int format, int type, const void* pixels, size_t pixels_bytes,
+	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
+	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result);
+
+/* Device buffers: pixels (any alignment), ref (pointer and pitch aligned to the texel size), result_device (8-byte
+ * aligned).  mask_rgba is host memory.  The stream rules of cfhip_compare_device. */
+int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* pixels,
+	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
+	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device, void* stream);
+
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_* or cfhip_image_ops_device call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
