@@ -189,7 +189,8 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_decode_sse_device", "cfhip_image_ops_device", "cfhip_compare", "cfhip_compare_device",
            "cfhip_pvrtc_query", "cfhip_pvrtc_encode", "cfhip_pvrtc_encode_device", "cfhip_pvrtc_decode",
            "cfhip_pvrtc_decode_device", "cfhip_pvrtc_decode_sse", "cfhip_pvrtc_decode_sse_device",
-           "cfhip_std_unpack", "cfhip_std_unpack_device", "cfhip_std_compare", "cfhip_std_compare_device"]
+           "cfhip_std_unpack", "cfhip_std_unpack_device", "cfhip_std_compare", "cfhip_std_compare_device",
+           "cfhip_decode_batch", "cfhip_decode_batch_device", "cfhip_decode_out_supported"]
 
 
 class Layout(enum.IntEnum):
@@ -278,6 +279,18 @@ class Surface(ctypes.Structure):
                 ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
                 ("row_pitch_bytes", ctypes.c_ssize_t), ("out", ctypes.c_void_p),
                 ("out_capacity", ctypes.c_size_t)]
+
+
+class DecodeSurface(ctypes.Structure):
+    """struct cfhip_decode_surface"""
+    _fields_ = [("blocks", ctypes.c_void_p), ("blocks_bytes", ctypes.c_size_t), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32), ("out", ctypes.c_void_p), ("out_pitch_bytes", ctypes.c_size_t),
+                ("out_capacity", ctypes.c_size_t)]
+
+
+DECODE_NATIVE = -1              # CFHIP_DECODE_NATIVE
+# output texel (channels, dtype) of a batched decode to a pixel type
+PIXEL_ARRAY = {PixelType.RGBA8: (4, np.uint8), PixelType.RGBA32F: (4, np.float32), PixelType.RGBA16F: (4, np.float16)}
 
 
 class ImageOps(ctypes.Structure):
@@ -455,6 +468,15 @@ def load_library(path: Optional[str] = None):
                                            ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int,
                                            ctypes.c_size_t, u8p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_std_compare_device.restype = ctypes.c_int
+    L.cfhip_decode_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.POINTER(DecodeSurface), ctypes.c_size_t, u64p]
+    L.cfhip_decode_batch.restype = ctypes.c_int
+    L.cfhip_decode_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(DecodeSurface), ctypes.c_size_t, ctypes.c_void_p,
+                                            ctypes.c_void_p]
+    L.cfhip_decode_batch_device.restype = ctypes.c_int
+    L.cfhip_decode_out_supported.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.cfhip_decode_out_supported.restype = ctypes.c_int
     _lib = L
     return L
 
@@ -503,6 +525,12 @@ def decoded_layout(fmt, typ=Type.UNorm):
     if rc != 0:
         raise CfhipError(rc, "no decoded layout for (format, type) = (%r, %r)" % (fmt, typ))
     return Layout(lay.value), tb.value
+
+
+def decode_out_supported(fmt, typ, out_pixel=None) -> bool:
+    """Whether a batched decode of (fmt, typ) can store out_pixel (None: the native layout).  Needs no device."""
+    return bool(load_library().cfhip_decode_out_supported(int(fmt), int(typ),
+                                                          DECODE_NATIVE if out_pixel is None else int(out_pixel)))
 
 
 def psnr_from_sse(sse, n_texels: int, channels: int = 3) -> float:
@@ -781,6 +809,51 @@ class Context:
             self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(out)),
             out_pitch_bytes, ctypes.c_void_p(int(error_blocks)) if error_blocks else None,
             ctypes.c_void_p(stream) if stream else None))
+
+    def decode_batch(self, payloads: Sequence[np.ndarray], fmt, typ, sizes: Sequence, out_pixel=None):
+        """Decode every surface of a call in one launch (cfhip_decode_batch).  payloads[i] is the payload of a
+        sizes[i] = (width, height) surface.  out_pixel None: the native layout, arrays as decode() returns them;
+        a PixelType: (h, w, 4) arrays of that type (decode_out_supported says which exist).  Payloads that lie
+        one after the other in memory (Texture.load keeps them so) travel as one upload, the texels as one download.  -> (list of arrays, list of error-block counts)."""
+        n = len(payloads)
+        if len(sizes) != n:
+            raise ValueError("payloads and sizes must list the same surfaces")
+        if out_pixel is None:
+            ch, dt = LAYOUT_ARRAY[decoded_layout(fmt, typ)[0]]
+        else:
+            ch, dt = PIXEL_ARRAY[PixelType(out_pixel)]
+        tb = ch*np.dtype(dt).itemsize
+        parts = [np.ascontiguousarray(p, dtype=np.uint8).reshape(-1) for p in payloads]
+        total = sum(int(w)*int(h)*tb for w, h in sizes)
+        texels = np.empty(max(total, 1), np.uint8)
+        surf = (DecodeSurface*max(n, 1))()
+        outs, to = [], 0
+        for i, ((w, h), p) in enumerate(zip(sizes, parts)):
+            w, h = int(w), int(h)
+            surf[i].blocks, surf[i].blocks_bytes = p.ctypes.data, p.nbytes
+            surf[i].width, surf[i].height = w, h
+            surf[i].out, surf[i].out_pitch_bytes, surf[i].out_capacity = texels.ctypes.data + to, w*tb, w*h*tb
+            outs.append(texels[to:to + w*h*tb].view(dt).reshape(h, w, ch))
+            to += w*h*tb
+        bad = (ctypes.c_uint64*max(n, 1))()
+        self._check(self._lib.cfhip_decode_batch(self._h, int(fmt), int(typ),
+                                                 DECODE_NATIVE if out_pixel is None else int(out_pixel), surf, n, bad))
+        return outs, [int(bad[i]) for i in range(n)]
+
+    def decode_batch_device(self, surfaces: Sequence[dict], fmt, typ, out_pixel=None, error_blocks: int = 0,
+                            stream: int = 0):
+        """Device path of decode_batch.  surfaces: dicts with blocks, out (device pointers as ints), width, height,
+        out_pitch_bytes.  error_blocks: device pointer to len(surfaces) uint64 (zeroed by the call; 0 = not
+        counted).  stream 0 = the context's stream (the call then synchronises)."""
+        n = len(surfaces)
+        surf = (DecodeSurface*max(n, 1))()
+        for i, s in enumerate(surfaces):
+            surf[i].blocks, surf[i].out = int(s["blocks"]), int(s["out"])
+            surf[i].width, surf[i].height = s["width"], s["height"]
+            surf[i].out_pitch_bytes = s["out_pitch_bytes"]
+        self._check(self._lib.cfhip_decode_batch_device(
+            self._h, int(fmt), int(typ), DECODE_NATIVE if out_pixel is None else int(out_pixel), surf, n,
+            ctypes.c_void_p(int(error_blocks)) if error_blocks else None, ctypes.c_void_p(stream) if stream else None))
 
     def decode_sse(self, payload: np.ndarray, ref: np.ndarray, fmt, typ=Type.UNorm):
         """Per-channel sums of squared differences between the decoded payload and an (h, w, 4) uint8

@@ -118,6 +118,8 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  # the decoders (csrc/decode.hip): every cfhip_decode_*_kernel, the fused SSE ones included
                  "cfhip_decode_block_kernel", "cfhip_decode_astc_kernel", "cfhip_decode_sse_block_kernel",
                  "cfhip_decode_sse_astc_kernel",
+                 # the batched decoders (csrc/decode.hip, csrc/decode_batch.h)
+                 "cfhip_decode_batch_kernel", "cfhip_decode_batch_astc_kernel",
                  # the per-image pixel ops (csrc/image_ops.hip)
                  "cfhip_image_ops_kernel",
                  # the quality metrics (csrc/compare.hip)

@@ -558,3 +558,277 @@ def write_pvr_texture(stream, tex: TextureLayout, color_space=ColorSpace.Linear,
                 out += tex.surfaces[l][d][f]
     stream.write(out)
     return len(out)
+
+
+# ---- readers: the exact inverse of the three *_texture writers -------------------------------
+# Format maps are the writers' tables inverted at import, so reader and writer cannot drift.  A code written
+# by more than one (format, type) is a collision set: a header field that tells the members apart decides,
+# otherwise the lowest (format, type) wins and the format= / type= hints select another member.
+
+class TextureFile:
+    """What a reader returns: the fields of TextureLayout plus colour space and alpha type."""
+
+    def __init__(self, fmt, typ, color_space, alpha, dimension, width, height, depth, is_array, surfaces):
+        self.fmt, self.typ = Format(fmt), Type(typ)
+        self.color_space, self.alpha = ColorSpace(color_space), Alpha(alpha)
+        self.dimension, self.width, self.height, self.depth = dimension, width, height, depth
+        self.is_array, self.surfaces, self.levels = bool(is_array), surfaces, len(surfaces)
+
+    def layout(self) -> TextureLayout:
+        return TextureLayout(self.fmt, self.typ, self.width, self.height, self.surfaces, self.dimension,
+                             self.depth, self.is_array)
+
+
+def _invert(table, codes):
+    rev = {}
+    for key in sorted(table, key=lambda k: (int(k[0]), int(k[1]))):
+        for code, cs in codes(table[key]):
+            if code is not None:
+                rev.setdefault(code, []).append((key[0], key[1], cs))
+    return rev
+
+
+_DXGI_REV = _invert(_DXGI, lambda v: ((v[0], ColorSpace.Linear), (v[1], ColorSpace.sRGB)))
+# KTX: every header field that tells formats apart is part of the key
+_KTX_REV = _invert(_GL, lambda v: (((0, 1, 0, v[0], v[2]), ColorSpace.Linear), ((0, 1, 0, v[1], v[2]) if v[1] else None, ColorSpace.sRGB)))
+for _k, _v in _invert(_GLU, lambda v: (((v[0], v[1], v[2], v[3][0], v[4]), ColorSpace.Linear),
+                                       ((v[0], v[1], v[2], v[3][1], v[4]) if v[3][1] else None, ColorSpace.sRGB))).items():
+    _KTX_REV.setdefault(_k, []).extend(_v)
+_PVR_REV = {}
+for _f in sorted(set(_PVR_GENERIC) | set(_PVR_SPECIAL), key=int):
+    for _a in (Alpha.Standard, Alpha.PreMultiplied):
+        for _t in Type:
+            _e = _PVR_REV.setdefault((pvr_pixel_format(_f, _a), pvr_channel_type(_f, _t)), [])
+            if (_f, _t) not in _e:
+                _e.append((_f, _t))
+# files from elsewhere: legacy FourCC headers and the typeless DXGI codes
+_DDS_FOURCC = {b"DXT1": 71, b"DXT3": 74, b"DXT5": 77, b"ATI1": 80, b"BC4U": 80, b"BC4S": 81, b"ATI2": 83,
+               b"BC5U": 83, b"BC5S": 84}
+_DXGI_TYPELESS = {70: 71, 73: 74, 76: 77, 79: 80, 82: 83, 94: 95, 97: 98}
+
+
+def _legal(fmt, typ) -> bool:
+    from .api import CfhipError
+    try:
+        query(fmt, typ)
+        return Format(fmt) not in PVRTC_FORMATS or Type(typ) == Type.UNorm
+    except (CfhipError, ValueError):
+        return False
+
+
+def _choose(cands, fmt, typ, what):
+    """The member of a collision set: the lowest legal (format, type), or the one the hints name."""
+    cands = [c for c in cands if _legal(c[0], c[1])]
+    if not cands:
+        raise ValueError("%s: no legal (format, type) for this code" % what)
+    pick = [c for c in cands if (fmt is None or Format(fmt) == c[0]) and (typ is None or Type(typ) == c[1])]
+    if not pick:
+        raise ValueError("%s: the format / type hint is not in the collision set %r" %
+                         (what, [(c[0].name, c[1].name) for c in cands]))
+    return pick[0]
+
+
+def _need(data, off, n, what):
+    if off < 0 or n < 0 or off + n > len(data):
+        raise ValueError("%s: truncated (%d bytes at %d of %d)" % (what, n, off, len(data)))
+
+
+def _shape_check(what, width, height, depth, levels, faces, elements):
+    if width < 1 or height < 1 or levels < 1 or levels > max(width, height, depth, 1).bit_length():
+        raise ValueError("%s: bad size %dx%d or level count %d" % (what, width, height, levels))
+    if faces not in (1, 6) or elements < 1:
+        raise ValueError("%s: bad face or element count" % what)
+
+
+def _size(fmt, typ, w, h, what):
+    from .api import CfhipError
+    try:
+        return payload_size(fmt, typ, w, h)
+    except CfhipError:
+        raise ValueError("%s: no payload of %dx%d in this format" % (what, w, h))
+
+
+def _safely(fn):
+    def wrapped(data, *a, **k):
+        try:
+            return fn(bytes(data), *a, **k)
+        except ValueError:
+            raise
+        except struct.error as e:
+            raise ValueError("malformed file: %s" % e)
+    wrapped.__doc__, wrapped.__name__ = fn.__doc__, fn.__name__
+    return wrapped
+
+
+@_safely
+def read_dds_texture(data, format=None, type=None) -> TextureFile:
+    """Inverse of write_dds_texture.  Also reads the legacy FourCC headers DXT1 / DXT3 / DXT5 / ATI1 / BC4U / BC4S /
+    ATI2 / BC5U / BC5S and the typeless DXGI codes of BC1-BC7.  Raises ValueError for anything else."""
+    _need(data, 0, 128, "DDS")
+    magic, size, flags, height, width, pitch, depth, levels = struct.unpack_from("<8I", data, 0)
+    pf_size, pf_flags, fourcc = struct.unpack_from("<2I4s", data, 76)
+    caps, caps2 = struct.unpack_from("<2I", data, 108)
+    if magic != DDS_MAGIC or size != 124 or pf_size != 32 or not pf_flags & _DDPF_FOURCC:
+        raise ValueError("not a FourCC / DX10 DDS file (legacy mask-described files are out of scope)")
+    off, misc2, array = 128, None, 0
+    if fourcc == b"DX10":
+        _need(data, 128, 20, "DDS DX10 header")
+        dxgi, dim, misc, array, misc2 = struct.unpack_from("<5I", data, 128)
+        off = 148
+        dimension = {_DIM_TEXTURE1D: "1d", _DIM_TEXTURE2D: "2d", _DIM_TEXTURE3D: "3d"}.get(dim)
+        if dimension == "2d" and misc & _DDS_MISC_CUBEMAP:
+            dimension = "cube"
+    elif fourcc in _DDS_FOURCC:
+        dxgi = _DDS_FOURCC[fourcc]
+        dimension = "cube" if caps2 & 0x200 else ("3d" if caps2 & _DDSCAPS2_VOLUME else "2d")
+    else:
+        raise ValueError("DDS FourCC %r is not supported" % fourcc)
+    dxgi = _DXGI_TYPELESS.get(dxgi, dxgi)
+    if dimension is None or dxgi not in _DXGI_REV:
+        raise ValueError("DDS: unknown dimension or DXGI format %d" % dxgi)
+    cands = _DXGI_REV[dxgi]
+    if misc2 is not None and format is None:
+        # the alpha mode tells the BC1 pair apart: straight, premultiplied or custom -> BC1_RGBA; opaque, and the
+        # "unknown" 0 of files from elsewhere -> BC1_RGB (the lowest member).  A format= hint overrides it; the
+        # re-save then carries what the hinted format writes.
+        cands = [c for c in cands if has_alpha(c[0]) == (misc2 in (1, 2, 4))] or cands
+    fmt, typ, cs = _choose(cands, format, type, "DDS")
+    alpha = Alpha.Standard
+    if has_alpha(fmt) and misc2 is not None:
+        alpha = {v: k for k, v in _ALPHA_MODE.items()}.get(misc2, Alpha.Standard)
+    is3d = dimension == "3d"
+    levels = max(levels, 1)
+    # arraySize: this project's writer emits 0 for a texture that is not an array, D3D and every other writer 1.
+    # 1 therefore reads as "not an array"; a ONE-element array written here is the one shape that comes back as a
+    # plain texture (and re-saves with arraySize 0).
+    is_array = not is3d and array > 1
+    elements, faces = (array if is_array else 1), (6 if dimension == "cube" else 1)
+    _shape_check("DDS", width, height, depth if is3d else 0, levels, faces, elements)
+    if is3d and depth < 1:
+        raise ValueError("DDS: a volume texture needs a depth")
+    tex_depth = depth if is3d else (array if is_array else 0)
+    per = [(_size(fmt, typ, max(1, width >> l), max(1, height >> l), "DDS"), max(depth >> l, 1) if is3d else 1)
+           for l in range(levels)]
+    if elements*faces*sum(s*v for s, v in per) != len(data) - off:
+        raise ValueError("DDS: %d payload bytes do not match the header" % (len(data) - off))
+    surfaces = [[[None]*faces for _ in range(v if is3d else elements)] for _s, v in per]
+    for e in range(elements):
+        for f in range(faces):
+            for l, (s, v) in enumerate(per):
+                for vol in range(v):
+                    surfaces[l][vol + e][f] = data[off:off + s]
+                    off += s
+    return TextureFile(fmt, typ, cs, alpha, dimension, width, height, tex_depth, is_array, surfaces)
+
+
+@_safely
+def read_ktx_texture(data, format=None, type=None) -> TextureFile:
+    """Inverse of write_ktx_texture (KTX 1.1, little endian).  KTX2 and big-endian files raise ValueError."""
+    _need(data, 0, 64, "KTX")
+    if data[:12] != KTX_IDENTIFIER or struct.unpack_from("<I", data, 12)[0] != KTX_ENDIANNESS:
+        raise ValueError("not a little-endian KTX 1.1 file")
+    gl_type, type_size, gl_format, internal, base, width, height, pdepth, array, faces, levels, kv = \
+        struct.unpack_from("<12I", data, 16)
+    key = (gl_type, type_size, gl_format, internal, base)
+    if key not in _KTX_REV:
+        raise ValueError("KTX: unknown format %r" % (key,))
+    fmt, typ, cs = _choose(_KTX_REV[key], format, type, "KTX")
+    dimension = "cube" if faces == 6 else ("3d" if pdepth > 0 else ("1d" if height == 0 else "2d"))
+    height, levels = max(height, 1), max(levels, 1)
+    is3d, is_array = dimension == "3d", array > 0
+    _shape_check("KTX", width, height, pdepth, levels, faces, max(array, 1))
+    if (is3d and (is_array or faces != 1)):
+        raise ValueError("KTX: 3-D arrays and 3-D cubes are not supported")
+    off = 64 + kv
+    _need(data, off, 0, "KTX key/value data")
+    compressed = gl_type == 0
+    bpp = query(fmt, typ)[2]
+    surfaces = []
+    for l in range(levels):
+        w, h = max(1, width >> l), max(1, height >> l)
+        nd = max(pdepth >> l, 1) if is3d else max(array, 1)
+        row = w*bpp
+        pad = 0 if compressed else (4 - row % 4) % 4
+        one = _size(fmt, typ, w, h, "KTX") if compressed else (row + pad)*h
+        _need(data, off, 4, "KTX imageSize")
+        image_size = struct.unpack_from("<I", data, off)[0]
+        off += 4
+        if image_size != one*nd*(faces if is_array else 1):
+            raise ValueError("KTX: level %d imageSize %d does not match the header" % (l, image_size))
+        _need(data, off, one*nd*faces, "KTX level")
+        level = []
+        for d in range(nd):
+            dep = []
+            for f in range(faces):
+                raw = data[off:off + one]
+                off += one
+                dep.append(raw if pad == 0 else b"".join(raw[y*(row + pad):y*(row + pad) + row] for y in range(h)))
+            level.append(dep)
+        surfaces.append(level)
+    if off != len(data):
+        raise ValueError("KTX: %d bytes after the last level" % (len(data) - off))
+    return TextureFile(fmt, typ, cs, Alpha.Standard, dimension, width, height, pdepth if is3d else array,
+                       is_array, surfaces)
+
+
+@_safely
+def read_pvr_texture(data, format=None, type=None) -> TextureFile:
+    """Inverse of write_pvr_texture (PVR v3, CTFS metadata included).  PVR v2 files raise ValueError."""
+    _need(data, 0, 52, "PVR")
+    version, flags, pixfmt, cspace, chtype, height, width, depth, nsurf, faces, levels, meta = \
+        struct.unpack_from("<IIQIIIIIIIII", data, 0)
+    if version != _fourcc("P", "V", "R", 3):
+        raise ValueError("not a PVR v3 file")
+    _need(data, 52, meta, "PVR metadata")
+    keys, m = set(), 52
+    while m < 52 + meta:
+        _need(data, m, 12, "PVR metadata entry")
+        four, key, n = struct.unpack_from("<3I", data, m)
+        if m + 12 + n > 52 + meta:
+            raise ValueError("PVR: metadata entry runs past the metadata block")
+        if four == _fourcc("C", "T", "F", "S"):
+            keys.add(key)
+        m += 12 + n
+    if (pixfmt, chtype) not in _PVR_REV or cspace > 1:
+        raise ValueError("PVR: unknown pixel format %#x / channel type %d" % (pixfmt, chtype))
+    cands = [(f, t, cspace) for f, t in _PVR_REV[(pixfmt, chtype)]]
+    if format is None and any(c[0] in (Format.BC1_RGB, Format.BC1_RGBA) for c in cands):
+        if _fourcc("B", "C", "1", "A") in keys:
+            cands = [c for c in cands if c[0] == Format.BC1_RGBA]
+        elif _fourcc("B", "C", "1", 0) in keys:
+            cands = [c for c in cands if c[0] == Format.BC1_RGB]
+    fmt, typ, cs = _choose(cands, format, type, "PVR")
+    alpha = Alpha.PreMultiplied if flags & 0x2 or pvr_pixel_format(fmt, Alpha.Standard) != pixfmt else Alpha.Standard
+    is3d = depth > 1
+    is_array = _fourcc("A", "R", "R", "Y") in keys or nsurf > 1
+    dimension = "cube" if faces == 6 else ("3d" if is3d else ("1d" if _fourcc("D", "I", "M", "1") in keys else "2d"))
+    _shape_check("PVR", width, height, depth, levels, faces, nsurf)
+    if depth < 1 or (is3d and (is_array or faces != 1)):
+        raise ValueError("PVR: bad depth, or a 3-D array / cube")
+    off = 52 + meta
+    sizes = [(_size(fmt, typ, max(1, width >> l), max(1, height >> l), "PVR"),
+              max(depth >> l, 1) if is3d else nsurf) for l in range(levels)]
+    if faces*sum(s*d for s, d in sizes) != len(data) - off:
+        raise ValueError("PVR: %d payload bytes do not match the header" % (len(data) - off))
+    surfaces = []
+    for s, nd in sizes:
+        level = []
+        for d in range(nd):
+            level.append([data[off + f*s:off + (f + 1)*s] for f in range(faces)])
+            off += faces*s
+        surfaces.append(level)
+    return TextureFile(fmt, typ, cs, alpha, dimension, width, height, depth if is3d else (nsurf if is_array else 0),
+                       is_array, surfaces)
+
+
+def read_texture(data, file_type=0, format=None, type=None) -> TextureFile:
+    """Read a DDS (1), KTX (2) or PVR (3) file; file_type 0 sniffs the magic (Texture.FileType values)."""
+    data = bytes(data)
+    file_type = int(file_type)
+    if file_type == 0:
+        file_type = 1 if data[:4] == b"DDS " else (2 if data[:12] == KTX_IDENTIFIER else
+                                                   (3 if data[:4] == b"PVR\x03" else 0))
+    readers = {1: read_dds_texture, 2: read_ktx_texture, 3: read_pvr_texture}
+    if file_type not in readers:
+        raise ValueError("unknown container")
+    return readers[file_type](data, format=format, type=type)

@@ -8,6 +8,7 @@
 #include "cf_device.h"
 #include "astc_tables.h"
 #include "pvrtc_surf.h"
+#include "decode_batch.h"
 #include "../../include/cuttlefish_hip.h"
 
 #include <cmath>
@@ -2188,6 +2189,249 @@ int cfhip_decode_device(cfhip_ctx* ctx, int format, int type, const void* blocks
 		HIP_TRY(ctx, hipMemsetAsync(cnt, 0, 8, lease.stream));
 	rc = decode_launch(ctx, format, type, g, blocks, out, out_pitch_bytes, nullptr, 0, width, height, cnt, false,
 		lease.stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	return lease.done(!stream_);
+}
+
+// ---- batched decode (csrc/decode.hip: cfhip_decode_batch_kernel, cfhip_decode_batch_astc_kernel) -------------
+// What a (layout, out_pixel) pair stores: false where the table of include/cuttlefish_hip.h says unsupported.
+// *kind: the CFDEC_OUT_* value of the launch (a pixel type that equals the native layout is the native launch).
+static bool decode_out_kind(int layout, int native_tb, int out_pixel, int* kind, int* out_tb)
+{
+	const bool u8 = layout == CFHIP_LAYOUT_RGBA8 || layout == CFHIP_LAYOUT_R8 || layout == CFHIP_LAYOUT_RG8;
+	switch (out_pixel) {
+		case CFHIP_DECODE_NATIVE: *kind = CFDEC_OUT_NATIVE; *out_tb = native_tb; return true;
+		case CFHIP_PIXEL_RGBA8:
+			if (!u8) return false;
+			*kind = layout == CFHIP_LAYOUT_RGBA8 ? CFDEC_OUT_NATIVE : CFDEC_OUT_RGBA8; *out_tb = 4; return true;
+		case CFHIP_PIXEL_RGBA16F:
+			if (layout != CFHIP_LAYOUT_RGBA16F) return false;
+			*kind = CFDEC_OUT_NATIVE; *out_tb = 8; return true;
+		case CFHIP_PIXEL_RGBA32F: *kind = CFDEC_OUT_RGBA32F; *out_tb = 16; return true;
+		default: return false;
+	}
+}
+
+int cfhip_decode_out_supported(int format, int type, int out_pixel)
+{
+	int l, tb, kind, otb;
+	return decoded_layout(format, type, &l, &tb) && decode_out_kind(l, tb, out_pixel, &kind, &otb) ? 1 : 0;
+}
+
+struct DecodeBatchPlan {
+	int kind, out_tb, bw, bh, bb;
+	std::vector<cfdec_batch_entry> entries;   // blocks / out still the caller's pointers
+	std::vector<size_t> payload, span;        // payload bytes; bytes from out to the end of the last row
+	uint32_t total_wg;
+};
+
+// Every check of a batched decode, made before the context is touched (so that they need no device): the pair,
+// the output, the table and every surface.  ctx may be NULL here; the caller rejects that afterwards.
+static int decode_batch_check(cfhip_ctx* ctx, const char* what, int format, int type, int out_pixel,
+	const cfhip_decode_surface* s, size_t n, bool host, DecodeBatchPlan* p)
+{
+	int layout, tb;
+	if (!decoded_layout(format, type, &layout, &tb))
+		return fail(ctx, CFHIP_E_UNSUPPORTED, "%s: (format %d, type %d) has no decoded layout", what, format, type);
+	if (!decode_out_kind(layout, tb, out_pixel, &p->kind, &p->out_tb))
+		return fail(ctx, CFHIP_E_UNSUPPORTED, "%s: output pixel type %d is not offered for (format %d, type %d)", what,
+			out_pixel, format, type);
+	if (n && !s)
+		return fail(ctx, CFHIP_E_INVALID, "%s: surfaces is NULL", what);
+	if (n > 0xFFFFFFu)
+		return fail(ctx, CFHIP_E_INVALID, "%s: too many surfaces (%zu)", what, n);
+	block_dims(format, &p->bw, &p->bh);
+	p->bb = block_bytes(format);
+	const bool astc = format >= CFHIP_FORMAT_ASTC_4x4;
+	p->entries.resize(n);
+	p->payload.resize(n);
+	p->span.resize(n);
+	uint64_t wg = 0;
+	for (size_t i = 0; i < n; ++i) {
+		if (!s[i].blocks || !s[i].out)
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: blocks or out is NULL", what, i);
+		if (!s[i].width || !s[i].height)
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu is empty (%ux%u)", what, i, s[i].width, s[i].height);
+		const size_t row = (size_t)s[i].width*(size_t)p->out_tb;
+		if (s[i].out_pitch_bytes < row)
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: out pitch %zu < %zu", what, i, s[i].out_pitch_bytes, row);
+		cfdec_batch_entry& e = p->entries[i];
+		e.blocks = static_cast<const uint8_t*>(s[i].blocks);
+		e.out = static_cast<uint8_t*>(s[i].out);
+		e.out_pitch = s[i].out_pitch_bytes;
+		e.width = s[i].width; e.height = s[i].height;
+		e.bx = (e.width + (uint32_t)p->bw - 1)/(uint32_t)p->bw;
+		e.by = (e.height + (uint32_t)p->bh - 1)/(uint32_t)p->bh;
+		p->payload[i] = (size_t)e.bx*e.by*(size_t)p->bb;
+		p->span[i] = (size_t)(e.height - 1)*s[i].out_pitch_bytes + row;
+		if (host && s[i].blocks_bytes < p->payload[i])
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: blocks_bytes %zu < %zu", what, i, s[i].blocks_bytes,
+				p->payload[i]);
+		if (host && s[i].out_capacity < p->span[i])
+			return fail(ctx, CFHIP_E_CAPACITY, "%s: surface %zu: out_capacity %zu < %zu", what, i, s[i].out_capacity,
+				p->span[i]);
+		e.wgx = astc ? (e.bx + CFDEC_ASTC_RUN - 1)/CFDEC_ASTC_RUN : 0;
+		e.wg_begin = (uint32_t)wg;
+		wg += astc ? (uint64_t)e.wgx*e.by : ((uint64_t)e.bx*e.by + CFDEC_WG - 1)/CFDEC_WG;
+		if (wg > 0x7FFFFFFFull)
+			return fail(ctx, CFHIP_E_INVALID, "%s: the surfaces are too large for one launch", what);
+	}
+	p->total_wg = (uint32_t)wg;
+	return CFHIP_OK;
+}
+
+// the surface table into staging and the one launch of the call; the entries hold device pointers by now
+static int decode_batch_launch(cfhip_ctx* ctx, StagingLease& lease, int format, int type, DecodeBatchPlan& p,
+	unsigned long long* d_errors)
+{
+	const hipStream_t stream = lease.stream;
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = format >= CFHIP_FORMAT_ASTC_4x4 ? "cfhip_decode_batch_astc_kernel" : "cfhip_decode_batch_kernel";
+	for (cfdec_batch_entry& e : p.entries) {
+		e.out_vec = ((uintptr_t)e.out % 16 == 0 && e.out_pitch % 16 == 0) ? 1 : 0;
+		e.blk_vec = ((uintptr_t)e.blocks % (uintptr_t)p.bb == 0) ? 1 : 0;
+	}
+	const size_t bytes = p.entries.size()*sizeof(cfdec_batch_entry);
+	int rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, bytes);
+	if (rc != CFHIP_OK)
+		return rc;
+	// pageable source: the runtime stages the copy before returning, so the plan may die
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, p.entries.data(), bytes, hipMemcpyHostToDevice, stream));
+	if (d_errors)
+		HIP_TRY(ctx, hipMemsetAsync(d_errors, 0, 8*p.entries.size(), stream));
+	hipEvent_t a, b;
+	rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, stream));
+	const hipError_t e = cfhip_launch_decode_batch(format, type, p.kind, static_cast<const cfdec_batch_entry*>(ctx->d_batch),
+		(uint32_t)p.entries.size(), p.total_wg, p.bw, p.bh, d_errors, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "decode_batch launch: %s", hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, stream));
+	return CFHIP_OK;
+}
+
+int cfhip_decode_batch(cfhip_ctx* ctx, int format, int type, int out_pixel, const cfhip_decode_surface* surfaces,
+	size_t n, uint64_t* error_blocks)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	DecodeBatchPlan p;
+	int rc = decode_batch_check(ctx, "decode_batch", format, type, out_pixel, surfaces, n, true, &p);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	if (!n)
+		return CFHIP_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, ctx->stream);
+	const hipStream_t stream = lease.stream;
+	// d_src: the payloads, a run of surfaces whose blocks are consecutive in host memory as one copy.  d_out: the
+	// texels, a run of tightly pitched surfaces whose outputs are consecutive in host memory as one copy back (a
+	// pitched output has rows of its own on the device and comes back as a 2-D copy); then the error counters.
+	struct Run { size_t first, last, dev, bytes; };
+	std::vector<Run> up, down;
+	std::vector<size_t> src_off(n), out_off(n);
+	size_t so = 0, oo = 0;
+	for (size_t i = 0; i < n; ++i) {
+		const uint8_t* b = static_cast<const uint8_t*>(surfaces[i].blocks);
+		if (i && b == static_cast<const uint8_t*>(surfaces[i - 1].blocks) + p.payload[i - 1]) {
+			src_off[i] = src_off[i - 1] + p.payload[i - 1];
+			up.back().last = i;
+			up.back().bytes += p.payload[i];
+		} else {
+			so = (so + 255) & ~(size_t)255;
+			src_off[i] = so;
+			up.push_back({i, i, so, p.payload[i]});
+		}
+		so = src_off[i] + p.payload[i];
+		const bool tight = surfaces[i].out_pitch_bytes == (size_t)surfaces[i].width*(size_t)p.out_tb;
+		const bool prev_tight = i && surfaces[i - 1].out_pitch_bytes == (size_t)surfaces[i - 1].width*(size_t)p.out_tb;
+		if (tight && prev_tight && static_cast<uint8_t*>(surfaces[i].out) == static_cast<uint8_t*>(surfaces[i - 1].out) + p.span[i - 1]) {
+			out_off[i] = out_off[i - 1] + p.span[i - 1];
+			down.back().last = i;
+			down.back().bytes += p.span[i];
+		} else {
+			oo = (oo + 255) & ~(size_t)255;
+			out_off[i] = oo;
+			down.push_back({i, i, oo, p.span[i]});
+		}
+		// on the device every surface is tightly pitched
+		oo = out_off[i] + (size_t)surfaces[i].width*(size_t)p.out_tb*surfaces[i].height;
+	}
+	const size_t cnt_off = (oo + 255) & ~(size_t)255;
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, so);
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, cnt_off + 8*n);
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* d_src = static_cast<uint8_t*>(ctx->d_src);
+	uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out);
+	for (const Run& r : up)
+		HIP_TRY(ctx, hipMemcpyAsync(d_src + r.dev, surfaces[r.first].blocks, r.bytes, hipMemcpyHostToDevice, stream));
+	for (size_t i = 0; i < n; ++i) {
+		p.entries[i].blocks = d_src + src_off[i];
+		p.entries[i].out = d_out + out_off[i];
+		p.entries[i].out_pitch = (size_t)surfaces[i].width*(size_t)p.out_tb;
+	}
+	unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(d_out + cnt_off);
+	rc = decode_batch_launch(ctx, lease, format, type, p, d_cnt);
+	if (rc != CFHIP_OK)
+		return rc;
+	for (const Run& r : down) {
+		const cfhip_decode_surface& s = surfaces[r.first];
+		const size_t row = (size_t)s.width*(size_t)p.out_tb;
+		if (s.out_pitch_bytes == row)
+			HIP_TRY(ctx, hipMemcpyAsync(s.out, d_out + r.dev, r.bytes, hipMemcpyDeviceToHost, stream));
+		else
+			HIP_TRY(ctx, hipMemcpy2DAsync(s.out, s.out_pitch_bytes, d_out + r.dev, row, row, s.height,
+				hipMemcpyDeviceToHost, stream));
+	}
+	std::vector<unsigned long long> counts(n, 0);
+	HIP_TRY(ctx, hipMemcpyAsync(counts.data(), d_cnt, 8*n, hipMemcpyDeviceToHost, stream));
+	rc = lease.done(true);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (error_blocks)
+		for (size_t i = 0; i < n; ++i)
+			error_blocks[i] = (uint64_t)counts[i];
+	return CFHIP_OK;
+}
+
+int cfhip_decode_batch_device(cfhip_ctx* ctx, int format, int type, int out_pixel,
+	const cfhip_decode_surface* surfaces, size_t n, uint64_t* error_blocks_device, void* stream_)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	DecodeBatchPlan p;
+	int rc = decode_batch_check(ctx, "decode_batch_device", format, type, out_pixel, surfaces, n, false, &p);
+	if (rc != CFHIP_OK)
+		return rc;
+	if ((uintptr_t)error_blocks_device % 8)
+		return fail(ctx, CFHIP_E_INVALID, "decode_batch_device: error_blocks_device must be 8-byte aligned");
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	if (!n)
+		return CFHIP_OK;
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	rc = decode_batch_launch(ctx, lease, format, type, p, reinterpret_cast<unsigned long long*>(error_blocks_device));
 	if (rc != CFHIP_OK)
 		return rc;
 	return lease.done(!stream_);

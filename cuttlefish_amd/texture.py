@@ -618,6 +618,35 @@ class Texture:
         self._alpha, self._mask = Alpha(alpha_type), tuple(bool(m) for m in color_mask)
         return True
 
+    @staticmethod
+    def load(file_name_or_bytes, file_type: FileType = FileType.Auto, format=None, type=None,
+             device_id: int = 0) -> Optional["Texture"]:
+        """A converted texture from a DDS / KTX / PVR file (a path or its bytes), None where it cannot be read.
+        format / type select another member of a collision set (containers.read_texture).  For a file this
+        project wrote, load(b).save_bytes(same type) returns b."""
+        data = file_name_or_bytes
+        try:
+            if not isinstance(data, (bytes, bytearray, memoryview)):
+                if FileType(file_type) == FileType.Auto:
+                    file_type = Texture.file_type(str(data))
+                with open(data, "rb") as f:
+                    data = f.read()
+            tf = containers.read_texture(data, int(file_type), format=format, type=type)
+        except (OSError, ValueError):
+            return None
+        dim = {"1d": Dimension.Dim1D, "2d": Dimension.Dim2D, "3d": Dimension.Dim3D, "cube": Dimension.Cube}[tf.dimension]
+        t = Texture(device_id=device_id)
+        if not t.initialize(dim, tf.width, tf.height, tf.depth, tf.levels, tf.color_space):
+            return None
+        # one buffer, the surfaces views of it in storage order: a batched decode then uploads them as one copy
+        blob = np.frombuffer(b"".join(f for level in tf.surfaces for dep in level for f in dep), np.uint8)
+        offs = np.cumsum([0] + [len(f) for level in tf.surfaces for dep in level for f in dep])
+        it = iter(range(len(offs) - 1))
+        t._textures = [[[blob[offs[i]:offs[i + 1]] for i in (next(it) for _ in dep)] for dep in level]
+                       for level in tf.surfaces]
+        t._format, t._type, t._alpha = tf.fmt, tf.typ, tf.alpha
+        return t
+
     def converted(self) -> bool:
         return bool(self._textures)
 
@@ -720,6 +749,145 @@ class Texture:
                    api.Layout.R16_SNorm: 1023.0, api.Layout.RG16_SNorm: 1023.0}[layout]
             val = np.maximum(raw.astype(np.float64)/div, -1.0).astype(np.float32)
         out[..., :n] = val
+        return out
+
+    def _flat(self):
+        """[(mip, depth, face, payload)] in storage order"""
+        return [(m, d, f, p) for m, level in enumerate(self._textures) for d, dep in enumerate(level)
+                for f, p in enumerate(dep)]
+
+    def decode_images(self, pixel=api.PixelType.RGBA32F):
+        """Every surface of this converted texture as [mip][depth][face] arrays of `pixel` ((h, w, 4)); RGBA32F
+        equals decode_image() of each surface bit for bit.  Block formats decode in ONE batched launch
+        (Context.decode_batch); standard formats and PVRTC go through their per-surface entries, which offer
+        RGBA32F and RGBA8 respectively (PVRTC as RGBA32F is v / 255 of those bytes).  Raises ValueError for a pixel
+        type the format does not offer; None when the texture is not converted."""
+        if not self._textures:
+            return None
+        pixel = api.PixelType(pixel)
+        flat = self._flat()
+        ctx = self._context()
+        if int(self._format) >= int(Format.BC1_RGB) and self._format not in api.PVRTC_FORMATS:
+            if not api.decode_out_supported(self._format, self._type, pixel):
+                raise ValueError("decode_images: %s / %s does not decode to %s" %
+                                 (self._format.name, self._type.name, pixel.name))
+            outs, _ = ctx.decode_batch([p for _, _, _, p in flat], self._format, self._type,
+                                       [(self.width(m), self.height(m)) for m, _, _, _ in flat], pixel)
+        elif self._format in api.PVRTC_FORMATS:
+            if pixel == api.PixelType.RGBA16F:
+                raise ValueError("decode_images: PVRTC decodes to RGBA8 or RGBA32F")
+            outs = [ctx.decode_pvrtc(p, self._format, self.width(m), self.height(m), self._type) for m, _, _, p in flat]
+            if pixel == api.PixelType.RGBA32F:
+                outs = [(o.astype(np.float64)/255.0).astype(np.float32) for o in outs]
+        else:
+            if pixel != api.PixelType.RGBA32F:
+                raise ValueError("decode_images: standard formats unpack to RGBA32F")
+            outs = [ctx.unpack(p, self._format, self._type, self.width(m), self.height(m)) for m, _, _, p in flat]
+        it = iter(outs)
+        return [[[next(it) for _ in dep] for dep in level] for level in self._textures]
+
+    def transcode(self, format, type, quality: Quality = Quality.Normal, alpha_type: Optional[Alpha] = None,
+                  color_mask: Sequence[bool] = (True, True, True, True), regenerate_mips: bool = False,
+                  filter=api.ResizeFilter.CatmullRom) -> Optional["Texture"]:
+        """A new converted texture of the same shape in another (format, type), made on the device: the payloads
+        are uploaded, decoded into device buffers (one batched launch for block formats), encoded from there with
+        cfhip_encode_device / cfhip_pvrtc_encode_device and only the new payloads come back.  regenerate_mips:
+        only level 0 is decoded and the other levels (as many as this texture has) come from
+        cfhip_generate_mips_array_device with `filter`.  The colour space and, unless given, the alpha type carry
+        over.  None where convert() would return False, and when this texture is not converted.
+        The result is byte-identical to an unconverted Texture built from decode_image() of every surface (of
+        level 0, then generate_mipmaps(filter, mip_levels=mip_level_count()), when regenerating) and convert()
+        with the same arguments.  3-D textures with regenerate_mips take that host route itself."""
+        import torch
+        if not self._textures or not self.is_format_valid(format, type):
+            return None
+        format, type = Format(format), Type(type)
+        if self._color_space == ColorSpace.sRGB and not self.has_native_srgb(format, type):
+            return None
+        alpha_type = self._alpha if alpha_type is None else Alpha(alpha_type)
+        pvrtc_out = format in api.PVRTC_FORMATS
+        if pvrtc_out and any(v & (v - 1) for m in range(self._mips) for v in (self.width(m), self.height(m))):
+            return None
+        out = Texture(self._dim, self._w, self._h, self._depth, self._mips, self._color_space,
+                      device_id=self._device_id)
+        out._ctx = self._ctx
+        src_block = int(self._format) >= int(Format.BC1_RGB) and self._format not in api.PVRTC_FORMATS
+        src_pvrtc = self._format in api.PVRTC_FORMATS
+        # the intermediate: RGBA8 where the source offers it and the target quantises its source to 8 bits (the
+        # encoder's round(clamp(f) * 255) of (float)(v / 255.0) is v again); RGBA32F otherwise
+        to8 = (type == Type.UNorm and int(format) >= int(Format.BC1_RGB) and
+               format not in (Format.EAC_R11, Format.EAC_R11G11))        # EAC keeps more than 8 bits of a float
+        if (regenerate_mips and self._dim == Dimension.Dim3D) or (src_pvrtc and not to8):
+            # the defined route itself, through the host: 3-D chains (generated along the depth too) and PVRTC
+            # sources, which decode to RGBA8 only, into targets that read floats
+            for m, d, f, _ in self._flat():
+                if m == 0 or not regenerate_mips:
+                    args = (CubeFace(f), m, d) if self._faces == 6 else (m, d)
+                    out._images[m][d][f] = self.decode_image(*args)
+            if regenerate_mips and not out.generate_mipmaps(filter, mip_levels=self._mips):
+                return None
+            return out if out.convert(format, type, quality, alpha_type, color_mask) else None
+        ctx = self._context()
+        dev = "cuda:%d" % self._device_id
+        flat = [s for s in self._flat() if not regenerate_mips or s[0] == 0]
+        if src_pvrtc or (src_block and to8 and api.decode_out_supported(self._format, self._type, api.PixelType.RGBA8)):
+            pix, tb = api.PixelType.RGBA8, 4
+        else:
+            pix, tb = api.PixelType.RGBA32F, 16
+        blob = torch.from_numpy(np.concatenate([np.ascontiguousarray(p, dtype=np.uint8).reshape(-1)
+                                                for _, _, _, p in flat])).to(dev)
+        offs, o = [], 0
+        for _, _, _, p in flat:
+            offs.append(o)
+            o += int(p.nbytes)
+        texels = [torch.empty((self.height(m), self.width(m), tb), dtype=torch.uint8, device=dev) for m, _, _, _ in flat]
+        if src_block:
+            ctx.decode_batch_device([dict(blocks=blob.data_ptr() + off, out=t.data_ptr(), width=self.width(m),
+                                          height=self.height(m), out_pitch_bytes=self.width(m)*tb)
+                                     for (m, _, _, _), off, t in zip(flat, offs, texels)],
+                                    self._format, self._type, pix)
+        else:
+            # per-surface entries; a payload inside the blob may sit at any offset, PVRTC wants 4-byte alignment
+            # (its payloads are multiples of 8 bytes, so the offsets are)
+            for (m, _, _, _), off, t in zip(flat, offs, texels):
+                if src_pvrtc:
+                    ctx.decode_pvrtc_device(blob.data_ptr() + off, self._format, self.width(m), self.height(m),
+                                            t.data_ptr(), self.width(m)*4, self._type)
+                else:
+                    ctx.unpack_device(blob.data_ptr() + off, self._format, self._type, self.width(m), self.height(m),
+                                      t.data_ptr(), self.width(m)*16)
+        # sources of the encode: (mip, depth, face, tensor, pixel type)
+        srcs = [(m, d, f, t, pix) for (m, d, f, _), t in zip(flat, texels)]
+        if regenerate_mips and self._mips > 1:
+            gen = [[torch.empty((self.height(m), self.width(m), 4), dtype=torch.float32, device=dev)
+                    for m in range(1, self._mips)] for _ in srcs]
+            ctx.generate_mips_array_device([t.data_ptr() for _, _, _, t, _ in srcs], pix, self._w, self._h,
+                                           self._w*tb, [[g.data_ptr() for g in chain] for chain in gen],
+                                           color_space=self._color_space, filter=int(api.ResizeFilter(filter)))
+            for (_, d, f, _, _), chain in zip(list(srcs), gen):
+                srcs += [(m, d, f, g, api.PixelType.RGBA32F) for m, g in enumerate(chain, start=1)]
+        params = api.make_params(format, type, quality, alpha_type, color_mask, self._color_space)
+        size = (api.pvrtc_payload_size if pvrtc_out else api.payload_size)
+        pays = [torch.empty(size(format, type, self.width(m), self.height(m)), dtype=torch.uint8, device=dev)
+                for m, _, _, _, _ in srcs]
+        surfaces = [dict(pixels=t.data_ptr(), pixel_type=int(pt), width=self.width(m), height=self.height(m),
+                         row_pitch_bytes=self.width(m)*(4 if pt == api.PixelType.RGBA8 else 16), out=p.data_ptr(),
+                         out_capacity=p.numel()) for (m, _, _, t, pt), p in zip(srcs, pays)]
+        try:
+            # one call per pixel type: level 0 may be RGBA8 where the regenerated levels are RGBA32F
+            for pt in sorted({s["pixel_type"] for s in surfaces}):
+                group = [s for s in surfaces if s["pixel_type"] == pt]
+                (ctx.encode_pvrtc_device if pvrtc_out else ctx.encode_device)(group, params)
+        except api.CfhipError as e:
+            if e.code == api.E_UNSUPPORTED:
+                return None
+            raise
+        host = {(m, d, f): p.cpu().numpy() for (m, d, f, _, _), p in zip(srcs, pays)}
+        out._textures = [[[host[(m, d, f)] for f in range(self._faces)] for d in range(self.depth(m))]
+                         for m in range(self._mips)]
+        out._images = [[[None]*self._faces for _ in range(self.depth(m))] for m in range(self._mips)]
+        out._format, out._type = format, type
+        out._alpha, out._mask = alpha_type, tuple(bool(c) for c in color_mask)
         return out
 
     def _compare_pvrtc(self, ctx, source, mask, ssim):

@@ -369,6 +369,51 @@ int cfhip_decode_device(cfhip_ctx* ctx, int format, int type, const void* blocks
 	uint32_t width, uint32_t height, void* out, size_t out_pitch_bytes,
 	uint64_t* error_blocks_device, void* stream);
 
+/* ---- Batched decode: every surface of a texture (mip chain, cube faces, array layers) in ONE launch, to the
+ * native layout or to pixels an encoder, cfhip_image_ops_device or cfhip_generate_mips*_device can read ----
+ *
+ * Formats 29..56, the pairs cfhip_query accepts; standard formats and PVRTC are CFHIP_E_UNSUPPORTED (they keep
+ * their own per-surface entries).  out_pixel is CFHIP_DECODE_NATIVE or a cfhip_pixel_type; the values are the
+ * ones cfhip_compare documents, absent channels 0, 0, 1, every quotient the correctly rounded single:
+ *
+ *   native layout        RGBA8                 RGBA16F            RGBA32F
+ *   RGBA8, R8, RG8       the bytes, expanded   unsupported        (float)(v / 255.0)
+ *   R8 / RG8 SNorm       unsupported           unsupported        (float)max(v / 127.0, -1)
+ *   R16 / RG16 (EAC)     unsupported           unsupported        (float)(v / 2047.0), signed (float)max(v / 1023.0, -1)
+ *   RGBA16F              unsupported           the bit patterns   the half widened exactly
+ *
+ * An unsupported cell is CFHIP_E_UNSUPPORTED; cfhip_decode_out_supported answers the table (1 / 0) without a
+ * device.  Each surface decodes exactly as cfhip_decode decodes it; error blocks are counted per surface.
+ * One launch per call: a surface table travels through the context's staging and every workgroup finds its
+ * surface by a wave-uniform binary search.  n == 0 is CFHIP_OK and does nothing.
+ * Stream and error rules are those of cfhip_decode*: every argument of every surface is checked before anything
+ * is enqueued (and before ctx is looked at: a NULL ctx is reported last); stream == NULL means the context's
+ * stream and the call synchronises. */
+typedef struct cfhip_decode_surface {
+	const void* blocks;      /* payload of this surface */
+	size_t blocks_bytes;     /* host form: >= its payload size; device form: ignored */
+	uint32_t width, height;
+	void* out;               /* texels, rows out_pitch_bytes apart */
+	size_t out_pitch_bytes;  /* >= width * bytes per output texel */
+	size_t out_capacity;     /* host form: >= (height - 1) * pitch + width * texel bytes, else CFHIP_E_CAPACITY */
+} cfhip_decode_surface;
+#define CFHIP_DECODE_NATIVE (-1)   /* the layout cfhip_decoded_layout names */
+
+/* Host buffers.  Surfaces whose blocks are consecutive in host memory (a loaded file) upload as one copy; tightly
+ * pitched outputs that are consecutive in host memory come back as one copy.  error_blocks: n counts, or NULL.
+ * Blocking. */
+int cfhip_decode_batch(cfhip_ctx* ctx, int format, int type, int out_pixel,
+	const cfhip_decode_surface* surfaces, size_t n_surfaces, uint64_t* error_blocks);
+
+/* Device buffers: `surfaces` is a host array of device pointers.  16-byte aligned outputs and pitches and
+ * block-aligned payloads take the vector paths, per surface; anything else is legal.  error_blocks_device: n
+ * uint64 on the device (8-byte aligned), zeroed by the call on the stream, or NULL. */
+int cfhip_decode_batch_device(cfhip_ctx* ctx, int format, int type, int out_pixel,
+	const cfhip_decode_surface* surfaces, size_t n_surfaces, uint64_t* error_blocks_device, void* stream);
+
+/* 1 where (format, type) decodes to out_pixel, else 0.  Pure, needs no device. */
+int cfhip_decode_out_supported(int format, int type, int out_pixel);
+
 /* Decode and compare in one pass, without writing texels: sse[c] = the exact sum over the width x height
  * texels of (decoded - reference)^2 of channel c.  ref_rgba8: RGBA8 rows ref_pitch_bytes apart
  * (>= width * 4).  Layouts RGBA8, and R8 / RG8 (BC4 / BC5 UNorm), which compare R (and G) and report 0 for
