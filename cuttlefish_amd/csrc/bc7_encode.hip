@@ -88,6 +88,18 @@ __device__ const uint8_t k_anchor3b[64] = {
 	15, 3,15,15,15,15,15,15, 15,15,15,15, 3,15,15, 8
 };
 
+// Texels of subset sb of a three-subset partition word (2 bits per texel): the texels whose pair equals sb as
+// bits at the even positions, then the even bits squeezed into the low half.
+__device__ __forceinline__ uint32_t part3_mask(uint32_t p3, uint32_t sb)
+{
+	const uint32_t lo = p3 & 0x55555555u, hi = (p3 >> 1) & 0x55555555u;
+	uint32_t x = sb == 0u ? ~(lo | hi) & 0x55555555u : (sb == 1u ? lo & ~hi : (sb == 2u ? hi & ~lo : 0u));
+	x = (x | (x >> 1)) & 0x33333333u;
+	x = (x | (x >> 2)) & 0x0F0F0F0Fu;
+	x = (x | (x >> 4)) & 0x00FF00FFu;
+	return (x | (x >> 8)) & 0xFFFFu;
+}
+
 struct SubFit {
 	uint32_t e0, e1;   // dequantised endpoints, bytes r,g,b,a
 	uint32_t q0, q1;   // quantised fields, bytes r,g,b,a
@@ -343,13 +355,15 @@ __device__ __forceinline__ uint32_t ycc_pp_sum(const Tex& tx, uint32_t mask, con
 #endif
 
 // Diagnostic counters (never set in the product build): per wave pass, how often the starts trip reads the
-// fit-geometry cache and how often the starts trip / the perturbation pass have only fits of <= 4 palette entries.
+// fit-geometry cache, how often the starts trip / the perturbation pass have only fits of <= 4 palette entries, how
+// often they have no fit with p-bits, and how often the perturbation pass finds pp_sum in the cache.
 // Read by cfhip_bc7_diag() below.
 #ifndef CF_BC7_DIAG
 #define CF_BC7_DIAG 0
 #endif
 #if CF_BC7_DIAG
-enum { CF_DIAG_STARTS, CF_DIAG_STARTS_CACHED, CF_DIAG_STARTS_NARROW, CF_DIAG_PERTURB, CF_DIAG_PERTURB_NARROW, CF_DIAG_N };
+enum { CF_DIAG_STARTS, CF_DIAG_STARTS_CACHED, CF_DIAG_STARTS_NARROW, CF_DIAG_PERTURB, CF_DIAG_PERTURB_NARROW,
+	CF_DIAG_STARTS_NOPB, CF_DIAG_PERTURB_NOPB, CF_DIAG_PERTURB_PPHIT, CF_DIAG_N };
 __device__ unsigned long long cf_bc7_diag[CF_DIAG_N];
 #define CF_DIAG_COUNT(i, cond) do { uint32_t l_; CF_FRESH_LANE(l_); if (l_ == 0u && (cond)) atomicAdd(&cf_bc7_diag[i], 1ull); } while (0)
 #else
@@ -924,39 +938,105 @@ __device__ __forceinline__ uint4 pack_block_group(const uint32_t* wcol, uint32_t
 	return r;
 }
 
-// Partition score of the two-phase search (oracle: subset_residual): the scatter of the
-// subset that no line through its mean can capture, (trace(C) - a'Ca)/n, with a = the
-// power-iterated principal axis.  Same statistics and axis arithmetic as fit_lane.
-// A4 = false: the block is opaque (the alpha plane is masked to zero), so every term that
-// carries the fourth channel is an exact zero and is left out -- same result, bit for bit.
-template <bool A4>
-__device__ __forceinline__ float subset_residual(const Tex& tx, uint32_t mask, float& along)
+// The 14 integer moments of a set of texels: channel sums and sums of products.  Exact unsigned integers, so the
+// moments of a subset are the block's minus those of the other subsets, bit for bit.
+struct Moments {
+	uint32_t s[4];
+	uint32_t q00, q01, q02, q03, q11, q12, q13, q22, q23, q33;
+};
+
+// Per-block table of the whole block's moments (built once per workgroup, kernel prologue), 10 words per block:
+// words 0..3 = q_cc | s_c << 20 (q <= 16 * 255^2 < 2^20, s <= 16 * 255 < 2^12), words 4..9 = q01 q02 q03 q12 q13 q23.
+// The block's own channel set is applied: every alpha term of an opaque block is zero, as planes() zeroes its plane.
+#define CF_BC7_MOM_WORDS 10
+__device__ __forceinline__ void block_moments_put(const uint32_t* plan, uint32_t* mom, uint32_t t)
 {
-	const uint32_t n = (uint32_t)__builtin_popcount(mask);
-	uint32_t s[4] = {0, 0, 0, 0};
-	uint32_t q00 = 0, q01 = 0, q02 = 0, q03 = 0, q11 = 0, q12 = 0, q13 = 0, q22 = 0, q23 = 0,
-		q33 = 0;
+	const uint32_t b = t >> 4, m = t & 15u;
+	if (m >= CF_BC7_MOM_WORDS)
+		return;
+	// channel pair (ca, cb) of word m
+	const uint32_t ca = m < 4u ? m : (m < 7u ? 0u : (m < 9u ? 1u : 2u));
+	const uint32_t cb = m < 4u ? m : (m < 7u ? m - 3u : (m < 9u ? m - 5u : 3u));
+	const uint32_t* pb = plan + b*16u;
+	const bool opaque = (pb[3] & pb[7] & pb[11] & pb[15]) == 0xFFFFFFFFu;
+	uint32_t q = 0, sm = 0;
+#pragma unroll
+	for (uint32_t r = 0; r < 4u; ++r) {
+		const uint32_t A = (opaque && ca == 3u) ? 0u : pb[4u*r + ca], B = (opaque && cb == 3u) ? 0u : pb[4u*r + cb];
+		q = __builtin_amdgcn_udot4(A, B, q, false);
+		sm = __builtin_amdgcn_udot4(A, 0x01010101u, sm, false);
+	}
+	mom[b*CF_BC7_MOM_WORDS + m] = m < 4u ? q | (sm << 20) : q;
+}
+
+// Moments of one (TWO = false) or two disjoint texel sets of a block in one pass over its planar rows.
+// A4 = false: the block is opaque, every term that carries the fourth channel is an exact zero and is left out.
+template <bool A4, bool TWO>
+__device__ __forceinline__ void moments_rows(const Tex& tx, uint32_t mask1, uint32_t mask2, Moments& a, Moments& b)
+{
+#pragma unroll
+	for (int c = 0; c < 4; ++c) { a.s[c] = 0; b.s[c] = 0; }
+	a.q00 = a.q01 = a.q02 = a.q03 = a.q11 = a.q12 = a.q13 = a.q22 = a.q23 = a.q33 = 0;
+	b.q00 = b.q01 = b.q02 = b.q03 = b.q11 = b.q12 = b.q13 = b.q22 = b.q23 = b.q33 = 0;
 #pragma unroll 1
 	for (uint32_t r = 0; r < 4u; ++r) {
 		uint32_t P[4];
 		planes<false>(tx, *reinterpret_cast<const uint4*>(tx.pl() + 4u*r), P);
-		const uint32_t m4 = bytemask4((mask >> (4u*r)) & 15u);
-		const uint32_t M0 = P[0] & m4, M1 = P[1] & m4, M2 = P[2] & m4, M3 = A4 ? P[3] & m4 : 0u;
-		s[0] = __builtin_amdgcn_udot4(M0, 0x01010101u, s[0], false);
-		s[1] = __builtin_amdgcn_udot4(M1, 0x01010101u, s[1], false);
-		s[2] = __builtin_amdgcn_udot4(M2, 0x01010101u, s[2], false);
-		if (A4) s[3] = __builtin_amdgcn_udot4(M3, 0x01010101u, s[3], false);
-		q00 = __builtin_amdgcn_udot4(M0, P[0], q00, false);
-		q01 = __builtin_amdgcn_udot4(M0, P[1], q01, false);
-		q02 = __builtin_amdgcn_udot4(M0, P[2], q02, false);
-		if (A4) q03 = __builtin_amdgcn_udot4(M0, P[3], q03, false);
-		q11 = __builtin_amdgcn_udot4(M1, P[1], q11, false);
-		q12 = __builtin_amdgcn_udot4(M1, P[2], q12, false);
-		if (A4) q13 = __builtin_amdgcn_udot4(M1, P[3], q13, false);
-		q22 = __builtin_amdgcn_udot4(M2, P[2], q22, false);
-		if (A4) q23 = __builtin_amdgcn_udot4(M2, P[3], q23, false);
-		if (A4) q33 = __builtin_amdgcn_udot4(M3, P[3], q33, false);
+#pragma unroll
+		for (int k = 0; k < (TWO ? 2 : 1); ++k) {
+			Moments& o = k ? b : a;
+			const uint32_t m4 = bytemask4(((k ? mask2 : mask1) >> (4u*r)) & 15u);
+			const uint32_t M0 = P[0] & m4, M1 = P[1] & m4, M2 = P[2] & m4, M3 = A4 ? P[3] & m4 : 0u;
+			o.s[0] = __builtin_amdgcn_udot4(M0, 0x01010101u, o.s[0], false);
+			o.s[1] = __builtin_amdgcn_udot4(M1, 0x01010101u, o.s[1], false);
+			o.s[2] = __builtin_amdgcn_udot4(M2, 0x01010101u, o.s[2], false);
+			if (A4) o.s[3] = __builtin_amdgcn_udot4(M3, 0x01010101u, o.s[3], false);
+			o.q00 = __builtin_amdgcn_udot4(M0, P[0], o.q00, false);
+			o.q01 = __builtin_amdgcn_udot4(M0, P[1], o.q01, false);
+			o.q02 = __builtin_amdgcn_udot4(M0, P[2], o.q02, false);
+			if (A4) o.q03 = __builtin_amdgcn_udot4(M0, P[3], o.q03, false);
+			o.q11 = __builtin_amdgcn_udot4(M1, P[1], o.q11, false);
+			o.q12 = __builtin_amdgcn_udot4(M1, P[2], o.q12, false);
+			if (A4) o.q13 = __builtin_amdgcn_udot4(M1, P[3], o.q13, false);
+			o.q22 = __builtin_amdgcn_udot4(M2, P[2], o.q22, false);
+			if (A4) o.q23 = __builtin_amdgcn_udot4(M2, P[3], o.q23, false);
+			if (A4) o.q33 = __builtin_amdgcn_udot4(M3, P[3], o.q33, false);
+		}
 	}
+}
+
+// The block's moments (table words tw) minus those of a (TWO: and of b): the subset that was not summed
+template <bool A4, bool TWO>
+__device__ __forceinline__ Moments moments_rest(const uint32_t* tw, const Moments& a, const Moments& b)
+{
+	Moments o;
+	const uint32_t w0 = tw[0], w1 = tw[1], w2 = tw[2], w3 = A4 ? tw[3] : 0u;
+#define CF_REST(f, tot) o.f = (tot) - a.f - (TWO ? b.f : 0u)
+	CF_REST(s[0], w0 >> 20); CF_REST(s[1], w1 >> 20); CF_REST(s[2], w2 >> 20);
+	CF_REST(q00, w0 & 0xFFFFFu); CF_REST(q11, w1 & 0xFFFFFu); CF_REST(q22, w2 & 0xFFFFFu);
+	CF_REST(q01, tw[4]); CF_REST(q02, tw[5]); CF_REST(q12, tw[7]);
+	if (A4) {
+		CF_REST(s[3], w3 >> 20); CF_REST(q33, w3 & 0xFFFFFu);
+		CF_REST(q03, tw[6]); CF_REST(q13, tw[8]); CF_REST(q23, tw[9]);
+	} else {
+		o.s[3] = 0; o.q33 = 0; o.q03 = 0; o.q13 = 0; o.q23 = 0;
+	}
+#undef CF_REST
+	return o;
+}
+
+// Partition score of the two-phase search (oracle: subset_residual): the scatter of the
+// subset that no line through its mean can capture, (trace(C) - a'Ca)/n, with a = the
+// power-iterated principal axis.  Same statistics and axis arithmetic as fit_lane; mo: the subset's moments.
+// A4 = false: the block is opaque (the alpha plane is masked to zero), so every term that
+// carries the fourth channel is an exact zero and is left out -- same result, bit for bit.
+template <bool A4>
+__device__ __forceinline__ float subset_residual(const Moments& mo, uint32_t mask, float& along)
+{
+	const uint32_t n = (uint32_t)__builtin_popcount(mask);
+	const uint32_t s[4] = {mo.s[0], mo.s[1], mo.s[2], mo.s[3]};
+	const uint32_t q00 = mo.q00, q01 = mo.q01, q02 = mo.q02, q03 = mo.q03, q11 = mo.q11, q12 = mo.q12, q13 = mo.q13,
+		q22 = mo.q22, q23 = mo.q23, q33 = mo.q33;
 	const float C00 = (float)(int)(__umul24(n, q00) - __umul24(s[0], s[0])), C01 = (float)(int)(__umul24(n, q01) - __umul24(s[0], s[1]));
 	const float C02 = (float)(int)(__umul24(n, q02) - __umul24(s[0], s[2])), C03 = (float)(int)(__umul24(n, q03) - __umul24(s[0], s[3]));
 	const float C11 = (float)(int)(__umul24(n, q11) - __umul24(s[1], s[1])), C12 = (float)(int)(__umul24(n, q12) - __umul24(s[1], s[2]));
@@ -1008,6 +1088,22 @@ __device__ __forceinline__ float subset_residual(const Tex& tx, uint32_t mask, f
 	return res;
 }
 
+// The (error, id) key of a candidate, ordered like the pair.  Unit weights: a block's error is at most
+// 16 * 4 * 255^2 < 2^22 and ids are below 384 < 2^9, so error << 9 | id is one word and its group minimum a 32-bit
+// DPP reduction; a column that holds no candidate (error 0xFFFFFFFF) gets 0xFFFFFFFE, below `taken` and above every
+// candidate.  The perceptual metric's weighted errors do not fit: 64 bits.
+template <bool UNITW> struct CandKey;
+template <> struct CandKey<true> {
+	typedef uint32_t T;
+	static __device__ __forceinline__ T make(uint32_t err, uint32_t id) { return err == 0xFFFFFFFFu ? 0xFFFFFFFEu : (err << 9) | id; }
+	static __device__ __forceinline__ T group_min(T k, bool pair, uint32_t h) { return cf_group_min_u32(k, pair, h); }
+};
+template <> struct CandKey<false> {
+	typedef unsigned long long T;
+	static __device__ __forceinline__ T make(uint32_t err, uint32_t id) { return ((unsigned long long)err << 32) | id; }
+	static __device__ __forceinline__ T group_min(T k, bool pair, uint32_t h) { return cf_group_min_u64(k, pair, h); }
+};
+
 // Geometry of fit kf of candidate id (oracle: fit_geometry): mode, partition / rotation / index selector,
 // the channels and precisions the fit codes, its index width and its texels.
 struct FitGeo {
@@ -1052,10 +1148,7 @@ __device__ __forceinline__ FitGeo fit_geo(uint32_t id, uint32_t kf)
 			g.mask = kf ? p2 : (~p2 & 0xFFFFu);
 		} else if (g.ns == 3u) {
 			const uint32_t p3 = k_part3[g.part];
-			g.mask = 0;
-#pragma unroll
-			for (int i = 0; i < 16; ++i)
-				g.mask |= (((p3 >> (2*i)) & 3u) == kf ? 1u : 0u) << i;
+			g.mask = part3_mask(p3, kf);
 		}
 	}
 	return g;
@@ -1088,7 +1181,7 @@ __device__ __forceinline__ void column_put_fit(uint32_t* wc, const FitGeo& g, ui
 // Encode one block with the whole wavefront.  tp: the block's 16 texels in LDS
 // (colour mask already applied), identical for every lane.
 template <bool UNITW, bool WIDE>
-__device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint32_t* plan, const uint32_t* yccp, uint32_t b,
+__device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint32_t* plan, const uint32_t* yccp, const uint32_t* mom, uint32_t b,
 	bool pair, uint32_t* cbase, uint32_t* gbase, const cf_kparams& kp)
 {
 	uint32_t lane;
@@ -1178,16 +1271,16 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			if (sst && koff == 0u) {
 				// ---- the `ntop` best candidates of each group in (error, id) order (oracle: top[]) ----
 				{
-					unsigned long long kk = ((unsigned long long)L_CSLOT[18*CF_WG_THREADS] << 32) | L_CSLOT[19*CF_WG_THREADS];
+					typename CandKey<UNITW>::T kk = CandKey<UNITW>::make(L_CSLOT[18*CF_WG_THREADS], L_CSLOT[19*CF_WG_THREADS]);
 					uint32_t wls = 0, wls2 = 0;          // byte k & 3 of word k >> 2: lane whose column holds the k-th best candidate
 					for (uint32_t k = 0; k < ntop; ++k) {
-						const unsigned long long km = cf_group_min_u64(kk, pair, L_H);
+						const typename CandKey<UNITW>::T km = CandKey<UNITW>::group_min(kk, pair, L_H);
 						const unsigned long long bal = __ballot(kk == km);
 						const uint32_t gmask = pair ? (L_H ? (uint32_t)(bal >> 32) : (uint32_t)bal) : 0u;
 						const uint32_t wl = pair ? L_HBASE + (uint32_t)__ffs((int)gmask) - 1u
 							: (uint32_t)__ffsll((long long)bal) - 1u;
 						if (k < 4u) wls |= wl << (8u*k); else wls2 |= wl << (8u*(k - 4u));
-						kk = lane == wl ? ~0ull : kk;
+						kk = lane == wl ? ~(typename CandKey<UNITW>::T)0 : kk;   // taken
 					}
 					L_CSLOT[20*CF_WG_THREADS] = wls;     // every lane keeps its group's list in its own column
 					L_CSLOT[21*CF_WG_THREADS] = wls2;
@@ -1233,19 +1326,32 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				for (uint32_t pi = 0; pi < npi; ++pi) {
 					const uint32_t part = pair ? L_HL + 32u*pi : lane;
 					const uint32_t p2 = k_part2[part], p3 = k_part3[part];
-					float sc = 0.0f, sl = 0.0f;
-					for (uint32_t sb = 0; sb < ns; ++sb) {
-						uint32_t mask;
-						if (st == 0u)
-							mask = sb ? p2 : (~p2 & 0xFFFFu);
-						else {
-							mask = 0;
-#pragma unroll
-							for (int i = 0; i < 16; ++i)
-								mask |= (((p3 >> (2*i)) & 3u) == sb ? 1u : 0u) << i;
+					// one pass over the rows sums subset 1 (and 2); subset 0 is the block's table entry minus them
+					const uint32_t m0 = st == 0u ? (~p2 & 0xFFFFu) : part3_mask(p3, 0u);
+					const uint32_t m1 = st == 0u ? p2 : part3_mask(p3, 1u), m2 = st == 0u ? 0u : part3_mask(p3, 2u);
+					Moments ma, mb;
+					if (any_alpha) {
+						if (st == 0u) moments_rows<true, false>(txp, m1, m2, ma, mb); else moments_rows<true, true>(txp, m1, m2, ma, mb);
+					} else {
+						if (st == 0u) moments_rows<false, false>(txp, m1, m2, ma, mb); else moments_rows<false, true>(txp, m1, m2, ma, mb);
+					}
+					// subsets 0, 1 (, 2) in the oracle's order of summation
+					float sc = 0.0f, sl = 0.0f, al;
+					{
+						const uint32_t* tw = mom + (txp.boff >> 4)*CF_BC7_MOM_WORDS;
+						if (any_alpha) {
+							const Moments m0s = st == 0u ? moments_rest<true, false>(tw, ma, mb) : moments_rest<true, true>(tw, ma, mb);
+							sc = sc + subset_residual<true>(m0s, m0, al);
+						} else {
+							const Moments m0s = st == 0u ? moments_rest<false, false>(tw, ma, mb) : moments_rest<false, true>(tw, ma, mb);
+							sc = sc + subset_residual<false>(m0s, m0, al);
 						}
-						float al;
-						sc = sc + (any_alpha ? subset_residual<true>(txp, mask, al) : subset_residual<false>(txp, mask, al));
+						sl = sl + al;
+					}
+					sc = sc + (any_alpha ? subset_residual<true>(ma, m1, al) : subset_residual<false>(ma, m1, al));
+					sl = sl + al;
+					if (st != 0u) {
+						sc = sc + (any_alpha ? subset_residual<true>(mb, m2, al) : subset_residual<false>(mb, m2, al));
 						sl = sl + al;
 					}
 					if (pi == 0u) { sc0 = sc; sl0 = sl; } else { sc1 = sc; sl1 = sl; }
@@ -1349,16 +1455,16 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				const uint32_t sp2 = k_part2[mypart], sp3 = k_part3[mypart];
 				if (st == 0u)
 					mask = sub ? sp2 : (~sp2 & 0xFFFFu);
-				else {
-					mask = 0;
-#pragma unroll
-					for (int i = 0; i < 16; ++i)
-						mask |= (((sp3 >> (2*i)) & 3u) == sub ? 1u : 0u) << i;
-				}
+				else
+					mask = part3_mask(sp3, sub);
 				active = true;
 			}
 			if (CF_BC7_ABLATE & 1) active = active && (m6 || plane);
 			if (CF_BC7_ABLATE & 2) active = active && !plane;
+#if CF_BC7_DIAG
+			const bool nopb = __ballot(active && pbk != 0u) == 0ull;   // (a ballot of the whole wave: outside the counter's lane test)
+			CF_DIAG_COUNT(CF_DIAG_STARTS_NOPB, sst && nopb);
+#endif
 			uint32_t wl[4] = {wt[0], wt[1], wt[2], wt[3]};
 			if (!UNITW && rot) {
 				const uint32_t t3 = wl[3];
@@ -1543,8 +1649,8 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			}
 			if (kk == ntop && !fp) {
 				// the leader after the candidates' own rounds
-				const unsigned long long key = ((unsigned long long)L_CSLOT[18*CF_WG_THREADS] << 32) | L_CSLOT[19*CF_WG_THREADS];
-				const unsigned long long kmin = cf_group_min_u64(key, pair, L_H);
+				const typename CandKey<UNITW>::T key = CandKey<UNITW>::make(L_CSLOT[18*CF_WG_THREADS], L_CSLOT[19*CF_WG_THREADS]);
+				const typename CandKey<UNITW>::T kmin = CandKey<UNITW>::group_min(key, pair, L_H);
 				const unsigned long long bal = __ballot(key == kmin);
 				const uint32_t gmask = pair ? (L_H ? (uint32_t)(bal >> 32) : (uint32_t)bal) : 0u;
 				wl = pair ? L_HBASE + (uint32_t)__ffs((int)gmask) - 1u : (uint32_t)__ffsll((long long)bal) - 1u;
@@ -1560,9 +1666,15 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			const Tex tx = make_tex(tile, plan, yccp, B_OFF, g.rot, g.chm);
 			const uint32_t yw[2] = {(g.chm & 7u) ? ywrg : 0u,
 				((g.chm & 7u) ? (ywba & 0xFFFFu) : 0u) | ((g.chm & 8u) ? (ywba & 0xFFFF0000u) : 0u)};
-			// sum over the fit's texels of sum_c p_c^2 (the constant part of its error)
+			// sum over the fit's texels of sum_c p_c^2 (the constant part of its error): word 11 of the fit-geometry cache
+			// when every active lane of the wave finds its fit's column there (the starts trip's test), a row loop otherwise
 			uint32_t pp_sum = 0;
-			if (UNITW) {
+			const uint32_t gsrc = geo_src(id, kf, wl, lay32);
+			const bool ghit = gbase[gsrc + 12*CF_WG_THREADS] == geo_tag(id, kf) && (!lay32 || ((gsrc ^ wl) & 32u) == 0u);
+			const bool pphit = __ballot(act && !ghit) == 0ull;
+			if (pphit)
+				pp_sum = gbase[gsrc + 11*CF_WG_THREADS];
+			else if (UNITW) {
 #pragma unroll 1
 				for (uint32_t r = 0; r < 4u; ++r) {
 					uint32_t P[4];
@@ -1578,6 +1690,11 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			const bool narrow = __ballot(act && (g.m6 || g.ib > 2u)) == 0ull;
 			CF_DIAG_COUNT(CF_DIAG_PERTURB, !(CF_BC7_ABLATE & 32) && (kk == ntop ? uber2 : uber) != 0u);
 			CF_DIAG_COUNT(CF_DIAG_PERTURB_NARROW, !(CF_BC7_ABLATE & 32) && (kk == ntop ? uber2 : uber) != 0u && narrow);
+#if CF_BC7_DIAG
+			const bool nopb = __ballot(act && g.pbk != 0u) == 0ull;   // (a ballot of the whole wave: outside the counter's lane test)
+			CF_DIAG_COUNT(CF_DIAG_PERTURB_NOPB, !(CF_BC7_ABLATE & 32) && (kk == ntop ? uber2 : uber) != 0u && nopb);
+#endif
+			CF_DIAG_COUNT(CF_DIAG_PERTURB_PPHIT, !(CF_BC7_ABLATE & 32) && (kk == ntop ? uber2 : uber) != 0u && pphit);
 			const uint32_t S = g.pbk ? 1u : 0u;
 			const uint32_t fq0 = g.planes45 ? (g.sca ? 4u : 0u) : 2u*kf, fq1 = fq0 + 1u;   // column words of the fit's fields
 #pragma unroll 1
@@ -1706,6 +1823,7 @@ cfhip_bc7_encode_kernel(cf_kparams kp)
 	__shared__ __attribute__((aligned(16))) uint32_t tile[CF_BLOCKS_PER_WG*16];
 	__shared__ __attribute__((aligned(16))) uint32_t plan[CF_BLOCKS_PER_WG*16];
 	__shared__ uint4 outb[CF_BLOCKS_PER_WG];
+	__shared__ uint32_t mom[CF_BLOCKS_PER_WG*CF_BC7_MOM_WORDS];
 	__shared__ __attribute__((aligned(16))) uint32_t yccp[UNITW ? 4 : CF_BLOCKS_PER_WG*32];
 	uint32_t gx_, gy_;
 	cf_resolve(kp, gx_, gy_);
@@ -1729,6 +1847,8 @@ cfhip_bc7_encode_kernel(cf_kparams kp)
 			(((row.z >> (8u*c)) & 255u) << 16) | (((row.w >> (8u*c)) & 255u) << 24);
 	}
 	__syncthreads();
+	block_moments_put(plan, mom, threadIdx.x);
+	__syncthreads();
 
 	// wave index as a scalar (the loop counter, block index and pair flag then live in SGPRs), lane id
 	// from mbcnt where it is needed: nothing derived from threadIdx stays in a VGPR across the phases
@@ -1742,7 +1862,7 @@ cfhip_bc7_encode_kernel(cf_kparams kp)
 			!(CF_BC7_ABLATE & 4);
 		// opaque copy: keeps the (many) lane-role values of encode_blocks from being hoisted
 		// out of this loop and held in registers across all phases
-		const uint4 blk = encode_blocks<UNITW, WIDE>(tile, plan, yccp, b, pair, cands + wave*64u, geoc + wave*64u, kp);
+		const uint4 blk = encode_blocks<UNITW, WIDE>(tile, plan, yccp, mom, b, pair, cands + wave*64u, geoc + wave*64u, kp);
 		uint32_t lo;
 		asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lo));
 		if (pair) {
@@ -1789,7 +1909,7 @@ extern "C" hipError_t cfhip_launch_bc7(const cf_kparams* kp, int pixel_type, int
 }
 
 #if CF_BC7_DIAG
-// copy the diagnostic counters to out[0 .. 4] and zero them
+// copy the diagnostic counters to out[0 .. CF_DIAG_N - 1] and zero them
 extern "C" hipError_t cfhip_bc7_diag(unsigned long long* out)
 {
 	hipError_t e = hipMemcpyFromSymbol(out, HIP_SYMBOL(cf_bc7_diag), sizeof(cf_bc7_diag));
