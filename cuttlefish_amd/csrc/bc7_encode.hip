@@ -155,6 +155,15 @@ __device__ __forceinline__ uint32_t bc7_weight(uint32_t ib, uint32_t k)
 	return __umul24(k*64u + (d >> 1), mg) >> 16;
 }
 
+// 1/n of a subset of n = 1..16 texels: the correctly rounded quotients as literals, the same floats as the
+// division gives (which the compiler expands to the full IEEE sequence, ~10 instructions, for a per-lane n).
+// Entry 0 keeps the division's result for a lane that carries no subset.
+__device__ const float k_inv_n[17] = {
+	__builtin_huge_valf(), 1.0f/1.0f, 1.0f/2.0f, 1.0f/3.0f, 1.0f/4.0f, 1.0f/5.0f, 1.0f/6.0f, 1.0f/7.0f, 1.0f/8.0f,
+	1.0f/9.0f, 1.0f/10.0f, 1.0f/11.0f, 1.0f/12.0f, 1.0f/13.0f, 1.0f/14.0f, 1.0f/15.0f, 1.0f/16.0f
+};
+__device__ __forceinline__ float inv_n(uint32_t n) { return k_inv_n[n < 16u ? n : 16u]; }
+
 // (2^t - 1)/255 for a per-lane t: a select chain on literals instead of a table load
 // (a divergent index would make it a vector memory load on the critical path).
 __device__ __forceinline__ float sc_of(uint32_t t)
@@ -248,7 +257,7 @@ struct Tex {
 	__device__ __forceinline__ const uint32_t* tp() const { return tile_ + boff; }
 	__device__ __forceinline__ const uint32_t* pl() const { return plan_ + boff; }
 	__device__ __forceinline__ const uint32_t* yc() const { return yccp_ + 2u*boff; }
-	uint32_t sel;      // v_perm_b32 selector of the rotation
+	uint32_t sel;      // v_perm_b32 selector of the rotation; 0x0C (a zero byte) for a channel that is not coded
 	uint32_t rot;      // 0..3
 	uint32_t chmask;   // bit c: rotated channel c is coded by this fit
 	uint32_t vmask;    // byte mask of chmask
@@ -259,18 +268,19 @@ __device__ __forceinline__ Tex make_tex(const uint32_t* tile, const uint32_t* pl
 {
 	Tex t;
 	t.tile_ = tile; t.plan_ = plan; t.yccp_ = yccp; t.boff = boff; t.rot = rot; t.chmask = chmask;
-	t.sel = rot == 0u ? 0x03020100u : (rot == 1u ? 0x00020103u :
+	const uint32_t sel = rot == 0u ? 0x03020100u : (rot == 1u ? 0x00020103u :
 		(rot == 2u ? 0x01020300u : 0x02030100u));
 	t.vmask = ((chmask & 1u) ? 0xFFu : 0u) | ((chmask & 2u) ? 0xFF00u : 0u) |
 		((chmask & 4u) ? 0xFF0000u : 0u) | ((chmask & 8u) ? 0xFF000000u : 0u);
+	t.sel = (sel & t.vmask) | (0x0C0C0C0Cu & ~t.vmask);
 	return t;
 }
 
 template <bool ROT>
 __device__ __forceinline__ uint32_t texel(const Tex& t, uint32_t raw)
 {
-	const uint32_t p = ROT ? __builtin_amdgcn_perm(raw, raw, t.sel) : raw;
-	return p & t.vmask;
+	// rotated: the selector already zeroes the channels that are not coded
+	return ROT ? __builtin_amdgcn_perm(raw, raw, t.sel) : raw & t.vmask;
 }
 
 // The four channel planes of one texel row after rotation, non-coded channels zeroed.
@@ -380,7 +390,7 @@ struct LaneFit {
 template <bool UNITW, int NK = 8>
 __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bool m6,
 	uint32_t khalf, uint32_t ib, const uint32_t (&yw)[2], uint32_t pp_sum, bool want_lsq, uint32_t fe0, uint32_t fe1,
-	LaneFit& f, float (&nx0)[4], float (&nx1)[4], float (&hq)[3], bool& ok)
+	LaneFit& f, float (&nx0)[4], float (&nx1)[4], float (&hq)[3], bool& ok, uint32_t s01 = 0u, uint32_t s23 = 0u)   // s01, s23: want_lsq only
 {
 	const uint32_t nk = m6 ? 8u : (1u << ib), kbase = m6 ? 8u*khalf : 0u;
 	const uint32_t e00 = ub(fe0, 0), e01 = ub(fe0, 1), e02 = ub(fe0, 2), e03 = ub(fe0, 3);
@@ -424,56 +434,67 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 	uint32_t err = pp_sum;
 	uint32_t wp0 = 0, wp1 = 0, wp2 = 0, wp3 = 0;
 #pragma unroll 1
-	for (uint32_t r = 0; r < 4u; ++r) {
-		// unit weights: the row's packed RGBA texels; perceptual: its (Y | Cr, Cb | A) word pairs
-		uint32_t raw[4], rawh[4];
-		if (UNITW) {
-			const uint4 rw = *reinterpret_cast<const uint4*>(tx.tp() + 4u*r);
-			raw[0] = rw.x; raw[1] = rw.y; raw[2] = rw.z; raw[3] = rw.w;
-			rawh[0] = rawh[1] = rawh[2] = rawh[3] = 0u;
-		} else {
-			const uint4 ya = *reinterpret_cast<const uint4*>(tx.yc() + 8u*r);
-			const uint4 yb = *reinterpret_cast<const uint4*>(tx.yc() + 8u*r + 4u);
-			raw[0] = ya.x; raw[1] = ya.z; raw[2] = yb.x; raw[3] = yb.z;
-			rawh[0] = ya.y; rawh[1] = ya.w; rawh[2] = yb.y; rawh[3] = yb.w;
-		}
-		const uint32_t mrow = (mask >> (4u*r)) & 15u;
-		uint32_t wrow = 0;
+	for (uint32_t r2 = 0; r2 < 4u; r2 += 2u) {
+		// two rows per trip: the four weight words then rotate by two once per trip instead of by one per row
+		// (the loop-carried copies were six v_mov_b32 per row)
+		uint32_t wpair[2];
 #pragma unroll
-		for (int j = 0; j < 4; ++j) {
-			uint32_t rawj = raw[j];
-			// one texel at a time: interleaving the 32 dot products of a row for ILP costs
-			// ~20 registers, and the kernel is issue-bound, not latency-bound
-			asm volatile("" : "+v"(rawj), "+v"(wrow));
-			const uint32_t p = UNITW ? texel<true>(tx, rawj) : 0u;
-			uint32_t key;
-			{
-				int bestk = -0x7FFFFFFF;
-				const uint32_t prg = rawj, pba = rawh[j];
-#pragma unroll
-				for (int k = 0; k < NK; ++k) {
-					int dt;
-					if (UNITW)
-						dt = (int)__builtin_amdgcn_udot4(p, pal[k], 0u, false);
-					else
-						dt = (int)dot2_u16(pba, palh[k], dot2_u16(prg, pal[k], 0u));
-					const int v = (dt << 8) + base[k];
-					bestk = v > bestk ? v : bestk;
-				}
-				// mode 6: the other palette half lives in the neighbouring lane
-				const int other = (int)cf_xor1((uint32_t)bestk);
-				bestk = (m6 && other > bestk) ? other : bestk;
-				key = (uint32_t)(-bestk);   // 128 (sum w c^2 - 2 p.(w c)) + weight, two's complement
+		for (uint32_t h = 0; h < 2u; ++h) {
+			const uint32_t r = r2 + h;
+			// unit weights: the row's packed RGBA texels; perceptual: its (Y | Cr, Cb | A) word pairs
+			uint32_t raw[4], rawh[4];
+			if (UNITW) {
+				const uint4 rw = *reinterpret_cast<const uint4*>(tx.tp() + 4u*r);
+				raw[0] = rw.x; raw[1] = rw.y; raw[2] = rw.z; raw[3] = rw.w;
+				rawh[0] = rawh[1] = rawh[2] = rawh[3] = 0u;
+			} else {
+				const uint4 ya = *reinterpret_cast<const uint4*>(tx.yc() + 8u*r);
+				const uint4 yb = *reinterpret_cast<const uint4*>(tx.yc() + 8u*r + 4u);
+				raw[0] = ya.x; raw[1] = ya.z; raw[2] = yb.x; raw[3] = yb.z;
+				rawh[0] = ya.y; rawh[1] = ya.w; rawh[2] = yb.y; rawh[3] = yb.w;
 			}
-			key = ((mrow >> j) & 1u) ? key : 0u;
-			err += (uint32_t)((int)key >> 7);
-			wrow |= (key & 127u) << (8*j);
+			const uint32_t mrow = (mask >> (4u*r)) & 15u;
+			uint32_t wrow = 0;
+#pragma unroll
+			for (int j = 0; j < 4; ++j) {
+				uint32_t rawj = raw[j];
+				// one texel at a time: interleaving the 32 dot products of a row for ILP costs
+				// ~20 registers, and the kernel is issue-bound, not latency-bound
+				asm volatile("" : "+v"(rawj), "+v"(wrow));
+				const uint32_t p = UNITW ? texel<true>(tx, rawj) : 0u;
+				uint32_t key;
+				{
+					int bestk = -0x7FFFFFFF;
+					const uint32_t prg = rawj, pba = rawh[j];
+#pragma unroll
+					for (int k = 0; k < NK; ++k) {
+						int dt;
+						if (UNITW)
+							dt = (int)__builtin_amdgcn_udot4(p, pal[k], 0u, false);
+						else
+							dt = (int)dot2_u16(pba, palh[k], dot2_u16(prg, pal[k], 0u));
+						const int v = (dt << 8) + base[k];
+						bestk = v > bestk ? v : bestk;
+					}
+					// mode 6: the other palette half lives in the neighbouring lane (the 4-entry search is entered
+					// only when no active lane of the wave is a mode-6 lane: it has no exchange at all)
+					if (NK == 8) {
+						const int other = (int)cf_xor1((uint32_t)bestk);
+						bestk = (m6 && other > bestk) ? other : bestk;
+					}
+					key = (uint32_t)(-bestk);   // 128 (sum w c^2 - 2 p.(w c)) + weight, two's complement
+				}
+				key = ((mrow >> j) & 1u) ? key : 0u;
+				err += (uint32_t)((int)key >> 7);
+				wrow |= (key & 127u) << (8*j);
+			}
+			wpair[h] = wrow;
 		}
-		wp0 = wp1; wp1 = wp2; wp2 = wp3; wp3 = wrow;
+		wp0 = wp2; wp1 = wp3; wp2 = wpair[0]; wp3 = wpair[1];
 	}
 	f.err = err;
 	f.w[0] = wp0; f.w[1] = wp1; f.w[2] = wp2; f.w[3] = wp3;
-	// the refit sums in a loop of their own: their 12 accumulators and the planar rows are
+	// the refit sums in a loop of their own: their 6 accumulators and the planar rows are
 	// then not live across the texel search above (which holds the 16 palette registers)
 	uint32_t S = 0, A = 0, B = 0, C = 0, U[4] = {0, 0, 0, 0}, V[4] = {0, 0, 0, 0};
 	if (want_lsq) {   // uniform: the last round's refit would never be used
@@ -481,7 +502,6 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 		for (uint32_t r = 0; r < 4u; ++r) {
 			const uint32_t wrow = wp0;
 			wp0 = wp1; wp1 = wp2; wp2 = wp3; wp3 = wrow;   // rotates back to the start after 4 trips
-			const uint32_t iwrow = (0x40404040u - wrow) & bytemask4((mask >> (4u*r)) & 15u);
 			uint32_t P[4];
 			// (the block offset made opaque per trip: the row address is then formed here, with the array's base in
 			// the instruction's offset field, instead of being hoisted into a register that lives across the search)
@@ -489,15 +509,17 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 			asm volatile("" : "+v"(bo));
 			planes<true>(tx, *reinterpret_cast<const uint4*>(tx.plan_ + bo + 4u*r), P);
 			S = __builtin_amdgcn_udot4(wrow, 0x01010101u, S, false);
-			A = __builtin_amdgcn_udot4(iwrow, iwrow, A, false);
-			B = __builtin_amdgcn_udot4(iwrow, wrow, B, false);
 			C = __builtin_amdgcn_udot4(wrow, wrow, C, false);
 #pragma unroll
-			for (int c = 0; c < 4; ++c) {
-				U[c] = __builtin_amdgcn_udot4(iwrow, P[c], U[c], false);
+			for (int c = 0; c < 4; ++c)
 				V[c] = __builtin_amdgcn_udot4(wrow, P[c], V[c], false);
-			}
 		}
+		// the sums with iw = 64 - w (exact on the subset, where both are integers; w = 0 outside it) from the sums
+		// with w and the subset's channel sums s_c (s01, s23: 16-bit pairs)
+		A = 4096u*(uint32_t)__builtin_popcount(mask) - 128u*S + C;
+		B = 64u*S - C;
+		U[0] = 64u*(s01 & 0xFFFFu) - V[0]; U[1] = 64u*(s01 >> 16) - V[1];
+		U[2] = 64u*(s23 & 0xFFFFu) - V[2]; U[3] = 64u*(s23 >> 16) - V[3];
 	}
 	const int det = (int)__umul24((uint32_t)__builtin_popcount(mask), C) - (int)__umul24(S, S);
 	ok = det > 0;
@@ -614,7 +636,7 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 {
 	float axis[4], mean[4];
 	float tmin, tmax;
-	uint32_t lo, hi, pp_sum;
+	uint32_t lo, hi, pp_sum, s01, s23;
 	if (gmode == 2u) {
 		const uint32_t* gc = gbase + gsrc;
 #pragma unroll
@@ -627,6 +649,11 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 		const uint32_t lh = gc[10*CF_WG_THREADS];
 		lo = lh & 255u; hi = lh >> 8;
 		pp_sum = gc[11*CF_WG_THREADS];
+		// the subset's channel sums back from the means: mean = s/n to within 2^-22 of s <= 4080, so the
+		// product rounds to s exactly
+		const float fn = (float)__builtin_popcount(mask);
+		s01 = (uint32_t)(mean[0]*fn + 0.5f) | ((uint32_t)(mean[1]*fn + 0.5f) << 16);
+		s23 = (uint32_t)(mean[2]*fn + 0.5f) | ((uint32_t)(mean[3]*fn + 0.5f) << 16);
 	} else {
 		// A: statistics of the subset + extremes of the (rotated) alpha channel
 		const uint32_t n = (uint32_t)__builtin_popcount(mask);
@@ -697,7 +724,7 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 		}
 
 		// B: extremes of the projection on the axis
-		const float in = 1.0f/(float)n;
+		const float in = inv_n(n);
 #pragma unroll
 		for (int c = 0; c < 4; ++c)
 			mean[c] = (float)s[c]*in;
@@ -722,6 +749,8 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 		// sum over the subset of sum_c p_c^2 (channels that are not coded have p = 0), or of the
 		// weighted squares on the perceptual axes
 		pp_sum = UNITW ? q00 + q11 + q22 + q33 : ycc_pp_sum(tx, mask, yw);
+		s01 = s[0] | (s[1] << 16);
+		s23 = s[2] | (s[3] << 16);
 		if (gmode == 1u) {
 			uint32_t lane;
 			CF_FRESH_LANE(lane);
@@ -771,7 +800,7 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 	best.q0 = q.q0; best.q1 = q.q1; best.pb = q.pb;
 	bool live;
 	float hq[3];
-	assign_lsq_lane<UNITW, NK>(tx, mask, m6, khalf, G_IB, yw, pp_sum, iters > 0u, q.e0, q.e1, best, x0, x1, hq, live);
+	assign_lsq_lane<UNITW, NK>(tx, mask, m6, khalf, G_IB, yw, pp_sum, iters > 0u, q.e0, q.e1, best, x0, x1, hq, live, s01, s23);
 	for (uint32_t r = 0; r < iters; ++r) {
 		LaneFit cur;
 		bool ok;
@@ -788,7 +817,7 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 		}
 		if (!(CF_BC7_ABLATE & 8)) refit_window(x0, x1, hq, G_CB, G_AB, G_PBK, q);
 		cur.q0 = q.q0; cur.q1 = q.q1; cur.pb = q.pb;
-		assign_lsq_lane<UNITW, NK>(tx, mask, m6, khalf, G_IB, yw, pp_sum, r + 1u < iters, q.e0, q.e1, cur, x0, x1, hq, ok);
+		assign_lsq_lane<UNITW, NK>(tx, mask, m6, khalf, G_IB, yw, pp_sum, r + 1u < iters, q.e0, q.e1, cur, x0, x1, hq, ok, s01, s23);
 		const bool better = live && cur.err < best.err;
 		if (better)
 			best = cur;
@@ -1079,9 +1108,10 @@ __device__ __forceinline__ float subset_residual(const Moments& mo, uint32_t mas
 		den = fmaf(v2, v2, den);
 		if (A4) den = fmaf(v3, v3, den);
 		const float lam = num*(1.0f/den);
-		res = (tr - lam)*(1.0f/(float)n);
+		const float in = inv_n(n);
+		res = (tr - lam)*in;
 		res = res > 0.0f ? res : 0.0f;
-		const float al = lam*(1.0f/(float)n);
+		const float al = lam*in;
 		along = al > 0.0f ? al : 0.0f;
 	}
 #undef CF_MATVEC
