@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import enum
 import os
-from typing import Iterable, Optional, Sequence
+from typing import Iterable, List, Optional, Sequence
 
 import numpy as np
 
@@ -190,7 +190,8 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_pvrtc_query", "cfhip_pvrtc_encode", "cfhip_pvrtc_encode_device", "cfhip_pvrtc_decode",
            "cfhip_pvrtc_decode_device", "cfhip_pvrtc_decode_sse", "cfhip_pvrtc_decode_sse_device",
            "cfhip_std_unpack", "cfhip_std_unpack_device", "cfhip_std_compare", "cfhip_std_compare_device",
-           "cfhip_decode_batch", "cfhip_decode_batch_device", "cfhip_decode_out_supported"]
+           "cfhip_decode_batch", "cfhip_decode_batch_device", "cfhip_decode_out_supported",
+           "cfhip_compare_batch", "cfhip_compare_batch_device"]
 
 
 class Layout(enum.IntEnum):
@@ -286,6 +287,13 @@ class DecodeSurface(ctypes.Structure):
     _fields_ = [("blocks", ctypes.c_void_p), ("blocks_bytes", ctypes.c_size_t), ("width", ctypes.c_uint32),
                 ("height", ctypes.c_uint32), ("out", ctypes.c_void_p), ("out_pitch_bytes", ctypes.c_size_t),
                 ("out_capacity", ctypes.c_size_t)]
+
+
+class CompareSurface(ctypes.Structure):
+    """struct cfhip_compare_surface"""
+    _fields_ = [("blocks", ctypes.c_void_p), ("blocks_bytes", ctypes.c_size_t), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32), ("ref", ctypes.c_void_p), ("ref_pitch_bytes", ctypes.c_size_t),
+                ("block_errors", ctypes.c_void_p), ("block_errors_capacity", ctypes.c_size_t)]
 
 
 DECODE_NATIVE = -1              # CFHIP_DECODE_NATIVE
@@ -475,6 +483,13 @@ def load_library(path: Optional[str] = None):
                                             ctypes.POINTER(DecodeSurface), ctypes.c_size_t, ctypes.c_void_p,
                                             ctypes.c_void_p]
     L.cfhip_decode_batch_device.restype = ctypes.c_int
+    L.cfhip_compare_batch.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(CompareSurface),
+                                      ctypes.c_size_t, ctypes.c_int, u8p, ctypes.c_uint, ctypes.c_void_p]
+    L.cfhip_compare_batch.restype = ctypes.c_int
+    L.cfhip_compare_batch_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.POINTER(CompareSurface), ctypes.c_size_t, ctypes.c_int, u8p,
+                                             ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_compare_batch_device.restype = ctypes.c_int
     L.cfhip_decode_out_supported.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.cfhip_decode_out_supported.restype = ctypes.c_int
     _lib = L
@@ -922,6 +937,64 @@ class Context:
             int(ref_pixel_type), ref_pitch_bytes, self._mask(mask), COMPARE_SSIM if ssim else 0,
             ctypes.c_void_p(int(result)), ctypes.c_void_p(int(block_errors)) if block_errors else None,
             block_errors_capacity, ctypes.c_void_p(stream) if stream else None))
+
+    def compare_batch(self, payloads: Sequence[np.ndarray], refs: Sequence[np.ndarray], fmt, typ=Type.UNorm,
+                      mask=None, ssim: bool = False, block_map: bool = False) -> List[Comparison]:
+        """compare() for every surface of a call at once (cfhip_compare_batch): payloads[i] against refs[i], an
+        (h, w, 4) array whose size is the surface's.  All refs must share one dtype (uint8, float16 or float32).
+        The launch count does not depend on the number of surfaces, and each Comparison holds the bits compare()
+        returns for its surface alone.  Payloads (and references) that lie one after the other in memory travel
+        as one upload."""
+        n = len(payloads)
+        if len(refs) != n:
+            raise ValueError("payloads and refs must list the same surfaces")
+        layout, _ = decoded_layout(fmt, typ)
+        if n == 0:
+            return []
+        refs = [np.asarray(r) for r in refs]
+        if len({r.dtype for r in refs}) != 1:
+            raise ValueError("all references of one compare_batch call must share one dtype")
+        pix = {np.dtype(np.uint8): PixelType.RGBA8, np.dtype(np.float32): PixelType.RGBA32F,
+               np.dtype(np.float16): PixelType.RGBA16F}.get(refs[0].dtype)
+        if pix is None or any(r.ndim != 3 or r.shape[2] != 4 for r in refs):
+            raise ValueError("references must be (h, w, 4) uint8, float16 or float32")
+        refs = [np.ascontiguousarray(r) for r in refs]
+        parts = [np.ascontiguousarray(p, dtype=np.uint8).reshape(-1) for p in payloads]
+        surf = (CompareSurface*n)()
+        maps = []
+        if block_map:
+            bw, bh, _ = query(fmt, typ)
+        for i, (p, r) in enumerate(zip(parts, refs)):
+            h, w = r.shape[:2]
+            surf[i].blocks, surf[i].blocks_bytes = p.ctypes.data, p.nbytes
+            surf[i].width, surf[i].height = w, h
+            surf[i].ref, surf[i].ref_pitch_bytes = r.ctypes.data, r.strides[0]
+            if block_map:
+                maps.append(np.zeros(((h + bh - 1) // bh, (w + bw - 1) // bw), np.float32))
+                surf[i].block_errors, surf[i].block_errors_capacity = maps[i].ctypes.data, maps[i].size
+        res = (CompareResult*n)()
+        self._check(self._lib.cfhip_compare_batch(self._h, int(fmt), int(typ), surf, n, int(pix), self._mask(mask),
+                                                  COMPARE_SSIM if ssim else 0, ctypes.addressof(res)))
+        return [Comparison(res[i], layout, maps[i] if block_map else None) for i in range(n)]
+
+    def compare_batch_device(self, surfaces: Sequence[dict], fmt, typ, ref_pixel_type, results: int, mask=None,
+                             ssim: bool = False, stream: int = 0):
+        """Device path of compare_batch.  surfaces: dicts with blocks, ref (device pointers as ints), width, height,
+        ref_pitch_bytes and, optionally, block_errors (device pointer to floats) with block_errors_capacity.
+        results: device pointer to len(surfaces) cfhip_compare_result.  stream 0 = the context's stream (the call
+        then synchronises)."""
+        n = len(surfaces)
+        surf = (CompareSurface*max(n, 1))()
+        for i, s in enumerate(surfaces):
+            surf[i].blocks, surf[i].ref = int(s["blocks"]) or None, int(s["ref"]) or None
+            surf[i].width, surf[i].height = s["width"], s["height"]
+            surf[i].ref_pitch_bytes = s["ref_pitch_bytes"]
+            if s.get("block_errors"):
+                surf[i].block_errors = int(s["block_errors"])
+                surf[i].block_errors_capacity = int(s.get("block_errors_capacity", 0))
+        self._check(self._lib.cfhip_compare_batch_device(
+            self._h, int(fmt), int(typ), surf, n, int(ref_pixel_type), self._mask(mask), COMPARE_SSIM if ssim else 0,
+            ctypes.c_void_p(int(results)) if results else None, ctypes.c_void_p(stream) if stream else None))
 
     def unpack(self, payload: np.ndarray, fmt, typ, width: int, height: int) -> np.ndarray:
         """The payload of a standard (uncompressed) format, formats 1..28, back to texels on the GPU ->

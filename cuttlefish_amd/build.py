@@ -125,6 +125,9 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  # the quality metrics (csrc/compare.hip)
                  "cfhip_compare_block_kernel", "cfhip_compare_astc_kernel", "cfhip_compare_ssim_kernel",
                  "cfhip_compare_final_kernel",
+                 # their batched forms (csrc/compare.hip, csrc/compare_batch.h)
+                 "cfhip_compare_batch_block_kernel", "cfhip_compare_batch_astc_kernel",
+                 "cfhip_compare_batch_ssim_kernel", "cfhip_compare_batch_final_kernel",
                  # PVRTC1 4 bpp (csrc/pvrtc.hip): the encoder's passes and the decoder
                  "cfhip_pvrtc_load_kernel", "cfhip_pvrtc_init_kernel", "cfhip_pvrtc_mod_kernel",
                  "cfhip_pvrtc_refine_kernel", "cfhip_pvrtc_pack_kernel", "cfhip_pvrtc_decode_kernel",

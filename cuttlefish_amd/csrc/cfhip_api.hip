@@ -8,6 +8,7 @@
 #include "cf_device.h"
 #include "astc_tables.h"
 #include "pvrtc_surf.h"
+#include "compare_batch.h"
 #include "decode_batch.h"
 #include "../../include/cuttlefish_hip.h"
 
@@ -2597,6 +2598,309 @@ int cfhip_compare_device(cfhip_ctx* ctx, int format, int type, const void* block
 		return rc;
 	rc = compare_enqueue(ctx, format, type, c, blocks, ref, ref_pixel_type, ref_pitch_bytes, width, height,
 		static_cast<uint8_t*>(ctx->d_out), result_device, block_errors_device, lease.stream);
+	if (rc != CFHIP_OK)
+		return rc;
+	return lease.done(!stream_);
+}
+
+// ---- batched compare (csrc/compare.hip: the cfhip_compare_batch_* kernels; csrc/compare_batch.h) -------------
+// What one batched compare runs and where its device scratch lies: the decoded surfaces of the SSIM pass (each
+// 16-byte aligned, only those with a valid window), then the Pass A partials of every workgroup of the call, then
+// the SSIM partials of every tile.  The scratch grows with the sum over the surfaces and is not capped.
+struct CompareBatchPlan {
+	int layout, texel_bytes, ref_bytes, bw, bh, bb;
+	unsigned cmask;
+	bool hdr, ssim;                           // ssim: the SSIM pass runs (some surface has a valid window)
+	std::vector<cmp_batch_entry> entries;     // blocks / ref / block_errors still the caller's pointers
+	std::vector<size_t> payload;              // payload bytes
+	uint32_t total_wg, total_tiles;
+	size_t pa_off, pb_off, scratch_bytes;
+};
+
+// Every check of a batched compare, made before the context is touched (so that they need no device): the pair,
+// the table and every surface, each by compare_check, the rules of the per-surface entries.  ctx may be NULL here;
+// the caller rejects that afterwards.
+static int compare_batch_check(cfhip_ctx* ctx, const char* what, int format, int type, const cfhip_compare_surface* s,
+	size_t n, int ref_pixel_type, const uint8_t* mask, unsigned flags, const void* results, bool host,
+	CompareBatchPlan* p)
+{
+	if (!decoded_layout(format, type, &p->layout, &p->texel_bytes))
+		return fail(ctx, CFHIP_E_UNSUPPORTED, "%s: (format %d, type %d) has no decoded layout", what, format, type);
+	p->total_wg = p->total_tiles = 0;
+	if (!n)
+		return CFHIP_OK;
+	if (!s || !results)
+		return fail(ctx, CFHIP_E_INVALID, "%s: surfaces or results is NULL", what);
+	if (n > 0xFFFFFFu)
+		return fail(ctx, CFHIP_E_INVALID, "%s: too many surfaces (%zu)", what, n);
+	if ((uintptr_t)results % 8u != 0)
+		return fail(ctx, CFHIP_E_INVALID, "%s: results must be 8-byte aligned", what);
+	const bool astc = format >= CFHIP_FORMAT_ASTC_4x4;
+	p->entries.resize(n);
+	p->payload.resize(n);
+	uint64_t wg = 0, tiles = 0;
+	size_t dec = 0;
+	for (size_t i = 0; i < n; ++i) {
+		char who[64];
+		snprintf(who, sizeof(who), "%s: surface %zu", what, i);
+		CompareGeom c;
+		const int rc = compare_check(ctx, who, format, type, s[i].blocks, s[i].width, s[i].height, s[i].ref,
+			ref_pixel_type, s[i].ref_pitch_bytes, mask, flags, results, s[i].block_errors, s[i].block_errors_capacity, &c);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (host && s[i].blocks_bytes < c.g.payload_bytes)
+			return fail(ctx, CFHIP_E_INVALID, "%s: blocks_bytes %zu < %zu for %ux%u", who, s[i].blocks_bytes,
+				c.g.payload_bytes, s[i].width, s[i].height);
+		if (!host) {
+			// the kernels read reference texels with one aligned load each and store floats to the maps
+			const size_t rb = (size_t)c.ref_bytes;
+			if ((uintptr_t)s[i].ref % rb != 0 || s[i].ref_pitch_bytes % rb != 0)
+				return fail(ctx, CFHIP_E_INVALID, "%s: reference and its pitch must be %zu-byte aligned", who, rb);
+			if ((uintptr_t)s[i].block_errors % 4u != 0)
+				return fail(ctx, CFHIP_E_INVALID, "%s: misaligned block_errors", who);
+		}
+		if (!i) {
+			p->ref_bytes = c.ref_bytes; p->cmask = c.cmask; p->hdr = c.hdr;
+			p->bw = c.g.bw; p->bh = c.g.bh; p->bb = c.g.bb;
+		}
+		cmp_batch_entry& e = p->entries[i];
+		e.blocks = static_cast<const uint8_t*>(s[i].blocks);
+		e.ref = static_cast<const uint8_t*>(s[i].ref);
+		e.ref_pitch = s[i].ref_pitch_bytes;
+		e.block_errors = s[i].block_errors;
+		e.width = s[i].width; e.height = s[i].height; e.bx = c.g.bx; e.by = c.g.by;
+		e.wgx = astc ? (e.bx + 63u)/64u : 0;
+		e.wg_begin = (uint32_t)wg;
+		e.na = (uint32_t)c.na;
+		e.tile_begin = (uint32_t)tiles;
+		e.tiles_x = c.ssim ? (e.width - 10u + 15u)/16u : 0;
+		e.nb = (uint32_t)c.nb;
+		e.windows = c.windows;
+		e.dec_off = dec;
+		e.blk_vec = 0;
+		p->payload[i] = c.g.payload_bytes;
+		wg += c.na;
+		tiles += c.nb;
+		if (c.ssim)
+			dec = align16(dec + (size_t)e.width*e.height*(size_t)p->texel_bytes);
+		if (c.na > 0x7FFFFFFFull || wg > 0x7FFFFFFFull || tiles > 0x7FFFFFFFull)
+			return fail(ctx, CFHIP_E_INVALID, "%s: the surfaces are too large for one launch", what);
+	}
+	p->total_wg = (uint32_t)wg;
+	p->total_tiles = (uint32_t)tiles;
+	p->ssim = tiles > 0;
+	p->pa_off = align16(dec);
+	p->pb_off = p->pa_off + (size_t)wg*16u*sizeof(double);
+	p->scratch_bytes = p->pb_off + (size_t)tiles*4u*sizeof(double);
+	return CFHIP_OK;
+}
+
+// the surface tables into staging and the two (without an SSIM pass) or four launches of the call, each timed as
+// every encode launch is; the entries hold device pointers by now
+static int compare_batch_launch(cfhip_ctx* ctx, StagingLease& lease, int format, int type, int ref_pixel_type,
+	CompareBatchPlan& p, uint8_t* scratch, cfhip_compare_result* results)
+{
+	const hipStream_t stream = lease.stream;
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = format >= CFHIP_FORMAT_ASTC_4x4 ? "cfhip_compare_batch_astc_kernel" : "cfhip_compare_batch_block_kernel";
+	const size_t n = p.entries.size();
+	// the compare table, then the decode table of the surfaces the SSIM pass covers (the decoders' workgroup shapes
+	// are Pass A's: 256 blocks, or a run of 64 ASTC blocks)
+	std::vector<cfdec_batch_entry> dec;
+	uint32_t dec_wg = 0;
+	for (cmp_batch_entry& e : p.entries) {
+		e.blk_vec = ((uintptr_t)e.blocks % (uintptr_t)p.bb == 0) ? 1 : 0;
+		if (!e.nb)
+			continue;
+		cfdec_batch_entry d;
+		d.blocks = e.blocks;
+		d.out = scratch + e.dec_off;
+		d.out_pitch = (unsigned long long)e.width*(unsigned)p.texel_bytes;
+		d.width = e.width; d.height = e.height; d.bx = e.bx; d.by = e.by;
+		d.wg_begin = dec_wg;
+		d.wgx = e.wgx;
+		d.out_vec = ((uintptr_t)d.out % 16 == 0 && d.out_pitch % 16 == 0) ? 1 : 0;
+		d.blk_vec = e.blk_vec;
+		dec_wg += e.na;
+		dec.push_back(d);
+	}
+	const size_t cmp_bytes = n*sizeof(cmp_batch_entry), dec_off = align16(cmp_bytes);
+	std::vector<uint8_t> tables(dec_off + dec.size()*sizeof(cfdec_batch_entry));
+	memcpy(tables.data(), p.entries.data(), cmp_bytes);
+	if (!dec.empty())
+		memcpy(tables.data() + dec_off, dec.data(), dec.size()*sizeof(cfdec_batch_entry));
+	int rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tables.size());
+	if (rc != CFHIP_OK)
+		return rc;
+	// pageable source: the runtime stages the copy before returning, so the tables may die
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, tables.data(), tables.size(), hipMemcpyHostToDevice, stream));
+	const cmp_batch_entry* d_cmp = static_cast<const cmp_batch_entry*>(ctx->d_batch);
+	const cfdec_batch_entry* d_dec = reinterpret_cast<const cfdec_batch_entry*>(static_cast<uint8_t*>(ctx->d_batch) + dec_off);
+	double* pa = reinterpret_cast<double*>(scratch + p.pa_off);
+	double* pb = p.ssim ? reinterpret_cast<double*>(scratch + p.pb_off) : nullptr;
+	const int steps = p.ssim ? 4 : 2;
+	for (int step = 0; step < steps; ++step) {
+		hipEvent_t a, b;
+		rc = next_event_pair(ctx, &a, &b);
+		if (rc != CFHIP_OK)
+			return rc;
+		HIP_TRY(ctx, hipEventRecord(a, stream));
+		hipError_t e;
+		if (step == 0) {
+			e = cfhip_launch_compare_batch(format, type, d_cmp, (uint32_t)n, p.total_wg, p.bw, p.bh, ref_pixel_type,
+				p.cmask, pa, stream);
+		} else if (step == steps - 1) {
+			e = cfhip_launch_compare_batch_final(d_cmp, (uint32_t)n, pa, pb, p.cmask, p.hdr ? 1 : 0, results, stream);
+		} else if (step == 1) {
+			e = cfhip_launch_decode_batch(format, type, CFDEC_OUT_NATIVE, d_dec, (uint32_t)dec.size(), dec_wg, p.bw, p.bh,
+				nullptr, stream);
+		} else {
+			const int l = p.layout;
+			const double range = (l == CFHIP_LAYOUT_R8_SNORM || l == CFHIP_LAYOUT_RG8_SNORM ||
+				l == CFHIP_LAYOUT_R16_SNORM || l == CFHIP_LAYOUT_RG16_SNORM) ? 2.0 : 1.0;
+			e = cfhip_launch_ssim_batch(d_cmp, (uint32_t)n, p.total_tiles, scratch, l, ref_pixel_type, p.cmask,
+				ssim_taps(), range, pb, stream);
+		}
+		if (e != hipSuccess)
+			return fail(ctx, CFHIP_E_DEVICE, "compare_batch launch: %s", hipGetErrorString(e));
+		HIP_TRY(ctx, hipEventRecord(b, stream));
+	}
+	return CFHIP_OK;
+}
+
+int cfhip_compare_batch(cfhip_ctx* ctx, int format, int type, const cfhip_compare_surface* surfaces, size_t n,
+	int ref_pixel_type, const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* results)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	CompareBatchPlan p;
+	int rc = compare_batch_check(ctx, "compare_batch", format, type, surfaces, n, ref_pixel_type, mask_rgba, flags,
+		results, true, &p);
+	if (rc != CFHIP_OK || !n)
+		return rc;
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, ctx->stream);
+	const hipStream_t stream = lease.stream;
+	// d_src: the payloads, a run of surfaces whose blocks are consecutive in host memory as one copy.  d_out: the
+	// references, tightly pitched and packed without gaps (a texel keeps its alignment: every surface is a whole
+	// number of texels), so that tight references that are consecutive in host memory are one copy too; then the
+	// scratch, the n results and the error maps.
+	struct Run { size_t first, dev, bytes; };
+	std::vector<Run> up, refs;
+	std::vector<size_t> src_off(n), ref_off(n), map_off(n);
+	size_t so = 0, ro = 0;
+	bool prev_tight = false;
+	const uint8_t* prev_end = nullptr;
+	for (size_t i = 0; i < n; ++i) {
+		const uint8_t* b = static_cast<const uint8_t*>(surfaces[i].blocks);
+		if (i && b == static_cast<const uint8_t*>(surfaces[i - 1].blocks) + p.payload[i - 1]) {
+			src_off[i] = src_off[i - 1] + p.payload[i - 1];
+			up.back().bytes += p.payload[i];
+		} else {
+			so = (so + 255) & ~(size_t)255;
+			src_off[i] = so;
+			up.push_back({i, so, p.payload[i]});
+		}
+		so = src_off[i] + p.payload[i];
+		const size_t row = (size_t)surfaces[i].width*(size_t)p.ref_bytes, bytes = row*surfaces[i].height;
+		const bool tight = surfaces[i].ref_pitch_bytes == row;
+		ref_off[i] = ro;
+		if (tight && prev_tight && static_cast<const uint8_t*>(surfaces[i].ref) == prev_end)
+			refs.back().bytes += bytes;
+		else
+			refs.push_back({i, ro, bytes});
+		prev_tight = tight;
+		prev_end = static_cast<const uint8_t*>(surfaces[i].ref) + bytes;
+		ro += bytes;
+	}
+	const size_t scr_off = align16(ro), res_off = align16(scr_off + p.scratch_bytes);
+	size_t mo = align16(res_off + n*sizeof(cfhip_compare_result));
+	for (size_t i = 0; i < n; ++i) {
+		map_off[i] = mo;
+		if (surfaces[i].block_errors)
+			mo = align16(mo + (size_t)p.entries[i].bx*p.entries[i].by*sizeof(float));
+	}
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, so);
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, mo);
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* d_src = static_cast<uint8_t*>(ctx->d_src);
+	uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
+	for (const Run& r : up)
+		HIP_TRY(ctx, hipMemcpyAsync(d_src + r.dev, surfaces[r.first].blocks, r.bytes, hipMemcpyHostToDevice, stream));
+	for (const Run& r : refs) {
+		const cfhip_compare_surface& s = surfaces[r.first];
+		const size_t row = (size_t)s.width*(size_t)p.ref_bytes;
+		if (s.ref_pitch_bytes == row)
+			HIP_TRY(ctx, hipMemcpyAsync(d + r.dev, s.ref, r.bytes, hipMemcpyHostToDevice, stream));
+		else
+			HIP_TRY(ctx, hipMemcpy2DAsync(d + r.dev, row, s.ref, s.ref_pitch_bytes, row, s.height, hipMemcpyHostToDevice,
+				stream));
+	}
+	for (size_t i = 0; i < n; ++i) {
+		cmp_batch_entry& e = p.entries[i];
+		e.blocks = d_src + src_off[i];
+		e.ref = d + ref_off[i];
+		e.ref_pitch = (unsigned long long)e.width*(unsigned)p.ref_bytes;
+		e.block_errors = surfaces[i].block_errors ? reinterpret_cast<float*>(d + map_off[i]) : nullptr;
+	}
+	cfhip_compare_result* d_res = reinterpret_cast<cfhip_compare_result*>(d + res_off);
+	rc = compare_batch_launch(ctx, lease, format, type, ref_pixel_type, p, d + scr_off, d_res);
+	if (rc != CFHIP_OK)
+		return rc;
+	std::vector<cfhip_compare_result> res(n);
+	HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_res, n*sizeof(cfhip_compare_result), hipMemcpyDeviceToHost, stream));
+	for (size_t i = 0; i < n; ++i)
+		if (surfaces[i].block_errors)
+			HIP_TRY(ctx, hipMemcpyAsync(surfaces[i].block_errors, d + map_off[i],
+				(size_t)p.entries[i].bx*p.entries[i].by*sizeof(float), hipMemcpyDeviceToHost, stream));
+	rc = lease.done(true);
+	if (rc != CFHIP_OK)
+		return rc;
+	for (size_t i = 0; i < n; ++i)
+		results[i] = res[i];
+	return CFHIP_OK;
+}
+
+int cfhip_compare_batch_device(cfhip_ctx* ctx, int format, int type, const cfhip_compare_surface* surfaces, size_t n,
+	int ref_pixel_type, const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* results_device, void* stream_)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	CompareBatchPlan p;
+	int rc = compare_batch_check(ctx, "compare_batch_device", format, type, surfaces, n, ref_pixel_type, mask_rgba,
+		flags, results_device, false, &p);
+	if (rc != CFHIP_OK || !n)
+		return rc;
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	// the partials (and the SSIM pass's decoded surfaces) live in d_out, the tables in d_batch: the lease orders them
+	// across streams
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, p.scratch_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
+	rc = compare_batch_launch(ctx, lease, format, type, ref_pixel_type, p, static_cast<uint8_t*>(ctx->d_out),
+		results_device);
 	if (rc != CFHIP_OK)
 		return rc;
 	return lease.done(!stream_);

@@ -15,10 +15,15 @@
 //     LDS and runs the separable 11-tap Gaussian in FP64.
 //   * Every workgroup writes its FP64 partials; one single-workgroup kernel reduces them in a fixed order and
 //     writes the cfhip_compare_result.  No float atomics: two identical calls return identical bits.
+//   * Batched launches (compare_batch.h): the per-workgroup work of every pass is a
+//     __device__ function of its argument struct; the cfhip_compare_batch_* kernels resolve their surface from the
+//     call's table and run the same function with the same workgroup shape, so surface i of a batch returns the
+//     bits the per-surface kernels return for it alone.
 // No kernel here may use scratch, spill a vector register or use AGPRs (cuttlefish_amd/build.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "compare_batch.h"
 #include "decode_blocks.h"
 #include "std_unpack.h"
 #include "../../include/cuttlefish_hip.h"
@@ -156,7 +161,7 @@ __device__ __forceinline__ double wave_max_d(double v)
 	return v;
 }
 
-// the workgroup's partial: per-wave butterflies, then the waves in order by thread 0
+// the workgroup's partial (out: its kPartA doubles): per-wave butterflies, then the waves in order by thread 0
 template <int NT>
 __device__ __forceinline__ void write_partial(const Acc& s, double err, double* out)
 {
@@ -178,16 +183,17 @@ __device__ __forceinline__ void write_partial(const Acc& s, double err, double* 
 #pragma unroll
 		for (int k = 1; k < NW; ++k)
 			v = (q >= 8 && q < 12) ? fmax(v, wp[k][q]) : v + wp[k][q];
-		out[(uint64_t)blockIdx.x*kPartA + q] = v;
+		out[q] = v;
 	}
 }
 
+// Pass A of workgroup `wg` of surface a (lane-per-block formats); out: the workgroup's partial
 template <int FMT, int TYPE>
-__global__ __launch_bounds__(kCmpWg) void cfhip_compare_block_kernel(cmp_args a)
+__device__ __forceinline__ void compare_block_wg(const cmp_args& a, uint32_t wg, double* out)
 {
 	constexpr int TB = texel_bytes<FMT, TYPE>();
 	constexpr int BB = (FMT == 29 || FMT == 30 || FMT == 33 || (FMT >= 37 && FMT <= 39) || FMT == 41) ? 8 : 16;
-	const uint64_t b = (uint64_t)blockIdx.x*kCmpWg + threadIdx.x;
+	const uint64_t b = (uint64_t)wg*kCmpWg + threadIdx.x;
 	const uint64_t nblk = (uint64_t)a.bx*a.by;
 	Acc s;
 	acc_init(s);
@@ -211,7 +217,48 @@ __global__ __launch_bounds__(kCmpWg) void cfhip_compare_block_kernel(cmp_args a)
 		if (a.block_errors)
 			a.block_errors[b] = (float)blk;
 	}
-	write_partial<kCmpWg>(s, err, a.partials);
+	write_partial<kCmpWg>(s, err, out);
+}
+
+template <int FMT, int TYPE>
+__global__ __launch_bounds__(kCmpWg) void cfhip_compare_block_kernel(cmp_args a)
+{
+	compare_block_wg<FMT, TYPE>(a, blockIdx.x, a.partials + (uint64_t)blockIdx.x*kPartA);
+}
+
+// ---------------------------------------------------------------- batched launches (compare_batch.h)
+struct cmp_batch {
+	const cmp_batch_entry* table;
+	uint32_t n;
+	uint32_t ref_pix, cmask;
+	double* partials;             // Pass A: kPartA doubles per workgroup of the call
+};
+
+// entry of Pass A workgroup wg: a wave-uniform binary search over wg_begin (cf_resolve's, cf_device.h)
+__device__ __forceinline__ uint32_t batch_surface(const cmp_batch& t, uint32_t wg, cmp_args& a, uint32_t& wgx)
+{
+	uint32_t lo = 0, hi = t.n - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi + 1u) >> 1;
+		if (t.table[mid].wg_begin <= wg) lo = mid; else hi = mid - 1u;
+	}
+	const cmp_batch_entry e = t.table[lo];
+	a.blocks = e.blocks; a.ref = e.ref; a.ref_pitch = e.ref_pitch;
+	a.width = e.width; a.height = e.height; a.bx = e.bx; a.by = e.by;
+	a.ref_pix = t.ref_pix; a.cmask = t.cmask; a.blk_vec = e.blk_vec;
+	a.block_errors = e.block_errors;
+	a.partials = t.partials;
+	wgx = e.wgx;
+	return wg - e.wg_begin;
+}
+
+template <int FMT, int TYPE>
+__global__ __launch_bounds__(kCmpWg) void cfhip_compare_batch_block_kernel(cmp_batch t)
+{
+	cmp_args a;
+	uint32_t wgx;
+	const uint32_t local = batch_surface(t, blockIdx.x, a, wgx);
+	compare_block_wg<FMT, TYPE>(a, local, t.partials + (uint64_t)blockIdx.x*kPartA);
 }
 
 struct std_cmp_args {
@@ -253,15 +300,16 @@ __global__ __launch_bounds__(kCmpWg) void cfhip_std_compare_kernel(std_cmp_args 
 		else
 			acc_texel<false>(s, d, r, a.cmask);
 	}
-	write_partial<kCmpWg>(s, 0.0, a.partials);
+	write_partial<kCmpWg>(s, 0.0, a.partials + (uint64_t)blockIdx.x*kPartA);
 }
 
 // one wave = a run of kCmpRun blocks of one block row; grid (ceil(bx / kCmpRun), by)
+// (run: the run's index in its block row; out: the workgroup's partial)
 template <bool HDR>
-__global__ __launch_bounds__(kCmpRun) void cfhip_compare_astc_kernel(cmp_args a, int bw, int bh)
+__device__ __forceinline__ void compare_astc_wg(const cmp_args& a, int bw, int bh, uint32_t run, uint32_t by, double* out)
 {
 	__shared__ AstcRec rec[kCmpRun];
-	const uint32_t run0 = blockIdx.x*kCmpRun, by = blockIdx.y;
+	const uint32_t run0 = run*kCmpRun;
 	const uint32_t nb = a.bx - run0 < (uint32_t)kCmpRun ? a.bx - run0 : (uint32_t)kCmpRun;
 	const uint64_t b = (uint64_t)by*a.bx + run0 + threadIdx.x;
 	if (threadIdx.x < nb) {
@@ -299,7 +347,7 @@ __global__ __launch_bounds__(kCmpRun) void cfhip_compare_astc_kernel(cmp_args a,
 		if (a.block_errors)
 			a.block_errors[b] = (float)blk;
 	}
-	// one wave per workgroup: the partial's index is the workgroup's linear index
+	// one wave per workgroup
 	Acc t = s;
 	double e = wave_sum_d(err);
 #pragma unroll
@@ -308,7 +356,6 @@ __global__ __launch_bounds__(kCmpRun) void cfhip_compare_astc_kernel(cmp_args a,
 		t.lsse[c] = wave_sum_d(s.lsse[c]);
 		t.rmax[c] = wave_max_d(s.rmax[c]);
 	}
-	double* out = a.partials + ((uint64_t)blockIdx.y*gridDim.x + blockIdx.x)*kPartA;
 	if (threadIdx.x < 13) {
 		const int q = threadIdx.x;
 		double v = e;
@@ -320,6 +367,23 @@ __global__ __launch_bounds__(kCmpRun) void cfhip_compare_astc_kernel(cmp_args a,
 		}
 		out[q] = v;
 	}
+}
+
+// the partial's index is the workgroup's linear index
+template <bool HDR>
+__global__ __launch_bounds__(kCmpRun) void cfhip_compare_astc_kernel(cmp_args a, int bw, int bh)
+{
+	compare_astc_wg<HDR>(a, bw, bh, blockIdx.x, blockIdx.y, a.partials + ((uint64_t)blockIdx.y*gridDim.x + blockIdx.x)*kPartA);
+}
+
+template <bool HDR>
+__global__ __launch_bounds__(kCmpRun) void cfhip_compare_batch_astc_kernel(cmp_batch t, int bw, int bh)
+{
+	cmp_args a;
+	uint32_t wgx;
+	const uint32_t local = batch_surface(t, blockIdx.x, a, wgx);
+	const uint32_t by = local/wgx;
+	compare_astc_wg<HDR>(a, bw, bh, local - by*wgx, by, t.partials + (uint64_t)blockIdx.x*kPartA);
 }
 
 // ---------------------------------------------------------------- Pass B: SSIM on the decoded surface
@@ -365,12 +429,13 @@ __device__ __forceinline__ double ref_channel(const ssim_args& a, uint32_t x, ui
 	return half_to_double(reinterpret_cast<const uint16_t*>(row)[(uint64_t)x*4u + c]);
 }
 
-// one workgroup per kTile x kTile window centres; grid (tiles_x, tiles_y); centre (5 + tx*16 + lx, 5 + ty*16 + ly)
-__global__ __launch_bounds__(kCmpWg) void cfhip_compare_ssim_kernel(ssim_args a)
+// one workgroup per kTile x kTile window centres: tile (tx, ty), centre (5 + tx*16 + lx, 5 + ty*16 + ly); out: the
+// tile's 4 doubles
+__device__ __forceinline__ void ssim_tile(const ssim_args& a, uint32_t tx, uint32_t ty, double* out)
 {
 	__shared__ double xs[kReg][kReg], ys[kReg][kReg];
 	__shared__ double hs[5][kReg][kTile];
-	const uint32_t ox = blockIdx.x*kTile, oy = blockIdx.y*kTile;
+	const uint32_t ox = tx*kTile, oy = ty*kTile;
 	const int lx = threadIdx.x % kTile, ly = threadIdx.x / kTile;
 	const uint32_t cx = ox + kHalo + lx, cy = oy + kHalo + ly;
 	const bool valid = cx + kHalo < a.width && cy + kHalo < a.height;
@@ -425,8 +490,50 @@ __global__ __launch_bounds__(kCmpWg) void cfhip_compare_ssim_kernel(ssim_args a)
 	if (threadIdx.x < 4) {
 		const int c = threadIdx.x;
 		const double v = ((wp[0][c] + wp[1][c]) + wp[2][c]) + wp[3][c];
-		a.partials[((uint64_t)blockIdx.y*a.tiles_x + blockIdx.x)*4u + c] = v;
+		out[c] = v;
 	}
+}
+
+// grid (tiles_x, tiles_y)
+__global__ __launch_bounds__(kCmpWg) void cfhip_compare_ssim_kernel(ssim_args a)
+{
+	ssim_tile(a, blockIdx.x, blockIdx.y, a.partials + ((uint64_t)blockIdx.y*a.tiles_x + blockIdx.x)*4u);
+}
+
+struct ssim_batch {
+	const cmp_batch_entry* table;
+	uint32_t n;
+	uint32_t layout, ref_pix, cmask, texel_bytes;
+	const uint8_t* scratch;       // the decoded surfaces, entry i at dec_off
+	float w[11];
+	double c1, c2;
+	double* partials;             // 4 doubles per tile of the call
+};
+
+// 1-D grid over the tiles of the call; surfaces without a valid window own no tile and are never found
+__global__ __launch_bounds__(kCmpWg) void cfhip_compare_batch_ssim_kernel(ssim_batch t)
+{
+	const uint32_t tile = blockIdx.x;
+	uint32_t lo = 0, hi = t.n - 1u;
+	while (lo < hi) {
+		const uint32_t mid = (lo + hi + 1u) >> 1;
+		if (t.table[mid].tile_begin <= tile) lo = mid; else hi = mid - 1u;
+	}
+	const cmp_batch_entry e = t.table[lo];
+	ssim_args a;
+	a.dec = t.scratch + e.dec_off;
+	a.ref = e.ref;
+	a.dec_pitch = (unsigned long long)e.width*t.texel_bytes;
+	a.ref_pitch = e.ref_pitch;
+	a.width = e.width; a.height = e.height; a.tiles_x = e.tiles_x;
+	a.layout = t.layout; a.ref_pix = t.ref_pix; a.cmask = t.cmask;
+#pragma unroll
+	for (int k = 0; k < 11; ++k)
+		a.w[k] = t.w[k];
+	a.c1 = t.c1; a.c2 = t.c2;
+	a.partials = t.partials;
+	const uint32_t local = tile - e.tile_begin, ty = local/e.tiles_x;
+	ssim_tile(a, local - ty*e.tiles_x, ty, t.partials + (uint64_t)tile*4u);
 }
 
 // ---------------------------------------------------------------- the final reduction
@@ -441,7 +548,7 @@ struct final_args {
 };
 
 // one workgroup: thread t folds rows t, t + 256, ... in order, then column q is folded over the threads in order
-__global__ __launch_bounds__(kCmpWg) void cfhip_compare_final_kernel(final_args f)
+__device__ __forceinline__ void final_fold(const final_args& f)
 {
 	constexpr int NQ = 17;        // 13 Pass A fields, 4 SSIM sums
 	__shared__ double part[NQ][kCmpWg];
@@ -489,6 +596,35 @@ __global__ __launch_bounds__(kCmpWg) void cfhip_compare_final_kernel(final_args 
 		r->channels = f.cmask;
 		r->ssim_windows = f.pb ? f.windows : 0u;
 	}
+}
+
+__global__ __launch_bounds__(kCmpWg) void cfhip_compare_final_kernel(final_args f)
+{
+	final_fold(f);
+}
+
+struct final_batch {
+	const cmp_batch_entry* table;
+	const double* pa;             // Pass A partials of the call
+	const double* pb;             // SSIM partials of the call (null: no SSIM pass)
+	uint32_t cmask, hdr;
+	cfhip_compare_result* results;
+};
+
+// workgroup i folds surface i's partials, in cfhip_compare_final_kernel's order
+__global__ __launch_bounds__(kCmpWg) void cfhip_compare_batch_final_kernel(final_batch t)
+{
+	const cmp_batch_entry e = t.table[blockIdx.x];
+	final_args f;
+	f.pa = t.pa + (uint64_t)e.wg_begin*kPartA;
+	// a surface without tiles folds as a per-surface call without the SSIM flag does: NaN, 0 windows
+	f.pb = (t.pb && e.nb) ? t.pb + (uint64_t)e.tile_begin*4u : nullptr;
+	f.na = e.na; f.nb = e.nb;
+	f.texels = (uint64_t)e.width*e.height;
+	f.cmask = t.cmask; f.hdr = t.hdr;
+	f.windows = e.windows;
+	f.result = t.results + blockIdx.x;
+	final_fold(f);
 }
 
 template <int FMT, int TYPE>
@@ -638,5 +774,100 @@ extern "C" hipError_t cfhip_launch_compare_final(const double* pa, uint64_t na, 
 	f.windows = windows;
 	f.result = result;
 	hipLaunchKernelGGL(cfhip_compare_final_kernel, dim3(1), dim3(kCmpWg), 0, stream, f);
+	return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- batched launchers (compare_batch.h)
+namespace {
+
+template <int FMT, int TYPE>
+hipError_t launch_batch_a(const cmp_batch& t, uint32_t total_wg, hipStream_t stream)
+{
+	hipLaunchKernelGGL((cfhip_compare_batch_block_kernel<FMT, TYPE>), dim3(total_wg), dim3(kCmpWg), 0, stream, t);
+	return hipGetLastError();
+}
+
+} // namespace
+
+extern "C" hipError_t cfhip_launch_compare_batch(int format, int type, const cmp_batch_entry* table, uint32_t n,
+	uint32_t total_wg, int bw, int bh, int ref_pix, unsigned cmask, double* partials, hipStream_t stream)
+{
+	if (!n || !total_wg)
+		return hipErrorInvalidValue;
+	cmp_batch t;
+	t.table = table;
+	t.n = n;
+	t.ref_pix = (uint32_t)ref_pix;
+	t.cmask = cmask;
+	t.partials = partials;
+	if (format >= 43 && format <= 56) {
+		const dim3 grid(total_wg), block(kCmpRun);
+		if (type == 4)
+			hipLaunchKernelGGL(cfhip_compare_batch_astc_kernel<true>, grid, block, 0, stream, t, bw, bh);
+		else
+			hipLaunchKernelGGL(cfhip_compare_batch_astc_kernel<false>, grid, block, 0, stream, t, bw, bh);
+		return hipGetLastError();
+	}
+	const bool sn = type == 1;
+	switch (format) {
+		case 29: return launch_batch_a<29, 0>(t, total_wg, stream);
+		case 30: return launch_batch_a<30, 0>(t, total_wg, stream);
+		case 31: return launch_batch_a<31, 0>(t, total_wg, stream);
+		case 32: return launch_batch_a<32, 0>(t, total_wg, stream);
+		case 33: return sn ? launch_batch_a<33, 1>(t, total_wg, stream) : launch_batch_a<33, 0>(t, total_wg, stream);
+		case 34: return sn ? launch_batch_a<34, 1>(t, total_wg, stream) : launch_batch_a<34, 0>(t, total_wg, stream);
+		case 35: return type == 5 ? launch_batch_a<35, 5>(t, total_wg, stream) : launch_batch_a<35, 4>(t, total_wg, stream);
+		case 36: return launch_batch_a<36, 0>(t, total_wg, stream);
+		case 37: return launch_batch_a<37, 0>(t, total_wg, stream);
+		case 38: return launch_batch_a<38, 0>(t, total_wg, stream);
+		case 39: return launch_batch_a<39, 0>(t, total_wg, stream);
+		case 40: return launch_batch_a<40, 0>(t, total_wg, stream);
+		case 41: return sn ? launch_batch_a<41, 1>(t, total_wg, stream) : launch_batch_a<41, 0>(t, total_wg, stream);
+		case 42: return sn ? launch_batch_a<42, 1>(t, total_wg, stream) : launch_batch_a<42, 0>(t, total_wg, stream);
+		default: return hipErrorInvalidValue;
+	}
+}
+
+extern "C" hipError_t cfhip_launch_ssim_batch(const cmp_batch_entry* table, uint32_t n, uint32_t total_tiles,
+	const void* scratch, int layout, int ref_pix, unsigned cmask, const float* taps, double range, double* partials,
+	hipStream_t stream)
+{
+	if (!n || !total_tiles)
+		return hipErrorInvalidValue;
+	ssim_batch t;
+	t.table = table;
+	t.n = n;
+	t.layout = (uint32_t)layout;
+	t.ref_pix = (uint32_t)ref_pix;
+	t.cmask = cmask;
+	switch (layout) {
+		case CFHIP_LAYOUT_R8: case CFHIP_LAYOUT_R8_SNORM: t.texel_bytes = 1; break;
+		case CFHIP_LAYOUT_RG8: case CFHIP_LAYOUT_RG8_SNORM: case CFHIP_LAYOUT_R16: case CFHIP_LAYOUT_R16_SNORM:
+			t.texel_bytes = 2; break;
+		case CFHIP_LAYOUT_RGBA8: case CFHIP_LAYOUT_RG16: case CFHIP_LAYOUT_RG16_SNORM: t.texel_bytes = 4; break;
+		default: return hipErrorInvalidValue;      // HDR layouts have no SSIM pass
+	}
+	t.scratch = static_cast<const uint8_t*>(scratch);
+	for (int k = 0; k < 11; ++k)
+		t.w[k] = taps[k];
+	t.c1 = (0.01*range)*(0.01*range);
+	t.c2 = (0.03*range)*(0.03*range);
+	t.partials = partials;
+	hipLaunchKernelGGL(cfhip_compare_batch_ssim_kernel, dim3(total_tiles), dim3(kCmpWg), 0, stream, t);
+	return hipGetLastError();
+}
+
+extern "C" hipError_t cfhip_launch_compare_batch_final(const cmp_batch_entry* table, uint32_t n, const double* pa,
+	const double* pb, unsigned cmask, int hdr, cfhip_compare_result* results, hipStream_t stream)
+{
+	if (!n)
+		return hipErrorInvalidValue;
+	final_batch t;
+	t.table = table;
+	t.pa = pa; t.pb = pb;
+	t.cmask = cmask;
+	t.hdr = (uint32_t)hdr;
+	t.results = results;
+	hipLaunchKernelGGL(cfhip_compare_batch_final_kernel, dim3(n), dim3(kCmpWg), 0, stream, t);
 	return hipGetLastError();
 }

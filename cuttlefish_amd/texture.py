@@ -701,22 +701,157 @@ class Texture:
         # Their texels are floats, so an 8-bit source is measured as the RGBAF image the converter read
         # (float(v/255), Image.cpp:293-296): a lossless conversion then compares equal, PSNR inf.
         std = int(self._format) < int(Format.BC1_RGB)
-        measure = ctx.compare_std if std else ctx.compare
-        results = []
-        for m, level in enumerate(self._textures):
-            for d, dep in enumerate(level):
-                for f, payload in enumerate(dep):
-                    ref = source._images[m][d][f]
-                    if std and ref.dtype == np.uint8:
-                        ref = (ref.astype(np.float64)/255.0).astype(np.float32)
-                    results.append(measure(payload, ref, self._format, self._type, mask=mask, ssim=ssim))
+        flat = self._flat()
+        refs = [source._images[m][d][f] for m, d, f, _ in flat]
+        if std:
+            results = []
+            for (_, _, _, payload), ref in zip(flat, refs):
+                if ref.dtype == np.uint8:
+                    ref = (ref.astype(np.float64)/255.0).astype(np.float32)
+                results.append(ctx.compare_std(payload, ref, self._format, self._type, mask=mask, ssim=ssim))
+        else:
+            # one batched call per reference dtype (cfhip_compare_batch measures one pixel type per call)
+            results = [None]*len(flat)
+            for dt in sorted({r.dtype for r in refs}, key=str):
+                idx = [i for i, r in enumerate(refs) if r.dtype == dt]
+                got = ctx.compare_batch([flat[i][3] for i in idx], [refs[i] for i in idx], self._format, self._type,
+                                        mask=mask, ssim=ssim)
+                for i, r in zip(idx, got):
+                    results[i] = r
+        return results, self._pooled(results)
+
+    @staticmethod
+    def _pooled(results) -> float:
+        """the pooled PSNR of compare(): over every surface and compared channel"""
         sse = sum(sum(r.sse[c] for c in r.compared()) for r in results)
         n = sum(r.texels * len(r.compared()) for r in results)
         if n == 0:
             raise ValueError("compare: no channel compared")
         peak = max(r.peak() for r in results)
-        pooled = float("inf") if sse == 0.0 else 10.0 * float(np.log10(peak * peak * n / sse))
-        return results, pooled
+        return float("inf") if sse == 0.0 else 10.0 * float(np.log10(peak * peak * n / sse))
+
+    @staticmethod
+    def _pooled_pvrtc(results, texels: int, chans) -> float:
+        sse = sum(r[c] for r in results for c in chans)
+        return float("inf") if sse == 0 else 10.0 * float(np.log10(255.0 * 255.0 * texels * len(chans) / sse))
+
+    def _measure_device(self, ctx, format, type, items, mask, ssim):
+        """Quality of device payloads against device texels, without a copy through the host.  items: one
+        (payload tensor, texel tensor, PixelType, width, height) per surface, the texels tightly pitched.  Block
+        formats: one Context.compare_batch_device call per pixel type; standard formats and PVRTC: their
+        per-surface device entries (an RGBA8 reference of a standard format is first widened on the device to the
+        RGBAF image the converter read, as compare() widens it on the host; a float reference of PVRTC is
+        quantised on the host as compare() quantises it: PVRTC's fused SSE reads RGBA8 alone).  Returns what
+        compare() returns per surface."""
+        import ctypes
+        import torch
+        dev = "cuda:%d" % self._device_id
+        tb = {api.PixelType.RGBA8: 4, api.PixelType.RGBA32F: 16, api.PixelType.RGBA16F: 8}
+        n = len(items)
+        if format in api.PVRTC_FORMATS:
+            sums = torch.empty((n, 4), dtype=torch.int64, device=dev)
+            host = {}
+            for i, (pay, tex, pt, w, h) in enumerate(items):
+                if pt == api.PixelType.RGBA8:
+                    ctx.decode_pvrtc_sse_device(pay.data_ptr(), format, w, h, tex.data_ptr(), w*4,
+                                                sums[i].data_ptr(), type)
+                else:
+                    dt = np.float32 if pt == api.PixelType.RGBA32F else np.float16
+                    ref = _rgba8_of(tex.cpu().numpy().view(dt).reshape(h, w, 4))
+                    host[i] = ctx.decode_pvrtc_sse(pay.cpu().numpy(), ref, format, type)
+            got = sums.cpu().numpy().astype(np.uint64)
+            return [host[i] if i in host else [int(v) for v in got[i]] for i in range(n)]
+        size = ctypes.sizeof(api.CompareResult)
+        raw = np.empty((n, size), np.uint8)
+        if int(format) < int(Format.BC1_RGB):
+            res = torch.empty(n*size, dtype=torch.uint8, device=dev)
+            for i, (pay, tex, pt, w, h) in enumerate(items):
+                ref, rp = tex, pt
+                if pt == api.PixelType.RGBA8:
+                    ref, rp = torch.empty((h, w, 4), dtype=torch.float32, device=dev), api.PixelType.RGBA32F
+                    ctx.image_ops_device(tex.data_ptr(), pt, w, h, w*4, api.make_image_ops(), ref.data_ptr(), w*16)
+                ctx.compare_std_device(pay.data_ptr(), format, type, w, h, ref.data_ptr(), rp, w*tb[rp],
+                                       res.data_ptr() + i*size, mask=mask, ssim=ssim)
+            raw[:] = res.cpu().numpy().reshape(n, size)
+            layout = api.Layout.RGBA32F
+        else:
+            for pt in sorted({int(it[2]) for it in items}):
+                idx = [i for i, it in enumerate(items) if int(it[2]) == pt]
+                res = torch.empty(len(idx)*size, dtype=torch.uint8, device=dev)
+                ctx.compare_batch_device([dict(blocks=items[i][0].data_ptr(), ref=items[i][1].data_ptr(),
+                                               width=items[i][3], height=items[i][4],
+                                               ref_pitch_bytes=items[i][3]*tb[api.PixelType(pt)]) for i in idx],
+                                         format, type, pt, res.data_ptr(), mask=mask, ssim=ssim)
+                raw[idx] = res.cpu().numpy().reshape(len(idx), size)
+            layout, _ = api.decoded_layout(format, type)
+        std = layout == api.Layout.RGBA32F
+        return [api.Comparison(api.CompareResult.from_buffer_copy(raw[i].tobytes()), layout, None,
+                               typ=type if std else None) for i in range(n)]
+
+    def convert_and_compare(self, format: Format, type: Type, quality: Quality = Quality.Normal,
+                            alpha_type: Alpha = Alpha.Standard,
+                            color_mask: Sequence[bool] = (True, True, True, True), ssim: bool = True):
+        """convert(), and the quality of the result against the images it was made from, in one visit to the
+        device: every image is uploaded once, in the pixel type convert() hands to the encoder, encoded from there
+        (Context.encode_device), the fresh payloads are measured against those same buffers, and only payloads and
+        results come back.  Returns (results, pooled) -- exactly what compare(source) returns afterwards for an
+        identical unconverted `source` -- or None wherever convert() returns False (the texture is then left
+        unconverted).  The end state is convert()'s: the same payload bytes, the images freed.
+        Block formats are measured by the batched entry (Context.compare_batch_device), standard formats and PVRTC
+        by their per-surface device entries with compare()'s restrictions: PVRTC has no SSIM, so ssim must be
+        False for it (ValueError, raised before any work).
+        There is no strip pipeline here: the whole texture -- images, payloads and the compare's scratch -- is
+        resident on the device during the call."""
+        import torch
+        if not self.images_complete() or not self.is_format_valid(format, type):
+            return None
+        format, type = Format(format), Type(type)
+        if self._color_space == ColorSpace.sRGB and not self.has_native_srgb(format, type):
+            return None
+        pvrtc = format in api.PVRTC_FORMATS
+        flat = [im for level in self._images for dep in level for im in dep]
+        if not (format == Format.BC6H or int(format) < int(Format.BC1_RGB)):
+            flat = [im.astype(np.float32) if im.dtype == np.float16 else im for im in flat]
+        if pvrtc:
+            if any(im.shape[0] & (im.shape[0] - 1) or im.shape[1] & (im.shape[1] - 1) for im in flat):
+                return None
+            if ssim:
+                raise ValueError("compare: PVRTC has no SSIM (pass ssim=False)")
+        mask = [bool(m) for m in color_mask]
+        if Alpha(alpha_type) == Alpha.None_ or not self.has_alpha(format):
+            mask[3] = False
+        if pvrtc and not any(mask):
+            raise ValueError("compare: no channel compared")
+        params = api.make_params(format, type, quality, alpha_type, color_mask, self._color_space)
+        ctx = self._context()
+        dev = "cuda:%d" % self._device_id
+        hosts = [np.ascontiguousarray(im) for im in flat]
+        texels = [torch.from_numpy(h).to(dev) for h in hosts]
+        size = api.pvrtc_payload_size if pvrtc else api.payload_size
+        try:
+            pays = [torch.empty(size(format, type, h.shape[1], h.shape[0]), dtype=torch.uint8, device=dev) for h in hosts]
+            surfaces = [dict(pixels=t.data_ptr(), pixel_type=int(api.pixel_type_of(h)), width=h.shape[1],
+                             height=h.shape[0], row_pitch_bytes=h.strides[0], out=p.data_ptr(), out_capacity=p.numel())
+                        for h, t, p in zip(hosts, texels, pays)]
+            # one call per pixel type, as transcode() encodes
+            for pt in sorted({s["pixel_type"] for s in surfaces}):
+                group = [s for s in surfaces if s["pixel_type"] == pt]
+                (ctx.encode_pvrtc_device if pvrtc else ctx.encode_device)(group, params)
+        except api.CfhipError as e:
+            if e.code == api.E_UNSUPPORTED:
+                return None
+            raise
+        items = [(p, t, api.pixel_type_of(h), h.shape[1], h.shape[0]) for h, t, p in zip(hosts, texels, pays)]
+        results = self._measure_device(ctx, format, type, items, mask, ssim)
+        it = iter([p.cpu().numpy() for p in pays])
+        self._textures = [[[next(it) for _ in dep] for dep in level] for level in self._images]
+        self._images = [[[None]*len(dep) for dep in level] for level in self._images]
+        self._format, self._type = format, type
+        self._alpha, self._mask = Alpha(alpha_type), tuple(bool(m) for m in color_mask)
+        if pvrtc:
+            chans = [c for c in range(4) if mask[c]]
+            return results, self._pooled_pvrtc(results, sum(h.shape[0]*h.shape[1] for h in hosts), chans)
+        return results, self._pooled(results)
 
     def decode_image(self, *args) -> Optional[np.ndarray]:
         """decode_image([face,] mip=0, depth=0): the surface of this converted texture as the RGBAF image a
@@ -788,7 +923,7 @@ class Texture:
 
     def transcode(self, format, type, quality: Quality = Quality.Normal, alpha_type: Optional[Alpha] = None,
                   color_mask: Sequence[bool] = (True, True, True, True), regenerate_mips: bool = False,
-                  filter=api.ResizeFilter.CatmullRom) -> Optional["Texture"]:
+                  filter=api.ResizeFilter.CatmullRom, measure: bool = False, ssim: bool = True):
         """A new converted texture of the same shape in another (format, type), made on the device: the payloads
         are uploaded, decoded into device buffers (one batched launch for block formats), encoded from there with
         cfhip_encode_device / cfhip_pvrtc_encode_device and only the new payloads come back.  regenerate_mips:
@@ -797,7 +932,13 @@ class Texture:
         over.  None where convert() would return False, and when this texture is not converted.
         The result is byte-identical to an unconverted Texture built from decode_image() of every surface (of
         level 0, then generate_mipmaps(filter, mip_levels=mip_level_count()), when regenerating) and convert()
-        with the same arguments.  3-D textures with regenerate_mips take that host route itself."""
+        with the same arguments.  3-D textures with regenerate_mips take that host route itself.
+        measure=True: returns (texture, results, pooled) instead, results and pooled as compare() returns them, the
+        reference being the intermediate the encoder read -- the decoded RGBA8 or RGBA32F texels and the
+        regenerated RGBA32F levels -- still on the device: each new payload is measured as Context.compare measures
+        it against decode_images(pixel) of this texture (or against the regenerated level), with the mask compare()
+        uses, one compare call per pixel type as the encode makes.  The two host routes measure with compare() on
+        the host.  ssim as in compare(): a PVRTC target needs ssim=False (ValueError, raised before any work)."""
         import torch
         if not self._textures or not self.is_format_valid(format, type):
             return None
@@ -808,6 +949,8 @@ class Texture:
         pvrtc_out = format in api.PVRTC_FORMATS
         if pvrtc_out and any(v & (v - 1) for m in range(self._mips) for v in (self.width(m), self.height(m))):
             return None
+        if measure and pvrtc_out and ssim:
+            raise ValueError("compare: PVRTC has no SSIM (pass ssim=False)")
         out = Texture(self._dim, self._w, self._h, self._depth, self._mips, self._color_space,
                       device_id=self._device_id)
         out._ctx = self._ctx
@@ -826,7 +969,15 @@ class Texture:
                     out._images[m][d][f] = self.decode_image(*args)
             if regenerate_mips and not out.generate_mipmaps(filter, mip_levels=self._mips):
                 return None
-            return out if out.convert(format, type, quality, alpha_type, color_mask) else None
+            if not measure:
+                return out if out.convert(format, type, quality, alpha_type, color_mask) else None
+            source = Texture(self._dim, self._w, self._h, self._depth, self._mips, self._color_space,
+                             device_id=self._device_id)
+            source._ctx = self._ctx
+            source._images = [[list(dep) for dep in level] for level in out._images]
+            if not out.convert(format, type, quality, alpha_type, color_mask):
+                return None
+            return (out,) + tuple(out.compare(source, ssim=ssim))
         ctx = self._context()
         dev = "cuda:%d" % self._device_id
         flat = [s for s in self._flat() if not regenerate_mips or s[0] == 0]
@@ -882,12 +1033,29 @@ class Texture:
             if e.code == api.E_UNSUPPORTED:
                 return None
             raise
+        measured = None
+        if measure:
+            mask = [bool(c) for c in color_mask]
+            if alpha_type == Alpha.None_ or not self.has_alpha(format):
+                mask[3] = False
+            # storage order, as compare() lists its results
+            order = sorted(range(len(srcs)), key=lambda i: srcs[i][:3])
+            measured = self._measure_device(ctx, format, type, [(pays[i], srcs[i][3], srcs[i][4], self.width(srcs[i][0]),
+                                                                 self.height(srcs[i][0])) for i in order], mask, ssim)
         host = {(m, d, f): p.cpu().numpy() for (m, d, f, _, _), p in zip(srcs, pays)}
         out._textures = [[[host[(m, d, f)] for f in range(self._faces)] for d in range(self.depth(m))]
                          for m in range(self._mips)]
         out._images = [[[None]*self._faces for _ in range(self.depth(m))] for m in range(self._mips)]
         out._format, out._type = format, type
         out._alpha, out._mask = alpha_type, tuple(bool(c) for c in color_mask)
+        if measure:
+            if pvrtc_out:
+                chans = [c for c in range(4) if mask[c]]
+                if not chans:
+                    raise ValueError("compare: no channel compared")
+                texels = sum(self.width(m)*self.height(m) for m, _, _, _, _ in srcs)
+                return out, measured, self._pooled_pvrtc(measured, texels, chans)
+            return out, measured, self._pooled(measured)
         return out
 
     def _compare_pvrtc(self, ctx, source, mask, ssim):
@@ -905,11 +1073,9 @@ class Texture:
                 for f, payload in enumerate(dep):
                     ref = _rgba8_of(source._images[m][d][f])
                     results.append(ctx.decode_pvrtc_sse(payload, ref, self._format, self._type))
-        sse = sum(r[c] for r in results for c in chans)
         n = sum(int(np.prod(source._images[m][d][f].shape[:2]))
                 for m, level in enumerate(self._textures) for d, dep in enumerate(level) for f in range(len(dep)))
-        pooled = float("inf") if sse == 0 else 10.0 * float(np.log10(255.0 * 255.0 * n * len(chans) / sse))
-        return results, pooled
+        return results, self._pooled_pvrtc(results, n, chans)
 
     # ---- saving (Texture.cpp:1636-1685) --------------------------------------------------------
     def _layout(self) -> containers.TextureLayout:

@@ -532,6 +532,44 @@ int cfhip_compare_device(cfhip_ctx* ctx, int format, int type, const void* block
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device,
 	float* block_errors_device, size_t block_errors_capacity, void* stream);
 
+/* ---- Batched compare: every surface of a texture (mip chain, cube faces, array layers) measured in ONE call ----
+ *
+ * Each surface is measured exactly as cfhip_compare measures it: the same formats (29..56, the pairs cfhip_query
+ * accepts; standard formats and PVRTC are CFHIP_E_UNSUPPORTED and keep their own entries), the same errors and
+ * alignment rules, and results[i] holds the very bits cfhip_compare / cfhip_compare_device return for surface i
+ * alone.  All surfaces share format, type, ref_pixel_type, mask and flags.
+ * The launch count does not depend on n: one Pass A launch over the workgroups of every surface and one final
+ * launch with a workgroup per surface; with CFHIP_COMPARE_SSIM (and a surface of at least 11 x 11 texels) one
+ * batched decode into scratch and one SSIM launch over the tiles of every surface in between.  A surface table
+ * travels through the context's staging and every workgroup finds its surface by a wave-uniform binary search.
+ * Surfaces below 11 texels a side report SSIM NaN and 0 windows.  The device scratch (decoded surfaces, partial
+ * sums) grows with the sum over the surfaces; it is not capped, so a caller short of memory splits the call.
+ * n == 0 is CFHIP_OK and does nothing.  Every argument of every surface is checked before anything is enqueued
+ * (and before ctx is looked at: a NULL ctx is reported last). */
+typedef struct cfhip_compare_surface {
+	const void* blocks;            /* payload of this surface */
+	size_t blocks_bytes;           /* host form: >= its payload size; device form: ignored */
+	uint32_t width, height;
+	const void* ref;               /* width x height texels of ref_pixel_type */
+	size_t ref_pitch_bytes;        /* >= width * bytes per reference texel */
+	float* block_errors;           /* the surface's error map, or NULL: no map for this surface */
+	size_t block_errors_capacity;  /* floats; >= blocks of the surface where block_errors is given, else CFHIP_E_CAPACITY */
+} cfhip_compare_surface;
+
+/* Host buffers.  Payloads that are consecutive in host memory (a loaded file) upload as one copy, and so do tightly
+ * pitched references that are; the n results come back as one copy, the maps one copy each.  Blocking. */
+int cfhip_compare_batch(cfhip_ctx* ctx, int format, int type, const cfhip_compare_surface* surfaces,
+	size_t n_surfaces, int ref_pixel_type, const uint8_t mask_rgba[4], unsigned flags,
+	cfhip_compare_result* results);
+
+/* Device buffers: `surfaces` is a host array of device pointers (references and their pitches aligned to the texel
+ * size, maps to 4 bytes); results_device: n cfhip_compare_result on the device, 8-byte aligned.  mask_rgba is host
+ * memory.  stream NULL = the context's stream, and the call then synchronises; on a caller's stream it returns
+ * once the work is queued. */
+int cfhip_compare_batch_device(cfhip_ctx* ctx, int format, int type, const cfhip_compare_surface* surfaces,
+	size_t n_surfaces, int ref_pixel_type, const uint8_t mask_rgba[4], unsigned flags,
+	cfhip_compare_result* results_device, void* stream);
+
 /* ---- PVRTC1 4 bpp (formats 59 RGB, 60 RGBA; type UNorm) ----
  *
  * PVRTC1 is outside the cfhip_surface block contract: blocks are stored in twiddled (Morton) order, a level is never
