@@ -628,10 +628,11 @@ __device__ __forceinline__ uint32_t geo_src(uint32_t id, uint32_t fi, uint32_t w
 // fraction of their distance (oracle: fitopt.start, cfo_start_frac; 0 = the extremes themselves).
 // gmode (wave-uniform): 0 computes parts A and B, 1 computes them and writes them to the lane's own column of
 // the geometry cache gbase, 2 reads them from column gsrc instead.  NK: palette entries of the selector search
-// (assign_lsq_lane).
-template <bool UNITW, int NK = 8>
+// (assign_lsq_lane).  ITERS: refit rounds of the instance's quality level (one round is straight-line code: it asks
+// for no least-squares solution and its `live` is dead).
+template <bool UNITW, uint32_t ITERS, int NK = 8>
 __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, uint32_t khalf,
-	uint32_t cb, uint32_t ab, uint32_t pbk, uint32_t ib, uint32_t iters, const uint32_t (&wt)[4],
+	uint32_t cb, uint32_t ab, uint32_t pbk, uint32_t ib, const uint32_t (&wt)[4],
 	const uint32_t (&yw)[2], bool scalar, float frac, uint32_t* gbase, uint32_t gmode, uint32_t gsrc, LaneFit& best)
 {
 	float axis[4], mean[4];
@@ -800,8 +801,10 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 	best.q0 = q.q0; best.q1 = q.q1; best.pb = q.pb;
 	bool live;
 	float hq[3];
-	assign_lsq_lane<UNITW, NK>(tx, mask, m6, khalf, G_IB, yw, pp_sum, iters > 0u, q.e0, q.e1, best, x0, x1, hq, live, s01, s23);
-	for (uint32_t r = 0; r < iters; ++r) {
+	assign_lsq_lane<UNITW, NK>(tx, mask, m6, khalf, G_IB, yw, pp_sum, ITERS > 0u, q.e0, q.e1, best, x0, x1, hq, live, s01, s23);
+	// (Highest's two rounds stay a loop: unrolled, the second copy of the search spills 12 vector registers)
+#pragma unroll 1
+	for (uint32_t r = 0; r < ITERS; ++r) {
 		LaneFit cur;
 		bool ok;
 		asm volatile("" : "+v"(geo));
@@ -817,7 +820,7 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 		}
 		if (!(CF_BC7_ABLATE & 8)) refit_window(x0, x1, hq, G_CB, G_AB, G_PBK, q);
 		cur.q0 = q.q0; cur.q1 = q.q1; cur.pb = q.pb;
-		assign_lsq_lane<UNITW, NK>(tx, mask, m6, khalf, G_IB, yw, pp_sum, r + 1u < iters, q.e0, q.e1, cur, x0, x1, hq, ok, s01, s23);
+		assign_lsq_lane<UNITW, NK>(tx, mask, m6, khalf, G_IB, yw, pp_sum, r + 1u < ITERS, q.e0, q.e1, cur, x0, x1, hq, ok, s01, s23);
 		const bool better = live && cur.err < best.err;
 		if (better)
 			best = cur;
@@ -1210,7 +1213,11 @@ __device__ __forceinline__ void column_put_fit(uint32_t* wc, const FitGeo& g, ui
 
 // Encode one block with the whole wavefront.  tp: the block's 16 texels in LDS
 // (colour mask already applied), identical for every lane.
-template <bool UNITW, bool WIDE>
+// LEVEL: the quality level (0 Lowest .. 4 Highest).  Its whole search budget -- refit rounds, list length,
+// perturbation rounds, move sets, streams, the lane layout -- is a compile-time constant of the instance: held as
+// run-time scalars across every phase the budget cost 53 spilled SGPRs in the Normal build, and every lane-role
+// expression selected its layout again.
+template <bool UNITW, bool WIDE, int LEVEL>
 __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint32_t* plan, const uint32_t* yccp, const uint32_t* mom, uint32_t b,
 	bool pair, uint32_t* cbase, uint32_t* gbase, const cf_kparams& kp)
 {
@@ -1238,13 +1245,14 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 #define H_ALPHA (pair ? ((uint32_t)(L_H ? abal >> 32 : abal) & 0xFFFFu) != 0u : ((uint32_t)abal & 0xFFFFu) != 0u)
 	// Low runs Normal's candidate set without the refit round (oracle: quality_budget): `quality`
 	// below selects the LAYOUT, so Low is mapped onto Normal's
-	const uint32_t iters = (0x21100u >> (4u*(kp.quality < 4u ? kp.quality : 4u))) & 15u;   // refit rounds 0,0,1,1,2
+	static_assert(LEVEL >= 0 && LEVEL <= 4 && WIDE == (LEVEL >= 3), "levels 0..2 use the 32-lane layouts, 3 and 4 the wide one");
+	constexpr uint32_t iters = LEVEL >= 4 ? 2u : (LEVEL >= 2 ? 1u : 0u);   // refit rounds 0,0,1,1,2
 	// WIDE (Highest): the 64-lane layout with both streams.  Otherwise the 32-lane layouts: Low and
 	// High walk Normal's candidate set (High adds a refit round and the perturbation rounds below)
-	const uint32_t quality = WIDE ? 3u : ((kp.quality == 1u || kp.quality >= 3u) ? 2u : kp.quality);
+	constexpr uint32_t quality = WIDE ? 3u : (LEVEL == 1 ? 2u : (uint32_t)LEVEL);
 	const uint32_t wt[4] = {kp.wt[0], kp.wt[1], kp.wt[2], kp.wt[3]};
-	// fits with refit rounds start 1/16 inside the extremes (oracle: fitopt.start 1); a scalar, not a hoisted VGPR
-	const float frac_main = __int_as_float(__builtin_amdgcn_readfirstlane(iters ? 0x3d800000 : 0));
+	// fits with refit rounds start 1/16 inside the extremes (oracle: fitopt.start 1)
+	constexpr float frac_main = iters ? 1.0f/16.0f : 0.0f;
 
 	// a lane's best (error, id) so far live in words 18 / 19 of its column, like the payload fields: nothing of
 	// a candidate is carried in registers from one trip of the stream loop to the next
@@ -1270,13 +1278,13 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 	// The partitions come from phase 1: every partition is scored once per subset count with
 	// the residual estimator and the best are taken in (score, index) order.
 	// Highest instead refits every partition (below), after a stream 0 without partitions.
-	const bool lay32 = !WIDE;
+	constexpr bool lay32 = !WIDE;
 #define L_HL (lay32 ? (lane & 31u) : lane)
 #define L_SLOT_OK (!lay32 || pair || lane < 32u)
-	const uint32_t ntop = kp.quality >= 3u ? 8u : (kp.quality == 2u ? 4u : 1u);   // oracle: budget.top
-	const uint32_t uber = kp.quality >= 4u ? 2u : (kp.quality == 3u ? 1u : 0u);    // rounds per top candidate
-	const uint32_t uber2 = kp.quality >= 4u ? 2u : (kp.quality >= 2u ? 1u : 0u);   // rounds on the leader
-	const uint32_t msets = kp.quality >= 4u ? 3u : 1u;       // move sets of a round: bit 0 single, bit 1 joint (Highest only since round 6: oracle quality_budget)
+	constexpr uint32_t ntop = LEVEL >= 3 ? 8u : (LEVEL == 2 ? 4u : 1u);   // oracle: budget.top
+	constexpr uint32_t uber = LEVEL >= 4 ? 2u : (LEVEL == 3 ? 1u : 0u);    // rounds per top candidate
+	constexpr uint32_t uber2 = LEVEL >= 4 ? 2u : (LEVEL >= 2 ? 1u : 0u);   // rounds on the leader
+	constexpr uint32_t msets = LEVEL >= 4 ? 3u : 1u;       // move sets of a round: bit 0 single, bit 1 joint (Highest only since round 6: oracle quality_budget)
 	bool solved = false;
 	// which halves walk the second pass: bit 0 / bit 32 = the best candidate of the first pass leaves the block
 	// of half 0 / 1 with an error of at least 48 (oracle: best_err >= 48u); a scalar pair
@@ -1286,11 +1294,14 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 #define ANY_OPAQUE (pair ? (((uint32_t)abal & 0xFFFFu) == 0u || ((uint32_t)(abal >> 32) & 0xFFFFu) == 0u) : ((uint32_t)abal & 0xFFFFu) == 0u)
 	{
 		// second pass: the three-subset modes of an opaque block (Normal: mode 4 of an alpha-carrying one)
-		const uint32_t nstreams = WIDE ? (has_alpha ? 1u : 2u) : (kp.quality == 2u ? 2u : 1u);
+		// (the one budget value that stays a run-time scalar: with a constant trip count the compiler specialises the
+		// loop by trip and holds more lane-role values across the fit -- the Normal build then spills a vector register)
+		uint32_t nstreams = WIDE ? (has_alpha ? 1u : 2u) : (LEVEL == 2 ? 2u : 1u);
+		asm volatile("" : "+s"(nstreams));
 		// The last trip of this loop (sst) is not a stream of new candidates: it selects the `ntop` best so
 		// far and refits them from four more starts (oracle: encode_block, "more starts") -- through the SAME
 		// fit_lane call as the streams (one copy of the fit in the code object, one register allocation).
-		const uint32_t nsst = ntop > 4u ? 2u : 1u;       // four candidates per starts trip
+		constexpr uint32_t nsst = ntop > 4u ? 2u : 1u;       // four candidates per starts trip
 #pragma unroll 1
 		for (uint32_t st = 0; st < nstreams + nsst; ++st) {
 			const bool sst = st >= nstreams;
@@ -1330,12 +1341,8 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				(!s1l || __ballot(L_SLOT_OK && !(H_ALPHA) && H_GATE) != 0ull);
 			// partition lanes: first lane, slots of the first mode, slots in all
 			// (nper0 depends on the half's H_ALPHA: an expression, like the roles, not a carried value)
-			uint32_t pfirst, nslots;
-			if (lay32) {
-				if (quality == 2u) { pfirst = 10u; nslots = 11u; }
-				else { pfirst = 4u; nslots = 14u; }
-			} else if (st == 1u) { pfirst = 0u; nslots = 10u; }
-			else { pfirst = 26u; nslots = 16u; }
+			const uint32_t pfirst = lay32 ? (quality == 2u ? 10u : 4u) : (st == 1u ? 0u : 26u);
+			const uint32_t nslots = lay32 ? (quality == 2u ? 11u : 14u) : (st == 1u ? 10u : 16u);
 #define R_NPER0 (st == 1u ? 5u : (lay32 ? (quality == 2u ? (H_ALPHA ? 11u : 6u) : 14u) : (H_ALPHA ? 16u : 12u)))
 			// lane roles as expressions of the CURRENT lane id (re-read where a phase starts), so that none of
 			// them is carried in a register through the fit
@@ -1391,7 +1398,10 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				const uint32_t nruns = (st == 1u || ANY_OPAQUE) ? 2u : 1u;
 				for (uint32_t run = 0; run < nruns; ++run) {
 					CF_FRESH_LANE(lane);
-					const float qf = (run == 0u && !(st == 0u && (H_ALPHA))) ? 1.0f/128.0f : 1.0f/32.0f;
+					// (formed here from its bits: as a float select it is hoisted out of the stream loop and held in a register)
+					uint32_t qfb = (run == 0u && !(st == 0u && (H_ALPHA))) ? 0x3C000000u : 0x3D000000u;   // 1/128 : 1/32
+					asm volatile("" : "+v"(qfb));
+					const float qf = __uint_as_float(qfb);
 					const uint32_t part0 = pair ? L_HL : lane;
 					const uint32_t npart = (st == 1u && run == 0u) ? 16u : 64u;   // mode 0 ranks its own 16 partitions
 					uint32_t ka = part0 < npart ? ((__float_as_uint(fmaf(qf, sl0, sc0)) & ~63u) | part0) : 0xFFFFFFFFu;
@@ -1515,10 +1525,10 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				((chm & 7u) ? (ywba & 0xFFFFu) : 0u) | ((chm & 8u) ? (ywba & 0xFFFF0000u) : 0u)};
 			if (active) {
 				if (narrow)
-					fit_lane<UNITW, 4>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib, iters,
+					fit_lane<UNITW, iters, 4>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
 						wv, yw, sca, frac, gbase, gmode, gsrc, lf);
 				else
-					fit_lane<UNITW>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib, iters,
+					fit_lane<UNITW, iters>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
 						wv, yw, sca, frac, gbase, gmode, gsrc, lf);
 			}
 			CF_FRESH_LANE(lane);         // the roles below are computed again from here
@@ -1843,7 +1853,7 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 #ifndef CF_BC7_WAVES
 #define CF_BC7_WAVES(UNITW, WIDE) ((UNITW) ? 4 : 3)
 #endif
-template <int PIX, bool UNITW, bool WIDE>
+template <int PIX, bool UNITW, bool WIDE, int LEVEL>
 __global__ void __launch_bounds__(CF_WG_THREADS)
 __attribute__((amdgpu_waves_per_eu(CF_BC7_WAVES(UNITW, WIDE), CF_BC7_WAVES(UNITW, WIDE))))
 cfhip_bc7_encode_kernel(cf_kparams kp)
@@ -1892,7 +1902,7 @@ cfhip_bc7_encode_kernel(cf_kparams kp)
 			!(CF_BC7_ABLATE & 4);
 		// opaque copy: keeps the (many) lane-role values of encode_blocks from being hoisted
 		// out of this loop and held in registers across all phases
-		const uint4 blk = encode_blocks<UNITW, WIDE>(tile, plan, yccp, mom, b, pair, cands + wave*64u, geoc + wave*64u, kp);
+		const uint4 blk = encode_blocks<UNITW, WIDE, LEVEL>(tile, plan, yccp, mom, b, pair, cands + wave*64u, geoc + wave*64u, kp);
 		uint32_t lo;
 		asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lo));
 		if (pair) {
@@ -1924,16 +1934,23 @@ extern "C" hipError_t cfhip_launch_bc7(const cf_kparams* kp, int pixel_type, int
 	if (kp->batch)
 		grid = dim3(kp->total_wg, 1, 1);
 	dim3 block(CF_WG_THREADS, 1, 1);
-	const bool exh = kp->quality >= 3u;   // High, Highest: the wide (64-lane, two-stream) candidate set
-#define CF_BC7_LAUNCH(P, U, E) \
-	hipLaunchKernelGGL((cfhip_bc7_encode_kernel<P, U, E>), grid, block, 0, stream, *kp)
-	if (pixel_type == 0) {
-		if (unit_weights) { if (exh) CF_BC7_LAUNCH(0, true, true); else CF_BC7_LAUNCH(0, true, false); }
-		else { if (exh) CF_BC7_LAUNCH(0, false, true); else CF_BC7_LAUNCH(0, false, false); }
-	} else {
-		if (unit_weights) { if (exh) CF_BC7_LAUNCH(1, true, true); else CF_BC7_LAUNCH(1, true, false); }
-		else { if (exh) CF_BC7_LAUNCH(1, false, true); else CF_BC7_LAUNCH(1, false, false); }
+	// one instance per quality level (levels above Highest run Highest's, like the oracle's clamp)
+#define CF_BC7_LAUNCH(P, U, E, L) \
+	hipLaunchKernelGGL((cfhip_bc7_encode_kernel<P, U, E, L>), grid, block, 0, stream, *kp)
+#define CF_BC7_LEVELS(P, U) \
+	switch (kp->quality) { \
+		case 0u: CF_BC7_LAUNCH(P, U, false, 0); break; \
+		case 1u: CF_BC7_LAUNCH(P, U, false, 1); break; \
+		case 2u: CF_BC7_LAUNCH(P, U, false, 2); break; \
+		case 3u: CF_BC7_LAUNCH(P, U, true, 3); break; \
+		default: CF_BC7_LAUNCH(P, U, true, 4); break; \
 	}
+	if (pixel_type == 0) {
+		if (unit_weights) CF_BC7_LEVELS(0, true) else CF_BC7_LEVELS(0, false)
+	} else {
+		if (unit_weights) CF_BC7_LEVELS(1, true) else CF_BC7_LEVELS(1, false)
+	}
+#undef CF_BC7_LEVELS
 #undef CF_BC7_LAUNCH
 	return hipGetLastError();
 }

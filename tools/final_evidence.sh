@@ -8,9 +8,10 @@ G=$R/gpurun_out
 mkdir -p $G
 for q in 2 3 4; do
   sfx=""; [ $q != 2 ] && sfx="_q$q"
-  kern="cfhip_bc7_encode_kernel<0, true, false>"; mang="cfhip_bc7_encode_kernelILi0ELb1ELb0E"
+  # one instance per level: <PIX, UNITW, WIDE, LEVEL>; bench.py matches the first three arguments (the largest instance wins)
+  kern="cfhip_bc7_encode_kernel<0, true, false, $q>"; mang="cfhip_bc7_encode_kernelILi0ELb1ELb0E"
   # (round 5: High runs the wide kernel too)
-  [ $q -ge 3 ] && kern="cfhip_bc7_encode_kernel<0, true, true>" && mang="cfhip_bc7_encode_kernelILi0ELb1ELb1E"
+  [ $q -ge 3 ] && kern="cfhip_bc7_encode_kernel<0, true, true, $q>" && mang="cfhip_bc7_encode_kernelILi0ELb1ELb1E"
   bash $R/tools/profile.sh ${tag}$sfx --quality $q > $G/${tag}${sfx}_bc7_pmc_summary.txt 2>&1
   python $R/tools/pmc_to_json.py $G/prof_${tag}$sfx --tag ${tag}$sfx --quality $q --kernel "$kern" --mangled "$mang" --out $G/bc7_pmc$sfx.json > /dev/null \
     && cp $G/bc7_pmc$sfx.json $R/profiles/bc7_pmc$sfx.json

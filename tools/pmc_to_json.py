@@ -39,7 +39,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("prof_dir")
     ap.add_argument("--tag", required=True)
-    ap.add_argument("--kernel", default="cfhip_bc7_encode_kernel<0, true, false>")
+    ap.add_argument("--kernel", default="cfhip_bc7_encode_kernel<0, true, false, 2>")   # <PIX, UNITW, WIDE, LEVEL>
     ap.add_argument("--mangled", default="cfhip_bc7_encode_kernelILi0ELb1ELb0E")
     ap.add_argument("--quality", type=int, default=2, help="Texture::Quality the passes ran at")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bc7_pmc.json"))

@@ -65,6 +65,48 @@ __global__ void __launch_bounds__(256) k(uint32_t* out, uint32_t seed)
 #pragma unroll
 		for (int i = 0; i < 8; ++i) a[i] = (uint32_t)acc[i] ^ (uint32_t)(acc[i] >> 32);
 	}
+	if (OP >= 29 && OP <= 31) {   // packed fp32: both operands and the destination are register pairs (two floats per lane)
+		unsigned long long acc[8];
+		const unsigned long long b2 = ((unsigned long long)__float_as_uint(1.0f + (float)(b & 255u)/1024.0f) << 32) | __float_as_uint(0.999f);
+		const unsigned long long c2 = ((unsigned long long)__float_as_uint(0.25f) << 32) | __float_as_uint((float)(c & 15u));
+#pragma unroll
+		for (int i = 0; i < 8; ++i)
+			acc[i] = ((unsigned long long)__float_as_uint((float)a[i]) << 32) | __float_as_uint((float)a[i + 8]);
+		for (int it = 0; it < ITER; ++it) {
+#pragma unroll
+			for (int rep = 0; rep < 2; ++rep)
+#pragma unroll
+				for (int i = 0; i < 8; ++i) {
+					if (OP == 29) asm volatile("v_pk_mul_f32 %0, %0, %1" : "+v"(acc[i]) : "v"(b2), "v"(c2));
+					if (OP == 30) asm volatile("v_pk_add_f32 %0, %0, %1" : "+v"(acc[i]) : "v"(b2), "v"(c2));
+					if (OP == 31) asm volatile("v_pk_fma_f32 %0, %0, %1, %2" : "+v"(acc[i]) : "v"(b2), "v"(c2));
+				}
+		}
+#pragma unroll
+		for (int i = 0; i < 8; ++i) a[i] = (uint32_t)acc[i] ^ (uint32_t)(acc[i] >> 32);
+	}
+	if (OP == 32) {   // what a scalar-spill reload is: one lane of a vector register to a scalar register
+		uint32_t s[16];
+		for (int it = 0; it < ITER; ++it) {
+#pragma unroll
+			for (int i = 0; i < 16; ++i)
+				asm volatile("v_readlane_b32 %0, %1, 5" : "=s"(s[i]) : "v"(a[i]));
+		}
+#pragma unroll
+		for (int i = 0; i < 16; ++i) a[i] ^= s[i];
+	}
+	if (OP == 33) {   // ... and the spill itself: a scalar into one lane
+		const uint32_t sv = (uint32_t)__builtin_amdgcn_readfirstlane((int)c);
+		for (int it = 0; it < ITER; ++it) {
+#pragma unroll
+			for (int i = 0; i < 16; ++i)
+				asm volatile("v_writelane_b32 %0, %1, 5" : "+v"(a[i]) : "s"(sv));
+		}
+	}
+	// a select behind the compare that produces its mask (the v_cndmask_b32 row above reads a VCC nobody wrote and is not
+	// representative): two instructions per chain step, reported per instruction
+	if (OP == 34) BODY("v_cmp_lt_u32 vcc, %1, %0\n\tv_cndmask_b32 %0, %0, %2, vcc", : "vcc")
+	if (OP == 35) BODY("v_cmp_lt_u32 vcc, %1, %0", : "vcc")   // the compare alone
 	uint32_t r = 0;
 #pragma unroll
 	for (int i = 0; i < 16; ++i) r ^= a[i];
@@ -72,7 +114,7 @@ __global__ void __launch_bounds__(256) k(uint32_t* out, uint32_t seed)
 }
 
 template <int OP>
-static void run(const char* name, int waves_per_simd)
+static void run(const char* name, int waves_per_simd, int per_step = 1)   // per_step: instructions per chain step
 {
 	int ncu = 0;
 	(void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0);
@@ -90,7 +132,7 @@ static void run(const char* name, int waves_per_simd)
 	(void)hipEventSynchronize(e1);
 	float ms; (void)hipEventElapsedTime(&ms, e0, e1);
 	ms /= 5.0f;
-	const double instr = (double)ITER*16*waves_per_simd;   // wave-instructions per SIMD
+	const double instr = (double)ITER*16*waves_per_simd*per_step;   // wave-instructions per SIMD
 	const double ns = ms*1e6/instr;
 	printf("%-18s waves/SIMD %d  %7.3f ms  %5.2f ns/wave-instr/SIMD  = %4.2f cycles @2.4GHz\n",
 		name, waves_per_simd, ms, ns, ns*2.4);
@@ -110,6 +152,9 @@ int main()
 		run<1>("v_fma_f32", w);       run<15>("v_mul_f32", w);     run<16>("v_add_f32", w);
 		run<23>("v_mad_i32_i24", w);  run<24>("v_mul_i32_i24", w); run<25>("v_sad_u8", w);
 		run<26>("v_med3_i32", w);     run<27>("v_ashrrev_i32", w); run<28>("v_mad_u64_u32", w);
+		run<29>("v_pk_mul_f32", w);   run<30>("v_pk_add_f32", w);  run<31>("v_pk_fma_f32", w);
+		run<32>("v_readlane_b32", w); run<33>("v_writelane_b32", w);
+		run<35>("v_cmp_lt_u32", w);   run<34>("v_cmp+v_cndmask", w, 2);
 	}
 	return 0;
 }
