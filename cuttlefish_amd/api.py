@@ -191,7 +191,8 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_pvrtc_decode_device", "cfhip_pvrtc_decode_sse", "cfhip_pvrtc_decode_sse_device",
            "cfhip_std_unpack", "cfhip_std_unpack_device", "cfhip_std_compare", "cfhip_std_compare_device",
            "cfhip_decode_batch", "cfhip_decode_batch_device", "cfhip_decode_out_supported",
-           "cfhip_compare_batch", "cfhip_compare_batch_device"]
+           "cfhip_compare_batch", "cfhip_compare_batch_device",
+           "cfhip_rdo_supported", "cfhip_rdo", "cfhip_rdo_device"]
 
 
 class Layout(enum.IntEnum):
@@ -295,6 +296,29 @@ class CompareSurface(ctypes.Structure):
                 ("height", ctypes.c_uint32), ("ref", ctypes.c_void_p), ("ref_pitch_bytes", ctypes.c_size_t),
                 ("block_errors", ctypes.c_void_p), ("block_errors_capacity", ctypes.c_size_t)]
 
+
+class RdoParams(ctypes.Structure):
+    """struct cfhip_rdo_params"""
+    _fields_ = [("lam", ctypes.c_float), ("max_sse_increase", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class RdoSurface(ctypes.Structure):
+    """struct cfhip_rdo_surface"""
+    _fields_ = [("blocks", ctypes.c_void_p), ("blocks_bytes", ctypes.c_size_t), ("out", ctypes.c_void_p),
+                ("out_capacity", ctypes.c_size_t), ("width", ctypes.c_uint32), ("height", ctypes.c_uint32),
+                ("pixels", ctypes.c_void_p), ("pixel_type", ctypes.c_int32), ("row_pitch_bytes", ctypes.c_size_t)]
+
+
+class RdoStats(ctypes.Structure):
+    """struct cfhip_rdo_stats"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("blocks", "blocks_changed", "sse_before", "sse_after", "bits_before",
+                                               "bits_after")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+RDO_NO_CAP = 0xFFFFFFFF         # max_sse_increase: no cap
 
 DECODE_NATIVE = -1              # CFHIP_DECODE_NATIVE
 # output texel (channels, dtype) of a batched decode to a pixel type
@@ -490,6 +514,14 @@ def load_library(path: Optional[str] = None):
                                              ctypes.POINTER(CompareSurface), ctypes.c_size_t, ctypes.c_int, u8p,
                                              ctypes.c_uint, ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_compare_batch_device.restype = ctypes.c_int
+    L.cfhip_rdo_supported.argtypes = [ctypes.c_int, ctypes.c_int]
+    L.cfhip_rdo_supported.restype = ctypes.c_int
+    L.cfhip_rdo.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RdoSurface), ctypes.c_size_t,
+                            ctypes.POINTER(RdoParams), u8p, ctypes.c_void_p]
+    L.cfhip_rdo.restype = ctypes.c_int
+    L.cfhip_rdo_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RdoSurface),
+                                   ctypes.c_size_t, ctypes.POINTER(RdoParams), u8p, ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_rdo_device.restype = ctypes.c_int
     L.cfhip_decode_out_supported.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.cfhip_decode_out_supported.restype = ctypes.c_int
     _lib = L
@@ -546,6 +578,18 @@ def decode_out_supported(fmt, typ, out_pixel=None) -> bool:
     """Whether a batched decode of (fmt, typ) can store out_pixel (None: the native layout).  Needs no device."""
     return bool(load_library().cfhip_decode_out_supported(int(fmt), int(typ),
                                                           DECODE_NATIVE if out_pixel is None else int(out_pixel)))
+
+
+def rdo_supported(fmt, typ=Type.UNorm) -> bool:
+    """Whether Context.rdo optimises payloads of this (format, type) pair: BC1-5 and BC7, UNorm."""
+    return bool(load_library().cfhip_rdo_supported(int(fmt), int(typ)))
+
+
+def make_rdo_params(lam: float, max_sse_increase: Optional[int] = None) -> RdoParams:
+    p = RdoParams()
+    p.lam = float(lam)
+    p.max_sse_increase = RDO_NO_CAP if max_sse_increase is None else int(max_sse_increase)
+    return p
 
 
 def psnr_from_sse(sse, n_texels: int, channels: int = 3) -> float:
@@ -995,6 +1039,51 @@ class Context:
         self._check(self._lib.cfhip_compare_batch_device(
             self._h, int(fmt), int(typ), surf, n, int(ref_pixel_type), self._mask(mask), COMPARE_SSIM if ssim else 0,
             ctypes.c_void_p(int(results)) if results else None, ctypes.c_void_p(stream) if stream else None))
+
+    def rdo(self, payloads: Sequence[np.ndarray], sources: Sequence[np.ndarray], fmt, typ=Type.UNorm, lam: float = 1.0,
+            max_sse_increase: Optional[int] = None, mask=None):
+        """Rate-distortion optimisation of encoded payloads (cfhip_rdo): payloads[i] was encoded from sources[i],
+        an (h, w, 4) uint8, float16 or float32 array.  Blocks are rewritten to copy byte ranges from the blocks before
+        them where J = 16 SSE + round(16 lam) R falls (see include/cuttlefish_hip.h), no block's SSE rising by more
+        than max_sse_increase (None: no cap).  All surfaces share one launch.  Returns (the optimised payloads, one
+        dict of statistics per surface: blocks, blocks_changed, sse_before, sse_after, bits_before, bits_after)."""
+        n = len(payloads)
+        if len(sources) != n:
+            raise ValueError("payloads and sources must list the same surfaces")
+        params = make_rdo_params(lam, max_sse_increase)
+        surf = (RdoSurface*max(n, 1))()
+        srcs = [np.ascontiguousarray(s) for s in sources]
+        if any(s.ndim != 3 or s.shape[2] != 4 for s in srcs):
+            raise ValueError("sources must be (h, w, 4) uint8, float16 or float32")
+        parts = [np.ascontiguousarray(p, dtype=np.uint8).reshape(-1) for p in payloads]
+        outs = [np.empty_like(p) for p in parts]
+        for i, (p, o, s) in enumerate(zip(parts, outs, srcs)):
+            surf[i].blocks, surf[i].blocks_bytes = p.ctypes.data, p.nbytes
+            surf[i].out, surf[i].out_capacity = o.ctypes.data, o.nbytes
+            surf[i].height, surf[i].width = s.shape[:2]
+            surf[i].pixels, surf[i].pixel_type, surf[i].row_pitch_bytes = s.ctypes.data, int(pixel_type_of(s)), s.strides[0]
+        stats = (RdoStats*max(n, 1))()
+        self._check(self._lib.cfhip_rdo(self._h, int(fmt), int(typ), surf, n, ctypes.byref(params), self._mask(mask),
+                                        ctypes.addressof(stats)))
+        return outs, [stats[i].as_dict() for i in range(n)]
+
+    def rdo_device(self, surfaces: Sequence[dict], fmt, typ, lam: float, stats: int,
+                   max_sse_increase: Optional[int] = None, mask=None, stream: int = 0):
+        """Device path of rdo.  surfaces: dicts with blocks, out, pixels (device pointers as ints; out may equal
+        blocks), out_capacity, width, height, pixel_type and row_pitch_bytes.  stats: device pointer to
+        len(surfaces) cfhip_rdo_stats (overwritten).  stream 0 = the context's stream (the call then synchronises)."""
+        n = len(surfaces)
+        params = make_rdo_params(lam, max_sse_increase)
+        surf = (RdoSurface*max(n, 1))()
+        for i, s in enumerate(surfaces):
+            surf[i].blocks, surf[i].out = int(s["blocks"]) or None, int(s["out"]) or None
+            surf[i].out_capacity = int(s["out_capacity"])
+            surf[i].width, surf[i].height = s["width"], s["height"]
+            surf[i].pixels, surf[i].pixel_type = int(s["pixels"]) or None, int(s["pixel_type"])
+            surf[i].row_pitch_bytes = s["row_pitch_bytes"]
+        self._check(self._lib.cfhip_rdo_device(
+            self._h, int(fmt), int(typ), surf, n, ctypes.byref(params), self._mask(mask),
+            ctypes.c_void_p(int(stats)) if stats else None, ctypes.c_void_p(stream) if stream else None))
 
     def unpack(self, payload: np.ndarray, fmt, typ, width: int, height: int) -> np.ndarray:
         """The payload of a standard (uncompressed) format, formats 1..28, back to texels on the GPU ->

@@ -10,6 +10,7 @@
 #include "pvrtc_surf.h"
 #include "compare_batch.h"
 #include "decode_batch.h"
+#include "rdo.h"
 #include "../../include/cuttlefish_hip.h"
 
 #include <cmath>
@@ -2901,6 +2902,223 @@ int cfhip_compare_batch_device(cfhip_ctx* ctx, int format, int type, const cfhip
 		return rc;
 	rc = compare_batch_launch(ctx, lease, format, type, ref_pixel_type, p, static_cast<uint8_t*>(ctx->d_out),
 		results_device);
+	if (rc != CFHIP_OK)
+		return rc;
+	return lease.done(!stream_);
+}
+
+// ---- rate-distortion optimisation of BC1-5 / BC7 payloads (csrc/rdo.hip, csrc/rdo.h) ---------------------------
+struct RdoPlan {
+	int row;
+	uint32_t lam16, cap;
+	unsigned cmask;
+	std::vector<cfrdo_entry> entries;         // blocks / out / pixels still the caller's pointers
+	std::vector<size_t> payload, texel;       // payload bytes; bytes of a source texel
+	uint32_t total_seg;
+};
+
+// Every check of an RDO call, made before the context is touched (so that they need no device).  ctx may be NULL
+// here; the caller rejects that afterwards.
+static int rdo_check(cfhip_ctx* ctx, const char* what, int format, int type, const cfhip_rdo_surface* s, size_t n,
+	const cfhip_rdo_params* params, const uint8_t* mask, const void* stats, bool host, RdoPlan* p)
+{
+	p->row = cfrdo_find_row(format, type);
+	if (p->row < 0)
+		return fail(ctx, CFHIP_E_UNSUPPORTED, "%s: (format %d, type %d) is outside the RDO table", what, format, type);
+	p->total_seg = 0;
+	if (!n)
+		return CFHIP_OK;
+	if (!s || !params || !stats)
+		return fail(ctx, CFHIP_E_INVALID, "%s: surfaces, params or stats is NULL", what);
+	if (!(params->lambda > 0.0f && params->lambda <= 1024.0f))
+		return fail(ctx, CFHIP_E_INVALID, "%s: lambda %g is outside (0, 1024]", what, (double)params->lambda);
+	if (params->reserved[0] || params->reserved[1])
+		return fail(ctx, CFHIP_E_INVALID, "%s: reserved parameters must be 0", what);
+	if (n > 0xFFFFFFu)
+		return fail(ctx, CFHIP_E_INVALID, "%s: too many surfaces (%zu)", what, n);
+	if ((uintptr_t)stats % 8u != 0)
+		return fail(ctx, CFHIP_E_INVALID, "%s: stats must be 8-byte aligned", what);
+	p->lam16 = (uint32_t)std::floor((double)params->lambda*16.0 + 0.5);
+	p->cap = params->max_sse_increase;
+	unsigned m = 15u;
+	if (mask)
+		m = (mask[0] ? 1u : 0u) | (mask[1] ? 2u : 0u) | (mask[2] ? 4u : 0u) | (mask[3] ? 8u : 0u);
+	const cfrdo_row& row = kCfrdoRows[p->row];
+	p->cmask = row.channels & m;
+	p->entries.resize(n);
+	p->payload.resize(n);
+	p->texel.resize(n);
+	uint64_t segs = 0;
+	for (size_t i = 0; i < n; ++i) {
+		if (!s[i].blocks || !s[i].out || !s[i].pixels)
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: blocks, out or pixels is NULL", what, i);
+		if (!s[i].width || !s[i].height)
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: empty surface %ux%u", what, i, s[i].width, s[i].height);
+		size_t tb;
+		switch (s[i].pixel_type) {
+			case CFHIP_PIXEL_RGBA8: tb = 4; break;
+			case CFHIP_PIXEL_RGBA32F: tb = 16; break;
+			case CFHIP_PIXEL_RGBA16F: tb = 8; break;
+			default: return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: pixel type %d", what, i, s[i].pixel_type);
+		}
+		if (s[i].row_pitch_bytes < (size_t)s[i].width*tb)
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: row pitch %zu < %zu", what, i, s[i].row_pitch_bytes,
+				(size_t)s[i].width*tb);
+		if (!host && ((uintptr_t)s[i].pixels % tb != 0 || s[i].row_pitch_bytes % tb != 0))
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: pixels and their pitch must be %zu-byte aligned", what, i, tb);
+		const uint32_t bx = (s[i].width + 3u)/4u, by = (s[i].height + 3u)/4u;
+		const size_t bytes = (size_t)bx*by*(size_t)row.block_bytes;
+		if (host && s[i].blocks_bytes < bytes)
+			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: blocks_bytes %zu < %zu for %ux%u", what, i,
+				s[i].blocks_bytes, bytes, s[i].width, s[i].height);
+		if (s[i].out_capacity < bytes)
+			return fail(ctx, CFHIP_E_CAPACITY, "%s: surface %zu: out_capacity %zu < %zu", what, i, s[i].out_capacity, bytes);
+		cfrdo_entry& e = p->entries[i];
+		e.blocks = static_cast<const uint8_t*>(s[i].blocks);
+		e.out = static_cast<uint8_t*>(s[i].out);
+		e.pixels = static_cast<const uint8_t*>(s[i].pixels);
+		e.pitch = s[i].row_pitch_bytes;
+		e.width = s[i].width; e.height = s[i].height; e.bx = bx; e.by = by;
+		e.seg_begin = (uint32_t)segs;
+		e.segx = (bx + CFRDO_SEG - 1u)/CFRDO_SEG;
+		e.pix = (uint32_t)s[i].pixel_type;
+		e.vec = 0;
+		p->payload[i] = bytes;
+		p->texel[i] = tb;
+		segs += (uint64_t)e.segx*by;
+		if (segs > 0x7FFFFFFFull)
+			return fail(ctx, CFHIP_E_INVALID, "%s: the surfaces are too large for one launch", what);
+	}
+	p->total_seg = (uint32_t)segs;
+	return CFHIP_OK;
+}
+
+// the surface table into staging, the counters cleared and the one launch of the call, timed as every encode launch
+// is; the entries hold device pointers by now
+static int rdo_launch(cfhip_ctx* ctx, StagingLease& lease, RdoPlan& p, cfhip_rdo_stats* stats)
+{
+	static_assert(sizeof(cfhip_rdo_stats) == CFRDO_STATS*sizeof(unsigned long long), "the kernel's counters are the struct");
+	const hipStream_t stream = lease.stream;
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = "cfhip_rdo_kernel";
+	const size_t n = p.entries.size();
+	const size_t bb = (size_t)kCfrdoRows[p.row].block_bytes;
+	for (cfrdo_entry& e : p.entries)
+		e.vec = ((uintptr_t)e.blocks % bb == 0 && (uintptr_t)e.out % bb == 0) ? 1 : 0;
+	int rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, n*sizeof(cfrdo_entry));
+	if (rc != CFHIP_OK)
+		return rc;
+	// pageable source: the runtime stages the copy before returning, so the table may die
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, p.entries.data(), n*sizeof(cfrdo_entry), hipMemcpyHostToDevice, stream));
+	HIP_TRY(ctx, hipMemsetAsync(stats, 0, n*sizeof(cfhip_rdo_stats), stream));
+	hipEvent_t a, b;
+	rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, stream));
+	const hipError_t e = cfhip_launch_rdo(p.row, static_cast<const cfrdo_entry*>(ctx->d_batch), (uint32_t)n, p.total_seg,
+		p.lam16, p.cap, p.cmask, reinterpret_cast<unsigned long long*>(stats), stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "rdo launch: %s", hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, stream));
+	return CFHIP_OK;
+}
+
+int cfhip_rdo_supported(int format, int type)
+{
+	return cfrdo_find_row(format, type) >= 0 ? 1 : 0;
+}
+
+int cfhip_rdo(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
+	const cfhip_rdo_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	RdoPlan p;
+	int rc = rdo_check(ctx, "rdo", format, type, surfaces, n, params, mask_rgba, stats, true, &p);
+	if (rc != CFHIP_OK || !n)
+		return rc;
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, ctx->stream);
+	const hipStream_t stream = lease.stream;
+	// d_src: the payloads (optimised in place there), each 256-byte aligned; d_out: the sources, tightly pitched and
+	// 16-byte aligned, then the counters
+	std::vector<size_t> blk_off(n), pix_off(n);
+	size_t so = 0, po = 0;
+	for (size_t i = 0; i < n; ++i) {
+		blk_off[i] = so;
+		so = (so + p.payload[i] + 255u) & ~(size_t)255u;
+		pix_off[i] = po;
+		po = align16(po + (size_t)surfaces[i].width*p.texel[i]*surfaces[i].height);
+	}
+	const size_t stats_off = po;
+	rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, so);
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, stats_off + n*sizeof(cfhip_rdo_stats));
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* d_blk = static_cast<uint8_t*>(ctx->d_src);
+	uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
+	for (size_t i = 0; i < n; ++i) {
+		const cfhip_rdo_surface& s = surfaces[i];
+		const size_t rowb = (size_t)s.width*p.texel[i];
+		HIP_TRY(ctx, hipMemcpyAsync(d_blk + blk_off[i], s.blocks, p.payload[i], hipMemcpyHostToDevice, stream));
+		if (s.row_pitch_bytes == rowb)
+			HIP_TRY(ctx, hipMemcpyAsync(d + pix_off[i], s.pixels, rowb*s.height, hipMemcpyHostToDevice, stream));
+		else
+			HIP_TRY(ctx, hipMemcpy2DAsync(d + pix_off[i], rowb, s.pixels, s.row_pitch_bytes, rowb, s.height,
+				hipMemcpyHostToDevice, stream));
+		cfrdo_entry& e = p.entries[i];
+		e.blocks = e.out = d_blk + blk_off[i];
+		e.pixels = d + pix_off[i];
+		e.pitch = rowb;
+	}
+	cfhip_rdo_stats* d_stats = reinterpret_cast<cfhip_rdo_stats*>(d + stats_off);
+	rc = rdo_launch(ctx, lease, p, d_stats);
+	if (rc != CFHIP_OK)
+		return rc;
+	std::vector<cfhip_rdo_stats> res(n);
+	HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_stats, n*sizeof(cfhip_rdo_stats), hipMemcpyDeviceToHost, stream));
+	for (size_t i = 0; i < n; ++i)
+		HIP_TRY(ctx, hipMemcpyAsync(surfaces[i].out, d_blk + blk_off[i], p.payload[i], hipMemcpyDeviceToHost, stream));
+	rc = lease.done(true);
+	if (rc != CFHIP_OK)
+		return rc;
+	for (size_t i = 0; i < n; ++i)
+		stats[i] = res[i];
+	return CFHIP_OK;
+}
+
+int cfhip_rdo_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
+	const cfhip_rdo_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats_device, void* stream_)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	RdoPlan p;
+	int rc = rdo_check(ctx, "rdo_device", format, type, surfaces, n, params, mask_rgba, stats_device, false, &p);
+	if (rc != CFHIP_OK || !n)
+		return rc;
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	// the surface table lives in d_batch: the lease orders it across streams
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	rc = rdo_launch(ctx, lease, p, stats_device);
 	if (rc != CFHIP_OK)
 		return rc;
 	return lease.done(!stream_);

@@ -328,6 +328,7 @@ class Texture:
         self._type: Optional[Type] = None
         self._alpha = Alpha.Standard
         self._mask = (True, True, True, True)
+        self._rdo_stats = None
 
     def initialize(self, dimension, width: int, height: int, depth: int = 0, mip_levels: int = 1,
                    color_space: ColorSpace = ColorSpace.Linear) -> bool:
@@ -788,6 +789,85 @@ class Texture:
         return [api.Comparison(api.CompareResult.from_buffer_copy(raw[i].tobytes()), layout, None,
                                typ=type if std else None) for i in range(n)]
 
+    def _encode_resident(self, ctx, flat, format, type, params):
+        """Upload every image once and encode it from there (Context.encode_device): (the host arrays, their device
+        copies, the device payloads), or None where the encoder answers UNSUPPORTED."""
+        import torch
+        dev = "cuda:%d" % self._device_id
+        pvrtc = format in api.PVRTC_FORMATS
+        hosts = [np.ascontiguousarray(im) for im in flat]
+        texels = [torch.from_numpy(h).to(dev) for h in hosts]
+        size = api.pvrtc_payload_size if pvrtc else api.payload_size
+        try:
+            pays = [torch.empty(size(format, type, h.shape[1], h.shape[0]), dtype=torch.uint8, device=dev) for h in hosts]
+            surfaces = [dict(pixels=t.data_ptr(), pixel_type=int(api.pixel_type_of(h)), width=h.shape[1],
+                             height=h.shape[0], row_pitch_bytes=h.strides[0], out=p.data_ptr(), out_capacity=p.numel())
+                        for h, t, p in zip(hosts, texels, pays)]
+            # one call per pixel type, as transcode() encodes
+            for pt in sorted({s["pixel_type"] for s in surfaces}):
+                group = [s for s in surfaces if s["pixel_type"] == pt]
+                (ctx.encode_pvrtc_device if pvrtc else ctx.encode_device)(group, params)
+        except api.CfhipError as e:
+            if e.code == api.E_UNSUPPORTED:
+                return None
+            raise
+        return hosts, texels, pays
+
+    def _adopt(self, payloads, format, type, alpha_type, color_mask):
+        """convert()'s end state: the payloads in (mip, depth, face) order, the images freed"""
+        it = iter(payloads)
+        self._rdo_stats = None
+        self._textures = [[[next(it) for _ in dep] for dep in level] for level in self._images]
+        self._images = [[[None]*len(dep) for dep in level] for level in self._images]
+        self._format, self._type = format, type
+        self._alpha, self._mask = Alpha(alpha_type), tuple(bool(m) for m in color_mask)
+
+    def convert_rdo(self, format: Format, type: Type, quality: Quality = Quality.Normal,
+                    alpha_type: Alpha = Alpha.Standard,
+                    color_mask: Sequence[bool] = (True, True, True, True), rdo_lambda: float = 1.0,
+                    max_sse_increase: Optional[int] = None) -> bool:
+        """convert(), then the rate-distortion pass (Context.rdo_device) over the fresh payloads against the texels
+        they were encoded from, in one visit to the device: every image is uploaded once, encoded from there,
+        optimised in place, and only the final payloads and the statistics (rdo_stats()) come back.  The channels
+        the pass measures are compare()'s: the colour mask's, without alpha when the alpha type is None.  Returns
+        False wherever convert() does and for the formats the pass does not cover (api.rdo_supported); the texture
+        is then left unconverted.  A lambda outside (0, 1024] raises api.CfhipError."""
+        import ctypes
+        import torch
+        if not self.images_complete() or not self.is_format_valid(format, type):
+            return False
+        format, type = Format(format), Type(type)
+        if self._color_space == ColorSpace.sRGB and not self.has_native_srgb(format, type):
+            return False
+        if not api.rdo_supported(format, type):
+            return False
+        flat = [im for level in self._images for dep in level for im in dep]
+        flat = [im.astype(np.float32) if im.dtype == np.float16 else im for im in flat]
+        mask = [bool(m) for m in color_mask]
+        if Alpha(alpha_type) == Alpha.None_ or not self.has_alpha(format):
+            mask[3] = False
+        params = api.make_params(format, type, quality, alpha_type, color_mask, self._color_space)
+        ctx = self._context()
+        resident = self._encode_resident(ctx, flat, format, type, params)
+        if resident is None:
+            return False
+        hosts, texels, pays = resident
+        size = ctypes.sizeof(api.RdoStats)
+        stats = torch.empty(len(pays)*size, dtype=torch.uint8, device=pays[0].device)
+        ctx.rdo_device([dict(blocks=p.data_ptr(), out=p.data_ptr(), out_capacity=p.numel(), pixels=t.data_ptr(),
+                             pixel_type=int(api.pixel_type_of(h)), width=h.shape[1], height=h.shape[0],
+                             row_pitch_bytes=h.strides[0]) for h, t, p in zip(hosts, texels, pays)],
+                       format, type, rdo_lambda, stats.data_ptr(), max_sse_increase=max_sse_increase, mask=mask)
+        raw = stats.cpu().numpy().tobytes()
+        self._adopt([p.cpu().numpy() for p in pays], format, type, alpha_type, color_mask)
+        self._rdo_stats = [api.RdoStats.from_buffer_copy(raw[i*size:(i + 1)*size]).as_dict() for i in range(len(pays))]
+        return True
+
+    def rdo_stats(self):
+        """The statistics of the last convert_rdo(), one dict per surface in (mip, depth, face) order; None before
+        the first one."""
+        return self._rdo_stats
+
     def convert_and_compare(self, format: Format, type: Type, quality: Quality = Quality.Normal,
                             alpha_type: Alpha = Alpha.Standard,
                             color_mask: Sequence[bool] = (True, True, True, True), ssim: bool = True):
@@ -802,7 +882,6 @@ class Texture:
         False for it (ValueError, raised before any work).
         There is no strip pipeline here: the whole texture -- images, payloads and the compare's scratch -- is
         resident on the device during the call."""
-        import torch
         if not self.images_complete() or not self.is_format_valid(format, type):
             return None
         format, type = Format(format), Type(type)
@@ -824,30 +903,13 @@ class Texture:
             raise ValueError("compare: no channel compared")
         params = api.make_params(format, type, quality, alpha_type, color_mask, self._color_space)
         ctx = self._context()
-        dev = "cuda:%d" % self._device_id
-        hosts = [np.ascontiguousarray(im) for im in flat]
-        texels = [torch.from_numpy(h).to(dev) for h in hosts]
-        size = api.pvrtc_payload_size if pvrtc else api.payload_size
-        try:
-            pays = [torch.empty(size(format, type, h.shape[1], h.shape[0]), dtype=torch.uint8, device=dev) for h in hosts]
-            surfaces = [dict(pixels=t.data_ptr(), pixel_type=int(api.pixel_type_of(h)), width=h.shape[1],
-                             height=h.shape[0], row_pitch_bytes=h.strides[0], out=p.data_ptr(), out_capacity=p.numel())
-                        for h, t, p in zip(hosts, texels, pays)]
-            # one call per pixel type, as transcode() encodes
-            for pt in sorted({s["pixel_type"] for s in surfaces}):
-                group = [s for s in surfaces if s["pixel_type"] == pt]
-                (ctx.encode_pvrtc_device if pvrtc else ctx.encode_device)(group, params)
-        except api.CfhipError as e:
-            if e.code == api.E_UNSUPPORTED:
-                return None
-            raise
+        resident = self._encode_resident(ctx, flat, format, type, params)
+        if resident is None:
+            return None
+        hosts, texels, pays = resident
         items = [(p, t, api.pixel_type_of(h), h.shape[1], h.shape[0]) for h, t, p in zip(hosts, texels, pays)]
         results = self._measure_device(ctx, format, type, items, mask, ssim)
-        it = iter([p.cpu().numpy() for p in pays])
-        self._textures = [[[next(it) for _ in dep] for dep in level] for level in self._images]
-        self._images = [[[None]*len(dep) for dep in level] for level in self._images]
-        self._format, self._type = format, type
-        self._alpha, self._mask = Alpha(alpha_type), tuple(bool(m) for m in color_mask)
+        self._adopt([p.cpu().numpy() for p in pays], format, type, alpha_type, color_mask)
         if pvrtc:
             chans = [c for c in range(4) if mask[c]]
             return results, self._pooled_pvrtc(results, sum(h.shape[0]*h.shape[1] for h in hosts), chans)

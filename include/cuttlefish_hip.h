@@ -570,6 +570,60 @@ int cfhip_compare_batch_device(cfhip_ctx* ctx, int format, int type, const cfhip
 	size_t n_surfaces, int ref_pixel_type, const uint8_t mask_rgba[4], unsigned flags,
 	cfhip_compare_result* results_device, void* stream);
 
+/* ---- Rate-distortion optimisation of BC1-5 / BC7 payloads ----
+ *
+ * A post-pass over an encoded payload: byte ranges of some blocks are overwritten by the same byte range of one of
+ * the 16 blocks before them in the same segment (64 blocks) of their block row, so that a deflate-class compressor
+ * finds matches.  Per block, candidate 0 is the block as encoded and every other candidate one splice of the
+ * format's table taken from one distance d = 1..16; the pass keeps the first minimum of
+ *   J = 16 SSE + round(16 lambda) R
+ * where SSE is the integer squared error of the decoded candidate against the source as RGBA8 (floats quantised as
+ * the encoders quantise them: round(clamp(f) * 255), NaN 0) over the channels the format stores AND mask_rgba
+ * (BC1_RGB stores no alpha) and the texels inside the surface, and R its model rate in bits: 8 BS for the block as
+ * encoded, 8 (BS - n) + 12 + 2 floor(log2(d BS)) for a splice of n bytes (BS: bytes of a block).  Only candidates
+ * with SSE <= SSE(candidate 0) + max_sse_increase take part (0xFFFFFFFF: no cap); a candidate the decoder counts
+ * as an error block (BC7's reserved mode) never does.  Blocks are taken left to right and copy from FINAL blocks.
+ * Supported: BC1_RGB, BC1_RGBA, BC2, BC3, BC4, BC5 and BC7, type UNorm; every other pair is CFHIP_E_UNSUPPORTED.
+ * All surfaces of a call share format, type, parameters and mask, and one launch.  The statistics are integer
+ * sums: identical calls return identical bits.  n == 0 is CFHIP_OK and does nothing.  Every argument of every
+ * surface is checked before anything is enqueued (and before ctx is looked at: a NULL ctx is reported last). */
+typedef struct cfhip_rdo_params {
+	float lambda;               /* 0 < lambda <= 1024, else CFHIP_E_INVALID */
+	uint32_t max_sse_increase;  /* per block; 0xFFFFFFFF = no cap */
+	uint32_t reserved[2];       /* must be 0 */
+} cfhip_rdo_params;
+
+typedef struct cfhip_rdo_surface {
+	const void* blocks;         /* payload of this surface as encoded */
+	size_t blocks_bytes;        /* host form: >= its payload size; device form: ignored */
+	void* out;                  /* the optimised payload; may equal blocks (in place), must not overlap it otherwise */
+	size_t out_capacity;        /* >= the payload size, else CFHIP_E_CAPACITY */
+	uint32_t width, height;
+	const void* pixels;         /* the source the payload was encoded from: width x height texels */
+	int pixel_type;             /* cfhip_pixel_type */
+	size_t row_pitch_bytes;     /* >= width * bytes per texel */
+} cfhip_rdo_surface;
+
+typedef struct cfhip_rdo_stats {
+	uint64_t blocks, blocks_changed;  /* blocks of the surface; those whose bytes differ from the input */
+	uint64_t sse_before, sse_after;   /* summed over the blocks, as defined above */
+	uint64_t bits_before, bits_after; /* model rate R summed over the blocks */
+} cfhip_rdo_stats;
+
+/* 1 for the (format, type) pairs of the table above, else 0.  Pure, needs no device. */
+int cfhip_rdo_supported(int format, int type);
+
+/* Host buffers; stats: n_surfaces entries.  Blocking. */
+int cfhip_rdo(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n_surfaces,
+	const cfhip_rdo_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats);
+
+/* Device buffers: `surfaces` is a host array of device pointers (pixels and their pitch aligned to the texel size);
+ * stats_device: n_surfaces cfhip_rdo_stats on the device, 8-byte aligned, overwritten.  params and mask_rgba are
+ * host memory.  stream NULL = the context's stream, and the call then synchronises; on a caller's stream it
+ * returns once the work is queued. */
+int cfhip_rdo_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n_surfaces,
+	const cfhip_rdo_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats_device, void* stream);
+
 /* ---- PVRTC1 4 bpp (formats 59 RGB, 60 RGBA; type UNorm) ----
  *
  * PVRTC1 is outside the cfhip_surface block contract: blocks are stored in twiddled (Morton) order, a level is never
@@ -656,7 +710,7 @@ int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* p
 	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_* or cfhip_image_ops_device call on
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* or cfhip_image_ops_device call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
