@@ -192,7 +192,8 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_std_unpack", "cfhip_std_unpack_device", "cfhip_std_compare", "cfhip_std_compare_device",
            "cfhip_decode_batch", "cfhip_decode_batch_device", "cfhip_decode_out_supported",
            "cfhip_compare_batch", "cfhip_compare_batch_device",
-           "cfhip_rdo_supported", "cfhip_rdo", "cfhip_rdo_device"]
+           "cfhip_rdo_supported", "cfhip_rdo", "cfhip_rdo_device",
+           "cfhip_rdo_ex", "cfhip_rdo_ex_device"]
 
 
 class Layout(enum.IntEnum):
@@ -302,6 +303,12 @@ class RdoParams(ctypes.Structure):
     _fields_ = [("lam", ctypes.c_float), ("max_sse_increase", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
 
 
+class RdoExParams(ctypes.Structure):
+    """struct cfhip_rdo_ex_params"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("lam", ctypes.c_float), ("max_sse_increase", ctypes.c_uint32),
+                ("flags", ctypes.c_uint32), ("window_bytes", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
 class RdoSurface(ctypes.Structure):
     """struct cfhip_rdo_surface"""
     _fields_ = [("blocks", ctypes.c_void_p), ("blocks_bytes", ctypes.c_size_t), ("out", ctypes.c_void_p),
@@ -319,6 +326,7 @@ class RdoStats(ctypes.Structure):
 
 
 RDO_NO_CAP = 0xFFFFFFFF         # max_sse_increase: no cap
+RDO_ROW_ABOVE = 1               # CFHIP_RDO_ROW_ABOVE
 
 DECODE_NATIVE = -1              # CFHIP_DECODE_NATIVE
 # output texel (channels, dtype) of a batched decode to a pixel type
@@ -522,6 +530,13 @@ def load_library(path: Optional[str] = None):
     L.cfhip_rdo_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RdoSurface),
                                    ctypes.c_size_t, ctypes.POINTER(RdoParams), u8p, ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_rdo_device.restype = ctypes.c_int
+    L.cfhip_rdo_ex.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RdoSurface), ctypes.c_size_t,
+                               ctypes.POINTER(RdoExParams), u8p, ctypes.c_void_p]
+    L.cfhip_rdo_ex.restype = ctypes.c_int
+    L.cfhip_rdo_ex_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RdoSurface),
+                                      ctypes.c_size_t, ctypes.POINTER(RdoExParams), u8p, ctypes.c_void_p,
+                                      ctypes.c_void_p]
+    L.cfhip_rdo_ex_device.restype = ctypes.c_int
     L.cfhip_decode_out_supported.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.cfhip_decode_out_supported.restype = ctypes.c_int
     _lib = L
@@ -589,6 +604,19 @@ def make_rdo_params(lam: float, max_sse_increase: Optional[int] = None) -> RdoPa
     p = RdoParams()
     p.lam = float(lam)
     p.max_sse_increase = RDO_NO_CAP if max_sse_increase is None else int(max_sse_increase)
+    return p
+
+
+def make_rdo_ex_params(lam: float, max_sse_increase: Optional[int] = None, row_above: bool = False,
+                       window_bytes: Optional[int] = None) -> RdoExParams:
+    """cfhip_rdo_ex_params: row_above lets a block copy from the block row above; window_bytes is the compressor's
+    window (None: deflate's 32768)."""
+    p = RdoExParams()
+    p.struct_size = ctypes.sizeof(RdoExParams)
+    p.lam = float(lam)
+    p.max_sse_increase = RDO_NO_CAP if max_sse_increase is None else int(max_sse_increase)
+    p.flags = RDO_ROW_ABOVE if row_above else 0
+    p.window_bytes = 0 if window_bytes is None else int(window_bytes)
     return p
 
 
@@ -1041,16 +1069,19 @@ class Context:
             ctypes.c_void_p(int(results)) if results else None, ctypes.c_void_p(stream) if stream else None))
 
     def rdo(self, payloads: Sequence[np.ndarray], sources: Sequence[np.ndarray], fmt, typ=Type.UNorm, lam: float = 1.0,
-            max_sse_increase: Optional[int] = None, mask=None):
+            max_sse_increase: Optional[int] = None, mask=None, row_above: bool = False,
+            window_bytes: Optional[int] = None):
         """Rate-distortion optimisation of encoded payloads (cfhip_rdo): payloads[i] was encoded from sources[i],
         an (h, w, 4) uint8, float16 or float32 array.  Blocks are rewritten to copy byte ranges from the blocks before
         them where J = 16 SSE + round(16 lam) R falls (see include/cuttlefish_hip.h), no block's SSE rising by more
-        than max_sse_increase (None: no cap).  All surfaces share one launch.  Returns (the optimised payloads, one
+        than max_sse_increase (None: no cap).  All surfaces share one launch.  row_above: blocks may also copy from
+        the block row above, on surfaces where that row lies within window_bytes (None: 32768) of the payload; either
+        of the two arguments sends the call through cfhip_rdo_ex.  Returns (the optimised payloads, one
         dict of statistics per surface: blocks, blocks_changed, sse_before, sse_after, bits_before, bits_after)."""
         n = len(payloads)
         if len(sources) != n:
             raise ValueError("payloads and sources must list the same surfaces")
-        params = make_rdo_params(lam, max_sse_increase)
+        entry, params = self._rdo_entry(False, lam, max_sse_increase, row_above, window_bytes)
         surf = (RdoSurface*max(n, 1))()
         srcs = [np.ascontiguousarray(s) for s in sources]
         if any(s.ndim != 3 or s.shape[2] != 4 for s in srcs):
@@ -1063,17 +1094,25 @@ class Context:
             surf[i].height, surf[i].width = s.shape[:2]
             surf[i].pixels, surf[i].pixel_type, surf[i].row_pitch_bytes = s.ctypes.data, int(pixel_type_of(s)), s.strides[0]
         stats = (RdoStats*max(n, 1))()
-        self._check(self._lib.cfhip_rdo(self._h, int(fmt), int(typ), surf, n, ctypes.byref(params), self._mask(mask),
-                                        ctypes.addressof(stats)))
+        self._check(entry(self._h, int(fmt), int(typ), surf, n, ctypes.byref(params), self._mask(mask),
+                          ctypes.addressof(stats)))
         return outs, [stats[i].as_dict() for i in range(n)]
 
+    def _rdo_entry(self, device: bool, lam, max_sse_increase, row_above, window_bytes):
+        """(the entry point, its parameters): the plain entry unless an option of cfhip_rdo_ex_params is given"""
+        if row_above or window_bytes is not None:
+            entry = self._lib.cfhip_rdo_ex_device if device else self._lib.cfhip_rdo_ex
+            return entry, make_rdo_ex_params(lam, max_sse_increase, row_above, window_bytes)
+        return (self._lib.cfhip_rdo_device if device else self._lib.cfhip_rdo), make_rdo_params(lam, max_sse_increase)
+
     def rdo_device(self, surfaces: Sequence[dict], fmt, typ, lam: float, stats: int,
-                   max_sse_increase: Optional[int] = None, mask=None, stream: int = 0):
+                   max_sse_increase: Optional[int] = None, mask=None, stream: int = 0, row_above: bool = False,
+                   window_bytes: Optional[int] = None):
         """Device path of rdo.  surfaces: dicts with blocks, out, pixels (device pointers as ints; out may equal
         blocks), out_capacity, width, height, pixel_type and row_pitch_bytes.  stats: device pointer to
         len(surfaces) cfhip_rdo_stats (overwritten).  stream 0 = the context's stream (the call then synchronises)."""
         n = len(surfaces)
-        params = make_rdo_params(lam, max_sse_increase)
+        entry, params = self._rdo_entry(True, lam, max_sse_increase, row_above, window_bytes)
         surf = (RdoSurface*max(n, 1))()
         for i, s in enumerate(surfaces):
             surf[i].blocks, surf[i].out = int(s["blocks"]) or None, int(s["out"]) or None
@@ -1081,7 +1120,7 @@ class Context:
             surf[i].width, surf[i].height = s["width"], s["height"]
             surf[i].pixels, surf[i].pixel_type = int(s["pixels"]) or None, int(s["pixel_type"])
             surf[i].row_pitch_bytes = s["row_pitch_bytes"]
-        self._check(self._lib.cfhip_rdo_device(
+        self._check(entry(
             self._h, int(fmt), int(typ), surf, n, ctypes.byref(params), self._mask(mask),
             ctypes.c_void_p(int(stats)) if stats else None, ctypes.c_void_p(stream) if stream else None))
 

@@ -2915,31 +2915,49 @@ struct RdoPlan {
 	std::vector<cfrdo_entry> entries;         // blocks / out / pixels still the caller's pointers
 	std::vector<size_t> payload, texel;       // payload bytes; bytes of a source texel
 	uint32_t total_seg;
+	bool row_above;                           // CFHIP_RDO_ROW_ABOVE: the 2-D kernel, one wavefront per tile
+	uint32_t total_tile;
 };
 
 // Every check of an RDO call, made before the context is touched (so that they need no device).  ctx may be NULL
-// here; the caller rejects that afterwards.
+// here; the caller rejects that afterwards.  The parameters come as params (cfhip_rdo*) or as ex (cfhip_rdo_ex*).
 static int rdo_check(cfhip_ctx* ctx, const char* what, int format, int type, const cfhip_rdo_surface* s, size_t n,
-	const cfhip_rdo_params* params, const uint8_t* mask, const void* stats, bool host, RdoPlan* p)
+	const cfhip_rdo_params* params, const cfhip_rdo_ex_params* ex, const uint8_t* mask, const void* stats, bool host,
+	RdoPlan* p)
 {
 	p->row = cfrdo_find_row(format, type);
 	if (p->row < 0)
 		return fail(ctx, CFHIP_E_UNSUPPORTED, "%s: (format %d, type %d) is outside the RDO table", what, format, type);
-	p->total_seg = 0;
+	p->total_seg = p->total_tile = 0;
+	p->row_above = false;
 	if (!n)
 		return CFHIP_OK;
-	if (!s || !params || !stats)
+	if (!s || !(params || ex) || !stats)
 		return fail(ctx, CFHIP_E_INVALID, "%s: surfaces, params or stats is NULL", what);
-	if (!(params->lambda > 0.0f && params->lambda <= 1024.0f))
-		return fail(ctx, CFHIP_E_INVALID, "%s: lambda %g is outside (0, 1024]", what, (double)params->lambda);
-	if (params->reserved[0] || params->reserved[1])
+	if (ex && ex->struct_size != sizeof(cfhip_rdo_ex_params))
+		return fail(ctx, CFHIP_E_INVALID, "%s: struct_size %u is not %zu", what, ex->struct_size, sizeof(cfhip_rdo_ex_params));
+	const float lambda = ex ? ex->lambda : params->lambda;
+	if (!(lambda > 0.0f && lambda <= 1024.0f))
+		return fail(ctx, CFHIP_E_INVALID, "%s: lambda %g is outside (0, 1024]", what, (double)lambda);
+	uint32_t window = 32768u;
+	if (ex) {
+		if (ex->flags & ~CFHIP_RDO_ROW_ABOVE)
+			return fail(ctx, CFHIP_E_INVALID, "%s: unknown flags 0x%x", what, ex->flags);
+		if (ex->window_bytes && (ex->window_bytes < 64u || ex->window_bytes > (1u << 30)))
+			return fail(ctx, CFHIP_E_INVALID, "%s: window_bytes %u is outside 64 .. 2^30", what, ex->window_bytes);
+		if (ex->reserved[0] || ex->reserved[1] || ex->reserved[2])
+			return fail(ctx, CFHIP_E_INVALID, "%s: reserved parameters must be 0", what);
+		p->row_above = (ex->flags & CFHIP_RDO_ROW_ABOVE) != 0;
+		if (ex->window_bytes)
+			window = ex->window_bytes;
+	} else if (params->reserved[0] || params->reserved[1])
 		return fail(ctx, CFHIP_E_INVALID, "%s: reserved parameters must be 0", what);
 	if (n > 0xFFFFFFu)
 		return fail(ctx, CFHIP_E_INVALID, "%s: too many surfaces (%zu)", what, n);
 	if ((uintptr_t)stats % 8u != 0)
 		return fail(ctx, CFHIP_E_INVALID, "%s: stats must be 8-byte aligned", what);
-	p->lam16 = (uint32_t)std::floor((double)params->lambda*16.0 + 0.5);
-	p->cap = params->max_sse_increase;
+	p->lam16 = (uint32_t)std::floor((double)lambda*16.0 + 0.5);
+	p->cap = ex ? ex->max_sse_increase : params->max_sse_increase;
 	unsigned m = 15u;
 	if (mask)
 		m = (mask[0] ? 1u : 0u) | (mask[1] ? 2u : 0u) | (mask[2] ? 4u : 0u) | (mask[3] ? 8u : 0u);
@@ -2948,7 +2966,7 @@ static int rdo_check(cfhip_ctx* ctx, const char* what, int format, int type, con
 	p->entries.resize(n);
 	p->payload.resize(n);
 	p->texel.resize(n);
-	uint64_t segs = 0;
+	uint64_t segs = 0, tiles = 0;
 	for (size_t i = 0; i < n; ++i) {
 		if (!s[i].blocks || !s[i].out || !s[i].pixels)
 			return fail(ctx, CFHIP_E_INVALID, "%s: surface %zu: blocks, out or pixels is NULL", what, i);
@@ -2985,11 +3003,15 @@ static int rdo_check(cfhip_ctx* ctx, const char* what, int format, int type, con
 		e.vec = 0;
 		p->payload[i] = bytes;
 		p->texel[i] = tb;
+		e.tile_begin = (uint32_t)tiles;
+		e.up = p->row_above && ((uint64_t)bx + CFRDO_UP/2)*(uint64_t)row.block_bytes <= window ? 1u : 0u;
 		segs += (uint64_t)e.segx*by;
+		tiles += (uint64_t)e.segx*((by + CFRDO_TILE_ROWS - 1u)/CFRDO_TILE_ROWS);
 		if (segs > 0x7FFFFFFFull)
 			return fail(ctx, CFHIP_E_INVALID, "%s: the surfaces are too large for one launch", what);
 	}
 	p->total_seg = (uint32_t)segs;
+	p->total_tile = (uint32_t)tiles;
 	return CFHIP_OK;
 }
 
@@ -3003,7 +3025,7 @@ static int rdo_launch(cfhip_ctx* ctx, StagingLease& lease, RdoPlan& p, cfhip_rdo
 		ctx->events_used = 0;
 	ctx->events_stream = stream;
 	ctx->last_ms = -1.0f;
-	ctx->last_kernel = "cfhip_rdo_kernel";
+	ctx->last_kernel = p.row_above ? "cfhip_rdo2d_kernel" : "cfhip_rdo_kernel";
 	const size_t n = p.entries.size();
 	const size_t bb = (size_t)kCfrdoRows[p.row].block_bytes;
 	for (cfrdo_entry& e : p.entries)
@@ -3021,8 +3043,11 @@ static int rdo_launch(cfhip_ctx* ctx, StagingLease& lease, RdoPlan& p, cfhip_rdo
 	if (rc != CFHIP_OK)
 		return rc;
 	HIP_TRY(ctx, hipEventRecord(a, stream));
-	const hipError_t e = cfhip_launch_rdo(p.row, static_cast<const cfrdo_entry*>(ctx->d_batch), (uint32_t)n, p.total_seg,
-		p.lam16, p.cap, p.cmask, reinterpret_cast<unsigned long long*>(stats), stream);
+	const cfrdo_entry* table = static_cast<const cfrdo_entry*>(ctx->d_batch);
+	unsigned long long* counters = reinterpret_cast<unsigned long long*>(stats);
+	const hipError_t e = p.row_above
+		? cfhip_launch_rdo2d(p.row, table, (uint32_t)n, p.total_tile, p.lam16, p.cap, p.cmask, counters, stream)
+		: cfhip_launch_rdo(p.row, table, (uint32_t)n, p.total_seg, p.lam16, p.cap, p.cmask, counters, stream);
 	if (e != hipSuccess)
 		return fail(ctx, CFHIP_E_DEVICE, "rdo launch: %s", hipGetErrorString(e));
 	HIP_TRY(ctx, hipEventRecord(b, stream));
@@ -3034,8 +3059,9 @@ int cfhip_rdo_supported(int format, int type)
 	return cfrdo_find_row(format, type) >= 0 ? 1 : 0;
 }
 
-int cfhip_rdo(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
-	const cfhip_rdo_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats)
+// cfhip_rdo and cfhip_rdo_ex: one of params and ex is the caller's
+static int rdo_host(cfhip_ctx* ctx, const char* what, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
+	const cfhip_rdo_params* params, const cfhip_rdo_ex_params* ex, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats)
 {
 	std::unique_lock<std::mutex> guard;
 	if (ctx) {
@@ -3043,7 +3069,7 @@ int cfhip_rdo(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* sur
 		ctx->error.clear();
 	}
 	RdoPlan p;
-	int rc = rdo_check(ctx, "rdo", format, type, surfaces, n, params, mask_rgba, stats, true, &p);
+	int rc = rdo_check(ctx, what, format, type, surfaces, n, params, ex, mask_rgba, stats, true, &p);
 	if (rc != CFHIP_OK || !n)
 		return rc;
 	if (!ctx)
@@ -3101,8 +3127,10 @@ int cfhip_rdo(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* sur
 	return CFHIP_OK;
 }
 
-int cfhip_rdo_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
-	const cfhip_rdo_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats_device, void* stream_)
+// cfhip_rdo_device and cfhip_rdo_ex_device
+static int rdo_device(cfhip_ctx* ctx, const char* what, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
+	const cfhip_rdo_params* params, const cfhip_rdo_ex_params* ex, const uint8_t mask_rgba[4],
+	cfhip_rdo_stats* stats_device, void* stream_)
 {
 	std::unique_lock<std::mutex> guard;
 	if (ctx) {
@@ -3110,7 +3138,7 @@ int cfhip_rdo_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surfa
 		ctx->error.clear();
 	}
 	RdoPlan p;
-	int rc = rdo_check(ctx, "rdo_device", format, type, surfaces, n, params, mask_rgba, stats_device, false, &p);
+	int rc = rdo_check(ctx, what, format, type, surfaces, n, params, ex, mask_rgba, stats_device, false, &p);
 	if (rc != CFHIP_OK || !n)
 		return rc;
 	if (!ctx)
@@ -3122,6 +3150,30 @@ int cfhip_rdo_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surfa
 	if (rc != CFHIP_OK)
 		return rc;
 	return lease.done(!stream_);
+}
+
+int cfhip_rdo(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
+	const cfhip_rdo_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats)
+{
+	return rdo_host(ctx, "rdo", format, type, surfaces, n, params, nullptr, mask_rgba, stats);
+}
+
+int cfhip_rdo_ex(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
+	const cfhip_rdo_ex_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats)
+{
+	return rdo_host(ctx, "rdo_ex", format, type, surfaces, n, nullptr, params, mask_rgba, stats);
+}
+
+int cfhip_rdo_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
+	const cfhip_rdo_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats_device, void* stream_)
+{
+	return rdo_device(ctx, "rdo_device", format, type, surfaces, n, params, nullptr, mask_rgba, stats_device, stream_);
+}
+
+int cfhip_rdo_ex_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
+	const cfhip_rdo_ex_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats_device, void* stream_)
+{
+	return rdo_device(ctx, "rdo_ex_device", format, type, surfaces, n, nullptr, params, mask_rgba, stats_device, stream_);
 }
 
 } // extern "C"

@@ -825,13 +825,15 @@ class Texture:
     def convert_rdo(self, format: Format, type: Type, quality: Quality = Quality.Normal,
                     alpha_type: Alpha = Alpha.Standard,
                     color_mask: Sequence[bool] = (True, True, True, True), rdo_lambda: float = 1.0,
-                    max_sse_increase: Optional[int] = None) -> bool:
+                    max_sse_increase: Optional[int] = None, row_above: bool = False,
+                    window_bytes: Optional[int] = None) -> bool:
         """convert(), then the rate-distortion pass (Context.rdo_device) over the fresh payloads against the texels
         they were encoded from, in one visit to the device: every image is uploaded once, encoded from there,
         optimised in place, and only the final payloads and the statistics (rdo_stats()) come back.  The channels
         the pass measures are compare()'s: the colour mask's, without alpha when the alpha type is None.  Returns
         False wherever convert() does and for the formats the pass does not cover (api.rdo_supported); the texture
-        is then left unconverted.  A lambda outside (0, 1024] raises api.CfhipError."""
+        is then left unconverted.  A lambda outside (0, 1024] raises api.CfhipError.  row_above and window_bytes are
+        Context.rdo's: blocks may also copy from the block row above."""
         import ctypes
         import torch
         if not self.images_complete() or not self.is_format_valid(format, type):
@@ -857,7 +859,8 @@ class Texture:
         ctx.rdo_device([dict(blocks=p.data_ptr(), out=p.data_ptr(), out_capacity=p.numel(), pixels=t.data_ptr(),
                              pixel_type=int(api.pixel_type_of(h)), width=h.shape[1], height=h.shape[0],
                              row_pitch_bytes=h.strides[0]) for h, t, p in zip(hosts, texels, pays)],
-                       format, type, rdo_lambda, stats.data_ptr(), max_sse_increase=max_sse_increase, mask=mask)
+                       format, type, rdo_lambda, stats.data_ptr(), max_sse_increase=max_sse_increase, mask=mask,
+                       row_above=row_above, window_bytes=window_bytes)
         raw = stats.cpu().numpy().tobytes()
         self._adopt([p.cpu().numpy() for p in pays], format, type, alpha_type, color_mask)
         self._rdo_stats = [api.RdoStats.from_buffer_copy(raw[i*size:(i + 1)*size]).as_dict() for i in range(len(pays))]

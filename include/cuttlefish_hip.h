@@ -624,6 +624,36 @@ int cfhip_rdo(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* sur
 int cfhip_rdo_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n_surfaces,
 	const cfhip_rdo_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats_device, void* stream);
 
+/* The pass with options.  flags == 0 returns exactly what cfhip_rdo / cfhip_rdo_device return.
+ *
+ * CFHIP_RDO_ROW_ABOVE: a block may also copy from the block row above (2-D lookback).  A surface is cut into tiles
+ * of 64 blocks x 8 block rows, counted from its top-left corner; tiles are independent, and inside a tile rows are
+ * taken top to bottom, blocks left to right.  A block at position i of its segment, not in the first row of its tile,
+ * has 8 more sources: the FINAL blocks at positions i + dx, dx = -4..3, of the row above in the same tile (those
+ * that exist), each with every splice of the format's table.  These candidates follow the 16 S of the plain pass, in
+ * the order (dx, splice), and cost R = 8 (BS - n) + 12 + 2 floor(log2((bx - dx) BS)) bits, bx the blocks of a row of
+ * the surface: the distance of the match in the payload.  Everything else is the plain pass: J, the first minimum,
+ * the cap, the error-block rule, the mask, the statistics.  A surface whose row above lies outside the compressor's
+ * window, (bx + 4) BS > window_bytes, gets the plain pass's result.  Surfaces with and without share the one launch. */
+#define CFHIP_RDO_ROW_ABOVE 1u
+
+typedef struct cfhip_rdo_ex_params {
+	uint32_t struct_size;       /* sizeof(cfhip_rdo_ex_params), else CFHIP_E_INVALID */
+	float lambda;               /* as cfhip_rdo_params */
+	uint32_t max_sse_increase;  /* as cfhip_rdo_params */
+	uint32_t flags;             /* CFHIP_RDO_*; unknown bits are CFHIP_E_INVALID */
+	uint32_t window_bytes;      /* the compressor's window: 0 = 32768 (deflate), else 64 .. 2^30 */
+	uint32_t reserved[3];       /* must be 0 */
+} cfhip_rdo_ex_params;
+
+/* cfhip_rdo with cfhip_rdo_ex_params: same buffers, same checks, the params' fields checked in their order. */
+int cfhip_rdo_ex(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n_surfaces,
+	const cfhip_rdo_ex_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats);
+
+/* cfhip_rdo_device with cfhip_rdo_ex_params. */
+int cfhip_rdo_ex_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n_surfaces,
+	const cfhip_rdo_ex_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats_device, void* stream);
+
 /* ---- PVRTC1 4 bpp (formats 59 RGB, 60 RGBA; type UNorm) ----
  *
  * PVRTC1 is outside the cfhip_surface block contract: blocks are stored in twiddled (Morton) order, a level is never

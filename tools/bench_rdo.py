@@ -9,7 +9,12 @@ warm-up round, with spread = max - min.  Times are cfhip_last_kernel_ms (hipEven
 rdo_best / encode_best.  The row also carries the pass's statistics and the library's segment length, so that rows
 of libraries built with another CFRDO_SEG (CFHIP_LIB=...) can be told apart: pass --seg to label them.
 
-    python tools/bench_rdo.py [--steps 8] [--size 4096] [--seg 64] [--out profiles/rdo_bench.jsonl]
+--row-above adds the pass with copies from the block row above (cfhip_rdo2d_kernel) as a third kernel of the
+alternation: rdo2d_ms_best / _spread, its ratio to the plain pass and to the encode, and its statistics.  Label a
+library built with another CFRDO_TILE_ROWS with --tile-rows.
+
+    python tools/bench_rdo.py [--steps 8] [--size 4096] [--seg 64] [--row-above [--tile-rows 8]]
+                              [--out profiles/rdo_bench.jsonl]
 """
 import argparse
 import ctypes
@@ -35,6 +40,8 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--size", type=int, default=4096)
     ap.add_argument("--seg", type=int, default=64, help="label: CFRDO_SEG of the library under test")
+    ap.add_argument("--row-above", action="store_true", help="also time the pass with copies from the row above")
+    ap.add_argument("--tile-rows", type=int, default=8, help="label: CFRDO_TILE_ROWS of the library under test")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "rdo_bench.jsonl"))
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
@@ -65,12 +72,23 @@ def main():
                 def rdo():
                     ctx.rdo_device(rdo_surface, fmt, Type.UNorm, lam, stats.data_ptr())
                     return ctx.last_kernel_ms()
+
+                def rdo2d():
+                    ctx.rdo_device(rdo_surface, fmt, Type.UNorm, lam, stats.data_ptr(), row_above=True)
+                    return ctx.last_kernel_ms()
                 torch.cuda.synchronize()                          # torch's fills run on its own stream
-                encode(), rdo()                                   # warm-up round
-                runs = {"encode": [], "rdo": []}
+                kernels = {"encode": encode, "rdo": rdo}
+                if args.row_above:
+                    kernels["rdo2d"] = rdo2d
+                for k in kernels.values():                        # warm-up round
+                    k()
+                runs = {name: [] for name in kernels}
                 for _ in range(args.steps):
-                    runs["encode"].append(encode())
-                    runs["rdo"].append(rdo())
+                    for name, k in kernels.items():
+                        runs[name].append(k())
+                if args.row_above:
+                    st2d = api.RdoStats.from_buffer_copy(stats.cpu().numpy().tobytes()).as_dict()
+                    rdo()
                 st = api.RdoStats.from_buffer_copy(stats.cpu().numpy().tobytes()).as_dict()
                 row = {"format": fmt.name, "input": name, "size": n, "lambda": lam, "seg": args.seg, "steps": args.steps,
                        "encode_normal_ms_best": round(min(runs["encode"]), 4),
@@ -80,6 +98,11 @@ def main():
                 row["ratio"] = round(row["rdo_ms_best"]/row["encode_normal_ms_best"], 3)
                 row["gblocks_per_s"] = round(st["blocks"]/(row["rdo_ms_best"]*1e-3)/1e9, 3)
                 row["stats"] = st
+                if args.row_above:
+                    row.update({"tile_rows": args.tile_rows, "rdo2d_ms_best": round(min(runs["rdo2d"]), 4),
+                                "rdo2d_ms_spread": round(max(runs["rdo2d"]) - min(runs["rdo2d"]), 4), "stats_2d": st2d})
+                    row["rdo2d_over_rdo"] = round(row["rdo2d_ms_best"]/row["rdo_ms_best"], 3)
+                    row["rdo2d_over_encode"] = round(row["rdo2d_ms_best"]/row["encode_normal_ms_best"], 3)
                 print(json.dumps(row), flush=True)
                 lines.append(json.dumps(row))
                 del pay, out
