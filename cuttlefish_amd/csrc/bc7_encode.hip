@@ -31,6 +31,7 @@
 // (oracle/bc7_encode.c), so the payload is byte-identical to it.
 // Build with -ffp-contract=off: fused ops are written as explicit fmaf().
 #include "cf_device.h"
+#include "bc7_packed.h"
 
 namespace {
 
@@ -142,11 +143,6 @@ __device__ __forceinline__ float clamp255(float x)
 	return x < 0.0f ? 0.0f : (x > 255.0f ? 255.0f : x);
 }
 
-__device__ __forceinline__ uint32_t dequant(uint32_t v, uint32_t t)
-{
-	return ((v << (8u - t)) | (v >> (2u*t - 8u))) & 255u;
-}
-
 // BC7 interpolation weight k of an ib-bit index: ((k*64 + d/2)/d), d = 2^ib - 1
 __device__ __forceinline__ uint32_t bc7_weight(uint32_t ib, uint32_t k)
 {
@@ -194,11 +190,10 @@ __device__ __forceinline__ void quantize(const float (&x0)[4], const float (&x1)
 	const float H = pbk ? 0.5f : 1.0f;
 	const uint32_t Tc = cb + S, Ta = ab + S;
 	const float scc = cb ? sc_of(Tc) : 0.0f, sca = ab ? sc_of(Ta) : 0.0f;
-	const int qmc = (1 << cb) - 1, qma = (1 << ab) - 1;
-	const uint32_t shc = cb ? Tc : 8u, sha = ab ? Ta : 8u;   // dequant shifts (masked when not coded)
-	const uint32_t cmask = cb ? 255u : 0u, amask = ab ? 255u : 0u;
-	// [endpoint][p]
-	uint32_t q[2][2] = {{0, 0}, {0, 0}}, d[2][2] = {{0, 0}, {0, 0}};
+	const float qmc = (float)((1 << cb) - 1), qma = (float)((1 << ab) - 1);
+	const uint32_t tc = cb ? Tc : 0u, ta = ab ? Ta : 0u;
+	// [endpoint][p]: the fields and the dequantised bytes as whole words (bc7_packed.h)
+	uint32_t q[2][2], d[2][2];
 	float er[2][2];
 #pragma unroll
 	for (int e = 0; e < 2; ++e) {
@@ -206,24 +201,28 @@ __device__ __forceinline__ void quantize(const float (&x0)[4], const float (&x1)
 		for (int p = 0; p < 2; ++p) {
 			const uint32_t P = pbk ? (uint32_t)p : 0u;
 			const float Pf = (float)P;
-			float acc = 0.0f;
+			uint32_t qw = 0;
 #pragma unroll
 			for (int c = 0; c < 4; ++c) {
-				const uint32_t t = c < 3 ? shc : sha;
 				const float sc = c < 3 ? scc : sca;
-				const int qmax = c < 3 ? qmc : qma;
 				const float xv = e ? x1[c] : x0[c];
 				const float y = xv*sc;
 				const float u = (y - Pf)*H;
-				int qq = (int)floorf(u + 0.5f);
-				qq = qq < 0 ? 0 : (qq > qmax ? qmax : qq);
-				const uint32_t dd = dequant(((uint32_t)qq << S) | P, t) & (c < 3 ? cmask : amask);
-				const float dx = (float)dd - xv;
+				// clamped as a float (an integer below 256 either way), converted and inserted as byte c in one instruction
+				const float r = __builtin_amdgcn_fmed3f(floorf(u + 0.5f), 0.0f, c < 3 ? qmc : qma);
+				qw = __builtin_amdgcn_cvt_pk_u8_f32(r, (uint32_t)c, qw);
+			}
+			const uint32_t dw = dequant_word(code_word(qw, S, P), tc, ta);
+			float acc = 0.0f;
+#pragma unroll
+			for (int c = 0; c < 4; ++c) {
+				const float xv = e ? x1[c] : x0[c];
+				const float dx = fb(dw, c) - xv;
 				const float t2 = dx*dx;
 				acc = UNITW ? acc + t2 : fmaf((float)wt[c], t2, acc);
-				q[e][p] |= (uint32_t)qq << (8*c);
-				d[e][p] |= dd << (8*c);
 			}
+			q[e][p] = qw;
+			d[e][p] = dw;
 			er[e][p] = acc;
 		}
 	}
@@ -408,16 +407,16 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 		// an entry past 2^ib interpolates with weight 0: its colour stays a byte vector, so the
 		// dot products below stay in range and its constant keeps it from ever winning
 		const uint32_t w = bc7_weight(ib, valid ? kbase + (uint32_t)k : 0u), iw = 64u - w;
-		const uint32_t c0 = (__umul24(iw, e00) + __umul24(w, e10) + 32u) >> 6;
-		const uint32_t c1 = (__umul24(iw, e01) + __umul24(w, e11) + 32u) >> 6;
-		const uint32_t c2 = (__umul24(iw, e02) + __umul24(w, e12) + 32u) >> 6;
-		const uint32_t c3 = (__umul24(iw, e03) + __umul24(w, e13) + 32u) >> 6;
 		if (UNITW) {
-			pal[k] = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+			pal[k] = pal_word(fe0, fe1, w);     // two channels per multiply (bc7_packed.h)
 			palh[k] = 0;
 			base[k] = valid ? -(int)((__builtin_amdgcn_udot4(pal[k], pal[k], 0u, false) << 7) | w)
 				: -0x3FFFFFFF;
 		} else {
+			const uint32_t c0 = (__umul24(iw, e00) + __umul24(w, e10) + 32u) >> 6;
+			const uint32_t c1 = (__umul24(iw, e01) + __umul24(w, e11) + 32u) >> 6;
+			const uint32_t c2 = (__umul24(iw, e02) + __umul24(w, e12) + 32u) >> 6;
+			const uint32_t c3 = (__umul24(iw, e03) + __umul24(w, e13) + 32u) >> 6;
 			uint32_t qrg, qba;
 			ycc_pairs(c0, c1, c2, c3, qrg, qba);
 			// (wY Y, wCr Cr) and (wCb Cb, wA A), each <= 4080; an entry past 2^ib repeats entry 0's
@@ -550,29 +549,46 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 // clamped solution (quantize: p-bits and the centre of the search); every channel then takes, among the
 // 3 x 3 pairs of quantised values within one step of that centre, the pair that minimises the form
 // (end 0 outer, end 1 inner, -1, 0, +1; first minimum).  A value outside the field's range gets a
-// deviation of 1e18: its form value is +inf and never the minimum.
+// deviation of 1e18: its form value is +inf and never the minimum -- where the least-squares system was solvable.
+// In a lane whose system is singular A or C is 0, the sentinel's form value is not +inf and a candidate outside the
+// range can win; what such a lane returns is garbage and fit_lane discards it (`live`).
 __device__ __forceinline__ void refit_window(const float (&xu0)[4], const float (&xu1)[4], const float (&hq)[3],
 	uint32_t cb, uint32_t ab, uint32_t pbk, SubFit& f)
 {
 	const uint32_t S = pbk ? 1u : 0u;
 	const uint32_t P0 = f.pb & 1u, P1 = (f.pb >> 1) & 1u;
 	const float fA = hq[0], fC = hq[2], fB2 = hq[1] + hq[1];
-	uint32_t nq0 = 0, nq1 = 0, ne0 = 0, ne1 = 0;
+	const uint32_t tc = cb ? cb + S : 0u, ta = ab ? ab + S : 0u;
+	// The three candidates of every channel as whole words (bc7_packed.h).  q - 1: bit 7 lent to each colour byte
+	// (a colour field has at most 7 bits) so that a zero byte borrows from it and not from its neighbour; alpha is the
+	// top byte.  Masked to the field width, a candidate outside the range (below 0, above qmax) becomes some code
+	// inside it: its deviation is the sentinel and its bytes are never read.
+	const uint32_t qmaxw = ((1u << cb) - 1u)*0x010101u | (((1u << ab) - 1u) << 24);
+	const uint32_t lo0 = f.q0, lo1 = f.q1;                    // byte c == 0: the channel has no candidate below
+	const uint32_t hi0 = f.q0 ^ qmaxw, hi1 = f.q1 ^ qmaxw;    // byte c == 0: none above
+	uint32_t dw0[3], dw1[3];
+	dw0[0] = dequant_word(code_word(((f.q0 | 0x00808080u) - 0x01010101u) & qmaxw, S, P0), tc, ta);
+	dw0[1] = f.e0;
+	dw0[2] = dequant_word(code_word((f.q0 + 0x01010101u) & qmaxw, S, P0), tc, ta);
+	dw1[0] = dequant_word(code_word(((f.q1 | 0x00808080u) - 0x01010101u) & qmaxw, S, P1), tc, ta);
+	dw1[1] = f.e1;
+	dw1[2] = dequant_word(code_word((f.q1 + 0x01010101u) & qmaxw, S, P1), tc, ta);
+	uint32_t pick = 0;     // byte c: the chosen candidate of end 0 in bits 0..1, of end 1 in bits 4..5
 #pragma unroll
 	for (int c = 0; c < 4; ++c) {
-		const uint32_t bits = c < 3 ? cb : ab;
-		const uint32_t sh = bits ? bits + S : 8u, cmask = bits ? 255u : 0u, qmax = (1u << bits) - 1u;
-		const uint32_t qc0 = (f.q0 >> (8*c)) & 255u, qc1 = (f.q1 >> (8*c)) & 255u;
+		const uint32_t bm = 255u << (8*c);
 		float dl0[3], dl1[3];
 #pragma unroll
 		for (int d = 0; d < 3; ++d) {
-			const uint32_t q0 = qc0 + (uint32_t)d - 1u, q1 = qc1 + (uint32_t)d - 1u;   // wraps below zero: > qmax
-			const uint32_t d0 = dequant((q0 << S) | P0, sh) & cmask, d1 = dequant((q1 << S) | P1, sh) & cmask;
-			dl0[d] = q0 <= qmax ? (float)d0 - xu0[c] : 1.0e18f;
-			dl1[d] = q1 <= qmax ? (float)d1 - xu1[c] : 1.0e18f;
+			dl0[d] = fb(dw0[d], c) - xu0[c];
+			dl1[d] = fb(dw1[d], c) - xu1[c];
 		}
+		dl0[0] = (lo0 & bm) ? dl0[0] : 1.0e18f;
+		dl0[2] = (hi0 & bm) ? dl0[2] : 1.0e18f;
+		dl1[0] = (lo1 & bm) ? dl1[0] : 1.0e18f;
+		dl1[2] = (hi1 & bm) ? dl1[2] : 1.0e18f;
 		float best = 3.0e38f;
-		uint32_t bi = 4u;      // 3 i + j; the centre unless something is better (the centre is always valid)
+		uint32_t bi = 0x11u << (8*c);      // the centre unless something is better (the centre is always valid)
 #pragma unroll
 		for (int i = 0; i < 3; ++i) {
 			const float d0 = dl0[i];
@@ -587,16 +603,18 @@ __device__ __forceinline__ void refit_window(const float (&xu0)[4], const float 
 				v = fmaf(cr, d1, v);
 				const bool take = v < best;
 				best = take ? v : best;
-				bi = take ? (uint32_t)(3*i + j) : bi;
+				bi = take ? (uint32_t)(i | (j << 4)) << (8*c) : bi;
 			}
 		}
-		const uint32_t b0 = bi/3u, b1 = bi - 3u*b0;
-		const uint32_t q0 = qc0 + b0 - 1u, q1 = qc1 + b1 - 1u;
-		nq0 |= (q0 & 255u) << (8*c);
-		nq1 |= (q1 & 255u) << (8*c);
-		ne0 |= (dequant((q0 << S) | P0, sh) & cmask) << (8*c);
-		ne1 |= (dequant((q1 << S) | P1, sh) & cmask) << (8*c);
+		pick |= bi;
 	}
+	// q + pick - 1 per byte: every chosen candidate lies inside its field's range, so the word sum has no carry or borrow.
+	// (A singular lane may choose one outside it: the sum then carries or borrows into the neighbouring bytes, garbage
+	// that is discarded with the rest of that lane's result.)
+	const uint32_t nq0 = f.q0 + (pick & 0x03030303u) - 0x01010101u;
+	const uint32_t nq1 = f.q1 + ((pick >> 4) & 0x03030303u) - 0x01010101u;
+	const uint32_t ne0 = dequant_word(code_word(nq0, S, P0), tc, ta);
+	const uint32_t ne1 = dequant_word(code_word(nq1, S, P1), tc, ta);
 	f.q0 = nq0; f.q1 = nq1; f.e0 = ne0; f.e1 = ne1;
 }
 
@@ -1777,15 +1795,11 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 					}
 					LaneFit f;
 					f.q0 = nq0; f.q1 = nq1; f.pb = npb; f.err = 0;
-					uint32_t fe0 = 0, fe1 = 0;
-#pragma unroll
-					for (uint32_t c = 0; c < 4u; ++c) {
-						const uint32_t bc = c < 3u ? g.cb : g.ab;
-						if (bc) {       // (uniform per lane group of a fit; a select chain otherwise)
-							fe0 |= dequant((((nq0 >> (8u*c)) & 255u) << S) | (npb & S), bc + S) << (8u*c);
-							fe1 |= dequant((((nq1 >> (8u*c)) & 255u) << S) | ((npb >> 1) & S), bc + S) << (8u*c);
-						}
-					}
+					// (a move out of the field's range leaves a byte of 255 or 2^bits in nq0 / nq1, which the shift by S pushes into
+					// the neighbouring byte: such a lane is not `valid`, its key never wins and its endpoints are not stored)
+					const uint32_t tc = g.cb ? g.cb + S : 0u, ta = g.ab ? g.ab + S : 0u;
+					const uint32_t fe0 = dequant_word(code_word(nq0, S, npb & S), tc, ta);
+					const uint32_t fe1 = dequant_word(code_word(nq1, S, (npb >> 1) & S), tc, ta);
 #pragma unroll
 					for (int j = 0; j < 4; ++j) f.w[j] = 0;
 					float x0[4], x1[4], hq[3];
