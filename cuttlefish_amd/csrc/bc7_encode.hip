@@ -640,18 +640,28 @@ __device__ __forceinline__ uint32_t geo_src(uint32_t id, uint32_t fi, uint32_t w
 	return s & 63u;
 }
 
+// What part A's row loop produces, for a fit whose integer statistics are known beforehand: the packed moments of its
+// texels in its own (rotated, masked) channel slots (bc7_packed.h) and the extremes lo | hi << 8 of the rotated alpha
+// over the block.
+struct FitStats {
+	uint32_t W[CF_MOM_WORDS];
+	uint32_t lohi;
+};
+
 // scalar: the fit codes only the rotated alpha channel (modes 4/5 second plane); its start
 // endpoints are the exact extremes of that channel (oracle: fit_scalar).
 // frac: where the fit starts -- the extremes along the axis pulled in (positive) or pushed out by this
 // fraction of their distance (oracle: fitopt.start, cfo_start_frac; 0 = the extremes themselves).
 // gmode (wave-uniform): 0 computes parts A and B, 1 computes them and writes them to the lane's own column of
-// the geometry cache gbase, 2 reads them from column gsrc instead.  NK: palette entries of the selector search
+// the geometry cache gbase, 2 reads them from column gsrc instead, 3 (GIVEN instances only) is 1 with the integers of
+// part A handed in (gs: the first stream trip, whose fits' moments exist before the fit starts) instead of summed over
+// the rows.  NK: palette entries of the selector search
 // (assign_lsq_lane).  ITERS: refit rounds of the instance's quality level (one round is straight-line code: it asks
 // for no least-squares solution and its `live` is dead).
-template <bool UNITW, uint32_t ITERS, int NK = 8>
+template <bool UNITW, uint32_t ITERS, int NK = 8, bool GIVEN = false>
 __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, uint32_t khalf,
 	uint32_t cb, uint32_t ab, uint32_t pbk, uint32_t ib, const uint32_t (&wt)[4],
-	const uint32_t (&yw)[2], bool scalar, float frac, uint32_t* gbase, uint32_t gmode, uint32_t gsrc, LaneFit& best)
+	const uint32_t (&yw)[2], bool scalar, float frac, uint32_t* gbase, uint32_t gmode, uint32_t gsrc, const FitStats& gs, LaneFit& best)
 {
 	float axis[4], mean[4];
 	float tmin, tmax;
@@ -680,6 +690,13 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 		uint32_t q00 = 0, q01 = 0, q02 = 0, q03 = 0, q11 = 0, q12 = 0, q13 = 0, q22 = 0, q23 = 0,
 			q33 = 0;
 		lo = 255u; hi = 0u;
+		if (GIVEN && gmode == 3u) {
+			// the same integers as the loop below sums: same floats from here on
+			uint32_t q[10];
+			mom_unpack(gs.W, s, q);
+			q00 = q[0]; q01 = q[1]; q02 = q[2]; q03 = q[3]; q11 = q[4]; q12 = q[5]; q13 = q[6]; q22 = q[7]; q23 = q[8]; q33 = q[9];
+			lo = gs.lohi & 255u; hi = gs.lohi >> 8;
+		} else
 #pragma unroll 1
 		for (uint32_t r = 0; r < 4u; ++r) {
 			uint32_t P[4];
@@ -770,7 +787,7 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 		pp_sum = UNITW ? q00 + q11 + q22 + q33 : ycc_pp_sum(tx, mask, yw);
 		s01 = s[0] | (s[1] << 16);
 		s23 = s[2] | (s[3] << 16);
-		if (gmode == 1u) {
+		if (GIVEN ? gmode != 0u : gmode == 1u) {   // 1 or 3
 			uint32_t lane;
 			CF_FRESH_LANE(lane);
 			uint32_t* gc = gbase + lane;
@@ -1236,7 +1253,7 @@ __device__ __forceinline__ void column_put_fit(uint32_t* wc, const FitGeo& g, ui
 // run-time scalars across every phase the budget cost 53 spilled SGPRs in the Normal build, and every lane-role
 // expression selected its layout again.
 template <bool UNITW, bool WIDE, int LEVEL>
-__device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint32_t* plan, const uint32_t* yccp, const uint32_t* mom, uint32_t b,
+__device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint32_t* plan, const uint32_t* yccp, const uint32_t* mom, const uint32_t* lohi, uint32_t b,
 	bool pair, uint32_t* cbase, uint32_t* gbase, const cf_kparams& kp)
 {
 	uint32_t lane;
@@ -1297,6 +1314,9 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 	// the residual estimator and the best are taken in (score, index) order.
 	// Highest instead refits every partition (below), after a stream 0 without partitions.
 	constexpr bool lay32 = !WIDE;
+	// the first stream trip's fits get their integer statistics handed in ("moments handed in" below): the 32-lane
+	// layouts.  The wide instances keep the row loop: with the hand-off Highest's linear build spills 5 vector registers.
+	constexpr bool given = lay32;
 #define L_HL (lay32 ? (lane & 31u) : lane)
 #define L_SLOT_OK (!lay32 || pair || lane < 32u)
 	constexpr uint32_t ntop = LEVEL >= 3 ? 8u : (LEVEL == 2 ? 4u : 1u);   // oracle: budget.top
@@ -1390,6 +1410,21 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 					} else {
 						if (st == 0u) moments_rows<false, false>(txp, m1, m2, ma, mb); else moments_rows<false, true>(txp, m1, m2, ma, mb);
 					}
+					// first stream trip: the owner of a partition leaves its subset-1 moments, packed like the block table,
+					// where the lanes that fit the winning partitions find them (below, "moments handed in"): partition
+					// lane + 32 pi in words 0..9 of the lane's candidate column (pi = 0) or fit-geometry column (pi = 1).
+					// Both are dead here: no leader has stored a candidate of this block yet, and this trip's fits write
+					// the geometry words after they have read these.  The geometry column's tag goes first, so that the
+					// column cannot pass for a fit while it holds moments.
+					if (given && st == 0u) {
+						uint32_t* sc = (pi ? gbase : cbase) + lane;
+						if (pi)
+							sc[12*CF_WG_THREADS] = CF_BC7_GEO_NONE;
+						sc[0*CF_WG_THREADS] = ma.q00 | (ma.s[0] << 20); sc[1*CF_WG_THREADS] = ma.q11 | (ma.s[1] << 20);
+						sc[2*CF_WG_THREADS] = ma.q22 | (ma.s[2] << 20); sc[3*CF_WG_THREADS] = ma.q33 | (ma.s[3] << 20);
+						sc[4*CF_WG_THREADS] = ma.q01; sc[5*CF_WG_THREADS] = ma.q02; sc[6*CF_WG_THREADS] = ma.q03;
+						sc[7*CF_WG_THREADS] = ma.q12; sc[8*CF_WG_THREADS] = ma.q13; sc[9*CF_WG_THREADS] = ma.q23;
+					}
 					// subsets 0, 1 (, 2) in the oracle's order of summation
 					float sc = 0.0f, sl = 0.0f, al;
 					{
@@ -1437,6 +1472,8 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				}
 			}
 			// ---- lane roles ----
+			if (given)
+				__builtin_amdgcn_wave_barrier();   // the moments phase 1 left in LDS are read below
 			CF_FRESH_LANE(lane);
 			asm volatile("" : "+v"(mypart));   // nothing of phase 1 but mypart lives on
 #define R_M6 (st == 0u && L_SLOT_OK && L_HL < 2u)
@@ -1541,13 +1578,42 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			// perceptual weight pairs of this fit: zero on the axes it does not code
 			const uint32_t yw[2] = {(chm & 7u) ? ywrg : 0u,
 				((chm & 7u) ? (ywba & 0xFFFFu) : 0u) | ((chm & 8u) ? (ywba & 0xFFFF0000u) : 0u)};
+			// ---- moments handed in: in the first stream trip every fit's integer statistics exist already ----
+			// mode 6 and the planes of modes 4 / 5 fit the whole block: the block table's words in the fit's channel slots
+			// (mom_whole), the extremes of its rotated alpha from the table of channel extremes.  A partition lane takes the
+			// subset-1 moments its partition's owner left in LDS (phase 1); subset 0 is the block minus them, as in
+			// moments_rest.  The later trips keep the row loop: the second pass, whose candidate columns are live, and the
+			// starts trip where the cache misses.
+			FitStats gs;   // (filled, and read by the fit, in the first stream trip alone)
+			if (given && st == 0u) {
+				const uint32_t blk = B_OFF >> 4;
+				uint32_t T[CF_MOM_WORDS];
+#pragma unroll
+				for (int m = 0; m < CF_MOM_WORDS; ++m) T[m] = mom[__umul24(blk, CF_BC7_MOM_WORDS) + (uint32_t)m];
+				gs.lohi = lohi[blk*4u + ((rot + 3u) & 3u)];
+				// (branches on the lane's role, not selects: under the execution mask a subset-1 lane's words are loaded
+				// straight into place and only the subset-0 lanes' subtraction and the whole-block lanes' derivation issue)
+				if (quality >= 1u && plane) {
+					// owner of partition p: lane p & 31 of the half, word set p >> 5 (one block per wave: lane p)
+					const uint32_t* sc = ((pair && mypart >= 32u) ? gbase : cbase) + (pair ? L_HBASE + (mypart & 31u) : mypart);
+#pragma unroll
+					for (int m = 0; m < CF_MOM_WORDS; ++m) gs.W[m] = sc[m*CF_WG_THREADS];
+					if (sub == 0u) {
+						mom_sub(T, gs.W, gs.W);
+						asm volatile("" : "+v"(gs.W[0]));   // (keeps this a branch: as a select every lane pays for both forms)
+					}
+				} else
+					mom_whole(T, !(H_ALPHA), rot, chm, gs.W);
+				__builtin_amdgcn_wave_barrier();   // read before any fit writes its geometry words
+				gmode = 3u;
+			}
 			if (active) {
 				if (narrow)
 					fit_lane<UNITW, iters, 4>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
-						wv, yw, sca, frac, gbase, gmode, gsrc, lf);
+						wv, yw, sca, frac, gbase, gmode, gsrc, gs, lf);
 				else
-					fit_lane<UNITW, iters>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
-						wv, yw, sca, frac, gbase, gmode, gsrc, lf);
+					fit_lane<UNITW, iters, 8, given>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
+						wv, yw, sca, frac, gbase, gmode, gsrc, gs, lf);
 			}
 			CF_FRESH_LANE(lane);         // the roles below are computed again from here
 			if (sst) {
@@ -1897,8 +1963,23 @@ cfhip_bc7_encode_kernel(cf_kparams kp)
 		// channel-planar copy: plan[b*16 + r*4 + c] = channel c of the 4 texels of row r
 		const uint32_t t = threadIdx.x, c = t & 3u;
 		const uint4 row = *reinterpret_cast<const uint4*>(tile + (t & ~3u));
-		plan[t] = ((row.x >> (8u*c)) & 255u) | (((row.y >> (8u*c)) & 255u) << 8) |
+		const uint32_t pw = ((row.x >> (8u*c)) & 255u) | (((row.y >> (8u*c)) & 255u) << 8) |
 			(((row.z >> (8u*c)) & 255u) << 16) | (((row.w >> (8u*c)) & 255u) << 24);
+		plan[t] = pw;
+		// per-block table of the four channels' extremes, word c = lo | hi << 8 over the block's 16 texels: this thread's row,
+		// then the rows of the other three (lanes 4 and 8 away in the DPP row of 16).  It lives in the block's 16 bytes of
+		// outb, which are dead until the block's payload is stored there after its search.
+		// (read by the 32-lane layouts' first stream trip)
+		if (!WIDE) {
+			const uint32_t lh = byte_lohi(pw);
+			uint32_t lo = lh & 255u, hi = lh >> 8, o;
+			o = cf_dpp<0x128>(lo); lo = o < lo ? o : lo;   // row_ror:8
+			o = cf_dpp<0x128>(hi); hi = o > hi ? o : hi;
+			o = cf_dpp<0x124>(lo); lo = o < lo ? o : lo;   // row_ror:4
+			o = cf_dpp<0x124>(hi); hi = o > hi ? o : hi;
+			if ((t & 12u) == 0u)
+				reinterpret_cast<uint32_t*>(outb)[(t >> 4)*4u + c] = lo | (hi << 8);
+		}
 	}
 	__syncthreads();
 	block_moments_put(plan, mom, threadIdx.x);
@@ -1916,7 +1997,7 @@ cfhip_bc7_encode_kernel(cf_kparams kp)
 			!(CF_BC7_ABLATE & 4);
 		// opaque copy: keeps the (many) lane-role values of encode_blocks from being hoisted
 		// out of this loop and held in registers across all phases
-		const uint4 blk = encode_blocks<UNITW, WIDE, LEVEL>(tile, plan, yccp, mom, b, pair, cands + wave*64u, geoc + wave*64u, kp);
+		const uint4 blk = encode_blocks<UNITW, WIDE, LEVEL>(tile, plan, yccp, mom, reinterpret_cast<const uint32_t*>(outb), b, pair, cands + wave*64u, geoc + wave*64u, kp);
 		uint32_t lo;
 		asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lo));
 		if (pair) {

@@ -2,6 +2,8 @@
 // Plain integer functions: the kernels of bc7_encode.hip use them on the device, a host program can
 // include this file and compare them with the per-byte formulas (tests/test_bc7_packed_identities.py).
 // Every identity here is exact, so the encoder's payloads do not depend on which form computes them.
+// Below them: the integer moments of a set of texels as packed words (the block table, what phase 1 hands to the fits),
+// compared with per-texel sums by tests/test_bc7_moment_derivation.py.
 #ifndef CFHIP_BC7_PACKED_H
 #define CFHIP_BC7_PACKED_H
 
@@ -61,6 +63,67 @@ CF_PK uint32_t pal_word(uint32_t e0, uint32_t e1, uint32_t w)
 	const uint32_t rb = CF_PK_MUL24(iw, e0 & m) + CF_PK_MUL24(w, e1 & m) + half;
 	const uint32_t ga = CF_PK_MUL24(iw, (e0 >> 8) & m) + CF_PK_MUL24(w, (e1 >> 8) & m) + half;
 	return ((rb >> 6) & m) | ((ga << 2) & ~m);
+}
+
+// ---- packed integer moments ----
+// The 14 integer moments of a set of texels (channel sums s_c, sums of products q_cd) in 10 words, as the per-block
+// table of bc7_encode.hip holds the whole block's: words 0..3 = q_cc | s_c << 20 (q <= 16 * 255^2 < 2^20,
+// s <= 16 * 255 < 2^12), words 4..9 = q01 q02 q03 q12 q13 q23.
+#define CF_MOM_WORDS 10
+
+// Moments of a set minus those of a subset of it, on the packed words: every field of the subset is at most the set's
+// field (sums of non-negative terms over fewer texels), so no field borrows from its neighbour.
+CF_PK void mom_sub(const uint32_t (&T)[CF_MOM_WORDS], const uint32_t (&A)[CF_MOM_WORDS], uint32_t (&W)[CF_MOM_WORDS])
+{
+	for (int m = 0; m < CF_MOM_WORDS; ++m)
+		W[m] = T[m] - A[m];
+}
+
+// Moments of a fit that covers the whole block, from the block's table words T: the channels as the fit sees them,
+// rotation rot (0..3: colour rot - 1 and alpha change places) and channel set chm applied (7: the vector plane,
+// slot 3 not coded; 8: the scalar plane, slot 3 alone; 15: all four, which only fits without rotation have).
+// opaque: T holds zeros for every alpha term (the table applies the block's own channel set); the alpha plane such a
+// fit reads is the constant 255, so s_a = 255 * 16, q_aa = 255^2 * 16, q_ca = 255 * s_c.
+CF_PK void mom_whole(const uint32_t (&T)[CF_MOM_WORDS], bool opaque, uint32_t rot, uint32_t chm, uint32_t (&W)[CF_MOM_WORDS])
+{
+	// (the table's zeros plus the constant's terms: one multiply-add per word, the factor 0 for a block with alpha)
+	const uint32_t k = opaque ? 255u : 0u;
+	const uint32_t t3 = opaque ? (1040400u | (4080u << 20)) : T[3];
+	const uint32_t t6 = CF_PK_MUL24(T[0] >> 20, k) + T[6];
+	const uint32_t t8 = CF_PK_MUL24(T[1] >> 20, k) + T[8];
+	const uint32_t t9 = CF_PK_MUL24(T[2] >> 20, k) + T[9];
+	const bool vec = (chm & 7u) != 0u, sca = (chm & 8u) != 0u, all = vec && sca;
+	// slot c < 3 holds colour c, or alpha when the rotation moved it there; slot 3 holds alpha or colour rot - 1
+	const uint32_t d0 = rot == 1u ? t3 : T[0], d1 = rot == 2u ? t3 : T[1], d2 = rot == 3u ? t3 : T[2];
+	const uint32_t d3 = rot == 0u ? t3 : (rot == 1u ? T[0] : (rot == 2u ? T[1] : T[2]));
+	const uint32_t q01 = rot == 1u ? t8 : (rot == 2u ? t6 : T[4]);
+	const uint32_t q02 = rot == 1u ? t9 : (rot == 3u ? t6 : T[5]);
+	const uint32_t q12 = rot == 2u ? t9 : (rot == 3u ? t8 : T[7]);
+	W[0] = vec ? d0 : 0u; W[1] = vec ? d1 : 0u; W[2] = vec ? d2 : 0u; W[3] = sca ? d3 : 0u;
+	W[4] = vec ? q01 : 0u; W[5] = vec ? q02 : 0u; W[7] = vec ? q12 : 0u;
+	// products of a colour slot with slot 3: coded by four-channel fits alone, and those are not rotated
+	W[6] = all ? t6 : 0u; W[8] = all ? t8 : 0u; W[9] = all ? t9 : 0u;
+}
+
+// The packed words apart: channel sums s[4] and the ten products in the order q00 q01 q02 q03 q11 q12 q13 q22 q23 q33
+CF_PK void mom_unpack(const uint32_t (&W)[CF_MOM_WORDS], uint32_t (&s)[4], uint32_t (&q)[10])
+{
+	for (int c = 0; c < 4; ++c)
+		s[c] = W[c] >> 20;
+	q[0] = W[0] & 0xFFFFFu; q[1] = W[4]; q[2] = W[5]; q[3] = W[6];
+	q[4] = W[1] & 0xFFFFFu; q[5] = W[7]; q[6] = W[8];
+	q[7] = W[2] & 0xFFFFFu; q[8] = W[9];
+	q[9] = W[3] & 0xFFFFFu;
+}
+
+// Minimum and maximum of the four bytes of a word, as lo | hi << 8
+CF_PK uint32_t byte_lohi(uint32_t w)
+{
+	const uint32_t b0 = w & 255u, b1 = (w >> 8) & 255u, b2 = (w >> 16) & 255u, b3 = w >> 24;
+	uint32_t lo = b0 < b1 ? b0 : b1, hi = b0 > b1 ? b0 : b1;
+	lo = b2 < lo ? b2 : lo; hi = b2 > hi ? b2 : hi;
+	lo = b3 < lo ? b3 : lo; hi = b3 > hi ? b3 : hi;
+	return lo | (hi << 8);
 }
 
 #endif
