@@ -13,6 +13,12 @@
 //     set, precision, p-bit kind, index width and subset mask are per-lane values (fit_lane:
 //     integer statistics -> covariance -> principal axis -> extremes -> quantise -> exhaustive
 //     selectors via v_dot4_u32_u8 -> closed-form least-squares refit rounds).
+//   * what a lane fits in a stream trip -- its role -- depends on the layout, the trip, whether its half carries alpha
+//     and walks the second pass, and its index in the half, on nothing the search computes: two packed words per lane
+//     (kind, candidate id, fit index, rank, leader and gather flags; rotation, precisions, channel set) from a table
+//     built at compile time (bc7_roles.h).  They are loaded before the fit and again after it, so no role lives in a
+//     register through the fit, and the candidate assembly after the fit is straight-line code under one guard.
+//     (Lowest keeps its roles as expressions: four lanes with a role fold to constants, and the words did not pay.)
 //   * up to High a block's candidates fill 32 lanes (mode 6, mode 5 x rotations, modes 1/3
 //     or 7 on their best partitions) and two neighbouring blocks share a wavefront; Highest uses
 //     64 lanes (mode 4, 16 two-subset partitions) and a second stream for the three-subset modes.
@@ -32,6 +38,7 @@
 // Build with -ffp-contract=off: fused ops are written as explicit fmaf().
 #include "cf_device.h"
 #include "bc7_packed.h"
+#include "bc7_roles.h"
 
 namespace {
 
@@ -45,6 +52,9 @@ __device__ __forceinline__ int cf_bperm(int v, uint32_t src)
 {
 	return __builtin_amdgcn_ds_bpermute((int)(src << 2), v);
 }
+
+// what every lane of a stream trip does, as two words per (layout, row, lane): bc7_roles.h
+__device__ const cf_bc7_role_table k_bc7_roles = cf_bc7_make_roles();
 
 __device__ const uint16_t k_part2[64] = {
 	0xcccc, 0x8888, 0xeeee, 0xecc8, 0xc880, 0xfeec, 0xfec8, 0xec80,
@@ -1246,6 +1256,18 @@ __device__ __forceinline__ void column_put_fit(uint32_t* wc, const FitGeo& g, ui
 }
 
 
+// Rows of k_bc7_roles for the two halves of a wave in the 32-lane layouts, half 1's in bits 8..10 (wave-uniform).
+// abal: ballot of the texels with alpha, 16 per half; gb: bit 0 / 32 = half 0 / 1 walks the second pass (one block per
+// wave: bit 0, and the upper lanes have no roles).
+__device__ __forceinline__ uint32_t role_rows32(uint32_t st, unsigned long long abal, unsigned long long gb, bool pair)
+{
+	const uint32_t a0 = ((uint32_t)abal & 0xFFFFu) != 0u ? 1u : 0u, a1 = ((uint32_t)(abal >> 32) & 0xFFFFu) != 0u ? 1u : 0u;
+	const uint32_t g0 = (uint32_t)gb & 1u, g1 = (uint32_t)(gb >> 32) & 1u;
+	const uint32_t r0 = st == 0u ? a0 : (g0 ? 2u + a0 : CF_ROLE_ROW_NONE);
+	const uint32_t r1 = !pair ? CF_ROLE_ROW_NONE : (st == 0u ? a1 : (g1 ? 2u + a1 : CF_ROLE_ROW_NONE));
+	return r0 | (r1 << 8);
+}
+
 // Encode one block with the whole wavefront.  tp: the block's 16 texels in LDS
 // (colour mask already applied), identical for every lane.
 // LEVEL: the quality level (0 Lowest .. 4 Highest).  Its whole search budget -- refit rounds, list length,
@@ -1368,7 +1390,6 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 					break;
 			}
 			const Tex txp = make_tex(tile, plan, yccp, B_OFF, 0u, H_ALPHA ? 15u : 7u);   // partition fits: no rotation
-			const uint32_t ns = 2u + st;
 			// the second pass of the 32-lane layout (s1l): slot s of an opaque half that walks it has its subsets
 			// in lanes 11 + 2 s, 12 + 2 s and s; candidate 5 + k (mode 4) of an alpha-carrying half its vector /
 			// scalar plane in lanes 11 + 2 k, 12 + 2 k -- the leaders are odd lanes from 11 up, whose columns no
@@ -1377,6 +1398,20 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			// phase 1 is walked when some group ranks partitions in this trip
 			const bool parts = quality >= 1u && !sst &&
 				(!s1l || __ballot(L_SLOT_OK && !(H_ALPHA) && H_GATE) != 0ull);
+			// A lane's roles are two words of k_bc7_roles (bc7_roles.h): the row is the half's (trip, alpha, second pass), the
+			// column the lane of the half.  The address is an expression of a lane id re-read where a phase starts -- before
+			// the fit, after the fit; phase 1's ranking forms it from the id re-read at the top of the trip, which phase 1
+			// holds anyway -- and the words are dead where their phase ends: no role is carried in a register through the fit.
+			// Lowest keeps the roles as expressions (below): its layout has four lanes with a role, which the compiler folds
+			// to constants, and with the words it ran 1 % slower (profiles/lane_roles_bc7_ab.txt).
+			constexpr bool words = quality != 0u;
+			constexpr uint32_t rlay = WIDE ? CF_ROLE_LAY_WIDE : CF_ROLE_LAY_NORMAL;
+			// (the rows of both halves are one wave-uniform word, a lane takes its half's byte: no branch on the lane id)
+#define R_ROW (lay32 ? (role_rows32(st, abal, gb, pair) >> ((lane >> 2) & 8u)) & 7u : (st == 0u ? (uint32_t)(((uint32_t)abal & 0xFFFFu) != 0u) : 2u))
+#define R_WORDS (k_bc7_roles.w + cf_bc7_role_index(rlay, R_ROW, L_HL))
+			const uint32_t ns = 2u + st;     // subsets of this trip's partitions
+			// The expression macros from here to R_RANK, and R_M6 .. R_IDBASE before the fit, serve the Lowest instances
+			// alone (`!words`): in every other instance each use of them sits in a discarded `if constexpr` branch.
 			// partition lanes: first lane, slots of the first mode, slots in all
 			// (nper0 depends on the half's H_ALPHA: an expression, like the roles, not a carried value)
 			const uint32_t pfirst = lay32 ? (quality == 2u ? 10u : 4u) : (st == 1u ? 0u : 26u);
@@ -1449,6 +1484,9 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				// one ranking per mode of the group: modes 1 / 3 (alpha: mode 7 alone), modes 0 / 2; key = bits of
 				// residual + along / (4 (2^ib)^2), low 6 bits = the partition (oracle: encode_block, "qf")
 				const uint32_t nruns = (st == 1u || ANY_OPAQUE) ? 2u : 1u;
+				// the slot this lane fits: mi | rank << 1 of its role word (no partition lane: a rank no selection reaches)
+				static_assert(CF_ROLE_NO_RANK >= 16u, "no selection below (at most 16 per run) may reach the rank of a lane that fits no subset");
+				const uint32_t rankmi = words ? CF_ROLE_RANKMI(R_WORDS[0]) : ((R_RANK << 1) | R_MI);
 				for (uint32_t run = 0; run < nruns; ++run) {
 					CF_FRESH_LANE(lane);
 					// (formed here from its bits: as a float select it is hoisted out of the stream loop and held in a register)
@@ -1464,7 +1502,7 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 						: (lay32 ? 5u : 4u));
 					for (uint32_t t = 0; t < nsel; ++t) {
 						const uint32_t kmin = cf_group_min_u32(ka < kb ? ka : kb, pair, L_H);
-						const bool mine = R_RANK == t && R_MI == run;
+						const bool mine = rankmi == ((t << 1) | run);
 						mypart = mine ? (kmin & 63u) : mypart;
 						ka = ka == kmin ? 0xFFFFFFFFu : ka;
 						kb = kb == kmin ? 0xFFFFFFFFu : kb;
@@ -1481,10 +1519,13 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 #define R_SCA (lay32 ? (st == 1u ? (R_S1M4 && ((L_HL - 11u) & 1u) != 0u) : (quality == 2u ? (L_SLOT_OK && L_HL >= 6u && L_HL < 10u) : (L_SLOT_OK && L_HL == 3u))) : (st == 0u && lane >= 14u && lane < 26u))
 #define R_CID (R_M6 ? 0u : (lay32 ? (st == 1u ? 5u + ((L_HL - 11u) >> 1) : (quality == 2u ? L_HL - (R_SCA ? 5u : 1u) : 1u)) : 1u + (lane - (R_SCA ? 14u : 2u))))   /* meaningful for vecp / sca */
 #define R_IDBASE (R_PLANE ? (st == 1u ? (R_MI ? 256u : 192u) : (H_ALPHA ? 320u : (R_MI ? 128u : 64u))) : 0u)
-			bool m6 = R_M6, sca = R_SCA;
-			const bool vecp = R_VECP, plane = R_PLANE;
-			const uint32_t cid = R_CID, sub = R_SUB, mi = R_MI;
-			const uint32_t s2off = lay32 ? ((quality == 2u && st == 0u) ? 4u : 1u) : (st == 0u ? 12u : 2u);
+			bool m6 = false, sca = false, vecp = false, plane = false;
+			uint32_t cid = 0, sub = 0, mi = 0;
+			if constexpr (!words) {
+				m6 = R_M6; sca = R_SCA; vecp = R_VECP; plane = R_PLANE;
+				cid = R_CID; sub = R_SUB; mi = R_MI;
+			}
+			const uint32_t s2off = lay32 ? ((quality == 2u && st == 0u) ? 4u : 1u) : (st == 0u ? 12u : 2u);   // (read by the assembly on the expressions alone)
 			uint32_t rot = 0, cb = 7, ab = 7, pbk = 1, ib = 4, mask = 0xFFFFu;
 			bool active = m6;
 			float frac = frac_main;
@@ -1521,6 +1562,18 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				CF_DIAG_COUNT(CF_DIAG_STARTS, true);
 				CF_DIAG_COUNT(CF_DIAG_STARTS_CACHED, gmode == 2u);
 				CF_DIAG_COUNT(CF_DIAG_STARTS_NARROW, narrow);
+			} else if constexpr (words) {
+				const uint32_t* rp = R_WORDS;   // (one address, one two-word load)
+				const uint32_t rw = rp[0], fw = rp[1];
+				m6 = (rw & CF_ROLE_M6) != 0u; sca = (rw & CF_ROLE_SCA) != 0u; plane = (rw & CF_ROLE_PLANE) != 0u;
+				sub = CF_ROLE_KF(rw);
+				active = CF_ROLE_ACTIVE(rw, UNITW) != 0u;
+				rot = CF_FIT_ROT(fw); chm_s = CF_FIT_CHM(fw);
+				cb = CF_FIT_GEO(fw) & 15u; ab = (CF_FIT_GEO(fw) >> 4) & 15u; pbk = (CF_FIT_GEO(fw) >> 8) & 15u; ib = CF_FIT_GEO(fw) >> 12;
+				// a subset's texels (mypart is 0 on every other lane: a valid index, and the whole block is its mask)
+				const uint32_t sp2 = k_part2[mypart], sp3 = k_part3[mypart];
+				const uint32_t smask = st == 0u ? (sub ? sp2 : (~sp2 & 0xFFFFu)) : part3_mask(sp3, sub);
+				mask = plane ? smask : 0xFFFFu;
 			} else if (vecp || sca) {
 				if (cid <= 4u) {
 					rot = cid - 1u; pbk = 0; ib = 2;
@@ -1568,7 +1621,7 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				else { wl[3] = wl[2]; wl[2] = t3; }
 			}
 			// channels this fit codes (after rotation) and their weights
-			const uint32_t chm = sst ? chm_s : (m6 ? 15u : (sca ? 8u : (vecp ? 7u : (H_ALPHA ? 15u : 7u))));
+			const uint32_t chm = (sst || words) ? chm_s : (m6 ? 15u : (sca ? 8u : (vecp ? 7u : (H_ALPHA ? 15u : 7u))));
 			const uint32_t wv[4] = {(chm & 1u) ? wl[0] : 0u, (chm & 2u) ? wl[1] : 0u,
 				(chm & 4u) ? wl[2] : 0u, (chm & 8u) ? wl[3] : 0u};
 			LaneFit lf;
@@ -1650,59 +1703,122 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				}
 				continue;
 			}
-			// the fit this lane's geometry-cache column now holds: written by every lane of the first stream trip (a
-			// column of the previous block must not pass for this one's), by the lanes that ran a fit in a later one
-			if (active || st == 0u)
-				gbase[lane + 12*CF_WG_THREADS] = active ? geo_tag(R_M6 ? 0u : ((R_VECP || R_SCA) ? R_CID : R_IDBASE + mypart),
-					R_SCA ? 1u : (R_PLANE ? R_SUB : 0u)) : CF_BC7_GEO_NONE;
-			// ---- assemble candidates in their leader lanes ----
-			//   mode 6: its first lane;  mode 4/5: vector lane (scalar plane s2off lanes up);
-			//   partitions: subset-0 lane (the other subsets in the next lanes)
-			const int s1 = (int)((lane + 1u) & 63u);
-			const int s2 = (s1l && R_PLANE) ? (int)(L_HBASE + ((L_HL - 11u) >> 1)) : (int)((lane + s2off) & 63u);
-			// error and id first: only a leader whose candidate beats its best so far stores
-			// the payload fields, straight from the shuffles into its LDS column
-			const uint32_t e1 = (uint32_t)cf_bperm((int)lf.err, (uint32_t)(s1)), e2 = (uint32_t)cf_bperm((int)lf.err, (uint32_t)(s2));
-			const bool use1 = R_PLANE, use2 = R_VECP || (R_PLANE && st == 1u);
-			const uint32_t cerr = lf.err + (use1 ? e1 : 0u) + (use2 ? e2 : 0u);
-			const uint32_t cidv = R_M6 ? 0u : (R_VECP ? R_CID : R_IDBASE + mypart);
-			const bool leader = active && (R_M6 ? L_HL == 0u : (R_VECP || (R_PLANE && R_SUB == 0u)));
-			const uint32_t old_err = L_CSLOT[18*CF_WG_THREADS], old_id = L_CSLOT[19*CF_WG_THREADS];
-			const bool take = leader && (cerr < old_err || (cerr == old_err && cidv < old_id));
-			const uint32_t best_err = take ? cerr : old_err;
-			if (take) {
-				L_CSLOT[18*CF_WG_THREADS] = cerr;
-				L_CSLOT[19*CF_WG_THREADS] = cidv;
-			}
-			{
-				const uint32_t a01 = (uint32_t)cf_bperm((int)lf.q0, (uint32_t)(s1)), a11 = (uint32_t)cf_bperm((int)lf.q1, (uint32_t)(s1));
-				const uint32_t a02 = (uint32_t)cf_bperm((int)lf.q0, (uint32_t)(s2)), a12 = (uint32_t)cf_bperm((int)lf.q1, (uint32_t)(s2));
-				const uint32_t pb1 = (uint32_t)cf_bperm((int)lf.pb, (uint32_t)(s1)), pb2 = (uint32_t)cf_bperm((int)lf.pb, (uint32_t)(s2));
+			uint32_t best_err;
+			if constexpr (words) {
+				// ---- assemble candidates in their leader lanes: straight-line code on the lane's role word ----
+				//   mode 6: its first lane;  mode 4/5: vector lane (scalar plane in lane s2);
+				//   partitions: subset-0 lane (subset 1 in the next lane, subset 2 in lane s2)
+				const uint32_t rw = R_WORDS[0];
+				bool act = CF_ROLE_ACTIVE(rw, UNITW) != 0u;
+				if (CF_BC7_ABLATE & 1) act = act && (rw & (CF_ROLE_M6 | CF_ROLE_PLANE)) != 0u;
+				if (CF_BC7_ABLATE & 2) act = act && (rw & CF_ROLE_PLANE) == 0u;
+				// the candidate of this lane's fit (a lane that fits no subset has ranked no partition: mypart is 0)
+				const uint32_t cidv = CF_ROLE_IDB(rw) + mypart;
+				// the fit this lane's geometry-cache column now holds: written by every lane of the first stream trip (a
+				// column of the previous block must not pass for this one's), by the lanes that ran a fit in a later one
+				if (act || st == 0u)
+					gbase[lane + 12*CF_WG_THREADS] = act ? cidv*4u + CF_ROLE_KF(rw) : CF_BC7_GEO_NONE;   // geo_tag (mode 6: fit 0)
+				const uint32_t s1 = (lane + 1u) & 63u;
+				const uint32_t s2 = (lay32 ? (lane & 32u) : 0u) + CF_ROLE_S2(rw);
+				// which gathered fits belong to this lane's candidate, as masks: subset 1 (use1: every partition), the scalar
+				// plane (vector lanes), subset 2 (the second pass's partitions: use2 of a lane that is no vector plane)
+				const uint32_t m1 = 0u - CF_ROLE_USE1(rw), mv = 0u - ((rw / CF_ROLE_VECP) & 1u), m2 = 0u - CF_ROLE_USE2(rw);
+				const uint32_t m3 = m2 & ~mv, m4 = (mv & 0xFF000000u) | m3;
+				const uint32_t e1 = (uint32_t)cf_bperm((int)lf.err, s1), e2 = (uint32_t)cf_bperm((int)lf.err, s2);
+				const uint32_t a01 = (uint32_t)cf_bperm((int)lf.q0, s1), a11 = (uint32_t)cf_bperm((int)lf.q1, s1);
+				const uint32_t a02 = (uint32_t)cf_bperm((int)lf.q0, s2), a12 = (uint32_t)cf_bperm((int)lf.q1, s2);
+				const uint32_t pb1 = (uint32_t)cf_bperm((int)lf.pb, s1), pb2 = (uint32_t)cf_bperm((int)lf.pb, s2);
+				uint32_t w1[4], w2[4];
+#pragma unroll
+				for (int k = 0; k < 4; ++k) {
+					w1[k] = (uint32_t)cf_bperm((int)lf.w[k], s1);
+					w2[k] = (uint32_t)cf_bperm((int)lf.w[k], s2);
+				}
+				// only a leader whose candidate beats its best so far stores the payload fields into its LDS column
+				const uint32_t cerr = lf.err + (e1 & m1) + (e2 & m2);
+				const bool leader = act && CF_ROLE_LEADER(rw) != 0u;
+				const uint32_t old_err = L_CSLOT[18*CF_WG_THREADS], old_id = L_CSLOT[19*CF_WG_THREADS];
+				// (error, id) order as one 64-bit comparison
+				const bool take = leader & ((((unsigned long long)cerr << 32) | cidv) < (((unsigned long long)old_err << 32) | old_id));
+				best_err = take ? cerr : old_err;
 				if (take) {
+					L_CSLOT[18*CF_WG_THREADS] = cerr;
+					L_CSLOT[19*CF_WG_THREADS] = cidv;
 					L_CSLOT[0*CF_WG_THREADS] = lf.q0;
 					L_CSLOT[1*CF_WG_THREADS] = lf.q1;
-					L_CSLOT[2*CF_WG_THREADS] = R_PLANE ? a01 : 0u;
-					L_CSLOT[3*CF_WG_THREADS] = R_PLANE ? a11 : 0u;
+					L_CSLOT[2*CF_WG_THREADS] = a01 & m1;
+					L_CSLOT[3*CF_WG_THREADS] = a11 & m1;
 					// modes 4/5: the scalar plane's endpoints are parked in q[4], q[5] (byte 3)
-					L_CSLOT[4*CF_WG_THREADS] = R_VECP ? (a02 & 0xFF000000u) : ((R_PLANE && st == 1u) ? a02 : 0u);
-					L_CSLOT[5*CF_WG_THREADS] = R_VECP ? (a12 & 0xFF000000u) : ((R_PLANE && st == 1u) ? a12 : 0u);
-					L_CSLOT[6*CF_WG_THREADS] = lf.pb | (R_PLANE ? (pb1 << 2) : 0u) |
-						((R_PLANE && st == 1u) ? (pb2 << 4) : 0u);
+					L_CSLOT[4*CF_WG_THREADS] = a02 & m4;
+					L_CSLOT[5*CF_WG_THREADS] = a12 & m4;
+					L_CSLOT[6*CF_WG_THREADS] = lf.pb | ((pb1 << 2) & m1) | ((pb2 << 4) & m3);
 					// errors of the candidate's fits: subset 0 / vector plane / mode 6, then subset 1 or
 					// the scalar plane, then subset 2
 					L_CSLOT[15*CF_WG_THREADS] = lf.err;
-					L_CSLOT[16*CF_WG_THREADS] = R_PLANE ? e1 : (R_VECP ? e2 : 0u);
-					L_CSLOT[17*CF_WG_THREADS] = (R_PLANE && st == 1u) ? e2 : 0u;
-				}
-			}
+					L_CSLOT[16*CF_WG_THREADS] = (e1 & m1) | (e2 & mv);
+					L_CSLOT[17*CF_WG_THREADS] = e2 & m3;
 #pragma unroll
-			for (int k = 0; k < 4; ++k) {
-				const uint32_t w1 = (uint32_t)cf_bperm((int)lf.w[k], (uint32_t)(s1));
-				const uint32_t w2 = (uint32_t)cf_bperm((int)lf.w[k], (uint32_t)(s2));
+					for (int k = 0; k < 4; ++k) {
+						L_CSLOT[(7 + k)*CF_WG_THREADS] = lf.w[k] | (w1[k] & m1) | (w2[k] & m3);
+						L_CSLOT[(11 + k)*CF_WG_THREADS] = w2[k] & mv;
+					}
+				}
+			} else {
+				// Lowest: the assembly on the role expressions, its gathers and stores behind the branches on them
+				// the fit this lane's geometry-cache column now holds: written by every lane of the first stream trip (a
+				// column of the previous block must not pass for this one's), by the lanes that ran a fit in a later one
+				if (active || st == 0u)
+					gbase[lane + 12*CF_WG_THREADS] = active ? geo_tag(R_M6 ? 0u : ((R_VECP || R_SCA) ? R_CID : R_IDBASE + mypart),
+						R_SCA ? 1u : (R_PLANE ? R_SUB : 0u)) : CF_BC7_GEO_NONE;
+				// ---- assemble candidates in their leader lanes ----
+				//   mode 6: its first lane;  mode 4/5: vector lane (scalar plane s2off lanes up);
+				//   partitions: subset-0 lane (the other subsets in the next lanes)
+				const int s1 = (int)((lane + 1u) & 63u);
+				const int s2 = (s1l && R_PLANE) ? (int)(L_HBASE + ((L_HL - 11u) >> 1)) : (int)((lane + s2off) & 63u);
+				// error and id first: only a leader whose candidate beats its best so far stores
+				// the payload fields, straight from the shuffles into its LDS column
+				const uint32_t e1 = (uint32_t)cf_bperm((int)lf.err, (uint32_t)(s1)), e2 = (uint32_t)cf_bperm((int)lf.err, (uint32_t)(s2));
+				const bool use1 = R_PLANE, use2 = R_VECP || (R_PLANE && st == 1u);
+				const uint32_t cerr = lf.err + (use1 ? e1 : 0u) + (use2 ? e2 : 0u);
+				const uint32_t cidv = R_M6 ? 0u : (R_VECP ? R_CID : R_IDBASE + mypart);
+				const bool leader = active && (R_M6 ? L_HL == 0u : (R_VECP || (R_PLANE && R_SUB == 0u)));
+				const uint32_t old_err = L_CSLOT[18*CF_WG_THREADS], old_id = L_CSLOT[19*CF_WG_THREADS];
+				const bool take = leader && (cerr < old_err || (cerr == old_err && cidv < old_id));
+				best_err = take ? cerr : old_err;
 				if (take) {
-					L_CSLOT[(7 + k)*CF_WG_THREADS] = lf.w[k] | (R_PLANE ? w1 : 0u) |
-						((R_PLANE && st == 1u) ? w2 : 0u);
-					L_CSLOT[(11 + k)*CF_WG_THREADS] = R_VECP ? w2 : 0u;
+					L_CSLOT[18*CF_WG_THREADS] = cerr;
+					L_CSLOT[19*CF_WG_THREADS] = cidv;
+				}
+				{
+					const uint32_t a01 = (uint32_t)cf_bperm((int)lf.q0, (uint32_t)(s1)), a11 = (uint32_t)cf_bperm((int)lf.q1, (uint32_t)(s1));
+					const uint32_t a02 = (uint32_t)cf_bperm((int)lf.q0, (uint32_t)(s2)), a12 = (uint32_t)cf_bperm((int)lf.q1, (uint32_t)(s2));
+					const uint32_t pb1 = (uint32_t)cf_bperm((int)lf.pb, (uint32_t)(s1)), pb2 = (uint32_t)cf_bperm((int)lf.pb, (uint32_t)(s2));
+					if (take) {
+						L_CSLOT[0*CF_WG_THREADS] = lf.q0;
+						L_CSLOT[1*CF_WG_THREADS] = lf.q1;
+						L_CSLOT[2*CF_WG_THREADS] = R_PLANE ? a01 : 0u;
+						L_CSLOT[3*CF_WG_THREADS] = R_PLANE ? a11 : 0u;
+						// modes 4/5: the scalar plane's endpoints are parked in q[4], q[5] (byte 3)
+						L_CSLOT[4*CF_WG_THREADS] = R_VECP ? (a02 & 0xFF000000u) : ((R_PLANE && st == 1u) ? a02 : 0u);
+						L_CSLOT[5*CF_WG_THREADS] = R_VECP ? (a12 & 0xFF000000u) : ((R_PLANE && st == 1u) ? a12 : 0u);
+						L_CSLOT[6*CF_WG_THREADS] = lf.pb | (R_PLANE ? (pb1 << 2) : 0u) |
+							((R_PLANE && st == 1u) ? (pb2 << 4) : 0u);
+						// errors of the candidate's fits: subset 0 / vector plane / mode 6, then subset 1 or
+						// the scalar plane, then subset 2
+						L_CSLOT[15*CF_WG_THREADS] = lf.err;
+						L_CSLOT[16*CF_WG_THREADS] = R_PLANE ? e1 : (R_VECP ? e2 : 0u);
+						L_CSLOT[17*CF_WG_THREADS] = (R_PLANE && st == 1u) ? e2 : 0u;
+					}
+				}
+#pragma unroll
+				for (int k = 0; k < 4; ++k) {
+					const uint32_t w1 = (uint32_t)cf_bperm((int)lf.w[k], (uint32_t)(s1));
+					const uint32_t w2 = (uint32_t)cf_bperm((int)lf.w[k], (uint32_t)(s2));
+					if (take) {
+						L_CSLOT[(7 + k)*CF_WG_THREADS] = lf.w[k] | (R_PLANE ? w1 : 0u) |
+							((R_PLANE && st == 1u) ? w2 : 0u);
+						L_CSLOT[(11 + k)*CF_WG_THREADS] = R_VECP ? w2 : 0u;
+					}
 				}
 			}
 			// A zero-error candidate cannot be beaten by a later one (ids grow with the
@@ -1714,6 +1830,8 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				gb = __ballot(gmin >= (UNITW ? 48u : 256u));     // oracle: gate2
 				solved = gb == 0ull;
 			}
+#undef R_ROW
+#undef R_WORDS
 #undef R_NPER0
 #undef R_REL
 #undef R_SLOT

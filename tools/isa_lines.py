@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Static VALU instructions of one kernel instance per region of its source, from the line table of the assembly.
+"""Static VALU, scalar and branch instructions of one kernel instance per region of its source, from the line table
+of the assembly.
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -gline-tables-only \
           --cuda-device-only -S -o bc7.s cuttlefish_amd/csrc/bc7_encode.hip
@@ -7,8 +8,12 @@
 
 Inlined code keeps the line of the statement it came from, so a region is a range of source lines: from the first
 line that contains its start text to the line before the one that contains its end text.  Lines of other files
-(headers) are counted per file.  The counts are static: a region inlined at n call sites is counted n times, a
-loop body once per copy.  What runs how often is not in this table.
+(headers) are counted per file.  Instructions the compiler gives line 0 (merged or generated code: the rejoin of a
+divergent branch, a hoisted constant) go to the region of the last source line before them.  Scalar instructions are
+every s_* that is no branch (s_nop and s_waitcnt among them), branches every s_branch / s_cbranch_*.  The counts are
+static: a region inlined at n call sites is counted n times, a loop body once per copy.  What runs how often is not
+in this table.  A start or end text may be a tuple of alternatives: the first line that holds any of them (the same
+region in sources that word its opening differently).
 """
 import argparse
 import collections
@@ -16,6 +21,7 @@ import os
 import re
 
 # (label, text that opens the region, text of the first line after it); searched in this order from the top
+_ASSEMBLY = ("// the fit this lane's geometry-cache column now holds", "// ---- assemble candidates in their leader lanes")
 BC7_REGIONS = (
     ("quantize", "__device__ __forceinline__ void quantize(", "// View of one block's texels in LDS"),
     ("assign_lsq_lane: palette", "__device__ __forceinline__ void assign_lsq_lane(", "\tuint32_t err = pp_sum;"),
@@ -23,11 +29,30 @@ BC7_REGIONS = (
     ("assign_lsq_lane: refit sums", "\tf.err = err;", "// Least squares WITH the quantisation inside"),
     ("refit_window", "__device__ __forceinline__ void refit_window(", "// Fit-geometry cache"),
     ("fit_lane", "__device__ __forceinline__ void fit_lane(", "__device__ __forceinline__ uint32_t w2i("),
+    ("pack_block_group", "__device__ __forceinline__ uint4 pack_block_group(", "// The 14 integer moments of a set of texels"),
+    ("phase 1", "// ---- phase 1: partition scores", "// ---- lane roles ----"),
+    ("lane roles before the fit", "// ---- lane roles ----", "\t\t\tuint32_t wl[4] = {wt[0], wt[1], wt[2], wt[3]};"),
+    ("starts-trip epilogue", "// the roles below are computed again from here", _ASSEMBLY),
+    ("candidate assembly", _ASSEMBLY, "#undef R_"),
+    ("perturbation pass", "// ---- endpoint perturbation (oracle: uber_refine)", "\treturn pack_block_group("),
 )
 
 
 def is_valu(op):
     return op.startswith("v_") and not op.startswith(("v_readlane", "v_readfirstlane", "v_writelane"))
+
+
+def is_branch(op):
+    return op.startswith(("s_branch", "s_cbranch"))
+
+
+def is_salu(op):
+    return op.startswith("s_") and not is_branch(op)
+
+
+def _find(src, text, at):
+    texts = (text,) if isinstance(text, str) else text
+    return next((i for i in range(at, len(src)) if any(t in src[i] for t in texts)), None)
 
 
 def main():
@@ -39,15 +64,15 @@ def main():
     src = open(a.source).read().split("\n")
     regions, at = [], 0
     for label, start, end in BC7_REGIONS:
-        s = next((i for i in range(at, len(src)) if start in src[i]), None)
+        s = _find(src, start, at)
         if s is None:
             raise SystemExit("%s: no line with %r (region %r): update BC7_REGIONS" % (a.source, start, label))
-        e = next((i for i in range(s + 1, len(src)) if end in src[i]), None)
+        e = _find(src, end, s + 1)
         if e is None:
             raise SystemExit("%s: no line with %r after line %d (end of region %r): update BC7_REGIONS" % (a.source, end, s + 1, label))
         regions.append((label, s + 1, e))        # 1-based, inclusive
         at = s
-    files, counts, ops = {}, collections.Counter(), collections.defaultdict(collections.Counter)
+    files, counts, ops = {}, collections.defaultdict(collections.Counter), collections.defaultdict(collections.Counter)
     inside, cur = False, ("?", 0)
     for line in open(a.asm):
         t = line.strip()
@@ -65,21 +90,25 @@ def main():
             continue
         m = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
         if m:
-            cur = (files.get(int(m.group(1)), "?"), int(m.group(2)))
+            if int(m.group(2)) != 0:          # line 0 stays with the source line before it
+                cur = (files.get(int(m.group(1)), "?"), int(m.group(2)))
             continue
         op = t.split()[0] if t and not t.startswith((".", ";")) and not t.endswith(":") else ""
-        if not is_valu(op):
+        kind = "valu" if is_valu(op) else ("branch" if is_branch(op) else ("salu" if is_salu(op) else None))
+        if kind is None:
             continue
         key = "other files: " + cur[0]
         if cur[0] == os.path.basename(a.source):
             key = next((lab for lab, s, e in regions if s <= cur[1] <= e), "rest of " + cur[0])
-        counts[key] += 1
-        ops[key][op.replace("_e32", "").replace("_e64", "")] += 1
-    total = sum(counts.values())
-    print("%s: %d static VALU instructions" % (a.kernel, total))
-    for key, n in sorted(counts.items(), key=lambda kv: -kv[1]):
+        counts[key][kind] += 1
+        if kind == "valu":
+            ops[key][op.replace("_e32", "").replace("_e64", "")] += 1
+    total = {k: sum(c[k] for c in counts.values()) for k in ("valu", "salu", "branch")}
+    print("%s: %d static VALU instructions, %d scalar, %d branches" % (a.kernel, total["valu"], total["salu"], total["branch"]))
+    print("  %-34s %5s  %6s  %5s %6s   %s" % ("region", "VALU", "", "SALU", "branch", "most frequent VALU"))
+    for key, c in sorted(counts.items(), key=lambda kv: -kv[1]["valu"]):
         top = ", ".join("%s %d" % kv for kv in ops[key].most_common(6))
-        print("  %-34s %5d  %4.1f %%   %s" % (key, n, 100.0*n/total, top))
+        print("  %-34s %5d  %4.1f %%  %5d  %5d   %s" % (key, c["valu"], 100.0*c["valu"]/max(total["valu"], 1), c["salu"], c["branch"], top))
 
 
 if __name__ == "__main__":
