@@ -39,6 +39,7 @@
 #include "cf_device.h"
 #include "bc7_packed.h"
 #include "bc7_roles.h"
+#include "bc7_cand.h"
 
 namespace {
 
@@ -56,16 +57,11 @@ __device__ __forceinline__ int cf_bperm(int v, uint32_t src)
 // what every lane of a stream trip does, as two words per (layout, row, lane): bc7_roles.h
 __device__ const cf_bc7_role_table k_bc7_roles = cf_bc7_make_roles();
 
-__device__ const uint16_t k_part2[64] = {
-	0xcccc, 0x8888, 0xeeee, 0xecc8, 0xc880, 0xfeec, 0xfec8, 0xec80,
-	0xc800, 0xffec, 0xfe80, 0xe800, 0xffe8, 0xff00, 0xfff0, 0xf000,
-	0xf710, 0x008e, 0x7100, 0x08ce, 0x008c, 0x7310, 0x3100, 0x8cce,
-	0x088c, 0x3110, 0x6666, 0x366c, 0x17e8, 0x0ff0, 0x718e, 0x399c,
-	0xaaaa, 0xf0f0, 0x5a5a, 0x33cc, 0x3c3c, 0x55aa, 0x9696, 0xa55a,
-	0x73ce, 0x13c8, 0x324c, 0x3bdc, 0x6996, 0xc33c, 0x9966, 0x0660,
-	0x0272, 0x04e4, 0x4e40, 0x2720, 0xc936, 0x936c, 0x39c6, 0x639c,
-	0x9336, 0x9cc6, 0x817e, 0xe718, 0xccf0, 0x0fcc, 0x7744, 0xee22
-};
+// what a stored candidate is, by id, and the texels of its fits (bc7_cand.h)
+__device__ const cf_bc7_cand_table k_bc7_cands = cf_bc7_make_cands();
+__device__ const cf_bc7_mask_table k_bc7_masks = cf_bc7_make_masks();
+
+__device__ const uint16_t k_part2[64] = CF_BC7_PART2_INIT;
 
 __device__ const uint8_t k_anchor2[64] = {
 	15,15,15,15,15,15,15,15, 15,15,15,15,15,15,15,15,
@@ -74,16 +70,7 @@ __device__ const uint8_t k_anchor2[64] = {
 	 6, 2, 6, 8,15,15, 2, 2, 15,15,15,15,15, 2, 2,15
 };
 
-__device__ const uint32_t k_part3[64] = {
-	0xaa685050, 0x6a5a5040, 0x5a5a4200, 0x5450a0a8, 0xa5a50000, 0xa0a05050, 0x5555a0a0, 0x5a5a5050,
-	0xaa550000, 0xaa555500, 0xaaaa5500, 0x90909090, 0x94949494, 0xa4a4a4a4, 0xa9a59450, 0x2a0a4250,
-	0xa5945040, 0x0a425054, 0xa5a5a500, 0x55a0a0a0, 0xa8a85454, 0x6a6a4040, 0xa4a45000, 0x1a1a0500,
-	0x0050a4a4, 0xaaa59090, 0x14696914, 0x69691400, 0xa08585a0, 0xaa821414, 0x50a4a450, 0x6a5a0200,
-	0xa9a58000, 0x5090a0a8, 0xa8a09050, 0x24242424, 0x00aa5500, 0x24924924, 0x24499224, 0x50a50a50,
-	0x500aa550, 0xaaaa4444, 0x66660000, 0xa5a0a5a0, 0x50a050a0, 0x69286928, 0x44aaaa44, 0x66666600,
-	0xaa444444, 0x54a854a8, 0x95809580, 0x96969600, 0xa85454a8, 0x80959580, 0xaa141414, 0x96960000,
-	0xaaaa1414, 0xa05050a0, 0xa0a5a5a0, 0x96000000, 0x40804080, 0xa9a8a9a8, 0xaaaaaa44, 0x2a4a5254
-};
+__device__ const uint32_t k_part3[64] = CF_BC7_PART3_INIT;
 
 __device__ const uint8_t k_anchor3a[64] = {
 	 3, 3,15,15, 8, 3,15,15,  8, 8, 6, 6, 6, 5, 3, 3,
@@ -148,9 +135,12 @@ __device__ __forceinline__ void cand_store(uint32_t* slot, const Cand& c)
 __device__ __forceinline__ uint32_t ub(uint32_t v, int c) { return (v >> (8*c)) & 255u; }
 __device__ __forceinline__ float fb(uint32_t v, int c) { return (float)((v >> (8*c)) & 255u); }
 
+// One median instruction.  Equal to the two compares and selects for every finite x, but that -0.0 may come out as
+// +0.0, which changes no product, floorf or difference downstream; no active lane clamps a NaN (axis, mean and extremes
+// of a non-empty subset are finite, and a singular refit divides by 64).
 __device__ __forceinline__ float clamp255(float x)
 {
-	return x < 0.0f ? 0.0f : (x > 255.0f ? 255.0f : x);
+	return __builtin_amdgcn_fmed3f(x, 0.0f, 255.0f);
 }
 
 // BC7 interpolation weight k of an ib-bit index: ((k*64 + d/2)/d), d = 2^ib - 1
@@ -369,8 +359,17 @@ __device__ __forceinline__ uint32_t ycc_pp_sum(const Tex& tx, uint32_t mask, con
 }
 
 // Timing-ablation switches for tools/ab_bench.sh (never set in the product build).
+//   64: the pack is a trivial store of the winner's id and lane (what the bit-packing costs)
+//  128: the starts trip and the perturbation pass take a constant geometry (mode 6) instead of decoding their
+//       candidate's (what the decode costs; the fits then run on other arguments, so only the levels' difference
+//       to the parent says something)
 #ifndef CF_BC7_ABLATE
 #define CF_BC7_ABLATE 0
+#endif
+// A/B switch: 0 decodes a stored candidate from its id (fit_geo, geo_src: the ladders) instead of reading the candidate
+// word its leader stored (bc7_cand.h).  Same payload either way.
+#ifndef CF_BC7_CANDW
+#define CF_BC7_CANDW 1
 #endif
 
 // Diagnostic counters (never set in the product build): per wave pass, how often the starts trip reads the
@@ -893,6 +892,11 @@ __device__ __forceinline__ uint4 pack_block_group(const uint32_t* wcol, uint32_t
 	bool pair)
 {
 	const uint32_t h = lane >> 5, hl = pair ? (lane & 31u) : lane, hbase = pair ? (lane & 32u) : 0u;
+	if (CF_BC7_ABLATE & 64) {
+		uint4 r;
+		r.x = id; r.y = wcol[0]; r.z = wcol[CF_WG_THREADS]; r.w = h;
+		return r;
+	}
 	uint32_t mode, part = 0, rot = 0, isel = 0;
 	if (id == 0u) mode = 6;
 	else if (id < 5u) { mode = 5; rot = id - 1u; }
@@ -1232,6 +1236,40 @@ __device__ __forceinline__ FitGeo fit_geo(uint32_t id, uint32_t kf)
 	return g;
 }
 
+// The same geometry from what the candidate's leader stored with it: the candidate word (word 6 of its column,
+// bc7_cand.h) by bit-field extracts, the fit's texels by one table load.  The word of a column that holds no candidate is
+// whatever the word held before: every field is masked to its range, and the lanes that read it are idle.
+__device__ __forceinline__ FitGeo cand_geo(uint32_t cw, uint32_t id, uint32_t kf)
+{
+	const cf_bc7_cand_fit c = cf_bc7_cand_fit_of(cw, id, kf);
+	FitGeo g;
+	g.mode = c.mode; g.part = c.part; g.rot = c.rot; g.isel = c.isel; g.ns = c.ns; g.nfits = c.nfits;
+	g.cb = c.cb; g.ab = c.ab; g.pbk = c.pbk; g.ib = c.ib; g.chm = c.chm;
+	g.m6 = c.m6; g.planes45 = c.planes45; g.sca = c.sca;
+	g.mask = k_bc7_masks.m[c.mi];
+	return g;
+}
+
+// Geometry of fit kf of the candidate stored in column wc
+__device__ __forceinline__ FitGeo column_geo(const uint32_t* wc, uint32_t id, uint32_t kf)
+{
+	if (CF_BC7_ABLATE & 128)
+		return fit_geo(0u, 0u);
+	return CF_BC7_CANDW ? cand_geo(wc[6*CF_WG_THREADS], id, kf) : fit_geo(id, kf);
+}
+
+// geo_tag / geo_src of a candidate whose geometry is at hand: no id ladder
+__device__ __forceinline__ uint32_t geo_tag(const FitGeo& g, uint32_t id, uint32_t fi) { return id*4u + (g.m6 ? 0u : fi); }
+__device__ __forceinline__ uint32_t geo_src(const FitGeo& g, uint32_t fi, uint32_t wl, bool lay32)
+{
+	uint32_t s = wl + fi;
+	if (g.m6) s = wl;
+	else if (g.planes45) s = fi ? wl + (lay32 ? (g.mode == 5u ? 4u : 1u) : 12u) : wl;
+	else if (lay32 && g.ns == 3u && fi == 2u)
+		s = (wl & 32u) + (((wl & 31u) - 11u) >> 1);
+	return s & 63u;
+}
+
 // Store a fit (quantised fields, p-bits, weights, error) into fit slot kf of a candidate's column.
 __device__ __forceinline__ void column_put_fit(uint32_t* wc, const FitGeo& g, uint32_t kf, uint32_t q0, uint32_t q1,
 	uint32_t pb, const uint32_t (&w)[4], uint32_t err)
@@ -1542,12 +1580,13 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				const uint32_t k = koff + (lay32 ? (L_HL >> 3) : (lane >> 4));
 				const uint32_t wl = TOP_LANE(k & 7u);
 				const uint32_t id = cbase[wl + 19*CF_WG_THREADS], cerr = cbase[wl + 18*CF_WG_THREADS];
-				const bool n3 = lay32 && id >= 192u && id < 320u;
+				// (three subsets, from the candidate word: ids 192 .. 319)
+				const bool n3 = lay32 && (CF_BC7_CANDW ? CF_CAND_NS(cbase[wl + 6*CF_WG_THREADS]) == 3u : id >= 192u && id < 320u);
 				const uint32_t j8 = L_HL & 7u;
 				const uint32_t v = lay32 ? (n3 ? (j8 >= 3u ? 1u : 0u) : (L_HL >> 1) & 3u) : (lane >> 2) & 3u;
 				const uint32_t fi = lay32 ? (n3 ? (j8 >= 6u ? 3u : j8 - 3u*v) : (L_HL & 1u)) : (lane & 3u);
 				const uint32_t err0 = cbase[TOP_LANE(0u) + 18*CF_WG_THREADS];
-				const FitGeo g = fit_geo(id, fi);
+				const FitGeo g = column_geo(cbase + wl, id, fi);
 				m6 = g.m6; sca = g.sca; rot = g.rot; cb = g.cb; ab = g.ab; pbk = g.pbk; ib = g.ib; mask = g.mask;
 				chm_s = g.chm;
 				active = L_SLOT_OK && k < ntop && cerr != 0xFFFFFFFFu && err0 != 0u && (g.m6 ? fi < 2u : fi < g.nfits);
@@ -1555,8 +1594,8 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				frac = v == 0u ? 0.0f : (v == 1u ? -1.0f/16.0f : (v == 2u ? 1.0f/8.0f : 3.0f/16.0f));
 				// parts A and B of the fit come from the cache when every active lane of the wave finds its fit there
 				// (in its own block's half); otherwise the whole wave computes them
-				gsrc = geo_src(id, fi, wl, lay32);
-				const bool ghit = gbase[gsrc + 12*CF_WG_THREADS] == geo_tag(id, fi) && (!lay32 || ((gsrc ^ wl) & 32u) == 0u);
+				gsrc = CF_BC7_CANDW ? geo_src(g, fi, wl, lay32) : geo_src(id, fi, wl, lay32);
+				const bool ghit = gbase[gsrc + 12*CF_WG_THREADS] == (CF_BC7_CANDW ? geo_tag(g, id, fi) : geo_tag(id, fi)) && (!lay32 || ((gsrc ^ wl) & 32u) == 0u);
 				gmode = __ballot(active && !ghit) == 0ull ? 2u : 0u;
 				narrow = __ballot(active && (g.m6 || g.ib > 2u)) == 0ull;
 				CF_DIAG_COUNT(CF_DIAG_STARTS, true);
@@ -1674,12 +1713,12 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				const uint32_t k2 = koff + (lay32 ? (L_HL >> 3) : (lane >> 4));
 				const uint32_t wl2 = TOP_LANE(k2 & 7u);
 				const uint32_t id2 = cbase[wl2 + 19*CF_WG_THREADS], cerr2 = cbase[wl2 + 18*CF_WG_THREADS];
-				const bool n32 = lay32 && id2 >= 192u && id2 < 320u;
+				const bool n32 = lay32 && (CF_BC7_CANDW ? CF_CAND_NS(cbase[wl2 + 6*CF_WG_THREADS]) == 3u : id2 >= 192u && id2 < 320u);
 				const uint32_t j82 = L_HL & 7u;
 				const uint32_t v2 = lay32 ? (n32 ? (j82 >= 3u ? 1u : 0u) : (L_HL >> 1) & 3u) : (lane >> 2) & 3u;
 				const uint32_t fi2 = lay32 ? (n32 ? (j82 >= 6u ? 3u : j82 - 3u*v2) : (L_HL & 1u)) : (lane & 3u);
 				const uint32_t err02 = cbase[TOP_LANE(0u) + 18*CF_WG_THREADS];
-				const FitGeo g2 = fit_geo(id2, fi2);
+				const FitGeo g2 = column_geo(cbase + wl2, id2, fi2);
 				const uint32_t kf2 = g2.m6 ? 0u : fi2;
 				const bool active2 = L_SLOT_OK && k2 < ntop && cerr2 != 0xFFFFFFFFu && err02 != 0u && (g2.m6 ? fi2 < 2u : fi2 < g2.nfits);
 				// best start of the fit: minimum of (error, v) over the four lanes of (k, fit)
@@ -1751,7 +1790,9 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 					// modes 4/5: the scalar plane's endpoints are parked in q[4], q[5] (byte 3)
 					L_CSLOT[4*CF_WG_THREADS] = a02 & m4;
 					L_CSLOT[5*CF_WG_THREADS] = a12 & m4;
-					L_CSLOT[6*CF_WG_THREADS] = lf.pb | ((pb1 << 2) & m1) | ((pb2 << 4) & m3);
+					// the p-bits, and above them what the candidate is (bc7_cand.h): no later phase decodes it from its id
+					// (stored where it is read: the levels that come back to their candidates, Normal and up)
+					L_CSLOT[6*CF_WG_THREADS] = lf.pb | ((pb1 << 2) & m1) | ((pb2 << 4) & m3) | ((CF_BC7_CANDW && uber2) ? k_bc7_cands.w[cf_bc7_cand_index(cidv)] : 0u);
 					// errors of the candidate's fits: subset 0 / vector plane / mode 6, then subset 1 or
 					// the scalar plane, then subset 2
 					L_CSLOT[15*CF_WG_THREADS] = lf.err;
@@ -1901,7 +1942,7 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			uint32_t* wc = cbase + wl;
 			const uint32_t id = wc[19*CF_WG_THREADS], cerr = wc[18*CF_WG_THREADS];
 			const uint32_t kf0 = (L_HL >> 4) + 2u*fp;
-			const FitGeo g0 = fit_geo(id, kf0);
+			const FitGeo g0 = column_geo(wc, id, kf0);
 			const uint32_t kf = g0.m6 ? 0u : kf0, mv = g0.m6 ? (L_HL >> 1) & 15u : (L_HL & 15u);
 			const FitGeo g = g0;
 			const bool act = L_SLOT_OK && L_HL < 64u && (g.m6 ? (L_HL < 32u && !fp) : kf < g.nfits) && cerr != 0u && cerr != 0xFFFFFFFFu;
@@ -1911,8 +1952,8 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			// sum over the fit's texels of sum_c p_c^2 (the constant part of its error): word 11 of the fit-geometry cache
 			// when every active lane of the wave finds its fit's column there (the starts trip's test), a row loop otherwise
 			uint32_t pp_sum = 0;
-			const uint32_t gsrc = geo_src(id, kf, wl, lay32);
-			const bool ghit = gbase[gsrc + 12*CF_WG_THREADS] == geo_tag(id, kf) && (!lay32 || ((gsrc ^ wl) & 32u) == 0u);
+			const uint32_t gsrc = CF_BC7_CANDW ? geo_src(g, kf, wl, lay32) : geo_src(id, kf, wl, lay32);
+			const bool ghit = gbase[gsrc + 12*CF_WG_THREADS] == (CF_BC7_CANDW ? geo_tag(g, id, kf) : geo_tag(id, kf)) && (!lay32 || ((gsrc ^ wl) & 32u) == 0u);
 			const bool pphit = __ballot(act && !ghit) == 0ull;
 			if (pphit)
 				pp_sum = gbase[gsrc + 11*CF_WG_THREADS];
