@@ -193,7 +193,9 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_decode_batch", "cfhip_decode_batch_device", "cfhip_decode_out_supported",
            "cfhip_compare_batch", "cfhip_compare_batch_device",
            "cfhip_rdo_supported", "cfhip_rdo", "cfhip_rdo_device",
-           "cfhip_rdo_ex", "cfhip_rdo_ex_device"]
+           "cfhip_rdo_ex", "cfhip_rdo_ex_device",
+           "cfhip_lz_size", "cfhip_lz_size_device", "cfhip_lz_slice_bytes", "cfhip_lz_stage_ms",
+           "cfhip_rdo_target", "cfhip_rdo_target_device"]
 
 
 class Layout(enum.IntEnum):
@@ -324,6 +326,31 @@ class RdoStats(ctypes.Structure):
     def as_dict(self) -> dict:
         return {n: int(getattr(self, n)) for n, _ in self._fields_}
 
+
+class LzSpan(ctypes.Structure):
+    """struct cfhip_lz_span"""
+    _fields_ = [("bytes", ctypes.c_void_p), ("n", ctypes.c_size_t)]
+
+
+class LzStats(ctypes.Structure):
+    """struct cfhip_lz_stats"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("bytes_in", "bits_q16", "est_bytes", "literals", "matches",
+                                               "matched_bytes")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class RdoTargetResult(ctypes.Structure):
+    """struct cfhip_rdo_target_result"""
+    _fields_ = [("lambda16", ctypes.c_uint32), ("reached", ctypes.c_uint32), ("trials", ctypes.c_uint32),
+                ("est_bytes_plain", ctypes.c_uint64), ("est_bytes_final", ctypes.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+LZ_STAGES = ("keys", "sort", "match", "parse", "cost")      # cfhip_lz_stage_ms
 
 RDO_NO_CAP = 0xFFFFFFFF         # max_sse_increase: no cap
 RDO_ROW_ABOVE = 1               # CFHIP_RDO_ROW_ABOVE
@@ -537,6 +564,24 @@ def load_library(path: Optional[str] = None):
                                       ctypes.c_size_t, ctypes.POINTER(RdoExParams), u8p, ctypes.c_void_p,
                                       ctypes.c_void_p]
     L.cfhip_rdo_ex_device.restype = ctypes.c_int
+    L.cfhip_lz_size.argtypes = [ctypes.c_void_p, ctypes.POINTER(LzSpan), ctypes.c_size_t, ctypes.c_void_p]
+    L.cfhip_lz_size.restype = ctypes.c_int
+    L.cfhip_lz_size_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(LzSpan), ctypes.c_size_t, ctypes.c_void_p,
+                                       ctypes.c_void_p]
+    L.cfhip_lz_size_device.restype = ctypes.c_int
+    L.cfhip_lz_slice_bytes.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
+    L.cfhip_lz_slice_bytes.restype = ctypes.c_size_t
+    L.cfhip_lz_stage_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    L.cfhip_lz_stage_ms.restype = ctypes.c_int
+    L.cfhip_rdo_target.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RdoSurface),
+                                   ctypes.c_size_t, ctypes.POINTER(RdoExParams), ctypes.POINTER(ctypes.c_uint8),
+                                   ctypes.c_void_p, ctypes.c_float, ctypes.POINTER(RdoTargetResult)]
+    L.cfhip_rdo_target.restype = ctypes.c_int
+    L.cfhip_rdo_target_device.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RdoSurface),
+                                          ctypes.c_size_t, ctypes.POINTER(RdoExParams), ctypes.POINTER(ctypes.c_uint8),
+                                          ctypes.c_void_p, ctypes.c_float, ctypes.POINTER(RdoTargetResult),
+                                          ctypes.c_void_p]
+    L.cfhip_rdo_target_device.restype = ctypes.c_int
     L.cfhip_decode_out_supported.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.cfhip_decode_out_supported.restype = ctypes.c_int
     _lib = L
@@ -1123,6 +1168,92 @@ class Context:
         self._check(entry(
             self._h, int(fmt), int(typ), surf, n, ctypes.byref(params), self._mask(mask),
             ctypes.c_void_p(int(stats)) if stats else None, ctypes.c_void_p(stream) if stream else None))
+
+    def lz_size(self, payloads) -> dict:
+        """The deflate-size estimate (cfhip_lz_size) of a byte stream: one array / bytes object, or a sequence of them
+        taken as their concatenation.  Returns bytes_in, bits_q16, est_bytes, literals, matches, matched_bytes --
+        the numbers of tests/lzsize_ref.py, exactly."""
+        if isinstance(payloads, (bytes, bytearray, np.ndarray)):
+            payloads = [payloads]
+        parts = [np.frombuffer(bytes(p), np.uint8) if isinstance(p, (bytes, bytearray))
+                 else np.ascontiguousarray(p).reshape(-1).view(np.uint8) for p in payloads]
+        spans = (LzSpan*max(len(parts), 1))()
+        for i, p in enumerate(parts):
+            spans[i].bytes, spans[i].n = (p.ctypes.data if p.size else None), p.size
+        out = LzStats()
+        self._check(self._lib.cfhip_lz_size(self._h, spans, len(parts), ctypes.addressof(out)))
+        return out.as_dict()
+
+    def lz_size_device(self, spans: Sequence[tuple], out: int, stream: int = 0):
+        """Device path of lz_size.  spans: (device pointer as int, bytes) pairs; out: device pointer to one
+        cfhip_lz_stats (overwritten).  stream 0 = the context's stream (the call then synchronises)."""
+        arr = (LzSpan*max(len(spans), 1))()
+        for i, (ptr, n) in enumerate(spans):
+            arr[i].bytes, arr[i].n = int(ptr) or None, int(n)
+        self._check(self._lib.cfhip_lz_size_device(self._h, arr, len(spans), ctypes.c_void_p(int(out)) if out else None,
+                                                   ctypes.c_void_p(stream) if stream else None))
+
+    def lz_slice_bytes(self, nbytes: int = 0) -> int:
+        """Set the slice the estimator cuts long streams into (whole blocks of 65536 bytes; 0: the default); returns
+        the previous one.  Results do not depend on it; the context's scratch does."""
+        return int(self._lib.cfhip_lz_slice_bytes(self._h, int(nbytes)))
+
+    def lz_stage_ms(self) -> dict:
+        """Kernel ms of the last estimate's stages: keys, sort, match, parse, cost"""
+        ms = (ctypes.c_float*5)()
+        self._check(self._lib.cfhip_lz_stage_ms(self._h, ms))
+        return dict(zip(LZ_STAGES, (float(v) for v in ms)))
+
+    def rdo_target(self, payloads: Sequence[np.ndarray], sources: Sequence[np.ndarray], fmt, typ=Type.UNorm,
+                   target_ratio: float = 0.85, lam: float = 32.0, max_sse_increase: Optional[int] = None, mask=None,
+                   row_above: bool = False, window_bytes: Optional[int] = None):
+        """The rate-distortion pass to a target (cfhip_rdo_target): the smallest lambda <= lam (in steps of 1/16)
+        whose payloads, concatenated, are estimated (lz_size) at no more than target_ratio x the estimate of the
+        payloads as given; found by bisection on the device.  Returns (the payloads, one dict of statistics per
+        surface, the result: lambda16, reached, trials, est_bytes_plain, est_bytes_final).  reached 0: even lam
+        misses the target, and the pass at lam is returned."""
+        n = len(payloads)
+        if len(sources) != n:
+            raise ValueError("payloads and sources must list the same surfaces")
+        params = make_rdo_ex_params(lam, max_sse_increase, row_above, window_bytes)
+        surf = (RdoSurface*max(n, 1))()
+        srcs = [np.ascontiguousarray(s) for s in sources]
+        if any(s.ndim != 3 or s.shape[2] != 4 for s in srcs):
+            raise ValueError("sources must be (h, w, 4) uint8, float16 or float32")
+        parts = [np.ascontiguousarray(p, dtype=np.uint8).reshape(-1) for p in payloads]
+        outs = [np.empty_like(p) for p in parts]
+        for i, (p, o, s) in enumerate(zip(parts, outs, srcs)):
+            surf[i].blocks, surf[i].blocks_bytes = p.ctypes.data, p.nbytes
+            surf[i].out, surf[i].out_capacity = o.ctypes.data, o.nbytes
+            surf[i].height, surf[i].width = s.shape[:2]
+            surf[i].pixels, surf[i].pixel_type, surf[i].row_pitch_bytes = s.ctypes.data, int(pixel_type_of(s)), s.strides[0]
+        stats = (RdoStats*max(n, 1))()
+        res = RdoTargetResult()
+        self._check(self._lib.cfhip_rdo_target(self._h, int(fmt), int(typ), surf, n, ctypes.byref(params),
+                                               self._mask(mask), ctypes.addressof(stats), float(target_ratio),
+                                               ctypes.byref(res)))
+        return outs, [stats[i].as_dict() for i in range(n)], res.as_dict()
+
+    def rdo_target_device(self, surfaces: Sequence[dict], fmt, typ, target_ratio: float, lam: float, stats: int,
+                          max_sse_increase: Optional[int] = None, mask=None, stream: int = 0, row_above: bool = False,
+                          window_bytes: Optional[int] = None) -> dict:
+        """Device path of rdo_target: the surfaces and stats of rdo_device (out may equal blocks: the pristine
+        payloads are then kept in the context's scratch).  Blocks on either stream; returns the result dict."""
+        n = len(surfaces)
+        params = make_rdo_ex_params(lam, max_sse_increase, row_above, window_bytes)
+        surf = (RdoSurface*max(n, 1))()
+        for i, s in enumerate(surfaces):
+            surf[i].blocks, surf[i].out = int(s["blocks"]) or None, int(s["out"]) or None
+            surf[i].out_capacity = int(s["out_capacity"])
+            surf[i].width, surf[i].height = s["width"], s["height"]
+            surf[i].pixels, surf[i].pixel_type = int(s["pixels"]) or None, int(s["pixel_type"])
+            surf[i].row_pitch_bytes = s["row_pitch_bytes"]
+        res = RdoTargetResult()
+        self._check(self._lib.cfhip_rdo_target_device(
+            self._h, int(fmt), int(typ), surf, n, ctypes.byref(params), self._mask(mask),
+            ctypes.c_void_p(int(stats)) if stats else None, float(target_ratio), ctypes.byref(res),
+            ctypes.c_void_p(stream) if stream else None))
+        return res.as_dict()
 
     def unpack(self, payload: np.ndarray, fmt, typ, width: int, height: int) -> np.ndarray:
         """The payload of a standard (uncompressed) format, formats 1..28, back to texels on the GPU ->

@@ -144,7 +144,10 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  # the standard formats back to texels (csrc/std_unpack.hip) and their Pass A (csrc/compare.hip)
                  "cfhip_std_unpack_kernel", "cfhip_std_compare_kernel",
                  # the rate-distortion pass over BC1-5 / BC7 payloads (csrc/rdo.hip)
-                 "cfhip_rdo_kernel", "cfhip_rdo2d_kernel")
+                 "cfhip_rdo_kernel", "cfhip_rdo2d_kernel",
+                 # the deflate-size estimator (csrc/lzsize.hip); the sort between them is rocprim's
+                 "cfhip_lz_keys_kernel", "cfhip_lz_match_kernel", "cfhip_lz_parse_kernel", "cfhip_lz_cost_kernel",
+                 "cfhip_lz_final_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

@@ -11,6 +11,7 @@
 #include "compare_batch.h"
 #include "decode_batch.h"
 #include "rdo.h"
+#include "lzsize.h"
 #include "../../include/cuttlefish_hip.h"
 
 #include <cmath>
@@ -193,6 +194,12 @@ struct cfhip_ctx {
 	size_t mip3d_cap = 0;
 	void* d_pvrtc = nullptr;          // PVRTC1 encoder state: surface table, texels, colour words, modulation bytes
 	size_t pvrtc_cap = 0;
+	void* d_lz = nullptr;             // deflate-size estimator: one slice's scratch (csrc/lzsize.h), grown on demand
+	size_t lz_cap = 0;
+	size_t lz_slice = 0;              // cfhip_lz_slice_bytes: 0 = CFLZ_SLICE_DEFAULT
+	size_t lz_first_event = 0, lz_slices = 0;   // the last estimate's event pairs: CFLZ_STAGES per slice
+	void* d_rdo_keep = nullptr;       // cfhip_rdo_target: the pristine payloads every trial starts from
+	size_t rdo_keep_cap = 0;
 	std::map<int, void*> astc_tables; // per-format device tables (built on first use)
 	std::map<int, cfastc::AstcBlobHeader> astc_hdr;   // their headers (sizes the launch's dynamic LDS)
 	std::vector<hipEvent_t> events;   // start/stop pairs of the last call
@@ -638,7 +645,8 @@ int reserve(cfhip_ctx* ctx, void** buf, size_t* cap, size_t need)
 	return CFHIP_OK;
 }
 
-// The one owner of the staging buffers (d_src, d_out, d_batch, d_mip3d) for one call on one stream; the only code
+// The one owner of the staging buffers (d_src, d_out, d_batch, d_mip3d, and the estimator's d_lz and the target
+// search's d_rdo_keep) for one call on one stream; the only code
 // that writes staging_busy / staging_stream / staging_done.  Declared after the context's lock guard, so that it
 // ends before the lock is released.
 //  * acquire(): before the first touch of a buffer; the first call makes the stream wait for the last asynchronous
@@ -1307,6 +1315,8 @@ void cfhip_destroy(cfhip_ctx* ctx)
 	if (ctx->d_batch) (void)hipFree(ctx->d_batch);
 	if (ctx->d_mip3d) (void)hipFree(ctx->d_mip3d);
 	if (ctx->d_pvrtc) (void)hipFree(ctx->d_pvrtc);
+	if (ctx->d_lz) (void)hipFree(ctx->d_lz);
+	if (ctx->d_rdo_keep) (void)hipFree(ctx->d_rdo_keep);
 	if (ctx->d_src) (void)hipFree(ctx->d_src);
 	if (ctx->d_out) (void)hipFree(ctx->d_out);
 	delete ctx;
@@ -3017,11 +3027,12 @@ static int rdo_check(cfhip_ctx* ctx, const char* what, int format, int type, con
 
 // the surface table into staging, the counters cleared and the one launch of the call, timed as every encode launch
 // is; the entries hold device pointers by now
-static int rdo_launch(cfhip_ctx* ctx, StagingLease& lease, RdoPlan& p, cfhip_rdo_stats* stats)
+// keep_events: a trial of cfhip_rdo_target, whose event pairs join those of the trials before it
+static int rdo_launch(cfhip_ctx* ctx, StagingLease& lease, RdoPlan& p, cfhip_rdo_stats* stats, bool keep_events = false)
 {
 	static_assert(sizeof(cfhip_rdo_stats) == CFRDO_STATS*sizeof(unsigned long long), "the kernel's counters are the struct");
 	const hipStream_t stream = lease.stream;
-	if (!ctx->profiling)
+	if (!ctx->profiling && !keep_events)
 		ctx->events_used = 0;
 	ctx->events_stream = stream;
 	ctx->last_ms = -1.0f;
@@ -3174,6 +3185,384 @@ int cfhip_rdo_ex_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_su
 	const cfhip_rdo_ex_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats_device, void* stream_)
 {
 	return rdo_device(ctx, "rdo_ex_device", format, type, surfaces, n, nullptr, params, mask_rgba, stats_device, stream_);
+}
+
+// ---- deflate-size estimate of payloads (csrc/lzsize.hip, csrc/lzsize.h) and RDO to a target ratio ----------------
+struct LzPlan {
+	std::vector<cfhip_lz_span> spans;         // the non-empty ones
+	size_t total = 0;
+};
+
+// Every check of an estimator call, made before the context is touched.
+static int lz_check(cfhip_ctx* ctx, const char* what, const cfhip_lz_span* spans, size_t n, const void* out, bool host,
+	LzPlan* p)
+{
+	if (!out)
+		return fail(ctx, CFHIP_E_INVALID, "%s: out is NULL", what);
+	if (!host && (uintptr_t)out % 8u != 0)
+		return fail(ctx, CFHIP_E_INVALID, "%s: out must be 8-byte aligned", what);
+	if (n && !spans)
+		return fail(ctx, CFHIP_E_INVALID, "%s: spans is NULL", what);
+	for (size_t i = 0; i < n; ++i) {
+		if (!spans[i].n)
+			continue;
+		if (!spans[i].bytes)
+			return fail(ctx, CFHIP_E_INVALID, "%s: span %zu: bytes is NULL", what, i);
+		if (spans[i].n >= ((size_t)1 << 31) || p->total + spans[i].n >= ((size_t)1 << 31))
+			return fail(ctx, CFHIP_E_CAPACITY, "%s: the spans hold 2^31 bytes or more", what);
+		p->total += spans[i].n;
+		p->spans.push_back(spans[i]);
+	}
+	return CFHIP_OK;
+}
+
+// bytes [a, b) of the concatenated spans -> dst (device), on the stream
+static int lz_gather(cfhip_ctx* ctx, const LzPlan& p, size_t a, size_t b, uint8_t* dst, hipMemcpyKind kind, hipStream_t stream)
+{
+	size_t at = 0;
+	for (const cfhip_lz_span& s : p.spans) {
+		const size_t lo = std::max(a, at), hi = std::min(b, at + s.n);
+		if (lo < hi)
+			HIP_TRY(ctx, hipMemcpyAsync(dst + (lo - a), static_cast<const uint8_t*>(s.bytes) + (lo - at), hi - lo, kind, stream));
+		at += s.n;
+		if (at >= b)
+			break;
+	}
+	return CFHIP_OK;
+}
+
+static size_t lz_slice_of(const cfhip_ctx* ctx)
+{
+	size_t s = ctx->lz_slice ? ctx->lz_slice : (size_t)CFLZ_SLICE_DEFAULT;
+	s = std::min(std::max(s, (size_t)CFLZ_COSTBLK), (size_t)1 << 30);     // before rounding: no overflow, never 0
+	return (s + CFLZ_COSTBLK - 1u)/CFLZ_COSTBLK*CFLZ_COSTBLK;
+}
+
+// The estimate of p's stream (total > 0) into six counters on the device, enqueued on the lease's stream: the stream in
+// slices of whole cost blocks, each behind the W bytes before it.  out_device NULL: the scratch's own result slot,
+// returned in *result.  The caller has set up the call's event bookkeeping.
+static int lz_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hipMemcpyKind kind,
+	unsigned long long* out_device, unsigned long long** result)
+{
+	const hipStream_t stream = lease.stream;
+	const size_t slice = std::min(lz_slice_of(ctx), (p.total + CFLZ_COSTBLK - 1u)/CFLZ_COSTBLK*CFLZ_COSTBLK);
+	size_t sort_bytes = 0;
+	HIP_TRY(ctx, cfhip_lz_sort_bytes(slice + CFLZ_WINDOW, &sort_bytes));
+	const cflz_layout lay = cflz_scratch(slice, sort_bytes);
+	int rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, lay.total);
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* base = static_cast<uint8_t*>(ctx->d_lz);
+	unsigned long long* acc = reinterpret_cast<unsigned long long*>(base + lay.acc);
+	if (!out_device)
+		out_device = acc + 8;                 // the sums take 32 bytes of the 256 reserved
+	if (result)
+		*result = out_device;
+	HIP_TRY(ctx, hipMemsetAsync(acc, 0, 4u*sizeof(unsigned long long), stream));
+	ctx->lz_first_event = ctx->events_used;
+	ctx->lz_slices = 0;
+	for (size_t s0 = 0; s0 < p.total; s0 += slice) {
+		const size_t s1 = std::min(p.total, s0 + slice);
+		const size_t carry = s0 ? CFLZ_WINDOW : 0u;        // s0 >= one cost block > W
+		rc = lz_gather(ctx, p, s0 - carry, s1, base + lay.bytes, kind, stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		hipEvent_t ev[2*CFLZ_STAGES];
+		for (int k = 0; k < CFLZ_STAGES; ++k) {
+			rc = next_event_pair(ctx, &ev[2*k], &ev[2*k + 1]);
+			if (rc != CFHIP_OK)
+				return rc;
+		}
+		const hipError_t e = cfhip_launch_lz_slice(base, &lay, sort_bytes, (uint32_t)carry, (uint32_t)(s1 - s0), ev, stream);
+		if (e != hipSuccess)
+			return fail(ctx, CFHIP_E_DEVICE, "lz_size launch: %s", hipGetErrorString(e));
+		++ctx->lz_slices;
+	}
+	const hipError_t e = cfhip_launch_lz_final(acc, (unsigned long long)p.total, out_device, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "lz_size launch: %s", hipGetErrorString(e));
+	return CFHIP_OK;
+}
+
+static void lz_begin_call(cfhip_ctx* ctx, hipStream_t stream)
+{
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = "cfhip_lz_match_kernel";
+}
+
+int cfhip_lz_size(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, cfhip_lz_stats* out)
+{
+	static_assert(sizeof(cfhip_lz_stats) == 6*sizeof(unsigned long long), "the kernel's counters are the struct");
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	LzPlan p;
+	int rc = lz_check(ctx, "lz_size", spans, n_spans, out, true, &p);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!p.total) {
+		memset(out, 0, sizeof(*out));
+		return CFHIP_OK;
+	}
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, ctx->stream);
+	lz_begin_call(ctx, lease.stream);
+	unsigned long long* d_res = nullptr;
+	rc = lz_run(ctx, lease, p, hipMemcpyHostToDevice, nullptr, &d_res);
+	if (rc != CFHIP_OK)
+		return rc;
+	cfhip_lz_stats res;
+	HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
+	rc = lease.done(true);
+	if (rc != CFHIP_OK)
+		return rc;
+	*out = res;
+	return CFHIP_OK;
+}
+
+int cfhip_lz_size_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, cfhip_lz_stats* out_device,
+	void* stream_)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	LzPlan p;
+	int rc = lz_check(ctx, "lz_size_device", spans, n_spans, out_device, false, &p);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	lz_begin_call(ctx, lease.stream);
+	if (!p.total)
+		HIP_TRY(ctx, hipMemsetAsync(out_device, 0, sizeof(cfhip_lz_stats), lease.stream));
+	else {
+		rc = lz_run(ctx, lease, p, hipMemcpyDeviceToDevice, reinterpret_cast<unsigned long long*>(out_device), nullptr);
+		if (rc != CFHIP_OK)
+			return rc;
+	}
+	return lease.done(!stream_);
+}
+
+size_t cfhip_lz_slice_bytes(cfhip_ctx* ctx, size_t bytes)
+{
+	if (!ctx)
+		return 0;
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	const size_t before = lz_slice_of(ctx);
+	ctx->lz_slice = bytes;
+	return before;
+}
+
+int cfhip_lz_stage_ms(cfhip_ctx* ctx, float ms[CFLZ_STAGES])
+{
+	if (!ctx || !ms)
+		return CFHIP_E_INVALID;
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	const size_t first = ctx->lz_first_event, pairs = ctx->lz_slices*CFLZ_STAGES;
+	// every entry point names its kernel in last_kernel, so another call since the estimate shows there
+	if (!pairs || first + 2*pairs > ctx->events_used || ctx->last_kernel.compare(0, 8, "cfhip_lz") != 0)
+		return fail(ctx, CFHIP_E_INVALID, "lz_stage_ms: the last call on this context was no cfhip_lz_size*");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->events_stream));
+	for (int k = 0; k < CFLZ_STAGES; ++k)
+		ms[k] = 0.0f;
+	for (size_t i = 0; i < pairs; ++i) {
+		float t = 0.0f;
+		HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->events[first + 2*i], ctx->events[first + 2*i + 1]));
+		ms[i % CFLZ_STAGES] += t;
+	}
+	return CFHIP_OK;
+}
+
+// cfhip_rdo_target and cfhip_rdo_target_device
+static int rdo_target(cfhip_ctx* ctx, const char* what, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
+	const cfhip_rdo_ex_params* ex, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats, bool host, float target_ratio,
+	cfhip_rdo_target_result* result, void* stream_)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	RdoPlan p;
+	int rc = rdo_check(ctx, what, format, type, surfaces, n, nullptr, ex, mask_rgba, stats, host, &p);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (!n) {
+		if (result)
+			memset(result, 0, sizeof(*result));
+		return CFHIP_OK;
+	}
+	if (!(target_ratio > 0.0f && target_ratio < 1.0f))
+		return fail(ctx, CFHIP_E_INVALID, "%s: target_ratio %g is outside (0, 1)", what, (double)target_ratio);
+	if (!result)
+		return fail(ctx, CFHIP_E_INVALID, "%s: result is NULL", what);
+	size_t total = 0;
+	for (size_t i = 0; i < n; ++i)
+		total += p.payload[i];
+	if (total >= ((size_t)1 << 31))
+		return fail(ctx, CFHIP_E_CAPACITY, "%s: the payloads hold 2^31 bytes or more", what);
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, !host && stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	const hipStream_t stream = lease.stream;
+	// every launch of the search is timed: the call's event pairs start here and every trial adds its own
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	rc = lease.acquire();
+	if (rc != CFHIP_OK)
+		return rc;
+	// the pristine payloads: scratch for the host form and for surfaces optimised in place, else the caller's
+	std::vector<size_t> off(n), pix_off(n);
+	size_t keep = 0, po = 0;
+	for (size_t i = 0; i < n; ++i) {
+		off[i] = keep;
+		keep = (keep + p.payload[i] + 255u) & ~(size_t)255u;
+		pix_off[i] = po;
+		po = align16(po + (size_t)surfaces[i].width*p.texel[i]*surfaces[i].height);
+	}
+	// (the device form needs the copy only for surfaces optimised in place)
+	bool keeps = host;
+	for (size_t i = 0; i < n && !keeps; ++i)
+		keeps = surfaces[i].out == surfaces[i].blocks;
+	if (keeps)
+		rc = reserve(ctx, &ctx->d_rdo_keep, &ctx->rdo_keep_cap, keep);
+	cfhip_rdo_stats* d_stats = stats;
+	if (host) {
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, keep);
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, po + n*sizeof(cfhip_rdo_stats));
+	}
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* d_keep = static_cast<uint8_t*>(ctx->d_rdo_keep);
+	LzPlan plain, work;
+	for (size_t i = 0; i < n; ++i) {
+		const cfhip_rdo_surface& s = surfaces[i];
+		cfrdo_entry& e = p.entries[i];
+		if (host) {
+			uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
+			const size_t rowb = (size_t)s.width*p.texel[i];
+			HIP_TRY(ctx, hipMemcpyAsync(d_keep + off[i], s.blocks, p.payload[i], hipMemcpyHostToDevice, stream));
+			if (s.row_pitch_bytes == rowb)
+				HIP_TRY(ctx, hipMemcpyAsync(d + pix_off[i], s.pixels, rowb*s.height, hipMemcpyHostToDevice, stream));
+			else
+				HIP_TRY(ctx, hipMemcpy2DAsync(d + pix_off[i], rowb, s.pixels, s.row_pitch_bytes, rowb, s.height,
+					hipMemcpyHostToDevice, stream));
+			e.blocks = d_keep + off[i];
+			e.out = static_cast<uint8_t*>(ctx->d_src) + off[i];
+			e.pixels = d + pix_off[i];
+			e.pitch = rowb;
+			d_stats = reinterpret_cast<cfhip_rdo_stats*>(d + po);
+		} else if (s.out == s.blocks) {
+			HIP_TRY(ctx, hipMemcpyAsync(d_keep + off[i], s.blocks, p.payload[i], hipMemcpyDeviceToDevice, stream));
+			e.blocks = d_keep + off[i];
+		}
+		plain.spans.push_back(cfhip_lz_span{e.blocks, p.payload[i]});
+		work.spans.push_back(cfhip_lz_span{e.out, p.payload[i]});
+	}
+	plain.total = work.total = total;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	// one estimate, read back: every trial decides on the host what the next one is
+	auto estimate = [&](const LzPlan& of, uint64_t* est) -> int {
+		unsigned long long* d_res = nullptr;
+		int r = lz_run(ctx, lease, of, hipMemcpyDeviceToDevice, nullptr, &d_res);
+		if (r != CFHIP_OK)
+			return r;
+		cfhip_lz_stats st;
+		HIP_TRY(ctx, hipMemcpyAsync(&st, d_res, sizeof(st), hipMemcpyDeviceToHost, stream));
+		HIP_TRY(ctx, hipStreamSynchronize(stream));
+		*est = st.est_bytes;
+		return CFHIP_OK;
+	};
+	uint32_t current = 0xFFFFFFFFu;               // the lambda16 whose pass lies in the outputs
+	auto pass = [&](uint32_t lam16) -> int {
+		p.lam16 = lam16;
+		current = lam16;
+		return rdo_launch(ctx, lease, p, d_stats, true);
+	};
+	cfhip_rdo_target_result res;
+	memset(&res, 0, sizeof(res));
+	rc = estimate(plain, &res.est_bytes_plain);
+	if (rc != CFHIP_OK)
+		return rc;
+	const uint64_t target = (uint64_t)std::floor((double)target_ratio*(double)res.est_bytes_plain);
+	uint32_t hi = p.lam16, lo = 0u;
+	uint64_t est = 0;
+	rc = pass(hi);
+	if (rc == CFHIP_OK)
+		rc = estimate(work, &est);
+	if (rc != CFHIP_OK)
+		return rc;
+	res.trials = 1u;
+	res.est_bytes_final = est;
+	res.reached = est <= target ? 1u : 0u;
+	while (res.reached && hi - lo > 1u) {
+		const uint32_t mid = lo + (hi - lo)/2u;
+		rc = pass(mid);
+		if (rc == CFHIP_OK)
+			rc = estimate(work, &est);
+		if (rc != CFHIP_OK)
+			return rc;
+		++res.trials;
+		if (est <= target) {
+			hi = mid;
+			res.est_bytes_final = est;
+		} else
+			lo = mid;
+	}
+	if (current != hi) {
+		rc = pass(hi);
+		if (rc != CFHIP_OK)
+			return rc;
+	}
+	res.lambda16 = hi;
+	ctx->last_kernel = p.row_above ? "cfhip_rdo2d_kernel" : "cfhip_rdo_kernel";
+	std::vector<cfhip_rdo_stats> host_stats(host ? n : 0);
+	if (host) {
+		HIP_TRY(ctx, hipMemcpyAsync(host_stats.data(), d_stats, n*sizeof(cfhip_rdo_stats), hipMemcpyDeviceToHost, stream));
+		for (size_t i = 0; i < n; ++i)
+			HIP_TRY(ctx, hipMemcpyAsync(surfaces[i].out, p.entries[i].out, p.payload[i], hipMemcpyDeviceToHost, stream));
+	}
+	rc = lease.done(true);
+	if (rc != CFHIP_OK)
+		return rc;
+	for (size_t i = 0; i < host_stats.size(); ++i)
+		stats[i] = host_stats[i];
+	*result = res;
+	return CFHIP_OK;
+}
+
+int cfhip_rdo_target(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
+	const cfhip_rdo_ex_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats, float target_ratio,
+	cfhip_rdo_target_result* result)
+{
+	return rdo_target(ctx, "rdo_target", format, type, surfaces, n, params, mask_rgba, stats, true, target_ratio, result,
+		nullptr);
+}
+
+int cfhip_rdo_target_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
+	const cfhip_rdo_ex_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats_device, float target_ratio,
+	cfhip_rdo_target_result* result, void* stream_)
+{
+	return rdo_target(ctx, "rdo_target_device", format, type, surfaces, n, params, mask_rgba, stats_device, false,
+		target_ratio, result, stream_);
 }
 
 } // extern "C"

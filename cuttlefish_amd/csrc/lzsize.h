@@ -1,0 +1,73 @@
+// lzsize.h -- what the host side (cfhip_api.hip) and the kernels (lzsize.hip) of the deflate-size estimator share: the
+// constants of the model, the layout of a slice's scratch and the launcher.
+// The definition of the estimate is tests/lzsize_ref.py; every constant below has its twin
+// there.
+#ifndef CF_LZSIZE_H
+#define CF_LZSIZE_H
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#define CFLZ_MIN 4            // shortest match
+#define CFLZ_MAX 258          // longest match
+#define CFLZ_WINDOW 32768u    // W: a match reaches at most this far back
+#define CFLZ_CANDS 4          // K: candidates per position, nearest first
+#define CFLZ_CHUNK 4096u      // bytes parsed independently; one wavefront parses one chunk
+#define CFLZ_COSTBLK 65536u   // bytes priced with one pair of code tables; one wavefront prices one block
+#define CFLZ_LL 286           // literal / length alphabet
+#define CFLZ_DD 30            // distance alphabet
+// One cost block's counters (uint32): ll[286], dd[30], then the extra bits, literals, matches and matched bytes.
+#define CFLZ_EXTRA 316
+#define CFLZ_LITERALS 317
+#define CFLZ_MATCHES 318
+#define CFLZ_MATCHED 319
+#define CFLZ_HIST 320
+// The slice a stream is cut into unless cfhip_lz_slice_bytes says otherwise: whole cost blocks.
+#define CFLZ_SLICE_DEFAULT (4u << 20)
+// The five timed stages of a slice, in launch order.
+#define CFLZ_STAGES 5
+
+// The scratch of one slice of at most `slice` target bytes (a multiple of CFLZ_COSTBLK), which arrive behind the
+// up to W bytes before them (sources only).  Offsets in bytes from a 256-byte aligned base; every array is 256-byte
+// aligned.  m = slice + W positions: 1 (bytes) + 4 x 4 (keys and positions, in and out of the sort) per position,
+// 4 (length and distance) per target byte, 1280 per cost block, the sort's own storage and 32 bytes of sums:
+// 21.02 bytes per byte of slice + 17 W + the sort's storage (cflz_sort_bytes).
+struct cflz_layout {
+	size_t bytes, keys_in, keys_out, pos_in, pos_out, ld, hist, acc, sort, total;
+};
+
+inline cflz_layout cflz_scratch(size_t slice, size_t sort_bytes)
+{
+	const size_t m = slice + CFLZ_WINDOW;
+	auto up = [](size_t v) { return (v + 255u) & ~(size_t)255u; };
+	cflz_layout l;
+	size_t o = 0;
+	l.bytes = o;    o = up(o + m + 16u);
+	l.keys_in = o;  o = up(o + 4u*m);
+	l.keys_out = o; o = up(o + 4u*m);
+	l.pos_in = o;   o = up(o + 4u*m);
+	l.pos_out = o;  o = up(o + 4u*m);
+	l.ld = o;       o = up(o + 4u*slice);
+	l.hist = o;     o = up(o + (slice/CFLZ_COSTBLK)*CFLZ_HIST*4u);
+	l.acc = o;      o = up(o + 4u*sizeof(unsigned long long));
+	l.sort = o;     o = up(o + sort_bytes);
+	l.total = o;
+	return l;
+}
+
+// Bytes of temporary storage the radix sort needs for m pairs (a query, nothing runs).
+extern "C" hipError_t cfhip_lz_sort_bytes(size_t m, size_t* bytes);
+
+// One slice.  base: the scratch, laid out by cflz_scratch(slice_cap, sort_bytes).  Its byte array already holds
+// `carry` source bytes (0 or W) followed by the n target bytes of the slice, n <= slice_cap.  The stages are
+// enqueued on `stream` in order: keys, sort, match, parse + histogram, cost; the four sums (bits_q16, literals,
+// matches, matched_bytes) are ADDED to acc (zeroed by the caller before the first slice).  ev: NULL, or
+// 2 x CFLZ_STAGES events recorded around the stages.
+extern "C" hipError_t cfhip_launch_lz_slice(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t carry,
+	uint32_t n, hipEvent_t* ev, hipStream_t stream);
+
+// out[0..5] = bytes_in, bits_q16, est_bytes, literals, matches, matched_bytes from the four sums.
+extern "C" hipError_t cfhip_launch_lz_final(const unsigned long long* acc, unsigned long long bytes_in,
+	unsigned long long* out, hipStream_t stream);
+
+#endif

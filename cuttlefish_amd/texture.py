@@ -329,6 +329,7 @@ class Texture:
         self._alpha = Alpha.Standard
         self._mask = (True, True, True, True)
         self._rdo_stats = None
+        self._rdo_target = None
 
     def initialize(self, dimension, width: int, height: int, depth: int = 0, mip_levels: int = 1,
                    color_space: ColorSpace = ColorSpace.Linear) -> bool:
@@ -817,6 +818,7 @@ class Texture:
         """convert()'s end state: the payloads in (mip, depth, face) order, the images freed"""
         it = iter(payloads)
         self._rdo_stats = None
+        self._rdo_target = None
         self._textures = [[[next(it) for _ in dep] for dep in level] for level in self._images]
         self._images = [[[None]*len(dep) for dep in level] for level in self._images]
         self._format, self._type = format, type
@@ -826,14 +828,18 @@ class Texture:
                     alpha_type: Alpha = Alpha.Standard,
                     color_mask: Sequence[bool] = (True, True, True, True), rdo_lambda: float = 1.0,
                     max_sse_increase: Optional[int] = None, row_above: bool = False,
-                    window_bytes: Optional[int] = None) -> bool:
+                    window_bytes: Optional[int] = None, target_ratio: Optional[float] = None) -> bool:
         """convert(), then the rate-distortion pass (Context.rdo_device) over the fresh payloads against the texels
         they were encoded from, in one visit to the device: every image is uploaded once, encoded from there,
         optimised in place, and only the final payloads and the statistics (rdo_stats()) come back.  The channels
         the pass measures are compare()'s: the colour mask's, without alpha when the alpha type is None.  Returns
         False wherever convert() does and for the formats the pass does not cover (api.rdo_supported); the texture
         is then left unconverted.  A lambda outside (0, 1024] raises api.CfhipError.  row_above and window_bytes are
-        Context.rdo's: blocks may also copy from the block row above."""
+        Context.rdo's: blocks may also copy from the block row above.
+        target_ratio (None: the pass at rdo_lambda): the pass to a target (Context.rdo_target_device) -- the smallest
+        lambda <= rdo_lambda whose payloads, all surfaces as one stream, are estimated at no more than target_ratio x
+        the estimate of the plain ones.  Encoding still happens once, the search runs against the resident texels,
+        rdo_stats() are the final pass's and rdo_target() returns the search's result."""
         import ctypes
         import torch
         if not self.images_complete() or not self.is_format_valid(format, type):
@@ -856,13 +862,20 @@ class Texture:
         hosts, texels, pays = resident
         size = ctypes.sizeof(api.RdoStats)
         stats = torch.empty(len(pays)*size, dtype=torch.uint8, device=pays[0].device)
-        ctx.rdo_device([dict(blocks=p.data_ptr(), out=p.data_ptr(), out_capacity=p.numel(), pixels=t.data_ptr(),
-                             pixel_type=int(api.pixel_type_of(h)), width=h.shape[1], height=h.shape[0],
-                             row_pitch_bytes=h.strides[0]) for h, t, p in zip(hosts, texels, pays)],
-                       format, type, rdo_lambda, stats.data_ptr(), max_sse_increase=max_sse_increase, mask=mask,
-                       row_above=row_above, window_bytes=window_bytes)
+        surfaces = [dict(blocks=p.data_ptr(), out=p.data_ptr(), out_capacity=p.numel(), pixels=t.data_ptr(),
+                         pixel_type=int(api.pixel_type_of(h)), width=h.shape[1], height=h.shape[0],
+                         row_pitch_bytes=h.strides[0]) for h, t, p in zip(hosts, texels, pays)]
+        target = None
+        if target_ratio is None:
+            ctx.rdo_device(surfaces, format, type, rdo_lambda, stats.data_ptr(), max_sse_increase=max_sse_increase,
+                           mask=mask, row_above=row_above, window_bytes=window_bytes)
+        else:
+            target = ctx.rdo_target_device(surfaces, format, type, target_ratio, rdo_lambda, stats.data_ptr(),
+                                           max_sse_increase=max_sse_increase, mask=mask, row_above=row_above,
+                                           window_bytes=window_bytes)
         raw = stats.cpu().numpy().tobytes()
         self._adopt([p.cpu().numpy() for p in pays], format, type, alpha_type, color_mask)
+        self._rdo_target = target
         self._rdo_stats = [api.RdoStats.from_buffer_copy(raw[i*size:(i + 1)*size]).as_dict() for i in range(len(pays))]
         return True
 
@@ -870,6 +883,19 @@ class Texture:
         """The statistics of the last convert_rdo(), one dict per surface in (mip, depth, face) order; None before
         the first one."""
         return self._rdo_stats
+
+    def rdo_target(self):
+        """The result of the last convert_rdo(target_ratio=...): lambda16, reached, trials, est_bytes_plain,
+        est_bytes_final; None when the last conversion had no target."""
+        return self._rdo_target
+
+    def packed_size(self):
+        """The deflate-size estimate (Context.lz_size) of this converted texture's payloads, data() of every surface
+        in (mip, depth, face) order as one stream; no container header is counted.  Any format.  None when the
+        texture is not converted."""
+        if not self._textures:
+            return None
+        return self._context().lz_size([p for _, _, _, p in self._flat()])
 
     def convert_and_compare(self, format: Format, type: Type, quality: Quality = Quality.Normal,
                             alpha_type: Alpha = Alpha.Standard,

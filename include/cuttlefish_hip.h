@@ -654,6 +654,77 @@ int cfhip_rdo_ex(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* 
 int cfhip_rdo_ex_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n_surfaces,
 	const cfhip_rdo_ex_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats_device, void* stream);
 
+/* ---- Deflate-size estimate of payloads, and the rate-distortion pass to a target ratio ----
+ *
+ * How many bytes a byte stream takes inside a zip / PNG-class package, computed on the device for payloads of any
+ * format.  The stream (the spans of a call, concatenated; fewer than 2^31 bytes) is parsed the way a deflate encoder
+ * parses it -- hash candidates on 4-byte keys (the 4 nearest within 32768 bytes), matches of 4..258 bytes that end at
+ * 4096-byte chunk boundaries, one-step lazy evaluation -- and priced, per block of 65536 input bytes, with the
+ * zeroth-order entropy of deflate's literal/length and distance alphabets plus their extra bits.  There is no term for
+ * the code-table headers, so streams that compress to a few hundred bytes are underestimated.  The definition, down
+ * to the fixed-point logarithm, is tests/lzsize_ref.py; every result is an integer sum, so identical calls return
+ * identical bits.  Scratch belongs to the context: about 21 bytes per byte of a slice (cfhip_lz_slice_bytes). */
+typedef struct cfhip_lz_span {
+	const void* bytes;
+	size_t n;
+} cfhip_lz_span;
+
+typedef struct cfhip_lz_stats {
+	uint64_t bytes_in;          /* bytes of the stream */
+	uint64_t bits_q16;          /* the estimate in 1/65536 bit */
+	uint64_t est_bytes;         /* ceil(bits_q16 / (8 * 65536)) */
+	uint64_t literals, matches; /* tokens of the parse */
+	uint64_t matched_bytes;     /* bytes covered by matches */
+} cfhip_lz_stats;
+
+/* Host spans.  A span of 0 bytes is skipped (its pointer may be NULL); a stream of 0 bytes is CFHIP_OK with all-zero
+ * stats and needs no context.  2^31 bytes or more: CFHIP_E_CAPACITY.  Every argument is checked before anything is
+ * enqueued (a NULL ctx is reported last).  Blocking. */
+int cfhip_lz_size(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, cfhip_lz_stats* out);
+
+/* Device spans (`spans` is a host array of device pointers, any alignment); out_device: one cfhip_lz_stats on the
+ * device, 8-byte aligned, overwritten.  The stream rules of cfhip_compare_device. */
+int cfhip_lz_size_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, cfhip_lz_stats* out_device,
+	void* stream);
+
+/* The two entries below are diagnostic: they serve the tests and tools/bench_lzsize.py, are not needed to use the
+ * estimator, and may change without a new CFHIP_ABI_VERSION.
+ *
+ * A stream longer than a slice is processed in slices, each behind the 32768 bytes before it; the result does not
+ * depend on the slice.  Sets the slice (rounded up to whole blocks of 65536 bytes; 0 = the default, 4 MiB) and
+ * returns the one in force before.  It bounds the context's scratch. */
+size_t cfhip_lz_slice_bytes(cfhip_ctx* ctx, size_t bytes);
+
+/* Kernel time of the five stages (keys, sort, match, parse, cost) of the estimate the most recent call on this
+ * context made last, summed over its slices (ms); CFHIP_E_INVALID unless that call was a cfhip_lz_size*.
+ * Synchronises the stream. */
+int cfhip_lz_stage_ms(cfhip_ctx* ctx, float ms[5]);
+
+/* The pass to a target: the smallest lambda whose result is estimated at no more than
+ * T = floor(target_ratio * est_bytes_plain), est_bytes_plain being the estimate of the payloads as given.  The stream
+ * is the surfaces' payloads concatenated in call order.  params->lambda is the largest lambda allowed:
+ * hi = round(16 lambda); the pass runs at hi from the pristine payloads; if its estimate exceeds T that result is
+ * returned with reached = 0.  Otherwise lo = 0 and, while hi - lo > 1, mid = (lo + hi) / 2 is tried: hi = mid if its
+ * estimate is <= T, else lo = mid; the pass at hi is returned with reached = 1.  Every trial starts from the pristine
+ * payloads (kept in the context's scratch where out == blocks).  stats are those of the returned pass; flags, cap,
+ * mask and window are cfhip_rdo_ex's, as are the checks; target_ratio outside (0, 1) is CFHIP_E_INVALID.  No host
+ * compressor runs.  Both forms block: each trial's estimate is read back before the next one is chosen. */
+typedef struct cfhip_rdo_target_result {
+	uint32_t lambda16;          /* round(16 lambda) of the returned pass */
+	uint32_t reached;           /* 1: est_bytes_final <= T */
+	uint32_t trials;            /* passes estimated during the search */
+	uint64_t est_bytes_plain, est_bytes_final;
+} cfhip_rdo_target_result;
+
+int cfhip_rdo_target(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n_surfaces,
+	const cfhip_rdo_ex_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats, float target_ratio,
+	cfhip_rdo_target_result* result);
+
+/* The buffers of cfhip_rdo_ex_device; result is host memory. */
+int cfhip_rdo_target_device(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n_surfaces,
+	const cfhip_rdo_ex_params* params, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats_device, float target_ratio,
+	cfhip_rdo_target_result* result, void* stream);
+
 /* ---- PVRTC1 4 bpp (formats 59 RGB, 60 RGBA; type UNorm) ----
  *
  * PVRTC1 is outside the cfhip_surface block contract: blocks are stored in twiddled (Morton) order, a level is never
@@ -740,7 +811,7 @@ int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* p
 	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* or cfhip_image_ops_device call on
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size* or cfhip_image_ops_device call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
