@@ -6,7 +6,9 @@
 // nearest-even packing of the block (:113-129, HalfFloat.h:96-136).
 //
 // Candidates: id 0 = one subset (modes 14/13/12/11), ids 1..32 = the 32 two-subset partitions
-// (ten modes); wavefront 0 fits the one-subset candidates of the workgroup's 16 blocks on 16 lanes, every
+// (ten modes), id 33 = the flat block at the rounded per-channel mean of the half-space values
+// (mode 14, zero deltas; no fit, every level: no block ends worse than a constant one);
+// wavefront 0 fits the one-subset candidates of the workgroup's 16 blocks on 16 lanes, every
 // wavefront its four blocks' partitions in two passes (see the kernel body).  Per subset: PCA axis in the decoder's 16-bit
 // interpolation space -> extremes -> refit rounds (projection selectors, closed-form
 // least squares) -> anchor fix-up -> highest-precision mode whose deltas fit -> exact
@@ -564,6 +566,49 @@ __device__ __forceinline__ void eval_two(const uint32_t* tp, uint32_t part, uint
 	finish_candidate<SIGNED>(tp, true, m1, 1u + part, part, e, idx, c);
 }
 
+// candidate 33: the constant block at the rounded per-channel mean of the half-space values, as
+// mode 14 with zero deltas and zero selectors (twin of eval_flat() of the oracle).  Its exact error
+// follows from the sums: sum (h - m)^2 = sum h^2 - 2 m sum h + 16 m^2, m = what the decoder returns
+// for the stored endpoint.  It takes c's place where its (error, id) key is the smaller one; with
+// the highest id that is only where it is strictly better.
+template <bool SIGNED>
+__device__ __forceinline__ void eval_flat(const uint32_t* tp, HCand& c, unsigned long long& key)
+{
+	int s1[3] = {0, 0, 0};
+	unsigned long long s2 = 0ull;   // < 48 * 0x7BFF^2 < 2^36
+#pragma unroll 1
+	for (uint32_t i = 0; i < 16u; ++i) {
+		const Tx t = load_tx<SIGNED>(tp, i);
+#pragma unroll
+		for (int ch = 0; ch < 3; ++ch) {
+			s1[ch] += t.h[ch];
+			s2 += (unsigned long long)(uint32_t)(t.h[ch]*t.h[ch]);
+		}
+	}
+	int v[3];
+	long long cross = 0ll;          // sum over channels of 2 m s1 - 16 m^2
+#pragma unroll
+	for (int ch = 0; ch < 3; ++ch) {
+		const int mean = ((s1[ch] + 8 + (1 << 20)) >> 4) - (1 << 16);   // floor((s1 + 8)/16)
+		const int a = mean < 0 ? -mean : mean;
+		const int va = SIGNED ? (a*32 + 30)/31 : (a*64 + 30)/31;
+		v[ch] = mean < 0 ? -va : va;
+		const long long m = (long long)v_to_h<SIGNED>(v[ch]);
+		cross += 2ll*m*(long long)s1[ch] - 16ll*m*m;
+	}
+	const unsigned long long err = (unsigned long long)((long long)s2 - cross);
+	const unsigned long long fkey = (err << 6) | 33ull;
+	if (fkey < key) {
+		key = fkey;
+		c.err = err; c.id = 33u; c.mode = 13u; c.part = 0u; c.idx = 0ull;
+#pragma unroll
+		for (int ch = 0; ch < 3; ++ch) {
+			c.q[0][ch] = c.q[1][ch] = v[ch];
+			c.q[2][ch] = c.q[3][ch] = 0;
+		}
+	}
+}
+
 struct Bits128 {
 	unsigned long long lo, hi;
 	__device__ __forceinline__ void put(uint32_t pos, uint32_t v, uint32_t n)
@@ -712,7 +757,8 @@ cfhip_bc6h_encode_kernel(cf_kparams kp)
 	const uint32_t iters = quality <= 1u ? 0u : (quality == 2u ? 2u : (quality == 3u ? 3u : 4u));   // oracle: cfo_encode_bc6h_block
 	// Schedule of a workgroup's 16 blocks (33 candidates each: one one-subset fit, 32 partitions
 	// of two fits):
-	//   wavefront 0, lanes 0..15: the one-subset candidate of all 16 blocks, parked in cand_lds
+	//   wavefront 0, lanes 0..15: the one-subset candidate of all 16 blocks, or the flat block
+	//            (id 33) where that is strictly better, parked in cand_lds
 	//            (one 16-lane pass per workgroup instead of a 4-lane pass per wavefront -- the
 	//            kernel is bound by issued instructions, not by the slowest wave);
 	//   every wavefront, 2 passes over its four blocks: two blocks per pass, lane group
@@ -731,7 +777,9 @@ cfhip_bc6h_encode_kernel(cf_kparams kp)
 				c.q[k][ch] = 0;
 		if (lane < nwg) {
 			eval_one<SIGNED>(tile + lane*48u, iters, c);
-			store_cand(cand_lds + lane*20u, c, (c.err << 6) | c.id);   // error < 2^37, id < 64
+			unsigned long long key = (c.err << 6) | c.id;   // error < 2^37, id < 64
+			eval_flat<SIGNED>(tile + lane*48u, c, key);
+			store_cand(cand_lds + lane*20u, c, key);
 		}
 	}
 	if (quality != 0u) {

@@ -10,7 +10,8 @@
  * is a from-specification encoder of the same class:
  *
  *   candidates: id 0 = one subset (modes 14,13,12,11), id 1+p = partition p (0..31) with the
- *   ten two-subset modes.  Per subset: PCA axis in the decoder's 16-bit interpolation
+ *   ten two-subset modes, id 33 = the flat block at the rounded per-channel mean of the
+ *   half-space values (mode 14, zero deltas: no fit, every level).  Per subset: PCA axis in the decoder's 16-bit interpolation
  *   space -> extremes -> `iters` rounds of (projection selectors -> least-squares
  *   endpoints) -> anchor fix-up -> the highest-precision mode whose endpoint deltas
  *   fit -> exact integer error in half-float-bit space.  Winner = min (error, id).
@@ -300,6 +301,34 @@ static void eval_candidate(const int v[16][3], const int h[16][3], int id, int i
 	c->err = err;
 }
 
+/* id 33: the constant block at the rounded per-channel mean of the half-space values, written as
+ * mode 14 with zero deltas and zero selectors.  Exact error from the sums: sum (h - m)^2 =
+ * sum h^2 - 2 m sum h + 16 m^2, m being what the decoder returns for the stored endpoint. */
+static void eval_flat(const int h[16][3], int is_signed, hcand* c)
+{
+	memset(c, 0, sizeof(*c));
+	c->id = 33;
+	c->mode = 13;
+	uint64_t err = 0;
+	for (int ch = 0; ch < 3; ++ch) {
+		int s1 = 0;
+		int64_t s2 = 0;
+		for (int i = 0; i < 16; ++i) {
+			s1 += h[i][ch];
+			s2 += (int64_t)(h[i][ch]*h[i][ch]);
+		}
+		int mean = ((s1 + 8 + (1 << 20)) >> 4) - (1 << 16);   /* floor((s1 + 8)/16) */
+		int a = mean < 0 ? -mean : mean;
+		int v = is_signed ? (a*32 + 30)/31 : (a*64 + 30)/31;
+		if (mean < 0)
+			v = -v;
+		int m = v_to_h(v, is_signed);
+		c->q[0][ch] = c->q[1][ch] = v;
+		err += (uint64_t)(s2 - 2*(int64_t)m*s1 + 16*(int64_t)m*m);
+	}
+	c->err = err;
+}
+
 static void put_bits(uint8_t* out, unsigned pos, unsigned v, unsigned n)
 {
 	for (unsigned i = 0; i < n; ++i)
@@ -364,6 +393,10 @@ void cfo_encode_bc6h_block(const uint16_t rgba_half[64], uint8_t out[16], const 
 		if (cur.err < best.err)
 			best = cur;
 	}
+	/* last id: the flat block wins only where it is strictly better than every fit */
+	eval_flat(h, is_signed, &cur);
+	if (cur.err < best.err)
+		best = cur;
 	pack(&best, out);
 }
 

@@ -72,9 +72,12 @@ def run(format_name, cases, seed, verbose=True):
                 if typ == Type.Float:
                     f = f*np.where(rng.random(f.shape) < 0.3, -1.0, 1.0).astype(np.float32)
                 sp = rng.random(f.shape) < 0.01
-                f = np.where(sp, rng.choice(np.array([0.0, 65504.0, 1e9, -1e9, 6e-8, np.inf], np.float32), f.shape), f)
+                special = np.array([0.0, 65504.0, 1e9, -1e9, 6e-8, np.inf, np.nan, np.nan], np.float32)
+                special.view(np.uint32)[-1] |= 0x80000000                                 # -NaN: its sign bit set
+                f = np.where(sp, rng.choice(special, f.shape), f)
                 k = int(rng.integers(0, 3))
-                img = f.astype(np.float16) if k == 0 else (f.astype(np.float32) if k == 1 else img)
+                with np.errstate(over="ignore"):                                          # 1e9 -> Inf as a half
+                    img = f.astype(np.float16) if k == 0 else (f.astype(np.float32) if k == 1 else img)
                 cs, mask = 0, (1, 1, 1, 1)
             elif fmt.name.startswith("ASTC") and rng.integers(0, 3) == 0:
                 # HDR profiles: float content over 18 stops with special values; alpha type picks
