@@ -195,7 +195,9 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_rdo_supported", "cfhip_rdo", "cfhip_rdo_device",
            "cfhip_rdo_ex", "cfhip_rdo_ex_device",
            "cfhip_lz_size", "cfhip_lz_size_device", "cfhip_lz_slice_bytes", "cfhip_lz_stage_ms",
-           "cfhip_rdo_target", "cfhip_rdo_target_device"]
+           "cfhip_rdo_target", "cfhip_rdo_target_device",
+           "cfhip_deflate_bound", "cfhip_deflate", "cfhip_deflate_device", "cfhip_deflate_stage_ms",
+           "cfhip_deflate_code_lengths"]
 
 
 class Layout(enum.IntEnum):
@@ -351,6 +353,24 @@ class RdoTargetResult(ctypes.Structure):
 
 
 LZ_STAGES = ("keys", "sort", "match", "parse", "cost")      # cfhip_lz_stage_ms
+
+
+class DeflateResult(ctypes.Structure):
+    """struct cfhip_deflate_result"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("bytes_in", "bytes_out", "blocks_stored", "blocks_fixed",
+                                               "blocks_dynamic", "literals", "matches", "matched_bytes")] + \
+               [("adler32", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+DEFLATE_STAGES = ("keys", "sort", "match", "parse", "adler", "codes", "offsets", "emit")   # cfhip_deflate_stage_ms
+
+
+def deflate_bound(n: int) -> int:
+    """cfhip_deflate_bound: bytes that hold the zlib stream of any n input bytes (no device needed)"""
+    return int(load_library().cfhip_deflate_bound(int(n)))
 
 RDO_NO_CAP = 0xFFFFFFFF         # max_sse_increase: no cap
 RDO_ROW_ABOVE = 1               # CFHIP_RDO_ROW_ABOVE
@@ -573,6 +593,19 @@ def load_library(path: Optional[str] = None):
     L.cfhip_lz_slice_bytes.restype = ctypes.c_size_t
     L.cfhip_lz_stage_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     L.cfhip_lz_stage_ms.restype = ctypes.c_int
+    L.cfhip_deflate_bound.argtypes = [ctypes.c_size_t]
+    L.cfhip_deflate_bound.restype = ctypes.c_size_t
+    L.cfhip_deflate.argtypes = [ctypes.c_void_p, ctypes.POINTER(LzSpan), ctypes.c_size_t, ctypes.c_void_p,
+                                ctypes.c_size_t, ctypes.c_void_p]
+    L.cfhip_deflate.restype = ctypes.c_int
+    L.cfhip_deflate_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(LzSpan), ctypes.c_size_t, ctypes.c_void_p,
+                                       ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_deflate_device.restype = ctypes.c_int
+    L.cfhip_deflate_stage_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    L.cfhip_deflate_stage_ms.restype = ctypes.c_int
+    L.cfhip_deflate_code_lengths.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32,
+                                             ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8)]
+    L.cfhip_deflate_code_lengths.restype = ctypes.c_int
     L.cfhip_rdo_target.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RdoSurface),
                                    ctypes.c_size_t, ctypes.POINTER(RdoExParams), ctypes.POINTER(ctypes.c_uint8),
                                    ctypes.c_void_p, ctypes.c_float, ctypes.POINTER(RdoTargetResult)]
@@ -1203,6 +1236,54 @@ class Context:
         ms = (ctypes.c_float*5)()
         self._check(self._lib.cfhip_lz_stage_ms(self._h, ms))
         return dict(zip(LZ_STAGES, (float(v) for v in ms)))
+
+    def deflate(self, payloads) -> bytes:
+        """The zlib stream (cfhip_deflate) of a byte stream: one array / bytes object, or a sequence of them taken as
+        their concatenation.  zlib.decompress inverts it; the bytes are those of tests/deflate_ref.py, exactly.
+        deflate_result() returns the call's cfhip_deflate_result."""
+        if isinstance(payloads, (bytes, bytearray, np.ndarray)):
+            payloads = [payloads]
+        parts = [np.frombuffer(bytes(p), np.uint8) if isinstance(p, (bytes, bytearray))
+                 else np.ascontiguousarray(p).reshape(-1).view(np.uint8) for p in payloads]
+        spans = (LzSpan*max(len(parts), 1))()
+        for i, p in enumerate(parts):
+            spans[i].bytes, spans[i].n = (p.ctypes.data if p.size else None), p.size
+        cap = deflate_bound(sum(p.size for p in parts))
+        out = np.empty(cap, np.uint8)
+        res = DeflateResult()
+        self._check(self._lib.cfhip_deflate(self._h, spans, len(parts), out.ctypes.data, cap, ctypes.addressof(res)))
+        self._deflate_result = res.as_dict()
+        return out[:res.bytes_out].tobytes()
+
+    def deflate_result(self) -> Optional[dict]:
+        """The cfhip_deflate_result of the last deflate() on this context; None before the first one."""
+        return getattr(self, "_deflate_result", None)
+
+    def deflate_device(self, spans: Sequence[tuple], out: int, cap: int, result: int, stream: int = 0):
+        """Device path of deflate.  spans: (device pointer as int, bytes) pairs; out: device pointer to cap bytes,
+        4-byte aligned; result: device pointer to one cfhip_deflate_result (overwritten).  stream 0 = the context's
+        stream (the call then synchronises)."""
+        arr = (LzSpan*max(len(spans), 1))()
+        for i, (ptr, n) in enumerate(spans):
+            arr[i].bytes, arr[i].n = int(ptr) or None, int(n)
+        self._check(self._lib.cfhip_deflate_device(
+            self._h, arr, len(spans), ctypes.c_void_p(int(out)) if out else None, int(cap),
+            ctypes.c_void_p(int(result)) if result else None, ctypes.c_void_p(stream) if stream else None))
+
+    def deflate_stage_ms(self) -> dict:
+        """Kernel ms of the last deflate's stages: keys, sort, match, parse, adler, codes, offsets, emit"""
+        ms = (ctypes.c_float*len(DEFLATE_STAGES))()
+        self._check(self._lib.cfhip_deflate_stage_ms(self._h, ms))
+        return dict(zip(DEFLATE_STAGES, (float(v) for v in ms)))
+
+    def deflate_code_lengths(self, counts, limit: int) -> np.ndarray:
+        """The device code builder alone (cfhip_deflate_code_lengths): one code length per count"""
+        c = np.ascontiguousarray(counts, np.uint32)
+        out = np.zeros(c.size, np.uint8)
+        self._check(self._lib.cfhip_deflate_code_lengths(
+            self._h, c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), c.size, int(limit),
+            out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        return out
 
     def rdo_target(self, payloads: Sequence[np.ndarray], sources: Sequence[np.ndarray], fmt, typ=Type.UNorm,
                    target_ratio: float = 0.85, lam: float = 32.0, max_sse_increase: Optional[int] = None, mask=None,

@@ -147,7 +147,11 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  "cfhip_rdo_kernel", "cfhip_rdo2d_kernel",
                  # the deflate-size estimator (csrc/lzsize.hip); the sort between them is rocprim's
                  "cfhip_lz_keys_kernel", "cfhip_lz_match_kernel", "cfhip_lz_parse_kernel", "cfhip_lz_cost_kernel",
-                 "cfhip_lz_final_kernel")
+                 "cfhip_lz_final_kernel",
+                 # the zlib encoder behind it (csrc/deflate.hip)
+                 "cfhip_deflate_parse_kernel", "cfhip_deflate_adler_kernel", "cfhip_deflate_codes_kernel",
+                 "cfhip_deflate_lengths_kernel", "cfhip_deflate_offsets_kernel", "cfhip_deflate_emit_kernel",
+                 "cfhip_deflate_final_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

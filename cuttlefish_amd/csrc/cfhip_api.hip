@@ -12,6 +12,7 @@
 #include "decode_batch.h"
 #include "rdo.h"
 #include "lzsize.h"
+#include "deflate.h"
 #include "../../include/cuttlefish_hip.h"
 
 #include <cmath>
@@ -198,6 +199,7 @@ struct cfhip_ctx {
 	size_t lz_cap = 0;
 	size_t lz_slice = 0;              // cfhip_lz_slice_bytes: 0 = CFLZ_SLICE_DEFAULT
 	size_t lz_first_event = 0, lz_slices = 0;   // the last estimate's event pairs: CFLZ_STAGES per slice
+	size_t df_first_event = 0, df_slices = 0;   // the last cfhip_deflate*'s event pairs: CFDF_STAGES per slice
 	void* d_rdo_keep = nullptr;       // cfhip_rdo_target: the pristine payloads every trial starts from
 	size_t rdo_keep_cap = 0;
 	std::map<int, void*> astc_tables; // per-format device tables (built on first use)
@@ -3385,6 +3387,248 @@ int cfhip_lz_stage_ms(cfhip_ctx* ctx, float ms[CFLZ_STAGES])
 		ms[i % CFLZ_STAGES] += t;
 	}
 	return CFHIP_OK;
+}
+
+// ---- the zlib stream of payloads (csrc/deflate.hip, csrc/deflate.h; the definition is tests/deflate_ref.py) --------
+static const uint8_t kDeflateEmpty[11] = {0x78, 0x9C, 0x01, 0x00, 0x00, 0xFF, 0xFF, 0x00, 0x00, 0x00, 0x01};
+
+static cfhip_deflate_result deflate_empty_result()
+{
+	cfhip_deflate_result r;
+	memset(&r, 0, sizeof(r));
+	r.bytes_out = sizeof(kDeflateEmpty);
+	r.adler32 = 1u;
+	return r;
+}
+
+size_t cfhip_deflate_bound(size_t n)
+{
+	return cfdf_bound(n);
+}
+
+// Every check of an encoder call, made before the context is touched.
+static int deflate_check(cfhip_ctx* ctx, const char* what, const cfhip_lz_span* spans, size_t n, const void* out, size_t cap,
+	const void* result, bool host, LzPlan* p)
+{
+	if (!out)
+		return fail(ctx, CFHIP_E_INVALID, "%s: out is NULL", what);
+	if (!result)
+		return fail(ctx, CFHIP_E_INVALID, "%s: result is NULL", what);
+	if (!host && ((uintptr_t)out % 4u != 0 || (uintptr_t)result % 8u != 0))
+		return fail(ctx, CFHIP_E_INVALID, "%s: out must be 4-byte and result 8-byte aligned", what);
+	const int rc = lz_check(ctx, what, spans, n, out, true, p);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (cap < cfdf_bound(p->total))
+		return fail(ctx, CFHIP_E_CAPACITY, "%s: out holds %zu bytes, cfhip_deflate_bound(%zu) = %zu", what, cap, p->total,
+			cfdf_bound(p->total));
+	return CFHIP_OK;
+}
+
+// The stream of p (total > 0) into out_device (zeroed here) and the result into result_device, enqueued on the lease's
+// stream: slices of whole groups, each behind the W bytes before it, the state carried on the device.
+static int deflate_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hipMemcpyKind kind, uint8_t* out_device,
+	unsigned long long* result_device)
+{
+	const hipStream_t stream = lease.stream;
+	const size_t slice = std::min(lz_slice_of(ctx), (p.total + CFLZ_COSTBLK - 1u)/CFLZ_COSTBLK*CFLZ_COSTBLK);
+	size_t sort_bytes = 0;
+	HIP_TRY(ctx, cfhip_lz_sort_bytes(slice + CFLZ_WINDOW, &sort_bytes));
+	const cfdf_layout lay = cfdf_scratch(slice, sort_bytes);
+	int rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, lay.total);
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* base = static_cast<uint8_t*>(ctx->d_lz);
+	unsigned long long* state = reinterpret_cast<unsigned long long*>(base + lay.state);
+	HIP_TRY(ctx, hipMemsetAsync(out_device, 0, cfdf_bound(p.total), stream));
+	ctx->df_first_event = ctx->events_used;
+	ctx->df_slices = 0;
+	for (size_t s0 = 0; s0 < p.total; s0 += slice) {
+		const size_t s1 = std::min(p.total, s0 + slice);
+		const size_t carry = s0 ? CFLZ_WINDOW : 0u;
+		rc = lz_gather(ctx, p, s0 - carry, s1, base + lay.lz.bytes, kind, stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		hipEvent_t ev[2*CFDF_STAGES];
+		for (int k = 0; k < CFDF_STAGES; ++k) {
+			rc = next_event_pair(ctx, &ev[2*k], &ev[2*k + 1]);
+			if (rc != CFHIP_OK)
+				return rc;
+		}
+		const hipError_t e = cfhip_launch_deflate_slice(base, &lay, sort_bytes, (uint32_t)carry, (uint32_t)(s1 - s0), s0 == 0,
+			s1 == p.total, out_device, ev, stream);
+		if (e != hipSuccess)
+			return fail(ctx, CFHIP_E_DEVICE, "deflate launch: %s", hipGetErrorString(e));
+		++ctx->df_slices;
+	}
+	const hipError_t e = cfhip_launch_deflate_final(state, (unsigned long long)p.total, out_device, result_device, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "deflate launch: %s", hipGetErrorString(e));
+	return CFHIP_OK;
+}
+
+static void deflate_begin_call(cfhip_ctx* ctx, hipStream_t stream)
+{
+	lz_begin_call(ctx, stream);
+	ctx->last_kernel = "cfhip_deflate_emit_kernel";
+}
+
+static int deflate_host(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, void* out, cfhip_deflate_result* result)
+{
+	static_assert(sizeof(cfhip_deflate_result) == 9*sizeof(unsigned long long), "the final kernel's words are the struct");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	deflate_begin_call(ctx, lease.stream);
+	// the result lies behind the stream's bytes, 256-byte aligned
+	const size_t res_off = (cfdf_bound(p.total) + 255u)/256u*256u;
+	int rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, res_off + 256u);
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out);
+	unsigned long long* d_res = reinterpret_cast<unsigned long long*>(d_out + res_off);
+	rc = deflate_run(ctx, lease, p, hipMemcpyHostToDevice, d_out, d_res);
+	if (rc != CFHIP_OK)
+		return rc;
+	cfhip_deflate_result res;
+	HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
+	HIP_TRY(ctx, hipStreamSynchronize(lease.stream));
+	if (res.bytes_out > cfdf_bound(p.total))
+		return fail(ctx, CFHIP_E_DEVICE, "deflate: %llu bytes exceed the bound", (unsigned long long)res.bytes_out);
+	HIP_TRY(ctx, hipMemcpyAsync(out, d_out, (size_t)res.bytes_out, hipMemcpyDeviceToHost, lease.stream));
+	rc = lease.done(true);
+	if (rc != CFHIP_OK)
+		return rc;
+	*result = res;
+	return CFHIP_OK;
+}
+
+int cfhip_deflate(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out, size_t cap,
+	cfhip_deflate_result* result)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		LzPlan p;
+		const int rc = deflate_check(ctx, "deflate", spans, n_spans, out, cap, result, true, &p);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!p.total) {
+			memcpy(out, kDeflateEmpty, sizeof(kDeflateEmpty));
+			*result = deflate_empty_result();
+			return CFHIP_OK;
+		}
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		StagingLease lease(ctx, ctx->stream);
+		return deflate_host(ctx, lease, p, out, result);
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "deflate: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "deflate: unknown exception");
+	}
+}
+
+int cfhip_deflate_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out_device, size_t cap,
+	cfhip_deflate_result* result_device, void* stream_)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		LzPlan p;
+		int rc = deflate_check(ctx, "deflate_device", spans, n_spans, out_device, cap, result_device, false, &p);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		deflate_begin_call(ctx, lease.stream);
+		if (!p.total) {
+			// both sources are static: the copies may outlive the call
+			static const cfhip_deflate_result empty = deflate_empty_result();
+			HIP_TRY(ctx, hipMemcpyAsync(out_device, kDeflateEmpty, sizeof(kDeflateEmpty), hipMemcpyHostToDevice, lease.stream));
+			HIP_TRY(ctx, hipMemcpyAsync(result_device, &empty, sizeof(empty), hipMemcpyHostToDevice, lease.stream));
+		} else {
+			rc = lease.acquire();
+			if (rc == CFHIP_OK)
+				rc = deflate_run(ctx, lease, p, hipMemcpyDeviceToDevice, static_cast<uint8_t*>(out_device),
+					reinterpret_cast<unsigned long long*>(result_device));
+			if (rc != CFHIP_OK)
+				return rc;
+		}
+		return lease.done(!stream_);
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "deflate_device: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "deflate_device: unknown exception");
+	}
+}
+
+int cfhip_deflate_stage_ms(cfhip_ctx* ctx, float ms[CFDF_STAGES])
+{
+	if (!ctx || !ms)
+		return CFHIP_E_INVALID;
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	const size_t first = ctx->df_first_event, pairs = ctx->df_slices*CFDF_STAGES;
+	if (!pairs || first + 2*pairs > ctx->events_used || ctx->last_kernel.compare(0, 13, "cfhip_deflate") != 0)
+		return fail(ctx, CFHIP_E_INVALID, "deflate_stage_ms: the last call on this context was no cfhip_deflate*");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->events_stream));
+	for (int k = 0; k < CFDF_STAGES; ++k)
+		ms[k] = 0.0f;
+	for (size_t i = 0; i < pairs; ++i) {
+		float t = 0.0f;
+		HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->events[first + 2*i], ctx->events[first + 2*i + 1]));
+		ms[i % CFDF_STAGES] += t;
+	}
+	return CFHIP_OK;
+}
+
+int cfhip_deflate_code_lengths(cfhip_ctx* ctx, const uint32_t* counts, uint32_t n, uint32_t limit, uint8_t* lengths)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	ctx->error.clear();
+	if (!counts || !lengths)
+		return fail(ctx, CFHIP_E_INVALID, "deflate_code_lengths: counts or lengths is NULL");
+	if (n < 2u || n > 288u || limit < 1u || limit > (uint32_t)CFDF_LIMIT || (1u << limit) < n)
+		return fail(ctx, CFHIP_E_INVALID, "deflate_code_lengths: %u symbols at limit %u", n, limit);
+	unsigned long long sum = 0;
+	for (uint32_t i = 0; i < n; ++i)
+		sum += counts[i];
+	if (sum + 2u >= 1ull << 32)
+		return fail(ctx, CFHIP_E_INVALID, "deflate_code_lengths: the counts sum to 2^32 or more");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, ctx->stream);
+	deflate_begin_call(ctx, lease.stream);
+	ctx->df_slices = 0;
+	int rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, 4096u);
+	if (rc != CFHIP_OK)
+		return rc;
+	uint32_t* d_counts = static_cast<uint32_t*>(ctx->d_lz);
+	uint8_t* d_lengths = static_cast<uint8_t*>(ctx->d_lz) + 2048u;
+	HIP_TRY(ctx, hipMemcpyAsync(d_counts, counts, 4u*n, hipMemcpyHostToDevice, lease.stream));
+	hipEvent_t a, b;
+	rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, lease.stream));
+	const hipError_t e = cfhip_launch_deflate_code_lengths(d_counts, n, limit, d_lengths, lease.stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "deflate_code_lengths launch: %s", hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, lease.stream));
+	HIP_TRY(ctx, hipMemcpyAsync(lengths, d_lengths, n, hipMemcpyDeviceToHost, lease.stream));
+	return lease.done(true);
 }
 
 // cfhip_rdo_target and cfhip_rdo_target_device

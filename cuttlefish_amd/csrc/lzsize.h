@@ -55,6 +55,41 @@ inline cflz_layout cflz_scratch(size_t slice, size_t sort_bytes)
 	return l;
 }
 
+// A position's word after the match stage: L | (D - 1) << 16.  The parse flags it in bits 14 and 15.
+#define CFLZ_TAKEN 0x8000u    // the position's match survives the lazy rule
+#define CFLZ_SEEN 0x4000u     // the parse visits the position
+
+#ifdef __HIPCC__
+// deflate's length code - 257 and its extra bits for 3 <= len <= 258 (RFC 1951, 3.2.5)
+__device__ __forceinline__ uint32_t lz_length_code(uint32_t len, uint32_t* extra)
+{
+	if (len == 258u) {
+		*extra = 0u;
+		return 28u;
+	}
+	const uint32_t l = len - 3u;
+	if (l < 8u) {
+		*extra = 0u;
+		return l;
+	}
+	const uint32_t e = 29u - (uint32_t)__builtin_clz(l);     // floor(log2 l) - 2
+	*extra = e;
+	return 4u*e + 4u + ((l >> e) & 3u);
+}
+
+// deflate's distance code and its extra bits for d1 = distance - 1, 0 <= d1 < 32768
+__device__ __forceinline__ uint32_t lz_dist_code(uint32_t d1, uint32_t* extra)
+{
+	if (d1 < 4u) {
+		*extra = 0u;
+		return d1;
+	}
+	const uint32_t e = 30u - (uint32_t)__builtin_clz(d1);    // floor(log2 d1) - 1
+	*extra = e;
+	return 2u*e + 2u + ((d1 >> e) & 1u);
+}
+#endif
+
 // Bytes of temporary storage the radix sort needs for m pairs (a query, nothing runs).
 extern "C" hipError_t cfhip_lz_sort_bytes(size_t m, size_t* bytes);
 
@@ -64,6 +99,11 @@ extern "C" hipError_t cfhip_lz_sort_bytes(size_t m, size_t* bytes);
 // matches, matched_bytes) are ADDED to acc (zeroed by the caller before the first slice).  ev: NULL, or
 // 2 x CFLZ_STAGES events recorded around the stages.
 extern "C" hipError_t cfhip_launch_lz_slice(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t carry,
+	uint32_t n, hipEvent_t* ev, hipStream_t stream);
+
+// The first three stages alone (keys, sort, match): the (L, D - 1) word of every target position in the layout's ld
+// array.  ev: NULL, or the first 2 x 3 events of a stage list.  csrc/deflate.hip builds on it.
+extern "C" hipError_t cfhip_launch_lz_matches(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t carry,
 	uint32_t n, hipEvent_t* ev, hipStream_t stream);
 
 // out[0..5] = bytes_in, bits_q16, est_bytes, literals, matches, matched_bytes from the four sums.

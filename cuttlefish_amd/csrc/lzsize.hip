@@ -93,37 +93,8 @@ __global__ __launch_bounds__(256) void cfhip_lz_match_kernel(const uint8_t* __re
 	ld[t] = best ? (best | ((dist - 1u) << 16)) : 0u;
 }
 
-// deflate's length code - 257 and its extra bits for 3 <= len <= 258 (RFC 1951, 3.2.5)
-__device__ __forceinline__ uint32_t lz_length_code(uint32_t len, uint32_t* extra)
-{
-	if (len == 258u) {
-		*extra = 0u;
-		return 28u;
-	}
-	const uint32_t l = len - 3u;
-	if (l < 8u) {
-		*extra = 0u;
-		return l;
-	}
-	const uint32_t e = 29u - (uint32_t)__builtin_clz(l);     // floor(log2 l) - 2
-	*extra = e;
-	return 4u*e + 4u + ((l >> e) & 3u);
-}
-
-// deflate's distance code and its extra bits for d1 = distance - 1, 0 <= d1 < 32768
-__device__ __forceinline__ uint32_t lz_dist_code(uint32_t d1, uint32_t* extra)
-{
-	if (d1 < 4u) {
-		*extra = 0u;
-		return d1;
-	}
-	const uint32_t e = 30u - (uint32_t)__builtin_clz(d1);    // floor(log2 d1) - 1
-	*extra = e;
-	return 2u*e + 2u + ((d1 >> e) & 1u);
-}
-
-#define LZ_TAKEN 0x8000u     // the position's match survives the lazy rule
-#define LZ_SEEN 0x4000u      // the parse visits the position
+#define LZ_TAKEN CFLZ_TAKEN
+#define LZ_SEEN CFLZ_SEEN
 
 // One wavefront per chunk.  bytes: the slice's first TARGET byte.  LDS: 16 KiB of L / D and 1280 bytes of counters.
 __global__ __launch_bounds__(64) void cfhip_lz_parse_kernel(const uint8_t* __restrict__ bytes,
@@ -294,29 +265,25 @@ extern "C" hipError_t cfhip_lz_sort_bytes(size_t m, size_t* bytes)
 	return rocprim::radix_sort_pairs(nullptr, *bytes, none, none, none, none, m, 0u, 32u, (hipStream_t)nullptr, false);
 }
 
-extern "C" hipError_t cfhip_launch_lz_slice(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t carry,
-	uint32_t n, hipEvent_t* ev, hipStream_t stream)
-{
-	const uint32_t m = carry + n;
-	const uint32_t pairs = m >= 4u ? m - 3u : 0u;
-	const uint32_t blocks = (n + CFLZ_COSTBLK - 1u)/CFLZ_COSTBLK, chunks = (n + CFLZ_CHUNK - 1u)/CFLZ_CHUNK;
-	uint8_t* bytes = base + lay->bytes;
-	uint32_t* keys_in = reinterpret_cast<uint32_t*>(base + lay->keys_in);
-	uint32_t* keys_out = reinterpret_cast<uint32_t*>(base + lay->keys_out);
-	uint32_t* pos_in = reinterpret_cast<uint32_t*>(base + lay->pos_in);
-	uint32_t* pos_out = reinterpret_cast<uint32_t*>(base + lay->pos_out);
-	uint32_t* ld = reinterpret_cast<uint32_t*>(base + lay->ld);
-	uint32_t* hist = reinterpret_cast<uint32_t*>(base + lay->hist);
-	unsigned long long* acc = reinterpret_cast<unsigned long long*>(base + lay->acc);
-	hipError_t e = hipSuccess;
 #define LZ_STAGE(k, body) do { \
 		if (ev && (e = hipEventRecord(ev[2*(k)], stream)) != hipSuccess) return e; \
 		body; \
 		if ((e = hipGetLastError()) != hipSuccess) return e; \
 		if (ev && (e = hipEventRecord(ev[2*(k) + 1], stream)) != hipSuccess) return e; \
 	} while (0)
-	if ((e = hipMemsetAsync(hist, 0, (size_t)blocks*CFLZ_HIST*4u, stream)) != hipSuccess)
-		return e;
+
+extern "C" hipError_t cfhip_launch_lz_matches(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t carry,
+	uint32_t n, hipEvent_t* ev, hipStream_t stream)
+{
+	const uint32_t m = carry + n;
+	const uint32_t pairs = m >= 4u ? m - 3u : 0u;
+	uint8_t* bytes = base + lay->bytes;
+	uint32_t* keys_in = reinterpret_cast<uint32_t*>(base + lay->keys_in);
+	uint32_t* keys_out = reinterpret_cast<uint32_t*>(base + lay->keys_out);
+	uint32_t* pos_in = reinterpret_cast<uint32_t*>(base + lay->pos_in);
+	uint32_t* pos_out = reinterpret_cast<uint32_t*>(base + lay->pos_out);
+	uint32_t* ld = reinterpret_cast<uint32_t*>(base + lay->ld);
+	hipError_t e = hipSuccess;
 	LZ_STAGE(0, hipLaunchKernelGGL(cfhip_lz_keys_kernel, dim3((m + 255u)/256u), dim3(256), 0, stream, bytes, m, carry,
 		keys_in, pos_in, ld));
 	LZ_STAGE(1, {
@@ -339,11 +306,27 @@ extern "C" hipError_t cfhip_launch_lz_slice(uint8_t* base, const cflz_layout* la
 			hipLaunchKernelGGL(cfhip_lz_match_kernel, dim3((pairs + 255u)/256u), dim3(256), 0, stream, bytes, keys_out,
 				pos_out, pairs, carry, n, ld);
 	});
-	LZ_STAGE(3, hipLaunchKernelGGL(cfhip_lz_parse_kernel, dim3(chunks), dim3(64), 0, stream, bytes + carry, ld, n, hist));
-	LZ_STAGE(4, hipLaunchKernelGGL(cfhip_lz_cost_kernel, dim3(blocks), dim3(64), 0, stream, hist, acc));
-#undef LZ_STAGE
 	return hipSuccess;
 }
+
+extern "C" hipError_t cfhip_launch_lz_slice(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t carry,
+	uint32_t n, hipEvent_t* ev, hipStream_t stream)
+{
+	const uint32_t blocks = (n + CFLZ_COSTBLK - 1u)/CFLZ_COSTBLK, chunks = (n + CFLZ_CHUNK - 1u)/CFLZ_CHUNK;
+	uint8_t* bytes = base + lay->bytes;
+	uint32_t* ld = reinterpret_cast<uint32_t*>(base + lay->ld);
+	uint32_t* hist = reinterpret_cast<uint32_t*>(base + lay->hist);
+	unsigned long long* acc = reinterpret_cast<unsigned long long*>(base + lay->acc);
+	hipError_t e = hipSuccess;
+	if ((e = hipMemsetAsync(hist, 0, (size_t)blocks*CFLZ_HIST*4u, stream)) != hipSuccess)
+		return e;
+	if ((e = cfhip_launch_lz_matches(base, lay, sort_bytes, carry, n, ev, stream)) != hipSuccess)
+		return e;
+	LZ_STAGE(3, hipLaunchKernelGGL(cfhip_lz_parse_kernel, dim3(chunks), dim3(64), 0, stream, bytes + carry, ld, n, hist));
+	LZ_STAGE(4, hipLaunchKernelGGL(cfhip_lz_cost_kernel, dim3(blocks), dim3(64), 0, stream, hist, acc));
+	return hipSuccess;
+}
+#undef LZ_STAGE
 
 extern "C" hipError_t cfhip_launch_lz_final(const unsigned long long* acc, unsigned long long bytes_in,
 	unsigned long long* out, hipStream_t stream)

@@ -897,6 +897,21 @@ class Texture:
             return None
         return self._context().lz_size([p for _, _, _, p in self._flat()])
 
+    def pack(self):
+        """The zlib stream (Context.deflate) of this converted texture's payloads: data() of every surface in
+        packed_size()'s order as one stream, for any format; zlib.decompress returns those bytes.  Its tokens are the
+        ones packed_size() prices.  None when the texture is not converted."""
+        if not self._textures:
+            return None
+        ctx = self._context()
+        out = ctx.deflate([p for _, _, _, p in self._flat()])
+        self._pack_result = ctx.deflate_result()
+        return out
+
+    def pack_result(self):
+        """The cfhip_deflate_result of the last pack() as a dict; None before the first one."""
+        return getattr(self, "_pack_result", None)
+
     def convert_and_compare(self, format: Format, type: Type, quality: Quality = Quality.Normal,
                             alpha_type: Alpha = Alpha.Standard,
                             color_mask: Sequence[bool] = (True, True, True, True), ssim: bool = True):

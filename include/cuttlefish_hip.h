@@ -700,6 +700,49 @@ size_t cfhip_lz_slice_bytes(cfhip_ctx* ctx, size_t bytes);
  * Synchronises the stream. */
 int cfhip_lz_stage_ms(cfhip_ctx* ctx, float ms[5]);
 
+/* ---- the zlib stream of payloads (csrc/deflate.hip) ----
+ * The real encoder behind the estimate: the stream (the spans of a call, concatenated; fewer than 2^31 bytes) becomes
+ * one zlib stream (RFC 1950 around RFC 1951) that any inflate reads back.  The tokens are exactly those cfhip_lz_size
+ * prices -- same candidates, same parse, same 4096-byte chunks -- so literals, matches and matched_bytes equal its.
+ * Every 65536 input bytes form a group that starts on a byte boundary and takes the smallest of three forms: stored
+ * blocks, the fixed codes, or its own length-limited Huffman codes (15 bits; 7 for the code-length code) with the
+ * code-table header; a coded group ends in an empty stored block.  The definition, byte for byte, is
+ * tests/deflate_ref.py; identical calls return identical bytes, whatever the slice (cfhip_lz_slice_bytes governs this
+ * path too).  Scratch belongs to the context: about 21.4 bytes per byte of a slice. */
+typedef struct cfhip_deflate_result {
+	uint64_t bytes_in, bytes_out;                           /* bytes of the stream, bytes written */
+	uint64_t blocks_stored, blocks_fixed, blocks_dynamic;   /* groups per form */
+	uint64_t literals, matches, matched_bytes;              /* cfhip_lz_stats' */
+	uint32_t adler32, reserved;                             /* the stream's Adler-32; 0 */
+} cfhip_deflate_result;
+
+/* Bytes that hold the zlib stream of any n input bytes: 11 + n + 10 per started group of 65536.  Needs no device. */
+size_t cfhip_deflate_bound(size_t n);
+
+/* Host spans and a host buffer of `cap` bytes; cap < cfhip_deflate_bound(bytes of the stream) is CFHIP_E_CAPACITY,
+ * 2^31 bytes or more too.  Bytes of `out` past result->bytes_out are unspecified.  A span of 0 bytes is skipped; a
+ * stream of 0 bytes is CFHIP_OK with the 11-byte stream of an empty input and needs no context.  Every argument is
+ * checked before anything is enqueued (a NULL ctx is reported last).  Blocking. */
+int cfhip_deflate(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out, size_t cap,
+	cfhip_deflate_result* result);
+
+/* Device spans (a host array of device pointers, any alignment); out_device: `cap` bytes on the device, 4-byte aligned,
+ * overwritten up to cfhip_deflate_bound; result_device: one cfhip_deflate_result on the device, 8-byte aligned.
+ * The stream rules of cfhip_compare_device. */
+int cfhip_deflate_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out_device, size_t cap,
+	cfhip_deflate_result* result_device, void* stream);
+
+/* The two entries below are diagnostic, like cfhip_lz_stage_ms.
+ *
+ * Kernel time of the eight stages (keys, sort, match, parse, adler, codes, offsets, emit) of the most recent call on
+ * this context, summed over its slices (ms); CFHIP_E_INVALID unless that call was a cfhip_deflate*.  Synchronises. */
+int cfhip_deflate_stage_ms(cfhip_ctx* ctx, float ms[8]);
+
+/* The device code builder alone: the code lengths (at most `limit` <= 15 bits, 2 <= n <= 288 <= 2^limit symbols) of a
+ * histogram in host memory, by the rule of tests/deflate_ref.py code_lengths: fewer than two used symbols are made two,
+ * the lengths' Kraft sum is exactly 1.  Blocking. */
+int cfhip_deflate_code_lengths(cfhip_ctx* ctx, const uint32_t* counts, uint32_t n, uint32_t limit, uint8_t* lengths);
+
 /* The pass to a target: the smallest lambda whose result is estimated at no more than
  * T = floor(target_ratio * est_bytes_plain), est_bytes_plain being the estimate of the payloads as given.  The stream
  * is the surfaces' payloads concatenated in call order.  params->lambda is the largest lambda allowed:
@@ -811,7 +854,7 @@ int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* p
 	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size* or cfhip_image_ops_device call on
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate* or cfhip_image_ops_device call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
