@@ -175,6 +175,7 @@ class PixelType(enum.IntEnum):
 
 
 E_INVALID, E_UNSUPPORTED, E_CAPACITY, E_DEVICE, E_NO_DEVICE = -1, -2, -3, -4, -5
+E_DATA = -6                     # cfhip_inflate: the stream or its index is invalid
 
 # cfhip_consumed_fn: void (*)(void* user, size_t surface_index)
 CONSUMED_FN = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_size_t)
@@ -197,7 +198,9 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_lz_size", "cfhip_lz_size_device", "cfhip_lz_slice_bytes", "cfhip_lz_stage_ms",
            "cfhip_rdo_target", "cfhip_rdo_target_device",
            "cfhip_deflate_bound", "cfhip_deflate", "cfhip_deflate_device", "cfhip_deflate_stage_ms",
-           "cfhip_deflate_code_lengths"]
+           "cfhip_deflate_code_lengths",
+           "cfhip_zindex_entries", "cfhip_deflate_indexed", "cfhip_deflate_indexed_device",
+           "cfhip_inflate", "cfhip_inflate_device", "cfhip_inflate_stage_ms"]
 
 
 class Layout(enum.IntEnum):
@@ -372,6 +375,33 @@ def deflate_bound(n: int) -> int:
     """cfhip_deflate_bound: bytes that hold the zlib stream of any n input bytes (no device needed)"""
     return int(load_library().cfhip_deflate_bound(int(n)))
 
+
+
+class ZIndexEntry(ctypes.Structure):
+    """struct cfhip_zindex_entry"""
+    _fields_ = [("header_bit", ctypes.c_uint64), ("token_bit", ctypes.c_uint64)]
+
+
+class InflateResult(ctypes.Structure):
+    """struct cfhip_inflate_result"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("bytes_in", "bytes_out", "literals", "matches", "matched_bytes")] + \
+               [(n, ctypes.c_uint32) for n in ("adler32", "status", "bad_chunk", "rounds")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+INFLATE_STAGES = ("decode", "resolve", "pack", "fold")      # cfhip_inflate_stage_ms
+# enum cfhip_inflate_status
+INFLATE_CLASSES = ("ok", "wrapper", "index", "block header", "code", "distance", "overrun", "checksum")
+ZINDEX_CHUNK = 4096             # output bytes per index entry
+
+
+def zindex_entries(n: int) -> int:
+    """cfhip_zindex_entries: entries of the index of a stream whose output is n bytes (no device needed)"""
+    return int(load_library().cfhip_zindex_entries(int(n)))
+
+
 RDO_NO_CAP = 0xFFFFFFFF         # max_sse_increase: no cap
 RDO_ROW_ABOVE = 1               # CFHIP_RDO_ROW_ABOVE
 
@@ -405,9 +435,10 @@ def make_image_ops(ops=0, src_color_space=ColorSpace.Linear, dst_color_space=Non
 
 
 class CfhipError(RuntimeError):
-    def __init__(self, code: int, text: str):
+    def __init__(self, code: int, text: str, status: Optional[int] = None, bad_chunk: Optional[int] = None):
         super().__init__("cfhip error %d: %s" % (code, text))
         self.code = code
+        self.status, self.bad_chunk = status, bad_chunk     # E_DATA: the error class and the lowest failing chunk
 
 
 _lib = None
@@ -606,6 +637,23 @@ def load_library(path: Optional[str] = None):
     L.cfhip_deflate_code_lengths.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32,
                                              ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8)]
     L.cfhip_deflate_code_lengths.restype = ctypes.c_int
+    L.cfhip_zindex_entries.argtypes = [ctypes.c_size_t]
+    L.cfhip_zindex_entries.restype = ctypes.c_size_t
+    L.cfhip_deflate_indexed.argtypes = [ctypes.c_void_p, ctypes.POINTER(LzSpan), ctypes.c_size_t, ctypes.c_void_p,
+                                        ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.cfhip_deflate_indexed.restype = ctypes.c_int
+    L.cfhip_deflate_indexed_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(LzSpan), ctypes.c_size_t, ctypes.c_void_p,
+                                               ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                               ctypes.c_void_p]
+    L.cfhip_deflate_indexed_device.restype = ctypes.c_int
+    L.cfhip_inflate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+    L.cfhip_inflate.restype = ctypes.c_int
+    L.cfhip_inflate_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_inflate_device.restype = ctypes.c_int
+    L.cfhip_inflate_stage_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    L.cfhip_inflate_stage_ms.restype = ctypes.c_int
     L.cfhip_rdo_target.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RdoSurface),
                                    ctypes.c_size_t, ctypes.POINTER(RdoExParams), ctypes.POINTER(ctypes.c_uint8),
                                    ctypes.c_void_p, ctypes.c_float, ctypes.POINTER(RdoTargetResult)]
@@ -1284,6 +1332,78 @@ class Context:
             self._h, c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), c.size, int(limit),
             out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
         return out
+
+    def deflate_indexed(self, payloads):
+        """deflate() with the stream's index (cfhip_deflate_indexed): -> (the same bytes, the index as an (entries, 2)
+        uint64 array of header_bit, token_bit per 4096 input bytes).  deflate_result() returns the call's result."""
+        if isinstance(payloads, (bytes, bytearray, np.ndarray)):
+            payloads = [payloads]
+        parts = [np.frombuffer(bytes(p), np.uint8) if isinstance(p, (bytes, bytearray))
+                 else np.ascontiguousarray(p).reshape(-1).view(np.uint8) for p in payloads]
+        spans = (LzSpan*max(len(parts), 1))()
+        for i, p in enumerate(parts):
+            spans[i].bytes, spans[i].n = (p.ctypes.data if p.size else None), p.size
+        total = sum(p.size for p in parts)
+        cap = deflate_bound(total)
+        out = np.empty(cap, np.uint8)
+        index = np.zeros((zindex_entries(total), 2), np.uint64)
+        res = DeflateResult()
+        self._check(self._lib.cfhip_deflate_indexed(self._h, spans, len(parts), out.ctypes.data, cap,
+                                                    index.ctypes.data if index.size else None, index.shape[0],
+                                                    ctypes.addressof(res)))
+        self._deflate_result = res.as_dict()
+        return out[:res.bytes_out].tobytes(), index
+
+    def deflate_indexed_device(self, spans: Sequence[tuple], out: int, cap: int, index: int, index_entries: int,
+                               result: int, stream: int = 0):
+        """Device path of deflate_indexed: deflate_device's arguments, and index: device pointer to index_entries
+        cfhip_zindex_entry, 8-byte aligned."""
+        arr = (LzSpan*max(len(spans), 1))()
+        for i, (ptr, n) in enumerate(spans):
+            arr[i].bytes, arr[i].n = int(ptr) or None, int(n)
+        self._check(self._lib.cfhip_deflate_indexed_device(
+            self._h, arr, len(spans), ctypes.c_void_p(int(out)) if out else None, int(cap),
+            ctypes.c_void_p(int(index)) if index else None, int(index_entries),
+            ctypes.c_void_p(int(result)) if result else None, ctypes.c_void_p(stream) if stream else None))
+
+    def inflate(self, stream, index, n: int) -> bytes:
+        """The n bytes of an indexed zlib stream (cfhip_inflate).  index: (entries, 2) integers, header_bit and token_bit
+        per 4096 output bytes.  A stream or index that is invalid raises CfhipError with code E_DATA, the error class
+        in .status and the lowest failing chunk in .bad_chunk.  inflate_result() returns the call's result either way."""
+        z = np.frombuffer(bytes(stream), np.uint8)
+        idx = np.ascontiguousarray(np.asarray(index, np.uint64).reshape(-1, 2))
+        out = np.empty(int(n), np.uint8)
+        res = InflateResult()
+        # (an empty stream still passes a pointer: NULL is an argument error)
+        zbuf = z if z.size else np.zeros(1, np.uint8)
+        rc = self._lib.cfhip_inflate(self._h, zbuf.ctypes.data, z.size, idx.ctypes.data if idx.size else None,
+                                     idx.shape[0], out.ctypes.data if out.size else None, out.size, ctypes.addressof(res))
+        if rc == E_DATA:
+            self._inflate_result = res.as_dict()
+            raise CfhipError(rc, self._lib.cfhip_last_error(self._h).decode(), res.status, res.bad_chunk)
+        self._check(rc)
+        self._inflate_result = res.as_dict()
+        return out.tobytes()
+
+    def inflate_result(self) -> Optional[dict]:
+        """The cfhip_inflate_result of the last inflate() on this context; None before the first one."""
+        return getattr(self, "_inflate_result", None)
+
+    def inflate_device(self, zstream: int, zbytes: int, index: int, index_entries: int, out: int, out_bytes: int,
+                       result: int, stream: int = 0):
+        """Device path of inflate.  zstream, index (8-byte aligned), out (4-byte aligned) and result (one
+        cfhip_inflate_result, 8-byte aligned) are device pointers.  An invalid stream is reported through the result's
+        status, not raised.  stream 0 = the context's stream (the call then synchronises)."""
+        def ptr(v):
+            return ctypes.c_void_p(int(v)) if v else None
+        self._check(self._lib.cfhip_inflate_device(self._h, ptr(zstream), int(zbytes), ptr(index), int(index_entries),
+                                                   ptr(out), int(out_bytes), ptr(result), ptr(stream)))
+
+    def inflate_stage_ms(self) -> dict:
+        """Kernel ms of the last inflate's stages: decode, resolve, pack, fold"""
+        ms = (ctypes.c_float*len(INFLATE_STAGES))()
+        self._check(self._lib.cfhip_inflate_stage_ms(self._h, ms))
+        return dict(zip(INFLATE_STAGES, (float(v) for v in ms)))
 
     def rdo_target(self, payloads: Sequence[np.ndarray], sources: Sequence[np.ndarray], fmt, typ=Type.UNorm,
                    target_ratio: float = 0.85, lam: float = 32.0, max_sse_increase: Optional[int] = None, mask=None,

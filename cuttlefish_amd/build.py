@@ -151,7 +151,10 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  # the zlib encoder behind it (csrc/deflate.hip)
                  "cfhip_deflate_parse_kernel", "cfhip_deflate_adler_kernel", "cfhip_deflate_codes_kernel",
                  "cfhip_deflate_lengths_kernel", "cfhip_deflate_offsets_kernel", "cfhip_deflate_emit_kernel",
-                 "cfhip_deflate_final_kernel")
+                 "cfhip_deflate_final_kernel",
+                 # indexed zlib streams back to bytes (csrc/inflate.hip), and the encoder's index
+                 "cfhip_inflate_decode_kernel", "cfhip_inflate_resolve_kernel", "cfhip_inflate_pack_kernel",
+                 "cfhip_inflate_fold_kernel", "cfhip_inflate_final_kernel", "cfhip_zindex_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

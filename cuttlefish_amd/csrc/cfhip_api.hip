@@ -13,6 +13,7 @@
 #include "rdo.h"
 #include "lzsize.h"
 #include "deflate.h"
+#include "inflate.h"
 #include "../../include/cuttlefish_hip.h"
 
 #include <cmath>
@@ -25,6 +26,7 @@
 #include <new>
 #include <algorithm>
 #include <map>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -200,6 +202,7 @@ struct cfhip_ctx {
 	size_t lz_slice = 0;              // cfhip_lz_slice_bytes: 0 = CFLZ_SLICE_DEFAULT
 	size_t lz_first_event = 0, lz_slices = 0;   // the last estimate's event pairs: CFLZ_STAGES per slice
 	size_t df_first_event = 0, df_slices = 0;   // the last cfhip_deflate*'s event pairs: CFDF_STAGES per slice
+	size_t inf_first_event = 0, inf_slices = 0; // the last cfhip_inflate*'s event pairs: CFINF_STAGES per slice
 	void* d_rdo_keep = nullptr;       // cfhip_rdo_target: the pristine payloads every trial starts from
 	size_t rdo_keep_cap = 0;
 	std::map<int, void*> astc_tables; // per-format device tables (built on first use)
@@ -3427,8 +3430,9 @@ static int deflate_check(cfhip_ctx* ctx, const char* what, const cfhip_lz_span* 
 
 // The stream of p (total > 0) into out_device (zeroed here) and the result into result_device, enqueued on the lease's
 // stream: slices of whole groups, each behind the W bytes before it, the state carried on the device.
+// index_device: NULL, or the stream's index entries (cfhip_deflate_indexed*), written slice by slice from the group records.
 static int deflate_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hipMemcpyKind kind, uint8_t* out_device,
-	unsigned long long* result_device)
+	unsigned long long* result_device, cfinf_entry* index_device = nullptr)
 {
 	const hipStream_t stream = lease.stream;
 	const size_t slice = std::min(lz_slice_of(ctx), (p.total + CFLZ_COSTBLK - 1u)/CFLZ_COSTBLK*CFLZ_COSTBLK);
@@ -3459,6 +3463,12 @@ static int deflate_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hip
 			s1 == p.total, out_device, ev, stream);
 		if (e != hipSuccess)
 			return fail(ctx, CFHIP_E_DEVICE, "deflate launch: %s", hipGetErrorString(e));
+		if (index_device) {
+			const hipError_t ie = cfhip_launch_zindex(reinterpret_cast<const uint32_t*>(base + lay.blk), (uint32_t)(s1 - s0),
+				s0/CFLZ_CHUNK, index_device, stream);
+			if (ie != hipSuccess)
+				return fail(ctx, CFHIP_E_DEVICE, "deflate index launch: %s", hipGetErrorString(ie));
+		}
 		++ctx->df_slices;
 	}
 	const hipError_t e = cfhip_launch_deflate_final(state, (unsigned long long)p.total, out_device, result_device, stream);
@@ -3473,21 +3483,24 @@ static void deflate_begin_call(cfhip_ctx* ctx, hipStream_t stream)
 	ctx->last_kernel = "cfhip_deflate_emit_kernel";
 }
 
-static int deflate_host(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, void* out, cfhip_deflate_result* result)
+static int deflate_host(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, void* out, cfhip_deflate_result* result,
+	cfhip_zindex_entry* index = nullptr)
 {
 	static_assert(sizeof(cfhip_deflate_result) == 9*sizeof(unsigned long long), "the final kernel's words are the struct");
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	deflate_begin_call(ctx, lease.stream);
 	// the result lies behind the stream's bytes, 256-byte aligned
 	const size_t res_off = (cfdf_bound(p.total) + 255u)/256u*256u;
+	const size_t entries = (p.total + CFLZ_CHUNK - 1u)/CFLZ_CHUNK;      // the index lies behind the result
 	int rc = lease.acquire();
 	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, res_off + 256u);
+		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, res_off + 256u + (index ? entries*sizeof(cfinf_entry) : 0u));
 	if (rc != CFHIP_OK)
 		return rc;
 	uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out);
 	unsigned long long* d_res = reinterpret_cast<unsigned long long*>(d_out + res_off);
-	rc = deflate_run(ctx, lease, p, hipMemcpyHostToDevice, d_out, d_res);
+	cfinf_entry* d_index = index ? reinterpret_cast<cfinf_entry*>(d_out + res_off + 256u) : nullptr;
+	rc = deflate_run(ctx, lease, p, hipMemcpyHostToDevice, d_out, d_res, d_index);
 	if (rc != CFHIP_OK)
 		return rc;
 	cfhip_deflate_result res;
@@ -3496,6 +3509,8 @@ static int deflate_host(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, vo
 	if (res.bytes_out > cfdf_bound(p.total))
 		return fail(ctx, CFHIP_E_DEVICE, "deflate: %llu bytes exceed the bound", (unsigned long long)res.bytes_out);
 	HIP_TRY(ctx, hipMemcpyAsync(out, d_out, (size_t)res.bytes_out, hipMemcpyDeviceToHost, lease.stream));
+	if (index)
+		HIP_TRY(ctx, hipMemcpyAsync(index, d_index, entries*sizeof(cfinf_entry), hipMemcpyDeviceToHost, lease.stream));
 	rc = lease.done(true);
 	if (rc != CFHIP_OK)
 		return rc;
@@ -3629,6 +3644,303 @@ int cfhip_deflate_code_lengths(cfhip_ctx* ctx, const uint32_t* counts, uint32_t 
 	HIP_TRY(ctx, hipEventRecord(b, lease.stream));
 	HIP_TRY(ctx, hipMemcpyAsync(lengths, d_lengths, n, hipMemcpyDeviceToHost, lease.stream));
 	return lease.done(true);
+}
+
+// ---- indexed zlib streams and their inflate (csrc/inflate.hip, csrc/inflate.h; the definition is tests/inflate_ref.py) --
+static_assert(sizeof(cfhip_zindex_entry) == sizeof(cfinf_entry) && sizeof(cfinf_entry) == 16, "the kernels' entry is the struct");
+
+size_t cfhip_zindex_entries(size_t n)
+{
+	return n/CFINF_CHUNK + (n % CFINF_CHUNK ? 1u : 0u);
+}
+
+// The checks cfhip_deflate_indexed* add to deflate_check's.
+static int zindex_check(cfhip_ctx* ctx, const char* what, const LzPlan& p, const void* index, size_t index_entries, bool host)
+{
+	const size_t need = cfhip_zindex_entries(p.total);
+	if (need && !index)
+		return fail(ctx, CFHIP_E_INVALID, "%s: index is NULL", what);
+	if (!host && (uintptr_t)index % 8u != 0)
+		return fail(ctx, CFHIP_E_INVALID, "%s: index must be 8-byte aligned", what);
+	if (index_entries < need)
+		return fail(ctx, CFHIP_E_CAPACITY, "%s: index holds %zu entries, cfhip_zindex_entries(%zu) = %zu", what, index_entries,
+			p.total, need);
+	return CFHIP_OK;
+}
+
+int cfhip_deflate_indexed(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out, size_t cap,
+	cfhip_zindex_entry* index, size_t index_entries, cfhip_deflate_result* result)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		LzPlan p;
+		int rc = deflate_check(ctx, "deflate_indexed", spans, n_spans, out, cap, result, true, &p);
+		if (rc == CFHIP_OK)
+			rc = zindex_check(ctx, "deflate_indexed", p, index, index_entries, true);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!p.total) {
+			memcpy(out, kDeflateEmpty, sizeof(kDeflateEmpty));
+			*result = deflate_empty_result();
+			return CFHIP_OK;
+		}
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		StagingLease lease(ctx, ctx->stream);
+		return deflate_host(ctx, lease, p, out, result, index);
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "deflate_indexed: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "deflate_indexed: unknown exception");
+	}
+}
+
+int cfhip_deflate_indexed_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out_device, size_t cap,
+	cfhip_zindex_entry* index_device, size_t index_entries, cfhip_deflate_result* result_device, void* stream_)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		LzPlan p;
+		int rc = deflate_check(ctx, "deflate_indexed_device", spans, n_spans, out_device, cap, result_device, false, &p);
+		if (rc == CFHIP_OK)
+			rc = zindex_check(ctx, "deflate_indexed_device", p, index_device, index_entries, false);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		deflate_begin_call(ctx, lease.stream);
+		if (!p.total) {
+			static const cfhip_deflate_result empty = deflate_empty_result();
+			HIP_TRY(ctx, hipMemcpyAsync(out_device, kDeflateEmpty, sizeof(kDeflateEmpty), hipMemcpyHostToDevice, lease.stream));
+			HIP_TRY(ctx, hipMemcpyAsync(result_device, &empty, sizeof(empty), hipMemcpyHostToDevice, lease.stream));
+		} else {
+			rc = lease.acquire();
+			if (rc == CFHIP_OK)
+				rc = deflate_run(ctx, lease, p, hipMemcpyDeviceToDevice, static_cast<uint8_t*>(out_device),
+					reinterpret_cast<unsigned long long*>(result_device), reinterpret_cast<cfinf_entry*>(index_device));
+			if (rc != CFHIP_OK)
+				return rc;
+		}
+		return lease.done(!stream_);
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "deflate_indexed_device: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "deflate_indexed_device: unknown exception");
+	}
+}
+
+static const char* const kInflateClass[8] = {"no", "wrapper", "index", "block header", "code", "distance", "overrun",
+	"checksum"};
+
+// Every check of an inflate call, made before the context is touched.
+static int inflate_check(cfhip_ctx* ctx, const char* what, const void* z, size_t zbytes, const void* index,
+	size_t index_entries, const void* out, size_t out_bytes, const void* result, bool host)
+{
+	if (!z)
+		return fail(ctx, CFHIP_E_INVALID, "%s: zstream is NULL", what);
+	if (!result)
+		return fail(ctx, CFHIP_E_INVALID, "%s: result is NULL", what);
+	if (out_bytes && !out)
+		return fail(ctx, CFHIP_E_INVALID, "%s: out is NULL", what);
+	if (out_bytes >= ((size_t)1 << 31) || zbytes > ((size_t)1 << 32))
+		return fail(ctx, CFHIP_E_CAPACITY, "%s: 2^31 output bytes or more, or a stream above 2^32 bytes", what);
+	const size_t need = cfhip_zindex_entries(out_bytes);
+	if (need && !index)
+		return fail(ctx, CFHIP_E_INVALID, "%s: index is NULL", what);
+	if (!host && ((uintptr_t)out % 4u != 0 || (uintptr_t)result % 8u != 0 || (uintptr_t)index % 8u != 0))
+		return fail(ctx, CFHIP_E_INVALID, "%s: out must be 4-byte, index and result 8-byte aligned", what);
+	if (index_entries < need)
+		return fail(ctx, CFHIP_E_CAPACITY, "%s: index holds %zu entries, cfhip_zindex_entries(%zu) = %zu", what, index_entries,
+			out_bytes, need);
+	return CFHIP_OK;
+}
+
+// The stream at z_device into out_device and the result into result_device, enqueued on the lease's stream: the output
+// in slices of whole groups, the state carried on the device.
+static int inflate_run(cfhip_ctx* ctx, StagingLease& lease, const uint8_t* z_device, size_t zbytes,
+	const cfinf_entry* index_device, uint8_t* out_device, size_t out_bytes, unsigned long long* result_device)
+{
+	const hipStream_t stream = lease.stream;
+	const size_t slice = std::min(lz_slice_of(ctx), (std::max(out_bytes, (size_t)1) + CFLZ_COSTBLK - 1u)/CFLZ_COSTBLK*CFLZ_COSTBLK);
+	const cfinf_layout lay = cfinf_scratch(slice);
+	int rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, lay.total);
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* base = static_cast<uint8_t*>(ctx->d_lz);
+	ctx->inf_first_event = ctx->events_used;
+	ctx->inf_slices = 0;
+	size_t at = 0;
+	do {
+		const size_t end = std::min(out_bytes, at + slice);
+		hipEvent_t ev[2*CFINF_STAGES];
+		for (int k = 0; k < CFINF_STAGES; ++k) {
+			rc = next_event_pair(ctx, &ev[2*k], &ev[2*k + 1]);
+			if (rc != CFHIP_OK)
+				return rc;
+		}
+		const hipError_t e = cfhip_launch_inflate_slice(base, &lay, z_device, zbytes, index_device, out_bytes, at,
+			(uint32_t)(end - at), at == 0, out_device, ev, stream);
+		if (e != hipSuccess)
+			return fail(ctx, CFHIP_E_DEVICE, "inflate launch: %s", hipGetErrorString(e));
+		++ctx->inf_slices;
+		at = end;
+	} while (at < out_bytes);
+	const hipError_t e = cfhip_launch_inflate_final(reinterpret_cast<const unsigned long long*>(base + lay.state), z_device,
+		zbytes, out_bytes, result_device, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "inflate launch: %s", hipGetErrorString(e));
+	return CFHIP_OK;
+}
+
+static void inflate_begin_call(cfhip_ctx* ctx, hipStream_t stream)
+{
+	lz_begin_call(ctx, stream);
+	ctx->last_kernel = "cfhip_inflate_decode_kernel";
+}
+
+// A stream of no output bytes on the host: the walk from bit 16 through everything that produces no output, the
+// trailer, Adler-32 = 1 -- the kernels' routine (inflate.h), one lane wide.
+static void inflate_empty(const uint8_t* z, size_t zbytes, cfhip_inflate_result* r)
+{
+	std::unique_ptr<CfinfWork> w(new CfinfWork);
+	memset(r, 0, sizeof(*r));
+	r->bytes_in = zbytes;
+	r->status = cfinf_chunk(*w, z, zbytes, nullptr, 0u, 0u, 0u, 0u, 1u);
+	if (r->status == CFINF_OK) {
+		const uint8_t* t = z + zbytes - 4u;
+		if (((uint32_t)t[0] << 24 | (uint32_t)t[1] << 16 | (uint32_t)t[2] << 8 | t[3]) != 1u)
+			r->status = CFINF_E_CHECKSUM;
+		else
+			r->adler32 = 1u;
+	}
+}
+
+static int inflate_verdict(cfhip_ctx* ctx, const cfhip_inflate_result& r)
+{
+	if (r.status == CFINF_OK)
+		return CFHIP_OK;
+	return fail(ctx, CFHIP_E_DATA, "inflate: %s error in chunk %u", kInflateClass[r.status & 7u], r.bad_chunk);
+}
+
+int cfhip_inflate(cfhip_ctx* ctx, const void* zstream, size_t zbytes, const cfhip_zindex_entry* index, size_t index_entries,
+	void* out, size_t out_bytes, cfhip_inflate_result* result)
+{
+	static_assert(sizeof(cfhip_inflate_result) == 7*sizeof(unsigned long long), "the final kernel's words are the struct");
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		int rc = inflate_check(ctx, "inflate", zstream, zbytes, index, index_entries, out, out_bytes, result, true);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!out_bytes) {
+			inflate_empty(static_cast<const uint8_t*>(zstream), zbytes, result);
+			return inflate_verdict(ctx, *result);
+		}
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		inflate_begin_call(ctx, lease.stream);
+		// the stream and behind it the index; the output and behind it the result
+		const size_t entries = cfhip_zindex_entries(out_bytes);
+		const size_t idx_off = (zbytes + 255u)/256u*256u, res_off = (out_bytes + 255u)/256u*256u;
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, idx_off + entries*sizeof(cfinf_entry));
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, res_off + 256u);
+		if (rc != CFHIP_OK)
+			return rc;
+		uint8_t* d_z = static_cast<uint8_t*>(ctx->d_src);
+		uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out);
+		unsigned long long* d_res = reinterpret_cast<unsigned long long*>(d_out + res_off);
+		if (zbytes)
+			HIP_TRY(ctx, hipMemcpyAsync(d_z, zstream, zbytes, hipMemcpyHostToDevice, lease.stream));
+		HIP_TRY(ctx, hipMemcpyAsync(d_z + idx_off, index, entries*sizeof(cfinf_entry), hipMemcpyHostToDevice, lease.stream));
+		rc = inflate_run(ctx, lease, d_z, zbytes, reinterpret_cast<const cfinf_entry*>(d_z + idx_off), d_out, out_bytes, d_res);
+		if (rc != CFHIP_OK)
+			return rc;
+		cfhip_inflate_result res;
+		HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
+		HIP_TRY(ctx, hipStreamSynchronize(lease.stream));
+		if (res.status == CFINF_OK)
+			HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, lease.stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		*result = res;
+		return inflate_verdict(ctx, res);
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "inflate: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "inflate: unknown exception");
+	}
+}
+
+int cfhip_inflate_device(cfhip_ctx* ctx, const void* zstream_device, size_t zbytes, const cfhip_zindex_entry* index_device,
+	size_t index_entries, void* out_device, size_t out_bytes, cfhip_inflate_result* result_device, void* stream_)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		int rc = inflate_check(ctx, "inflate_device", zstream_device, zbytes, index_device, index_entries, out_device, out_bytes,
+			result_device, false);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		inflate_begin_call(ctx, lease.stream);
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = inflate_run(ctx, lease, static_cast<const uint8_t*>(zstream_device), zbytes,
+				reinterpret_cast<const cfinf_entry*>(index_device), static_cast<uint8_t*>(out_device), out_bytes,
+				reinterpret_cast<unsigned long long*>(result_device));
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "inflate_device: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "inflate_device: unknown exception");
+	}
+}
+
+int cfhip_inflate_stage_ms(cfhip_ctx* ctx, float ms[CFINF_STAGES])
+{
+	if (!ctx || !ms)
+		return CFHIP_E_INVALID;
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	const size_t first = ctx->inf_first_event, pairs = ctx->inf_slices*CFINF_STAGES;
+	if (!pairs || first + 2*pairs > ctx->events_used || ctx->last_kernel.compare(0, 13, "cfhip_inflate") != 0)
+		return fail(ctx, CFHIP_E_INVALID, "inflate_stage_ms: the last call on this context was no cfhip_inflate*");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->events_stream));
+	for (int k = 0; k < CFINF_STAGES; ++k)
+		ms[k] = 0.0f;
+	for (size_t i = 0; i < pairs; ++i) {
+		float t = 0.0f;
+		HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->events[first + 2*i], ctx->events[first + 2*i + 1]));
+		ms[i % CFINF_STAGES] += t;
+	}
+	return CFHIP_OK;
 }
 
 // cfhip_rdo_target and cfhip_rdo_target_device

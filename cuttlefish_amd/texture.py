@@ -897,16 +897,42 @@ class Texture:
             return None
         return self._context().lz_size([p for _, _, _, p in self._flat()])
 
-    def pack(self):
+    def pack(self, indexed: bool = False):
         """The zlib stream (Context.deflate) of this converted texture's payloads: data() of every surface in
         packed_size()'s order as one stream, for any format; zlib.decompress returns those bytes.  Its tokens are the
-        ones packed_size() prices.  None when the texture is not converted."""
+        ones packed_size() prices.  indexed=True: (the same stream, its index) from Context.deflate_indexed, what
+        unpack() and Context.inflate_device read back on the GPU.  None when the texture is not converted."""
         if not self._textures:
             return None
         ctx = self._context()
-        out = ctx.deflate([p for _, _, _, p in self._flat()])
+        payloads = [p for _, _, _, p in self._flat()]
+        out = ctx.deflate_indexed(payloads) if indexed else ctx.deflate(payloads)
         self._pack_result = ctx.deflate_result()
         return out
+
+    @staticmethod
+    def unpack(like: "Texture", stream, index) -> Optional["Texture"]:
+        """pack(indexed=True) undone on the GPU (Context.inflate): a converted texture with `like`'s layout, format,
+        type, alpha type, colour mask and colour space whose surfaces are the inflated bytes -- one buffer, the
+        surfaces views of it in storage order, as load() builds them.  None when `like` is not converted, and where
+        the stream with its index does not inflate to exactly the bytes of like's payloads."""
+        if not like._textures:
+            return None
+        sizes = [int(p.nbytes) for _, _, _, p in like._flat()]
+        try:
+            raw = like._context().inflate(stream, index, sum(sizes))
+        except (api.CfhipError, ValueError):
+            return None
+        t = Texture(device_id=like._device_id)
+        if not t.initialize(like._dim, like._w, like._h, like._depth, like._mips, like._color_space):
+            return None
+        blob = np.frombuffer(raw, np.uint8)
+        offs = np.cumsum([0] + sizes)
+        it = iter(range(len(sizes)))
+        t._textures = [[[blob[offs[i]:offs[i + 1]] for i in (next(it) for _ in dep)] for dep in level]
+                       for level in like._textures]
+        t._format, t._type, t._alpha, t._mask = like._format, like._type, like._alpha, like._mask
+        return t
 
     def pack_result(self):
         """The cfhip_deflate_result of the last pack() as a dict; None before the first one."""

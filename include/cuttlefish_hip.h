@@ -156,7 +156,8 @@ enum cfhip_error {
 	CFHIP_E_UNSUPPORTED = -2,  /* (format, type) pair createConverter would reject / not built yet */
 	CFHIP_E_CAPACITY = -3,     /* out_capacity too small */
 	CFHIP_E_DEVICE = -4,       /* HIP runtime error (text in cfhip_last_error) */
-	CFHIP_E_NO_DEVICE = -5     /* no usable gfx950 device */
+	CFHIP_E_NO_DEVICE = -5,    /* no usable gfx950 device */
+	CFHIP_E_DATA = -6          /* cfhip_inflate: the stream or its index is invalid (class and chunk in cfhip_last_error) */
 };
 
 typedef struct cfhip_ctx cfhip_ctx;
@@ -742,6 +743,79 @@ int cfhip_deflate_stage_ms(cfhip_ctx* ctx, float ms[8]);
  * histogram in host memory, by the rule of tests/deflate_ref.py code_lengths: fewer than two used symbols are made two,
  * the lengths' Kraft sum is exactly 1.  Blocking. */
 int cfhip_deflate_code_lengths(cfhip_ctx* ctx, const uint32_t* counts, uint32_t n, uint32_t limit, uint8_t* lengths);
+
+/* ---- indexed zlib streams and their inflate (csrc/inflate.hip, csrc/inflate.h) ----
+ * A zlib stream is serial; with a small side index every 4096 output bytes of it decode on their own.  Bits are numbered
+ * from the start of the zlib stream: bit k is bit k & 7 of byte k >> 3.  For a stream whose output is n bytes the index
+ * has ceil(n / 4096) entries.  A stream is indexable when every output position 4096 c is the first byte of a token:
+ * every stream of cfhip_deflate is, and so is any stream flushed (Z_SYNC_FLUSH) after every 4096 input bytes.  The index
+ * is a pure function of the stream; its definition, and that of everything below, is tests/inflate_ref.py. */
+typedef struct cfhip_zindex_entry {
+	uint64_t header_bit;  /* the BFINAL bit of the deflate block that holds output byte 4096*c */
+	uint64_t token_bit;   /* first bit of the literal/length code of the token that produces that byte;
+	                         in a stored block: 8 * the position of that data byte */
+} cfhip_zindex_entry;
+
+/* ceil(n / 4096).  Needs no device. */
+size_t cfhip_zindex_entries(size_t n);
+
+/* cfhip_deflate / cfhip_deflate_device with the stream's index: the same bytes and the same result for the same spans,
+ * and entry c of `index` (host memory / device memory, 8-byte aligned) for every 4096 bytes of the spans.
+ * index_entries < cfhip_zindex_entries(bytes of the spans) is CFHIP_E_CAPACITY, checked with the other arguments
+ * before anything is enqueued. */
+int cfhip_deflate_indexed(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out, size_t cap,
+	cfhip_zindex_entry* index, size_t index_entries, cfhip_deflate_result* result);
+int cfhip_deflate_indexed_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out_device, size_t cap,
+	cfhip_zindex_entry* index_device, size_t index_entries, cfhip_deflate_result* result_device, void* stream);
+
+/* The error classes of cfhip_inflate_result.status.  Which defect yields which class, and in what order a chunk
+ * notices them, is defined by tests/inflate_ref.py inflate_indexed; the kernels return its (status, bad_chunk). */
+enum cfhip_inflate_status {
+	CFHIP_INFLATE_OK = 0,
+	CFHIP_INFLATE_WRAPPER = 1,    /* CMF / FLG, or the stream is not exactly zbytes long */
+	CFHIP_INFLATE_INDEX = 2,      /* an entry is not where the stream's tokens are, or the stream holds more than out_bytes */
+	CFHIP_INFLATE_HEADER = 3,     /* a block header */
+	CFHIP_INFLATE_CODE = 4,       /* a bit pattern of no code, symbols 286 / 287, distance codes 30 / 31 */
+	CFHIP_INFLATE_DISTANCE = 5,   /* a distance that reaches before output byte 0 */
+	CFHIP_INFLATE_OVERRUN = 6,    /* the stream, or its BFINAL block, ends before the output does */
+	CFHIP_INFLATE_CHECKSUM = 7    /* the Adler-32 of the output is not the trailer's */
+};
+
+typedef struct cfhip_inflate_result {
+	uint64_t bytes_in, bytes_out;                /* bytes of the zlib stream; bytes written (0 unless status is 0) */
+	uint64_t literals, matches, matched_bytes;   /* of the tokens read (a stored byte is a literal): cfhip_deflate_result's
+	                                                for our own streams without stored groups; 0 unless status is 0 */
+	uint32_t adler32, status, bad_chunk, rounds; /* computed Adler-32; 0 or an error class; lowest failing chunk; resolve rounds run */
+} cfhip_inflate_result;
+
+/* The out_bytes bytes of an indexed zlib stream of exactly zbytes bytes (out_bytes is the expected size; fewer than
+ * 2^31, zbytes at most 2^32).  Every chunk of 4096 output bytes decodes from its entry on its own wavefront and checks
+ * that it arrives exactly at the next entry; chunk 0 checks the link from bit 16, the last chunk the end of the stream:
+ * the index is validated, not trusted, and a stream that passes is a valid zlib stream whose output is what was written.
+ * The rules of the format.  Wrapper: the low four bits of CMF are 8, FCHECK is valid, no FDICT, and the stream is
+ * exactly zbytes long (after the BFINAL block the padding bits, the big-endian Adler-32, nothing).  A dynamic header
+ * is rejected when HLIT > 286 or HDIST > 30, when a repeat code comes first or a run goes past HLIT + HDIST, when
+ * symbol 256 has length 0, or when one of the three codes has a Kraft sum above 1; an incomplete code is accepted.  A
+ * bit pattern that belongs to no code, literal/length symbols 286 and 287 and distance codes 30 and 31 are code
+ * errors; a distance that reaches before output byte 0 is a distance error.
+ * Returns CFHIP_E_DATA for a stream that fails, with *result filled and the class and chunk in cfhip_last_error; the
+ * contents of `out` are then unspecified.  Nothing outside [out, out + out_bytes) is ever written.
+ * index_entries < cfhip_zindex_entries(out_bytes) is CFHIP_E_CAPACITY; every argument is checked before anything is
+ * enqueued (a NULL ctx is reported last).  out_bytes == 0 needs no context.  `rounds` is the depth of the longest copy
+ * chain inside one slice (cfhip_lz_slice_bytes): the one field that depends on the slice.  Scratch belongs to the
+ * context: 8 bytes per byte of a slice.  Blocking. */
+int cfhip_inflate(cfhip_ctx* ctx, const void* zstream, size_t zbytes, const cfhip_zindex_entry* index,
+	size_t index_entries, void* out, size_t out_bytes, cfhip_inflate_result* result);
+
+/* Everything on the device: index_device and result_device 8-byte aligned, out_device 4-byte aligned.  Returns CFHIP_OK
+ * once enqueued; an invalid stream is reported through result_device->status.  The stream rules of
+ * cfhip_compare_device. */
+int cfhip_inflate_device(cfhip_ctx* ctx, const void* zstream_device, size_t zbytes, const cfhip_zindex_entry* index_device,
+	size_t index_entries, void* out_device, size_t out_bytes, cfhip_inflate_result* result_device, void* stream);
+
+/* Diagnostic: kernel time of the four stages (decode, resolve, pack, fold) of the most recent call on this context,
+ * summed over its slices (ms); CFHIP_E_INVALID unless that call was a cfhip_inflate*.  Synchronises. */
+int cfhip_inflate_stage_ms(cfhip_ctx* ctx, float ms[4]);
 
 /* The pass to a target: the smallest lambda whose result is estimated at no more than
  * T = floor(target_ratio * est_bytes_plain), est_bytes_plain being the estimate of the payloads as given.  The stream
