@@ -61,6 +61,9 @@ __device__ const cf_bc7_role_table k_bc7_roles = cf_bc7_make_roles();
 __device__ const cf_bc7_cand_table k_bc7_cands = cf_bc7_make_cands();
 __device__ const cf_bc7_mask_table k_bc7_masks = cf_bc7_make_masks();
 
+// the interpolation weights of a fit's palette entries as bytes (bc7_packed.h)
+__device__ const cf_bc7_weight_table k_bc7_weights = cf_bc7_make_weights();
+
 __device__ const uint16_t k_part2[64] = CF_BC7_PART2_INIT;
 
 __device__ const uint8_t k_anchor2[64] = {
@@ -371,6 +374,14 @@ __device__ __forceinline__ uint32_t ycc_pp_sum(const Tex& tx, uint32_t mask, con
 #ifndef CF_BC7_CANDW
 #define CF_BC7_CANDW 1
 #endif
+// A/B switch, a bit mask: what the selector search does before it walks the texels.  0 builds the parent's forms.
+//   1: the unit-weight palette in difference form (pal_line once per assignment, pal_at per entry: bc7_packed.h)
+//   2: the entries' weights as bytes of two table words loaded once per assignment, instead of arithmetic on ib per
+//      entry; entries 0..3 exist in every fit, so only entries 4..7 keep a validity select
+// Same payload either way.
+#ifndef CF_BC7_FITTRIMS
+#define CF_BC7_FITTRIMS 3
+#endif
 
 // Diagnostic counters (never set in the product build): per wave pass, how often the starts trip reads the
 // fit-geometry cache, how often the starts trip / the perturbation pass have only fits of <= 4 palette entries, how
@@ -410,14 +421,26 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 	// its weighted form is two words of 16-bit pairs, the cross term two v_dot2_u32_u16.
 	uint32_t pal[8], palh[8];
 	int base[8];
+	// what every entry of this fit shares: the row of weight bytes and the palette's line (bc7_packed.h)
+	uint32_t w03 = 0, w47 = 0;
+	if (CF_BC7_FITTRIMS & 2) {
+		const uint32_t* wr = k_bc7_weights.w[weight_row(m6, khalf, ib)];
+		w03 = wr[0];
+		w47 = NK == 8 ? wr[1] : 0u;
+	}
+	const PalLine line = pal_line(fe0, fe1);
 #pragma unroll
 	for (int k = 0; k < NK; ++k) {
-		const bool valid = (uint32_t)k < nk;
+		// entries 0..3 exist in every fit (an index has at least two bits)
+		const bool valid = ((CF_BC7_FITTRIMS & 2) && k < 4) || (uint32_t)k < nk;
 		// an entry past 2^ib interpolates with weight 0: its colour stays a byte vector, so the
 		// dot products below stay in range and its constant keeps it from ever winning
-		const uint32_t w = bc7_weight(ib, valid ? kbase + (uint32_t)k : 0u), iw = 64u - w;
+		const uint32_t w = (CF_BC7_FITTRIMS & 2) ? weight_at(w03, w47, (uint32_t)k)
+			: bc7_weight(ib, valid ? kbase + (uint32_t)k : 0u);
+		const uint32_t iw = 64u - w;
 		if (UNITW) {
-			pal[k] = pal_word(fe0, fe1, w);     // two channels per multiply (bc7_packed.h)
+			// two channels per multiply; in difference form one multiply and one add per channel pair
+			pal[k] = (CF_BC7_FITTRIMS & 1) ? pal_at(line, w) : pal_word(fe0, fe1, w);
 			palh[k] = 0;
 			base[k] = valid ? -(int)((__builtin_amdgcn_udot4(pal[k], pal[k], 0u, false) << 7) | w)
 				: -0x3FFFFFFF;

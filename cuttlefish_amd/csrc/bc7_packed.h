@@ -65,6 +65,64 @@ CF_PK uint32_t pal_word(uint32_t e0, uint32_t e1, uint32_t w)
 	return ((rb >> 6) & m) | ((ga << 2) & ~m);
 }
 
+// The same palette in difference form.  With a = e0 & m and b = e1 & m a pair's sum is
+// iw*a + w*b + half = (64*a + half) + w*(b - a): what stands in front of w is the same for every entry of a fit.
+// A half of b - a may be negative and then borrows from the half above it, but the true sum is non-negative and
+// below 2^32, and both sides agree mod 2^32: unsigned arithmetic gives it exactly.  The line of a fit is formed
+// once per assignment; an entry then costs one multiply and one add per channel pair.
+struct PalLine { uint32_t rb0, rbd, ga0, gad; };
+
+CF_PK PalLine pal_line(uint32_t e0, uint32_t e1)
+{
+	const uint32_t m = 0x00FF00FFu, half = 0x00200020u;
+	const uint32_t a_rb = e0 & m, a_ga = (e0 >> 8) & m;
+	PalLine l;
+	l.rb0 = (a_rb << 6) + half; l.rbd = (e1 & m) - a_rb;
+	l.ga0 = (a_ga << 6) + half; l.gad = ((e1 >> 8) & m) - a_ga;
+	return l;
+}
+
+CF_PK uint32_t pal_at(const PalLine& l, uint32_t w)
+{
+	const uint32_t m = 0x00FF00FFu;
+	// (w*d needs the full 32-bit product: d's upper half carries the borrow)
+	const uint32_t rb = l.rb0 + w*l.rbd;
+	const uint32_t ga = l.ga0 + w*l.gad;
+	return ((rb >> 6) & m) | ((ga << 2) & ~m);
+}
+
+// The interpolation weights ((k*64 + d/2)/d, d = 2^ib - 1) of a fit's up to eight palette entries as bytes of two
+// words.  Rows: index width 2 (entries 4..7 do not exist: weight 0), index width 3, and the two halves of mode 6's
+// sixteen entries, which a lane pair shares.
+#define CF_BC7_WEIGHT_ROWS 4u
+constexpr uint32_t cf_bc7_weight(uint32_t ib, uint32_t k)
+{
+	return (k*64u + (((1u << ib) - 1u) >> 1))/((1u << ib) - 1u);
+}
+struct cf_bc7_weight_table { uint32_t w[CF_BC7_WEIGHT_ROWS][2]; };
+constexpr cf_bc7_weight_table cf_bc7_make_weights()
+{
+	cf_bc7_weight_table t = {};
+	for (uint32_t k = 0; k < 8u; ++k) {
+		t.w[0][k >> 2] |= (k < 4u ? cf_bc7_weight(2u, k) : 0u) << (8u*(k & 3u));
+		t.w[1][k >> 2] |= cf_bc7_weight(3u, k) << (8u*(k & 3u));
+		t.w[2][k >> 2] |= cf_bc7_weight(4u, k) << (8u*(k & 3u));
+		t.w[3][k >> 2] |= cf_bc7_weight(4u, 8u + k) << (8u*(k & 3u));
+	}
+	return t;
+}
+// Row of a fit: mode 6's half, or the index width (a width that is neither 2 nor 3 belongs to a lane without a fit
+// and reads row 0: the index never leaves the table).
+CF_PK uint32_t weight_row(bool m6, uint32_t khalf, uint32_t ib)
+{
+	return m6 ? 2u + (khalf & 1u) : (ib == 3u ? 1u : 0u);
+}
+// Entry k = 0..7 of a row's two words
+CF_PK uint32_t weight_at(uint32_t w03, uint32_t w47, uint32_t k)
+{
+	return ((k < 4u ? w03 : w47) >> (8u*(k & 3u))) & 255u;
+}
+
 // ---- packed integer moments ----
 // The 14 integer moments of a set of texels (channel sums s_c, sums of products q_cd) in 10 words, as the per-block
 // table of bc7_encode.hip holds the whole block's: words 0..3 = q_cc | s_c << 20 (q <= 16 * 255^2 < 2^20,

@@ -107,6 +107,19 @@ __global__ void __launch_bounds__(256) k(uint32_t* out, uint32_t seed)
 	// representative): two instructions per chain step, reported per instruction
 	if (OP == 34) BODY("v_cmp_lt_u32 vcc, %1, %0\n\tv_cndmask_b32 %0, %0, %2, vcc", : "vcc")
 	if (OP == 35) BODY("v_cmp_lt_u32 vcc, %1, %0", : "vcc")   // the compare alone
+	// the classes the bookkeeping of the BC7 selector search and its reciprocals are made of, and the two fp16 dot
+	// products a float-keyed search would issue per (texel, palette entry)
+	if (OP == 36) BODY("v_alignbit_b32 %0, %0, %1, 8", )
+	if (OP == 37) BODY("v_lshrrev_b32 %0, 3, %0", )
+	if (OP == 38) BODY("v_bfe_i32 %0, %0, 7, 25", )
+	if (OP == 39) BODY("v_and_or_b32 %0, %0, %1, %2", )
+	if (OP == 40) BODY("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96", )
+	if (OP == 41) BODY("v_max_f32 %0, %0, %1", )
+	if (OP == 42) BODY("v_max3_f32 %0, %0, %1, %2", )
+	if (OP == 43) BODY("v_rcp_f32 %0, %0", )
+	if (OP == 44) BODY("v_cvt_i32_f32 %0, %0", )
+	if (OP == 45) BODY("v_dot2_f32_f16 %0, %1, %2, %0", )
+	if (OP == 46) BODY("v_dot2c_f32_f16 %0, %1, %2", )
 	uint32_t r = 0;
 #pragma unroll
 	for (int i = 0; i < 16; ++i) r ^= a[i];
@@ -155,6 +168,11 @@ int main()
 		run<29>("v_pk_mul_f32", w);   run<30>("v_pk_add_f32", w);  run<31>("v_pk_fma_f32", w);
 		run<32>("v_readlane_b32", w); run<33>("v_writelane_b32", w);
 		run<35>("v_cmp_lt_u32", w);   run<34>("v_cmp+v_cndmask", w, 2);
+		run<36>("v_alignbit_b32", w); run<37>("v_lshrrev_b32", w); run<38>("v_bfe_i32", w);
+		run<39>("v_and_or_b32", w);   run<40>("v_bitop3_b32", w);
+		run<41>("v_max_f32", w);      run<42>("v_max3_f32", w);
+		run<43>("v_rcp_f32", w);      run<44>("v_cvt_i32_f32", w);
+		run<45>("v_dot2_f32_f16", w); run<46>("v_dot2c_f32_f16", w);
 	}
 	return 0;
 }
