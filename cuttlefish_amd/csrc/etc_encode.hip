@@ -1353,6 +1353,7 @@ __device__ __forceinline__ uint2 eac_search(const uint32_t* tp, uint32_t* pre, i
 __device__ __forceinline__ uint32_t r11_word(float f, bool snorm)
 {
 	int v;
+	f = f != f ? 0.0f : f;   // NaN -> 0 before the clamp (oracle: cfo_encode_etc_block), whatever the conversion would make of it
 	if (snorm) {
 		f = f < -1.0f ? -1.0f : (f > 1.0f ? 1.0f : f);
 		v = (int)roundf(f*1023.0f);

@@ -1324,6 +1324,8 @@ int cfo_encode_etc_block(const float rgbaf[64], const uint8_t rgba[64], unsigned
 				int v[16];
 				for (int i = 0; i < 16; ++i) {
 					float f = rgbaf[4*i + ch];
+					if (f != f)
+						f = 0.0f;   /* NaN -> 0 before the clamp, like the colour loader (an int cast of NaN is undefined) */
 					if (p->type == CFO_TYPE_SNORM) {
 						f = f < -1.0f ? -1.0f : (f > 1.0f ? 1.0f : f);
 						v[i] = (int)roundf(f*1023.0f);

@@ -13,6 +13,7 @@ pytestmark = pytest.mark.gpu
 
 
 @pytest.mark.parametrize("fmt,cases", [("BC7", 60), ("BC1_RGBA", 20), ("BC3", 20), ("ETC2_R8G8B8A8", 25),
-                                       ("ETC2_R8G8B8A1", 20), ("ASTC_6x6", 20), ("ASTC_5x4", 15), ("BC6H", 30)])
+                                       ("ETC2_R8G8B8A1", 20), ("ASTC_6x6", 20), ("ASTC_5x4", 15), ("BC6H", 30),
+                                       ("ETC1", 20), ("ETC2_R8G8B8", 20), ("EAC_R11", 20), ("EAC_R11G11", 15)])
 def test_random_surfaces_match_the_oracle(fmt, cases):
     assert fuzz_parity.run(fmt, cases, seed=len(fmt)*1000 + cases) == 0

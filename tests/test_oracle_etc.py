@@ -6,6 +6,7 @@ import pytest
 
 import oracle_lib as O
 from cuttlefish_amd import synth
+from etc_cases import etc_mode as _etc_mode
 
 ETC1, RGB, A1, A8, R11, RG11 = 37, 38, 39, 40, 41, 42
 
@@ -110,24 +111,6 @@ def test_partial_blocks_ignore_out_of_image_texels():
 def test_threads_deterministic():
     img = synth.photo(64, 64, seed=2)
     assert np.array_equal(O.encode(img, A8, threads=1), O.encode(img, A8, threads=4))
-
-
-def _etc_mode(block8):
-    """0 individual/differential, 1 T, 2 H, 3 planar -- from the overflow rules of the ETC2 spec."""
-    hi = int.from_bytes(bytes(block8[:4]), "big")
-    if not (hi >> 1) & 1:
-        return 0
-    sx = lambda v: v - 8 if v >= 4 else v
-    r, dr = (hi >> 27) & 31, sx((hi >> 24) & 7)
-    g, dg = (hi >> 19) & 31, sx((hi >> 16) & 7)
-    b, db = (hi >> 11) & 31, sx((hi >> 8) & 7)
-    if not 0 <= r + dr <= 31:
-        return 1
-    if not 0 <= g + dg <= 31:
-        return 2
-    if not 0 <= b + db <= 31:
-        return 3
-    return 0
 
 
 def test_two_colour_blocks_use_t_or_h_mode_and_etc1_never_does():

@@ -101,6 +101,11 @@ def run(format_name, cases, seed, verbose=True):
             elif fmt in (Format.BC4, Format.BC5, Format.EAC_R11, Format.EAC_R11G11) and rng.integers(0, 2):
                 typ = Type.SNorm
                 cs = 0
+            if fmt in (Format.EAC_R11, Format.EAC_R11G11) and rng.integers(0, 2):
+                # a float32 source over -1.2 .. 1.2 (both clamps), noise within a byte step: all 2048 levels occur,
+                # where the byte image holds 256 of them.  (Draws only the EAC formats make: the other streams stay.)
+                f = img.astype(np.float32)/255.0*2.4 - 1.2
+                img = np.ascontiguousarray((f + rng.uniform(-0.5, 0.5, f.shape)*(2.4/255.0)).astype(np.float32))
             ref = O.encode(img, int(fmt), int(typ), quality=q, threads=16, color_space=cs, mask=mask)
             got = ctx.encode([img], make_params(fmt, typ, q, color_space=ColorSpace(cs),
                                                 color_mask=tuple(bool(m) for m in mask)))[0]
