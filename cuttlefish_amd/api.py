@@ -200,7 +200,9 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_deflate_bound", "cfhip_deflate", "cfhip_deflate_device", "cfhip_deflate_stage_ms",
            "cfhip_deflate_code_lengths",
            "cfhip_zindex_entries", "cfhip_deflate_indexed", "cfhip_deflate_indexed_device",
-           "cfhip_inflate", "cfhip_inflate_device", "cfhip_inflate_stage_ms"]
+           "cfhip_inflate", "cfhip_inflate_device", "cfhip_inflate_stage_ms",
+           "cfhip_lz4_bound", "cfhip_lz4_encode", "cfhip_lz4_encode_device", "cfhip_lz4_encode_stage_ms",
+           "cfhip_lz4_decode", "cfhip_lz4_decode_device", "cfhip_lz4_decode_stage_ms"]
 
 
 class Layout(enum.IntEnum):
@@ -402,6 +404,37 @@ def zindex_entries(n: int) -> int:
     return int(load_library().cfhip_zindex_entries(int(n)))
 
 
+class Lz4Result(ctypes.Structure):
+    """struct cfhip_lz4_result"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("bytes_in", "bytes_out", "blocks_compressed", "blocks_stored", "sequences",
+                                               "literals", "matched_bytes")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+class Lz4DecodeResult(ctypes.Structure):
+    """struct cfhip_lz4_decode_result"""
+    _fields_ = Lz4Result._fields_ + [(n, ctypes.c_uint32) for n in ("status", "bad_block", "content_checksum", "reserved")]
+
+    def as_dict(self) -> dict:
+        return {n: int(getattr(self, n)) for n, _ in self._fields_}
+
+
+LZ4_ENCODE_STAGES = ("keys", "sort", "match", "parse", "plan", "offsets", "emit", "hash", "final")   # cfhip_lz4_encode_stage_ms
+LZ4_DECODE_STAGES = ("chain", "blocks", "final")                                                     # cfhip_lz4_decode_stage_ms
+# enum cfhip_lz4_status
+LZ4_CLASSES = ("ok", "header", "unsupported", "blocks", "checksum", "sequence", "offset", "size")
+LZ4_UNSUPPORTED = 2             # a valid frame this decoder does not take: decode it on the host
+LZ4_BLOCK = 65536               # input bytes per block
+LZ4_MAGIC = b"\x04\x22\x4D\x18"
+
+
+def lz4_bound(n: int) -> int:
+    """cfhip_lz4_bound: bytes that hold the LZ4 frame of any n input bytes (no device needed)"""
+    return int(load_library().cfhip_lz4_bound(int(n)))
+
+
 RDO_NO_CAP = 0xFFFFFFFF         # max_sse_increase: no cap
 RDO_ROW_ABOVE = 1               # CFHIP_RDO_ROW_ABOVE
 
@@ -439,6 +472,7 @@ class CfhipError(RuntimeError):
         super().__init__("cfhip error %d: %s" % (code, text))
         self.code = code
         self.status, self.bad_chunk = status, bad_chunk     # E_DATA: the error class and the lowest failing chunk
+        self.bad_block = bad_chunk                          # ... which cfhip_lz4_decode calls a block
 
 
 _lib = None
@@ -654,6 +688,23 @@ def load_library(path: Optional[str] = None):
     L.cfhip_inflate_device.restype = ctypes.c_int
     L.cfhip_inflate_stage_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
     L.cfhip_inflate_stage_ms.restype = ctypes.c_int
+    L.cfhip_lz4_bound.argtypes = [ctypes.c_size_t]
+    L.cfhip_lz4_bound.restype = ctypes.c_size_t
+    L.cfhip_lz4_encode.argtypes = [ctypes.c_void_p, ctypes.POINTER(LzSpan), ctypes.c_size_t, ctypes.c_void_p,
+                                   ctypes.c_size_t, ctypes.c_void_p]
+    L.cfhip_lz4_encode.restype = ctypes.c_int
+    L.cfhip_lz4_encode_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(LzSpan), ctypes.c_size_t, ctypes.c_void_p,
+                                          ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_lz4_encode_device.restype = ctypes.c_int
+    L.cfhip_lz4_decode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                   ctypes.c_void_p]
+    L.cfhip_lz4_decode.restype = ctypes.c_int
+    L.cfhip_lz4_decode_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                          ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_lz4_decode_device.restype = ctypes.c_int
+    for f in (L.cfhip_lz4_encode_stage_ms, L.cfhip_lz4_decode_stage_ms):
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t]
+        f.restype = ctypes.c_int
     L.cfhip_rdo_target.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RdoSurface),
                                    ctypes.c_size_t, ctypes.POINTER(RdoExParams), ctypes.POINTER(ctypes.c_uint8),
                                    ctypes.c_void_p, ctypes.c_float, ctypes.POINTER(RdoTargetResult)]
@@ -1404,6 +1455,83 @@ class Context:
         ms = (ctypes.c_float*len(INFLATE_STAGES))()
         self._check(self._lib.cfhip_inflate_stage_ms(self._h, ms))
         return dict(zip(INFLATE_STAGES, (float(v) for v in ms)))
+
+    def lz4_encode(self, payloads) -> bytes:
+        """The LZ4 frame (cfhip_lz4_encode) of a byte stream: one array / bytes object, or a sequence of them taken as
+        their concatenation.  The lz4 tool and LZ4F_decompress invert it, and so does lz4_decode; the bytes are those of
+        tests/lz4_ref.py, exactly.  lz4_encode_result() returns the call's cfhip_lz4_result."""
+        if isinstance(payloads, (bytes, bytearray, np.ndarray)):
+            payloads = [payloads]
+        parts = [np.frombuffer(bytes(p), np.uint8) if isinstance(p, (bytes, bytearray))
+                 else np.ascontiguousarray(p).reshape(-1).view(np.uint8) for p in payloads]
+        spans = (LzSpan*max(len(parts), 1))()
+        for i, p in enumerate(parts):
+            spans[i].bytes, spans[i].n = (p.ctypes.data if p.size else None), p.size
+        cap = lz4_bound(sum(p.size for p in parts))
+        out = np.empty(cap, np.uint8)
+        res = Lz4Result()
+        self._check(self._lib.cfhip_lz4_encode(self._h, spans, len(parts), out.ctypes.data, cap, ctypes.addressof(res)))
+        self._lz4_encode_result = res.as_dict()
+        return out[:res.bytes_out].tobytes()
+
+    def lz4_encode_result(self) -> Optional[dict]:
+        """The cfhip_lz4_result of the last lz4_encode() on this context; None before the first one."""
+        return getattr(self, "_lz4_encode_result", None)
+
+    def lz4_encode_device(self, spans: Sequence[tuple], out: int, cap: int, result: int, stream: int = 0):
+        """Device path of lz4_encode.  spans: (device pointer as int, bytes) pairs; out: device pointer to cap bytes;
+        result: device pointer to one cfhip_lz4_result (overwritten), 8-byte aligned.  stream 0 = the context's stream
+        (the call then synchronises)."""
+        arr = (LzSpan*max(len(spans), 1))()
+        for i, (ptr, n) in enumerate(spans):
+            arr[i].bytes, arr[i].n = int(ptr) or None, int(n)
+        self._check(self._lib.cfhip_lz4_encode_device(
+            self._h, arr, len(spans), ctypes.c_void_p(int(out)) if out else None, int(cap),
+            ctypes.c_void_p(int(result)) if result else None, ctypes.c_void_p(stream) if stream else None))
+
+    def lz4_encode_stage_ms(self) -> dict:
+        """Kernel ms of the last lz4_encode's stages: keys, sort, match, parse, plan, offsets, emit, hash, final"""
+        ms = (ctypes.c_float*len(LZ4_ENCODE_STAGES))()
+        self._check(self._lib.cfhip_lz4_encode_stage_ms(self._h, ms, len(LZ4_ENCODE_STAGES)))
+        return dict(zip(LZ4_ENCODE_STAGES, (float(v) for v in ms)))
+
+    def lz4_decode(self, frame, n: int) -> bytes:
+        """The n bytes of one LZ4 frame (cfhip_lz4_decode): anyone's frame with independent blocks of at most 64 KiB.  A
+        frame that is invalid, or valid but outside that (status LZ4_UNSUPPORTED: decode it on the host), raises
+        CfhipError with code E_DATA, the class in .status and the lowest failing block in .bad_block.  A content
+        checksum is not verified (lz4_decode_result()["content_checksum"] says whether one was there).
+        lz4_decode_result() returns the call's result either way."""
+        z = np.frombuffer(bytes(frame), np.uint8)
+        out = np.empty(int(n), np.uint8)
+        res = Lz4DecodeResult()
+        zbuf = z if z.size else np.zeros(1, np.uint8)         # (an empty frame still passes a pointer)
+        rc = self._lib.cfhip_lz4_decode(self._h, zbuf.ctypes.data, z.size, out.ctypes.data if out.size else None, out.size,
+                                        ctypes.addressof(res))
+        if rc == E_DATA:
+            self._lz4_decode_result = res.as_dict()
+            raise CfhipError(rc, self._lib.cfhip_last_error(self._h).decode(), res.status, res.bad_block)
+        self._check(rc)
+        self._lz4_decode_result = res.as_dict()
+        return out.tobytes()
+
+    def lz4_decode_result(self) -> Optional[dict]:
+        """The cfhip_lz4_decode_result of the last lz4_decode() on this context; None before the first one."""
+        return getattr(self, "_lz4_decode_result", None)
+
+    def lz4_decode_device(self, frame: int, nbytes: int, out: int, out_bytes: int, result: int, stream: int = 0):
+        """Device path of lz4_decode.  frame, out (4-byte aligned) and result (one cfhip_lz4_decode_result, 8-byte
+        aligned) are device pointers.  An invalid frame is reported through the result's status, not raised.  stream 0 =
+        the context's stream (the call then synchronises)."""
+        def ptr(v):
+            return ctypes.c_void_p(int(v)) if v else None
+        self._check(self._lib.cfhip_lz4_decode_device(self._h, ptr(frame), int(nbytes), ptr(out), int(out_bytes),
+                                                      ptr(result), ptr(stream)))
+
+    def lz4_decode_stage_ms(self) -> dict:
+        """Kernel ms of the last lz4_decode's stages: chain, blocks, final"""
+        ms = (ctypes.c_float*len(LZ4_DECODE_STAGES))()
+        self._check(self._lib.cfhip_lz4_decode_stage_ms(self._h, ms, len(LZ4_DECODE_STAGES)))
+        return dict(zip(LZ4_DECODE_STAGES, (float(v) for v in ms)))
 
     def rdo_target(self, payloads: Sequence[np.ndarray], sources: Sequence[np.ndarray], fmt, typ=Type.UNorm,
                    target_ratio: float = 0.85, lam: float = 32.0, max_sse_increase: Optional[int] = None, mask=None,

@@ -154,7 +154,11 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  "cfhip_deflate_final_kernel",
                  # indexed zlib streams back to bytes (csrc/inflate.hip), and the encoder's index
                  "cfhip_inflate_decode_kernel", "cfhip_inflate_resolve_kernel", "cfhip_inflate_pack_kernel",
-                 "cfhip_inflate_fold_kernel", "cfhip_inflate_final_kernel", "cfhip_zindex_kernel")
+                 "cfhip_inflate_fold_kernel", "cfhip_inflate_final_kernel", "cfhip_zindex_kernel",
+                 # LZ4 frames, both ways (csrc/lz4.hip); the encoder's match stage lives in csrc/lzsize.hip
+                 "cfhip_lz4_match_kernel", "cfhip_lz4_parse_kernel", "cfhip_lz4_plan_kernel", "cfhip_lz4_offsets_kernel",
+                 "cfhip_lz4_emit_kernel", "cfhip_lz4_hash_kernel", "cfhip_lz4_final_kernel", "cfhip_lz4_chain_kernel",
+                 "cfhip_lz4_block_kernel", "cfhip_lz4_dfinal_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

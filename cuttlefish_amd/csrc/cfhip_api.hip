@@ -14,6 +14,7 @@
 #include "lzsize.h"
 #include "deflate.h"
 #include "inflate.h"
+#include "lz4.h"
 #include "../../include/cuttlefish_hip.h"
 
 #include <cmath>
@@ -203,6 +204,7 @@ struct cfhip_ctx {
 	size_t lz_first_event = 0, lz_slices = 0;   // the last estimate's event pairs: CFLZ_STAGES per slice
 	size_t df_first_event = 0, df_slices = 0;   // the last cfhip_deflate*'s event pairs: CFDF_STAGES per slice
 	size_t inf_first_event = 0, inf_slices = 0; // the last cfhip_inflate*'s event pairs: CFINF_STAGES per slice
+	size_t l4_first_event = 0, l4_pairs = 0;    // the last cfhip_lz4_*'s event pairs (csrc/lz4.h: the stages)
 	void* d_rdo_keep = nullptr;       // cfhip_rdo_target: the pristine payloads every trial starts from
 	size_t rdo_keep_cap = 0;
 	std::map<int, void*> astc_tables; // per-format device tables (built on first use)
@@ -3941,6 +3943,373 @@ int cfhip_inflate_stage_ms(cfhip_ctx* ctx, float ms[CFINF_STAGES])
 		ms[i % CFINF_STAGES] += t;
 	}
 	return CFHIP_OK;
+}
+
+// ---- LZ4 frames, both ways (csrc/lz4.hip, csrc/lz4.h; the definition is tests/lz4_ref.py) ---------------------------
+size_t cfhip_lz4_bound(size_t n)
+{
+	return cflz4_bound(n);
+}
+
+static void lz4_begin_call(cfhip_ctx* ctx, hipStream_t stream, const char* kernel)
+{
+	lz_begin_call(ctx, stream);
+	ctx->last_kernel = kernel;
+	ctx->lz_slices = 0;                       // "cfhip_lz4" begins with the estimator's prefix: its stage times end here
+	ctx->l4_pairs = 0;
+}
+
+// Every check of an encoder call, made before the context is touched.
+static int lz4_check(cfhip_ctx* ctx, const char* what, const cfhip_lz_span* spans, size_t n, const void* out, size_t cap,
+	const void* result, bool host, LzPlan* p)
+{
+	if (!out)
+		return fail(ctx, CFHIP_E_INVALID, "%s: out is NULL", what);
+	if (!result)
+		return fail(ctx, CFHIP_E_INVALID, "%s: result is NULL", what);
+	if (!host && (uintptr_t)result % 8u != 0)
+		return fail(ctx, CFHIP_E_INVALID, "%s: result must be 8-byte aligned", what);
+	const int rc = lz_check(ctx, what, spans, n, out, true, p);
+	if (rc != CFHIP_OK)
+		return rc;
+	if (cap < cflz4_bound(p->total))
+		return fail(ctx, CFHIP_E_CAPACITY, "%s: out holds %zu bytes, cfhip_lz4_bound(%zu) = %zu", what, cap, p->total,
+			cflz4_bound(p->total));
+	return CFHIP_OK;
+}
+
+static cfhip_lz4_result lz4_empty_result()
+{
+	cfhip_lz4_result r;
+	memset(&r, 0, sizeof(r));
+	r.bytes_out = CFLZ4_HEADER + 4u;
+	return r;
+}
+
+static void lz4_empty_frame(uint8_t out[CFLZ4_HEADER + 4u])
+{
+	cflz4_write_header(out, 0u);
+	memset(out + CFLZ4_HEADER, 0, 4u);
+}
+
+// The frame of p (total > 0) into out_device and the result into result_device, enqueued on the lease's stream: slices
+// of whole blocks without a carry (blocks are independent), the state carried on the device.
+static int lz4_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hipMemcpyKind kind, uint8_t* out_device,
+	unsigned long long* result_device)
+{
+	const hipStream_t stream = lease.stream;
+	const size_t slice = std::min(lz_slice_of(ctx), (p.total + CFLZ4_BLOCK - 1u)/CFLZ4_BLOCK*CFLZ4_BLOCK);
+	size_t sort_bytes = 0;
+	HIP_TRY(ctx, cfhip_lz_sort_bytes(slice + CFLZ_WINDOW, &sort_bytes));
+	const cflz4_layout lay = cflz4_scratch(slice, sort_bytes);
+	int rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, lay.total);
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* base = static_cast<uint8_t*>(ctx->d_lz);
+	ctx->l4_first_event = ctx->events_used;
+	ctx->l4_pairs = 0;
+	for (size_t s0 = 0; s0 < p.total; s0 += slice) {
+		const size_t s1 = std::min(p.total, s0 + slice);
+		rc = lz_gather(ctx, p, s0, s1, base + lay.lz.bytes, kind, stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		hipEvent_t ev[2*(CFLZ4_STAGES - 1)];
+		for (int k = 0; k < CFLZ4_STAGES - 1; ++k) {
+			rc = next_event_pair(ctx, &ev[2*k], &ev[2*k + 1]);
+			if (rc != CFHIP_OK)
+				return rc;
+		}
+		const hipError_t e = cfhip_launch_lz4_slice(base, &lay, sort_bytes, (uint32_t)(s1 - s0), s0 == 0, out_device, ev, stream);
+		if (e != hipSuccess)
+			return fail(ctx, CFHIP_E_DEVICE, "lz4_encode launch: %s", hipGetErrorString(e));
+		ctx->l4_pairs += CFLZ4_STAGES - 1;
+	}
+	hipEvent_t ev[2];
+	rc = next_event_pair(ctx, &ev[0], &ev[1]);
+	if (rc != CFHIP_OK)
+		return rc;
+	const hipError_t e = cfhip_launch_lz4_final(reinterpret_cast<const unsigned long long*>(base + lay.state),
+		(unsigned long long)p.total, out_device, result_device, ev, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "lz4_encode launch: %s", hipGetErrorString(e));
+	ctx->l4_pairs += 1;
+	return CFHIP_OK;
+}
+
+int cfhip_lz4_encode(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out, size_t cap,
+	cfhip_lz4_result* result)
+{
+	static_assert(sizeof(cfhip_lz4_result) == 7*sizeof(unsigned long long), "the final kernel's words are the struct");
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		LzPlan p;
+		int rc = lz4_check(ctx, "lz4_encode", spans, n_spans, out, cap, result, true, &p);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!p.total) {
+			lz4_empty_frame(static_cast<uint8_t*>(out));
+			*result = lz4_empty_result();
+			return CFHIP_OK;
+		}
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		lz4_begin_call(ctx, lease.stream, "cfhip_lz4_emit_kernel");
+		// the result lies behind the frame's bytes, 256-byte aligned
+		const size_t res_off = (cflz4_bound(p.total) + 255u)/256u*256u;
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, res_off + 256u);
+		if (rc != CFHIP_OK)
+			return rc;
+		uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out);
+		unsigned long long* d_res = reinterpret_cast<unsigned long long*>(d_out + res_off);
+		rc = lz4_run(ctx, lease, p, hipMemcpyHostToDevice, d_out, d_res);
+		if (rc != CFHIP_OK)
+			return rc;
+		cfhip_lz4_result res;
+		HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
+		HIP_TRY(ctx, hipStreamSynchronize(lease.stream));
+		if (res.bytes_out > cflz4_bound(p.total))
+			return fail(ctx, CFHIP_E_DEVICE, "lz4_encode: %llu bytes exceed the bound", (unsigned long long)res.bytes_out);
+		HIP_TRY(ctx, hipMemcpyAsync(out, d_out, (size_t)res.bytes_out, hipMemcpyDeviceToHost, lease.stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		*result = res;
+		return CFHIP_OK;
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "lz4_encode: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "lz4_encode: unknown exception");
+	}
+}
+
+int cfhip_lz4_encode_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out_device, size_t cap,
+	cfhip_lz4_result* result_device, void* stream_)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		LzPlan p;
+		int rc = lz4_check(ctx, "lz4_encode_device", spans, n_spans, out_device, cap, result_device, false, &p);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		lz4_begin_call(ctx, lease.stream, "cfhip_lz4_emit_kernel");
+		if (!p.total) {
+			// both sources are static: the copies may outlive the call
+			static const cfhip_lz4_result empty = lz4_empty_result();
+			static const struct Frame { uint8_t b[CFLZ4_HEADER + 4u]; Frame() { lz4_empty_frame(b); } } frame;
+			HIP_TRY(ctx, hipMemcpyAsync(out_device, frame.b, sizeof(frame.b), hipMemcpyHostToDevice, lease.stream));
+			HIP_TRY(ctx, hipMemcpyAsync(result_device, &empty, sizeof(empty), hipMemcpyHostToDevice, lease.stream));
+		} else {
+			rc = lease.acquire();
+			if (rc == CFHIP_OK)
+				rc = lz4_run(ctx, lease, p, hipMemcpyDeviceToDevice, static_cast<uint8_t*>(out_device),
+					reinterpret_cast<unsigned long long*>(result_device));
+			if (rc != CFHIP_OK)
+				return rc;
+		}
+		return lease.done(!stream_);
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "lz4_encode_device: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "lz4_encode_device: unknown exception");
+	}
+}
+
+// The event pairs [first, first + pairs) of the last call summed into ms[0 .. n) by stage: a slice's `per_slice` stages
+// repeat, the rest follow once.
+static int lz4_stage_ms(cfhip_ctx* ctx, const char* what, const char* prefix, size_t per_slice, size_t stages, float* ms, size_t n)
+{
+	if (!ctx || !ms || n > stages)
+		return CFHIP_E_INVALID;
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	const size_t first = ctx->l4_first_event, pairs = ctx->l4_pairs;
+	if (!pairs || first + 2*pairs > ctx->events_used || ctx->last_kernel.compare(0, strlen(prefix), prefix) != 0)
+		return fail(ctx, CFHIP_E_INVALID, "%s: the last call on this context was no %s*", what, what);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->events_stream));
+	std::vector<float> sum(stages, 0.0f);
+	const size_t tail = stages - per_slice;                  // pairs = slices x per_slice + tail
+	for (size_t i = 0; i < pairs; ++i) {
+		float t = 0.0f;
+		HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->events[first + 2*i], ctx->events[first + 2*i + 1]));
+		sum[i < pairs - tail ? i % per_slice : per_slice + (i - (pairs - tail))] += t;
+	}
+	for (size_t k = 0; k < n; ++k)
+		ms[k] = sum[k];
+	return CFHIP_OK;
+}
+
+int cfhip_lz4_encode_stage_ms(cfhip_ctx* ctx, float* ms, size_t n)
+{
+	return lz4_stage_ms(ctx, "cfhip_lz4_encode", "cfhip_lz4_emit", CFLZ4_STAGES - 1, CFLZ4_STAGES, ms, n);
+}
+
+static const char* const kLz4Class[8] = {"no", "header", "unsupported", "blocks", "checksum", "sequence", "offset", "size"};
+
+// Every check of a decoder call, made before the context is touched.
+static int lz4d_check(cfhip_ctx* ctx, const char* what, const void* frame, size_t bytes, const void* out, size_t out_bytes,
+	const void* result, bool host)
+{
+	if (!frame)
+		return fail(ctx, CFHIP_E_INVALID, "%s: frame is NULL", what);
+	if (!result)
+		return fail(ctx, CFHIP_E_INVALID, "%s: result is NULL", what);
+	if (out_bytes && !out)
+		return fail(ctx, CFHIP_E_INVALID, "%s: out is NULL", what);
+	if (out_bytes >= ((size_t)1 << 31) || bytes > ((size_t)1 << 32))
+		return fail(ctx, CFHIP_E_CAPACITY, "%s: 2^31 output bytes or more, or a frame above 2^32 bytes", what);
+	if (!host && ((uintptr_t)out % 4u != 0 || (uintptr_t)result % 8u != 0))
+		return fail(ctx, CFHIP_E_INVALID, "%s: out must be 4-byte and result 8-byte aligned", what);
+	return CFHIP_OK;
+}
+
+static int lz4d_run(cfhip_ctx* ctx, StagingLease& lease, const uint8_t* z_device, size_t bytes, uint8_t* out_device,
+	size_t out_bytes, unsigned long long* result_device)
+{
+	const cflz4_dlayout lay = cflz4_dscratch((out_bytes + CFLZ4_BLOCK - 1u)/CFLZ4_BLOCK);
+	int rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, lay.total);
+	if (rc != CFHIP_OK)
+		return rc;
+	ctx->l4_first_event = ctx->events_used;
+	ctx->l4_pairs = 0;
+	hipEvent_t ev[2*CFLZ4_DSTAGES];
+	for (int k = 0; k < CFLZ4_DSTAGES; ++k) {
+		rc = next_event_pair(ctx, &ev[2*k], &ev[2*k + 1]);
+		if (rc != CFHIP_OK)
+			return rc;
+	}
+	const hipError_t e = cfhip_launch_lz4_decode(static_cast<uint8_t*>(ctx->d_lz), &lay, z_device, bytes, out_device, out_bytes,
+		result_device, ev, lease.stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "lz4_decode launch: %s", hipGetErrorString(e));
+	ctx->l4_pairs = CFLZ4_DSTAGES;
+	return CFHIP_OK;
+}
+
+// A frame of no output bytes on the host: the header and the frame's end -- the kernels' routines (lz4.h).
+static void lz4d_empty(const uint8_t* z, size_t bytes, cfhip_lz4_decode_result* r)
+{
+	memset(r, 0, sizeof(*r));
+	r->bytes_in = bytes;
+	cflz4_header h;
+	r->status = cflz4_parse_header(z, bytes, 0u, &h);
+	if (r->status == CFLZ4_OK) {
+		r->content_checksum = h.content_checksum;
+		r->status = cflz4_frame_end(z, bytes, h.content_checksum, h.length);
+	}
+}
+
+static int lz4d_verdict(cfhip_ctx* ctx, const cfhip_lz4_decode_result& r)
+{
+	if (r.status == CFLZ4_OK)
+		return CFHIP_OK;
+	return fail(ctx, CFHIP_E_DATA, "lz4_decode: %s error in block %u", kLz4Class[r.status & 7u], r.bad_block);
+}
+
+int cfhip_lz4_decode(cfhip_ctx* ctx, const void* frame, size_t bytes, void* out, size_t out_bytes,
+	cfhip_lz4_decode_result* result)
+{
+	static_assert(sizeof(cfhip_lz4_decode_result) == 9*sizeof(unsigned long long), "the final kernel's words are the struct");
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		int rc = lz4d_check(ctx, "lz4_decode", frame, bytes, out, out_bytes, result, true);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!out_bytes) {
+			lz4d_empty(static_cast<const uint8_t*>(frame), bytes, result);
+			return lz4d_verdict(ctx, *result);
+		}
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		lz4_begin_call(ctx, lease.stream, "cfhip_lz4_block_kernel");
+		const size_t res_off = (out_bytes + 255u)/256u*256u;
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, std::max(bytes, (size_t)1));
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, res_off + 256u);
+		if (rc != CFHIP_OK)
+			return rc;
+		uint8_t* d_z = static_cast<uint8_t*>(ctx->d_src);
+		uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out);
+		unsigned long long* d_res = reinterpret_cast<unsigned long long*>(d_out + res_off);
+		if (bytes)
+			HIP_TRY(ctx, hipMemcpyAsync(d_z, frame, bytes, hipMemcpyHostToDevice, lease.stream));
+		rc = lz4d_run(ctx, lease, d_z, bytes, d_out, out_bytes, d_res);
+		if (rc != CFHIP_OK)
+			return rc;
+		cfhip_lz4_decode_result res;
+		HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
+		HIP_TRY(ctx, hipStreamSynchronize(lease.stream));
+		if (res.status == CFLZ4_OK)
+			HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, lease.stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		*result = res;
+		return lz4d_verdict(ctx, res);
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "lz4_decode: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "lz4_decode: unknown exception");
+	}
+}
+
+int cfhip_lz4_decode_device(cfhip_ctx* ctx, const void* frame_device, size_t bytes, void* out_device, size_t out_bytes,
+	cfhip_lz4_decode_result* result_device, void* stream_)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		int rc = lz4d_check(ctx, "lz4_decode_device", frame_device, bytes, out_device, out_bytes, result_device, false);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		lz4_begin_call(ctx, lease.stream, "cfhip_lz4_block_kernel");
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = lz4d_run(ctx, lease, static_cast<const uint8_t*>(frame_device), bytes, static_cast<uint8_t*>(out_device),
+				out_bytes, reinterpret_cast<unsigned long long*>(result_device));
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "lz4_decode_device: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "lz4_decode_device: unknown exception");
+	}
+}
+
+int cfhip_lz4_decode_stage_ms(cfhip_ctx* ctx, float* ms, size_t n)
+{
+	return lz4_stage_ms(ctx, "cfhip_lz4_decode", "cfhip_lz4_block", CFLZ4_DSTAGES, CFLZ4_DSTAGES, ms, n);
 }
 
 // cfhip_rdo_target and cfhip_rdo_target_device

@@ -106,6 +106,11 @@ extern "C" hipError_t cfhip_launch_lz_slice(uint8_t* base, const cflz_layout* la
 extern "C" hipError_t cfhip_launch_lz_matches(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t carry,
 	uint32_t n, hipEvent_t* ev, hipStream_t stream);
 
+// The same three stages on n bytes without a carry, cut into blocks of CFLZ_COSTBLK bytes that are matched as streams
+// of their own: no match reaches in front of its position's block.  csrc/lz4.hip builds on it.
+extern "C" hipError_t cfhip_launch_lz_block_matches(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t n,
+	hipEvent_t* ev, hipStream_t stream);
+
 // out[0..5] = bytes_in, bits_q16, est_bytes, literals, matches, matched_bytes from the four sums.
 extern "C" hipError_t cfhip_launch_lz_final(const unsigned long long* acc, unsigned long long bytes_in,
 	unsigned long long* out, hipStream_t stream);

@@ -45,9 +45,11 @@ __global__ __launch_bounds__(256) void cfhip_lz_keys_kernel(const uint8_t* __res
 }
 
 // pairs = M - 3 sorted entries.  Entry i at position p >= carry (a target) looks at the entries before it.
-__global__ __launch_bounds__(256) void cfhip_lz_match_kernel(const uint8_t* __restrict__ bytes,
-	const uint32_t* __restrict__ keys, const uint32_t* __restrict__ pos, uint32_t pairs, uint32_t carry, uint32_t n,
-	uint32_t* __restrict__ ld)
+// BLOCKS (csrc/lz4.hip, carry 0): the stream is cut into blocks of CFLZ_COSTBLK bytes that are matched as streams of
+// their own -- a candidate in front of p's block ends the walk, as one outside the window does.
+template <bool BLOCKS>
+__device__ __forceinline__ void lz_match(const uint8_t* __restrict__ bytes, const uint32_t* __restrict__ keys,
+	const uint32_t* __restrict__ pos, uint32_t pairs, uint32_t carry, uint32_t n, uint32_t* __restrict__ ld)
 {
 	const uint32_t i = blockIdx.x*256u + threadIdx.x;
 	if (i >= pairs)
@@ -67,6 +69,8 @@ __global__ __launch_bounds__(256) void cfhip_lz_match_kernel(const uint8_t* __re
 			break;
 		const uint32_t q = pos[i - j];                   // q < p: the sort is stable
 		if (p - q > CFLZ_WINDOW)
+			break;
+		if (BLOCKS && q < (p & ~(CFLZ_COSTBLK - 1u)))
 			break;
 		const uint8_t* a = bytes + p;
 		const uint8_t* b = bytes + q;
@@ -91,6 +95,21 @@ __global__ __launch_bounds__(256) void cfhip_lz_match_kernel(const uint8_t* __re
 			break;
 	}
 	ld[t] = best ? (best | ((dist - 1u) << 16)) : 0u;
+}
+
+__global__ __launch_bounds__(256) void cfhip_lz_match_kernel(const uint8_t* __restrict__ bytes,
+	const uint32_t* __restrict__ keys, const uint32_t* __restrict__ pos, uint32_t pairs, uint32_t carry, uint32_t n,
+	uint32_t* __restrict__ ld)
+{
+	lz_match<false>(bytes, keys, pos, pairs, carry, n, ld);
+}
+
+// The match stage of the LZ4 encoder: every candidate inside the position's own block.
+__global__ __launch_bounds__(256) void cfhip_lz4_match_kernel(const uint8_t* __restrict__ bytes,
+	const uint32_t* __restrict__ keys, const uint32_t* __restrict__ pos, uint32_t pairs, uint32_t carry, uint32_t n,
+	uint32_t* __restrict__ ld)
+{
+	lz_match<true>(bytes, keys, pos, pairs, carry, n, ld);
 }
 
 #define LZ_TAKEN CFLZ_TAKEN
@@ -272,8 +291,8 @@ extern "C" hipError_t cfhip_lz_sort_bytes(size_t m, size_t* bytes)
 		if (ev && (e = hipEventRecord(ev[2*(k) + 1], stream)) != hipSuccess) return e; \
 	} while (0)
 
-extern "C" hipError_t cfhip_launch_lz_matches(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t carry,
-	uint32_t n, hipEvent_t* ev, hipStream_t stream)
+static hipError_t lz_launch_matches(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t carry,
+	uint32_t n, bool blocks, hipEvent_t* ev, hipStream_t stream)
 {
 	const uint32_t m = carry + n;
 	const uint32_t pairs = m >= 4u ? m - 3u : 0u;
@@ -302,11 +321,26 @@ extern "C" hipError_t cfhip_launch_lz_matches(uint8_t* base, const cflz_layout* 
 		}
 	});
 	LZ_STAGE(2, {
-		if (pairs)
+		if (pairs && blocks)
+			hipLaunchKernelGGL(cfhip_lz4_match_kernel, dim3((pairs + 255u)/256u), dim3(256), 0, stream, bytes, keys_out,
+				pos_out, pairs, carry, n, ld);
+		else if (pairs)
 			hipLaunchKernelGGL(cfhip_lz_match_kernel, dim3((pairs + 255u)/256u), dim3(256), 0, stream, bytes, keys_out,
 				pos_out, pairs, carry, n, ld);
 	});
 	return hipSuccess;
+}
+
+extern "C" hipError_t cfhip_launch_lz_matches(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t carry,
+	uint32_t n, hipEvent_t* ev, hipStream_t stream)
+{
+	return lz_launch_matches(base, lay, sort_bytes, carry, n, false, ev, stream);
+}
+
+extern "C" hipError_t cfhip_launch_lz_block_matches(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t n,
+	hipEvent_t* ev, hipStream_t stream)
+{
+	return lz_launch_matches(base, lay, sort_bytes, 0u, n, true, ev, stream);
 }
 
 extern "C" hipError_t cfhip_launch_lz_slice(uint8_t* base, const cflz_layout* lay, size_t sort_bytes, uint32_t carry,

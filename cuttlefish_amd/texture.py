@@ -897,30 +897,46 @@ class Texture:
             return None
         return self._context().lz_size([p for _, _, _, p in self._flat()])
 
-    def pack(self, indexed: bool = False):
+    def pack(self, indexed: bool = False, codec: str = "zlib"):
         """The zlib stream (Context.deflate) of this converted texture's payloads: data() of every surface in
         packed_size()'s order as one stream, for any format; zlib.decompress returns those bytes.  Its tokens are the
         ones packed_size() prices.  indexed=True: (the same stream, its index) from Context.deflate_indexed, what
-        unpack() and Context.inflate_device read back on the GPU.  None when the texture is not converted."""
+        unpack() and Context.inflate_device read back on the GPU.  codec="lz4": one LZ4 frame (Context.lz4_encode)
+        instead, which needs no index -- unpack() and Context.lz4_decode_device read it as it is, and so does the lz4
+        tool; larger than the zlib stream (no entropy stage), worth it behind convert_rdo.  None when the texture is not
+        converted."""
+        if codec not in ("zlib", "lz4"):
+            raise ValueError("codec must be 'zlib' or 'lz4'")
+        if codec == "lz4" and indexed:
+            raise ValueError("an LZ4 frame has no index: its blocks decode on their own")
         if not self._textures:
             return None
         ctx = self._context()
         payloads = [p for _, _, _, p in self._flat()]
+        if codec == "lz4":
+            out = ctx.lz4_encode(payloads)
+            self._pack_result = ctx.lz4_encode_result()
+            return out
         out = ctx.deflate_indexed(payloads) if indexed else ctx.deflate(payloads)
         self._pack_result = ctx.deflate_result()
         return out
 
     @staticmethod
-    def unpack(like: "Texture", stream, index) -> Optional["Texture"]:
+    def unpack(like: "Texture", stream, index=None) -> Optional["Texture"]:
         """pack(indexed=True) undone on the GPU (Context.inflate): a converted texture with `like`'s layout, format,
         type, alpha type, colour mask and colour space whose surfaces are the inflated bytes -- one buffer, the
-        surfaces views of it in storage order, as load() builds them.  None when `like` is not converted, and where
-        the stream with its index does not inflate to exactly the bytes of like's payloads."""
+        surfaces views of it in storage order, as load() builds them.  With no index, a stream that begins with the LZ4
+        magic is pack(codec="lz4")'s, or anyone's LZ4 frame of independent 64 KiB blocks, and goes through
+        Context.lz4_decode.  None when `like` is not converted, and where the stream does not decode to exactly the
+        bytes of like's payloads."""
         if not like._textures:
             return None
         sizes = [int(p.nbytes) for _, _, _, p in like._flat()]
         try:
-            raw = like._context().inflate(stream, index, sum(sizes))
+            if index is None and bytes(stream[:4]) == api.LZ4_MAGIC:
+                raw = like._context().lz4_decode(stream, sum(sizes))
+            else:
+                raw = like._context().inflate(stream, [] if index is None else index, sum(sizes))
         except (api.CfhipError, ValueError):
             return None
         t = Texture(device_id=like._device_id)
@@ -935,7 +951,8 @@ class Texture:
         return t
 
     def pack_result(self):
-        """The cfhip_deflate_result of the last pack() as a dict; None before the first one."""
+        """The cfhip_deflate_result (codec="lz4": the cfhip_lz4_result) of the last pack() as a dict; None before the
+        first one."""
         return getattr(self, "_pack_result", None)
 
     def convert_and_compare(self, format: Format, type: Type, quality: Quality = Quality.Normal,

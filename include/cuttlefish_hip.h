@@ -817,6 +817,84 @@ int cfhip_inflate_device(cfhip_ctx* ctx, const void* zstream_device, size_t zbyt
  * summed over its slices (ms); CFHIP_E_INVALID unless that call was a cfhip_inflate*.  Synchronises. */
 int cfhip_inflate_stage_ms(cfhip_ctx* ctx, float ms[4]);
 
+/* ---- LZ4 frames of payloads, both ways (csrc/lz4.hip, csrc/lz4.h) ----
+ * The fast-to-load companion of the rate-distortion pass, not a replacement for cfhip_deflate: LZ4 has no entropy
+ * stage, so plain payloads barely shrink and payloads after cfhip_rdo* do (DESIGN.md section 4.18 has the figures).
+ * The stream (the spans of a call, concatenated; fewer than 2^31 bytes) becomes ONE LZ4 frame (LZ4 Frame Format 1.6)
+ * that the lz4 tool and liblz4's LZ4F_decompress read: version 01, independent blocks of 64 KiB, block checksums,
+ * content size, no content checksum, no dictionary id.  The tokens of a block are cfhip_lz_size's on that block
+ * taken as a stream of its own; adjacent matches of one distance are merged, the block format's end rules applied,
+ * and a block that does not shrink is stored raw.  The definition, byte for byte, is tests/lz4_ref.py; identical
+ * calls return identical bytes, whatever the slice (cfhip_lz_slice_bytes).  Scratch belongs to the context: about 27
+ * bytes per byte of a slice. */
+typedef struct cfhip_lz4_result {
+	uint64_t bytes_in, bytes_out;                  /* bytes of the stream, bytes of the frame */
+	uint64_t blocks_compressed, blocks_stored;
+	uint64_t sequences, literals, matched_bytes;   /* over the compressed blocks; each block's last, literal-only
+	                                                  sequence is counted */
+} cfhip_lz4_result;
+
+/* Bytes that hold the frame of any n input bytes: 19 + n + 8 per started block of 65536.  Needs no device. */
+size_t cfhip_lz4_bound(size_t n);
+
+/* The argument rules of cfhip_deflate: cap < cfhip_lz4_bound(bytes of the stream) is CFHIP_E_CAPACITY, 2^31 bytes or
+ * more too; a stream of 0 bytes is CFHIP_OK with the 19-byte frame of an empty input and needs no context; every
+ * argument is checked before anything is enqueued (a NULL ctx is reported last).  Blocking. */
+int cfhip_lz4_encode(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out, size_t cap,
+	cfhip_lz4_result* result);
+
+/* Device spans; out_device: `cap` bytes on the device, overwritten up to cfhip_lz4_bound; result_device: one
+ * cfhip_lz4_result on the device, 8-byte aligned.  The stream rules of cfhip_compare_device. */
+int cfhip_lz4_encode_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out_device, size_t cap,
+	cfhip_lz4_result* result_device, void* stream);
+
+/* Diagnostic: kernel time of the first n <= 9 stages (keys, sort, match, parse, plan, offsets, emit, hash, final) of the
+ * most recent call on this context, summed over its slices (ms); CFHIP_E_INVALID unless that call was a
+ * cfhip_lz4_encode*.  Synchronises. */
+int cfhip_lz4_encode_stage_ms(cfhip_ctx* ctx, float* ms, size_t n);
+
+/* The classes of cfhip_lz4_decode_result.status.  Which defect yields which class, and in what order a block notices
+ * them, is defined by tests/lz4_ref.py decode; the kernels return its (status, bad_block). */
+enum cfhip_lz4_status {
+	CFHIP_LZ4_OK = 0,
+	CFHIP_LZ4_HEADER = 1,        /* magic, version, reserved bits, a block-size code below 4, HC, a frame shorter than its header */
+	CFHIP_LZ4_UNSUPPORTED = 2,   /* a valid header this decoder does not take: linked blocks, blocks above 64 KiB, a dictionary id */
+	CFHIP_LZ4_BLOCKS = 3,        /* the size chain leaves the stream, a size above 65536 or a raw size of 0, no end mark, trailing bytes */
+	CFHIP_LZ4_CHECKSUM = 4,      /* a block's XXH32 is not the one stored behind it */
+	CFHIP_LZ4_SEQUENCE = 5,      /* a literal run or a match leaves the block's input or its output; a truncated sequence */
+	CFHIP_LZ4_OFFSET = 6,        /* an offset of 0, or one that reaches before the block's first byte */
+	CFHIP_LZ4_SIZE = 7           /* the content size is not out_bytes; a block does not decode to its share of out_bytes */
+};
+
+typedef struct cfhip_lz4_decode_result {
+	uint64_t bytes_in, bytes_out;                  /* bytes of the frame; bytes written (0 unless status is 0) */
+	uint64_t blocks_compressed, blocks_stored;     /* cfhip_lz4_result's for our own frames; 0 unless status is 0 */
+	uint64_t sequences, literals, matched_bytes;
+	uint32_t status, bad_block;                    /* 0 or a class; the lowest failing block (the number of blocks: the frame's end) */
+	uint32_t content_checksum, reserved;           /* 1: the frame carries a content checksum, which was NOT verified; 0 */
+} cfhip_lz4_decode_result;
+
+/* The out_bytes bytes (the expected size; fewer than 2^31) of exactly one LZ4 frame of exactly `bytes` bytes, anyone's:
+ * version 01, independent blocks, 64 KiB maximum block size, no dictionary id; block checksums and the content size
+ * are verified where present, a content checksum may be present and is skipped (XXH32 is one serial chain over the
+ * whole output); every block but the last decodes to exactly 65536 bytes.  One wavefront decodes one block.  The frame
+ * is validated, not trusted: every length is range-checked before use, nothing outside the frame is read, nothing
+ * outside [out, out + out_bytes) is written.  Returns CFHIP_E_DATA for a frame that fails, with *result filled and the
+ * class and block in cfhip_last_error; the contents of `out` are then unspecified.  Every argument is checked before
+ * anything is enqueued (a NULL ctx is reported last); out_bytes == 0 needs no context.  Blocking. */
+int cfhip_lz4_decode(cfhip_ctx* ctx, const void* frame, size_t bytes, void* out, size_t out_bytes,
+	cfhip_lz4_decode_result* result);
+
+/* Everything on the device: out_device 4-byte aligned, result_device 8-byte aligned, frame_device any alignment.
+ * Returns CFHIP_OK once enqueued; an invalid frame is reported through result_device->status.  The stream rules of
+ * cfhip_compare_device. */
+int cfhip_lz4_decode_device(cfhip_ctx* ctx, const void* frame_device, size_t bytes, void* out_device, size_t out_bytes,
+	cfhip_lz4_decode_result* result_device, void* stream);
+
+/* Diagnostic: kernel time of the first n <= 3 stages (chain, blocks, final) of the most recent call on this context
+ * (ms); CFHIP_E_INVALID unless that call was a cfhip_lz4_decode*.  Synchronises. */
+int cfhip_lz4_decode_stage_ms(cfhip_ctx* ctx, float* ms, size_t n);
+
 /* The pass to a target: the smallest lambda whose result is estimated at no more than
  * T = floor(target_ratio * est_bytes_plain), est_bytes_plain being the estimate of the payloads as given.  The stream
  * is the surfaces' payloads concatenated in call order.  params->lambda is the largest lambda allowed:
