@@ -202,7 +202,8 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_zindex_entries", "cfhip_deflate_indexed", "cfhip_deflate_indexed_device",
            "cfhip_inflate", "cfhip_inflate_device", "cfhip_inflate_stage_ms",
            "cfhip_lz4_bound", "cfhip_lz4_encode", "cfhip_lz4_encode_device", "cfhip_lz4_encode_stage_ms",
-           "cfhip_lz4_decode", "cfhip_lz4_decode_device", "cfhip_lz4_decode_stage_ms"]
+           "cfhip_lz4_decode", "cfhip_lz4_decode_device", "cfhip_lz4_decode_stage_ms",
+           "cfhip_png_bound", "cfhip_png_encode", "cfhip_png_encode_device", "cfhip_png_stage_ms"]
 
 
 class Layout(enum.IntEnum):
@@ -433,6 +434,28 @@ LZ4_MAGIC = b"\x04\x22\x4D\x18"
 def lz4_bound(n: int) -> int:
     """cfhip_lz4_bound: bytes that hold the LZ4 frame of any n input bytes (no device needed)"""
     return int(load_library().cfhip_lz4_bound(int(n)))
+
+
+class PngResult(ctypes.Structure):
+    """struct cfhip_png_result"""
+    _fields_ = [(n, ctypes.c_uint64) for n in ("bytes_out", "idat_bytes", "filtered_bytes")] + \
+               [("rows_by_filter", ctypes.c_uint32*5), ("idat_crc32", ctypes.c_uint32), ("deflate", DeflateResult)]
+
+    def as_dict(self) -> dict:
+        return {"bytes_out": int(self.bytes_out), "idat_bytes": int(self.idat_bytes),
+                "filtered_bytes": int(self.filtered_bytes), "rows_by_filter": [int(v) for v in self.rows_by_filter],
+                "idat_crc32": int(self.idat_crc32), "deflate": self.deflate.as_dict()}
+
+
+PNG_STAGES = ("filter",) + DEFLATE_STAGES + ("crc", "final")       # cfhip_png_stage_ms
+PNG_GREY, PNG_RGB, PNG_GREY_ALPHA, PNG_RGBA = 0, 2, 4, 6           # the colour types written
+PNG_FILTERS = ("none", "sub", "up", "average", "paeth")            # cfhip_png_result.rows_by_filter
+
+
+def png_bound(width: int, height: int, color_type: int = PNG_RGBA, bit_depth: int = 8, color_space=0) -> int:
+    """cfhip_png_bound: bytes that hold the PNG file of any such image (no device needed); 0 for an image
+    cfhip_png_encode does not take"""
+    return int(load_library().cfhip_png_bound(int(width), int(height), int(color_type), int(bit_depth), int(color_space)))
 
 
 RDO_NO_CAP = 0xFFFFFFFF         # max_sse_increase: no cap
@@ -705,6 +728,16 @@ def load_library(path: Optional[str] = None):
     for f in (L.cfhip_lz4_encode_stage_ms, L.cfhip_lz4_decode_stage_ms):
         f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t]
         f.restype = ctypes.c_int
+    L.cfhip_png_bound.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.cfhip_png_bound.restype = ctypes.c_size_t
+    L.cfhip_png_encode.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_uint32,
+                                   ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                   ctypes.c_size_t, ctypes.c_void_p]
+    L.cfhip_png_encode.restype = ctypes.c_int
+    L.cfhip_png_encode_device.argtypes = L.cfhip_png_encode.argtypes + [ctypes.c_void_p]
+    L.cfhip_png_encode_device.restype = ctypes.c_int
+    L.cfhip_png_stage_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
+    L.cfhip_png_stage_ms.restype = ctypes.c_int
     L.cfhip_rdo_target.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RdoSurface),
                                    ctypes.c_size_t, ctypes.POINTER(RdoExParams), ctypes.POINTER(ctypes.c_uint8),
                                    ctypes.c_void_p, ctypes.c_float, ctypes.POINTER(RdoTargetResult)]
@@ -1532,6 +1565,51 @@ class Context:
         ms = (ctypes.c_float*len(LZ4_DECODE_STAGES))()
         self._check(self._lib.cfhip_lz4_decode_stage_ms(self._h, ms, len(LZ4_DECODE_STAGES)))
         return dict(zip(LZ4_DECODE_STAGES, (float(v) for v in ms)))
+
+    def png_encode(self, pixels: np.ndarray, color_type: int = PNG_RGBA, bit_depth: int = 8,
+                   color_space=ColorSpace.Linear) -> bytes:
+        """The PNG file (cfhip_png_encode) of an (h, w, 4) uint8 / float16 / float32 image, rows any pitch apart (a
+        view of a wider image is taken as it is): colour type 0, 2, 4 or 6 at depth 8 or 16, an sRGB chunk for
+        ColorSpace.sRGB.  Any PNG reader opens it; the bytes are those of tests/png_ref.py, exactly.  png_result()
+        returns the call's cfhip_png_result."""
+        a = np.asarray(pixels)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("expected an (h, w, 4) image, got shape %r" % (a.shape,))
+        pt = pixel_type_of(a)
+        if a.size and (a.strides[2] != a.itemsize or a.strides[1] != 4*a.itemsize or a.strides[0] < a.shape[1]*4*a.itemsize):
+            a = np.ascontiguousarray(a)
+        h, w = a.shape[:2]
+        cap = png_bound(w, h, color_type, bit_depth, color_space)
+        out = np.empty(max(cap, 1), np.uint8)
+        res = PngResult()
+        self._check(self._lib.cfhip_png_encode(self._h, a.ctypes.data if a.size else None, int(pt),
+                                               a.strides[0] if a.size else 0, w, h, int(color_type), int(bit_depth),
+                                               int(color_space), out.ctypes.data, cap, ctypes.addressof(res)))
+        self._png_result = res.as_dict()
+        return out[:res.bytes_out].tobytes()
+
+    def png_result(self) -> Optional[dict]:
+        """The cfhip_png_result of the last png_encode() on this context; None before the first one."""
+        return getattr(self, "_png_result", None)
+
+    def png_encode_device(self, pixels: int, pixel_type, pitch_bytes: int, width: int, height: int, out: int, cap: int,
+                          result: int, color_type: int = PNG_RGBA, bit_depth: int = 8, color_space=ColorSpace.Linear,
+                          stream: int = 0):
+        """Device path of png_encode.  pixels: device pointer, aligned to the texel like pitch_bytes; out: device
+        pointer to cap >= png_bound(...) bytes, any alignment; result: device pointer to one cfhip_png_result
+        (overwritten; its bytes_out says where the file ends), 8-byte aligned.  stream 0 = the context's stream (the
+        call then synchronises)."""
+        def ptr(v):
+            return ctypes.c_void_p(int(v)) if v else None
+        self._check(self._lib.cfhip_png_encode_device(self._h, ptr(pixels), int(pixel_type), int(pitch_bytes), int(width),
+                                                      int(height), int(color_type), int(bit_depth), int(color_space),
+                                                      ptr(out), int(cap), ptr(result), ptr(stream)))
+
+    def png_stage_ms(self) -> dict:
+        """Kernel ms of the last png_encode's stages: filter, the zlib encoder's eight, crc, final"""
+        ms = (ctypes.c_float*len(PNG_STAGES))()
+        self._check(self._lib.cfhip_png_stage_ms(self._h, ms))
+        return dict(zip(PNG_STAGES, (float(v) for v in ms)))
 
     def rdo_target(self, payloads: Sequence[np.ndarray], sources: Sequence[np.ndarray], fmt, typ=Type.UNorm,
                    target_ratio: float = 0.85, lam: float = 32.0, max_sse_increase: Optional[int] = None, mask=None,

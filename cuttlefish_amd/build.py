@@ -158,7 +158,9 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  # LZ4 frames, both ways (csrc/lz4.hip); the encoder's match stage lives in csrc/lzsize.hip
                  "cfhip_lz4_match_kernel", "cfhip_lz4_parse_kernel", "cfhip_lz4_plan_kernel", "cfhip_lz4_offsets_kernel",
                  "cfhip_lz4_emit_kernel", "cfhip_lz4_hash_kernel", "cfhip_lz4_final_kernel", "cfhip_lz4_chain_kernel",
-                 "cfhip_lz4_block_kernel", "cfhip_lz4_dfinal_kernel")
+                 "cfhip_lz4_block_kernel", "cfhip_lz4_dfinal_kernel",
+                 # PNG files of images (csrc/png.hip): the 24 filter kernels (source type x channels x depth), crc, final
+                 "cfhip_png_filter_kernel", "cfhip_png_crc_kernel", "cfhip_png_final_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

@@ -15,6 +15,7 @@
 #include "deflate.h"
 #include "inflate.h"
 #include "lz4.h"
+#include "png.h"
 #include "../../include/cuttlefish_hip.h"
 
 #include <cmath>
@@ -205,6 +206,9 @@ struct cfhip_ctx {
 	size_t df_first_event = 0, df_slices = 0;   // the last cfhip_deflate*'s event pairs: CFDF_STAGES per slice
 	size_t inf_first_event = 0, inf_slices = 0; // the last cfhip_inflate*'s event pairs: CFINF_STAGES per slice
 	size_t l4_first_event = 0, l4_pairs = 0;    // the last cfhip_lz4_*'s event pairs (csrc/lz4.h: the stages)
+	void* d_png = nullptr;            // cfhip_png_encode*: the filtered bytes, an unplaced zlib stream, the state (csrc/png.h)
+	size_t png_cap = 0;
+	size_t png_first_event = 0, png_pairs = 0;  // the last cfhip_png_encode*'s event pairs: filter, the encoder's, crc, final
 	void* d_rdo_keep = nullptr;       // cfhip_rdo_target: the pristine payloads every trial starts from
 	size_t rdo_keep_cap = 0;
 	std::map<int, void*> astc_tables; // per-format device tables (built on first use)
@@ -653,7 +657,7 @@ int reserve(cfhip_ctx* ctx, void** buf, size_t* cap, size_t need)
 }
 
 // The one owner of the staging buffers (d_src, d_out, d_batch, d_mip3d, and the estimator's d_lz and the target
-// search's d_rdo_keep) for one call on one stream; the only code
+// search's d_rdo_keep, the PNG writer's d_png) for one call on one stream; the only code
 // that writes staging_busy / staging_stream / staging_done.  Declared after the context's lock guard, so that it
 // ends before the lock is released.
 //  * acquire(): before the first touch of a buffer; the first call makes the stream wait for the last asynchronous
@@ -1324,6 +1328,7 @@ void cfhip_destroy(cfhip_ctx* ctx)
 	if (ctx->d_pvrtc) (void)hipFree(ctx->d_pvrtc);
 	if (ctx->d_lz) (void)hipFree(ctx->d_lz);
 	if (ctx->d_rdo_keep) (void)hipFree(ctx->d_rdo_keep);
+	if (ctx->d_png) (void)hipFree(ctx->d_png);
 	if (ctx->d_src) (void)hipFree(ctx->d_src);
 	if (ctx->d_out) (void)hipFree(ctx->d_out);
 	delete ctx;
@@ -4310,6 +4315,248 @@ int cfhip_lz4_decode_device(cfhip_ctx* ctx, const void* frame_device, size_t byt
 int cfhip_lz4_decode_stage_ms(cfhip_ctx* ctx, float* ms, size_t n)
 {
 	return lz4_stage_ms(ctx, "cfhip_lz4_decode", "cfhip_lz4_block", CFLZ4_DSTAGES, CFLZ4_DSTAGES, ms, n);
+}
+
+// ---- PNG files of images (csrc/png.hip, csrc/png.h; the definition is tests/png_ref.py) ----------------------------
+size_t cfhip_png_bound(uint32_t width, uint32_t height, int color_type, int bit_depth, int color_space)
+{
+	if (color_space != CFHIP_COLOR_LINEAR && color_space != CFHIP_COLOR_SRGB)
+		return 0;
+	const uint64_t b = cfpng_bound(width, height, color_type, bit_depth, color_space == CFHIP_COLOR_SRGB);
+	return b > (uint64_t)SIZE_MAX ? SIZE_MAX : (size_t)b;
+}
+
+struct PngPlan {
+	uint32_t bpp = 0;
+	size_t texel = 0, filtered = 0, bound = 0;
+	int srgb = 0;
+};
+
+// Every check of a call, made before the context is touched.
+static int png_check(cfhip_ctx* ctx, const char* what, const void* pixels, int pixel_type, size_t pitch, uint32_t width,
+	uint32_t height, int color_type, int bit_depth, int color_space, const void* out, size_t cap, const void* result, bool host,
+	PngPlan* p)
+{
+	if (!out)
+		return fail(ctx, CFHIP_E_INVALID, "%s: out is NULL", what);
+	if (!result)
+		return fail(ctx, CFHIP_E_INVALID, "%s: result is NULL", what);
+	if (!pixels)
+		return fail(ctx, CFHIP_E_INVALID, "%s: pixels is NULL", what);
+	if (!width || !height)
+		return fail(ctx, CFHIP_E_INVALID, "%s: empty image %ux%u", what, width, height);
+	p->texel = pixel_bytes(pixel_type);
+	if (!p->texel)
+		return fail(ctx, CFHIP_E_INVALID, "%s: pixel type %d", what, pixel_type);
+	if (color_space != CFHIP_COLOR_LINEAR && color_space != CFHIP_COLOR_SRGB)
+		return fail(ctx, CFHIP_E_INVALID, "%s: colour space %d", what, color_space);
+	if (color_type == CFPNG_PALETTE)
+		return fail(ctx, CFHIP_E_UNSUPPORTED, "%s: palette images are not written", what);
+	if (!cfpng_channels(color_type))
+		return fail(ctx, CFHIP_E_INVALID, "%s: colour type %d", what, color_type);
+	if (bit_depth == 1 || bit_depth == 2 || bit_depth == 4)
+		return fail(ctx, CFHIP_E_UNSUPPORTED, "%s: bit depth %d is not written (8 or 16)", what, bit_depth);
+	if (bit_depth != 8 && bit_depth != 16)
+		return fail(ctx, CFHIP_E_INVALID, "%s: bit depth %d", what, bit_depth);
+	if (pitch < (size_t)width*p->texel)
+		return fail(ctx, CFHIP_E_INVALID, "%s: pitch %zu < %zu", what, pitch, (size_t)width*p->texel);
+	if (!host && ((uintptr_t)pixels % p->texel || pitch % p->texel))
+		return fail(ctx, CFHIP_E_INVALID, "%s: pixels or the pitch not aligned to the texel size", what);
+	if (!host && (uintptr_t)result % 8u != 0)
+		return fail(ctx, CFHIP_E_INVALID, "%s: result must be 8-byte aligned", what);
+	p->bpp = cfpng_bpp(color_type, bit_depth);
+	p->srgb = color_space == CFHIP_COLOR_SRGB;
+	const uint64_t n = cfpng_filtered_bytes(width, height, p->bpp);
+	if (n >= ((uint64_t)1 << 31))
+		return fail(ctx, CFHIP_E_CAPACITY, "%s: 2^31 filtered bytes or more", what);
+	p->filtered = (size_t)n;
+	p->bound = (size_t)cfpng_bound(width, height, color_type, bit_depth, p->srgb);
+	if (cap < p->bound)
+		return fail(ctx, CFHIP_E_CAPACITY, "%s: out holds %zu bytes, cfhip_png_bound = %zu", what, cap, p->bound);
+	return CFHIP_OK;
+}
+
+static void png_begin_call(cfhip_ctx* ctx, hipStream_t stream)
+{
+	lz_begin_call(ctx, stream);
+	ctx->last_kernel = "cfhip_png_filter_kernel";
+	ctx->lz_slices = ctx->df_slices = 0;
+	ctx->png_pairs = 0;
+}
+
+// The file of the image at pixels_device into out_device and the result into result_device, enqueued on the lease's stream.
+static int png_run(cfhip_ctx* ctx, StagingLease& lease, const PngPlan& p, const void* pixels_device, int pixel_type, size_t pitch,
+	uint32_t width, uint32_t height, int color_type, int bit_depth, uint8_t* out_device, unsigned long long* result_device)
+{
+	static_assert(sizeof(cfhip_png_result) == 15*sizeof(unsigned long long), "the final kernel's words are the struct");
+	static_assert(offsetof(cfhip_png_result, deflate) == 48, "the final kernel's words are the struct");
+	const hipStream_t stream = lease.stream;
+	cfpng_head head;
+	cfpng_write_head(&head, width, height, color_type, bit_depth, p.srgb);
+	const size_t zbound = cfdf_bound(p.filtered);
+	if (head.bytes + zbound + CFPNG_TAIL != p.bound)
+		return fail(ctx, CFHIP_E_DEVICE, "png_encode: the bound's parts do not add up");
+	// the encoder writes whole words: in place where the IDAT data starts on one, into scratch otherwise
+	const bool in_place = ((uintptr_t)out_device + head.bytes) % 4u == 0;
+	const cfpng_layout lay = cfpng_scratch(p.filtered, in_place ? 0u : zbound);
+	int rc = reserve(ctx, &ctx->d_png, &ctx->png_cap, lay.total);
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* base = static_cast<uint8_t*>(ctx->d_png);
+	uint32_t* state = reinterpret_cast<uint32_t*>(base + lay.state);
+	uint8_t* data = out_device + head.bytes;
+	uint8_t* z = in_place ? data : base + lay.zstream;
+	HIP_TRY(ctx, hipMemsetAsync(state, 0, CFPNG_S_WORDS*4u, stream));
+	ctx->png_first_event = ctx->events_used;
+	hipEvent_t a, b;
+	rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, stream));
+	hipError_t e = cfhip_launch_png_filter(pixels_device, pixel_type, pitch, width, height, color_type, bit_depth,
+		base + lay.filtered, state, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "png_encode launch: %s", hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, stream));
+	LzPlan lz;
+	cfhip_lz_span span;
+	span.bytes = base + lay.filtered;
+	span.n = p.filtered;
+	lz.spans.push_back(span);
+	lz.total = p.filtered;
+	rc = deflate_run(ctx, lease, lz, hipMemcpyDeviceToDevice, z, reinterpret_cast<unsigned long long*>(state + CFPNG_S_DEFLATE));
+	if (rc != CFHIP_OK)
+		return rc;
+	rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, stream));
+	e = cfhip_launch_png_crc(z, data, zbound, state, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "png_encode launch: %s", hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, stream));
+	rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, stream));
+	e = cfhip_launch_png_final(&head, z, p.filtered, state, out_device, result_device, stream);
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "png_encode launch: %s", hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, stream));
+	ctx->png_pairs = (ctx->events_used - ctx->png_first_event)/2u;
+	return CFHIP_OK;
+}
+
+int cfhip_png_encode(cfhip_ctx* ctx, const void* pixels, int pixel_type, size_t pitch_bytes, uint32_t width, uint32_t height,
+	int color_type, int bit_depth, int color_space, void* out, size_t cap, cfhip_png_result* result)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		PngPlan p;
+		int rc = png_check(ctx, "png_encode", pixels, pixel_type, pitch_bytes, width, height, color_type, bit_depth, color_space,
+			out, cap, result, true, &p);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		png_begin_call(ctx, lease.stream);
+		// the file starts where its IDAT data falls on a word; the result lies behind it, 256-byte aligned
+		const size_t lead = (4u - cfpng_data_offset(p.srgb) % 4u) % 4u;
+		const size_t res_off = (lead + p.bound + 255u)/256u*256u;
+		const size_t row = (size_t)width*p.texel;
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, row*height);
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, res_off + 256u);
+		if (rc != CFHIP_OK)
+			return rc;
+		uint8_t* d_file = static_cast<uint8_t*>(ctx->d_out) + lead;
+		unsigned long long* d_res = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(ctx->d_out) + res_off);
+		HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_src, row, pixels, pitch_bytes, row, height, hipMemcpyHostToDevice, lease.stream));
+		rc = png_run(ctx, lease, p, ctx->d_src, pixel_type, row, width, height, color_type, bit_depth, d_file, d_res);
+		if (rc != CFHIP_OK)
+			return rc;
+		cfhip_png_result res;
+		HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
+		HIP_TRY(ctx, hipStreamSynchronize(lease.stream));
+		if (res.bytes_out > p.bound)
+			return fail(ctx, CFHIP_E_DEVICE, "png_encode: %llu bytes exceed the bound", (unsigned long long)res.bytes_out);
+		HIP_TRY(ctx, hipMemcpyAsync(out, d_file, (size_t)res.bytes_out, hipMemcpyDeviceToHost, lease.stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		*result = res;
+		return CFHIP_OK;
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "png_encode: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "png_encode: unknown exception");
+	}
+}
+
+int cfhip_png_encode_device(cfhip_ctx* ctx, const void* pixels_device, int pixel_type, size_t pitch_bytes, uint32_t width,
+	uint32_t height, int color_type, int bit_depth, int color_space, void* out_device, size_t cap,
+	cfhip_png_result* result_device, void* stream_)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		PngPlan p;
+		int rc = png_check(ctx, "png_encode_device", pixels_device, pixel_type, pitch_bytes, width, height, color_type, bit_depth,
+			color_space, out_device, cap, result_device, false, &p);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		png_begin_call(ctx, lease.stream);
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = png_run(ctx, lease, p, pixels_device, pixel_type, pitch_bytes, width, height, color_type, bit_depth,
+				static_cast<uint8_t*>(out_device), reinterpret_cast<unsigned long long*>(result_device));
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "png_encode_device: %s", e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "png_encode_device: unknown exception");
+	}
+}
+
+int cfhip_png_stage_ms(cfhip_ctx* ctx, float ms[CFPNG_STAGES])
+{
+	static_assert(CFPNG_STAGES == 1 + CFDF_STAGES + 2, "filter, the encoder's stages, crc, final");
+	if (!ctx || !ms)
+		return CFHIP_E_INVALID;
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	const size_t first = ctx->png_first_event, pairs = ctx->png_pairs;
+	if (pairs < 3u + CFDF_STAGES || (pairs - 3u) % CFDF_STAGES || first + 2*pairs > ctx->events_used ||
+		ctx->last_kernel.compare(0, 9, "cfhip_png") != 0)
+		return fail(ctx, CFHIP_E_INVALID, "png_stage_ms: the last call on this context was no cfhip_png_encode*");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->events_stream));
+	for (int k = 0; k < CFPNG_STAGES; ++k)
+		ms[k] = 0.0f;
+	for (size_t i = 0; i < pairs; ++i) {
+		float t = 0.0f;
+		HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->events[first + 2*i], ctx->events[first + 2*i + 1]));
+		// the first pair is the filter's, the last two are crc and final, the encoder's slices lie between
+		const size_t k = i == 0 ? 0u : i >= pairs - 2u ? CFPNG_STAGES - (pairs - i) : 1u + (i - 1u) % CFDF_STAGES;
+		ms[k] += t;
+	}
+	return CFHIP_OK;
 }
 
 // cfhip_rdo_target and cfhip_rdo_target_device

@@ -70,6 +70,17 @@ class _Device:
     def download(self, buf) -> np.ndarray:
         return buf[0].cpu().numpy()
 
+    def png(self, buf, color_type: int, bit_depth: int, color_space) -> bytes:
+        """The PNG file of a buffer (cfhip_png_encode_device): only the file's bytes come back."""
+        import torch
+        t, pt, w, h, pitch = buf
+        cap = api.png_bound(w, h, color_type, bit_depth, color_space)
+        out = torch.empty(cap, dtype=torch.uint8, device=t.device)
+        res = torch.empty(15, dtype=torch.int64, device=t.device)          # one cfhip_png_result
+        self.ctx.png_encode_device(t.data_ptr(), pt, pitch, w, h, out.data_ptr(), cap, res.data_ptr(),
+                                   color_type=color_type, bit_depth=bit_depth, color_space=color_space)
+        return out[:int(res[0].item())].cpu().numpy().tobytes()
+
 
 class Image:
     """A numpy-backed mirror of cuttlefish::Image's pixel methods, under the reference's names.  Each op runs on
@@ -81,6 +92,7 @@ class Image:
         self.color_space = ColorSpace(color_space)
         self.rgbf = bool(rgbf)
         self.device_id = device_id
+        self._last = None       # (the device buffer the last op wrote, the host array downloaded from it)
 
     @property
     def width(self) -> int:
@@ -93,11 +105,47 @@ class Image:
     def _run(self, ops: int, **fields) -> np.ndarray:
         d = _Device(self.device_id)
         desc = api.make_image_ops(ops, self.color_space, rgbf=self.rgbf, **fields)
-        return d.download(d.ops(d.upload(self.pixels), desc))
+        buf = d.ops(d.upload(self.pixels), desc)
+        out = d.download(buf)
+        self._last = (buf, out)
+        return out
 
     def _derived(self, pixels, color_space=None, rgbf=None) -> "Image":
-        return Image(pixels, self.color_space if color_space is None else color_space,
-                     self.rgbf if rgbf is None else rgbf, self.device_id)
+        img = Image(pixels, self.color_space if color_space is None else color_space,
+                    self.rgbf if rgbf is None else rgbf, self.device_id)
+        if self._last is not None and self._last[1] is img.pixels:
+            img._last, self._last = self._last, None          # the buffer belongs to the new image
+        return img
+
+    def save_bytes(self, color_type: Optional[int] = None, bit_depth: int = 8) -> bytes:
+        """The PNG file Image::save writes for the .png extension, made on the GPU (Context.png_encode_device): colour
+        type 0 (grey: the red channel), 2, 4 or 6 -- None: RGBA, or RGB for an RGBF image -- at depth 8 or 16, with an
+        sRGB chunk when the image's colour space is sRGB.  The pixels go from the device buffer the last op left them
+        in while `pixels` is still the array that op returned (assigning another array uploads that one; an array
+        edited in place is not noticed); only the file's bytes come back."""
+        if color_type is None:
+            color_type = api.PNG_RGB if self.rgbf else api.PNG_RGBA
+        if color_type not in (api.PNG_GREY, api.PNG_RGB, api.PNG_GREY_ALPHA, api.PNG_RGBA):
+            raise ValueError("save: colour type %r (0, 2, 4 or 6)" % (color_type,))
+        if bit_depth not in (8, 16):
+            raise ValueError("save: bit depth %r (8 or 16)" % (bit_depth,))
+        d = _Device(self.device_id)
+        if self._last is not None and self._last[1] is self.pixels:
+            buf = self._last[0]
+        else:
+            buf = d.upload(self.pixels)
+        return d.png(buf, int(color_type), int(bit_depth), self.color_space)
+
+    def save(self, file_name: str, color_type: Optional[int] = None, bit_depth: int = 8) -> bool:
+        """Image::save: writes save_bytes() to file_name when its extension is .png; any other extension returns
+        False and writes nothing."""
+        import os
+        if os.path.splitext(str(file_name))[1].lower() != ".png":
+            return False
+        data = self.save_bytes(color_type, bit_depth)
+        with open(file_name, "wb") as f:
+            f.write(data)
+        return True
 
     def flip_horizontal(self) -> bool:
         self.pixels = self._run(ImageOp.FlipX)
@@ -137,7 +185,9 @@ class Image:
     def resize(self, width: int, height: int, filter: ResizeFilter = ResizeFilter.CatmullRom) -> "Image":
         """Image::resize through cfhip_resize_device, in linear space for an sRGB image; equal sizes copy."""
         d = _Device(self.device_id)
-        out = d.download(d.resize(d.upload(self.pixels), width, height, self.color_space, filter))
+        buf = d.resize(d.upload(self.pixels), width, height, self.color_space, filter)
+        out = d.download(buf)
+        self._last = (buf, out)
         return self._derived(out)
 
 

@@ -1035,6 +1035,44 @@ class Texture:
         out[..., :n] = val
         return out
 
+    def decoded_png(self, *args, bit_depth: int = 8) -> Optional[bytes]:
+        """decoded_png([face,] mip=0, depth=0, bit_depth=8): the PNG file (RGBA, depth 8 or 16, an sRGB chunk for an
+        sRGB texture) of one surface of this converted texture, decoded and written on the device: the payload goes up,
+        Context.decode_batch_device (block formats), decode_pvrtc_device or unpack_device (standard formats) writes
+        the texels, Context.png_encode_device reads them there and only the file comes back -- no host copy of texels.
+        The file equals tests/png_ref.py on decode_image() of the surface.  Raises ValueError where decode_images()
+        does (a format that does not decode to RGBA32F); None where data() returns None."""
+        import torch
+        if bit_depth not in (8, 16):
+            raise ValueError("decoded_png: bit depth %r (8 or 16)" % (bit_depth,))
+        payload = self.data(*args)
+        if payload is None:
+            return None
+        _, mip, _ = self._face_args(args)
+        w, h = self.width(mip), self.height(mip)
+        ctx = self._context()
+        dev = "cuda:%d" % self._device_id
+        pvrtc = self._format in api.PVRTC_FORMATS
+        block = int(self._format) >= int(Format.BC1_RGB) and not pvrtc
+        pix, tb = (api.PixelType.RGBA8, 4) if pvrtc else (api.PixelType.RGBA32F, 16)
+        if block and not api.decode_out_supported(self._format, self._type, pix):
+            raise ValueError("decoded_png: %s / %s does not decode to %s" % (self._format.name, self._type.name, pix.name))
+        blob = torch.from_numpy(np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1).copy()).to(dev)
+        texels = torch.empty((h, w, tb), dtype=torch.uint8, device=dev)
+        if block:
+            ctx.decode_batch_device([dict(blocks=blob.data_ptr(), out=texels.data_ptr(), width=w, height=h,
+                                          out_pitch_bytes=w*tb)], self._format, self._type, pix)
+        elif pvrtc:
+            ctx.decode_pvrtc_device(blob.data_ptr(), self._format, w, h, texels.data_ptr(), w*tb, self._type)
+        else:
+            ctx.unpack_device(blob.data_ptr(), self._format, self._type, w, h, texels.data_ptr(), w*tb)
+        cap = api.png_bound(w, h, api.PNG_RGBA, bit_depth, self._color_space)
+        out = torch.empty(cap, dtype=torch.uint8, device=dev)
+        res = torch.empty(15, dtype=torch.int64, device=dev)               # one cfhip_png_result
+        ctx.png_encode_device(texels.data_ptr(), pix, w*tb, w, h, out.data_ptr(), cap, res.data_ptr(),
+                              color_type=api.PNG_RGBA, bit_depth=bit_depth, color_space=self._color_space)
+        return out[:int(res[0].item())].cpu().numpy().tobytes()
+
     def _flat(self):
         """[(mip, depth, face, payload)] in storage order"""
         return [(m, d, f, p) for m, level in enumerate(self._textures) for d, dep in enumerate(level)

@@ -895,6 +895,52 @@ int cfhip_lz4_decode_device(cfhip_ctx* ctx, const void* frame_device, size_t byt
  * (ms); CFHIP_E_INVALID unless that call was a cfhip_lz4_decode*.  Synchronises. */
 int cfhip_lz4_decode_stage_ms(cfhip_ctx* ctx, float* ms, size_t n);
 
+/* ---- PNG files of images (csrc/png.hip, csrc/png.h) ----
+ * Image::save for the .png extension with the texels on the device: one file of signature, IHDR, an sRGB chunk
+ * (rendering intent 0) when color_space is CFHIP_COLOR_SRGB, exactly one IDAT chunk holding one zlib stream, IEND.
+ * color_type 0 (grey), 2 (RGB), 4 (grey + alpha) or 6 (RGBA) at bit_depth 8 or 16; no interlace.  The source is RGBA8,
+ * RGBA16F or RGBA32F with a row pitch.  Samples: floats as the encoders quantise them, round(clamp(f, 0, 1) x 255) or
+ * x 65535, computed in float, NaN -> 0; an RGBA8 source at depth 16 is widened by v x 257; grey takes the red channel;
+ * colour types without alpha drop it; 16-bit samples are big-endian.  Every row gets the filter type, 0 to 4, with the
+ * smallest sum over its filtered bytes of (b < 128 ? b : 256 - b), the lowest type winning a tie (the PNG
+ * specification's heuristic); filters read the raw row above, zeros above the first.  The zlib stream is cfhip_deflate's
+ * of the filtered bytes, height x (1 + row bytes) of them, fewer than 2^31.  The definition, byte for byte, is
+ * tests/png_ref.py; identical calls return identical bytes and result bits.  Not written: palette, sub-byte and
+ * interlaced images (CFHIP_E_UNSUPPORTED), ancillary chunks other than sRGB.  Scratch belongs to the context: about 2
+ * bytes per filtered byte beside the deflate encoder's. */
+typedef struct cfhip_png_result {
+	uint64_t bytes_out, idat_bytes, filtered_bytes;   /* bytes of the file, of the IDAT data (the zlib stream), of its input */
+	uint32_t rows_by_filter[5];                       /* rows per filter type: None, Sub, Up, Average, Paeth */
+	uint32_t idat_crc32;                              /* the IDAT chunk's CRC */
+	cfhip_deflate_result deflate;                     /* the zlib stream's */
+} cfhip_png_result;
+
+/* Bytes that hold the file of any such image: 8 + 25 + (sRGB ? 13 : 0) + 12 + cfhip_deflate_bound(height x (1 + row
+ * bytes)) + 12.  0 for a zero size, and for a colour type, depth or colour space the calls below do not take.  Needs no
+ * device. */
+size_t cfhip_png_bound(uint32_t width, uint32_t height, int color_type, int bit_depth, int color_space);
+
+/* Host buffers.  pixels: rows pitch_bytes apart (>= width x the texel's bytes).  The argument rules of cfhip_deflate:
+ * every argument is checked before anything is enqueued, in this order -- out, result, pixels NULL; a zero width or
+ * height (CFHIP_E_INVALID); the pixel type; the colour space; colour type 3 (CFHIP_E_UNSUPPORTED) or unknown; depth 1,
+ * 2 or 4 (CFHIP_E_UNSUPPORTED) or unknown; the pitch; 2^31 filtered bytes or more, then cap < cfhip_png_bound
+ * (CFHIP_E_CAPACITY); a NULL ctx last.  Nothing outside [out, out + cap) is written; bytes past result->bytes_out are
+ * unspecified.  Blocking. */
+int cfhip_png_encode(cfhip_ctx* ctx, const void* pixels, int pixel_type, size_t pitch_bytes, uint32_t width,
+	uint32_t height, int color_type, int bit_depth, int color_space, void* out, size_t cap, cfhip_png_result* result);
+
+/* Everything on the device: pixels_device and pitch_bytes aligned to the texel's size (4, 8 or 16 bytes), out_device
+ * any alignment (where the IDAT data, 41 or 54 bytes in, falls on a 4-byte boundary the stream is written in place;
+ * otherwise the CRC kernel moves it there), result_device 8-byte aligned.  The stream rules of cfhip_compare_device. */
+int cfhip_png_encode_device(cfhip_ctx* ctx, const void* pixels_device, int pixel_type, size_t pitch_bytes,
+	uint32_t width, uint32_t height, int color_type, int bit_depth, int color_space, void* out_device, size_t cap,
+	cfhip_png_result* result_device, void* stream);
+
+/* Diagnostic, like cfhip_lz4_encode_stage_ms: kernel time of the eleven stages (filter; keys, sort, match, parse, adler,
+ * codes, offsets, emit of the zlib encoder, summed over its slices; crc; final) of the most recent call on this context
+ * (ms); CFHIP_E_INVALID unless that call was a cfhip_png_encode*.  Synchronises. */
+int cfhip_png_stage_ms(cfhip_ctx* ctx, float ms[11]);
+
 /* The pass to a target: the smallest lambda whose result is estimated at no more than
  * T = floor(target_ratio * est_bytes_plain), est_bytes_plain being the estimate of the payloads as given.  The stream
  * is the surfaces' payloads concatenated in call order.  params->lambda is the largest lambda allowed:
@@ -1006,7 +1052,7 @@ int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* p
 	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate* or cfhip_image_ops_device call on
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final) or cfhip_image_ops_device call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
