@@ -38,6 +38,7 @@
 // Build with -ffp-contract=off: fused ops are written as explicit fmaf().
 #include "cf_device.h"
 #include "bc7_packed.h"
+#include "bc7_rcp.h"
 #include "bc7_roles.h"
 #include "bc7_cand.h"
 
@@ -135,6 +136,10 @@ __device__ __forceinline__ void cand_store(uint32_t* slot, const Cand& c)
 		slot[(11 + k)*CF_WG_THREADS] = c.w2[k];
 	}
 }
+// 1.0f/x where x's range is known by construction, and where it comes out of the power iteration (bc7_rcp.h)
+__device__ __forceinline__ float rcp_ranged(float x) { return (CF_BC7_KEYTRIMS & 2) ? cf_rcp_ranged(x) : 1.0f/x; }
+__device__ __forceinline__ float rcp_tested(float x) { return (CF_BC7_KEYTRIMS & 2) ? cf_rcp_tested(x) : 1.0f/x; }
+
 __device__ __forceinline__ uint32_t ub(uint32_t v, int c) { return (v >> (8*c)) & 255u; }
 __device__ __forceinline__ float fb(uint32_t v, int c) { return (float)((v >> (8*c)) & 255u); }
 
@@ -411,12 +416,14 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 	uint32_t khalf, uint32_t ib, const uint32_t (&yw)[2], uint32_t pp_sum, bool want_lsq, uint32_t fe0, uint32_t fe1,
 	LaneFit& f, float (&nx0)[4], float (&nx1)[4], float (&hq)[3], bool& ok, uint32_t s01 = 0u, uint32_t s23 = 0u)   // s01, s23: want_lsq only
 {
+	// keys in minimum form (bc7_packed.h)
+	constexpr bool MINKEY = (CF_BC7_KEYTRIMS & 1) != 0;
 	const uint32_t nk = m6 ? 8u : (1u << ib), kbase = m6 ? 8u*khalf : 0u;
 	const uint32_t e00 = ub(fe0, 0), e01 = ub(fe0, 1), e02 = ub(fe0, 2), e03 = ub(fe0, 3);
 	const uint32_t e10 = ub(fe1, 0), e11 = ub(fe1, 1), e12 = ub(fe1, 2), e13 = ub(fe1, 3);
 	// straight-line palette: entries past this lane's 2^ib get a key that never wins.
-	// A texel's key is the NEGATED 128 (sum_c w_c c_k^2 - 2 sum_c p_c (w_c c_k)) + weight_k,
-	// maximised over k; sum_c w_c p_c^2 is added once per subset (pp_sum).  Unit weights: the
+	// A texel's key is 128 (sum_c w_c c_k^2 - 2 sum_c p_c (w_c c_k)) + weight_k, minimised over k
+	// (CF_BC7_KEYTRIMS bit 1; the parent's form maximises its negation); sum_c w_c p_c^2 is added once per subset (pp_sum).  Unit weights: the
 	// cross term is one v_dot4(p, c_k).  Perceptual metric: the palette entry goes to (Y, Cr, Cb, A),
 	// its weighted form is two words of 16-bit pairs, the cross term two v_dot2_u32_u16.
 	uint32_t pal[8], palh[8];
@@ -442,8 +449,8 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 			// two channels per multiply; in difference form one multiply and one add per channel pair
 			pal[k] = (CF_BC7_FITTRIMS & 1) ? pal_at(line, w) : pal_word(fe0, fe1, w);
 			palh[k] = 0;
-			base[k] = valid ? -(int)((__builtin_amdgcn_udot4(pal[k], pal[k], 0u, false) << 7) | w)
-				: -0x3FFFFFFF;
+			const int B = (int)((__builtin_amdgcn_udot4(pal[k], pal[k], 0u, false) << 7) | w);
+			base[k] = MINKEY ? (valid ? B : CF_BC7_NO_ENTRY) : (valid ? -B : -CF_BC7_NO_ENTRY);
 		} else {
 			const uint32_t c0 = (__umul24(iw, e00) + __umul24(w, e10) + 32u) >> 6;
 			const uint32_t c1 = (__umul24(iw, e01) + __umul24(w, e11) + 32u) >> 6;
@@ -456,12 +463,17 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 			pal[k] = pk_mul_u16(qrg, yw[0]);
 			palh[k] = pk_mul_u16(qba, yw[1]);
 			const uint32_t qq = dot2_u16(pal[k], qrg, dot2_u16(palh[k], qba, 0u));   // <= 3.7e6
-			base[k] = valid ? -(int)((qq << 7) | w) : -0x3FFFFFFF;
+			const int B = (int)((qq << 7) | w);
+			base[k] = MINKEY ? (valid ? B : CF_BC7_NO_ENTRY) : (valid ? -B : -CF_BC7_NO_ENTRY);
 		}
-		// hide that base is a negation: "(dt << 8) + base" then stays ONE v_lshl_add_u32 per entry
-		// and texel (the compiler otherwise emits a shift and a subtract for half of them)
+		// hide what base is: the maximum form's "(dt << 8) + base" then stays ONE v_lshl_add_u32 per entry and texel
+		// (the compiler otherwise emits a shift and a subtract for half of them), the minimum form's ONE v_mad_i32_i24
 		asm volatile("" : "+v"(base[k]));
 	}
+	// the minimum form's factor from a scalar register (a VOP3 instruction takes no literal), opaque so that the
+	// multiply is not turned back into a shift and a subtraction
+	int m256 = -256;
+	if (MINKEY) asm volatile("" : "+s"(m256));
 	uint32_t err = pp_sum;
 	uint32_t wp0 = 0, wp1 = 0, wp2 = 0, wp3 = 0;
 #pragma unroll 1
@@ -495,7 +507,7 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 				const uint32_t p = UNITW ? texel<true>(tx, rawj) : 0u;
 				uint32_t key;
 				{
-					int bestk = -0x7FFFFFFF;
+					int bestk = MINKEY ? 0x7FFFFFFF : -0x7FFFFFFF;
 					const uint32_t prg = rawj, pba = rawh[j];
 #pragma unroll
 					for (int k = 0; k < NK; ++k) {
@@ -504,16 +516,21 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 							dt = (int)__builtin_amdgcn_udot4(p, pal[k], 0u, false);
 						else
 							dt = (int)dot2_u16(pba, palh[k], dot2_u16(prg, pal[k], 0u));
-						const int v = (dt << 8) + base[k];
-						bestk = v > bestk ? v : bestk;
+						if (MINKEY) {
+							const int v = key_min_form(dt, m256, base[k]);
+							bestk = v < bestk ? v : bestk;
+						} else {
+							const int v = key_max_form(dt, base[k]);
+							bestk = v > bestk ? v : bestk;
+						}
 					}
 					// mode 6: the other palette half lives in the neighbouring lane (the 4-entry search is entered
 					// only when no active lane of the wave is a mode-6 lane: it has no exchange at all)
 					if (NK == 8) {
 						const int other = (int)cf_xor1((uint32_t)bestk);
-						bestk = (m6 && other > bestk) ? other : bestk;
+						bestk = (m6 && (MINKEY ? other < bestk : other > bestk)) ? other : bestk;
 					}
-					key = (uint32_t)(-bestk);   // 128 (sum w c^2 - 2 p.(w c)) + weight, two's complement
+					key = (uint32_t)(MINKEY ? bestk : -bestk);   // 128 (sum w c^2 - 2 p.(w c)) + weight, two's complement
 				}
 				key = ((mrow >> j) & 1u) ? key : 0u;
 				err += (uint32_t)((int)key >> 7);
@@ -554,7 +571,7 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 	}
 	const int det = (int)__umul24((uint32_t)__builtin_popcount(mask), C) - (int)__umul24(S, S);
 	ok = det > 0;
-	const float inv = 1.0f/(64.0f*(float)(det > 0 ? det : 1));
+	const float inv = rcp_ranged(64.0f*(float)(det > 0 ? det : 1));
 	const float fA = (float)A, fB = (float)B, fC = (float)C;
 #pragma unroll
 	for (int c = 0; c < 4; ++c) {
@@ -781,13 +798,13 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 #pragma unroll
 		for (int c = 0; c < 4; ++c) axis[c] = 0.0f;
 		if (mx > 0.0f) {
-			const float im = 1.0f/mx;
+			const float im = rcp_tested(mx);
 			v0 = v0*im; v1 = v1*im; v2 = v2*im; v3 = v3*im;
 			float l2 = v0*v0;
 			l2 = fmaf(v1, v1, l2);
 			l2 = fmaf(v2, v2, l2);
 			l2 = fmaf(v3, v3, l2);
-			const float is = 1.0f/sqrtf(l2);
+			const float is = rcp_ranged(sqrtf(l2));
 			axis[0] = v0*is; axis[1] = v1*is; axis[2] = v2*is; axis[3] = v3*is;
 		}
 
@@ -1171,7 +1188,7 @@ __device__ __forceinline__ float subset_residual(const Moments& mo, uint32_t mas
 	float res = 0.0f;
 	along = 0.0f;
 	if (mx > 0.0f) {
-		const float im = 1.0f/mx;
+		const float im = rcp_tested(mx);
 		v0 = v0*im; v1 = v1*im; v2 = v2*im; v3 = A4 ? v3*im : 0.0f;
 		CF_MATVEC(w0, w1, w2, w3)
 		float num = v0*w0;
@@ -1182,7 +1199,7 @@ __device__ __forceinline__ float subset_residual(const Moments& mo, uint32_t mas
 		den = fmaf(v1, v1, den);
 		den = fmaf(v2, v2, den);
 		if (A4) den = fmaf(v3, v3, den);
-		const float lam = num*(1.0f/den);
+		const float lam = num*rcp_ranged(den);
 		const float in = inv_n(n);
 		res = (tr - lam)*in;
 		res = res > 0.0f ? res : 0.0f;

@@ -21,6 +21,34 @@
 #define CF_PK_MUL24(a, b) ((a)*(b))
 #endif
 
+// A/B switch, a bit mask: instruction-level forms of the selector search's keys and of the reciprocals.  0 builds the
+// parent's forms.
+//   1: a texel's key in minimum form, B_k - 256 dt minimised over the entries, instead of (dt << 8) - B_k maximised
+//      and negated per texel (key_min_form / key_max_form below)
+//   2: 1.0f/x as v_rcp_f32 and one Newton step where the argument's range is known (bc7_rcp.h)
+// Same payload either way.
+#ifndef CF_BC7_KEYTRIMS
+#define CF_BC7_KEYTRIMS 3
+#endif
+
+// product of two signed operands that fit 24 bits
+#if defined(__HIP_DEVICE_COMPILE__)
+#define CF_PK_MUL24S(a, b) __mul24((a), (b))
+#else
+#define CF_PK_MUL24S(a, b) ((a)*(b))
+#endif
+
+// ---- a texel's key against one palette entry ----
+// B = (cc << 7) | w is the entry's constant (cc = sum_c w_c c^2 of its colour, w its interpolation weight), dt the cross
+// term sum_c p_c (w_c c).  The key 128 (cc - 2 dt) + w = B - 256 dt orders entries by error, then by weight.
+// Maximum form (the parent's): the entry holds -B, a texel's value is (dt << 8) - B, the largest wins and the key is
+// its negation.  Minimum form: the key itself, one multiply-add of 24-bit operands (dt < 2^23, m256 = -256 from a
+// register), the smallest wins and nothing is negated.  a - b == -(b - a) in two's complement and max(-x) == -min(x), so
+// both give the same key; no value leaves 32 bits (B < 2^30 and 256 dt < 2^30 under both metrics).
+#define CF_BC7_NO_ENTRY 0x3FFFFFFF      // constant of an entry that does not exist: never the minimum
+CF_PK int key_max_form(int dt, int negB) { return (dt << 8) + negB; }
+CF_PK int key_min_form(int dt, int m256, int B) { return CF_PK_MUL24S(dt, m256) + B; }
+
 // Dequantise one t-bit code v < 2^t (t = 4..8) to a byte: (v << (8 - t)) | (v >> (2t - 8)).
 // v * (2^t + 1) holds v twice, t bits apart and without overlap; the shift drops what falls below the byte.
 CF_PK uint32_t dequant1(uint32_t v, uint32_t t)

@@ -14,11 +14,19 @@ every s_* that is no branch (s_nop and s_waitcnt among them), branches every s_b
 static: a region inlined at n call sites is counted n times, a loop body once per copy.  What runs how often is not
 in this table.  A start or end text may be a tuple of alternatives: the first line that holds any of them (the same
 region in sources that word its opening differently).
+
+--classes prints another table: per region, how many of its VALU instructions are in the 2-cycle class and how many in
+the 4-cycle class (the class list of tools/isa_mix.py), and how many v_mov_b32 and s_nop it holds; the last line gives
+the v_mov_b32 the compiler put on line 0.
 """
 import argparse
 import collections
 import os
 import re
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from isa_mix import FAST  # noqa: E402
 
 # (label, text that opens the region, text of the first line after it); searched in this order from the top
 _ASSEMBLY = ("// the fit this lane's geometry-cache column now holds", "// ---- assemble candidates in their leader lanes")
@@ -64,6 +72,7 @@ def main():
     ap.add_argument("asm")
     ap.add_argument("source")
     ap.add_argument("--kernel", default="cfhip_bc7_encode_kernelILi0ELb1ELb0ELi2E")
+    ap.add_argument("--classes", action="store_true", help="per region: VALU by issue class, v_mov_b32 and s_nop counts")
     a = ap.parse_args()
     src = open(a.source).read().split("\n")
     regions, at = [], 0
@@ -79,7 +88,8 @@ def main():
         regions.append((label, s + 1, e))        # 1-based, inclusive
         at = s
     files, counts, ops = {}, collections.defaultdict(collections.Counter), collections.defaultdict(collections.Counter)
-    inside, cur = False, ("?", 0)
+    cls = collections.defaultdict(collections.Counter)      # region -> fast / slow / mov / nop
+    inside, cur, line0, mov_line0 = False, ("?", 0), False, 0
     for line in open(a.asm):
         t = line.strip()
         m = re.match(r'\.file\s+(\d+)\s+(?:"[^"]*"\s+)?"([^"]+)"', t)
@@ -96,7 +106,8 @@ def main():
             continue
         m = re.match(r"\.loc\s+(\d+)\s+(\d+)", t)
         if m:
-            if int(m.group(2)) != 0:          # line 0 stays with the source line before it
+            line0 = int(m.group(2)) == 0
+            if not line0:                     # line 0 stays with the source line before it
                 cur = (files.get(int(m.group(1)), "?"), int(m.group(2)))
             continue
         op = t.split()[0] if t and not t.startswith((".", ";")) and not t.endswith(":") else ""
@@ -109,12 +120,27 @@ def main():
         counts[key][kind] += 1
         if kind == "valu":
             ops[key][op.replace("_e32", "").replace("_e64", "")] += 1
+            plain = re.sub(r"_(e32|e64|dpp|sdwa|e64_dpp)$", "", op)
+            cls[key]["fast" if plain in FAST else "slow"] += 1
+            if plain == "v_mov_b32":
+                cls[key]["mov"] += 1
+                mov_line0 += line0
+        elif op == "s_nop":
+            cls[key]["nop"] += 1
     total = {k: sum(c[k] for c in counts.values()) for k in ("valu", "salu", "branch")}
     print("%s: %d static VALU instructions, %d scalar, %d branches" % (a.kernel, total["valu"], total["salu"], total["branch"]))
     print("  %-34s %5s  %6s  %5s %6s   %s" % ("region", "VALU", "", "SALU", "branch", "most frequent VALU"))
     for key, c in sorted(counts.items(), key=lambda kv: -kv[1]["valu"]):
         top = ", ".join("%s %d" % kv for kv in ops[key].most_common(6))
         print("  %-34s %5d  %4.1f %%  %5d  %5d   %s" % (key, c["valu"], 100.0*c["valu"]/max(total["valu"], 1), c["salu"], c["branch"], top))
+    if a.classes:
+        tot = collections.Counter()
+        for c in cls.values():
+            tot.update(c)
+        print("  %-34s %7s %7s %9s %6s" % ("region", "2-cycle", "4-cycle", "v_mov_b32", "s_nop"))
+        for key, c in sorted(cls.items(), key=lambda kv: -(kv[1]["fast"] + kv[1]["slow"])):
+            print("  %-34s %7d %7d %9d %6d" % (key, c["fast"], c["slow"], c["mov"], c["nop"]))
+        print("  %-34s %7d %7d %9d %6d   (%d of the v_mov_b32 on line 0)" % ("all", tot["fast"], tot["slow"], tot["mov"], tot["nop"], mov_line0))
 
 
 if __name__ == "__main__":

@@ -120,6 +120,19 @@ __global__ void __launch_bounds__(256) k(uint32_t* out, uint32_t seed)
 	if (OP == 44) BODY("v_cvt_i32_f32 %0, %0", )
 	if (OP == 45) BODY("v_dot2_f32_f16 %0, %1, %2, %0", )
 	if (OP == 46) BODY("v_dot2c_f32_f16 %0, %1, %2", )
+	// the minimum-form key of the BC7 selector search (multiply-add with the factor in a scalar register, as the kernel
+	// holds its -256; v_min3_i32) and the refit window's row minima
+	if (OP == 47) BODY("v_min3_i32 %0, %0, %1, %2", )
+	if (OP == 48) BODY("v_min3_f32 %0, %0, %1, %2", )
+	if (OP == 49) {
+		int sm = -256;
+		asm volatile("" : "+s"(sm));
+		for (int it = 0; it < ITER; ++it) {
+#pragma unroll
+			for (int i = 0; i < 16; ++i)
+				asm volatile("v_mad_i32_i24 %0, %0, %1, %2" : "+v"(a[i]) : "s"(sm), "v"(c));
+		}
+	}
 	uint32_t r = 0;
 #pragma unroll
 	for (int i = 0; i < 16; ++i) r ^= a[i];
@@ -173,6 +186,7 @@ int main()
 		run<41>("v_max_f32", w);      run<42>("v_max3_f32", w);
 		run<43>("v_rcp_f32", w);      run<44>("v_cvt_i32_f32", w);
 		run<45>("v_dot2_f32_f16", w); run<46>("v_dot2c_f32_f16", w);
+		run<47>("v_min3_i32", w);     run<48>("v_min3_f32", w);    run<49>("v_mad_i32_i24 sgpr", w);
 	}
 	return 0;
 }
