@@ -203,7 +203,8 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_inflate", "cfhip_inflate_device", "cfhip_inflate_stage_ms",
            "cfhip_lz4_bound", "cfhip_lz4_encode", "cfhip_lz4_encode_device", "cfhip_lz4_encode_stage_ms",
            "cfhip_lz4_decode", "cfhip_lz4_decode_device", "cfhip_lz4_decode_stage_ms",
-           "cfhip_png_bound", "cfhip_png_encode", "cfhip_png_encode_device", "cfhip_png_stage_ms"]
+           "cfhip_png_bound", "cfhip_png_encode", "cfhip_png_encode_device", "cfhip_png_stage_ms",
+           "cfhip_mip_post_array_device", "cfhip_alpha_coverage_device"]
 
 
 class Layout(enum.IntEnum):
@@ -458,6 +459,44 @@ def png_bound(width: int, height: int, color_type: int = PNG_RGBA, bit_depth: in
     return int(load_library().cfhip_png_bound(int(width), int(height), int(color_type), int(bit_depth), int(color_space)))
 
 
+MIP_POST_COVERAGE, MIP_POST_NORMALIZE, MIP_POST_SIGNED_NORMALS = 1, 2, 4     # cfhip_mip_post_params.flags
+
+
+class MipPostParams(ctypes.Structure):
+    """cfhip_mip_post_params"""
+    _fields_ = [("flags", ctypes.c_uint32), ("alpha_threshold", ctypes.c_float)]
+
+
+class MipPostResult(ctypes.Structure):
+    """cfhip_mip_post_result: one generated level's scale, its target count and its counts at scale 1 and at the scale"""
+    _fields_ = [("scale", ctypes.c_float), ("target", ctypes.c_uint32), ("count_before", ctypes.c_uint32),
+                ("count_after", ctypes.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {"scale": float(self.scale), "target": int(self.target), "count_before": int(self.count_before),
+                "count_after": int(self.count_after)}
+
+
+MIP_POST_RESULT_DTYPE = np.dtype([("scale", np.float32), ("target", np.uint32), ("count_before", np.uint32),
+                                  ("count_after", np.uint32)])
+
+
+class CoverageSurface(ctypes.Structure):
+    """cfhip_coverage_surface"""
+    _fields_ = [("pixels", ctypes.c_void_p), ("pixel_type", ctypes.c_int32), ("width", ctypes.c_uint32),
+                ("height", ctypes.c_uint32), ("pitch_bytes", ctypes.c_size_t)]
+
+
+def make_mip_post_params(alpha_coverage: Optional[float] = None, normalize: Optional[str] = None) -> MipPostParams:
+    """alpha_coverage: the alpha-test threshold in (0, 1], or None; normalize: "unorm" (Image.create_normal_map's
+    storage without KEEP_SIGN), "snorm" (signed storage) or None."""
+    if normalize not in (None, "unorm", "snorm"):
+        raise ValueError('normalize is "unorm", "snorm" or None, not %r' % (normalize,))
+    flags = (MIP_POST_COVERAGE if alpha_coverage is not None else 0) | (MIP_POST_NORMALIZE if normalize else 0) | \
+        (MIP_POST_SIGNED_NORMALS if normalize == "snorm" else 0)
+    return MipPostParams(flags, float(alpha_coverage) if alpha_coverage is not None else 0.0)
+
+
 RDO_NO_CAP = 0xFFFFFFFF         # max_sse_increase: no cap
 RDO_ROW_ABOVE = 1               # CFHIP_RDO_ROW_ABOVE
 
@@ -564,6 +603,14 @@ def load_library(path: Optional[str] = None):
         ctypes.c_uint32, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
         ctypes.c_uint32, ctypes.c_void_p]
     L.cfhip_generate_mips_array_device.restype = ctypes.c_int
+    L.cfhip_mip_post_array_device.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
+        ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32,
+        ctypes.POINTER(MipPostParams), ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_mip_post_array_device.restype = ctypes.c_int
+    L.cfhip_alpha_coverage_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(CoverageSurface), ctypes.c_uint32,
+                                              ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_alpha_coverage_device.restype = ctypes.c_int
     L.cfhip_generate_mips3d_device.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
         ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
@@ -1053,6 +1100,56 @@ class Context:
         self._check(self._lib.cfhip_generate_mips_array_device(
             self._h, sarr, nl, int(pixel_type), width, height, row_pitch_bytes, int(color_space), int(filter),
             darr, per + 1, ctypes.c_void_p(stream) if stream else None))
+
+    def mip_post_device(self, srcs: Sequence[int], pixel_type, width: int, height: int, row_pitch_bytes: int,
+                        levels: Sequence[Sequence[int]], alpha_coverage: Optional[float] = None,
+                        normalize: Optional[str] = None, results: int = 0, stream: int = 0):
+        """The repairs of generated mip chains in place (cfhip_mip_post_array_device), on the buffers as
+        generate_mips_array_device takes them: srcs[l] = level 0 of layer l (only read), levels[l][k-1] = its level k
+        (RGBA32F, tightly packed).  alpha_coverage = t scales each level's alpha so that its share of texels with
+        alpha >= t matches level 0's; normalize = "unorm" / "snorm" renormalises every RGB.  results: device pointer to
+        len(srcs) * len(levels[0]) cfhip_mip_post_result records (MIP_POST_RESULT_DTYPE), required with alpha_coverage.
+        Premultiplied colour is out of scope: the pass scales alpha alone, so run it on straight alpha."""
+        nl = len(srcs)
+        if nl == 0 or len(levels) != nl or len({len(d) for d in levels}) != 1:
+            raise ValueError("srcs and levels must list the same layers, every layer the same levels")
+        per = len(levels[0])
+        params = make_mip_post_params(alpha_coverage, normalize)
+        sarr = (ctypes.c_void_p * nl)(*[ctypes.c_void_p(int(p)) for p in srcs])
+        flat = [ctypes.c_void_p(int(p)) for d in levels for p in d]
+        darr = (ctypes.c_void_p * max(len(flat), 1))(*flat)
+        self._check(self._lib.cfhip_mip_post_array_device(
+            self._h, sarr, nl, int(pixel_type), width, height, row_pitch_bytes, darr, per + 1, ctypes.byref(params),
+            ctypes.c_void_p(int(results)) if results else None, ctypes.c_void_p(stream) if stream else None))
+
+    def alpha_coverage_device(self, surfaces: Sequence[dict], threshold: float, counts: int, scale: float = 1.0,
+                              stream: int = 0):
+        """counts[i] (device pointer to len(surfaces) uint32) = the texels of surface i with fl32(alpha * scale) >=
+        threshold.  surfaces: dicts with pixels (device ptr int), pixel_type, width, height, row_pitch_bytes; any mix
+        of sizes and pixel types, one launch."""
+        surf = (CoverageSurface * max(len(surfaces), 1))()
+        for i, s in enumerate(surfaces):
+            surf[i].pixels = s["pixels"]
+            surf[i].pixel_type = int(s["pixel_type"])
+            surf[i].width, surf[i].height = s["width"], s["height"]
+            surf[i].pitch_bytes = s["row_pitch_bytes"]
+        self._check(self._lib.cfhip_alpha_coverage_device(
+            self._h, surf, len(surfaces), threshold, scale, ctypes.c_void_p(int(counts)) if counts else None,
+            ctypes.c_void_p(stream) if stream else None))
+
+    def alpha_coverage(self, image: np.ndarray, threshold: float, scale: float = 1.0) -> int:
+        """Host convenience: the number of texels of an (h, w, 4) uint8 / float16 / float32 image whose alpha passes
+        fl32(alpha * scale) >= threshold, counted on the GPU."""
+        import torch
+        host = np.ascontiguousarray(image)
+        if host.ndim != 3 or host.shape[2] != 4:
+            raise ValueError("expected (h, w, 4)")
+        pt = pixel_type_of(host)
+        dev = torch.from_numpy(host.view(np.uint8)).to("cuda:%d" % self.device_id)
+        out = torch.zeros(1, dtype=torch.int32, device=dev.device)
+        self.alpha_coverage_device([dict(pixels=dev.data_ptr(), pixel_type=pt, width=host.shape[1], height=host.shape[0],
+                                         row_pitch_bytes=host.strides[0])], threshold, out.data_ptr(), scale)
+        return int(out.cpu().numpy().view(np.uint32)[0])
 
     def generate_mips3d_device(self, src: int, pixel_type, width: int, height: int, depth: int,
                                row_pitch_bytes: int, slice_pitch_bytes: int, dst_levels: Sequence[int],

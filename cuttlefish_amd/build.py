@@ -160,7 +160,10 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  "cfhip_lz4_emit_kernel", "cfhip_lz4_hash_kernel", "cfhip_lz4_final_kernel", "cfhip_lz4_chain_kernel",
                  "cfhip_lz4_block_kernel", "cfhip_lz4_dfinal_kernel",
                  # PNG files of images (csrc/png.hip): the 24 filter kernels (source type x channels x depth), crc, final
-                 "cfhip_png_filter_kernel", "cfhip_png_crc_kernel", "cfhip_png_final_kernel")
+                 "cfhip_png_filter_kernel", "cfhip_png_crc_kernel", "cfhip_png_final_kernel",
+                 # the mip post-pass (csrc/mip_post.hip): alpha coverage and normal renormalisation
+                 "cfhip_mip_post_gather_kernel", "cfhip_mip_post_count_kernel", "cfhip_mip_post_decide_kernel",
+                 "cfhip_mip_post_apply_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

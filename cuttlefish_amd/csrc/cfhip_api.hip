@@ -16,6 +16,7 @@
 #include "inflate.h"
 #include "lz4.h"
 #include "png.h"
+#include "mip_post.h"
 #include "../../include/cuttlefish_hip.h"
 
 #include <cmath>
@@ -1967,6 +1968,233 @@ int cfhip_generate_mips_array_device(cfhip_ctx* ctx, const void* const* srcs, ui
 			pw = w; ph = h;
 		}
 	}
+	return lease.done(!stream_);
+}
+
+// ---- mip post-pass (csrc/mip_post.hip): alpha-test coverage and normal renormalisation ---------------------------
+// one launch of the post-pass, timed like every encode launch (cfhip_last_kernel_ms / profiling)
+#define MIP_POST_TIMED(ctx, stream, launch_expr) do { \
+		hipEvent_t a_, b_; \
+		const int rc_ = next_event_pair((ctx), &a_, &b_); \
+		if (rc_ != CFHIP_OK) return rc_; \
+		HIP_TRY((ctx), hipEventRecord(a_, (stream))); \
+		const hipError_t le_ = (launch_expr); \
+		if (le_ != hipSuccess) return fail((ctx), CFHIP_E_DEVICE, "mip post-pass launch: %s", hipGetErrorString(le_)); \
+		HIP_TRY((ctx), hipEventRecord(b_, (stream))); \
+	} while (0)
+
+// the alpha component must be loadable: its size divides the pointer and the pitch
+static bool alpha_aligned(const void* p, size_t pitch, int pixel_type)
+{
+	const size_t a = pixel_type == CFHIP_PIXEL_RGBA8 ? 1u : pixel_type == CFHIP_PIXEL_RGBA16F ? 2u : 4u;
+	return (uintptr_t)p % a == 0 && pitch % a == 0;
+}
+
+static void mip_post_begin_call(cfhip_ctx* ctx, hipStream_t stream, const char* kernel)
+{
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = kernel;
+}
+
+int cfhip_alpha_coverage_device(cfhip_ctx* ctx, const cfhip_coverage_surface* surfaces, uint32_t count, float threshold,
+	float scale, uint32_t* counts_device, void* stream_)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	if (!surfaces)
+		return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces is NULL");
+	if (!counts_device)
+		return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: counts_device is NULL");
+	if (!count)
+		return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: count is 0");
+	if (!(threshold > 0.0f && threshold <= 1.0f))
+		return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: threshold %g outside (0, 1]", (double)threshold);
+	if (!(scale > 0.0f) || std::isinf(scale))
+		return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: scale %g is not a positive finite number", (double)scale);
+	std::vector<cfmp_surf> tab(count);
+	uint64_t wg = 0;
+	for (uint32_t i = 0; i < count; ++i) {
+		const cfhip_coverage_surface& s = surfaces[i];
+		if (!s.pixels)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u].pixels is NULL", i);
+		if (!s.width || !s.height)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u] has a zero width or height", i);
+		const size_t pb = pixel_bytes(s.pixel_type);
+		if (!pb)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u]: pixel type %d", i, s.pixel_type);
+		if (s.pitch_bytes < (size_t)s.width*pb)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u]: pitch_bytes %zu < %zu", i, s.pitch_bytes,
+				(size_t)s.width*pb);
+		if ((uint64_t)s.width*s.height > CFMP_MAX_TEXELS)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u]: more than 2^30 texels", i);
+		if (!alpha_aligned(s.pixels, s.pitch_bytes, s.pixel_type))
+			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u]: pixels or pitch_bytes not aligned to a component", i);
+		cfmp_surf& e = tab[i];
+		e.pixels = static_cast<const uint8_t*>(s.pixels);
+		e.pitch = s.pitch_bytes;
+		e.plane_off = 0;
+		e.width = s.width; e.height = s.height;
+		e.n = s.width*s.height;
+		e.pixel_type = s.pixel_type;
+		e.wg_begin = (uint32_t)wg;
+		e.ref = 0;
+		wg += (e.n + CFMP_CHUNK - 1u)/CFMP_CHUNK;
+		if (wg > 0x7FFFFFFFull)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: the surfaces are too large for one launch");
+	}
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	const hipStream_t stream = lease.stream;
+	mip_post_begin_call(ctx, stream, "cfhip_mip_post_gather_kernel");
+	int rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab.size()*sizeof(cfmp_surf));
+	if (rc != CFHIP_OK)
+		return rc;
+	// pageable source: the runtime stages the copy before returning, so `tab` may die
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, tab.data(), tab.size()*sizeof(cfmp_surf), hipMemcpyHostToDevice, stream));
+	HIP_TRY(ctx, hipMemsetAsync(counts_device, 0, (size_t)count*4u, stream));
+	MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_gather(static_cast<const cfmp_surf*>(ctx->d_batch), count, 0u,
+		(uint32_t)wg, threshold, scale, scale, scale, 1u, 1u, nullptr, counts_device, stream));
+	return lease.done(!stream_);
+}
+
+int cfhip_mip_post_array_device(cfhip_ctx* ctx, const void* const* srcs, uint32_t layers, int src_pixel_type,
+	uint32_t width, uint32_t height, size_t src_pitch_bytes, void* const* levels, uint32_t levels_count,
+	const cfhip_mip_post_params* params, cfhip_mip_post_result* results_device, void* stream_)
+{
+	static_assert(sizeof(cfhip_mip_post_params) == 8 && sizeof(cfhip_mip_post_result) == 16, "the ABI's sizes");
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	if (!params)
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: params is NULL");
+	if (!srcs)
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: srcs is NULL");
+	if (!levels)
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: levels is NULL");
+	if (!layers || layers > 65535u)
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: layers is %u (1 to 65535 per call)", layers);
+	if (!width || !height)
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: a zero width or height (%ux%u)", width, height);
+	const size_t pb = pixel_bytes(src_pixel_type);
+	if (!pb)
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: src_pixel_type %d", src_pixel_type);
+	uint32_t max_levels = 1;
+	for (uint32_t d = std::max(width, height); d > 1; d >>= 1)
+		++max_levels;
+	if (levels_count < 2 || levels_count > max_levels)
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: levels_count is %u, a chain to repair has 2 to %u levels at %ux%u",
+			levels_count, max_levels, width, height);
+	const uint32_t flags = params->flags;
+	const uint32_t all_flags = CFHIP_MIP_POST_COVERAGE | CFHIP_MIP_POST_NORMALIZE | CFHIP_MIP_POST_SIGNED_NORMALS;
+	if (!flags || (flags & ~all_flags))
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: params->flags 0x%x: none or unknown", flags);
+	if ((flags & CFHIP_MIP_POST_SIGNED_NORMALS) && !(flags & CFHIP_MIP_POST_NORMALIZE))
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: params->flags: SIGNED_NORMALS without NORMALIZE");
+	const bool coverage = flags & CFHIP_MIP_POST_COVERAGE;
+	const float t = params->alpha_threshold;
+	if (coverage && !(t > 0.0f && t <= 1.0f))
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: params->alpha_threshold %g outside (0, 1]", (double)t);
+	if (src_pitch_bytes < (size_t)width*pb)
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: src_pitch_bytes %zu < %zu, a row", src_pitch_bytes, (size_t)width*pb);
+	if (coverage && !results_device)
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: results_device is NULL under COVERAGE");
+	if ((uint64_t)width*height > CFMP_MAX_TEXELS)
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: more than 2^30 texels in level 0");
+	const uint32_t per = levels_count - 1u;
+	const size_t nlev = (size_t)layers*per, nsurf = nlev + (coverage ? layers : 0u);
+	std::vector<cfmp_surf> tab(nsurf);
+	uint64_t wg = 0, plane = 0;
+	for (uint32_t l = 0; l < layers; ++l) {
+		if (!srcs[l])
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: srcs[%u] is NULL", l);
+		if (coverage && !alpha_aligned(srcs[l], src_pitch_bytes, src_pixel_type))
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: srcs[%u] or src_pitch_bytes not aligned to a component", l);
+		for (uint32_t k = 1; k < levels_count; ++k) {
+			const size_t i = (size_t)l*per + (k - 1u);
+			if (!levels[i])
+				return fail(ctx, CFHIP_E_INVALID, "mip_post: levels[%zu] (layer %u, level %u) is NULL", i, l, k);
+			if ((uintptr_t)levels[i] % 16u)
+				return fail(ctx, CFHIP_E_INVALID, "mip_post: levels[%zu] is not aligned to a texel (16 bytes)", i);
+			cfmp_surf& e = tab[i];
+			e.width = (width >> k) ? (width >> k) : 1u;
+			e.height = (height >> k) ? (height >> k) : 1u;
+			e.pixels = static_cast<const uint8_t*>(levels[i]);
+			e.pitch = (unsigned long long)e.width*16u;
+			e.plane_off = plane;
+			e.n = e.width*e.height;
+			e.pixel_type = CFHIP_PIXEL_RGBA32F;
+			e.wg_begin = (uint32_t)wg;
+			e.ref = (uint32_t)(nlev + l);
+			wg += (e.n + CFMP_CHUNK - 1u)/CFMP_CHUNK;
+			plane += e.n;
+		}
+	}
+	const uint64_t wg_levels = wg;
+	for (uint32_t l = 0; coverage && l < layers; ++l) {
+		cfmp_surf& e = tab[nlev + l];
+		e.pixels = static_cast<const uint8_t*>(srcs[l]);
+		e.pitch = src_pitch_bytes;
+		e.plane_off = 0;
+		e.width = width; e.height = height;
+		e.n = width*height;
+		e.pixel_type = src_pixel_type;
+		e.wg_begin = (uint32_t)wg;
+		e.ref = 0;
+		wg += (e.n + CFMP_CHUNK - 1u)/CFMP_CHUNK;
+	}
+	if (wg > 0x7FFFFFFFull)
+		return fail(ctx, CFHIP_E_INVALID, "mip_post: the surfaces are too large for one launch");
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	const hipStream_t stream = lease.stream;
+	mip_post_begin_call(ctx, stream, coverage ? "cfhip_mip_post_count_kernel" : "cfhip_mip_post_apply_kernel");
+	// d_batch: the surface table, then the levels' search states, then the counters; d_src: the alpha plane
+	const size_t tab_bytes = (nsurf*sizeof(cfmp_surf) + 15u) & ~(size_t)15u;
+	const size_t state_bytes = coverage ? nlev*sizeof(cfmp_state) : 0u;
+	const size_t cnt_bytes = coverage ? nsurf*CFMP_SLOTS*4u : 0u;
+	int rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab_bytes + state_bytes + cnt_bytes);
+	if (rc == CFHIP_OK && coverage)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, (size_t)plane*4u);
+	if (rc != CFHIP_OK)
+		return rc;
+	uint8_t* base = static_cast<uint8_t*>(ctx->d_batch);
+	const cfmp_surf* d_tab = reinterpret_cast<const cfmp_surf*>(base);
+	cfmp_state* d_state = coverage ? reinterpret_cast<cfmp_state*>(base + tab_bytes) : nullptr;
+	uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base + tab_bytes + state_bytes);
+	// pageable source: the runtime stages the copy before returning, so `tab` may die
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, tab.data(), nsurf*sizeof(cfmp_surf), hipMemcpyHostToDevice, stream));
+	if (coverage) {
+		// (the states too: a level's first decide step writes every field it later reads, dir included)
+		HIP_TRY(ctx, hipMemsetAsync(base + tab_bytes, 0, state_bytes + cnt_bytes, stream));
+		float* d_plane = static_cast<float*>(ctx->d_src);
+		const float s_min = 0.25f, s_max = 4.0f;
+		MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_gather(d_tab, (uint32_t)nsurf, (uint32_t)nlev, (uint32_t)wg, t, 1.0f,
+			s_min, s_max, 3u, CFMP_SLOTS, d_plane, d_cnt, stream));
+		MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_decide(d_tab, (uint32_t)nlev, 1, d_state, d_cnt, results_device, stream));
+		for (uint32_t pass = 0; pass < CFMP_SEARCH_PASSES; ++pass) {
+			MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_count(d_tab, (uint32_t)nlev, (uint32_t)wg_levels, t, d_state,
+				d_plane, d_cnt, stream));
+			MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_decide(d_tab, (uint32_t)nlev, 0, d_state, d_cnt, results_device,
+				stream));
+		}
+	}
+	MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_apply(d_tab, (uint32_t)nlev, (uint32_t)wg_levels, flags, d_state, stream));
 	return lease.done(!stream_);
 }
 

@@ -330,6 +330,7 @@ class Texture:
         self._mask = (True, True, True, True)
         self._rdo_stats = None
         self._rdo_target = None
+        self._mip_post: List[List[dict]] = []
 
     def initialize(self, dimension, width: int, height: int, depth: int = 0, mip_levels: int = 1,
                    color_space: ColorSpace = ColorSpace.Linear) -> bool:
@@ -465,8 +466,9 @@ class Texture:
                                       color_space=self._color_space, filter=int(filter))
         return dst.cpu().numpy()
 
-    def _chain_2d(self, base: np.ndarray, levels: int, filter) -> List[np.ndarray]:
-        """levels 1..levels-1 of one 2-D image, each from the one before"""
+    def _chain_2d(self, base: np.ndarray, levels: int, filter, post=None) -> List[np.ndarray]:
+        """levels 1..levels-1 of one 2-D image, each from the one before; post = (alpha_coverage, normalize): the
+        post-pass runs on the chain before it leaves the device"""
         import torch
         if levels <= 1:
             return []
@@ -477,6 +479,27 @@ class Texture:
         self._context().generate_mips_device(src.data_ptr(), api.pixel_type_of(host), w, h, host.strides[0],
                                              [d.data_ptr() for d in dsts], color_space=self._color_space,
                                              filter=int(filter))
+        if post is not None:
+            self._post_device(host, src, dsts, post)
+        return [d.cpu().numpy() for d in dsts]
+
+    def _post_device(self, host: np.ndarray, src, dsts, post):
+        """the mip post-pass on one chain's device buffers; its records join self._mip_post"""
+        import torch
+        res = torch.zeros((len(dsts), 4), dtype=torch.int32, device=src.device)
+        self._context().mip_post_device([src.data_ptr()], api.pixel_type_of(host), host.shape[1], host.shape[0],
+                                        host.strides[0], [[d.data_ptr() for d in dsts]], alpha_coverage=post[0],
+                                        normalize=post[1], results=res.data_ptr() if post[0] is not None else 0)
+        if post[0] is not None:
+            rec = res.cpu().numpy().view(api.MIP_POST_RESULT_DTYPE).reshape(-1)
+            self._mip_post.append([{k: r[k].item() for k in rec.dtype.names} for r in rec])
+
+    def _post_images(self, base: np.ndarray, images: Sequence[np.ndarray], post) -> List[np.ndarray]:
+        """the post-pass on levels that are on the host (a chain with custom mip images)"""
+        import torch
+        host, src = self._to_device(base)
+        dsts = [torch.from_numpy(np.ascontiguousarray(im, dtype=np.float32)).to(src.device) for im in images]
+        self._post_device(host, src, dsts, post)
         return [d.cpu().numpy() for d in dsts]
 
     def _level_3d(self, slices: Sequence[np.ndarray], filter) -> List[np.ndarray]:
@@ -501,7 +524,8 @@ class Texture:
         return [out[i] for i in range(d)]
 
     def generate_mipmaps(self, filter=api.ResizeFilter.CatmullRom, mip_levels: Optional[int] = None,
-                         custom_mip_images: Optional[Dict[Tuple[int, int, int], CustomMipImage]] = None) -> bool:
+                         custom_mip_images: Optional[Dict[Tuple[int, int, int], CustomMipImage]] = None,
+                         alpha_coverage: Optional[float] = None, normalize: Optional[str] = None) -> bool:
         """Texture::generateMipmaps(filter, mipLevels = allMipLevels, customMipImages)
         (Texture.cpp:1320-1514): every level from the previous one through Image::resize in linear
         space (3-D textures: also along the depth), on the GPU.  custom_mip_images maps
@@ -509,9 +533,25 @@ class Texture:
         MipReplacement.Once resumes the generated chain below it, Continue builds the lower levels
         from the replacement.  Box / Linear: the reference's in-tree arithmetic; Cubic, CatmullRom
         (the default, as in the reference) and BSpline: FreeImage's resampler restated (FreeImage is
-        absent: parity unpinned).  Generated levels are RGBAF (float32) images."""
+        absent: parity unpinned).  Generated levels are RGBAF (float32) images.
+
+        alpha_coverage = t (0 < t <= 1) and normalize = "unorm" / "snorm" run the mip post-pass
+        (Context.mip_post_device) on every surface's chain, custom mip images included, each against its own
+        level 0: every level's alpha scaled so that its share of texels with alpha >= t matches level 0's, and every
+        RGB renormalised as a normal ("unorm": create_normal_map's storage without KEEP_SIGN).  The pass scales alpha
+        alone -- premultiplied colour is out of scope, so run it on straight alpha.  mip_post_results() returns the
+        records.  3-D textures return False with either keyword: coverage of a volume is another definition.  With
+        both left at None nothing changes."""
         if not self._valid or self._textures:
             return False
+        post = None
+        if alpha_coverage is not None or normalize is not None:
+            if self._dim == Dimension.Dim3D or normalize not in (None, "unorm", "snorm"):
+                return False
+            if alpha_coverage is not None and not (0.0 < float(alpha_coverage) <= 1.0):
+                return False
+            post = (alpha_coverage, normalize)
+        self._mip_post = []
         if any(im is None for dep in self._images[0] for im in dep):
             return False
         custom = dict(custom_mip_images or {})
@@ -565,7 +605,7 @@ class Texture:
             for f in range(self._faces):
                 keys = [(f, mip, d) in custom for mip in range(1, levels)]
                 if not any(keys):
-                    for mip, im in enumerate(self._chain_2d(base[d][f], levels, filter), start=1):
+                    for mip, im in enumerate(self._chain_2d(base[d][f], levels, filter, post), start=1):
                         images[mip][d][f] = im
                     continue
                 prev = None
@@ -578,8 +618,17 @@ class Texture:
                         cur = self._resize(prev if prev is not None else images[mip - 1][d][f], mw, mh, filter)
                     prev = cur if restore else None
                     images[mip][d][f] = self._resize(_as_image(c.image), mw, mh, filter) if c is not None else cur
+                if post is not None and levels > 1:
+                    chain = [images[mip][d][f] for mip in range(1, levels)]
+                    for mip, im in enumerate(self._post_images(base[d][f], chain, post), start=1):
+                        images[mip][d][f] = im
         self._images = images
         return True
+
+    def mip_post_results(self):
+        """The records of the last generate_mipmaps(alpha_coverage=...): one list per surface in [depth][face] order,
+        one dict per generated level (scale, target, count_before, count_after); [] when coverage was not asked."""
+        return [list(r) for r in self._mip_post]
 
     # ---- conversion (Texture.cpp:1536-1561) ----------------------------------------------------
     def convert(self, format: Format, type: Type, quality: Quality = Quality.Normal,

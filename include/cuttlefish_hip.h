@@ -290,6 +290,64 @@ int cfhip_generate_mips_array_device(cfhip_ctx* ctx, const void* const* srcs, ui
 	int src_pixel_type, uint32_t width, uint32_t height, size_t src_pitch_bytes, int color_space,
 	int filter, void* const* dst_levels, uint32_t levels, void* stream);
 
+/* The repairs of a generated mip chain before it is encoded, on the chain where cfhip_generate_mips_array_device
+ * left it (same srcs / levels layout; levels[] are modified in place, level 0 is only read).
+ *
+ * CFHIP_MIP_POST_COVERAGE: alpha-tested textures thin out level by level, because every filter averages alpha.  Each
+ * level's alpha is scaled so that as many of its texels pass `alpha >= alpha_threshold` as of level 0's, in proportion.
+ *   alpha(x)        level 0: RGBA8 (float)(v / 255.0), RGBA16F half -> float, RGBA32F as stored; levels: as stored
+ *   count(L, s, t)  texels of L with fl32(alpha * s) >= t: one float32 multiply, one compare; NaN and negative alphas
+ *                   never count; 0 < t <= 1; non-decreasing in s > 0
+ *   C0, T_k         C0 = count(level 0, 1, t); T_k = (C0 * n_k + n_0 / 2) / n_0 in 64-bit integers, n = texels
+ *   scale of level k, with S_MIN = 0.25f, S_MAX = 4.0f, c1 = count(level k, 1, t), prev / next the adjacent float32:
+ *     1. c1 == T_k: s = 1
+ *     2. c1 <  T_k: u = the smallest float32 in (1, S_MAX] with count >= T_k and d = prev(u); no such u: S_MAX alone
+ *     3. c1 >  T_k: d = the largest float32 in [S_MIN, 1) with count <= T_k and u = next(d); no such d: S_MIN alone
+ *     4. of two candidates the one whose count is nearer to T_k, a tie to u (the larger count)
+ *     5. if the chosen candidate's count equals c1: s = 1
+ *   applied         s != 1: alpha = fminf(fl32(alpha * s), 1.0f); s == 1: no byte of the level changes; RGB untouched
+ * Premultiplied colour is out of scope: alpha alone is scaled, so run the pass on straight alpha.
+ *
+ * CFHIP_MIP_POST_NORMALIZE: every texel's RGB of every level renormalised, in double, alpha untouched.
+ *   x = (double)c with CFHIP_MIP_POST_SIGNED_NORMALS, else (double)c * 2.0 - 1.0 (Image::createNormalMap's storage
+ *   without KEEP_SIGN); len = sqrt((x*x + y*y) + z*z); len not finite or not > 0: the normal is (0, 0, 1), else x / len;
+ *   stored as (float)x, or (float)(x * 0.5 + 0.5).
+ * With both flags one pass over the levels applies both; the result equals the two flags in two calls.
+ *
+ *   results_device  layers * (levels_count - 1) records, [l * (levels_count - 1) + (k - 1)] for level k of layer l;
+ *                   required with COVERAGE, ignored otherwise
+ * All layers and levels share every launch: 15 with COVERAGE (1 gather, 7 decide, 6 count, 1 apply), 1 without, and
+ * nothing inside the call waits for the host.  levels[] entries are 16-byte aligned.  levels_count: 2 to the chain's
+ * length.  Every argument is checked before anything is enqueued; stream == NULL means the context's stream and the
+ * call synchronises.  Identical calls return identical bytes. */
+enum { CFHIP_MIP_POST_COVERAGE = 1, CFHIP_MIP_POST_NORMALIZE = 2, CFHIP_MIP_POST_SIGNED_NORMALS = 4 };
+typedef struct cfhip_mip_post_params {
+	uint32_t flags;
+	float alpha_threshold;
+} cfhip_mip_post_params;
+typedef struct cfhip_mip_post_result {
+	float scale;
+	uint32_t target;
+	uint32_t count_before;
+	uint32_t count_after;
+} cfhip_mip_post_result;
+int cfhip_mip_post_array_device(cfhip_ctx* ctx, const void* const* srcs, uint32_t layers, int src_pixel_type,
+	uint32_t width, uint32_t height, size_t src_pitch_bytes, void* const* levels, uint32_t levels_count,
+	const cfhip_mip_post_params* params, cfhip_mip_post_result* results_device, void* stream);
+
+/* The building block: counts_device[i] = count(surfaces[i], scale, threshold) as defined above, for `count` surfaces
+ * of any sizes and pixel types in one launch (users measure the coverage of decoded payloads with it).  pixels and
+ * pitch_bytes are aligned to a component of the pixel type; scale is positive and finite. */
+typedef struct cfhip_coverage_surface {
+	const void* pixels;
+	int32_t pixel_type;
+	uint32_t width;
+	uint32_t height;
+	size_t pitch_bytes;
+} cfhip_coverage_surface;
+int cfhip_alpha_coverage_device(cfhip_ctx* ctx, const cfhip_coverage_surface* surfaces, uint32_t count, float threshold,
+	float scale, uint32_t* counts_device, void* stream);
+
 /* One Image::resize on the GPU (lib/src/Image.cpp:1324-1511) -- what Texture::generateMipmaps calls
  * per level, and per custom mip image (Texture.cpp:1499-1503, any source size): src (any of the
  * three pixel types) -> dst, dst_width x dst_height tightly packed RGBA32F, in linear space as
@@ -1052,7 +1110,7 @@ int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* p
 	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final) or cfhip_image_ops_device call on
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass) or cfhip_alpha_coverage_device call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
