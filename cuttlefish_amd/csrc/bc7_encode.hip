@@ -404,6 +404,22 @@ __device__ unsigned long long cf_bc7_diag[CF_DIAG_N];
 #define CF_DIAG_COUNT(i, cond) do { } while (0)
 #endif
 
+typedef int cf_int4 __attribute__((ext_vector_type(4)));
+// The A operand of the matrix-pipe cross terms (assign_lsq_lane): texel (row r, column lane & 3) of block boff, bit 7 of
+// every byte flipped.  Zeros where the build does not use it.
+template <bool UNITW>
+__device__ __forceinline__ void arow_load(const uint32_t* tile, uint32_t boff, uint32_t (&arow)[4])
+{
+	arow[0] = arow[1] = arow[2] = arow[3] = 0u;
+	if (UNITW && (CF_BC7_KEYTRIMS & 1) && (CF_BC7_MFMADOT & 1)) {
+		uint32_t lane;
+		CF_FRESH_LANE(lane);
+#pragma unroll
+		for (uint32_t r = 0; r < 4u; ++r)
+			arow[r] = tile[boff + 4u*r + (lane & 3u)] ^ 0x80808080u;
+	}
+}
+
 struct LaneFit {
 	uint32_t q0, q1, pb, err;   // (the dequantised endpoints are an input of the assignment, not part of a result)
 	uint32_t w[4];          // weights per texel (bytes), 0 outside the subset
@@ -411,13 +427,21 @@ struct LaneFit {
 
 // NK: palette entries walked per lane -- 8, or 4 when no lane of the wave has more than 4 (index width 2, not mode 6):
 // entries 4..7 then carry the never-winning key and dropping them changes no maximum.
-template <bool UNITW, int NK = 8>
+// arow (CF_BC7_MFMADOT bit 1): the A operand of the matrix-pipe cross terms, words r = 0..3: texel (row r, column lane & 3)
+// of the lane's block xored with 0x80808080, loaded by the caller where the whole wave is on (arow_load); CBSZ: 3 in the
+// 32-lane layouts (one block per half-wavefront), 4 in the wide one.
+template <bool UNITW, int NK = 8, int CBSZ = 3>
 __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bool m6,
-	uint32_t khalf, uint32_t ib, const uint32_t (&yw)[2], uint32_t pp_sum, bool want_lsq, uint32_t fe0, uint32_t fe1,
+	uint32_t khalf, uint32_t ib, const uint32_t (&yw)[2], uint32_t pp_sum, bool want_lsq, uint32_t fe0, uint32_t fe1, const uint32_t (&arow)[4],
 	LaneFit& f, float (&nx0)[4], float (&nx1)[4], float (&hq)[3], bool& ok, uint32_t s01 = 0u, uint32_t s23 = 0u)   // s01, s23: want_lsq only
 {
 	// keys in minimum form (bc7_packed.h)
 	constexpr bool MINKEY = (CF_BC7_KEYTRIMS & 1) != 0;
+	// unit weights, minimum form: the weight in a full byte of the key (CF_BC7_MFMADOT, bc7_packed.h)
+	constexpr bool WBYTE = UNITW && MINKEY && (CF_BC7_MFMADOT & 4) != 0;
+	constexpr int WBITS = WBYTE ? 8 : 7;
+	// unit weights, minimum form: the cross terms of a texel row by one v_mfma_i32_4x4x4_16b_i8 per entry (bc7_packed.h)
+	constexpr bool MFMA = UNITW && MINKEY && (CF_BC7_MFMADOT & 1) != 0;
 	const uint32_t nk = m6 ? 8u : (1u << ib), kbase = m6 ? 8u*khalf : 0u;
 	const uint32_t e00 = ub(fe0, 0), e01 = ub(fe0, 1), e02 = ub(fe0, 2), e03 = ub(fe0, 3);
 	const uint32_t e10 = ub(fe1, 0), e11 = ub(fe1, 1), e12 = ub(fe1, 2), e13 = ub(fe1, 3);
@@ -435,7 +459,10 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 		w03 = wr[0];
 		w47 = NK == 8 ? wr[1] : 0u;
 	}
-	const PalLine line = pal_line(fe0, fe1);
+	// matrix pipe: the palette in raw channel order (the rotation is a swap of two bytes, its own inverse; the slots the
+	// fit does not code hold zeros in both endpoint words), so that the raw texel is the other operand
+	const uint32_t rsel = tx.rot == 0u ? 0x03020100u : (tx.rot == 1u ? 0x00020103u : (tx.rot == 2u ? 0x01020300u : 0x02030100u));
+	const PalLine line = MFMA ? pal_line(__builtin_amdgcn_perm(fe0, fe0, rsel), __builtin_amdgcn_perm(fe1, fe1, rsel)) : pal_line(fe0, fe1);
 #pragma unroll
 	for (int k = 0; k < NK; ++k) {
 		// entries 0..3 exist in every fit (an index has at least two bits)
@@ -449,7 +476,11 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 			// two channels per multiply; in difference form one multiply and one add per channel pair
 			pal[k] = (CF_BC7_FITTRIMS & 1) ? pal_at(line, w) : pal_word(fe0, fe1, w);
 			palh[k] = 0;
-			const int B = (int)((__builtin_amdgcn_udot4(pal[k], pal[k], 0u, false) << 7) | w);
+			int B = (int)((__builtin_amdgcn_udot4(pal[k], pal[k], 0u, false) << WBITS) | w);
+			if (MFMA) {
+				B = mfma_entry_base(B, __builtin_amdgcn_udot4(pal[k], 0x01010101u, 0u, false), WBITS + 1);
+				pal[k] ^= 0x80808080u;
+			}
 			base[k] = MINKEY ? (valid ? B : CF_BC7_NO_ENTRY) : (valid ? -B : -CF_BC7_NO_ENTRY);
 		} else {
 			const uint32_t c0 = (__umul24(iw, e00) + __umul24(w, e10) + 32u) >> 6;
@@ -472,8 +503,8 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 	}
 	// the minimum form's factor from a scalar register (a VOP3 instruction takes no literal), opaque so that the
 	// multiply is not turned back into a shift and a subtraction
-	int m256 = -256;
-	if (MINKEY) asm volatile("" : "+s"(m256));
+	int kfac = WBYTE ? -512 : -256;   // -F
+	if (MINKEY) asm volatile("" : "+s"(kfac));
 	uint32_t err = pp_sum;
 	uint32_t wp0 = 0, wp1 = 0, wp2 = 0, wp3 = 0;
 #pragma unroll 1
@@ -497,27 +528,47 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 				rawh[0] = ya.y; rawh[1] = ya.w; rawh[2] = yb.y; rawh[3] = yb.w;
 			}
 			const uint32_t mrow = (mask >> (4u*r)) & 15u;
-			uint32_t wrow = 0;
+			uint32_t wrow = 0, krow[4];
+			int bestm[4] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF};
+			if (MFMA) {
+				// C: 128 sum_c a_c of the row's four texels; D = dt - 128 sum_c b'_c for the four texels against entry k
+				cf_int4 cop;
+				cop.x = (int)__builtin_amdgcn_udot4(raw[0], 0x80808080u, 0u, false);
+				cop.y = (int)__builtin_amdgcn_udot4(raw[1], 0x80808080u, 0u, false);
+				cop.z = (int)__builtin_amdgcn_udot4(raw[2], 0x80808080u, 0u, false);
+				cop.w = (int)__builtin_amdgcn_udot4(raw[3], 0x80808080u, 0u, false);
+				const uint32_t aop = r2 == 0u ? (h == 0u ? arow[0] : arow[1]) : (h == 0u ? arow[2] : arow[3]);
+#pragma unroll
+				for (int k = 0; k < NK; ++k) {
+					const cf_int4 d = __builtin_amdgcn_mfma_i32_4x4x4i8((int)aop, (int)pal[k], cop, CBSZ, 0, 0);
+					const int v0 = key_min_form(d.x, kfac, base[k]), v1 = key_min_form(d.y, kfac, base[k]);
+					const int v2 = key_min_form(d.z, kfac, base[k]), v3 = key_min_form(d.w, kfac, base[k]);
+					bestm[0] = v0 < bestm[0] ? v0 : bestm[0]; bestm[1] = v1 < bestm[1] ? v1 : bestm[1];
+					bestm[2] = v2 < bestm[2] ? v2 : bestm[2]; bestm[3] = v3 < bestm[3] ? v3 : bestm[3];
+				}
+			}
 #pragma unroll
 			for (int j = 0; j < 4; ++j) {
 				uint32_t rawj = raw[j];
 				// one texel at a time: interleaving the 32 dot products of a row for ILP costs
 				// ~20 registers, and the kernel is issue-bound, not latency-bound
-				asm volatile("" : "+v"(rawj), "+v"(wrow));
-				const uint32_t p = UNITW ? texel<true>(tx, rawj) : 0u;
+				if (MFMA) { }
+				else if (WBYTE) asm volatile("" : "+v"(rawj));   // (the row's weights are gathered behind its four texels)
+				else asm volatile("" : "+v"(rawj), "+v"(wrow));
+				const uint32_t p = (UNITW && !MFMA) ? texel<true>(tx, rawj) : 0u;
 				uint32_t key;
 				{
-					int bestk = MINKEY ? 0x7FFFFFFF : -0x7FFFFFFF;
+					int bestk = MFMA ? bestm[j] : (MINKEY ? 0x7FFFFFFF : -0x7FFFFFFF);
 					const uint32_t prg = rawj, pba = rawh[j];
 #pragma unroll
-					for (int k = 0; k < NK; ++k) {
+					for (int k = 0; k < (MFMA ? 0 : NK); ++k) {
 						int dt;
 						if (UNITW)
 							dt = (int)__builtin_amdgcn_udot4(p, pal[k], 0u, false);
 						else
 							dt = (int)dot2_u16(pba, palh[k], dot2_u16(prg, pal[k], 0u));
 						if (MINKEY) {
-							const int v = key_min_form(dt, m256, base[k]);
+							const int v = key_min_form(dt, kfac, base[k]);
 							bestk = v < bestk ? v : bestk;
 						} else {
 							const int v = key_max_form(dt, base[k]);
@@ -530,13 +581,14 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 						const int other = (int)cf_xor1((uint32_t)bestk);
 						bestk = (m6 && (MINKEY ? other < bestk : other > bestk)) ? other : bestk;
 					}
-					key = (uint32_t)(MINKEY ? bestk : -bestk);   // 128 (sum w c^2 - 2 p.(w c)) + weight, two's complement
+					key = (uint32_t)(MINKEY ? bestk : -bestk);   // F/2 (sum w c^2 - 2 p.(w c)) + weight, two's complement; F = 256, or 512 with the weight in a full byte
 				}
 				key = ((mrow >> j) & 1u) ? key : 0u;
-				err += (uint32_t)((int)key >> 7);
-				wrow |= (key & 127u) << (8*j);
+				err += (uint32_t)((int)key >> WBITS);
+				if (WBYTE) krow[j] = key;
+				else wrow |= (key & 127u) << (8*j);
 			}
-			wpair[h] = wrow;
+			wpair[h] = WBYTE ? key_row_weights(krow[0], krow[1], krow[2], krow[3]) : wrow;
 		}
 		wp0 = wp2; wp1 = wp3; wp2 = wpair[0]; wp3 = wpair[1];
 	}
@@ -707,10 +759,15 @@ struct FitStats {
 // the rows.  NK: palette entries of the selector search
 // (assign_lsq_lane).  ITERS: refit rounds of the instance's quality level (one round is straight-line code: it asks
 // for no least-squares solution and its `live` is dead).
-template <bool UNITW, uint32_t ITERS, int NK = 8, bool GIVEN = false>
+// owner (CF_BC7_MFMADOT bit 1): the fit runs with the whole wave on, and a lane that has no fit walks it on whatever its role
+// row holds; `owner` is false there and its result is thrown away by the caller.  The invariant this rests on: inside
+// fit_lane and everything it calls, NO store (LDS or global) and NO table or LDS index derived from cb / ab / pbk / ib / mask
+// may be reached without `owner` unless it stays in range for any value (weight_row, inv_n, gsrc & 63 do by construction).
+// Today the only store is the geometry-cache write below, and it is guarded.
+template <bool UNITW, uint32_t ITERS, int NK = 8, bool GIVEN = false, int CBSZ = 3>
 __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, uint32_t khalf,
 	uint32_t cb, uint32_t ab, uint32_t pbk, uint32_t ib, const uint32_t (&wt)[4],
-	const uint32_t (&yw)[2], bool scalar, float frac, uint32_t* gbase, uint32_t gmode, uint32_t gsrc, const FitStats& gs, LaneFit& best)
+	const uint32_t (&yw)[2], bool scalar, float frac, uint32_t* gbase, uint32_t gmode, uint32_t gsrc, const FitStats& gs, bool owner, LaneFit& best)
 {
 	float axis[4], mean[4];
 	float tmin, tmax;
@@ -836,7 +893,7 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 		pp_sum = UNITW ? q00 + q11 + q22 + q33 : ycc_pp_sum(tx, mask, yw);
 		s01 = s[0] | (s[1] << 16);
 		s23 = s[2] | (s[3] << 16);
-		if (GIVEN ? gmode != 0u : gmode == 1u) {   // 1 or 3
+		if ((GIVEN ? gmode != 0u : gmode == 1u) && ((UNITW && (CF_BC7_KEYTRIMS & 1) && (CF_BC7_MFMADOT & 1)) ? owner : true)) {   // 1 or 3; owner: see the call (a lane without a fit stores nothing)
 			uint32_t lane;
 			CF_FRESH_LANE(lane);
 			uint32_t* gc = gbase + lane;
@@ -885,7 +942,10 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 	best.q0 = q.q0; best.q1 = q.q1; best.pb = q.pb;
 	bool live;
 	float hq[3];
-	assign_lsq_lane<UNITW, NK>(tx, mask, m6, khalf, G_IB, yw, pp_sum, ITERS > 0u, q.e0, q.e1, best, x0, x1, hq, live, s01, s23);
+	// (matrix pipe: the whole wave is on here, so the A operand is loaded where it is used)
+	uint32_t arow[4];
+	arow_load<UNITW>(tx.tile_, tx.boff, arow);
+	assign_lsq_lane<UNITW, NK, CBSZ>(tx, mask, m6, khalf, G_IB, yw, pp_sum, ITERS > 0u, q.e0, q.e1, arow, best, x0, x1, hq, live, s01, s23);
 	// (Highest's two rounds stay a loop: unrolled, the second copy of the search spills 12 vector registers)
 #pragma unroll 1
 	for (uint32_t r = 0; r < ITERS; ++r) {
@@ -904,7 +964,8 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 		}
 		if (!(CF_BC7_ABLATE & 8)) refit_window(x0, x1, hq, G_CB, G_AB, G_PBK, q);
 		cur.q0 = q.q0; cur.q1 = q.q1; cur.pb = q.pb;
-		assign_lsq_lane<UNITW, NK>(tx, mask, m6, khalf, G_IB, yw, pp_sum, r + 1u < ITERS, q.e0, q.e1, cur, x0, x1, hq, ok, s01, s23);
+		arow_load<UNITW>(tx.tile_, tx.boff, arow);
+		assign_lsq_lane<UNITW, NK, CBSZ>(tx, mask, m6, khalf, G_IB, yw, pp_sum, r + 1u < ITERS, q.e0, q.e1, arow, cur, x0, x1, hq, ok, s01, s23);
 		const bool better = live && cur.err < best.err;
 		if (better)
 			best = cur;
@@ -1739,13 +1800,22 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				__builtin_amdgcn_wave_barrier();   // read before any fit writes its geometry words
 				gmode = 3u;
 			}
-			if (active) {
+			// Matrix pipe: v_mfma takes a row's texels from lanes 32h + 0..3 and gives wrong results when lanes are switched off
+			// (tools/ubench/mfma_layout.hip), so the fit runs with the whole wave on whenever any lane has one.  A lane without
+			// a fit walks it on its role row's defaults, stores nothing (owner) and its result is cleared below.
+			constexpr bool wholewave = UNITW && (CF_BC7_KEYTRIMS & 1) && (CF_BC7_MFMADOT & 1);
+			if (wholewave ? __ballot(active) != 0ull : active) {
 				if (narrow)
-					fit_lane<UNITW, iters, 4>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
-						wv, yw, sca, frac, gbase, gmode, gsrc, gs, lf);
+					fit_lane<UNITW, iters, 4, false, WIDE ? 4 : 3>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
+						wv, yw, sca, frac, gbase, gmode, gsrc, gs, active, lf);
 				else
-					fit_lane<UNITW, iters, 8, given>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
-						wv, yw, sca, frac, gbase, gmode, gsrc, gs, lf);
+					fit_lane<UNITW, iters, 8, given, WIDE ? 4 : 3>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
+						wv, yw, sca, frac, gbase, gmode, gsrc, gs, active, lf);
+				if (wholewave && !active) {
+					lf.err = 0; lf.q0 = 0; lf.q1 = 0; lf.pb = 0;
+#pragma unroll
+					for (int k = 0; k < 4; ++k) lf.w[k] = 0;
+				}
 			}
 			CF_FRESH_LANE(lane);         // the roles below are computed again from here
 			if (sst) {
@@ -2069,10 +2139,12 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 					for (int j = 0; j < 4; ++j) f.w[j] = 0;
 					float x0[4], x1[4], hq[3];
 					bool okk;
+					uint32_t arow[4];
+					arow_load<UNITW>(tx.tile_, tx.boff, arow);   // (the whole wave is on here)
 					if (narrow)
-						assign_lsq_lane<UNITW, 4>(tx, g.mask, g.m6, L_HL & 1u, g.ib, yw, pp_sum, false, fe0, fe1, f, x0, x1, hq, okk);
+						assign_lsq_lane<UNITW, 4, WIDE ? 4 : 3>(tx, g.mask, g.m6, L_HL & 1u, g.ib, yw, pp_sum, false, fe0, fe1, arow, f, x0, x1, hq, okk);
 					else
-						assign_lsq_lane<UNITW>(tx, g.mask, g.m6, L_HL & 1u, g.ib, yw, pp_sum, false, fe0, fe1, f, x0, x1, hq, okk);
+						assign_lsq_lane<UNITW, 8, WIDE ? 4 : 3>(tx, g.mask, g.m6, L_HL & 1u, g.ib, yw, pp_sum, false, fe0, fe1, arow, f, x0, x1, hq, okk);
 					const uint32_t key = valid ? ((f.err << 4) | mv) : 0xFFFFFFFFu;
 					uint32_t fitmin = cf_row_min_u32(key);
 					if (g.m6) {

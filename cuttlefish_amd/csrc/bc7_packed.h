@@ -49,6 +49,46 @@
 CF_PK int key_max_form(int dt, int negB) { return (dt << 8) + negB; }
 CF_PK int key_min_form(int dt, int m256, int B) { return CF_PK_MUL24S(dt, m256) + B; }
 
+// A/B switch, a bit mask: forms of the unit-weight selector search around its keys (minimum form only).  0 builds the
+// parent's forms.  (Bit 2, the error from the raw key sum, stayed under the bar and is not in the tree: DESIGN.md section
+// 4.1, tenth step; profiles/mfma_dots_bc7_ab.txt.)
+//   1: the cross terms of a texel row against an entry by one v_mfma_i32_4x4x4_16b_i8 instead of four v_dot4_u32_u8
+//      (mfma_entry_base below); the fit then runs with the whole wave on, because the instruction needs the lanes that hold
+//      its A rows switched on
+//   4: the weight in a full byte, B = (cc << 8) | w and the key B - 512 dt: the four weights of a texel row are then the
+//      low bytes of four keys and leave them by byte permutes (key_row_weights) instead of a shift and an and-or per texel
+// Same payload either way.
+#ifndef CF_BC7_MFMADOT
+#define CF_BC7_MFMADOT 5
+#endif
+// With the weight in 8 bits below cc: cc = sum_c c^2 <= 4 * 255^2 < 2^18 and dt <= 4 * 255^2, so B < 2^26, 512 dt < 2^27 and
+// |key| = |256 (cc - 2 dt) + w| <= 256 * 260100 + 64 < 2^26; -512 and dt fit the 24-bit multiply; an entry that does not
+// exist has the key CF_BC7_NO_ENTRY - 512 dt > 2^29, above every real one.  The key's low byte is the weight (<= 64), its
+// error part key >> 8 (arithmetic), and a texel outside the subset has the key 0.
+
+// Cross terms on the matrix pipe (bit 1).  For texel bytes a_c, palette bytes b_c and a' = a ^ 0x80, b' = b ^ 0x80 read as
+// signed bytes (a' = a - 128): sum a_c b_c = sum a'_c b'_c + 128 sum a_c + 128 sum b'_c, for any bytes.  The instruction
+// returns D = sum a'b' + C with C = 128 sum_c a_c, so dt = D + 128 sum b' and the key B - F dt (F = 2^fbits: 256, or 512 with
+// the weight byte) is base' - F D with base' = B - 128 F (sb - 512), sb = sum_c b_c.  Ranges: D in [-65024, 325636], |D| < 2^19
+// and fits the 24-bit multiply; |base'| < 2^26 + 2^25 < 2^27 with F = 512 (< 2^26 with F = 256); F D < 2^28; an entry that
+// does not exist keeps CF_BC7_NO_ENTRY and its key CF_BC7_NO_ENTRY - F D stays inside 32 bits and above every real key.
+CF_PK int mfma_entry_base(int B, uint32_t sb, int fbits)
+{
+	return B + (int)(512u << (7 + fbits)) - (int)CF_PK_MUL24(sb, 1u << (7 + fbits));
+}
+
+// The low bytes of four keys as the bytes of one word (a key's low byte is its weight, 0 for a texel outside the subset).
+// Two byte permutes and an or on the device.
+CF_PK uint32_t key_row_weights(uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+	// (selector bytes 0..3 address the second operand, 4..7 the first, 0x0C gives a zero byte)
+	return __builtin_amdgcn_perm(k1, k0, 0x0C0C0400u) | __builtin_amdgcn_perm(k3, k2, 0x04000C0Cu);
+#else
+	return (k0 & 255u) | ((k1 & 255u) << 8) | ((k2 & 255u) << 16) | ((k3 & 255u) << 24);
+#endif
+}
+
 // Dequantise one t-bit code v < 2^t (t = 4..8) to a byte: (v << (8 - t)) | (v >> (2t - 8)).
 // v * (2^t + 1) holds v twice, t bits apart and without overlap; the shift drops what falls below the byte.
 CF_PK uint32_t dequant1(uint32_t v, uint32_t t)

@@ -139,6 +139,86 @@ __global__ void __launch_bounds__(256) k(uint32_t* out, uint32_t seed)
 	out[blockIdx.x*blockDim.x + threadIdx.x] = r;
 }
 
+// The matrix pipe beside the vector pipe: v_mfma_i32_4x4x4_16b_i8 (16 batches of 4x4x4 int8, cbsz:3 as the BC7 selector
+// search would issue it), four per loop trip, with FILL independent v_mad_i32_i24 / v_min3_i32 (alternating) behind
+// every MFMA and, with READ, four v_mad_i32_i24 that read its four result registers.  Builtins and plain C++ here, not
+// inline asm: the compiler then places the wait states an MFMA's result needs, as it would in the kernel (s_nop 4
+// between an MFMA and the first reader of its result, s_nop 0 between a vector instruction and the MFMA behind it).
+// A "group" in the output is one MFMA with its fillers and readers.
+typedef int cf_i4 __attribute__((ext_vector_type(4)));
+#define MFMA_ITER 1024
+
+template <int FILL, bool READ>
+__global__ void __launch_bounds__(256, 4) kmfma(uint32_t* out, uint32_t seed)
+{
+	cf_i4 acc[4];
+	int f[12], rd[4];
+#pragma unroll
+	for (int i = 0; i < 4; ++i) acc[i] = cf_i4{(int)seed + i, (int)threadIdx.x, i, 1};
+#pragma unroll
+	for (int i = 0; i < 12; ++i) f[i] = (int)(seed*7u + threadIdx.x + i);
+#pragma unroll
+	for (int i = 0; i < 4; ++i) rd[i] = i;
+	int a = (int)(seed*3u + 1u + threadIdx.x), b = (int)(seed ^ 0x5bd1e995u ^ threadIdx.x), c = (int)(seed & 0xFFFFu);
+	int sm = -256;
+	asm volatile("" : "+s"(sm), "+v"(a), "+v"(b), "+v"(c));
+	cf_i4 c0 = acc[0];
+	asm volatile("" : "+v"(c0.x), "+v"(c0.y), "+v"(c0.z), "+v"(c0.w));
+	for (int it = 0; it < MFMA_ITER; ++it) {
+#pragma unroll
+		for (int i = 0; i < 4; ++i) {
+			// C is not carried round the loop (the kernel's is a fresh operand per row), and the result is pinned to
+			// vector registers as the kernel holds it: an accumulation chain would be moved to the AGPR file
+			asm volatile("" : "+v"(a));   // (opaque per issue: the product is not loop-invariant to the compiler)
+			acc[i] = __builtin_amdgcn_mfma_i32_4x4x4i8(a, b, c0, 3, 0, 0);
+			asm volatile("" : "+v"(acc[i]));
+#pragma unroll
+			for (int j = 0; j < FILL; ++j) {
+				if (j & 1) { const int m = f[j] < b ? f[j] : b; f[j] = m < c ? m : c; }
+				else f[j] = __mul24(f[j], sm) + c;
+				asm volatile("" : "+v"(f[j]));
+			}
+			if (READ) {
+				rd[0] = __mul24(acc[i].x, sm) + rd[0]; rd[1] = __mul24(acc[i].y, sm) + rd[1];
+				rd[2] = __mul24(acc[i].z, sm) + rd[2]; rd[3] = __mul24(acc[i].w, sm) + rd[3];
+				asm volatile("" : "+v"(rd[0]), "+v"(rd[1]), "+v"(rd[2]), "+v"(rd[3]));
+			}
+		}
+	}
+	int r = 0;
+#pragma unroll
+	for (int i = 0; i < 4; ++i) r ^= acc[i].x ^ acc[i].y ^ acc[i].z ^ acc[i].w ^ rd[i];
+#pragma unroll
+	for (int i = 0; i < 12; ++i) r ^= f[i];
+	out[blockIdx.x*blockDim.x + threadIdx.x] = (uint32_t)r;
+}
+
+template <int FILL, bool READ>
+static void run_mfma(int waves_per_simd)
+{
+	int ncu = 0;
+	(void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, 0);
+	const int blocks = ncu*waves_per_simd;
+	uint32_t* out;
+	(void)hipMalloc(&out, (size_t)blocks*256*4);
+	hipEvent_t e0, e1;
+	(void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+	hipLaunchKernelGGL((kmfma<FILL, READ>), dim3(blocks), dim3(256), 0, 0, out, 12345u);
+	(void)hipDeviceSynchronize();
+	(void)hipEventRecord(e0);
+	for (int rep = 0; rep < 5; ++rep)
+		hipLaunchKernelGGL((kmfma<FILL, READ>), dim3(blocks), dim3(256), 0, 0, out, 12345u);
+	(void)hipEventRecord(e1);
+	(void)hipEventSynchronize(e1);
+	float ms; (void)hipEventElapsedTime(&ms, e0, e1);
+	ms /= 5.0f;
+	const double groups = (double)MFMA_ITER*4*waves_per_simd;   // (MFMA + its fillers and readers) per SIMD
+	const double ns = ms*1e6/groups;
+	printf("mfma_i32_4x4x4_i8 + %2d fill + %d readers  waves/SIMD %d  %7.3f ms  %6.2f ns/group/SIMD  = %5.2f cycles @2.4GHz\n",
+		FILL, READ ? 4 : 0, waves_per_simd, ms, ns, ns*2.4);
+	(void)hipFree(out);
+}
+
 template <int OP>
 static void run(const char* name, int waves_per_simd, int per_step = 1)   // per_step: instructions per chain step
 {
@@ -165,8 +245,17 @@ static void run(const char* name, int waves_per_simd, int per_step = 1)   // per
 	(void)hipFree(out);
 }
 
-int main()
+int main(int argc, char** argv)
 {
+	// "mfma" as the argument: the matrix-pipe rows alone, with the three vector rows they are compared with
+	const bool only_mfma = argc > 1 && argv[1][0] == 'm';
+	for (int w : {4, 8}) {
+		if (only_mfma) { run<2>("v_dot4_u32_u8", w);   run<49>("v_mad_i32_i24 sgpr", w);   run<12>("v_perm_b32", w); }
+		run_mfma<0, false>(w);  run_mfma<4, false>(w);  run_mfma<8, false>(w);  run_mfma<12, false>(w);
+		run_mfma<0, true>(w);   run_mfma<4, true>(w);   run_mfma<8, true>(w);   run_mfma<12, true>(w);
+	}
+	if (only_mfma)
+		return 0;
 	for (int w : {4, 8}) {
 		run<0>("v_add_u32", w);       run<20>("v_sub_u32", w);     run<22>("v_add3_u32", w);
 		run<5>("v_and_b32", w);       run<3>("v_lshlrev_b32", w);  run<4>("v_lshl_add_u32", w);
