@@ -147,7 +147,7 @@ constexpr cf_bc7_mask_table cf_bc7_make_masks()
 				m3 |= ((p3[p] >> (2u*x)) & 3u) == kf ? 1u << x : 0u;
 			t.m[(0u*64u + p)*4u + kf] = 0xFFFFu;
 			t.m[(1u*64u + p)*4u + kf] = 0xFFFFu;
-			// (a fit index past the subsets belongs to an idle lane; fit_geo gave such a lane subset 1's texels)
+			// (a fit index past the subsets belongs to an idle lane; the id ladder before this table gave such a lane subset 1's texels)
 			t.m[(2u*64u + p)*4u + kf] = (uint16_t)(kf ? p2[p] : ~p2[p] & 0xFFFFu);
 			t.m[(3u*64u + p)*4u + kf] = (uint16_t)m3;
 		}

@@ -31,7 +31,9 @@
 //   * all error arithmetic is integer; a lane keeps (error, id) in registers and its best
 //     candidate's fields in its LDS column; group argmin on (error, id); the whole group then
 //     bit-packs the winner (one bit field per lane, OR-reduced), written out coalesced via LDS.
-//   * no MFMA: integer/float search (roofline in DESIGN.md section 4).
+//   * the search is integer and float VALU work (roofline in DESIGN.md section 4) with one use of the matrix pipe: under unit
+//     weights the selector search takes the cross terms of a row of four texels against a palette entry from one
+//     v_mfma_i32_4x4x4_16b_i8, for which the fit runs with the whole wave on; the perceptual metric's are v_dot2_u32_u16 pairs.
 //
 // Candidate ids and every float operation order are identical to the CPU oracle
 // (oracle/bc7_encode.c), so the payload is byte-identical to it.
@@ -136,9 +138,6 @@ __device__ __forceinline__ void cand_store(uint32_t* slot, const Cand& c)
 		slot[(11 + k)*CF_WG_THREADS] = c.w2[k];
 	}
 }
-// 1.0f/x where x's range is known by construction, and where it comes out of the power iteration (bc7_rcp.h)
-__device__ __forceinline__ float rcp_ranged(float x) { return (CF_BC7_KEYTRIMS & 2) ? cf_rcp_ranged(x) : 1.0f/x; }
-__device__ __forceinline__ float rcp_tested(float x) { return (CF_BC7_KEYTRIMS & 2) ? cf_rcp_tested(x) : 1.0f/x; }
 
 __device__ __forceinline__ uint32_t ub(uint32_t v, int c) { return (v >> (8*c)) & 255u; }
 __device__ __forceinline__ float fb(uint32_t v, int c) { return (float)((v >> (8*c)) & 255u); }
@@ -149,14 +148,6 @@ __device__ __forceinline__ float fb(uint32_t v, int c) { return (float)((v >> (8
 __device__ __forceinline__ float clamp255(float x)
 {
 	return __builtin_amdgcn_fmed3f(x, 0.0f, 255.0f);
-}
-
-// BC7 interpolation weight k of an ib-bit index: ((k*64 + d/2)/d), d = 2^ib - 1
-__device__ __forceinline__ uint32_t bc7_weight(uint32_t ib, uint32_t k)
-{
-	const uint32_t d = (1u << ib) - 1u;
-	const uint32_t mg = ib == 2u ? 21846u : (ib == 3u ? 9363u : 4370u);
-	return __umul24(k*64u + (d >> 1), mg) >> 16;
 }
 
 // 1/n of a subset of n = 1..16 texels: the correctly rounded quotients as literals, the same floats as the
@@ -366,26 +357,11 @@ __device__ __forceinline__ uint32_t ycc_pp_sum(const Tex& tx, uint32_t mask, con
 	return pp;
 }
 
-// Timing-ablation switches for tools/ab_bench.sh (never set in the product build).
-//   64: the pack is a trivial store of the winner's id and lane (what the bit-packing costs)
-//  128: the starts trip and the perturbation pass take a constant geometry (mode 6) instead of decoding their
-//       candidate's (what the decode costs; the fits then run on other arguments, so only the levels' difference
-//       to the parent says something)
+// Timing-ablation switches for tools/ab_build.sh (never set in the product build; every bit changes the payload):
+//    1: stream fits of mode 6 and the two-plane modes only    2: no two-plane fits    4: one block per wave at every level
+//    8: no refit_window   16: no starts trips   32: no perturbation rounds
 #ifndef CF_BC7_ABLATE
 #define CF_BC7_ABLATE 0
-#endif
-// A/B switch: 0 decodes a stored candidate from its id (fit_geo, geo_src: the ladders) instead of reading the candidate
-// word its leader stored (bc7_cand.h).  Same payload either way.
-#ifndef CF_BC7_CANDW
-#define CF_BC7_CANDW 1
-#endif
-// A/B switch, a bit mask: what the selector search does before it walks the texels.  0 builds the parent's forms.
-//   1: the unit-weight palette in difference form (pal_line once per assignment, pal_at per entry: bc7_packed.h)
-//   2: the entries' weights as bytes of two table words loaded once per assignment, instead of arithmetic on ib per
-//      entry; entries 0..3 exist in every fit, so only entries 4..7 keep a validity select
-// Same payload either way.
-#ifndef CF_BC7_FITTRIMS
-#define CF_BC7_FITTRIMS 3
 #endif
 
 // Diagnostic counters (never set in the product build): per wave pass, how often the starts trip reads the
@@ -406,12 +382,12 @@ __device__ unsigned long long cf_bc7_diag[CF_DIAG_N];
 
 typedef int cf_int4 __attribute__((ext_vector_type(4)));
 // The A operand of the matrix-pipe cross terms (assign_lsq_lane): texel (row r, column lane & 3) of block boff, bit 7 of
-// every byte flipped.  Zeros where the build does not use it.
+// every byte flipped.  Zeros under the perceptual metric, whose search does not use it.
 template <bool UNITW>
 __device__ __forceinline__ void arow_load(const uint32_t* tile, uint32_t boff, uint32_t (&arow)[4])
 {
 	arow[0] = arow[1] = arow[2] = arow[3] = 0u;
-	if (UNITW && (CF_BC7_KEYTRIMS & 1) && (CF_BC7_MFMADOT & 1)) {
+	if (UNITW) {
 		uint32_t lane;
 		CF_FRESH_LANE(lane);
 #pragma unroll
@@ -426,8 +402,8 @@ struct LaneFit {
 };
 
 // NK: palette entries walked per lane -- 8, or 4 when no lane of the wave has more than 4 (index width 2, not mode 6):
-// entries 4..7 then carry the never-winning key and dropping them changes no maximum.
-// arow (CF_BC7_MFMADOT bit 1): the A operand of the matrix-pipe cross terms, words r = 0..3: texel (row r, column lane & 3)
+// entries 4..7 then carry the never-winning key and dropping them changes no minimum.
+// arow (unit weights): the A operand of the matrix-pipe cross terms, words r = 0..3: texel (row r, column lane & 3)
 // of the lane's block xored with 0x80808080, loaded by the caller where the whole wave is on (arow_load); CBSZ: 3 in the
 // 32-lane layouts (one block per half-wavefront), 4 in the wide one.
 template <bool UNITW, int NK = 8, int CBSZ = 3>
@@ -435,53 +411,46 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 	uint32_t khalf, uint32_t ib, const uint32_t (&yw)[2], uint32_t pp_sum, bool want_lsq, uint32_t fe0, uint32_t fe1, const uint32_t (&arow)[4],
 	LaneFit& f, float (&nx0)[4], float (&nx1)[4], float (&hq)[3], bool& ok, uint32_t s01 = 0u, uint32_t s23 = 0u)   // s01, s23: want_lsq only
 {
-	// keys in minimum form (bc7_packed.h)
-	constexpr bool MINKEY = (CF_BC7_KEYTRIMS & 1) != 0;
-	// unit weights, minimum form: the weight in a full byte of the key (CF_BC7_MFMADOT, bc7_packed.h)
-	constexpr bool WBYTE = UNITW && MINKEY && (CF_BC7_MFMADOT & 4) != 0;
-	constexpr int WBITS = WBYTE ? 8 : 7;
-	// unit weights, minimum form: the cross terms of a texel row by one v_mfma_i32_4x4x4_16b_i8 per entry (bc7_packed.h)
-	constexpr bool MFMA = UNITW && MINKEY && (CF_BC7_MFMADOT & 1) != 0;
-	const uint32_t nk = m6 ? 8u : (1u << ib), kbase = m6 ? 8u*khalf : 0u;
+	// the weight's bits below the error part of a key (bc7_packed.h): a full byte under unit weights, where a row's weights
+	// leave their keys by byte permutes; 7 under the perceptual metric
+	constexpr int WBITS = UNITW ? 8 : 7;
+	const uint32_t nk = m6 ? 8u : (1u << ib);
 	const uint32_t e00 = ub(fe0, 0), e01 = ub(fe0, 1), e02 = ub(fe0, 2), e03 = ub(fe0, 3);
 	const uint32_t e10 = ub(fe1, 0), e11 = ub(fe1, 1), e12 = ub(fe1, 2), e13 = ub(fe1, 3);
 	// straight-line palette: entries past this lane's 2^ib get a key that never wins.
-	// A texel's key is 128 (sum_c w_c c_k^2 - 2 sum_c p_c (w_c c_k)) + weight_k, minimised over k
-	// (CF_BC7_KEYTRIMS bit 1; the parent's form maximises its negation); sum_c w_c p_c^2 is added once per subset (pp_sum).  Unit weights: the
-	// cross term is one v_dot4(p, c_k).  Perceptual metric: the palette entry goes to (Y, Cr, Cb, A),
-	// its weighted form is two words of 16-bit pairs, the cross term two v_dot2_u32_u16.
+	// A texel's key is F/2 (sum_c w_c c_k^2 - 2 sum_c p_c (w_c c_k)) + weight_k with F = 2^(WBITS + 1), minimised over k;
+	// sum_c w_c p_c^2 is added once per subset (pp_sum).  Unit weights: the cross terms of a row of four texels against
+	// entry k are one v_mfma_i32_4x4x4_16b_i8 (bc7_packed.h: mfma_entry_base).  Perceptual metric: the palette entry goes
+	// to (Y, Cr, Cb, A), its weighted form is two words of 16-bit pairs, the cross term two v_dot2_u32_u16.
 	uint32_t pal[8], palh[8];
 	int base[8];
 	// what every entry of this fit shares: the row of weight bytes and the palette's line (bc7_packed.h)
+	// (the zeros are dead, but the code generated for the refit sums below depends on their presence: a different order
+	// of two v_mov_b32 and an unfused shift-add without them)
 	uint32_t w03 = 0, w47 = 0;
-	if (CF_BC7_FITTRIMS & 2) {
-		const uint32_t* wr = k_bc7_weights.w[weight_row(m6, khalf, ib)];
-		w03 = wr[0];
-		w47 = NK == 8 ? wr[1] : 0u;
-	}
+	const uint32_t* wr = k_bc7_weights.w[weight_row(m6, khalf, ib)];
+	w03 = wr[0];
+	w47 = NK == 8 ? wr[1] : 0u;
 	// matrix pipe: the palette in raw channel order (the rotation is a swap of two bytes, its own inverse; the slots the
 	// fit does not code hold zeros in both endpoint words), so that the raw texel is the other operand
 	const uint32_t rsel = tx.rot == 0u ? 0x03020100u : (tx.rot == 1u ? 0x00020103u : (tx.rot == 2u ? 0x01020300u : 0x02030100u));
-	const PalLine line = MFMA ? pal_line(__builtin_amdgcn_perm(fe0, fe0, rsel), __builtin_amdgcn_perm(fe1, fe1, rsel)) : pal_line(fe0, fe1);
+	const PalLine line = pal_line(__builtin_amdgcn_perm(fe0, fe0, rsel), __builtin_amdgcn_perm(fe1, fe1, rsel));   // (unit weights only)
 #pragma unroll
 	for (int k = 0; k < NK; ++k) {
 		// entries 0..3 exist in every fit (an index has at least two bits)
-		const bool valid = ((CF_BC7_FITTRIMS & 2) && k < 4) || (uint32_t)k < nk;
+		const bool valid = k < 4 || (uint32_t)k < nk;
 		// an entry past 2^ib interpolates with weight 0: its colour stays a byte vector, so the
 		// dot products below stay in range and its constant keeps it from ever winning
-		const uint32_t w = (CF_BC7_FITTRIMS & 2) ? weight_at(w03, w47, (uint32_t)k)
-			: bc7_weight(ib, valid ? kbase + (uint32_t)k : 0u);
+		const uint32_t w = weight_at(w03, w47, (uint32_t)k);
 		const uint32_t iw = 64u - w;
 		if (UNITW) {
-			// two channels per multiply; in difference form one multiply and one add per channel pair
-			pal[k] = (CF_BC7_FITTRIMS & 1) ? pal_at(line, w) : pal_word(fe0, fe1, w);
+			// the palette in difference form: one multiply and one add per channel pair
+			pal[k] = pal_at(line, w);
 			palh[k] = 0;
-			int B = (int)((__builtin_amdgcn_udot4(pal[k], pal[k], 0u, false) << WBITS) | w);
-			if (MFMA) {
-				B = mfma_entry_base(B, __builtin_amdgcn_udot4(pal[k], 0x01010101u, 0u, false), WBITS + 1);
-				pal[k] ^= 0x80808080u;
-			}
-			base[k] = MINKEY ? (valid ? B : CF_BC7_NO_ENTRY) : (valid ? -B : -CF_BC7_NO_ENTRY);
+			const int B = mfma_entry_base((int)((__builtin_amdgcn_udot4(pal[k], pal[k], 0u, false) << WBITS) | w),
+				__builtin_amdgcn_udot4(pal[k], 0x01010101u, 0u, false), WBITS + 1);
+			pal[k] ^= 0x80808080u;
+			base[k] = valid ? B : CF_BC7_NO_ENTRY;
 		} else {
 			const uint32_t c0 = (__umul24(iw, e00) + __umul24(w, e10) + 32u) >> 6;
 			const uint32_t c1 = (__umul24(iw, e01) + __umul24(w, e11) + 32u) >> 6;
@@ -494,17 +463,16 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 			pal[k] = pk_mul_u16(qrg, yw[0]);
 			palh[k] = pk_mul_u16(qba, yw[1]);
 			const uint32_t qq = dot2_u16(pal[k], qrg, dot2_u16(palh[k], qba, 0u));   // <= 3.7e6
-			const int B = (int)((qq << 7) | w);
-			base[k] = MINKEY ? (valid ? B : CF_BC7_NO_ENTRY) : (valid ? -B : -CF_BC7_NO_ENTRY);
+			const int B = (int)((qq << WBITS) | w);
+			base[k] = valid ? B : CF_BC7_NO_ENTRY;
 		}
-		// hide what base is: the maximum form's "(dt << 8) + base" then stays ONE v_lshl_add_u32 per entry and texel
-		// (the compiler otherwise emits a shift and a subtract for half of them), the minimum form's ONE v_mad_i32_i24
+		// hide what base is: "base - F dt" then stays ONE v_mad_i32_i24 per entry and texel
 		asm volatile("" : "+v"(base[k]));
 	}
-	// the minimum form's factor from a scalar register (a VOP3 instruction takes no literal), opaque so that the
+	// the key's factor -F from a scalar register (a VOP3 instruction takes no literal), opaque so that the
 	// multiply is not turned back into a shift and a subtraction
-	int kfac = WBYTE ? -512 : -256;   // -F
-	if (MINKEY) asm volatile("" : "+s"(kfac));
+	int kfac = -(2 << WBITS);
+	asm volatile("" : "+s"(kfac));
 	uint32_t err = pp_sum;
 	uint32_t wp0 = 0, wp1 = 0, wp2 = 0, wp3 = 0;
 #pragma unroll 1
@@ -530,7 +498,7 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 			const uint32_t mrow = (mask >> (4u*r)) & 15u;
 			uint32_t wrow = 0, krow[4];
 			int bestm[4] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF};
-			if (MFMA) {
+			if (UNITW) {
 				// C: 128 sum_c a_c of the row's four texels; D = dt - 128 sum_c b'_c for the four texels against entry k
 				cf_int4 cop;
 				cop.x = (int)__builtin_amdgcn_udot4(raw[0], 0x80808080u, 0u, false);
@@ -552,43 +520,31 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 				uint32_t rawj = raw[j];
 				// one texel at a time: interleaving the 32 dot products of a row for ILP costs
 				// ~20 registers, and the kernel is issue-bound, not latency-bound
-				if (MFMA) { }
-				else if (WBYTE) asm volatile("" : "+v"(rawj));   // (the row's weights are gathered behind its four texels)
-				else asm volatile("" : "+v"(rawj), "+v"(wrow));
-				const uint32_t p = (UNITW && !MFMA) ? texel<true>(tx, rawj) : 0u;
+				if (!UNITW) asm volatile("" : "+v"(rawj), "+v"(wrow));
 				uint32_t key;
 				{
-					int bestk = MFMA ? bestm[j] : (MINKEY ? 0x7FFFFFFF : -0x7FFFFFFF);
+					int bestk = bestm[j];
 					const uint32_t prg = rawj, pba = rawh[j];
 #pragma unroll
-					for (int k = 0; k < (MFMA ? 0 : NK); ++k) {
-						int dt;
-						if (UNITW)
-							dt = (int)__builtin_amdgcn_udot4(p, pal[k], 0u, false);
-						else
-							dt = (int)dot2_u16(pba, palh[k], dot2_u16(prg, pal[k], 0u));
-						if (MINKEY) {
-							const int v = key_min_form(dt, kfac, base[k]);
-							bestk = v < bestk ? v : bestk;
-						} else {
-							const int v = key_max_form(dt, base[k]);
-							bestk = v > bestk ? v : bestk;
-						}
+					for (int k = 0; k < (UNITW ? 0 : NK); ++k) {
+						const int dt = (int)dot2_u16(pba, palh[k], dot2_u16(prg, pal[k], 0u));
+						const int v = key_min_form(dt, kfac, base[k]);
+						bestk = v < bestk ? v : bestk;
 					}
 					// mode 6: the other palette half lives in the neighbouring lane (the 4-entry search is entered
 					// only when no active lane of the wave is a mode-6 lane: it has no exchange at all)
 					if (NK == 8) {
 						const int other = (int)cf_xor1((uint32_t)bestk);
-						bestk = (m6 && (MINKEY ? other < bestk : other > bestk)) ? other : bestk;
+						bestk = (m6 && other < bestk) ? other : bestk;
 					}
-					key = (uint32_t)(MINKEY ? bestk : -bestk);   // F/2 (sum w c^2 - 2 p.(w c)) + weight, two's complement; F = 256, or 512 with the weight in a full byte
+					key = (uint32_t)bestk;   // F/2 (sum w c^2 - 2 p.(w c)) + weight, two's complement
 				}
 				key = ((mrow >> j) & 1u) ? key : 0u;
 				err += (uint32_t)((int)key >> WBITS);
-				if (WBYTE) krow[j] = key;
+				if (UNITW) krow[j] = key;
 				else wrow |= (key & 127u) << (8*j);
 			}
-			wpair[h] = WBYTE ? key_row_weights(krow[0], krow[1], krow[2], krow[3]) : wrow;
+			wpair[h] = UNITW ? key_row_weights(krow[0], krow[1], krow[2], krow[3]) : wrow;
 		}
 		wp0 = wp2; wp1 = wp3; wp2 = wpair[0]; wp3 = wpair[1];
 	}
@@ -623,7 +579,7 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 	}
 	const int det = (int)__umul24((uint32_t)__builtin_popcount(mask), C) - (int)__umul24(S, S);
 	ok = det > 0;
-	const float inv = rcp_ranged(64.0f*(float)(det > 0 ? det : 1));
+	const float inv = cf_rcp_ranged(64.0f*(float)(det > 0 ? det : 1));
 	const float fA = (float)A, fB = (float)B, fC = (float)C;
 #pragma unroll
 	for (int c = 0; c < 4; ++c) {
@@ -729,18 +685,6 @@ __device__ __forceinline__ void refit_window(const float (&xu0)[4], const float 
 #define CF_BC7_GEO_NONE 0xFFFFFFFFu
 __device__ __forceinline__ uint32_t geo_tag(uint32_t id, uint32_t fi) { return id*4u + (id == 0u ? 0u : fi); }
 
-// Lane that ran fit fi of the candidate whose leader (first-fit lane) is wl, in the stream trips' layouts
-// (a guess checked by the tag: a wrong one only costs the fall-back to the full fit).
-__device__ __forceinline__ uint32_t geo_src(uint32_t id, uint32_t fi, uint32_t wl, bool lay32)
-{
-	uint32_t s = wl + fi;                                          // partitions: the subsets in consecutive lanes
-	if (id == 0u) s = wl;                                          // mode 6: both palette halves fit the same geometry
-	else if (id < 13u) s = fi ? wl + (lay32 ? (id < 5u ? 4u : 1u) : 12u) : wl;   // modes 5 / 4: scalar plane s2off lanes up
-	else if (lay32 && id >= 192u && id < 320u && fi == 2u)        // 32-lane second pass: subset 2 of slot s in lane s
-		s = (wl & 32u) + (((wl & 31u) - 11u) >> 1);
-	return s & 63u;
-}
-
 // What part A's row loop produces, for a fit whose integer statistics are known beforehand: the packed moments of its
 // texels in its own (rotated, masked) channel slots (bc7_packed.h) and the extremes lo | hi << 8 of the rotated alpha
 // over the block.
@@ -759,7 +703,7 @@ struct FitStats {
 // the rows.  NK: palette entries of the selector search
 // (assign_lsq_lane).  ITERS: refit rounds of the instance's quality level (one round is straight-line code: it asks
 // for no least-squares solution and its `live` is dead).
-// owner (CF_BC7_MFMADOT bit 1): the fit runs with the whole wave on, and a lane that has no fit walks it on whatever its role
+// owner (unit weights, whose selector search is on the matrix pipe): the fit runs with the whole wave on, and a lane that has no fit walks it on whatever its role
 // row holds; `owner` is false there and its result is thrown away by the caller.  The invariant this rests on: inside
 // fit_lane and everything it calls, NO store (LDS or global) and NO table or LDS index derived from cb / ab / pbk / ib / mask
 // may be reached without `owner` unless it stays in range for any value (weight_row, inv_n, gsrc & 63 do by construction).
@@ -855,13 +799,13 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 #pragma unroll
 		for (int c = 0; c < 4; ++c) axis[c] = 0.0f;
 		if (mx > 0.0f) {
-			const float im = rcp_tested(mx);
+			const float im = cf_rcp_tested(mx);
 			v0 = v0*im; v1 = v1*im; v2 = v2*im; v3 = v3*im;
 			float l2 = v0*v0;
 			l2 = fmaf(v1, v1, l2);
 			l2 = fmaf(v2, v2, l2);
 			l2 = fmaf(v3, v3, l2);
-			const float is = rcp_ranged(sqrtf(l2));
+			const float is = cf_rcp_ranged(sqrtf(l2));
 			axis[0] = v0*is; axis[1] = v1*is; axis[2] = v2*is; axis[3] = v3*is;
 		}
 
@@ -893,7 +837,7 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 		pp_sum = UNITW ? q00 + q11 + q22 + q33 : ycc_pp_sum(tx, mask, yw);
 		s01 = s[0] | (s[1] << 16);
 		s23 = s[2] | (s[3] << 16);
-		if ((GIVEN ? gmode != 0u : gmode == 1u) && ((UNITW && (CF_BC7_KEYTRIMS & 1) && (CF_BC7_MFMADOT & 1)) ? owner : true)) {   // 1 or 3; owner: see the call (a lane without a fit stores nothing)
+		if ((GIVEN ? gmode != 0u : gmode == 1u) && (UNITW ? owner : true)) {   // 1 or 3; owner: see the call (a lane without a fit stores nothing)
 			uint32_t lane;
 			CF_FRESH_LANE(lane);
 			uint32_t* gc = gbase + lane;
@@ -993,11 +937,6 @@ __device__ __forceinline__ uint4 pack_block_group(const uint32_t* wcol, uint32_t
 	bool pair)
 {
 	const uint32_t h = lane >> 5, hl = pair ? (lane & 31u) : lane, hbase = pair ? (lane & 32u) : 0u;
-	if (CF_BC7_ABLATE & 64) {
-		uint4 r;
-		r.x = id; r.y = wcol[0]; r.z = wcol[CF_WG_THREADS]; r.w = h;
-		return r;
-	}
 	uint32_t mode, part = 0, rot = 0, isel = 0;
 	if (id == 0u) mode = 6;
 	else if (id < 5u) { mode = 5; rot = id - 1u; }
@@ -1249,7 +1188,7 @@ __device__ __forceinline__ float subset_residual(const Moments& mo, uint32_t mas
 	float res = 0.0f;
 	along = 0.0f;
 	if (mx > 0.0f) {
-		const float im = rcp_tested(mx);
+		const float im = cf_rcp_tested(mx);
 		v0 = v0*im; v1 = v1*im; v2 = v2*im; v3 = A4 ? v3*im : 0.0f;
 		CF_MATVEC(w0, w1, w2, w3)
 		float num = v0*w0;
@@ -1260,7 +1199,7 @@ __device__ __forceinline__ float subset_residual(const Moments& mo, uint32_t mas
 		den = fmaf(v1, v1, den);
 		den = fmaf(v2, v2, den);
 		if (A4) den = fmaf(v3, v3, den);
-		const float lam = num*rcp_ranged(den);
+		const float lam = num*cf_rcp_ranged(den);
 		const float in = inv_n(n);
 		res = (tr - lam)*in;
 		res = res > 0.0f ? res : 0.0f;
@@ -1294,50 +1233,7 @@ struct FitGeo {
 	bool m6, planes45, sca;
 };
 
-__device__ __forceinline__ FitGeo fit_geo(uint32_t id, uint32_t kf)
-{
-	FitGeo g;
-	g.part = 0; g.rot = 0; g.isel = 0;
-	if (id == 0u) g.mode = 6;
-	else if (id < 5u) { g.mode = 5; g.rot = id - 1u; }
-	else if (id < 13u) { g.mode = 4; g.rot = (id - 5u) & 3u; g.isel = (id - 5u) >> 2; }
-	else if (id < 128u) { g.mode = 1; g.part = id - 64u; }
-	else if (id < 192u) { g.mode = 3; g.part = id - 128u; }
-	else if (id < 256u) { g.mode = 0; g.part = id - 192u; }
-	else if (id < 320u) { g.mode = 2; g.part = id - 256u; }
-	else { g.mode = 7; g.part = (id - 320u) & 63u; }
-	const uint32_t mode = g.mode;
-	g.ns = (0x21112323u >> (4u*mode)) & 15u;
-	g.m6 = mode == 6u;
-	g.planes45 = mode == 4u || mode == 5u;
-	g.nfits = g.planes45 ? 2u : g.ns;
-	g.sca = g.planes45 && kf == 1u;
-	g.mask = 0xFFFFu;
-	if (g.planes45) {
-		const uint32_t ibc = mode == 5u ? 2u : (g.isel ? 3u : 2u), iba = mode == 5u ? 2u : (g.isel ? 2u : 3u);
-		g.cb = g.sca ? 0u : (mode == 5u ? 7u : 5u);
-		g.ab = g.sca ? (mode == 5u ? 8u : 6u) : 0u;
-		g.ib = g.sca ? iba : ibc;
-		g.pbk = 0;
-		g.chm = g.sca ? 8u : 7u;
-	} else {
-		g.cb = (0x57757564u >> (4u*mode)) & 15u;
-		g.ab = (0x57860000u >> (4u*mode)) & 15u;
-		g.pbk = (0x11001021u >> (4u*mode)) & 15u;
-		g.ib = (0x24222233u >> (4u*mode)) & 15u;
-		g.chm = g.ab ? 15u : 7u;
-		if (g.ns == 2u) {
-			const uint32_t p2 = k_part2[g.part];
-			g.mask = kf ? p2 : (~p2 & 0xFFFFu);
-		} else if (g.ns == 3u) {
-			const uint32_t p3 = k_part3[g.part];
-			g.mask = part3_mask(p3, kf);
-		}
-	}
-	return g;
-}
-
-// The same geometry from what the candidate's leader stored with it: the candidate word (word 6 of its column,
+// It is read from what the candidate's leader stored with it: the candidate word (word 6 of its column,
 // bc7_cand.h) by bit-field extracts, the fit's texels by one table load.  The word of a column that holds no candidate is
 // whatever the word held before: every field is masked to its range, and the lanes that read it are idle.
 __device__ __forceinline__ FitGeo cand_geo(uint32_t cw, uint32_t id, uint32_t kf)
@@ -1354,19 +1250,19 @@ __device__ __forceinline__ FitGeo cand_geo(uint32_t cw, uint32_t id, uint32_t kf
 // Geometry of fit kf of the candidate stored in column wc
 __device__ __forceinline__ FitGeo column_geo(const uint32_t* wc, uint32_t id, uint32_t kf)
 {
-	if (CF_BC7_ABLATE & 128)
-		return fit_geo(0u, 0u);
-	return CF_BC7_CANDW ? cand_geo(wc[6*CF_WG_THREADS], id, kf) : fit_geo(id, kf);
+	return cand_geo(wc[6*CF_WG_THREADS], id, kf);
 }
 
-// geo_tag / geo_src of a candidate whose geometry is at hand: no id ladder
+// The geometry-cache tag of a candidate whose geometry is at hand (geo_tag(id, fi) without the compare on id)
 __device__ __forceinline__ uint32_t geo_tag(const FitGeo& g, uint32_t id, uint32_t fi) { return id*4u + (g.m6 ? 0u : fi); }
+// Lane that ran fit fi of the candidate whose leader (first-fit lane) is wl, in the stream trips' layouts
+// (a guess checked by the tag: a wrong one only costs the fall-back to the full fit).
 __device__ __forceinline__ uint32_t geo_src(const FitGeo& g, uint32_t fi, uint32_t wl, bool lay32)
 {
-	uint32_t s = wl + fi;
-	if (g.m6) s = wl;
-	else if (g.planes45) s = fi ? wl + (lay32 ? (g.mode == 5u ? 4u : 1u) : 12u) : wl;
-	else if (lay32 && g.ns == 3u && fi == 2u)
+	uint32_t s = wl + fi;                                          // partitions: the subsets in consecutive lanes
+	if (g.m6) s = wl;                                              // mode 6: both palette halves fit the same geometry
+	else if (g.planes45) s = fi ? wl + (lay32 ? (g.mode == 5u ? 4u : 1u) : 12u) : wl;   // modes 5 / 4: scalar plane s2off lanes up
+	else if (lay32 && g.ns == 3u && fi == 2u)                      // 32-lane second pass: subset 2 of slot s in lane s
 		s = (wl & 32u) + (((wl & 31u) - 11u) >> 1);
 	return s & 63u;
 }
@@ -1682,7 +1578,7 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				const uint32_t wl = TOP_LANE(k & 7u);
 				const uint32_t id = cbase[wl + 19*CF_WG_THREADS], cerr = cbase[wl + 18*CF_WG_THREADS];
 				// (three subsets, from the candidate word: ids 192 .. 319)
-				const bool n3 = lay32 && (CF_BC7_CANDW ? CF_CAND_NS(cbase[wl + 6*CF_WG_THREADS]) == 3u : id >= 192u && id < 320u);
+				const bool n3 = lay32 && CF_CAND_NS(cbase[wl + 6*CF_WG_THREADS]) == 3u;
 				const uint32_t j8 = L_HL & 7u;
 				const uint32_t v = lay32 ? (n3 ? (j8 >= 3u ? 1u : 0u) : (L_HL >> 1) & 3u) : (lane >> 2) & 3u;
 				const uint32_t fi = lay32 ? (n3 ? (j8 >= 6u ? 3u : j8 - 3u*v) : (L_HL & 1u)) : (lane & 3u);
@@ -1695,8 +1591,8 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				frac = v == 0u ? 0.0f : (v == 1u ? -1.0f/16.0f : (v == 2u ? 1.0f/8.0f : 3.0f/16.0f));
 				// parts A and B of the fit come from the cache when every active lane of the wave finds its fit there
 				// (in its own block's half); otherwise the whole wave computes them
-				gsrc = CF_BC7_CANDW ? geo_src(g, fi, wl, lay32) : geo_src(id, fi, wl, lay32);
-				const bool ghit = gbase[gsrc + 12*CF_WG_THREADS] == (CF_BC7_CANDW ? geo_tag(g, id, fi) : geo_tag(id, fi)) && (!lay32 || ((gsrc ^ wl) & 32u) == 0u);
+				gsrc = geo_src(g, fi, wl, lay32);
+				const bool ghit = gbase[gsrc + 12*CF_WG_THREADS] == geo_tag(g, id, fi) && (!lay32 || ((gsrc ^ wl) & 32u) == 0u);
 				gmode = __ballot(active && !ghit) == 0ull ? 2u : 0u;
 				narrow = __ballot(active && (g.m6 || g.ib > 2u)) == 0ull;
 				CF_DIAG_COUNT(CF_DIAG_STARTS, true);
@@ -1803,15 +1699,14 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			// Matrix pipe: v_mfma takes a row's texels from lanes 32h + 0..3 and gives wrong results when lanes are switched off
 			// (tools/ubench/mfma_layout.hip), so the fit runs with the whole wave on whenever any lane has one.  A lane without
 			// a fit walks it on its role row's defaults, stores nothing (owner) and its result is cleared below.
-			constexpr bool wholewave = UNITW && (CF_BC7_KEYTRIMS & 1) && (CF_BC7_MFMADOT & 1);
-			if (wholewave ? __ballot(active) != 0ull : active) {
+			if (UNITW ? __ballot(active) != 0ull : active) {
 				if (narrow)
 					fit_lane<UNITW, iters, 4, false, WIDE ? 4 : 3>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
 						wv, yw, sca, frac, gbase, gmode, gsrc, gs, active, lf);
 				else
 					fit_lane<UNITW, iters, 8, given, WIDE ? 4 : 3>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
 						wv, yw, sca, frac, gbase, gmode, gsrc, gs, active, lf);
-				if (wholewave && !active) {
+				if (UNITW && !active) {
 					lf.err = 0; lf.q0 = 0; lf.q1 = 0; lf.pb = 0;
 #pragma unroll
 					for (int k = 0; k < 4; ++k) lf.w[k] = 0;
@@ -1823,7 +1718,7 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				const uint32_t k2 = koff + (lay32 ? (L_HL >> 3) : (lane >> 4));
 				const uint32_t wl2 = TOP_LANE(k2 & 7u);
 				const uint32_t id2 = cbase[wl2 + 19*CF_WG_THREADS], cerr2 = cbase[wl2 + 18*CF_WG_THREADS];
-				const bool n32 = lay32 && (CF_BC7_CANDW ? CF_CAND_NS(cbase[wl2 + 6*CF_WG_THREADS]) == 3u : id2 >= 192u && id2 < 320u);
+				const bool n32 = lay32 && CF_CAND_NS(cbase[wl2 + 6*CF_WG_THREADS]) == 3u;
 				const uint32_t j82 = L_HL & 7u;
 				const uint32_t v2 = lay32 ? (n32 ? (j82 >= 3u ? 1u : 0u) : (L_HL >> 1) & 3u) : (lane >> 2) & 3u;
 				const uint32_t fi2 = lay32 ? (n32 ? (j82 >= 6u ? 3u : j82 - 3u*v2) : (L_HL & 1u)) : (lane & 3u);
@@ -1902,7 +1797,7 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 					L_CSLOT[5*CF_WG_THREADS] = a12 & m4;
 					// the p-bits, and above them what the candidate is (bc7_cand.h): no later phase decodes it from its id
 					// (stored where it is read: the levels that come back to their candidates, Normal and up)
-					L_CSLOT[6*CF_WG_THREADS] = lf.pb | ((pb1 << 2) & m1) | ((pb2 << 4) & m3) | ((CF_BC7_CANDW && uber2) ? k_bc7_cands.w[cf_bc7_cand_index(cidv)] : 0u);
+					L_CSLOT[6*CF_WG_THREADS] = lf.pb | ((pb1 << 2) & m1) | ((pb2 << 4) & m3) | (uber2 ? k_bc7_cands.w[cf_bc7_cand_index(cidv)] : 0u);
 					// errors of the candidate's fits: subset 0 / vector plane / mode 6, then subset 1 or
 					// the scalar plane, then subset 2
 					L_CSLOT[15*CF_WG_THREADS] = lf.err;
@@ -2062,8 +1957,8 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			// sum over the fit's texels of sum_c p_c^2 (the constant part of its error): word 11 of the fit-geometry cache
 			// when every active lane of the wave finds its fit's column there (the starts trip's test), a row loop otherwise
 			uint32_t pp_sum = 0;
-			const uint32_t gsrc = CF_BC7_CANDW ? geo_src(g, kf, wl, lay32) : geo_src(id, kf, wl, lay32);
-			const bool ghit = gbase[gsrc + 12*CF_WG_THREADS] == (CF_BC7_CANDW ? geo_tag(g, id, kf) : geo_tag(id, kf)) && (!lay32 || ((gsrc ^ wl) & 32u) == 0u);
+			const uint32_t gsrc = geo_src(g, kf, wl, lay32);
+			const bool ghit = gbase[gsrc + 12*CF_WG_THREADS] == geo_tag(g, id, kf) && (!lay32 || ((gsrc ^ wl) & 32u) == 0u);
 			const bool pphit = __ballot(act && !ghit) == 0ull;
 			if (pphit)
 				pp_sum = gbase[gsrc + 11*CF_WG_THREADS];

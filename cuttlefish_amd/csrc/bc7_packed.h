@@ -21,16 +21,6 @@
 #define CF_PK_MUL24(a, b) ((a)*(b))
 #endif
 
-// A/B switch, a bit mask: instruction-level forms of the selector search's keys and of the reciprocals.  0 builds the
-// parent's forms.
-//   1: a texel's key in minimum form, B_k - 256 dt minimised over the entries, instead of (dt << 8) - B_k maximised
-//      and negated per texel (key_min_form / key_max_form below)
-//   2: 1.0f/x as v_rcp_f32 and one Newton step where the argument's range is known (bc7_rcp.h)
-// Same payload either way.
-#ifndef CF_BC7_KEYTRIMS
-#define CF_BC7_KEYTRIMS 3
-#endif
-
 // product of two signed operands that fit 24 bits
 #if defined(__HIP_DEVICE_COMPILE__)
 #define CF_PK_MUL24S(a, b) __mul24((a), (b))
@@ -41,32 +31,23 @@
 // ---- a texel's key against one palette entry ----
 // B = (cc << 7) | w is the entry's constant (cc = sum_c w_c c^2 of its colour, w its interpolation weight), dt the cross
 // term sum_c p_c (w_c c).  The key 128 (cc - 2 dt) + w = B - 256 dt orders entries by error, then by weight.
-// Maximum form (the parent's): the entry holds -B, a texel's value is (dt << 8) - B, the largest wins and the key is
-// its negation.  Minimum form: the key itself, one multiply-add of 24-bit operands (dt < 2^23, m256 = -256 from a
-// register), the smallest wins and nothing is negated.  a - b == -(b - a) in two's complement and max(-x) == -min(x), so
-// both give the same key; no value leaves 32 bits (B < 2^30 and 256 dt < 2^30 under both metrics).
+// The search keeps the key itself, one multiply-add of 24-bit operands (dt < 2^23, m256 = -256 from a register), and
+// the smallest wins (minimum form).  It equals the negation of (dt << 8) - B maximised over the entries, the form the
+// search once had (a - b == -(b - a) in two's complement and max(-x) == -min(x): tests/test_bc7_key_forms.py); no value
+// leaves 32 bits (B < 2^30 and 256 dt < 2^30 under both metrics).  That is the perceptual metric's key.
 #define CF_BC7_NO_ENTRY 0x3FFFFFFF      // constant of an entry that does not exist: never the minimum
-CF_PK int key_max_form(int dt, int negB) { return (dt << 8) + negB; }
 CF_PK int key_min_form(int dt, int m256, int B) { return CF_PK_MUL24S(dt, m256) + B; }
 
-// A/B switch, a bit mask: forms of the unit-weight selector search around its keys (minimum form only).  0 builds the
-// parent's forms.  (Bit 2, the error from the raw key sum, stayed under the bar and is not in the tree: DESIGN.md section
-// 4.1, tenth step; profiles/mfma_dots_bc7_ab.txt.)
-//   1: the cross terms of a texel row against an entry by one v_mfma_i32_4x4x4_16b_i8 instead of four v_dot4_u32_u8
-//      (mfma_entry_base below); the fit then runs with the whole wave on, because the instruction needs the lanes that hold
-//      its A rows switched on
-//   4: the weight in a full byte, B = (cc << 8) | w and the key B - 512 dt: the four weights of a texel row are then the
-//      low bytes of four keys and leave them by byte permutes (key_row_weights) instead of a shift and an and-or per texel
-// Same payload either way.
-#ifndef CF_BC7_MFMADOT
-#define CF_BC7_MFMADOT 5
-#endif
-// With the weight in 8 bits below cc: cc = sum_c c^2 <= 4 * 255^2 < 2^18 and dt <= 4 * 255^2, so B < 2^26, 512 dt < 2^27 and
+// Unit weights hold the weight in a full byte, B = (cc << 8) | w and the key B - 512 dt: the four weights of a texel row are
+// then the low bytes of four keys and leave them by byte permutes (key_row_weights) instead of a shift and an and-or per
+// texel.  With the weight in 8 bits below cc: cc = sum_c c^2 <= 4 * 255^2 < 2^18 and dt <= 4 * 255^2, so B < 2^26, 512 dt < 2^27 and
 // |key| = |256 (cc - 2 dt) + w| <= 256 * 260100 + 64 < 2^26; -512 and dt fit the 24-bit multiply; an entry that does not
 // exist has the key CF_BC7_NO_ENTRY - 512 dt > 2^29, above every real one.  The key's low byte is the weight (<= 64), its
 // error part key >> 8 (arithmetic), and a texel outside the subset has the key 0.
 
-// Cross terms on the matrix pipe (bit 1).  For texel bytes a_c, palette bytes b_c and a' = a ^ 0x80, b' = b ^ 0x80 read as
+// Unit weights take the cross terms of a texel row against an entry from one v_mfma_i32_4x4x4_16b_i8 instead of four
+// v_dot4_u32_u8; the fit then runs with the whole wave on, because the instruction needs the lanes that hold its A rows
+// switched on.  For texel bytes a_c, palette bytes b_c and a' = a ^ 0x80, b' = b ^ 0x80 read as
 // signed bytes (a' = a - 128): sum a_c b_c = sum a'_c b'_c + 128 sum a_c + 128 sum b'_c, for any bytes.  The instruction
 // returns D = sum a'b' + C with C = 128 sum_c a_c, so dt = D + 128 sum b' and the key B - F dt (F = 2^fbits: 256, or 512 with
 // the weight byte) is base' - F D with base' = B - 128 F (sb - 512), sb = sum_c b_c.  Ranges: D in [-65024, 325636], |D| < 2^19
@@ -124,6 +105,8 @@ CF_PK uint32_t code_word(uint32_t qword, uint32_t S, uint32_t P)
 // Palette entry of weight w (0..64) between two dequantised endpoint words, every channel
 // (iw*e0 + w*e1 + 32) >> 6 with iw = 64 - w: two channels per multiply on 0x00FF00FF pairs.  A channel's
 // sum is at most 64*255 + 32 < 2^16, so the halves of a pair never meet, and every operand fits 24 bits.
+// The kernel computes it in difference form (pal_line / pal_at below); this is the packed definition the tests hold that
+// form and the matrix-pipe identities against.
 CF_PK uint32_t pal_word(uint32_t e0, uint32_t e1, uint32_t w)
 {
 	const uint32_t iw = 64u - w;

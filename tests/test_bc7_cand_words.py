@@ -1,12 +1,12 @@
-"""The candidate word of csrc/bc7_cand.h against the id ladder it replaces, on the CPU.
+"""The candidate word of csrc/bc7_cand.h against the id ladder it replaced, on the CPU.
 
 A stand-alone host program includes bc7_cand.h, builds the two tables the kernel reads (candidate words by shape, fit
 masks by subset count, partition and fit) and, for every candidate id the encoder can produce -- 0 (mode 6), 1..12
 (modes 5 and 4) and 64..383 (the partition modes) -- and every fit index 0..3, takes the fields of the fit the way the
 kernel does: the word from the table entry of the id (what the leader stores into word 6 of its column, above the
 p-bits), the fields by cf_bc7_cand_fit_of, the texels by the mask table.  The word it decodes carries p-bits, as the
-stored word does.  The test derives every field again from `fit_geo` as it stood before the word existed -- transcribed
-here in Python -- and compares: mode, part, rot, isel, ns, nfits, cb, ab, pbk, ib, chm, mask, m6, planes45, sca.
+stored word does.  The test derives every field again from `fit_geo`, the ladder bc7_encode.hip had before the word existed -- transcribed
+here in Python, the only place it still stands -- and compares: mode, part, rot, isel, ns, nfits, cb, ab, pbk, ib, chm, mask, m6, planes45, sca.
 
 It also runs column_put_fit's read-modify-write of the p-bit word -- the expression is cut out of bc7_encode.hip as it
 stands -- on the stored word, for every fit slot and every value of the p-bits: the two new bits land, the other p-bits
@@ -93,7 +93,7 @@ def nib(word, mode):
 
 
 def fit_geo(id_, kf):
-    """fit_geo of bc7_encode.hip, line by line"""
+    """fit_geo as bc7_encode.hip had it, line by line"""
     g = dict(part=0, rot=0, isel=0)
     if id_ == 0:
         g["mode"] = 6

@@ -1,8 +1,9 @@
-"""The two forms of a texel's key in the BC7 selector search (csrc/bc7_packed.h: key_max_form, key_min_form), on the CPU.
+"""The key of a texel in the BC7 selector search (csrc/bc7_packed.h: key_min_form) against the maximum form the search
+had before it, on the CPU.  The maximum form is the reference and is defined here (key_max_form in the program below).
 
 A stand-alone program (its own main, host compiler) includes bc7_packed.h and walks a texel over a palette both ways:
   old   every entry holds -B_k, the texel's value is (dt << 8) - B_k, the largest wins, the key is its negation
-  new   every entry holds B_k, the value is B_k - 256 dt, the smallest wins and is the key
+  new   every entry holds B_k, the value is B_k - 256 dt, the smallest wins and is the key (what the kernel computes)
 with B_k = (cc_k << 7) | w_k, an entry that does not exist at -/+0x3FFFFFFF, the start values -/+0x7FFFFFFF and, for the
 sixteen entries of mode 6, the larger / smaller of the two halves' results, as assign_lsq_lane does it.  Compared per
 case: the error part U >> 7 (arithmetic shift), the weight U & 127 and the index of the winning entry; both are also
@@ -31,6 +32,8 @@ static uint32_t dot4(uint32_t a, uint32_t b)
 	for (int c = 0; c < 4; ++c) s += ((a >> (8*c)) & 255u)*((b >> (8*c)) & 255u);
 	return s;
 }
+/* the reference: the maximum form, whose entries hold -B */
+static int key_max_form(int dt, int negB) { return (dt << 8) + negB; }
 static unsigned long ncase = 0, nties = 0;
 /* n entries (8: one lane; 16: the two halves of mode 6), of which the first `have` exist */
 static int walk(const int* dt, const int* B, int n, int have)

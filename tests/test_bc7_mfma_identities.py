@@ -1,5 +1,5 @@
-"""The forms of the unit-weight BC7 selector search's keys behind CF_BC7_MFMADOT (csrc/bc7_packed.h: the cross terms on the
-matrix pipe, mfma_entry_base; the weight in a full byte, key_row_weights), on the CPU.  DESIGN.md section 4.1, tenth step.
+"""The forms of the unit-weight BC7 selector search's keys (csrc/bc7_packed.h: the cross terms on the matrix pipe,
+mfma_entry_base; the weight in a full byte, key_row_weights), on the CPU.  DESIGN.md section 4.1, tenth step.
 The host program reaches key_row_weights through its host branch only; the device's v_perm_b32 selectors are covered by
 tests/test_gpu_bc7_mfma_dots.py.
 
@@ -260,8 +260,12 @@ def test_matrix_pipe_and_weight_byte_keys_equal_todays_keys(tmp_path):
     assert ties > 100000 and nsum == 1 << 20 and flat == 1 << 16 and empty >= 4096 and full >= 4096, run.stdout
 
 
-def test_switch_defaults_to_the_kept_bits():
-    with open(os.path.join(CSRC, "bc7_packed.h")) as f:
-        text = f.read()
-    m = re.search(r"#ifndef CF_BC7_MFMADOT\s*\n#define CF_BC7_MFMADOT (\d+)", text)
-    assert m and int(m.group(1)) == 5, "the switch and its default"
+def test_no_switch_selects_another_form():
+    """The product kernel builds the forms compared above and no other: the compile-time switches that once chose between
+    them and their predecessors (the names below, behind the common prefix) occur nowhere in the encoder's source or in
+    bc7_packed.h, so no -D can change what is built."""
+    for name in ("bc7_encode.hip", "bc7_packed.h"):
+        with open(os.path.join(CSRC, name)) as f:
+            text = f.read()
+        for switch in ("CANDW", "FITTRIMS", "KEYTRIMS", "MFMADOT"):
+            assert "CF_BC7_" + switch not in text, (name, switch)

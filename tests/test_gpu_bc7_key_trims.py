@@ -1,4 +1,5 @@
-"""GPU parity of BC7 with the key trims (ninth step; CF_BC7_KEYTRIMS in csrc/bc7_packed.h): the
+"""GPU parity of BC7 with the key trims (ninth step; key_min_form in csrc/bc7_packed.h,
+csrc/bc7_rcp.h): the
 selector search's keys in minimum form, the reciprocals as v_rcp_f32 and a Newton step.  Every payload must equal the CPU oracle's byte for byte, at levels 0..4, with both
 metrics, from an RGBA8 and from an RGBA32F source.
 

@@ -1,6 +1,6 @@
 """GPU parity of BC7 with the selector search's cross terms on the matrix pipe (v_mfma_i32_4x4x4_16b_i8, the fit run with the
-whole wave on) and the weight in a full byte of its keys (tenth step; CF_BC7_MFMADOT in
-csrc/bc7_packed.h).  Every payload must equal the
+whole wave on) and the weight in a full byte of its keys (tenth step; mfma_entry_base and
+key_row_weights in csrc/bc7_packed.h).  Every payload must equal the
 CPU oracle's byte for byte, at levels 0..4, with both metrics (the perceptual instances keep their forms and are covered
 as the untouched half), from an RGBA8 and from an RGBA32F source.
 

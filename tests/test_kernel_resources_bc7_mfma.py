@@ -1,5 +1,5 @@
 """The matrix-pipe cross terms and the weight-byte keys of the selector search (tenth step;
-CF_BC7_MFMADOT) keep every BC7 instance
+assign_lsq_lane in csrc/bc7_encode.hip) keep every BC7 instance
 inside its limits, read from the code objects inside the built library (no GPU needed): all 20 instances
 <PIX, UNITW, WIDE, LEVEL> without scratch, vector spill or AGPRs; the linear-metric builds in at most 128 VGPRs (4 waves
 per SIMD), the perceptual ones in at most 168 (3 waves); LDS at most 40 960 B, four workgroups per CU.  With the weight in

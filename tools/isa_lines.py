@@ -30,8 +30,10 @@ from isa_mix import FAST  # noqa: E402
 
 # (label, text that opens the region, text of the first line after it); searched in this order from the top
 _ASSEMBLY = ("// the fit this lane's geometry-cache column now holds", "// ---- assemble candidates in their leader lanes")
-_CAND_GEO = "// The same geometry from what the candidate's leader stored with it"
-# (a fourth element marks a region that older sources do not have: skipped there, so that a parent can be tabulated)
+_CAND_GEO = ("// The same geometry from what the candidate's leader stored with it",
+             "// It is read from what the candidate's leader stored with it")
+# (a fourth element marks a region that not every source has -- fit_geo left the encoder, cand_geo came late --: skipped
+# where its opening is missing, so that this source and its parents can both be tabulated)
 BC7_REGIONS = (
     ("quantize", "__device__ __forceinline__ void quantize(", "// View of one block's texels in LDS"),
     ("assign_lsq_lane: palette", "__device__ __forceinline__ void assign_lsq_lane(", "\tuint32_t err = pp_sum;"),
@@ -40,7 +42,7 @@ BC7_REGIONS = (
     ("refit_window", "__device__ __forceinline__ void refit_window(", "// Fit-geometry cache"),
     ("fit_lane", "__device__ __forceinline__ void fit_lane(", "__device__ __forceinline__ uint32_t w2i("),
     ("pack_block_group", "__device__ __forceinline__ uint4 pack_block_group(", "// The 14 integer moments of a set of texels"),
-    ("fit_geo", "__device__ __forceinline__ FitGeo fit_geo(", (_CAND_GEO, "// Store a fit (quantised fields")),
+    ("fit_geo", "__device__ __forceinline__ FitGeo fit_geo(", _CAND_GEO + ("// Store a fit (quantised fields",), "optional"),
     ("cand_geo / geo_src", _CAND_GEO, "// Store a fit (quantised fields", "optional"),
     ("phase 1", "// ---- phase 1: partition scores", "// ---- lane roles ----"),
     ("lane roles before the fit", "// ---- lane roles ----", "\t\t\tuint32_t wl[4] = {wt[0], wt[1], wt[2], wt[3]};"),
