@@ -726,8 +726,6 @@ def load_library(path: Optional[str] = None):
     L.cfhip_lz_size_device.restype = ctypes.c_int
     L.cfhip_lz_slice_bytes.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
     L.cfhip_lz_slice_bytes.restype = ctypes.c_size_t
-    L.cfhip_lz_stage_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
-    L.cfhip_lz_stage_ms.restype = ctypes.c_int
     L.cfhip_deflate_bound.argtypes = [ctypes.c_size_t]
     L.cfhip_deflate_bound.restype = ctypes.c_size_t
     L.cfhip_deflate.argtypes = [ctypes.c_void_p, ctypes.POINTER(LzSpan), ctypes.c_size_t, ctypes.c_void_p,
@@ -736,8 +734,6 @@ def load_library(path: Optional[str] = None):
     L.cfhip_deflate_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(LzSpan), ctypes.c_size_t, ctypes.c_void_p,
                                        ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_deflate_device.restype = ctypes.c_int
-    L.cfhip_deflate_stage_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
-    L.cfhip_deflate_stage_ms.restype = ctypes.c_int
     L.cfhip_deflate_code_lengths.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32,
                                              ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint8)]
     L.cfhip_deflate_code_lengths.restype = ctypes.c_int
@@ -756,8 +752,6 @@ def load_library(path: Optional[str] = None):
     L.cfhip_inflate_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
                                        ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_inflate_device.restype = ctypes.c_int
-    L.cfhip_inflate_stage_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
-    L.cfhip_inflate_stage_ms.restype = ctypes.c_int
     L.cfhip_lz4_bound.argtypes = [ctypes.c_size_t]
     L.cfhip_lz4_bound.restype = ctypes.c_size_t
     L.cfhip_lz4_encode.argtypes = [ctypes.c_void_p, ctypes.POINTER(LzSpan), ctypes.c_size_t, ctypes.c_void_p,
@@ -772,8 +766,10 @@ def load_library(path: Optional[str] = None):
     L.cfhip_lz4_decode_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                           ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_lz4_decode_device.restype = ctypes.c_int
-    for f in (L.cfhip_lz4_encode_stage_ms, L.cfhip_lz4_decode_stage_ms):
-        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_size_t]
+    for name, takes_n in (("lz", False), ("deflate", False), ("inflate", False), ("lz4_encode", True), ("lz4_decode", True),
+                          ("png", False)):
+        f = getattr(L, "cfhip_%s_stage_ms" % name)
+        f.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)] + ([ctypes.c_size_t] if takes_n else [])
         f.restype = ctypes.c_int
     L.cfhip_png_bound.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.cfhip_png_bound.restype = ctypes.c_size_t
@@ -783,8 +779,6 @@ def load_library(path: Optional[str] = None):
     L.cfhip_png_encode.restype = ctypes.c_int
     L.cfhip_png_encode_device.argtypes = L.cfhip_png_encode.argtypes + [ctypes.c_void_p]
     L.cfhip_png_encode_device.restype = ctypes.c_int
-    L.cfhip_png_stage_ms.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]
-    L.cfhip_png_stage_ms.restype = ctypes.c_int
     L.cfhip_rdo_target.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(RdoSurface),
                                    ctypes.c_size_t, ctypes.POINTER(RdoExParams), ctypes.POINTER(ctypes.c_uint8),
                                    ctypes.c_void_p, ctypes.c_float, ctypes.POINTER(RdoTargetResult)]
@@ -1460,11 +1454,15 @@ class Context:
         the previous one.  Results do not depend on it; the context's scratch does."""
         return int(self._lib.cfhip_lz_slice_bytes(self._h, int(nbytes)))
 
+    def _stage_ms(self, fn, names: tuple, takes_n: bool = False) -> dict:
+        """One of the cfhip_*_stage_ms: kernel ms by stage name, in the stages' order"""
+        ms = (ctypes.c_float*len(names))()
+        self._check(fn(self._h, ms, len(names)) if takes_n else fn(self._h, ms))
+        return dict(zip(names, (float(v) for v in ms)))
+
     def lz_stage_ms(self) -> dict:
         """Kernel ms of the last estimate's stages: keys, sort, match, parse, cost"""
-        ms = (ctypes.c_float*5)()
-        self._check(self._lib.cfhip_lz_stage_ms(self._h, ms))
-        return dict(zip(LZ_STAGES, (float(v) for v in ms)))
+        return self._stage_ms(self._lib.cfhip_lz_stage_ms, LZ_STAGES)
 
     def deflate(self, payloads) -> bytes:
         """The zlib stream (cfhip_deflate) of a byte stream: one array / bytes object, or a sequence of them taken as
@@ -1501,9 +1499,7 @@ class Context:
 
     def deflate_stage_ms(self) -> dict:
         """Kernel ms of the last deflate's stages: keys, sort, match, parse, adler, codes, offsets, emit"""
-        ms = (ctypes.c_float*len(DEFLATE_STAGES))()
-        self._check(self._lib.cfhip_deflate_stage_ms(self._h, ms))
-        return dict(zip(DEFLATE_STAGES, (float(v) for v in ms)))
+        return self._stage_ms(self._lib.cfhip_deflate_stage_ms, DEFLATE_STAGES)
 
     def deflate_code_lengths(self, counts, limit: int) -> np.ndarray:
         """The device code builder alone (cfhip_deflate_code_lengths): one code length per count"""
@@ -1582,9 +1578,7 @@ class Context:
 
     def inflate_stage_ms(self) -> dict:
         """Kernel ms of the last inflate's stages: decode, resolve, pack, fold"""
-        ms = (ctypes.c_float*len(INFLATE_STAGES))()
-        self._check(self._lib.cfhip_inflate_stage_ms(self._h, ms))
-        return dict(zip(INFLATE_STAGES, (float(v) for v in ms)))
+        return self._stage_ms(self._lib.cfhip_inflate_stage_ms, INFLATE_STAGES)
 
     def lz4_encode(self, payloads) -> bytes:
         """The LZ4 frame (cfhip_lz4_encode) of a byte stream: one array / bytes object, or a sequence of them taken as
@@ -1621,9 +1615,7 @@ class Context:
 
     def lz4_encode_stage_ms(self) -> dict:
         """Kernel ms of the last lz4_encode's stages: keys, sort, match, parse, plan, offsets, emit, hash, final"""
-        ms = (ctypes.c_float*len(LZ4_ENCODE_STAGES))()
-        self._check(self._lib.cfhip_lz4_encode_stage_ms(self._h, ms, len(LZ4_ENCODE_STAGES)))
-        return dict(zip(LZ4_ENCODE_STAGES, (float(v) for v in ms)))
+        return self._stage_ms(self._lib.cfhip_lz4_encode_stage_ms, LZ4_ENCODE_STAGES, takes_n=True)
 
     def lz4_decode(self, frame, n: int) -> bytes:
         """The n bytes of one LZ4 frame (cfhip_lz4_decode): anyone's frame with independent blocks of at most 64 KiB.  A
@@ -1659,9 +1651,7 @@ class Context:
 
     def lz4_decode_stage_ms(self) -> dict:
         """Kernel ms of the last lz4_decode's stages: chain, blocks, final"""
-        ms = (ctypes.c_float*len(LZ4_DECODE_STAGES))()
-        self._check(self._lib.cfhip_lz4_decode_stage_ms(self._h, ms, len(LZ4_DECODE_STAGES)))
-        return dict(zip(LZ4_DECODE_STAGES, (float(v) for v in ms)))
+        return self._stage_ms(self._lib.cfhip_lz4_decode_stage_ms, LZ4_DECODE_STAGES, takes_n=True)
 
     def png_encode(self, pixels: np.ndarray, color_type: int = PNG_RGBA, bit_depth: int = 8,
                    color_space=ColorSpace.Linear) -> bytes:
@@ -1704,9 +1694,7 @@ class Context:
 
     def png_stage_ms(self) -> dict:
         """Kernel ms of the last png_encode's stages: filter, the zlib encoder's eight, crc, final"""
-        ms = (ctypes.c_float*len(PNG_STAGES))()
-        self._check(self._lib.cfhip_png_stage_ms(self._h, ms))
-        return dict(zip(PNG_STAGES, (float(v) for v in ms)))
+        return self._stage_ms(self._lib.cfhip_png_stage_ms, PNG_STAGES)
 
     def rdo_target(self, payloads: Sequence[np.ndarray], sources: Sequence[np.ndarray], fmt, typ=Type.UNorm,
                    target_ratio: float = 0.85, lam: float = 32.0, max_sse_increase: Optional[int] = None, mask=None,

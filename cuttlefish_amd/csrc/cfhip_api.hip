@@ -17,6 +17,7 @@
 #include "lz4.h"
 #include "png.h"
 #include "mip_post.h"
+#include "stage_log.h"
 #include "../../include/cuttlefish_hip.h"
 
 #include <cmath>
@@ -203,13 +204,9 @@ struct cfhip_ctx {
 	void* d_lz = nullptr;             // deflate-size estimator: one slice's scratch (csrc/lzsize.h), grown on demand
 	size_t lz_cap = 0;
 	size_t lz_slice = 0;              // cfhip_lz_slice_bytes: 0 = CFLZ_SLICE_DEFAULT
-	size_t lz_first_event = 0, lz_slices = 0;   // the last estimate's event pairs: CFLZ_STAGES per slice
-	size_t df_first_event = 0, df_slices = 0;   // the last cfhip_deflate*'s event pairs: CFDF_STAGES per slice
-	size_t inf_first_event = 0, inf_slices = 0; // the last cfhip_inflate*'s event pairs: CFINF_STAGES per slice
-	size_t l4_first_event = 0, l4_pairs = 0;    // the last cfhip_lz4_*'s event pairs (csrc/lz4.h: the stages)
+	StageLog stages = {nullptr, 0, 0, 0, 0, 0};   // the last stream-codec call's event pairs by stage (csrc/stage_log.h)
 	void* d_png = nullptr;            // cfhip_png_encode*: the filtered bytes, an unplaced zlib stream, the state (csrc/png.h)
 	size_t png_cap = 0;
-	size_t png_first_event = 0, png_pairs = 0;  // the last cfhip_png_encode*'s event pairs: filter, the encoder's, crc, final
 	void* d_rdo_keep = nullptr;       // cfhip_rdo_target: the pristine payloads every trial starts from
 	size_t rdo_keep_cap = 0;
 	std::map<int, void*> astc_tables; // per-format device tables (built on first use)
@@ -659,10 +656,11 @@ int reserve(cfhip_ctx* ctx, void** buf, size_t* cap, size_t need)
 
 // The one owner of the staging buffers (d_src, d_out, d_batch, d_mip3d, and the estimator's d_lz and the target
 // search's d_rdo_keep, the PNG writer's d_png) for one call on one stream; the only code
-// that writes staging_busy / staging_stream / staging_done.  Declared after the context's lock guard, so that it
-// ends before the lock is released.
+// that writes staging_busy / staging_stream / staging_done.  Declared after the context's lock guard (inside the body
+// that guarded() runs), so that it ends before the lock is released.
 //  * acquire(): before the first touch of a buffer; the first call makes the stream wait for the last asynchronous
-//    user when that was another stream (same-stream reuse is ordered anyway).
+//    user when that was another stream (same-stream reuse is ordered anyway).  The entry point, its host wrapper or
+//    the target search acquires; the stream codecs' *_run routines never do.
 //  * done(synchronous): the only success exit.  An asynchronous call that acquired records staging_done and becomes
 //    the last user; a synchronous one drains its stream, after which the buffers are idle if it acquired (its stream
 //    waited for the previous user) or was the last user itself.
@@ -719,6 +717,141 @@ struct StagingLease {
 		(void)hipGetLastError();
 	}
 };
+
+// ---- what the stream codecs' entry points share (estimator, deflate, inflate, LZ4, PNG: the sections far below) -----
+// An entry point's frame: the context's lock while the body runs (none for a NULL context: the checks and the
+// empty-input answers need none), its error text cleared, and no exception across the C boundary.  The body declares its
+// StagingLease itself, so the lease ends -- also while an exception unwinds -- before the lock is released.
+template <class Body>
+int guarded(cfhip_ctx* ctx, const char* what, Body&& body)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	try {
+		return body();
+	} catch (const std::exception& e) {
+		return fail(ctx, CFHIP_E_DEVICE, "%s: %s", what, e.what());
+	} catch (...) {
+		return fail(ctx, CFHIP_E_DEVICE, "%s: unknown exception", what);
+	}
+}
+
+// The event bookkeeping of a call that starts: its pairs are counted from here (all pairs, while profiling), and the
+// stage log of the call before it is closed.
+void begin_call(cfhip_ctx* ctx, hipStream_t stream, const char* kernel)
+{
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = kernel;
+	ctx->stages.owner = nullptr;
+}
+
+// A family of calls that keeps a stage log: the public names its cfhip_*_stage_ms answers for (the log's owner tag), the
+// kernel name its calls leave in last_kernel, and the shape of its event pairs (csrc/stage_log.h).
+struct StageFamily {
+	const char* calls;
+	const char* kernel;
+	size_t head, per_slice, tail;
+};
+const StageFamily kLzSizeStages = {"cfhip_lz_size", "cfhip_lz_match_kernel", 0, CFLZ_STAGES, 0};
+const StageFamily kDeflateStages = {"cfhip_deflate", "cfhip_deflate_emit_kernel", 0, CFDF_STAGES, 0};
+const StageFamily kInflateStages = {"cfhip_inflate", "cfhip_inflate_decode_kernel", 0, CFINF_STAGES, 0};
+const StageFamily kLz4EncodeStages = {"cfhip_lz4_encode", "cfhip_lz4_emit_kernel", 0, CFLZ4_STAGES - 1, 1};
+const StageFamily kLz4DecodeStages = {"cfhip_lz4_decode", "cfhip_lz4_block_kernel", CFLZ4_DSTAGES, 0, 0};
+// filter; the encoder's stages per slice (png_run calls deflate_run, the log stays the writer's); crc, final
+const StageFamily kPngStages = {"cfhip_png_encode", "cfhip_png_filter_kernel", 1, CFDF_STAGES, 2};
+
+// begin_call of an entry point of family f: the log is f's, empty, and starts at the call's next event pair.  Entry
+// points alone open it -- the *_run routines below them serve several families, and a search that owns no log.
+void begin_call(cfhip_ctx* ctx, hipStream_t stream, const StageFamily& f)
+{
+	begin_call(ctx, stream, f.kernel);
+	ctx->stages = StageLog{f.calls, ctx->events_used, 0, f.head, f.per_slice, f.tail};
+}
+
+// n event pairs into ev[0 .. 2n), counted into the open stage log
+int take_event_pairs(cfhip_ctx* ctx, hipEvent_t* ev, size_t n)
+{
+	for (size_t k = 0; k < n; ++k) {
+		const int rc = next_event_pair(ctx, &ev[2*k], &ev[2*k + 1]);
+		if (rc != CFHIP_OK)
+			return rc;
+	}
+	if (ctx->stages.owner)
+		ctx->stages.pairs += n;
+	return CFHIP_OK;
+}
+
+// cfhip_*_stage_ms of family f: the open log's pairs summed by stage into ms[0 .. n).  The log is f's last call's while
+// f owns it and last_kernel still holds what that call wrote there: the entry points of the other families (encode,
+// decode, compare, ...) do not pass through begin_call, but every one of them names its own kernel.
+int stage_ms(cfhip_ctx* ctx, const StageFamily& f, const char* what, float* ms, size_t n)
+{
+	const size_t stages = f.head + f.per_slice + f.tail;
+	if (!ctx || !ms || n > stages)
+		return CFHIP_E_INVALID;
+	std::lock_guard<std::mutex> guard(ctx->lock);
+	const StageLog& log = ctx->stages;
+	if (log.owner != f.calls || ctx->last_kernel != f.kernel || !stage_log_valid(log, ctx->events_used))
+		return fail(ctx, CFHIP_E_INVALID, "%s: the last call on this context was no %s*", what, f.calls);
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	HIP_TRY(ctx, hipStreamSynchronize(ctx->events_stream));
+	float sum[16] = {};
+	static_assert(CFPNG_STAGES <= 16 && CFLZ4_STAGES <= 16, "the longest family's stages fit");
+	for (size_t i = 0; i < log.pairs; ++i) {
+		float t = 0.0f;
+		HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->events[log.first + 2*i], ctx->events[log.first + 2*i + 1]));
+		sum[stage_log_stage(log, i)] += t;
+	}
+	std::copy(sum, sum + n, ms);
+	return CFHIP_OK;
+}
+
+// Where a host call's result words lie in d_out: behind `bytes` of output, 256-byte aligned; they take 256 bytes.
+size_t result_offset(size_t bytes)
+{
+	return (bytes + 255u)/256u*256u;
+}
+
+// The tail of a host call whose output's size the device decides: the result words at d_res, then exactly bytes_out
+// bytes (never more than `bound`) from d_from into out, the lease's end, *result.
+template <class Result>
+int download_sized(cfhip_ctx* ctx, StagingLease& lease, const char* what, const void* d_res, const void* d_from, size_t bound,
+	void* out, Result* result)
+{
+	Result res;
+	HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
+	HIP_TRY(ctx, hipStreamSynchronize(lease.stream));
+	if (res.bytes_out > bound)
+		return fail(ctx, CFHIP_E_DEVICE, "%s: %llu bytes exceed the bound", what, (unsigned long long)res.bytes_out);
+	HIP_TRY(ctx, hipMemcpyAsync(out, d_from, (size_t)res.bytes_out, hipMemcpyDeviceToHost, lease.stream));
+	const int rc = lease.done(true);
+	if (rc == CFHIP_OK)
+		*result = res;
+	return rc;
+}
+
+// Its twin for the decoders, whose output's size the caller knows: the bytes come only where the status is 0 (no
+// error).  The caller turns *result's status into the call's verdict.
+template <class Result>
+int download_checked(cfhip_ctx* ctx, StagingLease& lease, const void* d_res, const void* d_from, size_t out_bytes, void* out,
+	Result* result)
+{
+	Result res;
+	HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
+	HIP_TRY(ctx, hipStreamSynchronize(lease.stream));
+	if (res.status == 0)
+		HIP_TRY(ctx, hipMemcpyAsync(out, d_from, out_bytes, hipMemcpyDeviceToHost, lease.stream));
+	const int rc = lease.done(true);
+	if (rc == CFHIP_OK)
+		*result = res;
+	return rc;
+}
 
 // One launch for many surfaces (same format / pixel type): workgroups are numbered across
 // the surfaces, the kernel resolves its surface with a uniform binary search (cf_resolve).
@@ -1990,15 +2123,6 @@ static bool alpha_aligned(const void* p, size_t pitch, int pixel_type)
 	return (uintptr_t)p % a == 0 && pitch % a == 0;
 }
 
-static void mip_post_begin_call(cfhip_ctx* ctx, hipStream_t stream, const char* kernel)
-{
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	ctx->last_kernel = kernel;
-}
-
 int cfhip_alpha_coverage_device(cfhip_ctx* ctx, const cfhip_coverage_surface* surfaces, uint32_t count, float threshold,
 	float scale, uint32_t* counts_device, void* stream_)
 {
@@ -2053,7 +2177,7 @@ int cfhip_alpha_coverage_device(cfhip_ctx* ctx, const cfhip_coverage_surface* su
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
 	const hipStream_t stream = lease.stream;
-	mip_post_begin_call(ctx, stream, "cfhip_mip_post_gather_kernel");
+	begin_call(ctx, stream, "cfhip_mip_post_gather_kernel");
 	int rc = lease.acquire();
 	if (rc == CFHIP_OK)
 		rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab.size()*sizeof(cfmp_surf));
@@ -2161,7 +2285,7 @@ int cfhip_mip_post_array_device(cfhip_ctx* ctx, const void* const* srcs, uint32_
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
 	const hipStream_t stream = lease.stream;
-	mip_post_begin_call(ctx, stream, coverage ? "cfhip_mip_post_count_kernel" : "cfhip_mip_post_apply_kernel");
+	begin_call(ctx, stream, coverage ? "cfhip_mip_post_count_kernel" : "cfhip_mip_post_apply_kernel");
 	// d_batch: the surface table, then the levels' search states, then the counters; d_src: the alpha plane
 	const size_t tab_bytes = (nsurf*sizeof(cfmp_surf) + 15u) & ~(size_t)15u;
 	const size_t state_bytes = coverage ? nlev*sizeof(cfmp_state) : 0u;
@@ -3478,20 +3602,31 @@ static size_t lz_slice_of(const cfhip_ctx* ctx)
 	return (s + CFLZ_COSTBLK - 1u)/CFLZ_COSTBLK*CFLZ_COSTBLK;
 }
 
-// The estimate of p's stream (total > 0) into six counters on the device, enqueued on the lease's stream: the stream in
-// slices of whole cost blocks, each behind the W bytes before it.  out_device NULL: the scratch's own result slot,
-// returned in *result.  The caller has set up the call's event bookkeeping.
+// The slice of a stream of `total` bytes that is cut into whole `unit`s, and the scratch the sort of one slice (behind
+// its window) takes.
+static int lz_slice_plan(cfhip_ctx* ctx, size_t total, size_t unit, size_t* slice, size_t* sort_bytes)
+{
+	*slice = std::min(lz_slice_of(ctx), (total + unit - 1u)/unit*unit);
+	HIP_TRY(ctx, cfhip_lz_sort_bytes(*slice + CFLZ_WINDOW, sort_bytes));
+	return CFHIP_OK;
+}
+
+// The *_run routines below enqueue one codec's work on the lease's stream.  Their caller -- an entry point, its host
+// wrapper, or the target search -- has acquired the lease, begun the call and, where the call keeps one, opened its
+// stage log; the routines take their event pairs through take_event_pairs and know no family.
+
+// The estimate of p's stream (total > 0) into six counters on the device: the stream in slices of whole cost blocks,
+// each behind the W bytes before it.  out_device NULL: the scratch's own result slot, returned in *result.
 static int lz_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hipMemcpyKind kind,
 	unsigned long long* out_device, unsigned long long** result)
 {
 	const hipStream_t stream = lease.stream;
-	const size_t slice = std::min(lz_slice_of(ctx), (p.total + CFLZ_COSTBLK - 1u)/CFLZ_COSTBLK*CFLZ_COSTBLK);
-	size_t sort_bytes = 0;
-	HIP_TRY(ctx, cfhip_lz_sort_bytes(slice + CFLZ_WINDOW, &sort_bytes));
+	size_t slice = 0, sort_bytes = 0;
+	int rc = lz_slice_plan(ctx, p.total, CFLZ_COSTBLK, &slice, &sort_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
 	const cflz_layout lay = cflz_scratch(slice, sort_bytes);
-	int rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, lay.total);
+	rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, lay.total);
 	if (rc != CFHIP_OK)
 		return rc;
 	uint8_t* base = static_cast<uint8_t*>(ctx->d_lz);
@@ -3501,8 +3636,6 @@ static int lz_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hipMemcp
 	if (result)
 		*result = out_device;
 	HIP_TRY(ctx, hipMemsetAsync(acc, 0, 4u*sizeof(unsigned long long), stream));
-	ctx->lz_first_event = ctx->events_used;
-	ctx->lz_slices = 0;
 	for (size_t s0 = 0; s0 < p.total; s0 += slice) {
 		const size_t s1 = std::min(p.total, s0 + slice);
 		const size_t carry = s0 ? CFLZ_WINDOW : 0u;        // s0 >= one cost block > W
@@ -3510,15 +3643,12 @@ static int lz_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hipMemcp
 		if (rc != CFHIP_OK)
 			return rc;
 		hipEvent_t ev[2*CFLZ_STAGES];
-		for (int k = 0; k < CFLZ_STAGES; ++k) {
-			rc = next_event_pair(ctx, &ev[2*k], &ev[2*k + 1]);
-			if (rc != CFHIP_OK)
-				return rc;
-		}
+		rc = take_event_pairs(ctx, ev, CFLZ_STAGES);
+		if (rc != CFHIP_OK)
+			return rc;
 		const hipError_t e = cfhip_launch_lz_slice(base, &lay, sort_bytes, (uint32_t)carry, (uint32_t)(s1 - s0), ev, stream);
 		if (e != hipSuccess)
 			return fail(ctx, CFHIP_E_DEVICE, "lz_size launch: %s", hipGetErrorString(e));
-		++ctx->lz_slices;
 	}
 	const hipError_t e = cfhip_launch_lz_final(acc, (unsigned long long)p.total, out_device, stream);
 	if (e != hipSuccess)
@@ -3526,74 +3656,63 @@ static int lz_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hipMemcp
 	return CFHIP_OK;
 }
 
-static void lz_begin_call(cfhip_ctx* ctx, hipStream_t stream)
-{
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	ctx->last_kernel = "cfhip_lz_match_kernel";
-}
-
 int cfhip_lz_size(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, cfhip_lz_stats* out)
 {
 	static_assert(sizeof(cfhip_lz_stats) == 6*sizeof(unsigned long long), "the kernel's counters are the struct");
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	LzPlan p;
-	int rc = lz_check(ctx, "lz_size", spans, n_spans, out, true, &p);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!p.total) {
-		memset(out, 0, sizeof(*out));
+	return guarded(ctx, "lz_size", [&]() -> int {
+		LzPlan p;
+		int rc = lz_check(ctx, "lz_size", spans, n_spans, out, true, &p);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!p.total) {
+			memset(out, 0, sizeof(*out));
+			return CFHIP_OK;
+		}
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		begin_call(ctx, lease.stream, kLzSizeStages);
+		unsigned long long* d_res = nullptr;
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = lz_run(ctx, lease, p, hipMemcpyHostToDevice, nullptr, &d_res);
+		if (rc != CFHIP_OK)
+			return rc;
+		cfhip_lz_stats res;
+		HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		*out = res;
 		return CFHIP_OK;
-	}
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, ctx->stream);
-	lz_begin_call(ctx, lease.stream);
-	unsigned long long* d_res = nullptr;
-	rc = lz_run(ctx, lease, p, hipMemcpyHostToDevice, nullptr, &d_res);
-	if (rc != CFHIP_OK)
-		return rc;
-	cfhip_lz_stats res;
-	HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
-	rc = lease.done(true);
-	if (rc != CFHIP_OK)
-		return rc;
-	*out = res;
-	return CFHIP_OK;
+	});
 }
 
 int cfhip_lz_size_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, cfhip_lz_stats* out_device,
 	void* stream_)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	LzPlan p;
-	int rc = lz_check(ctx, "lz_size_device", spans, n_spans, out_device, false, &p);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	lz_begin_call(ctx, lease.stream);
-	if (!p.total)
-		HIP_TRY(ctx, hipMemsetAsync(out_device, 0, sizeof(cfhip_lz_stats), lease.stream));
-	else {
-		rc = lz_run(ctx, lease, p, hipMemcpyDeviceToDevice, reinterpret_cast<unsigned long long*>(out_device), nullptr);
+	return guarded(ctx, "lz_size_device", [&]() -> int {
+		LzPlan p;
+		int rc = lz_check(ctx, "lz_size_device", spans, n_spans, out_device, false, &p);
 		if (rc != CFHIP_OK)
 			return rc;
-	}
-	return lease.done(!stream_);
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		begin_call(ctx, lease.stream, kLzSizeStages);
+		if (!p.total)
+			HIP_TRY(ctx, hipMemsetAsync(out_device, 0, sizeof(cfhip_lz_stats), lease.stream));
+		else {
+			rc = lease.acquire();
+			if (rc == CFHIP_OK)
+				rc = lz_run(ctx, lease, p, hipMemcpyDeviceToDevice, reinterpret_cast<unsigned long long*>(out_device), nullptr);
+			if (rc != CFHIP_OK)
+				return rc;
+		}
+		return lease.done(!stream_);
+	});
 }
 
 size_t cfhip_lz_slice_bytes(cfhip_ctx* ctx, size_t bytes)
@@ -3608,23 +3727,7 @@ size_t cfhip_lz_slice_bytes(cfhip_ctx* ctx, size_t bytes)
 
 int cfhip_lz_stage_ms(cfhip_ctx* ctx, float ms[CFLZ_STAGES])
 {
-	if (!ctx || !ms)
-		return CFHIP_E_INVALID;
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	const size_t first = ctx->lz_first_event, pairs = ctx->lz_slices*CFLZ_STAGES;
-	// every entry point names its kernel in last_kernel, so another call since the estimate shows there
-	if (!pairs || first + 2*pairs > ctx->events_used || ctx->last_kernel.compare(0, 8, "cfhip_lz") != 0)
-		return fail(ctx, CFHIP_E_INVALID, "lz_stage_ms: the last call on this context was no cfhip_lz_size*");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->events_stream));
-	for (int k = 0; k < CFLZ_STAGES; ++k)
-		ms[k] = 0.0f;
-	for (size_t i = 0; i < pairs; ++i) {
-		float t = 0.0f;
-		HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->events[first + 2*i], ctx->events[first + 2*i + 1]));
-		ms[i % CFLZ_STAGES] += t;
-	}
-	return CFHIP_OK;
+	return stage_ms(ctx, kLzSizeStages, "lz_stage_ms", ms, CFLZ_STAGES);
 }
 
 // ---- the zlib stream of payloads (csrc/deflate.hip, csrc/deflate.h; the definition is tests/deflate_ref.py) --------
@@ -3663,25 +3766,24 @@ static int deflate_check(cfhip_ctx* ctx, const char* what, const cfhip_lz_span* 
 	return CFHIP_OK;
 }
 
-// The stream of p (total > 0) into out_device (zeroed here) and the result into result_device, enqueued on the lease's
-// stream: slices of whole groups, each behind the W bytes before it, the state carried on the device.
+// The stream of p (total > 0) into out_device (zeroed here) and the result into result_device: slices of whole groups,
+// each behind the W bytes before it, the state carried on the device.
 // index_device: NULL, or the stream's index entries (cfhip_deflate_indexed*), written slice by slice from the group records.
 static int deflate_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hipMemcpyKind kind, uint8_t* out_device,
 	unsigned long long* result_device, cfinf_entry* index_device = nullptr)
 {
 	const hipStream_t stream = lease.stream;
-	const size_t slice = std::min(lz_slice_of(ctx), (p.total + CFLZ_COSTBLK - 1u)/CFLZ_COSTBLK*CFLZ_COSTBLK);
-	size_t sort_bytes = 0;
-	HIP_TRY(ctx, cfhip_lz_sort_bytes(slice + CFLZ_WINDOW, &sort_bytes));
+	size_t slice = 0, sort_bytes = 0;
+	int rc = lz_slice_plan(ctx, p.total, CFLZ_COSTBLK, &slice, &sort_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
 	const cfdf_layout lay = cfdf_scratch(slice, sort_bytes);
-	int rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, lay.total);
+	rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, lay.total);
 	if (rc != CFHIP_OK)
 		return rc;
 	uint8_t* base = static_cast<uint8_t*>(ctx->d_lz);
 	unsigned long long* state = reinterpret_cast<unsigned long long*>(base + lay.state);
 	HIP_TRY(ctx, hipMemsetAsync(out_device, 0, cfdf_bound(p.total), stream));
-	ctx->df_first_event = ctx->events_used;
-	ctx->df_slices = 0;
 	for (size_t s0 = 0; s0 < p.total; s0 += slice) {
 		const size_t s1 = std::min(p.total, s0 + slice);
 		const size_t carry = s0 ? CFLZ_WINDOW : 0u;
@@ -3689,11 +3791,9 @@ static int deflate_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hip
 		if (rc != CFHIP_OK)
 			return rc;
 		hipEvent_t ev[2*CFDF_STAGES];
-		for (int k = 0; k < CFDF_STAGES; ++k) {
-			rc = next_event_pair(ctx, &ev[2*k], &ev[2*k + 1]);
-			if (rc != CFHIP_OK)
-				return rc;
-		}
+		rc = take_event_pairs(ctx, ev, CFDF_STAGES);
+		if (rc != CFHIP_OK)
+			return rc;
 		const hipError_t e = cfhip_launch_deflate_slice(base, &lay, sort_bytes, (uint32_t)carry, (uint32_t)(s1 - s0), s0 == 0,
 			s1 == p.total, out_device, ev, stream);
 		if (e != hipSuccess)
@@ -3704,7 +3804,6 @@ static int deflate_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hip
 			if (ie != hipSuccess)
 				return fail(ctx, CFHIP_E_DEVICE, "deflate index launch: %s", hipGetErrorString(ie));
 		}
-		++ctx->df_slices;
 	}
 	const hipError_t e = cfhip_launch_deflate_final(state, (unsigned long long)p.total, out_device, result_device, stream);
 	if (e != hipSuccess)
@@ -3712,20 +3811,13 @@ static int deflate_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hip
 	return CFHIP_OK;
 }
 
-static void deflate_begin_call(cfhip_ctx* ctx, hipStream_t stream)
-{
-	lz_begin_call(ctx, stream);
-	ctx->last_kernel = "cfhip_deflate_emit_kernel";
-}
-
 static int deflate_host(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, void* out, cfhip_deflate_result* result,
 	cfhip_zindex_entry* index = nullptr)
 {
 	static_assert(sizeof(cfhip_deflate_result) == 9*sizeof(unsigned long long), "the final kernel's words are the struct");
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	deflate_begin_call(ctx, lease.stream);
-	// the result lies behind the stream's bytes, 256-byte aligned
-	const size_t res_off = (cfdf_bound(p.total) + 255u)/256u*256u;
+	begin_call(ctx, lease.stream, kDeflateStages);
+	const size_t res_off = result_offset(cfdf_bound(p.total));
 	const size_t entries = (p.total + CFLZ_CHUNK - 1u)/CFLZ_CHUNK;      // the index lies behind the result
 	int rc = lease.acquire();
 	if (rc == CFHIP_OK)
@@ -3738,30 +3830,15 @@ static int deflate_host(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, vo
 	rc = deflate_run(ctx, lease, p, hipMemcpyHostToDevice, d_out, d_res, d_index);
 	if (rc != CFHIP_OK)
 		return rc;
-	cfhip_deflate_result res;
-	HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
-	HIP_TRY(ctx, hipStreamSynchronize(lease.stream));
-	if (res.bytes_out > cfdf_bound(p.total))
-		return fail(ctx, CFHIP_E_DEVICE, "deflate: %llu bytes exceed the bound", (unsigned long long)res.bytes_out);
-	HIP_TRY(ctx, hipMemcpyAsync(out, d_out, (size_t)res.bytes_out, hipMemcpyDeviceToHost, lease.stream));
 	if (index)
 		HIP_TRY(ctx, hipMemcpyAsync(index, d_index, entries*sizeof(cfinf_entry), hipMemcpyDeviceToHost, lease.stream));
-	rc = lease.done(true);
-	if (rc != CFHIP_OK)
-		return rc;
-	*result = res;
-	return CFHIP_OK;
+	return download_sized(ctx, lease, "deflate", d_res, d_out, cfdf_bound(p.total), out, result);
 }
 
 int cfhip_deflate(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out, size_t cap,
 	cfhip_deflate_result* result)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	try {
+	return guarded(ctx, "deflate", [&]() -> int {
 		LzPlan p;
 		const int rc = deflate_check(ctx, "deflate", spans, n_spans, out, cap, result, true, &p);
 		if (rc != CFHIP_OK)
@@ -3775,22 +3852,13 @@ int cfhip_deflate(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, vo
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		StagingLease lease(ctx, ctx->stream);
 		return deflate_host(ctx, lease, p, out, result);
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "deflate: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "deflate: unknown exception");
-	}
+	});
 }
 
 int cfhip_deflate_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out_device, size_t cap,
 	cfhip_deflate_result* result_device, void* stream_)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	try {
+	return guarded(ctx, "deflate_device", [&]() -> int {
 		LzPlan p;
 		int rc = deflate_check(ctx, "deflate_device", spans, n_spans, out_device, cap, result_device, false, &p);
 		if (rc != CFHIP_OK)
@@ -3799,7 +3867,7 @@ int cfhip_deflate_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_sp
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
 		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-		deflate_begin_call(ctx, lease.stream);
+		begin_call(ctx, lease.stream, kDeflateStages);
 		if (!p.total) {
 			// both sources are static: the copies may outlive the call
 			static const cfhip_deflate_result empty = deflate_empty_result();
@@ -3814,31 +3882,12 @@ int cfhip_deflate_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_sp
 				return rc;
 		}
 		return lease.done(!stream_);
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "deflate_device: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "deflate_device: unknown exception");
-	}
+	});
 }
 
 int cfhip_deflate_stage_ms(cfhip_ctx* ctx, float ms[CFDF_STAGES])
 {
-	if (!ctx || !ms)
-		return CFHIP_E_INVALID;
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	const size_t first = ctx->df_first_event, pairs = ctx->df_slices*CFDF_STAGES;
-	if (!pairs || first + 2*pairs > ctx->events_used || ctx->last_kernel.compare(0, 13, "cfhip_deflate") != 0)
-		return fail(ctx, CFHIP_E_INVALID, "deflate_stage_ms: the last call on this context was no cfhip_deflate*");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->events_stream));
-	for (int k = 0; k < CFDF_STAGES; ++k)
-		ms[k] = 0.0f;
-	for (size_t i = 0; i < pairs; ++i) {
-		float t = 0.0f;
-		HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->events[first + 2*i], ctx->events[first + 2*i + 1]));
-		ms[i % CFDF_STAGES] += t;
-	}
-	return CFHIP_OK;
+	return stage_ms(ctx, kDeflateStages, "deflate_stage_ms", ms, CFDF_STAGES);
 }
 
 int cfhip_deflate_code_lengths(cfhip_ctx* ctx, const uint32_t* counts, uint32_t n, uint32_t limit, uint8_t* lengths)
@@ -3858,8 +3907,7 @@ int cfhip_deflate_code_lengths(cfhip_ctx* ctx, const uint32_t* counts, uint32_t 
 		return fail(ctx, CFHIP_E_INVALID, "deflate_code_lengths: the counts sum to 2^32 or more");
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	StagingLease lease(ctx, ctx->stream);
-	deflate_begin_call(ctx, lease.stream);
-	ctx->df_slices = 0;
+	begin_call(ctx, lease.stream, kDeflateStages.kernel);     // the encoder's kernel name, and no stage log
 	int rc = lease.acquire();
 	if (rc == CFHIP_OK)
 		rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, 4096u);
@@ -3906,12 +3954,7 @@ static int zindex_check(cfhip_ctx* ctx, const char* what, const LzPlan& p, const
 int cfhip_deflate_indexed(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out, size_t cap,
 	cfhip_zindex_entry* index, size_t index_entries, cfhip_deflate_result* result)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	try {
+	return guarded(ctx, "deflate_indexed", [&]() -> int {
 		LzPlan p;
 		int rc = deflate_check(ctx, "deflate_indexed", spans, n_spans, out, cap, result, true, &p);
 		if (rc == CFHIP_OK)
@@ -3927,22 +3970,13 @@ int cfhip_deflate_indexed(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_s
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		StagingLease lease(ctx, ctx->stream);
 		return deflate_host(ctx, lease, p, out, result, index);
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "deflate_indexed: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "deflate_indexed: unknown exception");
-	}
+	});
 }
 
 int cfhip_deflate_indexed_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out_device, size_t cap,
 	cfhip_zindex_entry* index_device, size_t index_entries, cfhip_deflate_result* result_device, void* stream_)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	try {
+	return guarded(ctx, "deflate_indexed_device", [&]() -> int {
 		LzPlan p;
 		int rc = deflate_check(ctx, "deflate_indexed_device", spans, n_spans, out_device, cap, result_device, false, &p);
 		if (rc == CFHIP_OK)
@@ -3953,7 +3987,7 @@ int cfhip_deflate_indexed_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, siz
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
 		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-		deflate_begin_call(ctx, lease.stream);
+		begin_call(ctx, lease.stream, kDeflateStages);
 		if (!p.total) {
 			static const cfhip_deflate_result empty = deflate_empty_result();
 			HIP_TRY(ctx, hipMemcpyAsync(out_device, kDeflateEmpty, sizeof(kDeflateEmpty), hipMemcpyHostToDevice, lease.stream));
@@ -3967,11 +4001,7 @@ int cfhip_deflate_indexed_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, siz
 				return rc;
 		}
 		return lease.done(!stream_);
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "deflate_indexed_device: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "deflate_indexed_device: unknown exception");
-	}
+	});
 }
 
 static const char* const kInflateClass[8] = {"no", "wrapper", "index", "block header", "code", "distance", "overrun",
@@ -4000,8 +4030,8 @@ static int inflate_check(cfhip_ctx* ctx, const char* what, const void* z, size_t
 	return CFHIP_OK;
 }
 
-// The stream at z_device into out_device and the result into result_device, enqueued on the lease's stream: the output
-// in slices of whole groups, the state carried on the device.
+// The stream at z_device into out_device and the result into result_device: the output in slices of whole groups, the
+// state carried on the device.
 static int inflate_run(cfhip_ctx* ctx, StagingLease& lease, const uint8_t* z_device, size_t zbytes,
 	const cfinf_entry* index_device, uint8_t* out_device, size_t out_bytes, unsigned long long* result_device)
 {
@@ -4012,22 +4042,17 @@ static int inflate_run(cfhip_ctx* ctx, StagingLease& lease, const uint8_t* z_dev
 	if (rc != CFHIP_OK)
 		return rc;
 	uint8_t* base = static_cast<uint8_t*>(ctx->d_lz);
-	ctx->inf_first_event = ctx->events_used;
-	ctx->inf_slices = 0;
 	size_t at = 0;
 	do {
 		const size_t end = std::min(out_bytes, at + slice);
 		hipEvent_t ev[2*CFINF_STAGES];
-		for (int k = 0; k < CFINF_STAGES; ++k) {
-			rc = next_event_pair(ctx, &ev[2*k], &ev[2*k + 1]);
-			if (rc != CFHIP_OK)
-				return rc;
-		}
+		rc = take_event_pairs(ctx, ev, CFINF_STAGES);
+		if (rc != CFHIP_OK)
+			return rc;
 		const hipError_t e = cfhip_launch_inflate_slice(base, &lay, z_device, zbytes, index_device, out_bytes, at,
 			(uint32_t)(end - at), at == 0, out_device, ev, stream);
 		if (e != hipSuccess)
 			return fail(ctx, CFHIP_E_DEVICE, "inflate launch: %s", hipGetErrorString(e));
-		++ctx->inf_slices;
 		at = end;
 	} while (at < out_bytes);
 	const hipError_t e = cfhip_launch_inflate_final(reinterpret_cast<const unsigned long long*>(base + lay.state), z_device,
@@ -4035,12 +4060,6 @@ static int inflate_run(cfhip_ctx* ctx, StagingLease& lease, const uint8_t* z_dev
 	if (e != hipSuccess)
 		return fail(ctx, CFHIP_E_DEVICE, "inflate launch: %s", hipGetErrorString(e));
 	return CFHIP_OK;
-}
-
-static void inflate_begin_call(cfhip_ctx* ctx, hipStream_t stream)
-{
-	lz_begin_call(ctx, stream);
-	ctx->last_kernel = "cfhip_inflate_decode_kernel";
 }
 
 // A stream of no output bytes on the host: the walk from bit 16 through everything that produces no output, the
@@ -4071,12 +4090,8 @@ int cfhip_inflate(cfhip_ctx* ctx, const void* zstream, size_t zbytes, const cfhi
 	void* out, size_t out_bytes, cfhip_inflate_result* result)
 {
 	static_assert(sizeof(cfhip_inflate_result) == 7*sizeof(unsigned long long), "the final kernel's words are the struct");
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	try {
+	static_assert(CFINF_OK == 0, "download_checked's status of no error");
+	return guarded(ctx, "inflate", [&]() -> int {
 		int rc = inflate_check(ctx, "inflate", zstream, zbytes, index, index_entries, out, out_bytes, result, true);
 		if (rc != CFHIP_OK)
 			return rc;
@@ -4088,10 +4103,10 @@ int cfhip_inflate(cfhip_ctx* ctx, const void* zstream, size_t zbytes, const cfhi
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
 		StagingLease lease(ctx, ctx->stream);
-		inflate_begin_call(ctx, lease.stream);
+		begin_call(ctx, lease.stream, kInflateStages);
 		// the stream and behind it the index; the output and behind it the result
 		const size_t entries = cfhip_zindex_entries(out_bytes);
-		const size_t idx_off = (zbytes + 255u)/256u*256u, res_off = (out_bytes + 255u)/256u*256u;
+		const size_t idx_off = (zbytes + 255u)/256u*256u, res_off = result_offset(out_bytes);
 		rc = lease.acquire();
 		if (rc == CFHIP_OK)
 			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, idx_off + entries*sizeof(cfinf_entry));
@@ -4108,32 +4123,15 @@ int cfhip_inflate(cfhip_ctx* ctx, const void* zstream, size_t zbytes, const cfhi
 		rc = inflate_run(ctx, lease, d_z, zbytes, reinterpret_cast<const cfinf_entry*>(d_z + idx_off), d_out, out_bytes, d_res);
 		if (rc != CFHIP_OK)
 			return rc;
-		cfhip_inflate_result res;
-		HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
-		HIP_TRY(ctx, hipStreamSynchronize(lease.stream));
-		if (res.status == CFINF_OK)
-			HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, lease.stream));
-		rc = lease.done(true);
-		if (rc != CFHIP_OK)
-			return rc;
-		*result = res;
-		return inflate_verdict(ctx, res);
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "inflate: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "inflate: unknown exception");
-	}
+		rc = download_checked(ctx, lease, d_res, d_out, out_bytes, out, result);
+		return rc == CFHIP_OK ? inflate_verdict(ctx, *result) : rc;
+	});
 }
 
 int cfhip_inflate_device(cfhip_ctx* ctx, const void* zstream_device, size_t zbytes, const cfhip_zindex_entry* index_device,
 	size_t index_entries, void* out_device, size_t out_bytes, cfhip_inflate_result* result_device, void* stream_)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	try {
+	return guarded(ctx, "inflate_device", [&]() -> int {
 		int rc = inflate_check(ctx, "inflate_device", zstream_device, zbytes, index_device, index_entries, out_device, out_bytes,
 			result_device, false);
 		if (rc != CFHIP_OK)
@@ -4142,7 +4140,7 @@ int cfhip_inflate_device(cfhip_ctx* ctx, const void* zstream_device, size_t zbyt
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
 		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-		inflate_begin_call(ctx, lease.stream);
+		begin_call(ctx, lease.stream, kInflateStages);
 		rc = lease.acquire();
 		if (rc == CFHIP_OK)
 			rc = inflate_run(ctx, lease, static_cast<const uint8_t*>(zstream_device), zbytes,
@@ -4151,45 +4149,18 @@ int cfhip_inflate_device(cfhip_ctx* ctx, const void* zstream_device, size_t zbyt
 		if (rc != CFHIP_OK)
 			return rc;
 		return lease.done(!stream_);
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "inflate_device: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "inflate_device: unknown exception");
-	}
+	});
 }
 
 int cfhip_inflate_stage_ms(cfhip_ctx* ctx, float ms[CFINF_STAGES])
 {
-	if (!ctx || !ms)
-		return CFHIP_E_INVALID;
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	const size_t first = ctx->inf_first_event, pairs = ctx->inf_slices*CFINF_STAGES;
-	if (!pairs || first + 2*pairs > ctx->events_used || ctx->last_kernel.compare(0, 13, "cfhip_inflate") != 0)
-		return fail(ctx, CFHIP_E_INVALID, "inflate_stage_ms: the last call on this context was no cfhip_inflate*");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->events_stream));
-	for (int k = 0; k < CFINF_STAGES; ++k)
-		ms[k] = 0.0f;
-	for (size_t i = 0; i < pairs; ++i) {
-		float t = 0.0f;
-		HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->events[first + 2*i], ctx->events[first + 2*i + 1]));
-		ms[i % CFINF_STAGES] += t;
-	}
-	return CFHIP_OK;
+	return stage_ms(ctx, kInflateStages, "inflate_stage_ms", ms, CFINF_STAGES);
 }
 
 // ---- LZ4 frames, both ways (csrc/lz4.hip, csrc/lz4.h; the definition is tests/lz4_ref.py) ---------------------------
 size_t cfhip_lz4_bound(size_t n)
 {
 	return cflz4_bound(n);
-}
-
-static void lz4_begin_call(cfhip_ctx* ctx, hipStream_t stream, const char* kernel)
-{
-	lz_begin_call(ctx, stream);
-	ctx->last_kernel = kernel;
-	ctx->lz_slices = 0;                       // "cfhip_lz4" begins with the estimator's prefix: its stage times end here
-	ctx->l4_pairs = 0;
 }
 
 // Every check of an encoder call, made before the context is touched.
@@ -4225,47 +4196,42 @@ static void lz4_empty_frame(uint8_t out[CFLZ4_HEADER + 4u])
 	memset(out + CFLZ4_HEADER, 0, 4u);
 }
 
-// The frame of p (total > 0) into out_device and the result into result_device, enqueued on the lease's stream: slices
-// of whole blocks without a carry (blocks are independent), the state carried on the device.
+// The frame of p (total > 0) into out_device and the result into result_device: slices of whole blocks without a carry
+// (blocks are independent), the state carried on the device.
 static int lz4_run(cfhip_ctx* ctx, StagingLease& lease, const LzPlan& p, hipMemcpyKind kind, uint8_t* out_device,
 	unsigned long long* result_device)
 {
 	const hipStream_t stream = lease.stream;
-	const size_t slice = std::min(lz_slice_of(ctx), (p.total + CFLZ4_BLOCK - 1u)/CFLZ4_BLOCK*CFLZ4_BLOCK);
-	size_t sort_bytes = 0;
-	HIP_TRY(ctx, cfhip_lz_sort_bytes(slice + CFLZ_WINDOW, &sort_bytes));
+	size_t slice = 0, sort_bytes = 0;
+	int rc = lz_slice_plan(ctx, p.total, CFLZ4_BLOCK, &slice, &sort_bytes);
+	if (rc != CFHIP_OK)
+		return rc;
 	const cflz4_layout lay = cflz4_scratch(slice, sort_bytes);
-	int rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, lay.total);
+	rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, lay.total);
 	if (rc != CFHIP_OK)
 		return rc;
 	uint8_t* base = static_cast<uint8_t*>(ctx->d_lz);
-	ctx->l4_first_event = ctx->events_used;
-	ctx->l4_pairs = 0;
 	for (size_t s0 = 0; s0 < p.total; s0 += slice) {
 		const size_t s1 = std::min(p.total, s0 + slice);
 		rc = lz_gather(ctx, p, s0, s1, base + lay.lz.bytes, kind, stream);
 		if (rc != CFHIP_OK)
 			return rc;
 		hipEvent_t ev[2*(CFLZ4_STAGES - 1)];
-		for (int k = 0; k < CFLZ4_STAGES - 1; ++k) {
-			rc = next_event_pair(ctx, &ev[2*k], &ev[2*k + 1]);
-			if (rc != CFHIP_OK)
-				return rc;
-		}
+		rc = take_event_pairs(ctx, ev, CFLZ4_STAGES - 1);
+		if (rc != CFHIP_OK)
+			return rc;
 		const hipError_t e = cfhip_launch_lz4_slice(base, &lay, sort_bytes, (uint32_t)(s1 - s0), s0 == 0, out_device, ev, stream);
 		if (e != hipSuccess)
 			return fail(ctx, CFHIP_E_DEVICE, "lz4_encode launch: %s", hipGetErrorString(e));
-		ctx->l4_pairs += CFLZ4_STAGES - 1;
 	}
 	hipEvent_t ev[2];
-	rc = next_event_pair(ctx, &ev[0], &ev[1]);
+	rc = take_event_pairs(ctx, ev, 1);
 	if (rc != CFHIP_OK)
 		return rc;
 	const hipError_t e = cfhip_launch_lz4_final(reinterpret_cast<const unsigned long long*>(base + lay.state),
 		(unsigned long long)p.total, out_device, result_device, ev, stream);
 	if (e != hipSuccess)
 		return fail(ctx, CFHIP_E_DEVICE, "lz4_encode launch: %s", hipGetErrorString(e));
-	ctx->l4_pairs += 1;
 	return CFHIP_OK;
 }
 
@@ -4273,12 +4239,7 @@ int cfhip_lz4_encode(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans,
 	cfhip_lz4_result* result)
 {
 	static_assert(sizeof(cfhip_lz4_result) == 7*sizeof(unsigned long long), "the final kernel's words are the struct");
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	try {
+	return guarded(ctx, "lz4_encode", [&]() -> int {
 		LzPlan p;
 		int rc = lz4_check(ctx, "lz4_encode", spans, n_spans, out, cap, result, true, &p);
 		if (rc != CFHIP_OK)
@@ -4292,9 +4253,8 @@ int cfhip_lz4_encode(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans,
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
 		StagingLease lease(ctx, ctx->stream);
-		lz4_begin_call(ctx, lease.stream, "cfhip_lz4_emit_kernel");
-		// the result lies behind the frame's bytes, 256-byte aligned
-		const size_t res_off = (cflz4_bound(p.total) + 255u)/256u*256u;
+		begin_call(ctx, lease.stream, kLz4EncodeStages);
+		const size_t res_off = result_offset(cflz4_bound(p.total));
 		rc = lease.acquire();
 		if (rc == CFHIP_OK)
 			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, res_off + 256u);
@@ -4305,33 +4265,14 @@ int cfhip_lz4_encode(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans,
 		rc = lz4_run(ctx, lease, p, hipMemcpyHostToDevice, d_out, d_res);
 		if (rc != CFHIP_OK)
 			return rc;
-		cfhip_lz4_result res;
-		HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
-		HIP_TRY(ctx, hipStreamSynchronize(lease.stream));
-		if (res.bytes_out > cflz4_bound(p.total))
-			return fail(ctx, CFHIP_E_DEVICE, "lz4_encode: %llu bytes exceed the bound", (unsigned long long)res.bytes_out);
-		HIP_TRY(ctx, hipMemcpyAsync(out, d_out, (size_t)res.bytes_out, hipMemcpyDeviceToHost, lease.stream));
-		rc = lease.done(true);
-		if (rc != CFHIP_OK)
-			return rc;
-		*result = res;
-		return CFHIP_OK;
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "lz4_encode: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "lz4_encode: unknown exception");
-	}
+		return download_sized(ctx, lease, "lz4_encode", d_res, d_out, cflz4_bound(p.total), out, result);
+	});
 }
 
 int cfhip_lz4_encode_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_spans, void* out_device, size_t cap,
 	cfhip_lz4_result* result_device, void* stream_)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	try {
+	return guarded(ctx, "lz4_encode_device", [&]() -> int {
 		LzPlan p;
 		int rc = lz4_check(ctx, "lz4_encode_device", spans, n_spans, out_device, cap, result_device, false, &p);
 		if (rc != CFHIP_OK)
@@ -4340,7 +4281,7 @@ int cfhip_lz4_encode_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
 		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-		lz4_begin_call(ctx, lease.stream, "cfhip_lz4_emit_kernel");
+		begin_call(ctx, lease.stream, kLz4EncodeStages);
 		if (!p.total) {
 			// both sources are static: the copies may outlive the call
 			static const cfhip_lz4_result empty = lz4_empty_result();
@@ -4356,40 +4297,12 @@ int cfhip_lz4_encode_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n
 				return rc;
 		}
 		return lease.done(!stream_);
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "lz4_encode_device: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "lz4_encode_device: unknown exception");
-	}
-}
-
-// The event pairs [first, first + pairs) of the last call summed into ms[0 .. n) by stage: a slice's `per_slice` stages
-// repeat, the rest follow once.
-static int lz4_stage_ms(cfhip_ctx* ctx, const char* what, const char* prefix, size_t per_slice, size_t stages, float* ms, size_t n)
-{
-	if (!ctx || !ms || n > stages)
-		return CFHIP_E_INVALID;
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	const size_t first = ctx->l4_first_event, pairs = ctx->l4_pairs;
-	if (!pairs || first + 2*pairs > ctx->events_used || ctx->last_kernel.compare(0, strlen(prefix), prefix) != 0)
-		return fail(ctx, CFHIP_E_INVALID, "%s: the last call on this context was no %s*", what, what);
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->events_stream));
-	std::vector<float> sum(stages, 0.0f);
-	const size_t tail = stages - per_slice;                  // pairs = slices x per_slice + tail
-	for (size_t i = 0; i < pairs; ++i) {
-		float t = 0.0f;
-		HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->events[first + 2*i], ctx->events[first + 2*i + 1]));
-		sum[i < pairs - tail ? i % per_slice : per_slice + (i - (pairs - tail))] += t;
-	}
-	for (size_t k = 0; k < n; ++k)
-		ms[k] = sum[k];
-	return CFHIP_OK;
+	});
 }
 
 int cfhip_lz4_encode_stage_ms(cfhip_ctx* ctx, float* ms, size_t n)
 {
-	return lz4_stage_ms(ctx, "cfhip_lz4_encode", "cfhip_lz4_emit", CFLZ4_STAGES - 1, CFLZ4_STAGES, ms, n);
+	return stage_ms(ctx, kLz4EncodeStages, "cfhip_lz4_encode", ms, n);
 }
 
 static const char* const kLz4Class[8] = {"no", "header", "unsupported", "blocks", "checksum", "sequence", "offset", "size"};
@@ -4418,19 +4331,14 @@ static int lz4d_run(cfhip_ctx* ctx, StagingLease& lease, const uint8_t* z_device
 	int rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, lay.total);
 	if (rc != CFHIP_OK)
 		return rc;
-	ctx->l4_first_event = ctx->events_used;
-	ctx->l4_pairs = 0;
 	hipEvent_t ev[2*CFLZ4_DSTAGES];
-	for (int k = 0; k < CFLZ4_DSTAGES; ++k) {
-		rc = next_event_pair(ctx, &ev[2*k], &ev[2*k + 1]);
-		if (rc != CFHIP_OK)
-			return rc;
-	}
+	rc = take_event_pairs(ctx, ev, CFLZ4_DSTAGES);
+	if (rc != CFHIP_OK)
+		return rc;
 	const hipError_t e = cfhip_launch_lz4_decode(static_cast<uint8_t*>(ctx->d_lz), &lay, z_device, bytes, out_device, out_bytes,
 		result_device, ev, lease.stream);
 	if (e != hipSuccess)
 		return fail(ctx, CFHIP_E_DEVICE, "lz4_decode launch: %s", hipGetErrorString(e));
-	ctx->l4_pairs = CFLZ4_DSTAGES;
 	return CFHIP_OK;
 }
 
@@ -4458,12 +4366,8 @@ int cfhip_lz4_decode(cfhip_ctx* ctx, const void* frame, size_t bytes, void* out,
 	cfhip_lz4_decode_result* result)
 {
 	static_assert(sizeof(cfhip_lz4_decode_result) == 9*sizeof(unsigned long long), "the final kernel's words are the struct");
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	try {
+	static_assert(CFLZ4_OK == 0, "download_checked's status of no error");
+	return guarded(ctx, "lz4_decode", [&]() -> int {
 		int rc = lz4d_check(ctx, "lz4_decode", frame, bytes, out, out_bytes, result, true);
 		if (rc != CFHIP_OK)
 			return rc;
@@ -4475,8 +4379,8 @@ int cfhip_lz4_decode(cfhip_ctx* ctx, const void* frame, size_t bytes, void* out,
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
 		StagingLease lease(ctx, ctx->stream);
-		lz4_begin_call(ctx, lease.stream, "cfhip_lz4_block_kernel");
-		const size_t res_off = (out_bytes + 255u)/256u*256u;
+		begin_call(ctx, lease.stream, kLz4DecodeStages);
+		const size_t res_off = result_offset(out_bytes);
 		rc = lease.acquire();
 		if (rc == CFHIP_OK)
 			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, std::max(bytes, (size_t)1));
@@ -4492,32 +4396,15 @@ int cfhip_lz4_decode(cfhip_ctx* ctx, const void* frame, size_t bytes, void* out,
 		rc = lz4d_run(ctx, lease, d_z, bytes, d_out, out_bytes, d_res);
 		if (rc != CFHIP_OK)
 			return rc;
-		cfhip_lz4_decode_result res;
-		HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
-		HIP_TRY(ctx, hipStreamSynchronize(lease.stream));
-		if (res.status == CFLZ4_OK)
-			HIP_TRY(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, lease.stream));
-		rc = lease.done(true);
-		if (rc != CFHIP_OK)
-			return rc;
-		*result = res;
-		return lz4d_verdict(ctx, res);
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "lz4_decode: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "lz4_decode: unknown exception");
-	}
+		rc = download_checked(ctx, lease, d_res, d_out, out_bytes, out, result);
+		return rc == CFHIP_OK ? lz4d_verdict(ctx, *result) : rc;
+	});
 }
 
 int cfhip_lz4_decode_device(cfhip_ctx* ctx, const void* frame_device, size_t bytes, void* out_device, size_t out_bytes,
 	cfhip_lz4_decode_result* result_device, void* stream_)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	try {
+	return guarded(ctx, "lz4_decode_device", [&]() -> int {
 		int rc = lz4d_check(ctx, "lz4_decode_device", frame_device, bytes, out_device, out_bytes, result_device, false);
 		if (rc != CFHIP_OK)
 			return rc;
@@ -4525,7 +4412,7 @@ int cfhip_lz4_decode_device(cfhip_ctx* ctx, const void* frame_device, size_t byt
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
 		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-		lz4_begin_call(ctx, lease.stream, "cfhip_lz4_block_kernel");
+		begin_call(ctx, lease.stream, kLz4DecodeStages);
 		rc = lease.acquire();
 		if (rc == CFHIP_OK)
 			rc = lz4d_run(ctx, lease, static_cast<const uint8_t*>(frame_device), bytes, static_cast<uint8_t*>(out_device),
@@ -4533,16 +4420,12 @@ int cfhip_lz4_decode_device(cfhip_ctx* ctx, const void* frame_device, size_t byt
 		if (rc != CFHIP_OK)
 			return rc;
 		return lease.done(!stream_);
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "lz4_decode_device: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "lz4_decode_device: unknown exception");
-	}
+	});
 }
 
 int cfhip_lz4_decode_stage_ms(cfhip_ctx* ctx, float* ms, size_t n)
 {
-	return lz4_stage_ms(ctx, "cfhip_lz4_decode", "cfhip_lz4_block", CFLZ4_DSTAGES, CFLZ4_DSTAGES, ms, n);
+	return stage_ms(ctx, kLz4DecodeStages, "cfhip_lz4_decode", ms, n);
 }
 
 // ---- PNG files of images (csrc/png.hip, csrc/png.h; the definition is tests/png_ref.py) ----------------------------
@@ -4604,14 +4487,6 @@ static int png_check(cfhip_ctx* ctx, const char* what, const void* pixels, int p
 	return CFHIP_OK;
 }
 
-static void png_begin_call(cfhip_ctx* ctx, hipStream_t stream)
-{
-	lz_begin_call(ctx, stream);
-	ctx->last_kernel = "cfhip_png_filter_kernel";
-	ctx->lz_slices = ctx->df_slices = 0;
-	ctx->png_pairs = 0;
-}
-
 // The file of the image at pixels_device into out_device and the result into result_device, enqueued on the lease's stream.
 static int png_run(cfhip_ctx* ctx, StagingLease& lease, const PngPlan& p, const void* pixels_device, int pixel_type, size_t pitch,
 	uint32_t width, uint32_t height, int color_type, int bit_depth, uint8_t* out_device, unsigned long long* result_device)
@@ -4635,17 +4510,16 @@ static int png_run(cfhip_ctx* ctx, StagingLease& lease, const PngPlan& p, const 
 	uint8_t* data = out_device + head.bytes;
 	uint8_t* z = in_place ? data : base + lay.zstream;
 	HIP_TRY(ctx, hipMemsetAsync(state, 0, CFPNG_S_WORDS*4u, stream));
-	ctx->png_first_event = ctx->events_used;
-	hipEvent_t a, b;
-	rc = next_event_pair(ctx, &a, &b);
+	hipEvent_t ev[2];
+	rc = take_event_pairs(ctx, ev, 1);
 	if (rc != CFHIP_OK)
 		return rc;
-	HIP_TRY(ctx, hipEventRecord(a, stream));
+	HIP_TRY(ctx, hipEventRecord(ev[0], stream));
 	hipError_t e = cfhip_launch_png_filter(pixels_device, pixel_type, pitch, width, height, color_type, bit_depth,
 		base + lay.filtered, state, stream);
 	if (e != hipSuccess)
 		return fail(ctx, CFHIP_E_DEVICE, "png_encode launch: %s", hipGetErrorString(e));
-	HIP_TRY(ctx, hipEventRecord(b, stream));
+	HIP_TRY(ctx, hipEventRecord(ev[1], stream));
 	LzPlan lz;
 	cfhip_lz_span span;
 	span.bytes = base + lay.filtered;
@@ -4655,35 +4529,29 @@ static int png_run(cfhip_ctx* ctx, StagingLease& lease, const PngPlan& p, const 
 	rc = deflate_run(ctx, lease, lz, hipMemcpyDeviceToDevice, z, reinterpret_cast<unsigned long long*>(state + CFPNG_S_DEFLATE));
 	if (rc != CFHIP_OK)
 		return rc;
-	rc = next_event_pair(ctx, &a, &b);
+	rc = take_event_pairs(ctx, ev, 1);
 	if (rc != CFHIP_OK)
 		return rc;
-	HIP_TRY(ctx, hipEventRecord(a, stream));
+	HIP_TRY(ctx, hipEventRecord(ev[0], stream));
 	e = cfhip_launch_png_crc(z, data, zbound, state, stream);
 	if (e != hipSuccess)
 		return fail(ctx, CFHIP_E_DEVICE, "png_encode launch: %s", hipGetErrorString(e));
-	HIP_TRY(ctx, hipEventRecord(b, stream));
-	rc = next_event_pair(ctx, &a, &b);
+	HIP_TRY(ctx, hipEventRecord(ev[1], stream));
+	rc = take_event_pairs(ctx, ev, 1);
 	if (rc != CFHIP_OK)
 		return rc;
-	HIP_TRY(ctx, hipEventRecord(a, stream));
+	HIP_TRY(ctx, hipEventRecord(ev[0], stream));
 	e = cfhip_launch_png_final(&head, z, p.filtered, state, out_device, result_device, stream);
 	if (e != hipSuccess)
 		return fail(ctx, CFHIP_E_DEVICE, "png_encode launch: %s", hipGetErrorString(e));
-	HIP_TRY(ctx, hipEventRecord(b, stream));
-	ctx->png_pairs = (ctx->events_used - ctx->png_first_event)/2u;
+	HIP_TRY(ctx, hipEventRecord(ev[1], stream));
 	return CFHIP_OK;
 }
 
 int cfhip_png_encode(cfhip_ctx* ctx, const void* pixels, int pixel_type, size_t pitch_bytes, uint32_t width, uint32_t height,
 	int color_type, int bit_depth, int color_space, void* out, size_t cap, cfhip_png_result* result)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	try {
+	return guarded(ctx, "png_encode", [&]() -> int {
 		PngPlan p;
 		int rc = png_check(ctx, "png_encode", pixels, pixel_type, pitch_bytes, width, height, color_type, bit_depth, color_space,
 			out, cap, result, true, &p);
@@ -4693,10 +4561,10 @@ int cfhip_png_encode(cfhip_ctx* ctx, const void* pixels, int pixel_type, size_t 
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
 		StagingLease lease(ctx, ctx->stream);
-		png_begin_call(ctx, lease.stream);
+		begin_call(ctx, lease.stream, kPngStages);
 		// the file starts where its IDAT data falls on a word; the result lies behind it, 256-byte aligned
 		const size_t lead = (4u - cfpng_data_offset(p.srgb) % 4u) % 4u;
-		const size_t res_off = (lead + p.bound + 255u)/256u*256u;
+		const size_t res_off = result_offset(lead + p.bound);
 		const size_t row = (size_t)width*p.texel;
 		rc = lease.acquire();
 		if (rc == CFHIP_OK)
@@ -4711,34 +4579,15 @@ int cfhip_png_encode(cfhip_ctx* ctx, const void* pixels, int pixel_type, size_t 
 		rc = png_run(ctx, lease, p, ctx->d_src, pixel_type, row, width, height, color_type, bit_depth, d_file, d_res);
 		if (rc != CFHIP_OK)
 			return rc;
-		cfhip_png_result res;
-		HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, lease.stream));
-		HIP_TRY(ctx, hipStreamSynchronize(lease.stream));
-		if (res.bytes_out > p.bound)
-			return fail(ctx, CFHIP_E_DEVICE, "png_encode: %llu bytes exceed the bound", (unsigned long long)res.bytes_out);
-		HIP_TRY(ctx, hipMemcpyAsync(out, d_file, (size_t)res.bytes_out, hipMemcpyDeviceToHost, lease.stream));
-		rc = lease.done(true);
-		if (rc != CFHIP_OK)
-			return rc;
-		*result = res;
-		return CFHIP_OK;
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "png_encode: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "png_encode: unknown exception");
-	}
+		return download_sized(ctx, lease, "png_encode", d_res, d_file, p.bound, out, result);
+	});
 }
 
 int cfhip_png_encode_device(cfhip_ctx* ctx, const void* pixels_device, int pixel_type, size_t pitch_bytes, uint32_t width,
 	uint32_t height, int color_type, int bit_depth, int color_space, void* out_device, size_t cap,
 	cfhip_png_result* result_device, void* stream_)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	try {
+	return guarded(ctx, "png_encode_device", [&]() -> int {
 		PngPlan p;
 		int rc = png_check(ctx, "png_encode_device", pixels_device, pixel_type, pitch_bytes, width, height, color_type, bit_depth,
 			color_space, out_device, cap, result_device, false, &p);
@@ -4748,7 +4597,7 @@ int cfhip_png_encode_device(cfhip_ctx* ctx, const void* pixels_device, int pixel
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
 		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-		png_begin_call(ctx, lease.stream);
+		begin_call(ctx, lease.stream, kPngStages);
 		rc = lease.acquire();
 		if (rc == CFHIP_OK)
 			rc = png_run(ctx, lease, p, pixels_device, pixel_type, pitch_bytes, width, height, color_type, bit_depth,
@@ -4756,35 +4605,13 @@ int cfhip_png_encode_device(cfhip_ctx* ctx, const void* pixels_device, int pixel
 		if (rc != CFHIP_OK)
 			return rc;
 		return lease.done(!stream_);
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "png_encode_device: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "png_encode_device: unknown exception");
-	}
+	});
 }
 
 int cfhip_png_stage_ms(cfhip_ctx* ctx, float ms[CFPNG_STAGES])
 {
 	static_assert(CFPNG_STAGES == 1 + CFDF_STAGES + 2, "filter, the encoder's stages, crc, final");
-	if (!ctx || !ms)
-		return CFHIP_E_INVALID;
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	const size_t first = ctx->png_first_event, pairs = ctx->png_pairs;
-	if (pairs < 3u + CFDF_STAGES || (pairs - 3u) % CFDF_STAGES || first + 2*pairs > ctx->events_used ||
-		ctx->last_kernel.compare(0, 9, "cfhip_png") != 0)
-		return fail(ctx, CFHIP_E_INVALID, "png_stage_ms: the last call on this context was no cfhip_png_encode*");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	HIP_TRY(ctx, hipStreamSynchronize(ctx->events_stream));
-	for (int k = 0; k < CFPNG_STAGES; ++k)
-		ms[k] = 0.0f;
-	for (size_t i = 0; i < pairs; ++i) {
-		float t = 0.0f;
-		HIP_TRY(ctx, hipEventElapsedTime(&t, ctx->events[first + 2*i], ctx->events[first + 2*i + 1]));
-		// the first pair is the filter's, the last two are crc and final, the encoder's slices lie between
-		const size_t k = i == 0 ? 0u : i >= pairs - 2u ? CFPNG_STAGES - (pairs - i) : 1u + (i - 1u) % CFDF_STAGES;
-		ms[k] += t;
-	}
-	return CFHIP_OK;
+	return stage_ms(ctx, kPngStages, "png_stage_ms", ms, CFPNG_STAGES);
 }
 
 // cfhip_rdo_target and cfhip_rdo_target_device
@@ -4823,6 +4650,7 @@ static int rdo_target(cfhip_ctx* ctx, const char* what, int format, int type, co
 	// every launch of the search is timed: the call's event pairs start here and every trial adds its own
 	if (!ctx->profiling)
 		ctx->events_used = 0;
+	ctx->stages.owner = nullptr;                  // the search's estimates (lz_run) belong to no stage log
 	rc = lease.acquire();
 	if (rc != CFHIP_OK)
 		return rc;
