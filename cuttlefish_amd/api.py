@@ -8,7 +8,7 @@ from __future__ import annotations
 import ctypes
 import enum
 import os
-from typing import Iterable, List, Optional, Sequence
+from typing import Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -204,7 +204,7 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_lz4_bound", "cfhip_lz4_encode", "cfhip_lz4_encode_device", "cfhip_lz4_encode_stage_ms",
            "cfhip_lz4_decode", "cfhip_lz4_decode_device", "cfhip_lz4_decode_stage_ms",
            "cfhip_png_bound", "cfhip_png_encode", "cfhip_png_encode_device", "cfhip_png_stage_ms",
-           "cfhip_mip_post_array_device", "cfhip_alpha_coverage_device"]
+           "cfhip_mip_post_array_device", "cfhip_alpha_coverage_device", "cfhip_alpha_bleed_array_device"]
 
 
 class Layout(enum.IntEnum):
@@ -497,6 +497,40 @@ def make_mip_post_params(alpha_coverage: Optional[float] = None, normalize: Opti
     return MipPostParams(flags, float(alpha_coverage) if alpha_coverage is not None else 0.0)
 
 
+BLEED_WRAP_X, BLEED_WRAP_Y = 1, 2                # cfhip_bleed_params.flags
+
+
+class BleedParams(ctypes.Structure):
+    """cfhip_bleed_params"""
+    _fields_ = [("flags", ctypes.c_uint32), ("alpha_threshold", ctypes.c_float), ("max_distance", ctypes.c_uint32)]
+
+
+class BleedResult(ctypes.Structure):
+    """cfhip_bleed_result: one surface's seeds, its filled texels and the largest squared distance a colour travelled"""
+    _fields_ = [("seeds", ctypes.c_uint32), ("filled", ctypes.c_uint32), ("max_dist2", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+BLEED_RESULT_DTYPE = np.dtype([("seeds", np.uint32), ("filled", np.uint32), ("max_dist2", np.uint32),
+                               ("reserved", np.uint32)])
+
+
+def wrap_axes(wrap) -> Tuple[bool, bool]:
+    """wrap as the bleed methods take it: one bool for both axes, or (x, y)"""
+    if isinstance(wrap, (bool, np.bool_)):
+        return bool(wrap), bool(wrap)
+    x, y = wrap
+    return bool(x), bool(y)
+
+
+def make_bleed_params(threshold: float = 0.0, wrap=(False, False), max_distance: int = 0) -> BleedParams:
+    """threshold: texels with alpha > threshold are the seeds (0 <= threshold < 1); wrap: a bool or (x, y), the axes
+    on which the surface tiles; max_distance: how far a colour may travel in texels, 0 = unlimited.  Ranges are the
+    library's to check."""
+    wx, wy = wrap_axes(wrap)
+    return BleedParams((BLEED_WRAP_X if wx else 0) | (BLEED_WRAP_Y if wy else 0), float(threshold), int(max_distance))
+
+
 RDO_NO_CAP = 0xFFFFFFFF         # max_sse_increase: no cap
 RDO_ROW_ABOVE = 1               # CFHIP_RDO_ROW_ABOVE
 
@@ -611,6 +645,10 @@ def load_library(path: Optional[str] = None):
     L.cfhip_alpha_coverage_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(CoverageSurface), ctypes.c_uint32,
                                               ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_alpha_coverage_device.restype = ctypes.c_int
+    L.cfhip_alpha_bleed_array_device.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
+        ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(BleedParams), ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_alpha_bleed_array_device.restype = ctypes.c_int
     L.cfhip_generate_mips3d_device.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
         ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
@@ -1144,6 +1182,38 @@ class Context:
         self.alpha_coverage_device([dict(pixels=dev.data_ptr(), pixel_type=pt, width=host.shape[1], height=host.shape[0],
                                          row_pitch_bytes=host.strides[0])], threshold, out.data_ptr(), scale)
         return int(out.cpu().numpy().view(np.uint32)[0])
+
+    def alpha_bleed_device(self, images: Sequence[int], pixel_type, width: int, height: int, row_pitch_bytes: int,
+                           threshold: float = 0.0, wrap=(False, False), max_distance: int = 0, results: int = 0,
+                           stream: int = 0):
+        """Alpha bleeding in place (cfhip_alpha_bleed_array_device): on each of the device surfaces images[l] (all of
+        one size and pixel type) every texel with alpha <= threshold takes the R, G, B bits of the nearest texel with
+        alpha > threshold, found by a jump flood; alpha is untouched.  wrap: a bool or (x, y), the axes on which the
+        surface tiles; max_distance: how far a colour may travel, 0 = unlimited.  results: device pointer to len(images)
+        cfhip_bleed_result records (BLEED_RESULT_DTYPE), or 0 for none.  One call is 2 + log2(P) launches whatever the
+        number of layers, and takes 8 bytes of the context's scratch per texel.  The remedy for straight alpha: run it
+        before mips and encoding, not on premultiplied colour."""
+        nl = len(images)
+        params = make_bleed_params(threshold, wrap, max_distance)
+        arr = (ctypes.c_void_p * max(nl, 1))(*[ctypes.c_void_p(int(p)) for p in images])
+        self._check(self._lib.cfhip_alpha_bleed_array_device(
+            self._h, arr, nl, int(pixel_type), width, height, row_pitch_bytes, ctypes.byref(params),
+            ctypes.c_void_p(int(results)) if results else None, ctypes.c_void_p(stream) if stream else None))
+
+    def alpha_bleed(self, image: np.ndarray, threshold: float = 0.0, wrap=(False, False), max_distance: int = 0):
+        """Host convenience: one (h, w, 4) uint8 / float16 / float32 image through alpha_bleed_device -> (the bled
+        array of the same dtype, the record as a dict of seeds, filled, max_dist2, reserved)."""
+        import torch
+        host = np.ascontiguousarray(image)
+        if host.ndim != 3 or host.shape[2] != 4:
+            raise ValueError("expected (h, w, 4)")
+        pt = pixel_type_of(host)
+        dev = torch.from_numpy(host.view(np.uint8)).to("cuda:%d" % self.device_id)
+        res = torch.zeros(4, dtype=torch.int32, device=dev.device)
+        self.alpha_bleed_device([dev.data_ptr()], pt, host.shape[1], host.shape[0], host.strides[0], threshold, wrap,
+                                max_distance, res.data_ptr())
+        rec = res.cpu().numpy().view(BLEED_RESULT_DTYPE)[0]
+        return dev.cpu().numpy().view(host.dtype), {k: int(rec[k]) for k in rec.dtype.names}
 
     def generate_mips3d_device(self, src: int, pixel_type, width: int, height: int, depth: int,
                                row_pitch_bytes: int, slice_pitch_bytes: int, dst_levels: Sequence[int],

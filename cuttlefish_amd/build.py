@@ -163,7 +163,9 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  "cfhip_png_filter_kernel", "cfhip_png_crc_kernel", "cfhip_png_final_kernel",
                  # the mip post-pass (csrc/mip_post.hip): alpha coverage and normal renormalisation
                  "cfhip_mip_post_gather_kernel", "cfhip_mip_post_count_kernel", "cfhip_mip_post_decide_kernel",
-                 "cfhip_mip_post_apply_kernel")
+                 "cfhip_mip_post_apply_kernel",
+                 # alpha bleeding (csrc/alpha_bleed.hip): pass 0, a step of the flood, the last step fused with the fill
+                 "cfhip_alpha_bleed_seed_kernel", "cfhip_alpha_bleed_step_kernel", "cfhip_alpha_bleed_fill_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

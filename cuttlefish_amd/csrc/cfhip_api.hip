@@ -17,6 +17,7 @@
 #include "lz4.h"
 #include "png.h"
 #include "mip_post.h"
+#include "alpha_bleed.h"
 #include "stage_log.h"
 #include "../../include/cuttlefish_hip.h"
 
@@ -2319,6 +2320,102 @@ int cfhip_mip_post_array_device(cfhip_ctx* ctx, const void* const* srcs, uint32_
 		}
 	}
 	MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_apply(d_tab, (uint32_t)nlev, (uint32_t)wg_levels, flags, d_state, stream));
+	return lease.done(!stream_);
+}
+
+// ---- alpha bleeding (csrc/alpha_bleed.hip): colour under transparent texels from the nearest visible one -------------
+// one launch of the pass, timed like every encode launch (cfhip_last_kernel_ms / profiling)
+#define BLEED_TIMED(ctx, stream, launch_expr) do { \
+		hipEvent_t a_, b_; \
+		const int rc_ = next_event_pair((ctx), &a_, &b_); \
+		if (rc_ != CFHIP_OK) return rc_; \
+		HIP_TRY((ctx), hipEventRecord(a_, (stream))); \
+		const hipError_t le_ = (launch_expr); \
+		if (le_ != hipSuccess) return fail((ctx), CFHIP_E_DEVICE, "alpha_bleed launch: %s", hipGetErrorString(le_)); \
+		HIP_TRY((ctx), hipEventRecord(b_, (stream))); \
+	} while (0)
+
+int cfhip_alpha_bleed_array_device(cfhip_ctx* ctx, void* const* images, uint32_t layers, int pixel_type, uint32_t width,
+	uint32_t height, size_t pitch_bytes, const cfhip_bleed_params* params, cfhip_bleed_result* results_device, void* stream_)
+{
+	static_assert(sizeof(cfhip_bleed_params) == 12 && sizeof(cfhip_bleed_result) == 16, "the ABI's sizes");
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	if (!params)
+		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params is NULL");
+	if (!images)
+		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: images is NULL");
+	if (!layers || layers > 65535u)
+		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: layers is %u (1 to 65535 per call)", layers);
+	if (!width || !height || width > CFAB_MAX_SIDE || height > CFAB_MAX_SIDE)
+		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: width and height are 1 to %u each, not %ux%u", CFAB_MAX_SIDE, width, height);
+	const size_t pb = pixel_bytes(pixel_type);
+	if (!pb)
+		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: pixel_type %d", pixel_type);
+	if (params->flags & ~(uint32_t)(CFHIP_BLEED_WRAP_X | CFHIP_BLEED_WRAP_Y))
+		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params->flags 0x%x: unknown", params->flags);
+	const float t = params->alpha_threshold;
+	if (!(t >= 0.0f && t < 1.0f))
+		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params->alpha_threshold %g outside [0, 1)", (double)t);
+	if (params->max_distance > 65535u)
+		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params->max_distance %u above 65535", params->max_distance);
+	if (pitch_bytes < (size_t)width*pb)
+		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: pitch_bytes %zu < %zu, a row", pitch_bytes, (size_t)width*pb);
+	if (pitch_bytes % (pb/4u))
+		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: pitch_bytes %zu not aligned to a component (%zu bytes)", pitch_bytes, pb/4u);
+	const uint64_t texels = (uint64_t)layers*width*height;
+	if (texels > CFAB_MAX_TEXELS)
+		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: more than 2^31 texels in one call");
+	for (uint32_t l = 0; l < layers; ++l) {
+		if (!images[l])
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: images[%u] is NULL", l);
+		if ((uintptr_t)images[l] % (pb/4u))
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: images[%u] not aligned to a component (%zu bytes)", l, pb/4u);
+	}
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+	const hipStream_t stream = lease.stream;
+	if (!ctx->profiling)
+		ctx->events_used = 0;
+	ctx->events_stream = stream;
+	ctx->last_ms = -1.0f;
+	ctx->last_kernel = "cfhip_alpha_bleed_step_kernel";
+	// d_batch: the layers' pointers; d_src: the two seed buffers, 4 bytes per texel each
+	int rc = lease.acquire();
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, (size_t)layers*sizeof(void*));
+	if (rc == CFHIP_OK)
+		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, (size_t)texels*8u);
+	if (rc != CFHIP_OK)
+		return rc;
+	// pageable source: the runtime stages the copy before returning
+	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, images, (size_t)layers*sizeof(void*), hipMemcpyHostToDevice, stream));
+	if (results_device)
+		HIP_TRY(ctx, hipMemsetAsync(results_device, 0, (size_t)layers*sizeof(cfhip_bleed_result), stream));
+	cfab_call call;
+	call.images = static_cast<void* const*>(ctx->d_batch);
+	call.pitch = pitch_bytes;
+	call.width = width; call.height = height;
+	call.pixel_type = pixel_type;
+	call.flags = params->flags;
+	uint32_t* buf[2] = {static_cast<uint32_t*>(ctx->d_src), static_cast<uint32_t*>(ctx->d_src) + texels};
+	uint32_t p2 = 1;
+	while (p2 < std::max(width, height))
+		p2 <<= 1;
+	// on a wrapped axis positions are taken modulo the size: so is the step
+	const auto sx = [&](uint32_t k) { return (call.flags & CFHIP_BLEED_WRAP_X) ? k % width : k; };
+	const auto sy = [&](uint32_t k) { return (call.flags & CFHIP_BLEED_WRAP_Y) ? k % height : k; };
+	BLEED_TIMED(ctx, stream, cfhip_launch_alpha_bleed_seed(&call, layers, t, buf[0], results_device, stream));
+	int cur = 0;
+	for (uint32_t k = p2 >> 1; k >= 1u; k >>= 1, cur ^= 1)
+		BLEED_TIMED(ctx, stream, cfhip_launch_alpha_bleed_step(&call, layers, sx(k), sy(k), buf[cur], buf[cur ^ 1], stream));
+	BLEED_TIMED(ctx, stream, cfhip_launch_alpha_bleed_fill(&call, layers, sx(1u), sy(1u), params->max_distance*params->max_distance,
+		buf[cur], results_device, stream));
 	return lease.done(!stream_);
 }
 

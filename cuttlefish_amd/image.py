@@ -70,6 +70,12 @@ class _Device:
     def download(self, buf) -> np.ndarray:
         return buf[0].cpu().numpy()
 
+    def bleed(self, buf, threshold: float = 0.0, wrap=False, max_distance: int = 0):
+        """Alpha bleeding of a buffer in place (cfhip_alpha_bleed_array_device) -> the buffer"""
+        t, pt, w, h, pitch = buf
+        self.ctx.alpha_bleed_device([t.data_ptr()], pt, w, h, pitch, threshold, wrap, max_distance)
+        return buf
+
     def png(self, buf, color_type: int, bit_depth: int, color_space) -> bytes:
         """The PNG file of a buffer (cfhip_png_encode_device): only the file's bytes come back."""
         import torch
@@ -163,6 +169,20 @@ class Image:
         self.pixels = self._run(ImageOp.PreMultiply)
         return True
 
+    def bleed_alpha(self, threshold: float = 0.0, wrap=False, max_distance: int = 0) -> bool:
+        """Alpha bleeding (Context.alpha_bleed_device): every texel with alpha <= threshold takes the colour of the
+        nearest texel with alpha > threshold, bit for bit; alpha and the pixel type stay.  The remedy of straight alpha
+        for fringes in mips and for block endpoints spent on hidden colour -- the alternative to pre_multiply_alpha,
+        not a companion.  wrap: a bool or (x, y) for tiling images; max_distance: texels, 0 = unlimited.  False for
+        an RGBF image: it has no alpha."""
+        if self.rgbf:
+            return False
+        d = _Device(self.device_id)
+        buf = d.bleed(d.upload(self.pixels), threshold, wrap, max_distance)
+        self.pixels = d.download(buf)
+        self._last = (buf, self.pixels)
+        return True
+
     def change_color_space(self, color_space: ColorSpace) -> bool:
         self.pixels = self._run(ImageOp.ColorSpace, dst_color_space=ColorSpace(color_space))
         self.color_space = ColorSpace(color_space)
@@ -197,9 +217,22 @@ _SIGNED = (Type.SNorm, Type.Int, Type.Float)      # isSigned (tool/main.cpp:63-7
 def plan_process_image(width: int, height: int, src_width: int, src_height: int, image_color_space,
                        texture_color_space, mip_level: int = 0, type=Type.UNorm, rotate=None,
                        grayscale: bool = False, normal_map=None, flip_x: bool = False, flip_y: bool = False,
-                       swizzle=None, premultiply: bool = False):
+                       swizzle=None, premultiply: bool = False, bleed: Optional[dict] = None):
     """The device steps of process_image, in order: ("ops", ImageOps) and ("resize", width, height, colour space).
-    At most three ops steps: before the first resize, between the resizes, after the last."""
+    At most three ops steps: before the first resize, between the resizes, after the last.  bleed = dict(threshold=,
+    wrap=, max_distance=) (any of them; Image.bleed_alpha's defaults) adds one ("bleed", threshold, wrap, max_distance)
+    step directly before the first resize -- after the ops pass in front of it, so that the filter's taps find the bled
+    colour -- or after the last ops step when nothing is resized; None adds nothing.  With premultiply it raises
+    ValueError: bleeding is the remedy of straight alpha."""
+    bleed_step = None
+    if bleed is not None:
+        if premultiply:
+            raise ValueError("bleed and premultiply exclude each other: alpha bleeding is for straight alpha")
+        unknown = set(bleed) - {"threshold", "wrap", "max_distance"}
+        if unknown:
+            raise ValueError("bleed: unknown keys %r" % (sorted(unknown),))
+        bleed_step = ("bleed", float(bleed.get("threshold", 0.0)), api.wrap_axes(bleed.get("wrap", False)),
+                      int(bleed.get("max_distance", 0)))
     steps = []
     cs = ColorSpace(image_color_space)
     tcs = ColorSpace(texture_color_space)
@@ -252,6 +285,9 @@ def plan_process_image(width: int, height: int, src_width: int, src_height: int,
     if premultiply:
         group["ops"] |= ImageOp.PreMultiply
     close(final=True)
+    if bleed_step is not None:
+        first = next((i for i, st in enumerate(steps) if st[0] == "resize"), len(steps))
+        steps.insert(first, bleed_step)
     return steps
 
 
@@ -259,12 +295,15 @@ def process_image(image, image_color_space, texture_color_space, width: int, hei
                   type=Type.UNorm, filter=ResizeFilter.CatmullRom, rotate: Optional[RotateAngle] = None,
                   grayscale: bool = False, normal_map: Optional[Tuple[NormalOptions, float]] = None,
                   flip_x: bool = False, flip_y: bool = False, swizzle: Optional[Sequence[Channel]] = None,
-                  premultiply: bool = False, orig_image_format=ImageFormat.Invalid, device_id: int = 0) -> np.ndarray:
+                  premultiply: bool = False, orig_image_format=ImageFormat.Invalid, device_id: int = 0,
+                  bleed: Optional[dict] = None) -> np.ndarray:
     """loadAndProcessImage (tool/main.cpp:147-277) after the load: colour-space change, resize to the target size
     (max(1, size >> mip_level); the full size first when a normal map is made), rotation, grayscale, normal map
     (normal_map = (NormalOptions, height); KeepSign added for signed types; resized to the mip size afterwards),
     X then Y flip, swizzle, premultiplication and Texture.adjust_image_value_range.  The intermediates stay on the
-    device.  Returns the RGBA32F array for Texture.set_image.  image: an (h, w, 4) array or an Image (its pixels)."""
+    device.  Returns the RGBA32F array for Texture.set_image.  image: an (h, w, 4) array or an Image (its pixels).
+    bleed = dict(threshold=, wrap=, max_distance=) runs alpha bleeding (Image.bleed_alpha) after the ops pass in front
+    of the resize to the texture's size and before that resize (plan_process_image); not with premultiply."""
     if isinstance(image, Image):
         image = image.pixels
     pixels = _pixels(image)
@@ -272,12 +311,14 @@ def process_image(image, image_color_space, texture_color_space, width: int, hei
         orig_image_format = ImageFormat.RGBA8 if pixels.dtype == np.uint8 else ImageFormat.RGBAF
     steps = plan_process_image(width, height, pixels.shape[1], pixels.shape[0], image_color_space,
                                texture_color_space, mip_level, type, rotate, grayscale, normal_map, flip_x, flip_y,
-                               swizzle, premultiply)
+                               swizzle, premultiply, bleed)
     d = _Device(device_id)
     buf = d.upload(pixels)
     for s in steps:
         if s[0] == "ops":
             buf = d.ops(buf, s[1])
+        elif s[0] == "bleed":
+            buf = d.bleed(buf, s[1], s[2], s[3])
         else:
             buf = d.resize(buf, s[1], s[2], s[3], filter)
     out = d.download(buf)

@@ -331,6 +331,7 @@ class Texture:
         self._rdo_stats = None
         self._rdo_target = None
         self._mip_post: List[List[dict]] = []
+        self._bleed: List[dict] = []
 
     def initialize(self, dimension, width: int, height: int, depth: int = 0, mip_levels: int = 1,
                    color_space: ColorSpace = ColorSpace.Linear) -> bool:
@@ -624,6 +625,47 @@ class Texture:
                         images[mip][d][f] = im
         self._images = images
         return True
+
+    def bleed_alpha(self, threshold: float = 0.0, wrap=False, max_distance: int = 0) -> bool:
+        """Alpha bleeding (Context.alpha_bleed_device) of every image currently set -- all levels, depths and faces,
+        each within itself: every texel with alpha <= threshold takes the colour of the nearest texel with
+        alpha > threshold, bit for bit, alpha untouched.  Call it before generate_mipmaps / convert, so that the
+        filters and the block encoders see a sensible colour under the transparent texels; it is for straight alpha,
+        the alternative to premultiplication.  Images of equal size and dtype share one call.  wrap: a bool or (x, y)
+        for tiling surfaces; max_distance: texels, 0 = unlimited.  bleed_results() returns the records.  False on
+        an invalid or already converted texture, and on a 3-D texture: a volume's nearest seed is another
+        definition."""
+        import torch
+        if not self._valid or self._textures or self._dim == Dimension.Dim3D:
+            return False
+        groups: Dict[tuple, List[Tuple[int, int, int]]] = {}
+        for m, level in enumerate(self._images):
+            for d, dep in enumerate(level):
+                for f, im in enumerate(dep):
+                    if im is not None:
+                        groups.setdefault((im.shape[0], im.shape[1], im.dtype.str), []).append((m, d, f))
+        records = {}
+        for (h, w, _), where in groups.items():
+            stack = np.stack([np.ascontiguousarray(self._images[m][d][f]) for m, d, f in where])
+            dev = torch.from_numpy(stack).to("cuda:%d" % self._device_id)
+            res = torch.zeros((len(where), 4), dtype=torch.int32, device=dev.device)
+            size = dev[0].numel()*dev.element_size()
+            self._context().alpha_bleed_device([dev.data_ptr() + i*size for i in range(len(where))],
+                                               api.pixel_type_of(stack[0]), w, h, stack.strides[1], threshold, wrap,
+                                               max_distance, res.data_ptr())
+            out = dev.cpu().numpy()
+            rec = res.cpu().numpy().view(api.BLEED_RESULT_DTYPE).reshape(-1)
+            for i, (m, d, f) in enumerate(where):
+                self._images[m][d][f] = out[i]
+                records[(m, d, f)] = dict(mip=m, depth=d, face=f, seeds=int(rec[i]["seeds"]), filled=int(rec[i]["filled"]),
+                                          max_dist2=int(rec[i]["max_dist2"]))
+        self._bleed = [records[k] for k in sorted(records)]
+        return True
+
+    def bleed_results(self):
+        """The records of the last bleed_alpha(): one dict per image it ran on, in [mip][depth][face] order -- mip, depth,
+        face, seeds, filled and max_dist2, the largest squared distance a colour travelled; [] before any call."""
+        return [dict(r) for r in self._bleed]
 
     def mip_post_results(self):
         """The records of the last generate_mipmaps(alpha_coverage=...): one list per surface in [depth][face] order,

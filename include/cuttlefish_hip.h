@@ -348,6 +348,55 @@ typedef struct cfhip_coverage_surface {
 int cfhip_alpha_coverage_device(cfhip_ctx* ctx, const cfhip_coverage_surface* surfaces, uint32_t count, float threshold,
 	float scale, uint32_t* counts_device, void* stream);
 
+/* Alpha bleeding (solidify, edge padding): before mips and encoding, every texel whose alpha is not above a threshold
+ * takes the colour of the nearest texel whose alpha is.  Alpha is untouched, so the image looks the same, but filters
+ * and block encoders see a sensible colour on both sides of a cut-out's silhouette instead of whatever the exporter left
+ * there.  The remedy for straight alpha; premultiplied input is out of scope.  In place, on `layers` surfaces of one size
+ * and pixel type: images[l] is width x height texels, 1 <= width, height <= 32768, rows pitch_bytes apart.
+ *
+ *   seed            texel p is a seed iff alpha(p) > alpha_threshold, 0 <= alpha_threshold < 1, compared in float32;
+ *                   alpha() as the coverage pass reads it: RGBA8 (float)(v / 255.0), RGBA16F half -> float, RGBA32F as
+ *                   stored.  A NaN alpha is not a seed.  Seed word: x | y << 16; 0xFFFFFFFF means none.
+ *   distance        dx = |px - sx|, on a wrapped axis (CFHIP_BLEED_WRAP_X / _Y) dx = min(dx, width - dx); the same for
+ *                   y; d^2 = dx^2 + dy^2 < 2^31.  The key of a candidate seed s for texel p is the 64-bit
+ *                   d^2(p, s) << 32 | s: ties go to the smaller seed word.
+ *   passes          P = the smallest power of two >= max(width, height); the steps are P/2, P/4, ..., 1 and one more 1
+ *                   (a 1 x 1 surface: the one step 1).  Pass 0 writes each texel's own seed word, or none.  Each step k
+ *                   reads only the buffer the pass before it wrote: texel p's candidates are the seeds stored at
+ *                   p + k * (dx, dy), dx, dy in {-1, 0, 1}, p itself included; on a wrapped axis the position is taken
+ *                   modulo the size, on an unwrapped axis a position outside the surface is skipped.  p keeps the
+ *                   candidate of minimal key, or none; the minimum makes the order of the nine reads irrelevant.
+ *   fill            after the last step every texel that is not a seed takes the R, G, B storage bits of its seed's
+ *                   texel if it has a seed and max_distance == 0 (unlimited) or d^2 <= max_distance^2,
+ *                   max_distance <= 65535.  No arithmetic: the bits are copied in the surface's own pixel type.  Alpha
+ *                   and all seed texels are never written.  A surface without seeds is left untouched.
+ *   results_device  one record per layer, or NULL for none: seeds, filled, max_dist2 (the largest d^2 among the filled
+ *                   texels, 0 if none), reserved = 0.  Sums and a maximum: identical calls return identical bytes.
+ * This is a jump flood, not an exact Euclidean transform: without wrap every texel receives a seed whenever the surface
+ * has one (any offset below P is a sum of distinct steps, and the path stays inside the bounding box of seed and texel),
+ * its seed is never nearer than the nearest one, and rarely farther (tests/test_alpha_bleed_ref.py bounds how often).
+ *
+ * All layers share every launch: 2 + log2(P) launches per call (seed, log2(P) steps, the last step fused with the fill),
+ * plain launches on the call's stream, nothing waits for the host.  The scratch is the context's, grown on demand:
+ * 8 bytes per texel of the call (two buffers of seed words), at most 2^31 texels per call.  images[l] and pitch_bytes
+ * are aligned to a component of the pixel type.  Every argument is checked before anything is enqueued; stream == NULL
+ * means the context's stream and the call synchronises. */
+enum { CFHIP_BLEED_WRAP_X = 1, CFHIP_BLEED_WRAP_Y = 2 };
+typedef struct cfhip_bleed_params {
+	uint32_t flags;
+	float alpha_threshold;
+	uint32_t max_distance;
+} cfhip_bleed_params;
+typedef struct cfhip_bleed_result {
+	uint32_t seeds;
+	uint32_t filled;
+	uint32_t max_dist2;
+	uint32_t reserved;
+} cfhip_bleed_result;
+int cfhip_alpha_bleed_array_device(cfhip_ctx* ctx, void* const* images, uint32_t layers, int pixel_type,
+	uint32_t width, uint32_t height, size_t pitch_bytes, const cfhip_bleed_params* params,
+	cfhip_bleed_result* results_device, void* stream);
+
 /* One Image::resize on the GPU (lib/src/Image.cpp:1324-1511) -- what Texture::generateMipmaps calls
  * per level, and per custom mip image (Texture.cpp:1499-1503, any source size): src (any of the
  * three pixel types) -> dst, dst_width x dst_height tightly packed RGBA32F, in linear space as
@@ -1110,7 +1159,7 @@ int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* p
 	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass) or cfhip_alpha_coverage_device call on
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass), cfhip_alpha_coverage_device or cfhip_alpha_bleed_array_device (every pass) call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
