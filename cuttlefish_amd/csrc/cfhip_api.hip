@@ -626,6 +626,25 @@ int next_event_pair(cfhip_ctx* ctx, hipEvent_t* a, hipEvent_t* b)
 	return CFHIP_OK;
 }
 
+// One timed span on the stream (cfhip_last_kernel_ms / profiling): an event pair around what `launch` enqueues, one
+// kernel or several; it returns the first hipError_t that is no success.  `what` names the family in the error text.
+template <class Launch>
+int timed(cfhip_ctx* ctx, hipStream_t stream, const char* what, Launch&& launch)
+{
+	hipEvent_t a, b;
+	const int rc = next_event_pair(ctx, &a, &b);
+	if (rc != CFHIP_OK)
+		return rc;
+	HIP_TRY(ctx, hipEventRecord(a, stream));
+	const hipError_t e = launch();
+	if (e != hipSuccess)
+		return fail(ctx, CFHIP_E_DEVICE, "%s launch: %s", what, hipGetErrorString(e));
+	HIP_TRY(ctx, hipEventRecord(b, stream));
+	return CFHIP_OK;
+}
+
+// The encoders' form of it: launch() picks the kernel, names it in last_kernel and formats its own errors (an
+// unsupported pixel type among them), so it returns an int and stays apart from timed().
 int timed_launch(cfhip_ctx* ctx, const cf_kparams& kp, const cfhip_params& p, int pixel_type,
 	hipStream_t stream)
 {
@@ -665,7 +684,7 @@ int reserve(cfhip_ctx* ctx, void** buf, size_t* cap, size_t need)
 //  * done(synchronous): the only success exit.  An asynchronous call that acquired records staging_done and becomes
 //    the last user; a synchronous one drains its stream, after which the buffers are idle if it acquired (its stream
 //    waited for the previous user) or was the last user itself.
-//  * any other exit (an error return, an exception unwinding to encode_impl): a call that acquired drains its stream
+//  * any other exit (an error return, an exception unwinding to guarded()): a call that acquired drains its stream
 //    and the host pipeline's copy streams, and the buffers are idle once that succeeded; a call that never acquired
 //    leaves their state as it found it -- another stream's work may still be in flight on them.
 struct StagingLease {
@@ -719,18 +738,13 @@ struct StagingLease {
 	}
 };
 
-// ---- what the stream codecs' entry points share (estimator, deflate, inflate, LZ4, PNG: the sections far below) -----
-// An entry point's frame: the context's lock while the body runs (none for a NULL context: the checks and the
-// empty-input answers need none), its error text cleared, and no exception across the C boundary.  The body declares its
-// StagingLease itself, so the lease ends -- also while an exception unwinds -- before the lock is released.
+// ---- what every entry point that works on a context shares ---------------------------------------------------------
+// No exception across the C boundary: std::bad_alloc / std::system_error from the vectors and threads of a body become
+// CFHIP_E_DEVICE with the text in cfhip_last_error.  On its own only where no single context's lock fits: the planning
+// of cfhip_encode_multi_ex, which runs guarded calls on every context.
 template <class Body>
-int guarded(cfhip_ctx* ctx, const char* what, Body&& body)
+int no_throw(cfhip_ctx* ctx, const char* what, Body&& body)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
 	try {
 		return body();
 	} catch (const std::exception& e) {
@@ -740,18 +754,42 @@ int guarded(cfhip_ctx* ctx, const char* what, Body&& body)
 	}
 }
 
+// An entry point's frame: the context's lock while the body runs (none for a NULL context: the checks and the
+// empty-input answers need none), its error text cleared, and no exception out of it.  The body makes the checks in the
+// entry point's own order -- the NULL-context check first or after the argument checks -- and declares its StagingLease
+// itself, so the lease ends, also while an exception unwinds, before the lock is released.
+template <class Body>
+int guarded(cfhip_ctx* ctx, const char* what, Body&& body)
+{
+	std::unique_lock<std::mutex> guard;
+	if (ctx) {
+		guard = std::unique_lock<std::mutex>(ctx->lock);
+		ctx->error.clear();
+	}
+	return no_throw(ctx, what, body);
+}
+
+// the stream a call works on: the caller's, or the context's own
+hipStream_t call_stream(cfhip_ctx* ctx, void* stream_)
+{
+	return stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream;
+}
+
 // The event bookkeeping of a call that starts: its pairs are counted from here (all pairs, while profiling), and the
-// stage log of the call before it is closed.
+// stage log of the call before it is closed.  kernel: what the call leaves in last_kernel; NULL where the call names it
+// only when it launches (the encoders' launch()), so that a call that fails before that leaves the name as it found it.
 void begin_call(cfhip_ctx* ctx, hipStream_t stream, const char* kernel)
 {
 	if (!ctx->profiling)
 		ctx->events_used = 0;
 	ctx->events_stream = stream;
 	ctx->last_ms = -1.0f;
-	ctx->last_kernel = kernel;
+	if (kernel)
+		ctx->last_kernel = kernel;
 	ctx->stages.owner = nullptr;
 }
 
+// ---- the stream codecs' stage logs (estimator, deflate, inflate, LZ4, PNG: the sections far below) ------------------
 // A family of calls that keeps a stage log: the public names its cfhip_*_stage_ms answers for (the log's owner tag), the
 // kernel name its calls leave in last_kernel, and the shape of its event pairs (csrc/stage_log.h).
 struct StageFamily {
@@ -789,8 +827,10 @@ int take_event_pairs(cfhip_ctx* ctx, hipEvent_t* ev, size_t n)
 }
 
 // cfhip_*_stage_ms of family f: the open log's pairs summed by stage into ms[0 .. n).  The log is f's last call's while
-// f owns it and last_kernel still holds what that call wrote there: the entry points of the other families (encode,
-// decode, compare, ...) do not pass through begin_call, but every one of them names its own kernel.
+// f owns it and last_kernel still holds what that call wrote there.  Every call that times its launches passes through
+// begin_call, which closes the log; mip generation (2-D, array, 3-D) and resize do not -- their launches are untimed and
+// they leave the event state, the log and last_kernel alone, so f's log stays readable across them.  The comparison
+// stays for a call that wrote last_kernel past begin_call.
 int stage_ms(cfhip_ctx* ctx, const StageFamily& f, const char* what, float* ms, size_t n)
 {
 	const size_t stages = f.head + f.per_slice + f.tail;
@@ -1237,30 +1277,19 @@ int decode_launch(cfhip_ctx* ctx, int format, int type, const DecodeGeom& g, con
 	size_t out_pitch, const void* ref, size_t ref_pitch, uint32_t width, uint32_t height, unsigned long long* acc,
 	bool sse, hipStream_t stream)
 {
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
 	const bool astc = format >= CFHIP_FORMAT_ASTC_4x4;
-	ctx->last_kernel = sse ? (astc ? "cfhip_decode_sse_astc_kernel" : "cfhip_decode_sse_block_kernel")
-		: (astc ? "cfhip_decode_astc_kernel" : "cfhip_decode_block_kernel");
+	begin_call(ctx, stream, sse ? (astc ? "cfhip_decode_sse_astc_kernel" : "cfhip_decode_sse_block_kernel")
+		: (astc ? "cfhip_decode_astc_kernel" : "cfhip_decode_block_kernel"));
 	const uintptr_t op = sse ? (uintptr_t)ref : (uintptr_t)out;
 	const size_t pitch = sse ? ref_pitch : out_pitch;
 	// decode: 16-byte row stores need a 16-byte aligned output; SSE: word loads of the reference need 4 bytes
 	const int align = sse ? 4 : 16;
 	const int out_vec = (op % align == 0 && pitch % align == 0) ? 1 : 0;
 	const int blk_vec = ((uintptr_t)blocks % (uintptr_t)g.bb == 0) ? 1 : 0;
-	hipEvent_t a, b;
-	int rc = next_event_pair(ctx, &a, &b);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipEventRecord(a, stream));
-	const hipError_t e = cfhip_launch_decode(format, type, blocks, blk_vec, out, out_pitch, ref, ref_pitch, out_vec,
-		width, height, g.bx, g.by, g.bw, g.bh, acc, sse ? 1 : 0, stream);
-	if (e != hipSuccess)
-		return fail(ctx, CFHIP_E_DEVICE, "decode launch: %s", hipGetErrorString(e));
-	HIP_TRY(ctx, hipEventRecord(b, stream));
-	return CFHIP_OK;
+	return timed(ctx, stream, "decode", [&] {
+		return cfhip_launch_decode(format, type, blocks, blk_vec, out, out_pitch, ref, ref_pitch, out_vec,
+			width, height, g.bx, g.by, g.bw, g.bh, acc, sse ? 1 : 0, stream);
+	});
 }
 
 // ---- quality metrics (csrc/compare.hip) -----------------------------------------------------------
@@ -1350,40 +1379,30 @@ int compare_enqueue(cfhip_ctx* ctx, int format, int type, const CompareGeom& c, 
 	int ref_pixel_type, size_t ref_pitch, uint32_t width, uint32_t height, uint8_t* scratch,
 	cfhip_compare_result* result, float* block_errors, hipStream_t stream)
 {
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	ctx->last_kernel = format >= CFHIP_FORMAT_ASTC_4x4 ? "cfhip_compare_astc_kernel" : "cfhip_compare_block_kernel";
+	begin_call(ctx, stream, format >= CFHIP_FORMAT_ASTC_4x4 ? "cfhip_compare_astc_kernel" : "cfhip_compare_block_kernel");
 	const DecodeGeom& g = c.g;
 	const int blk_vec = ((uintptr_t)blocks % (uintptr_t)g.bb == 0) ? 1 : 0;
 	double* pa = reinterpret_cast<double*>(scratch + c.pa_off);
 	double* pb = c.ssim ? reinterpret_cast<double*>(scratch + c.pb_off) : nullptr;
-	hipEvent_t a, b;
-	int rc = next_event_pair(ctx, &a, &b);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipEventRecord(a, stream));
-	hipError_t e = cfhip_launch_compare(format, type, blocks, blk_vec, ref, ref_pixel_type, ref_pitch, width, height,
-		g.bx, g.by, g.bw, g.bh, c.cmask, block_errors, pa, stream);
-	if (e == hipSuccess && c.ssim) {
-		const size_t dec_pitch = (size_t)width*(size_t)g.texel_bytes;
-		e = cfhip_launch_decode(format, type, blocks, blk_vec, scratch, dec_pitch, nullptr, 0,
-			dec_pitch % 16u == 0 ? 1 : 0, width, height, g.bx, g.by, g.bw, g.bh, nullptr, 0, stream);
-		if (e == hipSuccess) {
-			const double range = (g.layout == CFHIP_LAYOUT_R8_SNORM || g.layout == CFHIP_LAYOUT_RG8_SNORM ||
-				g.layout == CFHIP_LAYOUT_R16_SNORM || g.layout == CFHIP_LAYOUT_RG16_SNORM) ? 2.0 : 1.0;
-			e = cfhip_launch_ssim(scratch, dec_pitch, g.layout, ref, ref_pixel_type, ref_pitch, width, height, c.cmask,
-				ssim_taps(), range, pb, stream);
+	return timed(ctx, stream, "compare", [&] {
+		hipError_t e = cfhip_launch_compare(format, type, blocks, blk_vec, ref, ref_pixel_type, ref_pitch, width, height,
+			g.bx, g.by, g.bw, g.bh, c.cmask, block_errors, pa, stream);
+		if (e == hipSuccess && c.ssim) {
+			const size_t dec_pitch = (size_t)width*(size_t)g.texel_bytes;
+			e = cfhip_launch_decode(format, type, blocks, blk_vec, scratch, dec_pitch, nullptr, 0,
+				dec_pitch % 16u == 0 ? 1 : 0, width, height, g.bx, g.by, g.bw, g.bh, nullptr, 0, stream);
+			if (e == hipSuccess) {
+				const double range = (g.layout == CFHIP_LAYOUT_R8_SNORM || g.layout == CFHIP_LAYOUT_RG8_SNORM ||
+					g.layout == CFHIP_LAYOUT_R16_SNORM || g.layout == CFHIP_LAYOUT_RG16_SNORM) ? 2.0 : 1.0;
+				e = cfhip_launch_ssim(scratch, dec_pitch, g.layout, ref, ref_pixel_type, ref_pitch, width, height, c.cmask,
+					ssim_taps(), range, pb, stream);
+			}
 		}
-	}
-	if (e == hipSuccess)
-		e = cfhip_launch_compare_final(pa, c.na, pb, c.nb, c.cmask, c.hdr ? 1 : 0, c.windows,
-			(uint64_t)width*height, result, stream);
-	if (e != hipSuccess)
-		return fail(ctx, CFHIP_E_DEVICE, "compare launch: %s", hipGetErrorString(e));
-	HIP_TRY(ctx, hipEventRecord(b, stream));
-	return CFHIP_OK;
+		if (e == hipSuccess)
+			e = cfhip_launch_compare_final(pa, c.na, pb, c.nb, c.cmask, c.hdr ? 1 : 0, c.windows,
+				(uint64_t)width*height, result, stream);
+		return e;
+	});
 }
 
 } // namespace
@@ -1551,31 +1570,24 @@ static int validate_surfaces(cfhip_ctx* ctx, const cfhip_surface* surfaces, size
 static int encode_body(cfhip_ctx* ctx, StagingLease& lease, const cfhip_surface* surfaces, size_t n,
 	const cfhip_params* params, bool device_mem, bool user_stream, cfhip_consumed_fn consumed, void* user);
 
-// Every encode entry point of the C ABI comes through here (round-5 ADVICE: the guard used to cover the strip pipeline
-// only).  No exception crosses the extern "C" boundary -- std::bad_alloc / std::system_error from the vectors and
-// threads of the body become CFHIP_E_DEVICE with the text in cfhip_last_error -- and the lease, which outlives the
-// catch, drains whatever an error return or an exception left queued on the staging buffers.
+// Every encode entry point of the C ABI comes through here.  The lease ends inside the frame: as an exception unwinds
+// through it -- before guarded() turns that into an error code, and under the lock -- it drains whatever the body left
+// queued on the staging buffers, as it does on an error return.
 static int encode_impl(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n,
 	const cfhip_params* params, bool device_mem, hipStream_t user_stream,
 	cfhip_consumed_fn consumed = nullptr, void* user = nullptr)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	StagingLease lease(ctx, user_stream ? user_stream : ctx->stream);
-	try {
+	return guarded(ctx, "encode", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		StagingLease lease(ctx, user_stream ? user_stream : ctx->stream);
 		return encode_body(ctx, lease, surfaces, n, params, device_mem, user_stream != nullptr, consumed, user);
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "encode: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "encode: unknown exception");
-	}
+	});
 }
 
 static int encode_body(cfhip_ctx* ctx, StagingLease& lease, const cfhip_surface* surfaces, size_t n,
 	const cfhip_params* params, bool device_mem, bool user_stream, cfhip_consumed_fn consumed, void* user)
 {
-	ctx->error.clear();
 	int rc = check_params(ctx, params);
 	if (rc != CFHIP_OK)
 		return rc;
@@ -1583,10 +1595,7 @@ static int encode_body(cfhip_ctx* ctx, StagingLease& lease, const cfhip_surface*
 		return fail(ctx, CFHIP_E_INVALID, "surfaces is NULL");
 	HIP_TRY(ctx, hipSetDevice(ctx->device));
 	const hipStream_t stream = lease.stream;
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
+	begin_call(ctx, stream, nullptr);             // launch() names the kernel
 
 	// validate everything first, compute sizes
 	std::vector<Item> items(n);
@@ -1730,14 +1739,11 @@ int cfhip_encode_multi_ex(cfhip_ctx* const* ctxs, int n_ctx, const cfhip_surface
 	if (!ctxs || n_ctx <= 0 || !ctxs[0])
 		return CFHIP_E_INVALID;
 	// (the planning below builds vectors: an allocation failure there is an error code, not an exception across the C
-	// ABI; the per-context encodes are guarded by encode_impl, and a thread that cannot be started runs its share here)
-	try {
+	// ABI.  No lock here: the per-context encodes take each context's own in encode_impl, the first context's among
+	// them, and a thread that cannot be started runs its share here)
+	return no_throw(ctxs[0], "encode_multi", [&]() -> int {
 		return encode_multi_body(ctxs, n_ctx, surfaces, n_surfaces, params, consumed, user);
-	} catch (const std::exception& e) {
-		return fail(ctxs[0], CFHIP_E_DEVICE, "encode_multi: %s", e.what());
-	} catch (...) {
-		return fail(ctxs[0], CFHIP_E_DEVICE, "encode_multi: unknown exception");
-	}
+	});
 }
 
 static int encode_multi_body(cfhip_ctx* const* ctxs, int n_ctx, const cfhip_surface* surfaces,
@@ -1975,37 +1981,39 @@ int cfhip_generate_mips_device(cfhip_ctx* ctx, const void* src, int src_pixel_ty
 	uint32_t width, uint32_t height, size_t src_pitch_bytes, int color_space, int filter,
 	void* const* dst_levels, uint32_t levels, void* stream_)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	if (!src || !width || !height || !levels || (levels > 1 && !dst_levels))
-		return fail(ctx, CFHIP_E_INVALID, "mip generation: NULL or empty argument");
-	int rc = check_mip_args(ctx, "mip generation", src_pixel_type, color_space, filter, width, height, 0, levels,
-		src_pitch_bytes);
-	if (rc != CFHIP_OK)
-		return rc;
-	for (uint32_t k = 1; k < levels; ++k)
-		if (!dst_levels[k - 1])
-			return fail(ctx, CFHIP_E_INVALID, "mip generation: dst_levels[%u] is NULL", k - 1);
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	// level k from level k-1, as Texture::generateMipmaps does (Texture.cpp:1480-1487)
-	const void* prev = src;
-	int prev_type = src_pixel_type;
-	size_t prev_pitch = src_pitch_bytes;
-	uint32_t pw = width, ph = height;
-	for (uint32_t k = 1; k < levels; ++k) {
-		const uint32_t w = (width >> k) ? (width >> k) : 1u, h = (height >> k) ? (height >> k) : 1u;
-		rc = mip_level_2d(ctx, lease, prev, prev_type, prev_pitch, pw, ph, dst_levels[k - 1], w, h, filter,
-			color_space == CFHIP_COLOR_SRGB ? 1 : 0);
+	return guarded(ctx, "mip generation", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		if (!src || !width || !height || !levels || (levels > 1 && !dst_levels))
+			return fail(ctx, CFHIP_E_INVALID, "mip generation: NULL or empty argument");
+		int rc = check_mip_args(ctx, "mip generation", src_pixel_type, color_space, filter, width, height, 0, levels,
+			src_pitch_bytes);
 		if (rc != CFHIP_OK)
 			return rc;
-		prev = dst_levels[k - 1];
-		prev_type = CFHIP_PIXEL_RGBA32F;
-		prev_pitch = (size_t)w*16u;
-		pw = w; ph = h;
-	}
-	return lease.done(!stream_);
+		for (uint32_t k = 1; k < levels; ++k)
+			if (!dst_levels[k - 1])
+				return fail(ctx, CFHIP_E_INVALID, "mip generation: dst_levels[%u] is NULL", k - 1);
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		// (no begin_call: the launches of mip generation and resize are untimed and leave last_kernel alone)
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		// level k from level k-1, as Texture::generateMipmaps does (Texture.cpp:1480-1487)
+		const void* prev = src;
+		int prev_type = src_pixel_type;
+		size_t prev_pitch = src_pitch_bytes;
+		uint32_t pw = width, ph = height;
+		for (uint32_t k = 1; k < levels; ++k) {
+			const uint32_t w = (width >> k) ? (width >> k) : 1u, h = (height >> k) ? (height >> k) : 1u;
+			rc = mip_level_2d(ctx, lease, prev, prev_type, prev_pitch, pw, ph, dst_levels[k - 1], w, h, filter,
+				color_space == CFHIP_COLOR_SRGB ? 1 : 0);
+			if (rc != CFHIP_OK)
+				return rc;
+			prev = dst_levels[k - 1];
+			prev_type = CFHIP_PIXEL_RGBA32F;
+			prev_pitch = (size_t)w*16u;
+			pw = w; ph = h;
+		}
+		return lease.done(!stream_);
+	});
 }
 
 // Array / cube textures: Texture::generateMipmaps resizes every [depth][face] image of a level on its own
@@ -2018,105 +2026,95 @@ int cfhip_generate_mips_array_device(cfhip_ctx* ctx, const void* const* srcs, ui
 	int src_pixel_type, uint32_t width, uint32_t height, size_t src_pitch_bytes, int color_space,
 	int filter, void* const* dst_levels, uint32_t levels, void* stream_)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	if (!srcs || !layers || !width || !height || !levels || (levels > 1 && !dst_levels))
-		return fail(ctx, CFHIP_E_INVALID, "mip generation: NULL or empty argument");
-	if (layers > 65535u)
-		return fail(ctx, CFHIP_E_INVALID, "mip generation: %u layers (at most 65535 per call)", layers);
-	int rc = check_mip_args(ctx, "mip generation", src_pixel_type, color_space, filter, width, height, 0, levels,
-		src_pitch_bytes);
-	if (rc != CFHIP_OK)
-		return rc;
-	for (uint32_t l = 0; l < layers; ++l) {
-		if (!srcs[l])
-			return fail(ctx, CFHIP_E_INVALID, "mip generation: srcs[%u] is NULL", l);
-		for (uint32_t k = 1; k < levels; ++k)
-			if (!dst_levels[(size_t)l*(levels - 1u) + (k - 1u)])
-				return fail(ctx, CFHIP_E_INVALID, "mip generation: dst_levels[%u][%u] is NULL", l, k - 1u);
-	}
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	const hipStream_t stream = lease.stream;
-	const int srgb = color_space == CFHIP_COLOR_SRGB ? 1 : 0;
-	if (levels > 1) {
-		// device pointer tables, level-major: row 0 = the sources, row k = level k of every layer
-		std::vector<const void*> tab((size_t)levels*layers);
-		for (uint32_t l = 0; l < layers; ++l) {
-			tab[l] = srcs[l];
-			for (uint32_t k = 1; k < levels; ++k)
-				tab[(size_t)k*layers + l] = dst_levels[(size_t)l*(levels - 1u) + (k - 1u)];
-		}
-		rc = lease.acquire();
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab.size()*sizeof(void*));
+	return guarded(ctx, "mip generation", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		if (!srcs || !layers || !width || !height || !levels || (levels > 1 && !dst_levels))
+			return fail(ctx, CFHIP_E_INVALID, "mip generation: NULL or empty argument");
+		if (layers > 65535u)
+			return fail(ctx, CFHIP_E_INVALID, "mip generation: %u layers (at most 65535 per call)", layers);
+		int rc = check_mip_args(ctx, "mip generation", src_pixel_type, color_space, filter, width, height, 0, levels,
+			src_pitch_bytes);
 		if (rc != CFHIP_OK)
 			return rc;
-		// pageable source: the runtime stages the copy before returning, so `tab` may die
-		if (hipMemcpyAsync(ctx->d_batch, tab.data(), tab.size()*sizeof(void*), hipMemcpyHostToDevice, stream) != hipSuccess)
-			return fail(ctx, CFHIP_E_DEVICE, "mip generation: table upload failed");
-		const void* const* d_tab = static_cast<const void* const*>(ctx->d_batch);
-		const size_t kStagingBudget = (size_t)1 << 30;           // the float image between the two passes, all layers
-		uint32_t pw = width, ph = height;
-		int prev_type = src_pixel_type;
-		size_t prev_pitch = src_pitch_bytes;
-		for (uint32_t k = 1; k < levels; ++k) {
-			const uint32_t w = (width >> k) ? (width >> k) : 1u, h = (height >> k) ? (height >> k) : 1u;
-			const void* const* s_tab = d_tab + (size_t)(k - 1u)*layers;
-			void* const* o_tab = const_cast<void* const*>(d_tab + (size_t)k*layers);
-			const bool x_first = (unsigned long long)w*ph <= (unsigned long long)h*pw;
-			const bool need_x = w != pw, need_y = h != ph;
-			const uint32_t tw = x_first ? w : pw, th = x_first ? ph : h;
-			const size_t timg = (size_t)tw*th*16u;
-			const bool fused = filter == CFHIP_FILTER_BOX && need_x && need_y;
-			const bool batched = !(filter & CFHIP_FILTER_FALLBACK) && (fused || !(need_x && need_y) || timg*layers <= kStagingBudget);
-			hipError_t e = hipSuccess;
-			if (fused) {
-				e = cfhip_launch_mip_fused_layers(nullptr, prev_type, prev_pitch, pw, ph, nullptr, w, h,
-					x_first ? 1 : 0, filter, srgb, layers, s_tab, o_tab, 0, 0, stream);
-			} else if (!batched) {
-				for (uint32_t l = 0; l < layers; ++l) {
-					rc = mip_level_2d(ctx, lease, tab[(size_t)(k - 1u)*layers + l], prev_type, prev_pitch, pw, ph,
-						const_cast<void*>(tab[(size_t)k*layers + l]), w, h, filter, srgb);
+		for (uint32_t l = 0; l < layers; ++l) {
+			if (!srcs[l])
+				return fail(ctx, CFHIP_E_INVALID, "mip generation: srcs[%u] is NULL", l);
+			for (uint32_t k = 1; k < levels; ++k)
+				if (!dst_levels[(size_t)l*(levels - 1u) + (k - 1u)])
+					return fail(ctx, CFHIP_E_INVALID, "mip generation: dst_levels[%u][%u] is NULL", l, k - 1u);
+		}
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		const hipStream_t stream = lease.stream;
+		const int srgb = color_space == CFHIP_COLOR_SRGB ? 1 : 0;
+		if (levels > 1) {
+			// device pointer tables, level-major: row 0 = the sources, row k = level k of every layer
+			std::vector<const void*> tab((size_t)levels*layers);
+			for (uint32_t l = 0; l < layers; ++l) {
+				tab[l] = srcs[l];
+				for (uint32_t k = 1; k < levels; ++k)
+					tab[(size_t)k*layers + l] = dst_levels[(size_t)l*(levels - 1u) + (k - 1u)];
+			}
+			rc = lease.acquire();
+			if (rc == CFHIP_OK)
+				rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab.size()*sizeof(void*));
+			if (rc != CFHIP_OK)
+				return rc;
+			// pageable source: the runtime stages the copy before returning, so `tab` may die
+			if (hipMemcpyAsync(ctx->d_batch, tab.data(), tab.size()*sizeof(void*), hipMemcpyHostToDevice, stream) != hipSuccess)
+				return fail(ctx, CFHIP_E_DEVICE, "mip generation: table upload failed");
+			const void* const* d_tab = static_cast<const void* const*>(ctx->d_batch);
+			const size_t kStagingBudget = (size_t)1 << 30;           // the float image between the two passes, all layers
+			uint32_t pw = width, ph = height;
+			int prev_type = src_pixel_type;
+			size_t prev_pitch = src_pitch_bytes;
+			for (uint32_t k = 1; k < levels; ++k) {
+				const uint32_t w = (width >> k) ? (width >> k) : 1u, h = (height >> k) ? (height >> k) : 1u;
+				const void* const* s_tab = d_tab + (size_t)(k - 1u)*layers;
+				void* const* o_tab = const_cast<void* const*>(d_tab + (size_t)k*layers);
+				const bool x_first = (unsigned long long)w*ph <= (unsigned long long)h*pw;
+				const bool need_x = w != pw, need_y = h != ph;
+				const uint32_t tw = x_first ? w : pw, th = x_first ? ph : h;
+				const size_t timg = (size_t)tw*th*16u;
+				const bool fused = filter == CFHIP_FILTER_BOX && need_x && need_y;
+				const bool batched = !(filter & CFHIP_FILTER_FALLBACK) && (fused || !(need_x && need_y) || timg*layers <= kStagingBudget);
+				hipError_t e = hipSuccess;
+				if (fused) {
+					e = cfhip_launch_mip_fused_layers(nullptr, prev_type, prev_pitch, pw, ph, nullptr, w, h,
+						x_first ? 1 : 0, filter, srgb, layers, s_tab, o_tab, 0, 0, stream);
+				} else if (!batched) {
+					for (uint32_t l = 0; l < layers; ++l) {
+						rc = mip_level_2d(ctx, lease, tab[(size_t)(k - 1u)*layers + l], prev_type, prev_pitch, pw, ph,
+							const_cast<void*>(tab[(size_t)k*layers + l]), w, h, filter, srgb);
+						if (rc != CFHIP_OK)
+							return rc;
+					}
+				} else if (need_x && need_y) {
+					rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, timg*layers);
 					if (rc != CFHIP_OK)
 						return rc;
+					e = cfhip_launch_mip_pass_layers(nullptr, prev_type, prev_pitch, x_first ? pw : ph, ctx->d_src, tw, th,
+						x_first ? 1 : 0, filter, srgb, 0, layers, s_tab, nullptr, 0, timg, stream);
+					if (e == hipSuccess)
+						e = cfhip_launch_mip_pass_layers(ctx->d_src, CFHIP_PIXEL_RGBA32F, (size_t)tw*16u, x_first ? ph : pw, nullptr, w, h,
+							x_first ? 0 : 1, filter, 0, srgb, layers, nullptr, o_tab, timg, 0, stream);
+				} else {
+					e = cfhip_launch_mip_pass_layers(nullptr, prev_type, prev_pitch, need_x ? pw : ph, nullptr, w, h,
+						need_x ? 1 : 0, filter, srgb, srgb, layers, s_tab, o_tab, 0, 0, stream);
 				}
-			} else if (need_x && need_y) {
-				rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, timg*layers);
-				if (rc != CFHIP_OK)
-					return rc;
-				e = cfhip_launch_mip_pass_layers(nullptr, prev_type, prev_pitch, x_first ? pw : ph, ctx->d_src, tw, th,
-					x_first ? 1 : 0, filter, srgb, 0, layers, s_tab, nullptr, 0, timg, stream);
-				if (e == hipSuccess)
-					e = cfhip_launch_mip_pass_layers(ctx->d_src, CFHIP_PIXEL_RGBA32F, (size_t)tw*16u, x_first ? ph : pw, nullptr, w, h,
-						x_first ? 0 : 1, filter, 0, srgb, layers, nullptr, o_tab, timg, 0, stream);
-			} else {
-				e = cfhip_launch_mip_pass_layers(nullptr, prev_type, prev_pitch, need_x ? pw : ph, nullptr, w, h,
-					need_x ? 1 : 0, filter, srgb, srgb, layers, s_tab, o_tab, 0, 0, stream);
+				if (e != hipSuccess)
+					return fail(ctx, CFHIP_E_DEVICE, "mip pass: %s", hipGetErrorString(e));
+				prev_type = CFHIP_PIXEL_RGBA32F;
+				prev_pitch = (size_t)w*16u;
+				pw = w; ph = h;
 			}
-			if (e != hipSuccess)
-				return fail(ctx, CFHIP_E_DEVICE, "mip pass: %s", hipGetErrorString(e));
-			prev_type = CFHIP_PIXEL_RGBA32F;
-			prev_pitch = (size_t)w*16u;
-			pw = w; ph = h;
 		}
-	}
-	return lease.done(!stream_);
+		return lease.done(!stream_);
+	});
 }
 
 // ---- mip post-pass (csrc/mip_post.hip): alpha-test coverage and normal renormalisation ---------------------------
-// one launch of the post-pass, timed like every encode launch (cfhip_last_kernel_ms / profiling)
-#define MIP_POST_TIMED(ctx, stream, launch_expr) do { \
-		hipEvent_t a_, b_; \
-		const int rc_ = next_event_pair((ctx), &a_, &b_); \
-		if (rc_ != CFHIP_OK) return rc_; \
-		HIP_TRY((ctx), hipEventRecord(a_, (stream))); \
-		const hipError_t le_ = (launch_expr); \
-		if (le_ != hipSuccess) return fail((ctx), CFHIP_E_DEVICE, "mip post-pass launch: %s", hipGetErrorString(le_)); \
-		HIP_TRY((ctx), hipEventRecord(b_, (stream))); \
-	} while (0)
-
 // the alpha component must be loadable: its size divides the pointer and the pitch
 static bool alpha_aligned(const void* p, size_t pitch, int pixel_type)
 {
@@ -2127,69 +2125,70 @@ static bool alpha_aligned(const void* p, size_t pitch, int pixel_type)
 int cfhip_alpha_coverage_device(cfhip_ctx* ctx, const cfhip_coverage_surface* surfaces, uint32_t count, float threshold,
 	float scale, uint32_t* counts_device, void* stream_)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	if (!surfaces)
-		return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces is NULL");
-	if (!counts_device)
-		return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: counts_device is NULL");
-	if (!count)
-		return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: count is 0");
-	if (!(threshold > 0.0f && threshold <= 1.0f))
-		return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: threshold %g outside (0, 1]", (double)threshold);
-	if (!(scale > 0.0f) || std::isinf(scale))
-		return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: scale %g is not a positive finite number", (double)scale);
-	std::vector<cfmp_surf> tab(count);
-	uint64_t wg = 0;
-	for (uint32_t i = 0; i < count; ++i) {
-		const cfhip_coverage_surface& s = surfaces[i];
-		if (!s.pixels)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u].pixels is NULL", i);
-		if (!s.width || !s.height)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u] has a zero width or height", i);
-		const size_t pb = pixel_bytes(s.pixel_type);
-		if (!pb)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u]: pixel type %d", i, s.pixel_type);
-		if (s.pitch_bytes < (size_t)s.width*pb)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u]: pitch_bytes %zu < %zu", i, s.pitch_bytes,
-				(size_t)s.width*pb);
-		if ((uint64_t)s.width*s.height > CFMP_MAX_TEXELS)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u]: more than 2^30 texels", i);
-		if (!alpha_aligned(s.pixels, s.pitch_bytes, s.pixel_type))
-			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u]: pixels or pitch_bytes not aligned to a component", i);
-		cfmp_surf& e = tab[i];
-		e.pixels = static_cast<const uint8_t*>(s.pixels);
-		e.pitch = s.pitch_bytes;
-		e.plane_off = 0;
-		e.width = s.width; e.height = s.height;
-		e.n = s.width*s.height;
-		e.pixel_type = s.pixel_type;
-		e.wg_begin = (uint32_t)wg;
-		e.ref = 0;
-		wg += (e.n + CFMP_CHUNK - 1u)/CFMP_CHUNK;
-		if (wg > 0x7FFFFFFFull)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: the surfaces are too large for one launch");
-	}
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	const hipStream_t stream = lease.stream;
-	begin_call(ctx, stream, "cfhip_mip_post_gather_kernel");
-	int rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab.size()*sizeof(cfmp_surf));
-	if (rc != CFHIP_OK)
-		return rc;
-	// pageable source: the runtime stages the copy before returning, so `tab` may die
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, tab.data(), tab.size()*sizeof(cfmp_surf), hipMemcpyHostToDevice, stream));
-	HIP_TRY(ctx, hipMemsetAsync(counts_device, 0, (size_t)count*4u, stream));
-	MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_gather(static_cast<const cfmp_surf*>(ctx->d_batch), count, 0u,
-		(uint32_t)wg, threshold, scale, scale, scale, 1u, 1u, nullptr, counts_device, stream));
-	return lease.done(!stream_);
+	return guarded(ctx, "alpha_coverage", [&]() -> int {
+		if (!surfaces)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces is NULL");
+		if (!counts_device)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: counts_device is NULL");
+		if (!count)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: count is 0");
+		if (!(threshold > 0.0f && threshold <= 1.0f))
+			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: threshold %g outside (0, 1]", (double)threshold);
+		if (!(scale > 0.0f) || std::isinf(scale))
+			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: scale %g is not a positive finite number", (double)scale);
+		std::vector<cfmp_surf> tab(count);
+		uint64_t wg = 0;
+		for (uint32_t i = 0; i < count; ++i) {
+			const cfhip_coverage_surface& s = surfaces[i];
+			if (!s.pixels)
+				return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u].pixels is NULL", i);
+			if (!s.width || !s.height)
+				return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u] has a zero width or height", i);
+			const size_t pb = pixel_bytes(s.pixel_type);
+			if (!pb)
+				return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u]: pixel type %d", i, s.pixel_type);
+			if (s.pitch_bytes < (size_t)s.width*pb)
+				return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u]: pitch_bytes %zu < %zu", i, s.pitch_bytes,
+					(size_t)s.width*pb);
+			if ((uint64_t)s.width*s.height > CFMP_MAX_TEXELS)
+				return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u]: more than 2^30 texels", i);
+			if (!alpha_aligned(s.pixels, s.pitch_bytes, s.pixel_type))
+				return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces[%u]: pixels or pitch_bytes not aligned to a component", i);
+			cfmp_surf& e = tab[i];
+			e.pixels = static_cast<const uint8_t*>(s.pixels);
+			e.pitch = s.pitch_bytes;
+			e.plane_off = 0;
+			e.width = s.width; e.height = s.height;
+			e.n = s.width*s.height;
+			e.pixel_type = s.pixel_type;
+			e.wg_begin = (uint32_t)wg;
+			e.ref = 0;
+			wg += (e.n + CFMP_CHUNK - 1u)/CFMP_CHUNK;
+			if (wg > 0x7FFFFFFFull)
+				return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: the surfaces are too large for one launch");
+		}
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		const hipStream_t stream = lease.stream;
+		begin_call(ctx, stream, "cfhip_mip_post_gather_kernel");
+		int rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab.size()*sizeof(cfmp_surf));
+		if (rc != CFHIP_OK)
+			return rc;
+		// pageable source: the runtime stages the copy before returning, so `tab` may die
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, tab.data(), tab.size()*sizeof(cfmp_surf), hipMemcpyHostToDevice, stream));
+		HIP_TRY(ctx, hipMemsetAsync(counts_device, 0, (size_t)count*4u, stream));
+		rc = timed(ctx, stream, "mip post-pass", [&] {
+			return cfhip_launch_mip_post_gather(static_cast<const cfmp_surf*>(ctx->d_batch), count, 0u, (uint32_t)wg, threshold,
+				scale, scale, scale, 1u, 1u, nullptr, counts_device, stream);
+		});
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 int cfhip_mip_post_array_device(cfhip_ctx* ctx, const void* const* srcs, uint32_t layers, int src_pixel_type,
@@ -2197,255 +2196,259 @@ int cfhip_mip_post_array_device(cfhip_ctx* ctx, const void* const* srcs, uint32_
 	const cfhip_mip_post_params* params, cfhip_mip_post_result* results_device, void* stream_)
 {
 	static_assert(sizeof(cfhip_mip_post_params) == 8 && sizeof(cfhip_mip_post_result) == 16, "the ABI's sizes");
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	if (!params)
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: params is NULL");
-	if (!srcs)
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: srcs is NULL");
-	if (!levels)
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: levels is NULL");
-	if (!layers || layers > 65535u)
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: layers is %u (1 to 65535 per call)", layers);
-	if (!width || !height)
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: a zero width or height (%ux%u)", width, height);
-	const size_t pb = pixel_bytes(src_pixel_type);
-	if (!pb)
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: src_pixel_type %d", src_pixel_type);
-	uint32_t max_levels = 1;
-	for (uint32_t d = std::max(width, height); d > 1; d >>= 1)
-		++max_levels;
-	if (levels_count < 2 || levels_count > max_levels)
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: levels_count is %u, a chain to repair has 2 to %u levels at %ux%u",
-			levels_count, max_levels, width, height);
-	const uint32_t flags = params->flags;
-	const uint32_t all_flags = CFHIP_MIP_POST_COVERAGE | CFHIP_MIP_POST_NORMALIZE | CFHIP_MIP_POST_SIGNED_NORMALS;
-	if (!flags || (flags & ~all_flags))
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: params->flags 0x%x: none or unknown", flags);
-	if ((flags & CFHIP_MIP_POST_SIGNED_NORMALS) && !(flags & CFHIP_MIP_POST_NORMALIZE))
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: params->flags: SIGNED_NORMALS without NORMALIZE");
-	const bool coverage = flags & CFHIP_MIP_POST_COVERAGE;
-	const float t = params->alpha_threshold;
-	if (coverage && !(t > 0.0f && t <= 1.0f))
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: params->alpha_threshold %g outside (0, 1]", (double)t);
-	if (src_pitch_bytes < (size_t)width*pb)
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: src_pitch_bytes %zu < %zu, a row", src_pitch_bytes, (size_t)width*pb);
-	if (coverage && !results_device)
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: results_device is NULL under COVERAGE");
-	if ((uint64_t)width*height > CFMP_MAX_TEXELS)
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: more than 2^30 texels in level 0");
-	const uint32_t per = levels_count - 1u;
-	const size_t nlev = (size_t)layers*per, nsurf = nlev + (coverage ? layers : 0u);
-	std::vector<cfmp_surf> tab(nsurf);
-	uint64_t wg = 0, plane = 0;
-	for (uint32_t l = 0; l < layers; ++l) {
-		if (!srcs[l])
-			return fail(ctx, CFHIP_E_INVALID, "mip_post: srcs[%u] is NULL", l);
-		if (coverage && !alpha_aligned(srcs[l], src_pitch_bytes, src_pixel_type))
-			return fail(ctx, CFHIP_E_INVALID, "mip_post: srcs[%u] or src_pitch_bytes not aligned to a component", l);
-		for (uint32_t k = 1; k < levels_count; ++k) {
-			const size_t i = (size_t)l*per + (k - 1u);
-			if (!levels[i])
-				return fail(ctx, CFHIP_E_INVALID, "mip_post: levels[%zu] (layer %u, level %u) is NULL", i, l, k);
-			if ((uintptr_t)levels[i] % 16u)
-				return fail(ctx, CFHIP_E_INVALID, "mip_post: levels[%zu] is not aligned to a texel (16 bytes)", i);
-			cfmp_surf& e = tab[i];
-			e.width = (width >> k) ? (width >> k) : 1u;
-			e.height = (height >> k) ? (height >> k) : 1u;
-			e.pixels = static_cast<const uint8_t*>(levels[i]);
-			e.pitch = (unsigned long long)e.width*16u;
-			e.plane_off = plane;
-			e.n = e.width*e.height;
-			e.pixel_type = CFHIP_PIXEL_RGBA32F;
+	return guarded(ctx, "mip_post", [&]() -> int {
+		if (!params)
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: params is NULL");
+		if (!srcs)
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: srcs is NULL");
+		if (!levels)
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: levels is NULL");
+		if (!layers || layers > 65535u)
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: layers is %u (1 to 65535 per call)", layers);
+		if (!width || !height)
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: a zero width or height (%ux%u)", width, height);
+		const size_t pb = pixel_bytes(src_pixel_type);
+		if (!pb)
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: src_pixel_type %d", src_pixel_type);
+		uint32_t max_levels = 1;
+		for (uint32_t d = std::max(width, height); d > 1; d >>= 1)
+			++max_levels;
+		if (levels_count < 2 || levels_count > max_levels)
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: levels_count is %u, a chain to repair has 2 to %u levels at %ux%u",
+				levels_count, max_levels, width, height);
+		const uint32_t flags = params->flags;
+		const uint32_t all_flags = CFHIP_MIP_POST_COVERAGE | CFHIP_MIP_POST_NORMALIZE | CFHIP_MIP_POST_SIGNED_NORMALS;
+		if (!flags || (flags & ~all_flags))
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: params->flags 0x%x: none or unknown", flags);
+		if ((flags & CFHIP_MIP_POST_SIGNED_NORMALS) && !(flags & CFHIP_MIP_POST_NORMALIZE))
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: params->flags: SIGNED_NORMALS without NORMALIZE");
+		const bool coverage = flags & CFHIP_MIP_POST_COVERAGE;
+		const float t = params->alpha_threshold;
+		if (coverage && !(t > 0.0f && t <= 1.0f))
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: params->alpha_threshold %g outside (0, 1]", (double)t);
+		if (src_pitch_bytes < (size_t)width*pb)
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: src_pitch_bytes %zu < %zu, a row", src_pitch_bytes, (size_t)width*pb);
+		if (coverage && !results_device)
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: results_device is NULL under COVERAGE");
+		if ((uint64_t)width*height > CFMP_MAX_TEXELS)
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: more than 2^30 texels in level 0");
+		const uint32_t per = levels_count - 1u;
+		const size_t nlev = (size_t)layers*per, nsurf = nlev + (coverage ? layers : 0u);
+		std::vector<cfmp_surf> tab(nsurf);
+		uint64_t wg = 0, plane = 0;
+		for (uint32_t l = 0; l < layers; ++l) {
+			if (!srcs[l])
+				return fail(ctx, CFHIP_E_INVALID, "mip_post: srcs[%u] is NULL", l);
+			if (coverage && !alpha_aligned(srcs[l], src_pitch_bytes, src_pixel_type))
+				return fail(ctx, CFHIP_E_INVALID, "mip_post: srcs[%u] or src_pitch_bytes not aligned to a component", l);
+			for (uint32_t k = 1; k < levels_count; ++k) {
+				const size_t i = (size_t)l*per + (k - 1u);
+				if (!levels[i])
+					return fail(ctx, CFHIP_E_INVALID, "mip_post: levels[%zu] (layer %u, level %u) is NULL", i, l, k);
+				if ((uintptr_t)levels[i] % 16u)
+					return fail(ctx, CFHIP_E_INVALID, "mip_post: levels[%zu] is not aligned to a texel (16 bytes)", i);
+				cfmp_surf& e = tab[i];
+				e.width = (width >> k) ? (width >> k) : 1u;
+				e.height = (height >> k) ? (height >> k) : 1u;
+				e.pixels = static_cast<const uint8_t*>(levels[i]);
+				e.pitch = (unsigned long long)e.width*16u;
+				e.plane_off = plane;
+				e.n = e.width*e.height;
+				e.pixel_type = CFHIP_PIXEL_RGBA32F;
+				e.wg_begin = (uint32_t)wg;
+				e.ref = (uint32_t)(nlev + l);
+				wg += (e.n + CFMP_CHUNK - 1u)/CFMP_CHUNK;
+				plane += e.n;
+			}
+		}
+		const uint64_t wg_levels = wg;
+		for (uint32_t l = 0; coverage && l < layers; ++l) {
+			cfmp_surf& e = tab[nlev + l];
+			e.pixels = static_cast<const uint8_t*>(srcs[l]);
+			e.pitch = src_pitch_bytes;
+			e.plane_off = 0;
+			e.width = width; e.height = height;
+			e.n = width*height;
+			e.pixel_type = src_pixel_type;
 			e.wg_begin = (uint32_t)wg;
-			e.ref = (uint32_t)(nlev + l);
+			e.ref = 0;
 			wg += (e.n + CFMP_CHUNK - 1u)/CFMP_CHUNK;
-			plane += e.n;
 		}
-	}
-	const uint64_t wg_levels = wg;
-	for (uint32_t l = 0; coverage && l < layers; ++l) {
-		cfmp_surf& e = tab[nlev + l];
-		e.pixels = static_cast<const uint8_t*>(srcs[l]);
-		e.pitch = src_pitch_bytes;
-		e.plane_off = 0;
-		e.width = width; e.height = height;
-		e.n = width*height;
-		e.pixel_type = src_pixel_type;
-		e.wg_begin = (uint32_t)wg;
-		e.ref = 0;
-		wg += (e.n + CFMP_CHUNK - 1u)/CFMP_CHUNK;
-	}
-	if (wg > 0x7FFFFFFFull)
-		return fail(ctx, CFHIP_E_INVALID, "mip_post: the surfaces are too large for one launch");
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	const hipStream_t stream = lease.stream;
-	begin_call(ctx, stream, coverage ? "cfhip_mip_post_count_kernel" : "cfhip_mip_post_apply_kernel");
-	// d_batch: the surface table, then the levels' search states, then the counters; d_src: the alpha plane
-	const size_t tab_bytes = (nsurf*sizeof(cfmp_surf) + 15u) & ~(size_t)15u;
-	const size_t state_bytes = coverage ? nlev*sizeof(cfmp_state) : 0u;
-	const size_t cnt_bytes = coverage ? nsurf*CFMP_SLOTS*4u : 0u;
-	int rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab_bytes + state_bytes + cnt_bytes);
-	if (rc == CFHIP_OK && coverage)
-		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, (size_t)plane*4u);
-	if (rc != CFHIP_OK)
-		return rc;
-	uint8_t* base = static_cast<uint8_t*>(ctx->d_batch);
-	const cfmp_surf* d_tab = reinterpret_cast<const cfmp_surf*>(base);
-	cfmp_state* d_state = coverage ? reinterpret_cast<cfmp_state*>(base + tab_bytes) : nullptr;
-	uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base + tab_bytes + state_bytes);
-	// pageable source: the runtime stages the copy before returning, so `tab` may die
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, tab.data(), nsurf*sizeof(cfmp_surf), hipMemcpyHostToDevice, stream));
-	if (coverage) {
-		// (the states too: a level's first decide step writes every field it later reads, dir included)
-		HIP_TRY(ctx, hipMemsetAsync(base + tab_bytes, 0, state_bytes + cnt_bytes, stream));
-		float* d_plane = static_cast<float*>(ctx->d_src);
-		const float s_min = 0.25f, s_max = 4.0f;
-		MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_gather(d_tab, (uint32_t)nsurf, (uint32_t)nlev, (uint32_t)wg, t, 1.0f,
-			s_min, s_max, 3u, CFMP_SLOTS, d_plane, d_cnt, stream));
-		MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_decide(d_tab, (uint32_t)nlev, 1, d_state, d_cnt, results_device, stream));
-		for (uint32_t pass = 0; pass < CFMP_SEARCH_PASSES; ++pass) {
-			MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_count(d_tab, (uint32_t)nlev, (uint32_t)wg_levels, t, d_state,
-				d_plane, d_cnt, stream));
-			MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_decide(d_tab, (uint32_t)nlev, 0, d_state, d_cnt, results_device,
-				stream));
+		if (wg > 0x7FFFFFFFull)
+			return fail(ctx, CFHIP_E_INVALID, "mip_post: the surfaces are too large for one launch");
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		const hipStream_t stream = lease.stream;
+		begin_call(ctx, stream, coverage ? "cfhip_mip_post_count_kernel" : "cfhip_mip_post_apply_kernel");
+		// d_batch: the surface table, then the levels' search states, then the counters; d_src: the alpha plane
+		const size_t tab_bytes = (nsurf*sizeof(cfmp_surf) + 15u) & ~(size_t)15u;
+		const size_t state_bytes = coverage ? nlev*sizeof(cfmp_state) : 0u;
+		const size_t cnt_bytes = coverage ? nsurf*CFMP_SLOTS*4u : 0u;
+		int rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab_bytes + state_bytes + cnt_bytes);
+		if (rc == CFHIP_OK && coverage)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, (size_t)plane*4u);
+		if (rc != CFHIP_OK)
+			return rc;
+		uint8_t* base = static_cast<uint8_t*>(ctx->d_batch);
+		const cfmp_surf* d_tab = reinterpret_cast<const cfmp_surf*>(base);
+		cfmp_state* d_state = coverage ? reinterpret_cast<cfmp_state*>(base + tab_bytes) : nullptr;
+		uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base + tab_bytes + state_bytes);
+		// pageable source: the runtime stages the copy before returning, so `tab` may die
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, tab.data(), nsurf*sizeof(cfmp_surf), hipMemcpyHostToDevice, stream));
+		// every launch of the pass is a timed span of its own
+		const auto post = [&](auto&& launch) { return timed(ctx, stream, "mip post-pass", launch); };
+		if (coverage) {
+			// (the states too: a level's first decide step writes every field it later reads, dir included)
+			HIP_TRY(ctx, hipMemsetAsync(base + tab_bytes, 0, state_bytes + cnt_bytes, stream));
+			float* d_plane = static_cast<float*>(ctx->d_src);
+			const float s_min = 0.25f, s_max = 4.0f;
+			const auto decide = [&](int first) {
+				return post([&] {
+					return cfhip_launch_mip_post_decide(d_tab, (uint32_t)nlev, first, d_state, d_cnt, results_device, stream);
+				});
+			};
+			rc = post([&] {
+				return cfhip_launch_mip_post_gather(d_tab, (uint32_t)nsurf, (uint32_t)nlev, (uint32_t)wg, t, 1.0f, s_min, s_max, 3u,
+					CFMP_SLOTS, d_plane, d_cnt, stream);
+			});
+			if (rc == CFHIP_OK)
+				rc = decide(1);
+			for (uint32_t pass = 0; rc == CFHIP_OK && pass < CFMP_SEARCH_PASSES; ++pass) {
+				rc = post([&] {
+					return cfhip_launch_mip_post_count(d_tab, (uint32_t)nlev, (uint32_t)wg_levels, t, d_state, d_plane, d_cnt, stream);
+				});
+				if (rc == CFHIP_OK)
+					rc = decide(0);
+			}
+			if (rc != CFHIP_OK)
+				return rc;
 		}
-	}
-	MIP_POST_TIMED(ctx, stream, cfhip_launch_mip_post_apply(d_tab, (uint32_t)nlev, (uint32_t)wg_levels, flags, d_state, stream));
-	return lease.done(!stream_);
+		rc = post([&] {
+			return cfhip_launch_mip_post_apply(d_tab, (uint32_t)nlev, (uint32_t)wg_levels, flags, d_state, stream);
+		});
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 // ---- alpha bleeding (csrc/alpha_bleed.hip): colour under transparent texels from the nearest visible one -------------
-// one launch of the pass, timed like every encode launch (cfhip_last_kernel_ms / profiling)
-#define BLEED_TIMED(ctx, stream, launch_expr) do { \
-		hipEvent_t a_, b_; \
-		const int rc_ = next_event_pair((ctx), &a_, &b_); \
-		if (rc_ != CFHIP_OK) return rc_; \
-		HIP_TRY((ctx), hipEventRecord(a_, (stream))); \
-		const hipError_t le_ = (launch_expr); \
-		if (le_ != hipSuccess) return fail((ctx), CFHIP_E_DEVICE, "alpha_bleed launch: %s", hipGetErrorString(le_)); \
-		HIP_TRY((ctx), hipEventRecord(b_, (stream))); \
-	} while (0)
-
 int cfhip_alpha_bleed_array_device(cfhip_ctx* ctx, void* const* images, uint32_t layers, int pixel_type, uint32_t width,
 	uint32_t height, size_t pitch_bytes, const cfhip_bleed_params* params, cfhip_bleed_result* results_device, void* stream_)
 {
 	static_assert(sizeof(cfhip_bleed_params) == 12 && sizeof(cfhip_bleed_result) == 16, "the ABI's sizes");
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	if (!params)
-		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params is NULL");
-	if (!images)
-		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: images is NULL");
-	if (!layers || layers > 65535u)
-		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: layers is %u (1 to 65535 per call)", layers);
-	if (!width || !height || width > CFAB_MAX_SIDE || height > CFAB_MAX_SIDE)
-		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: width and height are 1 to %u each, not %ux%u", CFAB_MAX_SIDE, width, height);
-	const size_t pb = pixel_bytes(pixel_type);
-	if (!pb)
-		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: pixel_type %d", pixel_type);
-	if (params->flags & ~(uint32_t)(CFHIP_BLEED_WRAP_X | CFHIP_BLEED_WRAP_Y))
-		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params->flags 0x%x: unknown", params->flags);
-	const float t = params->alpha_threshold;
-	if (!(t >= 0.0f && t < 1.0f))
-		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params->alpha_threshold %g outside [0, 1)", (double)t);
-	if (params->max_distance > 65535u)
-		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params->max_distance %u above 65535", params->max_distance);
-	if (pitch_bytes < (size_t)width*pb)
-		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: pitch_bytes %zu < %zu, a row", pitch_bytes, (size_t)width*pb);
-	if (pitch_bytes % (pb/4u))
-		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: pitch_bytes %zu not aligned to a component (%zu bytes)", pitch_bytes, pb/4u);
-	const uint64_t texels = (uint64_t)layers*width*height;
-	if (texels > CFAB_MAX_TEXELS)
-		return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: more than 2^31 texels in one call");
-	for (uint32_t l = 0; l < layers; ++l) {
-		if (!images[l])
-			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: images[%u] is NULL", l);
-		if ((uintptr_t)images[l] % (pb/4u))
-			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: images[%u] not aligned to a component (%zu bytes)", l, pb/4u);
-	}
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	const hipStream_t stream = lease.stream;
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	ctx->last_kernel = "cfhip_alpha_bleed_step_kernel";
-	// d_batch: the layers' pointers; d_src: the two seed buffers, 4 bytes per texel each
-	int rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, (size_t)layers*sizeof(void*));
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, (size_t)texels*8u);
-	if (rc != CFHIP_OK)
-		return rc;
-	// pageable source: the runtime stages the copy before returning
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, images, (size_t)layers*sizeof(void*), hipMemcpyHostToDevice, stream));
-	if (results_device)
-		HIP_TRY(ctx, hipMemsetAsync(results_device, 0, (size_t)layers*sizeof(cfhip_bleed_result), stream));
-	cfab_call call;
-	call.images = static_cast<void* const*>(ctx->d_batch);
-	call.pitch = pitch_bytes;
-	call.width = width; call.height = height;
-	call.pixel_type = pixel_type;
-	call.flags = params->flags;
-	uint32_t* buf[2] = {static_cast<uint32_t*>(ctx->d_src), static_cast<uint32_t*>(ctx->d_src) + texels};
-	uint32_t p2 = 1;
-	while (p2 < std::max(width, height))
-		p2 <<= 1;
-	// on a wrapped axis positions are taken modulo the size: so is the step
-	const auto sx = [&](uint32_t k) { return (call.flags & CFHIP_BLEED_WRAP_X) ? k % width : k; };
-	const auto sy = [&](uint32_t k) { return (call.flags & CFHIP_BLEED_WRAP_Y) ? k % height : k; };
-	BLEED_TIMED(ctx, stream, cfhip_launch_alpha_bleed_seed(&call, layers, t, buf[0], results_device, stream));
-	int cur = 0;
-	for (uint32_t k = p2 >> 1; k >= 1u; k >>= 1, cur ^= 1)
-		BLEED_TIMED(ctx, stream, cfhip_launch_alpha_bleed_step(&call, layers, sx(k), sy(k), buf[cur], buf[cur ^ 1], stream));
-	BLEED_TIMED(ctx, stream, cfhip_launch_alpha_bleed_fill(&call, layers, sx(1u), sy(1u), params->max_distance*params->max_distance,
-		buf[cur], results_device, stream));
-	return lease.done(!stream_);
+	return guarded(ctx, "alpha_bleed", [&]() -> int {
+		if (!params)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params is NULL");
+		if (!images)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: images is NULL");
+		if (!layers || layers > 65535u)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: layers is %u (1 to 65535 per call)", layers);
+		if (!width || !height || width > CFAB_MAX_SIDE || height > CFAB_MAX_SIDE)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: width and height are 1 to %u each, not %ux%u", CFAB_MAX_SIDE, width, height);
+		const size_t pb = pixel_bytes(pixel_type);
+		if (!pb)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: pixel_type %d", pixel_type);
+		if (params->flags & ~(uint32_t)(CFHIP_BLEED_WRAP_X | CFHIP_BLEED_WRAP_Y))
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params->flags 0x%x: unknown", params->flags);
+		const float t = params->alpha_threshold;
+		if (!(t >= 0.0f && t < 1.0f))
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params->alpha_threshold %g outside [0, 1)", (double)t);
+		if (params->max_distance > 65535u)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params->max_distance %u above 65535", params->max_distance);
+		if (pitch_bytes < (size_t)width*pb)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: pitch_bytes %zu < %zu, a row", pitch_bytes, (size_t)width*pb);
+		if (pitch_bytes % (pb/4u))
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: pitch_bytes %zu not aligned to a component (%zu bytes)", pitch_bytes, pb/4u);
+		const uint64_t texels = (uint64_t)layers*width*height;
+		if (texels > CFAB_MAX_TEXELS)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: more than 2^31 texels in one call");
+		for (uint32_t l = 0; l < layers; ++l) {
+			if (!images[l])
+				return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: images[%u] is NULL", l);
+			if ((uintptr_t)images[l] % (pb/4u))
+				return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: images[%u] not aligned to a component (%zu bytes)", l, pb/4u);
+		}
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		const hipStream_t stream = lease.stream;
+		begin_call(ctx, stream, "cfhip_alpha_bleed_step_kernel");
+		// d_batch: the layers' pointers; d_src: the two seed buffers, 4 bytes per texel each
+		int rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, (size_t)layers*sizeof(void*));
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, (size_t)texels*8u);
+		if (rc != CFHIP_OK)
+			return rc;
+		// pageable source: the runtime stages the copy before returning
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, images, (size_t)layers*sizeof(void*), hipMemcpyHostToDevice, stream));
+		if (results_device)
+			HIP_TRY(ctx, hipMemsetAsync(results_device, 0, (size_t)layers*sizeof(cfhip_bleed_result), stream));
+		cfab_call call;
+		call.images = static_cast<void* const*>(ctx->d_batch);
+		call.pitch = pitch_bytes;
+		call.width = width; call.height = height;
+		call.pixel_type = pixel_type;
+		call.flags = params->flags;
+		uint32_t* buf[2] = {static_cast<uint32_t*>(ctx->d_src), static_cast<uint32_t*>(ctx->d_src) + texels};
+		uint32_t p2 = 1;
+		while (p2 < std::max(width, height))
+			p2 <<= 1;
+		// on a wrapped axis positions are taken modulo the size: so is the step
+		const auto sx = [&](uint32_t k) { return (call.flags & CFHIP_BLEED_WRAP_X) ? k % width : k; };
+		const auto sy = [&](uint32_t k) { return (call.flags & CFHIP_BLEED_WRAP_Y) ? k % height : k; };
+		// every launch of the pass is a timed span of its own
+		const auto bleed = [&](auto&& launch) { return timed(ctx, stream, "alpha_bleed", launch); };
+		rc = bleed([&] { return cfhip_launch_alpha_bleed_seed(&call, layers, t, buf[0], results_device, stream); });
+		int cur = 0;
+		for (uint32_t k = p2 >> 1; rc == CFHIP_OK && k >= 1u; k >>= 1, cur ^= 1)
+			rc = bleed([&] { return cfhip_launch_alpha_bleed_step(&call, layers, sx(k), sy(k), buf[cur], buf[cur ^ 1], stream); });
+		if (rc == CFHIP_OK)
+			rc = bleed([&] {
+				return cfhip_launch_alpha_bleed_fill(&call, layers, sx(1u), sy(1u), params->max_distance*params->max_distance,
+					buf[cur], results_device, stream);
+			});
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 int cfhip_resize_device(cfhip_ctx* ctx, const void* src, int src_pixel_type, uint32_t src_width,
 	uint32_t src_height, size_t src_pitch_bytes, int color_space, int filter, void* dst,
 	uint32_t dst_width, uint32_t dst_height, void* stream_)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	if (!src || !dst || !src_width || !src_height || !dst_width || !dst_height)
-		return fail(ctx, CFHIP_E_INVALID, "resize: NULL or empty argument");
-	int rc = check_mip_args(ctx, "resize", src_pixel_type, color_space, filter, src_width, src_height, 0, 1,
-		src_pitch_bytes);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	if (src_width == dst_width && src_height == dst_height) {
-		// Image::resize returns the image itself (Image.cpp:1330-1334): the texels as RGBAF, no
-		// colour-space round trip (a 1:1 box footprint is the texel)
-		HIP_TRY(ctx, cfhip_launch_mip_resize(src, src_pixel_type, src_pitch_bytes, src_width, src_height, dst,
-			dst_width, dst_height, CFHIP_FILTER_BOX, 0, lease.stream));
-	} else {
-		rc = mip_level_2d(ctx, lease, src, src_pixel_type, src_pitch_bytes, src_width, src_height, dst,
-			dst_width, dst_height, filter, color_space == CFHIP_COLOR_SRGB ? 1 : 0);
+	return guarded(ctx, "resize", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		if (!src || !dst || !src_width || !src_height || !dst_width || !dst_height)
+			return fail(ctx, CFHIP_E_INVALID, "resize: NULL or empty argument");
+		int rc = check_mip_args(ctx, "resize", src_pixel_type, color_space, filter, src_width, src_height, 0, 1,
+			src_pitch_bytes);
 		if (rc != CFHIP_OK)
 			return rc;
-	}
-	return lease.done(!stream_);
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		if (src_width == dst_width && src_height == dst_height) {
+			// Image::resize returns the image itself (Image.cpp:1330-1334): the texels as RGBAF, no
+			// colour-space round trip (a 1:1 box footprint is the texel)
+			HIP_TRY(ctx, cfhip_launch_mip_resize(src, src_pixel_type, src_pitch_bytes, src_width, src_height, dst,
+				dst_width, dst_height, CFHIP_FILTER_BOX, 0, lease.stream));
+		} else {
+			rc = mip_level_2d(ctx, lease, src, src_pixel_type, src_pitch_bytes, src_width, src_height, dst,
+				dst_width, dst_height, filter, color_space == CFHIP_COLOR_SRGB ? 1 : 0);
+			if (rc != CFHIP_OK)
+				return rc;
+		}
+		return lease.done(!stream_);
+	});
 }
 
 // Image's pixel operations (csrc/image_ops.hip).  No staging buffer is touched, so no StagingLease: the call
@@ -2453,130 +2456,122 @@ int cfhip_resize_device(cfhip_ctx* ctx, const void* src, int src_pixel_type, uin
 int cfhip_image_ops_device(cfhip_ctx* ctx, const void* src, int src_pixel_type, uint32_t w, uint32_t h,
 	size_t src_pitch_bytes, const cfhip_image_ops* ops, void* dst, size_t dst_pitch_bytes, void* stream_)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	if (!src || !dst || !ops)
-		return fail(ctx, CFHIP_E_INVALID, "image ops: src, dst or ops is NULL");
-	if (!w || !h)
-		return fail(ctx, CFHIP_E_INVALID, "image ops: empty image %ux%u", w, h);
-	if (w > (1u << 20) || h > (1u << 20))
-		return fail(ctx, CFHIP_E_INVALID, "image ops: image %ux%u too large for one launch", w, h);
-	if (src_pixel_type < CFHIP_PIXEL_RGBA8 || src_pixel_type > CFHIP_PIXEL_RGBA16F)
-		return fail(ctx, CFHIP_E_INVALID, "image ops: pixel type %d", src_pixel_type);
-	const uint32_t all_ops = CFHIP_IMAGE_OP_COLOR_SPACE | CFHIP_IMAGE_OP_ROTATE | CFHIP_IMAGE_OP_GRAYSCALE |
-		CFHIP_IMAGE_OP_NORMAL_MAP | CFHIP_IMAGE_OP_FLIP_X | CFHIP_IMAGE_OP_FLIP_Y | CFHIP_IMAGE_OP_SWIZZLE |
-		CFHIP_IMAGE_OP_PREMULTIPLY;
-	if (ops->ops & ~all_ops)
-		return fail(ctx, CFHIP_E_INVALID, "image ops: unknown op bits 0x%x", ops->ops & ~all_ops);
-	for (int cs : {ops->src_color_space, ops->dst_color_space})
-		if (cs != CFHIP_COLOR_LINEAR && cs != CFHIP_COLOR_SRGB)
-			return fail(ctx, CFHIP_E_INVALID, "image ops: colour space %d", cs);
-	if (ops->rotate < CFHIP_ROTATE_CW90 || ops->rotate > CFHIP_ROTATE_CCW270)
-		return fail(ctx, CFHIP_E_INVALID, "image ops: rotate angle %d", ops->rotate);
-	if (ops->normal_options & ~(uint32_t)(CFHIP_NORMAL_KEEP_SIGN | CFHIP_NORMAL_WRAP_X | CFHIP_NORMAL_WRAP_Y))
-		return fail(ctx, CFHIP_E_INVALID, "image ops: normal options 0x%x", ops->normal_options);
-	for (int c = 0; c < 4; ++c)
-		if (ops->swizzle[c] < CFHIP_CHANNEL_RED || ops->swizzle[c] > CFHIP_CHANNEL_NONE)
-			return fail(ctx, CFHIP_E_INVALID, "image ops: swizzle[%d] channel %d", c, ops->swizzle[c]);
-	if (ops->rgbf > 1u)
-		return fail(ctx, CFHIP_E_INVALID, "image ops: rgbf flag %u", ops->rgbf);
-	const size_t pb = pixel_bytes(src_pixel_type);
-	const bool quarter = (ops->ops & CFHIP_IMAGE_OP_ROTATE) && ops->rotate != CFHIP_ROTATE_CW180 &&
-		ops->rotate != CFHIP_ROTATE_CCW180;
-	const uint32_t rw = quarter ? h : w, rh = quarter ? w : h;
-	if (src_pitch_bytes < (size_t)w*pb)
-		return fail(ctx, CFHIP_E_INVALID, "image ops: source pitch %zu < %zu", src_pitch_bytes, (size_t)w*pb);
-	if (dst_pitch_bytes < (size_t)rw*16u)
-		return fail(ctx, CFHIP_E_INVALID, "image ops: destination pitch %zu < %zu", dst_pitch_bytes, (size_t)rw*16u);
-	// the kernel loads whole texels and stores float4
-	if ((uintptr_t)src % pb || src_pitch_bytes % pb || (uintptr_t)dst % 16u || dst_pitch_bytes % 16u)
-		return fail(ctx, CFHIP_E_INVALID, "image ops: src / dst or a pitch not aligned to its texel size");
-	const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)(h - 1u)*src_pitch_bytes + (size_t)w*pb;
-	const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)(rh - 1u)*dst_pitch_bytes + (size_t)rw*16u;
-	if (s0 < d1 && d0 < s1)
-		return fail(ctx, CFHIP_E_INVALID, "image ops: src and dst overlap");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	const hipStream_t stream = stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream;
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	ctx->last_kernel = "cfhip_image_ops_kernel";
-	hipEvent_t a, b;
-	int rc = next_event_pair(ctx, &a, &b);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipEventRecord(a, stream));
-	const hipError_t e = cfhip_launch_image_ops(src, src_pixel_type, src_pitch_bytes, w, h, ops, dst,
-		dst_pitch_bytes, stream);
-	if (e != hipSuccess)
-		return fail(ctx, CFHIP_E_DEVICE, "image ops launch: %s", hipGetErrorString(e));
-	HIP_TRY(ctx, hipEventRecord(b, stream));
-	if (!stream_)
-		HIP_TRY(ctx, hipStreamSynchronize(stream));
-	return CFHIP_OK;
+	return guarded(ctx, "image ops", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		if (!src || !dst || !ops)
+			return fail(ctx, CFHIP_E_INVALID, "image ops: src, dst or ops is NULL");
+		if (!w || !h)
+			return fail(ctx, CFHIP_E_INVALID, "image ops: empty image %ux%u", w, h);
+		if (w > (1u << 20) || h > (1u << 20))
+			return fail(ctx, CFHIP_E_INVALID, "image ops: image %ux%u too large for one launch", w, h);
+		if (src_pixel_type < CFHIP_PIXEL_RGBA8 || src_pixel_type > CFHIP_PIXEL_RGBA16F)
+			return fail(ctx, CFHIP_E_INVALID, "image ops: pixel type %d", src_pixel_type);
+		const uint32_t all_ops = CFHIP_IMAGE_OP_COLOR_SPACE | CFHIP_IMAGE_OP_ROTATE | CFHIP_IMAGE_OP_GRAYSCALE |
+			CFHIP_IMAGE_OP_NORMAL_MAP | CFHIP_IMAGE_OP_FLIP_X | CFHIP_IMAGE_OP_FLIP_Y | CFHIP_IMAGE_OP_SWIZZLE |
+			CFHIP_IMAGE_OP_PREMULTIPLY;
+		if (ops->ops & ~all_ops)
+			return fail(ctx, CFHIP_E_INVALID, "image ops: unknown op bits 0x%x", ops->ops & ~all_ops);
+		for (int cs : {ops->src_color_space, ops->dst_color_space})
+			if (cs != CFHIP_COLOR_LINEAR && cs != CFHIP_COLOR_SRGB)
+				return fail(ctx, CFHIP_E_INVALID, "image ops: colour space %d", cs);
+		if (ops->rotate < CFHIP_ROTATE_CW90 || ops->rotate > CFHIP_ROTATE_CCW270)
+			return fail(ctx, CFHIP_E_INVALID, "image ops: rotate angle %d", ops->rotate);
+		if (ops->normal_options & ~(uint32_t)(CFHIP_NORMAL_KEEP_SIGN | CFHIP_NORMAL_WRAP_X | CFHIP_NORMAL_WRAP_Y))
+			return fail(ctx, CFHIP_E_INVALID, "image ops: normal options 0x%x", ops->normal_options);
+		for (int c = 0; c < 4; ++c)
+			if (ops->swizzle[c] < CFHIP_CHANNEL_RED || ops->swizzle[c] > CFHIP_CHANNEL_NONE)
+				return fail(ctx, CFHIP_E_INVALID, "image ops: swizzle[%d] channel %d", c, ops->swizzle[c]);
+		if (ops->rgbf > 1u)
+			return fail(ctx, CFHIP_E_INVALID, "image ops: rgbf flag %u", ops->rgbf);
+		const size_t pb = pixel_bytes(src_pixel_type);
+		const bool quarter = (ops->ops & CFHIP_IMAGE_OP_ROTATE) && ops->rotate != CFHIP_ROTATE_CW180 &&
+			ops->rotate != CFHIP_ROTATE_CCW180;
+		const uint32_t rw = quarter ? h : w, rh = quarter ? w : h;
+		if (src_pitch_bytes < (size_t)w*pb)
+			return fail(ctx, CFHIP_E_INVALID, "image ops: source pitch %zu < %zu", src_pitch_bytes, (size_t)w*pb);
+		if (dst_pitch_bytes < (size_t)rw*16u)
+			return fail(ctx, CFHIP_E_INVALID, "image ops: destination pitch %zu < %zu", dst_pitch_bytes, (size_t)rw*16u);
+		// the kernel loads whole texels and stores float4
+		if ((uintptr_t)src % pb || src_pitch_bytes % pb || (uintptr_t)dst % 16u || dst_pitch_bytes % 16u)
+			return fail(ctx, CFHIP_E_INVALID, "image ops: src / dst or a pitch not aligned to its texel size");
+		const uintptr_t s0 = (uintptr_t)src, s1 = s0 + (size_t)(h - 1u)*src_pitch_bytes + (size_t)w*pb;
+		const uintptr_t d0 = (uintptr_t)dst, d1 = d0 + (size_t)(rh - 1u)*dst_pitch_bytes + (size_t)rw*16u;
+		if (s0 < d1 && d0 < s1)
+			return fail(ctx, CFHIP_E_INVALID, "image ops: src and dst overlap");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		const hipStream_t stream = call_stream(ctx, stream_);
+		begin_call(ctx, stream, "cfhip_image_ops_kernel");
+		const int rc = timed(ctx, stream, "image ops", [&] {
+			return cfhip_launch_image_ops(src, src_pixel_type, src_pitch_bytes, w, h, ops, dst, dst_pitch_bytes, stream);
+		});
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!stream_)
+			HIP_TRY(ctx, hipStreamSynchronize(stream));
+		return CFHIP_OK;
+	});
 }
 
 int cfhip_generate_mips3d_device(cfhip_ctx* ctx, const void* src, int src_pixel_type,
 	uint32_t width, uint32_t height, uint32_t depth, size_t src_pitch_bytes, size_t src_slice_pitch_bytes,
 	int color_space, int filter, void* const* dst_levels, uint32_t levels, void* stream_)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	if (!src || !width || !height || !depth || !levels || (levels > 1 && !dst_levels))
-		return fail(ctx, CFHIP_E_INVALID, "3-D mip generation: NULL or empty argument");
-	int rc = check_mip_args(ctx, "3-D mip generation", src_pixel_type, color_space, filter, width, height, depth,
-		levels, src_pitch_bytes);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (src_slice_pitch_bytes < src_pitch_bytes*height)
-		return fail(ctx, CFHIP_E_INVALID, "3-D mip generation: slice pitch smaller than a slice");
-	for (uint32_t k = 1; k < levels; ++k)
-		if (!dst_levels[k - 1])
-			return fail(ctx, CFHIP_E_INVALID, "3-D mip generation: dst_levels[%u] is NULL", k - 1);
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	const hipStream_t stream = lease.stream;
-	const int srgb = color_space == CFHIP_COLOR_SRGB ? 1 : 0;
-	// level k (Texture.cpp:1345-1402): every slice of level k-1 is resized to the level's width and
-	// height with Image::resize, then generateMips3d interpolates the slices along the depth
-	const uint8_t* prev = static_cast<const uint8_t*>(src);
-	int prev_type = src_pixel_type;
-	size_t prev_pitch = src_pitch_bytes, prev_slice = src_slice_pitch_bytes;
-	uint32_t pw = width, ph = height, pd = depth;
-	for (uint32_t k = 1; k < levels; ++k) {
-		const uint32_t w = (width >> k) ? (width >> k) : 1u, h = (height >> k) ? (height >> k) : 1u,
-			d = (depth >> k) ? (depth >> k) : 1u;
-		const size_t slice_bytes = (size_t)w*h*16u;
-		// the slice buffer is a context buffer like the staging buffers: owned through the same lease
-		rc = lease.acquire();
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_mip3d, &ctx->mip3d_cap, slice_bytes*pd);
+	return guarded(ctx, "3-D mip generation", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		if (!src || !width || !height || !depth || !levels || (levels > 1 && !dst_levels))
+			return fail(ctx, CFHIP_E_INVALID, "3-D mip generation: NULL or empty argument");
+		int rc = check_mip_args(ctx, "3-D mip generation", src_pixel_type, color_space, filter, width, height, depth,
+			levels, src_pitch_bytes);
 		if (rc != CFHIP_OK)
 			return rc;
-		for (uint32_t i = 0; i < pd; ++i) {
-			uint8_t* dst = static_cast<uint8_t*>(ctx->d_mip3d) + slice_bytes*i;
-			if (w == pw && h == ph)    // Image::resize returns a copy (Image.cpp:1330-1334): an exact Box identity
-				HIP_TRY(ctx, cfhip_launch_mip_resize(prev + prev_slice*i, prev_type, prev_pitch, pw, ph, dst, w, h,
-					CFHIP_FILTER_BOX, 0, stream));
-			else {
-				rc = mip_level_2d(ctx, lease, prev + prev_slice*i, prev_type, prev_pitch, pw, ph, dst, w, h, filter, srgb);
-				if (rc != CFHIP_OK)
-					return rc;
+		if (src_slice_pitch_bytes < src_pitch_bytes*height)
+			return fail(ctx, CFHIP_E_INVALID, "3-D mip generation: slice pitch smaller than a slice");
+		for (uint32_t k = 1; k < levels; ++k)
+			if (!dst_levels[k - 1])
+				return fail(ctx, CFHIP_E_INVALID, "3-D mip generation: dst_levels[%u] is NULL", k - 1);
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		const hipStream_t stream = lease.stream;
+		const int srgb = color_space == CFHIP_COLOR_SRGB ? 1 : 0;
+		// level k (Texture.cpp:1345-1402): every slice of level k-1 is resized to the level's width and
+		// height with Image::resize, then generateMips3d interpolates the slices along the depth
+		const uint8_t* prev = static_cast<const uint8_t*>(src);
+		int prev_type = src_pixel_type;
+		size_t prev_pitch = src_pitch_bytes, prev_slice = src_slice_pitch_bytes;
+		uint32_t pw = width, ph = height, pd = depth;
+		for (uint32_t k = 1; k < levels; ++k) {
+			const uint32_t w = (width >> k) ? (width >> k) : 1u, h = (height >> k) ? (height >> k) : 1u,
+				d = (depth >> k) ? (depth >> k) : 1u;
+			const size_t slice_bytes = (size_t)w*h*16u;
+			// the slice buffer is a context buffer like the staging buffers: owned through the same lease
+			rc = lease.acquire();
+			if (rc == CFHIP_OK)
+				rc = reserve(ctx, &ctx->d_mip3d, &ctx->mip3d_cap, slice_bytes*pd);
+			if (rc != CFHIP_OK)
+				return rc;
+			for (uint32_t i = 0; i < pd; ++i) {
+				uint8_t* dst = static_cast<uint8_t*>(ctx->d_mip3d) + slice_bytes*i;
+				if (w == pw && h == ph)    // Image::resize returns a copy (Image.cpp:1330-1334): an exact Box identity
+					HIP_TRY(ctx, cfhip_launch_mip_resize(prev + prev_slice*i, prev_type, prev_pitch, pw, ph, dst, w, h,
+						CFHIP_FILTER_BOX, 0, stream));
+				else {
+					rc = mip_level_2d(ctx, lease, prev + prev_slice*i, prev_type, prev_pitch, pw, ph, dst, w, h, filter, srgb);
+					if (rc != CFHIP_OK)
+						return rc;
+				}
 			}
+			HIP_TRY(ctx, cfhip_launch_mip_depth(ctx->d_mip3d, pd, w*h, dst_levels[k - 1], d,
+				(filter & 0xFF) == CFHIP_FILTER_BOX ? 1 : 0, srgb, stream));
+			prev = static_cast<const uint8_t*>(dst_levels[k - 1]);
+			prev_type = CFHIP_PIXEL_RGBA32F;
+			prev_pitch = (size_t)w*16u;
+			prev_slice = slice_bytes;
+			pw = w; ph = h; pd = d;
 		}
-		HIP_TRY(ctx, cfhip_launch_mip_depth(ctx->d_mip3d, pd, w*h, dst_levels[k - 1], d,
-			(filter & 0xFF) == CFHIP_FILTER_BOX ? 1 : 0, srgb, stream));
-		prev = static_cast<const uint8_t*>(dst_levels[k - 1]);
-		prev_type = CFHIP_PIXEL_RGBA32F;
-		prev_pitch = (size_t)w*16u;
-		prev_slice = slice_bytes;
-		pw = w; ph = h; pd = d;
-	}
-	return lease.done(!stream_);
+		return lease.done(!stream_);
+	});
 }
 
 int cfhip_decoded_layout(int format, int type, int* layout, int* texel_bytes)
@@ -2592,79 +2587,79 @@ int cfhip_decoded_layout(int format, int type, int* layout, int* texel_bytes)
 int cfhip_decode(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes, uint32_t width,
 	uint32_t height, void* out, size_t out_capacity, uint64_t* error_blocks)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	DecodeGeom g;
-	int rc = decode_check(ctx, "decode", format, type, blocks, width, height, false, &g);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!out)
-		return fail(ctx, CFHIP_E_INVALID, "decode: out is NULL");
-	if (blocks_bytes < g.payload_bytes)
-		return fail(ctx, CFHIP_E_INVALID, "decode: blocks_bytes %zu < %zu for %ux%u", blocks_bytes, g.payload_bytes,
-			width, height);
-	const size_t out_bytes = (size_t)width*height*(size_t)g.texel_bytes;
-	if (out_capacity < out_bytes)
-		return fail(ctx, CFHIP_E_CAPACITY, "decode: out_capacity %zu < %zu", out_capacity, out_bytes);
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, ctx->stream);
-	const hipStream_t stream = lease.stream;
-	// d_src: the payload; d_out: the texels, then the error-block counter
-	const size_t cnt_off = (out_bytes + 15u) & ~(size_t)15u;
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, g.payload_bytes);
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, cnt_off + 8u);
-	if (rc != CFHIP_OK)
-		return rc;
-	unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(ctx->d_out) + cnt_off);
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, g.payload_bytes, hipMemcpyHostToDevice, stream));
-	HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 8, stream));
-	rc = decode_launch(ctx, format, type, g, ctx->d_src, ctx->d_out, (size_t)width*(size_t)g.texel_bytes, nullptr, 0,
-		width, height, d_cnt, false, stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	unsigned long long count = 0;
-	HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
-	HIP_TRY(ctx, hipMemcpyAsync(&count, d_cnt, 8, hipMemcpyDeviceToHost, stream));
-	rc = lease.done(true);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (error_blocks)
-		*error_blocks = (uint64_t)count;
-	return CFHIP_OK;
+	return guarded(ctx, "decode", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		DecodeGeom g;
+		int rc = decode_check(ctx, "decode", format, type, blocks, width, height, false, &g);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!out)
+			return fail(ctx, CFHIP_E_INVALID, "decode: out is NULL");
+		if (blocks_bytes < g.payload_bytes)
+			return fail(ctx, CFHIP_E_INVALID, "decode: blocks_bytes %zu < %zu for %ux%u", blocks_bytes, g.payload_bytes,
+				width, height);
+		const size_t out_bytes = (size_t)width*height*(size_t)g.texel_bytes;
+		if (out_capacity < out_bytes)
+			return fail(ctx, CFHIP_E_CAPACITY, "decode: out_capacity %zu < %zu", out_capacity, out_bytes);
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		const hipStream_t stream = lease.stream;
+		// d_src: the payload; d_out: the texels, then the error-block counter
+		const size_t cnt_off = (out_bytes + 15u) & ~(size_t)15u;
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, g.payload_bytes);
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, cnt_off + 8u);
+		if (rc != CFHIP_OK)
+			return rc;
+		unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(ctx->d_out) + cnt_off);
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, g.payload_bytes, hipMemcpyHostToDevice, stream));
+		HIP_TRY(ctx, hipMemsetAsync(d_cnt, 0, 8, stream));
+		rc = decode_launch(ctx, format, type, g, ctx->d_src, ctx->d_out, (size_t)width*(size_t)g.texel_bytes, nullptr, 0,
+			width, height, d_cnt, false, stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		unsigned long long count = 0;
+		HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+		HIP_TRY(ctx, hipMemcpyAsync(&count, d_cnt, 8, hipMemcpyDeviceToHost, stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (error_blocks)
+			*error_blocks = (uint64_t)count;
+		return CFHIP_OK;
+	});
 }
 
 int cfhip_decode_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width, uint32_t height,
 	void* out, size_t out_pitch_bytes, uint64_t* error_blocks_device, void* stream_)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	DecodeGeom g;
-	int rc = decode_check(ctx, "decode_device", format, type, blocks, width, height, false, &g);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!out)
-		return fail(ctx, CFHIP_E_INVALID, "decode_device: out is NULL");
-	if (out_pitch_bytes < (size_t)width*(size_t)g.texel_bytes)
-		return fail(ctx, CFHIP_E_INVALID, "decode_device: out pitch %zu < %zu", out_pitch_bytes,
-			(size_t)width*(size_t)g.texel_bytes);
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	// no staging buffer is touched: the lease only carries the synchronisation rule of the stream
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	unsigned long long* cnt = reinterpret_cast<unsigned long long*>(error_blocks_device);
-	if (cnt)
-		HIP_TRY(ctx, hipMemsetAsync(cnt, 0, 8, lease.stream));
-	rc = decode_launch(ctx, format, type, g, blocks, out, out_pitch_bytes, nullptr, 0, width, height, cnt, false,
-		lease.stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	return lease.done(!stream_);
+	return guarded(ctx, "decode_device", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		DecodeGeom g;
+		int rc = decode_check(ctx, "decode_device", format, type, blocks, width, height, false, &g);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!out)
+			return fail(ctx, CFHIP_E_INVALID, "decode_device: out is NULL");
+		if (out_pitch_bytes < (size_t)width*(size_t)g.texel_bytes)
+			return fail(ctx, CFHIP_E_INVALID, "decode_device: out pitch %zu < %zu", out_pitch_bytes,
+				(size_t)width*(size_t)g.texel_bytes);
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		// no staging buffer is touched: the lease only carries the synchronisation rule of the stream
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		unsigned long long* cnt = reinterpret_cast<unsigned long long*>(error_blocks_device);
+		if (cnt)
+			HIP_TRY(ctx, hipMemsetAsync(cnt, 0, 8, lease.stream));
+		rc = decode_launch(ctx, format, type, g, blocks, out, out_pitch_bytes, nullptr, 0, width, height, cnt, false,
+			lease.stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 // ---- batched decode (csrc/decode.hip: cfhip_decode_batch_kernel, cfhip_decode_batch_astc_kernel) -------------
@@ -2759,11 +2754,7 @@ static int decode_batch_launch(cfhip_ctx* ctx, StagingLease& lease, int format, 
 	unsigned long long* d_errors)
 {
 	const hipStream_t stream = lease.stream;
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	ctx->last_kernel = format >= CFHIP_FORMAT_ASTC_4x4 ? "cfhip_decode_batch_astc_kernel" : "cfhip_decode_batch_kernel";
+	begin_call(ctx, stream, format >= CFHIP_FORMAT_ASTC_4x4 ? "cfhip_decode_batch_astc_kernel" : "cfhip_decode_batch_kernel");
 	for (cfdec_batch_entry& e : p.entries) {
 		e.out_vec = ((uintptr_t)e.out % 16 == 0 && e.out_pitch % 16 == 0) ? 1 : 0;
 		e.blk_vec = ((uintptr_t)e.blocks % (uintptr_t)p.bb == 0) ? 1 : 0;
@@ -2778,301 +2769,288 @@ static int decode_batch_launch(cfhip_ctx* ctx, StagingLease& lease, int format, 
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, p.entries.data(), bytes, hipMemcpyHostToDevice, stream));
 	if (d_errors)
 		HIP_TRY(ctx, hipMemsetAsync(d_errors, 0, 8*p.entries.size(), stream));
-	hipEvent_t a, b;
-	rc = next_event_pair(ctx, &a, &b);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipEventRecord(a, stream));
-	const hipError_t e = cfhip_launch_decode_batch(format, type, p.kind, static_cast<const cfdec_batch_entry*>(ctx->d_batch),
-		(uint32_t)p.entries.size(), p.total_wg, p.bw, p.bh, d_errors, stream);
-	if (e != hipSuccess)
-		return fail(ctx, CFHIP_E_DEVICE, "decode_batch launch: %s", hipGetErrorString(e));
-	HIP_TRY(ctx, hipEventRecord(b, stream));
-	return CFHIP_OK;
+	return timed(ctx, stream, "decode_batch", [&] {
+		return cfhip_launch_decode_batch(format, type, p.kind, static_cast<const cfdec_batch_entry*>(ctx->d_batch),
+			(uint32_t)p.entries.size(), p.total_wg, p.bw, p.bh, d_errors, stream);
+	});
 }
 
 int cfhip_decode_batch(cfhip_ctx* ctx, int format, int type, int out_pixel, const cfhip_decode_surface* surfaces,
 	size_t n, uint64_t* error_blocks)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	DecodeBatchPlan p;
-	int rc = decode_batch_check(ctx, "decode_batch", format, type, out_pixel, surfaces, n, true, &p);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	if (!n)
+	return guarded(ctx, "decode_batch", [&]() -> int {
+		DecodeBatchPlan p;
+		int rc = decode_batch_check(ctx, "decode_batch", format, type, out_pixel, surfaces, n, true, &p);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		if (!n)
+			return CFHIP_OK;
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		const hipStream_t stream = lease.stream;
+		// d_src: the payloads, a run of surfaces whose blocks are consecutive in host memory as one copy.  d_out: the
+		// texels, a run of tightly pitched surfaces whose outputs are consecutive in host memory as one copy back (a
+		// pitched output has rows of its own on the device and comes back as a 2-D copy); then the error counters.
+		struct Run { size_t first, last, dev, bytes; };
+		std::vector<Run> up, down;
+		std::vector<size_t> src_off(n), out_off(n);
+		size_t so = 0, oo = 0;
+		for (size_t i = 0; i < n; ++i) {
+			const uint8_t* b = static_cast<const uint8_t*>(surfaces[i].blocks);
+			if (i && b == static_cast<const uint8_t*>(surfaces[i - 1].blocks) + p.payload[i - 1]) {
+				src_off[i] = src_off[i - 1] + p.payload[i - 1];
+				up.back().last = i;
+				up.back().bytes += p.payload[i];
+			} else {
+				so = (so + 255) & ~(size_t)255;
+				src_off[i] = so;
+				up.push_back({i, i, so, p.payload[i]});
+			}
+			so = src_off[i] + p.payload[i];
+			const bool tight = surfaces[i].out_pitch_bytes == (size_t)surfaces[i].width*(size_t)p.out_tb;
+			const bool prev_tight = i && surfaces[i - 1].out_pitch_bytes == (size_t)surfaces[i - 1].width*(size_t)p.out_tb;
+			if (tight && prev_tight && static_cast<uint8_t*>(surfaces[i].out) == static_cast<uint8_t*>(surfaces[i - 1].out) + p.span[i - 1]) {
+				out_off[i] = out_off[i - 1] + p.span[i - 1];
+				down.back().last = i;
+				down.back().bytes += p.span[i];
+			} else {
+				oo = (oo + 255) & ~(size_t)255;
+				out_off[i] = oo;
+				down.push_back({i, i, oo, p.span[i]});
+			}
+			// on the device every surface is tightly pitched
+			oo = out_off[i] + (size_t)surfaces[i].width*(size_t)p.out_tb*surfaces[i].height;
+		}
+		const size_t cnt_off = (oo + 255) & ~(size_t)255;
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, so);
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, cnt_off + 8*n);
+		if (rc != CFHIP_OK)
+			return rc;
+		uint8_t* d_src = static_cast<uint8_t*>(ctx->d_src);
+		uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out);
+		for (const Run& r : up)
+			HIP_TRY(ctx, hipMemcpyAsync(d_src + r.dev, surfaces[r.first].blocks, r.bytes, hipMemcpyHostToDevice, stream));
+		for (size_t i = 0; i < n; ++i) {
+			p.entries[i].blocks = d_src + src_off[i];
+			p.entries[i].out = d_out + out_off[i];
+			p.entries[i].out_pitch = (size_t)surfaces[i].width*(size_t)p.out_tb;
+		}
+		unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(d_out + cnt_off);
+		rc = decode_batch_launch(ctx, lease, format, type, p, d_cnt);
+		if (rc != CFHIP_OK)
+			return rc;
+		for (const Run& r : down) {
+			const cfhip_decode_surface& s = surfaces[r.first];
+			const size_t row = (size_t)s.width*(size_t)p.out_tb;
+			if (s.out_pitch_bytes == row)
+				HIP_TRY(ctx, hipMemcpyAsync(s.out, d_out + r.dev, r.bytes, hipMemcpyDeviceToHost, stream));
+			else
+				HIP_TRY(ctx, hipMemcpy2DAsync(s.out, s.out_pitch_bytes, d_out + r.dev, row, row, s.height,
+					hipMemcpyDeviceToHost, stream));
+		}
+		std::vector<unsigned long long> counts(n, 0);
+		HIP_TRY(ctx, hipMemcpyAsync(counts.data(), d_cnt, 8*n, hipMemcpyDeviceToHost, stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (error_blocks)
+			for (size_t i = 0; i < n; ++i)
+				error_blocks[i] = (uint64_t)counts[i];
 		return CFHIP_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, ctx->stream);
-	const hipStream_t stream = lease.stream;
-	// d_src: the payloads, a run of surfaces whose blocks are consecutive in host memory as one copy.  d_out: the
-	// texels, a run of tightly pitched surfaces whose outputs are consecutive in host memory as one copy back (a
-	// pitched output has rows of its own on the device and comes back as a 2-D copy); then the error counters.
-	struct Run { size_t first, last, dev, bytes; };
-	std::vector<Run> up, down;
-	std::vector<size_t> src_off(n), out_off(n);
-	size_t so = 0, oo = 0;
-	for (size_t i = 0; i < n; ++i) {
-		const uint8_t* b = static_cast<const uint8_t*>(surfaces[i].blocks);
-		if (i && b == static_cast<const uint8_t*>(surfaces[i - 1].blocks) + p.payload[i - 1]) {
-			src_off[i] = src_off[i - 1] + p.payload[i - 1];
-			up.back().last = i;
-			up.back().bytes += p.payload[i];
-		} else {
-			so = (so + 255) & ~(size_t)255;
-			src_off[i] = so;
-			up.push_back({i, i, so, p.payload[i]});
-		}
-		so = src_off[i] + p.payload[i];
-		const bool tight = surfaces[i].out_pitch_bytes == (size_t)surfaces[i].width*(size_t)p.out_tb;
-		const bool prev_tight = i && surfaces[i - 1].out_pitch_bytes == (size_t)surfaces[i - 1].width*(size_t)p.out_tb;
-		if (tight && prev_tight && static_cast<uint8_t*>(surfaces[i].out) == static_cast<uint8_t*>(surfaces[i - 1].out) + p.span[i - 1]) {
-			out_off[i] = out_off[i - 1] + p.span[i - 1];
-			down.back().last = i;
-			down.back().bytes += p.span[i];
-		} else {
-			oo = (oo + 255) & ~(size_t)255;
-			out_off[i] = oo;
-			down.push_back({i, i, oo, p.span[i]});
-		}
-		// on the device every surface is tightly pitched
-		oo = out_off[i] + (size_t)surfaces[i].width*(size_t)p.out_tb*surfaces[i].height;
-	}
-	const size_t cnt_off = (oo + 255) & ~(size_t)255;
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, so);
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, cnt_off + 8*n);
-	if (rc != CFHIP_OK)
-		return rc;
-	uint8_t* d_src = static_cast<uint8_t*>(ctx->d_src);
-	uint8_t* d_out = static_cast<uint8_t*>(ctx->d_out);
-	for (const Run& r : up)
-		HIP_TRY(ctx, hipMemcpyAsync(d_src + r.dev, surfaces[r.first].blocks, r.bytes, hipMemcpyHostToDevice, stream));
-	for (size_t i = 0; i < n; ++i) {
-		p.entries[i].blocks = d_src + src_off[i];
-		p.entries[i].out = d_out + out_off[i];
-		p.entries[i].out_pitch = (size_t)surfaces[i].width*(size_t)p.out_tb;
-	}
-	unsigned long long* d_cnt = reinterpret_cast<unsigned long long*>(d_out + cnt_off);
-	rc = decode_batch_launch(ctx, lease, format, type, p, d_cnt);
-	if (rc != CFHIP_OK)
-		return rc;
-	for (const Run& r : down) {
-		const cfhip_decode_surface& s = surfaces[r.first];
-		const size_t row = (size_t)s.width*(size_t)p.out_tb;
-		if (s.out_pitch_bytes == row)
-			HIP_TRY(ctx, hipMemcpyAsync(s.out, d_out + r.dev, r.bytes, hipMemcpyDeviceToHost, stream));
-		else
-			HIP_TRY(ctx, hipMemcpy2DAsync(s.out, s.out_pitch_bytes, d_out + r.dev, row, row, s.height,
-				hipMemcpyDeviceToHost, stream));
-	}
-	std::vector<unsigned long long> counts(n, 0);
-	HIP_TRY(ctx, hipMemcpyAsync(counts.data(), d_cnt, 8*n, hipMemcpyDeviceToHost, stream));
-	rc = lease.done(true);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (error_blocks)
-		for (size_t i = 0; i < n; ++i)
-			error_blocks[i] = (uint64_t)counts[i];
-	return CFHIP_OK;
+	});
 }
 
 int cfhip_decode_batch_device(cfhip_ctx* ctx, int format, int type, int out_pixel,
 	const cfhip_decode_surface* surfaces, size_t n, uint64_t* error_blocks_device, void* stream_)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	DecodeBatchPlan p;
-	int rc = decode_batch_check(ctx, "decode_batch_device", format, type, out_pixel, surfaces, n, false, &p);
-	if (rc != CFHIP_OK)
-		return rc;
-	if ((uintptr_t)error_blocks_device % 8)
-		return fail(ctx, CFHIP_E_INVALID, "decode_batch_device: error_blocks_device must be 8-byte aligned");
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	if (!n)
-		return CFHIP_OK;
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	rc = decode_batch_launch(ctx, lease, format, type, p, reinterpret_cast<unsigned long long*>(error_blocks_device));
-	if (rc != CFHIP_OK)
-		return rc;
-	return lease.done(!stream_);
+	return guarded(ctx, "decode_batch_device", [&]() -> int {
+		DecodeBatchPlan p;
+		int rc = decode_batch_check(ctx, "decode_batch_device", format, type, out_pixel, surfaces, n, false, &p);
+		if (rc != CFHIP_OK)
+			return rc;
+		if ((uintptr_t)error_blocks_device % 8)
+			return fail(ctx, CFHIP_E_INVALID, "decode_batch_device: error_blocks_device must be 8-byte aligned");
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		if (!n)
+			return CFHIP_OK;
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		rc = decode_batch_launch(ctx, lease, format, type, p, reinterpret_cast<unsigned long long*>(error_blocks_device));
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 int cfhip_decode_sse(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes, uint32_t width,
 	uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t sse[4])
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	DecodeGeom g;
-	int rc = decode_check(ctx, "decode_sse", format, type, blocks, width, height, true, &g);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!ref_rgba8 || !sse)
-		return fail(ctx, CFHIP_E_INVALID, "decode_sse: NULL reference or result");
-	if (blocks_bytes < g.payload_bytes)
-		return fail(ctx, CFHIP_E_INVALID, "decode_sse: blocks_bytes %zu < %zu for %ux%u", blocks_bytes,
-			g.payload_bytes, width, height);
-	const size_t row = (size_t)width*4u;
-	if (ref_pitch_bytes < row)
-		return fail(ctx, CFHIP_E_INVALID, "decode_sse: reference pitch %zu < %zu", ref_pitch_bytes, row);
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, ctx->stream);
-	const hipStream_t stream = lease.stream;
-	// d_src: the payload; d_out: the reference, tightly packed, then the four sums
-	const size_t sum_off = (row*height + 15u) & ~(size_t)15u;
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, g.payload_bytes);
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, sum_off + 32u);
-	if (rc != CFHIP_OK)
-		return rc;
-	unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(ctx->d_out) + sum_off);
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, g.payload_bytes, hipMemcpyHostToDevice, stream));
-	HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_out, row, ref_rgba8, ref_pitch_bytes, row, height, hipMemcpyHostToDevice,
-		stream));
-	HIP_TRY(ctx, hipMemsetAsync(d_sum, 0, 32, stream));
-	rc = decode_launch(ctx, format, type, g, ctx->d_src, nullptr, 0, ctx->d_out, row, width, height, d_sum, true,
-		stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	unsigned long long sums[4] = {0, 0, 0, 0};
-	HIP_TRY(ctx, hipMemcpyAsync(sums, d_sum, 32, hipMemcpyDeviceToHost, stream));
-	rc = lease.done(true);
-	if (rc != CFHIP_OK)
-		return rc;
-	for (int c = 0; c < 4; ++c)
-		sse[c] = (uint64_t)sums[c];
-	return CFHIP_OK;
+	return guarded(ctx, "decode_sse", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		DecodeGeom g;
+		int rc = decode_check(ctx, "decode_sse", format, type, blocks, width, height, true, &g);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!ref_rgba8 || !sse)
+			return fail(ctx, CFHIP_E_INVALID, "decode_sse: NULL reference or result");
+		if (blocks_bytes < g.payload_bytes)
+			return fail(ctx, CFHIP_E_INVALID, "decode_sse: blocks_bytes %zu < %zu for %ux%u", blocks_bytes,
+				g.payload_bytes, width, height);
+		const size_t row = (size_t)width*4u;
+		if (ref_pitch_bytes < row)
+			return fail(ctx, CFHIP_E_INVALID, "decode_sse: reference pitch %zu < %zu", ref_pitch_bytes, row);
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		const hipStream_t stream = lease.stream;
+		// d_src: the payload; d_out: the reference, tightly packed, then the four sums
+		const size_t sum_off = (row*height + 15u) & ~(size_t)15u;
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, g.payload_bytes);
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, sum_off + 32u);
+		if (rc != CFHIP_OK)
+			return rc;
+		unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(ctx->d_out) + sum_off);
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, g.payload_bytes, hipMemcpyHostToDevice, stream));
+		HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_out, row, ref_rgba8, ref_pitch_bytes, row, height, hipMemcpyHostToDevice,
+			stream));
+		HIP_TRY(ctx, hipMemsetAsync(d_sum, 0, 32, stream));
+		rc = decode_launch(ctx, format, type, g, ctx->d_src, nullptr, 0, ctx->d_out, row, width, height, d_sum, true,
+			stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		unsigned long long sums[4] = {0, 0, 0, 0};
+		HIP_TRY(ctx, hipMemcpyAsync(sums, d_sum, 32, hipMemcpyDeviceToHost, stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		for (int c = 0; c < 4; ++c)
+			sse[c] = (uint64_t)sums[c];
+		return CFHIP_OK;
+	});
 }
 
 int cfhip_decode_sse_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width,
 	uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t* sse_device, void* stream_)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	DecodeGeom g;
-	int rc = decode_check(ctx, "decode_sse_device", format, type, blocks, width, height, true, &g);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!ref_rgba8 || !sse_device)
-		return fail(ctx, CFHIP_E_INVALID, "decode_sse_device: NULL reference or result");
-	if (ref_pitch_bytes < (size_t)width*4u)
-		return fail(ctx, CFHIP_E_INVALID, "decode_sse_device: reference pitch %zu < %zu", ref_pitch_bytes,
-			(size_t)width*4u);
-	// the kernels add to the four sums with 64-bit atomics
-	if ((uintptr_t)sse_device % 8u != 0)
-		return fail(ctx, CFHIP_E_INVALID, "decode_sse_device: sse_device must be 8-byte aligned");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	unsigned long long* sum = reinterpret_cast<unsigned long long*>(sse_device);
-	HIP_TRY(ctx, hipMemsetAsync(sum, 0, 32, lease.stream));
-	rc = decode_launch(ctx, format, type, g, blocks, nullptr, 0, ref_rgba8, ref_pitch_bytes, width, height, sum, true,
-		lease.stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	return lease.done(!stream_);
+	return guarded(ctx, "decode_sse_device", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		DecodeGeom g;
+		int rc = decode_check(ctx, "decode_sse_device", format, type, blocks, width, height, true, &g);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!ref_rgba8 || !sse_device)
+			return fail(ctx, CFHIP_E_INVALID, "decode_sse_device: NULL reference or result");
+		if (ref_pitch_bytes < (size_t)width*4u)
+			return fail(ctx, CFHIP_E_INVALID, "decode_sse_device: reference pitch %zu < %zu", ref_pitch_bytes,
+				(size_t)width*4u);
+		// the kernels add to the four sums with 64-bit atomics
+		if ((uintptr_t)sse_device % 8u != 0)
+			return fail(ctx, CFHIP_E_INVALID, "decode_sse_device: sse_device must be 8-byte aligned");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		unsigned long long* sum = reinterpret_cast<unsigned long long*>(sse_device);
+		HIP_TRY(ctx, hipMemsetAsync(sum, 0, 32, lease.stream));
+		rc = decode_launch(ctx, format, type, g, blocks, nullptr, 0, ref_rgba8, ref_pitch_bytes, width, height, sum, true,
+			lease.stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 int cfhip_compare(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes, uint32_t width,
 	uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes, const uint8_t mask_rgba[4],
 	unsigned flags, cfhip_compare_result* result, float* block_errors, size_t block_errors_capacity)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	CompareGeom c;
-	int rc = compare_check(ctx, "compare", format, type, blocks, width, height, ref, ref_pixel_type, ref_pitch_bytes,
-		mask_rgba, flags, result, block_errors, block_errors_capacity, &c);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (blocks_bytes < c.g.payload_bytes)
-		return fail(ctx, CFHIP_E_INVALID, "compare: blocks_bytes %zu < %zu for %ux%u", blocks_bytes,
-			c.g.payload_bytes, width, height);
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, ctx->stream);
-	const hipStream_t stream = lease.stream;
-	// d_src: the payload; d_out: the reference, tightly packed, the scratch, the result, the block map
-	const size_t row = (size_t)width*(size_t)c.ref_bytes;
-	const size_t scr_off = align16(row*height), res_off = align16(scr_off + c.scratch_bytes);
-	const size_t map_off = align16(res_off + sizeof(cfhip_compare_result));
-	const size_t map_bytes = block_errors ? (size_t)c.g.bx*c.g.by*sizeof(float) : 0;
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, c.g.payload_bytes);
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, map_off + map_bytes);
-	if (rc != CFHIP_OK)
-		return rc;
-	uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
-	cfhip_compare_result* d_res = reinterpret_cast<cfhip_compare_result*>(d + res_off);
-	float* d_map = block_errors ? reinterpret_cast<float*>(d + map_off) : nullptr;
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, c.g.payload_bytes, hipMemcpyHostToDevice, stream));
-	HIP_TRY(ctx, hipMemcpy2DAsync(d, row, ref, ref_pitch_bytes, row, height, hipMemcpyHostToDevice, stream));
-	rc = compare_enqueue(ctx, format, type, c, ctx->d_src, d, ref_pixel_type, row, width, height, d + scr_off, d_res,
-		d_map, stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	cfhip_compare_result res;
-	HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, stream));
-	if (d_map)
-		HIP_TRY(ctx, hipMemcpyAsync(block_errors, d_map, map_bytes, hipMemcpyDeviceToHost, stream));
-	rc = lease.done(true);
-	if (rc != CFHIP_OK)
-		return rc;
-	*result = res;
-	return CFHIP_OK;
+	return guarded(ctx, "compare", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		CompareGeom c;
+		int rc = compare_check(ctx, "compare", format, type, blocks, width, height, ref, ref_pixel_type, ref_pitch_bytes,
+			mask_rgba, flags, result, block_errors, block_errors_capacity, &c);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (blocks_bytes < c.g.payload_bytes)
+			return fail(ctx, CFHIP_E_INVALID, "compare: blocks_bytes %zu < %zu for %ux%u", blocks_bytes,
+				c.g.payload_bytes, width, height);
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		const hipStream_t stream = lease.stream;
+		// d_src: the payload; d_out: the reference, tightly packed, the scratch, the result, the block map
+		const size_t row = (size_t)width*(size_t)c.ref_bytes;
+		const size_t scr_off = align16(row*height), res_off = align16(scr_off + c.scratch_bytes);
+		const size_t map_off = align16(res_off + sizeof(cfhip_compare_result));
+		const size_t map_bytes = block_errors ? (size_t)c.g.bx*c.g.by*sizeof(float) : 0;
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, c.g.payload_bytes);
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, map_off + map_bytes);
+		if (rc != CFHIP_OK)
+			return rc;
+		uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
+		cfhip_compare_result* d_res = reinterpret_cast<cfhip_compare_result*>(d + res_off);
+		float* d_map = block_errors ? reinterpret_cast<float*>(d + map_off) : nullptr;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, c.g.payload_bytes, hipMemcpyHostToDevice, stream));
+		HIP_TRY(ctx, hipMemcpy2DAsync(d, row, ref, ref_pitch_bytes, row, height, hipMemcpyHostToDevice, stream));
+		rc = compare_enqueue(ctx, format, type, c, ctx->d_src, d, ref_pixel_type, row, width, height, d + scr_off, d_res,
+			d_map, stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		cfhip_compare_result res;
+		HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, stream));
+		if (d_map)
+			HIP_TRY(ctx, hipMemcpyAsync(block_errors, d_map, map_bytes, hipMemcpyDeviceToHost, stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		*result = res;
+		return CFHIP_OK;
+	});
 }
 
 int cfhip_compare_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width, uint32_t height,
 	const void* ref, int ref_pixel_type, size_t ref_pitch_bytes, const uint8_t mask_rgba[4], unsigned flags,
 	cfhip_compare_result* result_device, float* block_errors_device, size_t block_errors_capacity, void* stream_)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	CompareGeom c;
-	int rc = compare_check(ctx, "compare_device", format, type, blocks, width, height, ref, ref_pixel_type,
-		ref_pitch_bytes, mask_rgba, flags, result_device, block_errors_device, block_errors_capacity, &c);
-	if (rc != CFHIP_OK)
-		return rc;
-	// the kernels read reference texels with one aligned load each and store doubles / floats to the outputs
-	const size_t rb = (size_t)c.ref_bytes;
-	if ((uintptr_t)ref % rb != 0 || ref_pitch_bytes % rb != 0)
-		return fail(ctx, CFHIP_E_INVALID, "compare_device: reference and its pitch must be %zu-byte aligned", rb);
-	if ((uintptr_t)result_device % 8u != 0 || (uintptr_t)block_errors_device % 4u != 0)
-		return fail(ctx, CFHIP_E_INVALID, "compare_device: misaligned result or block_errors");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	// the partials (and the SSIM pass's decoded surface) live in d_out: the lease orders them across streams
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, c.scratch_bytes);
-	if (rc != CFHIP_OK)
-		return rc;
-	rc = compare_enqueue(ctx, format, type, c, blocks, ref, ref_pixel_type, ref_pitch_bytes, width, height,
-		static_cast<uint8_t*>(ctx->d_out), result_device, block_errors_device, lease.stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	return lease.done(!stream_);
+	return guarded(ctx, "compare_device", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		CompareGeom c;
+		int rc = compare_check(ctx, "compare_device", format, type, blocks, width, height, ref, ref_pixel_type,
+			ref_pitch_bytes, mask_rgba, flags, result_device, block_errors_device, block_errors_capacity, &c);
+		if (rc != CFHIP_OK)
+			return rc;
+		// the kernels read reference texels with one aligned load each and store doubles / floats to the outputs
+		const size_t rb = (size_t)c.ref_bytes;
+		if ((uintptr_t)ref % rb != 0 || ref_pitch_bytes % rb != 0)
+			return fail(ctx, CFHIP_E_INVALID, "compare_device: reference and its pitch must be %zu-byte aligned", rb);
+		if ((uintptr_t)result_device % 8u != 0 || (uintptr_t)block_errors_device % 4u != 0)
+			return fail(ctx, CFHIP_E_INVALID, "compare_device: misaligned result or block_errors");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		// the partials (and the SSIM pass's decoded surface) live in d_out: the lease orders them across streams
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, c.scratch_bytes);
+		if (rc != CFHIP_OK)
+			return rc;
+		rc = compare_enqueue(ctx, format, type, c, blocks, ref, ref_pixel_type, ref_pitch_bytes, width, height,
+			static_cast<uint8_t*>(ctx->d_out), result_device, block_errors_device, lease.stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 // ---- batched compare (csrc/compare.hip: the cfhip_compare_batch_* kernels; csrc/compare_batch.h) -------------
@@ -3173,11 +3151,7 @@ static int compare_batch_launch(cfhip_ctx* ctx, StagingLease& lease, int format,
 	CompareBatchPlan& p, uint8_t* scratch, cfhip_compare_result* results)
 {
 	const hipStream_t stream = lease.stream;
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	ctx->last_kernel = format >= CFHIP_FORMAT_ASTC_4x4 ? "cfhip_compare_batch_astc_kernel" : "cfhip_compare_batch_block_kernel";
+	begin_call(ctx, stream, format >= CFHIP_FORMAT_ASTC_4x4 ? "cfhip_compare_batch_astc_kernel" : "cfhip_compare_batch_block_kernel");
 	const size_t n = p.entries.size();
 	// the compare table, then the decode table of the surfaces the SSIM pass covers (the decoders' workgroup shapes
 	// are Pass A's: 256 blocks, or a run of 64 ASTC blocks)
@@ -3217,30 +3191,23 @@ static int compare_batch_launch(cfhip_ctx* ctx, StagingLease& lease, int format,
 	double* pb = p.ssim ? reinterpret_cast<double*>(scratch + p.pb_off) : nullptr;
 	const int steps = p.ssim ? 4 : 2;
 	for (int step = 0; step < steps; ++step) {
-		hipEvent_t a, b;
-		rc = next_event_pair(ctx, &a, &b);
-		if (rc != CFHIP_OK)
-			return rc;
-		HIP_TRY(ctx, hipEventRecord(a, stream));
-		hipError_t e;
-		if (step == 0) {
-			e = cfhip_launch_compare_batch(format, type, d_cmp, (uint32_t)n, p.total_wg, p.bw, p.bh, ref_pixel_type,
-				p.cmask, pa, stream);
-		} else if (step == steps - 1) {
-			e = cfhip_launch_compare_batch_final(d_cmp, (uint32_t)n, pa, pb, p.cmask, p.hdr ? 1 : 0, results, stream);
-		} else if (step == 1) {
-			e = cfhip_launch_decode_batch(format, type, CFDEC_OUT_NATIVE, d_dec, (uint32_t)dec.size(), dec_wg, p.bw, p.bh,
-				nullptr, stream);
-		} else {
+		rc = timed(ctx, stream, "compare_batch", [&] {
+			if (step == 0)
+				return cfhip_launch_compare_batch(format, type, d_cmp, (uint32_t)n, p.total_wg, p.bw, p.bh, ref_pixel_type,
+					p.cmask, pa, stream);
+			if (step == steps - 1)
+				return cfhip_launch_compare_batch_final(d_cmp, (uint32_t)n, pa, pb, p.cmask, p.hdr ? 1 : 0, results, stream);
+			if (step == 1)
+				return cfhip_launch_decode_batch(format, type, CFDEC_OUT_NATIVE, d_dec, (uint32_t)dec.size(), dec_wg, p.bw, p.bh,
+					nullptr, stream);
 			const int l = p.layout;
 			const double range = (l == CFHIP_LAYOUT_R8_SNORM || l == CFHIP_LAYOUT_RG8_SNORM ||
 				l == CFHIP_LAYOUT_R16_SNORM || l == CFHIP_LAYOUT_RG16_SNORM) ? 2.0 : 1.0;
-			e = cfhip_launch_ssim_batch(d_cmp, (uint32_t)n, p.total_tiles, scratch, l, ref_pixel_type, p.cmask,
+			return cfhip_launch_ssim_batch(d_cmp, (uint32_t)n, p.total_tiles, scratch, l, ref_pixel_type, p.cmask,
 				ssim_taps(), range, pb, stream);
-		}
-		if (e != hipSuccess)
-			return fail(ctx, CFHIP_E_DEVICE, "compare_batch launch: %s", hipGetErrorString(e));
-		HIP_TRY(ctx, hipEventRecord(b, stream));
+		});
+		if (rc != CFHIP_OK)
+			return rc;
 	}
 	return CFHIP_OK;
 }
@@ -3248,134 +3215,128 @@ static int compare_batch_launch(cfhip_ctx* ctx, StagingLease& lease, int format,
 int cfhip_compare_batch(cfhip_ctx* ctx, int format, int type, const cfhip_compare_surface* surfaces, size_t n,
 	int ref_pixel_type, const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* results)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	CompareBatchPlan p;
-	int rc = compare_batch_check(ctx, "compare_batch", format, type, surfaces, n, ref_pixel_type, mask_rgba, flags,
-		results, true, &p);
-	if (rc != CFHIP_OK || !n)
-		return rc;
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, ctx->stream);
-	const hipStream_t stream = lease.stream;
-	// d_src: the payloads, a run of surfaces whose blocks are consecutive in host memory as one copy.  d_out: the
-	// references, tightly pitched and packed without gaps (a texel keeps its alignment: every surface is a whole
-	// number of texels), so that tight references that are consecutive in host memory are one copy too; then the
-	// scratch, the n results and the error maps.
-	struct Run { size_t first, dev, bytes; };
-	std::vector<Run> up, refs;
-	std::vector<size_t> src_off(n), ref_off(n), map_off(n);
-	size_t so = 0, ro = 0;
-	bool prev_tight = false;
-	const uint8_t* prev_end = nullptr;
-	for (size_t i = 0; i < n; ++i) {
-		const uint8_t* b = static_cast<const uint8_t*>(surfaces[i].blocks);
-		if (i && b == static_cast<const uint8_t*>(surfaces[i - 1].blocks) + p.payload[i - 1]) {
-			src_off[i] = src_off[i - 1] + p.payload[i - 1];
-			up.back().bytes += p.payload[i];
-		} else {
-			so = (so + 255) & ~(size_t)255;
-			src_off[i] = so;
-			up.push_back({i, so, p.payload[i]});
+	return guarded(ctx, "compare_batch", [&]() -> int {
+		CompareBatchPlan p;
+		int rc = compare_batch_check(ctx, "compare_batch", format, type, surfaces, n, ref_pixel_type, mask_rgba, flags,
+			results, true, &p);
+		if (rc != CFHIP_OK || !n)
+			return rc;
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		const hipStream_t stream = lease.stream;
+		// d_src: the payloads, a run of surfaces whose blocks are consecutive in host memory as one copy.  d_out: the
+		// references, tightly pitched and packed without gaps (a texel keeps its alignment: every surface is a whole
+		// number of texels), so that tight references that are consecutive in host memory are one copy too; then the
+		// scratch, the n results and the error maps.
+		struct Run { size_t first, dev, bytes; };
+		std::vector<Run> up, refs;
+		std::vector<size_t> src_off(n), ref_off(n), map_off(n);
+		size_t so = 0, ro = 0;
+		bool prev_tight = false;
+		const uint8_t* prev_end = nullptr;
+		for (size_t i = 0; i < n; ++i) {
+			const uint8_t* b = static_cast<const uint8_t*>(surfaces[i].blocks);
+			if (i && b == static_cast<const uint8_t*>(surfaces[i - 1].blocks) + p.payload[i - 1]) {
+				src_off[i] = src_off[i - 1] + p.payload[i - 1];
+				up.back().bytes += p.payload[i];
+			} else {
+				so = (so + 255) & ~(size_t)255;
+				src_off[i] = so;
+				up.push_back({i, so, p.payload[i]});
+			}
+			so = src_off[i] + p.payload[i];
+			const size_t row = (size_t)surfaces[i].width*(size_t)p.ref_bytes, bytes = row*surfaces[i].height;
+			const bool tight = surfaces[i].ref_pitch_bytes == row;
+			ref_off[i] = ro;
+			if (tight && prev_tight && static_cast<const uint8_t*>(surfaces[i].ref) == prev_end)
+				refs.back().bytes += bytes;
+			else
+				refs.push_back({i, ro, bytes});
+			prev_tight = tight;
+			prev_end = static_cast<const uint8_t*>(surfaces[i].ref) + bytes;
+			ro += bytes;
 		}
-		so = src_off[i] + p.payload[i];
-		const size_t row = (size_t)surfaces[i].width*(size_t)p.ref_bytes, bytes = row*surfaces[i].height;
-		const bool tight = surfaces[i].ref_pitch_bytes == row;
-		ref_off[i] = ro;
-		if (tight && prev_tight && static_cast<const uint8_t*>(surfaces[i].ref) == prev_end)
-			refs.back().bytes += bytes;
-		else
-			refs.push_back({i, ro, bytes});
-		prev_tight = tight;
-		prev_end = static_cast<const uint8_t*>(surfaces[i].ref) + bytes;
-		ro += bytes;
-	}
-	const size_t scr_off = align16(ro), res_off = align16(scr_off + p.scratch_bytes);
-	size_t mo = align16(res_off + n*sizeof(cfhip_compare_result));
-	for (size_t i = 0; i < n; ++i) {
-		map_off[i] = mo;
-		if (surfaces[i].block_errors)
-			mo = align16(mo + (size_t)p.entries[i].bx*p.entries[i].by*sizeof(float));
-	}
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, so);
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, mo);
-	if (rc != CFHIP_OK)
-		return rc;
-	uint8_t* d_src = static_cast<uint8_t*>(ctx->d_src);
-	uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
-	for (const Run& r : up)
-		HIP_TRY(ctx, hipMemcpyAsync(d_src + r.dev, surfaces[r.first].blocks, r.bytes, hipMemcpyHostToDevice, stream));
-	for (const Run& r : refs) {
-		const cfhip_compare_surface& s = surfaces[r.first];
-		const size_t row = (size_t)s.width*(size_t)p.ref_bytes;
-		if (s.ref_pitch_bytes == row)
-			HIP_TRY(ctx, hipMemcpyAsync(d + r.dev, s.ref, r.bytes, hipMemcpyHostToDevice, stream));
-		else
-			HIP_TRY(ctx, hipMemcpy2DAsync(d + r.dev, row, s.ref, s.ref_pitch_bytes, row, s.height, hipMemcpyHostToDevice,
-				stream));
-	}
-	for (size_t i = 0; i < n; ++i) {
-		cmp_batch_entry& e = p.entries[i];
-		e.blocks = d_src + src_off[i];
-		e.ref = d + ref_off[i];
-		e.ref_pitch = (unsigned long long)e.width*(unsigned)p.ref_bytes;
-		e.block_errors = surfaces[i].block_errors ? reinterpret_cast<float*>(d + map_off[i]) : nullptr;
-	}
-	cfhip_compare_result* d_res = reinterpret_cast<cfhip_compare_result*>(d + res_off);
-	rc = compare_batch_launch(ctx, lease, format, type, ref_pixel_type, p, d + scr_off, d_res);
-	if (rc != CFHIP_OK)
-		return rc;
-	std::vector<cfhip_compare_result> res(n);
-	HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_res, n*sizeof(cfhip_compare_result), hipMemcpyDeviceToHost, stream));
-	for (size_t i = 0; i < n; ++i)
-		if (surfaces[i].block_errors)
-			HIP_TRY(ctx, hipMemcpyAsync(surfaces[i].block_errors, d + map_off[i],
-				(size_t)p.entries[i].bx*p.entries[i].by*sizeof(float), hipMemcpyDeviceToHost, stream));
-	rc = lease.done(true);
-	if (rc != CFHIP_OK)
-		return rc;
-	for (size_t i = 0; i < n; ++i)
-		results[i] = res[i];
-	return CFHIP_OK;
+		const size_t scr_off = align16(ro), res_off = align16(scr_off + p.scratch_bytes);
+		size_t mo = align16(res_off + n*sizeof(cfhip_compare_result));
+		for (size_t i = 0; i < n; ++i) {
+			map_off[i] = mo;
+			if (surfaces[i].block_errors)
+				mo = align16(mo + (size_t)p.entries[i].bx*p.entries[i].by*sizeof(float));
+		}
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, so);
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, mo);
+		if (rc != CFHIP_OK)
+			return rc;
+		uint8_t* d_src = static_cast<uint8_t*>(ctx->d_src);
+		uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
+		for (const Run& r : up)
+			HIP_TRY(ctx, hipMemcpyAsync(d_src + r.dev, surfaces[r.first].blocks, r.bytes, hipMemcpyHostToDevice, stream));
+		for (const Run& r : refs) {
+			const cfhip_compare_surface& s = surfaces[r.first];
+			const size_t row = (size_t)s.width*(size_t)p.ref_bytes;
+			if (s.ref_pitch_bytes == row)
+				HIP_TRY(ctx, hipMemcpyAsync(d + r.dev, s.ref, r.bytes, hipMemcpyHostToDevice, stream));
+			else
+				HIP_TRY(ctx, hipMemcpy2DAsync(d + r.dev, row, s.ref, s.ref_pitch_bytes, row, s.height, hipMemcpyHostToDevice,
+					stream));
+		}
+		for (size_t i = 0; i < n; ++i) {
+			cmp_batch_entry& e = p.entries[i];
+			e.blocks = d_src + src_off[i];
+			e.ref = d + ref_off[i];
+			e.ref_pitch = (unsigned long long)e.width*(unsigned)p.ref_bytes;
+			e.block_errors = surfaces[i].block_errors ? reinterpret_cast<float*>(d + map_off[i]) : nullptr;
+		}
+		cfhip_compare_result* d_res = reinterpret_cast<cfhip_compare_result*>(d + res_off);
+		rc = compare_batch_launch(ctx, lease, format, type, ref_pixel_type, p, d + scr_off, d_res);
+		if (rc != CFHIP_OK)
+			return rc;
+		std::vector<cfhip_compare_result> res(n);
+		HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_res, n*sizeof(cfhip_compare_result), hipMemcpyDeviceToHost, stream));
+		for (size_t i = 0; i < n; ++i)
+			if (surfaces[i].block_errors)
+				HIP_TRY(ctx, hipMemcpyAsync(surfaces[i].block_errors, d + map_off[i],
+					(size_t)p.entries[i].bx*p.entries[i].by*sizeof(float), hipMemcpyDeviceToHost, stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		for (size_t i = 0; i < n; ++i)
+			results[i] = res[i];
+		return CFHIP_OK;
+	});
 }
 
 int cfhip_compare_batch_device(cfhip_ctx* ctx, int format, int type, const cfhip_compare_surface* surfaces, size_t n,
 	int ref_pixel_type, const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* results_device, void* stream_)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	CompareBatchPlan p;
-	int rc = compare_batch_check(ctx, "compare_batch_device", format, type, surfaces, n, ref_pixel_type, mask_rgba,
-		flags, results_device, false, &p);
-	if (rc != CFHIP_OK || !n)
-		return rc;
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	// the partials (and the SSIM pass's decoded surfaces) live in d_out, the tables in d_batch: the lease orders them
-	// across streams
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, p.scratch_bytes);
-	if (rc != CFHIP_OK)
-		return rc;
-	rc = compare_batch_launch(ctx, lease, format, type, ref_pixel_type, p, static_cast<uint8_t*>(ctx->d_out),
-		results_device);
-	if (rc != CFHIP_OK)
-		return rc;
-	return lease.done(!stream_);
+	return guarded(ctx, "compare_batch_device", [&]() -> int {
+		CompareBatchPlan p;
+		int rc = compare_batch_check(ctx, "compare_batch_device", format, type, surfaces, n, ref_pixel_type, mask_rgba,
+			flags, results_device, false, &p);
+		if (rc != CFHIP_OK || !n)
+			return rc;
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		// the partials (and the SSIM pass's decoded surfaces) live in d_out, the tables in d_batch: the lease orders them
+		// across streams
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, p.scratch_bytes);
+		if (rc != CFHIP_OK)
+			return rc;
+		rc = compare_batch_launch(ctx, lease, format, type, ref_pixel_type, p, static_cast<uint8_t*>(ctx->d_out),
+			results_device);
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 // ---- rate-distortion optimisation of BC1-5 / BC7 payloads (csrc/rdo.hip, csrc/rdo.h) ---------------------------
@@ -3486,18 +3447,22 @@ static int rdo_check(cfhip_ctx* ctx, const char* what, int format, int type, con
 	return CFHIP_OK;
 }
 
+static const char* rdo_kernel(const RdoPlan& p)
+{
+	return p.row_above ? "cfhip_rdo2d_kernel" : "cfhip_rdo_kernel";
+}
+
 // the surface table into staging, the counters cleared and the one launch of the call, timed as every encode launch
 // is; the entries hold device pointers by now
-// keep_events: a trial of cfhip_rdo_target, whose event pairs join those of the trials before it
+// keep_events: a trial of cfhip_rdo_target, which began the call itself: the trial's pair joins those before it
 static int rdo_launch(cfhip_ctx* ctx, StagingLease& lease, RdoPlan& p, cfhip_rdo_stats* stats, bool keep_events = false)
 {
 	static_assert(sizeof(cfhip_rdo_stats) == CFRDO_STATS*sizeof(unsigned long long), "the kernel's counters are the struct");
 	const hipStream_t stream = lease.stream;
-	if (!ctx->profiling && !keep_events)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	ctx->last_kernel = p.row_above ? "cfhip_rdo2d_kernel" : "cfhip_rdo_kernel";
+	if (!keep_events)
+		begin_call(ctx, stream, rdo_kernel(p));
+	else
+		ctx->last_kernel = rdo_kernel(p);
 	const size_t n = p.entries.size();
 	const size_t bb = (size_t)kCfrdoRows[p.row].block_bytes;
 	for (cfrdo_entry& e : p.entries)
@@ -3510,20 +3475,13 @@ static int rdo_launch(cfhip_ctx* ctx, StagingLease& lease, RdoPlan& p, cfhip_rdo
 	// pageable source: the runtime stages the copy before returning, so the table may die
 	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, p.entries.data(), n*sizeof(cfrdo_entry), hipMemcpyHostToDevice, stream));
 	HIP_TRY(ctx, hipMemsetAsync(stats, 0, n*sizeof(cfhip_rdo_stats), stream));
-	hipEvent_t a, b;
-	rc = next_event_pair(ctx, &a, &b);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipEventRecord(a, stream));
 	const cfrdo_entry* table = static_cast<const cfrdo_entry*>(ctx->d_batch);
 	unsigned long long* counters = reinterpret_cast<unsigned long long*>(stats);
-	const hipError_t e = p.row_above
-		? cfhip_launch_rdo2d(p.row, table, (uint32_t)n, p.total_tile, p.lam16, p.cap, p.cmask, counters, stream)
-		: cfhip_launch_rdo(p.row, table, (uint32_t)n, p.total_seg, p.lam16, p.cap, p.cmask, counters, stream);
-	if (e != hipSuccess)
-		return fail(ctx, CFHIP_E_DEVICE, "rdo launch: %s", hipGetErrorString(e));
-	HIP_TRY(ctx, hipEventRecord(b, stream));
-	return CFHIP_OK;
+	return timed(ctx, stream, "rdo", [&] {
+		return p.row_above
+			? cfhip_launch_rdo2d(p.row, table, (uint32_t)n, p.total_tile, p.lam16, p.cap, p.cmask, counters, stream)
+			: cfhip_launch_rdo(p.row, table, (uint32_t)n, p.total_seg, p.lam16, p.cap, p.cmask, counters, stream);
+	});
 }
 
 int cfhip_rdo_supported(int format, int type)
@@ -3535,68 +3493,65 @@ int cfhip_rdo_supported(int format, int type)
 static int rdo_host(cfhip_ctx* ctx, const char* what, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
 	const cfhip_rdo_params* params, const cfhip_rdo_ex_params* ex, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	RdoPlan p;
-	int rc = rdo_check(ctx, what, format, type, surfaces, n, params, ex, mask_rgba, stats, true, &p);
-	if (rc != CFHIP_OK || !n)
-		return rc;
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, ctx->stream);
-	const hipStream_t stream = lease.stream;
-	// d_src: the payloads (optimised in place there), each 256-byte aligned; d_out: the sources, tightly pitched and
-	// 16-byte aligned, then the counters
-	std::vector<size_t> blk_off(n), pix_off(n);
-	size_t so = 0, po = 0;
-	for (size_t i = 0; i < n; ++i) {
-		blk_off[i] = so;
-		so = (so + p.payload[i] + 255u) & ~(size_t)255u;
-		pix_off[i] = po;
-		po = align16(po + (size_t)surfaces[i].width*p.texel[i]*surfaces[i].height);
-	}
-	const size_t stats_off = po;
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, so);
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, stats_off + n*sizeof(cfhip_rdo_stats));
-	if (rc != CFHIP_OK)
-		return rc;
-	uint8_t* d_blk = static_cast<uint8_t*>(ctx->d_src);
-	uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
-	for (size_t i = 0; i < n; ++i) {
-		const cfhip_rdo_surface& s = surfaces[i];
-		const size_t rowb = (size_t)s.width*p.texel[i];
-		HIP_TRY(ctx, hipMemcpyAsync(d_blk + blk_off[i], s.blocks, p.payload[i], hipMemcpyHostToDevice, stream));
-		if (s.row_pitch_bytes == rowb)
-			HIP_TRY(ctx, hipMemcpyAsync(d + pix_off[i], s.pixels, rowb*s.height, hipMemcpyHostToDevice, stream));
-		else
-			HIP_TRY(ctx, hipMemcpy2DAsync(d + pix_off[i], rowb, s.pixels, s.row_pitch_bytes, rowb, s.height,
-				hipMemcpyHostToDevice, stream));
-		cfrdo_entry& e = p.entries[i];
-		e.blocks = e.out = d_blk + blk_off[i];
-		e.pixels = d + pix_off[i];
-		e.pitch = rowb;
-	}
-	cfhip_rdo_stats* d_stats = reinterpret_cast<cfhip_rdo_stats*>(d + stats_off);
-	rc = rdo_launch(ctx, lease, p, d_stats);
-	if (rc != CFHIP_OK)
-		return rc;
-	std::vector<cfhip_rdo_stats> res(n);
-	HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_stats, n*sizeof(cfhip_rdo_stats), hipMemcpyDeviceToHost, stream));
-	for (size_t i = 0; i < n; ++i)
-		HIP_TRY(ctx, hipMemcpyAsync(surfaces[i].out, d_blk + blk_off[i], p.payload[i], hipMemcpyDeviceToHost, stream));
-	rc = lease.done(true);
-	if (rc != CFHIP_OK)
-		return rc;
-	for (size_t i = 0; i < n; ++i)
-		stats[i] = res[i];
-	return CFHIP_OK;
+	return guarded(ctx, what, [&]() -> int {
+		RdoPlan p;
+		int rc = rdo_check(ctx, what, format, type, surfaces, n, params, ex, mask_rgba, stats, true, &p);
+		if (rc != CFHIP_OK || !n)
+			return rc;
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		const hipStream_t stream = lease.stream;
+		// d_src: the payloads (optimised in place there), each 256-byte aligned; d_out: the sources, tightly pitched and
+		// 16-byte aligned, then the counters
+		std::vector<size_t> blk_off(n), pix_off(n);
+		size_t so = 0, po = 0;
+		for (size_t i = 0; i < n; ++i) {
+			blk_off[i] = so;
+			so = (so + p.payload[i] + 255u) & ~(size_t)255u;
+			pix_off[i] = po;
+			po = align16(po + (size_t)surfaces[i].width*p.texel[i]*surfaces[i].height);
+		}
+		const size_t stats_off = po;
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, so);
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, stats_off + n*sizeof(cfhip_rdo_stats));
+		if (rc != CFHIP_OK)
+			return rc;
+		uint8_t* d_blk = static_cast<uint8_t*>(ctx->d_src);
+		uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
+		for (size_t i = 0; i < n; ++i) {
+			const cfhip_rdo_surface& s = surfaces[i];
+			const size_t rowb = (size_t)s.width*p.texel[i];
+			HIP_TRY(ctx, hipMemcpyAsync(d_blk + blk_off[i], s.blocks, p.payload[i], hipMemcpyHostToDevice, stream));
+			if (s.row_pitch_bytes == rowb)
+				HIP_TRY(ctx, hipMemcpyAsync(d + pix_off[i], s.pixels, rowb*s.height, hipMemcpyHostToDevice, stream));
+			else
+				HIP_TRY(ctx, hipMemcpy2DAsync(d + pix_off[i], rowb, s.pixels, s.row_pitch_bytes, rowb, s.height,
+					hipMemcpyHostToDevice, stream));
+			cfrdo_entry& e = p.entries[i];
+			e.blocks = e.out = d_blk + blk_off[i];
+			e.pixels = d + pix_off[i];
+			e.pitch = rowb;
+		}
+		cfhip_rdo_stats* d_stats = reinterpret_cast<cfhip_rdo_stats*>(d + stats_off);
+		rc = rdo_launch(ctx, lease, p, d_stats);
+		if (rc != CFHIP_OK)
+			return rc;
+		std::vector<cfhip_rdo_stats> res(n);
+		HIP_TRY(ctx, hipMemcpyAsync(res.data(), d_stats, n*sizeof(cfhip_rdo_stats), hipMemcpyDeviceToHost, stream));
+		for (size_t i = 0; i < n; ++i)
+			HIP_TRY(ctx, hipMemcpyAsync(surfaces[i].out, d_blk + blk_off[i], p.payload[i], hipMemcpyDeviceToHost, stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		for (size_t i = 0; i < n; ++i)
+			stats[i] = res[i];
+		return CFHIP_OK;
+	});
 }
 
 // cfhip_rdo_device and cfhip_rdo_ex_device
@@ -3604,24 +3559,21 @@ static int rdo_device(cfhip_ctx* ctx, const char* what, int format, int type, co
 	const cfhip_rdo_params* params, const cfhip_rdo_ex_params* ex, const uint8_t mask_rgba[4],
 	cfhip_rdo_stats* stats_device, void* stream_)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	RdoPlan p;
-	int rc = rdo_check(ctx, what, format, type, surfaces, n, params, ex, mask_rgba, stats_device, false, &p);
-	if (rc != CFHIP_OK || !n)
-		return rc;
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	// the surface table lives in d_batch: the lease orders it across streams
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	rc = rdo_launch(ctx, lease, p, stats_device);
-	if (rc != CFHIP_OK)
-		return rc;
-	return lease.done(!stream_);
+	return guarded(ctx, what, [&]() -> int {
+		RdoPlan p;
+		int rc = rdo_check(ctx, what, format, type, surfaces, n, params, ex, mask_rgba, stats_device, false, &p);
+		if (rc != CFHIP_OK || !n)
+			return rc;
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		// the surface table lives in d_batch: the lease orders it across streams
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		rc = rdo_launch(ctx, lease, p, stats_device);
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 int cfhip_rdo(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
@@ -3797,7 +3749,7 @@ int cfhip_lz_size_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_sp
 		if (!ctx)
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		StagingLease lease(ctx, call_stream(ctx, stream_));
 		begin_call(ctx, lease.stream, kLzSizeStages);
 		if (!p.total)
 			HIP_TRY(ctx, hipMemsetAsync(out_device, 0, sizeof(cfhip_lz_stats), lease.stream));
@@ -3963,7 +3915,7 @@ int cfhip_deflate_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n_sp
 		if (!ctx)
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		StagingLease lease(ctx, call_stream(ctx, stream_));
 		begin_call(ctx, lease.stream, kDeflateStages);
 		if (!p.total) {
 			// both sources are static: the copies may outlive the call
@@ -3989,41 +3941,37 @@ int cfhip_deflate_stage_ms(cfhip_ctx* ctx, float ms[CFDF_STAGES])
 
 int cfhip_deflate_code_lengths(cfhip_ctx* ctx, const uint32_t* counts, uint32_t n, uint32_t limit, uint8_t* lengths)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	if (!counts || !lengths)
-		return fail(ctx, CFHIP_E_INVALID, "deflate_code_lengths: counts or lengths is NULL");
-	if (n < 2u || n > 288u || limit < 1u || limit > (uint32_t)CFDF_LIMIT || (1u << limit) < n)
-		return fail(ctx, CFHIP_E_INVALID, "deflate_code_lengths: %u symbols at limit %u", n, limit);
-	unsigned long long sum = 0;
-	for (uint32_t i = 0; i < n; ++i)
-		sum += counts[i];
-	if (sum + 2u >= 1ull << 32)
-		return fail(ctx, CFHIP_E_INVALID, "deflate_code_lengths: the counts sum to 2^32 or more");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, ctx->stream);
-	begin_call(ctx, lease.stream, kDeflateStages.kernel);     // the encoder's kernel name, and no stage log
-	int rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, 4096u);
-	if (rc != CFHIP_OK)
-		return rc;
-	uint32_t* d_counts = static_cast<uint32_t*>(ctx->d_lz);
-	uint8_t* d_lengths = static_cast<uint8_t*>(ctx->d_lz) + 2048u;
-	HIP_TRY(ctx, hipMemcpyAsync(d_counts, counts, 4u*n, hipMemcpyHostToDevice, lease.stream));
-	hipEvent_t a, b;
-	rc = next_event_pair(ctx, &a, &b);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipEventRecord(a, lease.stream));
-	const hipError_t e = cfhip_launch_deflate_code_lengths(d_counts, n, limit, d_lengths, lease.stream);
-	if (e != hipSuccess)
-		return fail(ctx, CFHIP_E_DEVICE, "deflate_code_lengths launch: %s", hipGetErrorString(e));
-	HIP_TRY(ctx, hipEventRecord(b, lease.stream));
-	HIP_TRY(ctx, hipMemcpyAsync(lengths, d_lengths, n, hipMemcpyDeviceToHost, lease.stream));
-	return lease.done(true);
+	return guarded(ctx, "deflate_code_lengths", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		if (!counts || !lengths)
+			return fail(ctx, CFHIP_E_INVALID, "deflate_code_lengths: counts or lengths is NULL");
+		if (n < 2u || n > 288u || limit < 1u || limit > (uint32_t)CFDF_LIMIT || (1u << limit) < n)
+			return fail(ctx, CFHIP_E_INVALID, "deflate_code_lengths: %u symbols at limit %u", n, limit);
+		unsigned long long sum = 0;
+		for (uint32_t i = 0; i < n; ++i)
+			sum += counts[i];
+		if (sum + 2u >= 1ull << 32)
+			return fail(ctx, CFHIP_E_INVALID, "deflate_code_lengths: the counts sum to 2^32 or more");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		begin_call(ctx, lease.stream, kDeflateStages.kernel);     // the encoder's kernel name, and no stage log
+		int rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_lz, &ctx->lz_cap, 4096u);
+		if (rc != CFHIP_OK)
+			return rc;
+		uint32_t* d_counts = static_cast<uint32_t*>(ctx->d_lz);
+		uint8_t* d_lengths = static_cast<uint8_t*>(ctx->d_lz) + 2048u;
+		HIP_TRY(ctx, hipMemcpyAsync(d_counts, counts, 4u*n, hipMemcpyHostToDevice, lease.stream));
+		rc = timed(ctx, lease.stream, "deflate_code_lengths", [&] {
+			return cfhip_launch_deflate_code_lengths(d_counts, n, limit, d_lengths, lease.stream);
+		});
+		if (rc != CFHIP_OK)
+			return rc;
+		HIP_TRY(ctx, hipMemcpyAsync(lengths, d_lengths, n, hipMemcpyDeviceToHost, lease.stream));
+		return lease.done(true);
+	});
 }
 
 // ---- indexed zlib streams and their inflate (csrc/inflate.hip, csrc/inflate.h; the definition is tests/inflate_ref.py) --
@@ -4083,7 +4031,7 @@ int cfhip_deflate_indexed_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, siz
 		if (!ctx)
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		StagingLease lease(ctx, call_stream(ctx, stream_));
 		begin_call(ctx, lease.stream, kDeflateStages);
 		if (!p.total) {
 			static const cfhip_deflate_result empty = deflate_empty_result();
@@ -4236,7 +4184,7 @@ int cfhip_inflate_device(cfhip_ctx* ctx, const void* zstream_device, size_t zbyt
 		if (!ctx)
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		StagingLease lease(ctx, call_stream(ctx, stream_));
 		begin_call(ctx, lease.stream, kInflateStages);
 		rc = lease.acquire();
 		if (rc == CFHIP_OK)
@@ -4377,7 +4325,7 @@ int cfhip_lz4_encode_device(cfhip_ctx* ctx, const cfhip_lz_span* spans, size_t n
 		if (!ctx)
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		StagingLease lease(ctx, call_stream(ctx, stream_));
 		begin_call(ctx, lease.stream, kLz4EncodeStages);
 		if (!p.total) {
 			// both sources are static: the copies may outlive the call
@@ -4508,7 +4456,7 @@ int cfhip_lz4_decode_device(cfhip_ctx* ctx, const void* frame_device, size_t byt
 		if (!ctx)
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		StagingLease lease(ctx, call_stream(ctx, stream_));
 		begin_call(ctx, lease.stream, kLz4DecodeStages);
 		rc = lease.acquire();
 		if (rc == CFHIP_OK)
@@ -4693,7 +4641,7 @@ int cfhip_png_encode_device(cfhip_ctx* ctx, const void* pixels_device, int pixel
 		if (!ctx)
 			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
 		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
+		StagingLease lease(ctx, call_stream(ctx, stream_));
 		begin_call(ctx, lease.stream, kPngStages);
 		rc = lease.acquire();
 		if (rc == CFHIP_OK)
@@ -4716,162 +4664,156 @@ static int rdo_target(cfhip_ctx* ctx, const char* what, int format, int type, co
 	const cfhip_rdo_ex_params* ex, const uint8_t mask_rgba[4], cfhip_rdo_stats* stats, bool host, float target_ratio,
 	cfhip_rdo_target_result* result, void* stream_)
 {
-	std::unique_lock<std::mutex> guard;
-	if (ctx) {
-		guard = std::unique_lock<std::mutex>(ctx->lock);
-		ctx->error.clear();
-	}
-	RdoPlan p;
-	int rc = rdo_check(ctx, what, format, type, surfaces, n, nullptr, ex, mask_rgba, stats, host, &p);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!n) {
-		if (result)
-			memset(result, 0, sizeof(*result));
-		return CFHIP_OK;
-	}
-	if (!(target_ratio > 0.0f && target_ratio < 1.0f))
-		return fail(ctx, CFHIP_E_INVALID, "%s: target_ratio %g is outside (0, 1)", what, (double)target_ratio);
-	if (!result)
-		return fail(ctx, CFHIP_E_INVALID, "%s: result is NULL", what);
-	size_t total = 0;
-	for (size_t i = 0; i < n; ++i)
-		total += p.payload[i];
-	if (total >= ((size_t)1 << 31))
-		return fail(ctx, CFHIP_E_CAPACITY, "%s: the payloads hold 2^31 bytes or more", what);
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, !host && stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	const hipStream_t stream = lease.stream;
-	// every launch of the search is timed: the call's event pairs start here and every trial adds its own
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->stages.owner = nullptr;                  // the search's estimates (lz_run) belong to no stage log
-	rc = lease.acquire();
-	if (rc != CFHIP_OK)
-		return rc;
-	// the pristine payloads: scratch for the host form and for surfaces optimised in place, else the caller's
-	std::vector<size_t> off(n), pix_off(n);
-	size_t keep = 0, po = 0;
-	for (size_t i = 0; i < n; ++i) {
-		off[i] = keep;
-		keep = (keep + p.payload[i] + 255u) & ~(size_t)255u;
-		pix_off[i] = po;
-		po = align16(po + (size_t)surfaces[i].width*p.texel[i]*surfaces[i].height);
-	}
-	// (the device form needs the copy only for surfaces optimised in place)
-	bool keeps = host;
-	for (size_t i = 0; i < n && !keeps; ++i)
-		keeps = surfaces[i].out == surfaces[i].blocks;
-	if (keeps)
-		rc = reserve(ctx, &ctx->d_rdo_keep, &ctx->rdo_keep_cap, keep);
-	cfhip_rdo_stats* d_stats = stats;
-	if (host) {
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, keep);
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, po + n*sizeof(cfhip_rdo_stats));
-	}
-	if (rc != CFHIP_OK)
-		return rc;
-	uint8_t* d_keep = static_cast<uint8_t*>(ctx->d_rdo_keep);
-	LzPlan plain, work;
-	for (size_t i = 0; i < n; ++i) {
-		const cfhip_rdo_surface& s = surfaces[i];
-		cfrdo_entry& e = p.entries[i];
-		if (host) {
-			uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
-			const size_t rowb = (size_t)s.width*p.texel[i];
-			HIP_TRY(ctx, hipMemcpyAsync(d_keep + off[i], s.blocks, p.payload[i], hipMemcpyHostToDevice, stream));
-			if (s.row_pitch_bytes == rowb)
-				HIP_TRY(ctx, hipMemcpyAsync(d + pix_off[i], s.pixels, rowb*s.height, hipMemcpyHostToDevice, stream));
-			else
-				HIP_TRY(ctx, hipMemcpy2DAsync(d + pix_off[i], rowb, s.pixels, s.row_pitch_bytes, rowb, s.height,
-					hipMemcpyHostToDevice, stream));
-			e.blocks = d_keep + off[i];
-			e.out = static_cast<uint8_t*>(ctx->d_src) + off[i];
-			e.pixels = d + pix_off[i];
-			e.pitch = rowb;
-			d_stats = reinterpret_cast<cfhip_rdo_stats*>(d + po);
-		} else if (s.out == s.blocks) {
-			HIP_TRY(ctx, hipMemcpyAsync(d_keep + off[i], s.blocks, p.payload[i], hipMemcpyDeviceToDevice, stream));
-			e.blocks = d_keep + off[i];
+	return guarded(ctx, what, [&]() -> int {
+		RdoPlan p;
+		int rc = rdo_check(ctx, what, format, type, surfaces, n, nullptr, ex, mask_rgba, stats, host, &p);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!n) {
+			if (result)
+				memset(result, 0, sizeof(*result));
+			return CFHIP_OK;
 		}
-		plain.spans.push_back(cfhip_lz_span{e.blocks, p.payload[i]});
-		work.spans.push_back(cfhip_lz_span{e.out, p.payload[i]});
-	}
-	plain.total = work.total = total;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	// one estimate, read back: every trial decides on the host what the next one is
-	auto estimate = [&](const LzPlan& of, uint64_t* est) -> int {
-		unsigned long long* d_res = nullptr;
-		int r = lz_run(ctx, lease, of, hipMemcpyDeviceToDevice, nullptr, &d_res);
-		if (r != CFHIP_OK)
-			return r;
-		cfhip_lz_stats st;
-		HIP_TRY(ctx, hipMemcpyAsync(&st, d_res, sizeof(st), hipMemcpyDeviceToHost, stream));
-		HIP_TRY(ctx, hipStreamSynchronize(stream));
-		*est = st.est_bytes;
-		return CFHIP_OK;
-	};
-	uint32_t current = 0xFFFFFFFFu;               // the lambda16 whose pass lies in the outputs
-	auto pass = [&](uint32_t lam16) -> int {
-		p.lam16 = lam16;
-		current = lam16;
-		return rdo_launch(ctx, lease, p, d_stats, true);
-	};
-	cfhip_rdo_target_result res;
-	memset(&res, 0, sizeof(res));
-	rc = estimate(plain, &res.est_bytes_plain);
-	if (rc != CFHIP_OK)
-		return rc;
-	const uint64_t target = (uint64_t)std::floor((double)target_ratio*(double)res.est_bytes_plain);
-	uint32_t hi = p.lam16, lo = 0u;
-	uint64_t est = 0;
-	rc = pass(hi);
-	if (rc == CFHIP_OK)
-		rc = estimate(work, &est);
-	if (rc != CFHIP_OK)
-		return rc;
-	res.trials = 1u;
-	res.est_bytes_final = est;
-	res.reached = est <= target ? 1u : 0u;
-	while (res.reached && hi - lo > 1u) {
-		const uint32_t mid = lo + (hi - lo)/2u;
-		rc = pass(mid);
+		if (!(target_ratio > 0.0f && target_ratio < 1.0f))
+			return fail(ctx, CFHIP_E_INVALID, "%s: target_ratio %g is outside (0, 1)", what, (double)target_ratio);
+		if (!result)
+			return fail(ctx, CFHIP_E_INVALID, "%s: result is NULL", what);
+		size_t total = 0;
+		for (size_t i = 0; i < n; ++i)
+			total += p.payload[i];
+		if (total >= ((size_t)1 << 31))
+			return fail(ctx, CFHIP_E_CAPACITY, "%s: the payloads hold 2^31 bytes or more", what);
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, host ? nullptr : stream_));
+		const hipStream_t stream = lease.stream;
+		// every launch of the search is timed: the call's event pairs start here and every trial adds its own; the
+		// search's estimates (lz_run) belong to no stage log; the trials name the kernel
+		begin_call(ctx, stream, nullptr);
+		rc = lease.acquire();
+		if (rc != CFHIP_OK)
+			return rc;
+		// the pristine payloads: scratch for the host form and for surfaces optimised in place, else the caller's
+		std::vector<size_t> off(n), pix_off(n);
+		size_t keep = 0, po = 0;
+		for (size_t i = 0; i < n; ++i) {
+			off[i] = keep;
+			keep = (keep + p.payload[i] + 255u) & ~(size_t)255u;
+			pix_off[i] = po;
+			po = align16(po + (size_t)surfaces[i].width*p.texel[i]*surfaces[i].height);
+		}
+		// (the device form needs the copy only for surfaces optimised in place)
+		bool keeps = host;
+		for (size_t i = 0; i < n && !keeps; ++i)
+			keeps = surfaces[i].out == surfaces[i].blocks;
+		if (keeps)
+			rc = reserve(ctx, &ctx->d_rdo_keep, &ctx->rdo_keep_cap, keep);
+		cfhip_rdo_stats* d_stats = stats;
+		if (host) {
+			if (rc == CFHIP_OK)
+				rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, keep);
+			if (rc == CFHIP_OK)
+				rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, po + n*sizeof(cfhip_rdo_stats));
+		}
+		if (rc != CFHIP_OK)
+			return rc;
+		uint8_t* d_keep = static_cast<uint8_t*>(ctx->d_rdo_keep);
+		LzPlan plain, work;
+		for (size_t i = 0; i < n; ++i) {
+			const cfhip_rdo_surface& s = surfaces[i];
+			cfrdo_entry& e = p.entries[i];
+			if (host) {
+				uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
+				const size_t rowb = (size_t)s.width*p.texel[i];
+				HIP_TRY(ctx, hipMemcpyAsync(d_keep + off[i], s.blocks, p.payload[i], hipMemcpyHostToDevice, stream));
+				if (s.row_pitch_bytes == rowb)
+					HIP_TRY(ctx, hipMemcpyAsync(d + pix_off[i], s.pixels, rowb*s.height, hipMemcpyHostToDevice, stream));
+				else
+					HIP_TRY(ctx, hipMemcpy2DAsync(d + pix_off[i], rowb, s.pixels, s.row_pitch_bytes, rowb, s.height,
+						hipMemcpyHostToDevice, stream));
+				e.blocks = d_keep + off[i];
+				e.out = static_cast<uint8_t*>(ctx->d_src) + off[i];
+				e.pixels = d + pix_off[i];
+				e.pitch = rowb;
+				d_stats = reinterpret_cast<cfhip_rdo_stats*>(d + po);
+			} else if (s.out == s.blocks) {
+				HIP_TRY(ctx, hipMemcpyAsync(d_keep + off[i], s.blocks, p.payload[i], hipMemcpyDeviceToDevice, stream));
+				e.blocks = d_keep + off[i];
+			}
+			plain.spans.push_back(cfhip_lz_span{e.blocks, p.payload[i]});
+			work.spans.push_back(cfhip_lz_span{e.out, p.payload[i]});
+		}
+		plain.total = work.total = total;
+		// one estimate, read back: every trial decides on the host what the next one is
+		auto estimate = [&](const LzPlan& of, uint64_t* est) -> int {
+			unsigned long long* d_res = nullptr;
+			int r = lz_run(ctx, lease, of, hipMemcpyDeviceToDevice, nullptr, &d_res);
+			if (r != CFHIP_OK)
+				return r;
+			cfhip_lz_stats st;
+			HIP_TRY(ctx, hipMemcpyAsync(&st, d_res, sizeof(st), hipMemcpyDeviceToHost, stream));
+			HIP_TRY(ctx, hipStreamSynchronize(stream));
+			*est = st.est_bytes;
+			return CFHIP_OK;
+		};
+		uint32_t current = 0xFFFFFFFFu;               // the lambda16 whose pass lies in the outputs
+		auto pass = [&](uint32_t lam16) -> int {
+			p.lam16 = lam16;
+			current = lam16;
+			return rdo_launch(ctx, lease, p, d_stats, true);
+		};
+		cfhip_rdo_target_result res;
+		memset(&res, 0, sizeof(res));
+		rc = estimate(plain, &res.est_bytes_plain);
+		if (rc != CFHIP_OK)
+			return rc;
+		const uint64_t target = (uint64_t)std::floor((double)target_ratio*(double)res.est_bytes_plain);
+		uint32_t hi = p.lam16, lo = 0u;
+		uint64_t est = 0;
+		rc = pass(hi);
 		if (rc == CFHIP_OK)
 			rc = estimate(work, &est);
 		if (rc != CFHIP_OK)
 			return rc;
-		++res.trials;
-		if (est <= target) {
-			hi = mid;
-			res.est_bytes_final = est;
-		} else
-			lo = mid;
-	}
-	if (current != hi) {
-		rc = pass(hi);
+		res.trials = 1u;
+		res.est_bytes_final = est;
+		res.reached = est <= target ? 1u : 0u;
+		while (res.reached && hi - lo > 1u) {
+			const uint32_t mid = lo + (hi - lo)/2u;
+			rc = pass(mid);
+			if (rc == CFHIP_OK)
+				rc = estimate(work, &est);
+			if (rc != CFHIP_OK)
+				return rc;
+			++res.trials;
+			if (est <= target) {
+				hi = mid;
+				res.est_bytes_final = est;
+			} else
+				lo = mid;
+		}
+		if (current != hi) {
+			rc = pass(hi);
+			if (rc != CFHIP_OK)
+				return rc;
+		}
+		res.lambda16 = hi;
+		ctx->last_kernel = rdo_kernel(p);
+		std::vector<cfhip_rdo_stats> host_stats(host ? n : 0);
+		if (host) {
+			HIP_TRY(ctx, hipMemcpyAsync(host_stats.data(), d_stats, n*sizeof(cfhip_rdo_stats), hipMemcpyDeviceToHost, stream));
+			for (size_t i = 0; i < n; ++i)
+				HIP_TRY(ctx, hipMemcpyAsync(surfaces[i].out, p.entries[i].out, p.payload[i], hipMemcpyDeviceToHost, stream));
+		}
+		rc = lease.done(true);
 		if (rc != CFHIP_OK)
 			return rc;
-	}
-	res.lambda16 = hi;
-	ctx->last_kernel = p.row_above ? "cfhip_rdo2d_kernel" : "cfhip_rdo_kernel";
-	std::vector<cfhip_rdo_stats> host_stats(host ? n : 0);
-	if (host) {
-		HIP_TRY(ctx, hipMemcpyAsync(host_stats.data(), d_stats, n*sizeof(cfhip_rdo_stats), hipMemcpyDeviceToHost, stream));
-		for (size_t i = 0; i < n; ++i)
-			HIP_TRY(ctx, hipMemcpyAsync(surfaces[i].out, p.entries[i].out, p.payload[i], hipMemcpyDeviceToHost, stream));
-	}
-	rc = lease.done(true);
-	if (rc != CFHIP_OK)
-		return rc;
-	for (size_t i = 0; i < host_stats.size(); ++i)
-		stats[i] = host_stats[i];
-	*result = res;
-	return CFHIP_OK;
+		for (size_t i = 0; i < host_stats.size(); ++i)
+			stats[i] = host_stats[i];
+		*result = res;
+		return CFHIP_OK;
+	});
 }
 
 int cfhip_rdo_target(cfhip_ctx* ctx, int format, int type, const cfhip_rdo_surface* surfaces, size_t n,
@@ -4903,21 +4845,6 @@ static int pvrtc_check(int format, int type, uint32_t width, uint32_t height, si
 		return CFHIP_E_INVALID;
 	const size_t bx = width/4u > 2u ? width/4u : 2u, by = height/4u > 2u ? height/4u : 2u;
 	if (bytes) *bytes = bx*by*8u;
-	return CFHIP_OK;
-}
-
-// one pass of the encoder or one decode, timed like every other launch (cfhip_last_kernel_ms / profiling)
-static int pvrtc_timed(cfhip_ctx* ctx, hipStream_t stream, const std::function<hipError_t()>& launch)
-{
-	hipEvent_t a, b;
-	int rc = next_event_pair(ctx, &a, &b);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipEventRecord(a, stream));
-	const hipError_t e = launch();
-	if (e != hipSuccess)
-		return fail(ctx, CFHIP_E_DEVICE, "pvrtc launch: %s", hipGetErrorString(e));
-	HIP_TRY(ctx, hipEventRecord(b, stream));
 	return CFHIP_OK;
 }
 
@@ -5025,14 +4952,11 @@ static int pvrtc_encode_body(cfhip_ctx* ctx, StagingLease& lease, const cfhip_su
 	uint8_t* mods = base + mod_off;
 	// pageable source: the runtime stages the copy before returning, so `tab` may die
 	HIP_TRY(ctx, hipMemcpyAsync(base, tab.data(), n*sizeof(cf_pvrtc_surf), hipMemcpyHostToDevice, stream));
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	ctx->last_kernel = "cfhip_pvrtc_refine_kernel";
+	begin_call(ctx, stream, "cfhip_pvrtc_refine_kernel");
 	const uint32_t nb = (uint32_t)blocks, np = (uint32_t)phase, ns = (uint32_t)n;
+	// every pass of the encoder is a timed span of its own
 	auto pass = [&](int k, uint32_t items, uint32_t ox, uint32_t oy, uint32_t flags) {
-		return pvrtc_timed(ctx, stream, [&]() {
+		return timed(ctx, stream, "pvrtc", [&] {
 			return cfhip_pvrtc_launch(k, d_tab, ns, items, tex, words, mods, wmask, rgb ? 1 : 0, ox, oy, flags, stream);
 		});
 	};
@@ -5056,21 +4980,15 @@ static int pvrtc_encode_body(cfhip_ctx* ctx, StagingLease& lease, const cfhip_su
 static int pvrtc_encode_impl(cfhip_ctx* ctx, const cfhip_surface* surfaces, size_t n, const cfhip_params* p,
 	bool device_mem, hipStream_t user_stream)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	StagingLease lease(ctx, user_stream ? user_stream : ctx->stream);
-	try {
+	return guarded(ctx, "pvrtc_encode", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		StagingLease lease(ctx, user_stream ? user_stream : ctx->stream);
 		const int rc = pvrtc_encode_body(ctx, lease, surfaces, n, p, device_mem);
 		if (rc != CFHIP_OK)
 			return rc;
 		return lease.done(!user_stream);
-	} catch (const std::exception& e) {
-		return fail(ctx, CFHIP_E_DEVICE, "pvrtc_encode: %s", e.what());
-	} catch (...) {
-		return fail(ctx, CFHIP_E_DEVICE, "pvrtc_encode: unknown exception");
-	}
+	});
 }
 
 // the checks every PVRTC decode entry point makes before anything is enqueued
@@ -5093,13 +5011,9 @@ static int pvrtc_decode_launch(cfhip_ctx* ctx, int format, const void* blocks, u
 	void* out, size_t out_pitch, const void* ref, size_t ref_pitch, unsigned long long* sums, bool sse,
 	hipStream_t stream)
 {
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	ctx->last_kernel = sse ? "cfhip_pvrtc_decode_sse_kernel" : "cfhip_pvrtc_decode_kernel";
+	begin_call(ctx, stream, sse ? "cfhip_pvrtc_decode_sse_kernel" : "cfhip_pvrtc_decode_kernel");
 	const int rgb = format == CFHIP_FORMAT_PVRTC1_RGB_4BPP ? 1 : 0;
-	return pvrtc_timed(ctx, stream, [&]() {
+	return timed(ctx, stream, "pvrtc", [&] {
 		return cfhip_pvrtc_launch_decode(blocks, width, height, rgb, out, out_pitch, ref, ref_pitch, sums, sse ? 1 : 0,
 			stream);
 	});
@@ -5126,138 +5040,138 @@ int cfhip_pvrtc_encode_device(cfhip_ctx* ctx, const cfhip_surface* surfaces, siz
 int cfhip_pvrtc_decode(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes, uint32_t width,
 	uint32_t height, void* out, size_t out_capacity)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	size_t payload = 0;
-	int rc = pvrtc_decode_check(ctx, "pvrtc_decode", format, type, blocks, width, height, &payload);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!out)
-		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode: out is NULL");
-	if (blocks_bytes < payload)
-		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode: blocks_bytes %zu < %zu", blocks_bytes, payload);
-	const size_t out_bytes = (size_t)width*height*4u;
-	if (out_capacity < out_bytes)
-		return fail(ctx, CFHIP_E_CAPACITY, "pvrtc_decode: out_capacity %zu < %zu", out_capacity, out_bytes);
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, ctx->stream);
-	const hipStream_t stream = lease.stream;
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, payload);
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, out_bytes);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, payload, hipMemcpyHostToDevice, stream));
-	rc = pvrtc_decode_launch(ctx, format, ctx->d_src, width, height, ctx->d_out, (size_t)width*4u, nullptr, 0, nullptr,
-		false, stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
-	return lease.done(true);
+	return guarded(ctx, "pvrtc_decode", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		size_t payload = 0;
+		int rc = pvrtc_decode_check(ctx, "pvrtc_decode", format, type, blocks, width, height, &payload);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!out)
+			return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode: out is NULL");
+		if (blocks_bytes < payload)
+			return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode: blocks_bytes %zu < %zu", blocks_bytes, payload);
+		const size_t out_bytes = (size_t)width*height*4u;
+		if (out_capacity < out_bytes)
+			return fail(ctx, CFHIP_E_CAPACITY, "pvrtc_decode: out_capacity %zu < %zu", out_capacity, out_bytes);
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		const hipStream_t stream = lease.stream;
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, payload);
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, out_bytes);
+		if (rc != CFHIP_OK)
+			return rc;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, payload, hipMemcpyHostToDevice, stream));
+		rc = pvrtc_decode_launch(ctx, format, ctx->d_src, width, height, ctx->d_out, (size_t)width*4u, nullptr, 0, nullptr,
+			false, stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+		return lease.done(true);
+	});
 }
 
 int cfhip_pvrtc_decode_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width,
 	uint32_t height, void* out, size_t out_pitch_bytes, void* stream_)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	int rc = pvrtc_decode_check(ctx, "pvrtc_decode_device", format, type, blocks, width, height, nullptr);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!out || out_pitch_bytes < (size_t)width*4u || ((uintptr_t)out & 3u) || (out_pitch_bytes & 3u) ||
-		((uintptr_t)blocks & 3u))
-		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_device: out, pitch and blocks must be 4-byte aligned, "
-			"pitch >= %zu", (size_t)width*4u);
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	// no staging buffer is touched: the lease only carries the synchronisation rule of the stream
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	rc = pvrtc_decode_launch(ctx, format, blocks, width, height, out, out_pitch_bytes, nullptr, 0, nullptr, false,
-		lease.stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	return lease.done(!stream_);
+	return guarded(ctx, "pvrtc_decode_device", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		int rc = pvrtc_decode_check(ctx, "pvrtc_decode_device", format, type, blocks, width, height, nullptr);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!out || out_pitch_bytes < (size_t)width*4u || ((uintptr_t)out & 3u) || (out_pitch_bytes & 3u) ||
+			((uintptr_t)blocks & 3u))
+			return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_device: out, pitch and blocks must be 4-byte aligned, "
+				"pitch >= %zu", (size_t)width*4u);
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		// no staging buffer is touched: the lease only carries the synchronisation rule of the stream
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		rc = pvrtc_decode_launch(ctx, format, blocks, width, height, out, out_pitch_bytes, nullptr, 0, nullptr, false,
+			lease.stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 int cfhip_pvrtc_decode_sse(cfhip_ctx* ctx, int format, int type, const void* blocks, size_t blocks_bytes,
 	uint32_t width, uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t sse[4])
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	size_t payload = 0;
-	int rc = pvrtc_decode_check(ctx, "pvrtc_decode_sse", format, type, blocks, width, height, &payload);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!ref_rgba8 || !sse)
-		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse: NULL reference or result");
-	if (blocks_bytes < payload)
-		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse: blocks_bytes %zu < %zu", blocks_bytes, payload);
-	const size_t row = (size_t)width*4u;
-	if (ref_pitch_bytes < row)
-		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse: reference pitch %zu < %zu", ref_pitch_bytes, row);
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, ctx->stream);
-	const hipStream_t stream = lease.stream;
-	// d_src: the payload; d_out: the reference, tightly packed, then the four sums
-	const size_t sum_off = (row*height + 15u) & ~(size_t)15u;
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, payload);
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, sum_off + 32u);
-	if (rc != CFHIP_OK)
-		return rc;
-	unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(ctx->d_out) + sum_off);
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, payload, hipMemcpyHostToDevice, stream));
-	HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_out, row, ref_rgba8, ref_pitch_bytes, row, height, hipMemcpyHostToDevice,
-		stream));
-	HIP_TRY(ctx, hipMemsetAsync(d_sum, 0, 32, stream));
-	rc = pvrtc_decode_launch(ctx, format, ctx->d_src, width, height, nullptr, 0, ctx->d_out, row, d_sum, true, stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	unsigned long long sums[4] = {0, 0, 0, 0};
-	HIP_TRY(ctx, hipMemcpyAsync(sums, d_sum, 32, hipMemcpyDeviceToHost, stream));
-	rc = lease.done(true);
-	if (rc != CFHIP_OK)
-		return rc;
-	for (int c = 0; c < 4; ++c)
-		sse[c] = (uint64_t)sums[c];
-	return CFHIP_OK;
+	return guarded(ctx, "pvrtc_decode_sse", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		size_t payload = 0;
+		int rc = pvrtc_decode_check(ctx, "pvrtc_decode_sse", format, type, blocks, width, height, &payload);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!ref_rgba8 || !sse)
+			return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse: NULL reference or result");
+		if (blocks_bytes < payload)
+			return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse: blocks_bytes %zu < %zu", blocks_bytes, payload);
+		const size_t row = (size_t)width*4u;
+		if (ref_pitch_bytes < row)
+			return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse: reference pitch %zu < %zu", ref_pitch_bytes, row);
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		const hipStream_t stream = lease.stream;
+		// d_src: the payload; d_out: the reference, tightly packed, then the four sums
+		const size_t sum_off = (row*height + 15u) & ~(size_t)15u;
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, payload);
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, sum_off + 32u);
+		if (rc != CFHIP_OK)
+			return rc;
+		unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(static_cast<uint8_t*>(ctx->d_out) + sum_off);
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, blocks, payload, hipMemcpyHostToDevice, stream));
+		HIP_TRY(ctx, hipMemcpy2DAsync(ctx->d_out, row, ref_rgba8, ref_pitch_bytes, row, height, hipMemcpyHostToDevice,
+			stream));
+		HIP_TRY(ctx, hipMemsetAsync(d_sum, 0, 32, stream));
+		rc = pvrtc_decode_launch(ctx, format, ctx->d_src, width, height, nullptr, 0, ctx->d_out, row, d_sum, true, stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		unsigned long long sums[4] = {0, 0, 0, 0};
+		HIP_TRY(ctx, hipMemcpyAsync(sums, d_sum, 32, hipMemcpyDeviceToHost, stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		for (int c = 0; c < 4; ++c)
+			sse[c] = (uint64_t)sums[c];
+		return CFHIP_OK;
+	});
 }
 
 int cfhip_pvrtc_decode_sse_device(cfhip_ctx* ctx, int format, int type, const void* blocks, uint32_t width,
 	uint32_t height, const void* ref_rgba8, size_t ref_pitch_bytes, uint64_t* sse_device, void* stream_)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	int rc = pvrtc_decode_check(ctx, "pvrtc_decode_sse_device", format, type, blocks, width, height, nullptr);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!ref_rgba8 || !sse_device || ref_pitch_bytes < (size_t)width*4u || ((uintptr_t)ref_rgba8 & 3u) ||
-		(ref_pitch_bytes & 3u) || ((uintptr_t)blocks & 3u))
-		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse_device: reference, pitch and blocks must be non-NULL and "
-			"4-byte aligned, pitch >= %zu", (size_t)width*4u);
-	// the kernel adds to the four sums with 64-bit atomics
-	if ((uintptr_t)sse_device % 8u != 0)
-		return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse_device: sse_device must be 8-byte aligned");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	unsigned long long* sum = reinterpret_cast<unsigned long long*>(sse_device);
-	HIP_TRY(ctx, hipMemsetAsync(sum, 0, 32, lease.stream));
-	rc = pvrtc_decode_launch(ctx, format, blocks, width, height, nullptr, 0, ref_rgba8, ref_pitch_bytes, sum, true,
-		lease.stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	return lease.done(!stream_);
+	return guarded(ctx, "pvrtc_decode_sse_device", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		int rc = pvrtc_decode_check(ctx, "pvrtc_decode_sse_device", format, type, blocks, width, height, nullptr);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!ref_rgba8 || !sse_device || ref_pitch_bytes < (size_t)width*4u || ((uintptr_t)ref_rgba8 & 3u) ||
+			(ref_pitch_bytes & 3u) || ((uintptr_t)blocks & 3u))
+			return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse_device: reference, pitch and blocks must be non-NULL and "
+				"4-byte aligned, pitch >= %zu", (size_t)width*4u);
+		// the kernel adds to the four sums with 64-bit atomics
+		if ((uintptr_t)sse_device % 8u != 0)
+			return fail(ctx, CFHIP_E_INVALID, "pvrtc_decode_sse_device: sse_device must be 8-byte aligned");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		unsigned long long* sum = reinterpret_cast<unsigned long long*>(sse_device);
+		HIP_TRY(ctx, hipMemsetAsync(sum, 0, 32, lease.stream));
+		rc = pvrtc_decode_launch(ctx, format, blocks, width, height, nullptr, 0, ref_rgba8, ref_pitch_bytes, sum, true,
+			lease.stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 } // extern "C"
@@ -5291,21 +5205,10 @@ static int std_check(cfhip_ctx* ctx, const char* what, int format, int type, con
 static int std_unpack_launch(cfhip_ctx* ctx, int format, int type, const StdGeom& g, const void* pixels, void* out,
 	size_t out_pitch, uint32_t width, uint32_t height, hipStream_t stream)
 {
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	ctx->last_kernel = "cfhip_std_unpack_kernel";
-	hipEvent_t a, b;
-	int rc = next_event_pair(ctx, &a, &b);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipEventRecord(a, stream));
-	const hipError_t e = cfhip_launch_std_unpack(format, type, g.bpp, pixels, width, height, out, out_pitch, stream);
-	if (e != hipSuccess)
-		return fail(ctx, CFHIP_E_DEVICE, "std_unpack launch: %s", hipGetErrorString(e));
-	HIP_TRY(ctx, hipEventRecord(b, stream));
-	return CFHIP_OK;
+	begin_call(ctx, stream, "cfhip_std_unpack_kernel");
+	return timed(ctx, stream, "std_unpack", [&] {
+		return cfhip_launch_std_unpack(format, type, g.bpp, pixels, width, height, out, out_pitch, stream);
+	});
 }
 
 // What one cfhip_std_compare call runs and where its device scratch lies: the unpacked surface of the SSIM pass
@@ -5386,34 +5289,24 @@ static int std_compare_enqueue(cfhip_ctx* ctx, int format, int type, const StdCo
 	const void* ref, int ref_pixel_type, size_t ref_pitch, uint32_t width, uint32_t height, uint8_t* scratch,
 	cfhip_compare_result* result, hipStream_t stream)
 {
-	if (!ctx->profiling)
-		ctx->events_used = 0;
-	ctx->events_stream = stream;
-	ctx->last_ms = -1.0f;
-	ctx->last_kernel = "cfhip_std_compare_kernel";
+	begin_call(ctx, stream, "cfhip_std_compare_kernel");
 	double* pa = reinterpret_cast<double*>(scratch + c.pa_off);
 	double* pb = c.ssim ? reinterpret_cast<double*>(scratch + c.pb_off) : nullptr;
-	hipEvent_t a, b;
-	int rc = next_event_pair(ctx, &a, &b);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipEventRecord(a, stream));
-	hipError_t e = cfhip_launch_std_compare(format, type, c.g.bpp, pixels, ref, ref_pixel_type, ref_pitch, width,
-		height, c.cmask, c.hdr ? 1 : 0, pa, stream);
-	if (e == hipSuccess && c.ssim) {
-		const size_t dec_pitch = (size_t)width*16u;
-		e = cfhip_launch_std_unpack(format, type, c.g.bpp, pixels, width, height, scratch, dec_pitch, stream);
+	return timed(ctx, stream, "std_compare", [&] {
+		hipError_t e = cfhip_launch_std_compare(format, type, c.g.bpp, pixels, ref, ref_pixel_type, ref_pitch, width,
+			height, c.cmask, c.hdr ? 1 : 0, pa, stream);
+		if (e == hipSuccess && c.ssim) {
+			const size_t dec_pitch = (size_t)width*16u;
+			e = cfhip_launch_std_unpack(format, type, c.g.bpp, pixels, width, height, scratch, dec_pitch, stream);
+			if (e == hipSuccess)
+				e = cfhip_launch_ssim(scratch, dec_pitch, CFHIP_LAYOUT_RGBA32F, ref, ref_pixel_type, ref_pitch, width,
+					height, c.cmask, ssim_taps(), type == CFHIP_TYPE_SNORM ? 2.0 : 1.0, pb, stream);
+		}
 		if (e == hipSuccess)
-			e = cfhip_launch_ssim(scratch, dec_pitch, CFHIP_LAYOUT_RGBA32F, ref, ref_pixel_type, ref_pitch, width,
-				height, c.cmask, ssim_taps(), type == CFHIP_TYPE_SNORM ? 2.0 : 1.0, pb, stream);
-	}
-	if (e == hipSuccess)
-		e = cfhip_launch_compare_final(pa, c.na, pb, c.nb, c.cmask, c.hdr ? 1 : 0, c.windows,
-			(uint64_t)width*height, result, stream);
-	if (e != hipSuccess)
-		return fail(ctx, CFHIP_E_DEVICE, "std_compare launch: %s", hipGetErrorString(e));
-	HIP_TRY(ctx, hipEventRecord(b, stream));
-	return CFHIP_OK;
+			e = cfhip_launch_compare_final(pa, c.na, pb, c.nb, c.cmask, c.hdr ? 1 : 0, c.windows,
+				(uint64_t)width*height, result, stream);
+		return e;
+	});
 }
 
 extern "C" {
@@ -5421,147 +5314,147 @@ extern "C" {
 int cfhip_std_unpack(cfhip_ctx* ctx, int format, int type, const void* pixels, size_t pixels_bytes, uint32_t width,
 	uint32_t height, void* out_rgba32f, size_t out_capacity)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	StdGeom g;
-	int rc = std_check(ctx, "std_unpack", format, type, pixels, width, height, &g);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!out_rgba32f)
-		return fail(ctx, CFHIP_E_INVALID, "std_unpack: out is NULL");
-	if (pixels_bytes < g.payload_bytes)
-		return fail(ctx, CFHIP_E_INVALID, "std_unpack: pixels_bytes %zu < %zu for %ux%u", pixels_bytes,
-			g.payload_bytes, width, height);
-	const size_t out_bytes = (size_t)width*height*16u;
-	if (out_capacity < out_bytes)
-		return fail(ctx, CFHIP_E_CAPACITY, "std_unpack: out_capacity %zu < %zu", out_capacity, out_bytes);
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, ctx->stream);
-	const hipStream_t stream = lease.stream;
-	// d_src: the payload; d_out: the texels
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, g.payload_bytes);
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, out_bytes);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, pixels, g.payload_bytes, hipMemcpyHostToDevice, stream));
-	rc = std_unpack_launch(ctx, format, type, g, ctx->d_src, ctx->d_out, (size_t)width*16u, width, height, stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	HIP_TRY(ctx, hipMemcpyAsync(out_rgba32f, ctx->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
-	return lease.done(true);
+	return guarded(ctx, "std_unpack", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		StdGeom g;
+		int rc = std_check(ctx, "std_unpack", format, type, pixels, width, height, &g);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!out_rgba32f)
+			return fail(ctx, CFHIP_E_INVALID, "std_unpack: out is NULL");
+		if (pixels_bytes < g.payload_bytes)
+			return fail(ctx, CFHIP_E_INVALID, "std_unpack: pixels_bytes %zu < %zu for %ux%u", pixels_bytes,
+				g.payload_bytes, width, height);
+		const size_t out_bytes = (size_t)width*height*16u;
+		if (out_capacity < out_bytes)
+			return fail(ctx, CFHIP_E_CAPACITY, "std_unpack: out_capacity %zu < %zu", out_capacity, out_bytes);
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		const hipStream_t stream = lease.stream;
+		// d_src: the payload; d_out: the texels
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, g.payload_bytes);
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, out_bytes);
+		if (rc != CFHIP_OK)
+			return rc;
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, pixels, g.payload_bytes, hipMemcpyHostToDevice, stream));
+		rc = std_unpack_launch(ctx, format, type, g, ctx->d_src, ctx->d_out, (size_t)width*16u, width, height, stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		HIP_TRY(ctx, hipMemcpyAsync(out_rgba32f, ctx->d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+		return lease.done(true);
+	});
 }
 
 int cfhip_std_unpack_device(cfhip_ctx* ctx, int format, int type, const void* pixels, uint32_t width,
 	uint32_t height, void* out_rgba32f, size_t out_pitch_bytes, void* stream_)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	StdGeom g;
-	int rc = std_check(ctx, "std_unpack_device", format, type, pixels, width, height, &g);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (!out_rgba32f)
-		return fail(ctx, CFHIP_E_INVALID, "std_unpack_device: out is NULL");
-	if (out_pitch_bytes < (size_t)width*16u)
-		return fail(ctx, CFHIP_E_INVALID, "std_unpack_device: out pitch %zu < %zu", out_pitch_bytes,
-			(size_t)width*16u);
-	// the kernel stores floats (whole float4 texels when pointer and pitch allow)
-	if ((uintptr_t)out_rgba32f % 4u != 0 || out_pitch_bytes % 4u != 0)
-		return fail(ctx, CFHIP_E_INVALID, "std_unpack_device: out and its pitch must be 4-byte aligned");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	// no staging buffer is touched: the lease only carries the synchronisation rule of the stream
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	rc = std_unpack_launch(ctx, format, type, g, pixels, out_rgba32f, out_pitch_bytes, width, height, lease.stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	return lease.done(!stream_);
+	return guarded(ctx, "std_unpack_device", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		StdGeom g;
+		int rc = std_check(ctx, "std_unpack_device", format, type, pixels, width, height, &g);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!out_rgba32f)
+			return fail(ctx, CFHIP_E_INVALID, "std_unpack_device: out is NULL");
+		if (out_pitch_bytes < (size_t)width*16u)
+			return fail(ctx, CFHIP_E_INVALID, "std_unpack_device: out pitch %zu < %zu", out_pitch_bytes,
+				(size_t)width*16u);
+		// the kernel stores floats (whole float4 texels when pointer and pitch allow)
+		if ((uintptr_t)out_rgba32f % 4u != 0 || out_pitch_bytes % 4u != 0)
+			return fail(ctx, CFHIP_E_INVALID, "std_unpack_device: out and its pitch must be 4-byte aligned");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		// no staging buffer is touched: the lease only carries the synchronisation rule of the stream
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		rc = std_unpack_launch(ctx, format, type, g, pixels, out_rgba32f, out_pitch_bytes, width, height, lease.stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 int cfhip_std_compare(cfhip_ctx* ctx, int format, int type, const void* pixels, size_t pixels_bytes, uint32_t width,
 	uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes, const uint8_t mask_rgba[4],
 	unsigned flags, cfhip_compare_result* result)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	StdCompareGeom c;
-	int rc = std_compare_check(ctx, "std_compare", format, type, pixels, width, height, ref, ref_pixel_type,
-		ref_pitch_bytes, mask_rgba, flags, result, &c);
-	if (rc != CFHIP_OK)
-		return rc;
-	if (pixels_bytes < c.g.payload_bytes)
-		return fail(ctx, CFHIP_E_INVALID, "std_compare: pixels_bytes %zu < %zu for %ux%u", pixels_bytes,
-			c.g.payload_bytes, width, height);
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	StagingLease lease(ctx, ctx->stream);
-	const hipStream_t stream = lease.stream;
-	// d_src: the payload; d_out: the reference, tightly packed, the scratch, the result
-	const size_t row = (size_t)width*(size_t)c.ref_bytes;
-	const size_t scr_off = align16(row*height), res_off = align16(scr_off + c.scratch_bytes);
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, c.g.payload_bytes);
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, res_off + sizeof(cfhip_compare_result));
-	if (rc != CFHIP_OK)
-		return rc;
-	uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
-	cfhip_compare_result* d_res = reinterpret_cast<cfhip_compare_result*>(d + res_off);
-	HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, pixels, c.g.payload_bytes, hipMemcpyHostToDevice, stream));
-	HIP_TRY(ctx, hipMemcpy2DAsync(d, row, ref, ref_pitch_bytes, row, height, hipMemcpyHostToDevice, stream));
-	rc = std_compare_enqueue(ctx, format, type, c, ctx->d_src, d, ref_pixel_type, row, width, height, d + scr_off,
-		d_res, stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	cfhip_compare_result res;
-	HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, stream));
-	rc = lease.done(true);
-	if (rc != CFHIP_OK)
-		return rc;
-	*result = res;
-	return CFHIP_OK;
+	return guarded(ctx, "std_compare", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		StdCompareGeom c;
+		int rc = std_compare_check(ctx, "std_compare", format, type, pixels, width, height, ref, ref_pixel_type,
+			ref_pitch_bytes, mask_rgba, flags, result, &c);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (pixels_bytes < c.g.payload_bytes)
+			return fail(ctx, CFHIP_E_INVALID, "std_compare: pixels_bytes %zu < %zu for %ux%u", pixels_bytes,
+				c.g.payload_bytes, width, height);
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, ctx->stream);
+		const hipStream_t stream = lease.stream;
+		// d_src: the payload; d_out: the reference, tightly packed, the scratch, the result
+		const size_t row = (size_t)width*(size_t)c.ref_bytes;
+		const size_t scr_off = align16(row*height), res_off = align16(scr_off + c.scratch_bytes);
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, c.g.payload_bytes);
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, res_off + sizeof(cfhip_compare_result));
+		if (rc != CFHIP_OK)
+			return rc;
+		uint8_t* d = static_cast<uint8_t*>(ctx->d_out);
+		cfhip_compare_result* d_res = reinterpret_cast<cfhip_compare_result*>(d + res_off);
+		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_src, pixels, c.g.payload_bytes, hipMemcpyHostToDevice, stream));
+		HIP_TRY(ctx, hipMemcpy2DAsync(d, row, ref, ref_pitch_bytes, row, height, hipMemcpyHostToDevice, stream));
+		rc = std_compare_enqueue(ctx, format, type, c, ctx->d_src, d, ref_pixel_type, row, width, height, d + scr_off,
+			d_res, stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		cfhip_compare_result res;
+		HIP_TRY(ctx, hipMemcpyAsync(&res, d_res, sizeof(res), hipMemcpyDeviceToHost, stream));
+		rc = lease.done(true);
+		if (rc != CFHIP_OK)
+			return rc;
+		*result = res;
+		return CFHIP_OK;
+	});
 }
 
 int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* pixels, uint32_t width,
 	uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes, const uint8_t mask_rgba[4],
 	unsigned flags, cfhip_compare_result* result_device, void* stream_)
 {
-	if (!ctx)
-		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-	std::lock_guard<std::mutex> guard(ctx->lock);
-	ctx->error.clear();
-	StdCompareGeom c;
-	int rc = std_compare_check(ctx, "std_compare_device", format, type, pixels, width, height, ref, ref_pixel_type,
-		ref_pitch_bytes, mask_rgba, flags, result_device, &c);
-	if (rc != CFHIP_OK)
-		return rc;
-	// the kernels read reference texels with one aligned load each and store doubles to the result
-	const size_t rb = (size_t)c.ref_bytes;
-	if ((uintptr_t)ref % rb != 0 || ref_pitch_bytes % rb != 0)
-		return fail(ctx, CFHIP_E_INVALID, "std_compare_device: reference and its pitch must be %zu-byte aligned", rb);
-	if ((uintptr_t)result_device % 8u != 0)
-		return fail(ctx, CFHIP_E_INVALID, "std_compare_device: misaligned result");
-	HIP_TRY(ctx, hipSetDevice(ctx->device));
-	// the partials (and the SSIM pass's unpacked surface) live in d_out: the lease orders them across streams
-	StagingLease lease(ctx, stream_ ? static_cast<hipStream_t>(stream_) : ctx->stream);
-	rc = lease.acquire();
-	if (rc == CFHIP_OK)
-		rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, c.scratch_bytes);
-	if (rc != CFHIP_OK)
-		return rc;
-	rc = std_compare_enqueue(ctx, format, type, c, pixels, ref, ref_pixel_type, ref_pitch_bytes, width, height,
-		static_cast<uint8_t*>(ctx->d_out), result_device, lease.stream);
-	if (rc != CFHIP_OK)
-		return rc;
-	return lease.done(!stream_);
+	return guarded(ctx, "std_compare_device", [&]() -> int {
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		StdCompareGeom c;
+		int rc = std_compare_check(ctx, "std_compare_device", format, type, pixels, width, height, ref, ref_pixel_type,
+			ref_pitch_bytes, mask_rgba, flags, result_device, &c);
+		if (rc != CFHIP_OK)
+			return rc;
+		// the kernels read reference texels with one aligned load each and store doubles to the result
+		const size_t rb = (size_t)c.ref_bytes;
+		if ((uintptr_t)ref % rb != 0 || ref_pitch_bytes % rb != 0)
+			return fail(ctx, CFHIP_E_INVALID, "std_compare_device: reference and its pitch must be %zu-byte aligned", rb);
+		if ((uintptr_t)result_device % 8u != 0)
+			return fail(ctx, CFHIP_E_INVALID, "std_compare_device: misaligned result");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		// the partials (and the SSIM pass's unpacked surface) live in d_out: the lease orders them across streams
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_out, &ctx->out_cap, c.scratch_bytes);
+		if (rc != CFHIP_OK)
+			return rc;
+		rc = std_compare_enqueue(ctx, format, type, c, pixels, ref, ref_pixel_type, ref_pitch_bytes, width, height,
+			static_cast<uint8_t*>(ctx->d_out), result_device, lease.stream);
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
 }
 
 } // extern "C"

@@ -99,6 +99,30 @@ def test_query_accepts_exactly_the_pairs_the_reference_convert_tests_list(hip_li
     assert accepted == listed, (sorted(accepted - listed), sorted(listed - accepted))
 
 
+def test_mip_and_resize_calls_without_a_context_are_invalid(hip_lib):
+    """cfhip_generate_mips_device, its array and 3-D forms and cfhip_resize_device check the context before any
+    argument: without one the answer is CFHIP_E_INVALID "ctx is NULL", also where an argument is NULL or empty as
+    well (with a context those draw the call's own "... NULL or empty argument")."""
+    from cuttlefish_amd import api
+    L = hip_lib
+    buf = (ctypes.c_uint8 * 256)()
+    src = ctypes.cast(buf, ctypes.c_void_p)
+    one = (ctypes.c_void_p * 1)(src)
+    rgba8, linear, box = int(api.PixelType.RGBA8), int(api.ColorSpace.Linear), 0
+    for s, w, tab in [(src, 4, one), (None, 4, one), (src, 0, one), (src, 4, None)]:
+        calls = {
+            "generate_mips": lambda: L.cfhip_generate_mips_device(None, s, rgba8, w, 4, 16, linear, box, tab, 2, None),
+            "generate_mips_array": lambda: L.cfhip_generate_mips_array_device(
+                None, one if s else None, 1, rgba8, w, 4, 16, linear, box, tab, 2, None),
+            "generate_mips3d": lambda: L.cfhip_generate_mips3d_device(
+                None, s, rgba8, w, 4, 2, 16, 64, linear, box, tab, 2, None),
+            "resize": lambda: L.cfhip_resize_device(None, s, rgba8, w, 4, 16, linear, box, src if tab else None, 2, 2, None),
+        }
+        for name, call in calls.items():
+            assert call() == api.E_INVALID, (name, s, w, tab)
+            assert L.cfhip_last_error(None) == b"ctx is NULL", (name, s, w, tab)
+
+
 def test_header_compiles_as_plain_c99(tmp_path):
     """integration/check_header.c: a C translation unit including include/cuttlefish_hip.h,
     -std=c99 -pedantic-errors (the boundary is a C ABI, not a C++ one)."""
