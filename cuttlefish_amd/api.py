@@ -204,7 +204,8 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_lz4_bound", "cfhip_lz4_encode", "cfhip_lz4_encode_device", "cfhip_lz4_encode_stage_ms",
            "cfhip_lz4_decode", "cfhip_lz4_decode_device", "cfhip_lz4_decode_stage_ms",
            "cfhip_png_bound", "cfhip_png_encode", "cfhip_png_encode_device", "cfhip_png_stage_ms",
-           "cfhip_mip_post_array_device", "cfhip_alpha_coverage_device", "cfhip_alpha_bleed_array_device"]
+           "cfhip_mip_post_array_device", "cfhip_alpha_coverage_device", "cfhip_alpha_bleed_array_device",
+           "cfhip_alpha_sdf_array_device"]
 
 
 class Layout(enum.IntEnum):
@@ -531,6 +532,62 @@ def make_bleed_params(threshold: float = 0.0, wrap=(False, False), max_distance:
     return BleedParams((BLEED_WRAP_X if wx else 0) | (BLEED_WRAP_Y if wy else 0), float(threshold), int(max_distance))
 
 
+SDF_WRAP_X, SDF_WRAP_Y = 1, 2                    # cfhip_sdf_params.flags
+SDF_SCALES = (1, 2, 4, 8, 16)
+SDF_MAX_SPREAD = 126
+SDF_CHANNELS = {"r": 1, "g": 2, "b": 4, "a": 8}   # cfhip_sdf_params.channel_mask
+
+
+class SdfParams(ctypes.Structure):
+    """cfhip_sdf_params"""
+    _fields_ = [("flags", ctypes.c_uint32), ("alpha_threshold", ctypes.c_float), ("spread", ctypes.c_uint32),
+                ("scale", ctypes.c_uint32), ("channel_mask", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class SdfResult(ctypes.Structure):
+    """cfhip_sdf_result: one surface's source texels inside, and those farther than the spread from the silhouette"""
+    _fields_ = [("inside", ctypes.c_uint32), ("saturated", ctypes.c_uint32), ("reserved", ctypes.c_uint32*2)]
+
+
+SDF_RESULT_DTYPE = np.dtype([("inside", np.uint32), ("saturated", np.uint32), ("reserved0", np.uint32),
+                             ("reserved1", np.uint32)])
+
+
+def sdf_channel_mask(channels) -> int:
+    """channels as the distance-field methods take them: a string of r, g, b, a (any case, each at most once) or the
+    mask itself (R = 1, G = 2, B = 4, A = 8)"""
+    if isinstance(channels, (int, np.integer)) and not isinstance(channels, (bool, np.bool_)):
+        mask = int(channels)
+    elif isinstance(channels, str) and channels:
+        mask = 0
+        for ch in channels.lower():
+            if ch not in SDF_CHANNELS or mask & SDF_CHANNELS[ch]:
+                raise ValueError("channels %r: a string of r, g, b, a, each at most once" % (channels,))
+            mask |= SDF_CHANNELS[ch]
+    else:
+        raise ValueError("channels %r: a string of r, g, b, a, or a mask of 1 to 15" % (channels,))
+    if not 1 <= mask <= 15:
+        raise ValueError("channels %r: a mask of 1 to 15" % (channels,))
+    return mask
+
+
+def make_sdf_params(spread: int, scale: int = 1, threshold: float = 0.5, wrap=(False, False), channels="a") -> SdfParams:
+    """spread: the distance in source texels at which the field reaches 0 and 1 (1 to 126); scale: source texels per
+    output texel and side (1, 2, 4, 8 or 16); threshold: texels with alpha > threshold are inside (0 <= threshold < 1);
+    wrap: a bool or (x, y), the axes on which the surface tiles; channels: the components that receive the field.
+    Every bad field is a ValueError here, before the library would refuse it."""
+    if isinstance(spread, (bool, np.bool_)) or not isinstance(spread, (int, np.integer)) or not 1 <= spread <= SDF_MAX_SPREAD:
+        raise ValueError("spread %r: an integer from 1 to %d" % (spread, SDF_MAX_SPREAD))
+    if isinstance(scale, (bool, np.bool_)) or scale not in SDF_SCALES:
+        raise ValueError("scale %r: one of %r" % (scale, SDF_SCALES))
+    t = float(threshold)
+    if not 0.0 <= t < 1.0 or not 0.0 <= float(np.float32(t)) < 1.0:
+        raise ValueError("threshold %r outside [0, 1)" % (threshold,))
+    wx, wy = wrap_axes(wrap)
+    return SdfParams((SDF_WRAP_X if wx else 0) | (SDF_WRAP_Y if wy else 0), t, int(spread), int(scale),
+                     sdf_channel_mask(channels), 0)
+
+
 RDO_NO_CAP = 0xFFFFFFFF         # max_sse_increase: no cap
 RDO_ROW_ABOVE = 1               # CFHIP_RDO_ROW_ABOVE
 
@@ -649,6 +706,11 @@ def load_library(path: Optional[str] = None):
         ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
         ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(BleedParams), ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_alpha_bleed_array_device.restype = ctypes.c_int
+    L.cfhip_alpha_sdf_array_device.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
+        ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_size_t,
+        ctypes.POINTER(SdfParams), ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_alpha_sdf_array_device.restype = ctypes.c_int
     L.cfhip_generate_mips3d_device.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
         ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
@@ -1214,6 +1276,57 @@ class Context:
                                 max_distance, res.data_ptr())
         rec = res.cpu().numpy().view(BLEED_RESULT_DTYPE)[0]
         return dev.cpu().numpy().view(host.dtype), {k: int(rec[k]) for k in rec.dtype.names}
+
+    def alpha_sdf_device(self, srcs: Sequence[int], pixel_type, width: int, height: int, row_pitch_bytes: int,
+                         dsts: Sequence[int], dst_pixel_type, dst_row_pitch_bytes: int, spread: int, scale: int = 1,
+                         threshold: float = 0.5, wrap=(False, False), channels="a", results: int = 0, stream: int = 0):
+        """A signed distance field from alpha (cfhip_alpha_sdf_array_device): the texels of each device surface srcs[l]
+        (all of one size and pixel type) with alpha > threshold are inside; every texel's Euclidean distance to the
+        nearest texel of the other class, exact up to `spread` source texels, is averaged over scale x scale tiles and
+        written to the `channels` of dsts[l] (width/scale x height/scale texels of dst_pixel_type) with 0.5 at the
+        silhouette, 0 a spread outside it and 1 a spread inside.  The other components of dsts[l] are not written;
+        dsts[l] may be srcs[l] at scale 1 with equal pixel types.  wrap: a bool or (x, y), the axes on which the
+        surface tiles.  results: device pointer to len(srcs) cfhip_sdf_result records (SDF_RESULT_DTYPE), or 0 for none.
+        One call is 3 launches at scale 1 and 4 above, whatever the layers and the spread."""
+        nl = len(srcs)
+        if len(dsts) != nl:
+            raise ValueError("srcs and dsts must list the same layers")
+        params = make_sdf_params(spread, scale, threshold, wrap, channels)
+        sarr = (ctypes.c_void_p * max(nl, 1))(*[ctypes.c_void_p(int(p)) for p in srcs])
+        darr = (ctypes.c_void_p * max(nl, 1))(*[ctypes.c_void_p(int(p)) for p in dsts])
+        self._check(self._lib.cfhip_alpha_sdf_array_device(
+            self._h, sarr, nl, int(pixel_type), width, height, row_pitch_bytes, darr, int(dst_pixel_type),
+            dst_row_pitch_bytes, ctypes.byref(params), ctypes.c_void_p(int(results)) if results else None,
+            ctypes.c_void_p(stream) if stream else None))
+
+    def alpha_sdf(self, image: np.ndarray, spread: int, scale: int = 1, threshold: float = 0.5, wrap=(False, False),
+                  channels="a", out_dtype=None):
+        """Host convenience: one (h, w, 4) uint8 / float16 / float32 image through alpha_sdf_device -> (a new
+        (h/scale, w/scale, 4) array of out_dtype -- the image's by default -- with the field in `channels`, the record as
+        a dict of inside, saturated, reserved0, reserved1).  The other channels are zero, except at scale 1 with the
+        image's own dtype, where they are the image's."""
+        import torch
+        host = np.ascontiguousarray(image)
+        if host.ndim != 3 or host.shape[2] != 4:
+            raise ValueError("expected (h, w, 4)")
+        make_sdf_params(spread, scale, threshold, wrap, channels)
+        h, w = host.shape[:2]
+        if h % scale or w % scale:
+            raise ValueError("%dx%d is not a multiple of the scale %d" % (w, h, scale))
+        out_dtype = host.dtype if out_dtype is None else np.dtype(out_dtype)
+        pt = pixel_type_of(host)
+        dpt = pixel_type_of(np.empty(0, out_dtype))
+        dev = torch.from_numpy(host.view(np.uint8)).to("cuda:%d" % self.device_id)
+        if scale == 1 and out_dtype == host.dtype:
+            out = dev.clone()
+        else:
+            out = torch.zeros((h//scale, (w//scale)*4*out_dtype.itemsize), dtype=torch.uint8, device=dev.device)
+        res = torch.zeros(4, dtype=torch.int32, device=dev.device)
+        self.alpha_sdf_device([dev.data_ptr()], pt, w, h, host.strides[0], [out.data_ptr()], dpt,
+                              (w//scale)*4*out_dtype.itemsize, spread, scale, threshold, wrap, channels, res.data_ptr())
+        rec = res.cpu().numpy().view(SDF_RESULT_DTYPE)[0]
+        return (out.cpu().numpy().view(out_dtype).reshape(h//scale, w//scale, 4),
+                {k: int(rec[k]) for k in rec.dtype.names})
 
     def generate_mips3d_device(self, src: int, pixel_type, width: int, height: int, depth: int,
                                row_pitch_bytes: int, slice_pitch_bytes: int, dst_levels: Sequence[int],

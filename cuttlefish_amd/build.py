@@ -165,7 +165,10 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  "cfhip_mip_post_gather_kernel", "cfhip_mip_post_count_kernel", "cfhip_mip_post_decide_kernel",
                  "cfhip_mip_post_apply_kernel",
                  # alpha bleeding (csrc/alpha_bleed.hip): pass 0, a step of the flood, the last step fused with the fill
-                 "cfhip_alpha_bleed_seed_kernel", "cfhip_alpha_bleed_step_kernel", "cfhip_alpha_bleed_fill_kernel")
+                 "cfhip_alpha_bleed_seed_kernel", "cfhip_alpha_bleed_step_kernel", "cfhip_alpha_bleed_fill_kernel",
+                 # the signed distance field from alpha (csrc/alpha_sdf.hip): classes, row distances, columns, tiles
+                 "cfhip_alpha_sdf_classify_kernel", "cfhip_alpha_sdf_row_kernel", "cfhip_alpha_sdf_column_kernel",
+                 "cfhip_alpha_sdf_resolve_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

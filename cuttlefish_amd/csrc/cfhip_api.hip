@@ -18,6 +18,7 @@
 #include "png.h"
 #include "mip_post.h"
 #include "alpha_bleed.h"
+#include "alpha_sdf.h"
 #include "stage_log.h"
 #include "../../include/cuttlefish_hip.h"
 
@@ -2415,6 +2416,119 @@ int cfhip_alpha_bleed_array_device(cfhip_ctx* ctx, void* const* images, uint32_t
 				return cfhip_launch_alpha_bleed_fill(&call, layers, sx(1u), sy(1u), params->max_distance*params->max_distance,
 					buf[cur], results_device, stream);
 			});
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
+}
+
+// ---- signed distance field from alpha (csrc/alpha_sdf.hip): exact to the spread, 0.5 at the silhouette --------------
+int cfhip_alpha_sdf_array_device(cfhip_ctx* ctx, const void* const* src, uint32_t layers, int src_pixel_type, uint32_t width,
+	uint32_t height, size_t src_pitch_bytes, void* const* dst, int dst_pixel_type, size_t dst_pitch_bytes,
+	const cfhip_sdf_params* params, cfhip_sdf_result* results_device, void* stream_)
+{
+	static_assert(sizeof(cfhip_sdf_params) == 24 && sizeof(cfhip_sdf_result) == 16, "the ABI's sizes");
+	return guarded(ctx, "alpha_sdf", [&]() -> int {
+		if (!params)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: params is NULL");
+		if (!src)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: src is NULL");
+		if (!dst)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst is NULL");
+		if (!layers || layers > 65535u)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: layers is %u (1 to 65535 per call)", layers);
+		if (!width || !height || width > CFSD_MAX_SIDE || height > CFSD_MAX_SIDE)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: width and height are 1 to %u each, not %ux%u", CFSD_MAX_SIDE, width, height);
+		const size_t spb = pixel_bytes(src_pixel_type), dpb = pixel_bytes(dst_pixel_type);
+		if (!spb)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: src_pixel_type %d", src_pixel_type);
+		if (!dpb)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst_pixel_type %d", dst_pixel_type);
+		if (params->flags & ~(uint32_t)(CFHIP_SDF_WRAP_X | CFHIP_SDF_WRAP_Y))
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: params->flags 0x%x: unknown", params->flags);
+		const float t = params->alpha_threshold;
+		if (!(t >= 0.0f && t < 1.0f))
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: params->alpha_threshold %g outside [0, 1)", (double)t);
+		if (params->spread < 1u || params->spread > CFSD_MAX_SPREAD)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: params->spread %u outside 1 to %u", params->spread, CFSD_MAX_SPREAD);
+		const uint32_t s = params->scale;
+		if (s != 1u && s != 2u && s != 4u && s != 8u && s != 16u)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: params->scale %u is not 1, 2, 4, 8 or 16", s);
+		if (!params->channel_mask || params->channel_mask > 15u)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: params->channel_mask 0x%x outside 1 to 15", params->channel_mask);
+		if (params->reserved)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: params->reserved is %u, not 0", params->reserved);
+		if (width % s || height % s)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: %ux%u is not a multiple of the scale %u", width, height, s);
+		if (src_pitch_bytes < (size_t)width*spb)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: src_pitch_bytes %zu < %zu, a row", src_pitch_bytes, (size_t)width*spb);
+		if (src_pitch_bytes % (spb/4u))
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: src_pitch_bytes %zu not aligned to a component (%zu bytes)", src_pitch_bytes,
+				spb/4u);
+		if (dst_pitch_bytes < (size_t)(width/s)*dpb)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst_pitch_bytes %zu < %zu, a row", dst_pitch_bytes, (size_t)(width/s)*dpb);
+		if (dst_pitch_bytes % (dpb/4u))
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst_pitch_bytes %zu not aligned to a component (%zu bytes)", dst_pitch_bytes,
+				dpb/4u);
+		const uint64_t texels = (uint64_t)layers*width*height;
+		if (texels > CFSD_MAX_TEXELS)
+			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: more than 2^31 texels in one call");
+		for (uint32_t l = 0; l < layers; ++l) {
+			if (!src[l])
+				return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: src[%u] is NULL", l);
+			if (!dst[l])
+				return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst[%u] is NULL", l);
+			if ((uintptr_t)src[l] % (spb/4u))
+				return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: src[%u] not aligned to a component (%zu bytes)", l, spb/4u);
+			if ((uintptr_t)dst[l] % (dpb/4u))
+				return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst[%u] not aligned to a component (%zu bytes)", l, dpb/4u);
+			// in place: every alpha is read before anything is written, but only a surface of the same geometry is one
+			if (dst[l] == src[l] && (s != 1u || dst_pixel_type != src_pixel_type))
+				return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst[%u] equals src[%u]: in place needs scale 1 and equal pixel types", l, l);
+		}
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		const hipStream_t stream = lease.stream;
+		begin_call(ctx, stream, "cfhip_alpha_sdf_column_kernel");
+		// d_batch: the layers' source pointers, then their destination pointers.  d_src: the bit plane (whole words per
+		// row), e (16 bits per texel, scale > 1 only), the row bytes -- in the order of their alignment
+		const size_t plane_bytes = (size_t)layers*height*((width + 63u)/64u)*8u, e_bytes = s > 1u ? (size_t)texels*2u : 0u;
+		int rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, (size_t)layers*2u*sizeof(void*));
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, plane_bytes + e_bytes + (size_t)texels);
+		if (rc != CFHIP_OK)
+			return rc;
+		// pageable sources: the runtime stages the copies before returning
+		void** table = static_cast<void**>(ctx->d_batch);
+		HIP_TRY(ctx, hipMemcpyAsync(table, src, (size_t)layers*sizeof(void*), hipMemcpyHostToDevice, stream));
+		HIP_TRY(ctx, hipMemcpyAsync(table + layers, dst, (size_t)layers*sizeof(void*), hipMemcpyHostToDevice, stream));
+		if (results_device)
+			HIP_TRY(ctx, hipMemsetAsync(results_device, 0, (size_t)layers*sizeof(cfhip_sdf_result), stream));
+		cfsd_call call;
+		call.src = table;
+		call.dst = table + layers;
+		call.src_pitch = src_pitch_bytes; call.dst_pitch = dst_pitch_bytes;
+		call.width = width; call.height = height;
+		call.src_type = src_pixel_type; call.dst_type = dst_pixel_type;
+		call.flags = params->flags;
+		call.spread = params->spread; call.scale = s; call.channel_mask = params->channel_mask;
+		uint8_t* scratch = static_cast<uint8_t*>(ctx->d_src);
+		uint64_t* plane = reinterpret_cast<uint64_t*>(scratch);
+		uint16_t* e = reinterpret_cast<uint16_t*>(scratch + plane_bytes);
+		uint8_t* rows = scratch + plane_bytes + e_bytes;
+		// every launch of the pass is a timed span of its own
+		const auto sdf = [&](auto&& launch) { return timed(ctx, stream, "alpha_sdf", launch); };
+		rc = sdf([&] { return cfhip_launch_alpha_sdf_classify(&call, layers, t, plane, results_device, stream); });
+		if (rc == CFHIP_OK)
+			rc = sdf([&] { return cfhip_launch_alpha_sdf_row(&call, layers, plane, rows, stream); });
+		if (rc == CFHIP_OK)
+			rc = sdf([&] { return cfhip_launch_alpha_sdf_column(&call, layers, rows, e, results_device, stream); });
+		if (rc == CFHIP_OK && s > 1u)
+			rc = sdf([&] { return cfhip_launch_alpha_sdf_resolve(&call, layers, e, stream); });
 		if (rc != CFHIP_OK)
 			return rc;
 		return lease.done(!stream_);

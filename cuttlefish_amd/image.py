@@ -76,6 +76,15 @@ class _Device:
         self.ctx.alpha_bleed_device([t.data_ptr()], pt, w, h, pitch, threshold, wrap, max_distance)
         return buf
 
+    def sdf(self, src, dst, spread: int, threshold: float = 0.5, wrap=False, channels="a"):
+        """The signed distance field of src's alpha (cfhip_alpha_sdf_array_device) into the named channels of dst, a
+        buffer 1, 2, 4, 8 or 16 times smaller per side (src itself: in place) -> dst"""
+        t, pt, w, h, pitch = src
+        dt, dpt, dw, dh, dpitch = dst
+        self.ctx.alpha_sdf_device([t.data_ptr()], pt, w, h, pitch, [dt.data_ptr()], dpt, dpitch, spread, w // dw,
+                                  threshold, wrap, channels)
+        return dst
+
     def png(self, buf, color_type: int, bit_depth: int, color_space) -> bytes:
         """The PNG file of a buffer (cfhip_png_encode_device): only the file's bytes come back."""
         import torch
@@ -183,6 +192,31 @@ class Image:
         self._last = (buf, self.pixels)
         return True
 
+    def distance_field(self, spread: int, scale: int = 1, threshold: float = 0.5, wrap=False,
+                       channels="a") -> Optional["Image"]:
+        """A signed distance field from this image's alpha (Context.alpha_sdf_device) as a new image of
+        width/scale x height/scale: texels with alpha > threshold are inside, and the named channels take the Euclidean
+        distance to the silhouette, exact up to `spread` source texels -- 0.5 on the edge, 0 a spread outside, 1 a spread
+        inside -- averaged over scale x scale texels.  Sampled bilinearly and tested against 0.5, it magnifies to a clean
+        edge where a small alpha mask goes blocky.  The other channels are this image's at scale 1 (the pixel type
+        stays), and at scale 2, 4, 8 or 16 those of resize(width/scale, height/scale, Box), an RGBA32F image.  wrap: a
+        bool or (x, y) for tiling images.  None for an RGBF image: it has no alpha."""
+        if self.rgbf:
+            return None
+        api.make_sdf_params(spread, scale, threshold, wrap, channels)
+        if self.width % scale or self.height % scale:
+            raise ValueError("%dx%d is not a multiple of the scale %d" % (self.width, self.height, scale))
+        d = _Device(self.device_id)
+        src = d.upload(self.pixels)
+        if scale == 1:
+            dst = (src[0].clone(),) + src[1:]
+        else:
+            dst = d.resize(src, self.width // scale, self.height // scale, self.color_space, ResizeFilter.Box)
+        buf = d.sdf(src, dst, spread, threshold, wrap, channels)
+        out = d.download(buf)
+        self._last = (buf, out)
+        return self._derived(out)
+
     def change_color_space(self, color_space: ColorSpace) -> bool:
         self.pixels = self._run(ImageOp.ColorSpace, dst_color_space=ColorSpace(color_space))
         self.color_space = ColorSpace(color_space)
@@ -217,13 +251,30 @@ _SIGNED = (Type.SNorm, Type.Int, Type.Float)      # isSigned (tool/main.cpp:63-7
 def plan_process_image(width: int, height: int, src_width: int, src_height: int, image_color_space,
                        texture_color_space, mip_level: int = 0, type=Type.UNorm, rotate=None,
                        grayscale: bool = False, normal_map=None, flip_x: bool = False, flip_y: bool = False,
-                       swizzle=None, premultiply: bool = False, bleed: Optional[dict] = None):
+                       swizzle=None, premultiply: bool = False, bleed: Optional[dict] = None,
+                       sdf: Optional[dict] = None):
     """The device steps of process_image, in order: ("ops", ImageOps) and ("resize", width, height, colour space).
     At most three ops steps: before the first resize, between the resizes, after the last.  bleed = dict(threshold=,
     wrap=, max_distance=) (any of them; Image.bleed_alpha's defaults) adds one ("bleed", threshold, wrap, max_distance)
     step directly before the first resize -- after the ops pass in front of it, so that the filter's taps find the bled
     colour -- or after the last ops step when nothing is resized; None adds nothing.  With premultiply it raises
-    ValueError: bleeding is the remedy of straight alpha."""
+    ValueError: bleeding is the remedy of straight alpha.
+    sdf = dict(spread=, threshold=, wrap=, channels=) (spread required; Image.distance_field's defaults) adds two steps:
+    ("sdf_class",) where a bleed step would go -- the buffer whose alpha gives the classes, after the bleed if there is
+    one -- and ("sdf", spread, scale, threshold, wrap, channels) directly after the resize that follows it, which writes
+    the field over the resized image's channels before any later ops step moves texels; nothing resized: scale 1, in
+    place.  The scale is the size before that resize divided by the size after it: ValueError unless it is 1, 2, 4, 8
+    or 16 on both axes, and with premultiply (the field replaces an alpha that is no longer coverage).  None adds
+    nothing."""
+    sdf_step = None
+    if sdf is not None:
+        if premultiply:
+            raise ValueError("sdf and premultiply exclude each other: a distance in alpha is not a coverage to multiply by")
+        unknown = set(sdf) - {"spread", "threshold", "wrap", "channels"}
+        if unknown or "spread" not in sdf:
+            raise ValueError("sdf: spread and any of threshold, wrap, channels; not %r" % (sorted(sdf),))
+        sdf_step = (sdf["spread"], float(sdf.get("threshold", 0.5)), api.wrap_axes(sdf.get("wrap", False)),
+                    sdf.get("channels", "a"))
     bleed_step = None
     if bleed is not None:
         if premultiply:
@@ -288,6 +339,15 @@ def plan_process_image(width: int, height: int, src_width: int, src_height: int,
     if bleed_step is not None:
         first = next((i for i, st in enumerate(steps) if st[0] == "resize"), len(steps))
         steps.insert(first, bleed_step)
+    if sdf_step is not None:
+        first = next((i for i, st in enumerate(steps) if st[0] == "resize"), len(steps))
+        before, after = (src_width, src_height), (steps[first][1:3] if first < len(steps) else (src_width, src_height))
+        scale = before[0] // after[0]
+        if scale not in api.SDF_SCALES or (after[0]*scale, after[1]*scale) != before:
+            raise ValueError("sdf: %dx%d to %dx%d is not a scale of 1, 2, 4, 8 or 16 on both axes" % (before + tuple(after)))
+        api.make_sdf_params(sdf_step[0], scale, sdf_step[1], sdf_step[2], sdf_step[3])
+        steps.insert(first, ("sdf_class",))
+        steps.insert(min(first + 2, len(steps)), ("sdf", sdf_step[0], scale) + sdf_step[1:])
     return steps
 
 
@@ -296,14 +356,18 @@ def process_image(image, image_color_space, texture_color_space, width: int, hei
                   grayscale: bool = False, normal_map: Optional[Tuple[NormalOptions, float]] = None,
                   flip_x: bool = False, flip_y: bool = False, swizzle: Optional[Sequence[Channel]] = None,
                   premultiply: bool = False, orig_image_format=ImageFormat.Invalid, device_id: int = 0,
-                  bleed: Optional[dict] = None) -> np.ndarray:
+                  bleed: Optional[dict] = None, sdf: Optional[dict] = None) -> np.ndarray:
     """loadAndProcessImage (tool/main.cpp:147-277) after the load: colour-space change, resize to the target size
     (max(1, size >> mip_level); the full size first when a normal map is made), rotation, grayscale, normal map
     (normal_map = (NormalOptions, height); KeepSign added for signed types; resized to the mip size afterwards),
     X then Y flip, swizzle, premultiplication and Texture.adjust_image_value_range.  The intermediates stay on the
     device.  Returns the RGBA32F array for Texture.set_image.  image: an (h, w, 4) array or an Image (its pixels).
     bleed = dict(threshold=, wrap=, max_distance=) runs alpha bleeding (Image.bleed_alpha) after the ops pass in front
-    of the resize to the texture's size and before that resize (plan_process_image); not with premultiply."""
+    of the resize to the texture's size and before that resize (plan_process_image); not with premultiply.
+    sdf = dict(spread=, threshold=, wrap=, channels=) writes a signed distance field (Image.distance_field) over the
+    named channels of the resized image: the classes come from the alpha in front of that resize, after the ops pass
+    there and the bleed, at a scale of source size / target size, which must be 1, 2, 4, 8 or 16 on both axes; not with
+    premultiply."""
     if isinstance(image, Image):
         image = image.pixels
     pixels = _pixels(image)
@@ -311,7 +375,7 @@ def process_image(image, image_color_space, texture_color_space, width: int, hei
         orig_image_format = ImageFormat.RGBA8 if pixels.dtype == np.uint8 else ImageFormat.RGBAF
     steps = plan_process_image(width, height, pixels.shape[1], pixels.shape[0], image_color_space,
                                texture_color_space, mip_level, type, rotate, grayscale, normal_map, flip_x, flip_y,
-                               swizzle, premultiply, bleed)
+                               swizzle, premultiply, bleed, sdf)
     d = _Device(device_id)
     buf = d.upload(pixels)
     for s in steps:
@@ -319,6 +383,10 @@ def process_image(image, image_color_space, texture_color_space, width: int, hei
             buf = d.ops(buf, s[1])
         elif s[0] == "bleed":
             buf = d.bleed(buf, s[1], s[2], s[3])
+        elif s[0] == "sdf_class":
+            classes = buf
+        elif s[0] == "sdf":
+            buf = d.sdf(classes, buf, s[1], s[3], s[4], s[5])
         else:
             buf = d.resize(buf, s[1], s[2], s[3], filter)
     out = d.download(buf)

@@ -332,6 +332,7 @@ class Texture:
         self._rdo_target = None
         self._mip_post: List[List[dict]] = []
         self._bleed: List[dict] = []
+        self._sdf: List[dict] = []
 
     def initialize(self, dimension, width: int, height: int, depth: int = 0, mip_levels: int = 1,
                    color_space: ColorSpace = ColorSpace.Linear) -> bool:
@@ -666,6 +667,49 @@ class Texture:
         """The records of the last bleed_alpha(): one dict per image it ran on, in [mip][depth][face] order -- mip, depth,
         face, seeds, filled and max_dist2, the largest squared distance a colour travelled; [] before any call."""
         return [dict(r) for r in self._bleed]
+
+    def alpha_distance_field(self, spread: int, threshold: float = 0.5, wrap=False, channels="a") -> bool:
+        """A signed distance field (Context.alpha_sdf_device) in place of the alpha -- or of the named channels -- of
+        every image currently set, all levels, depths and faces, each within itself and at its own size: texels with
+        alpha > threshold are inside, and the channels take the Euclidean distance to the silhouette, exact up to `spread`
+        texels, with 0.5 on the edge.  The intended order is the field first, then generate_mipmaps: a filtered distance
+        is still a distance.  Do not pass alpha_coverage= to that generate_mipmaps: it would rescale an alpha that is no
+        longer coverage.  Images of equal size and dtype share one call.  wrap: a bool or (x, y) for tiling surfaces.
+        sdf_results() returns the records.  False on an invalid or already converted texture, and on a 3-D texture."""
+        import torch
+        if not self._valid or self._textures or self._dim == Dimension.Dim3D:
+            return False
+        api.make_sdf_params(spread, 1, threshold, wrap, channels)
+        groups: Dict[tuple, List[Tuple[int, int, int]]] = {}
+        for m, level in enumerate(self._images):
+            for d, dep in enumerate(level):
+                for f, im in enumerate(dep):
+                    if im is not None:
+                        groups.setdefault((im.shape[0], im.shape[1], im.dtype.str), []).append((m, d, f))
+        records = {}
+        for (h, w, _), where in groups.items():
+            stack = np.stack([np.ascontiguousarray(self._images[m][d][f]) for m, d, f in where])
+            dev = torch.from_numpy(stack).to("cuda:%d" % self._device_id)
+            res = torch.zeros((len(where), 4), dtype=torch.int32, device=dev.device)
+            size = dev[0].numel()*dev.element_size()
+            ptrs = [dev.data_ptr() + i*size for i in range(len(where))]
+            pt = api.pixel_type_of(stack[0])
+            self._context().alpha_sdf_device(ptrs, pt, w, h, stack.strides[1], ptrs, pt, stack.strides[1], spread, 1,
+                                             threshold, wrap, channels, res.data_ptr())
+            out = dev.cpu().numpy()
+            rec = res.cpu().numpy().view(api.SDF_RESULT_DTYPE).reshape(-1)
+            for i, (m, d, f) in enumerate(where):
+                self._images[m][d][f] = out[i]
+                records[(m, d, f)] = dict(mip=m, depth=d, face=f, inside=int(rec[i]["inside"]),
+                                          saturated=int(rec[i]["saturated"]))
+        self._sdf = [records[k] for k in sorted(records)]
+        return True
+
+    def sdf_results(self):
+        """The records of the last alpha_distance_field(): one dict per image it ran on, in [mip][depth][face] order --
+        mip, depth, face, inside (texels inside) and saturated (texels farther than the spread from the silhouette); []
+        before any call."""
+        return [dict(r) for r in self._sdf]
 
     def mip_post_results(self):
         """The records of the last generate_mipmaps(alpha_coverage=...): one list per surface in [depth][face] order,

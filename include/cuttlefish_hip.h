@@ -397,6 +397,63 @@ int cfhip_alpha_bleed_array_device(cfhip_ctx* ctx, void* const* images, uint32_t
 	uint32_t width, uint32_t height, size_t pitch_bytes, const cfhip_bleed_params* params,
 	cfhip_bleed_result* results_device, void* stream);
 
+/* Signed distance field from alpha (Green, "Improved Alpha-Tested Magnification for Vector Textures and Special
+ * Effects", 2007): a high-resolution cut-out is classified, every texel's distance to the silhouette is measured, and
+ * the distance is stored at low resolution, scaled so that 0.5 is the edge.  Bilinear magnification then reconstructs a
+ * clean edge from a texture 8 or 16 times smaller per side.  The third tool for straight-alpha cut-outs, beside the
+ * coverage pass and alpha bleeding above.
+ *
+ *   input           `layers` source surfaces src[l] of one size width x height (1 to 32768 each) and one pixel type,
+ *                   rows src_pitch_bytes apart, only read.  alpha() as the coverage and bleed passes read it: RGBA8
+ *                   (float)(v / 255.0), RGBA16F half -> float, RGBA32F as stored.
+ *   class           texel p is inside iff alpha(p) > alpha_threshold, compared in float32, 0 <= alpha_threshold < 1.
+ *                   A NaN alpha is outside.
+ *   distance        spread: an integer, 1 to 126, in source texels; K = spread + 1.  For texel p,
+ *                   e(p) = min(K^2, min{dx^2 + dy^2 : q a texel of the other class}), dx = |px - qx|, on an axis wrapped
+ *                   by CFHIP_SDF_WRAP_X / _Y dx = min(dx, width - dx); the same for y.  Outside an unwrapped surface
+ *                   there are no texels; a surface of a single class has e = K^2 everywhere.  This is the true
+ *                   Euclidean transform between texel centres, capped at K -- not a flood.
+ *   signed distance rho(e) = (float)sqrt((double)e), both operations IEEE; sd(p) = rho - 0.5 inside, 0.5 - rho outside:
+ *                   the silhouette lies half-way between two centres.  Every sd is a multiple of 2^-23 below 2^7, so a
+ *                   double sum of up to 256 of them is exact in any order.
+ *   output          scale s in {1, 2, 4, 8, 16}; width and height are multiples of s.  Output texel (X, Y) takes
+ *                   m = (the sum of sd over its s x s source texels) / s^2 in double, which is exact, and
+ *                   v = 0.5 + m / (2.0 * spread) in double, clamped to [0, 1].  With K = spread + 1 a tile farther than
+ *                   the spread from the silhouette reaches exactly 0 or 1.
+ *   store           dst[l] is width/s x height/s texels of dst_pixel_type, rows dst_pitch_bytes apart.  channel_mask
+ *                   (bits R = 1, G = 2, B = 4, A = 8, not 0) names the components that receive v: RGBA8 takes
+ *                   (uint8)floor(v * 255 + 0.5), RGBA32F (float)v, RGBA16F (float)v rounded to half, nearest-even.  The
+ *                   other components are not written.  dst[l] may equal src[l] when s = 1 and the pixel types are
+ *                   equal: all alpha is read before anything is written.
+ *   results_device  one record per layer, or NULL for none: inside (source texels inside), saturated (source texels
+ *                   with e == K^2), two reserved zeros.  Sums: identical calls return identical bytes.
+ *
+ * All layers share every launch: a classify pass (one bit per texel), a row pass (each texel's capped distance within
+ * its row, from bit scans), a column pass (the windowed minimum of dy^2 + row distance^2, out of LDS) and, for s > 1, a
+ * resolve pass; at s = 1 the column pass stores v itself.  3 or 4 plain launches per call whatever the layers, spread or
+ * scale, on the call's stream; nothing waits for the host.  The scratch is the context's, grown on demand: per source
+ * texel one byte (row pass), two more for s > 1 (e), and one bit (the classes, whole 64-bit words per row) -- within
+ * 4 bytes per texel for widths from 8.  At most 2^31 source texels per call.  Pointers and pitches are aligned to a
+ * component of their pixel type.  Every argument is checked before anything is enqueued; stream == NULL means the
+ * context's stream and the call synchronises. */
+enum { CFHIP_SDF_WRAP_X = 1, CFHIP_SDF_WRAP_Y = 2 };
+typedef struct cfhip_sdf_params {
+	uint32_t flags;
+	float alpha_threshold;
+	uint32_t spread;
+	uint32_t scale;
+	uint32_t channel_mask;
+	uint32_t reserved;
+} cfhip_sdf_params;
+typedef struct cfhip_sdf_result {
+	uint32_t inside;
+	uint32_t saturated;
+	uint32_t reserved[2];
+} cfhip_sdf_result;
+int cfhip_alpha_sdf_array_device(cfhip_ctx* ctx, const void* const* src, uint32_t layers, int src_pixel_type,
+	uint32_t width, uint32_t height, size_t src_pitch_bytes, void* const* dst, int dst_pixel_type,
+	size_t dst_pitch_bytes, const cfhip_sdf_params* params, cfhip_sdf_result* results_device, void* stream);
+
 /* One Image::resize on the GPU (lib/src/Image.cpp:1324-1511) -- what Texture::generateMipmaps calls
  * per level, and per custom mip image (Texture.cpp:1499-1503, any source size): src (any of the
  * three pixel types) -> dst, dst_width x dst_height tightly packed RGBA32F, in linear space as
@@ -1159,7 +1216,7 @@ int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* p
 	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass), cfhip_alpha_coverage_device or cfhip_alpha_bleed_array_device (every pass) call on
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass), cfhip_alpha_coverage_device, cfhip_alpha_bleed_array_device or cfhip_alpha_sdf_array_device (every pass) call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
