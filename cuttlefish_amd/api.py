@@ -205,7 +205,9 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_lz4_decode", "cfhip_lz4_decode_device", "cfhip_lz4_decode_stage_ms",
            "cfhip_png_bound", "cfhip_png_encode", "cfhip_png_encode_device", "cfhip_png_stage_ms",
            "cfhip_mip_post_array_device", "cfhip_alpha_coverage_device", "cfhip_alpha_bleed_array_device",
-           "cfhip_alpha_sdf_array_device"]
+           "cfhip_alpha_sdf_array_device",
+           "cfhip_equirect_to_cube_device", "cfhip_ggx_sample_table", "cfhip_cube_prefilter_device",
+           "cfhip_cube_sh9_device"]
 
 
 class Layout(enum.IntEnum):
@@ -588,6 +590,68 @@ def make_sdf_params(spread: int, scale: int = 1, threshold: float = 0.5, wrap=(F
                      sdf_channel_mask(channels), 0)
 
 
+# ---- environment maps (cfhip_equirect_to_cube_device, cfhip_cube_prefilter_device, cfhip_cube_sh9_device) ----
+ENV_MAX_FACE = 8192
+ENV_MAX_PANORAMA = 32768
+ENV_SUPERSAMPLES = (1, 2, 4)
+ENV_MIN_SAMPLES, ENV_MAX_SAMPLES = 64, 4096
+
+
+class GgxSample(ctypes.Structure):
+    """cfhip_ggx_sample: a tangent-space light direction (lz is also its weight) and a source level of detail"""
+    _fields_ = [("lx", ctypes.c_float), ("ly", ctypes.c_float), ("lz", ctypes.c_float), ("lod", ctypes.c_float)]
+
+
+class Sh9Result(ctypes.Structure):
+    """cfhip_sh9_result: 9 coefficients x RGBA, normalised, then the sum of the texels' solid angles"""
+    _fields_ = [("coeff", (ctypes.c_double*4)*9), ("solid_angle", ctypes.c_double)]
+
+
+def cube_level_count(face_size: int) -> int:
+    """the levels of a full chain: sizes face_size >> k down to 1"""
+    return int(face_size).bit_length()
+
+
+def ggx_sample_table(roughness: float, samples: int, face_size: int, source_levels: int) -> np.ndarray:
+    """cfhip_ggx_sample_table -> (samples, 4) float32 records (lx, ly, lz, lod) for one destination level of
+    cube_prefilter_device: `samples` Hammersley points (a multiple of 64 from 64 to 4096) through the GGX distribution
+    of `roughness` (0 < roughness <= 1; 0 is a copy and has no table), the level of detail chosen per sample from its
+    density for a source cube of face_size with source_levels levels.  Host only: no context, no device."""
+    r = float(roughness)
+    if isinstance(samples, (bool, np.bool_)) or not isinstance(samples, (int, np.integer)) or samples % 64 \
+            or not ENV_MIN_SAMPLES <= samples <= ENV_MAX_SAMPLES:
+        raise ValueError("samples %r: a multiple of 64 from %d to %d" % (samples, ENV_MIN_SAMPLES, ENV_MAX_SAMPLES))
+    if not (0.0 < r <= 1.0):
+        raise ValueError("roughness %r outside (0, 1]: roughness 0 is a copy and has no table" % (roughness,))
+    if not 1 <= int(face_size) <= ENV_MAX_FACE or not 1 <= int(source_levels) <= cube_level_count(face_size):
+        raise ValueError("face_size %r with source_levels %r" % (face_size, source_levels))
+    out = np.empty((int(samples), 4), np.float32)
+    rc = load_library().cfhip_ggx_sample_table(r, int(samples), int(face_size), int(source_levels),
+                                               out.ctypes.data_as(ctypes.POINTER(GgxSample)))
+    if rc != 0:
+        raise ValueError("cfhip_ggx_sample_table refused (%r, %r, %r, %r)" % (roughness, samples, face_size, source_levels))
+    return out
+
+
+# the real basis in the order 1, y, z, x, xy, yz, 3z^2 - 1, xz, x^2 - y^2 (csrc/envmap.h)
+SH_C0, SH_C1, SH_C2 = 0.28209479177387814, 0.4886025119029199, 1.0925484305920792
+SH_C20, SH_C22 = 0.31539156525252005, 0.5462742152960396
+
+
+def sh9_irradiance(coeffs, directions) -> np.ndarray:
+    """The diffuse term from the nine coefficients of Context.cube_sh9: each band times its cosine-lobe factor (pi,
+    2 pi / 3, pi / 4), evaluated at unit `directions` (..., 3) -> (..., C) for coeffs of shape (9, C)."""
+    d = np.asarray(directions, np.float64)
+    k = np.asarray(coeffs, np.float64)
+    if k.ndim != 2 or k.shape[0] != 9 or d.shape[-1] != 3:
+        raise ValueError("expected coeffs (9, C) and directions (..., 3)")
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+    basis = [SH_C0*np.ones_like(x), SH_C1*y, SH_C1*z, SH_C1*x, SH_C2*(x*y), SH_C2*(y*z), SH_C20*(3.0*(z*z) - 1.0),
+             SH_C2*(x*z), SH_C22*(x*x - y*y)]
+    band = [np.pi] + [2.0*np.pi/3.0]*3 + [np.pi/4.0]*5
+    return sum((band[b]*basis[b])[..., None]*k[b] for b in range(9))
+
+
 RDO_NO_CAP = 0xFFFFFFFF         # max_sse_increase: no cap
 RDO_ROW_ABOVE = 1               # CFHIP_RDO_ROW_ABOVE
 
@@ -711,6 +775,21 @@ def load_library(path: Optional[str] = None):
         ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_size_t,
         ctypes.POINTER(SdfParams), ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_alpha_sdf_array_device.restype = ctypes.c_int
+    L.cfhip_equirect_to_cube_device.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+    L.cfhip_equirect_to_cube_device.restype = ctypes.c_int
+    L.cfhip_ggx_sample_table.argtypes = [ctypes.c_float, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                         ctypes.POINTER(GgxSample)]
+    L.cfhip_ggx_sample_table.restype = ctypes.c_int
+    L.cfhip_cube_prefilter_device.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_uint32,
+        ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(ctypes.c_void_p),
+        ctypes.POINTER(ctypes.c_uint32), ctypes.c_void_p]
+    L.cfhip_cube_prefilter_device.restype = ctypes.c_int
+    L.cfhip_cube_sh9_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32,
+                                        ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_cube_sh9_device.restype = ctypes.c_int
     L.cfhip_generate_mips3d_device.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
         ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
@@ -1327,6 +1406,114 @@ class Context:
         rec = res.cpu().numpy().view(SDF_RESULT_DTYPE)[0]
         return (out.cpu().numpy().view(out_dtype).reshape(h//scale, w//scale, 4),
                 {k: int(rec[k]) for k in rec.dtype.names})
+
+    def equirect_to_cube_device(self, src: int, pixel_type, width: int, height: int, row_pitch_bytes: int,
+                                faces: Sequence[int], face_size: int, supersample: int = 2, stream: int = 0):
+        """An equirectangular panorama onto the six faces of a cube (cfhip_equirect_to_cube_device): src is one
+        width x height device surface of any pixel type, read without a colour-space change; faces are six device
+        pointers in CubeFace order, each face_size^2 tightly packed RGBA32F.  Every texel averages supersample^2 (1, 2
+        or 4 per axis) bilinear fetches, x wrapped and y clamped; the panorama's centre column looks along +Z, its top
+        row along +Y.  One launch."""
+        if len(faces) != 6:
+            raise ValueError("faces must list the six faces in CubeFace order")
+        arr = (ctypes.c_void_p * 6)(*[ctypes.c_void_p(int(p)) for p in faces])
+        self._check(self._lib.cfhip_equirect_to_cube_device(
+            self._h, ctypes.c_void_p(int(src)), int(pixel_type), width, height, row_pitch_bytes, arr, face_size,
+            supersample, ctypes.c_void_p(stream) if stream else None))
+
+    def equirect_to_cube(self, image: np.ndarray, face_size: int, supersample: int = 2) -> List[np.ndarray]:
+        """Host convenience: one (h, w, 4) uint8 / float16 / float32 panorama through equirect_to_cube_device -> the six
+        (face_size, face_size, 4) float32 faces in CubeFace order."""
+        import torch
+        host = np.ascontiguousarray(image)
+        if host.ndim != 3 or host.shape[2] != 4:
+            raise ValueError("expected (h, w, 4)")
+        if supersample not in ENV_SUPERSAMPLES:
+            raise ValueError("supersample %r: one of %r" % (supersample, ENV_SUPERSAMPLES))
+        if not 1 <= int(face_size) <= ENV_MAX_FACE:
+            raise ValueError("face_size %r outside 1 to %d" % (face_size, ENV_MAX_FACE))
+        n = int(face_size)
+        dev = torch.from_numpy(host.view(np.uint8)).to("cuda:%d" % self.device_id)
+        out = torch.empty((6, n, n, 4), dtype=torch.float32, device=dev.device)
+        self.equirect_to_cube_device(dev.data_ptr(), pixel_type_of(host), host.shape[1], host.shape[0], host.strides[0],
+                                     [out[f].data_ptr() for f in range(6)], n, int(supersample))
+        faces = out.cpu().numpy()
+        return [faces[f] for f in range(6)]
+
+    def cube_prefilter_device(self, src_levels: Sequence[Sequence[int]], face_size: int,
+                              dst_levels: Sequence[Sequence[int]], tables: Sequence, stream: int = 0):
+        """The GGX-prefiltered chain of a cube (cfhip_cube_prefilter_device).  src_levels[f][l]: device pointers of the
+        cube's RGBA32F chain as generate_mips_array_device with the Box filter leaves it, level l of size
+        max(1, face_size >> l); dst_levels[f][k]: where destination level k of that size goes.  tables[k]: the
+        (S, 4) float32 records of ggx_sample_table for level k -- S a multiple of 64 from 64 to 4096 -- or None for a
+        copy of source level k (roughness 0).  One launch per destination level for the six faces."""
+        if len(src_levels) != 6 or len(dst_levels) != 6 or len({len(s) for s in src_levels}) != 1 \
+                or len({len(d) for d in dst_levels}) != 1:
+            raise ValueError("src_levels and dst_levels list six faces, every face the same levels")
+        L, K = len(src_levels[0]), len(dst_levels[0])
+        if len(tables) != K:
+            raise ValueError("one table (or None) per destination level")
+        keep = [None if t is None or len(t) == 0 else np.ascontiguousarray(t, dtype=np.float32) for t in tables]
+        for t in keep:
+            if t is not None and (t.ndim != 2 or t.shape[1] != 4):
+                raise ValueError("a table is (S, 4) float32: lx, ly, lz, lod")
+        sarr = (ctypes.c_void_p * max(6*L, 1))(*[ctypes.c_void_p(int(p)) for s in src_levels for p in s])
+        darr = (ctypes.c_void_p * max(6*K, 1))(*[ctypes.c_void_p(int(p)) for d in dst_levels for p in d])
+        tarr = (ctypes.c_void_p * max(K, 1))(*[ctypes.c_void_p(t.ctypes.data) if t is not None else None for t in keep])
+        counts = (ctypes.c_uint32 * max(K, 1))(*[0 if t is None else t.shape[0] for t in keep])
+        self._check(self._lib.cfhip_cube_prefilter_device(
+            self._h, sarr, face_size, L, darr, K, tarr, counts, ctypes.c_void_p(stream) if stream else None))
+
+    def cube_prefilter(self, faces: Sequence[np.ndarray], roughness: Sequence[float], samples: int = 256):
+        """Host convenience: six (n, n, 4) float32 faces in CubeFace order -> one (6, n_k, n_k, 4) float32 array per entry
+        of `roughness`, n_k = max(1, n >> k): the full Box chain of the faces is built on the device, then level k is the
+        environment under a GGX lobe of roughness[k] from `samples` samples; a roughness of 0 copies the Box level."""
+        import torch
+        stack = np.ascontiguousarray(np.stack([np.asarray(f) for f in faces]), dtype=np.float32)
+        if stack.ndim != 4 or stack.shape[0] != 6 or stack.shape[1] != stack.shape[2] or stack.shape[3] != 4:
+            raise ValueError("expected six (n, n, 4) faces")
+        n = stack.shape[1]
+        L, K = cube_level_count(n), len(roughness)
+        if not 1 <= K <= L:
+            raise ValueError("%d levels asked of a face of %d: 1 to %d" % (K, n, L))
+        tables = [None if float(r) == 0.0 else ggx_sample_table(r, samples, n, L) for r in roughness]
+        device = "cuda:%d" % self.device_id
+        chain = [torch.from_numpy(stack).to(device)]
+        chain += [torch.empty((6, max(1, n >> l), max(1, n >> l), 4), dtype=torch.float32, device=device) for l in range(1, L)]
+        if L > 1:
+            self.generate_mips_array_device([chain[0][f].data_ptr() for f in range(6)], PixelType.RGBA32F, n, n, n*16,
+                                            [[chain[l][f].data_ptr() for l in range(1, L)] for f in range(6)],
+                                            color_space=ColorSpace.Linear, filter=int(ResizeFilter.Box))
+        out = [torch.empty_like(chain[k]) for k in range(K)]
+        self.cube_prefilter_device([[chain[l][f].data_ptr() for l in range(L)] for f in range(6)], n,
+                                   [[out[k][f].data_ptr() for k in range(K)] for f in range(6)], tables)
+        return [o.cpu().numpy() for o in out]
+
+    def cube_sh9_device(self, faces: Sequence[int], face_size: int, result: int, stream: int = 0):
+        """The projection of a cube on nine spherical-harmonic coefficients (cfhip_cube_sh9_device): faces are six
+        device pointers in CubeFace order, each face_size^2 tightly packed RGBA32F; result: device pointer to one
+        cfhip_sh9_result, 37 float64 -- coefficient b, channel c at [4 b + c], normalised by 4 pi over the summed
+        solid angle, then that sum.  Two launches; identical calls give identical bytes."""
+        if len(faces) != 6:
+            raise ValueError("faces must list the six faces in CubeFace order")
+        arr = (ctypes.c_void_p * 6)(*[ctypes.c_void_p(int(p)) for p in faces])
+        self._check(self._lib.cfhip_cube_sh9_device(
+            self._h, arr, face_size, ctypes.c_void_p(int(result)) if result else None,
+            ctypes.c_void_p(stream) if stream else None))
+
+    def cube_sh9(self, faces: Sequence[np.ndarray]):
+        """Host convenience: six (n, n, 4) float32 faces -> (the (9, 4) float64 coefficients in the order 1, y, z, x, xy,
+        yz, 3z^2 - 1, xz, x^2 - y^2, the summed solid angle).  sh9_irradiance() evaluates the diffuse term from them."""
+        import torch
+        stack = np.ascontiguousarray(np.stack([np.asarray(f) for f in faces]), dtype=np.float32)
+        if stack.ndim != 4 or stack.shape[0] != 6 or stack.shape[1] != stack.shape[2] or stack.shape[3] != 4:
+            raise ValueError("expected six (n, n, 4) faces")
+        n = stack.shape[1]
+        dev = torch.from_numpy(stack).to("cuda:%d" % self.device_id)
+        res = torch.zeros(37, dtype=torch.float64, device=dev.device)
+        self.cube_sh9_device([dev[f].data_ptr() for f in range(6)], n, res.data_ptr())
+        rec = res.cpu().numpy()
+        return rec[:36].reshape(9, 4).copy(), float(rec[36])
 
     def generate_mips3d_device(self, src: int, pixel_type, width: int, height: int, depth: int,
                                row_pitch_bytes: int, slice_pitch_bytes: int, dst_levels: Sequence[int],

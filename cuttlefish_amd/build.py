@@ -168,7 +168,10 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  "cfhip_alpha_bleed_seed_kernel", "cfhip_alpha_bleed_step_kernel", "cfhip_alpha_bleed_fill_kernel",
                  # the signed distance field from alpha (csrc/alpha_sdf.hip): classes, row distances, columns, tiles
                  "cfhip_alpha_sdf_classify_kernel", "cfhip_alpha_sdf_row_kernel", "cfhip_alpha_sdf_column_kernel",
-                 "cfhip_alpha_sdf_resolve_kernel")
+                 "cfhip_alpha_sdf_resolve_kernel",
+                 # environment maps (csrc/envmap.hip): panorama to cube, the GGX chain and its copy, the SH9 rows and sum
+                 "cfhip_equirect_to_cube_kernel", "cfhip_cube_prefilter_kernel", "cfhip_cube_copy_kernel",
+                 "cfhip_cube_sh9_rows_kernel", "cfhip_cube_sh9_final_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

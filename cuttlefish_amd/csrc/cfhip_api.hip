@@ -19,6 +19,7 @@
 #include "mip_post.h"
 #include "alpha_bleed.h"
 #include "alpha_sdf.h"
+#include "envmap.h"
 #include "stage_log.h"
 #include "../../include/cuttlefish_hip.h"
 
@@ -2529,6 +2530,262 @@ int cfhip_alpha_sdf_array_device(cfhip_ctx* ctx, const void* const* src, uint32_
 			rc = sdf([&] { return cfhip_launch_alpha_sdf_column(&call, layers, rows, e, results_device, stream); });
 		if (rc == CFHIP_OK && s > 1u)
 			rc = sdf([&] { return cfhip_launch_alpha_sdf_resolve(&call, layers, e, stream); });
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
+}
+
+// ---- environment maps (csrc/envmap.hip): panorama to cube, the GGX chain, nine SH coefficients ------------------------
+static uint32_t cube_levels(uint32_t face_size)
+{
+	uint32_t levels = 0;
+	for (; face_size; face_size >>= 1)
+		++levels;
+	return levels;
+}
+
+static int check_faces(cfhip_ctx* ctx, const char* what, const void* const* faces, uint32_t face_size)
+{
+	if (!faces)
+		return fail(ctx, CFHIP_E_INVALID, "%s: faces is NULL", what);
+	if (!face_size || face_size > CFENV_MAX_FACE)
+		return fail(ctx, CFHIP_E_INVALID, "%s: face_size is 1 to %u, not %u", what, CFENV_MAX_FACE, face_size);
+	for (uint32_t f = 0; f < 6u; ++f) {
+		if (!faces[f])
+			return fail(ctx, CFHIP_E_INVALID, "%s: faces[%u] is NULL", what, f);
+		if ((uintptr_t)faces[f] % 16u)
+			return fail(ctx, CFHIP_E_INVALID, "%s: faces[%u] not aligned to a texel (16 bytes)", what, f);
+	}
+	return CFHIP_OK;
+}
+
+int cfhip_equirect_to_cube_device(cfhip_ctx* ctx, const void* src, int src_pixel_type, uint32_t width, uint32_t height,
+	size_t src_pitch_bytes, void* const* faces, uint32_t face_size, uint32_t supersample, void* stream_)
+{
+	return guarded(ctx, "equirect_to_cube", [&]() -> int {
+		if (!src)
+			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: src is NULL");
+		if (width < 2u || !height || width > CFENV_MAX_PANORAMA || height > CFENV_MAX_PANORAMA)
+			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: width is 2 to %u and height 1 to %u, not %ux%u", CFENV_MAX_PANORAMA,
+				CFENV_MAX_PANORAMA, width, height);
+		const size_t spb = pixel_bytes(src_pixel_type);
+		if (!spb)
+			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: src_pixel_type %d", src_pixel_type);
+		if (src_pitch_bytes < (size_t)width*spb)
+			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: src_pitch_bytes %zu < %zu, a row", src_pitch_bytes, (size_t)width*spb);
+		if (src_pitch_bytes % (spb/4u))
+			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: src_pitch_bytes %zu not aligned to a component (%zu bytes)",
+				src_pitch_bytes, spb/4u);
+		if ((uintptr_t)src % (spb/4u))
+			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: src not aligned to a component (%zu bytes)", spb/4u);
+		if (supersample != 1u && supersample != 2u && supersample != 4u)
+			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: supersample %u is not 1, 2 or 4", supersample);
+		int rc = check_faces(ctx, "equirect_to_cube", faces, face_size);
+		if (rc != CFHIP_OK)
+			return rc;
+		for (uint32_t f = 0; f < 6u; ++f)
+			if (faces[f] == src)
+				return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: faces[%u] equals src", f);
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		const hipStream_t stream = lease.stream;
+		begin_call(ctx, stream, "cfhip_equirect_to_cube_kernel");
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, 6u*sizeof(void*));
+		if (rc != CFHIP_OK)
+			return rc;
+		void** table = static_cast<void**>(ctx->d_batch);
+		HIP_TRY(ctx, hipMemcpyAsync(table, faces, 6u*sizeof(void*), hipMemcpyHostToDevice, stream));
+		rc = timed(ctx, stream, "equirect_to_cube", [&] {
+			return cfhip_launch_equirect_to_cube(src, src_pixel_type, width, height, src_pitch_bytes, table, face_size, supersample,
+				stream);
+		});
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
+}
+
+int cfhip_ggx_sample_table(float roughness, uint32_t samples, uint32_t face_size, uint32_t source_levels, cfhip_ggx_sample* out)
+{
+	if (!out || !(roughness > 0.0f && roughness <= 1.0f))
+		return CFHIP_E_INVALID;
+	if (samples % 64u || samples < CFENV_MIN_SAMPLES || samples > CFENV_MAX_SAMPLES)
+		return CFHIP_E_INVALID;
+	if (!face_size || face_size > CFENV_MAX_FACE || !source_levels || source_levels > cube_levels(face_size))
+		return CFHIP_E_INVALID;
+	const double S = (double)samples, N = (double)face_size, r = (double)roughness;
+	const double a = r*r, a2 = a*a;
+	for (uint32_t i = 0; i < samples; ++i) {
+		uint32_t bits = i;
+		bits = (bits << 16) | (bits >> 16);
+		bits = ((bits & 0x00FF00FFu) << 8) | ((bits & 0xFF00FF00u) >> 8);
+		bits = ((bits & 0x0F0F0F0Fu) << 4) | ((bits & 0xF0F0F0F0u) >> 4);
+		bits = ((bits & 0x33333333u) << 2) | ((bits & 0xCCCCCCCCu) >> 2);
+		bits = ((bits & 0x55555555u) << 1) | ((bits & 0xAAAAAAAAu) >> 1);
+		const double xi1 = ((double)i + 0.5)/S, xi2 = (double)bits*0x1p-32;
+		const double cos2 = (1.0 - xi1)/(1.0 + (a2 - 1.0)*xi1);
+		const double hz = std::sqrt(cos2), sine = std::sqrt(1.0 - cos2), phi = (2.0*CFENV_PI)*xi2;
+		const double hx = sine*std::cos(phi), hy = sine*std::sin(phi);
+		const double lx = (2.0*hz)*hx, ly = (2.0*hz)*hy;
+		double lz = (2.0*hz)*hz - 1.0;
+		const double e = (hz*hz)*(a2 - 1.0) + 1.0;
+		const double pdf = (a2/(CFENV_PI*(e*e)))/4.0;
+		double lod = 0.5*std::log2((1.0/(S*pdf))/((4.0*CFENV_PI)/(6.0*(N*N)))) + 1.0;
+		lod = std::fmin(std::fmax(lod, 0.0), (double)(source_levels - 1u));
+		if (lz <= 0.0) {
+			lz = 0.0;
+			lod = 0.0;
+		}
+		out[i].lx = (float)lx; out[i].ly = (float)ly; out[i].lz = (float)lz; out[i].lod = (float)lod;
+	}
+	return CFHIP_OK;
+}
+
+int cfhip_cube_prefilter_device(cfhip_ctx* ctx, const void* const* src_levels, uint32_t face_size, uint32_t source_levels,
+	void* const* dst_levels, uint32_t dst_count, const cfhip_ggx_sample* const* tables, const uint32_t* table_samples,
+	void* stream_)
+{
+	static_assert(sizeof(cfhip_ggx_sample) == 16 && sizeof(cfhip_sh9_result) == 296, "the ABI's sizes");
+	return guarded(ctx, "cube_prefilter", [&]() -> int {
+		if (!src_levels)
+			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: src_levels is NULL");
+		if (!dst_levels)
+			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: dst_levels is NULL");
+		if (!tables)
+			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: tables is NULL");
+		if (!table_samples)
+			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: table_samples is NULL");
+		if (!face_size || face_size > CFENV_MAX_FACE)
+			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: face_size is 1 to %u, not %u", CFENV_MAX_FACE, face_size);
+		const uint32_t full = cube_levels(face_size);
+		if (!source_levels || source_levels > full)
+			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: source_levels is 1 to %u for a face of %u, not %u", full, face_size,
+				source_levels);
+		if (!dst_count || dst_count > full)
+			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: dst_count is 1 to %u for a face of %u, not %u", full, face_size, dst_count);
+		for (uint32_t i = 0; i < 6u*source_levels; ++i) {
+			if (!src_levels[i])
+				return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: src_levels[%u][%u] is NULL", i/source_levels, i%source_levels);
+			if ((uintptr_t)src_levels[i] % 16u)
+				return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: src_levels[%u][%u] not aligned to a texel (16 bytes)", i/source_levels,
+					i%source_levels);
+		}
+		for (uint32_t i = 0; i < 6u*dst_count; ++i) {
+			if (!dst_levels[i])
+				return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: dst_levels[%u][%u] is NULL", i/dst_count, i%dst_count);
+			if ((uintptr_t)dst_levels[i] % 16u)
+				return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: dst_levels[%u][%u] not aligned to a texel (16 bytes)", i/dst_count,
+					i%dst_count);
+			for (uint32_t j = 0; j < 6u*source_levels; ++j)
+				if (dst_levels[i] == src_levels[j])
+					return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: dst_levels[%u][%u] equals src_levels[%u][%u]", i/dst_count,
+						i%dst_count, j/source_levels, j%source_levels);
+		}
+		size_t records = 0;
+		for (uint32_t k = 0; k < dst_count; ++k) {
+			const uint32_t S = table_samples[k];
+			if (!S) {
+				if (k >= source_levels)
+					return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: table_samples[%u] is 0, a copy, but there are %u source levels", k,
+						source_levels);
+				continue;
+			}
+			if (S % 64u || S < CFENV_MIN_SAMPLES || S > CFENV_MAX_SAMPLES)
+				return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: table_samples[%u] is %u, not 0 or a multiple of 64 from %u to %u", k, S,
+					CFENV_MIN_SAMPLES, CFENV_MAX_SAMPLES);
+			if (!tables[k])
+				return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: tables[%u] is NULL", k);
+			for (uint32_t i = 0; i < S; ++i) {
+				const cfhip_ggx_sample& r = tables[k][i];
+				if (!(std::isfinite(r.lx) && std::isfinite(r.ly) && r.lz >= 0.0f && std::isfinite(r.lz) && r.lod >= 0.0f &&
+					  r.lod <= (float)CFENV_MAX_LEVELS))
+					return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: tables[%u][%u] is not finite with lz >= 0 and 0 <= lod <= %u", k, i,
+						CFENV_MAX_LEVELS);
+			}
+			records += S;
+		}
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		const hipStream_t stream = lease.stream;
+		begin_call(ctx, stream, "cfhip_cube_prefilter_kernel");
+		// d_batch: the source chain's pointers, then the destination's.  d_src: the levels' tables, one after the other
+		const size_t ns = 6u*(size_t)source_levels, nd = 6u*(size_t)dst_count;
+		int rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, (ns + nd)*sizeof(void*));
+		if (rc == CFHIP_OK && records)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, records*sizeof(cfhip_ggx_sample));
+		if (rc != CFHIP_OK)
+			return rc;
+		// pageable sources: the runtime stages the copies before returning
+		void** table = static_cast<void**>(ctx->d_batch);
+		HIP_TRY(ctx, hipMemcpyAsync(table, src_levels, ns*sizeof(void*), hipMemcpyHostToDevice, stream));
+		HIP_TRY(ctx, hipMemcpyAsync(table + ns, dst_levels, nd*sizeof(void*), hipMemcpyHostToDevice, stream));
+		cfhip_ggx_sample* d_tables = static_cast<cfhip_ggx_sample*>(ctx->d_src);
+		size_t at = 0;
+		for (uint32_t k = 0; k < dst_count; ++k)
+			if (table_samples[k]) {
+				HIP_TRY(ctx, hipMemcpyAsync(d_tables + at, tables[k], (size_t)table_samples[k]*sizeof(cfhip_ggx_sample),
+					hipMemcpyHostToDevice, stream));
+				at += table_samples[k];
+			}
+		cfenv_prefilter_call call;
+		call.src = table;
+		call.dst = table + ns;
+		call.face_size = face_size; call.src_levels = source_levels; call.dst_levels = dst_count;
+		at = 0;
+		// every level is a timed span of its own
+		for (uint32_t k = 0; k < dst_count; ++k) {
+			call.level = k;
+			call.samples = table_samples[k];
+			call.table = d_tables + at;
+			at += table_samples[k];
+			rc = timed(ctx, stream, "cube_prefilter", [&] { return cfhip_launch_cube_prefilter(&call, stream); });
+			if (rc != CFHIP_OK)
+				return rc;
+		}
+		return lease.done(!stream_);
+	});
+}
+
+int cfhip_cube_sh9_device(cfhip_ctx* ctx, const void* const* faces, uint32_t face_size, cfhip_sh9_result* result_device,
+	void* stream_)
+{
+	return guarded(ctx, "cube_sh9", [&]() -> int {
+		int rc = check_faces(ctx, "cube_sh9", faces, face_size);
+		if (rc != CFHIP_OK)
+			return rc;
+		if (!result_device)
+			return fail(ctx, CFHIP_E_INVALID, "cube_sh9: result_device is NULL");
+		if ((uintptr_t)result_device % 8u)
+			return fail(ctx, CFHIP_E_INVALID, "cube_sh9: result_device not aligned to 8 bytes");
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		const hipStream_t stream = lease.stream;
+		begin_call(ctx, stream, "cfhip_cube_sh9_rows_kernel");
+		// d_batch: the six pointers.  d_src: a record of 37 doubles per face row
+		rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, 6u*sizeof(void*));
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, 6u*(size_t)face_size*CFENV_SH_VALUES*sizeof(double));
+		if (rc != CFHIP_OK)
+			return rc;
+		void** table = static_cast<void**>(ctx->d_batch);
+		HIP_TRY(ctx, hipMemcpyAsync(table, faces, 6u*sizeof(void*), hipMemcpyHostToDevice, stream));
+		double* rows = static_cast<double*>(ctx->d_src);
+		rc = timed(ctx, stream, "cube_sh9", [&] { return cfhip_launch_cube_sh9_rows(table, face_size, rows, stream); });
+		if (rc == CFHIP_OK)
+			rc = timed(ctx, stream, "cube_sh9", [&] { return cfhip_launch_cube_sh9_final(rows, face_size, result_device, stream); });
 		if (rc != CFHIP_OK)
 			return rc;
 		return lease.done(!stream_);

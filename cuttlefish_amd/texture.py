@@ -149,6 +149,13 @@ def _as_image(image) -> Optional[np.ndarray]:
     return image
 
 
+def _as_float32(image: np.ndarray) -> np.ndarray:
+    """an image's texels as the kernels read them: uint8 as (float)(v / 255.0), float16 widened, float32 as stored"""
+    if image.dtype == np.uint8:
+        return (image.astype(np.float64)/255.0).astype(np.float32)
+    return image.astype(np.float32, copy=False)
+
+
 class Texture:
     allMipLevels = 0xFFFFFFFF   # Texture::allMipLevels (Texture.h:405)
     allCores = 0xFFFFFFFF       # Texture::allCores (:410); a thread count is meaningless on the GPU path
@@ -710,6 +717,64 @@ class Texture:
         mip, depth, face, inside (texels inside) and saturated (texels farther than the spread from the silhouette); []
         before any call."""
         return [dict(r) for r in self._sdf]
+
+    # ---- environment maps (Context.equirect_to_cube / cube_prefilter / cube_sh9) ------------------------------------
+    @staticmethod
+    def from_panorama(image, face_size: int, supersample: int = 2, color_space: ColorSpace = ColorSpace.Linear,
+                      device_id: int = 0) -> Optional["Texture"]:
+        """A Dimension.Cube texture of face_size^2 faces with level 0 set from an equirectangular panorama (an
+        (h, w, 4) uint8 / float16 / float32 array or an Image), resampled on the GPU with supersample^2 fetches per texel.
+        The texels are read as stored; color_space only names the space of the texture made.  The panorama's centre
+        column looks along +Z and its top row along +Y.  None for what is no image."""
+        pixels = _as_image(getattr(image, "pixels", image))
+        if pixels is None:
+            return None
+        t = Texture(Dimension.Cube, int(face_size), int(face_size), 0, 1, color_space, device_id=device_id)
+        if not t.is_valid():
+            return None
+        for f, face in enumerate(t._context().equirect_to_cube(pixels, int(face_size), supersample)):
+            t.set_image(face, CubeFace(f), 0)
+        return t
+
+    def _cube_faces(self) -> Optional[List[np.ndarray]]:
+        """level 0 of a cube that is not an array, not converted and has its six faces; else None"""
+        if not self._valid or self._textures or self._dim != Dimension.Cube or self._depth > 0 or self._w != self._h:
+            return None
+        faces = self._images[0][0]
+        if any(im is None for im in faces):
+            return None
+        return [_as_float32(im) for im in faces]
+
+    def prefilter_environment(self, mip_levels: Optional[int] = None, samples: int = 256,
+                              roughness: Optional[Sequence[float]] = None) -> bool:
+        """The specular chain of an environment cube in place of generate_mipmaps: level k becomes level 0 convolved
+        with a GGX lobe of roughness r_k (Context.cube_prefilter: a Box chain on the device, then `samples` samples per
+        texel, a multiple of 64 from 64 to 4096).  mip_levels: all by default; roughness: one value in [0, 1] per level,
+        by default r_k = k / (K - 1), 0 -- a copy -- for a single level.  The levels are RGBAF (float32) images.  False,
+        before any device work, for a texture that is no cube, is an array, is converted or lacks a face of level 0."""
+        faces = self._cube_faces()
+        if faces is None:
+            return False
+        full = api.cube_level_count(self._w)
+        levels = full if mip_levels is None else min(max(int(mip_levels), 1), full)
+        if roughness is None:
+            roughness = [0.0] if levels == 1 else [k/float(levels - 1) for k in range(levels)]
+        roughness = [float(r) for r in roughness]
+        if len(roughness) != levels or any(not (0.0 <= r <= 1.0) for r in roughness):
+            return False
+        chain = self._context().cube_prefilter(faces, roughness, samples)
+        self._mips = levels
+        self._images = [[[chain[k][f] for f in range(6)]] for k in range(levels)]
+        return True
+
+    def irradiance_sh9(self) -> Optional[np.ndarray]:
+        """The nine spherical-harmonic coefficients of level 0 of an environment cube, (9, 4) float64 in the order 1, y,
+        z, x, xy, yz, 3z^2 - 1, xz, x^2 - y^2 (Context.cube_sh9); api.sh9_irradiance evaluates the diffuse term from
+        them.  None where prefilter_environment returns False."""
+        faces = self._cube_faces()
+        if faces is None:
+            return None
+        return self._context().cube_sh9(faces)[0]
 
     def mip_post_results(self):
         """The records of the last generate_mipmaps(alpha_coverage=...): one list per surface in [depth][face] order,

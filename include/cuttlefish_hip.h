@@ -454,6 +454,85 @@ int cfhip_alpha_sdf_array_device(cfhip_ctx* ctx, const void* const* src, uint32_
 	uint32_t width, uint32_t height, size_t src_pitch_bytes, void* const* dst, int dst_pixel_type,
 	size_t dst_pitch_bytes, const cfhip_sdf_params* params, cfhip_sdf_result* results_device, void* stream);
 
+/* Environment maps for image-based lighting: an equirectangular panorama onto the six faces of a cube, the cube's
+ * GGX-prefiltered mip chain (level k = the environment convolved with a lobe of roughness r_k), and its projection on
+ * nine spherical-harmonic coefficients (the diffuse term).  Every formula below is a sequence of IEEE double operations
+ * in the order written (the library is built without contraction), so results are defined to the bit -- but for atan2
+ * and asin of the panorama pass and cos, sin and log2 of the table helper, which are the math library's.
+ *
+ *   faces           CubeFace order +X, -X, +Y, -Y, +Z, -Z; a face is n x n texels (x, y), y downward, tightly packed
+ *                   RGBA32F, 16-byte aligned.  s = 2 (x + 0.5) / n - 1, t = 2 (y + 0.5) / n - 1.
+ *   d(f, s, t)      +X (1, -t, -s)   -X (-1, -t, s)   +Y (s, 1, t)   -Y (s, -1, -t)   +Z (s, -t, 1)   -Z (-s, -t, -1);
+ *                   |d|^2 = (dx^2 + dy^2) + dz^2, n^ = d / sqrt(|d|^2) component by component.
+ *   to a face       the major axis of a direction is X if |x| >= |y| and |x| >= |z|, else Y if |y| >= |z|, else Z; a
+ *                   negative major component picks the -face.  (s, t) invert the table above, divided by the major
+ *                   component's magnitude.
+ *   fetch           seamless and bilinear, of a direction from a face set of size n: px = (s + 1) 0.5 n - 0.5,
+ *                   x0 = floor(px), fx = px - x0, the same in y.  A tap (i, j) inside [0, n)^2 is that face's texel.  A
+ *                   tap outside -- a corner tap too -- is replaced: its centre's (s', t') on the extended face plane
+ *                   becomes a direction by the face's formula, the face is selected again, and the nearest texel there
+ *                   is taken, floor((s'' + 1) 0.5 n) held to [0, n - 1].  Per channel
+ *                   ((c00 (1 - fx) + c10 fx) (1 - fy)) + ((c01 (1 - fx) + c11 fx) fy).
+ *   sum64           of v_0 ... v_{m-1}, m a multiple of 64: p_j = the sum of v_i, i = j mod 64, added in increasing i to
+ *                   0.0; then p_j += p_{j xor 32}, then xor 16, 8, 4, 2, 1; the result is p_0.
+ *
+ * cfhip_equirect_to_cube_device: src is one width x height surface (2 <= width, 1 <= height, both <= 32768) of any of
+ * the three pixel types, rows src_pitch_bytes apart, read as the alpha passes above read alpha (RGBA8
+ * (float)(v / 255.0), RGBA16F half -> float, RGBA32F as stored) with no colour-space change; faces[6] are device
+ * pointers, face_size 1 to 8192.  supersample q in {1, 2, 4}: sub-sample (a, b) of texel (x, y) uses
+ * s = 2 (x + (a + 0.5) / q) / n - 1 and t likewise; its direction d gives phi = atan2(dx, dz), psi = asin(dy / sqrt(|d|^2)),
+ * u = (phi / (2 pi) + 0.5) width - 0.5, v = (0.5 - psi / pi) height - 0.5, and a bilinear fetch in the expression order
+ * above with x taps wrapped modulo the width and y taps clamped: the panorama's centre column looks along +Z, its top
+ * row along +Y.  The sub-samples are added to 0.0, b outer, a inner, the sum is divided by q^2 and stored as float.  One
+ * launch writes the six faces.
+ *
+ * cfhip_cube_prefilter_device: src_levels is a host table [6][source_levels] (face-major) of device pointers, level l of
+ * size max(1, face_size >> l) -- what cfhip_generate_mips_array_device leaves; dst_levels a host table [6][dst_count],
+ * level k of size max(1, face_size >> k); no destination may be a source.  tables[k] is host memory: table_samples[k]
+ * records of destination level k, a multiple of 64 from 64 to 4096, each a tangent-space light direction (lz >= 0 is also
+ * its weight) and a source level of detail, all finite, 0 <= lod <= 14.  table_samples[k] == 0 copies source level k's
+ * bits (roughness 0; k < source_levels).  For an output texel with n^ as above: tx = normalise(up x n^) with
+ * up = (0, 0, 1), up x n^ = (-ny, nx, 0), where |nz| < 0.999, else up = (1, 0, 0), up x n^ = (0, -nz, ny);
+ * ty = n^ x tx; record i has the world direction l = (tx lx + ty ly) + n^ lz per component,
+ * l0 = min((int)lod, L - 1), l1 = min(l0 + 1, L - 1), g = lod - (int)lod,
+ * c_i = fetch(l0, l) (1 - g) + fetch(l1, l) g, v_i = c_i lz; the texel is (float)(sum64(v) / sum64(lz)) per channel,
+ * alpha included.  One launch per destination level for the six faces; the tables travel through the context's staging.
+ *
+ * cfhip_ggx_sample_table (host only, no context): Hammersley points xi1 = (i + 0.5) / S, xi2 = the radical inverse of i;
+ * alpha = roughness^2 (0 < roughness <= 1), cos^2 theta = (1 - xi1) / (1 + (alpha^2 - 1) xi1),
+ * h = (sin theta cos phi, sin theta sin phi, cos theta) with phi = 2 pi xi2, l = 2 hz h - (0, 0, 1);
+ * pdf = D_GGX(hz, alpha) / 4 = (alpha^2 / (pi ((hz^2 (alpha^2 - 1) + 1)^2))) / 4,
+ * lod = clamp(0.5 log2((1 / (S pdf)) / (4 pi / (6 N^2))) + 1, 0, source_levels - 1); a record with lz <= 0 keeps lx, ly
+ * and gets lz = 0, lod = 0, so that S stays fixed.  All in double, rounded to float.
+ *
+ * cfhip_cube_sh9_device: per texel d omega = (4 / n^2) / (r sqrt(r)), r = (1 + s^2) + t^2, and the nine real basis
+ * values of n^ in the order 1, y, z, x, xy, yz, 3z^2 - 1, xz, x^2 - y^2 with the constants 0.282095, 0.488603 (y, z, x),
+ * 1.092548 (xy, yz, xz), 0.315392 (3z^2 - 1) and 0.546274 (x^2 - y^2) -- 1 / (2 sqrt(pi)), sqrt(3 / (4 pi)),
+ * sqrt(15 / (4 pi)), sqrt(5 / (16 pi)), sqrt(15 / (16 pi)), used at full double precision (csrc/envmap.h).  A row's
+ * partials are sum64 over c (Y d omega) and over d omega, the row padded with zeros to a multiple of 64; the rows are
+ * added in (face, y) order to 0.0; each of the 36 sums is multiplied by (4 pi) / (the sum of d omega).  The record is
+ * those 36 doubles, coefficient-major, then the sum of d omega.  Two launches; identical calls give identical bytes.
+ *
+ * Every argument is checked before anything is enqueued; stream == NULL means the context's stream and the call
+ * synchronises.  The scratch is the context's. */
+typedef struct cfhip_ggx_sample {
+	float lx, ly, lz;
+	float lod;
+} cfhip_ggx_sample;
+typedef struct cfhip_sh9_result {
+	double coeff[9][4];
+	double solid_angle;
+} cfhip_sh9_result;
+int cfhip_equirect_to_cube_device(cfhip_ctx* ctx, const void* src, int src_pixel_type, uint32_t width, uint32_t height,
+	size_t src_pitch_bytes, void* const* faces, uint32_t face_size, uint32_t supersample, void* stream);
+int cfhip_ggx_sample_table(float roughness, uint32_t samples, uint32_t face_size, uint32_t source_levels,
+	cfhip_ggx_sample* out);
+int cfhip_cube_prefilter_device(cfhip_ctx* ctx, const void* const* src_levels, uint32_t face_size, uint32_t source_levels,
+	void* const* dst_levels, uint32_t dst_count, const cfhip_ggx_sample* const* tables, const uint32_t* table_samples,
+	void* stream);
+int cfhip_cube_sh9_device(cfhip_ctx* ctx, const void* const* faces, uint32_t face_size, cfhip_sh9_result* result_device,
+	void* stream);
+
 /* One Image::resize on the GPU (lib/src/Image.cpp:1324-1511) -- what Texture::generateMipmaps calls
  * per level, and per custom mip image (Texture.cpp:1499-1503, any source size): src (any of the
  * three pixel types) -> dst, dst_width x dst_height tightly packed RGBA32F, in linear space as
@@ -1216,7 +1295,7 @@ int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* p
 	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass), cfhip_alpha_coverage_device, cfhip_alpha_bleed_array_device or cfhip_alpha_sdf_array_device (every pass) call on
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass), cfhip_alpha_coverage_device, cfhip_alpha_bleed_array_device, cfhip_alpha_sdf_array_device (every pass), cfhip_equirect_to_cube_device, cfhip_cube_prefilter_device (every level) or cfhip_cube_sh9_device (both launches) call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
