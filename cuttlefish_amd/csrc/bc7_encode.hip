@@ -420,7 +420,8 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 	// straight-line palette: entries past this lane's 2^ib get a key that never wins.
 	// A texel's key is F/2 (sum_c w_c c_k^2 - 2 sum_c p_c (w_c c_k)) + weight_k with F = 2^(WBITS + 1), minimised over k;
 	// sum_c w_c p_c^2 is added once per subset (pp_sum).  Unit weights: the cross terms of a row of four texels against
-	// entry k are one v_mfma_i32_4x4x4_16b_i8 (bc7_packed.h: mfma_entry_base).  Perceptual metric: the palette entry goes
+	// entry k are one v_mfma_i32_4x4x4_16b_i8 (bc7_packed.h: mfma_entry_base), issued without its C operand: pp_sum comes in
+	// with the texels' own term already taken off (search_pp_fold).  Perceptual metric: the palette entry goes
 	// to (Y, Cr, Cb, A), its weighted form is two words of 16-bit pairs, the cross term two v_dot2_u32_u16.
 	uint32_t pal[8], palh[8];
 	int base[8];
@@ -499,12 +500,9 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 			uint32_t wrow = 0, krow[4];
 			int bestm[4] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF};
 			if (UNITW) {
-				// C: 128 sum_c a_c of the row's four texels; D = dt - 128 sum_c b'_c for the four texels against entry k
-				cf_int4 cop;
-				cop.x = (int)__builtin_amdgcn_udot4(raw[0], 0x80808080u, 0u, false);
-				cop.y = (int)__builtin_amdgcn_udot4(raw[1], 0x80808080u, 0u, false);
-				cop.z = (int)__builtin_amdgcn_udot4(raw[2], 0x80808080u, 0u, false);
-				cop.w = (int)__builtin_amdgcn_udot4(raw[3], 0x80808080u, 0u, false);
+				// C = 0: D = sum_c a'_c b'_c for the four texels against entry k.  The texel's own term 128 sum_c a_c shifts all its
+				// keys alike and is taken off pp_sum once per fit (bc7_packed.h: search_pp_fold)
+				const cf_int4 cop = {0, 0, 0, 0};
 				const uint32_t aop = r2 == 0u ? (h == 0u ? arow[0] : arow[1]) : (h == 0u ? arow[2] : arow[3]);
 #pragma unroll
 				for (int k = 0; k < NK; ++k) {
@@ -708,10 +706,14 @@ struct FitStats {
 // fit_lane and everything it calls, NO store (LDS or global) and NO table or LDS index derived from cb / ab / pbk / ib / mask
 // may be reached without `owner` unless it stays in range for any value (weight_row, inv_n, gsrc & 63 do by construction).
 // Today the only store is the geometry-cache write below, and it is guarded.
+// whole, lohi (unit weights): the fit covers the whole block by its role (mode 6, a plane of modes 4 / 5), and the
+// per-block table whose words' upper halves hold the block's raw byte sum, such a fit's search bias (lohi_rawsum; indexed by
+// the block alone: in range on any lane).
 template <bool UNITW, uint32_t ITERS, int NK = 8, bool GIVEN = false, int CBSZ = 3>
 __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, uint32_t khalf,
 	uint32_t cb, uint32_t ab, uint32_t pbk, uint32_t ib, const uint32_t (&wt)[4],
-	const uint32_t (&yw)[2], bool scalar, float frac, uint32_t* gbase, uint32_t gmode, uint32_t gsrc, const FitStats& gs, bool owner, LaneFit& best)
+	const uint32_t (&yw)[2], bool scalar, float frac, uint32_t* gbase, uint32_t gmode, uint32_t gsrc, const FitStats& gs, bool owner,
+	bool whole, const uint32_t* lohi, LaneFit& best)
 {
 	float axis[4], mean[4];
 	float tmin, tmax;
@@ -745,7 +747,7 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 			uint32_t q[10];
 			mom_unpack(gs.W, s, q);
 			q00 = q[0]; q01 = q[1]; q02 = q[2]; q03 = q[3]; q11 = q[4]; q12 = q[5]; q13 = q[6]; q22 = q[7]; q23 = q[8]; q33 = q[9];
-			lo = gs.lohi & 255u; hi = gs.lohi >> 8;
+			lo = gs.lohi & 255u; hi = UNITW ? lohi_hi(gs.lohi) : gs.lohi >> 8;   // (unit weights: the raw byte sum sits above)
 		} else
 #pragma unroll 1
 		for (uint32_t r = 0; r < 4u; ++r) {
@@ -835,6 +837,13 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 		// sum over the subset of sum_c p_c^2 (channels that are not coded have p = 0), or of the
 		// weighted squares on the perceptual axes
 		pp_sum = UNITW ? q00 + q11 + q22 + q33 : ycc_pp_sum(tx, mask, yw);
+		if constexpr (UNITW) {
+			// the selector search runs without its C operand: the sum of the subset's raw bytes, times 256, leaves the
+			// constant here (bc7_packed.h).  By the lane's role: a whole-block fit's channel set hides raw channels from s.
+			const uint32_t bias = whole ? lohi_rawsum((GIVEN && gmode == 3u) ? gs.lohi : lohi[tx.boff >> 2])
+				: search_bias_part(s[0], s[1], s[2], s[3], n, !(tx.chmask & 8u));
+			pp_sum = search_pp_fold(pp_sum, bias);
+		}
 		s01 = s[0] | (s[1] << 16);
 		s23 = s[2] | (s[3] << 16);
 		if ((GIVEN ? gmode != 0u : gmode == 1u) && (UNITW ? owner : true)) {   // 1 or 3; owner: see the call (a lane without a fit stores nothing)
@@ -1567,6 +1576,7 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			uint32_t chm_s = 0;
 			uint32_t gmode = 1u, gsrc = 0u;   // stream trips write the fit-geometry cache, the starts trip reads it
 			bool narrow = false;              // starts trip: no active lane's fit has more than 4 palette entries
+			bool whole = true;                // the fit covers the whole block (its search bias: fit_lane); set below
 			if (sst) {
 				// lane = (top candidate k, start variant v, fit): 8 lanes per candidate in the 32-lane layouts
 				// (k = hl >> 3, v = (hl >> 1) & 3, fit = hl & 1 -- mode 6: its two palette halves), 16 in the wide
@@ -1586,6 +1596,7 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				const FitGeo g = column_geo(cbase + wl, id, fi);
 				m6 = g.m6; sca = g.sca; rot = g.rot; cb = g.cb; ab = g.ab; pbk = g.pbk; ib = g.ib; mask = g.mask;
 				chm_s = g.chm;
+				if constexpr (UNITW) whole = g.ns < 2u;   // one subset: mode 6, the planes of modes 4 / 5
 				active = L_SLOT_OK && k < ntop && cerr != 0xFFFFFFFFu && err0 != 0u && (g.m6 ? fi < 2u : fi < g.nfits);
 				// starts 0, 2, 3, 4 of the oracle: the extremes, pushed out by 1/16, pulled in by 1/8, by 3/16
 				frac = v == 0u ? 0.0f : (v == 1u ? -1.0f/16.0f : (v == 2u ? 1.0f/8.0f : 3.0f/16.0f));
@@ -1642,6 +1653,9 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				else
 					mask = part3_mask(sp3, sub);
 				active = true;
+			}
+			if constexpr (UNITW) {
+				if (!sst) whole = !plane;
 			}
 			if (CF_BC7_ABLATE & 1) active = active && (m6 || plane);
 			if (CF_BC7_ABLATE & 2) active = active && !plane;
@@ -1702,10 +1716,10 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			if (UNITW ? __ballot(active) != 0ull : active) {
 				if (narrow)
 					fit_lane<UNITW, iters, 4, false, WIDE ? 4 : 3>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
-						wv, yw, sca, frac, gbase, gmode, gsrc, gs, active, lf);
+						wv, yw, sca, frac, gbase, gmode, gsrc, gs, active, whole, lohi, lf);
 				else
 					fit_lane<UNITW, iters, 8, given, WIDE ? 4 : 3>(make_tex(tile, plan, yccp, B_OFF, rot, chm), mask, m6, lane & 1u, cb, ab, pbk, ib,
-						wv, yw, sca, frac, gbase, gmode, gsrc, gs, active, lf);
+						wv, yw, sca, frac, gbase, gmode, gsrc, gs, active, whole, lohi, lf);
 				if (UNITW && !active) {
 					lf.err = 0; lf.q0 = 0; lf.q1 = 0; lf.pb = 0;
 #pragma unroll
@@ -1962,16 +1976,24 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 			const bool pphit = __ballot(act && !ghit) == 0ull;
 			if (pphit)
 				pp_sum = gbase[gsrc + 11*CF_WG_THREADS];
-			else if (UNITW) {
+			else if constexpr (UNITW) {
+				// (with the search's bias taken off, as fit_lane leaves it in the cache: a whole-block fit's from the table word,
+				// a partition fit's from its own channel sums)
+				uint32_t ssum = 0;
 #pragma unroll 1
 				for (uint32_t r = 0; r < 4u; ++r) {
 					uint32_t P[4];
 					planes<true>(tx, *reinterpret_cast<const uint4*>(tx.pl() + 4u*r), P);
 					const uint32_t m4 = bytemask4((g.mask >> (4u*r)) & 15u);
 #pragma unroll
-					for (int c = 0; c < 4; ++c)
+					for (int c = 0; c < 4; ++c) {
 						pp_sum += __builtin_amdgcn_udot4(P[c] & m4, P[c], 0u, false);
+						ssum = __builtin_amdgcn_udot4(P[c] & m4, 0x01010101u, ssum, false);
+					}
 				}
+				const uint32_t bias = g.ns < 2u ? lohi_rawsum(lohi[B_OFF >> 2])
+					: search_bias_part(ssum, 0u, 0u, 0u, (uint32_t)__builtin_popcount(g.mask), !(g.chm & 8u));
+				pp_sum = search_pp_fold(pp_sum, bias);
 			} else
 				pp_sum = ycc_pp_sum(tx, g.mask, yw);
 			// the 4-entry selector search when no active lane's fit has more than 4 palette entries (wave-uniform)
@@ -2136,6 +2158,12 @@ cfhip_bc7_encode_kernel(cf_kparams kp)
 		// then the rows of the other three (lanes 4 and 8 away in the DPP row of 16).  It lives in the block's 16 bytes of
 		// outb, which are dead until the block's payload is stored there after its search.
 		// (read by the 32-lane layouts' first stream trip)
+		// Unit weights: the upper half of every word of the table holds the sum of the block's 64 raw bytes, alpha included
+		// whatever the block's channel set (bc7_packed.h: lohi_pack; the bias of a whole-block fit's selector search).  The
+		// wide layout has no table of extremes and keeps the sum in word 0 of the block's four.
+		uint32_t rs = 0;
+		if constexpr (UNITW)
+			rs = cf_row_sum_u32(__builtin_amdgcn_udot4(pw, 0x01010101u, 0u, false));   // (a DPP row of 16 lanes = the block's 16 planar words)
 		if (!WIDE) {
 			const uint32_t lh = byte_lohi(pw);
 			uint32_t lo = lh & 255u, hi = lh >> 8, o;
@@ -2144,7 +2172,10 @@ cfhip_bc7_encode_kernel(cf_kparams kp)
 			o = cf_dpp<0x124>(lo); lo = o < lo ? o : lo;   // row_ror:4
 			o = cf_dpp<0x124>(hi); hi = o > hi ? o : hi;
 			if ((t & 12u) == 0u)
-				reinterpret_cast<uint32_t*>(outb)[(t >> 4)*4u + c] = lo | (hi << 8);
+				reinterpret_cast<uint32_t*>(outb)[(t >> 4)*4u + c] = UNITW ? lohi_pack(lo | (hi << 8), rs) : lo | (hi << 8);
+		} else if constexpr (UNITW) {
+			if ((t & 15u) == 0u)
+				reinterpret_cast<uint32_t*>(outb)[(t >> 4)*4u] = lohi_pack(0u, rs);
 		}
 	}
 	__syncthreads();

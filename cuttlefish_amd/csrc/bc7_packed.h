@@ -58,6 +58,31 @@ CF_PK int mfma_entry_base(int B, uint32_t sb, int fbits)
 	return B + (int)(512u << (7 + fbits)) - (int)CF_PK_MUL24(sb, 1u << (7 + fbits));
 }
 
+// The search issues the instruction with C = 0 (tests/test_bc7_search_bias.py).  128 sum_c a_c depends on the texel alone,
+// not on the entry: without it D' = sum a'b' and a texel's keys all become key' = base' - 512 D' = key + 65536 A_t, with
+// A_t = sum_c a_c <= 1020 the sum of the texel's four RAW channels (the A operand is the raw texel, whatever the fit
+// codes).  The shift is the same for every entry and for both halves of mode 6, so the winning entry, the tie order and the
+// key's low byte (its weight) stay, and a texel outside the subset still has the key 0.  key' >> 8 = (key >> 8) + 256 A_t
+// exactly, so an assignment's error grows by 256 sum_{t in subset} A_t: the fit subtracts that once from the constant
+// pp_sum (search_pp_fold), in 32-bit modular arithmetic -- pp_sum' may wrap below zero (a dark block: 256 A_t > sum p^2),
+// pp_sum' + sum (key' >> 8) is the true error again.  Ranges: |D'| <= 4 * 128^2 = 2^16; key' in (-2^26, 2^27) (key in
+// (-2^26, 2^26), 65536 A_t < 2^26); CF_BC7_NO_ENTRY - 512 D' in (2^29, 2^31): above every real key and inside 32 bits;
+// both operands of the 24-bit multiply-add (-512, D') fit 24 bits.
+// The bias sum_{t in subset} A_t of a fit of the whole block (mode 6, the planes of modes 4 / 5: their channel sets
+// hide raw channels from the fit's own sums) is a per-block table word, the sum of the block's 64 raw bytes (<= 16 320 <
+// 2^14).  It lives in the upper half of the words of the per-block table of channel extremes, lo | hi << 8, whose upper
+// halves were unused (lohi_pack): no LDS is added.
+// A partition fit (no rotation; channel set 7 on an opaque block, 15 on one with alpha) has it in its own subset sums.
+CF_PK uint32_t lohi_pack(uint32_t lohi, uint32_t rawsum) { return lohi | (rawsum << 16); }
+CF_PK uint32_t lohi_rawsum(uint32_t w) { return w >> 16; }
+CF_PK uint32_t lohi_hi(uint32_t w) { return (w >> 8) & 255u; }
+// n: texels of the subset; opaque: the fit does not code alpha (s3 = 0), the raw alpha is the constant 255
+CF_PK uint32_t search_bias_part(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t s3, uint32_t n, bool opaque)
+{
+	return s0 + s1 + s2 + s3 + (opaque ? CF_PK_MUL24(n, 255u) : 0u);
+}
+CF_PK uint32_t search_pp_fold(uint32_t pp_sum, uint32_t bias) { return pp_sum - (bias << 8); }
+
 // The low bytes of four keys as the bytes of one word (a key's low byte is its weight, 0 for a texel outside the subset).
 // Two byte permutes and an or on the device.
 CF_PK uint32_t key_row_weights(uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3)
