@@ -205,7 +205,7 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_lz4_decode", "cfhip_lz4_decode_device", "cfhip_lz4_decode_stage_ms",
            "cfhip_png_bound", "cfhip_png_encode", "cfhip_png_encode_device", "cfhip_png_stage_ms",
            "cfhip_mip_post_array_device", "cfhip_alpha_coverage_device", "cfhip_alpha_bleed_array_device",
-           "cfhip_alpha_sdf_array_device",
+           "cfhip_alpha_sdf_array_device", "cfhip_spec_aa_array_device",
            "cfhip_equirect_to_cube_device", "cfhip_ggx_sample_table", "cfhip_cube_prefilter_device",
            "cfhip_cube_sh9_device"]
 
@@ -590,6 +590,58 @@ def make_sdf_params(spread: int, scale: int = 1, threshold: float = 0.5, wrap=(F
                      sdf_channel_mask(channels), 0)
 
 
+SPEC_AA_PERCEPTUAL, SPEC_AA_SIGNED_NORMALS, SPEC_AA_RECONSTRUCT_Z = 1, 2, 4      # cfhip_spec_aa_params.flags
+SPEC_AA_CHANNELS = {"r": 0, "g": 1, "b": 2, "a": 3}                               # cfhip_spec_aa_params.channel
+
+
+class SpecAaParams(ctypes.Structure):
+    """cfhip_spec_aa_params"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("channel", ctypes.c_uint32),
+                ("base_roughness", ctypes.c_float), ("variance_scale", ctypes.c_float), ("max_variance", ctypes.c_float),
+                ("reserved", ctypes.c_uint32*2)]
+
+
+class SpecAaResult(ctypes.Structure):
+    """cfhip_spec_aa_result: one level's texels whose variance met max_variance, those whose alpha^2 reached 1, and the
+    bit pattern of the largest (float)(variance_scale * v) added"""
+    _fields_ = [("clamped", ctypes.c_uint32), ("saturated", ctypes.c_uint32), ("max_added", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
+SPEC_AA_RESULT_DTYPE = np.dtype([("clamped", np.uint32), ("saturated", np.uint32), ("max_added", np.uint32),
+                                 ("reserved", np.uint32)])
+
+
+def spec_aa_channel(channel) -> int:
+    """channel as the specular anti-aliasing methods take it: one of "r", "g", "b", "a" (any case) or 0 to 3"""
+    if isinstance(channel, str) and channel.lower() in SPEC_AA_CHANNELS:
+        return SPEC_AA_CHANNELS[channel.lower()]
+    if isinstance(channel, (int, np.integer)) and not isinstance(channel, (bool, np.bool_)) and 0 <= channel <= 3:
+        return int(channel)
+    raise ValueError('channel %r: one of "r", "g", "b", "a" or 0 to 3' % (channel,))
+
+
+def make_spec_aa_params(channel, perceptual: bool = True, signed_normals: bool = False, reconstruct_z: bool = False,
+                        base_roughness: float = 0.5, variance_scale: float = 1.0,
+                        max_variance: float = 1.0) -> SpecAaParams:
+    """channel: the component of the roughness chain that is rewritten; perceptual: the stored value is perceptual
+    roughness (alpha = r^2), else alpha itself; signed_normals: the normals are stored as they are, else as n/2 + 1/2;
+    reconstruct_z: two-channel normals, z from x and y; base_roughness: every texel's roughness when there is no
+    level-0 roughness map; variance_scale, max_variance: 1 and 1 are the plain vMF form, 2 and 0.18 the clamp of
+    Kaplanyan et al.  Every bad field is a ValueError here, before the library would refuse it."""
+    with np.errstate(over="ignore"):                   # a value beyond float32 becomes inf and is refused below
+        b, s, m = (float(np.float32(v)) for v in (base_roughness, variance_scale, max_variance))
+    if not 0.0 <= b <= 1.0:
+        raise ValueError("base_roughness %r outside [0, 1]" % (base_roughness,))
+    if not (s >= 0.0 and np.isfinite(s)):
+        raise ValueError("variance_scale %r is negative or not finite" % (variance_scale,))
+    if not (m >= 0.0 and np.isfinite(m)):
+        raise ValueError("max_variance %r is negative or not finite" % (max_variance,))
+    flags = (SPEC_AA_PERCEPTUAL if perceptual else 0) | (SPEC_AA_SIGNED_NORMALS if signed_normals else 0) | \
+        (SPEC_AA_RECONSTRUCT_Z if reconstruct_z else 0)
+    return SpecAaParams(ctypes.sizeof(SpecAaParams), flags, spec_aa_channel(channel), b, s, m, (ctypes.c_uint32*2)(0, 0))
+
+
 # ---- environment maps (cfhip_equirect_to_cube_device, cfhip_cube_prefilter_device, cfhip_cube_sh9_device) ----
 ENV_MAX_FACE = 8192
 ENV_MAX_PANORAMA = 32768
@@ -775,6 +827,11 @@ def load_library(path: Optional[str] = None):
         ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_size_t,
         ctypes.POINTER(SdfParams), ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_alpha_sdf_array_device.restype = ctypes.c_int
+    L.cfhip_spec_aa_array_device.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
+        ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_size_t,
+        ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(SpecAaParams), ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_spec_aa_array_device.restype = ctypes.c_int
     L.cfhip_equirect_to_cube_device.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
@@ -1406,6 +1463,77 @@ class Context:
         rec = res.cpu().numpy().view(SDF_RESULT_DTYPE)[0]
         return (out.cpu().numpy().view(out_dtype).reshape(h//scale, w//scale, 4),
                 {k: int(rec[k]) for k in rec.dtype.names})
+
+    def specular_aa_device(self, normals: Sequence[int], pixel_type, width: int, height: int, pitch: int,
+                           levels: Sequence[Sequence[int]], *, rough0: Optional[Sequence[int]] = None,
+                           rough_pixel_type=None, rough_pitch: int = 0, channel, perceptual: bool = True,
+                           signed_normals: bool = False, reconstruct_z: bool = False, base_roughness: float = 0.5,
+                           variance_scale: float = 1.0, max_variance: float = 1.0, results: int = 0, stream: int = 0):
+        """Specular anti-aliasing of generated roughness chains in place (cfhip_spec_aa_array_device), on the buffers
+        as generate_mips_array_device takes them: normals[l] = level 0 of layer l's normal map (only read),
+        levels[l][k-1] = level k of its roughness chain (RGBA32F, tightly packed).  `channel` of every listed level is
+        overwritten with sqrt of (the mean alpha^2 of the level-0 texels under the texel + variance_scale * the
+        variance of their normals, as 1/kappa of the vMF lobe, at most max_variance); with perceptual the stored values
+        are perceptual roughness (alpha = r^2).  The value written replaces the mip filter's own value in that channel:
+        it is the footprint mean of alpha^2 plus the variance, not a correction of the filter's result.  Level 0, the
+        other channels and the normals are never written.  rough0[l] = level 0 of the roughness map (rough_pixel_type,
+        rows rough_pitch apart; it may be the normals' surface), or None: base_roughness in every texel.  results:
+        device pointer to len(normals) * len(levels[0]) cfhip_spec_aa_result records (SPEC_AA_RESULT_DTYPE), or 0.
+        One call is ceil(len(levels[0]) / 5) launches, at most 3, whatever the layers."""
+        nl = len(normals)
+        if nl == 0 or len(levels) != nl or len({len(d) for d in levels}) != 1:
+            raise ValueError("normals and levels must list the same layers, every layer the same levels")
+        if rough0 is not None and (len(rough0) != nl or rough_pixel_type is None):
+            raise ValueError("rough0 lists the layers of normals and comes with its rough_pixel_type")
+        per = len(levels[0])
+        params = make_spec_aa_params(channel, perceptual, signed_normals, reconstruct_z, base_roughness, variance_scale,
+                                     max_variance)
+        narr = (ctypes.c_void_p * nl)(*[ctypes.c_void_p(int(p)) for p in normals])
+        rarr = (ctypes.c_void_p * nl)(*[ctypes.c_void_p(int(p)) for p in rough0]) if rough0 is not None else None
+        flat = [ctypes.c_void_p(int(p)) for d in levels for p in d]
+        larr = (ctypes.c_void_p * max(len(flat), 1))(*flat)
+        self._check(self._lib.cfhip_spec_aa_array_device(
+            self._h, narr, nl, int(pixel_type), width, height, pitch, rarr,
+            int(rough_pixel_type) if rough0 is not None else 0, rough_pitch if rough0 is not None else 0, larr, per + 1,
+            ctypes.byref(params), ctypes.c_void_p(int(results)) if results else None,
+            ctypes.c_void_p(stream) if stream else None))
+
+    def specular_aa(self, normals: np.ndarray, roughness0, levels_count: int, channel="g", perceptual: bool = True,
+                    signed_normals: bool = False, reconstruct_z: bool = False, variance_scale: float = 1.0,
+                    max_variance: float = 1.0):
+        """Host convenience: one (h, w, 4) uint8 / float16 / float32 normal map and either its (h, w, 4) level-0
+        roughness map or a float (the roughness of every texel) through specular_aa_device -> (the channel's levels
+        1 ... levels_count - 1 as float32 arrays of (max(1, h >> k), max(1, w >> k)), the records as a list of dicts).
+        The values do not depend on any mip filter: they are the footprint mean of alpha^2 plus the variance."""
+        import torch
+        host = np.ascontiguousarray(normals)
+        if host.ndim != 3 or host.shape[2] != 4:
+            raise ValueError("expected (h, w, 4)")
+        h, w = host.shape[:2]
+        ch = spec_aa_channel(channel)
+        device = "cuda:%d" % self.device_id
+        dev = torch.from_numpy(host.view(np.uint8)).to(device)
+        kw = dict(channel=ch, perceptual=perceptual, signed_normals=signed_normals, reconstruct_z=reconstruct_z,
+                  variance_scale=variance_scale, max_variance=max_variance)
+        keep = None
+        if isinstance(roughness0, np.ndarray):
+            rh = np.ascontiguousarray(roughness0)
+            if rh.shape != host.shape:
+                raise ValueError("the roughness map has the shape of the normal map")
+            keep = torch.from_numpy(rh.view(np.uint8)).to(device)
+            kw.update(rough0=[keep.data_ptr()], rough_pixel_type=pixel_type_of(rh), rough_pitch=rh.strides[0])
+        else:
+            kw.update(base_roughness=float(roughness0))
+        per = int(levels_count) - 1
+        if per < 1:
+            raise ValueError("levels_count is at least 2")
+        lv = [torch.zeros((max(1, h >> k), max(1, w >> k), 4), dtype=torch.float32, device=device) for k in range(1, per + 1)]
+        res = torch.zeros(per*4, dtype=torch.int32, device=device)
+        self.specular_aa_device([dev.data_ptr()], pixel_type_of(host), w, h, host.strides[0], [[t.data_ptr() for t in lv]],
+                                results=res.data_ptr(), **kw)
+        rec = res.cpu().numpy().view(SPEC_AA_RESULT_DTYPE)
+        return ([t.cpu().numpy()[:, :, ch].copy() for t in lv],
+                [{k: int(r[k]) for k in rec.dtype.names} for r in rec])
 
     def equirect_to_cube_device(self, src: int, pixel_type, width: int, height: int, row_pitch_bytes: int,
                                 faces: Sequence[int], face_size: int, supersample: int = 2, stream: int = 0):

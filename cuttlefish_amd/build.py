@@ -169,6 +169,8 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  # the signed distance field from alpha (csrc/alpha_sdf.hip): classes, row distances, columns, tiles
                  "cfhip_alpha_sdf_classify_kernel", "cfhip_alpha_sdf_row_kernel", "cfhip_alpha_sdf_column_kernel",
                  "cfhip_alpha_sdf_resolve_kernel",
+                 # specular anti-aliasing (csrc/spec_aa.hip): five levels from texels, five more from a launch's moments
+                 "cfhip_spec_aa_texel_kernel", "cfhip_spec_aa_moment_kernel",
                  # environment maps (csrc/envmap.hip): panorama to cube, the GGX chain and its copy, the SH9 rows and sum
                  "cfhip_equirect_to_cube_kernel", "cfhip_cube_prefilter_kernel", "cfhip_cube_copy_kernel",
                  "cfhip_cube_sh9_rows_kernel", "cfhip_cube_sh9_final_kernel")

@@ -19,6 +19,7 @@
 #include "mip_post.h"
 #include "alpha_bleed.h"
 #include "alpha_sdf.h"
+#include "spec_aa.h"
 #include "envmap.h"
 #include "stage_log.h"
 #include "../../include/cuttlefish_hip.h"
@@ -2530,6 +2531,145 @@ int cfhip_alpha_sdf_array_device(cfhip_ctx* ctx, const void* const* src, uint32_
 			rc = sdf([&] { return cfhip_launch_alpha_sdf_column(&call, layers, rows, e, results_device, stream); });
 		if (rc == CFHIP_OK && s > 1u)
 			rc = sdf([&] { return cfhip_launch_alpha_sdf_resolve(&call, layers, e, stream); });
+		if (rc != CFHIP_OK)
+			return rc;
+		return lease.done(!stream_);
+	});
+}
+
+// ---- specular anti-aliasing (csrc/spec_aa.hip): the normals' variance into the levels of a roughness chain -----------
+int cfhip_spec_aa_array_device(cfhip_ctx* ctx, const void* const* normals, uint32_t layers, int normal_pixel_type, uint32_t width,
+	uint32_t height, size_t normal_pitch_bytes, const void* const* rough0, int rough_pixel_type, size_t rough_pitch_bytes,
+	void* const* levels, uint32_t levels_count, const cfhip_spec_aa_params* params, cfhip_spec_aa_result* results_device,
+	void* stream_)
+{
+	static_assert(sizeof(cfhip_spec_aa_params) == 32 && sizeof(cfhip_spec_aa_result) == 16, "the ABI's sizes");
+	static_assert(sizeof(cfsa_moments) == 32, "a tile's moments in the scratch");
+	return guarded(ctx, "spec_aa", [&]() -> int {
+		if (!params)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params is NULL");
+		if (params->struct_size != sizeof(cfhip_spec_aa_params))
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params->struct_size is %u, not %zu", params->struct_size,
+				sizeof(cfhip_spec_aa_params));
+		if (!normals)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: normals is NULL");
+		if (!levels)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: levels is NULL");
+		if (!layers || layers > CFSA_MAX_LAYERS)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: layers is %u (1 to %u per call)", layers, CFSA_MAX_LAYERS);
+		if (!width || !height || width > CFSA_MAX_SIDE || height > CFSA_MAX_SIDE)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: width and height are 1 to %u each, not %ux%u", CFSA_MAX_SIDE, width, height);
+		const size_t npb = pixel_bytes(normal_pixel_type), rpb = rough0 ? pixel_bytes(rough_pixel_type) : 0u;
+		if (!npb)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: normal_pixel_type %d", normal_pixel_type);
+		if (rough0 && !rpb)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: rough_pixel_type %d", rough_pixel_type);
+		if (params->flags & ~(uint32_t)(CFHIP_SPEC_AA_PERCEPTUAL | CFHIP_SPEC_AA_SIGNED_NORMALS | CFHIP_SPEC_AA_RECONSTRUCT_Z))
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params->flags 0x%x: unknown", params->flags);
+		if (params->channel > 3u)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params->channel %u above 3", params->channel);
+		if (!(params->base_roughness >= 0.0f && params->base_roughness <= 1.0f))
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params->base_roughness %g outside [0, 1]", (double)params->base_roughness);
+		if (!(params->variance_scale >= 0.0f) || !std::isfinite(params->variance_scale))
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params->variance_scale %g is negative or not finite",
+				(double)params->variance_scale);
+		if (!(params->max_variance >= 0.0f) || !std::isfinite(params->max_variance))
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params->max_variance %g is negative or not finite",
+				(double)params->max_variance);
+		if (params->reserved[0] || params->reserved[1])
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params->reserved is not 0");
+		uint32_t chain = 0;
+		for (uint32_t side = std::max(width, height); side; side >>= 1)
+			++chain;
+		if (levels_count < 2u || levels_count > chain)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: levels_count %u outside 2 to %u, the chain of %ux%u", levels_count, chain,
+				width, height);
+		if ((uint64_t)width*height > CFSA_MAX_TEXELS)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: more than 2^30 texels in level 0");
+		if (normal_pitch_bytes < (size_t)width*npb)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: normal_pitch_bytes %zu < %zu, a row", normal_pitch_bytes, (size_t)width*npb);
+		if (normal_pitch_bytes % npb)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: normal_pitch_bytes %zu not aligned to a texel (%zu bytes)", normal_pitch_bytes,
+				npb);
+		if (rough0 && rough_pitch_bytes < (size_t)width*rpb)
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: rough_pitch_bytes %zu < %zu, a row", rough_pitch_bytes, (size_t)width*rpb);
+		if (rough0 && rough_pitch_bytes % (rpb/4u))
+			return fail(ctx, CFHIP_E_INVALID, "spec_aa: rough_pitch_bytes %zu not aligned to a component (%zu bytes)",
+				rough_pitch_bytes, rpb/4u);
+		const uint32_t per = levels_count - 1u;
+		for (uint32_t l = 0; l < layers; ++l) {
+			if (!normals[l])
+				return fail(ctx, CFHIP_E_INVALID, "spec_aa: normals[%u] is NULL", l);
+			if ((uintptr_t)normals[l] % npb)
+				return fail(ctx, CFHIP_E_INVALID, "spec_aa: normals[%u] not aligned to a texel (%zu bytes)", l, npb);
+			if (rough0 && !rough0[l])
+				return fail(ctx, CFHIP_E_INVALID, "spec_aa: rough0[%u] is NULL", l);
+			if (rough0 && (uintptr_t)rough0[l] % (rpb/4u))
+				return fail(ctx, CFHIP_E_INVALID, "spec_aa: rough0[%u] not aligned to a component (%zu bytes)", l, rpb/4u);
+			for (uint32_t k = 1; k < levels_count; ++k) {
+				const size_t i = (size_t)l*per + (k - 1u);
+				if (!levels[i])
+					return fail(ctx, CFHIP_E_INVALID, "spec_aa: levels[%zu] (layer %u, level %u) is NULL", i, l, k);
+				if ((uintptr_t)levels[i] % 16u)
+					return fail(ctx, CFHIP_E_INVALID, "spec_aa: levels[%zu] is not aligned to a texel (16 bytes)", i);
+			}
+		}
+		if (!ctx)
+			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+		HIP_TRY(ctx, hipSetDevice(ctx->device));
+		StagingLease lease(ctx, call_stream(ctx, stream_));
+		const hipStream_t stream = lease.stream;
+		begin_call(ctx, stream, "cfhip_spec_aa_texel_kernel");
+		// d_batch: the layers' normals, their roughness maps (if any), then the levels.  d_src: a launch's last moments
+		// are the next one's input -- level 5, then level 10, layer after layer
+		const auto dim = [](uint32_t d, uint32_t k) { return (d >> k) ? (d >> k) : 1u; };
+		const uint32_t stages = (per + CFSA_STAGE_LEVELS - 1u)/CFSA_STAGE_LEVELS;
+		size_t moments[CFSA_MAX_STAGES] = {0, 0, 0};       // moments[s]: what stage s writes
+		for (uint32_t s = 0; s + 1u < stages; ++s) {
+			const uint32_t k = (s + 1u)*CFSA_STAGE_LEVELS;
+			moments[s] = (size_t)layers*dim(width, k)*dim(height, k);
+		}
+		const size_t ntab = (size_t)layers*(rough0 ? 2u : 1u) + (size_t)layers*per;
+		int rc = lease.acquire();
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, ntab*sizeof(void*));
+		if (rc == CFHIP_OK)
+			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, std::max<size_t>((moments[0] + moments[1])*sizeof(cfsa_moments), 16u));
+		if (rc != CFHIP_OK)
+			return rc;
+		// pageable sources: the runtime stages the copies before returning
+		void** table = static_cast<void**>(ctx->d_batch);
+		void** d_rough = table + layers;
+		void** d_levels = d_rough + (rough0 ? layers : 0u);
+		HIP_TRY(ctx, hipMemcpyAsync(table, normals, (size_t)layers*sizeof(void*), hipMemcpyHostToDevice, stream));
+		if (rough0)
+			HIP_TRY(ctx, hipMemcpyAsync(d_rough, rough0, (size_t)layers*sizeof(void*), hipMemcpyHostToDevice, stream));
+		HIP_TRY(ctx, hipMemcpyAsync(d_levels, levels, (size_t)layers*per*sizeof(void*), hipMemcpyHostToDevice, stream));
+		if (results_device)
+			HIP_TRY(ctx, hipMemsetAsync(results_device, 0, (size_t)layers*per*sizeof(cfhip_spec_aa_result), stream));
+		cfsa_call call;
+		call.normals = table;
+		call.rough0 = rough0 ? d_rough : nullptr;
+		call.levels = d_levels;
+		call.normal_pitch = normal_pitch_bytes;
+		call.rough_pitch = rough0 ? rough_pitch_bytes : 0u;
+		call.width = width; call.height = height;
+		call.levels_count = levels_count;
+		call.normal_type = normal_pixel_type;
+		call.rough_type = rough0 ? rough_pixel_type : 0;
+		call.flags = params->flags;
+		call.channel = params->channel;
+		call.base_roughness = params->base_roughness;
+		call.variance_scale = params->variance_scale;
+		call.max_variance = params->max_variance;
+		cfsa_moments* const m0 = static_cast<cfsa_moments*>(ctx->d_src);
+		cfsa_moments* const buf[CFSA_MAX_STAGES] = {m0, m0 + moments[0], nullptr};
+		// every launch of the pass is a timed span of its own
+		for (uint32_t s = 0; rc == CFHIP_OK && s < stages; ++s)
+			rc = timed(ctx, stream, "spec_aa", [&] {
+				return cfhip_launch_spec_aa(&call, layers, s, s ? buf[s - 1u] : nullptr, s + 1u < stages ? buf[s] : nullptr,
+					results_device, stream);
+			});
 		if (rc != CFHIP_OK)
 			return rc;
 		return lease.done(!stream_);

@@ -340,6 +340,7 @@ class Texture:
         self._mip_post: List[List[dict]] = []
         self._bleed: List[dict] = []
         self._sdf: List[dict] = []
+        self._spec_aa: List[dict] = []
 
     def initialize(self, dimension, width: int, height: int, depth: int = 0, mip_levels: int = 1,
                    color_space: ColorSpace = ColorSpace.Linear) -> bool:
@@ -717,6 +718,78 @@ class Texture:
         mip, depth, face, inside (texels inside) and saturated (texels farther than the spread from the silhouette); []
         before any call."""
         return [dict(r) for r in self._sdf]
+
+    def specular_antialias(self, normals: "Texture", channel="g", perceptual: bool = True, signed_normals: bool = False,
+                           reconstruct_z: bool = False, variance_scale: float = 1.0, max_variance: float = 1.0) -> bool:
+        """Specular anti-aliasing (Context.specular_aa_device) of this roughness -- or packed ORM -- texture against
+        the normal map `normals`: call it after generate_mipmaps and before convert.  `channel` of every level from 1
+        on, of every depth and face, takes sqrt of (the mean alpha^2 of the level-0 texels under the texel + the
+        variance of the level-0 normals under it), so that what averaging the normals loses shows up as roughness.
+        The value written replaces the mip filter's own value in that channel: it is the footprint mean of alpha^2
+        plus the variance, not a correction of the filter's result.  Level 0, the other channels and `normals` are
+        untouched; the levels become RGBAF (float32) images.  perceptual: the channel stores perceptual roughness
+        (alpha = r^2); signed_normals / reconstruct_z: how `normals` stores its vectors; variance_scale 2 with
+        max_variance 0.18 is the clamp of Kaplanyan et al.  `normals` may be this texture.  Surfaces of equal dtypes
+        share one call.  specular_aa_results() returns the records.  False on an invalid, converted or 3-D texture, on
+        `normals` of other dimensions, faces or depth, with an image missing, and with fewer than 2 levels."""
+        import torch
+        if not isinstance(normals, Texture) or not self._valid or self._textures or self._dim == Dimension.Dim3D:
+            return False
+        if not normals._valid or normals._textures or self._mips < 2:
+            return False
+        if (normals._dim, normals._w, normals._h, normals._depth, normals._faces) != \
+                (self._dim, self._w, self._h, self._depth, self._faces):
+            return False
+        if any(im is None for level in self._images for dep in level for im in dep) or \
+                any(im is None for dep in normals._images[0] for im in dep):
+            return False
+        api.make_spec_aa_params(channel, perceptual, signed_normals, reconstruct_z, 0.5, variance_scale, max_variance)
+        device = "cuda:%d" % self._device_id
+        per = self._mips - 1
+        groups: Dict[tuple, List[Tuple[int, int]]] = {}
+        for d, dep in enumerate(self._images[0]):
+            for f, im in enumerate(dep):
+                groups.setdefault((normals._images[0][d][f].dtype.str, im.dtype.str), []).append((d, f))
+        records = {}
+        for where in groups.values():
+            n = len(where)
+
+            def upload(stack):
+                dev = torch.from_numpy(stack).to(device)
+                size = dev[0].numel()*dev.element_size()
+                return dev, [dev.data_ptr() + i*size for i in range(n)]
+            nstack = np.stack([np.ascontiguousarray(normals._images[0][d][f]) for d, f in where])
+            ndev, nptrs = upload(nstack)
+            rstack, rdev, rptrs = nstack, ndev, nptrs         # the normals' own surfaces when `normals` is this texture
+            if normals is not self:
+                rstack = np.stack([np.ascontiguousarray(self._images[0][d][f]) for d, f in where])
+                rdev, rptrs = upload(rstack)
+            levels = [upload(np.stack([_as_float32(np.ascontiguousarray(self._images[m][d][f])) for d, f in where]))
+                      for m in range(1, self._mips)]
+            res = torch.zeros((n*per, 4), dtype=torch.int32, device=device)
+            self._context().specular_aa_device(
+                nptrs, api.pixel_type_of(nstack[0]), self._w, self._h, nstack.strides[1],
+                [[levels[k][1][i] for k in range(per)] for i in range(n)], rough0=rptrs,
+                rough_pixel_type=api.pixel_type_of(rstack[0]), rough_pitch=rstack.strides[1], channel=channel,
+                perceptual=perceptual, signed_normals=signed_normals, reconstruct_z=reconstruct_z,
+                variance_scale=variance_scale, max_variance=max_variance, results=res.data_ptr())
+            rec = res.cpu().numpy().view(api.SPEC_AA_RESULT_DTYPE).reshape(n, per)
+            for k in range(per):
+                out = levels[k][0].cpu().numpy()
+                for i, (d, f) in enumerate(where):
+                    self._images[k + 1][d][f] = out[i]
+                    r = rec[i][k]
+                    records[(k + 1, d, f)] = dict(mip=k + 1, depth=d, face=f, clamped=int(r["clamped"]),
+                                                  saturated=int(r["saturated"]),
+                                                  max_added=float(np.uint32(r["max_added"]).view(np.float32)))
+        self._spec_aa = [records[k] for k in sorted(records)]
+        return True
+
+    def specular_aa_results(self):
+        """The records of the last specular_antialias(): one dict per level it wrote, in [mip][depth][face] order -- mip,
+        depth, face, clamped (texels whose variance met max_variance), saturated (texels whose alpha^2 reached 1) and
+        max_added (the largest variance added, after variance_scale); [] before any call."""
+        return [dict(r) for r in self._spec_aa]
 
     # ---- environment maps (Context.equirect_to_cube / cube_prefilter / cube_sh9) ------------------------------------
     @staticmethod

@@ -454,6 +454,82 @@ int cfhip_alpha_sdf_array_device(cfhip_ctx* ctx, const void* const* src, uint32_
 	uint32_t width, uint32_t height, size_t src_pitch_bytes, void* const* dst, int dst_pixel_type,
 	size_t dst_pitch_bytes, const cfhip_sdf_params* params, cfhip_sdf_result* results_device, void* stream);
 
+/* Specular anti-aliasing (Toksvig 2005; Han et al. 2007; Neubelt and Pettineo 2013; Kaplanyan et al. 2016): the levels
+ * of a roughness chain take up the variance of the level-0 normals inside each texel's footprint -- what averaging and
+ * renormalising a normal map discards -- so that a distant, bumpy surface renders rough instead of mirror-smooth.  Run
+ * on the generated roughness (or packed ORM) chain before it is encoded.  One channel of levels 1... is overwritten:
+ * the value written replaces the mip filter's own value in that channel (it is the footprint mean of alpha^2 plus the
+ * variance, not a correction of the filter's result).  Level 0, the other three channels and the normal map are never
+ * written.  Every step below is an IEEE double operation in the order written (the library is built without
+ * contraction): add, multiply, divide, sqrt, fmin / fmax and rint only, so results are defined to the bit.
+ *
+ *   input           per layer l: normals[l], level 0 of a normal map, width x height texels of normal_pixel_type, rows
+ *                   normal_pitch_bytes apart; rough0[l], level 0 of the roughness map, the same size, of
+ *                   rough_pixel_type, rows rough_pitch_bytes apart -- it may be the surface of the normals -- or
+ *                   rough0 == NULL: base_roughness in every texel; levels[l * (levels_count - 1) + (k - 1)], level k
+ *                   of the roughness chain, max(1, width >> k) x max(1, height >> k) tightly packed RGBA32F.
+ *   decode          RGBA8 (double)((float)(v / 255.0)), RGBA16F half -> double, RGBA32F as stored
+ *   normal          x = (double)c with CFHIP_SPEC_AA_SIGNED_NORMALS, else (double)c * 2.0 - 1.0; with
+ *                   CFHIP_SPEC_AA_RECONSTRUCT_Z (two-channel normals) the stored blue is ignored and
+ *                   z = sqrt(fmax(0.0, 1.0 - (x*x + y*y))); len = sqrt((x*x + y*y) + z*z); len not finite or not > 0:
+ *                   the normal is (0, 0, 1), else x / len component by component; qx = (int64)rint(nx * 2^30), ties
+ *                   to even, the same for y and z.
+ *   roughness       r = the decoded `channel` (or base_roughness); r >= 0 false (a NaN too): r = 0; r > 1: r = 1;
+ *                   alpha = r * r with CFHIP_SPEC_AA_PERCEPTUAL (the stored value is perceptual roughness), else r;
+ *                   qa = (int64)rint(alpha*alpha * 2^32).
+ *   footprint       of texel (x, y) of level k: the level-0 columns [x 2^k, (x + 1) 2^k), but to `width` for the last
+ *                   column of the level (x == w_k - 1); the same for rows.  Every level-0 texel belongs to exactly one
+ *                   texel of each level, and level k's texel is the union of level k-1's 2x and 2x + 1, plus 2x + 2 at
+ *                   an odd end: a 3 x 3 map has a 1 x 1 level 1 of all nine texels.
+ *   moments         Sx, Sy, Sz, Sa: the int64 sums of qx, qy, qz, qa over the footprint, N its texels.  A surface has at
+ *                   most 2^30 texels, so the sums fit; integer sums are exact in any order.
+ *   level texel     int64 -> double rounds to nearest even.  mx = (double)Sx / ((double)N * 2^30), the same for my, mz;
+ *                   A2 = (double)Sa / ((double)N * 2^32); L2 = (mx*mx + my*my) + mz*mz.
+ *                     L2 < 1.0 false: v = 0
+ *                     else L2 > 0 false: v = max_variance                                              (clamped)
+ *                     else L = sqrt(L2), t = (1.0 - L2) / (L * (3.0 - L2)), 1 / kappa of the vMF lobe of mean length L,
+ *                          v = fmin((double)max_variance, t)                         (clamped iff t < max_variance false)
+ *                   a2 = fmin(1.0, A2 + (double)variance_scale * v)   (saturated iff the sum < 1.0 is false)
+ *                   stored: (float)sqrt(a2), with PERCEPTUAL (float)sqrt(sqrt(a2))
+ *   results_device  layers * (levels_count - 1) records, [l * (levels_count - 1) + (k - 1)], or NULL for none: clamped
+ *                   and saturated texels of the level, max_added = the largest (float)((double)variance_scale * v) of
+ *                   the level as its bit pattern (an unsigned maximum: the values are not negative), reserved = 0.
+ *
+ * variance_scale 1 and max_variance 1 are the plain vMF form; 2 and 0.18 give the clamp of Kaplanyan et al.
+ * CFHIP_E_INVALID, before anything is enqueued: unknown flags, struct_size != sizeof(cfhip_spec_aa_params), channel > 3,
+ * a variance_scale or max_variance that is negative or not finite, base_roughness outside [0, 1], non-zero reserved
+ * words, levels_count < 2 or beyond the chain of width x height, layers outside 1 to 65535, sides outside 1 to 32768,
+ * more than 2^30 texels in a surface, a pitch below a row, normals[] or normal_pitch_bytes not aligned to a texel of
+ * their pixel type (4, 8 or 16 bytes: a normal is one load), rough0[] or rough_pitch_bytes not aligned to a component,
+ * levels[] entries not 16-byte aligned, a NULL entry.
+ *
+ * All layers share every launch, and a launch finishes five levels: a workgroup owns a 32 x 32 tile of its input (the
+ * last tile of a row or column takes the remainder, up to 63), reads it once, reduces the moments in LDS, stores the
+ * roughness of five levels and leaves the tile's moments (32 bytes) in the context's scratch for the next launch, whose
+ * input they are.  ceil((levels_count - 1) / 5) launches per call -- at most 3 -- on the call's stream; level 0 is read
+ * once; nothing waits for the host.  stream == NULL means the context's stream and the call synchronises.  Identical
+ * calls return identical bytes. */
+enum { CFHIP_SPEC_AA_PERCEPTUAL = 1, CFHIP_SPEC_AA_SIGNED_NORMALS = 2, CFHIP_SPEC_AA_RECONSTRUCT_Z = 4 };
+typedef struct cfhip_spec_aa_params {
+	uint32_t struct_size;
+	uint32_t flags;
+	uint32_t channel;
+	float base_roughness;
+	float variance_scale;
+	float max_variance;
+	uint32_t reserved[2];
+} cfhip_spec_aa_params;
+typedef struct cfhip_spec_aa_result {
+	uint32_t clamped;
+	uint32_t saturated;
+	uint32_t max_added;
+	uint32_t reserved;
+} cfhip_spec_aa_result;
+int cfhip_spec_aa_array_device(cfhip_ctx* ctx, const void* const* normals, uint32_t layers, int normal_pixel_type,
+	uint32_t width, uint32_t height, size_t normal_pitch_bytes, const void* const* rough0, int rough_pixel_type,
+	size_t rough_pitch_bytes, void* const* levels, uint32_t levels_count, const cfhip_spec_aa_params* params,
+	cfhip_spec_aa_result* results_device, void* stream);
+
 /* Environment maps for image-based lighting: an equirectangular panorama onto the six faces of a cube, the cube's
  * GGX-prefiltered mip chain (level k = the environment convolved with a lobe of roughness r_k), and its projection on
  * nine spherical-harmonic coefficients (the diffuse term).  Every formula below is a sequence of IEEE double operations
@@ -1295,7 +1371,7 @@ int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* p
 	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass), cfhip_alpha_coverage_device, cfhip_alpha_bleed_array_device, cfhip_alpha_sdf_array_device (every pass), cfhip_equirect_to_cube_device, cfhip_cube_prefilter_device (every level) or cfhip_cube_sh9_device (both launches) call on
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass), cfhip_alpha_coverage_device, cfhip_alpha_bleed_array_device, cfhip_alpha_sdf_array_device (every pass), cfhip_spec_aa_array_device (every launch), cfhip_equirect_to_cube_device, cfhip_cube_prefilter_device (every level) or cfhip_cube_sh9_device (both launches) call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
