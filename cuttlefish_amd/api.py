@@ -1133,6 +1133,38 @@ def pixel_type_of(arr: np.ndarray) -> PixelType:
     raise TypeError("pixel dtype %s not accepted at the boundary" % arr.dtype)
 
 
+# ---- marshalling: what the methods below hand to ctypes ----
+def _ptr(x):
+    """an optional pointer argument: an address, or 0 / None for NULL"""
+    return ctypes.c_void_p(int(x)) if x else None
+
+
+def _stream(s):
+    """a stream argument: the caller's hipStream_t as an int, or 0 for the context's own"""
+    return ctypes.c_void_p(s) if s else None
+
+
+def _ptr_array(ptrs, n_min=1):
+    """a C array of the addresses in ptrs, n_min entries at the least (an empty list still passes a pointer)"""
+    ptrs = [ctypes.c_void_p(int(p)) for p in ptrs]
+    return (ctypes.c_void_p * max(len(ptrs), n_min))(*ptrs)
+
+
+def _same_layers(srcs, levels, names):
+    """srcs[l] and levels[l][k-1] of the array calls -> (layers, the levels listed per layer)"""
+    if len(srcs) == 0 or len(levels) != len(srcs) or len({len(d) for d in levels}) != 1:
+        raise ValueError("%s and %s must list the same layers, every layer the same levels" % names)
+    return len(srcs), len(levels[0])
+
+
+def _rgba_host(image) -> np.ndarray:
+    """one image as the host conveniences take it: contiguous and (h, w, 4)"""
+    host = np.ascontiguousarray(image)
+    if host.ndim != 3 or host.shape[2] != 4:
+        raise ValueError("expected (h, w, 4)")
+    return host
+
+
 class Context:
     """One encoder context = one GPU (one process per GPU in multi-GPU jobs)."""
 
@@ -1164,6 +1196,16 @@ class Context:
     def _check(self, rc: int):
         if rc != 0:
             raise CfhipError(rc, self._lib.cfhip_last_error(self._h).decode())
+
+    def _upload(self, host: np.ndarray):
+        """the bytes of a contiguous host array as a uint8 tensor on this context's device"""
+        import torch
+        return torch.from_numpy(host.view(np.uint8)).to("cuda:%d" % self.device_id)
+
+    def _rgba_device(self, image):
+        """one (h, w, 4) image of the host conveniences -> (its contiguous array, its pixel type, its bytes on the device)"""
+        host = _rgba_host(image)
+        return host, pixel_type_of(host), self._upload(host)
 
     def encode(self, images: Iterable[np.ndarray], params: Params):
         """Host-buffer path (what HipConverter::process calls): list of (h, w, 4) arrays
@@ -1225,7 +1267,7 @@ class Context:
             surf[i].out_capacity = s["out_capacity"]
         self._check(self._lib.cfhip_encode_device(self._h, surf, len(surfaces),
                                                    ctypes.byref(params),
-                                                   ctypes.c_void_p(stream) if stream else None))
+                                                   _stream(stream)))
 
     def encode_pvrtc(self, images: Iterable[np.ndarray], params: Params):
         """PVRTC1 4 bpp (params.format 59 / 60): list of (h, w, 4) arrays, both sides powers of two (rows may run
@@ -1263,7 +1305,7 @@ class Context:
             surf[i].out = s["out"]
             surf[i].out_capacity = s["out_capacity"]
         self._check(self._lib.cfhip_pvrtc_encode_device(self._h, surf, len(surfaces), ctypes.byref(params),
-                                                         ctypes.c_void_p(stream) if stream else None))
+                                                         _stream(stream)))
 
     def decode_pvrtc(self, payload: np.ndarray, fmt, width: int, height: int, typ=Type.UNorm):
         """PVRTC1 4 bpp payload -> (height, width, 4) uint8 (alpha 255 for the RGB format)"""
@@ -1278,7 +1320,7 @@ class Context:
         """Device path of decode_pvrtc: blocks / out are device pointers as ints (4-byte aligned)."""
         self._check(self._lib.cfhip_pvrtc_decode_device(
             self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(out)),
-            out_pitch_bytes, ctypes.c_void_p(stream) if stream else None))
+            out_pitch_bytes, _stream(stream)))
 
     def decode_pvrtc_sse(self, payload: np.ndarray, ref: np.ndarray, fmt, typ=Type.UNorm):
         """Per-channel sums of squared differences between the decoded PVRTC1 payload and an (h, w, 4) uint8
@@ -1300,7 +1342,7 @@ class Context:
         """Device path of decode_pvrtc_sse: sse = device pointer to four uint64 (8-byte aligned, zeroed by the call)."""
         self._check(self._lib.cfhip_pvrtc_decode_sse_device(
             self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(ref)),
-            ref_pitch_bytes, ctypes.c_void_p(int(sse)), ctypes.c_void_p(stream) if stream else None))
+            ref_pitch_bytes, ctypes.c_void_p(int(sse)), _stream(stream)))
 
     def generate_mips_device(self, src: int, pixel_type, width: int, height: int,
                              row_pitch_bytes: int, dst_levels: Sequence[int],
@@ -1308,11 +1350,9 @@ class Context:
         """Texture::generateMipmaps on the GPU: level k (k = 1..len(dst_levels)) of a width x height
         texture into dst_levels[k-1] (device pointers, RGBA32F tightly packed), each level resized
         from the previous one in linear space.  filter: ResizeFilter (0 Box, 1 Linear)."""
-        n = len(dst_levels) + 1
-        arr = (ctypes.c_void_p * max(len(dst_levels), 1))(*[ctypes.c_void_p(int(p)) for p in dst_levels])
         self._check(self._lib.cfhip_generate_mips_device(
             self._h, ctypes.c_void_p(int(src)), int(pixel_type), width, height, row_pitch_bytes,
-            int(color_space), int(filter), arr, n, ctypes.c_void_p(stream) if stream else None))
+            int(color_space), int(filter), _ptr_array(dst_levels), len(dst_levels) + 1, _stream(stream)))
 
     def generate_mips_array_device(self, srcs: Sequence[int], pixel_type, width: int, height: int,
                                    row_pitch_bytes: int, dst_levels: Sequence[Sequence[int]],
@@ -1320,16 +1360,10 @@ class Context:
         """generate_mips_device for the layers of an array / cube texture in one call: srcs[l] = level 0
         of layer l, dst_levels[l][k-1] receives its level k.  One launch per pass and level for all
         layers; bit-identical to one call per layer."""
-        nl = len(srcs)
-        if nl == 0 or len(dst_levels) != nl or len({len(d) for d in dst_levels}) != 1:
-            raise ValueError("srcs and dst_levels must list the same layers, every layer the same levels")
-        per = len(dst_levels[0])
-        sarr = (ctypes.c_void_p * nl)(*[ctypes.c_void_p(int(p)) for p in srcs])
-        flat = [ctypes.c_void_p(int(p)) for d in dst_levels for p in d]
-        darr = (ctypes.c_void_p * max(len(flat), 1))(*flat)
+        nl, per = _same_layers(srcs, dst_levels, ("srcs", "dst_levels"))
         self._check(self._lib.cfhip_generate_mips_array_device(
-            self._h, sarr, nl, int(pixel_type), width, height, row_pitch_bytes, int(color_space), int(filter),
-            darr, per + 1, ctypes.c_void_p(stream) if stream else None))
+            self._h, _ptr_array(srcs), nl, int(pixel_type), width, height, row_pitch_bytes, int(color_space), int(filter),
+            _ptr_array([p for d in dst_levels for p in d]), per + 1, _stream(stream)))
 
     def mip_post_device(self, srcs: Sequence[int], pixel_type, width: int, height: int, row_pitch_bytes: int,
                         levels: Sequence[Sequence[int]], alpha_coverage: Optional[float] = None,
@@ -1340,17 +1374,11 @@ class Context:
         alpha >= t matches level 0's; normalize = "unorm" / "snorm" renormalises every RGB.  results: device pointer to
         len(srcs) * len(levels[0]) cfhip_mip_post_result records (MIP_POST_RESULT_DTYPE), required with alpha_coverage.
         Premultiplied colour is out of scope: the pass scales alpha alone, so run it on straight alpha."""
-        nl = len(srcs)
-        if nl == 0 or len(levels) != nl or len({len(d) for d in levels}) != 1:
-            raise ValueError("srcs and levels must list the same layers, every layer the same levels")
-        per = len(levels[0])
+        nl, per = _same_layers(srcs, levels, ("srcs", "levels"))
         params = make_mip_post_params(alpha_coverage, normalize)
-        sarr = (ctypes.c_void_p * nl)(*[ctypes.c_void_p(int(p)) for p in srcs])
-        flat = [ctypes.c_void_p(int(p)) for d in levels for p in d]
-        darr = (ctypes.c_void_p * max(len(flat), 1))(*flat)
         self._check(self._lib.cfhip_mip_post_array_device(
-            self._h, sarr, nl, int(pixel_type), width, height, row_pitch_bytes, darr, per + 1, ctypes.byref(params),
-            ctypes.c_void_p(int(results)) if results else None, ctypes.c_void_p(stream) if stream else None))
+            self._h, _ptr_array(srcs), nl, int(pixel_type), width, height, row_pitch_bytes,
+            _ptr_array([p for d in levels for p in d]), per + 1, ctypes.byref(params), _ptr(results), _stream(stream)))
 
     def alpha_coverage_device(self, surfaces: Sequence[dict], threshold: float, counts: int, scale: float = 1.0,
                               stream: int = 0):
@@ -1364,18 +1392,14 @@ class Context:
             surf[i].width, surf[i].height = s["width"], s["height"]
             surf[i].pitch_bytes = s["row_pitch_bytes"]
         self._check(self._lib.cfhip_alpha_coverage_device(
-            self._h, surf, len(surfaces), threshold, scale, ctypes.c_void_p(int(counts)) if counts else None,
-            ctypes.c_void_p(stream) if stream else None))
+            self._h, surf, len(surfaces), threshold, scale, _ptr(counts),
+            _stream(stream)))
 
     def alpha_coverage(self, image: np.ndarray, threshold: float, scale: float = 1.0) -> int:
         """Host convenience: the number of texels of an (h, w, 4) uint8 / float16 / float32 image whose alpha passes
         fl32(alpha * scale) >= threshold, counted on the GPU."""
         import torch
-        host = np.ascontiguousarray(image)
-        if host.ndim != 3 or host.shape[2] != 4:
-            raise ValueError("expected (h, w, 4)")
-        pt = pixel_type_of(host)
-        dev = torch.from_numpy(host.view(np.uint8)).to("cuda:%d" % self.device_id)
+        host, pt, dev = self._rgba_device(image)
         out = torch.zeros(1, dtype=torch.int32, device=dev.device)
         self.alpha_coverage_device([dict(pixels=dev.data_ptr(), pixel_type=pt, width=host.shape[1], height=host.shape[0],
                                          row_pitch_bytes=host.strides[0])], threshold, out.data_ptr(), scale)
@@ -1391,22 +1415,16 @@ class Context:
         cfhip_bleed_result records (BLEED_RESULT_DTYPE), or 0 for none.  One call is 2 + log2(P) launches whatever the
         number of layers, and takes 8 bytes of the context's scratch per texel.  The remedy for straight alpha: run it
         before mips and encoding, not on premultiplied colour."""
-        nl = len(images)
         params = make_bleed_params(threshold, wrap, max_distance)
-        arr = (ctypes.c_void_p * max(nl, 1))(*[ctypes.c_void_p(int(p)) for p in images])
         self._check(self._lib.cfhip_alpha_bleed_array_device(
-            self._h, arr, nl, int(pixel_type), width, height, row_pitch_bytes, ctypes.byref(params),
-            ctypes.c_void_p(int(results)) if results else None, ctypes.c_void_p(stream) if stream else None))
+            self._h, _ptr_array(images), len(images), int(pixel_type), width, height, row_pitch_bytes, ctypes.byref(params),
+            _ptr(results), _stream(stream)))
 
     def alpha_bleed(self, image: np.ndarray, threshold: float = 0.0, wrap=(False, False), max_distance: int = 0):
         """Host convenience: one (h, w, 4) uint8 / float16 / float32 image through alpha_bleed_device -> (the bled
         array of the same dtype, the record as a dict of seeds, filled, max_dist2, reserved)."""
         import torch
-        host = np.ascontiguousarray(image)
-        if host.ndim != 3 or host.shape[2] != 4:
-            raise ValueError("expected (h, w, 4)")
-        pt = pixel_type_of(host)
-        dev = torch.from_numpy(host.view(np.uint8)).to("cuda:%d" % self.device_id)
+        host, pt, dev = self._rgba_device(image)
         res = torch.zeros(4, dtype=torch.int32, device=dev.device)
         self.alpha_bleed_device([dev.data_ptr()], pt, host.shape[1], host.shape[0], host.strides[0], threshold, wrap,
                                 max_distance, res.data_ptr())
@@ -1428,12 +1446,9 @@ class Context:
         if len(dsts) != nl:
             raise ValueError("srcs and dsts must list the same layers")
         params = make_sdf_params(spread, scale, threshold, wrap, channels)
-        sarr = (ctypes.c_void_p * max(nl, 1))(*[ctypes.c_void_p(int(p)) for p in srcs])
-        darr = (ctypes.c_void_p * max(nl, 1))(*[ctypes.c_void_p(int(p)) for p in dsts])
         self._check(self._lib.cfhip_alpha_sdf_array_device(
-            self._h, sarr, nl, int(pixel_type), width, height, row_pitch_bytes, darr, int(dst_pixel_type),
-            dst_row_pitch_bytes, ctypes.byref(params), ctypes.c_void_p(int(results)) if results else None,
-            ctypes.c_void_p(stream) if stream else None))
+            self._h, _ptr_array(srcs), nl, int(pixel_type), width, height, row_pitch_bytes, _ptr_array(dsts),
+            int(dst_pixel_type), dst_row_pitch_bytes, ctypes.byref(params), _ptr(results), _stream(stream)))
 
     def alpha_sdf(self, image: np.ndarray, spread: int, scale: int = 1, threshold: float = 0.5, wrap=(False, False),
                   channels="a", out_dtype=None):
@@ -1442,9 +1457,7 @@ class Context:
         a dict of inside, saturated, reserved0, reserved1).  The other channels are zero, except at scale 1 with the
         image's own dtype, where they are the image's."""
         import torch
-        host = np.ascontiguousarray(image)
-        if host.ndim != 3 or host.shape[2] != 4:
-            raise ValueError("expected (h, w, 4)")
+        host = _rgba_host(image)
         make_sdf_params(spread, scale, threshold, wrap, channels)
         h, w = host.shape[:2]
         if h % scale or w % scale:
@@ -1452,7 +1465,7 @@ class Context:
         out_dtype = host.dtype if out_dtype is None else np.dtype(out_dtype)
         pt = pixel_type_of(host)
         dpt = pixel_type_of(np.empty(0, out_dtype))
-        dev = torch.from_numpy(host.view(np.uint8)).to("cuda:%d" % self.device_id)
+        dev = self._upload(host)
         if scale == 1 and out_dtype == host.dtype:
             out = dev.clone()
         else:
@@ -1480,23 +1493,16 @@ class Context:
         rows rough_pitch apart; it may be the normals' surface), or None: base_roughness in every texel.  results:
         device pointer to len(normals) * len(levels[0]) cfhip_spec_aa_result records (SPEC_AA_RESULT_DTYPE), or 0.
         One call is ceil(len(levels[0]) / 5) launches, at most 3, whatever the layers."""
-        nl = len(normals)
-        if nl == 0 or len(levels) != nl or len({len(d) for d in levels}) != 1:
-            raise ValueError("normals and levels must list the same layers, every layer the same levels")
+        nl, per = _same_layers(normals, levels, ("normals", "levels"))
         if rough0 is not None and (len(rough0) != nl or rough_pixel_type is None):
             raise ValueError("rough0 lists the layers of normals and comes with its rough_pixel_type")
-        per = len(levels[0])
         params = make_spec_aa_params(channel, perceptual, signed_normals, reconstruct_z, base_roughness, variance_scale,
                                      max_variance)
-        narr = (ctypes.c_void_p * nl)(*[ctypes.c_void_p(int(p)) for p in normals])
-        rarr = (ctypes.c_void_p * nl)(*[ctypes.c_void_p(int(p)) for p in rough0]) if rough0 is not None else None
-        flat = [ctypes.c_void_p(int(p)) for d in levels for p in d]
-        larr = (ctypes.c_void_p * max(len(flat), 1))(*flat)
         self._check(self._lib.cfhip_spec_aa_array_device(
-            self._h, narr, nl, int(pixel_type), width, height, pitch, rarr,
-            int(rough_pixel_type) if rough0 is not None else 0, rough_pitch if rough0 is not None else 0, larr, per + 1,
-            ctypes.byref(params), ctypes.c_void_p(int(results)) if results else None,
-            ctypes.c_void_p(stream) if stream else None))
+            self._h, _ptr_array(normals), nl, int(pixel_type), width, height, pitch,
+            _ptr_array(rough0) if rough0 is not None else None, int(rough_pixel_type) if rough0 is not None else 0,
+            rough_pitch if rough0 is not None else 0, _ptr_array([p for d in levels for p in d]), per + 1,
+            ctypes.byref(params), _ptr(results), _stream(stream)))
 
     def specular_aa(self, normals: np.ndarray, roughness0, levels_count: int, channel="g", perceptual: bool = True,
                     signed_normals: bool = False, reconstruct_z: bool = False, variance_scale: float = 1.0,
@@ -1506,13 +1512,11 @@ class Context:
         1 ... levels_count - 1 as float32 arrays of (max(1, h >> k), max(1, w >> k)), the records as a list of dicts).
         The values do not depend on any mip filter: they are the footprint mean of alpha^2 plus the variance."""
         import torch
-        host = np.ascontiguousarray(normals)
-        if host.ndim != 3 or host.shape[2] != 4:
-            raise ValueError("expected (h, w, 4)")
+        host = _rgba_host(normals)
         h, w = host.shape[:2]
         ch = spec_aa_channel(channel)
         device = "cuda:%d" % self.device_id
-        dev = torch.from_numpy(host.view(np.uint8)).to(device)
+        dev = self._upload(host)
         kw = dict(channel=ch, perceptual=perceptual, signed_normals=signed_normals, reconstruct_z=reconstruct_z,
                   variance_scale=variance_scale, max_variance=max_variance)
         keep = None
@@ -1520,7 +1524,7 @@ class Context:
             rh = np.ascontiguousarray(roughness0)
             if rh.shape != host.shape:
                 raise ValueError("the roughness map has the shape of the normal map")
-            keep = torch.from_numpy(rh.view(np.uint8)).to(device)
+            keep = self._upload(rh)
             kw.update(rough0=[keep.data_ptr()], rough_pixel_type=pixel_type_of(rh), rough_pitch=rh.strides[0])
         else:
             kw.update(base_roughness=float(roughness0))
@@ -1544,24 +1548,21 @@ class Context:
         row along +Y.  One launch."""
         if len(faces) != 6:
             raise ValueError("faces must list the six faces in CubeFace order")
-        arr = (ctypes.c_void_p * 6)(*[ctypes.c_void_p(int(p)) for p in faces])
         self._check(self._lib.cfhip_equirect_to_cube_device(
-            self._h, ctypes.c_void_p(int(src)), int(pixel_type), width, height, row_pitch_bytes, arr, face_size,
-            supersample, ctypes.c_void_p(stream) if stream else None))
+            self._h, ctypes.c_void_p(int(src)), int(pixel_type), width, height, row_pitch_bytes, _ptr_array(faces),
+            face_size, supersample, _stream(stream)))
 
     def equirect_to_cube(self, image: np.ndarray, face_size: int, supersample: int = 2) -> List[np.ndarray]:
         """Host convenience: one (h, w, 4) uint8 / float16 / float32 panorama through equirect_to_cube_device -> the six
         (face_size, face_size, 4) float32 faces in CubeFace order."""
         import torch
-        host = np.ascontiguousarray(image)
-        if host.ndim != 3 or host.shape[2] != 4:
-            raise ValueError("expected (h, w, 4)")
+        host = _rgba_host(image)
         if supersample not in ENV_SUPERSAMPLES:
             raise ValueError("supersample %r: one of %r" % (supersample, ENV_SUPERSAMPLES))
         if not 1 <= int(face_size) <= ENV_MAX_FACE:
             raise ValueError("face_size %r outside 1 to %d" % (face_size, ENV_MAX_FACE))
         n = int(face_size)
-        dev = torch.from_numpy(host.view(np.uint8)).to("cuda:%d" % self.device_id)
+        dev = self._upload(host)
         out = torch.empty((6, n, n, 4), dtype=torch.float32, device=dev.device)
         self.equirect_to_cube_device(dev.data_ptr(), pixel_type_of(host), host.shape[1], host.shape[0], host.strides[0],
                                      [out[f].data_ptr() for f in range(6)], n, int(supersample))
@@ -1585,12 +1586,11 @@ class Context:
         for t in keep:
             if t is not None and (t.ndim != 2 or t.shape[1] != 4):
                 raise ValueError("a table is (S, 4) float32: lx, ly, lz, lod")
-        sarr = (ctypes.c_void_p * max(6*L, 1))(*[ctypes.c_void_p(int(p)) for s in src_levels for p in s])
-        darr = (ctypes.c_void_p * max(6*K, 1))(*[ctypes.c_void_p(int(p)) for d in dst_levels for p in d])
-        tarr = (ctypes.c_void_p * max(K, 1))(*[ctypes.c_void_p(t.ctypes.data) if t is not None else None for t in keep])
+        tarr = _ptr_array([0 if t is None else t.ctypes.data for t in keep])
         counts = (ctypes.c_uint32 * max(K, 1))(*[0 if t is None else t.shape[0] for t in keep])
         self._check(self._lib.cfhip_cube_prefilter_device(
-            self._h, sarr, face_size, L, darr, K, tarr, counts, ctypes.c_void_p(stream) if stream else None))
+            self._h, _ptr_array([p for s in src_levels for p in s]), face_size, L,
+            _ptr_array([p for d in dst_levels for p in d]), K, tarr, counts, _stream(stream)))
 
     def cube_prefilter(self, faces: Sequence[np.ndarray], roughness: Sequence[float], samples: int = 256):
         """Host convenience: six (n, n, 4) float32 faces in CubeFace order -> one (6, n_k, n_k, 4) float32 array per entry
@@ -1624,10 +1624,7 @@ class Context:
         solid angle, then that sum.  Two launches; identical calls give identical bytes."""
         if len(faces) != 6:
             raise ValueError("faces must list the six faces in CubeFace order")
-        arr = (ctypes.c_void_p * 6)(*[ctypes.c_void_p(int(p)) for p in faces])
-        self._check(self._lib.cfhip_cube_sh9_device(
-            self._h, arr, face_size, ctypes.c_void_p(int(result)) if result else None,
-            ctypes.c_void_p(stream) if stream else None))
+        self._check(self._lib.cfhip_cube_sh9_device(self._h, _ptr_array(faces), face_size, _ptr(result), _stream(stream)))
 
     def cube_sh9(self, faces: Sequence[np.ndarray]):
         """Host convenience: six (n, n, 4) float32 faces -> (the (9, 4) float64 coefficients in the order 1, y, z, x, xy,
@@ -1648,12 +1645,9 @@ class Context:
                                color_space=ColorSpace.Linear, filter=0, stream: int = 0):
         """Texture::generateMipmaps for a 3-D texture on the GPU: level k into dst_levels[k-1] as
         max(1, depth >> k) tightly packed RGBA32F slices."""
-        n = len(dst_levels) + 1
-        arr = (ctypes.c_void_p * max(len(dst_levels), 1))(*[ctypes.c_void_p(int(p)) for p in dst_levels])
         self._check(self._lib.cfhip_generate_mips3d_device(
             self._h, ctypes.c_void_p(int(src)), int(pixel_type), width, height, depth, row_pitch_bytes,
-            slice_pitch_bytes, int(color_space), int(filter), arr, n,
-            ctypes.c_void_p(stream) if stream else None))
+            slice_pitch_bytes, int(color_space), int(filter), _ptr_array(dst_levels), len(dst_levels) + 1, _stream(stream)))
 
     def resize_device(self, src: int, pixel_type, width: int, height: int, row_pitch_bytes: int,
                       dst: int, dst_width: int, dst_height: int, color_space=ColorSpace.Linear,
@@ -1663,7 +1657,7 @@ class Context:
         self._check(self._lib.cfhip_resize_device(
             self._h, ctypes.c_void_p(int(src)), int(pixel_type), width, height, row_pitch_bytes,
             int(color_space), int(filter), ctypes.c_void_p(int(dst)), dst_width, dst_height,
-            ctypes.c_void_p(stream) if stream else None))
+            _stream(stream)))
 
     def image_ops_device(self, src: int, pixel_type, width: int, height: int, row_pitch_bytes: int, ops: ImageOps,
                          dst: int, dst_pitch_bytes: int, stream: int = 0):
@@ -1671,9 +1665,9 @@ class Context:
         pixel_type) -> dst (RGBA32F, height x width under a 90 / 270 degree rotation).  stream 0 = the context's
         stream (the call then synchronises)."""
         self._check(self._lib.cfhip_image_ops_device(
-            self._h, ctypes.c_void_p(int(src)) if src else None, int(pixel_type), width, height, row_pitch_bytes,
-            ctypes.byref(ops) if ops is not None else None, ctypes.c_void_p(int(dst)) if dst else None,
-            dst_pitch_bytes, ctypes.c_void_p(stream) if stream else None))
+            self._h, _ptr(src), int(pixel_type), width, height, row_pitch_bytes,
+            ctypes.byref(ops) if ops is not None else None, _ptr(dst),
+            dst_pitch_bytes, _stream(stream)))
 
     def decode(self, payload: np.ndarray, fmt, typ, width: int, height: int):
         """Decode a payload on the GPU -> ((height, width, C) array in the layout's dtype, error blocks).
@@ -1693,8 +1687,8 @@ class Context:
         pointers as ints.  stream 0 = the context's stream (the call then synchronises)."""
         self._check(self._lib.cfhip_decode_device(
             self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(out)),
-            out_pitch_bytes, ctypes.c_void_p(int(error_blocks)) if error_blocks else None,
-            ctypes.c_void_p(stream) if stream else None))
+            out_pitch_bytes, _ptr(error_blocks),
+            _stream(stream)))
 
     def decode_batch(self, payloads: Sequence[np.ndarray], fmt, typ, sizes: Sequence, out_pixel=None):
         """Decode every surface of a call in one launch (cfhip_decode_batch).  payloads[i] is the payload of a
@@ -1739,7 +1733,7 @@ class Context:
             surf[i].out_pitch_bytes = s["out_pitch_bytes"]
         self._check(self._lib.cfhip_decode_batch_device(
             self._h, int(fmt), int(typ), DECODE_NATIVE if out_pixel is None else int(out_pixel), surf, n,
-            ctypes.c_void_p(int(error_blocks)) if error_blocks else None, ctypes.c_void_p(stream) if stream else None))
+            _ptr(error_blocks), _stream(stream)))
 
     def decode_sse(self, payload: np.ndarray, ref: np.ndarray, fmt, typ=Type.UNorm):
         """Per-channel sums of squared differences between the decoded payload and an (h, w, 4) uint8
@@ -1761,7 +1755,7 @@ class Context:
         """Device path of decode_sse: sse = device pointer to four uint64 (8-byte aligned, zeroed by the call)."""
         self._check(self._lib.cfhip_decode_sse_device(
             self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(ref)),
-            ref_pitch_bytes, ctypes.c_void_p(int(sse)), ctypes.c_void_p(stream) if stream else None))
+            ref_pitch_bytes, ctypes.c_void_p(int(sse)), _stream(stream)))
 
     @staticmethod
     def _mask(mask):
@@ -1806,8 +1800,8 @@ class Context:
         self._check(self._lib.cfhip_compare_device(
             self._h, int(fmt), int(typ), ctypes.c_void_p(int(blocks)), width, height, ctypes.c_void_p(int(ref)),
             int(ref_pixel_type), ref_pitch_bytes, self._mask(mask), COMPARE_SSIM if ssim else 0,
-            ctypes.c_void_p(int(result)), ctypes.c_void_p(int(block_errors)) if block_errors else None,
-            block_errors_capacity, ctypes.c_void_p(stream) if stream else None))
+            ctypes.c_void_p(int(result)), _ptr(block_errors),
+            block_errors_capacity, _stream(stream)))
 
     def compare_batch(self, payloads: Sequence[np.ndarray], refs: Sequence[np.ndarray], fmt, typ=Type.UNorm,
                       mask=None, ssim: bool = False, block_map: bool = False) -> List[Comparison]:
@@ -1865,7 +1859,7 @@ class Context:
                 surf[i].block_errors_capacity = int(s.get("block_errors_capacity", 0))
         self._check(self._lib.cfhip_compare_batch_device(
             self._h, int(fmt), int(typ), surf, n, int(ref_pixel_type), self._mask(mask), COMPARE_SSIM if ssim else 0,
-            ctypes.c_void_p(int(results)) if results else None, ctypes.c_void_p(stream) if stream else None))
+            _ptr(results), _stream(stream)))
 
     def rdo(self, payloads: Sequence[np.ndarray], sources: Sequence[np.ndarray], fmt, typ=Type.UNorm, lam: float = 1.0,
             max_sse_increase: Optional[int] = None, mask=None, row_above: bool = False,
@@ -1921,7 +1915,7 @@ class Context:
             surf[i].row_pitch_bytes = s["row_pitch_bytes"]
         self._check(entry(
             self._h, int(fmt), int(typ), surf, n, ctypes.byref(params), self._mask(mask),
-            ctypes.c_void_p(int(stats)) if stats else None, ctypes.c_void_p(stream) if stream else None))
+            _ptr(stats), _stream(stream)))
 
     def lz_size(self, payloads) -> dict:
         """The deflate-size estimate (cfhip_lz_size) of a byte stream: one array / bytes object, or a sequence of them
@@ -1944,8 +1938,8 @@ class Context:
         arr = (LzSpan*max(len(spans), 1))()
         for i, (ptr, n) in enumerate(spans):
             arr[i].bytes, arr[i].n = int(ptr) or None, int(n)
-        self._check(self._lib.cfhip_lz_size_device(self._h, arr, len(spans), ctypes.c_void_p(int(out)) if out else None,
-                                                   ctypes.c_void_p(stream) if stream else None))
+        self._check(self._lib.cfhip_lz_size_device(self._h, arr, len(spans), _ptr(out),
+                                                   _stream(stream)))
 
     def lz_slice_bytes(self, nbytes: int = 0) -> int:
         """Set the slice the estimator cuts long streams into (whole blocks of 65536 bytes; 0: the default); returns
@@ -1992,8 +1986,8 @@ class Context:
         for i, (ptr, n) in enumerate(spans):
             arr[i].bytes, arr[i].n = int(ptr) or None, int(n)
         self._check(self._lib.cfhip_deflate_device(
-            self._h, arr, len(spans), ctypes.c_void_p(int(out)) if out else None, int(cap),
-            ctypes.c_void_p(int(result)) if result else None, ctypes.c_void_p(stream) if stream else None))
+            self._h, arr, len(spans), _ptr(out), int(cap),
+            _ptr(result), _stream(stream)))
 
     def deflate_stage_ms(self) -> dict:
         """Kernel ms of the last deflate's stages: keys, sort, match, parse, adler, codes, offsets, emit"""
@@ -2037,9 +2031,9 @@ class Context:
         for i, (ptr, n) in enumerate(spans):
             arr[i].bytes, arr[i].n = int(ptr) or None, int(n)
         self._check(self._lib.cfhip_deflate_indexed_device(
-            self._h, arr, len(spans), ctypes.c_void_p(int(out)) if out else None, int(cap),
-            ctypes.c_void_p(int(index)) if index else None, int(index_entries),
-            ctypes.c_void_p(int(result)) if result else None, ctypes.c_void_p(stream) if stream else None))
+            self._h, arr, len(spans), _ptr(out), int(cap),
+            _ptr(index), int(index_entries),
+            _ptr(result), _stream(stream)))
 
     def inflate(self, stream, index, n: int) -> bytes:
         """The n bytes of an indexed zlib stream (cfhip_inflate).  index: (entries, 2) integers, header_bit and token_bit
@@ -2069,10 +2063,8 @@ class Context:
         """Device path of inflate.  zstream, index (8-byte aligned), out (4-byte aligned) and result (one
         cfhip_inflate_result, 8-byte aligned) are device pointers.  An invalid stream is reported through the result's
         status, not raised.  stream 0 = the context's stream (the call then synchronises)."""
-        def ptr(v):
-            return ctypes.c_void_p(int(v)) if v else None
-        self._check(self._lib.cfhip_inflate_device(self._h, ptr(zstream), int(zbytes), ptr(index), int(index_entries),
-                                                   ptr(out), int(out_bytes), ptr(result), ptr(stream)))
+        self._check(self._lib.cfhip_inflate_device(self._h, _ptr(zstream), int(zbytes), _ptr(index), int(index_entries),
+                                                   _ptr(out), int(out_bytes), _ptr(result), _ptr(stream)))
 
     def inflate_stage_ms(self) -> dict:
         """Kernel ms of the last inflate's stages: decode, resolve, pack, fold"""
@@ -2108,8 +2100,8 @@ class Context:
         for i, (ptr, n) in enumerate(spans):
             arr[i].bytes, arr[i].n = int(ptr) or None, int(n)
         self._check(self._lib.cfhip_lz4_encode_device(
-            self._h, arr, len(spans), ctypes.c_void_p(int(out)) if out else None, int(cap),
-            ctypes.c_void_p(int(result)) if result else None, ctypes.c_void_p(stream) if stream else None))
+            self._h, arr, len(spans), _ptr(out), int(cap),
+            _ptr(result), _stream(stream)))
 
     def lz4_encode_stage_ms(self) -> dict:
         """Kernel ms of the last lz4_encode's stages: keys, sort, match, parse, plan, offsets, emit, hash, final"""
@@ -2142,10 +2134,8 @@ class Context:
         """Device path of lz4_decode.  frame, out (4-byte aligned) and result (one cfhip_lz4_decode_result, 8-byte
         aligned) are device pointers.  An invalid frame is reported through the result's status, not raised.  stream 0 =
         the context's stream (the call then synchronises)."""
-        def ptr(v):
-            return ctypes.c_void_p(int(v)) if v else None
-        self._check(self._lib.cfhip_lz4_decode_device(self._h, ptr(frame), int(nbytes), ptr(out), int(out_bytes),
-                                                      ptr(result), ptr(stream)))
+        self._check(self._lib.cfhip_lz4_decode_device(self._h, _ptr(frame), int(nbytes), _ptr(out), int(out_bytes),
+                                                      _ptr(result), _ptr(stream)))
 
     def lz4_decode_stage_ms(self) -> dict:
         """Kernel ms of the last lz4_decode's stages: chain, blocks, final"""
@@ -2184,11 +2174,9 @@ class Context:
         pointer to cap >= png_bound(...) bytes, any alignment; result: device pointer to one cfhip_png_result
         (overwritten; its bytes_out says where the file ends), 8-byte aligned.  stream 0 = the context's stream (the
         call then synchronises)."""
-        def ptr(v):
-            return ctypes.c_void_p(int(v)) if v else None
-        self._check(self._lib.cfhip_png_encode_device(self._h, ptr(pixels), int(pixel_type), int(pitch_bytes), int(width),
+        self._check(self._lib.cfhip_png_encode_device(self._h, _ptr(pixels), int(pixel_type), int(pitch_bytes), int(width),
                                                       int(height), int(color_type), int(bit_depth), int(color_space),
-                                                      ptr(out), int(cap), ptr(result), ptr(stream)))
+                                                      _ptr(out), int(cap), _ptr(result), _ptr(stream)))
 
     def png_stage_ms(self) -> dict:
         """Kernel ms of the last png_encode's stages: filter, the zlib encoder's eight, crc, final"""
@@ -2241,8 +2229,8 @@ class Context:
         res = RdoTargetResult()
         self._check(self._lib.cfhip_rdo_target_device(
             self._h, int(fmt), int(typ), surf, n, ctypes.byref(params), self._mask(mask),
-            ctypes.c_void_p(int(stats)) if stats else None, float(target_ratio), ctypes.byref(res),
-            ctypes.c_void_p(stream) if stream else None))
+            _ptr(stats), float(target_ratio), ctypes.byref(res),
+            _stream(stream)))
         return res.as_dict()
 
     def unpack(self, payload: np.ndarray, fmt, typ, width: int, height: int) -> np.ndarray:
@@ -2260,8 +2248,8 @@ class Context:
         """Device path of unpack: pixels (any alignment) / out (RGBA32F rows out_pitch_bytes apart, 4-byte aligned)
         are device pointers as ints.  stream 0 = the context's stream (the call then synchronises)."""
         self._check(self._lib.cfhip_std_unpack_device(
-            self._h, int(fmt), int(typ), ctypes.c_void_p(int(pixels)) if pixels else None, width, height,
-            ctypes.c_void_p(int(out)) if out else None, out_pitch_bytes, ctypes.c_void_p(stream) if stream else None))
+            self._h, int(fmt), int(typ), _ptr(pixels), width, height,
+            _ptr(out), out_pitch_bytes, _stream(stream)))
 
     def compare_std(self, payload: np.ndarray, ref: np.ndarray, fmt, typ=Type.UNorm, mask=None,
                     ssim: bool = False) -> Comparison:
@@ -2287,10 +2275,10 @@ class Context:
         """Device path of compare_std: pixels / ref / result (one cfhip_compare_result) are device pointers as
         ints.  stream 0 = the context's stream (the call then synchronises)."""
         self._check(self._lib.cfhip_std_compare_device(
-            self._h, int(fmt), int(typ), ctypes.c_void_p(int(pixels)) if pixels else None, width, height,
-            ctypes.c_void_p(int(ref)) if ref else None, int(ref_pixel_type), ref_pitch_bytes, self._mask(mask),
-            COMPARE_SSIM if ssim else 0, ctypes.c_void_p(int(result)) if result else None,
-            ctypes.c_void_p(stream) if stream else None))
+            self._h, int(fmt), int(typ), _ptr(pixels), width, height,
+            _ptr(ref), int(ref_pixel_type), ref_pitch_bytes, self._mask(mask),
+            COMPARE_SSIM if ssim else 0, _ptr(result),
+            _stream(stream)))
 
     def last_kernel_ms(self) -> float:
         return float(self._lib.cfhip_last_kernel_ms(self._h))

@@ -244,6 +244,8 @@ int fail(cfhip_ctx* ctx, int code, const char* fmt, ...)
 
 #define HIP_TRY(ctx, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
 	return fail((ctx), CFHIP_E_DEVICE, "%s: %s", #expr, hipGetErrorString(e_)); } while (0)
+// the same for a step that returns one of the library's own codes, its text already set
+#define CF_TRY(expr) do { const int rc_ = (expr); if (rc_ != CFHIP_OK) return rc_; } while (0)
 
 // ---- ASTC: footprints.  The per-footprint device table (partition lists, config lists, infill
 // and quantisation tables) is built by csrc/astc_tables.h once per format and context.
@@ -790,6 +792,169 @@ void begin_call(cfhip_ctx* ctx, hipStream_t stream, const char* kernel)
 	if (kernel)
 		ctx->last_kernel = kernel;
 	ctx->stages.owner = nullptr;
+}
+
+// ---- the image passes on device surfaces (mip post-pass, alpha bleeding, distance field, specular AA, environment
+// maps): one frame for what follows their argument checks, one vocabulary for the checks themselves ------------------
+// The frame, inside the body that guarded() runs: the NULL context reported last, the device, the lease on the call's
+// stream, the event reset with the name the call leaves in last_kernel, the two staging buffers at the sizes the pass
+// takes (0: not taken), then body(stream) -- the uploads and launches -- and the lease's success exit.  Any failure
+// returns with the lease unfinished, which drains what was enqueued.
+template <class Body>
+int device_pass(cfhip_ctx* ctx, void* stream_, const char* kernel, size_t batch_bytes, size_t src_bytes, Body&& body)
+{
+	if (!ctx)
+		return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
+	HIP_TRY(ctx, hipSetDevice(ctx->device));
+	StagingLease lease(ctx, call_stream(ctx, stream_));
+	begin_call(ctx, lease.stream, kernel);
+	CF_TRY(lease.acquire());
+	CF_TRY(reserve(ctx, &ctx->d_batch, &ctx->batch_cap, batch_bytes));
+	CF_TRY(reserve(ctx, &ctx->d_src, &ctx->src_cap, src_bytes));
+	CF_TRY(body(lease.stream));
+	return lease.done(!stream_);
+}
+
+// Host tables of pointers, one after the other into d_batch: slots[i] is where tabs[i] went.  A table of no entries
+// takes no room and is not read.  Pageable sources: the runtime stages each copy before returning.
+struct PtrTable {
+	const void* const* host;
+	size_t count;
+};
+
+template <size_t N>
+int upload_tables(cfhip_ctx* ctx, hipStream_t stream, const PtrTable (&tabs)[N], void** (&slots)[N])
+{
+	void** at = static_cast<void**>(ctx->d_batch);
+	for (size_t i = 0; i < N; at += tabs[i++].count) {
+		slots[i] = at;
+		if (tabs[i].count)
+			HIP_TRY(ctx, hipMemcpyAsync(at, tabs[i].host, tabs[i].count*sizeof(void*), hipMemcpyHostToDevice, stream));
+	}
+	return CFHIP_OK;
+}
+
+// A pass's launches, every one a timed span of its own; after the first failure the rest are skipped and rc keeps it.
+struct LaunchChain {
+	cfhip_ctx* ctx;
+	hipStream_t stream;
+	const char* what;
+	int rc = CFHIP_OK;
+
+	LaunchChain(cfhip_ctx* c, hipStream_t s, const char* w) : ctx(c), stream(s), what(w) {}
+
+	template <class Launch>
+	void operator()(Launch&& launch)
+	{
+		if (rc == CFHIP_OK)
+			rc = timed(ctx, stream, what, launch);
+	}
+};
+
+// The levels of a full chain: floor(log2(max(w, h))) + 1 (maxMipmapLevels, Texture.cpp)
+uint32_t chain_levels(uint32_t width, uint32_t height)
+{
+	uint32_t levels = 1;
+	for (uint32_t d = std::max(width, height); d > 1; d >>= 1)
+		++levels;
+	return levels;
+}
+
+uint32_t cube_levels(uint32_t face_size)
+{
+	return chain_levels(face_size, face_size);
+}
+
+// The checks' vocabulary: `what` names the pass, `name` the argument as the header spells it.  Every pass calls them in
+// its own order, the per-element ones from its own loop over the layers: which fault of several is reported is part of
+// the ABI.
+int check_given(cfhip_ctx* ctx, const char* what, const char* name, const void* p)
+{
+	return p ? CFHIP_OK : fail(ctx, CFHIP_E_INVALID, "%s: %s is NULL", what, name);
+}
+
+int check_layers(cfhip_ctx* ctx, const char* what, uint32_t layers)
+{
+	if (!layers || layers > 65535u)
+		return fail(ctx, CFHIP_E_INVALID, "%s: layers is %u (1 to 65535 per call)", what, layers);
+	return CFHIP_OK;
+}
+
+int check_sides(cfhip_ctx* ctx, const char* what, uint32_t width, uint32_t height, uint32_t max_side)
+{
+	if (!width || !height || width > max_side || height > max_side)
+		return fail(ctx, CFHIP_E_INVALID, "%s: width and height are 1 to %u each, not %ux%u", what, max_side, width, height);
+	return CFHIP_OK;
+}
+
+// *bytes: a texel of the pixel type
+int check_pixel_type(cfhip_ctx* ctx, const char* what, const char* name, int pixel_type, size_t* bytes)
+{
+	*bytes = pixel_bytes(pixel_type);
+	return *bytes ? CFHIP_OK : fail(ctx, CFHIP_E_INVALID, "%s: %s %d", what, name, pixel_type);
+}
+
+int check_row_pitch(cfhip_ctx* ctx, const char* what, const char* name, size_t pitch, size_t row)
+{
+	return pitch >= row ? CFHIP_OK : fail(ctx, CFHIP_E_INVALID, "%s: %s %zu < %zu, a row", what, name, pitch, row);
+}
+
+// unit_name: "a component" (a quarter of the texel) or "a texel"
+int check_pitch_aligned(cfhip_ctx* ctx, const char* what, const char* name, size_t pitch, size_t unit, const char* unit_name)
+{
+	if (pitch % unit)
+		return fail(ctx, CFHIP_E_INVALID, "%s: %s %zu not aligned to %s (%zu bytes)", what, name, pitch, unit_name, unit);
+	return CFHIP_OK;
+}
+
+int check_item_given(cfhip_ctx* ctx, const char* what, const char* name, uint32_t i, const void* p)
+{
+	return p ? CFHIP_OK : fail(ctx, CFHIP_E_INVALID, "%s: %s[%u] is NULL", what, name, i);
+}
+
+int check_item_aligned(cfhip_ctx* ctx, const char* what, const char* name, uint32_t i, const void* p, size_t unit,
+	const char* unit_name)
+{
+	if ((uintptr_t)p % unit)
+		return fail(ctx, CFHIP_E_INVALID, "%s: %s[%u] not aligned to %s (%zu bytes)", what, name, i, unit_name, unit);
+	return CFHIP_OK;
+}
+
+// level k of layer l in the levels list of a generated chain: RGBA32F, `per` listed levels a layer
+int check_chain_level(cfhip_ctx* ctx, const char* what, void* const* levels, uint32_t per, uint32_t l, uint32_t k)
+{
+	const size_t i = (size_t)l*per + (k - 1u);
+	if (!levels[i])
+		return fail(ctx, CFHIP_E_INVALID, "%s: levels[%zu] (layer %u, level %u) is NULL", what, i, l, k);
+	if ((uintptr_t)levels[i] % 16u)
+		return fail(ctx, CFHIP_E_INVALID, "%s: levels[%zu] is not aligned to a texel (16 bytes)", what, i);
+	return CFHIP_OK;
+}
+
+int check_flags(cfhip_ctx* ctx, const char* what, uint32_t flags, uint32_t known)
+{
+	return (flags & ~known) ? fail(ctx, CFHIP_E_INVALID, "%s: params->flags 0x%x: unknown", what, flags) : CFHIP_OK;
+}
+
+// the alpha threshold of the passes that split texels at alpha > t
+int check_threshold(cfhip_ctx* ctx, const char* what, float t)
+{
+	if (!(t >= 0.0f && t < 1.0f))
+		return fail(ctx, CFHIP_E_INVALID, "%s: params->alpha_threshold %g outside [0, 1)", what, (double)t);
+	return CFHIP_OK;
+}
+
+// the six faces of a cube, each face_size^2 tightly packed RGBA32F
+int check_faces(cfhip_ctx* ctx, const char* what, const void* const* faces, uint32_t face_size)
+{
+	CF_TRY(check_given(ctx, what, "faces", faces));
+	if (!face_size || face_size > CFENV_MAX_FACE)
+		return fail(ctx, CFHIP_E_INVALID, "%s: face_size is 1 to %u, not %u", what, CFENV_MAX_FACE, face_size);
+	for (uint32_t f = 0; f < 6u; ++f) {
+		CF_TRY(check_item_given(ctx, what, "faces", f, faces[f]));
+		CF_TRY(check_item_aligned(ctx, what, "faces", f, faces[f], 16u, "a texel"));
+	}
+	return CFHIP_OK;
 }
 
 // ---- the stream codecs' stage logs (estimator, deflate, inflate, LZ4, PNG: the sections far below) ------------------
@@ -1921,9 +2086,7 @@ static int check_mip_args(cfhip_ctx* ctx, const char* what, int pixel_type, int 
 	if (!filter_valid(filter))
 		return fail(ctx, CFHIP_E_INVALID, "%s: resize filter %d", what, filter);
 	// maxMipmapLevels: floor(log2(max(w, h, d))) + 1 (Texture.cpp)
-	uint32_t max_levels = 1;
-	for (uint32_t d = std::max({width, height, depth}); d > 1; d >>= 1)
-		++max_levels;
+	const uint32_t max_levels = chain_levels(std::max(width, depth), height);
 	if (levels > max_levels && depth)
 		return fail(ctx, CFHIP_E_INVALID, "%u mip levels requested, a %ux%ux%u texture has %u", levels,
 			width, height, depth, max_levels);
@@ -2129,10 +2292,9 @@ int cfhip_alpha_coverage_device(cfhip_ctx* ctx, const cfhip_coverage_surface* su
 	float scale, uint32_t* counts_device, void* stream_)
 {
 	return guarded(ctx, "alpha_coverage", [&]() -> int {
-		if (!surfaces)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: surfaces is NULL");
-		if (!counts_device)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: counts_device is NULL");
+		const char* const what = "alpha_coverage";
+		CF_TRY(check_given(ctx, what, "surfaces", surfaces));
+		CF_TRY(check_given(ctx, what, "counts_device", counts_device));
 		if (!count)
 			return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: count is 0");
 		if (!(threshold > 0.0f && threshold <= 1.0f))
@@ -2170,27 +2332,16 @@ int cfhip_alpha_coverage_device(cfhip_ctx* ctx, const cfhip_coverage_surface* su
 			if (wg > 0x7FFFFFFFull)
 				return fail(ctx, CFHIP_E_INVALID, "alpha_coverage: the surfaces are too large for one launch");
 		}
-		if (!ctx)
-			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, call_stream(ctx, stream_));
-		const hipStream_t stream = lease.stream;
-		begin_call(ctx, stream, "cfhip_mip_post_gather_kernel");
-		int rc = lease.acquire();
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab.size()*sizeof(cfmp_surf));
-		if (rc != CFHIP_OK)
-			return rc;
-		// pageable source: the runtime stages the copy before returning, so `tab` may die
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, tab.data(), tab.size()*sizeof(cfmp_surf), hipMemcpyHostToDevice, stream));
-		HIP_TRY(ctx, hipMemsetAsync(counts_device, 0, (size_t)count*4u, stream));
-		rc = timed(ctx, stream, "mip post-pass", [&] {
-			return cfhip_launch_mip_post_gather(static_cast<const cfmp_surf*>(ctx->d_batch), count, 0u, (uint32_t)wg, threshold,
-				scale, scale, scale, 1u, 1u, nullptr, counts_device, stream);
+		const size_t tab_bytes = tab.size()*sizeof(cfmp_surf);
+		return device_pass(ctx, stream_, "cfhip_mip_post_gather_kernel", tab_bytes, 0, [&](hipStream_t stream) -> int {
+			// pageable source: the runtime stages the copy before returning, so `tab` may die
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, tab.data(), tab_bytes, hipMemcpyHostToDevice, stream));
+			HIP_TRY(ctx, hipMemsetAsync(counts_device, 0, (size_t)count*4u, stream));
+			return timed(ctx, stream, "mip post-pass", [&] {
+				return cfhip_launch_mip_post_gather(static_cast<const cfmp_surf*>(ctx->d_batch), count, 0u, (uint32_t)wg, threshold,
+					scale, scale, scale, 1u, 1u, nullptr, counts_device, stream);
+			});
 		});
-		if (rc != CFHIP_OK)
-			return rc;
-		return lease.done(!stream_);
 	});
 }
 
@@ -2200,22 +2351,16 @@ int cfhip_mip_post_array_device(cfhip_ctx* ctx, const void* const* srcs, uint32_
 {
 	static_assert(sizeof(cfhip_mip_post_params) == 8 && sizeof(cfhip_mip_post_result) == 16, "the ABI's sizes");
 	return guarded(ctx, "mip_post", [&]() -> int {
-		if (!params)
-			return fail(ctx, CFHIP_E_INVALID, "mip_post: params is NULL");
-		if (!srcs)
-			return fail(ctx, CFHIP_E_INVALID, "mip_post: srcs is NULL");
-		if (!levels)
-			return fail(ctx, CFHIP_E_INVALID, "mip_post: levels is NULL");
-		if (!layers || layers > 65535u)
-			return fail(ctx, CFHIP_E_INVALID, "mip_post: layers is %u (1 to 65535 per call)", layers);
+		const char* const what = "mip_post";
+		CF_TRY(check_given(ctx, what, "params", params));
+		CF_TRY(check_given(ctx, what, "srcs", srcs));
+		CF_TRY(check_given(ctx, what, "levels", levels));
+		CF_TRY(check_layers(ctx, what, layers));
 		if (!width || !height)
 			return fail(ctx, CFHIP_E_INVALID, "mip_post: a zero width or height (%ux%u)", width, height);
-		const size_t pb = pixel_bytes(src_pixel_type);
-		if (!pb)
-			return fail(ctx, CFHIP_E_INVALID, "mip_post: src_pixel_type %d", src_pixel_type);
-		uint32_t max_levels = 1;
-		for (uint32_t d = std::max(width, height); d > 1; d >>= 1)
-			++max_levels;
+		size_t pb;
+		CF_TRY(check_pixel_type(ctx, what, "src_pixel_type", src_pixel_type, &pb));
+		const uint32_t max_levels = chain_levels(width, height);
 		if (levels_count < 2 || levels_count > max_levels)
 			return fail(ctx, CFHIP_E_INVALID, "mip_post: levels_count is %u, a chain to repair has 2 to %u levels at %ux%u",
 				levels_count, max_levels, width, height);
@@ -2229,8 +2374,7 @@ int cfhip_mip_post_array_device(cfhip_ctx* ctx, const void* const* srcs, uint32_
 		const float t = params->alpha_threshold;
 		if (coverage && !(t > 0.0f && t <= 1.0f))
 			return fail(ctx, CFHIP_E_INVALID, "mip_post: params->alpha_threshold %g outside (0, 1]", (double)t);
-		if (src_pitch_bytes < (size_t)width*pb)
-			return fail(ctx, CFHIP_E_INVALID, "mip_post: src_pitch_bytes %zu < %zu, a row", src_pitch_bytes, (size_t)width*pb);
+		CF_TRY(check_row_pitch(ctx, what, "src_pitch_bytes", src_pitch_bytes, (size_t)width*pb));
 		if (coverage && !results_device)
 			return fail(ctx, CFHIP_E_INVALID, "mip_post: results_device is NULL under COVERAGE");
 		if ((uint64_t)width*height > CFMP_MAX_TEXELS)
@@ -2240,16 +2384,12 @@ int cfhip_mip_post_array_device(cfhip_ctx* ctx, const void* const* srcs, uint32_
 		std::vector<cfmp_surf> tab(nsurf);
 		uint64_t wg = 0, plane = 0;
 		for (uint32_t l = 0; l < layers; ++l) {
-			if (!srcs[l])
-				return fail(ctx, CFHIP_E_INVALID, "mip_post: srcs[%u] is NULL", l);
+			CF_TRY(check_item_given(ctx, what, "srcs", l, srcs[l]));
 			if (coverage && !alpha_aligned(srcs[l], src_pitch_bytes, src_pixel_type))
 				return fail(ctx, CFHIP_E_INVALID, "mip_post: srcs[%u] or src_pitch_bytes not aligned to a component", l);
 			for (uint32_t k = 1; k < levels_count; ++k) {
+				CF_TRY(check_chain_level(ctx, what, levels, per, l, k));
 				const size_t i = (size_t)l*per + (k - 1u);
-				if (!levels[i])
-					return fail(ctx, CFHIP_E_INVALID, "mip_post: levels[%zu] (layer %u, level %u) is NULL", i, l, k);
-				if ((uintptr_t)levels[i] % 16u)
-					return fail(ctx, CFHIP_E_INVALID, "mip_post: levels[%zu] is not aligned to a texel (16 bytes)", i);
 				cfmp_surf& e = tab[i];
 				e.width = (width >> k) ? (width >> k) : 1u;
 				e.height = (height >> k) ? (height >> k) : 1u;
@@ -2279,63 +2419,47 @@ int cfhip_mip_post_array_device(cfhip_ctx* ctx, const void* const* srcs, uint32_
 		}
 		if (wg > 0x7FFFFFFFull)
 			return fail(ctx, CFHIP_E_INVALID, "mip_post: the surfaces are too large for one launch");
-		if (!ctx)
-			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, call_stream(ctx, stream_));
-		const hipStream_t stream = lease.stream;
-		begin_call(ctx, stream, coverage ? "cfhip_mip_post_count_kernel" : "cfhip_mip_post_apply_kernel");
 		// d_batch: the surface table, then the levels' search states, then the counters; d_src: the alpha plane
 		const size_t tab_bytes = (nsurf*sizeof(cfmp_surf) + 15u) & ~(size_t)15u;
 		const size_t state_bytes = coverage ? nlev*sizeof(cfmp_state) : 0u;
 		const size_t cnt_bytes = coverage ? nsurf*CFMP_SLOTS*4u : 0u;
-		int rc = lease.acquire();
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, tab_bytes + state_bytes + cnt_bytes);
-		if (rc == CFHIP_OK && coverage)
-			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, (size_t)plane*4u);
-		if (rc != CFHIP_OK)
-			return rc;
-		uint8_t* base = static_cast<uint8_t*>(ctx->d_batch);
-		const cfmp_surf* d_tab = reinterpret_cast<const cfmp_surf*>(base);
-		cfmp_state* d_state = coverage ? reinterpret_cast<cfmp_state*>(base + tab_bytes) : nullptr;
-		uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base + tab_bytes + state_bytes);
-		// pageable source: the runtime stages the copy before returning, so `tab` may die
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, tab.data(), nsurf*sizeof(cfmp_surf), hipMemcpyHostToDevice, stream));
-		// every launch of the pass is a timed span of its own
-		const auto post = [&](auto&& launch) { return timed(ctx, stream, "mip post-pass", launch); };
-		if (coverage) {
-			// (the states too: a level's first decide step writes every field it later reads, dir included)
-			HIP_TRY(ctx, hipMemsetAsync(base + tab_bytes, 0, state_bytes + cnt_bytes, stream));
-			float* d_plane = static_cast<float*>(ctx->d_src);
-			const float s_min = 0.25f, s_max = 4.0f;
-			const auto decide = [&](int first) {
-				return post([&] {
-					return cfhip_launch_mip_post_decide(d_tab, (uint32_t)nlev, first, d_state, d_cnt, results_device, stream);
+		const char* const kernel = coverage ? "cfhip_mip_post_count_kernel" : "cfhip_mip_post_apply_kernel";
+		return device_pass(ctx, stream_, kernel, tab_bytes + state_bytes + cnt_bytes, coverage ? (size_t)plane*4u : 0u,
+			[&](hipStream_t stream) -> int {
+			uint8_t* base = static_cast<uint8_t*>(ctx->d_batch);
+			const cfmp_surf* d_tab = reinterpret_cast<const cfmp_surf*>(base);
+			cfmp_state* d_state = coverage ? reinterpret_cast<cfmp_state*>(base + tab_bytes) : nullptr;
+			uint32_t* d_cnt = reinterpret_cast<uint32_t*>(base + tab_bytes + state_bytes);
+			// pageable source: the runtime stages the copy before returning, so `tab` may die
+			HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, tab.data(), nsurf*sizeof(cfmp_surf), hipMemcpyHostToDevice, stream));
+			LaunchChain post(ctx, stream, "mip post-pass");
+			if (coverage) {
+				// (the states too: a level's first decide step writes every field it later reads, dir included)
+				HIP_TRY(ctx, hipMemsetAsync(base + tab_bytes, 0, state_bytes + cnt_bytes, stream));
+				float* d_plane = static_cast<float*>(ctx->d_src);
+				const float s_min = 0.25f, s_max = 4.0f;
+				const auto decide = [&](int first) {
+					post([&] {
+						return cfhip_launch_mip_post_decide(d_tab, (uint32_t)nlev, first, d_state, d_cnt, results_device, stream);
+					});
+				};
+				post([&] {
+					return cfhip_launch_mip_post_gather(d_tab, (uint32_t)nsurf, (uint32_t)nlev, (uint32_t)wg, t, 1.0f, s_min, s_max, 3u,
+						CFMP_SLOTS, d_plane, d_cnt, stream);
 				});
-			};
-			rc = post([&] {
-				return cfhip_launch_mip_post_gather(d_tab, (uint32_t)nsurf, (uint32_t)nlev, (uint32_t)wg, t, 1.0f, s_min, s_max, 3u,
-					CFMP_SLOTS, d_plane, d_cnt, stream);
-			});
-			if (rc == CFHIP_OK)
-				rc = decide(1);
-			for (uint32_t pass = 0; rc == CFHIP_OK && pass < CFMP_SEARCH_PASSES; ++pass) {
-				rc = post([&] {
-					return cfhip_launch_mip_post_count(d_tab, (uint32_t)nlev, (uint32_t)wg_levels, t, d_state, d_plane, d_cnt, stream);
-				});
-				if (rc == CFHIP_OK)
-					rc = decide(0);
+				decide(1);
+				for (uint32_t pass = 0; pass < CFMP_SEARCH_PASSES; ++pass) {
+					post([&] {
+						return cfhip_launch_mip_post_count(d_tab, (uint32_t)nlev, (uint32_t)wg_levels, t, d_state, d_plane, d_cnt, stream);
+					});
+					decide(0);
+				}
 			}
-			if (rc != CFHIP_OK)
-				return rc;
-		}
-		rc = post([&] {
-			return cfhip_launch_mip_post_apply(d_tab, (uint32_t)nlev, (uint32_t)wg_levels, flags, d_state, stream);
+			post([&] {
+				return cfhip_launch_mip_post_apply(d_tab, (uint32_t)nlev, (uint32_t)wg_levels, flags, d_state, stream);
+			});
+			return post.rc;
 		});
-		if (rc != CFHIP_OK)
-			return rc;
-		return lease.done(!stream_);
 	});
 }
 
@@ -2345,82 +2469,58 @@ int cfhip_alpha_bleed_array_device(cfhip_ctx* ctx, void* const* images, uint32_t
 {
 	static_assert(sizeof(cfhip_bleed_params) == 12 && sizeof(cfhip_bleed_result) == 16, "the ABI's sizes");
 	return guarded(ctx, "alpha_bleed", [&]() -> int {
-		if (!params)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params is NULL");
-		if (!images)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: images is NULL");
-		if (!layers || layers > 65535u)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: layers is %u (1 to 65535 per call)", layers);
-		if (!width || !height || width > CFAB_MAX_SIDE || height > CFAB_MAX_SIDE)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: width and height are 1 to %u each, not %ux%u", CFAB_MAX_SIDE, width, height);
-		const size_t pb = pixel_bytes(pixel_type);
-		if (!pb)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: pixel_type %d", pixel_type);
-		if (params->flags & ~(uint32_t)(CFHIP_BLEED_WRAP_X | CFHIP_BLEED_WRAP_Y))
-			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params->flags 0x%x: unknown", params->flags);
+		const char* const what = "alpha_bleed";
+		CF_TRY(check_given(ctx, what, "params", params));
+		CF_TRY(check_given(ctx, what, "images", images));
+		CF_TRY(check_layers(ctx, what, layers));
+		CF_TRY(check_sides(ctx, what, width, height, CFAB_MAX_SIDE));
+		size_t pb;
+		CF_TRY(check_pixel_type(ctx, what, "pixel_type", pixel_type, &pb));
+		CF_TRY(check_flags(ctx, what, params->flags, CFHIP_BLEED_WRAP_X | CFHIP_BLEED_WRAP_Y));
 		const float t = params->alpha_threshold;
-		if (!(t >= 0.0f && t < 1.0f))
-			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params->alpha_threshold %g outside [0, 1)", (double)t);
+		CF_TRY(check_threshold(ctx, what, t));
 		if (params->max_distance > 65535u)
 			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: params->max_distance %u above 65535", params->max_distance);
-		if (pitch_bytes < (size_t)width*pb)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: pitch_bytes %zu < %zu, a row", pitch_bytes, (size_t)width*pb);
-		if (pitch_bytes % (pb/4u))
-			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: pitch_bytes %zu not aligned to a component (%zu bytes)", pitch_bytes, pb/4u);
+		CF_TRY(check_row_pitch(ctx, what, "pitch_bytes", pitch_bytes, (size_t)width*pb));
+		CF_TRY(check_pitch_aligned(ctx, what, "pitch_bytes", pitch_bytes, pb/4u, "a component"));
 		const uint64_t texels = (uint64_t)layers*width*height;
 		if (texels > CFAB_MAX_TEXELS)
 			return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: more than 2^31 texels in one call");
 		for (uint32_t l = 0; l < layers; ++l) {
-			if (!images[l])
-				return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: images[%u] is NULL", l);
-			if ((uintptr_t)images[l] % (pb/4u))
-				return fail(ctx, CFHIP_E_INVALID, "alpha_bleed: images[%u] not aligned to a component (%zu bytes)", l, pb/4u);
+			CF_TRY(check_item_given(ctx, what, "images", l, images[l]));
+			CF_TRY(check_item_aligned(ctx, what, "images", l, images[l], pb/4u, "a component"));
 		}
-		if (!ctx)
-			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, call_stream(ctx, stream_));
-		const hipStream_t stream = lease.stream;
-		begin_call(ctx, stream, "cfhip_alpha_bleed_step_kernel");
 		// d_batch: the layers' pointers; d_src: the two seed buffers, 4 bytes per texel each
-		int rc = lease.acquire();
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, (size_t)layers*sizeof(void*));
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, (size_t)texels*8u);
-		if (rc != CFHIP_OK)
-			return rc;
-		// pageable source: the runtime stages the copy before returning
-		HIP_TRY(ctx, hipMemcpyAsync(ctx->d_batch, images, (size_t)layers*sizeof(void*), hipMemcpyHostToDevice, stream));
-		if (results_device)
-			HIP_TRY(ctx, hipMemsetAsync(results_device, 0, (size_t)layers*sizeof(cfhip_bleed_result), stream));
-		cfab_call call;
-		call.images = static_cast<void* const*>(ctx->d_batch);
-		call.pitch = pitch_bytes;
-		call.width = width; call.height = height;
-		call.pixel_type = pixel_type;
-		call.flags = params->flags;
-		uint32_t* buf[2] = {static_cast<uint32_t*>(ctx->d_src), static_cast<uint32_t*>(ctx->d_src) + texels};
-		uint32_t p2 = 1;
-		while (p2 < std::max(width, height))
-			p2 <<= 1;
-		// on a wrapped axis positions are taken modulo the size: so is the step
-		const auto sx = [&](uint32_t k) { return (call.flags & CFHIP_BLEED_WRAP_X) ? k % width : k; };
-		const auto sy = [&](uint32_t k) { return (call.flags & CFHIP_BLEED_WRAP_Y) ? k % height : k; };
-		// every launch of the pass is a timed span of its own
-		const auto bleed = [&](auto&& launch) { return timed(ctx, stream, "alpha_bleed", launch); };
-		rc = bleed([&] { return cfhip_launch_alpha_bleed_seed(&call, layers, t, buf[0], results_device, stream); });
-		int cur = 0;
-		for (uint32_t k = p2 >> 1; rc == CFHIP_OK && k >= 1u; k >>= 1, cur ^= 1)
-			rc = bleed([&] { return cfhip_launch_alpha_bleed_step(&call, layers, sx(k), sy(k), buf[cur], buf[cur ^ 1], stream); });
-		if (rc == CFHIP_OK)
-			rc = bleed([&] {
+		return device_pass(ctx, stream_, "cfhip_alpha_bleed_step_kernel", (size_t)layers*sizeof(void*), (size_t)texels*8u,
+			[&](hipStream_t stream) -> int {
+			void** table[1];
+			CF_TRY(upload_tables(ctx, stream, {{images, layers}}, table));
+			if (results_device)
+				HIP_TRY(ctx, hipMemsetAsync(results_device, 0, (size_t)layers*sizeof(cfhip_bleed_result), stream));
+			cfab_call call;
+			call.images = table[0];
+			call.pitch = pitch_bytes;
+			call.width = width; call.height = height;
+			call.pixel_type = pixel_type;
+			call.flags = params->flags;
+			uint32_t* buf[2] = {static_cast<uint32_t*>(ctx->d_src), static_cast<uint32_t*>(ctx->d_src) + texels};
+			uint32_t p2 = 1;
+			while (p2 < std::max(width, height))
+				p2 <<= 1;
+			// on a wrapped axis positions are taken modulo the size: so is the step
+			const auto sx = [&](uint32_t k) { return (call.flags & CFHIP_BLEED_WRAP_X) ? k % width : k; };
+			const auto sy = [&](uint32_t k) { return (call.flags & CFHIP_BLEED_WRAP_Y) ? k % height : k; };
+			LaunchChain bleed(ctx, stream, "alpha_bleed");
+			bleed([&] { return cfhip_launch_alpha_bleed_seed(&call, layers, t, buf[0], results_device, stream); });
+			int cur = 0;
+			for (uint32_t k = p2 >> 1; k >= 1u; k >>= 1, cur ^= 1)
+				bleed([&] { return cfhip_launch_alpha_bleed_step(&call, layers, sx(k), sy(k), buf[cur], buf[cur ^ 1], stream); });
+			bleed([&] {
 				return cfhip_launch_alpha_bleed_fill(&call, layers, sx(1u), sy(1u), params->max_distance*params->max_distance,
 					buf[cur], results_device, stream);
 			});
-		if (rc != CFHIP_OK)
-			return rc;
-		return lease.done(!stream_);
+			return bleed.rc;
+		});
 	});
 }
 
@@ -2431,26 +2531,18 @@ int cfhip_alpha_sdf_array_device(cfhip_ctx* ctx, const void* const* src, uint32_
 {
 	static_assert(sizeof(cfhip_sdf_params) == 24 && sizeof(cfhip_sdf_result) == 16, "the ABI's sizes");
 	return guarded(ctx, "alpha_sdf", [&]() -> int {
-		if (!params)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: params is NULL");
-		if (!src)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: src is NULL");
-		if (!dst)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst is NULL");
-		if (!layers || layers > 65535u)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: layers is %u (1 to 65535 per call)", layers);
-		if (!width || !height || width > CFSD_MAX_SIDE || height > CFSD_MAX_SIDE)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: width and height are 1 to %u each, not %ux%u", CFSD_MAX_SIDE, width, height);
-		const size_t spb = pixel_bytes(src_pixel_type), dpb = pixel_bytes(dst_pixel_type);
-		if (!spb)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: src_pixel_type %d", src_pixel_type);
-		if (!dpb)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst_pixel_type %d", dst_pixel_type);
-		if (params->flags & ~(uint32_t)(CFHIP_SDF_WRAP_X | CFHIP_SDF_WRAP_Y))
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: params->flags 0x%x: unknown", params->flags);
+		const char* const what = "alpha_sdf";
+		CF_TRY(check_given(ctx, what, "params", params));
+		CF_TRY(check_given(ctx, what, "src", src));
+		CF_TRY(check_given(ctx, what, "dst", dst));
+		CF_TRY(check_layers(ctx, what, layers));
+		CF_TRY(check_sides(ctx, what, width, height, CFSD_MAX_SIDE));
+		size_t spb, dpb;
+		CF_TRY(check_pixel_type(ctx, what, "src_pixel_type", src_pixel_type, &spb));
+		CF_TRY(check_pixel_type(ctx, what, "dst_pixel_type", dst_pixel_type, &dpb));
+		CF_TRY(check_flags(ctx, what, params->flags, CFHIP_SDF_WRAP_X | CFHIP_SDF_WRAP_Y));
 		const float t = params->alpha_threshold;
-		if (!(t >= 0.0f && t < 1.0f))
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: params->alpha_threshold %g outside [0, 1)", (double)t);
+		CF_TRY(check_threshold(ctx, what, t));
 		if (params->spread < 1u || params->spread > CFSD_MAX_SPREAD)
 			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: params->spread %u outside 1 to %u", params->spread, CFSD_MAX_SPREAD);
 		const uint32_t s = params->scale;
@@ -2462,78 +2554,51 @@ int cfhip_alpha_sdf_array_device(cfhip_ctx* ctx, const void* const* src, uint32_
 			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: params->reserved is %u, not 0", params->reserved);
 		if (width % s || height % s)
 			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: %ux%u is not a multiple of the scale %u", width, height, s);
-		if (src_pitch_bytes < (size_t)width*spb)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: src_pitch_bytes %zu < %zu, a row", src_pitch_bytes, (size_t)width*spb);
-		if (src_pitch_bytes % (spb/4u))
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: src_pitch_bytes %zu not aligned to a component (%zu bytes)", src_pitch_bytes,
-				spb/4u);
-		if (dst_pitch_bytes < (size_t)(width/s)*dpb)
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst_pitch_bytes %zu < %zu, a row", dst_pitch_bytes, (size_t)(width/s)*dpb);
-		if (dst_pitch_bytes % (dpb/4u))
-			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst_pitch_bytes %zu not aligned to a component (%zu bytes)", dst_pitch_bytes,
-				dpb/4u);
+		CF_TRY(check_row_pitch(ctx, what, "src_pitch_bytes", src_pitch_bytes, (size_t)width*spb));
+		CF_TRY(check_pitch_aligned(ctx, what, "src_pitch_bytes", src_pitch_bytes, spb/4u, "a component"));
+		CF_TRY(check_row_pitch(ctx, what, "dst_pitch_bytes", dst_pitch_bytes, (size_t)(width/s)*dpb));
+		CF_TRY(check_pitch_aligned(ctx, what, "dst_pitch_bytes", dst_pitch_bytes, dpb/4u, "a component"));
 		const uint64_t texels = (uint64_t)layers*width*height;
 		if (texels > CFSD_MAX_TEXELS)
 			return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: more than 2^31 texels in one call");
 		for (uint32_t l = 0; l < layers; ++l) {
-			if (!src[l])
-				return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: src[%u] is NULL", l);
-			if (!dst[l])
-				return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst[%u] is NULL", l);
-			if ((uintptr_t)src[l] % (spb/4u))
-				return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: src[%u] not aligned to a component (%zu bytes)", l, spb/4u);
-			if ((uintptr_t)dst[l] % (dpb/4u))
-				return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst[%u] not aligned to a component (%zu bytes)", l, dpb/4u);
+			CF_TRY(check_item_given(ctx, what, "src", l, src[l]));
+			CF_TRY(check_item_given(ctx, what, "dst", l, dst[l]));
+			CF_TRY(check_item_aligned(ctx, what, "src", l, src[l], spb/4u, "a component"));
+			CF_TRY(check_item_aligned(ctx, what, "dst", l, dst[l], dpb/4u, "a component"));
 			// in place: every alpha is read before anything is written, but only a surface of the same geometry is one
 			if (dst[l] == src[l] && (s != 1u || dst_pixel_type != src_pixel_type))
 				return fail(ctx, CFHIP_E_INVALID, "alpha_sdf: dst[%u] equals src[%u]: in place needs scale 1 and equal pixel types", l, l);
 		}
-		if (!ctx)
-			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, call_stream(ctx, stream_));
-		const hipStream_t stream = lease.stream;
-		begin_call(ctx, stream, "cfhip_alpha_sdf_column_kernel");
 		// d_batch: the layers' source pointers, then their destination pointers.  d_src: the bit plane (whole words per
 		// row), e (16 bits per texel, scale > 1 only), the row bytes -- in the order of their alignment
 		const size_t plane_bytes = (size_t)layers*height*((width + 63u)/64u)*8u, e_bytes = s > 1u ? (size_t)texels*2u : 0u;
-		int rc = lease.acquire();
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, (size_t)layers*2u*sizeof(void*));
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, plane_bytes + e_bytes + (size_t)texels);
-		if (rc != CFHIP_OK)
-			return rc;
-		// pageable sources: the runtime stages the copies before returning
-		void** table = static_cast<void**>(ctx->d_batch);
-		HIP_TRY(ctx, hipMemcpyAsync(table, src, (size_t)layers*sizeof(void*), hipMemcpyHostToDevice, stream));
-		HIP_TRY(ctx, hipMemcpyAsync(table + layers, dst, (size_t)layers*sizeof(void*), hipMemcpyHostToDevice, stream));
-		if (results_device)
-			HIP_TRY(ctx, hipMemsetAsync(results_device, 0, (size_t)layers*sizeof(cfhip_sdf_result), stream));
-		cfsd_call call;
-		call.src = table;
-		call.dst = table + layers;
-		call.src_pitch = src_pitch_bytes; call.dst_pitch = dst_pitch_bytes;
-		call.width = width; call.height = height;
-		call.src_type = src_pixel_type; call.dst_type = dst_pixel_type;
-		call.flags = params->flags;
-		call.spread = params->spread; call.scale = s; call.channel_mask = params->channel_mask;
-		uint8_t* scratch = static_cast<uint8_t*>(ctx->d_src);
-		uint64_t* plane = reinterpret_cast<uint64_t*>(scratch);
-		uint16_t* e = reinterpret_cast<uint16_t*>(scratch + plane_bytes);
-		uint8_t* rows = scratch + plane_bytes + e_bytes;
-		// every launch of the pass is a timed span of its own
-		const auto sdf = [&](auto&& launch) { return timed(ctx, stream, "alpha_sdf", launch); };
-		rc = sdf([&] { return cfhip_launch_alpha_sdf_classify(&call, layers, t, plane, results_device, stream); });
-		if (rc == CFHIP_OK)
-			rc = sdf([&] { return cfhip_launch_alpha_sdf_row(&call, layers, plane, rows, stream); });
-		if (rc == CFHIP_OK)
-			rc = sdf([&] { return cfhip_launch_alpha_sdf_column(&call, layers, rows, e, results_device, stream); });
-		if (rc == CFHIP_OK && s > 1u)
-			rc = sdf([&] { return cfhip_launch_alpha_sdf_resolve(&call, layers, e, stream); });
-		if (rc != CFHIP_OK)
-			return rc;
-		return lease.done(!stream_);
+		return device_pass(ctx, stream_, "cfhip_alpha_sdf_column_kernel", (size_t)layers*2u*sizeof(void*),
+			plane_bytes + e_bytes + (size_t)texels, [&](hipStream_t stream) -> int {
+			void** table[2];
+			CF_TRY(upload_tables(ctx, stream, {{src, layers}, {dst, layers}}, table));
+			if (results_device)
+				HIP_TRY(ctx, hipMemsetAsync(results_device, 0, (size_t)layers*sizeof(cfhip_sdf_result), stream));
+			cfsd_call call;
+			call.src = table[0];
+			call.dst = table[1];
+			call.src_pitch = src_pitch_bytes; call.dst_pitch = dst_pitch_bytes;
+			call.width = width; call.height = height;
+			call.src_type = src_pixel_type; call.dst_type = dst_pixel_type;
+			call.flags = params->flags;
+			call.spread = params->spread; call.scale = s; call.channel_mask = params->channel_mask;
+			uint8_t* scratch = static_cast<uint8_t*>(ctx->d_src);
+			uint64_t* plane = reinterpret_cast<uint64_t*>(scratch);
+			uint16_t* e = reinterpret_cast<uint16_t*>(scratch + plane_bytes);
+			uint8_t* rows = scratch + plane_bytes + e_bytes;
+			LaunchChain sdf(ctx, stream, "alpha_sdf");
+			sdf([&] { return cfhip_launch_alpha_sdf_classify(&call, layers, t, plane, results_device, stream); });
+			sdf([&] { return cfhip_launch_alpha_sdf_row(&call, layers, plane, rows, stream); });
+			sdf([&] { return cfhip_launch_alpha_sdf_column(&call, layers, rows, e, results_device, stream); });
+			if (s > 1u)
+				sdf([&] { return cfhip_launch_alpha_sdf_resolve(&call, layers, e, stream); });
+			return sdf.rc;
+		});
 	});
 }
 
@@ -2545,27 +2610,23 @@ int cfhip_spec_aa_array_device(cfhip_ctx* ctx, const void* const* normals, uint3
 {
 	static_assert(sizeof(cfhip_spec_aa_params) == 32 && sizeof(cfhip_spec_aa_result) == 16, "the ABI's sizes");
 	static_assert(sizeof(cfsa_moments) == 32, "a tile's moments in the scratch");
+	static_assert(CFSA_MAX_LAYERS == 65535u, "check_layers' range");
 	return guarded(ctx, "spec_aa", [&]() -> int {
-		if (!params)
-			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params is NULL");
+		const char* const what = "spec_aa";
+		CF_TRY(check_given(ctx, what, "params", params));
 		if (params->struct_size != sizeof(cfhip_spec_aa_params))
 			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params->struct_size is %u, not %zu", params->struct_size,
 				sizeof(cfhip_spec_aa_params));
-		if (!normals)
-			return fail(ctx, CFHIP_E_INVALID, "spec_aa: normals is NULL");
-		if (!levels)
-			return fail(ctx, CFHIP_E_INVALID, "spec_aa: levels is NULL");
-		if (!layers || layers > CFSA_MAX_LAYERS)
-			return fail(ctx, CFHIP_E_INVALID, "spec_aa: layers is %u (1 to %u per call)", layers, CFSA_MAX_LAYERS);
-		if (!width || !height || width > CFSA_MAX_SIDE || height > CFSA_MAX_SIDE)
-			return fail(ctx, CFHIP_E_INVALID, "spec_aa: width and height are 1 to %u each, not %ux%u", CFSA_MAX_SIDE, width, height);
-		const size_t npb = pixel_bytes(normal_pixel_type), rpb = rough0 ? pixel_bytes(rough_pixel_type) : 0u;
-		if (!npb)
-			return fail(ctx, CFHIP_E_INVALID, "spec_aa: normal_pixel_type %d", normal_pixel_type);
-		if (rough0 && !rpb)
-			return fail(ctx, CFHIP_E_INVALID, "spec_aa: rough_pixel_type %d", rough_pixel_type);
-		if (params->flags & ~(uint32_t)(CFHIP_SPEC_AA_PERCEPTUAL | CFHIP_SPEC_AA_SIGNED_NORMALS | CFHIP_SPEC_AA_RECONSTRUCT_Z))
-			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params->flags 0x%x: unknown", params->flags);
+		CF_TRY(check_given(ctx, what, "normals", normals));
+		CF_TRY(check_given(ctx, what, "levels", levels));
+		CF_TRY(check_layers(ctx, what, layers));
+		CF_TRY(check_sides(ctx, what, width, height, CFSA_MAX_SIDE));
+		size_t npb, rpb = 0;
+		CF_TRY(check_pixel_type(ctx, what, "normal_pixel_type", normal_pixel_type, &npb));
+		if (rough0)
+			CF_TRY(check_pixel_type(ctx, what, "rough_pixel_type", rough_pixel_type, &rpb));
+		CF_TRY(check_flags(ctx, what, params->flags,
+			CFHIP_SPEC_AA_PERCEPTUAL | CFHIP_SPEC_AA_SIGNED_NORMALS | CFHIP_SPEC_AA_RECONSTRUCT_Z));
 		if (params->channel > 3u)
 			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params->channel %u above 3", params->channel);
 		if (!(params->base_roughness >= 0.0f && params->base_roughness <= 1.0f))
@@ -2578,48 +2639,29 @@ int cfhip_spec_aa_array_device(cfhip_ctx* ctx, const void* const* normals, uint3
 				(double)params->max_variance);
 		if (params->reserved[0] || params->reserved[1])
 			return fail(ctx, CFHIP_E_INVALID, "spec_aa: params->reserved is not 0");
-		uint32_t chain = 0;
-		for (uint32_t side = std::max(width, height); side; side >>= 1)
-			++chain;
+		const uint32_t chain = chain_levels(width, height);
 		if (levels_count < 2u || levels_count > chain)
 			return fail(ctx, CFHIP_E_INVALID, "spec_aa: levels_count %u outside 2 to %u, the chain of %ux%u", levels_count, chain,
 				width, height);
 		if ((uint64_t)width*height > CFSA_MAX_TEXELS)
 			return fail(ctx, CFHIP_E_INVALID, "spec_aa: more than 2^30 texels in level 0");
-		if (normal_pitch_bytes < (size_t)width*npb)
-			return fail(ctx, CFHIP_E_INVALID, "spec_aa: normal_pitch_bytes %zu < %zu, a row", normal_pitch_bytes, (size_t)width*npb);
-		if (normal_pitch_bytes % npb)
-			return fail(ctx, CFHIP_E_INVALID, "spec_aa: normal_pitch_bytes %zu not aligned to a texel (%zu bytes)", normal_pitch_bytes,
-				npb);
-		if (rough0 && rough_pitch_bytes < (size_t)width*rpb)
-			return fail(ctx, CFHIP_E_INVALID, "spec_aa: rough_pitch_bytes %zu < %zu, a row", rough_pitch_bytes, (size_t)width*rpb);
-		if (rough0 && rough_pitch_bytes % (rpb/4u))
-			return fail(ctx, CFHIP_E_INVALID, "spec_aa: rough_pitch_bytes %zu not aligned to a component (%zu bytes)",
-				rough_pitch_bytes, rpb/4u);
+		CF_TRY(check_row_pitch(ctx, what, "normal_pitch_bytes", normal_pitch_bytes, (size_t)width*npb));
+		CF_TRY(check_pitch_aligned(ctx, what, "normal_pitch_bytes", normal_pitch_bytes, npb, "a texel"));
+		if (rough0) {
+			CF_TRY(check_row_pitch(ctx, what, "rough_pitch_bytes", rough_pitch_bytes, (size_t)width*rpb));
+			CF_TRY(check_pitch_aligned(ctx, what, "rough_pitch_bytes", rough_pitch_bytes, rpb/4u, "a component"));
+		}
 		const uint32_t per = levels_count - 1u;
 		for (uint32_t l = 0; l < layers; ++l) {
-			if (!normals[l])
-				return fail(ctx, CFHIP_E_INVALID, "spec_aa: normals[%u] is NULL", l);
-			if ((uintptr_t)normals[l] % npb)
-				return fail(ctx, CFHIP_E_INVALID, "spec_aa: normals[%u] not aligned to a texel (%zu bytes)", l, npb);
-			if (rough0 && !rough0[l])
-				return fail(ctx, CFHIP_E_INVALID, "spec_aa: rough0[%u] is NULL", l);
-			if (rough0 && (uintptr_t)rough0[l] % (rpb/4u))
-				return fail(ctx, CFHIP_E_INVALID, "spec_aa: rough0[%u] not aligned to a component (%zu bytes)", l, rpb/4u);
-			for (uint32_t k = 1; k < levels_count; ++k) {
-				const size_t i = (size_t)l*per + (k - 1u);
-				if (!levels[i])
-					return fail(ctx, CFHIP_E_INVALID, "spec_aa: levels[%zu] (layer %u, level %u) is NULL", i, l, k);
-				if ((uintptr_t)levels[i] % 16u)
-					return fail(ctx, CFHIP_E_INVALID, "spec_aa: levels[%zu] is not aligned to a texel (16 bytes)", i);
+			CF_TRY(check_item_given(ctx, what, "normals", l, normals[l]));
+			CF_TRY(check_item_aligned(ctx, what, "normals", l, normals[l], npb, "a texel"));
+			if (rough0) {
+				CF_TRY(check_item_given(ctx, what, "rough0", l, rough0[l]));
+				CF_TRY(check_item_aligned(ctx, what, "rough0", l, rough0[l], rpb/4u, "a component"));
 			}
+			for (uint32_t k = 1; k < levels_count; ++k)
+				CF_TRY(check_chain_level(ctx, what, levels, per, l, k));
 		}
-		if (!ctx)
-			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, call_stream(ctx, stream_));
-		const hipStream_t stream = lease.stream;
-		begin_call(ctx, stream, "cfhip_spec_aa_texel_kernel");
 		// d_batch: the layers' normals, their roughness maps (if any), then the levels.  d_src: a launch's last moments
 		// are the next one's input -- level 5, then level 10, layer after layer
 		const auto dim = [](uint32_t d, uint32_t k) { return (d >> k) ? (d >> k) : 1u; };
@@ -2629,124 +2671,71 @@ int cfhip_spec_aa_array_device(cfhip_ctx* ctx, const void* const* normals, uint3
 			const uint32_t k = (s + 1u)*CFSA_STAGE_LEVELS;
 			moments[s] = (size_t)layers*dim(width, k)*dim(height, k);
 		}
-		const size_t ntab = (size_t)layers*(rough0 ? 2u : 1u) + (size_t)layers*per;
-		int rc = lease.acquire();
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, ntab*sizeof(void*));
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, std::max<size_t>((moments[0] + moments[1])*sizeof(cfsa_moments), 16u));
-		if (rc != CFHIP_OK)
-			return rc;
-		// pageable sources: the runtime stages the copies before returning
-		void** table = static_cast<void**>(ctx->d_batch);
-		void** d_rough = table + layers;
-		void** d_levels = d_rough + (rough0 ? layers : 0u);
-		HIP_TRY(ctx, hipMemcpyAsync(table, normals, (size_t)layers*sizeof(void*), hipMemcpyHostToDevice, stream));
-		if (rough0)
-			HIP_TRY(ctx, hipMemcpyAsync(d_rough, rough0, (size_t)layers*sizeof(void*), hipMemcpyHostToDevice, stream));
-		HIP_TRY(ctx, hipMemcpyAsync(d_levels, levels, (size_t)layers*per*sizeof(void*), hipMemcpyHostToDevice, stream));
-		if (results_device)
-			HIP_TRY(ctx, hipMemsetAsync(results_device, 0, (size_t)layers*per*sizeof(cfhip_spec_aa_result), stream));
-		cfsa_call call;
-		call.normals = table;
-		call.rough0 = rough0 ? d_rough : nullptr;
-		call.levels = d_levels;
-		call.normal_pitch = normal_pitch_bytes;
-		call.rough_pitch = rough0 ? rough_pitch_bytes : 0u;
-		call.width = width; call.height = height;
-		call.levels_count = levels_count;
-		call.normal_type = normal_pixel_type;
-		call.rough_type = rough0 ? rough_pixel_type : 0;
-		call.flags = params->flags;
-		call.channel = params->channel;
-		call.base_roughness = params->base_roughness;
-		call.variance_scale = params->variance_scale;
-		call.max_variance = params->max_variance;
-		cfsa_moments* const m0 = static_cast<cfsa_moments*>(ctx->d_src);
-		cfsa_moments* const buf[CFSA_MAX_STAGES] = {m0, m0 + moments[0], nullptr};
-		// every launch of the pass is a timed span of its own
-		for (uint32_t s = 0; rc == CFHIP_OK && s < stages; ++s)
-			rc = timed(ctx, stream, "spec_aa", [&] {
-				return cfhip_launch_spec_aa(&call, layers, s, s ? buf[s - 1u] : nullptr, s + 1u < stages ? buf[s] : nullptr,
-					results_device, stream);
-			});
-		if (rc != CFHIP_OK)
-			return rc;
-		return lease.done(!stream_);
+		const size_t nrough = rough0 ? layers : 0u, ntab = (size_t)layers + nrough + (size_t)layers*per;
+		return device_pass(ctx, stream_, "cfhip_spec_aa_texel_kernel", ntab*sizeof(void*),
+			std::max<size_t>((moments[0] + moments[1])*sizeof(cfsa_moments), 16u), [&](hipStream_t stream) -> int {
+			void** table[3];
+			CF_TRY(upload_tables(ctx, stream, {{normals, layers}, {rough0, nrough}, {levels, (size_t)layers*per}}, table));
+			if (results_device)
+				HIP_TRY(ctx, hipMemsetAsync(results_device, 0, (size_t)layers*per*sizeof(cfhip_spec_aa_result), stream));
+			cfsa_call call;
+			call.normals = table[0];
+			call.rough0 = rough0 ? table[1] : nullptr;
+			call.levels = table[2];
+			call.normal_pitch = normal_pitch_bytes;
+			call.rough_pitch = rough0 ? rough_pitch_bytes : 0u;
+			call.width = width; call.height = height;
+			call.levels_count = levels_count;
+			call.normal_type = normal_pixel_type;
+			call.rough_type = rough0 ? rough_pixel_type : 0;
+			call.flags = params->flags;
+			call.channel = params->channel;
+			call.base_roughness = params->base_roughness;
+			call.variance_scale = params->variance_scale;
+			call.max_variance = params->max_variance;
+			cfsa_moments* const m0 = static_cast<cfsa_moments*>(ctx->d_src);
+			cfsa_moments* const buf[CFSA_MAX_STAGES] = {m0, m0 + moments[0], nullptr};
+			LaunchChain spec(ctx, stream, "spec_aa");
+			for (uint32_t s = 0; s < stages; ++s)
+				spec([&] {
+					return cfhip_launch_spec_aa(&call, layers, s, s ? buf[s - 1u] : nullptr, s + 1u < stages ? buf[s] : nullptr,
+						results_device, stream);
+				});
+			return spec.rc;
+		});
 	});
 }
 
 // ---- environment maps (csrc/envmap.hip): panorama to cube, the GGX chain, nine SH coefficients ------------------------
-static uint32_t cube_levels(uint32_t face_size)
-{
-	uint32_t levels = 0;
-	for (; face_size; face_size >>= 1)
-		++levels;
-	return levels;
-}
-
-static int check_faces(cfhip_ctx* ctx, const char* what, const void* const* faces, uint32_t face_size)
-{
-	if (!faces)
-		return fail(ctx, CFHIP_E_INVALID, "%s: faces is NULL", what);
-	if (!face_size || face_size > CFENV_MAX_FACE)
-		return fail(ctx, CFHIP_E_INVALID, "%s: face_size is 1 to %u, not %u", what, CFENV_MAX_FACE, face_size);
-	for (uint32_t f = 0; f < 6u; ++f) {
-		if (!faces[f])
-			return fail(ctx, CFHIP_E_INVALID, "%s: faces[%u] is NULL", what, f);
-		if ((uintptr_t)faces[f] % 16u)
-			return fail(ctx, CFHIP_E_INVALID, "%s: faces[%u] not aligned to a texel (16 bytes)", what, f);
-	}
-	return CFHIP_OK;
-}
-
 int cfhip_equirect_to_cube_device(cfhip_ctx* ctx, const void* src, int src_pixel_type, uint32_t width, uint32_t height,
 	size_t src_pitch_bytes, void* const* faces, uint32_t face_size, uint32_t supersample, void* stream_)
 {
 	return guarded(ctx, "equirect_to_cube", [&]() -> int {
-		if (!src)
-			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: src is NULL");
+		const char* const what = "equirect_to_cube";
+		CF_TRY(check_given(ctx, what, "src", src));
 		if (width < 2u || !height || width > CFENV_MAX_PANORAMA || height > CFENV_MAX_PANORAMA)
 			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: width is 2 to %u and height 1 to %u, not %ux%u", CFENV_MAX_PANORAMA,
 				CFENV_MAX_PANORAMA, width, height);
-		const size_t spb = pixel_bytes(src_pixel_type);
-		if (!spb)
-			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: src_pixel_type %d", src_pixel_type);
-		if (src_pitch_bytes < (size_t)width*spb)
-			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: src_pitch_bytes %zu < %zu, a row", src_pitch_bytes, (size_t)width*spb);
-		if (src_pitch_bytes % (spb/4u))
-			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: src_pitch_bytes %zu not aligned to a component (%zu bytes)",
-				src_pitch_bytes, spb/4u);
+		size_t spb;
+		CF_TRY(check_pixel_type(ctx, what, "src_pixel_type", src_pixel_type, &spb));
+		CF_TRY(check_row_pitch(ctx, what, "src_pitch_bytes", src_pitch_bytes, (size_t)width*spb));
+		CF_TRY(check_pitch_aligned(ctx, what, "src_pitch_bytes", src_pitch_bytes, spb/4u, "a component"));
 		if ((uintptr_t)src % (spb/4u))
 			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: src not aligned to a component (%zu bytes)", spb/4u);
 		if (supersample != 1u && supersample != 2u && supersample != 4u)
 			return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: supersample %u is not 1, 2 or 4", supersample);
-		int rc = check_faces(ctx, "equirect_to_cube", faces, face_size);
-		if (rc != CFHIP_OK)
-			return rc;
+		CF_TRY(check_faces(ctx, what, faces, face_size));
 		for (uint32_t f = 0; f < 6u; ++f)
 			if (faces[f] == src)
 				return fail(ctx, CFHIP_E_INVALID, "equirect_to_cube: faces[%u] equals src", f);
-		if (!ctx)
-			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, call_stream(ctx, stream_));
-		const hipStream_t stream = lease.stream;
-		begin_call(ctx, stream, "cfhip_equirect_to_cube_kernel");
-		rc = lease.acquire();
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, 6u*sizeof(void*));
-		if (rc != CFHIP_OK)
-			return rc;
-		void** table = static_cast<void**>(ctx->d_batch);
-		HIP_TRY(ctx, hipMemcpyAsync(table, faces, 6u*sizeof(void*), hipMemcpyHostToDevice, stream));
-		rc = timed(ctx, stream, "equirect_to_cube", [&] {
-			return cfhip_launch_equirect_to_cube(src, src_pixel_type, width, height, src_pitch_bytes, table, face_size, supersample,
-				stream);
+		return device_pass(ctx, stream_, "cfhip_equirect_to_cube_kernel", 6u*sizeof(void*), 0, [&](hipStream_t stream) -> int {
+			void** table[1];
+			CF_TRY(upload_tables(ctx, stream, {{faces, 6u}}, table));
+			return timed(ctx, stream, "equirect_to_cube", [&] {
+				return cfhip_launch_equirect_to_cube(src, src_pixel_type, width, height, src_pitch_bytes, table[0], face_size,
+					supersample, stream);
+			});
 		});
-		if (rc != CFHIP_OK)
-			return rc;
-		return lease.done(!stream_);
 	});
 }
 
@@ -2792,14 +2781,11 @@ int cfhip_cube_prefilter_device(cfhip_ctx* ctx, const void* const* src_levels, u
 {
 	static_assert(sizeof(cfhip_ggx_sample) == 16 && sizeof(cfhip_sh9_result) == 296, "the ABI's sizes");
 	return guarded(ctx, "cube_prefilter", [&]() -> int {
-		if (!src_levels)
-			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: src_levels is NULL");
-		if (!dst_levels)
-			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: dst_levels is NULL");
-		if (!tables)
-			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: tables is NULL");
-		if (!table_samples)
-			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: table_samples is NULL");
+		const char* const what = "cube_prefilter";
+		CF_TRY(check_given(ctx, what, "src_levels", src_levels));
+		CF_TRY(check_given(ctx, what, "dst_levels", dst_levels));
+		CF_TRY(check_given(ctx, what, "tables", tables));
+		CF_TRY(check_given(ctx, what, "table_samples", table_samples));
 		if (!face_size || face_size > CFENV_MAX_FACE)
 			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: face_size is 1 to %u, not %u", CFENV_MAX_FACE, face_size);
 		const uint32_t full = cube_levels(face_size);
@@ -2808,6 +2794,7 @@ int cfhip_cube_prefilter_device(cfhip_ctx* ctx, const void* const* src_levels, u
 				source_levels);
 		if (!dst_count || dst_count > full)
 			return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: dst_count is 1 to %u for a face of %u, not %u", full, face_size, dst_count);
+		// (the two-index texts of these lists are this pass's own)
 		for (uint32_t i = 0; i < 6u*source_levels; ++i) {
 			if (!src_levels[i])
 				return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: src_levels[%u][%u] is NULL", i/source_levels, i%source_levels);
@@ -2838,8 +2825,7 @@ int cfhip_cube_prefilter_device(cfhip_ctx* ctx, const void* const* src_levels, u
 			if (S % 64u || S < CFENV_MIN_SAMPLES || S > CFENV_MAX_SAMPLES)
 				return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: table_samples[%u] is %u, not 0 or a multiple of 64 from %u to %u", k, S,
 					CFENV_MIN_SAMPLES, CFENV_MAX_SAMPLES);
-			if (!tables[k])
-				return fail(ctx, CFHIP_E_INVALID, "cube_prefilter: tables[%u] is NULL", k);
+			CF_TRY(check_item_given(ctx, what, "tables", k, tables[k]));
 			for (uint32_t i = 0; i < S; ++i) {
 				const cfhip_ggx_sample& r = tables[k][i];
 				if (!(std::isfinite(r.lx) && std::isfinite(r.ly) && r.lz >= 0.0f && std::isfinite(r.lz) && r.lod >= 0.0f &&
@@ -2849,49 +2835,36 @@ int cfhip_cube_prefilter_device(cfhip_ctx* ctx, const void* const* src_levels, u
 			}
 			records += S;
 		}
-		if (!ctx)
-			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, call_stream(ctx, stream_));
-		const hipStream_t stream = lease.stream;
-		begin_call(ctx, stream, "cfhip_cube_prefilter_kernel");
 		// d_batch: the source chain's pointers, then the destination's.  d_src: the levels' tables, one after the other
 		const size_t ns = 6u*(size_t)source_levels, nd = 6u*(size_t)dst_count;
-		int rc = lease.acquire();
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, (ns + nd)*sizeof(void*));
-		if (rc == CFHIP_OK && records)
-			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, records*sizeof(cfhip_ggx_sample));
-		if (rc != CFHIP_OK)
-			return rc;
-		// pageable sources: the runtime stages the copies before returning
-		void** table = static_cast<void**>(ctx->d_batch);
-		HIP_TRY(ctx, hipMemcpyAsync(table, src_levels, ns*sizeof(void*), hipMemcpyHostToDevice, stream));
-		HIP_TRY(ctx, hipMemcpyAsync(table + ns, dst_levels, nd*sizeof(void*), hipMemcpyHostToDevice, stream));
-		cfhip_ggx_sample* d_tables = static_cast<cfhip_ggx_sample*>(ctx->d_src);
-		size_t at = 0;
-		for (uint32_t k = 0; k < dst_count; ++k)
-			if (table_samples[k]) {
-				HIP_TRY(ctx, hipMemcpyAsync(d_tables + at, tables[k], (size_t)table_samples[k]*sizeof(cfhip_ggx_sample),
-					hipMemcpyHostToDevice, stream));
+		return device_pass(ctx, stream_, "cfhip_cube_prefilter_kernel", (ns + nd)*sizeof(void*), records*sizeof(cfhip_ggx_sample),
+			[&](hipStream_t stream) -> int {
+			void** table[2];
+			CF_TRY(upload_tables(ctx, stream, {{src_levels, ns}, {dst_levels, nd}}, table));
+			cfhip_ggx_sample* d_tables = static_cast<cfhip_ggx_sample*>(ctx->d_src);
+			size_t at = 0;
+			for (uint32_t k = 0; k < dst_count; ++k)
+				if (table_samples[k]) {
+					HIP_TRY(ctx, hipMemcpyAsync(d_tables + at, tables[k], (size_t)table_samples[k]*sizeof(cfhip_ggx_sample),
+						hipMemcpyHostToDevice, stream));
+					at += table_samples[k];
+				}
+			cfenv_prefilter_call call;
+			call.src = table[0];
+			call.dst = table[1];
+			call.face_size = face_size; call.src_levels = source_levels; call.dst_levels = dst_count;
+			at = 0;
+			// every level is a timed span of its own
+			LaunchChain level(ctx, stream, "cube_prefilter");
+			for (uint32_t k = 0; k < dst_count; ++k) {
+				call.level = k;
+				call.samples = table_samples[k];
+				call.table = d_tables + at;
 				at += table_samples[k];
+				level([&] { return cfhip_launch_cube_prefilter(&call, stream); });
 			}
-		cfenv_prefilter_call call;
-		call.src = table;
-		call.dst = table + ns;
-		call.face_size = face_size; call.src_levels = source_levels; call.dst_levels = dst_count;
-		at = 0;
-		// every level is a timed span of its own
-		for (uint32_t k = 0; k < dst_count; ++k) {
-			call.level = k;
-			call.samples = table_samples[k];
-			call.table = d_tables + at;
-			at += table_samples[k];
-			rc = timed(ctx, stream, "cube_prefilter", [&] { return cfhip_launch_cube_prefilter(&call, stream); });
-			if (rc != CFHIP_OK)
-				return rc;
-		}
-		return lease.done(!stream_);
+			return level.rc;
+		});
 	});
 }
 
@@ -2899,36 +2872,21 @@ int cfhip_cube_sh9_device(cfhip_ctx* ctx, const void* const* faces, uint32_t fac
 	void* stream_)
 {
 	return guarded(ctx, "cube_sh9", [&]() -> int {
-		int rc = check_faces(ctx, "cube_sh9", faces, face_size);
-		if (rc != CFHIP_OK)
-			return rc;
-		if (!result_device)
-			return fail(ctx, CFHIP_E_INVALID, "cube_sh9: result_device is NULL");
+		CF_TRY(check_faces(ctx, "cube_sh9", faces, face_size));
+		CF_TRY(check_given(ctx, "cube_sh9", "result_device", result_device));
 		if ((uintptr_t)result_device % 8u)
 			return fail(ctx, CFHIP_E_INVALID, "cube_sh9: result_device not aligned to 8 bytes");
-		if (!ctx)
-			return fail(nullptr, CFHIP_E_INVALID, "ctx is NULL");
-		HIP_TRY(ctx, hipSetDevice(ctx->device));
-		StagingLease lease(ctx, call_stream(ctx, stream_));
-		const hipStream_t stream = lease.stream;
-		begin_call(ctx, stream, "cfhip_cube_sh9_rows_kernel");
 		// d_batch: the six pointers.  d_src: a record of 37 doubles per face row
-		rc = lease.acquire();
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_batch, &ctx->batch_cap, 6u*sizeof(void*));
-		if (rc == CFHIP_OK)
-			rc = reserve(ctx, &ctx->d_src, &ctx->src_cap, 6u*(size_t)face_size*CFENV_SH_VALUES*sizeof(double));
-		if (rc != CFHIP_OK)
-			return rc;
-		void** table = static_cast<void**>(ctx->d_batch);
-		HIP_TRY(ctx, hipMemcpyAsync(table, faces, 6u*sizeof(void*), hipMemcpyHostToDevice, stream));
-		double* rows = static_cast<double*>(ctx->d_src);
-		rc = timed(ctx, stream, "cube_sh9", [&] { return cfhip_launch_cube_sh9_rows(table, face_size, rows, stream); });
-		if (rc == CFHIP_OK)
-			rc = timed(ctx, stream, "cube_sh9", [&] { return cfhip_launch_cube_sh9_final(rows, face_size, result_device, stream); });
-		if (rc != CFHIP_OK)
-			return rc;
-		return lease.done(!stream_);
+		return device_pass(ctx, stream_, "cfhip_cube_sh9_rows_kernel", 6u*sizeof(void*),
+			6u*(size_t)face_size*CFENV_SH_VALUES*sizeof(double), [&](hipStream_t stream) -> int {
+			void** table[1];
+			CF_TRY(upload_tables(ctx, stream, {{faces, 6u}}, table));
+			double* rows = static_cast<double*>(ctx->d_src);
+			LaunchChain sh9(ctx, stream, "cube_sh9");
+			sh9([&] { return cfhip_launch_cube_sh9_rows(table[0], face_size, rows, stream); });
+			sh9([&] { return cfhip_launch_cube_sh9_final(rows, face_size, result_device, stream); });
+			return sh9.rc;
+		});
 	});
 }
 

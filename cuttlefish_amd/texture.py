@@ -635,6 +635,38 @@ class Texture:
         self._images = images
         return True
 
+    def _stack_device(self, images):
+        """images of one size and dtype, stacked and uploaded -> (the host stack, its device tensor, one device pointer
+        per image)"""
+        import torch
+        stack = np.stack([np.ascontiguousarray(im) for im in images])
+        dev = torch.from_numpy(stack).to("cuda:%d" % self._device_id)
+        size = dev[0].numel()*dev.element_size()
+        return stack, dev, [dev.data_ptr() + i*size for i in range(len(images))]
+
+    def _in_place_pass(self, result_dtype, fields, call):
+        """A pass over every image currently set, each within itself: the images of equal size and dtype share one
+        call(pointers, pixel type, width, height, row pitch, pointer to their 16-byte records) and are replaced by what
+        it left in them.  -> the records in [mip][depth][face] order: mip, depth, face and `fields` of result_dtype."""
+        import torch
+        groups: Dict[tuple, List[Tuple[int, int, int]]] = {}
+        for m, level in enumerate(self._images):
+            for d, dep in enumerate(level):
+                for f, im in enumerate(dep):
+                    if im is not None:
+                        groups.setdefault((im.shape[0], im.shape[1], im.dtype.str), []).append((m, d, f))
+        records = {}
+        for (h, w, _), where in groups.items():
+            stack, dev, ptrs = self._stack_device([self._images[m][d][f] for m, d, f in where])
+            res = torch.zeros((len(where), 4), dtype=torch.int32, device=dev.device)
+            call(ptrs, api.pixel_type_of(stack[0]), w, h, stack.strides[1], res.data_ptr())
+            out = dev.cpu().numpy()
+            rec = res.cpu().numpy().view(result_dtype).reshape(-1)
+            for i, (m, d, f) in enumerate(where):
+                self._images[m][d][f] = out[i]
+                records[(m, d, f)] = dict(dict(mip=m, depth=d, face=f), **{k: int(rec[i][k]) for k in fields})
+        return [records[k] for k in sorted(records)]
+
     def bleed_alpha(self, threshold: float = 0.0, wrap=False, max_distance: int = 0) -> bool:
         """Alpha bleeding (Context.alpha_bleed_device) of every image currently set -- all levels, depths and faces,
         each within itself: every texel with alpha <= threshold takes the colour of the nearest texel with
@@ -644,31 +676,12 @@ class Texture:
         for tiling surfaces; max_distance: texels, 0 = unlimited.  bleed_results() returns the records.  False on
         an invalid or already converted texture, and on a 3-D texture: a volume's nearest seed is another
         definition."""
-        import torch
         if not self._valid or self._textures or self._dim == Dimension.Dim3D:
             return False
-        groups: Dict[tuple, List[Tuple[int, int, int]]] = {}
-        for m, level in enumerate(self._images):
-            for d, dep in enumerate(level):
-                for f, im in enumerate(dep):
-                    if im is not None:
-                        groups.setdefault((im.shape[0], im.shape[1], im.dtype.str), []).append((m, d, f))
-        records = {}
-        for (h, w, _), where in groups.items():
-            stack = np.stack([np.ascontiguousarray(self._images[m][d][f]) for m, d, f in where])
-            dev = torch.from_numpy(stack).to("cuda:%d" % self._device_id)
-            res = torch.zeros((len(where), 4), dtype=torch.int32, device=dev.device)
-            size = dev[0].numel()*dev.element_size()
-            self._context().alpha_bleed_device([dev.data_ptr() + i*size for i in range(len(where))],
-                                               api.pixel_type_of(stack[0]), w, h, stack.strides[1], threshold, wrap,
-                                               max_distance, res.data_ptr())
-            out = dev.cpu().numpy()
-            rec = res.cpu().numpy().view(api.BLEED_RESULT_DTYPE).reshape(-1)
-            for i, (m, d, f) in enumerate(where):
-                self._images[m][d][f] = out[i]
-                records[(m, d, f)] = dict(mip=m, depth=d, face=f, seeds=int(rec[i]["seeds"]), filled=int(rec[i]["filled"]),
-                                          max_dist2=int(rec[i]["max_dist2"]))
-        self._bleed = [records[k] for k in sorted(records)]
+        self._bleed = self._in_place_pass(
+            api.BLEED_RESULT_DTYPE, ("seeds", "filled", "max_dist2"),
+            lambda ptrs, pt, w, h, pitch, res: self._context().alpha_bleed_device(ptrs, pt, w, h, pitch, threshold, wrap,
+                                                                                  max_distance, res))
         return True
 
     def bleed_results(self):
@@ -684,33 +697,13 @@ class Texture:
         is still a distance.  Do not pass alpha_coverage= to that generate_mipmaps: it would rescale an alpha that is no
         longer coverage.  Images of equal size and dtype share one call.  wrap: a bool or (x, y) for tiling surfaces.
         sdf_results() returns the records.  False on an invalid or already converted texture, and on a 3-D texture."""
-        import torch
         if not self._valid or self._textures or self._dim == Dimension.Dim3D:
             return False
         api.make_sdf_params(spread, 1, threshold, wrap, channels)
-        groups: Dict[tuple, List[Tuple[int, int, int]]] = {}
-        for m, level in enumerate(self._images):
-            for d, dep in enumerate(level):
-                for f, im in enumerate(dep):
-                    if im is not None:
-                        groups.setdefault((im.shape[0], im.shape[1], im.dtype.str), []).append((m, d, f))
-        records = {}
-        for (h, w, _), where in groups.items():
-            stack = np.stack([np.ascontiguousarray(self._images[m][d][f]) for m, d, f in where])
-            dev = torch.from_numpy(stack).to("cuda:%d" % self._device_id)
-            res = torch.zeros((len(where), 4), dtype=torch.int32, device=dev.device)
-            size = dev[0].numel()*dev.element_size()
-            ptrs = [dev.data_ptr() + i*size for i in range(len(where))]
-            pt = api.pixel_type_of(stack[0])
-            self._context().alpha_sdf_device(ptrs, pt, w, h, stack.strides[1], ptrs, pt, stack.strides[1], spread, 1,
-                                             threshold, wrap, channels, res.data_ptr())
-            out = dev.cpu().numpy()
-            rec = res.cpu().numpy().view(api.SDF_RESULT_DTYPE).reshape(-1)
-            for i, (m, d, f) in enumerate(where):
-                self._images[m][d][f] = out[i]
-                records[(m, d, f)] = dict(mip=m, depth=d, face=f, inside=int(rec[i]["inside"]),
-                                          saturated=int(rec[i]["saturated"]))
-        self._sdf = [records[k] for k in sorted(records)]
+        self._sdf = self._in_place_pass(
+            api.SDF_RESULT_DTYPE, ("inside", "saturated"),
+            lambda ptrs, pt, w, h, pitch, res: self._context().alpha_sdf_device(ptrs, pt, w, h, pitch, ptrs, pt, pitch, spread, 1,
+                                                                                threshold, wrap, channels, res))
         return True
 
     def sdf_results(self):
@@ -753,18 +746,11 @@ class Texture:
         records = {}
         for where in groups.values():
             n = len(where)
-
-            def upload(stack):
-                dev = torch.from_numpy(stack).to(device)
-                size = dev[0].numel()*dev.element_size()
-                return dev, [dev.data_ptr() + i*size for i in range(n)]
-            nstack = np.stack([np.ascontiguousarray(normals._images[0][d][f]) for d, f in where])
-            ndev, nptrs = upload(nstack)
+            nstack, ndev, nptrs = self._stack_device([normals._images[0][d][f] for d, f in where])
             rstack, rdev, rptrs = nstack, ndev, nptrs         # the normals' own surfaces when `normals` is this texture
             if normals is not self:
-                rstack = np.stack([np.ascontiguousarray(self._images[0][d][f]) for d, f in where])
-                rdev, rptrs = upload(rstack)
-            levels = [upload(np.stack([_as_float32(np.ascontiguousarray(self._images[m][d][f])) for d, f in where]))
+                rstack, rdev, rptrs = self._stack_device([self._images[0][d][f] for d, f in where])
+            levels = [self._stack_device([_as_float32(np.ascontiguousarray(self._images[m][d][f])) for d, f in where])[1:]
                       for m in range(1, self._mips)]
             res = torch.zeros((n*per, 4), dtype=torch.int32, device=device)
             self._context().specular_aa_device(

@@ -71,6 +71,41 @@ def _alpha_bleed(ctx, b):
     ctx.alpha_bleed_device([work[0].data_ptr(), work[1].data_ptr()], U8, 8, 8, 32, threshold=0.5)
 
 
+def _alpha_sdf(scale):
+    def call(ctx, b):
+        out = b.zeros(2, 8//scale, 8//scale, 4, dtype="uint8")
+        ctx.alpha_sdf_device([b.d_two8[0].data_ptr(), b.d_two8[1].data_ptr()], U8, 8, 8, 32,
+                             [out[0].data_ptr(), out[1].data_ptr()], U8, (8//scale)*4, spread=2, scale=scale)
+    return call
+
+
+def _spec_aa(w, h, layers, levels_count):
+    def call(ctx, b):
+        nrm = b.dev(_pattern(w, h, layers))
+        lv = [[b.zeros(max(1, h >> k), max(1, w >> k), 4) for k in range(1, levels_count)] for _ in range(layers)]
+        ctx.specular_aa_device([nrm[l].data_ptr() for l in range(layers)], U8, w, h, w*4,
+                               [[t.data_ptr() for t in chain] for chain in lv], channel=1)
+    return call
+
+
+def _equirect_to_cube(ctx, b):
+    faces = b.zeros(6, 2, 2, 4)
+    ctx.equirect_to_cube_device(b.d_img8.data_ptr(), U8, 8, 4, 32, [faces[f].data_ptr() for f in range(6)], 2)
+
+
+def _cube_prefilter(ctx, b):
+    src = [b.zeros(6, n, n, 4) for n in (4, 2, 1)]
+    dst = [b.zeros(6, n, n, 4) for n in (4, 2)]
+    ctx.cube_prefilter_device([[s[f].data_ptr() for s in src] for f in range(6)], 4,
+                              [[d[f].data_ptr() for d in dst] for f in range(6)],
+                              [None, api.ggx_sample_table(0.5, 64, 4, 3)])
+
+
+def _cube_sh9(ctx, b):
+    faces, res = b.zeros(6, 2, 2, 4), b.zeros(37, dtype="float64")
+    ctx.cube_sh9_device([faces[f].data_ptr() for f in range(6)], 2, res.data_ptr())
+
+
 def _image_ops(ctx, b):
     dst = b.zeros(8, 8, 4)
     ctx.image_ops_device(b.d_img8.data_ptr(), U8, 8, 8, 32, api.make_image_ops(ops=api.ImageOp.FlipX), dst.data_ptr(), 128)
@@ -90,6 +125,16 @@ TIMED = {
     "mip_post": (_mip_post, "cfhip_mip_post_count_kernel", 15),
     # seed, the steps 4, 2, 1 of an 8 x 8 flood, fill
     "alpha_bleed": (_alpha_bleed, "cfhip_alpha_bleed_step_kernel", 5),
+    # classes, row distances, columns; above scale 1 the tiles too
+    "alpha_sdf": (_alpha_sdf(1), "cfhip_alpha_sdf_column_kernel", 3),
+    "alpha_sdf_scale2": (_alpha_sdf(2), "cfhip_alpha_sdf_column_kernel", 4),
+    # one launch per five levels: 64 x 2 has six, the second launch reads the first one's moments
+    "spec_aa": (_spec_aa(4, 4, 2, 3), "cfhip_spec_aa_texel_kernel", 1),
+    "spec_aa_two_stages": (_spec_aa(64, 2, 1, 7), "cfhip_spec_aa_texel_kernel", 2),
+    "equirect_to_cube": (_equirect_to_cube, "cfhip_equirect_to_cube_kernel", 1),
+    # one span per destination level: a copy, then 64 samples
+    "cube_prefilter": (_cube_prefilter, "cfhip_cube_prefilter_kernel", 2),
+    "cube_sh9": (_cube_sh9, "cfhip_cube_sh9_rows_kernel", 2),
     "image_ops": (_image_ops, "cfhip_image_ops_kernel", 1),
     "decode": (lambda c, b: c.decode(b.bc1_4, BC1, Type.UNorm, 4, 4), "cfhip_decode_block_kernel", 1),
     "decode_device": (_decode_device, "cfhip_decode_block_kernel", 1),
