@@ -206,6 +206,7 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_png_bound", "cfhip_png_encode", "cfhip_png_encode_device", "cfhip_png_stage_ms",
            "cfhip_mip_post_array_device", "cfhip_alpha_coverage_device", "cfhip_alpha_bleed_array_device",
            "cfhip_alpha_sdf_array_device", "cfhip_spec_aa_array_device",
+           "cfhip_height_ao_array_device", "cfhip_height_ao_directions",
            "cfhip_equirect_to_cube_device", "cfhip_ggx_sample_table", "cfhip_cube_prefilter_device",
            "cfhip_cube_sh9_device"]
 
@@ -642,6 +643,73 @@ def make_spec_aa_params(channel, perceptual: bool = True, signed_normals: bool =
     return SpecAaParams(ctypes.sizeof(SpecAaParams), flags, spec_aa_channel(channel), b, s, m, (ctypes.c_uint32*2)(0, 0))
 
 
+# ---- ambient occlusion from height maps (cfhip_height_ao_array_device) ----
+HAO_WRAP_X, HAO_WRAP_Y, HAO_UNIFORM, HAO_FALLOFF = 1, 2, 4, 8      # cfhip_height_ao_params.flags
+HAO_DIRECTIONS = (8, 16, 32)
+HAO_MAX_RADIUS = 64
+
+
+class HeightAoParams(ctypes.Structure):
+    """cfhip_height_ao_params"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("channel", ctypes.c_uint32),
+                ("directions", ctypes.c_uint32), ("radius", ctypes.c_uint32), ("channel_mask", ctypes.c_uint32),
+                ("height", ctypes.c_float), ("strength", ctypes.c_float), ("bias", ctypes.c_float),
+                ("reserved", ctypes.c_uint32)]
+
+
+class HeightAoResult(ctypes.Structure):
+    """cfhip_height_ao_result: one surface's texels with a horizon above the bias in any direction, and the bit pattern
+    of its smallest (float)v"""
+    _fields_ = [("occluded", ctypes.c_uint32), ("darkest", ctypes.c_uint32), ("reserved", ctypes.c_uint32*2)]
+
+
+HEIGHT_AO_RESULT_DTYPE = np.dtype([("occluded", np.uint32), ("darkest", np.uint32), ("reserved0", np.uint32),
+                                   ("reserved1", np.uint32)])
+
+
+def make_height_ao_params(radius: int, height_scale: float = 1.0, directions: int = 16, channel="r", channels="r",
+                          strength: float = 1.0, bias: float = 0.0, uniform: bool = False, falloff: bool = False,
+                          wrap=(False, False)) -> HeightAoParams:
+    """radius: how far a horizon is looked for, in texels (1 to 64); height_scale: texels per stored unit of height, the
+    meaning the normal-map op's height has (finite, negative for an inverted map); directions: 8, 16 or 32; channel:
+    the component that holds the height; channels: the components that receive the occlusion; strength: 1 is the
+    occlusion itself, 0 none, above 1 darker (clamped at 0); bias: the slope a horizon must exceed to count; uniform:
+    solid-angle visibility instead of the cosine-weighted one; falloff: a horizon's slope fades to 0 at radius + 1;
+    wrap: a bool or (x, y), the axes on which the surface tiles.  Every bad field is a ValueError here, before the
+    library would refuse it."""
+    if isinstance(radius, (bool, np.bool_)) or not isinstance(radius, (int, np.integer)) or not 1 <= radius <= HAO_MAX_RADIUS:
+        raise ValueError("radius %r: an integer from 1 to %d" % (radius, HAO_MAX_RADIUS))
+    if isinstance(directions, (bool, np.bool_)) or directions not in HAO_DIRECTIONS:
+        raise ValueError("directions %r: one of %r" % (directions, HAO_DIRECTIONS))
+    with np.errstate(over="ignore"):                   # a value beyond float32 becomes inf and is refused below
+        hs, s, b = (float(np.float32(v)) for v in (height_scale, strength, bias))
+    if not np.isfinite(hs):
+        raise ValueError("height_scale %r is not finite" % (height_scale,))
+    if not (s >= 0.0 and np.isfinite(s)):
+        raise ValueError("strength %r is negative or not finite" % (strength,))
+    if not (b >= 0.0 and np.isfinite(b)):
+        raise ValueError("bias %r is negative or not finite" % (bias,))
+    wx, wy = wrap_axes(wrap)
+    flags = (HAO_WRAP_X if wx else 0) | (HAO_WRAP_Y if wy else 0) | (HAO_UNIFORM if uniform else 0) | \
+        (HAO_FALLOFF if falloff else 0)
+    return HeightAoParams(ctypes.sizeof(HeightAoParams), flags, spec_aa_channel(channel), int(directions), int(radius),
+                          sdf_channel_mask(channels), hs, s, b, 0)
+
+
+def height_ao_directions(D: int):
+    """cfhip_height_ao_directions -> (vx, vy, weight): the D (8, 16 or 32) integer direction vectors of the horizon scan
+    as int32 arrays and each one's share of the circle as float64.  Host only: no context, no device."""
+    if isinstance(D, (bool, np.bool_)) or D not in HAO_DIRECTIONS:
+        raise ValueError("directions %r: one of %r" % (D, HAO_DIRECTIONS))
+    vx, vy, w = np.empty(D, np.int32), np.empty(D, np.int32), np.empty(D, np.float64)
+    rc = load_library().cfhip_height_ao_directions(int(D), vx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                   vy.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                                   w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    if rc != 0:
+        raise ValueError("cfhip_height_ao_directions refused %r" % (D,))
+    return vx, vy, w
+
+
 # ---- environment maps (cfhip_equirect_to_cube_device, cfhip_cube_prefilter_device, cfhip_cube_sh9_device) ----
 ENV_MAX_FACE = 8192
 ENV_MAX_PANORAMA = 32768
@@ -832,6 +900,14 @@ def load_library(path: Optional[str] = None):
         ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.POINTER(SpecAaParams), ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_spec_aa_array_device.restype = ctypes.c_int
+    L.cfhip_height_ao_array_device.argtypes = [
+        ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_int, ctypes.c_uint32,
+        ctypes.c_uint32, ctypes.c_size_t, ctypes.POINTER(ctypes.c_void_p), ctypes.c_int, ctypes.c_size_t,
+        ctypes.POINTER(HeightAoParams), ctypes.c_void_p, ctypes.c_void_p]
+    L.cfhip_height_ao_array_device.restype = ctypes.c_int
+    L.cfhip_height_ao_directions.argtypes = [ctypes.c_uint32, ctypes.POINTER(ctypes.c_int32),
+                                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]
+    L.cfhip_height_ao_directions.restype = ctypes.c_int
     L.cfhip_equirect_to_cube_device.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_size_t,
         ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
@@ -1476,6 +1552,53 @@ class Context:
         rec = res.cpu().numpy().view(SDF_RESULT_DTYPE)[0]
         return (out.cpu().numpy().view(out_dtype).reshape(h//scale, w//scale, 4),
                 {k: int(rec[k]) for k in rec.dtype.names})
+
+    def height_ao_device(self, srcs: Sequence[int], pixel_type, width: int, height: int, pitch: int, dsts: Sequence[int],
+                         dst_pixel_type, dst_pitch: int, *, radius: int, height_scale: float = 1.0, directions: int = 16,
+                         channel="r", channels="r", strength: float = 1.0, bias: float = 0.0, uniform: bool = False,
+                         falloff: bool = False, wrap=(False, False), results: int = 0, stream: int = 0):
+        """Ambient occlusion from height maps (cfhip_height_ao_array_device): `channel` of each device surface srcs[l]
+        (all of one size and pixel type) is a height field, height_scale texels per stored unit; for every texel the
+        highest horizon within `radius` texels is found in `directions` directions, and the share of the sky the
+        horizons leave open -- 1 on a flat surface -- is written to the `channels` of dsts[l] (the same size, of
+        dst_pixel_type).  The other components of dsts[l] are not written; dsts[l] may be srcs[l] with equal pixel
+        types, whatever the channels.  The remaining arguments are make_height_ao_params'.  results: device pointer to
+        len(srcs) cfhip_height_ao_result records (HEIGHT_AO_RESULT_DTYPE), or 0 for none.  One call is 2 launches,
+        whatever the layers, directions and radius."""
+        nl = len(srcs)
+        if len(dsts) != nl:
+            raise ValueError("srcs and dsts must list the same layers")
+        params = make_height_ao_params(radius, height_scale, directions, channel, channels, strength, bias, uniform,
+                                       falloff, wrap)
+        self._check(self._lib.cfhip_height_ao_array_device(
+            self._h, _ptr_array(srcs), nl, int(pixel_type), width, height, pitch, _ptr_array(dsts), int(dst_pixel_type),
+            dst_pitch, ctypes.byref(params), _ptr(results), _stream(stream)))
+
+    def height_ao(self, image: np.ndarray, radius: int, height_scale: float = 1.0, directions: int = 16, channel="r",
+                  channels="r", strength: float = 1.0, bias: float = 0.0, uniform: bool = False, falloff: bool = False,
+                  wrap=(False, False), out_dtype=None):
+        """Host convenience: one (h, w, 4) uint8 / float16 / float32 image through height_ao_device -> (a new (h, w, 4)
+        array of out_dtype -- the image's by default -- with the occlusion in `channels`, the record as a dict of
+        occluded, darkest, reserved0, reserved1).  The other channels are the image's with its own dtype, else zero."""
+        import torch
+        host, pt, dev = self._rgba_device(image)
+        kw = dict(radius=radius, height_scale=height_scale, directions=directions, channel=channel, channels=channels,
+                  strength=strength, bias=bias, uniform=uniform, falloff=falloff, wrap=wrap)
+        h, w = host.shape[:2]
+        out_dtype = host.dtype if out_dtype is None else np.dtype(out_dtype)
+        dpt = pixel_type_of(np.empty(0, out_dtype))
+        if out_dtype == host.dtype:
+            out = dev.clone()
+        else:
+            out = torch.zeros((h, w*4*out_dtype.itemsize), dtype=torch.uint8, device=dev.device)
+        res = torch.zeros(4, dtype=torch.int32, device=dev.device)
+        # the context's stream does not wait for torch's: the copy and the fills above must have landed before the pass
+        # writes into the same memory
+        torch.cuda.current_stream(dev.device).synchronize()
+        self.height_ao_device([dev.data_ptr()], pt, w, h, host.strides[0], [out.data_ptr()], dpt, w*4*out_dtype.itemsize,
+                              results=res.data_ptr(), **kw)
+        rec = res.cpu().numpy().view(HEIGHT_AO_RESULT_DTYPE)[0]
+        return out.cpu().numpy().view(out_dtype).reshape(h, w, 4), {k: int(rec[k]) for k in rec.dtype.names}
 
     def specular_aa_device(self, normals: Sequence[int], pixel_type, width: int, height: int, pitch: int,
                            levels: Sequence[Sequence[int]], *, rough0: Optional[Sequence[int]] = None,

@@ -171,6 +171,8 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  "cfhip_alpha_sdf_resolve_kernel",
                  # specular anti-aliasing (csrc/spec_aa.hip): five levels from texels, five more from a launch's moments
                  "cfhip_spec_aa_texel_kernel", "cfhip_spec_aa_moment_kernel",
+                 # ambient occlusion from height maps (csrc/height_ao.hip): the height plane, the scan per halo class
+                 "cfhip_height_ao_plane_kernel", "cfhip_height_ao_scan_kernel",
                  # environment maps (csrc/envmap.hip): panorama to cube, the GGX chain and its copy, the SH9 rows and sum
                  "cfhip_equirect_to_cube_kernel", "cfhip_cube_prefilter_kernel", "cfhip_cube_copy_kernel",
                  "cfhip_cube_sh9_rows_kernel", "cfhip_cube_sh9_final_kernel")

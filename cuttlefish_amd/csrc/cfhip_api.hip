@@ -20,6 +20,7 @@
 #include "alpha_bleed.h"
 #include "alpha_sdf.h"
 #include "spec_aa.h"
+#include "height_ao.h"
 #include "envmap.h"
 #include "stage_log.h"
 #include "../../include/cuttlefish_hip.h"
@@ -2702,6 +2703,162 @@ int cfhip_spec_aa_array_device(cfhip_ctx* ctx, const void* const* normals, uint3
 						results_device, stream);
 				});
 			return spec.rc;
+		});
+	});
+}
+
+// ---- ambient occlusion from height maps (csrc/height_ao.hip): the horizon in D directions within R texels -------------
+// The first quadrant of each direction set and its weights: half the angle between a direction's neighbours over 2 pi,
+// as the nearest double -- but (1,0) and (3,1) of D = 32, one unit in the last place above it, so that every set sums to
+// exactly 1.0 in direction order and a flat surface comes out as exactly 1.
+// The other quadrants are these turned by (x, y) -> (-y, x), with the same weights.
+namespace {
+struct HaoBase {
+	int32_t vx, vy;
+	double weight;
+};
+const HaoBase kHaoBase8[2] = {{1, 0, 0.125}, {1, 1, 0.125}};
+const HaoBase kHaoBase16[4] = {{1, 0, 0.07379180882521663}, {2, 1, 0.0625}, {1, 1, 0.05120819117478336}, {1, 2, 0.0625}};
+const HaoBase kHaoBase32[8] = {{1, 0, 0.05120819117478337}, {3, 1, 0.03689590441260832}, {2, 1, 0.021187664865358023},
+	{3, 2, 0.02560409558739168}, {1, 1, 0.03141647909450059}, {2, 3, 0.02560409558739168}, {1, 2, 0.021187664865358023},
+	{1, 3, 0.036895904412608316}};
+
+const HaoBase* hao_base(uint32_t directions)
+{
+	return directions == 8u ? kHaoBase8 : directions == 16u ? kHaoBase16 : directions == 32u ? kHaoBase32 : nullptr;
+}
+
+// direction d of a set
+HaoBase hao_direction(const HaoBase* base, uint32_t directions, uint32_t d)
+{
+	HaoBase v = base[d % (directions/4u)];
+	for (uint32_t q = d/(directions/4u); q; --q) {
+		const int32_t x = v.vx;
+		v.vx = -v.vy;
+		v.vy = x;
+	}
+	return v;
+}
+
+// The call's table, in double on the host: every direction's reach R_d and its gains g(d, 1 ... R_d)
+void hao_fill_table(cfhao_table* t, uint32_t directions, uint32_t radius, bool falloff)
+{
+	const HaoBase* base = hao_base(directions);
+	uint32_t first = 0;
+	for (uint32_t d = 0; d < directions; ++d) {
+		const HaoBase v = hao_direction(base, directions, d);
+		const uint32_t n = (uint32_t)(v.vx*v.vx + v.vy*v.vy);
+		uint32_t reach = 0;
+		while ((reach + 1u)*(reach + 1u)*n <= radius*radius)
+			++reach;
+		const double len = std::sqrt((double)n);
+		for (uint32_t k = 1; k <= reach; ++k) {
+			double g = 1.0/((double)k*len);
+			if (falloff)
+				g = g*(1.0 - (double)(k*k*n)/(double)((radius + 1u)*(radius + 1u)));
+			t->gain[first + k - 1u] = g;
+		}
+		t->dir[d] = cfhao_dir{v.vx, v.vy, reach, first, v.weight};
+		first += reach;
+	}
+}
+} // namespace
+
+int cfhip_height_ao_directions(uint32_t directions, int32_t* vx, int32_t* vy, double* weight)
+{
+	const HaoBase* base = hao_base(directions);
+	if (!base)
+		return CFHIP_E_INVALID;
+	for (uint32_t d = 0; d < directions; ++d) {
+		const HaoBase v = hao_direction(base, directions, d);
+		if (vx) vx[d] = v.vx;
+		if (vy) vy[d] = v.vy;
+		if (weight) weight[d] = v.weight;
+	}
+	return CFHIP_OK;
+}
+
+int cfhip_height_ao_array_device(cfhip_ctx* ctx, const void* const* src, uint32_t layers, int src_pixel_type, uint32_t width,
+	uint32_t height, size_t src_pitch_bytes, void* const* dst, int dst_pixel_type, size_t dst_pitch_bytes,
+	const cfhip_height_ao_params* params, cfhip_height_ao_result* results_device, void* stream_)
+{
+	static_assert(sizeof(cfhip_height_ao_params) == 40 && sizeof(cfhip_height_ao_result) == 16, "the ABI's sizes");
+	static_assert(CFHAO_MAX_LAYERS == 65535u, "check_layers' range");
+	static_assert(sizeof(cfhao_dir) == 24 && sizeof(cfhao_table) % 8u == 0, "the table the scan reads");
+	return guarded(ctx, "height_ao", [&]() -> int {
+		const char* const what = "height_ao";
+		CF_TRY(check_given(ctx, what, "params", params));
+		if (params->struct_size != sizeof(cfhip_height_ao_params))
+			return fail(ctx, CFHIP_E_INVALID, "height_ao: params->struct_size is %u, not %zu", params->struct_size,
+				sizeof(cfhip_height_ao_params));
+		CF_TRY(check_given(ctx, what, "src", src));
+		CF_TRY(check_given(ctx, what, "dst", dst));
+		CF_TRY(check_layers(ctx, what, layers));
+		CF_TRY(check_sides(ctx, what, width, height, CFHAO_MAX_SIDE));
+		size_t spb, dpb;
+		CF_TRY(check_pixel_type(ctx, what, "src_pixel_type", src_pixel_type, &spb));
+		CF_TRY(check_pixel_type(ctx, what, "dst_pixel_type", dst_pixel_type, &dpb));
+		CF_TRY(check_flags(ctx, what, params->flags,
+			CFHIP_HAO_WRAP_X | CFHIP_HAO_WRAP_Y | CFHIP_HAO_UNIFORM | CFHIP_HAO_FALLOFF));
+		if (params->channel > 3u)
+			return fail(ctx, CFHIP_E_INVALID, "height_ao: params->channel %u above 3", params->channel);
+		if (!hao_base(params->directions))
+			return fail(ctx, CFHIP_E_INVALID, "height_ao: params->directions %u is not 8, 16 or 32", params->directions);
+		if (params->radius < 1u || params->radius > CFHAO_MAX_RADIUS)
+			return fail(ctx, CFHIP_E_INVALID, "height_ao: params->radius %u outside 1 to %u", params->radius, CFHAO_MAX_RADIUS);
+		if (!params->channel_mask || params->channel_mask > 15u)
+			return fail(ctx, CFHIP_E_INVALID, "height_ao: params->channel_mask 0x%x outside 1 to 15", params->channel_mask);
+		if (!std::isfinite(params->height))
+			return fail(ctx, CFHIP_E_INVALID, "height_ao: params->height %g is not finite", (double)params->height);
+		if (!(params->strength >= 0.0f) || !std::isfinite(params->strength))
+			return fail(ctx, CFHIP_E_INVALID, "height_ao: params->strength %g is negative or not finite", (double)params->strength);
+		if (!(params->bias >= 0.0f) || !std::isfinite(params->bias))
+			return fail(ctx, CFHIP_E_INVALID, "height_ao: params->bias %g is negative or not finite", (double)params->bias);
+		if (params->reserved)
+			return fail(ctx, CFHIP_E_INVALID, "height_ao: params->reserved is %u, not 0", params->reserved);
+		if ((uint64_t)width*height > CFHAO_MAX_TEXELS)
+			return fail(ctx, CFHIP_E_INVALID, "height_ao: more than 2^30 texels in a surface");
+		CF_TRY(check_row_pitch(ctx, what, "src_pitch_bytes", src_pitch_bytes, (size_t)width*spb));
+		CF_TRY(check_pitch_aligned(ctx, what, "src_pitch_bytes", src_pitch_bytes, spb/4u, "a component"));
+		CF_TRY(check_row_pitch(ctx, what, "dst_pitch_bytes", dst_pitch_bytes, (size_t)width*dpb));
+		CF_TRY(check_pitch_aligned(ctx, what, "dst_pitch_bytes", dst_pitch_bytes, dpb/4u, "a component"));
+		for (uint32_t l = 0; l < layers; ++l) {
+			CF_TRY(check_item_given(ctx, what, "src", l, src[l]));
+			CF_TRY(check_item_given(ctx, what, "dst", l, dst[l]));
+			CF_TRY(check_item_aligned(ctx, what, "src", l, src[l], spb/4u, "a component"));
+			CF_TRY(check_item_aligned(ctx, what, "dst", l, dst[l], dpb/4u, "a component"));
+			// in place: every height is read before anything is written, but only a surface of the same geometry is one
+			if (dst[l] == src[l] && dst_pixel_type != src_pixel_type)
+				return fail(ctx, CFHIP_E_INVALID, "height_ao: dst[%u] equals src[%u]: in place needs equal pixel types", l, l);
+		}
+		// d_batch: the layers' source pointers, their destination pointers, then the call's table.  d_src: the plane,
+		// one float per texel, layer after layer
+		const size_t tab_bytes = (size_t)layers*2u*sizeof(void*);
+		return device_pass(ctx, stream_, "cfhip_height_ao_scan_kernel", tab_bytes + sizeof(cfhao_table),
+			(size_t)layers*width*height*sizeof(float), [&](hipStream_t stream) -> int {
+			void** table[2];
+			CF_TRY(upload_tables(ctx, stream, {{src, layers}, {dst, layers}}, table));
+			// (a pageable source, as the pointer tables are: the runtime stages the copy before it returns)
+			cfhao_table host;
+			std::memset(&host, 0, sizeof(host));
+			hao_fill_table(&host, params->directions, params->radius, params->flags & CFHIP_HAO_FALLOFF);
+			cfhao_table* const dtab = reinterpret_cast<cfhao_table*>(static_cast<uint8_t*>(ctx->d_batch) + tab_bytes);
+			HIP_TRY(ctx, hipMemcpyAsync(dtab, &host, sizeof(host), hipMemcpyHostToDevice, stream));
+			cfhao_call call;
+			call.src = table[0];
+			call.dst = table[1];
+			call.table = dtab;
+			call.src_pitch = src_pitch_bytes; call.dst_pitch = dst_pitch_bytes;
+			call.width = width; call.height = height;
+			call.src_type = src_pixel_type; call.dst_type = dst_pixel_type;
+			call.flags = params->flags; call.channel = params->channel;
+			call.directions = params->directions; call.radius = params->radius; call.channel_mask = params->channel_mask;
+			call.height_scale = params->height; call.strength = params->strength; call.bias = params->bias;
+			float* const plane = static_cast<float*>(ctx->d_src);
+			LaunchChain ao(ctx, stream, "height_ao");
+			ao([&] { return cfhip_launch_height_ao_plane(&call, layers, plane, results_device, stream); });
+			ao([&] { return cfhip_launch_height_ao_scan(&call, layers, plane, results_device, stream); });
+			return ao.rc;
 		});
 	});
 }

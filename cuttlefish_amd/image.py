@@ -85,6 +85,14 @@ class _Device:
                                   threshold, wrap, channels)
         return dst
 
+    def ao(self, src, dst, radius: int, **kw):
+        """The ambient occlusion of src's height channel (cfhip_height_ao_array_device) into the named channels of dst,
+        a buffer of the same size (src itself: in place) -> dst.  kw: Context.height_ao_device's keywords."""
+        t, pt, w, h, pitch = src
+        dt, dpt, dw, dh, dpitch = dst
+        self.ctx.height_ao_device([t.data_ptr()], pt, w, h, pitch, [dt.data_ptr()], dpt, dpitch, radius=radius, **kw)
+        return dst
+
     def png(self, buf, color_type: int, bit_depth: int, color_space) -> bytes:
         """The PNG file of a buffer (cfhip_png_encode_device): only the file's bytes come back."""
         import torch
@@ -217,6 +225,31 @@ class Image:
         self._last = (buf, out)
         return self._derived(out)
 
+    def ambient_occlusion(self, radius: int, height: float = 1.0, directions: int = 16, channel="r", channels="r",
+                          strength: float = 1.0, bias: float = 0.0, uniform: bool = False, falloff: bool = False,
+                          wrap=False) -> Optional["Image"]:
+        """The occlusion this image's height field casts on itself (Context.height_ao_device) as a new image of the
+        same size and pixel type: `channel` holds the heights, `height` texels per stored unit -- the meaning
+        create_normal_map's height has, so one value gives consistent normals and occlusion -- and the named
+        `channels` take the share of the sky the horizons within `radius` texels leave open, 1 on a flat surface.  The
+        other channels are this image's.  directions: 8, 16 or 32; strength, bias, uniform, falloff:
+        api.make_height_ao_params; wrap: a bool or (x, y) for tiling images.  None for an RGBF image, as
+        distance_field answers one."""
+        if self.rgbf:
+            return None
+        kw = dict(height_scale=height, directions=directions, channel=channel, channels=channels, strength=strength,
+                  bias=bias, uniform=uniform, falloff=falloff, wrap=wrap)
+        api.make_height_ao_params(radius, **kw)
+        d = _Device(self.device_id)
+        import torch
+        src = d.upload(self.pixels)
+        dst = (src[0].clone(),) + src[1:]
+        torch.cuda.current_stream(src[0].device).synchronize()     # the context's stream does not wait for the copy
+        buf = d.ao(src, dst, radius, **kw)
+        out = d.download(buf)
+        self._last = (buf, out)
+        return self._derived(out)
+
     def change_color_space(self, color_space: ColorSpace) -> bool:
         self.pixels = self._run(ImageOp.ColorSpace, dst_color_space=ColorSpace(color_space))
         self.color_space = ColorSpace(color_space)
@@ -246,13 +279,14 @@ class Image:
 
 
 _SIGNED = (Type.SNorm, Type.Int, Type.Float)      # isSigned (tool/main.cpp:63-75)
+_AO_KEYS = ("radius", "height", "directions", "channel", "channels", "strength", "bias", "uniform", "falloff", "wrap")
 
 
 def plan_process_image(width: int, height: int, src_width: int, src_height: int, image_color_space,
                        texture_color_space, mip_level: int = 0, type=Type.UNorm, rotate=None,
                        grayscale: bool = False, normal_map=None, flip_x: bool = False, flip_y: bool = False,
                        swizzle=None, premultiply: bool = False, bleed: Optional[dict] = None,
-                       sdf: Optional[dict] = None):
+                       sdf: Optional[dict] = None, ao: Optional[dict] = None):
     """The device steps of process_image, in order: ("ops", ImageOps) and ("resize", width, height, colour space).
     At most three ops steps: before the first resize, between the resizes, after the last.  bleed = dict(threshold=,
     wrap=, max_distance=) (any of them; Image.bleed_alpha's defaults) adds one ("bleed", threshold, wrap, max_distance)
@@ -265,7 +299,21 @@ def plan_process_image(width: int, height: int, src_width: int, src_height: int,
     the field over the resized image's channels before any later ops step moves texels; nothing resized: scale 1, in
     place.  The scale is the size before that resize divided by the size after it: ValueError unless it is 1, 2, 4, 8
     or 16 on both axes, and with premultiply (the field replaces an alpha that is no longer coverage).  None adds
-    nothing."""
+    nothing.
+    ao = dict(radius=, height=, directions=, channel=, channels=, strength=, bias=, uniform=, falloff=, wrap=) (radius
+    required; Image.ambient_occlusion's defaults) adds one ("ao", radius, keywords of Context.height_ao_device) step
+    where a bleed step would go, after the bleed if there is one: the occlusion of the height channel, in place.  With
+    normal_map it raises ValueError: the height is gone after that op."""
+    ao_step = None
+    if ao is not None:
+        if normal_map is not None:
+            raise ValueError("ao and normal_map exclude each other: the height is gone after the normal-map op")
+        unknown = set(ao) - set(_AO_KEYS)
+        if unknown or "radius" not in ao:
+            raise ValueError("ao: radius and any of %s; not %r" % (", ".join(_AO_KEYS[1:]), sorted(ao)))
+        kw = {("height_scale" if k == "height" else k): v for k, v in ao.items() if k != "radius"}
+        api.make_height_ao_params(ao["radius"], **kw)
+        ao_step = ("ao", ao["radius"], kw)
     sdf_step = None
     if sdf is not None:
         if premultiply:
@@ -339,6 +387,9 @@ def plan_process_image(width: int, height: int, src_width: int, src_height: int,
     if bleed_step is not None:
         first = next((i for i, st in enumerate(steps) if st[0] == "resize"), len(steps))
         steps.insert(first, bleed_step)
+    if ao_step is not None:
+        first = next((i for i, st in enumerate(steps) if st[0] == "resize"), len(steps))
+        steps.insert(first, ao_step)
     if sdf_step is not None:
         first = next((i for i, st in enumerate(steps) if st[0] == "resize"), len(steps))
         before, after = (src_width, src_height), (steps[first][1:3] if first < len(steps) else (src_width, src_height))
@@ -356,7 +407,7 @@ def process_image(image, image_color_space, texture_color_space, width: int, hei
                   grayscale: bool = False, normal_map: Optional[Tuple[NormalOptions, float]] = None,
                   flip_x: bool = False, flip_y: bool = False, swizzle: Optional[Sequence[Channel]] = None,
                   premultiply: bool = False, orig_image_format=ImageFormat.Invalid, device_id: int = 0,
-                  bleed: Optional[dict] = None, sdf: Optional[dict] = None) -> np.ndarray:
+                  bleed: Optional[dict] = None, sdf: Optional[dict] = None, ao: Optional[dict] = None) -> np.ndarray:
     """loadAndProcessImage (tool/main.cpp:147-277) after the load: colour-space change, resize to the target size
     (max(1, size >> mip_level); the full size first when a normal map is made), rotation, grayscale, normal map
     (normal_map = (NormalOptions, height); KeepSign added for signed types; resized to the mip size afterwards),
@@ -367,7 +418,10 @@ def process_image(image, image_color_space, texture_color_space, width: int, hei
     sdf = dict(spread=, threshold=, wrap=, channels=) writes a signed distance field (Image.distance_field) over the
     named channels of the resized image: the classes come from the alpha in front of that resize, after the ops pass
     there and the bleed, at a scale of source size / target size, which must be 1, 2, 4, 8 or 16 on both axes; not with
-    premultiply."""
+    premultiply.
+    ao = dict(radius=, height=, directions=, channel=, channels=, strength=, bias=, uniform=, falloff=, wrap=) writes
+    the ambient occlusion of the height channel (Image.ambient_occlusion) into the named channels, in front of the
+    resize to the texture's size, after the bleed; not with normal_map."""
     if isinstance(image, Image):
         image = image.pixels
     pixels = _pixels(image)
@@ -375,7 +429,7 @@ def process_image(image, image_color_space, texture_color_space, width: int, hei
         orig_image_format = ImageFormat.RGBA8 if pixels.dtype == np.uint8 else ImageFormat.RGBAF
     steps = plan_process_image(width, height, pixels.shape[1], pixels.shape[0], image_color_space,
                                texture_color_space, mip_level, type, rotate, grayscale, normal_map, flip_x, flip_y,
-                               swizzle, premultiply, bleed, sdf)
+                               swizzle, premultiply, bleed, sdf, ao)
     d = _Device(device_id)
     buf = d.upload(pixels)
     for s in steps:
@@ -383,6 +437,8 @@ def process_image(image, image_color_space, texture_color_space, width: int, hei
             buf = d.ops(buf, s[1])
         elif s[0] == "bleed":
             buf = d.bleed(buf, s[1], s[2], s[3])
+        elif s[0] == "ao":
+            buf = d.ao(buf, buf, s[1], **s[2])
         elif s[0] == "sdf_class":
             classes = buf
         elif s[0] == "sdf":

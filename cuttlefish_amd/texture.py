@@ -341,6 +341,7 @@ class Texture:
         self._bleed: List[dict] = []
         self._sdf: List[dict] = []
         self._spec_aa: List[dict] = []
+        self._ao: List[dict] = []
 
     def initialize(self, dimension, width: int, height: int, depth: int = 0, mip_levels: int = 1,
                    color_space: ColorSpace = ColorSpace.Linear) -> bool:
@@ -644,22 +645,32 @@ class Texture:
         size = dev[0].numel()*dev.element_size()
         return stack, dev, [dev.data_ptr() + i*size for i in range(len(images))]
 
-    def _in_place_pass(self, result_dtype, fields, call):
+    def _in_place_pass(self, result_dtype, fields, call, beside: Optional["Texture"] = None):
         """A pass over every image currently set, each within itself: the images of equal size and dtype share one
         call(pointers, pixel type, width, height, row pitch, pointer to their 16-byte records) and are replaced by what
-        it left in them.  -> the records in [mip][depth][face] order: mip, depth, face and `fields` of result_dtype."""
+        it left in them.  -> the records in [mip][depth][face] order: mip, depth, face and `fields` of result_dtype.
+        beside: a texture with an image of the same size wherever this one has one; those images are only read, their
+        dtype splits the groups too, and call() takes (their pointers, pixel type, row pitch) as three more arguments."""
         import torch
         groups: Dict[tuple, List[Tuple[int, int, int]]] = {}
         for m, level in enumerate(self._images):
             for d, dep in enumerate(level):
                 for f, im in enumerate(dep):
                     if im is not None:
-                        groups.setdefault((im.shape[0], im.shape[1], im.dtype.str), []).append((m, d, f))
+                        other = () if beside is None else (beside._images[m][d][f].dtype.str,)
+                        groups.setdefault((im.shape[0], im.shape[1], im.dtype.str) + other, []).append((m, d, f))
         records = {}
-        for (h, w, _), where in groups.items():
+        for key, where in groups.items():
+            h, w = key[:2]
             stack, dev, ptrs = self._stack_device([self._images[m][d][f] for m, d, f in where])
             res = torch.zeros((len(where), 4), dtype=torch.int32, device=dev.device)
-            call(ptrs, api.pixel_type_of(stack[0]), w, h, stack.strides[1], res.data_ptr())
+            torch.cuda.current_stream(dev.device).synchronize()      # the context's stream does not wait for the fill
+            if beside is None:
+                call(ptrs, api.pixel_type_of(stack[0]), w, h, stack.strides[1], res.data_ptr())
+            else:
+                bstack, bdev, bptrs = self._stack_device([beside._images[m][d][f] for m, d, f in where])
+                call(ptrs, api.pixel_type_of(stack[0]), w, h, stack.strides[1], res.data_ptr(), bptrs,
+                     api.pixel_type_of(bstack[0]), bstack.strides[1])
             out = dev.cpu().numpy()
             rec = res.cpu().numpy().view(result_dtype).reshape(-1)
             for i, (m, d, f) in enumerate(where):
@@ -776,6 +787,54 @@ class Texture:
         depth, face, clamped (texels whose variance met max_variance), saturated (texels whose alpha^2 reached 1) and
         max_added (the largest variance added, after variance_scale); [] before any call."""
         return [dict(r) for r in self._spec_aa]
+
+    def height_ambient_occlusion(self, heights: "Texture", channel="r", height_channel="r", *, radius: int,
+                                 height: float = 1.0, directions: int = 16, strength: float = 1.0, bias: float = 0.0,
+                                 uniform: bool = False, falloff: bool = False, wrap=False) -> bool:
+        """Ambient occlusion from height maps (Context.height_ao_device): `channel` of every image currently set in
+        this texture -- an occlusion or packed ORM texture -- takes the occlusion that the image of `heights` with the
+        same [mip][depth][face] index casts on itself, its heights in `height_channel`, `height` texels per stored unit
+        (the meaning the normal-map op's height has): the share of the sky the horizons within `radius` texels leave
+        open, 1 on a flat surface.  The other channels and `heights` are untouched; the pixel types stay.  The intended
+        order is the occlusion on level 0, then generate_mipmaps.  `heights` may be this texture: the height channel
+        may then be overwritten.  Images of equal size and dtypes share one call.  directions: 8, 16 or 32; strength,
+        bias, uniform, falloff: api.make_height_ao_params; wrap: a bool or (x, y) for tiling surfaces.  ao_results()
+        returns the records.  False on an invalid, converted or 3-D texture, on `heights` of other dimensions, levels,
+        faces or depth, and where `heights` lacks an image this texture has."""
+        if not isinstance(heights, Texture) or not self._valid or self._textures or self._dim == Dimension.Dim3D:
+            return False
+        if not heights._valid or heights._textures:
+            return False
+        if (heights._dim, heights._w, heights._h, heights._depth, heights._faces, heights._mips) != \
+                (self._dim, self._w, self._h, self._depth, self._faces, self._mips):
+            return False
+        for level, hlevel in zip(self._images, heights._images):
+            for dep, hdep in zip(level, hlevel):
+                for im, him in zip(dep, hdep):
+                    if im is not None and (him is None or him.shape != im.shape):
+                        return False
+        kw = dict(radius=radius, height_scale=height, directions=directions, channel=height_channel, channels=channel,
+                  strength=strength, bias=bias, uniform=uniform, falloff=falloff, wrap=wrap)
+        api.make_height_ao_params(**kw)
+        ctx = self._context()
+        if heights is self:
+            call = lambda ptrs, pt, w, h, pitch, res: ctx.height_ao_device(          # noqa: E731
+                ptrs, pt, w, h, pitch, ptrs, pt, pitch, results=res, **kw)
+            records = self._in_place_pass(api.HEIGHT_AO_RESULT_DTYPE, ("occluded", "darkest"), call)
+        else:
+            call = lambda ptrs, pt, w, h, pitch, res, hptrs, hpt, hpitch: ctx.height_ao_device(      # noqa: E731
+                hptrs, hpt, w, h, hpitch, ptrs, pt, pitch, results=res, **kw)
+            records = self._in_place_pass(api.HEIGHT_AO_RESULT_DTYPE, ("occluded", "darkest"), call, beside=heights)
+        for r in records:
+            r["darkest"] = float(np.uint32(r["darkest"]).view(np.float32))
+        self._ao = records
+        return True
+
+    def ao_results(self):
+        """The records of the last height_ambient_occlusion(): one dict per image it ran on, in [mip][depth][face] order
+        -- mip, depth, face, occluded (texels with a horizon above the bias) and darkest (the smallest value stored, as
+        a float); [] before any call."""
+        return [dict(r) for r in self._ao]
 
     # ---- environment maps (Context.equirect_to_cube / cube_prefilter / cube_sh9) ------------------------------------
     @staticmethod

@@ -530,6 +530,89 @@ int cfhip_spec_aa_array_device(cfhip_ctx* ctx, const void* const* normals, uint3
 	size_t rough_pitch_bytes, void* const* levels, uint32_t levels_count, const cfhip_spec_aa_params* params,
 	cfhip_spec_aa_result* results_device, void* stream);
 
+/* Ambient occlusion from height maps, by a horizon scan: the occlusion a height field casts on itself, the third map of
+ * an ORM set beside the normals (CFHIP_IMAGE_OP_NORMAL_MAP) and the roughness (above).  For every texel the highest
+ * horizon within `radius` texels is found in D directions; the share of the sky above a flat surface that each horizon
+ * hides is summed over the directions.  Every step below is an IEEE double operation in the order written (the library
+ * is built without contraction): add, subtract, multiply, divide, sqrt and fmin / fmax only, so results are defined to
+ * the bit.
+ *
+ *   input           `layers` source surfaces src[l] of one size width x height (1 to 32768 each, at most 2^30 texels)
+ *                   and one pixel type, rows src_pitch_bytes apart, only read.  h(p) is component `channel` (0 to 3),
+ *                   decoded as the pass above decodes: RGBA8 (float)(v / 255.0), RGBA16F half -> float, RGBA32F as
+ *                   stored.  A non-finite h reads 0.  H(p) = (double)height * (double)h(p): the product of two floats is
+ *                   exact.  height is finite, may be negative (an inverted map), and is in texels per stored unit --
+ *                   the meaning the normal-map op's height has, so one value gives consistent normals and occlusion.
+ *   directions      D = 8, 16 or 32.  The base vectors of the first quadrant:
+ *                     D = 8:  (1,0) (1,1)
+ *                     D = 16: (1,0) (2,1) (1,1) (1,2)
+ *                     D = 32: (1,0) (3,1) (2,1) (3,2) (1,1) (2,3) (1,2) (1,3)
+ *                   Direction d = q * D/4 + i is base i turned q times by (x, y) -> (-y, x).  Samples lie on texel
+ *                   centres: there is no interpolation.  The weight w_d is half the angle between the two neighbours of
+ *                   d, divided by 2 pi, as the nearest double -- but for (1,0) and (3,1) of D = 32 (and their three
+ *                   turns), which are one unit in the last place above it: so every set sums to exactly 1.0 in the
+ *                   order of the directions, and a flat surface comes out as exactly 1.
+ *                   cfhip_height_ao_directions exports the table.
+ *   reach           radius R: an integer, 1 to 64, in texels.  R_d is the largest k with k^2 (vx^2 + vy^2) <= R^2,
+ *                   decided in integers; it may be 0.  len_d = sqrt((double)(vx^2 + vy^2));
+ *                   r(d, k) = 1.0 / ((double)k * len_d); with CFHIP_HAO_FALLOFF
+ *                   g(d, k) = r(d, k) * (1.0 - (double)(k^2 (vx^2 + vy^2)) / (double)((R + 1)^2)), else g = r.
+ *   horizon         the samples q = p + k v_d, k = 1 ... R_d.  On an axis wrapped by CFHIP_HAO_WRAP_X / _Y the coordinate
+ *                   is taken modulo the side (a surface narrower than R is walked more than once); outside an unwrapped
+ *                   surface there is no sample.  m_d = the maximum over the samples of (H(q) - H(p)) * g(d, k);
+ *                   t_d = fmax(0.0, m_d - (double)bias), and t_d = 0 with no sample.
+ *   visibility      cosine-weighted, the default: vis_d = 1.0 / (1.0 + t_d*t_d), which is 1 - sin^2 of the horizon's
+ *                   elevation; with CFHIP_HAO_UNIFORM vis_d = 1.0 - t_d / sqrt(1.0 + t_d*t_d).  The surface normal is +z.
+ *   value           S = 0.0; for d = 0 ... D - 1 in that order S = S + w_d * vis_d;
+ *                   v = fmin(1.0, fmax(0.0, 1.0 - (double)strength * (1.0 - S))).
+ *   store           dst[l] is width x height texels of dst_pixel_type, rows dst_pitch_bytes apart.  channel_mask (bits
+ *                   R = 1, G = 2, B = 4, A = 8, not 0) names the components that receive v: RGBA8 takes
+ *                   (uint8)floor(v * 255 + 0.5), RGBA32F (float)v, RGBA16F (float)v rounded to half, nearest-even.  The
+ *                   other components are not written.  dst[l] may equal src[l] when the pixel types are equal, whatever
+ *                   the mask: all heights are read before anything is written.
+ *   results_device  one record per layer, or NULL for none: occluded (texels with any t_d > 0), darkest (the smallest
+ *                   (float)v of the layer as its bit pattern), two reserved zeros.  Identical calls return identical
+ *                   bytes.
+ *
+ * CFHIP_E_INVALID, before anything is enqueued: unknown flags, struct_size != sizeof(cfhip_height_ao_params),
+ * channel > 3, directions not 8, 16 or 32, radius outside 1 to 64, a channel_mask of 0 or above 15, a height that is not
+ * finite, a strength or bias that is negative or not finite, a non-zero reserved word, layers outside 1 to 65535, sides
+ * outside 1 to 32768, more than 2^30 texels in a surface, a pitch below a row, a pointer or pitch not aligned to a
+ * component of its pixel type, a NULL entry, dst[l] == src[l] with different pixel types.
+ *
+ * All layers share both launches: a plane pass (h of every texel as a float, 4 bytes per texel of the context's scratch,
+ * grown on demand) and the scan (a workgroup stages a tile of 64 x 16 texels -- 64 x 64 above R = 16 -- and a halo of R
+ * in LDS and walks every direction from there).  2 plain launches per call whatever the layers, directions or radius,
+ * on the call's stream; nothing waits for the host.  stream == NULL means the context's stream and the call
+ * synchronises. */
+enum { CFHIP_HAO_WRAP_X = 1, CFHIP_HAO_WRAP_Y = 2, CFHIP_HAO_UNIFORM = 4, CFHIP_HAO_FALLOFF = 8 };
+typedef struct cfhip_height_ao_params {
+	uint32_t struct_size;
+	uint32_t flags;
+	uint32_t channel;
+	uint32_t directions;
+	uint32_t radius;
+	uint32_t channel_mask;
+	float height;
+	float strength;
+	float bias;
+	uint32_t reserved;
+} cfhip_height_ao_params;
+typedef struct cfhip_height_ao_result {
+	uint32_t occluded;
+	uint32_t darkest;
+	uint32_t reserved[2];
+} cfhip_height_ao_result;
+int cfhip_height_ao_array_device(cfhip_ctx* ctx, const void* const* src, uint32_t layers, int src_pixel_type,
+	uint32_t width, uint32_t height, size_t src_pitch_bytes, void* const* dst, int dst_pixel_type,
+	size_t dst_pitch_bytes, const cfhip_height_ao_params* params, cfhip_height_ao_result* results_device, void* stream);
+
+/* The direction table of the pass above (host only, no context): vx[d], vy[d] and weight[d] for d = 0 ... directions - 1.
+ * The library carries the weights as 17-digit literals, within a unit in the last place of half the angle between a
+ * direction's neighbours over 2 pi; S = 0.0, S = S + weight[d] in the order of d ends at exactly 1.0.  Any of the
+ * three outputs may be NULL.  CFHIP_E_INVALID for a `directions` that is not 8, 16 or 32. */
+int cfhip_height_ao_directions(uint32_t directions, int32_t* vx, int32_t* vy, double* weight);
+
 /* Environment maps for image-based lighting: an equirectangular panorama onto the six faces of a cube, the cube's
  * GGX-prefiltered mip chain (level k = the environment convolved with a lobe of roughness r_k), and its projection on
  * nine spherical-harmonic coefficients (the diffuse term).  Every formula below is a sequence of IEEE double operations
@@ -1371,7 +1454,7 @@ int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* p
 	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass), cfhip_alpha_coverage_device, cfhip_alpha_bleed_array_device, cfhip_alpha_sdf_array_device (every pass), cfhip_spec_aa_array_device (every launch), cfhip_equirect_to_cube_device, cfhip_cube_prefilter_device (every level) or cfhip_cube_sh9_device (both launches) call on
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass), cfhip_alpha_coverage_device, cfhip_alpha_bleed_array_device, cfhip_alpha_sdf_array_device (every pass), cfhip_spec_aa_array_device (every launch), cfhip_height_ao_array_device (both launches), cfhip_equirect_to_cube_device, cfhip_cube_prefilter_device (every level) or cfhip_cube_sh9_device (both launches) call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
