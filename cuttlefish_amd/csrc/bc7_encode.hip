@@ -43,6 +43,7 @@
 #include "bc7_rcp.h"
 #include "bc7_roles.h"
 #include "bc7_cand.h"
+#include "bc7_pack.h"
 
 namespace {
 
@@ -63,6 +64,7 @@ __device__ const cf_bc7_role_table k_bc7_roles = cf_bc7_make_roles();
 // what a stored candidate is, by id, and the texels of its fits (bc7_cand.h)
 __device__ const cf_bc7_cand_table k_bc7_cands = cf_bc7_make_cands();
 __device__ const cf_bc7_mask_table k_bc7_masks = cf_bc7_make_masks();
+__device__ const cf_bc7_pack_table k_bc7_pack = cf_bc7_make_pack();
 
 // the interpolation weights of a fit's palette entries as bytes (bc7_packed.h)
 __device__ const cf_bc7_weight_table k_bc7_weights = cf_bc7_make_weights();
@@ -474,7 +476,9 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 	// multiply is not turned back into a shift and a subtraction
 	int kfac = -(2 << WBITS);
 	asm volatile("" : "+s"(kfac));
-	uint32_t err = pp_sum;
+	// unit weights: err sums the masked keys themselves and the error comes from that sum once per assignment
+	// (bc7_packed.h: search_key_sum_error) instead of a shift and an add per texel
+	uint32_t err = UNITW ? 0u : pp_sum;
 	uint32_t wp0 = 0, wp1 = 0, wp2 = 0, wp3 = 0;
 #pragma unroll 1
 	for (uint32_t r2 = 0; r2 < 4u; r2 += 2u) {
@@ -512,6 +516,20 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 					bestm[0] = v0 < bestm[0] ? v0 : bestm[0]; bestm[1] = v1 < bestm[1] ? v1 : bestm[1];
 					bestm[2] = v2 < bestm[2] ? v2 : bestm[2]; bestm[3] = v3 < bestm[3] ? v3 : bestm[3];
 				}
+				// mode 6: the other palette half lives in the neighbouring lane.  Once per row, behind the row's last
+				// matrix instruction and under the execution mask of the mode-6 lanes (a lane pair is on or off together):
+				// four v_min_i32_dpp for the wave's few mode-6 lanes instead of an exchange and a select per texel in every
+				// lane.  No matrix instruction may stand inside the masked region: it would mis-read the A rows of the
+				// lanes switched off (tools/ubench/mfma_layout.hip).
+				if (NK == 8) {
+					if (m6) {
+#pragma unroll
+						for (int j = 0; j < 4; ++j) {
+							const int other = (int)cf_xor1((uint32_t)bestm[j]);
+							bestm[j] = other < bestm[j] ? other : bestm[j];
+						}
+					}
+				}
 			}
 #pragma unroll
 			for (int j = 0; j < 4; ++j) {
@@ -529,16 +547,16 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 						const int v = key_min_form(dt, kfac, base[k]);
 						bestk = v < bestk ? v : bestk;
 					}
-					// mode 6: the other palette half lives in the neighbouring lane (the 4-entry search is entered
-					// only when no active lane of the wave is a mode-6 lane: it has no exchange at all)
-					if (NK == 8) {
+					// mode 6, perceptual metric: the other palette half lives in the neighbouring lane (the 4-entry search
+					// is entered only when no active lane of the wave is a mode-6 lane: it has no exchange at all)
+					if (NK == 8 && !UNITW) {
 						const int other = (int)cf_xor1((uint32_t)bestk);
 						bestk = (m6 && other < bestk) ? other : bestk;
 					}
 					key = (uint32_t)bestk;   // F/2 (sum w c^2 - 2 p.(w c)) + weight, two's complement
 				}
 				key = ((mrow >> j) & 1u) ? key : 0u;
-				err += (uint32_t)((int)key >> WBITS);
+				err += UNITW ? key : (uint32_t)((int)key >> WBITS);
 				if (UNITW) krow[j] = key;
 				else wrow |= (key & 127u) << (8*j);
 			}
@@ -546,16 +564,19 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 		}
 		wp0 = wp2; wp1 = wp3; wp2 = wpair[0]; wp3 = wpair[1];
 	}
-	f.err = err;
+	if (!UNITW) f.err = err;
 	f.w[0] = wp0; f.w[1] = wp1; f.w[2] = wp2; f.w[3] = wp3;
 	// the refit sums in a loop of their own: their 6 accumulators and the planar rows are
 	// then not live across the texel search above (which holds the 16 palette registers)
 	uint32_t S = 0, A = 0, B = 0, C = 0, U[4] = {0, 0, 0, 0}, V[4] = {0, 0, 0, 0};
+	// unit weights: the four trips unrolled, every weight word read where it lies (as a loop it rotated the four words
+	// through four v_mov_b32 per trip); the perceptual instances keep the loop
+	constexpr int SUMS_UNROLL = UNITW ? 4 : 1;
 	if (want_lsq) {   // uniform: the last round's refit would never be used
-#pragma unroll 1
+#pragma unroll SUMS_UNROLL
 		for (uint32_t r = 0; r < 4u; ++r) {
-			const uint32_t wrow = wp0;
-			wp0 = wp1; wp1 = wp2; wp2 = wp3; wp3 = wrow;   // rotates back to the start after 4 trips
+			const uint32_t wrow = UNITW ? f.w[r] : wp0;
+			if (!UNITW) { wp0 = wp1; wp1 = wp2; wp2 = wp3; wp3 = wrow; }   // rotates back to the start after 4 trips
 			uint32_t P[4];
 			// (the block offset made opaque per trip: the row address is then formed here, with the array's base in
 			// the instruction's offset field, instead of being hoisted into a register that lives across the search)
@@ -574,6 +595,14 @@ __device__ __forceinline__ void assign_lsq_lane(const Tex& tx, uint32_t mask, bo
 		B = 64u*S - C;
 		U[0] = 64u*(s01 & 0xFFFFu) - V[0]; U[1] = 64u*(s01 >> 16) - V[1];
 		U[2] = 64u*(s23 & 0xFFFFu) - V[2]; U[3] = 64u*(s23 >> 16) - V[3];
+	}
+	if (UNITW) {
+		// the weights' sum: the refit sums' S where they ran, otherwise four dot products
+		uint32_t ws = S;
+		if (!want_lsq)
+			ws = __builtin_amdgcn_udot4(f.w[0], 0x01010101u, __builtin_amdgcn_udot4(f.w[1], 0x01010101u,
+				__builtin_amdgcn_udot4(f.w[2], 0x01010101u, __builtin_amdgcn_udot4(f.w[3], 0x01010101u, 0u, false), false), false), false);
+		f.err = search_key_sum_error(pp_sum, err, ws);
 	}
 	const int det = (int)__umul24((uint32_t)__builtin_popcount(mask), C) - (int)__umul24(S, S);
 	ok = det > 0;
@@ -822,16 +851,32 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 			const uint4 rw = *reinterpret_cast<const uint4*>(tx.tp() + 4u*r);
 			const uint32_t raw[4] = {rw.x, rw.y, rw.z, rw.w};
 			const uint32_t mrow = (mask >> (4u*r)) & 15u;
+			if constexpr (UNITW) {
+				// one select per texel, then two texels per v_min3_f32 / v_max3_f32 (bc7_packed.h: proj_extremes2)
+				float tm[4];
 #pragma unroll
-			for (int j = 0; j < 4; ++j) {
-				const uint32_t p = texel<true>(tx, raw[j]);
-				const bool m = (mrow >> j) & 1u;
-				float t = axis[0]*(fb(p, 0) - mean[0]);
-				t = fmaf(axis[1], fb(p, 1) - mean[1], t);
-				t = fmaf(axis[2], fb(p, 2) - mean[2], t);
-				t = fmaf(axis[3], fb(p, 3) - mean[3], t);
-				tmin = m ? fminf(tmin, t) : tmin;
-				tmax = m ? fmaxf(tmax, t) : tmax;
+				for (int j = 0; j < 4; ++j) {
+					const uint32_t p = texel<true>(tx, raw[j]);
+					float t = axis[0]*(fb(p, 0) - mean[0]);
+					t = fmaf(axis[1], fb(p, 1) - mean[1], t);
+					t = fmaf(axis[2], fb(p, 2) - mean[2], t);
+					t = fmaf(axis[3], fb(p, 3) - mean[3], t);
+					tm[j] = proj_or_nan(t, (mrow >> j) & 1u);
+				}
+				proj_extremes2(tmin, tmax, tm[0], tm[1]);
+				proj_extremes2(tmin, tmax, tm[2], tm[3]);
+			} else {
+#pragma unroll
+				for (int j = 0; j < 4; ++j) {
+					const uint32_t p = texel<true>(tx, raw[j]);
+					const bool m = (mrow >> j) & 1u;
+					float t = axis[0]*(fb(p, 0) - mean[0]);
+					t = fmaf(axis[1], fb(p, 1) - mean[1], t);
+					t = fmaf(axis[2], fb(p, 2) - mean[2], t);
+					t = fmaf(axis[3], fb(p, 3) - mean[3], t);
+					tmin = m ? fminf(tmin, t) : tmin;
+					tmax = m ? fmaxf(tmax, t) : tmax;
+				}
 			}
 		}
 		// sum over the subset of sum_c p_c^2 (channels that are not coded have p = 0), or of the
@@ -942,30 +987,20 @@ __device__ __forceinline__ uint32_t w2i(uint32_t w, uint32_t ib)
 // Field slots f (a lane owns slot hl, and hl + 32 too when its group has only 32 lanes):
 //    0..15 : first index field, texel = f        16..31 : second index field, texel = f - 16
 //   32..55 : endpoint field (channel-major)      56..61 : p-bits      62 : mode/partition/... header
+// What a slot holds, where it stands and where its value comes from is one word of the shape's row of k_bc7_pack
+// (bc7_pack.h); what depends on the partition -- the anchors, the endpoint orders, the header's value -- is formed here.
 __device__ __forceinline__ uint4 pack_block_group(const uint32_t* wcol, uint32_t id, uint32_t lane,
 	bool pair)
 {
 	const uint32_t h = lane >> 5, hl = pair ? (lane & 31u) : lane, hbase = pair ? (lane & 32u) : 0u;
-	uint32_t mode, part = 0, rot = 0, isel = 0;
-	if (id == 0u) mode = 6;
-	else if (id < 5u) { mode = 5; rot = id - 1u; }
-	else if (id < 13u) { mode = 4; rot = (id - 5u) & 3u; isel = (id - 5u) >> 2; }
-	else if (id < 128u) { mode = 1; part = id - 64u; }
-	else if (id < 192u) { mode = 3; part = id - 128u; }
-	else if (id < 256u) { mode = 0; part = id - 192u; }
-	else if (id < 320u) { mode = 2; part = id - 256u; }
-	else { mode = 7; part = id - 320u; }
-	// per-mode constants, one nibble per mode (mode 0 in the low nibble)
-	const uint32_t ns  = (0x21112323u >> (4u*mode)) & 15u;
-	const uint32_t pbn = (0x60006664u >> (4u*mode)) & 15u;
-	const uint32_t cb  = (0x57757564u >> (4u*mode)) & 15u;
-	const uint32_t ab  = (0x57860000u >> (4u*mode)) & 15u;
-	const uint32_t pk  = (0x11001021u >> (4u*mode)) & 15u;
-	const uint32_t ib  = (0x24222233u >> (4u*mode)) & 15u;
-	const uint32_t ib2 = (0x00230000u >> (4u*mode)) & 15u;
-	uint32_t ibc = ib, iba = ib2;
-	const bool swapsets = mode == 4u && isel != 0u;
-	if (swapsets) { ibc = 3u; iba = 2u; }
+	// the shape's row: its candidate word, then one word per field slot (bc7_pack.h)
+	// (the winner's id is below 384; the clamp keeps the row inside the table whatever a lane without a block holds)
+	const uint32_t shape = cf_bc7_cand_index(id);
+	const uint32_t* row = k_bc7_pack.w + (shape < CF_CAND_TABLE_N ? shape : CF_CAND_TABLE_N - 1u)*CF_PACK_ROW;
+	const uint32_t cw = row[0];
+	const uint32_t mode = CF_CAND_MODE(cw), ns = CF_CAND_NS(cw);
+	const uint32_t part = ns > 1u ? id & 63u : 0u;
+	const uint32_t ibc = CF_CAND_IB(cw), iba = CF_CAND_IB2(cw);
 	const uint32_t p2 = k_part2[part], p3 = k_part3[part];
 	uint32_t a1 = 0, a2 = 0;
 	if (ns == 2u) a1 = k_anchor2[part];
@@ -990,68 +1025,26 @@ __device__ __forceinline__ uint4 pack_block_group(const uint32_t* wcol, uint32_t
 	const uint32_t swmask = sw0 | (sw1 << 1) | (sw2 << 2);
 	idxv = ((swmask >> sb) & 1u) ? ((1u << ibc) - 1u) - idxv : idxv;
 	idxs = sws ? ((1u << iba) - 1u) - idxs : idxs;
-
-	const uint32_t ne = 2u*ns;
-	const uint32_t hdr = mode + 1u + pbn + ((mode == 4u || mode == 5u) ? 2u : 0u) + (mode == 4u ? 1u : 0u);
-	const uint32_t base_pb = hdr + ne*(3u*cb + ab);
-	const uint32_t npb = pk == 1u ? ne : (pk == 2u ? 2u : 0u);
-	const uint32_t baseA = base_pb + npb;
-	const uint32_t baseB = baseA + 16u*ib - ns;
+	const uint32_t swall = swmask | (sws << 3);      // endpoint orders: subsets 0..2, the scalar plane
+	// the first index field loses the bit of every anchor before the texel
+	const uint32_t before = (t > 0u ? 1u : 0u) + ((ns >= 2u && t > a1) ? 1u : 0u) + ((ns == 3u && t > a2) ? 1u : 0u);
+	const uint32_t pbn = cf_bc7_pack_pbn(mode);
+	uint32_t hval = (1u << mode) | (part << (mode + 1u));
+	if (CF_CAND_P45(cw))
+		hval = (1u << mode) | (CF_CAND_ROT(cw) << (mode + 1u + pbn)) | (CF_CAND_ISEL(cw) << (mode + 1u + pbn + 2u));
 
 	uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
 	const uint32_t npass = pair ? 2u : 1u;
 	for (uint32_t pass = 0; pass < npass; ++pass) {
 		const uint32_t f = hl + 32u*pass;
-		uint32_t val = 0, off = 0;
-		bool have = false;
-		if (f < 16u) {
-			const uint32_t before = (t > 0u ? 1u : 0u) + ((ns >= 2u && t > a1) ? 1u : 0u) +
-				((ns == 3u && t > a2) ? 1u : 0u);
-			val = swapsets ? idxs : idxv;
-			off = baseA + t*ib - before;
-			have = true;
-		} else if (f < 32u) {
-			val = swapsets ? idxv : idxs;
-			off = baseB + t*ib2 - (t > 0u ? 1u : 0u);
-			have = ib2 != 0u;
-		} else if (f < 56u) {
-			const uint32_t g = f - 32u;
-			const uint32_t ch = g/ne, e = g - ch*ne;
-			const uint32_t es = e ^ ((swmask >> (e >> 1)) & 1u);          // endpoint order after the swap
-			const uint32_t qw = wcol[es*CF_WG_THREADS];
-			if (ch < 3u) {
-				val = (qw >> (8u*ch)) & 255u;
-				off = hdr + (ch*ne + e)*cb;
-				have = true;
-			} else if (ch == 3u && ab) {
-				// modes 4/5: the scalar plane's endpoints are parked in q[4], q[5] (byte 3)
-				const uint32_t sq = wcol[(4u + ((e ^ sws) & 1u))*CF_WG_THREADS];
-				val = (iba ? sq : qw) >> 24;
-				off = hdr + 3u*ne*cb + e*ab;
-				have = true;
-			}
-		} else if (f < 62u) {
-			const uint32_t e = f - 56u;
-			const uint32_t pbw = wcol[6u*CF_WG_THREADS];
-			if (pk == 1u && e < ne) {
-				val = (pbw >> (e ^ ((swmask >> (e >> 1)) & 1u))) & 1u;
-				off = base_pb + e;
-				have = true;
-			} else if (pk == 2u && e < 2u) {
-				// shared p-bit of subset e: both endpoint bits are equal
-				val = (pbw >> (2u*e)) & 1u;
-				off = base_pb + e;
-				have = true;
-			}
-		} else if (f == 62u) {
-			val = (1u << mode) | (part << (mode + 1u)) | (rot << (mode + 1u + pbn)) |
-				(isel << (mode + 1u + pbn + 2u));
-			if (!(mode == 4u || mode == 5u))
-				val = (1u << mode) | (part << (mode + 1u));
-			off = 0;
-			have = true;
-		}
-		val = have ? val : 0u;
+		const uint32_t s = row[1u + f];
+		const uint32_t kind = CF_PACK_KIND(s);
+		const uint32_t sbit = (swall >> CF_PACK_ORDER(s)) & 1u;
+		const uint32_t cword = wcol[(CF_PACK_WORD(s) ^ (CF_PACK_FLIPW(s) & sbit))*CF_WG_THREADS];
+		const uint32_t cval = (cword >> (CF_PACK_SHIFT(s) ^ (CF_PACK_FLIPS(s) & sbit))) & (CF_PACK_BYTE(s) ? 255u : 1u);
+		uint32_t val = kind == CF_PACK_KIND_COL ? cval : (kind == CF_PACK_KIND_HDR ? hval : (kind == CF_PACK_KIND_IDX1 ? idxv : idxs));
+		val = CF_PACK_HAVE(s) ? val : 0u;
+		const uint32_t off = CF_PACK_OFF(s) - (f < 16u ? before : 0u);
 		const uint32_t wi = off >> 5, sh = off & 31u;
 		const unsigned long long vv = (unsigned long long)val << sh;
 		const uint32_t lo = (uint32_t)vv, hi = (uint32_t)(vv >> 32);

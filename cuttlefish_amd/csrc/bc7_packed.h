@@ -83,6 +83,36 @@ CF_PK uint32_t search_bias_part(uint32_t s0, uint32_t s1, uint32_t s2, uint32_t 
 }
 CF_PK uint32_t search_pp_fold(uint32_t pp_sum, uint32_t bias) { return pp_sum - (bias << 8); }
 
+// An assignment's error from the SUM of its texels' masked keys instead of a shift and an add per texel
+// (tests/test_bc7_shelved_trims.py).  A key inside the subset is 256 e_t + w_t with e_t = key >> 8 its signed error part
+// and w_t in 0..64 its weight byte; outside the subset it is 0.  So sum_t key_t = 256 sum_t e_t + wsum, wsum the sum of
+// the assignment's weight bytes (the refit sums' S, or four dot products over the weight words), and
+// (ksum - wsum) >> 8 = sum_t e_t exactly: the difference is a multiple of 256.  Ranges, in the manner of search_pp_fold:
+// key' < 2^27 with the texel-constant term left out (search_pp_fold), and key' >= 0 there: its error part is
+// |p - c|^2 + (256 A_t - |p|^2) over the coded channels and 256 a >= a^2 for a byte.  At most 16 texels, so ksum in
+// [0, 2^31) and 0 <= wsum <= 1024 <= ksum's weight part: ksum - wsum = 256 sum e_t stays inside a word, the shift is
+// exact, and pp_sum + sum_t e_t is the sum the per-texel form reaches, in the same 32-bit modular arithmetic.  (The
+// shift is arithmetic all the same: the identity holds for keys of either sign while the sum fits a signed word.)
+CF_PK uint32_t search_key_sum_error(uint32_t pp_sum, uint32_t ksum, uint32_t wsum)
+{
+	return pp_sum + (uint32_t)((int)(ksum - wsum) >> 8);
+}
+
+// Extremes of a subset's projections, two texels per step: a texel outside the subset contributes a quiet NaN, which
+// minimum and maximum pass over (fminf / fmaxf return the other operand; v_min3_f32 / v_max3_f32 likewise), so one select
+// per texel replaces two.  Against the scan that selects after every fminf the value is the same; only where the
+// extreme is a zero met with both signs can the SIGN differ, since the order of the comparisons differs and +0 == -0.
+// A subset whose projections are all equal has tmin == tmax == that value; an empty one keeps the start values.
+// The sign of a zero extreme reaches no payload byte: tmin and tmax feed (tmax - tmin) frac, tmin + d and
+// fmaf(axis, t, mean), whose values agree for +0 and -0 except again in the sign of a zero, and clamp255 and the
+// quantiser's rounding map both zeros to code 0 (tests/test_bc7_shelved_trims.py, tests/test_gpu_bc7_shelved_trims.py).
+CF_PK float proj_or_nan(float t, bool in_subset) { return in_subset ? t : __builtin_nanf(""); }
+CF_PK void proj_extremes2(float& tmin, float& tmax, float a, float b)
+{
+	tmin = __builtin_fminf(__builtin_fminf(tmin, a), b);
+	tmax = __builtin_fmaxf(__builtin_fmaxf(tmax, a), b);
+}
+
 // The low bytes of four keys as the bytes of one word (a key's low byte is its weight, 0 for a texel outside the subset).
 // Two byte permutes and an or on the device.
 CF_PK uint32_t key_row_weights(uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3)

@@ -32,13 +32,15 @@ from isa_mix import FAST  # noqa: E402
 _ASSEMBLY = ("// the fit this lane's geometry-cache column now holds", "// ---- assemble candidates in their leader lanes")
 _CAND_GEO = ("// The same geometry from what the candidate's leader stored with it",
              "// It is read from what the candidate's leader stored with it")
+# (where the texel loop hands its error out: the unit-weight search forms it later, from the key sum)
+_ERR_OUT = ("\tf.err = err;", "\tif (!UNITW) f.err = err;")
 # (a fourth element marks a region that not every source has -- fit_geo left the encoder, cand_geo came late --: skipped
 # where its opening is missing, so that this source and its parents can both be tabulated)
 BC7_REGIONS = (
     ("quantize", "__device__ __forceinline__ void quantize(", "// View of one block's texels in LDS"),
-    ("assign_lsq_lane: palette", "__device__ __forceinline__ void assign_lsq_lane(", "\tuint32_t err = pp_sum;"),
-    ("assign_lsq_lane: texel loop", "\tuint32_t err = pp_sum;", "\tf.err = err;"),
-    ("assign_lsq_lane: refit sums", "\tf.err = err;", "// Least squares WITH the quantisation inside"),
+    ("assign_lsq_lane: palette", "__device__ __forceinline__ void assign_lsq_lane(", ("\tuint32_t err = pp_sum;", "\tuint32_t err = UNITW ? 0u : pp_sum;")),
+    ("assign_lsq_lane: texel loop", ("\tuint32_t err = pp_sum;", "\tuint32_t err = UNITW ? 0u : pp_sum;"), _ERR_OUT),
+    ("assign_lsq_lane: refit sums", _ERR_OUT, "// Least squares WITH the quantisation inside"),
     ("refit_window", "__device__ __forceinline__ void refit_window(", "// Fit-geometry cache"),
     ("fit_lane", "__device__ __forceinline__ void fit_lane(", "__device__ __forceinline__ uint32_t w2i("),
     ("pack_block_group", "__device__ __forceinline__ uint4 pack_block_group(", "// The 14 integer moments of a set of texels"),

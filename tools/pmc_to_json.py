@@ -72,6 +72,10 @@ def main():
         out["traffic_bytes_per_launch"] = int(2.0*c["FETCH_SIZE"]*1024 + c["WRITE_SIZE"]*1024)
         out["traffic_note"] = ("gfx950 FETCH_SIZE tallies 128-B requests at 64 B (MI355X_MICROARCH.md, HBM section): "
                                "doubled; WRITE_SIZE as is (equals the payload)")
+    # bench.py finds the kernel by the prefix of its first three template arguments and isa_mix takes the largest
+    # instance that matches: for the wide kernels that is level 4's, also in the file of level 3.  Say so in the file.
+    out["mix_note"] = ("code_sha256 and the static non-fp32 price are those of %s, the largest instance matching %r "
+                       "(tools/isa_mix.py), as bench.py looks the kernel up" % (mix["kernel"], a.mangled))
     json.dump(out, open(a.out, "w"), indent=1)
     print(json.dumps(out, indent=1))
 
