@@ -20,7 +20,7 @@
 //         vector atomic each per workgroup of 64 x 64 texels.
 // All layers of a call share every launch (grid z).  No kernel here may use scratch, spill a vector register or use
 // AGPRs (cuttlefish_amd/build.py).
-#include "cf_device.h"
+#include "cf_texel.h"
 #include "alpha_bleed.h"
 
 namespace {
@@ -75,12 +75,10 @@ __device__ __forceinline__ uint64_t nearest(const cfab_call& c, const uint32_t* 
 __global__ void __launch_bounds__(WG)
 cfhip_alpha_bleed_seed_kernel(cfab_call c, float t, uint32_t* __restrict__ seeds, cfhip_bleed_result* __restrict__ results)
 {
-	// an 8-bit alpha has 256 values: (float)(v / 255.0) once per workgroup, as the coverage pass reads it
 	__shared__ float of_u8[256];
 	__shared__ uint32_t sum;                           // the workgroup's seeds: its wavefronts meet here before memory
 	const uint32_t v = threadIdx.y*CFAB_WG_X + threadIdx.x;
-	if (c.pixel_type == CFHIP_PIXEL_RGBA8)
-		of_u8[v] = (float)((double)v/255.0);
+	cf_fill_of_u8(of_u8, v, c.pixel_type == CFHIP_PIXEL_RGBA8);
 	if (v == 0)
 		sum = 0;
 	__syncthreads();
@@ -94,15 +92,13 @@ cfhip_alpha_bleed_seed_kernel(cfab_call c, float t, uint32_t* __restrict__ seeds
 		float a = __builtin_nanf("");                  // a texel outside the surface is no seed
 		if (active) {
 			const uint8_t* row = static_cast<const uint8_t*>(c.images[layer]) + (size_t)y*c.pitch;
+			// (the ladder is written out: through a run-time helper it is lowered as a switch, two more scalar branches for RGBA8)
 			if (c.pixel_type == CFHIP_PIXEL_RGBA8)
-				a = of_u8[row[(size_t)x*4u + 3u]];
+				a = cf_load_channel<CFHIP_PIXEL_RGBA8>(row, x, 3u, of_u8);
 			else if (c.pixel_type == CFHIP_PIXEL_RGBA32F)
-				a = *reinterpret_cast<const float*>(row + (size_t)x*16u + 12u);
-			else {
-				union { unsigned short u; _Float16 f; } cv;
-				cv.u = *reinterpret_cast<const unsigned short*>(row + (size_t)x*8u + 6u);
-				a = (float)cv.f;
-			}
+				a = cf_load_channel<CFHIP_PIXEL_RGBA32F>(row, x, 3u, of_u8);
+			else
+				a = cf_load_channel<CFHIP_PIXEL_RGBA16F>(row, x, 3u, of_u8);
 		}
 		const bool seed = a > t;                       // false for a NaN
 		if (active)

@@ -17,17 +17,12 @@
 //   resolve   scale > 1: per output texel the sum of its s x s signed distances in double (exact), v and the store
 // All layers of a call share every launch (grid z).  No kernel here may use scratch, spill a vector register or use
 // AGPRs (cuttlefish_amd/build.py).
-#include "cf_device.h"
+#include "cf_texel.h"
 #include "alpha_sdf.h"
 
 namespace {
 
 constexpr uint32_t WG = CFSD_WG_X*CFSD_WG_Y;
-
-__device__ __forceinline__ uint32_t pixel_size(int32_t type)
-{
-	return type == CFHIP_PIXEL_RGBA8 ? 4u : type == CFHIP_PIXEL_RGBA32F ? 16u : 8u;
-}
 
 // the signed distance of a texel: rho - 0.5 inside, 0.5 - rho outside, rho = (float)sqrt((double)e) -- the double
 // square root is correctly rounded (mip_post.hip relies on the same)
@@ -43,38 +38,16 @@ __device__ __forceinline__ void store_field(const cfsd_call& c, uint32_t layer, 
 	const double m = sum/(double)(c.scale*c.scale);
 	double v = 0.5 + m/(2.0*(double)c.spread);
 	v = v < 0.0 ? 0.0 : v > 1.0 ? 1.0 : v;
-	uint8_t* p = static_cast<uint8_t*>(c.dst[layer]) + (size_t)y*c.dst_pitch + (size_t)x*pixel_size(c.dst_type);
-	if (c.dst_type == CFHIP_PIXEL_RGBA8) {
-		const uint8_t q = (uint8_t)floor(v*255.0 + 0.5);
-#pragma unroll
-		for (uint32_t ch = 0; ch < 4; ++ch)
-			if (c.channel_mask >> ch & 1u)
-				p[ch] = q;
-	} else if (c.dst_type == CFHIP_PIXEL_RGBA32F) {
-		const float q = (float)v;
-#pragma unroll
-		for (uint32_t ch = 0; ch < 4; ++ch)
-			if (c.channel_mask >> ch & 1u)
-				reinterpret_cast<float*>(p)[ch] = q;
-	} else {
-		union { unsigned short u; _Float16 f; } cv;
-		cv.f = (_Float16)(float)v;                     // nearest-even
-#pragma unroll
-		for (uint32_t ch = 0; ch < 4; ++ch)
-			if (c.channel_mask >> ch & 1u)
-				reinterpret_cast<unsigned short*>(p)[ch] = cv.u;
-	}
+	cf_store_unit(static_cast<uint8_t*>(c.dst[layer]) + (size_t)y*c.dst_pitch, x, c.dst_type, c.channel_mask, v);
 }
 
 __global__ void __launch_bounds__(WG)
 cfhip_alpha_sdf_classify_kernel(cfsd_call c, float t, uint64_t* __restrict__ plane, cfhip_sdf_result* __restrict__ results)
 {
-	// an 8-bit alpha has 256 values: (float)(v / 255.0) once per workgroup, as the coverage pass reads it
 	__shared__ float of_u8[256];
 	__shared__ uint32_t sum;                           // the workgroup's inside texels: its wavefronts meet here
 	const uint32_t v = threadIdx.y*CFSD_WG_X + threadIdx.x;
-	if (c.src_type == CFHIP_PIXEL_RGBA8)
-		of_u8[v] = (float)((double)v/255.0);
+	cf_fill_of_u8(of_u8, v, c.src_type == CFHIP_PIXEL_RGBA8);
 	if (v == 0)
 		sum = 0;
 	__syncthreads();
@@ -89,15 +62,13 @@ cfhip_alpha_sdf_classify_kernel(cfsd_call c, float t, uint64_t* __restrict__ pla
 		float a = __builtin_nanf("");                  // a texel outside the surface is not inside
 		if (active) {
 			const uint8_t* row = static_cast<const uint8_t*>(c.src[layer]) + (size_t)y*c.src_pitch;
+			// (the ladder is written out: through a run-time helper it is lowered as a switch, two more scalar branches for RGBA8)
 			if (c.src_type == CFHIP_PIXEL_RGBA8)
-				a = of_u8[row[(size_t)x*4u + 3u]];
+				a = cf_load_channel<CFHIP_PIXEL_RGBA8>(row, x, 3u, of_u8);
 			else if (c.src_type == CFHIP_PIXEL_RGBA32F)
-				a = *reinterpret_cast<const float*>(row + (size_t)x*16u + 12u);
-			else {
-				union { unsigned short u; _Float16 f; } cv;
-				cv.u = *reinterpret_cast<const unsigned short*>(row + (size_t)x*8u + 6u);
-				a = (float)cv.f;
-			}
+				a = cf_load_channel<CFHIP_PIXEL_RGBA32F>(row, x, 3u, of_u8);
+			else
+				a = cf_load_channel<CFHIP_PIXEL_RGBA16F>(row, x, 3u, of_u8);
 		}
 		const uint64_t inside = __ballot(a > t);       // false for a NaN
 		if (threadIdx.x == 0)
@@ -116,9 +87,7 @@ cfhip_alpha_sdf_classify_kernel(cfsd_call c, float t, uint64_t* __restrict__ pla
 // 64 texels of a row that repeats with period `width`, from position x0 (any sign) on: bit i = texel (x0 + i) mod width
 __device__ __forceinline__ uint64_t periodic_bits(const uint64_t* __restrict__ row, uint32_t width, int32_t x0)
 {
-	int32_t p = x0 % (int32_t)width;
-	if (p < 0)
-		p += (int32_t)width;
+	int32_t p = cf_floor_mod(x0, width);
 	uint64_t out = 0;
 	for (uint32_t got = 0; got < 64u;) {
 		const uint32_t s = (uint32_t)p & 63u;
@@ -196,11 +165,9 @@ cfhip_alpha_sdf_column_kernel(cfsd_call c, const uint8_t* __restrict__ rows, uin
 	// tile row i is surface row y0 - halo + i: modulo the height on a wrapped axis, not staged (and never read) outside
 	for (uint32_t i = wave; i < count + 2u*halo; i += CFSD_WG_Y) {
 		int32_t yy = (int32_t)(y0 + i) - (int32_t)halo;
-		if (wrap) {
-			yy %= (int32_t)h;
-			if (yy < 0)
-				yy += (int32_t)h;
-		} else if (yy < 0 || yy >= (int32_t)h)
+		if (wrap)
+			yy = cf_floor_mod(yy, h);
+		else if (yy < 0 || yy >= (int32_t)h)
 			continue;
 		tile[i*64u + lane] = active ? base[(size_t)yy*w + x] : (uint8_t)0;
 	}

@@ -390,39 +390,3 @@ __device__ __forceinline__ unsigned long long cf_wave_min_u64(unsigned long long
 	const unsigned long long a = r[0] < r[1] ? r[0] : r[1], b = r[2] < r[3] ? r[2] : r[3];
 	return a < b ? a : b;
 }
-
-// Color.h's sRGBToLinear / linearToSRGB (:224-242), in double as the reference computes them; shared by the
-// mip-chain resize (mipgen.hip) and the per-image ops (image_ops.hip)
-__device__ __forceinline__ double srgb_to_linear(double c)
-{
-	if (c <= 0.04045)
-		return c/12.92;
-	return pow((c + 0.055)/1.055, 2.4);
-}
-
-__device__ __forceinline__ double linear_to_srgb(double c)
-{
-	if (c <= 0.0031308)
-		return c*12.92;
-	return 1.055*pow(c, 1.0/2.4) - 0.055;
-}
-
-// source texel as the reference's RGBAF storage holds it (SRC_PIX: 0 RGBA8, 1 RGBA32F, 2 RGBA16F)
-template <int SRC_PIX>
-__device__ __forceinline__ float4 load_rgbaf(const uint8_t* row, uint32_t x)
-{
-	if (SRC_PIX == 0) {
-		const uint32_t p = *reinterpret_cast<const uint32_t*>(row + (size_t)x*4u);
-		// Image::convert RGBA8 -> RGBAF: toDoubleNorm (v/255.0, Image.cpp:293-296), float store
-		return make_float4((float)((double)(p & 255u)/255.0), (float)((double)((p >> 8) & 255u)/255.0),
-			(float)((double)((p >> 16) & 255u)/255.0), (float)((double)(p >> 24)/255.0));
-	} else if (SRC_PIX == 1) {
-		return *reinterpret_cast<const float4*>(row + (size_t)x*16u);
-	} else {
-		const uint2 h = *reinterpret_cast<const uint2*>(row + (size_t)x*8u);
-		union { unsigned short u; _Float16 f; } c0, c1, c2, c3;
-		c0.u = (unsigned short)(h.x & 0xFFFFu); c1.u = (unsigned short)(h.x >> 16);
-		c2.u = (unsigned short)(h.y & 0xFFFFu); c3.u = (unsigned short)(h.y >> 16);
-		return make_float4((float)c0.f, (float)c1.f, (float)c2.f, (float)c3.f);
-	}
-}

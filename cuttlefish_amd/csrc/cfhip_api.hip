@@ -6,6 +6,7 @@
 // payload.  There is deliberately no CPU fallback here: without a HIP device
 // cfhip_create() fails and the caller (HipConverter) keeps the reference path.
 #include "cf_device.h"
+#include "cf_texel.h"
 #include "astc_tables.h"
 #include "pvrtc_surf.h"
 #include "compare_batch.h"
@@ -404,12 +405,7 @@ bool format_implemented(int format, int type)
 
 size_t pixel_bytes(int pixel_type)
 {
-	switch (pixel_type) {
-		case CFHIP_PIXEL_RGBA8: return 4;
-		case CFHIP_PIXEL_RGBA32F: return 16;
-		case CFHIP_PIXEL_RGBA16F: return 8;
-		default: return 0;
-	}
+	return pixel_type >= CFHIP_PIXEL_RGBA8 && pixel_type <= CFHIP_PIXEL_RGBA16F ? cf_pixel_size(pixel_type) : 0;   // 0: no such type
 }
 
 int check_params(cfhip_ctx* ctx, const cfhip_params* p)

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cf_texel.h"
 #include "compare_batch.h"
 #include "decode_blocks.h"
 #include "std_unpack.h"
@@ -51,9 +52,7 @@ struct cmp_args {
 
 __device__ __forceinline__ double half_to_double(uint32_t h)
 {
-	union { unsigned short u; _Float16 f; } c;
-	c.u = (unsigned short)(h & 0xFFFFu);
-	return (double)(float)c.f;
+	return (double)cf_half_to_float(h & 0xFFFFu);
 }
 
 __device__ __forceinline__ double snorm_div(int v, double d)

@@ -15,7 +15,7 @@
 //              one record per row
 //   sh9 final  the rows added in (face, y) order, one value per lane, and the normalisation
 // No kernel here may use scratch, spill a vector register or use AGPRs (cuttlefish_amd/build.py).
-#include "cf_device.h"
+#include "cf_texel.h"
 #include "envmap.h"
 
 namespace {
@@ -107,29 +107,22 @@ __device__ __forceinline__ double butterfly(double p)
 }
 
 // ---- part 1 -------------------------------------------------------------------------------------------------------------
+// component by component: the panorama is the caller's memory, at any alignment its components allow
 __device__ __forceinline__ void panorama_texel(const uint8_t* row, uint32_t x, int32_t type, const float* of_u8, double out[4])
 {
-	if (type == CFHIP_PIXEL_RGBA8) {
-		const uint8_t* v = row + (size_t)x*4u;             // any alignment
-		out[0] = (double)of_u8[v[0]]; out[1] = (double)of_u8[v[1]]; out[2] = (double)of_u8[v[2]]; out[3] = (double)of_u8[v[3]];
-	} else if (type == CFHIP_PIXEL_RGBA32F) {
-		const float* v = reinterpret_cast<const float*>(row + (size_t)x*16u);
-		out[0] = (double)v[0]; out[1] = (double)v[1]; out[2] = (double)v[2]; out[3] = (double)v[3];
-	} else {
-		const _Float16* v = reinterpret_cast<const _Float16*>(row + (size_t)x*8u);
-		out[0] = (double)(float)v[0]; out[1] = (double)(float)v[1]; out[2] = (double)(float)v[2]; out[3] = (double)(float)v[3];
-	}
+	cf_pixel_dispatch(type, [&](auto pix) {
+		const float4 v = cf_load_texel<decltype(pix)::value, false>(row, x, of_u8);
+		out[0] = (double)v.x; out[1] = (double)v.y; out[2] = (double)v.z; out[3] = (double)v.w;
+	});
 }
 
 __global__ void __launch_bounds__(WG)
 cfhip_equirect_to_cube_kernel(const uint8_t* __restrict__ src, int32_t type, uint32_t W, uint32_t H, unsigned long long pitch,
 	void* const* __restrict__ faces, uint32_t n, uint32_t q)
 {
-	// an 8-bit component has 256 values: (float)(v / 255.0) once per workgroup
 	__shared__ float of_u8[256];
 	const uint32_t v = threadIdx.y*CFENV_WG_X + threadIdx.x;
-	if (type == CFHIP_PIXEL_RGBA8)
-		of_u8[v] = (float)((double)v/255.0);
+	cf_fill_of_u8(of_u8, v, type == CFHIP_PIXEL_RGBA8);
 	__syncthreads();
 	const uint32_t x = blockIdx.x*CFENV_WG_X + threadIdx.x, y = blockIdx.y*CFENV_WG_Y + threadIdx.y, f = blockIdx.z;
 	if (x >= n || y >= n)

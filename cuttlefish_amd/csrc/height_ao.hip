@@ -16,7 +16,7 @@
 //          min per workgroup.
 // All layers of a call share both launches (grid z).  No kernel here may use scratch, spill a vector register or use
 // AGPRs (cuttlefish_amd/build.py).
-#include "cf_device.h"
+#include "cf_texel.h"
 #include "height_ao.h"
 
 namespace {
@@ -25,19 +25,12 @@ constexpr uint32_t ONE_BITS = 0x3F800000u;         // 1.0f: v never exceeds it, 
 constexpr uint32_t PLANE_ROWS = CFHAO_WG/CFHAO_TILE_W;
 constexpr uint32_t OWN = CFHAO_OWN_ROWS;           // rows of a tile a wavefront owns: wave, wave + WAVES, ...
 
-__device__ __forceinline__ uint32_t pixel_size(int32_t type)
-{
-	return type == CFHIP_PIXEL_RGBA8 ? 4u : type == CFHIP_PIXEL_RGBA32F ? 16u : 8u;
-}
-
 __global__ void __launch_bounds__(CFHAO_WG)
 cfhip_height_ao_plane_kernel(cfhao_call c, float* __restrict__ plane, cfhip_height_ao_result* __restrict__ results)
 {
-	// an 8-bit height has 256 values: (float)(v / 255.0) once per workgroup
 	__shared__ float of_u8[256];
 	const uint32_t v = threadIdx.y*CFHAO_TILE_W + threadIdx.x, layer = blockIdx.z;
-	if (c.src_type == CFHIP_PIXEL_RGBA8)
-		of_u8[v] = (float)((double)v/255.0);
+	cf_fill_of_u8(of_u8, v, c.src_type == CFHIP_PIXEL_RGBA8);
 	__syncthreads();
 	if (results && v == 0 && blockIdx.x + blockIdx.y == 0) {
 		cfhip_height_ao_result open;
@@ -50,56 +43,17 @@ cfhip_height_ao_plane_kernel(cfhao_call c, float* __restrict__ plane, cfhip_heig
 	if (x >= c.width || y >= c.height)
 		return;
 	const uint8_t* row = static_cast<const uint8_t*>(c.src[layer]) + (size_t)y*c.src_pitch;
+	// (the ladder is written out: through a run-time helper it is lowered as a switch, two more scalar branches for RGBA8)
 	float a;
 	if (c.src_type == CFHIP_PIXEL_RGBA8)
-		a = of_u8[row[(size_t)x*4u + c.channel]];
+		a = cf_load_channel<CFHIP_PIXEL_RGBA8>(row, x, c.channel, of_u8);
 	else if (c.src_type == CFHIP_PIXEL_RGBA32F)
-		a = *reinterpret_cast<const float*>(row + (size_t)x*16u + c.channel*4u);
-	else {
-		union { unsigned short u; _Float16 f; } cv;
-		cv.u = *reinterpret_cast<const unsigned short*>(row + (size_t)x*8u + c.channel*2u);
-		a = (float)cv.f;
-	}
+		a = cf_load_channel<CFHIP_PIXEL_RGBA32F>(row, x, c.channel, of_u8);
+	else
+		a = cf_load_channel<CFHIP_PIXEL_RGBA16F>(row, x, c.channel, of_u8);
 	if (!__builtin_isfinite(a))
 		a = 0.0f;
 	plane[((size_t)layer*c.height + y)*c.width + x] = a;
-}
-
-// v in the components of the mask
-__device__ __forceinline__ void store_value(const cfhao_call& c, uint32_t layer, uint32_t x, uint32_t y, double v)
-{
-	uint8_t* p = static_cast<uint8_t*>(c.dst[layer]) + (size_t)y*c.dst_pitch + (size_t)x*pixel_size(c.dst_type);
-	if (c.dst_type == CFHIP_PIXEL_RGBA8) {
-		const uint8_t q = (uint8_t)floor(v*255.0 + 0.5);
-#pragma unroll
-		for (uint32_t ch = 0; ch < 4; ++ch)
-			if (c.channel_mask >> ch & 1u)
-				p[ch] = q;
-	} else if (c.dst_type == CFHIP_PIXEL_RGBA32F) {
-		const float q = (float)v;
-#pragma unroll
-		for (uint32_t ch = 0; ch < 4; ++ch)
-			if (c.channel_mask >> ch & 1u)
-				reinterpret_cast<float*>(p)[ch] = q;
-	} else {
-		union { unsigned short u; _Float16 f; } cv;
-		cv.f = (_Float16)(float)v;                     // nearest-even
-#pragma unroll
-		for (uint32_t ch = 0; ch < 4; ++ch)
-			if (c.channel_mask >> ch & 1u)
-				reinterpret_cast<unsigned short*>(p)[ch] = cv.u;
-	}
-}
-
-// a coordinate of the staged tile on the surface: modulo the side on a wrapped axis; false where there is no texel
-__device__ __forceinline__ bool surface_coord(int32_t& at, uint32_t side, bool wrap)
-{
-	if (!wrap)
-		return at >= 0 && at < (int32_t)side;
-	at %= (int32_t)side;
-	if (at < 0)
-		at += (int32_t)side;
-	return true;
 }
 
 // HALO: the largest radius of the build; WAVES: the wavefronts of its workgroup, four rows of the tile each.  Together
@@ -127,10 +81,10 @@ cfhip_height_ao_scan_kernel(cfhao_call c, const float* __restrict__ plane, cfhip
 	// LDS texel (i, j) is the surface's (x0 - R + i, y0 - R + j): CFHAO_TILE_W + 2R columns of count + 2R rows
 	for (uint32_t j = wave; j < count + 2u*R; j += WAVES) {
 		int32_t yy = (int32_t)(y0 + j) - (int32_t)R;
-		const bool row = surface_coord(yy, h, wrap_y);
+		const bool row = cf_wrap_coord(yy, h, wrap_y);
 		for (uint32_t i = lane; i < CFHAO_TILE_W + 2u*R; i += 64u) {
 			int32_t xx = (int32_t)(x0 + i) - (int32_t)R;
-			const bool there = surface_coord(xx, w, wrap_x) && row;
+			const bool there = cf_wrap_coord(xx, w, wrap_x) && row;
 			tile[j*P + i] = there ? base[(size_t)yy*w + (size_t)xx] : __builtin_nanf("");
 		}
 	}
@@ -181,7 +135,7 @@ cfhip_height_ao_scan_kernel(cfhao_call c, const float* __restrict__ plane, cfhip
 		const bool active = x < w && j < count;
 		const double v = fmin(1.0, fmax(0.0, 1.0 - strength*(1.0 - S[r])));
 		if (active) {
-			store_value(c, layer, x, y0 + j, v);
+			cf_store_unit(static_cast<uint8_t*>(c.dst[layer]) + (size_t)(y0 + j)*c.dst_pitch, x, c.dst_type, c.channel_mask, v);
 			dark = min(dark, __float_as_uint((float)v));
 		}
 		n += (uint32_t)__popcll(__ballot(active && occluded[r]));

@@ -14,8 +14,7 @@
 // premultiply -- and stores each as one float4 at its flipped position: a mirrored row is still one
 // contiguous run of 512 B, written in reversed lane order.
 // No kernel here may use scratch, spill a vector register or use AGPRs (cuttlefish_amd/build.py).
-#include "cf_device.h"
-#include "../../include/cuttlefish_hip.h"
+#include "cf_texel.h"
 
 namespace {
 
@@ -43,10 +42,8 @@ __device__ __forceinline__ uint32_t fold(int v, uint32_t n, bool wrap)
 {
 	if (v >= 0 && (uint32_t)v < n)
 		return (uint32_t)v;
-	if (wrap) {
-		const int m = v % (int)n;
-		return (uint32_t)(m < 0 ? m + (int)n : m);
-	}
+	if (wrap)
+		return (uint32_t)cf_floor_mod(v, n);
 	return v < 0 ? 0u : n - 1u;
 }
 
@@ -71,10 +68,11 @@ cfhip_image_ops_kernel(const image_ops_args a)
 	const bool rgbf = a.rgbf || normal;
 	// An 8-bit source has 256 possible sRGB values: their linear values are computed once per workgroup (the
 	// same function on the same input as the per-texel call).  Only for the first op that linearises the
-	// unmodified value, and kept in double: grayscale uses the linear value without a float store between.
+	// unmodified value, and kept in double: grayscale uses the linear value without a float store between -- which is
+	// why the texel below is not cf_load_linear's: that one reads a float table and rounds where the mip chain stores.
 	const bool lut = SRC_PIX == 0 && (change ? !a.dst_srgb : (gray && srgb));
 	if (lut) {
-		lin_of_u8[threadIdx.x] = srgb_to_linear((double)(float)((double)threadIdx.x/255.0));
+		lin_of_u8[threadIdx.x] = cf_linear_of_u8(threadIdx.x);
 		__syncthreads();
 	}
 
@@ -227,11 +225,8 @@ extern "C" hipError_t cfhip_launch_image_ops(const void* src, int src_pixel_type
 	for (int c = 0; c < 4; ++c)
 		a.swz[c] = o->swizzle[c];
 	const dim3 grid((a.rw + IT - 1u)/IT, (a.rh + IT - 1u)/IT, 1), block(256, 1, 1);
-	if (src_pixel_type == CFHIP_PIXEL_RGBA8)
-		hipLaunchKernelGGL(cfhip_image_ops_kernel<0>, grid, block, 0, stream, a);
-	else if (src_pixel_type == CFHIP_PIXEL_RGBA32F)
-		hipLaunchKernelGGL(cfhip_image_ops_kernel<1>, grid, block, 0, stream, a);
-	else
-		hipLaunchKernelGGL(cfhip_image_ops_kernel<2>, grid, block, 0, stream, a);
+	cf_pixel_dispatch(src_pixel_type, [&](auto pix) {
+		hipLaunchKernelGGL(cfhip_image_ops_kernel<decltype(pix)::value>, grid, block, 0, stream, a);
+	});
 	return hipGetLastError();
 }

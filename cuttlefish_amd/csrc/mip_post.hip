@@ -14,7 +14,7 @@
 //           vector atomic add per wavefront (lane j adds candidate j's count: 64 contiguous bytes)
 //   apply   alpha scale and renormalisation fused, in place
 // No kernel here may use scratch, spill a vector register or use AGPRs (cuttlefish_amd/build.py).
-#include "cf_device.h"
+#include "cf_texel.h"
 #include "mip_post.h"
 
 namespace {
@@ -46,34 +46,17 @@ __device__ __forceinline__ void load_alpha_raw(const cfmp_surf& s, uint32_t base
 			x = idx - y*s.width;
 		}
 		const uint8_t* row = s.pixels + (size_t)y*s.pitch;
-		if (PIX == CFHIP_PIXEL_RGBA8)
-			raw[i] = row[(size_t)x*4u + 3u];
-		else if (PIX == CFHIP_PIXEL_RGBA32F)
-			raw[i] = *reinterpret_cast<const uint32_t*>(row + (size_t)x*16u + 12u);
-		else
-			raw[i] = *reinterpret_cast<const unsigned short*>(row + (size_t)x*8u + 6u);
+		raw[i] = cf_channel_raw<PIX>(row, x, 3u);
 	}
 }
 
 template <int PIX>
-__device__ __forceinline__ void load_alpha_raw(const cfmp_surf& s, uint32_t base, uint32_t texel, uint32_t (&raw)[CFMP_PER_THREAD])
+__device__ __forceinline__ void load_alpha_raw(const cfmp_surf& s, uint32_t base, uint32_t (&raw)[CFMP_PER_THREAD])
 {
-	if (s.pitch == (unsigned long long)s.width*texel)
+	if (s.pitch == (unsigned long long)s.width*cf_pixel_size(PIX))
 		load_alpha_raw<PIX, true>(s, base, raw);
 	else
 		load_alpha_raw<PIX, false>(s, base, raw);
-}
-
-// ... as the reference's RGBAF storage holds it (cf_device.h: load_rgbaf)
-__device__ __forceinline__ float alpha_of_raw(int pixel_type, uint32_t raw, const float* of_u8)
-{
-	if (pixel_type == CFHIP_PIXEL_RGBA8)
-		return of_u8[raw];
-	if (pixel_type == CFHIP_PIXEL_RGBA32F)
-		return __uint_as_float(raw);
-	union { unsigned short u; _Float16 f; } c;
-	c.u = (unsigned short)raw;
-	return (float)c.f;
 }
 
 // lane j of the wavefront adds cnt[j]: one atomic instruction per wavefront
@@ -93,30 +76,30 @@ __global__ void __launch_bounds__(CFMP_WG)
 cfhip_mip_post_gather_kernel(const cfmp_surf* __restrict__ tab, uint32_t nsurf, uint32_t nlev, float t, float s0, float s1,
 	float s2, uint32_t ncand, uint32_t cstride, float* __restrict__ plane, uint32_t* __restrict__ counters)
 {
-	// an 8-bit alpha has 256 values: (float)(v / 255.0) once per workgroup, the same function on the same input
 	__shared__ float of_u8[256];
 	const uint32_t si = resolve(tab, nsurf, blockIdx.x);
 	const cfmp_surf s = tab[si];
 	if (s.pixel_type == CFHIP_PIXEL_RGBA8) {
-		of_u8[threadIdx.x] = (float)((double)threadIdx.x/255.0);
+		cf_fill_of_u8(of_u8, threadIdx.x, true);
 		__syncthreads();
 	}
 	const uint32_t base = (blockIdx.x - s.wg_begin)*CFMP_CHUNK + threadIdx.x;
 	const bool keep = plane && si < nlev;
 	uint32_t raw[CFMP_PER_THREAD];
+	// (not cf_pixel_dispatch: through a lambda the compiler merges the six bodies' loads into fewer, address-selected ones)
 	if (s.pixel_type == CFHIP_PIXEL_RGBA8)
-		load_alpha_raw<CFHIP_PIXEL_RGBA8>(s, base, 4u, raw);
+		load_alpha_raw<CFHIP_PIXEL_RGBA8>(s, base, raw);
 	else if (s.pixel_type == CFHIP_PIXEL_RGBA32F)
-		load_alpha_raw<CFHIP_PIXEL_RGBA32F>(s, base, 16u, raw);
+		load_alpha_raw<CFHIP_PIXEL_RGBA32F>(s, base, raw);
 	else
-		load_alpha_raw<CFHIP_PIXEL_RGBA16F>(s, base, 8u, raw);
+		load_alpha_raw<CFHIP_PIXEL_RGBA16F>(s, base, raw);
 	uint32_t cnt[3] = {0, 0, 0};
 #pragma unroll
 	for (uint32_t i = 0; i < CFMP_PER_THREAD; ++i) {
 		const uint32_t idx = base + i*CFMP_WG;
 		float a = __builtin_nanf("");              // a texel past the end never counts
 		if (idx < s.n) {
-			a = alpha_of_raw(s.pixel_type, raw[i], of_u8);
+			a = cf_channel_of_raw(s.pixel_type, raw[i], of_u8);
 			if (keep)
 				plane[s.plane_off + idx] = a;
 		}

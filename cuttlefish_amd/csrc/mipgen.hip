@@ -11,7 +11,7 @@
 // HBM-bound by construction (16 B written per texel, 4 x 4..16 B read), the opposite corner
 // of the roofline from the encoders; it exists so that a mip chain can be produced next to
 // the encoder's input without a host round trip.
-#include "cf_device.h"
+#include "cf_texel.h"
 
 namespace {
 
@@ -25,7 +25,7 @@ cfhip_mip_resize_kernel(const uint8_t* __restrict__ src, size_t pitch, uint32_t 
 	// once per texel read -- 12 of the 15 pow() of a 2x2 box footprint
 	__shared__ float lin_of_u8[SRC_PIX == 0 ? 256 : 1];
 	if (SRC_PIX == 0 && srgb) {
-		lin_of_u8[threadIdx.x] = (float)srgb_to_linear((double)(float)((double)threadIdx.x/255.0));
+		lin_of_u8[threadIdx.x] = (float)cf_linear_of_u8(threadIdx.x);
 		__syncthreads();
 	}
 	const uint32_t x = blockIdx.x*64u + (threadIdx.x & 63u);
@@ -74,19 +74,7 @@ cfhip_mip_resize_kernel(const uint8_t* __restrict__ src, size_t pitch, uint32_t 
 				if (scaleX == 0.0)
 					continue;
 			}
-			float4 p;
-			if (SRC_PIX == 0 && srgb) {
-				const uint32_t u = *reinterpret_cast<const uint32_t*>(row + (size_t)j*4u);
-				p = make_float4(lin_of_u8[u & 255u], lin_of_u8[(u >> 8) & 255u], lin_of_u8[(u >> 16) & 255u],
-					(float)((double)(u >> 24)/255.0));
-			} else {
-				p = load_rgbaf<SRC_PIX>(row, j);
-				if (srgb) {   // the linear copy of the source level is an RGBAF image: float store
-					p.x = (float)srgb_to_linear((double)p.x);
-					p.y = (float)srgb_to_linear((double)p.y);
-					p.z = (float)srgb_to_linear((double)p.z);
-				}
-			}
+			const float4 p = cf_load_linear<SRC_PIX>(row, j, srgb, lin_of_u8);
 			if (filter == 0) {
 				c0 += (double)p.x; c1 += (double)p.y; c2 += (double)p.z; c3 += (double)p.w;
 				total += 1.0;   // the reference counts texels in an unsigned: exact either way
@@ -163,7 +151,7 @@ cfhip_mip_pass_kernel(const uint8_t* src_base, size_t pitch, uint32_t src_n, flo
 		: reinterpret_cast<float4*>(reinterpret_cast<uint8_t*>(dst_base) + (size_t)blockIdx.z*L.dst_zstride);
 	__shared__ float lin_of_u8[SRC_PIX == 0 ? 256 : 1];   // see cfhip_mip_resize_kernel
 	if (SRC_PIX == 0 && to_linear) {
-		lin_of_u8[threadIdx.x] = (float)srgb_to_linear((double)(float)((double)threadIdx.x/255.0));
+		lin_of_u8[threadIdx.x] = (float)cf_linear_of_u8(threadIdx.x);
 		__syncthreads();
 	}
 	const uint32_t x = blockIdx.x*64u + (threadIdx.x & 63u);
@@ -191,21 +179,8 @@ cfhip_mip_pass_kernel(const uint8_t* src_base, size_t pitch, uint32_t src_n, flo
 		double w = fscale*fi_filter(filter, fscale*((double)i + 0.5 - center));
 		if (total > 0.0 && total != 1.0)
 			w /= total;
-		float4 p;
-		if (SRC_PIX == 0 && to_linear) {
-			const uint8_t* rowp = ALONG_X ? src + (size_t)y*pitch : src + (size_t)i*pitch;
-			const uint32_t v = *reinterpret_cast<const uint32_t*>(rowp + (size_t)(ALONG_X ? (uint32_t)i : x)*4u);
-			p = make_float4(lin_of_u8[v & 255u], lin_of_u8[(v >> 8) & 255u], lin_of_u8[(v >> 16) & 255u],
-				(float)((double)(v >> 24)/255.0));
-		} else {
-			p = ALONG_X ? load_rgbaf<SRC_PIX>(src + (size_t)y*pitch, (uint32_t)i)
-				: load_rgbaf<SRC_PIX>(src + (size_t)i*pitch, x);
-			if (to_linear) {
-				p.x = (float)srgb_to_linear((double)p.x);
-				p.y = (float)srgb_to_linear((double)p.y);
-				p.z = (float)srgb_to_linear((double)p.z);
-			}
-		}
+		const float4 p = ALONG_X ? cf_load_linear<SRC_PIX>(src + (size_t)y*pitch, (uint32_t)i, to_linear, lin_of_u8)
+			: cf_load_linear<SRC_PIX>(src + (size_t)i*pitch, x, to_linear, lin_of_u8);
 		c0 += w*(double)p.x; c1 += w*(double)p.y; c2 += w*(double)p.z; c3 += w*(double)p.w;
 	}
 	float4 o = make_float4((float)c0, (float)c1, (float)c2, (float)c3);
@@ -266,7 +241,7 @@ cfhip_mip_fused_kernel(const uint8_t* src_base, size_t pitch, uint32_t sw, uint3
 		: reinterpret_cast<float4*>(reinterpret_cast<uint8_t*>(dst_base) + (size_t)blockIdx.z*L.dst_zstride);
 	__shared__ float lin_of_u8[SRC_PIX == 0 ? 256 : 1];   // see cfhip_mip_resize_kernel
 	if (SRC_PIX == 0 && srgb) {
-		lin_of_u8[threadIdx.x] = (float)srgb_to_linear((double)(float)((double)threadIdx.x/255.0));
+		lin_of_u8[threadIdx.x] = (float)cf_linear_of_u8(threadIdx.x);
 		__syncthreads();
 	}
 	const uint32_t x = blockIdx.x*64u + (threadIdx.x & 63u);
@@ -275,21 +250,7 @@ cfhip_mip_fused_kernel(const uint8_t* src_base, size_t pitch, uint32_t sw, uint3
 		return;
 	const AxisTaps tx = axis_taps(x, sw, dw, filter), ty = axis_taps(y, sh, dh, filter);
 	auto texel = [&](int sx, int sy) -> float4 {
-		float4 p;
-		const uint8_t* rowp = src + (size_t)sy*pitch;
-		if (SRC_PIX == 0 && srgb) {
-			const uint32_t v = *reinterpret_cast<const uint32_t*>(rowp + (size_t)sx*4u);
-			p = make_float4(lin_of_u8[v & 255u], lin_of_u8[(v >> 8) & 255u], lin_of_u8[(v >> 16) & 255u],
-				(float)((double)(v >> 24)/255.0));
-		} else {
-			p = load_rgbaf<SRC_PIX>(rowp, (uint32_t)sx);
-			if (srgb) {
-				p.x = (float)srgb_to_linear((double)p.x);
-				p.y = (float)srgb_to_linear((double)p.y);
-				p.z = (float)srgb_to_linear((double)p.z);
-			}
-		}
-		return p;
+		return cf_load_linear<SRC_PIX>(src + (size_t)sy*pitch, (uint32_t)sx, srgb, lin_of_u8);
 	};
 	double o0 = 0, o1 = 0, o2 = 0, o3 = 0;
 	// outer = the SECOND pass's axis, inner = the first pass's: the inner sum is the float the first pass stored
@@ -393,14 +354,11 @@ extern "C" hipError_t cfhip_launch_mip_pass_layers(const void* src, int src_pixe
 	const uint8_t* s = static_cast<const uint8_t*>(src);
 	float4* d = static_cast<float4*>(dst);
 	const MipLayers L = {src_tab, dst_tab, src_zstride, dst_zstride};
-#define CF_PASS(P, AX) hipLaunchKernelGGL((cfhip_mip_pass_kernel<P, AX>), grid, block, 0, stream, s, pitch, \
-	src_n, d, dst_w, dst_h, filter, to_linear, to_srgb, L)
-	if (along_x) {
-		if (src_pixel_type == 0) CF_PASS(0, true); else if (src_pixel_type == 1) CF_PASS(1, true); else CF_PASS(2, true);
-	} else {
-		if (src_pixel_type == 0) CF_PASS(0, false); else if (src_pixel_type == 1) CF_PASS(1, false); else CF_PASS(2, false);
-	}
-#undef CF_PASS
+	cf_pixel_dispatch(src_pixel_type, [&](auto pix) {
+		constexpr int P = decltype(pix)::value;
+		auto kernel = along_x ? cfhip_mip_pass_kernel<P, true> : cfhip_mip_pass_kernel<P, false>;
+		hipLaunchKernelGGL(kernel, grid, block, 0, stream, s, pitch, src_n, d, dst_w, dst_h, filter, to_linear, to_srgb, L);
+	});
 	return hipGetLastError();
 }
 
@@ -421,14 +379,11 @@ extern "C" hipError_t cfhip_launch_mip_fused_layers(const void* src, int src_pix
 	const uint8_t* s = static_cast<const uint8_t*>(src);
 	float4* d = static_cast<float4*>(dst);
 	const MipLayers L = {src_tab, dst_tab, src_zstride, dst_zstride};
-#define CF_FUSED(P, XF) hipLaunchKernelGGL((cfhip_mip_fused_kernel<P, XF>), grid, block, 0, stream, s, pitch, sw, sh, \
-	d, dw, dh, filter, srgb, L)
-	if (x_first) {
-		if (src_pixel_type == 0) CF_FUSED(0, true); else if (src_pixel_type == 1) CF_FUSED(1, true); else CF_FUSED(2, true);
-	} else {
-		if (src_pixel_type == 0) CF_FUSED(0, false); else if (src_pixel_type == 1) CF_FUSED(1, false); else CF_FUSED(2, false);
-	}
-#undef CF_FUSED
+	cf_pixel_dispatch(src_pixel_type, [&](auto pix) {
+		constexpr int P = decltype(pix)::value;
+		auto kernel = x_first ? cfhip_mip_fused_kernel<P, true> : cfhip_mip_fused_kernel<P, false>;
+		hipLaunchKernelGGL(kernel, grid, block, 0, stream, s, pitch, sw, sh, d, dw, dh, filter, srgb, L);
+	});
 	return hipGetLastError();
 }
 
@@ -440,12 +395,10 @@ extern "C" hipError_t cfhip_launch_mip_resize(const void* src, int src_pixel_typ
 	const dim3 grid((dw + 63u)/64u, (dh + 3u)/4u, 1), block(256, 1, 1);
 	const uint8_t* s = static_cast<const uint8_t*>(src);
 	float4* d = static_cast<float4*>(dst);
-	if (src_pixel_type == 0)
-		hipLaunchKernelGGL((cfhip_mip_resize_kernel<0>), grid, block, 0, stream, s, pitch, sw, sh, d, dw, dh, filter, srgb);
-	else if (src_pixel_type == 1)
-		hipLaunchKernelGGL((cfhip_mip_resize_kernel<1>), grid, block, 0, stream, s, pitch, sw, sh, d, dw, dh, filter, srgb);
-	else
-		hipLaunchKernelGGL((cfhip_mip_resize_kernel<2>), grid, block, 0, stream, s, pitch, sw, sh, d, dw, dh, filter, srgb);
+	cf_pixel_dispatch(src_pixel_type, [&](auto pix) {
+		hipLaunchKernelGGL((cfhip_mip_resize_kernel<decltype(pix)::value>), grid, block, 0, stream, s, pitch, sw, sh, d, dw, dh,
+			filter, srgb);
+	});
 	return hipGetLastError();
 }
 

@@ -17,6 +17,7 @@
 //            where the encoder could not write it there
 //   final    the signature, IHDR, sRGB, the IDAT length, the IDAT CRC (the chunk type in front, the last len % 64 bytes
 //            behind), IEND and the result, by one lane in plain C++
+#include "cf_texel.h"
 #include "png.h"
 
 namespace {
@@ -36,12 +37,6 @@ __device__ __forceinline__ void png_load(const uint8_t* p, uint32_t w[4])
 		const uint4 v = *reinterpret_cast<const uint4*>(p);
 		w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
 	}
-}
-
-template <int PIX>
-__device__ __forceinline__ constexpr uint32_t png_texel_bytes()
-{
-	return PIX == CFPNG_PIX_RGBA8 ? 4u : PIX == CFPNG_PIX_RGBA16F ? 8u : 16u;
 }
 
 // a pixel's bytes from the lane before / from one given lane: only the words the pixel has
@@ -80,7 +75,7 @@ struct PngRow {
 	__device__ __forceinline__ uint64_t pixel(const uint8_t* row, uint32_t x) const
 	{
 		uint32_t w[4];
-		png_load<PIX>(row + (size_t)x*png_texel_bytes<PIX>(), w);
+		png_load<PIX>(row + (size_t)x*cf_pixel_size(PIX), w);
 		return cfpng_pixel<PIX, CH, D16>(w);
 	}
 

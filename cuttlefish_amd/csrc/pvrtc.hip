@@ -21,6 +21,7 @@
 // -ffp-contract=off (build.py); every value that reaches the payload is integer arithmetic.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "cf_texel.h"
 #include "pvrtc_surf.h"
 
 
@@ -164,15 +165,10 @@ __device__ __forceinline__ uint32_t load_texel(const cf_pvrtc_surf& s, uint32_t 
 	if (s.pix == 0)
 		return *reinterpret_cast<const uint32_t*>(row + (size_t)x*4u);
 	float4 f;
-	if (s.pix == 1) {
+	if (s.pix == 1)
 		f = *reinterpret_cast<const float4*>(row + (size_t)x*16u);
-	} else {
-		const uint2 hv = *reinterpret_cast<const uint2*>(row + (size_t)x*8u);
-		union { unsigned short u; _Float16 f; } c0, c1, c2, c3;
-		c0.u = (unsigned short)(hv.x & 0xFFFFu); c1.u = (unsigned short)(hv.x >> 16);
-		c2.u = (unsigned short)(hv.y & 0xFFFFu); c3.u = (unsigned short)(hv.y >> 16);
-		f = make_float4((float)c0.f, (float)c1.f, (float)c2.f, (float)c3.f);
-	}
+	else
+		f = cf_halves_to_float4(*reinterpret_cast<const uint2*>(row + (size_t)x*8u));
 	return unorm8(f.x) | unorm8(f.y) << 8 | unorm8(f.z) << 16 | unorm8(f.w) << 24;
 }
 

@@ -18,6 +18,7 @@
 // cfhip_rdo2d_kernel further down adds candidates from the block row above (tests/rdo2d_ref.py).
 #include "decode_blocks.h"
 #include "cf_device.h"
+#include "cf_texel.h"
 #include "rdo.h"
 
 namespace {

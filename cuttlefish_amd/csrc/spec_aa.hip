@@ -14,6 +14,7 @@
 // reach memory by one atomic add and one atomic max per workgroup.  Pixel types are template parameters, the storage
 // of the normals picks one of four bodies at the kernel's entry, and PERCEPTUAL is read once per thread, outside every
 // loop.  No kernel here may use scratch, spill a vector register or use AGPRs (cuttlefish_amd/build.py).
+#include "cf_texel.h"
 #include "spec_aa.h"
 
 namespace {
@@ -36,43 +37,14 @@ __device__ __forceinline__ void add(sums& s, const sums& t)
 	s.x += t.x; s.y += t.y; s.z += t.z; s.a += t.a;
 }
 
-// a component as the definition decodes it; of_u8: (float)(v / 255.0) of the 256 values, once per workgroup
-__device__ __forceinline__ double of_half(uint32_t bits)
-{
-	union { unsigned short u; _Float16 f; } c;
-	c.u = (unsigned short)bits;
-	return (double)c.f;
-}
-
+// the first three components as the definition decodes them (cf_texel.h), straight-line code
 template <int PIX>
 __device__ __forceinline__ void load_normal(const uint8_t* row, uint32_t x, const float* of_u8, double (&n)[3])
 {
-	if (PIX == CFHIP_PIXEL_RGBA8) {
-		const uint32_t v = *reinterpret_cast<const uint32_t*>(row + (size_t)x*4u);
-		n[0] = (double)of_u8[v & 255u];
-		n[1] = (double)of_u8[(v >> 8) & 255u];
-		n[2] = (double)of_u8[(v >> 16) & 255u];
-	} else if (PIX == CFHIP_PIXEL_RGBA32F) {
-		const float4 v = *reinterpret_cast<const float4*>(row + (size_t)x*16u);
-		n[0] = (double)v.x;
-		n[1] = (double)v.y;
-		n[2] = (double)v.z;
-	} else {
-		const uint2 v = *reinterpret_cast<const uint2*>(row + (size_t)x*8u);
-		n[0] = of_half(v.x & 0xFFFFu);
-		n[1] = of_half(v.x >> 16);
-		n[2] = of_half(v.y & 0xFFFFu);
-	}
-}
-
-template <int PIX>
-__device__ __forceinline__ double load_rough(const uint8_t* row, uint32_t x, uint32_t channel, const float* of_u8)
-{
-	if (PIX == CFHIP_PIXEL_RGBA8)
-		return (double)of_u8[row[(size_t)x*4u + channel]];
-	if (PIX == CFHIP_PIXEL_RGBA32F)
-		return (double)*reinterpret_cast<const float*>(row + (size_t)x*16u + channel*4u);
-	return of_half(*reinterpret_cast<const unsigned short*>(row + (size_t)x*8u + channel*2u));
+	const float4 v = cf_load_texel<PIX>(row, x, of_u8);
+	n[0] = (double)v.x;
+	n[1] = (double)v.y;
+	n[2] = (double)v.z;
 }
 
 __device__ __forceinline__ long long quantise_rough(double r, bool perceptual)
@@ -135,7 +107,7 @@ struct source {
 			load_normal<NPIX>(normals + (size_t)y*normal_pitch, x, of_u8, n);
 			q.a = qa_const;
 			if (RPIX != ROUGH_CONST)
-				q.a = quantise_rough(load_rough<RPIX>(rough + (size_t)y*rough_pitch, x, channel, of_u8), perceptual);
+				q.a = quantise_rough((double)cf_load_channel<RPIX>(rough + (size_t)y*rough_pitch, x, channel, of_u8), perceptual);
 			quantise_normal<SIGN, RECZ>(n, q);
 		}
 		return q;
@@ -360,10 +332,8 @@ cfhip_spec_aa_texel_kernel(cfsa_call c, cfsa_moments* __restrict__ out, cfhip_sp
 {
 	__shared__ long long lds[4][CFSA_LDS_ENTRIES];
 	__shared__ uint32_t rec[16];
-	// an 8-bit component has 256 values: (float)(v / 255.0) once per workgroup, the same function on the same input
 	__shared__ float of_u8[256];
-	if (NPIX == CFHIP_PIXEL_RGBA8 || RPIX == CFHIP_PIXEL_RGBA8)
-		of_u8[threadIdx.x] = (float)((double)threadIdx.x/255.0);
+	cf_fill_of_u8(of_u8, threadIdx.x, NPIX == CFHIP_PIXEL_RGBA8 || RPIX == CFHIP_PIXEL_RGBA8);
 	// the storage of the normals is chosen here, once: each of the four bodies is straight-line code per texel
 	const bool sign = c.flags & CFHIP_SPEC_AA_SIGNED_NORMALS, recz = c.flags & CFHIP_SPEC_AA_RECONSTRUCT_Z;
 	if (!sign && !recz)
@@ -385,20 +355,6 @@ cfhip_spec_aa_moment_kernel(cfsa_call c, uint32_t stage, const cfsa_moments* __r
 	stage_body<SRC_MOMENTS, ROUGH_CONST, false, false>(c, stage, in, out, results, lds, rec, nullptr);
 }
 
-template <int NPIX>
-void launch_texel(const cfsa_call& c, dim3 grid, cfsa_moments* out, cfhip_spec_aa_result* results, hipStream_t stream)
-{
-	const int rpix = c.rough0 ? c.rough_type : ROUGH_CONST;
-	if (rpix == ROUGH_CONST)
-		hipLaunchKernelGGL((cfhip_spec_aa_texel_kernel<NPIX, ROUGH_CONST>), grid, dim3(CFSA_WG), 0, stream, c, out, results);
-	else if (rpix == CFHIP_PIXEL_RGBA8)
-		hipLaunchKernelGGL((cfhip_spec_aa_texel_kernel<NPIX, CFHIP_PIXEL_RGBA8>), grid, dim3(CFSA_WG), 0, stream, c, out, results);
-	else if (rpix == CFHIP_PIXEL_RGBA32F)
-		hipLaunchKernelGGL((cfhip_spec_aa_texel_kernel<NPIX, CFHIP_PIXEL_RGBA32F>), grid, dim3(CFSA_WG), 0, stream, c, out, results);
-	else
-		hipLaunchKernelGGL((cfhip_spec_aa_texel_kernel<NPIX, CFHIP_PIXEL_RGBA16F>), grid, dim3(CFSA_WG), 0, stream, c, out, results);
-}
-
 } // namespace
 
 static_assert(sizeof(long long)*4u*CFSA_LDS_ENTRIES + 16u*4u == CFSA_LDS_BYTES, "the LDS DESIGN.md states");
@@ -410,11 +366,16 @@ extern "C" hipError_t cfhip_launch_spec_aa(const cfsa_call* call, uint32_t layer
 	const dim3 grid(level_dim(call->width, top)*level_dim(call->height, top), layers);
 	if (stage)
 		hipLaunchKernelGGL(cfhip_spec_aa_moment_kernel, grid, dim3(CFSA_WG), 0, stream, *call, stage, in, out, results);
-	else if (call->normal_type == CFHIP_PIXEL_RGBA8)
-		launch_texel<CFHIP_PIXEL_RGBA8>(*call, grid, out, results, stream);
-	else if (call->normal_type == CFHIP_PIXEL_RGBA32F)
-		launch_texel<CFHIP_PIXEL_RGBA32F>(*call, grid, out, results, stream);
 	else
-		launch_texel<CFHIP_PIXEL_RGBA16F>(*call, grid, out, results, stream);
+		cf_pixel_dispatch(call->normal_type, [&](auto npix) {
+			constexpr int NPIX = decltype(npix)::value;
+			if (!call->rough0)
+				hipLaunchKernelGGL((cfhip_spec_aa_texel_kernel<NPIX, ROUGH_CONST>), grid, dim3(CFSA_WG), 0, stream, *call, out, results);
+			else
+				cf_pixel_dispatch(call->rough_type, [&](auto rpix) {
+					hipLaunchKernelGGL((cfhip_spec_aa_texel_kernel<NPIX, decltype(rpix)::value>), grid, dim3(CFSA_WG), 0, stream, *call,
+						out, results);
+				});
+		});
 	return hipGetLastError();
 }

@@ -28,6 +28,7 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 #include "cf_device.h"
+#include "cf_texel.h"
 
 namespace {
 
@@ -133,13 +134,8 @@ __device__ __forceinline__ float4 load_texel(const uint8_t* p)
 		return *reinterpret_cast<const float4*>(p);
 #endif
 	}
-	if (SRC == 2) {
-		const uint2 h = *reinterpret_cast<const uint2*>(p);
-		union { unsigned short u; _Float16 f; } c0, c1, c2, c3;
-		c0.u = (unsigned short)(h.x & 0xFFFFu); c1.u = (unsigned short)(h.x >> 16);
-		c2.u = (unsigned short)(h.y & 0xFFFFu); c3.u = (unsigned short)(h.y >> 16);
-		return make_float4((float)c0.f, (float)c1.f, (float)c2.f, (float)c3.f);
-	}
+	if (SRC == 2)
+		return cf_halves_to_float4(*reinterpret_cast<const uint2*>(p));
 	const uint32_t v = *reinterpret_cast<const uint32_t*>(p);
 	return make_float4(unorm8_to_float(v & 255u), unorm8_to_float((v >> 8) & 255u),
 		unorm8_to_float((v >> 16) & 255u), unorm8_to_float(v >> 24));
