@@ -208,7 +208,8 @@ EXPORTS = ["cfhip_abi_version", "cfhip_device_count", "cfhip_create", "cfhip_des
            "cfhip_alpha_sdf_array_device", "cfhip_spec_aa_array_device",
            "cfhip_height_ao_array_device", "cfhip_height_ao_directions",
            "cfhip_equirect_to_cube_device", "cfhip_ggx_sample_table", "cfhip_cube_prefilter_device",
-           "cfhip_cube_sh9_device"]
+           "cfhip_cube_sh9_device",
+           "cfhip_lobe_sample_table", "cfhip_hammersley_table", "cfhip_brdf_lut_device", "cfhip_cube_irradiance_device"]
 
 
 class Layout(enum.IntEnum):
@@ -732,15 +733,21 @@ def cube_level_count(face_size: int) -> int:
     return int(face_size).bit_length()
 
 
+def _check_samples(samples) -> int:
+    """the records of a sample table: a multiple of 64 from 64 to 4096"""
+    if isinstance(samples, (bool, np.bool_)) or not isinstance(samples, (int, np.integer)) or samples % 64 \
+            or not ENV_MIN_SAMPLES <= samples <= ENV_MAX_SAMPLES:
+        raise ValueError("samples %r: a multiple of 64 from %d to %d" % (samples, ENV_MIN_SAMPLES, ENV_MAX_SAMPLES))
+    return int(samples)
+
+
 def ggx_sample_table(roughness: float, samples: int, face_size: int, source_levels: int) -> np.ndarray:
     """cfhip_ggx_sample_table -> (samples, 4) float32 records (lx, ly, lz, lod) for one destination level of
     cube_prefilter_device: `samples` Hammersley points (a multiple of 64 from 64 to 4096) through the GGX distribution
     of `roughness` (0 < roughness <= 1; 0 is a copy and has no table), the level of detail chosen per sample from its
     density for a source cube of face_size with source_levels levels.  Host only: no context, no device."""
     r = float(roughness)
-    if isinstance(samples, (bool, np.bool_)) or not isinstance(samples, (int, np.integer)) or samples % 64 \
-            or not ENV_MIN_SAMPLES <= samples <= ENV_MAX_SAMPLES:
-        raise ValueError("samples %r: a multiple of 64 from %d to %d" % (samples, ENV_MIN_SAMPLES, ENV_MAX_SAMPLES))
+    _check_samples(samples)
     if not (0.0 < r <= 1.0):
         raise ValueError("roughness %r outside (0, 1]: roughness 0 is a copy and has no table" % (roughness,))
     if not 1 <= int(face_size) <= ENV_MAX_FACE or not 1 <= int(source_levels) <= cube_level_count(face_size):
@@ -770,6 +777,50 @@ def sh9_irradiance(coeffs, directions) -> np.ndarray:
              SH_C2*(x*z), SH_C22*(x*x - y*y)]
     band = [np.pi] + [2.0*np.pi/3.0]*3 + [np.pi/4.0]*5
     return sum((band[b]*basis[b])[..., None]*k[b] for b in range(9))
+
+
+# ---- the other lobes, the BRDF lookup table, the irradiance cube (cfhip_lobe_sample_table, cfhip_hammersley_table,
+# cfhip_brdf_lut_device, cfhip_cube_irradiance_device) ----
+LOBE_GGX, LOBE_CHARLIE, LOBE_LAMBERT = 0, 1, 2      # enum CFHIP_LOBE_*
+ENV_MAX_LUT = 1024
+
+
+class HammersleySample(ctypes.Structure):
+    """cfhip_hammersley_sample: cos and sin of phi = 2 pi xi2, then xi1, of one Hammersley point"""
+    _fields_ = [("cos_phi", ctypes.c_float), ("sin_phi", ctypes.c_float), ("xi1", ctypes.c_float),
+                ("reserved", ctypes.c_float)]
+
+
+def lobe_sample_table(kind: int, roughness: float, samples: int, face_size: int, source_levels: int) -> np.ndarray:
+    """cfhip_lobe_sample_table -> (samples, 4) float32 records (lx, ly, lz, lod) for one destination level of
+    cube_prefilter_device, from the Hammersley points of ggx_sample_table.  kind LOBE_GGX: ggx_sample_table's records;
+    LOBE_CHARLIE: the sheen distribution of `roughness` (0 < roughness <= 1); LOBE_LAMBERT: uniform over the hemisphere
+    (roughness is not read) -- the prefilter weighs by lz, so the level is the irradiance over pi.  Host only."""
+    if isinstance(kind, (bool, np.bool_)) or kind not in (LOBE_GGX, LOBE_CHARLIE, LOBE_LAMBERT):
+        raise ValueError("kind %r: LOBE_GGX, LOBE_CHARLIE or LOBE_LAMBERT" % (kind,))
+    r = 1.0 if kind == LOBE_LAMBERT else float(roughness)
+    S = _check_samples(samples)
+    if not (0.0 < r <= 1.0):
+        raise ValueError("roughness %r outside (0, 1]: roughness 0 is a copy and has no table" % (roughness,))
+    if not 1 <= int(face_size) <= ENV_MAX_FACE or not 1 <= int(source_levels) <= cube_level_count(face_size):
+        raise ValueError("face_size %r with source_levels %r" % (face_size, source_levels))
+    out = np.empty((S, 4), np.float32)
+    rc = load_library().cfhip_lobe_sample_table(int(kind), r, S, int(face_size), int(source_levels),
+                                                out.ctypes.data_as(ctypes.POINTER(GgxSample)))
+    if rc != 0:
+        raise ValueError("cfhip_lobe_sample_table refused (%r, %r, %r, %r, %r)" % (kind, roughness, samples, face_size,
+                                                                                   source_levels))
+    return out
+
+
+def hammersley_table(samples: int) -> np.ndarray:
+    """cfhip_hammersley_table -> (samples, 4) float32 records (cos phi, sin phi, xi1, 0) of the Hammersley points every
+    sample table here is made from: what brdf_lut_device reads.  Host only: no context, no device."""
+    S = _check_samples(samples)
+    out = np.empty((S, 4), np.float32)
+    if load_library().cfhip_hammersley_table(S, out.ctypes.data_as(ctypes.POINTER(HammersleySample))) != 0:
+        raise ValueError("cfhip_hammersley_table refused %r" % (samples,))
+    return out
 
 
 RDO_NO_CAP = 0xFFFFFFFF         # max_sse_increase: no cap
@@ -923,6 +974,17 @@ def load_library(path: Optional[str] = None):
     L.cfhip_cube_sh9_device.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.c_uint32,
                                         ctypes.c_void_p, ctypes.c_void_p]
     L.cfhip_cube_sh9_device.restype = ctypes.c_int
+    L.cfhip_lobe_sample_table.argtypes = [ctypes.c_int, ctypes.c_float, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
+                                          ctypes.POINTER(GgxSample)]
+    L.cfhip_lobe_sample_table.restype = ctypes.c_int
+    L.cfhip_hammersley_table.argtypes = [ctypes.c_uint32, ctypes.POINTER(HammersleySample)]
+    L.cfhip_hammersley_table.restype = ctypes.c_int
+    L.cfhip_brdf_lut_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p,
+                                        ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+    L.cfhip_brdf_lut_device.restype = ctypes.c_int
+    L.cfhip_cube_irradiance_device.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                               ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p]
+    L.cfhip_cube_irradiance_device.restype = ctypes.c_int
     L.cfhip_generate_mips3d_device.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32,
         ctypes.c_size_t, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p),
@@ -1719,15 +1781,21 @@ class Context:
         """Host convenience: six (n, n, 4) float32 faces in CubeFace order -> one (6, n_k, n_k, 4) float32 array per entry
         of `roughness`, n_k = max(1, n >> k): the full Box chain of the faces is built on the device, then level k is the
         environment under a GGX lobe of roughness[k] from `samples` samples; a roughness of 0 copies the Box level."""
+        return self._cube_prefilter_tables(faces, len(roughness), lambda n, L: [
+            None if float(r) == 0.0 else ggx_sample_table(r, samples, n, L) for r in roughness])
+
+    def _cube_prefilter_tables(self, faces, K: int, make_tables):
+        """what cube_prefilter and cube_prefilter_lobe share: the Box chain of the faces on the device, then K levels from
+        make_tables(face size, source levels)"""
         import torch
         stack = np.ascontiguousarray(np.stack([np.asarray(f) for f in faces]), dtype=np.float32)
         if stack.ndim != 4 or stack.shape[0] != 6 or stack.shape[1] != stack.shape[2] or stack.shape[3] != 4:
             raise ValueError("expected six (n, n, 4) faces")
         n = stack.shape[1]
-        L, K = cube_level_count(n), len(roughness)
+        L = cube_level_count(n)
         if not 1 <= K <= L:
             raise ValueError("%d levels asked of a face of %d: 1 to %d" % (K, n, L))
-        tables = [None if float(r) == 0.0 else ggx_sample_table(r, samples, n, L) for r in roughness]
+        tables = make_tables(n, L)
         device = "cuda:%d" % self.device_id
         chain = [torch.from_numpy(stack).to(device)]
         chain += [torch.empty((6, max(1, n >> l), max(1, n >> l), 4), dtype=torch.float32, device=device) for l in range(1, L)]
@@ -1762,6 +1830,75 @@ class Context:
         self.cube_sh9_device([dev[f].data_ptr() for f in range(6)], n, res.data_ptr())
         rec = res.cpu().numpy()
         return rec[:36].reshape(9, 4).copy(), float(rec[36])
+
+    def cube_prefilter_lobe(self, faces: Sequence[np.ndarray], kind: int, roughness: Sequence, samples: int = 256):
+        """cube_prefilter with the tables of another lobe (lobe_sample_table): level k is the environment under the
+        lobe `kind` of roughness[k].  An entry of None copies the Box level, as a roughness of 0 does for LOBE_GGX and
+        LOBE_CHARLIE; LOBE_LAMBERT reads no roughness, so any other entry there is the uniform table.  The sheen
+        distribution peaks at grazing half vectors, whose reflections point below the horizon: of a Charlie table only
+        the share 2^-((2 a + 1) / (2 a)), a = roughness^2, carries weight (a third at roughness 1, one record in 512 at
+        0.25), and a level no record is left for is a ValueError, not a face of NaN."""
+        def make_tables(n, L):
+            tables = [None if r is None or (kind != LOBE_LAMBERT and float(r) == 0.0)
+                      else lobe_sample_table(kind, r, samples, n, L) for r in roughness]
+            for r, t in zip(roughness, tables):
+                if t is not None and not t[:, 2].any():
+                    raise ValueError("roughness %r leaves none of %d samples above the horizon: more samples, or a rougher "
+                                     "level" % (r, samples))
+            return tables
+        return self._cube_prefilter_tables(faces, len(roughness), make_tables)
+
+    def brdf_lut_device(self, dst: int, width: int, height: int, table: np.ndarray, sheen: bool = False, stream: int = 0):
+        """The BRDF lookup table of the split sum (cfhip_brdf_lut_device): dst is a device pointer to width x height (1
+        to 1024 each) tightly packed RGBA32F; texel (x, y) holds, for N.V = (x + 0.5) / width and roughness
+        (y + 0.5) / height, R and G = the scale and bias of F0 under GGX with the height-correlated Smith term, B = the
+        Charlie sheen lobe's directional albedo when `sheen` (else 0), A = 1.  table: the (S, 4) float32 records of
+        hammersley_table, S a multiple of 64 from 64 to 4096.  One launch; identical calls give identical bytes."""
+        t = np.ascontiguousarray(table, dtype=np.float32)
+        if t.ndim != 2 or t.shape[1] != 4:
+            raise ValueError("the table is (S, 4) float32: cos phi, sin phi, xi1, 0")
+        self._check(self._lib.cfhip_brdf_lut_device(self._h, _ptr(dst), width, height, ctypes.c_void_p(t.ctypes.data),
+                                                    t.shape[0], int(bool(sheen)), _stream(stream)))
+
+    def brdf_lut(self, width: int, height: int, samples: int = 1024, sheen: bool = False) -> np.ndarray:
+        """Host convenience: brdf_lut_device with hammersley_table(samples) -> the (height, width, 4) float32 table."""
+        import torch
+        w, h = int(width), int(height)
+        if not (1 <= w <= ENV_MAX_LUT and 1 <= h <= ENV_MAX_LUT):
+            raise ValueError("width and height %r x %r outside 1 to %d" % (width, height, ENV_MAX_LUT))
+        table = hammersley_table(samples)
+        out = torch.empty((h, w, 4), dtype=torch.float32, device="cuda:%d" % self.device_id)
+        self.brdf_lut_device(out.data_ptr(), w, h, table, sheen)
+        return out.cpu().numpy()
+
+    def cube_irradiance_device(self, sh9_result: int, faces: Sequence[int], face_size: int, over_pi: bool = False,
+                               stream: int = 0):
+        """The diffuse term as a cube (cfhip_cube_irradiance_device): sh9_result is the device pointer cube_sh9_device
+        wrote its record to -- no host round trip -- and faces are six device pointers in CubeFace order, each
+        face_size^2 tightly packed RGBA32F.  Every texel is sh9_irradiance at its direction, over pi with over_pi (what
+        a shader multiplies by the albedo).  One launch."""
+        if len(faces) != 6:
+            raise ValueError("faces must list the six faces in CubeFace order")
+        self._check(self._lib.cfhip_cube_irradiance_device(self._h, _ptr(sh9_result), _ptr_array(faces), face_size,
+                                                           int(bool(over_pi)), _stream(stream)))
+
+    def cube_irradiance(self, coeffs, face_size: int, over_pi: bool = False) -> np.ndarray:
+        """Host convenience: the (9, C) coefficients of cube_sh9 (C up to 4; missing channels are 0) through
+        cube_irradiance_device -> the (6, face_size, face_size, 4) float32 faces."""
+        import torch
+        k = np.asarray(coeffs, np.float64)
+        if k.ndim != 2 or k.shape[0] != 9 or not 1 <= k.shape[1] <= 4:
+            raise ValueError("expected coeffs (9, C), C from 1 to 4")
+        if not 1 <= int(face_size) <= ENV_MAX_FACE:
+            raise ValueError("face_size %r outside 1 to %d" % (face_size, ENV_MAX_FACE))
+        n = int(face_size)
+        rec = np.zeros(37, np.float64)
+        rec[:36].reshape(9, 4)[:, :k.shape[1]] = k
+        device = "cuda:%d" % self.device_id
+        res = torch.from_numpy(rec).to(device)
+        out = torch.empty((6, n, n, 4), dtype=torch.float32, device=device)
+        self.cube_irradiance_device(res.data_ptr(), [out[f].data_ptr() for f in range(6)], n, over_pi)
+        return out.cpu().numpy()
 
     def generate_mips3d_device(self, src: int, pixel_type, width: int, height: int, depth: int,
                                row_pitch_bytes: int, slice_pitch_bytes: int, dst_levels: Sequence[int],

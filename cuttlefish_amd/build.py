@@ -175,7 +175,9 @@ BLOCK_KERNELS = ("cfhip_bc7_encode_kernel", "cfhip_bc15_encode_kernel", "cfhip_b
                  "cfhip_height_ao_plane_kernel", "cfhip_height_ao_scan_kernel",
                  # environment maps (csrc/envmap.hip): panorama to cube, the GGX chain and its copy, the SH9 rows and sum
                  "cfhip_equirect_to_cube_kernel", "cfhip_cube_prefilter_kernel", "cfhip_cube_copy_kernel",
-                 "cfhip_cube_sh9_rows_kernel", "cfhip_cube_sh9_final_kernel")
+                 "cfhip_cube_sh9_rows_kernel", "cfhip_cube_sh9_final_kernel",
+                 # the BRDF lookup table (with and without the sheen column) and the irradiance cube (csrc/envmap.hip)
+                 "cfhip_brdf_lut_kernel", "cfhip_cube_irradiance_kernel")
 
 
 def kernel_metadata(lib: str = LIB):

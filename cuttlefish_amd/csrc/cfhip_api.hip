@@ -2892,24 +2892,36 @@ int cfhip_equirect_to_cube_device(cfhip_ctx* ctx, const void* src, int src_pixel
 	});
 }
 
+// the second Hammersley coordinate of point i: the 32 bits of i reversed, times 2^-32
+static double radical_inverse(uint32_t i)
+{
+	uint32_t bits = i;
+	bits = (bits << 16) | (bits >> 16);
+	bits = ((bits & 0x00FF00FFu) << 8) | ((bits & 0xFF00FF00u) >> 8);
+	bits = ((bits & 0x0F0F0F0Fu) << 4) | ((bits & 0xF0F0F0F0u) >> 4);
+	bits = ((bits & 0x33333333u) << 2) | ((bits & 0xCCCCCCCCu) >> 2);
+	bits = ((bits & 0x55555555u) << 1) | ((bits & 0xAAAAAAAAu) >> 1);
+	return (double)bits*0x1p-32;
+}
+
+// what every sample table takes: a multiple of 64 records, a face and the levels of its source chain
+static bool table_shape_ok(uint32_t samples, uint32_t face_size, uint32_t source_levels)
+{
+	if (samples % 64u || samples < CFENV_MIN_SAMPLES || samples > CFENV_MAX_SAMPLES)
+		return false;
+	return face_size && face_size <= CFENV_MAX_FACE && source_levels && source_levels <= cube_levels(face_size);
+}
+
 int cfhip_ggx_sample_table(float roughness, uint32_t samples, uint32_t face_size, uint32_t source_levels, cfhip_ggx_sample* out)
 {
 	if (!out || !(roughness > 0.0f && roughness <= 1.0f))
 		return CFHIP_E_INVALID;
-	if (samples % 64u || samples < CFENV_MIN_SAMPLES || samples > CFENV_MAX_SAMPLES)
-		return CFHIP_E_INVALID;
-	if (!face_size || face_size > CFENV_MAX_FACE || !source_levels || source_levels > cube_levels(face_size))
+	if (!table_shape_ok(samples, face_size, source_levels))
 		return CFHIP_E_INVALID;
 	const double S = (double)samples, N = (double)face_size, r = (double)roughness;
 	const double a = r*r, a2 = a*a;
 	for (uint32_t i = 0; i < samples; ++i) {
-		uint32_t bits = i;
-		bits = (bits << 16) | (bits >> 16);
-		bits = ((bits & 0x00FF00FFu) << 8) | ((bits & 0xFF00FF00u) >> 8);
-		bits = ((bits & 0x0F0F0F0Fu) << 4) | ((bits & 0xF0F0F0F0u) >> 4);
-		bits = ((bits & 0x33333333u) << 2) | ((bits & 0xCCCCCCCCu) >> 2);
-		bits = ((bits & 0x55555555u) << 1) | ((bits & 0xAAAAAAAAu) >> 1);
-		const double xi1 = ((double)i + 0.5)/S, xi2 = (double)bits*0x1p-32;
+		const double xi1 = ((double)i + 0.5)/S, xi2 = radical_inverse(i);
 		const double cos2 = (1.0 - xi1)/(1.0 + (a2 - 1.0)*xi1);
 		const double hz = std::sqrt(cos2), sine = std::sqrt(1.0 - cos2), phi = (2.0*CFENV_PI)*xi2;
 		const double hx = sine*std::cos(phi), hy = sine*std::sin(phi);
@@ -3039,6 +3051,118 @@ int cfhip_cube_sh9_device(cfhip_ctx* ctx, const void* const* faces, uint32_t fac
 			sh9([&] { return cfhip_launch_cube_sh9_rows(table[0], face_size, rows, stream); });
 			sh9([&] { return cfhip_launch_cube_sh9_final(rows, face_size, result_device, stream); });
 			return sh9.rc;
+		});
+	});
+}
+
+// ---- the other lobes' tables, the BRDF lookup table, the irradiance cube (csrc/envmap.hip) ------
+int cfhip_lobe_sample_table(int kind, float roughness, uint32_t samples, uint32_t face_size, uint32_t source_levels,
+	cfhip_ggx_sample* out)
+{
+	if (kind == CFENV_LOBE_GGX)
+		return cfhip_ggx_sample_table(roughness, samples, face_size, source_levels, out);
+	if (kind != CFENV_LOBE_CHARLIE && kind != CFENV_LOBE_LAMBERT)
+		return CFHIP_E_INVALID;
+	if (!out || !table_shape_ok(samples, face_size, source_levels))
+		return CFHIP_E_INVALID;
+	if (kind == CFENV_LOBE_CHARLIE && !(roughness > 0.0f && roughness <= 1.0f))
+		return CFHIP_E_INVALID;
+	const double S = (double)samples, N = (double)face_size, r = (double)roughness;
+	const double a = r*r;
+	for (uint32_t i = 0; i < samples; ++i) {
+		const double xi1 = ((double)i + 0.5)/S, xi2 = radical_inverse(i);
+		const double phi = (2.0*CFENV_PI)*xi2;
+		double lx, ly, lz, pdf;
+		if (kind == CFENV_LOBE_CHARLIE) {
+			const double sine = std::pow(xi1, a/(2.0*a + 1.0)), hz = std::sqrt(1.0 - sine*sine);
+			const double hx = sine*std::cos(phi), hy = sine*std::sin(phi);
+			lx = (2.0*hz)*hx;
+			ly = (2.0*hz)*hy;
+			lz = (2.0*hz)*hz - 1.0;
+			pdf = (((2.0 + 1.0/a)*std::pow(sine, 1.0/a))/(2.0*CFENV_PI))/4.0;
+		} else {
+			lz = 1.0 - xi1;
+			const double sine = std::sqrt(1.0 - lz*lz);
+			lx = sine*std::cos(phi);
+			ly = sine*std::sin(phi);
+			pdf = 1.0/(2.0*CFENV_PI);
+		}
+		double lod = 0.5*std::log2((1.0/(S*pdf))/((4.0*CFENV_PI)/(6.0*(N*N)))) + 1.0;
+		lod = std::fmin(std::fmax(lod, 0.0), (double)(source_levels - 1u));
+		if (lz <= 0.0) {
+			lz = 0.0;
+			lod = 0.0;
+		}
+		out[i].lx = (float)lx; out[i].ly = (float)ly; out[i].lz = (float)lz; out[i].lod = (float)lod;
+	}
+	return CFHIP_OK;
+}
+
+int cfhip_hammersley_table(uint32_t samples, cfhip_hammersley_sample* out)
+{
+	if (!out || !table_shape_ok(samples, 1u, 1u))
+		return CFHIP_E_INVALID;
+	const double S = (double)samples;
+	for (uint32_t i = 0; i < samples; ++i) {
+		const double phi = (2.0*CFENV_PI)*radical_inverse(i);
+		out[i].cos_phi = (float)std::cos(phi); out[i].sin_phi = (float)std::sin(phi);
+		out[i].xi1 = (float)(((double)i + 0.5)/S); out[i].reserved = 0.0f;
+	}
+	return CFHIP_OK;
+}
+
+int cfhip_brdf_lut_device(cfhip_ctx* ctx, void* dst, uint32_t width, uint32_t height, const cfhip_hammersley_sample* table,
+	uint32_t samples, uint32_t sheen, void* stream_)
+{
+	static_assert(sizeof(cfhip_hammersley_sample) == 16, "the ABI's sizes");
+	return guarded(ctx, "brdf_lut", [&]() -> int {
+		const char* const what = "brdf_lut";
+		CF_TRY(check_given(ctx, what, "dst", dst));
+		if ((uintptr_t)dst % 16u)
+			return fail(ctx, CFHIP_E_INVALID, "brdf_lut: dst not aligned to a texel (16 bytes)");
+		CF_TRY(check_sides(ctx, what, width, height, CFENV_MAX_LUT));
+		CF_TRY(check_given(ctx, what, "table", table));
+		if (samples % 64u || samples < CFENV_MIN_SAMPLES || samples > CFENV_MAX_SAMPLES)
+			return fail(ctx, CFHIP_E_INVALID, "brdf_lut: samples is %u, not a multiple of 64 from %u to %u", samples,
+				CFENV_MIN_SAMPLES, CFENV_MAX_SAMPLES);
+		if (sheen > 1u)
+			return fail(ctx, CFHIP_E_INVALID, "brdf_lut: sheen is 0 or 1, not %u", sheen);
+		for (uint32_t i = 0; i < samples; ++i) {
+			const cfhip_hammersley_sample& r = table[i];
+			if (!(std::isfinite(r.cos_phi) && std::isfinite(r.sin_phi) && r.xi1 > 0.0f && r.xi1 < 1.0f))
+				return fail(ctx, CFHIP_E_INVALID, "brdf_lut: table[%u] is not finite with 0 < xi1 < 1", i);
+		}
+		// d_src: the table
+		return device_pass(ctx, stream_, "cfhip_brdf_lut_kernel", 0, (size_t)samples*sizeof(cfhip_hammersley_sample),
+			[&](hipStream_t stream) -> int {
+			cfhip_hammersley_sample* d_table = static_cast<cfhip_hammersley_sample*>(ctx->d_src);
+			HIP_TRY(ctx, hipMemcpyAsync(d_table, table, (size_t)samples*sizeof(cfhip_hammersley_sample), hipMemcpyHostToDevice,
+				stream));
+			return timed(ctx, stream, "brdf_lut", [&] { return cfhip_launch_brdf_lut(dst, width, height, d_table, samples, sheen, stream); });
+		});
+	});
+}
+
+int cfhip_cube_irradiance_device(cfhip_ctx* ctx, const cfhip_sh9_result* sh9_result_device, void* const* faces,
+	uint32_t face_size, uint32_t over_pi, void* stream_)
+{
+	return guarded(ctx, "cube_irradiance", [&]() -> int {
+		const char* const what = "cube_irradiance";
+		CF_TRY(check_given(ctx, what, "sh9_result_device", sh9_result_device));
+		if ((uintptr_t)sh9_result_device % 8u)
+			return fail(ctx, CFHIP_E_INVALID, "cube_irradiance: sh9_result_device not aligned to 8 bytes");
+		CF_TRY(check_faces(ctx, what, faces, face_size));
+		for (uint32_t f = 0; f < 6u; ++f)
+			if (faces[f] == sh9_result_device)
+				return fail(ctx, CFHIP_E_INVALID, "cube_irradiance: faces[%u] equals sh9_result_device", f);
+		if (over_pi > 1u)
+			return fail(ctx, CFHIP_E_INVALID, "cube_irradiance: over_pi is 0 or 1, not %u", over_pi);
+		return device_pass(ctx, stream_, "cfhip_cube_irradiance_kernel", 6u*sizeof(void*), 0, [&](hipStream_t stream) -> int {
+			void** table[1];
+			CF_TRY(upload_tables(ctx, stream, {{faces, 6u}}, table));
+			return timed(ctx, stream, "cube_irradiance", [&] {
+				return cfhip_launch_cube_irradiance(sh9_result_device, table[0], face_size, over_pi, stream);
+			});
 		});
 	});
 }

@@ -59,4 +59,15 @@ extern "C" hipError_t cfhip_launch_cube_sh9_rows(const void* const* faces, uint3
 extern "C" hipError_t cfhip_launch_cube_sh9_final(const double* rows, uint32_t face_size, cfhip_sh9_result* result,
 	hipStream_t stream);
 
+// ---- the lobes beside GGX, the BRDF lookup table and the irradiance cube -----------------------
+constexpr int CFENV_LOBE_GGX = 0, CFENV_LOBE_CHARLIE = 1, CFENV_LOBE_LAMBERT = 2;      // cfhip_lobe_sample_table's kind
+constexpr uint32_t CFENV_MAX_LUT = 1024;           // a lookup table's width and height
+
+// one launch: a wavefront per texel of the width x height table; table: device, `samples` records
+extern "C" hipError_t cfhip_launch_brdf_lut(void* dst, uint32_t width, uint32_t height, const cfhip_hammersley_sample* table,
+	uint32_t samples, uint32_t sheen, hipStream_t stream);
+// one launch writes the six faces from the record cfhip_cube_sh9_device left on the device
+extern "C" hipError_t cfhip_launch_cube_irradiance(const cfhip_sh9_result* sh, void* const* faces, uint32_t face_size,
+	uint32_t over_pi, hipStream_t stream);
+
 #endif

@@ -14,6 +14,9 @@
 //   sh9 rows   one wavefront per face row: 37 sums per lane (9 basis values x RGBA, and the solid angle), the butterfly,
 //              one record per row
 //   sh9 final  the rows added in (face, y) order, one value per lane, and the normalisation
+//   brdf lut   (section 4.27) one wavefront per texel of the split sum's second factor: the prefilter's frame around a
+//              Hammersley table -- GGX scale and bias, and with sheen the Charlie albedo
+//   irradiance (section 4.27) one output texel per lane: the diffuse term evaluated from the record sh9 final left
 // No kernel here may use scratch, spill a vector register or use AGPRs (cuttlefish_amd/build.py).
 #include "cf_texel.h"
 #include "envmap.h"
@@ -300,7 +303,128 @@ cfhip_cube_sh9_final_kernel(const double* __restrict__ rows, uint32_t n, cfhip_s
 		out[v] = sum;
 }
 
+// ---- part 4: the BRDF lookup table -------------------------------------------------------------
+// One wavefront per texel, four per workgroup, as the prefilter: lane j takes the records i = j mod 64 of the Hammersley
+// table, staged in LDS CFENV_CHUNK at a time, and the lanes' sums meet in sum64's butterfly.  A wavefront past the end
+// works on the last texel and stores nothing.  SHEEN: the Charlie column too -- the only pow in this file.
+template <bool SHEEN>
+__global__ void __launch_bounds__(WG)
+cfhip_brdf_lut_kernel(float4* __restrict__ dst, uint32_t width, uint32_t height, const cfhip_hammersley_sample* __restrict__ table,
+	uint32_t samples)
+{
+	__shared__ cfhip_hammersley_sample tab[CFENV_CHUNK];
+	const uint32_t lane = threadIdx.x, wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)threadIdx.y);
+	const uint32_t tid = wave*CFENV_WG_X + lane, total = width*height;
+	uint32_t texel = blockIdx.x*CFENV_WG_Y + wave;
+	const bool live = texel < total;
+	if (!live)
+		texel = total - 1u;
+	const uint32_t y = texel/width, x = texel%width;
+	const double NoV = ((double)x + 0.5)/(double)width, r = ((double)y + 0.5)/(double)height;
+	const double alpha = r*r, a2 = alpha*alpha;
+	const double vx = sqrt(1.0 - NoV*NoV), vz = NoV;
+	const double gv = sqrt((NoV*NoV)*(1.0 - a2) + a2);     // the view's half of the visibility term
+	const double inv_alpha = 1.0/alpha, lead = 2.0 + inv_alpha;
+	double A = 0.0, B = 0.0, C = 0.0;
+	for (uint32_t base = 0; base < samples; base += CFENV_CHUNK) {
+		const uint32_t count = min(CFENV_CHUNK, samples - base);
+		__syncthreads();                               // the chunk before is read
+		for (uint32_t i = tid; i < count; i += WG)
+			tab[i] = table[base + i];
+		__syncthreads();
+		for (uint32_t i = lane; i < count; i += CFENV_WG_X) {
+			const cfhip_hammersley_sample rec = tab[i];
+			const double cphi = (double)rec.cos_phi, xi = (double)rec.xi1;
+			{
+				const double c2 = (1.0 - xi)/(1.0 + (a2 - 1.0)*xi);
+				const double hz = sqrt(c2), st = sqrt(1.0 - c2), hx = st*cphi;
+				const double VoH = (vx*hx) + (vz*hz), NoL = (2.0*VoH)*hz - vz;
+				if (NoL > 0.0 && VoH > 0.0) {
+					const double vis = 0.5/(NoL*gv + NoV*sqrt((NoL*NoL)*(1.0 - a2) + a2));
+					const double t = ((vis*VoH)*NoL)/hz, m = 1.0 - VoH, fc = ((m*m)*(m*m))*m;
+					A = A + (1.0 - fc)*t;
+					B = B + fc*t;
+				}
+			}
+			if (SHEEN) {
+				const double hz = 1.0 - xi, st = sqrt(1.0 - hz*hz), hx = st*cphi;
+				const double VoH = (vx*hx) + (vz*hz), NoL = (2.0*VoH)*hz - vz;
+				if (NoL > 0.0 && VoH > 0.0) {
+					const double vn = 1.0/(4.0*((NoL + NoV) - NoL*NoV));
+					const double d = (lead*pow(st, inv_alpha))/(2.0*CFENV_PI);
+					C = C + ((vn*d)*NoL)*VoH;
+				}
+			}
+		}
+	}
+	A = butterfly(A);
+	B = butterfly(B);
+	if (SHEEN)
+		C = butterfly(C);
+	if (live && lane == 0) {
+		const double S = (double)samples;
+		float4 out;
+		out.x = (float)((4.0*A)/S); out.y = (float)((4.0*B)/S); out.z = SHEEN ? (float)(((8.0*CFENV_PI)*C)/S) : 0.0f; out.w = 1.0f;
+		dst[texel] = out;
+	}
+}
+
+// ---- part 5: the irradiance cube from the nine coefficients --------------------------------------------------------------
+// one texel per lane, the six faces in grid z; the 36 coefficients are the same for every lane: scalar loads
+__global__ void __launch_bounds__(WG)
+cfhip_cube_irradiance_kernel(const cfhip_sh9_result* __restrict__ sh, void* const* __restrict__ faces, uint32_t n, uint32_t over_pi)
+{
+	const uint32_t x = blockIdx.x*CFENV_WG_X + threadIdx.x, y = blockIdx.y*CFENV_WG_Y + threadIdx.y, f = blockIdx.z;
+	if (x >= n || y >= n)
+		return;
+	const double dn = (double)n;
+	double dx, dy, dz;
+	face_dir(f, unit_coord((double)x + 0.5, dn), unit_coord((double)y + 0.5, dn), dx, dy, dz);
+	const double len = sqrt((dx*dx + dy*dy) + dz*dz);
+	dx = dx/len; dy = dy/len; dz = dz/len;
+	const double basis[9] = {CFENV_SH_C0, CFENV_SH_C1*dy, CFENV_SH_C1*dz, CFENV_SH_C1*dx, CFENV_SH_C2*(dx*dy),
+		CFENV_SH_C2*(dy*dz), CFENV_SH_C20*(3.0*(dz*dz) - 1.0), CFENV_SH_C2*(dx*dz), CFENV_SH_C22*(dx*dx - dy*dy)};
+	// the cosine lobe's factor of each band: pi, 2 pi / 3, pi / 4
+	constexpr double b1 = (2.0*CFENV_PI)/3.0, b2 = CFENV_PI/4.0;
+	constexpr double band[9] = {CFENV_PI, b1, b1, b1, b2, b2, b2, b2, b2};
+	double acc[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+	for (uint32_t b = 0; b < 9u; ++b) {
+		const double w = band[b]*basis[b];
+#pragma unroll
+		for (uint32_t ch = 0; ch < 4u; ++ch)
+			acc[ch] = acc[ch] + w*sh->coeff[b][ch];
+	}
+	if (over_pi) {
+#pragma unroll
+		for (uint32_t ch = 0; ch < 4u; ++ch)
+			acc[ch] = acc[ch]/CFENV_PI;
+	}
+	float4 out;
+	out.x = (float)acc[0]; out.y = (float)acc[1]; out.z = (float)acc[2]; out.w = (float)acc[3];
+	static_cast<float4*>(faces[f])[(size_t)y*n + x] = out;
+}
+
 } // namespace
+
+extern "C" hipError_t cfhip_launch_brdf_lut(void* dst, uint32_t width, uint32_t height, const cfhip_hammersley_sample* table,
+	uint32_t samples, uint32_t sheen, hipStream_t stream)
+{
+	const dim3 grid((width*height + CFENV_WG_Y - 1u)/CFENV_WG_Y), block(CFENV_WG_X, CFENV_WG_Y);
+	if (sheen)
+		hipLaunchKernelGGL(cfhip_brdf_lut_kernel<true>, grid, block, 0, stream, static_cast<float4*>(dst), width, height, table, samples);
+	else
+		hipLaunchKernelGGL(cfhip_brdf_lut_kernel<false>, grid, block, 0, stream, static_cast<float4*>(dst), width, height, table, samples);
+	return hipGetLastError();
+}
+
+extern "C" hipError_t cfhip_launch_cube_irradiance(const cfhip_sh9_result* sh, void* const* faces, uint32_t face_size,
+	uint32_t over_pi, hipStream_t stream)
+{
+	hipLaunchKernelGGL(cfhip_cube_irradiance_kernel, dim3((face_size + CFENV_WG_X - 1u)/CFENV_WG_X,
+		(face_size + CFENV_WG_Y - 1u)/CFENV_WG_Y, 6), dim3(CFENV_WG_X, CFENV_WG_Y), 0, stream, sh, faces, face_size, over_pi);
+	return hipGetLastError();
+}
 
 extern "C" hipError_t cfhip_launch_equirect_to_cube(const void* src, int32_t src_type, uint32_t width, uint32_t height,
 	unsigned long long src_pitch, void* const* faces, uint32_t face_size, uint32_t supersample, hipStream_t stream)

@@ -870,20 +870,31 @@ class Texture:
         texel, a multiple of 64 from 64 to 4096).  mip_levels: all by default; roughness: one value in [0, 1] per level,
         by default r_k = k / (K - 1), 0 -- a copy -- for a single level.  The levels are RGBAF (float32) images.  False,
         before any device work, for a texture that is no cube, is an array, is converted or lacks a face of level 0."""
+        plan = self._prefilter_plan(mip_levels, roughness)
+        if plan is None:
+            return False
+        faces, levels, roughness = plan
+        self._set_cube_chain(self._context().cube_prefilter(faces, roughness, samples), levels)
+        return True
+
+    def _prefilter_plan(self, mip_levels, roughness):
+        """what prefilter_environment and prefilter_lobe work from: (the faces of level 0, the level count, one roughness
+        or None per level), or None for their refusals"""
         faces = self._cube_faces()
         if faces is None:
-            return False
+            return None
         full = api.cube_level_count(self._w)
         levels = full if mip_levels is None else min(max(int(mip_levels), 1), full)
         if roughness is None:
             roughness = [0.0] if levels == 1 else [k/float(levels - 1) for k in range(levels)]
-        roughness = [float(r) for r in roughness]
-        if len(roughness) != levels or any(not (0.0 <= r <= 1.0) for r in roughness):
-            return False
-        chain = self._context().cube_prefilter(faces, roughness, samples)
+        roughness = [None if r is None else float(r) for r in roughness]
+        if len(roughness) != levels or any(r is not None and not (0.0 <= r <= 1.0) for r in roughness):
+            return None
+        return faces, levels, roughness
+
+    def _set_cube_chain(self, chain, levels: int):
         self._mips = levels
         self._images = [[[chain[k][f] for f in range(6)]] for k in range(levels)]
-        return True
 
     def irradiance_sh9(self) -> Optional[np.ndarray]:
         """The nine spherical-harmonic coefficients of level 0 of an environment cube, (9, 4) float64 in the order 1, y,
@@ -893,6 +904,76 @@ class Texture:
         if faces is None:
             return None
         return self._context().cube_sh9(faces)[0]
+
+    # ---- the rest of a split-sum shader's inputs (Context.brdf_lut / cube_prefilter_lobe / cube_irradiance) -----------
+    @staticmethod
+    def brdf_lut(size: int = 128, samples: int = 1024, sheen: bool = False, device_id: int = 0) -> Optional["Texture"]:
+        """The BRDF lookup table of the split sum as a 2-D size^2 RGBAF texture, ready for convert (a 16-bit float
+        standard format is the usual choice): x is N.V, y roughness, R and G the scale and bias of F0 under GGX, B the
+        Charlie sheen albedo when `sheen` (else 0), A 1 (Context.brdf_lut).  None for a size outside 1 to 1024."""
+        if isinstance(size, (bool, np.bool_)) or not isinstance(size, (int, np.integer)) or not 1 <= size <= api.ENV_MAX_LUT:
+            return None
+        t = Texture(int(size), int(size), device_id=device_id)
+        if not t.is_valid():
+            return None
+        t.set_image(t._context().brdf_lut(int(size), int(size), samples, sheen))
+        return t
+
+    def prefilter_lobe(self, kind: int, mip_levels: Optional[int] = None, samples: int = 256,
+                       roughness: Optional[Sequence[float]] = None) -> bool:
+        """prefilter_environment under another lobe: api.LOBE_CHARLIE for a sheen chain, api.LOBE_LAMBERT for the
+        irradiance over pi in every level (its roughness is not read: every level but a None entry is filtered),
+        api.LOBE_GGX for prefilter_environment itself.  The same levels, defaults and refusals, and one more: False
+        where a Charlie level is so sharp that none of `samples` records stays above the horizon
+        (Context.cube_prefilter_lobe; the default levels of a chain want 1024 samples)."""
+        if kind not in (api.LOBE_GGX, api.LOBE_CHARLIE, api.LOBE_LAMBERT):
+            return False
+        plan = self._prefilter_plan(mip_levels, roughness)
+        if plan is None:
+            return False
+        faces, levels, roughness = plan
+        api._check_samples(samples)                        # raises as prefilter_environment does
+        try:
+            chain = self._context().cube_prefilter_lobe(faces, kind, roughness, samples)
+        except ValueError:                                 # a level with no record above the horizon
+            return False
+        self._set_cube_chain(chain, levels)
+        return True
+
+    def irradiance_cube(self, face_size: int = 32, method: str = "sh9", samples: int = 1024) -> Optional["Texture"]:
+        """A new one-level cube of face_size^2 RGBAF faces holding the irradiance of this cube's level 0 over pi -- what
+        a shader multiplies by the albedo.  method "sh9": the nine coefficients and their evaluation, both on the device
+        (Context.cube_sh9_device, cube_irradiance_device), any face_size.  method "lambert": `samples` uniform
+        directions per texel weighted by the cosine, through the prefilter kernel; face_size must be this cube's size
+        halved some number of times, and the levels above the wanted one are made as copies and dropped -- accepted
+        for a pass that runs once per environment.  None where prefilter_environment returns False, and for another
+        method or such a face_size."""
+        import torch
+        faces = self._cube_faces()
+        if faces is None or method not in ("sh9", "lambert") or isinstance(face_size, (bool, np.bool_)) \
+                or not isinstance(face_size, (int, np.integer)) or not 1 <= face_size <= api.ENV_MAX_FACE:
+            return None
+        n, m = self._w, int(face_size)
+        if method == "lambert":
+            k = next((k for k in range(api.cube_level_count(n)) if max(1, n >> k) == m), None)
+            if k is None:
+                return None
+        ctx = self._context()
+        if method == "lambert":
+            level = ctx.cube_prefilter_lobe(faces, api.LOBE_LAMBERT, [None]*k + [1.0], samples)[k]
+        else:
+            device = "cuda:%d" % self._device_id
+            dev = torch.from_numpy(np.ascontiguousarray(np.stack(faces), dtype=np.float32)).to(device)
+            res = torch.zeros(37, dtype=torch.float64, device=device)
+            out = torch.empty((6, m, m, 4), dtype=torch.float32, device=device)
+            ctx.cube_sh9_device([dev[f].data_ptr() for f in range(6)], n, res.data_ptr())
+            ctx.cube_irradiance_device(res.data_ptr(), [out[f].data_ptr() for f in range(6)], m, over_pi=True)
+            level = out.cpu().numpy()
+        t = Texture(Dimension.Cube, m, m, 0, 1, self._color_space, device_id=self._device_id)
+        t._ctx = self._ctx
+        for f in range(6):
+            t.set_image(level[f], CubeFace(f), 0)
+        return t
 
     def mip_post_results(self):
         """The records of the last generate_mipmaps(alpha_coverage=...): one list per surface in [depth][face] order,

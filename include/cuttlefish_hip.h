@@ -692,6 +692,71 @@ int cfhip_cube_prefilter_device(cfhip_ctx* ctx, const void* const* src_levels, u
 int cfhip_cube_sh9_device(cfhip_ctx* ctx, const void* const* faces, uint32_t face_size, cfhip_sh9_result* result_device,
 	void* stream);
 
+/* The rest of what a split-sum shader with GGX, sheen and diffuse terms reads: sample tables of two more lobes for the
+ * prefilter above, the BRDF lookup table (the split sum's second factor) and a rendered irradiance cube.  The vocabulary
+ * (faces, n^, sum64, IEEE double in the written order) is that of the comment above; pow of the Charlie terms and cos,
+ * sin, log2 of the table helpers are the math library's.
+ *
+ * cfhip_lobe_sample_table (host only, no context): `samples` records for one destination level of
+ * cfhip_cube_prefilter_device, from the Hammersley points of cfhip_ggx_sample_table (xi1 = (i + 0.5) / S, xi2 = the
+ * radical inverse of i, phi = 2 pi xi2), S a multiple of 64 from 64 to 4096, all in double, rounded to float.
+ *   kind 0, GGX      exactly cfhip_ggx_sample_table(roughness, ...).
+ *   kind 1, Charlie  alpha = roughness^2 (0 < roughness <= 1); sin theta = pow(xi1, alpha / (2 alpha + 1)),
+ *                    cos theta = sqrt(1 - sin^2 theta); h = (sin theta cos phi, sin theta sin phi, cos theta),
+ *                    l = 2 hz h - (0, 0, 1) as (2 hz) hx, (2 hz) hy, (2 hz) hz - 1;
+ *                    pdf = D / 4, D = ((2 + 1 / alpha) pow(sin theta, 1 / alpha)) / (2 pi);
+ *                    lod = clamp(0.5 log2((1 / (S pdf)) / (4 pi / (6 N^2))) + 1, 0, source_levels - 1) -- a pdf of 0
+ *                    gives the last level; a record with lz <= 0 keeps lx, ly and gets lz = 0, lod = 0.
+ *   kind 2, Lambert  uniform over the hemisphere, because the prefilter weighs every record by lz: the level is then
+ *                    the integral of L cos over the integral of cos, the irradiance over pi.  roughness is not read;
+ *                    lz = 1 - xi1, sin theta = sqrt(1 - lz^2), l = (sin theta cos phi, sin theta sin phi, lz);
+ *                    pdf = 1 / (2 pi), so the lod -- the same formula -- is one value for the table.
+ * CFHIP_E_INVALID, with nothing written, for any other kind, a NULL out, samples, face_size or source_levels outside
+ * what cfhip_ggx_sample_table takes, and for kinds 0 and 1 a roughness outside (0, 1].
+ *
+ * cfhip_hammersley_table (host only, no context): record i is (float)cos phi, (float)sin phi, (float)xi1, 0 of the same
+ * points -- what cfhip_brdf_lut_device reads.  CFHIP_E_INVALID for a NULL out or such a `samples`.
+ *
+ * cfhip_brdf_lut_device: dst is width x height (1 to 1024 each) tightly packed RGBA32F on the device, 16-byte aligned;
+ * table is host memory, `samples` records (a multiple of 64 from 64 to 4096), each finite with 0 < xi1 < 1; it travels
+ * through the context's staging.  sheen is 0 or 1.  Texel (x, y): NoV = (x + 0.5) / width, r = (y + 0.5) / height,
+ * alpha = r r, a2 = alpha alpha, v = (vx, 0, vz) = (sqrt(1 - NoV NoV), 0, NoV).  With c = (double)cos_phi and
+ * xi = (double)xi1 of record i:
+ *   GGX      c2 = (1 - xi) / (1 + (a2 - 1) xi), hz = sqrt(c2), st = sqrt(1 - c2), hx = st c, VoH = (vx hx) + (vz hz),
+ *            NoL = (2 VoH) hz - vz.  Where NoL > 0 and VoH > 0:
+ *            vis = 0.5 / (NoL sqrt((NoV NoV) (1 - a2) + a2) + NoV sqrt((NoL NoL) (1 - a2) + a2)),
+ *            t = ((vis VoH) NoL) / hz, m = 1 - VoH, fc = ((m m) (m m)) m, A_i = (1 - fc) t, B_i = fc t; else both 0.
+ *            R = (float)((4 sum64(A)) / S), G = (float)((4 sum64(B)) / S): the scale and the bias of F0 under the
+ *            height-correlated Smith term and Schlick's Fresnel.
+ *   Charlie  with sheen: hz = 1 - xi (uniform half vectors), st = sqrt(1 - hz hz), hx, VoH and NoL as above.  Under the
+ *            same condition vn = 1 / (4 ((NoL + NoV) - NoL NoV)), d = ((2 + 1 / alpha) pow(st, 1 / alpha)) / (2 pi),
+ *            C_i = ((vn d) NoL) VoH; else 0.  B = (float)(((8 pi) sum64(C)) / S): the sheen lobe's directional albedo.
+ *            Without sheen B = 0.
+ * Alpha is 1.  One launch, a wavefront per texel; identical calls give identical bytes.
+ *
+ * cfhip_cube_irradiance_device: sh9_result_device is the record cfhip_cube_sh9_device left on the device (8-byte
+ * aligned, only read; no host round trip); faces[6] as above, face_size 1 to 8192, none equal to the record.  For a
+ * texel's n^ = (x, y, z) the nine basis values Y_b of cfhip_cube_sh9_device's order and constants, and the cosine
+ * lobe's band factors k_b = pi for b = 0, (2 pi) / 3 for b = 1 ... 3, pi / 4 for b = 4 ... 8: per channel E = 0.0,
+ * E = E + (k_b Y_b) coeff[b][c] for b = 0 ... 8 in that order; with over_pi (0 or 1) set E = E / pi; the texel is
+ * (float)E, alpha included.  One launch writes the six faces.
+ *
+ * Every argument is checked before anything is enqueued; stream == NULL means the context's stream and the call
+ * synchronises. */
+enum { CFHIP_LOBE_GGX = 0, CFHIP_LOBE_CHARLIE = 1, CFHIP_LOBE_LAMBERT = 2 };
+typedef struct cfhip_hammersley_sample {
+	float cos_phi, sin_phi;
+	float xi1;
+	float reserved;
+} cfhip_hammersley_sample;
+int cfhip_lobe_sample_table(int kind, float roughness, uint32_t samples, uint32_t face_size, uint32_t source_levels,
+	cfhip_ggx_sample* out);
+int cfhip_hammersley_table(uint32_t samples, cfhip_hammersley_sample* out);
+int cfhip_brdf_lut_device(cfhip_ctx* ctx, void* dst, uint32_t width, uint32_t height, const cfhip_hammersley_sample* table,
+	uint32_t samples, uint32_t sheen, void* stream);
+int cfhip_cube_irradiance_device(cfhip_ctx* ctx, const cfhip_sh9_result* sh9_result_device, void* const* faces,
+	uint32_t face_size, uint32_t over_pi, void* stream);
+
 /* One Image::resize on the GPU (lib/src/Image.cpp:1324-1511) -- what Texture::generateMipmaps calls
  * per level, and per custom mip image (Texture.cpp:1499-1503, any source size): src (any of the
  * three pixel types) -> dst, dst_width x dst_height tightly packed RGBA32F, in linear space as
@@ -1454,7 +1519,7 @@ int cfhip_std_compare_device(cfhip_ctx* ctx, int format, int type, const void* p
 	uint32_t width, uint32_t height, const void* ref, int ref_pixel_type, size_t ref_pitch_bytes,
 	const uint8_t mask_rgba[4], unsigned flags, cfhip_compare_result* result_device, void* stream);
 
-/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass), cfhip_alpha_coverage_device, cfhip_alpha_bleed_array_device, cfhip_alpha_sdf_array_device (every pass), cfhip_spec_aa_array_device (every launch), cfhip_height_ao_array_device (both launches), cfhip_equirect_to_cube_device, cfhip_cube_prefilter_device (every level) or cfhip_cube_sh9_device (both launches) call on
+/* Kernel-only time of the most recent cfhip_encode, cfhip_encode_device, cfhip_pvrtc_*, cfhip_decode*, cfhip_compare*, cfhip_std_*, cfhip_rdo* (every trial of cfhip_rdo_target*), cfhip_lz_size*, cfhip_deflate*, cfhip_png_encode* (the filter, the encoder's stages, crc and final), cfhip_image_ops_device, cfhip_mip_post_array_device (every launch of the post-pass), cfhip_alpha_coverage_device, cfhip_alpha_bleed_array_device, cfhip_alpha_sdf_array_device (every pass), cfhip_spec_aa_array_device (every launch), cfhip_height_ao_array_device (both launches), cfhip_equirect_to_cube_device, cfhip_cube_prefilter_device (every level), cfhip_cube_sh9_device (both launches), cfhip_brdf_lut_device or cfhip_cube_irradiance_device call on
  * this context, measured with hipEvents on the launch stream (ms; <0 if none).
  * Synchronises the stream. */
 float cfhip_last_kernel_ms(cfhip_ctx* ctx);
