@@ -3428,6 +3428,27 @@ extern "C" void cfhip_astc_plan(const cfastc::AstcBlobHeader* h, uint32_t qualit
 	*lds_bytes = astc_lds_bytes(h, quality, best_nw, best_c != 0u, hdr != 0u);
 }
 
+// the 168-register build only where three waves per SIMD actually become resident
+static bool cf_astc_dense(uint32_t nwaves, size_t lds_bytes, bool hdr)
+{
+	static const bool no_dense = getenv("CFHIP_ASTC_NO_DENSE") != nullptr;
+	return (cf_astc_cu_lds()/(lds_bytes + cf_astc_wg_slack(true)))*nwaves > 8u && !no_dense && !hdr;
+}
+
+// The whole launch shape of a surface with bx blocks per row, for the tests that enumerate the shapes (no device
+// needed): shape[0] waves per workgroup, [1] the 168-register build, [2] blocks a wave searches at a time (two up
+// to Quality::Normal: can_pair in the kernel, the second slot of astc_lds_bytes), [3] dynamic LDS bytes.
+extern "C" void cfhip_astc_launch_shape(const cfastc::AstcBlobHeader* h, uint32_t quality, uint32_t hdr, uint32_t bx, uint32_t shape[4])
+{
+	uint32_t nwaves, wcached;
+	size_t lds_bytes;
+	cfhip_astc_plan(h, quality, hdr, bx, &nwaves, &wcached, &lds_bytes);
+	shape[0] = nwaves;
+	shape[1] = cf_astc_dense(nwaves, lds_bytes, hdr != 0u) ? 1u : 0u;
+	shape[2] = quality <= (CF_ASTC_R4_HIGH ? 3u : 2u) ? 2u : 1u;
+	shape[3] = (uint32_t)lds_bytes;
+}
+
 extern "C" hipError_t cfhip_launch_astc(const cf_kparams* kp, int pixel_type, uint32_t nwaves, size_t lds_bytes, hipStream_t stream)
 {
 	dim3 grid((kp->bx + nwaves*4u - 1u)/(nwaves*4u), kp->by, 1);
@@ -3460,10 +3481,9 @@ extern "C" hipError_t cfhip_launch_astc(const cf_kparams* kp, int pixel_type, ui
 				attr_set[dev] = true;
 		}
 	}
-	// the 168-register build only where three waves per SIMD actually become resident
-	static const bool no_dense = getenv("CFHIP_ASTC_NO_DENSE") != nullptr, debug = getenv("CFHIP_ASTC_DEBUG") != nullptr;
+	static const bool debug = getenv("CFHIP_ASTC_DEBUG") != nullptr;
 	const bool hdr = ((kp->flags >> 19) & 3u) != 0u;
-	const bool dense = (cf_astc_cu_lds()/(lds_bytes + cf_astc_wg_slack(true)))*nwaves > 8u && !no_dense && !hdr;
+	const bool dense = cf_astc_dense(nwaves, lds_bytes, hdr);
 	void (*fn)(cf_kparams) = nullptr;
 	if (dense)
 		fn = pixel_type == 0 ? &cfhip_astc_encode_kernel<0, 12, false> : &cfhip_astc_encode_kernel<1, 12, false>;

@@ -49,6 +49,7 @@
 extern "C" hipError_t cfhip_launch_bc7(const cf_kparams* kp, int pixel_type, int unit_weights,
 	hipStream_t stream);
 extern "C" hipError_t cfhip_launch_astc(const cf_kparams* kp, int pixel_type, uint32_t nwaves, size_t lds_bytes, hipStream_t stream);
+extern "C" void cfhip_astc_launch_shape(const cfastc::AstcBlobHeader* h, uint32_t quality, uint32_t hdr, uint32_t bx, uint32_t shape[4]);
 extern "C" void cfhip_astc_plan(const cfastc::AstcBlobHeader* h, uint32_t quality, uint32_t hdr, uint32_t bx, uint32_t* nwaves, uint32_t* wcached, size_t* lds_bytes);
 extern "C" hipError_t cfhip_launch_etc(const cf_kparams* kp, int format, int pixel_type, int snorm,
 	hipStream_t stream);
@@ -1682,6 +1683,15 @@ int cfhip_debug_astc_table_info(int bw, int bh, int* npart3, int* ncfg10, uint16
 			cfg_modes[i*64 + k] = k < ncfg10[i] ? (uint16_t)(cfgs[i*64 + k].mode | (cfgs[i*64 + k].wq << 11)) : 0xFFFF;
 	}
 	return (int)h->total;
+}
+
+// Host-only, read-only: the launch shape cfhip_astc_plan and the launcher give a bw x bh surface of bx blocks per
+// row (tests/test_astc_cases.py enumerates the shapes; cfhip_astc_launch_shape in astc_encode.hip names the fields).
+int cfhip_debug_astc_launch_shape(int bw, int bh, uint32_t quality, uint32_t hdr, uint32_t bx, uint32_t shape[4])
+{
+	const std::vector<uint8_t> blob = cfastc::build_blob(bw, bh);
+	cfhip_astc_launch_shape(reinterpret_cast<const cfastc::AstcBlobHeader*>(blob.data()), quality, hdr, bx, shape);
+	return CFHIP_OK;
 }
 
 int cfhip_shard_rows(uint32_t block_rows, int rank, int world, uint32_t* row_begin,

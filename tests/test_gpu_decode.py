@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+from astc_cases import block_mode as _astc_block_mode    # (N, M, weight range index, dual) or None
 from cuttlefish_amd import Format, Type, api, make_params, synth
 
 pytestmark = pytest.mark.gpu
@@ -76,34 +77,6 @@ def _same(a, b):
 
 
 # ---- random bitstreams ------------------------------------------------------------------------------
-
-def _astc_block_mode(mode):
-    """(N, M, wq, dual) of an 11-bit block mode, None for reserved / void extent (specification)"""
-    R0, A, B = (mode >> 4) & 1, (mode >> 5) & 3, (mode >> 7) & 3
-    H, D = (mode >> 9) & 1, (mode >> 10) & 1
-    if mode & 3:
-        R1, R2 = mode & 1, (mode >> 1) & 1
-        k = (mode >> 2) & 3
-        if k == 0: N, M = B + 4, A + 2
-        elif k == 1: N, M = B + 8, A + 2
-        elif k == 2: N, M = A + 2, B + 8
-        elif not (mode >> 8) & 1: N, M = A + 2, (B & 1) + 6
-        else: N, M = (B & 1) + 2, A + 2
-    else:
-        if not mode & 0xC:
-            return None
-        R1, R2 = (mode >> 2) & 1, (mode >> 3) & 1
-        if B == 0: N, M = 12, A + 2
-        elif B == 1: N, M = A + 2, 12
-        elif B == 2: N, M, H, D = A + 6, ((mode >> 9) & 3) + 6, 0, 0
-        elif A == 0: N, M = 6, 10
-        elif A == 1: N, M = 10, 6
-        else: return None
-    r = (R2 << 2) | (R1 << 1) | R0
-    if r < 2:
-        return None
-    return N, M, (r - 2) + 6 * H, D
-
 
 _WQ = [(1, 0, 0), (0, 1, 0), (2, 0, 0), (0, 0, 1), (1, 1, 0), (3, 0, 0), (1, 0, 1), (2, 1, 0), (4, 0, 0),
        (2, 0, 1), (3, 1, 0), (5, 0, 0)]
