@@ -807,11 +807,13 @@ __device__ __forceinline__ void fit_lane(const Tex& tx, uint32_t mask, bool m6, 
 			q23 = __builtin_amdgcn_udot4(M2, P[3], q23, false);
 			q33 = __builtin_amdgcn_udot4(M3, P[3], q33, false);
 		}
-		const float C00 = (float)(int)(__umul24(n, q00) - __umul24(s[0], s[0])), C01 = (float)(int)(__umul24(n, q01) - __umul24(s[0], s[1]));
-		const float C02 = (float)(int)(__umul24(n, q02) - __umul24(s[0], s[2])), C03 = (float)(int)(__umul24(n, q03) - __umul24(s[0], s[3]));
-		const float C11 = (float)(int)(__umul24(n, q11) - __umul24(s[1], s[1])), C12 = (float)(int)(__umul24(n, q12) - __umul24(s[1], s[2]));
-		const float C13 = (float)(int)(__umul24(n, q13) - __umul24(s[1], s[3])), C22 = (float)(int)(__umul24(n, q22) - __umul24(s[2], s[2]));
-		const float C23 = (float)(int)(__umul24(n, q23) - __umul24(s[2], s[3])), C33 = (float)(int)(__umul24(n, q33) - __umul24(s[3], s[3]));
+		// n q_cd - s_c s_d on exact floats, one fused multiply-add per term (bc7_packed.h: cov_term); n, q and s converted once each
+		const float fn = (float)n, f0 = (float)s[0], f1 = (float)s[1], f2 = (float)s[2], f3 = (float)s[3];
+		const float C00 = cov_term(fn, q00, f0, f0), C01 = cov_term(fn, q01, f0, f1);
+		const float C02 = cov_term(fn, q02, f0, f2), C03 = cov_term(fn, q03, f0, f3);
+		const float C11 = cov_term(fn, q11, f1, f1), C12 = cov_term(fn, q12, f1, f2);
+		const float C13 = cov_term(fn, q13, f1, f3), C22 = cov_term(fn, q22, f2, f2);
+		const float C23 = cov_term(fn, q23, f2, f3), C33 = cov_term(fn, q33, f3, f3);
 
 		float bestd = C00;
 		float v0 = C00, v1 = C01, v2 = C02, v3 = C03;
@@ -1160,11 +1162,13 @@ __device__ __forceinline__ float subset_residual(const Moments& mo, uint32_t mas
 	const uint32_t s[4] = {mo.s[0], mo.s[1], mo.s[2], mo.s[3]};
 	const uint32_t q00 = mo.q00, q01 = mo.q01, q02 = mo.q02, q03 = mo.q03, q11 = mo.q11, q12 = mo.q12, q13 = mo.q13,
 		q22 = mo.q22, q23 = mo.q23, q33 = mo.q33;
-	const float C00 = (float)(int)(__umul24(n, q00) - __umul24(s[0], s[0])), C01 = (float)(int)(__umul24(n, q01) - __umul24(s[0], s[1]));
-	const float C02 = (float)(int)(__umul24(n, q02) - __umul24(s[0], s[2])), C03 = (float)(int)(__umul24(n, q03) - __umul24(s[0], s[3]));
-	const float C11 = (float)(int)(__umul24(n, q11) - __umul24(s[1], s[1])), C12 = (float)(int)(__umul24(n, q12) - __umul24(s[1], s[2]));
-	const float C13 = (float)(int)(__umul24(n, q13) - __umul24(s[1], s[3])), C22 = (float)(int)(__umul24(n, q22) - __umul24(s[2], s[2]));
-	const float C23 = (float)(int)(__umul24(n, q23) - __umul24(s[2], s[3])), C33 = (float)(int)(__umul24(n, q33) - __umul24(s[3], s[3]));
+	// (the covariance terms as in fit_lane: cov_term on exact floats; an opaque block's fourth-channel terms are +0 and unused)
+	const float fn = (float)n, f0 = (float)s[0], f1 = (float)s[1], f2 = (float)s[2], f3 = (float)s[3];
+	const float C00 = cov_term(fn, q00, f0, f0), C01 = cov_term(fn, q01, f0, f1);
+	const float C02 = cov_term(fn, q02, f0, f2), C03 = cov_term(fn, q03, f0, f3);
+	const float C11 = cov_term(fn, q11, f1, f1), C12 = cov_term(fn, q12, f1, f2);
+	const float C13 = cov_term(fn, q13, f1, f3), C22 = cov_term(fn, q22, f2, f2);
+	const float C23 = cov_term(fn, q23, f2, f3), C33 = cov_term(fn, q33, f3, f3);
 	float bestd = C00;
 	float v0 = C00, v1 = C01, v2 = C02, v3 = C03;
 	if (C11 > bestd) { bestd = C11; v0 = C01; v1 = C11; v2 = C12; v3 = C13; }
@@ -1269,27 +1273,46 @@ __device__ __forceinline__ uint32_t geo_src(const FitGeo& g, uint32_t fi, uint32
 	return s & 63u;
 }
 
-// Store a fit (quantised fields, p-bits, weights, error) into fit slot kf of a candidate's column.
+// and / or on a word of LDS with no value returned (ds_and_b32 / ds_or_b32): the lanes of a wave that meet in one word
+// are applied one after the other by the LDS itself.
+__device__ __forceinline__ void cf_lds_and(uint32_t* p, uint32_t v)
+{
+	(void)__hip_atomic_fetch_and(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void cf_lds_or(uint32_t* p, uint32_t v)
+{
+	(void)__hip_atomic_fetch_or(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// Store a fit (quantised fields, weights, error) into fit slot kf of a candidate's column; its p-bits go by
+// column_put_pbits.  The fields a fit owns alone are plain stores.  The four weight words are shared with the
+// candidate's other fits, which may store in the same instruction: there a fit clears and sets the bytes of its own
+// texels by and / or (bc7_packed.h: cf_put_weights), which needs no order between the fits.
 __device__ __forceinline__ void column_put_fit(uint32_t* wc, const FitGeo& g, uint32_t kf, uint32_t q0, uint32_t q1,
-	uint32_t pb, const uint32_t (&w)[4], uint32_t err)
+	const uint32_t (&w)[4], uint32_t err)
 {
 	const uint32_t fq0 = g.planes45 ? (g.sca ? 4u : 0u) : 2u*kf;
 	wc[fq0*CF_WG_THREADS] = q0;
 	wc[(fq0 + 1u)*CF_WG_THREADS] = q1;
 	wc[(15u + kf)*CF_WG_THREADS] = err;
-	if (!g.planes45) {
-		const uint32_t pw = wc[6*CF_WG_THREADS];
-		wc[6*CF_WG_THREADS] = (pw & ~(3u << (2u*kf))) | (pb << (2u*kf));
-	}
 #pragma unroll
 	for (uint32_t rr = 0; rr < 4u; ++rr) {
 		if (g.sca)
 			wc[(11u + rr)*CF_WG_THREADS] = w[rr];
 		else {
-			const uint32_t mb = bytemask4((g.mask >> (4u*rr)) & 15u);
-			wc[(7u + rr)*CF_WG_THREADS] = (wc[(7u + rr)*CF_WG_THREADS] & ~mb) | w[rr];
+			const cf_put_masks wm = cf_put_weights(g.mask, rr, w[rr]);
+			cf_lds_and(&wc[(7u + rr)*CF_WG_THREADS], wm.keep);
+			cf_lds_or(&wc[(7u + rr)*CF_WG_THREADS], wm.set);
 		}
 	}
+}
+
+// The p-bits of fit kf into the p-bit word of the column (word 6, below the candidate's fields): a read-modify-write,
+// so the fits of a candidate take it one at a time (the callers' loops).
+__device__ __forceinline__ void column_put_pbits(uint32_t* wc, uint32_t kf, uint32_t pb)
+{
+	const uint32_t pw = wc[6*CF_WG_THREADS];
+	wc[6*CF_WG_THREADS] = (pw & ~(3u << (2u*kf))) | (pb << (2u*kf));
 }
 
 
@@ -1745,11 +1768,14 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 				uint32_t* wc = cbase + wl2;
 				const uint32_t cur_err = wc[(15u + kf2)*CF_WG_THREADS];
 				const bool win = active2 && skey == ((lf.err << 2) | v2) && lf.err < cur_err && (!g2.m6 || fi2 == 0u);
-				// one fit at a time: the fits of a candidate share the p-bit word and the weight words of its column
+				// every fit at once: the fits of a candidate share the weight words of its column, and each puts its own
+				// bytes there by and / or (column_put_fit); the p-bit word one fit at a time
+				if (win)
+					column_put_fit(wc, g2, kf2, lf.q0, lf.q1, lf.w, lf.err);
 #pragma unroll 1
 				for (uint32_t j = 0; j < 3u; ++j) {
-					if (win && kf2 == j)
-						column_put_fit(wc, g2, kf2, lf.q0, lf.q1, lf.pb, lf.w, lf.err);
+					if (win && !g2.planes45 && kf2 == j)
+						column_put_pbits(wc, kf2, lf.pb);
 					__builtin_amdgcn_wave_barrier();
 				}
 				continue;
@@ -2062,11 +2088,13 @@ __device__ __forceinline__ uint4 encode_blocks(const uint32_t* tile, const uint3
 						fitmin = other < fitmin ? other : fitmin;
 					}
 					const bool win = valid && key == fitmin && f.err < cur_err && (!g.m6 || (L_HL & 1u) == 0u);
-					// one fit at a time: the fits share the p-bit word and the weight words of the column
+					// every fit at once: each puts its own bytes into the weight words of the column; the p-bit word one fit at a time
+					if (win)
+						column_put_fit(wc, g, kf, nq0, nq1, f.w, f.err);
 #pragma unroll 1
 					for (uint32_t j = 0; j < 3u; ++j) {
-						if (win && kf == j)
-							column_put_fit(wc, g, kf, nq0, nq1, npb, f.w, f.err);
+						if (win && !g.planes45 && kf == j)
+							column_put_pbits(wc, kf, npb);
 						__builtin_amdgcn_wave_barrier();
 					}
 					moved = moved || __ballot(win) != 0ull;

@@ -290,4 +290,26 @@ CF_PK uint32_t byte_lohi(uint32_t w)
 	return lo | (hi << 8);
 }
 
+// One covariance term n q_cd - s_c s_d as a float, from floats.  n q <= 16 * 16 * 255^2 and s_c s_d <= 4080^2 are both
+// 16 646 400 < 2^24: the conversions and the product are exact, and the fused result is an integer below 2^24 in
+// magnitude, so it is the float the integer subtraction and its conversion give (+0 where the two are equal).
+CF_PK float cov_term(float fn, uint32_t q, float sc, float sd)
+{
+	return __builtin_fmaf(fn, (float)q, -(sc*sd));
+}
+
+// A fit's bytes in a weight word of a candidate's column, which its fits share, as two masks: `keep` clears the bytes
+// of the fit's texels (and), `set` puts the new ones in (or).  The fits of a candidate own disjoint texels, so the ands
+// and ors of several fits give the same word in any order, each and before its own or, as LDS atomics do for the lanes
+// of one wave.
+struct cf_put_masks { uint32_t keep, set; };
+// rr: the row of the block, w: the fit's weight bytes of that row (zero outside its texels)
+CF_PK cf_put_masks cf_put_weights(uint32_t mask, uint32_t rr, uint32_t w)
+{
+	cf_put_masks m;
+	m.keep = ~(((((mask >> (4u*rr)) & 15u)*0x00204081u) & 0x01010101u)*0xFFu);   // (bytemask4 of the row's four mask bits)
+	m.set = w;
+	return m;
+}
+
 #endif
